@@ -17,6 +17,10 @@ index identical to the reference order).  At N=1 the same batch is then also tim
 kernel (PBD_CONV_MFMA: operands split into two bf16 terms, fp32 accumulation; responses within the
 north-star tolerance of 1e-4) and reported as `fast_mode`, together with a record-by-record comparison of
 its candidates with the exact ones (`agreement`).  `--conv-mode mfma` makes that kernel the timed one.
+
+`--dump-outputs DIR` writes the candidate list the timed path returned in its last timed step (rank 0: the gathered
+list) to DIR/*.npy, so that two builds run with the same arguments -- hence the same seeded inputs -- can be compared
+output for output.
 """
 import argparse
 import ctypes as C
@@ -43,9 +47,37 @@ sys.path.insert(0, ROOT)
 
 # algorithmic work of the convolution kernel per 640x480 frame (SURVEY.md section 8d / DESIGN.md):
 # read features 128*C + filters, write responses 4*F*C; 2*800*F*C flop
-PEAK_F32_TFLOPS = 157.3     # MI355X dense fp32 (vector = f32 MFMA) peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_F32_TFLOPS = 157.3     # MI355X dense fp32 (vector = f32 MFMA) peak
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak
 PEAK_HBM_GBPS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, rec):
+    """--dump-outputs: candidate records (n, stride) int32, laid out as include/pbd.h's pbd_candidate_hdr followed by
+    max_parts x {x, y, w, h}, written field by field as DIR/<name>.npy -- integers as float64 (exact), the score as the
+    float32 it is.  Part slots past a record's nparts carry nothing a caller reads and are written as 0.  When the arrays
+    would exceed DUMP_LIMIT_BYTES, a fixed seeded sample of the records is written, in list order; candidate_rows.npy
+    holds the row numbers of the written records in the whole list.  Returns {name: shape}."""
+    rec = np.ascontiguousarray(rec, dtype=np.int32)
+    n, stride = rec.shape
+    max_parts = (stride - 8) // 4
+    row_bytes = 8 * 6 + 4 + 8 * 4 * max_parts + 8
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        rec = rec[rows]
+    nparts = rec[:, 6]
+    parts = rec[:, 8:8 + 4 * max_parts].reshape(len(rec), max_parts, 4).astype(np.float64)
+    parts[np.arange(max_parts)[None, :] >= nparts[:, None]] = 0.0
+    out = {"candidate_header": rec[:, [0, 1, 2, 3, 4, 6]].astype(np.float64),     # frame, component, level, root_x, root_y, nparts
+           "candidate_score": np.ascontiguousarray(rec[:, 5]).view(np.float32),
+           "candidate_parts": parts,
+           "candidate_rows": rows.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def parse():
@@ -71,7 +103,14 @@ def parse():
                          "overlapped kernels, so the default stays 1")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1 rehearsal of the multi-GPU step: initialise torch.distributed (world size 1) and issue the RCCL all_gather of the device-resident candidate payload every step")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the candidate list of the last timed step to DIR/*.npy (rank 0; at most 64 MB, a seeded sample beyond)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def _spawn_workers(args):
@@ -161,10 +200,13 @@ def main():
     dgather = dgathers[0] if on_device else None
     gathered = [0]
     ncand_last = [0]
+    last_buf = [None]       # N = 1: the record buffer the last collected batch was returned in (reused by its handle)
+    last_rec = [None]       # N > 1, rank 0: the last gathered list
 
     def note(rec):
         if rec is not None:
             gathered[0] = len(rec)
+            last_rec[0] = rec
 
     def run(steps, K=NS):
         """`steps` passes of the hot path over the resident batch, pipelined one batch deep: the host never waits for batch
@@ -195,14 +237,14 @@ def main():
                 for k in range(steps):
                     if k + 1 < steps:
                         det.submit_batch_device(d_frames.data_ptr(), B, rows, cols, cn)
-                    _, ncand_last[0] = det.wait_batch(raw=True)
+                    last_buf[0], ncand_last[0] = det.wait_batch(raw=True)
             else:
                 for s_ in range(steps):
                     if s_ >= K:
-                        _, ncand_last[0] = dets[s_ % K].wait_batch(raw=True)
+                        last_buf[0], ncand_last[0] = dets[s_ % K].wait_batch(raw=True)
                     dets[s_ % K].submit_batch_device(d_frames.data_ptr(), B, rows, cols, cn)
                 for i in range(min(K, steps)):
-                    _, ncand_last[0] = dets[(steps - min(K, steps) + i) % K].wait_batch(raw=True)
+                    last_buf[0], ncand_last[0] = dets[(steps - min(K, steps) + i) % K].wait_batch(raw=True)
 
     def sync():
         for d_ in dets:
@@ -226,6 +268,13 @@ def main():
     run(args.steps)
     sync()
     dt = time.perf_counter() - t0
+    # what the last timed step returned, copied before the profiled steps below reuse the handles' record buffers
+    timed_out = None
+    if args.dump_outputs and rank == 0:
+        if use_dist:
+            timed_out = last_rec[0] if last_rec[0] is not None else np.zeros((0, stride), np.int32)
+        else:
+            timed_out = np.array(last_buf[0][:ncand_last[0] * stride]).reshape(-1, stride)
     prof_timed = det.hd.profile_read() if not args.no_profile else {}
     profiled_steps = 0
     if not args.no_profile:
@@ -477,6 +526,8 @@ def main():
             ("fast_mode" if args.conv_mode == "exact" else "exact_mode"): other_mode, "agreement": agreement,
             "host_input": host_input,
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, timed_out)}
         print(json.dumps(out), flush=True)
     for d_ in dets:
         d_.hd.close()

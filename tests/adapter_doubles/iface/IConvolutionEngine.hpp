@@ -1,4 +1,4 @@
-// Test double, used only where /root/reference/include is absent: the two pure virtuals of the reference's
+// Test double: the two pure virtuals of the reference's
 // IConvolutionEngine that HipConvolutionEngine overrides.  See ../README.md.
 #ifndef PBD_TEST_DOUBLE_ICONVOLUTIONENGINE_HPP_
 #define PBD_TEST_DOUBLE_ICONVOLUTIONENGINE_HPP_

@@ -1,4 +1,4 @@
-// Test double, used only where /root/reference/include is absent: the four pure virtuals of the reference's IFeatures
+// Test double: the four pure virtuals of the reference's IFeatures
 // that HipHOGFeatures overrides.  See ../README.md.
 #ifndef PBD_TEST_DOUBLE_IFEATURES_HPP_
 #define PBD_TEST_DOUBLE_IFEATURES_HPP_

@@ -1,4 +1,4 @@
-// Test double, used only where /root/reference/include is absent: the accessors of the reference's Model that
+// Test double: the accessors of the reference's Model that
 // pbdbind::FlatModel reads.  See ../README.md.
 #ifndef PBD_TEST_DOUBLE_MODEL_HPP_
 #define PBD_TEST_DOUBLE_MODEL_HPP_

@@ -1,4 +1,4 @@
-// Test double, used only where /root/reference/include is absent: the typedefs of the reference's types.hpp that the
+// Test double: the typedefs of the reference's types.hpp that the
 // adapter header names.  See ../README.md.
 #ifndef PBD_TEST_DOUBLE_TYPES_HPP_
 #define PBD_TEST_DOUBLE_TYPES_HPP_
