@@ -3,7 +3,9 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--top N] [--staged] [--stream HANDLES FRAMES]
+//   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
+//            [--stream HANDLES FRAMES]
+//   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -15,13 +17,15 @@
 using namespace pbdhost;
 
 template <typename T>
-static int run(FileStorageModel &model, const Image &im, bool staged, float nms, int top, int stream_k, int stream_n)
+static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n)
 {
     PartsBasedDetector<T> pbd;
+    if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
         // the image stream_n times through a FrameStream of stream_k handles: every result must be the first one's
         FrameStream<T> fs(model, stream_k);
+        if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         std::vector<Candidate> first, cur;
         size_t got = 0;
         bool same = true;
@@ -68,7 +72,8 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         pbd.detect(im, candidates);
     }
     std::printf("Number of candidates: %zu\n", candidates.size());
-    Candidate::sort(candidates);
+    if (dnms >= 0 && !staged) std::printf("After device NMS: %zu\n", candidates.size());   // already sorted (stably) and suppressed
+    else Candidate::sort(candidates);
     if (nms >= 0) {
         Candidate::nonMaximaSuppression(im.rows, im.cols, candidates, nms);
         std::printf("After NMS: %zu\n", candidates.size());
@@ -119,16 +124,17 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--top n] [--staged] [--stream handles frames]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames]\n");
         return -1;
     }
     bool dbl = false, staged = false;
-    float nms = -1.f;
+    float nms = -1.f, dnms = -1.f;
     int top = 1 << 30, stream_k = 0, stream_n = 0;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--device-nms") && i + 1 < argc) dnms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
     }
@@ -139,7 +145,8 @@ int main(int argc, char **argv)
         std::vector<uint8_t> pix;
         Image im;
         if (!readPNM(argv[2], pix, im)) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
-        return dbl ? run<double>(model, im, staged, nms, top, stream_k, stream_n) : run<float>(model, im, staged, nms, top, stream_k, stream_n);
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

@@ -137,6 +137,25 @@ int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst);
  * ranks is the full result.  pbd_pyramid_plan reports 0 x 0 feature maps for the levels of other ranks.  (1, 0..): off. */
 int pbd_set_level_shard(pbd_handle *h, int rank, int world);
 
+/* Per-frame post-processing (opt-in; off on a new handle): what every caller of the reference runs after detect() --
+ * Candidate::sort(candidates) then Candidate::nonMaximaSuppression(im, candidates, overlap) (cells/detect.cpp:237-238,
+ * ros/Node.cpp:192-196; include/Candidate.hpp:91-99,277-304) -- on the device, on the handle's stream, after argmin.  Per frame:
+ *   sort      by score descending; equal scores keep the device order (a stable sort; -0.0 and +0.0 tie)
+ *   suppress  greedily in that order: box = hull of the part rectangles (cv::Rect operator|) & Rect(0, 0, cols, rows);
+ *             skip the candidate when (double)painted_pixels_in_box / box.area() > (double)overlap, else paint box and keep it;
+ *             an empty box (area 0: NaN ratio) is kept and paints nothing
+ * Output: frame by frame (ascending), that frame's kept records in sorted order -- the same records, fewer of them.
+ * Applies to pbd_detect, pbd_detect_typed, pbd_detect_batch, pbd_detect_batch_device, pbd_detect_batch_submit / _wait,
+ * pbd_detect_batch_device_submit, pbd_detect_batch_device_out and pbd_argmin_device_out; NOT to pbd_dp_argmin (that is
+ * DynamicProgram::argmin, which does not suppress).  The stage reads the whole list the handle found (capacity
+ * pbd_config.max_candidates), never the caller-truncated one: when more than max_candidates are found the synchronous calls
+ * return PBD_ERR_CAPACITY with *ncand = 0 and the device-out payload's word 0 is -1; when only the kept records exceed the
+ * caller's capacity the behaviour is that of the unsuppressed list (truncation, PBD_ERR_CAPACITY, word 0 = kept count).
+ * enable = 0: off.  A NaN overlap is PBD_ERR_INVALID; PBD_ERR_STATE while a batch is in flight (the setting is latched at
+ * submit); PBD_ERR_UNSUPPORTED together with level sharding (world > 1), in either order of the two calls: suppression of one
+ * rank's levels is not suppression of the union. */
+int pbd_set_nms(pbd_handle *h, int enable, float overlap);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */

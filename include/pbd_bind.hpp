@@ -240,6 +240,14 @@ inline void dp_min(pbd_handle *h, int nfilters, int ncomponents, const std::vect
         }
 }
 
+// pbd_set_nms: the callers' Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) (cells/detect.cpp:237-238,
+// ros/Node.cpp:192-196) run on the device after every detect of this handle; enable = false: off
+template <class Tr>
+inline void set_nms(pbd_handle *h, bool enable, float overlap)
+{
+    check<Tr>(h, pbd_set_nms(h, enable ? 1 : 0, overlap));
+}
+
 // pbd_candidate records -> the host's Candidates (include/Candidate.hpp:56-80)
 template <class Tr>
 inline void unpack_candidates(pbd_handle *h, const std::vector<int32_t> &buf, int n, std::vector<typename Tr::Candidate> &out)

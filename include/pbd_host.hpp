@@ -515,10 +515,12 @@ class PartsBasedDetector {
     std::string name_;
     pbd_handle *h_;
     int device_;
+    bool nms_;
+    float overlap_;
     PartsBasedDetector(const PartsBasedDetector &);
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
-    explicit PartsBasedDetector(int device = 0) : h_(NULL), device_(device) {}
+    explicit PartsBasedDetector(int device = 0) : h_(NULL), device_(device), nms_(false), overlap_(0.f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -527,7 +529,17 @@ public:
         pbd_destroy(h_);
         h_ = NULL;
         h_ = pbdbind::create<HostTraits<T> >(model, device_, PBD_CONV_EXACT, 1, 1 << 18);
+        if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         name_ = model.name();
+    }
+    // new surface: detect() returns Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of what it
+    // found, computed on the device (pbd_set_nms) -- the callers' post-step, cells/detect.cpp:237-238.  Kept across
+    // distributeModel(); a negative overlap turns it off.
+    void setNonMaximaSuppression(float overlap)
+    {
+        if (h_) pbdbind::set_nms<HostTraits<T> >(h_, overlap >= 0, overlap);
+        nms_ = overlap >= 0;
+        overlap_ = overlap;
     }
     void detect(const Image &im, std::vector<Candidate> &candidates) { detect(im, Image(), candidates); }
     void detect(const Image &im, const Image & /*depth: ignored by the reference too, src/PartsBasedDetector.cpp:91-93*/,
@@ -565,6 +577,11 @@ public:
         }
     }
     ~FrameStream() { for (size_t i = 0; i < h_.size(); ++i) pbd_destroy(h_[i]); }
+    // every handle returns sorted, suppressed lists (PartsBasedDetector::setNonMaximaSuppression); nothing may be pending
+    void setNonMaximaSuppression(float overlap)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_nms<HostTraits<T> >(h_[i], overlap >= 0, overlap);
+    }
     size_t pending() const { return submitted_ - collected_; }
     bool full() const { return pending() >= h_.size(); }        // the handle the next frame would go to still holds a result
     void submit(const Image &im)

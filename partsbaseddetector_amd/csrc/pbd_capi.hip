@@ -239,6 +239,8 @@ struct pbd_handle {
     int cur_frames = 0, cur_cn = 3;
     int cur_depth = kDepth8U;        // image depth of the frames being processed (set by the entry point)
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
+    bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
+    float nms_overlap = 0.f;
     bool have_features = false, have_resp = false, have_dp = false;
     bool feat_c31_zero = false;      // h->feat was written by the HOG kernels (channel 31 = 0), not uploaded by the caller
 
@@ -246,6 +248,8 @@ struct pbd_handle {
     DevBuf frames, pyr, gmag, gori, hist, norm, feat, resp, acc, Ik, rootv, rooti;
     int totmix = 0;                  // (part, mixture) pairs of the model = planes of IxRaw / IyRaw per cell block
     DevBuf tmp, dt, IxRaw, IyRaw, stk, scales_tmp, find_blk;
+    DevBuf post_ws;                  // workspace of the post-processing stage (pbd_kernels_post.hip)
+    DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
 
     // A candidate list on its way out.  The device side is the "payload" the find / walk kernels write: word 0 = roots
     // found, then the records, already in (frame, level, component, y, x) order.  The host side is a pinned mirror: the
@@ -254,8 +258,11 @@ struct pbd_handle {
     // the records; a batch that outgrows the guess costs one more copy.
     struct CandBuf {
         DevBuf payload;
+        DevBuf post;                                      // the suppressed list when `nms` (then the read-back source)
+        bool nms = false;                                 // the stage was on when this list was enqueued
         int32_t *host = nullptr; size_t host_words = 0;
         int copied = 0;                                   // records covered by the enqueued copy
+        const DevBuf &out() const { return nms ? post : payload; }
     } cb;
     int cand_guess = 1024;                                // records the next speculative copy covers (shared by every CandBuf)
 
@@ -1306,6 +1313,32 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     return PBD_OK;
 }
 
+// ---- post-processing (pbd_set_nms): per-frame sort + suppression of the payload d_in (capacity in_cap records, frame-local
+// `frame` fields, nframes frames of rows x cols) into d_out = int32[1 + out_cap * stride]: word 0 = kept count (-1 when more
+// than in_cap candidates were found), then the kept records frame by frame, `frame` + frame_offset.  No host synchronisation.
+int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
+                 int32_t *d_out, int out_cap, hipStream_t st)
+{
+    PostParams pp{};
+    pp.in = d_in; pp.in_cap = std::max(in_cap, 1);
+    pp.stride = 8 + 4 * h->max_parts; pp.max_parts = h->max_parts; pp.nframes = nframes;
+    pp.rows = rows; pp.cols = cols; pp.wpr = (cols + 31) / 32; pp.overlap = overlap;
+    pp.out = d_out; pp.out_cap = std::max(out_cap, 0); pp.frame_offset = frame_offset;
+    // workspace: key, frame, perm, slot [in_cap] | box [in_cap] int4 | fkept [nframes] | global canvases (frames too big for LDS)
+    const size_t n = (size_t)pp.in_cap, a4 = (4 * n * sizeof(int) + 15) & ~(size_t)15;
+    const size_t fk = ((size_t)nframes * sizeof(int) + 15) & ~(size_t)15;
+    const size_t canvas = post_canvas_in_lds(rows, cols) ? 0 : (size_t)nframes * post_canvas_words(rows, cols) * sizeof(uint32_t);
+    HIPCHK(h, h->post_ws.ensure(a4 + n * sizeof(int4) + fk + canvas));
+    char *ws = h->post_ws.as<char>();
+    pp.key = reinterpret_cast<float *>(ws); pp.frame = reinterpret_cast<int *>(ws) + n;
+    pp.perm = reinterpret_cast<int *>(ws) + 2 * n; pp.slot = reinterpret_cast<int *>(ws) + 3 * n;
+    pp.box = reinterpret_cast<int4 *>(ws + a4);
+    pp.fkept = reinterpret_cast<int *>(ws + a4 + n * sizeof(int4));
+    pp.canvas = canvas ? reinterpret_cast<uint32_t *>(ws + a4 + n * sizeof(int4) + fk) : nullptr;
+    launch_postprocess(pp, st);
+    return PBD_OK;
+}
+
 int candbuf_host(pbd_handle *h, pbd_handle::CandBuf &cb, size_t words)
 {
     if (cb.host_words >= words) return PBD_OK;
@@ -1316,18 +1349,27 @@ int candbuf_host(pbd_handle *h, pbd_handle::CandBuf &cb, size_t words)
     return PBD_OK;
 }
 
-// find + walk into cb.payload and the speculative read-back of [count | first records], all on `st`
-int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, hipStream_t st)
+// find + walk into cb.payload (then, with `post`, the sort + suppression into cb.post) and the speculative read-back of
+// [count | first records], all on `st`
+int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, bool post,
+                            hipStream_t st)
 {
     const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
     int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st);
     if (rc != PBD_OK) return rc;
+    cb.nms = post;
+    if (post) {
+        HIPCHK(h, cb.post.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
+        if ((rc = enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, cb.payload.as<int32_t>(), cap, 0, cb.post.as<int32_t>(), cap,
+                               st)) != PBD_OK)
+            return rc;
+    }
     cb.copied = std::min(h->cand_guess, cap);
     const size_t words = 1 + (size_t)cb.copied * stride;
     // the mirror is sized for twice the guess: growing it (hipHostFree + hipHostMalloc) synchronises the device
     if (cb.host_words < words && (rc = candbuf_host(h, cb, 1 + (size_t)std::min(2 * (long long)cb.copied, (long long)cap) * stride)) != PBD_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(cb.host, cb.payload.p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(cb.host, cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     return PBD_OK;
 }
 
@@ -1337,12 +1379,17 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
 {
     const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
     const int found = cb.host[0];
+    if (found < 0) {         // the post-processing stage saw more candidates than the list holds: no suppressed prefix
+        *ncand = 0;
+        return fail(h, PBD_ERR_CAPACITY, "more than max_candidates (%d) candidates were found before non-maxima suppression: "
+                    "raise pbd_config.max_candidates", cap);
+    }
     const int n = std::min(found, cap);
     if (n > cb.copied) {     // more candidates than the speculative copy covered: fetch the list again, whole
         const size_t words = 1 + (size_t)n * stride;
         const int rc = candbuf_host(h, cb, words);
         if (rc != PBD_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(cb.host, cb.payload.p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(cb.host, cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
         cb.copied = n;
     }
@@ -1355,13 +1402,27 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
     return PBD_OK;
 }
 
-int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int32_t *cand, int capacity, int *ncand)
+int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, int32_t *cand, int capacity, int *ncand)
 {
-    const int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, h->stream);
+    const int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, h->stream);
     if (rc != PBD_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return argmin_deliver(h, h->cb, h->stream, cand, capacity, ncand);
+}
+
+// the device-out form: the list straight into the caller's payload, or -- with the post-processing stage on -- the whole list
+// into the handle's own payload (capacity max_candidates: the stage never sees a truncated list), then the kept records into
+// the caller's
+int enqueue_argmin_out(pbd_handle *h, Plan &P, int nframes, int frame_offset, int32_t *d_payload, int capacity)
+{
+    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.d, frame_offset, d_payload, capacity, h->stream);
+    const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
+    HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
+    const int rc = enqueue_argmin(h, P, nframes, P.d_scales.d, 0, h->cb.payload.as<int32_t>(), cap, h->stream);
+    if (rc != PBD_OK) return rc;
+    return enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap, frame_offset, d_payload, capacity,
+                        h->stream);
 }
 
 // enqueues pyramid -> HOG -> convolution -> dynamic program for the batch (no host synchronisation); *plan_out = its plan
@@ -1431,7 +1492,7 @@ int detect_device(pbd_handle *h, int nframes, const void *d_frames, int rows, in
     Plan *P = nullptr;
     const int rc = enqueue_detect(h, nframes, d_frames, rows, cols, cn, &P);
     if (rc != PBD_OK) return rc;
-    return run_argmin(h, *P, nframes, P->d_scales.d, cand, capacity, ncand);
+    return run_argmin(h, *P, nframes, P->d_scales.d, h->nms, cand, capacity, ncand);
 }
 
 int upload_frames(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int cn, size_t stride_bytes)
@@ -1512,6 +1573,50 @@ int pbd_debug_guard_selftest(int kind)
     });
 }
 
+// the post-processing stage of pbd_set_nms on a caller-built record list (tests: exact ties, boxes outside the frame, very
+// long lists): records[n] grouped by ascending frame (frames 0..), each with 1..max_parts parts; out receives min(kept,
+// capacity) records, *nout = that count; PBD_ERR_CAPACITY when more were kept
+int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *records, int n, float overlap, int32_t *out, int capacity,
+                          int *nout)
+{
+    return guarded(h, [&]() -> int {
+        if (!h || !nout || (n > 0 && !records) || (capacity > 0 && !out)) return PBD_ERR_INVALID;
+        *nout = 0;
+        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+        if (rows < 1 || cols < 1 || rows > 65536 || cols > 65536 || n < 0 || capacity < 0 || std::isnan(overlap))
+            return fail(h, PBD_ERR_INVALID, "rows %d, cols %d, n %d, capacity %d", rows, cols, n, capacity);
+        (void)hipSetDevice(h->cfg.device);
+        const int stride = 8 + 4 * h->max_parts;
+        int nframes = 1;
+        for (int i = 0; i < n; ++i) {
+            const int32_t *r = records + (size_t)i * stride;
+            if (r[0] < 0 || (i > 0 && r[0] < records[(size_t)(i - 1) * stride]) || r[6] < 1 || r[6] > h->max_parts)
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d, nparts %d (frames ascending from 0, 1..%d parts)", i, r[0], r[6],
+                            h->max_parts);
+            nframes = r[0] + 1;
+        }
+        if (nframes > 65536) return fail(h, PBD_ERR_INVALID, "%d frames", nframes);
+        const int in_cap = std::max(n, 1);
+        HIPCHK(h, h->dbg_in.ensure(((size_t)in_cap * stride + 1) * sizeof(int32_t)));
+        HIPCHK(h, h->dbg_out.ensure(((size_t)capacity * stride + 1) * sizeof(int32_t)));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(h->dbg_in.p, &n, sizeof(int32_t), hipMemcpyHostToDevice));
+        if (n) HIPCHK(h, hipMemcpy(h->dbg_in.as<int32_t>() + 1, records, (size_t)n * stride * sizeof(int32_t), hipMemcpyHostToDevice));
+        int rc = enqueue_post(h, nframes, rows, cols, overlap, h->dbg_in.as<int32_t>(), in_cap, 0, h->dbg_out.as<int32_t>(), capacity,
+                              h->stream);
+        if (rc != PBD_OK) return rc;
+        HIPCHK(h, hipGetLastError());
+        int kept = 0;
+        HIPCHK(h, hipMemcpyAsync(&kept, h->dbg_out.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int nret = std::min(kept, capacity);
+        if (nret > 0) HIPCHK(h, hipMemcpy(out, h->dbg_out.as<int32_t>() + 1, (size_t)nret * stride * sizeof(int32_t), hipMemcpyDeviceToHost));
+        *nout = nret;
+        if (kept > capacity) return fail(h, PBD_ERR_CAPACITY, "%d records kept, capacity %d", kept, capacity);
+        return PBD_OK;
+    });
+}
+
 const char *pbd_last_error(const pbd_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **out)
@@ -1571,17 +1676,17 @@ void pbd_destroy(pbd_handle *h)
         if (S.cb.host) (void)hipHostFree(S.cb.host);
         if (S.copied) (void)hipEventDestroy(S.copied);
         if (S.done) (void)hipEventDestroy(S.done);
-        S.frames.release(); S.cb.payload.release();
+        S.frames.release(); S.cb.payload.release(); S.cb.post.release();
     }
     if (h->cb.host) (void)hipHostFree(h->cb.host);
-    h->cb.payload.release();
+    h->cb.payload.release(); h->cb.post.release();
     if (h->stream_copy) (void)hipStreamDestroy(h->stream_copy);
     if (h->stream_d2h) (void)hipStreamDestroy(h->stream_d2h);
     for (auto e : h->chunk_events) (void)hipEventDestroy(e);
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     for (DevBuf *b : {&h->frames, &h->pyr, &h->gmag, &h->gori, &h->hist, &h->norm, &h->feat, &h->resp, &h->acc, &h->Ik, &h->rootv,
                       &h->rooti, &h->tmp, &h->dt, &h->IxRaw, &h->IyRaw, &h->stk, &h->find_blk,
-                      &h->scales_tmp})
+                      &h->scales_tmp, &h->post_ws, &h->dbg_in, &h->dbg_out})
         b->release();
     for (auto &c : h->conv_classes) { c.wts.release(); c.fmap.release(); c.wts3.release(); c.unit_f0.release(); c.unit_ql.release(); c.unit_woff.release(); c.c31tab.release(); }
     h->d_wrec.release(); h->d_biasw.release(); h->d_coord.release(); h->d_walk_off.release();
@@ -1611,6 +1716,9 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
         if (!h) return PBD_ERR_INVALID;
         if (world < 1 || rank < 0 || rank >= world) return fail(h, PBD_ERR_INVALID, "level shard %d of %d", rank, world);
         if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+        if (world > 1 && h->nms)
+            return fail(h, PBD_ERR_UNSUPPORTED, "level sharding with non-maxima suppression on: suppression of one rank's levels "
+                        "is not suppression of the union (pbd_set_nms(h, 0, ...) first)");
         if (rank == h->shard_rank && world == h->shard_world) return PBD_OK;
         (void)hipSetDevice(h->cfg.device);
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1620,6 +1728,21 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
         h->cur = nullptr; h->have_features = h->have_resp = h->have_dp = false;
         for (size_t i = 0; i < h->plans.size();)
             if (h->plans[i]->kind == 0) h->plans.erase(h->plans.begin() + i); else ++i;
+        return PBD_OK;
+    });
+}
+
+int pbd_set_nms(pbd_handle *h, int enable, float overlap)
+{
+    return guarded(h, [&]() -> int {
+        if (!h) return PBD_ERR_INVALID;
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+        if (enable && h->shard_world > 1)
+            return fail(h, PBD_ERR_UNSUPPORTED, "non-maxima suppression with level sharding (world %d): suppression of one rank's "
+                        "levels is not suppression of the union", h->shard_world);
+        h->nms = enable != 0;
+        h->nms_overlap = overlap;
         return PBD_OK;
     });
 }
@@ -1847,7 +1970,7 @@ int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacit
         Plan &P = *h->cur;
         HIPCHK(h, h->scales_tmp.ensure(sizeof(float) * PBD_MAX_LEVELS));
         HIPCHK(h, hipMemcpyAsync(h->scales_tmp.p, scales, sizeof(float) * P.nlevels, hipMemcpyHostToDevice, h->stream));
-        return run_argmin(h, P, h->cur_frames, h->scales_tmp.as<float>(), cand, capacity, ncand);
+        return run_argmin(h, P, h->cur_frames, h->scales_tmp.as<float>(), false, cand, capacity, ncand);   // no suppression (DynamicProgram::argmin)
     });
 }
 
@@ -1882,7 +2005,7 @@ static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, int nframes, const
     h->cur_depth = kDepth8U;
     int rc = enqueue_detect(h, nframes, d_frames, rows, cols, channels, &P);
     if (rc != PBD_OK) return rc;
-    if ((rc = enqueue_argmin_readback(h, *P, nframes, P->d_scales.d, S.cb, h->stream)) != PBD_OK) return rc;
+    if ((rc = enqueue_argmin_readback(h, *P, nframes, P->d_scales.d, S.cb, h->nms, h->stream)) != PBD_OK) return rc;
     HIPCHK(h, hipEventRecord(S.done, h->stream));
     HIPCHK(h, hipGetLastError());
     S.plan = P; S.nframes = nframes;
@@ -1965,7 +2088,7 @@ int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames
         Plan *P = nullptr;
         int rc = enqueue_detect(h, nframes, d_frames, rows, cols, channels, &P);
         if (rc != PBD_OK) return rc;
-        if ((rc = enqueue_argmin(h, *P, nframes, P->d_scales.d, frame_offset, d_payload, capacity, h->stream)) != PBD_OK) return rc;
+        if ((rc = enqueue_argmin_out(h, *P, nframes, frame_offset, d_payload, capacity)) != PBD_OK) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
     });
@@ -1979,7 +2102,7 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
         if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
         if (!h->cur || !h->have_dp || h->cur->kind != 0) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        const int rc = enqueue_argmin(h, *h->cur, h->cur_frames, h->cur->d_scales.d, frame_offset, d_payload, capacity, h->stream);
+        const int rc = enqueue_argmin_out(h, *h->cur, h->cur_frames, frame_offset, d_payload, capacity);
         if (rc != PBD_OK) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;

@@ -249,6 +249,20 @@ struct ArgminParams {
     int frame_offset;             // added to the `frame` field of every record (frames sharded over GPUs: global frame id)
 };
 
+// per-frame sort + non-maxima suppression of an argmin payload (pbd_set_nms; pbd_kernels_post.hip)
+struct PostParams {
+    const int32_t *in;            // payload: word 0 = candidates found, then the records grouped by frame (`frame` frame-local)
+    int in_cap;                   // records the input holds; found > in_cap -> output word 0 = -1
+    int stride, max_parts, nframes;
+    int rows, cols, wpr;          // frame size; canvas words per row = ceil(cols / 32)
+    float overlap;
+    // workspace, in_cap entries each (fkept: nframes)
+    float *key; int *frame; int4 *box; int *perm; int *slot; int *fkept;
+    uint32_t *canvas;             // nframes bit canvases of rows * wpr words when they do not fit in LDS
+    int32_t *out; int out_cap;    // output payload: word 0 = kept count, then min(kept, out_cap) records
+    int frame_offset;             // added to the `frame` field of every emitted record
+};
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -292,5 +306,8 @@ void launch_dp_root(const DpParams &p, int nframes, bool f64, hipStream_t s);
 void launch_argmin_find(const ArgminParams &p, bool f64, hipStream_t s);
 int argmin_find_span();       // root cells per block of the find kernels (sizes ArgminParams::blk)
 void launch_argmin_walk(const ArgminParams &p, bool f64, hipStream_t s);
+bool post_canvas_in_lds(int rows, int cols);
+size_t post_canvas_words(int rows, int cols);
+void launch_postprocess(const PostParams &p, hipStream_t s);
 
 }  // namespace pbd

@@ -121,6 +121,15 @@ class Handle:
         """pbd_set_level_shard: this handle computes only its share of the pyramid levels of each frame"""
         self.check(self.lib.pbd_set_level_shard(self.h, rank, world))
 
+    def set_nms(self, overlap: Optional[float]) -> None:
+        """pbd_set_nms: every detect* call of this handle returns, per frame, Candidate.sort + Candidate.nonMaximaSuppression(
+        (rows, cols), candidates, overlap) of what it found, computed on the device (cells/detect.cpp:237-238,
+        ros/Node.cpp:192-196); None: off (the default).  `overlap` crosses the ABI as a float."""
+        if overlap is None:
+            self.check(self.lib.pbd_set_nms(self.h, 0, 0.0))
+        else:
+            self.check(self.lib.pbd_set_nms(self.h, 1, float(overlap)))
+
     # ---- helpers -------------------------------------------------------------------------------
     def plan(self, rows: int, cols: int):
         n = C.c_int()
@@ -280,10 +289,13 @@ class PartsBasedDetector:
     """PartsBasedDetector<float> (include/PartsBasedDetector.hpp:152-175)."""
 
     def __init__(self, device: int = 0, conv_mode: int = _lib.CONV_EXACT, max_batch: int = 1,
-                 max_candidates: int = 1 << 18, stream: Optional[int] = None, dtype=np.float32):
-        """dtype: the reference's template parameter T (float32 as src/demo.cpp:85, float64 as the ECTO/ROS callers)."""
+                 max_candidates: int = 1 << 18, stream: Optional[int] = None, dtype=np.float32, nms: Optional[float] = None):
+        """dtype: the reference's template parameter T (float32 as src/demo.cpp:85, float64 as the ECTO/ROS callers).
+        nms: overlap of the per-frame sort + non-maxima suppression run on the device after every detect (Handle.set_nms;
+        the callers' post-step, 0.1 in cells/detect.cpp:238 -- config.max_overlap); None: the raw candidate list."""
         self._kw = dict(device=device, conv_mode=conv_mode, max_batch=max_batch, max_candidates=max_candidates,
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
+        self._nms = nms
         self.hd: Optional[Handle] = None
         self._name = ""
 
@@ -295,6 +307,8 @@ class PartsBasedDetector:
         if self.hd is not None:
             self.hd.close()
         self.hd = Handle(model, **self._kw)
+        if self._nms is not None:
+            self.hd.set_nms(self._nms)
         self._name = getattr(model, "name", "")
         self.features_ = HOGFeatures(self.hd)
         self.convolution_engine_ = SpatialConvolutionEngine(self.hd)
@@ -410,6 +424,7 @@ class DetectorPool:
     """
 
     def __init__(self, model: Model, n: int = 3, **kw):
+        """kw: PartsBasedDetector's keywords, for every handle (nms=overlap included)"""
         if n < 1:
             raise ValueError("DetectorPool needs at least one detector")
         self.dets: List[PartsBasedDetector] = []
