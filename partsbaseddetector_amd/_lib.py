@@ -19,6 +19,8 @@ STATUS = {0: "PBD_OK", -1: "PBD_ERR_INVALID", -2: "PBD_ERR_UNSUPPORTED", -3: "PB
 REAL_F32, REAL_F64 = 0, 1
 CONV_EXACT, CONV_FMA, CONV_MFMA, CONV_MFMA_F16 = 0, 1, 2, 3
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
+# options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
+DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3
 # cv::Mat::depth() codes of the image depths HOGFeatures::pyramid accepts (src/HOGFeatures.cpp:136-146)
 DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32): 5, np.dtype(np.float64): 6}
 KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows", "k_dt_cols", "k_dp_combine",
@@ -88,6 +90,7 @@ def load():
     lib.pbd_ptr_slot.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_level_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    lib.pbd_debug_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_debug_postprocess.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
                                           C.POINTER(C.c_int)]
     lib.pbd_pyramid_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_float)]

@@ -185,9 +185,7 @@ struct Prof {
 struct pbd_handle {
     pbd_config cfg{};
     std::string err;
-    hipStream_t stream = nullptr;      // pyramid, HOG, convolution (and everything in the staged calls)
-    hipStream_t stream2 = nullptr;     // dynamic program of the previous chunk, overlapped with the convolution
-    std::vector<hipEvent_t> chunk_events;
+    hipStream_t stream = nullptr;      // every kernel of the handle
     bool own_stream = false;
 
     // model (host copies)
@@ -241,6 +239,8 @@ struct pbd_handle {
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;
+    DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)
+    int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
     bool have_features = false, have_resp = false, have_dp = false;
     bool feat_c31_zero = false;      // h->feat was written by the HOG kernels (channel 31 = 0), not uploaded by the caller
 
@@ -1172,11 +1172,9 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
             // (T = double, 5 x 5) leaves ONE workgroup -- one wave per SIMD -- on a CU and the kernel then waits for its own LDS
             // reads: the largest block within 36 KB (four or more workgroups per CU) is taken, restaged per filter group.
             // Measured, one 640x480 frame, T = double: 9.84 ms with 32 channels -> see profiles/README.md.
-            static const int env_cb = getenv("PBD_CONV_CBLOCK") ? atoi(getenv("PBD_CONV_CBLOCK")) : 0;
             const size_t plane = (size_t)(((kConvTH + C.K - 1) * (kConvTW + C.K - 1)) | 1) * h->rs;
             cp.cblock = 32;
-            while (cp.cblock > 1 && cp.cblock * plane > (size_t)36 * 1024) cp.cblock /= 2;
-            if (env_cb > 0 && env_cb <= 32 && (size_t)env_cb * plane <= (size_t)160 * 1024) cp.cblock = env_cb;
+            while (cp.cblock > 1 && cp.cblock * plane > kConvLdsBudget) cp.cblock /= 2;
         }
         cp.wts3 = C.wts3.p;
         cp.unit_f0 = C.unit_f0.d; cp.unit_ql = C.unit_ql.d; cp.unit_woff = C.unit_woff.d; cp.nunits = C.nunits;
@@ -1193,10 +1191,9 @@ int dp_chunk_frames(pbd_handle *h, Plan &P, int want)
 {
     const size_t per_frame = (size_t)P.cell_per_frame * std::max(h->JGmax, 1);
     const size_t stk_per_frame = (size_t)P.stk_per_jf * std::max(h->JGmax, 1);
-    // bytes of scratch per chunk (12 B / cell-job + 16 B / two stack entries); PBD_DP_BUDGET_MB lets the tests
-    // force several chunks on a small batch
-    const char *env_budget = getenv("PBD_DP_BUDGET_MB");
-    const size_t budget = env_budget && atoll(env_budget) > 0 ? (size_t)atoll(env_budget) << 20 : (size_t)8 << 30;
+    // bytes of scratch per chunk (12 B / cell-job + 16 B / two stack entries); a handle's DP_BUDGET_MB debug option lets
+    // the tests force several chunks on a small batch
+    const size_t budget = h->dp_budget_mb > 0 ? (size_t)h->dp_budget_mb << 20 : (size_t)8 << 30;
     int chunk = std::max(want, 1);
     while (chunk > 1 && (per_frame * (6 + 2 * h->rs) + stk_per_frame * (h->f64 ? kStkPairF64 : kStkPairF32)) * chunk > budget) chunk = (chunk + 1) / 2;
     return chunk;
@@ -1243,8 +1240,8 @@ void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
         dp.JG = (int)g.jobs.size();
         dp.jobs = g.d_jobs.d; dp.cjobs = g.d_cjobs.d; dp.childs = g.d_childs.d;
         dp.bz_x = g.bz_x; dp.bz_y = g.bz_y;
-        { ProfScope ps(h, PBD_K_DT_ROWS, st); launch_dt_rows(dp, nb, h->f64, st); }
-        { ProfScope ps(h, PBD_K_DT_COLS, st); launch_dt_cols(dp, nb, h->f64, st); }
+        { ProfScope ps(h, PBD_K_DT_ROWS, st); launch_dt_rows(dp, h->dt_opt, nb, h->f64, st); }
+        { ProfScope ps(h, PBD_K_DT_COLS, st); launch_dt_cols(dp, h->dt_opt, nb, h->f64, st); }
         dp.sjobs = g.d_sjobs.d;
         {
             ProfScope ps(h, PBD_K_DP_COMBINE, st);
@@ -1255,12 +1252,12 @@ void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
     { ProfScope ps(h, PBD_K_DP_ROOT, st); launch_dp_root(dp, nb, h->f64, st); }
 }
 
-// single-stream wrappers used by the staged entry points
-int run_features(pbd_handle *h, Plan &P, int nframes, int cn)
+// the stages over the whole batch on the handle's stream (the dynamic program in chunks of frames within its scratch budget)
+int run_features(pbd_handle *h, Plan &P, const void *d_frames, int nframes, int cn)
 {
     int rc = alloc_features(h, P, nframes, cn);
     if (rc != PBD_OK) return rc;
-    launch_features(h, P, h->frames.p, cn, 0, nframes, h->stream);
+    launch_features(h, P, d_frames, cn, 0, nframes, h->stream);
     HIPCHK(h, hipGetLastError());
     h->have_features = true;
     return PBD_OK;
@@ -1438,48 +1435,9 @@ int enqueue_detect(pbd_handle *h, int nframes, const void *d_frames, int rows, i
     if (rc != PBD_OK) return rc;
     h->cur = P; h->cur_frames = nframes; h->cur_cn = cn;
     h->have_features = h->have_resp = h->have_dp = false;
-    // Software pipeline over chunks of frames: features + convolution of chunk c run on `stream`, the
-    // dynamic program of chunk c-1 on `stream2`.  The convolution is VALU-bound and the distance
-    // transform latency-bound, so the two overlap well; buffers are indexed by frame, so chunks never
-    // alias, and the DP scratch belongs to stream2 alone.
-    // (measured on MI355X: with the convolution holding 127 KB of LDS per CU the DP kernels get too few
-    //  waves to profit, so the pipeline is off unless PBD_PIPELINE_CHUNKS asks for it)
-    static const int env_chunks = getenv("PBD_PIPELINE_CHUNKS") ? atoi(getenv("PBD_PIPELINE_CHUNKS")) : 1;
-    const int want = env_chunks > 1 ? (nframes + env_chunks - 1) / env_chunks : nframes;
-    const int chunk = dp_chunk_frames(h, *P, want);
-    if ((rc = alloc_features(h, *P, nframes, cn)) != PBD_OK) return rc;
-    if ((rc = alloc_conv(h, *P, nframes)) != PBD_OK) return rc;
-    if ((rc = ensure_seg_tiles(h, *P, std::min(chunk, nframes))) != PBD_OK) return rc;
-    if (nframes % chunk && (rc = ensure_seg_tiles(h, *P, nframes % chunk)) != PBD_OK) return rc;
-    if ((rc = alloc_dp(h, *P, nframes, chunk)) != PBD_OK) return rc;
-    const int nchunks = (nframes + chunk - 1) / chunk;
-    while ((int)h->chunk_events.size() < nchunks + 1) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->chunk_events.push_back(e);
-    }
-    const bool two = nchunks > 1 && h->stream2 != nullptr;
-    hipStream_t sdp = two ? h->stream2 : h->stream;
-    if (two) {   // stream2 must not start before earlier work on `stream` (frame upload, previous call)
-        HIPCHK(h, hipEventRecord(h->chunk_events[nchunks], h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->chunk_events[nchunks], 0));
-    }
-    for (int c = 0; c < nchunks; ++c) {
-        const int f0 = c * chunk, nb = std::min(chunk, nframes - f0);
-        launch_features(h, *P, d_frames, cn, f0, nb, h->stream);
-        launch_conv_stage(h, *P, f0, nb, h->stream);
-        if (two) {
-            HIPCHK(h, hipEventRecord(h->chunk_events[c], h->stream));
-            HIPCHK(h, hipStreamWaitEvent(h->stream2, h->chunk_events[c], 0));
-        }
-        launch_dp_chunk(h, *P, f0, nb, sdp);
-    }
-    if (two) {   // join: argmin runs on `stream` after the last DP chunk
-        HIPCHK(h, hipEventRecord(h->chunk_events[nchunks], h->stream2));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, h->chunk_events[nchunks], 0));
-    }
-    HIPCHK(h, hipGetLastError());
-    h->have_features = h->have_resp = h->have_dp = true;
+    if ((rc = run_features(h, *P, d_frames, nframes, cn)) != PBD_OK) return rc;
+    if ((rc = run_conv(h, *P, nframes)) != PBD_OK) return rc;
+    if ((rc = run_dp(h, *P, nframes)) != PBD_OK) return rc;
     *plan_out = P;
     return PBD_OK;
 }
@@ -1617,6 +1575,38 @@ int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *reco
     });
 }
 
+// forces one of the handle's launch choices (tests: every distance-transform variant, DP chunking on small batches);
+// each option's default value restores the automatic choice
+enum { PBD_DEBUG_DT_LANE_SHIFT = 0, PBD_DEBUG_DT_COOP = 1, PBD_DEBUG_DT_COOP_G = 2, PBD_DEBUG_DP_BUDGET_MB = 3 };
+int pbd_debug_set_option(pbd_handle *h, int option, int value)
+{
+    return guarded(h, [&]() -> int {
+        if (!h) return PBD_ERR_INVALID;
+        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+        switch (option) {
+        case PBD_DEBUG_DT_LANE_SHIFT:   // 0..6: 64 >> value rows per wave; -1: automatic
+            if (value < -1 || value > 6) break;
+            h->dt_opt.lane_shift = value;
+            return PBD_OK;
+        case PBD_DEBUG_DT_COOP:         // 0: never the cooperative kernel; 1: when it fits
+            if (value != 0 && value != 1) break;
+            h->dt_opt.coop = value != 0;
+            return PBD_OK;
+        case PBD_DEBUG_DT_COOP_G:       // 4 or 8 rows per wave of the cooperative kernel; 0: automatic
+            if (value != 0 && value != 4 && value != 8) break;
+            h->dt_opt.coop_g = value;
+            return PBD_OK;
+        case PBD_DEBUG_DP_BUDGET_MB:    // DP scratch per chunk of frames in MB; 0: 8 GB
+            if (value < 0) break;
+            h->dp_budget_mb = value;
+            return PBD_OK;
+        default:
+            return fail(h, PBD_ERR_INVALID, "debug option %d unknown", option);
+        }
+        return fail(h, PBD_ERR_INVALID, "debug option %d: value %d out of range", option, value);
+    });
+}
+
 const char *pbd_last_error(const pbd_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **out)
@@ -1649,8 +1639,6 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
             if (e != hipSuccess) return fail(nullptr, PBD_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
             h->own_stream = true;
         }
-        e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
-        if (e != hipSuccess) return fail(nullptr, PBD_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
         int rc = build_model(h.get(), model);
         if (rc != PBD_OK) {
             g_create_error = h->err;
@@ -1667,7 +1655,6 @@ void pbd_destroy(pbd_handle *h)
     try {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     h->prof.release();
     if (h->stream_copy) (void)hipStreamSynchronize(h->stream_copy);
     if (h->stream_d2h) (void)hipStreamSynchronize(h->stream_d2h);
@@ -1682,8 +1669,6 @@ void pbd_destroy(pbd_handle *h)
     h->cb.payload.release(); h->cb.post.release();
     if (h->stream_copy) (void)hipStreamDestroy(h->stream_copy);
     if (h->stream_d2h) (void)hipStreamDestroy(h->stream_d2h);
-    for (auto e : h->chunk_events) (void)hipEventDestroy(e);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
     for (DevBuf *b : {&h->frames, &h->pyr, &h->gmag, &h->gori, &h->hist, &h->norm, &h->feat, &h->resp, &h->acc, &h->Ik, &h->rootv,
                       &h->rooti, &h->tmp, &h->dt, &h->IxRaw, &h->IyRaw, &h->stk, &h->find_blk,
                       &h->scales_tmp, &h->post_ws, &h->dbg_in, &h->dbg_out})
@@ -1722,7 +1707,6 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
         if (rank == h->shard_rank && world == h->shard_world) return PBD_OK;
         (void)hipSetDevice(h->cfg.device);
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
         h->shard_rank = rank; h->shard_world = world;
         // image plans depend on the shard
         h->cur = nullptr; h->have_features = h->have_resp = h->have_dp = false;
@@ -1785,7 +1769,7 @@ int pbd_features_pyramid(pbd_handle *h, const void *img, int rows, int cols, int
         if ((rc = upload_frames(h, 1, &img, rows, cols, channels, stride_bytes)) != PBD_OK) return rc;
         h->cur = P; h->cur_frames = 1; h->cur_cn = channels;
         h->have_features = h->have_resp = h->have_dp = false;
-        if ((rc = run_features(h, *P, 1, channels)) != PBD_OK) return rc;
+        if ((rc = run_features(h, *P, h->frames.p, 1, channels)) != PBD_OK) return rc;
         for (int l = 0; l < P->nlevels; ++l) {
             const LevelDesc &d = P->lv[l];
             const size_t n = (size_t)d.rows * d.cols * 32;
@@ -1823,7 +1807,6 @@ int pbd_conv_set_filters(pbd_handle *h, int nfilters, const void *const *filters
         if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
         (void)hipSetDevice(h->cfg.device);
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
         const int rc = upload_filters(h, nfilters, filters, ksize);
         if (rc != PBD_OK) return rc;
         h->have_resp = h->have_dp = false;   // staged results of the old bank are gone
@@ -2222,7 +2205,6 @@ int pbd_synchronize(pbd_handle *h)
     return guarded(h, [&]() -> int {
         if (!h) return PBD_ERR_INVALID;
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));
         return PBD_OK;
     });
 }

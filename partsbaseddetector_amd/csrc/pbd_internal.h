@@ -119,6 +119,11 @@ constexpr int kWalkMaxParts = 160;   // parts per component the back-tracking wa
 constexpr size_t kStkPairF32 = 16, kStkPairF64 = 32;
 constexpr int kConvTW = 32, kConvTH = 8, kConvQ = 8;
 constexpr int kConvMaxK = 31;        // largest filter side of the generic convolution kernel (the reference has no limit)
+// the generic kernel stages its haloed tile in LDS in blocks of channels that fit this budget (launch_conv_stage); one
+// channel of the widest filter fits, so its dynamic LDS never exceeds the budget
+constexpr size_t kConvLdsBudget = 36 * 1024;
+static_assert((size_t)(((kConvTH + kConvMaxK - 1) * (kConvTW + kConvMaxK - 1)) | 1) * sizeof(double) <= kConvLdsBudget,
+              "one channel of the widest double tile fits the generic kernel's LDS budget");
 #ifndef PBD_CONV3_NW
 #define PBD_CONV3_NW 8
 #endif
@@ -298,8 +303,14 @@ int conv_mfma_occupancy(bool f16);
 // PBD_CONV_MFMA_F16: 80 B fp16 records, one MFMA per product tile
 void launch_conv_mfma(const ConvParams &p, const void *wrec, bool f16, int nframes, hipStream_t s);
 constexpr int kMfmaFilterBlock = 160, kMfmaRecBytes = 144, kMfmaRecBytesF16 = 80;
-void launch_dt_rows(const DpParams &p, int nframes, bool f64, hipStream_t s);
-void launch_dt_cols(const DpParams &p, int nframes, bool f64, hipStream_t s);
+// the distance-transform passes' launch choices a handle may force (pbd_debug_set_option); the defaults decide per launch
+struct DtOptions {
+    int lane_shift = -1;          // 0..6: 64 >> lane_shift rows (columns) per wave; -1: by the launch's size
+    bool coop = true;             // false: never the wavefront-cooperative kernel k_dt_coop
+    int coop_g = 0;               // 4 or 8: rows per wave of k_dt_coop; 0: by the launch's size
+};
+void launch_dt_rows(const DpParams &p, const DtOptions &o, int nframes, bool f64, hipStream_t s);
+void launch_dt_cols(const DpParams &p, const DtOptions &o, int nframes, bool f64, hipStream_t s);
 void launch_dp_combine(const DpParams &p, int ncjobs, int nframes, bool f64, hipStream_t s);
 void launch_dp_combine_seq(const DpParams &p, int nsjobs, int nframes, bool f64, hipStream_t s);
 void launch_dp_root(const DpParams &p, int nframes, bool f64, hipStream_t s);

@@ -470,15 +470,16 @@ int conv_occupancy(int nw)
 template <typename R, bool FMA>
 static void launch_generic(const ConvParams &p, dim3 grid, hipStream_t s)
 {
+    static const bool lds_limit_set = [] {   // once: the largest block launch_conv_stage picks, whatever the handle
+        for (const void *k : {reinterpret_cast<const void *>(k_conv_generic<R, FMA, 5>), reinterpret_cast<const void *>(k_conv_generic<R, FMA, 0>)})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLdsBudget);
+        return true;
+    }();
+    (void)lds_limit_set;
     const int PW = kConvTW + p.ksize - 1, PH = kConvTH + p.ksize - 1;
     const size_t lds = (size_t)p.cblock * ((PH * PW) | 1) * sizeof(R);
-    if (p.ksize == 5) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_generic<R, FMA, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        PBD_LAUNCH((k_conv_generic<R, FMA, 5>), grid, dim3(256), lds, s, p);
-        return;
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_generic<R, FMA, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    PBD_LAUNCH((k_conv_generic<R, FMA, 0>), grid, dim3(256), lds, s, p);
+    if (p.ksize == 5) PBD_LAUNCH((k_conv_generic<R, FMA, 5>), grid, dim3(256), lds, s, p);
+    else PBD_LAUNCH((k_conv_generic<R, FMA, 0>), grid, dim3(256), lds, s, p);
 }
 
 template <bool FMA, int NW>

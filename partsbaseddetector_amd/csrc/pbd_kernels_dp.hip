@@ -346,26 +346,25 @@ __global__ __launch_bounds__(64 * kDtWaves) void k_dt_rows(DpParams p)
 }
 
 // Rows (columns) per wave of a pass: 64 when the launch fills the chip (1024 SIMDs), else 32 .. 1 -- see k_dt_rows.
-static int dt_lane_shift(long long waves64)
+static int dt_lane_shift(const DtOptions &o, long long waves64)
 {
-    static const int forced = getenv("PBD_DT_LANESHIFT") ? atoi(getenv("PBD_DT_LANESHIFT")) : -1;
-    if (forced >= 0 && forced <= 6) return forced;
+    if (o.lane_shift >= 0) return o.lane_shift;
     int sh = 0;
     while (sh < 6 && (waves64 << (sh + 1)) <= 6144) ++sh;       // at most one round of waves (six per SIMD)
     return sh;
 }
 
-template <bool COLS> static void launch_dt_coop(const DpParams &p, int nframes, int nflat, bool bz, hipStream_t s);
-static bool dt_coop_enabled(int longest);
+template <bool COLS> static void launch_dt_coop(const DpParams &p, int coop_g, int nframes, int nflat, bool bz, hipStream_t s);
+static bool dt_coop_fits(int longest);
 static int dt_coop_min_shift();
 
-void launch_dt_rows(const DpParams &p0, int nframes, bool f64, hipStream_t s)
+void launch_dt_rows(const DpParams &p0, const DtOptions &o, int nframes, bool f64, hipStream_t s)
 {
     if (p0.JG == 0 || p0.nrows_flat == 0) return;
     const int nwv = (p0.nrows_flat + 63) / 64;
     DpParams p = p0;
-    p.lane_shift = dt_lane_shift((long long)p.JG * nframes * nwv);
-    if (p.lane_shift >= dt_coop_min_shift() && !f64 && !p.resp_half && p.ptr8 && dt_coop_enabled(p.longest)) { launch_dt_coop<false>(p, nframes, p.nrows_flat, p.bz_x != 0, s); return; }
+    p.lane_shift = dt_lane_shift(o, (long long)p.JG * nframes * nwv);
+    if (o.coop && p.lane_shift >= dt_coop_min_shift() && !f64 && !p.resp_half && p.ptr8 && dt_coop_fits(p.longest)) { launch_dt_coop<false>(p, o.coop_g, nframes, p.nrows_flat, p.bz_x != 0, s); return; }
     dim3 grid(p.JG, nframes, nwv << p.lane_shift);
 #define PBD_ROWS(PT, BZ)                                                                                              \
     do {                                                                                                              \
@@ -435,13 +434,13 @@ void k_dt_cols(DpParams p)
     dt_stream<R, false, BZ, kDtCHC, EPW, NARROW>(H, job.ay, job.by, job.osy, ring, load, store, noaux);
 }
 
-void launch_dt_cols(const DpParams &p0, int nframes, bool f64, hipStream_t s)
+void launch_dt_cols(const DpParams &p0, const DtOptions &o, int nframes, bool f64, hipStream_t s)
 {
     if (p0.JG == 0 || p0.ncols_flat == 0) return;
     const int nwv = (p0.ncols_flat + 63) / 64;
     DpParams p = p0;
-    p.lane_shift = dt_lane_shift((long long)p.JG * nframes * nwv);
-    if (p.lane_shift >= dt_coop_min_shift() && !f64 && p.ptr8 && dt_coop_enabled(p.longest)) { launch_dt_coop<true>(p, nframes, p.ncols_flat, p.bz_y != 0, s); return; }
+    p.lane_shift = dt_lane_shift(o, (long long)p.JG * nframes * nwv);
+    if (o.coop && p.lane_shift >= dt_coop_min_shift() && !f64 && p.ptr8 && dt_coop_fits(p.longest)) { launch_dt_coop<true>(p, o.coop_g, nframes, p.ncols_flat, p.bz_y != 0, s); return; }
     dim3 grid(p.JG, nframes, nwv << p.lane_shift);
 #define PBD_COLS(PT, BZ)                                                                                   \
     do {                                                                                                   \
@@ -562,12 +561,11 @@ __global__ __launch_bounds__(64) void k_dt_coop(DpParams p)
 // launches that would run with 8 or fewer rows per wave go to the cooperative kernel (measured, one 640x480 frame: from 4 rows
 // per wave on 2.49 ms, from 8 on 2.37, from 16 on 2.43; a 1080p frame gets slower from 16 on: more waves than the chip holds)
 static int dt_coop_min_shift() { return 3; }
-static bool dt_coop_enabled(int longest)
+static bool dt_coop_fits(int longest)
 {
-    static const int v = getenv("PBD_DT_COOP") ? atoi(getenv("PBD_DT_COOP")) : 1;
     // the envelopes of a wave's rows live in LDS (12 bytes per element): beyond 12 KB per wave too few waves fit a CU (a
     // 1080p frame with four rows per wave: 23 KB, and its single-frame rate fell from 83 to 69 detections/s)
-    return v != 0 && (size_t)4 * 3 * longest * sizeof(float) <= (size_t)12 * 1024;
+    return (size_t)4 * 3 * longest * sizeof(float) <= (size_t)12 * 1024;
 }
 
 template <bool COLS, int G>
@@ -575,17 +573,16 @@ static void launch_dt_coop_g(const DpParams &p, int nframes, int nflat, bool bz,
 {
     dim3 grid(p.JG, nframes, (nflat + G - 1) / G);
     const unsigned lds = (unsigned)((size_t)G * 3 * p.longest * sizeof(float));
-    // (rows of at most 256 elements: the position planes are uint8 -- dt_coop_enabled)
+    // (rows of at most 256 elements: the position planes are uint8 -- dt_coop_fits)
     if (bz) PBD_LAUNCH((k_dt_coop<true, uint8_t, COLS, G>), grid, dim3(64), lds, s, p);
     else PBD_LAUNCH((k_dt_coop<false, uint8_t, COLS, G>), grid, dim3(64), lds, s, p);
 }
 template <bool COLS>
-static void launch_dt_coop(const DpParams &p, int nframes, int nflat, bool bz, hipStream_t s)
+static void launch_dt_coop(const DpParams &p, int coop_g, int nframes, int nflat, bool bz, hipStream_t s)
 {
-    // four rows per wave while that stays within one round of waves, else eight
-    static const int forced = getenv("PBD_DT_COOP_G") ? atoi(getenv("PBD_DT_COOP_G")) : 0;
+    // four rows per wave while that stays within one round of waves, else eight (coop_g: forced)
     const long long waves4 = (long long)p.JG * nframes * ((nflat + 3) / 4);
-    const bool g8 = forced ? forced == 8 : (waves4 > 6144 && (size_t)8 * 3 * p.longest * sizeof(float) <= (size_t)12 * 1024);
+    const bool g8 = coop_g ? coop_g == 8 : (waves4 > 6144 && (size_t)8 * 3 * p.longest * sizeof(float) <= (size_t)12 * 1024);
     if (g8) launch_dt_coop_g<COLS, 8>(p, nframes, nflat, bz, s);
     else launch_dt_coop_g<COLS, 4>(p, nframes, nflat, bz, s);
 }

@@ -800,8 +800,7 @@ __global__ __launch_bounds__(TBX * TBY) void k_hog_tile(HogParams p)
 
 void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s)
 {
-    static const bool two_pass = getenv("PBD_HOG_TWO_PASS") != nullptr;     // A/B switch: the unfused kernels
-    if (!f64 && p.depth == kDepth8U && p.cn == 3 && (p.sbin == 4 || p.sbin == 8) && !two_pass) {
+    if (!f64 && p.depth == kDepth8U && p.cn == 3 && (p.sbin == 4 || p.sbin == 8)) {
         if (p.nhtiles == 0) return;
         dim3 grid((unsigned)p.nhtiles, nframes);
         if (p.sbin == 4) PBD_LAUNCH((k_hog_tile<4, kHogTBX, 16>), grid, dim3(kHogTBX * 16), 0, s, p);

@@ -206,8 +206,13 @@ void launch_postprocess(const PostParams &p, hipStream_t s)
     PBD_LAUNCH(k_post_prep, dim3(rblocks), dim3(kPostThreads), 0, s, p);
     PBD_LAUNCH(k_post_rank, dim3(rblocks), dim3(kPostThreads), 0, s, p);
     if (post_canvas_in_lds(p.rows, p.cols)) {
+        static const bool lds_limit_set = [] {   // once: the largest canvas held in LDS
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_post_nms<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kPostLdsCanvasMax);
+            return true;
+        }();
+        (void)lds_limit_set;
         const unsigned lds = (unsigned)std::max<size_t>(post_canvas_words(p.rows, p.cols) * sizeof(uint32_t), 16);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_post_nms<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         PBD_LAUNCH(k_post_nms<true>, dim3(p.nframes), dim3(post_nms_threads<true>()), lds, s, p);
     } else {
         PBD_LAUNCH(k_post_nms<false>, dim3(p.nframes), dim3(post_nms_threads<false>()), 0, s, p);

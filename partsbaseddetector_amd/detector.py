@@ -130,6 +130,13 @@ class Handle:
         else:
             self.check(self.lib.pbd_set_nms(self.h, 1, float(overlap)))
 
+    def set_debug_option(self, option: int, value: int) -> None:
+        """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
+        one.  _lib.DT_LANE_SHIFT: 0..6, 64 >> value rows per wave of the distance transform (-1); _lib.DT_COOP: 0, never
+        its cooperative kernel (1); _lib.DT_COOP_G: 4 or 8 rows per wave of that kernel (0); _lib.DP_BUDGET_MB: > 0, the
+        dynamic program's scratch per chunk of frames (0: 8 GB)."""
+        self.check(self.lib.pbd_debug_set_option(self.h, option, value))
+
     # ---- helpers -------------------------------------------------------------------------------
     def plan(self, rows: int, cols: int):
         n = C.c_int()

@@ -38,7 +38,7 @@ def vga_batch():
     return np.stack([synth.synthetic_frame(i + 1, ROWS, COLS, 3) for i in range(B)])      # the bench's frames (rank 0)
 
 
-def test_config2_batch_of_64_vga_frames(oracle, vga_batch, monkeypatch):
+def test_config2_batch_of_64_vga_frames(oracle, vga_batch):
     import torch
     from partsbaseddetector_amd import detector, _lib
     model = M.synthetic_person_model()
@@ -50,12 +50,10 @@ def test_config2_batch_of_64_vga_frames(oracle, vga_batch, monkeypatch):
 
     def run(budget_mb):
         # budget_mb forces the dynamic program into chunks of 16 frames (None: the default budget, one chunk)
-        if budget_mb is None:
-            monkeypatch.delenv("PBD_DP_BUDGET_MB", raising=False)
-        else:
-            monkeypatch.setenv("PBD_DP_BUDGET_MB", str(budget_mb))
         det = detector.PartsBasedDetector(device=0, max_batch=B, max_candidates=1 << 16)
         det.distributeModel(model)
+        if budget_mb is not None:
+            det.hd.set_debug_option(_lib.DP_BUDGET_MB, budget_mb)
         d_frames = torch.from_numpy(vga_batch).cuda()
         dev = det.detect_batch_device(d_frames.data_ptr(), B, ROWS, COLS, 3)
         for i in check:
@@ -85,15 +83,15 @@ def test_config2_batch_of_64_vga_frames(oracle, vga_batch, monkeypatch):
     assert n1 == n2
 
 
-def test_f64_batch_with_several_dp_chunks(oracle, monkeypatch):
+def test_f64_batch_with_several_dp_chunks(oracle):
     """PBD_REAL_F64 with a budget that forces dp_chunk_frames < nframes: 6 frames 240x320, chunks of 2."""
-    from partsbaseddetector_amd import detector
-    monkeypatch.setenv("PBD_DP_BUDGET_MB", "60")
+    from partsbaseddetector_amd import detector, _lib
     model = M.synthetic_person_model(thresh=18.0)
     flat = model.flatten()
     frames = [synth.synthetic_frame(40 + i, 240, 320, 3) for i in range(6)]
     det = detector.PartsBasedDetector(device=0, max_batch=6, dtype=np.float64)
     det.distributeModel(model)
+    det.hd.set_debug_option(_lib.DP_BUDGET_MB, 60)
     got = det.detect_batch(frames)
     total = 0
     for i, f in enumerate(frames):

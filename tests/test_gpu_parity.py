@@ -228,6 +228,20 @@ def test_errors(det_mod):
     with pytest.raises(PbdError) as e:
         det.detect(synth.synthetic_frame(1, 100, 100), capacity=1)   # capacity overflow is reported
     assert e.value.code == -4
+    # the debug options: an unknown option or a value out of range is refused, not taken as "automatic"
+    from partsbaseddetector_amd import _lib
+    for option, value in ((99, 0), (-1, 0), (_lib.DT_LANE_SHIFT, 7), (_lib.DT_LANE_SHIFT, -2), (_lib.DT_COOP, 2),
+                          (_lib.DT_COOP_G, 6), (_lib.DT_COOP_G, 16), (_lib.DP_BUDGET_MB, -1)):
+        with pytest.raises(PbdError) as e:
+            det.hd.set_debug_option(option, value)
+        assert e.value.code == -1, (option, value)
+    det.submit_batch([synth.synthetic_frame(1, 100, 100)])
+    with pytest.raises(PbdError) as e:
+        det.hd.set_debug_option(_lib.DT_COOP, 0)              # a batch is in flight
+    assert e.value.code == -5
+    det.wait_batch()
+    for option, value in ((_lib.DT_LANE_SHIFT, -1), (_lib.DT_COOP, 1), (_lib.DT_COOP_G, 0), (_lib.DP_BUDGET_MB, 0)):
+        det.hd.set_debug_option(option, value)                 # the defaults are accepted
     det.hd.close()
 
 
@@ -848,51 +862,36 @@ def test_fused_path_responses_every_level(det_mod, oracle):
 def test_narrow_wave_distance_transform(det_mod, oracle):
     """Launches of the distance-transform passes that do not fill the chip run as more, narrower waves (64 >> lane_shift rows
     per wave, chosen per launch: pbd_kernels_dp.hip, dt_lane_shift).  The rows' arithmetic is untouched, so every setting must
-    give the oracle's candidates: each of 64 / 32 / 16 / 8 / 4 / 2 / 1 rows per wave is forced in a fresh interpreter
-    (PBD_DT_LANESHIFT is read once per process) on a frame with rows of up to 78 cells and int16-free uint8 planes, and once
-    on a frame wide enough for int16 planes."""
-    import hashlib, json, os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = (
-        "import sys, json, hashlib, numpy as np; sys.path.insert(0, %r)\n"
-        "from partsbaseddetector_amd import detector, synth, model as M\n"
-        "out = {}\n"
-        "for name, shape, sbin in (('u8', (150, 330), 4), ('i16', (60, 1100), 4)):\n"
-        "    model = M.synthetic_model(seed=31, pa=[0, 1, 1, 2, 2, 3], nmix=3, sbin=sbin, interval=4, thresh=-0.35, linear_def=(name == 'i16'), name='narrow')\n"
-        "    det = detector.PartsBasedDetector(device=0)\n"
-        "    det.distributeModel(model)\n"
-        "    cands = det.detect(synth.synthetic_frame(47, shape[0], shape[1], 3))\n"
-        "    h = hashlib.sha256()\n"
-        "    for c in cands:\n"
-        "        h.update(np.asarray([c.level, c.component, c.root[0], c.root[1]], np.int32).tobytes()); h.update(np.float32(c.score()).tobytes()); h.update(np.ascontiguousarray(c.parts, dtype=np.int32).tobytes())\n"
-        "    out[name] = [len(cands), h.hexdigest()]\n"
-        "    det.hd.close()\n"
-        "print(json.dumps(out))\n" % root)
-    results = {}
+    give the oracle's candidates: each of 64 / 32 / 16 / 8 / 4 / 2 / 1 rows per wave is forced on fresh handles
+    (Handle.set_debug_option) on two frames with rows of up to 78 cells and int16-free uint8 planes -- one without and one
+    with linear deformation terms, the two instantiations of the cooperative kernel -- and on a frame wide enough for int16
+    planes."""
+    from partsbaseddetector_amd import _lib
+    frames = (("u8", (150, 330), False), ("u8_linear", (150, 330), True), ("i16", (60, 1100), True))
+
+    def model(linear):
+        return M.synthetic_model(seed=31, pa=[0, 1, 1, 2, 2, 3], nmix=3, sbin=4, interval=4, thresh=-0.35, linear_def=linear,
+                                 name="narrow")
+
+    want = {name: oracle.detect(model(linear).flatten(), synth.synthetic_frame(47, shape[0], shape[1], 3))
+            for name, shape, linear in frames}
+    assert all(len(w) > 10 for w in want.values()), {k: len(w) for k, w in want.items()}
     # launches with eight or fewer rows per wave (lane_shift >= 3) go to the wavefront-cooperative kernel k_dt_coop (four rows
-    # per wave, sixteen lanes each holding the envelope's top block) unless PBD_DT_COOP=0: both forms are forced
-    for shift, coop in [("auto", None), ("0", None), ("1", None), ("2", None), ("3", None), ("4", None), ("5", None), ("6", None),
-                        ("3", "0"), ("4", "0"), ("6", "0"), ("4", "g8")]:
-        env = dict(os.environ)
-        for k_ in ("PBD_DT_LANESHIFT", "PBD_DT_COOP", "PBD_DT_COOP_G"):
-            env.pop(k_, None)
-        if shift != "auto":
-            env["PBD_DT_LANESHIFT"] = shift
-        if coop == "g8":
-            env["PBD_DT_COOP_G"] = "8"                  # eight rows per wave (windows of eight entries)
-        elif coop is not None:
-            env["PBD_DT_COOP"] = coop
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0, r.stderr[-2000:]
-        results[shift + ("" if coop is None else "/coop" + coop)] = json.loads(r.stdout.strip().splitlines()[-1])
-    assert all(v == results["0"] for v in results.values()), results
-    assert results["0"]["u8"][0] > 10 and results["0"]["i16"][0] > 10
-    # and the 64-rows-per-wave result is the oracle's
-    for name, shape in (("u8", (150, 330)), ("i16", (60, 1100))):
-        model = M.synthetic_model(seed=31, pa=[0, 1, 1, 2, 2, 3], nmix=3, sbin=4, interval=4, thresh=-0.35, linear_def=(name == "i16"), name="narrow")
-        want = oracle.detect(model.flatten(), synth.synthetic_frame(47, shape[0], shape[1], 3))
-        h = hashlib.sha256()
-        for w in want:
-            h.update(np.asarray([w["level"], w["component"], w["root_x"], w["root_y"]], np.int32).tobytes()); h.update(np.float32(w["score"]).tobytes())
-            h.update(np.ascontiguousarray(w["parts"], dtype=np.int32).tobytes())
-        assert [len(want), h.hexdigest()] == results["0"][name], (name, len(want), results["0"][name])
+    # per wave, sixteen lanes each holding the envelope's top block) unless DT_COOP is 0: both forms are forced
+    settings = {"auto": {}}
+    settings.update({str(shift): {_lib.DT_LANE_SHIFT: shift} for shift in range(7)})
+    settings.update({f"{shift}/coop0": {_lib.DT_LANE_SHIFT: shift, _lib.DT_COOP: 0} for shift in (3, 4, 6)})
+    settings["4/g8"] = {_lib.DT_LANE_SHIFT: 4, _lib.DT_COOP_G: 8}          # eight rows per wave (windows of eight entries)
+    assert len(settings) == 12
+    for setting, options in settings.items():
+        for name, shape, linear in frames:
+            det = det_mod.PartsBasedDetector(device=0)
+            det.distributeModel(model(linear))
+            for option, value in options.items():
+                det.hd.set_debug_option(option, value)
+            got = det.detect(synth.synthetic_frame(47, shape[0], shape[1], 3))
+            assert len(got) == len(want[name]), (setting, name, len(got), len(want[name]))
+            _compare_candidates(got, want[name])
+            assert np.array_equal(np.float32([g.score() for g in got]).view(np.uint32),
+                                  np.float32([w["score"] for w in want[name]]).view(np.uint32)), (setting, name)   # signed zeros too
+            det.hd.close()
