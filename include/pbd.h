@@ -228,7 +228,10 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
 /* the hipStream_t every kernel of this handle runs on (pbd_config.stream, or the library's own) */
 void *pbd_stream(const pbd_handle *h);
 
-/* ---- staged read-back of the last pbd_detect* call (tests, profiling) ---- */
+/* ---- staged read-back of the last pbd_detect* call (tests, profiling) ----
+ * A stage is readable only if the last computation produced it: after pbd_conv_set_filters the responses and DP
+ * results are gone, and after pbd_dp_min (which starts from uploaded responses) PBD_STAGE_FEATURES is PBD_ERR_STATE.
+ * A refused call leaves the previous result readable. */
 enum { PBD_STAGE_FEATURES = 0, PBD_STAGE_RESPONSES = 1, PBD_STAGE_ROOTV = 2, PBD_STAGE_ROOTI = 3 };
 int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, size_t dst_bytes);
 

@@ -20,6 +20,8 @@
 #include <new>
 #include <set>
 #include <stdexcept>
+#include <type_traits>
+#include <utility>
 
 using namespace pbd;
 
@@ -31,36 +33,71 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
+// Move-only owner of one HIP resource: device memory (Free = hipFree), pinned host memory (hipHostFree), an event or a
+// stream.  `size` is the bytes or elements held (memory only).  The destructor frees the resource and ignores HIP errors:
+// nothing is left to report them to.
+template <typename T, auto Free>
+struct Owned {
+    T *p = nullptr;
+    size_t size = 0;
+    Owned() = default;
+    Owned(Owned &&o) noexcept { swap(o); }
+    Owned &operator=(Owned o) noexcept { swap(o); return *this; }   // `o` takes the old resource away and frees it
+    ~Owned() { if (p) (void)Free(p); }
+    void swap(Owned &o) noexcept { std::swap(p, o.p); std::swap(size, o.size); }
+};
+using Event = Owned<std::remove_pointer_t<hipEvent_t>, hipEventDestroy>;
+
+struct DevBuf : Owned<void, hipFree> {   // grow-only device workspace; growing does not keep the contents
     hipError_t ensure(size_t bytes)
     {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+        if (bytes <= size) return hipSuccess;
+        *this = DevBuf{};
+        const size_t want = bytes + bytes / 8 + 256;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) size = want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+struct HostBuf : Owned<void, hipHostFree> {   // grow-only pinned host memory: below `bytes`, reallocated to `want`
+    hipError_t ensure(size_t bytes, size_t want)
+    {
+        if (bytes <= size) return hipSuccess;
+        *this = HostBuf{};
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) size = want;
+        return e;
+    }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
 };
 
 template <typename T>
-struct DevTable {   // small immutable table uploaded once
-    T *d = nullptr;
-    size_t n = 0;
+struct DevTable : Owned<T, hipFree> {   // small immutable table uploaded once; `size` elements
     hipError_t upload(const std::vector<T> &h)
     {
-        release();
-        n = h.size();
-        if (n == 0) return hipSuccess;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(T));
+        *this = DevTable{};
+        if (h.empty()) return hipSuccess;
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&this->p), h.size() * sizeof(T));
         if (e != hipSuccess) return e;
-        return hipMemcpy(d, h.data(), n * sizeof(T), hipMemcpyHostToDevice);
+        this->size = h.size();
+        return hipMemcpy(this->p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
     }
-    void release() { if (d) (void)hipFree(d); d = nullptr; n = 0; }
+};
+
+// A stream created here (and destroyed with its owner), or one borrowed from the caller (pbd_config.stream)
+struct Stream {
+    Owned<std::remove_pointer_t<hipStream_t>, hipStreamDestroy> own;   // null when borrowed
+    hipStream_t s = nullptr;
+    hipError_t create()
+    {
+        const hipError_t e = hipStreamCreateWithFlags(&own.p, hipStreamNonBlocking);
+        s = own.p;
+        return e;
+    }
+    void borrow(hipStream_t b) { s = b; }
+    operator hipStream_t() const { return s; }
 };
 
 // ---- pyramid geometry (host) -------------------------------------------------------------------
@@ -127,15 +164,6 @@ struct Plan {
     DevTable<long long> d_stk_row_off, d_stk_col_off;
     long long stk_per_jf = 0;
     DevTable<float> d_scales;
-    void release()
-    {
-        d_lv.release(); d_tabx.release(); d_taby.release(); d_tabxf.release(); d_tabyf.release(); d_tiles.release(); d_shaped.release(); d_htiles.release();
-        for (auto &kv : segtiles) kv.second.release();
-        segtiles.clear();
-        d_row2level.release(); d_rowoff.release(); d_col2level.release(); d_coloff.release(); d_scales.release();
-        d_stk_row_off.release(); d_stk_col_off.release();
-    }
-    ~Plan() { release(); }
 };
 
 struct Group {   // DT jobs of the parts of one tree depth + combine jobs of their parents
@@ -152,32 +180,40 @@ struct Group {   // DT jobs of the parts of one tree depth + combine jobs of the
 
 struct Prof {
     int on = 0;                      // 0: off, 1: every kernel, 2: the convolution only (pbd_profile_enable)
-    struct Rec { int k; hipEvent_t a, b; };
+    struct Rec { int k; Event a, b; };
     std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     double total[PBD_K_COUNT] = {0};
     int launches[PBD_K_COUNT] = {0};
-    hipEvent_t get()
+    Event get()
     {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e; (void)hipEventCreate(&e); return e;
+        Event e;
+        if (pool.empty()) { (void)hipEventCreate(&e.p); return e; }
+        e = std::move(pool.back());
+        pool.pop_back();
+        return e;
     }
     void flush()
     {
         for (auto &r : recs) {
-            (void)hipEventSynchronize(r.b);
+            (void)hipEventSynchronize(r.b.p);
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) { total[r.k] += ms; launches[r.k] += 1; }
-            pool.push_back(r.a); pool.push_back(r.b);
+            if (hipEventElapsedTime(&ms, r.a.p, r.b.p) == hipSuccess) { total[r.k] += ms; launches[r.k] += 1; }
+            pool.push_back(std::move(r.a)); pool.push_back(std::move(r.b));
         }
         recs.clear();
     }
-    void release()
-    {
-        flush();
-        for (auto e : pool) (void)hipEventDestroy(e);
-        pool.clear();
-    }
+};
+
+// What the last computation left on the device, for the entry points that read it back.  An entry point replaces the
+// record where it starts enqueueing (after every check), so a refused call leaves the previous result readable.
+struct Resident {
+    Plan *plan = nullptr;
+    int frames = 0, cn = 3, depth = kDepth8U;   // frames, channels and image depth of the pyramid
+    bool features = false, resp = false, dp = false;   // the stages held, all for `plan`
+    bool c31_zero = false;           // the features were written by the HOG kernels (channel 31 = 0), not uploaded by the caller
+    void drop_conv() { resp = dp = false; }   // the filter bank changed
+    void clear() { *this = Resident{}; }
 };
 
 }  // namespace
@@ -185,8 +221,7 @@ struct Prof {
 struct pbd_handle {
     pbd_config cfg{};
     std::string err;
-    hipStream_t stream = nullptr;      // every kernel of the handle
-    bool own_stream = false;
+    Stream stream;                   // every kernel of the handle
 
     // model (host copies)
     int NC = 0, F = 0, flen = 32, sbin = 4, interval = 10, norient = 18, NS = 0, NM = 0, max_parts = 0;
@@ -233,16 +268,12 @@ struct pbd_handle {
 
     // plans
     std::vector<std::unique_ptr<Plan>> plans;
-    Plan *cur = nullptr;
-    int cur_frames = 0, cur_cn = 3;
-    int cur_depth = kDepth8U;        // image depth of the frames being processed (set by the entry point)
+    Resident res;
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;
     DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)
     int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
-    bool have_features = false, have_resp = false, have_dp = false;
-    bool feat_c31_zero = false;      // h->feat was written by the HOG kernels (channel 31 = 0), not uploaded by the caller
 
     // workspace
     DevBuf frames, pyr, gmag, gori, hist, norm, feat, resp, acc, Ik, rootv, rooti;
@@ -260,22 +291,22 @@ struct pbd_handle {
         DevBuf payload;
         DevBuf post;                                      // the suppressed list when `nms` (then the read-back source)
         bool nms = false;                                 // the stage was on when this list was enqueued
-        int32_t *host = nullptr; size_t host_words = 0;
+        HostBuf host;
         int copied = 0;                                   // records covered by the enqueued copy
         const DevBuf &out() const { return nms ? post : payload; }
+        int32_t *words() const { return host.as<int32_t>(); }
+        hipError_t reserve(size_t words) { return host.ensure(words * 4, (words + words / 4 + 256) * 4); }
     } cb;
     int cand_guess = 1024;                                // records the next speculative copy covers (shared by every CandBuf)
 
     // pipelined host entry points (pbd_detect_batch_submit / _wait): two batches may be in flight
     struct Slot {
-        void *pinned = nullptr; size_t pinned_cap = 0;   // host staging of the frames (hipHostMalloc)
+        HostBuf pinned;                                   // host staging of the frames
         DevBuf frames;
         CandBuf cb;
-        hipEvent_t copied = nullptr, done = nullptr;
-        Plan *plan = nullptr;
-        int nframes = 0;
+        Event copied, done;
     } slot[2];
-    hipStream_t stream_copy = nullptr, stream_d2h = nullptr;
+    Stream stream_copy, stream_d2h;
     long long nsubmitted = 0, nwaited = 0;
 
     Prof prof;
@@ -326,14 +357,45 @@ int guarded(pbd_handle *h, F &&body) noexcept
     }
 }
 
+// The preamble of every entry point that takes a handle: a null handle or pointer argument (`args_ok` false) is
+// PBD_ERR_INVALID, then the handle's device is made current and, with kIdle, a call while a batch is in flight is refused.
+// The body then checks argument values and handle state before it enqueues or copies anything.
+enum InFlight { kBusyOk, kIdle };
+template <class F>
+int entry(pbd_handle *h, bool args_ok, InFlight need, F &&body) noexcept
+{
+    return guarded(h, [&]() -> int {
+        if (!h || !args_ok) return PBD_ERR_INVALID;
+        (void)hipSetDevice(h->cfg.device);
+        if (need == kIdle && h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+        return body();
+    });
+}
+
+// shared checks (also check_frames below): PBD_OK (0) or the failure's status code
+int check_batch(pbd_handle *h, int nframes)
+{
+    if (nframes >= 1 && nframes <= h->cfg.max_batch) return PBD_OK;
+    return fail(h, PBD_ERR_INVALID, "nframes %d outside 1..max_batch %d", nframes, h->cfg.max_batch);
+}
+int check_bank(pbd_handle *h)
+{
+    if (h->bank_matches_model) return PBD_OK;
+    return fail(h, PBD_ERR_STATE, "the filter bank set by setFilters() (%d filters) does not cover the model's filter ids", h->F);
+}
+
+int stride(const pbd_handle *h) { return 8 + 4 * h->max_parts; }   // int32 words per candidate record
+
 // While a ProfScope is alive, every kernel launched by this thread is timed under kernel id `k` (see PBD_LAUNCH).
 struct ProfScope {
     pbd_handle *h; int k; ProfHook hook; ProfHook *prev;
     static void take(void *ctx, hipEvent_t *a, hipEvent_t *b)
     {
         ProfScope *self = static_cast<ProfScope *>(ctx);
-        *a = self->h->prof.get(); *b = self->h->prof.get();
-        self->h->prof.recs.push_back({self->k, *a, *b});
+        Prof &prof = self->h->prof;
+        Prof::Rec r{self->k, prof.get(), prof.get()};
+        *a = r.a.p; *b = r.b.p;
+        prof.recs.push_back(std::move(r));
     }
     ProfScope(pbd_handle *h_, int k_, hipStream_t) : h(h_), k(k_), hook{this, &ProfScope::take}, prev(g_prof_hook)
     {
@@ -469,13 +531,13 @@ hipError_t finish_plan_tables(Plan &P, int sbin)
 }
 
 // A finished plan joins the cache; the cache holds at most 16 plans and never evicts the plan the handle's
-// staged results refer to (h->cur).
+// resident result refers to.
 void cache_plan(pbd_handle *h, std::unique_ptr<Plan> P)
 {
     h->plans.push_back(std::move(P));
     while (h->plans.size() > 16) {
         auto it = h->plans.begin();
-        if (it->get() == h->cur) ++it;
+        if (it->get() == h->res.plan) ++it;
         h->plans.erase(it);
     }
 }
@@ -712,17 +774,12 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
     const bool fast = (sizeof(R) == 4 && K == 5 && sizes.size() == 1);
     const bool mfma = h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16;
     if (mfma && !fast) return fail(h, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA / PBD_CONV_MFMA_F16 need 5x5 filters and PBD_REAL_F32");
-    // The new bank is built beside the old one and swapped in only when every upload has succeeded: a failed setFilters()
+    // The new bank is built beside the old one and moved in only when every upload has succeeded: a failed setFilters()
     // (out of memory, an unsupported size) leaves the handle with its previous, complete bank.
-    struct NewBank {
-        std::vector<pbd_handle::ConvClass> classes;
-        DevBuf wrec;
-        bool keep = false;
-        ~NewBank() { if (!keep) { for (auto &c : classes) { c.wts.release(); c.fmap.release(); c.wts3.release(); c.unit_f0.release(); c.unit_ql.release(); c.unit_woff.release(); c.c31tab.release(); } wrec.release(); } }
-    } nb;
-    nb.classes.assign(sizes.size(), pbd_handle::ConvClass{});
+    std::vector<pbd_handle::ConvClass> classes(sizes.size());
+    DevBuf wrec;
     for (size_t ci = 0; ci < sizes.size(); ++ci) {
-        pbd_handle::ConvClass &C = nb.classes[ci];
+        pbd_handle::ConvClass &C = classes[ci];
         C.K = sizes[ci];
         std::vector<int> ids;
         for (int f = 0; f < nfilters; ++f) if (ksize[f] == C.K) ids.push_back(f);
@@ -819,15 +876,12 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
                                 rec[base + (size_t)(64 + lane) * 8 + j] = f2bf(v - bf2f(hi));
                             }
                         }
-        HIPCHK(h, nb.wrec.ensure(rec.size() * 2));
-        HIPCHK(h, hipMemcpy(nb.wrec.p, rec.data(), rec.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(h, wrec.ensure(rec.size() * 2));
+        HIPCHK(h, hipMemcpy(wrec.p, rec.data(), rec.size() * 2, hipMemcpyHostToDevice));
     }
     // commit
-    for (auto &c : h->conv_classes) { c.wts.release(); c.fmap.release(); c.wts3.release(); c.unit_f0.release(); c.unit_ql.release(); c.unit_woff.release(); c.c31tab.release(); }
-    h->conv_classes.swap(nb.classes);
-    nb.classes.clear();
-    if (mfma) { h->d_wrec.release(); h->d_wrec = nb.wrec; nb.wrec = DevBuf{}; }
-    nb.keep = true;
+    h->conv_classes = std::move(classes);
+    if (mfma) h->d_wrec = std::move(wrec);
     h->F = nfilters; h->Fpad = Fpad; h->ksize = K;
     h->filter_ksize.assign(ksize, ksize + nfilters);
     h->filters_set = true;
@@ -887,8 +941,7 @@ int build_model(pbd_handle *h, const pbd_model *m)
         for (int f = 0; f < m->nfilters; ++f)
             fp[f] = h->f64 ? static_cast<const void *>(m->filters_f64 + m->filter_offset[f])
                            : static_cast<const void *>(m->filters_f32 + m->filter_offset[f]);
-        int rc = upload_filters(h, m->nfilters, fp.data(), m->filter_ksize);
-        if (rc != PBD_OK) return rc;
+        if (int rc = upload_filters(h, m->nfilters, fp.data(), m->filter_ksize)) return rc;
     }
 
     // validation + pointer slots + depth
@@ -1080,9 +1133,9 @@ int build_model(pbd_handle *h, const pbd_model *m)
 // ---- stages --------------------------------------------------------------------------------------
 // alloc_* size the grow-only workspace for `nframes`; launch_* enqueue the kernels for frames
 // [f0, f0+nb) on stream `st` (no allocation, no synchronisation inside).
-int alloc_features(pbd_handle *h, Plan &P, int nframes, int cn)
+int alloc_features(pbd_handle *h, Plan &P, int nframes, int cn, int depth)
 {
-    HIPCHK(h, h->pyr.ensure((size_t)nframes * P.pix_per_frame * cn * depth_size(h->cur_depth) + 32));   // slack: 8-bit pixels are read with 4- and 16-byte loads
+    HIPCHK(h, h->pyr.ensure((size_t)nframes * P.pix_per_frame * cn * depth_size(depth) + 32));   // slack: 8-bit pixels are read with 4- and 16-byte loads
     HIPCHK(h, h->gmag.ensure((size_t)nframes * P.pix_per_frame * h->rs));
     HIPCHK(h, h->gori.ensure((size_t)nframes * P.pix_per_frame + 16));
     HIPCHK(h, h->hist.ensure((size_t)nframes * P.blk_per_frame * 18 * h->rs));
@@ -1091,13 +1144,13 @@ int alloc_features(pbd_handle *h, Plan &P, int nframes, int cn)
     return PBD_OK;
 }
 
-void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int f0, int nb, hipStream_t st)
+void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int depth, int f0, int nb, hipStream_t st)
 {
     PyrParams pp{};
-    pp.lv = P.d_lv.d; pp.nlevels = P.nlevels; pp.interval = std::min(P.interval, P.nlevels); pp.cn = cn; pp.frame0 = f0;
+    pp.lv = P.d_lv.p; pp.nlevels = P.nlevels; pp.interval = std::min(P.interval, P.nlevels); pp.cn = cn; pp.frame0 = f0;
     pp.pix_per_frame = P.pix_per_frame; pp.pyr = h->pyr.as<uint8_t>(); pp.frames = static_cast<const uint8_t *>(d_frames);
-    pp.rows = P.rows; pp.cols = P.cols; pp.tabx = P.d_tabx.d; pp.taby = P.d_taby.d;
-    pp.depth = h->cur_depth; pp.tabxf = P.d_tabxf.d; pp.tabyf = P.d_tabyf.d;
+    pp.rows = P.rows; pp.cols = P.cols; pp.tabx = P.d_tabx.p; pp.taby = P.d_taby.p;
+    pp.depth = depth; pp.tabxf = P.d_tabxf.p; pp.tabyf = P.d_tabyf.p;
     {
         ProfScope ps(h, PBD_K_RESIZE, st);
         launch_resize(pp, nb, P.npix_resized, st);
@@ -1110,12 +1163,12 @@ void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int f
         launch_pyrdown_range(pp, nb, first, last, base, end - base, st);
     }
     HogParams hp{};
-    hp.lv = P.d_lv.d; hp.nlevels = P.nlevels; hp.cn = cn; hp.sbin = h->sbin; hp.frame0 = f0;
+    hp.lv = P.d_lv.p; hp.nlevels = P.nlevels; hp.cn = cn; hp.sbin = h->sbin; hp.frame0 = f0;
     hp.pix_per_frame = P.pix_per_frame; hp.blk_per_frame = P.blk_per_frame; hp.cell_per_frame = P.cell_per_frame;
-    hp.pyr = h->pyr.as<uint8_t>(); hp.depth = h->cur_depth; hp.coord = h->d_coord.p;
+    hp.pyr = h->pyr.as<uint8_t>(); hp.depth = depth; hp.coord = h->d_coord.p;
     hp.gmag = h->gmag.p; hp.gori = h->gori.as<uint8_t>();
     hp.hist = h->hist.p; hp.norm = h->norm.p; hp.feat = h->feat.p;
-    hp.htiles = P.d_htiles.d; hp.nhtiles = P.nhtiles;
+    hp.htiles = P.d_htiles.p; hp.nhtiles = P.nhtiles;
     {
         ProfScope ps(h, PBD_K_HOG_HIST, st);
         launch_hog_hist(hp, nb, h->f64, st);
@@ -1124,7 +1177,6 @@ void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int f
         ProfScope ps(h, PBD_K_HOG_FEAT, st);
         launch_hog_feat(hp, nb, h->f64, st);
     }
-    h->feat_c31_zero = true;
 }
 
 int ensure_seg_tiles(pbd_handle *h, Plan &P, int nb)
@@ -1134,7 +1186,7 @@ int ensure_seg_tiles(pbd_handle *h, Plan &P, int nb)
     build_seg_tiles(P.lv, nb, tiles);
     DevTable<ConvSegTile> t;
     HIPCHK(h, t.upload(tiles));
-    P.segtiles[nb] = t;
+    P.segtiles[nb] = std::move(t);
     return PBD_OK;
 }
 
@@ -1148,22 +1200,22 @@ int alloc_conv(pbd_handle *h, Plan &P, int nframes)
 void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
 {
     ConvParams cp{};
-    cp.lv = P.d_lv.d; cp.tiles = P.d_tiles.d; cp.ntiles = P.ntiles;
-    cp.shaped = P.d_shaped.d;
+    cp.lv = P.d_lv.p; cp.tiles = P.d_tiles.p; cp.ntiles = P.ntiles;
+    cp.shaped = P.d_shaped.p;
     for (int k = 0; k < 3; ++k) cp.nshaped[k] = P.nshaped[k];
     cp.segtiles = nullptr; cp.nsegtiles = 0;
     if (!h->f64 && h->cfg.conv_mode != PBD_CONV_MFMA && h->cfg.conv_mode != PBD_CONV_MFMA_F16) {
         const auto it = P.segtiles.find(nb);     // built by ensure_seg_tiles before the first launch of this many frames
-        if (it != P.segtiles.end()) { cp.segtiles = it->second.d; cp.nsegtiles = (int)it->second.n; }
+        if (it != P.segtiles.end()) { cp.segtiles = it->second.p; cp.nsegtiles = (int)it->second.size; }
     }
     cp.F = h->F; cp.frame0 = f0;
     cp.cell_per_frame = P.cell_per_frame;
     cp.feat = h->feat.p; cp.resp = h->resp.p;
     cp.fma = h->cfg.conv_mode == PBD_CONV_FMA;
-    cp.c31_zero = h->feat_c31_zero ? 1 : 0;
+    cp.c31_zero = h->res.c31_zero ? 1 : 0;
     ProfScope ps(h, PBD_K_CONV, st);
     for (const pbd_handle::ConvClass &C : h->conv_classes) {     // one launch per filter size (one class in every known model)
-        cp.nf = C.nf; cp.Fpad = C.Fpad; cp.ksize = C.K; cp.wts = C.wts.p; cp.fmap = C.fmap.d;
+        cp.nf = C.nf; cp.Fpad = C.Fpad; cp.ksize = C.K; cp.wts = C.wts.p; cp.fmap = C.fmap.p;
         const int ngroups = C.Fpad / kConvQ;
         // few workgroups (single frame): split the filter groups over more workgroups to fill the chip
         const long long wgs = (long long)P.ntiles * nb;
@@ -1177,8 +1229,8 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
             while (cp.cblock > 1 && cp.cblock * plane > kConvLdsBudget) cp.cblock /= 2;
         }
         cp.wts3 = C.wts3.p;
-        cp.unit_f0 = C.unit_f0.d; cp.unit_ql = C.unit_ql.d; cp.unit_woff = C.unit_woff.d; cp.nunits = C.nunits;
-        cp.c31tab = C.c31tab.d; cp.c31stride = C.c31stride;
+        cp.unit_f0 = C.unit_f0.p; cp.unit_ql = C.unit_ql.p; cp.unit_woff = C.unit_woff.p; cp.nunits = C.nunits;
+        cp.c31tab = C.c31tab.p; cp.c31stride = C.c31stride;
         cp.units_per_block = wgs >= 1024 ? std::max(C.nunits, 1) : std::max(1, (int)((long long)C.nunits * wgs / 1024));
         if (h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16)
             launch_conv_mfma(cp, h->d_wrec.p, h->cfg.conv_mode == PBD_CONV_MFMA_F16, nb, st);
@@ -1223,26 +1275,26 @@ int alloc_dp(pbd_handle *h, Plan &P, int nframes, int chunk)
 void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
 {
     DpParams dp{};
-    dp.lv = P.d_lv.d; dp.nlevels = P.nlevels; dp.F = h->F; dp.NS = h->NS; dp.NC = h->NC; dp.NM = h->NM;
+    dp.lv = P.d_lv.p; dp.nlevels = P.nlevels; dp.F = h->F; dp.NS = h->NS; dp.NC = h->NC; dp.NM = h->NM;
     dp.cell_per_frame = P.cell_per_frame; dp.quad_per_frame = P.quad_per_frame; dp.max_mix = h->max_mix;
     dp.resp = h->resp.p; dp.resp_half = h->resp_half ? 1 : 0; dp.acc = h->acc.p;
     dp.Ik = h->Ik.as<uint8_t>(); dp.NJ = h->totmix; dp.ptr8 = P.ptr8 ? 1 : 0;
     dp.tmp = h->tmp.p; dp.dt = h->dt.p;
     dp.IxRaw = h->IxRaw.p; dp.IyRaw = h->IyRaw.p;
     dp.stk = h->stk.p; dp.stk_per_jf = P.stk_per_jf;
-    dp.stk_row_off = P.d_stk_row_off.d; dp.stk_col_off = P.d_stk_col_off.d;
-    dp.biasw = h->d_biasw.d;
-    dp.row2level = P.d_row2level.d; dp.rowoff = P.d_rowoff.d; dp.col2level = P.d_col2level.d; dp.coloff = P.d_coloff.d;
+    dp.stk_row_off = P.d_stk_row_off.p; dp.stk_col_off = P.d_stk_col_off.p;
+    dp.biasw = h->d_biasw.p;
+    dp.row2level = P.d_row2level.p; dp.rowoff = P.d_rowoff.p; dp.col2level = P.d_col2level.p; dp.coloff = P.d_coloff.p;
     dp.nrows_flat = P.nrows_flat; dp.ncols_flat = P.ncols_flat; dp.longest = P.longest;
-    dp.rootv = h->rootv.p; dp.rooti = h->rooti.as<int>(); dp.rjobs = h->d_rjobs.d;
+    dp.rootv = h->rootv.p; dp.rooti = h->rooti.as<int>(); dp.rjobs = h->d_rjobs.p;
     dp.frame0 = f0;
     for (auto &g : h->groups) {
         dp.JG = (int)g.jobs.size();
-        dp.jobs = g.d_jobs.d; dp.cjobs = g.d_cjobs.d; dp.childs = g.d_childs.d;
+        dp.jobs = g.d_jobs.p; dp.cjobs = g.d_cjobs.p; dp.childs = g.d_childs.p;
         dp.bz_x = g.bz_x; dp.bz_y = g.bz_y;
         { ProfScope ps(h, PBD_K_DT_ROWS, st); launch_dt_rows(dp, h->dt_opt, nb, h->f64, st); }
         { ProfScope ps(h, PBD_K_DT_COLS, st); launch_dt_cols(dp, h->dt_opt, nb, h->f64, st); }
-        dp.sjobs = g.d_sjobs.d;
+        dp.sjobs = g.d_sjobs.p;
         {
             ProfScope ps(h, PBD_K_DP_COMBINE, st);
             if (h->seq_mode) launch_dp_combine_seq(dp, (int)g.sjobs.size(), nb, h->f64, st);
@@ -1253,35 +1305,23 @@ void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
 }
 
 // the stages over the whole batch on the handle's stream (the dynamic program in chunks of frames within its scratch budget)
-int run_features(pbd_handle *h, Plan &P, const void *d_frames, int nframes, int cn)
-{
-    int rc = alloc_features(h, P, nframes, cn);
-    if (rc != PBD_OK) return rc;
-    launch_features(h, P, d_frames, cn, 0, nframes, h->stream);
-    HIPCHK(h, hipGetLastError());
-    h->have_features = true;
-    return PBD_OK;
-}
-
 int run_conv(pbd_handle *h, Plan &P, int nframes)
 {
-    int rc = alloc_conv(h, P, nframes);
-    if (rc != PBD_OK) return rc;
-    if ((rc = ensure_seg_tiles(h, P, nframes)) != PBD_OK) return rc;
+    if (int rc = alloc_conv(h, P, nframes)) return rc;
+    if (int rc = ensure_seg_tiles(h, P, nframes)) return rc;
     launch_conv_stage(h, P, 0, nframes, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->have_resp = true;
+    h->res.resp = true;
     return PBD_OK;
 }
 
 int run_dp(pbd_handle *h, Plan &P, int nframes)
 {
     const int chunk = dp_chunk_frames(h, P, nframes);
-    int rc = alloc_dp(h, P, nframes, chunk);
-    if (rc != PBD_OK) return rc;
+    if (int rc = alloc_dp(h, P, nframes, chunk)) return rc;
     for (int f0 = 0; f0 < nframes; f0 += chunk) launch_dp_chunk(h, P, f0, std::min(chunk, nframes - f0), h->stream);
     HIPCHK(h, hipGetLastError());
-    h->have_dp = true;
+    h->res.dp = true;
     return PBD_OK;
 }
 
@@ -1292,13 +1332,13 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
                    int capacity, hipStream_t st)
 {
     ArgminParams ap{};
-    ap.lv = P.d_lv.d; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
+    ap.lv = P.d_lv.p; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
     ap.cell_per_frame = P.cell_per_frame;
     ap.rootv = h->rootv.p; ap.rooti = h->rooti.as<int>();
     ap.IxRaw = h->IxRaw.p; ap.IyRaw = h->IyRaw.p; ap.NJ = h->totmix; ap.Ik = h->Ik.as<uint8_t>(); ap.ptr8 = P.ptr8 ? 1 : 0;
     ap.thresh = h->thresh; ap.scales = d_scales;
-    ap.walk = h->d_walk.d; ap.walk_off = h->d_walk_off.d;
-    ap.max_parts = h->max_parts; ap.stride = 8 + 4 * h->max_parts; ap.capacity = std::max(capacity, 0);
+    ap.walk = h->d_walk.p; ap.walk_off = h->d_walk_off.p;
+    ap.max_parts = h->max_parts; ap.stride = stride(h); ap.capacity = std::max(capacity, 0);
     ap.payload = d_payload; ap.frame_offset = frame_offset;
     ap.ntotal = (long long)nframes * P.cell_per_frame * h->NC;
     ap.nblk = (int)std::max<long long>((ap.ntotal + argmin_find_span() - 1) / argmin_find_span(), 1);
@@ -1318,7 +1358,7 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
 {
     PostParams pp{};
     pp.in = d_in; pp.in_cap = std::max(in_cap, 1);
-    pp.stride = 8 + 4 * h->max_parts; pp.max_parts = h->max_parts; pp.nframes = nframes;
+    pp.stride = stride(h); pp.max_parts = h->max_parts; pp.nframes = nframes;
     pp.rows = rows; pp.cols = cols; pp.wpr = (cols + 31) / 32; pp.overlap = overlap;
     pp.out = d_out; pp.out_cap = std::max(out_cap, 0); pp.frame_offset = frame_offset;
     // workspace: key, frame, perm, slot [in_cap] | box [in_cap] int4 | fkept [nframes] | global canvases (frames too big for LDS)
@@ -1336,37 +1376,27 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
     return PBD_OK;
 }
 
-int candbuf_host(pbd_handle *h, pbd_handle::CandBuf &cb, size_t words)
-{
-    if (cb.host_words >= words) return PBD_OK;
-    if (cb.host) { (void)hipHostFree(cb.host); cb.host = nullptr; cb.host_words = 0; }
-    const size_t want = words + words / 4 + 256;
-    HIPCHK(h, hipHostMalloc(reinterpret_cast<void **>(&cb.host), want * sizeof(int32_t), hipHostMallocDefault));
-    cb.host_words = want;
-    return PBD_OK;
-}
-
 // find + walk into cb.payload (then, with `post`, the sort + suppression into cb.post) and the speculative read-back of
 // [count | first records], all on `st`
 int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, bool post,
                             hipStream_t st)
 {
-    const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
+    const int stride = ::stride(h), cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-    int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st);
-    if (rc != PBD_OK) return rc;
+    if (int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st)) return rc;
     cb.nms = post;
     if (post) {
         HIPCHK(h, cb.post.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-        if ((rc = enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, cb.payload.as<int32_t>(), cap, 0, cb.post.as<int32_t>(), cap,
-                               st)) != PBD_OK)
+        if (int rc = enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, cb.payload.as<int32_t>(), cap, 0, cb.post.as<int32_t>(),
+                                  cap, st))
             return rc;
     }
     cb.copied = std::min(h->cand_guess, cap);
     const size_t words = 1 + (size_t)cb.copied * stride;
-    // the mirror is sized for twice the guess: growing it (hipHostFree + hipHostMalloc) synchronises the device
-    if (cb.host_words < words && (rc = candbuf_host(h, cb, 1 + (size_t)std::min(2 * (long long)cb.copied, (long long)cap) * stride)) != PBD_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(cb.host, cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    // the mirror is sized for twice the guess: growing pinned memory synchronises the device
+    if (cb.host.size < words * sizeof(int32_t))
+        HIPCHK(h, cb.reserve(1 + (size_t)std::min(2 * (long long)cb.copied, (long long)cap) * stride));
+    HIPCHK(h, hipMemcpyAsync(cb.words(), cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     return PBD_OK;
 }
 
@@ -1374,8 +1404,8 @@ int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_
 // src/DynamicProgram.cpp:246-251; here it is (frame, level, component, y, x), produced on the device)
 int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32_t *cand, int capacity, int *ncand)
 {
-    const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
-    const int found = cb.host[0];
+    const int stride = ::stride(h), cap = std::max(h->cfg.max_candidates, 1);
+    const int found = cb.words()[0];
     if (found < 0) {         // the post-processing stage saw more candidates than the list holds: no suppressed prefix
         *ncand = 0;
         return fail(h, PBD_ERR_CAPACITY, "more than max_candidates (%d) candidates were found before non-maxima suppression: "
@@ -1384,15 +1414,14 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
     const int n = std::min(found, cap);
     if (n > cb.copied) {     // more candidates than the speculative copy covered: fetch the list again, whole
         const size_t words = 1 + (size_t)n * stride;
-        const int rc = candbuf_host(h, cb, words);
-        if (rc != PBD_OK) return rc;
-        HIPCHK(h, hipMemcpyAsync(cb.host, cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, cb.reserve(words));
+        HIPCHK(h, hipMemcpyAsync(cb.words(), cb.out().p, words * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
         cb.copied = n;
     }
     h->cand_guess = std::min(cap, std::max(n + n / 4 + 256, 1024));
     const int nout = std::min(n, std::max(capacity, 0));
-    if (nout > 0) memcpy(cand, cb.host + 1, (size_t)nout * stride * sizeof(int32_t));
+    if (nout > 0) memcpy(cand, cb.words() + 1, (size_t)nout * stride * sizeof(int32_t));
     *ncand = nout;
     if (found > cap || n > capacity)
         return fail(h, PBD_ERR_CAPACITY, "%d candidates found, capacity %d (config max_candidates %d)", found, capacity, cap);
@@ -1401,8 +1430,7 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
 
 int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, int32_t *cand, int capacity, int *ncand)
 {
-    const int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, h->stream);
-    if (rc != PBD_OK) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, h->stream)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return argmin_deliver(h, h->cb, h->stream, cand, capacity, ncand);
@@ -1413,69 +1441,116 @@ int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool 
 // the caller's
 int enqueue_argmin_out(pbd_handle *h, Plan &P, int nframes, int frame_offset, int32_t *d_payload, int capacity)
 {
-    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.d, frame_offset, d_payload, capacity, h->stream);
-    const int stride = 8 + 4 * h->max_parts, cap = std::max(h->cfg.max_candidates, 1);
-    HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-    const int rc = enqueue_argmin(h, P, nframes, P.d_scales.d, 0, h->cb.payload.as<int32_t>(), cap, h->stream);
-    if (rc != PBD_OK) return rc;
+    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.p, frame_offset, d_payload, capacity, h->stream);
+    const int cap = std::max(h->cfg.max_candidates, 1);
+    HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride(h) + 1) * sizeof(int32_t)));
+    if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream)) return rc;
     return enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap, frame_offset, d_payload, capacity,
                         h->stream);
 }
 
-// enqueues pyramid -> HOG -> convolution -> dynamic program for the batch (no host synchronisation); *plan_out = its plan
-int enqueue_detect(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int cn, Plan **plan_out)
+// Frames of a call: on the host (`host[i]`, rows `stride` bytes apart; uploaded to h->frames by enqueue_features) or
+// already packed on the device (`dev`)
+struct FrameSrc {
+    const void *const *host;
+    size_t stride;
+    const void *dev;
+};
+
+// image depth and channels; for host frames also the row stride and, for 32F / 64F, that every pixel is finite
+int check_frames(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int cols, int cn, int depth)
 {
-    if (nframes < 1 || nframes > h->cfg.max_batch)
-        return fail(h, PBD_ERR_INVALID, "nframes %d outside 1..max_batch %d", nframes, h->cfg.max_batch);
+    if (!depth_size(depth))
+        return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth);
     if (cn != 1 && cn != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", cn);
-    if (!h->bank_matches_model)
-        return fail(h, PBD_ERR_STATE, "the filter bank set by setFilters() (%d filters) does not cover the model's filter ids", h->F);
-    Plan *P = nullptr;
-    int rc = get_image_plan(h, rows, cols, &P);
-    if (rc != PBD_OK) return rc;
-    h->cur = P; h->cur_frames = nframes; h->cur_cn = cn;
-    h->have_features = h->have_resp = h->have_dp = false;
-    if ((rc = run_features(h, *P, d_frames, nframes, cn)) != PBD_OK) return rc;
-    if ((rc = run_conv(h, *P, nframes)) != PBD_OK) return rc;
-    if ((rc = run_dp(h, *P, nframes)) != PBD_OK) return rc;
-    *plan_out = P;
-    return PBD_OK;
-}
-
-int detect_device(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int cn, int32_t *cand,
-                  int capacity, int *ncand)
-{
-    if (!h || !cand || !ncand) return PBD_ERR_INVALID;
-    if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-    Plan *P = nullptr;
-    const int rc = enqueue_detect(h, nframes, d_frames, rows, cols, cn, &P);
-    if (rc != PBD_OK) return rc;
-    return run_argmin(h, *P, nframes, P->d_scales.d, h->nms, cand, capacity, ncand);
-}
-
-int upload_frames(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int cn, size_t stride_bytes)
-{
-    const size_t row_bytes = (size_t)cols * cn * depth_size(h->cur_depth);
-    if (stride_bytes < row_bytes) return fail(h, PBD_ERR_INVALID, "stride %zu < row bytes %zu", stride_bytes, row_bytes);
+    if (!src.host) return PBD_OK;
+    const size_t row_bytes = (size_t)cols * cn * depth_size(depth);
+    if (src.stride < row_bytes) return fail(h, PBD_ERR_INVALID, "stride %zu < row bytes %zu", src.stride, row_bytes);
     // 32F / 64F images: a NaN or Inf pixel is refused.  The reference computes *something* deterministic from one (NaN
     // gradients, NaN histogram bins, NaN responses whose envelope read-out order then matters); the distance transform here
     // walks the envelope top-down, which equals the reference's bottom-up walk only for strictly increasing finite
     // intersections -- so non-finite input is defined as an error instead of being allowed to differ silently.
-    if (h->cur_depth == kDepth32F || h->cur_depth == kDepth64F) {
+    if (depth == kDepth32F || depth == kDepth64F) {
         const size_t n = (size_t)cols * cn;
         for (int i = 0; i < nframes; ++i)
             for (int y = 0; y < rows; ++y) {
-                const char *row = static_cast<const char *>(imgs[i]) + (size_t)y * stride_bytes;
+                const char *row = static_cast<const char *>(src.host[i]) + (size_t)y * src.stride;
                 bool ok = true;
-                if (h->cur_depth == kDepth32F) { const float *p = reinterpret_cast<const float *>(row); for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(p[k]); }
+                if (depth == kDepth32F) { const float *p = reinterpret_cast<const float *>(row); for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(p[k]); }
                 else { const double *p = reinterpret_cast<const double *>(row); for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(p[k]); }
                 if (!ok) return fail(h, PBD_ERR_INVALID, "frame %d, row %d holds a NaN or Inf pixel", i, y);
             }
     }
+    return PBD_OK;
+}
+
+// every check of a detect call, before anything is enqueued; *plan = the batch's image plan
+int check_detect(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int cols, int cn, int depth, Plan **plan)
+{
+    if (int rc = check_batch(h, nframes)) return rc;
+    if (int rc = check_frames(h, nframes, src, rows, cols, cn, depth)) return rc;
+    if (int rc = check_bank(h)) return rc;
+    return get_image_plan(h, rows, cols, plan);
+}
+
+int upload_frames(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int cn, int depth, size_t stride_bytes)
+{
+    const size_t row_bytes = (size_t)cols * cn * depth_size(depth);
     HIPCHK(h, h->frames.ensure((size_t)nframes * rows * row_bytes + 4));
     for (int i = 0; i < nframes; ++i)
         HIPCHK(h, hipMemcpy2DAsync(h->frames.as<uint8_t>() + (size_t)i * rows * row_bytes, row_bytes, imgs[i], stride_bytes,
                                    row_bytes, rows, hipMemcpyHostToDevice, h->stream));
+    return PBD_OK;
+}
+
+// The batch's result replaces the resident one here; then its frames are uploaded (host frames) and the pyramid and HOG
+// features enqueued.  No host synchronisation.
+int enqueue_features(pbd_handle *h, Plan &P, int nframes, const FrameSrc &src, int cn, int depth)
+{
+    h->res = Resident{&P, nframes, cn, depth};
+    const void *d_frames = src.dev;
+    if (src.host) {
+        if (int rc = upload_frames(h, nframes, src.host, P.rows, P.cols, cn, depth, src.stride)) return rc;
+        d_frames = h->frames.p;
+    }
+    if (int rc = alloc_features(h, P, nframes, cn, depth)) return rc;
+    launch_features(h, P, d_frames, cn, depth, 0, nframes, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->res.features = h->res.c31_zero = true;
+    return PBD_OK;
+}
+
+// pyramid -> HOG -> convolution -> dynamic program for a batch that passed check_detect (no host synchronisation)
+int enqueue_detect(pbd_handle *h, Plan &P, int nframes, const FrameSrc &src, int cn, int depth)
+{
+    if (int rc = enqueue_features(h, P, nframes, src, cn, depth)) return rc;
+    if (int rc = run_conv(h, P, nframes)) return rc;
+    return run_dp(h, P, nframes);
+}
+
+// the synchronous detect entry points: the whole path, then the candidates' read-back
+int detect_sync(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int cols, int cn, int depth, int32_t *cand, int capacity,
+                int *ncand)
+{
+    Plan *P = nullptr;
+    if (int rc = check_detect(h, nframes, src, rows, cols, cn, depth, &P)) return rc;
+    if (int rc = enqueue_detect(h, *P, nframes, src, cn, depth)) return rc;
+    return run_argmin(h, *P, nframes, P->d_scales.p, h->nms, cand, capacity, ncand);
+}
+
+// copies n responses from the device to dst as T; in PBD_CONV_MFMA_F16 mode the device holds fp16, widened to float here
+int read_responses(pbd_handle *h, void *dst, const void *src, size_t n)
+{
+    if (!n) return PBD_OK;
+    if (!h->resp_half) {
+        HIPCHK(h, hipMemcpyAsync(dst, src, n * h->rs, hipMemcpyDeviceToHost, h->stream));
+        return PBD_OK;
+    }
+    std::vector<uint16_t> halfbuf(n);
+    HIPCHK(h, hipMemcpyAsync(halfbuf.data(), src, n * 2, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float *out = static_cast<float *>(dst);
+    for (size_t i = 0; i < n; ++i) out[i] = host_h2f(halfbuf[i]);
     return PBD_OK;
 }
 
@@ -1537,14 +1612,11 @@ int pbd_debug_guard_selftest(int kind)
 int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *records, int n, float overlap, int32_t *out, int capacity,
                           int *nout)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !nout || (n > 0 && !records) || (capacity > 0 && !out)) return PBD_ERR_INVALID;
+    return entry(h, nout && (n <= 0 || records) && (capacity <= 0 || out), kIdle, [&]() -> int {
         *nout = 0;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
         if (rows < 1 || cols < 1 || rows > 65536 || cols > 65536 || n < 0 || capacity < 0 || std::isnan(overlap))
             return fail(h, PBD_ERR_INVALID, "rows %d, cols %d, n %d, capacity %d", rows, cols, n, capacity);
-        (void)hipSetDevice(h->cfg.device);
-        const int stride = 8 + 4 * h->max_parts;
+        const int stride = ::stride(h);
         int nframes = 1;
         for (int i = 0; i < n; ++i) {
             const int32_t *r = records + (size_t)i * stride;
@@ -1560,9 +1632,8 @@ int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *reco
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipMemcpy(h->dbg_in.p, &n, sizeof(int32_t), hipMemcpyHostToDevice));
         if (n) HIPCHK(h, hipMemcpy(h->dbg_in.as<int32_t>() + 1, records, (size_t)n * stride * sizeof(int32_t), hipMemcpyHostToDevice));
-        int rc = enqueue_post(h, nframes, rows, cols, overlap, h->dbg_in.as<int32_t>(), in_cap, 0, h->dbg_out.as<int32_t>(), capacity,
-                              h->stream);
-        if (rc != PBD_OK) return rc;
+        if (int rc = enqueue_post(h, nframes, rows, cols, overlap, h->dbg_in.as<int32_t>(), in_cap, 0, h->dbg_out.as<int32_t>(), capacity,
+                              h->stream)) return rc;
         HIPCHK(h, hipGetLastError());
         int kept = 0;
         HIPCHK(h, hipMemcpyAsync(&kept, h->dbg_out.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1580,9 +1651,7 @@ int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *reco
 enum { PBD_DEBUG_DT_LANE_SHIFT = 0, PBD_DEBUG_DT_COOP = 1, PBD_DEBUG_DT_COOP_G = 2, PBD_DEBUG_DP_BUDGET_MB = 3 };
 int pbd_debug_set_option(pbd_handle *h, int option, int value)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+    return entry(h, true, kIdle, [&]() -> int {
         switch (option) {
         case PBD_DEBUG_DT_LANE_SHIFT:   // 0..6: 64 >> value rows per wave; -1: automatic
             if (value < -1 || value > 6) break;
@@ -1633,11 +1702,10 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
         if (h->cfg.max_batch < 1) h->cfg.max_batch = 1;
         if (h->cfg.max_candidates < 1) h->cfg.max_candidates = 65536;
         if (config->stream) {
-            h->stream = reinterpret_cast<hipStream_t>(config->stream);
+            h->stream.borrow(reinterpret_cast<hipStream_t>(config->stream));
         } else {
-            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+            e = h->stream.create();
             if (e != hipSuccess) return fail(nullptr, PBD_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-            h->own_stream = true;
         }
         int rc = build_model(h.get(), model);
         if (rc != PBD_OK) {
@@ -1652,39 +1720,17 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
 void pbd_destroy(pbd_handle *h)
 {
     if (!h) return;
-    try {
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->prof.release();
-    if (h->stream_copy) (void)hipStreamSynchronize(h->stream_copy);
-    if (h->stream_d2h) (void)hipStreamSynchronize(h->stream_d2h);
-    for (pbd_handle::Slot &S : h->slot) {
-        if (S.pinned) (void)hipHostFree(S.pinned);
-        if (S.cb.host) (void)hipHostFree(S.cb.host);
-        if (S.copied) (void)hipEventDestroy(S.copied);
-        if (S.done) (void)hipEventDestroy(S.done);
-        S.frames.release(); S.cb.payload.release(); S.cb.post.release();
-    }
-    if (h->cb.host) (void)hipHostFree(h->cb.host);
-    h->cb.payload.release(); h->cb.post.release();
-    if (h->stream_copy) (void)hipStreamDestroy(h->stream_copy);
-    if (h->stream_d2h) (void)hipStreamDestroy(h->stream_d2h);
-    for (DevBuf *b : {&h->frames, &h->pyr, &h->gmag, &h->gori, &h->hist, &h->norm, &h->feat, &h->resp, &h->acc, &h->Ik, &h->rootv,
-                      &h->rooti, &h->tmp, &h->dt, &h->IxRaw, &h->IyRaw, &h->stk, &h->find_blk,
-                      &h->scales_tmp, &h->post_ws, &h->dbg_in, &h->dbg_out})
-        b->release();
-    for (auto &c : h->conv_classes) { c.wts.release(); c.fmap.release(); c.wts3.release(); c.unit_f0.release(); c.unit_ql.release(); c.unit_woff.release(); c.c31tab.release(); }
-    h->d_wrec.release(); h->d_biasw.release(); h->d_coord.release(); h->d_walk_off.release();
-    h->d_rjobs.release(); h->d_walk.release();
-    for (auto &g : h->groups) { g.d_jobs.release(); g.d_childs.release(); g.d_cjobs.release(); g.d_sjobs.release(); }
-    h->plans.clear();
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    for (hipStream_t s : {h->stream.s, h->stream_copy.s, h->stream_d2h.s})   // work in flight ends before its memory is freed
+        if (s) (void)hipStreamSynchronize(s);
+    try {
+        h->prof.flush();
     } catch (...) {
     }
-    delete h;
+    delete h;   // the members' owners free every device, pinned, event and stream resource
 }
 
-int pbd_candidate_stride(const pbd_handle *h) { return h ? 8 + 4 * h->max_parts : 0; }
+int pbd_candidate_stride(const pbd_handle *h) { return h ? stride(h) : 0; }
 int pbd_binsize(const pbd_handle *h) { return h ? h->sbin : 0; }
 int pbd_num_ptr_slots(const pbd_handle *h) { return h ? h->NS : 0; }
 int pbd_ptr_slot(const pbd_handle *h, int component, int part)
@@ -1697,19 +1743,16 @@ int pbd_ptr_slot(const pbd_handle *h, int component, int part)
 
 int pbd_set_level_shard(pbd_handle *h, int rank, int world)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
+    return entry(h, true, kIdle, [&]() -> int {
         if (world < 1 || rank < 0 || rank >= world) return fail(h, PBD_ERR_INVALID, "level shard %d of %d", rank, world);
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
         if (world > 1 && h->nms)
             return fail(h, PBD_ERR_UNSUPPORTED, "level sharding with non-maxima suppression on: suppression of one rank's levels "
                         "is not suppression of the union (pbd_set_nms(h, 0, ...) first)");
         if (rank == h->shard_rank && world == h->shard_world) return PBD_OK;
-        (void)hipSetDevice(h->cfg.device);
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->shard_rank = rank; h->shard_world = world;
         // image plans depend on the shard
-        h->cur = nullptr; h->have_features = h->have_resp = h->have_dp = false;
+        h->res.clear();
         for (size_t i = 0; i < h->plans.size();)
             if (h->plans[i]->kind == 0) h->plans.erase(h->plans.begin() + i); else ++i;
         return PBD_OK;
@@ -1718,10 +1761,8 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
 
 int pbd_set_nms(pbd_handle *h, int enable, float overlap)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
+    return entry(h, true, kIdle, [&]() -> int {
         if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
         if (enable && h->shard_world > 1)
             return fail(h, PBD_ERR_UNSUPPORTED, "non-maxima suppression with level sharding (world %d): suppression of one rank's "
                         "levels is not suppression of the union", h->shard_world);
@@ -1734,12 +1775,9 @@ int pbd_set_nms(pbd_handle *h, int enable, float overlap)
 int pbd_pyramid_plan(pbd_handle *h, int rows, int cols, int *nlevels, int *img_rows, int *img_cols, int *feat_rows,
                      int *feat_cols, float *scales)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !nlevels) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, nlevels, kBusyOk, [&]() -> int {
         Plan *P = nullptr;
-        int rc = get_image_plan(h, rows, cols, &P);
-        if (rc != PBD_OK) return rc;
+        if (int rc = get_image_plan(h, rows, cols, &P)) return rc;
         *nlevels = P->nlevels;
         for (int l = 0; l < P->nlevels; ++l) {
             if (img_rows) img_rows[l] = P->lv[l].img_rows;
@@ -1755,21 +1793,12 @@ int pbd_pyramid_plan(pbd_handle *h, int rows, int cols, int *nlevels, int *img_r
 int pbd_features_pyramid(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes,
                          int depth_code, void *const *feat)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !img || !feat) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
-        if (!depth_size(depth_code))
-            return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth_code);
-        h->cur_depth = depth_code;
-        if (channels != 1 && channels != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", channels);
+    return entry(h, img && feat, kIdle, [&]() -> int {
+        const FrameSrc src{&img, stride_bytes, nullptr};
         Plan *P = nullptr;
-        int rc = get_image_plan(h, rows, cols, &P);
-        if (rc != PBD_OK) return rc;
-        if ((rc = upload_frames(h, 1, &img, rows, cols, channels, stride_bytes)) != PBD_OK) return rc;
-        h->cur = P; h->cur_frames = 1; h->cur_cn = channels;
-        h->have_features = h->have_resp = h->have_dp = false;
-        if ((rc = run_features(h, *P, h->frames.p, 1, channels)) != PBD_OK) return rc;
+        if (int rc = check_frames(h, 1, src, rows, cols, channels, depth_code)) return rc;
+        if (int rc = get_image_plan(h, rows, cols, &P)) return rc;
+        if (int rc = enqueue_features(h, *P, 1, src, channels, depth_code)) return rc;
         for (int l = 0; l < P->nlevels; ++l) {
             const LevelDesc &d = P->lv[l];
             const size_t n = (size_t)d.rows * d.cols * 32;
@@ -1784,17 +1813,15 @@ int pbd_features_pyramid(pbd_handle *h, const void *img, int rows, int cols, int
 
 int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !dst) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
-        if (!h->cur || h->cur->kind != 0 || !h->have_features) return fail(h, PBD_ERR_STATE, "no pyramid has been computed");
-        Plan &P = *h->cur;
-        if (frame < 0 || frame >= h->cur_frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
+    return entry(h, dst, kIdle, [&]() -> int {
+        const Resident &r = h->res;
+        if (!r.plan || r.plan->kind != 0 || !r.features) return fail(h, PBD_ERR_STATE, "no pyramid has been computed");
+        const Plan &P = *r.plan;
+        if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
         const LevelDesc &d = P.lv[level];
-        const size_t es = depth_size(h->cur_depth);
-        HIPCHK(h, hipMemcpyAsync(dst, h->pyr.as<uint8_t>() + ((size_t)frame * P.pix_per_frame + d.img_off) * h->cur_cn * es,
-                                 (size_t)d.img_rows * d.img_cols * h->cur_cn * es, hipMemcpyDeviceToHost, h->stream));
+        const size_t es = depth_size(r.depth);
+        HIPCHK(h, hipMemcpyAsync(dst, h->pyr.as<uint8_t>() + ((size_t)frame * P.pix_per_frame + d.img_off) * r.cn * es,
+                                 (size_t)d.img_rows * d.img_cols * r.cn * es, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return PBD_OK;
     });
@@ -1802,50 +1829,31 @@ int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst)
 
 int pbd_conv_set_filters(pbd_handle *h, int nfilters, const void *const *filters, const int *ksize)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !filters || !ksize) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, filters && ksize, kIdle, [&]() -> int {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        const int rc = upload_filters(h, nfilters, filters, ksize);
-        if (rc != PBD_OK) return rc;
-        h->have_resp = h->have_dp = false;   // staged results of the old bank are gone
+        if (int rc = upload_filters(h, nfilters, filters, ksize)) return rc;
+        h->res.drop_conv();   // the resident responses were those of the old bank
         return revalidate_bank(h);
     });
 }
 
 int pbd_conv_pdf(pbd_handle *h, int nlevels, const void *const *feat, const int *rows, const int *cols, void *const *resp)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !feat || !rows || !cols || !resp) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, feat && rows && cols && resp, kIdle, [&]() -> int {
         Plan *P = nullptr;
-        int rc = get_dims_plan(h, nlevels, rows, cols, &P);
-        if (rc != PBD_OK) return rc;
+        if (int rc = get_dims_plan(h, nlevels, rows, cols, &P)) return rc;
+        h->res = Resident{P, 1};
         HIPCHK(h, h->feat.ensure(std::max<size_t>((size_t)P->cell_per_frame * 32 * h->rs, 16)));
         for (int l = 0; l < nlevels; ++l) {
             const size_t n = (size_t)rows[l] * cols[l] * 32;
             if (n) HIPCHK(h, hipMemcpyAsync(h->feat.as<char>() + (size_t)P->lv[l].cell_off * 32 * h->rs, feat[l], n * h->rs,
                                             hipMemcpyHostToDevice, h->stream));
         }
-        h->cur = P; h->cur_frames = 1; h->have_features = true; h->have_resp = h->have_dp = false;
-        h->feat_c31_zero = false;
-        if ((rc = run_conv(h, *P, 1)) != PBD_OK) return rc;
-        std::vector<uint16_t> halfbuf;
+        h->res.features = true;
+        if (int rc = run_conv(h, *P, 1)) return rc;
         for (int l = 0; l < nlevels; ++l) {
-            const size_t n = (size_t)rows[l] * cols[l] * h->F;
-            if (!n) continue;
             const char *src = h->resp.as<char>() + (size_t)P->lv[l].cell_off * h->F * h->resp_es;
-            if (h->resp_half) {      // fp16 on the device, T = float at the seam
-                halfbuf.resize(n);
-                HIPCHK(h, hipMemcpyAsync(halfbuf.data(), src, n * 2, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                float *dst = static_cast<float *>(resp[l]);
-                for (size_t i = 0; i < n; ++i) dst[i] = host_h2f(halfbuf[i]);
-            } else {
-                HIPCHK(h, hipMemcpyAsync(resp[l], src, n * h->rs, hipMemcpyDeviceToHost, h->stream));
-            }
+            if (int rc = read_responses(h, resp[l], src, (size_t)rows[l] * cols[l] * h->F)) return rc;
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return PBD_OK;
@@ -1855,15 +1863,11 @@ int pbd_conv_pdf(pbd_handle *h, int nlevels, const void *const *feat, const int 
 int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, const void *const *resp, int32_t *const *Ix,
                int32_t *const *Iy, int32_t *const *Ik, void *const *rootv, int32_t *const *rooti)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !rows || !cols || !resp) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, rows && cols && resp, kIdle, [&]() -> int {
+        if (int rc = check_bank(h)) return rc;
         Plan *P = nullptr;
-        if (!h->bank_matches_model)
-            return fail(h, PBD_ERR_STATE, "the filter bank set by setFilters() (%d filters) does not cover the model's filter ids", h->F);
-        int rc = get_dims_plan(h, nlevels, rows, cols, &P);
-        if (rc != PBD_OK) return rc;
+        if (int rc = get_dims_plan(h, nlevels, rows, cols, &P)) return rc;
+        h->res = Resident{P, 1};
         HIPCHK(h, h->resp.ensure(std::max<size_t>((size_t)P->cell_per_frame * h->F * h->resp_es, 16) + 32));
         std::vector<uint16_t> halfbuf;
         for (int l = 0; l < nlevels; ++l) {
@@ -1879,8 +1883,8 @@ int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, con
                 HIPCHK(h, hipMemcpyAsync(dst, resp[l], n * h->rs, hipMemcpyHostToDevice, h->stream));
             }
         }
-        h->cur = P; h->cur_frames = 1; h->have_resp = true; h->have_dp = false;
-        if ((rc = run_dp(h, *P, 1)) != PBD_OK) return rc;
+        h->res.resp = true;
+        if (int rc = run_dp(h, *P, 1)) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
         std::vector<uint8_t> t8;
         for (int l = 0; l < nlevels; ++l) {
@@ -1945,15 +1949,12 @@ int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, con
 
 int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacity, int *ncand)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !scales || !cand || !ncand) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
-        if (!h->cur || !h->have_dp) return fail(h, PBD_ERR_STATE, "argmin() before min()");
-        Plan &P = *h->cur;
+    return entry(h, scales && cand && ncand, kIdle, [&]() -> int {
+        if (!h->res.plan || !h->res.dp) return fail(h, PBD_ERR_STATE, "argmin() before min()");
+        Plan &P = *h->res.plan;
         HIPCHK(h, h->scales_tmp.ensure(sizeof(float) * PBD_MAX_LEVELS));
         HIPCHK(h, hipMemcpyAsync(h->scales_tmp.p, scales, sizeof(float) * P.nlevels, hipMemcpyHostToDevice, h->stream));
-        return run_argmin(h, P, h->cur_frames, h->scales_tmp.as<float>(), false, cand, capacity, ncand);   // no suppression (DynamicProgram::argmin)
+        return run_argmin(h, P, h->res.frames, h->scales_tmp.as<float>(), false, cand, capacity, ncand);   // no suppression (DynamicProgram::argmin)
     });
 }
 
@@ -1966,32 +1967,36 @@ int pbd_detect(pbd_handle *h, const void *img, int rows, int cols, int channels,
 int pbd_detect_batch(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int channels,
                      size_t stride_bytes, int32_t *cand, int capacity, int *ncand)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !imgs || !cand || !ncand) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        if (nframes < 1 || nframes > h->cfg.max_batch)
-            return fail(h, PBD_ERR_INVALID, "nframes %d outside 1..max_batch %d", nframes, h->cfg.max_batch);
-        if (channels != 1 && channels != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", channels);
-        h->cur_depth = kDepth8U;
-        int rc = upload_frames(h, nframes, imgs, rows, cols, channels, stride_bytes);
-        if (rc != PBD_OK) return rc;
-        return detect_device(h, nframes, h->frames.p, rows, cols, channels, cand, capacity, ncand);
+    return entry(h, imgs && cand && ncand, kIdle, [&]() -> int {
+        return detect_sync(h, nframes, FrameSrc{imgs, stride_bytes, nullptr}, rows, cols, channels, kDepth8U, cand, capacity, ncand);
     });
 }
 
-// what submit() does once the frames of the batch are (being) made resident at d_frames: the whole path, the candidates'
-// read-back and the slot's completion event, all enqueued on the handle's stream without waiting
-static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, int nframes, const void *d_frames, int rows, int cols, int channels)
+int pbd_detect_batch_device(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int channels,
+                            int32_t *cand, int capacity, int *ncand)
 {
-    if (!S.done) HIPCHK(h, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-    Plan *P = nullptr;
-    h->cur_depth = kDepth8U;
-    int rc = enqueue_detect(h, nframes, d_frames, rows, cols, channels, &P);
-    if (rc != PBD_OK) return rc;
-    if ((rc = enqueue_argmin_readback(h, *P, nframes, P->d_scales.d, S.cb, h->nms, h->stream)) != PBD_OK) return rc;
-    HIPCHK(h, hipEventRecord(S.done, h->stream));
+    return entry(h, d_frames && cand && ncand, kIdle, [&]() -> int {
+        return detect_sync(h, nframes, FrameSrc{nullptr, 0, d_frames}, rows, cols, channels, kDepth8U, cand, capacity, ncand);
+    });
+}
+
+int pbd_detect_typed(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes, int depth_code,
+                     int32_t *cand, int capacity, int *ncand)
+{
+    return entry(h, img && cand && ncand, kIdle, [&]() -> int {
+        return detect_sync(h, 1, FrameSrc{&img, stride_bytes, nullptr}, rows, cols, channels, depth_code, cand, capacity, ncand);
+    });
+}
+
+// what submit() does once the batch has passed check_detect and its frames are (being) made resident at d_frames: the
+// whole path, the candidates' read-back and the slot's completion event, all enqueued on the handle's stream without waiting
+static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, Plan &P, int nframes, const void *d_frames, int channels)
+{
+    if (!S.done.p) HIPCHK(h, hipEventCreateWithFlags(&S.done.p, hipEventDisableTiming));
+    if (int rc = enqueue_detect(h, P, nframes, FrameSrc{nullptr, 0, d_frames}, channels, kDepth8U)) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, P.d_scales.p, S.cb, h->nms, h->stream)) return rc;
+    HIPCHK(h, hipEventRecord(S.done.p, h->stream));
     HIPCHK(h, hipGetLastError());
-    S.plan = P; S.nframes = nframes;
     h->nsubmitted += 1;
     return PBD_OK;
 }
@@ -1999,58 +2004,48 @@ static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, int nframes, const
 int pbd_detect_batch_submit(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int channels,
                             size_t stride_bytes)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !imgs) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, imgs, kBusyOk, [&]() -> int {
         if (h->nsubmitted - h->nwaited >= 2) return fail(h, PBD_ERR_STATE, "two batches are already in flight: call pbd_detect_batch_wait first");
-        if (nframes < 1 || nframes > h->cfg.max_batch)
-            return fail(h, PBD_ERR_INVALID, "nframes %d outside 1..max_batch %d", nframes, h->cfg.max_batch);
-        if (channels != 1 && channels != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", channels);
+        Plan *P = nullptr;
+        if (int rc = check_detect(h, nframes, FrameSrc{imgs, stride_bytes, nullptr}, rows, cols, channels, kDepth8U, &P)) return rc;
         const size_t row_bytes = (size_t)cols * channels, frame_bytes = row_bytes * rows, bytes = frame_bytes * nframes;
-        if (stride_bytes < row_bytes) return fail(h, PBD_ERR_INVALID, "stride %zu < row bytes %zu", stride_bytes, row_bytes);
         pbd_handle::Slot &S = h->slot[h->nsubmitted & 1];
-        if (!h->stream_copy) HIPCHK(h, hipStreamCreateWithFlags(&h->stream_copy, hipStreamNonBlocking));
-        if (!S.copied) HIPCHK(h, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
-        if (S.pinned_cap < bytes) {
-            if (S.pinned) { (void)hipHostFree(S.pinned); S.pinned = nullptr; S.pinned_cap = 0; }
-            HIPCHK(h, hipHostMalloc(&S.pinned, bytes + bytes / 8, hipHostMallocDefault));
-            S.pinned_cap = bytes + bytes / 8;
-        }
+        if (!h->stream_copy.s) HIPCHK(h, h->stream_copy.create());
+        if (!S.copied.p) HIPCHK(h, hipEventCreateWithFlags(&S.copied.p, hipEventDisableTiming));
+        HIPCHK(h, S.pinned.ensure(bytes, bytes + bytes / 8));
         HIPCHK(h, S.frames.ensure(bytes));
         // host staging (this is what overlaps the kernels of the batch submitted before), then one asynchronous copy
         for (int i = 0; i < nframes; ++i) {
-            char *dst = static_cast<char *>(S.pinned) + (size_t)i * frame_bytes;
+            char *dst = S.pinned.as<char>() + (size_t)i * frame_bytes;
             const char *src = static_cast<const char *>(imgs[i]);
             if (stride_bytes == row_bytes) memcpy(dst, src, frame_bytes);
             else for (int y = 0; y < rows; ++y) memcpy(dst + (size_t)y * row_bytes, src + (size_t)y * stride_bytes, row_bytes);
         }
-        HIPCHK(h, hipMemcpyAsync(S.frames.p, S.pinned, bytes, hipMemcpyHostToDevice, h->stream_copy));
-        HIPCHK(h, hipEventRecord(S.copied, h->stream_copy));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, S.copied, 0));
-        return submit_enqueue(h, S, nframes, S.frames.p, rows, cols, channels);
+        HIPCHK(h, hipMemcpyAsync(S.frames.p, S.pinned.p, bytes, hipMemcpyHostToDevice, h->stream_copy));
+        HIPCHK(h, hipEventRecord(S.copied.p, h->stream_copy));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, S.copied.p, 0));
+        return submit_enqueue(h, S, *P, nframes, S.frames.p, channels);
     });
 }
 
 int pbd_detect_batch_device_submit(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int channels)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !d_frames) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, d_frames, kBusyOk, [&]() -> int {
         if (h->nsubmitted - h->nwaited >= 2) return fail(h, PBD_ERR_STATE, "two batches are already in flight: call pbd_detect_batch_wait first");
-        return submit_enqueue(h, h->slot[h->nsubmitted & 1], nframes, d_frames, rows, cols, channels);
+        Plan *P = nullptr;
+        if (int rc = check_detect(h, nframes, FrameSrc{nullptr, 0, d_frames}, rows, cols, channels, kDepth8U, &P)) return rc;
+        return submit_enqueue(h, h->slot[h->nsubmitted & 1], *P, nframes, d_frames, channels);
     });
 }
 
 int pbd_detect_batch_wait(pbd_handle *h, int32_t *cand, int capacity, int *ncand)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !cand || !ncand) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
+    return entry(h, cand && ncand, kBusyOk, [&]() -> int {
         if (h->nsubmitted == h->nwaited) return fail(h, PBD_ERR_STATE, "no batch in flight");
         pbd_handle::Slot &S = h->slot[h->nwaited & 1];
         h->nwaited += 1;                       // the slot is released whatever happens below
-        HIPCHK(h, hipEventSynchronize(S.done));
-        if (!h->stream_d2h) HIPCHK(h, hipStreamCreateWithFlags(&h->stream_d2h, hipStreamNonBlocking));
+        HIPCHK(h, hipEventSynchronize(S.done.p));
+        if (!h->stream_d2h.s) HIPCHK(h, h->stream_d2h.create());
         // (a list longer than the speculative copy is fetched on a stream of its own: the compute stream may already hold
         //  the next batch, whose kernels this copy must not queue behind -- and they do not touch this slot's payload)
         return argmin_deliver(h, S.cb, h->stream_d2h, cand, capacity, ncand);
@@ -2062,16 +2057,13 @@ int pbd_detect_batch_wait(pbd_handle *h, int32_t *cand, int capacity, int *ncand
 int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int channels,
                                 int frame_offset, int32_t *d_payload, int capacity)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !d_frames || !d_payload) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+    return entry(h, d_frames && d_payload, kIdle, [&]() -> int {
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        h->cur_depth = kDepth8U;
+        const FrameSrc src{nullptr, 0, d_frames};
         Plan *P = nullptr;
-        int rc = enqueue_detect(h, nframes, d_frames, rows, cols, channels, &P);
-        if (rc != PBD_OK) return rc;
-        if ((rc = enqueue_argmin_out(h, *P, nframes, frame_offset, d_payload, capacity)) != PBD_OK) return rc;
+        if (int rc = check_detect(h, nframes, src, rows, cols, channels, kDepth8U, &P)) return rc;
+        if (int rc = enqueue_detect(h, *P, nframes, src, channels, kDepth8U)) return rc;
+        if (int rc = enqueue_argmin_out(h, *P, nframes, frame_offset, d_payload, capacity)) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
     });
@@ -2079,88 +2071,50 @@ int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames
 
 int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, int capacity)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !d_payload) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        if (!h->cur || !h->have_dp || h->cur->kind != 0) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
+    return entry(h, d_payload, kIdle, [&]() -> int {
+        const Resident &r = h->res;
+        if (!r.plan || !r.dp || r.plan->kind != 0) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        const int rc = enqueue_argmin_out(h, *h->cur, h->cur_frames, frame_offset, d_payload, capacity);
-        if (rc != PBD_OK) return rc;
+        if (int rc = enqueue_argmin_out(h, *r.plan, r.frames, frame_offset, d_payload, capacity)) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
     });
 }
 
-void *pbd_stream(const pbd_handle *h) { return h ? reinterpret_cast<void *>(h->stream) : nullptr; }
-
-int pbd_detect_batch_device(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int channels,
-                            int32_t *cand, int capacity, int *ncand)
-{
-    return guarded(h, [&]() -> int {
-        if (!h || !d_frames) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        h->cur_depth = kDepth8U;
-        return detect_device(h, nframes, d_frames, rows, cols, channels, cand, capacity, ncand);
-    });
-}
-
-int pbd_detect_typed(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes, int depth_code,
-                     int32_t *cand, int capacity, int *ncand)
-{
-    return guarded(h, [&]() -> int {
-        if (!h || !img || !cand || !ncand) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        if (!depth_size(depth_code))
-            return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth_code);
-        if (channels != 1 && channels != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", channels);
-        h->cur_depth = depth_code;
-        int rc = upload_frames(h, 1, &img, rows, cols, channels, stride_bytes);
-        if (rc != PBD_OK) return rc;
-        return detect_device(h, 1, h->frames.p, rows, cols, channels, cand, capacity, ncand);
-    });
-}
+void *pbd_stream(const pbd_handle *h) { return h ? reinterpret_cast<void *>(h->stream.s) : nullptr; }
 
 int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, size_t dst_bytes)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || !dst) return PBD_ERR_INVALID;
-        if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        (void)hipSetDevice(h->cfg.device);
-        if (!h->cur) return fail(h, PBD_ERR_STATE, "nothing has been computed");
-        Plan &P = *h->cur;
-        if (frame < 0 || frame >= h->cur_frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
+    return entry(h, dst, kIdle, [&]() -> int {
+        const Resident &r = h->res;
+        if (!r.plan) return fail(h, PBD_ERR_STATE, "nothing has been computed");
+        const Plan &P = *r.plan;
+        if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
         const LevelDesc &d = P.lv[level];
-        const size_t hw = (size_t)d.rows * d.cols, cpf = (size_t)P.cell_per_frame;
+        const size_t hw = (size_t)d.rows * d.cols, cell = (size_t)frame * P.cell_per_frame + d.cell_off;
         const void *src = nullptr;
         size_t bytes = 0;
         switch (stage) {
         case PBD_STAGE_FEATURES:
-            if (!h->have_features) return fail(h, PBD_ERR_STATE, "features not computed");
-            src = h->feat.as<char>() + ((size_t)frame * cpf + d.cell_off) * 32 * h->rs; bytes = hw * 32 * h->rs; break;
+            if (!r.features) return fail(h, PBD_ERR_STATE, "features not computed");
+            src = h->feat.as<char>() + cell * 32 * h->rs; bytes = hw * 32 * h->rs; break;
         case PBD_STAGE_RESPONSES:
-            if (!h->have_resp) return fail(h, PBD_ERR_STATE, "responses not computed");
-            src = h->resp.as<char>() + ((size_t)frame * cpf + d.cell_off) * h->F * h->resp_es; bytes = hw * h->F * h->rs; break;
+            if (!r.resp) return fail(h, PBD_ERR_STATE, "responses not computed");
+            src = h->resp.as<char>() + cell * h->F * h->resp_es; bytes = hw * h->F * h->rs; break;
         case PBD_STAGE_ROOTV:
-            if (!h->have_dp) return fail(h, PBD_ERR_STATE, "dp not computed");
-            src = h->rootv.as<char>() + ((size_t)frame * cpf + d.cell_off) * h->NC * h->rs; bytes = hw * h->NC * h->rs; break;
+            if (!r.dp) return fail(h, PBD_ERR_STATE, "dp not computed");
+            src = h->rootv.as<char>() + cell * h->NC * h->rs; bytes = hw * h->NC * h->rs; break;
         case PBD_STAGE_ROOTI:
-            if (!h->have_dp) return fail(h, PBD_ERR_STATE, "dp not computed");
-            src = h->rooti.as<int>() + ((size_t)frame * cpf + d.cell_off) * h->NC; bytes = hw * h->NC * sizeof(int); break;
+            if (!r.dp) return fail(h, PBD_ERR_STATE, "dp not computed");
+            src = h->rooti.as<int>() + cell * h->NC; bytes = hw * h->NC * sizeof(int); break;
         default: return fail(h, PBD_ERR_INVALID, "unknown stage %d", stage);
         }
         if (dst_bytes < bytes) return fail(h, PBD_ERR_INVALID, "destination holds %zu bytes, need %zu", dst_bytes, bytes);
-        if (stage == PBD_STAGE_RESPONSES && h->resp_half && bytes) {     // fp16 on the device -> T = float
-            const size_t n = bytes / sizeof(float);
-            std::vector<uint16_t> halfbuf(n);
-            HIPCHK(h, hipMemcpyAsync(halfbuf.data(), src, n * 2, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            float *out = static_cast<float *>(dst);
-            for (size_t i = 0; i < n; ++i) out[i] = host_h2f(halfbuf[i]);
-            return PBD_OK;
+        if (stage == PBD_STAGE_RESPONSES) {
+            if (int rc = read_responses(h, dst, src, hw * h->F)) return rc;
+        } else if (bytes) {
+            HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
         }
-        if (bytes) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return PBD_OK;
     });
@@ -2168,8 +2122,7 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
 
 int pbd_profile_enable(pbd_handle *h, int on)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
+    return entry(h, true, kBusyOk, [&]() -> int {
         h->prof.flush();
         h->prof.on = on == 2 ? 2 : (on != 0 ? 1 : 0);
         return PBD_OK;
@@ -2177,8 +2130,7 @@ int pbd_profile_enable(pbd_handle *h, int on)
 }
 int pbd_profile_reset(pbd_handle *h)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
+    return entry(h, true, kBusyOk, [&]() -> int {
         h->prof.flush();
         for (int k = 0; k < PBD_K_COUNT; ++k) { h->prof.total[k] = 0; h->prof.launches[k] = 0; }
         return PBD_OK;
@@ -2186,8 +2138,7 @@ int pbd_profile_reset(pbd_handle *h)
 }
 int pbd_profile_read(pbd_handle *h, int k, double *total_ms, int *launches)
 {
-    return guarded(h, [&]() -> int {
-        if (!h || k < 0 || k >= PBD_K_COUNT) return PBD_ERR_INVALID;
+    return entry(h, k >= 0 && k < PBD_K_COUNT, kBusyOk, [&]() -> int {
         h->prof.flush();
         if (total_ms) *total_ms = h->prof.total[k];
         if (launches) *launches = h->prof.launches[k];
@@ -2202,8 +2153,7 @@ const char *pbd_kernel_name(int k)
 }
 int pbd_synchronize(pbd_handle *h)
 {
-    return guarded(h, [&]() -> int {
-        if (!h) return PBD_ERR_INVALID;
+    return entry(h, true, kBusyOk, [&]() -> int {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return PBD_OK;
     });

@@ -895,3 +895,141 @@ def test_narrow_wave_distance_transform(det_mod, oracle):
             assert np.array_equal(np.float32([g.score() for g in got]).view(np.uint32),
                                   np.float32([w["score"] for w in want[name]]).view(np.uint32)), (setting, name)   # signed zeros too
             det.hd.close()
+
+
+def test_refused_calls_keep_the_resident_pyramid(det_mod):
+    """A refused call leaves the handle's resident result as it was.  After an 8-bit pyramid, a 64F image holding a NaN
+    (through pyramid() and through detect(), i.e. pbd_detect_typed) and a 2-channel 16U image are refused; the pyramid
+    images (read as uint8) and the features read back afterwards are still those of the 8-bit pyramid."""
+    from partsbaseddetector_amd import _lib
+    from partsbaseddetector_amd._lib import PbdError
+    det = det_mod.PartsBasedDetector(device=0)
+    det.distributeModel(M.synthetic_tiny_model(thresh=0.5))
+    im = synth.synthetic_frame(3, 96, 128, 3)
+    det.features_.pyramid(im)
+    plan = det.hd.plan(96, 128)
+
+    def resident():
+        imgs = det.features_.level_images(96, 128, 3, np.uint8)
+        feats = [det.hd.get_stage(_lib.STAGE_FEATURES, 0, l, int(r), int(c))
+                 for l, (r, c) in enumerate(zip(plan["feat_rows"], plan["feat_cols"]))]
+        return imgs, feats
+
+    imgs0, feats0 = resident()
+    nan64 = im.astype(np.float64)
+    nan64[40, 77, 1] = np.nan
+    for call, arg in ((det.features_.pyramid, nan64), (det.detect, nan64), (det.features_.pyramid, np.zeros((96, 128, 2), np.uint16))):
+        with pytest.raises(PbdError) as e:
+            call(arg)
+        assert e.value.code == -1, str(e.value)
+    imgs1, feats1 = resident()
+    assert all(np.array_equal(a, b) for a, b in zip(imgs0, imgs1))
+    assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(feats0, feats1))
+    det.hd.close()
+
+
+def test_dp_min_leaves_no_stale_features(det_mod, oracle):
+    """pbd_dp_min starts from the caller's responses on a plan of their sizes: the features of an earlier pyramid are not
+    readable through that plan any more (PBD_ERR_STATE); the responses and root scores it leaves are."""
+    from partsbaseddetector_amd import _lib
+    from partsbaseddetector_amd._lib import PbdError
+    flat = M.synthetic_tiny_model(linear_def=True).flatten()
+    hd = _handle(det_mod, flat)
+    det_mod.HOGFeatures(hd).pyramid(synth.synthetic_frame(3, 96, 128, 3))
+    plan = hd.plan(96, 128)
+    hd.get_stage(_lib.STAGE_FEATURES, 0, 0, int(plan["feat_rows"][0]), int(plan["feat_cols"][0]))
+    rng = np.random.default_rng(8)
+    dims = [(21, 30), (9, 7)]
+    scores = [rng.standard_normal((flat.nfilters, h, w)).astype(np.float32) for h, w in dims]
+    det_mod.DynamicProgram(hd).min(scores)
+    for l, (h, w) in enumerate(dims):
+        with pytest.raises(PbdError) as e:
+            hd.get_stage(_lib.STAGE_FEATURES, 0, l, h, w)
+        assert e.value.code == -5
+        assert np.array_equal(hd.get_stage(_lib.STAGE_RESPONSES, 0, l, h, w).view(np.uint32), scores[l].view(np.uint32))
+        rootv = hd.get_stage(_lib.STAGE_ROOTV, 0, l, h, w)
+        rooti = hd.get_stage(_lib.STAGE_ROOTI, 0, l, h, w)
+        for c in range(flat.ncomponents):
+            _, _, _, orv, ori = oracle.dp_min(flat, c, scores[l])
+            assert np.array_equal(rootv[c].view(np.uint32), orv.view(np.uint32)), (l, c)
+            assert np.array_equal(rooti[c], ori), (l, c)
+    hd.close()
+
+
+def _hip(lib):
+    """the HIP runtime functions the library itself is bound to, looked up through its own dependencies (a test that needs
+    device memory or the device's free memory uses these rather than a second runtime in the same process)"""
+    import ctypes as C
+    for name, args in (("hipMalloc", [C.POINTER(C.c_void_p), C.c_size_t]), ("hipFree", [C.c_void_p]),
+                       ("hipMemcpy", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+                       ("hipMemGetInfo", [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])):
+        getattr(lib, name).argtypes = args
+    return lib
+
+
+def test_synchronous_batches_are_refused_while_a_batch_is_in_flight(det_mod):
+    """pbd_detect_batch and pbd_detect_batch_device refuse (PBD_ERR_STATE) while a submitted batch has not been waited for,
+    before they upload or enqueue anything: the waited batch's records equal those of the synchronous call."""
+    import ctypes as C
+    from partsbaseddetector_amd._lib import PbdError
+    det = det_mod.PartsBasedDetector(device=0, max_batch=4)
+    det.distributeModel(M.synthetic_tiny_model(thresh=0.5))
+    frames = [synth.synthetic_frame(100 + i, 120, 150, 3) for i in range(4)]
+    key = lambda cands: [(c.frame, c.level, c.component, c.root, c.score(), c.parts.tobytes()) for c in cands]
+    want = key(det.detect_batch(frames))
+    assert len(want) > 0
+    hip = _hip(det.hd.lib)
+    packed = np.ascontiguousarray(np.stack(frames))
+    d_frames = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d_frames), packed.nbytes) == 0
+    try:
+        assert hip.hipMemcpy(d_frames, packed.ctypes.data, packed.nbytes, 1) == 0          # hipMemcpyHostToDevice
+        det.submit_batch(frames)
+        with pytest.raises(PbdError) as e:
+            det.detect_batch(frames)
+        assert e.value.code == -5
+        with pytest.raises(PbdError) as e:
+            det.detect_batch_device(d_frames.value, 4, 120, 150, 3)
+        assert e.value.code == -5
+        assert key(det.wait_batch()) == want
+        assert key(det.detect_batch_device(d_frames.value, 4, 120, 150, 3)) == want
+    finally:
+        det.hd.close()
+        hip.hipFree(d_frames)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_handle_churn_returns_device_memory(det_mod, dtype):
+    """Twenty cycles of create -> set_nms -> detect_batch -> a setFilters() that succeeds -> one that fails -> destroy leave
+    the device's free memory where it was after the third cycle, within half of one handle's footprint (the person model
+    at 4 x 240x320, measured in the first cycle)."""
+    import ctypes as C
+    from partsbaseddetector_amd import _lib
+    from partsbaseddetector_amd._lib import PbdError
+    model = M.synthetic_person_model(thresh=17.9)
+    frames = [synth.synthetic_frame(60 + i, 240, 320, 3) for i in range(4)]
+    unsupported = [np.zeros((33, 33 * 32), dtype)]                 # outside the sizes 1..31
+    hip = _hip(_lib.load())
+
+    def free():
+        f, t = C.c_size_t(), C.c_size_t()
+        assert hip.hipMemGetInfo(C.byref(f), C.byref(t)) == 0
+        return f.value
+
+    before = free()
+    footprint = after3 = None
+    for cycle in range(1, 21):
+        det = det_mod.PartsBasedDetector(device=0, max_batch=4, dtype=dtype, nms=0.1)
+        det.distributeModel(model)
+        det.detect_batch(frames)
+        if cycle == 1:
+            footprint = before - free()
+        det.convolution_engine_.setFilters(model.filtersw)
+        with pytest.raises(PbdError) as e:
+            det.convolution_engine_.setFilters(unsupported)
+        assert e.value.code == -2
+        det.hd.close()
+        if cycle == 3:
+            after3 = free()
+    assert footprint > 64 << 20, footprint
+    assert abs(free() - after3) <= footprint // 2, (free(), after3, footprint)
