@@ -4,8 +4,9 @@
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
-//            [--stream HANDLES FRAMES]
+//            [--stream HANDLES FRAMES] [--conv-mode N]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
+//   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -17,14 +18,15 @@
 using namespace pbdhost;
 
 template <typename T>
-static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n)
+static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
+               int conv_mode)
 {
-    PartsBasedDetector<T> pbd;
+    PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
         // the image stream_n times through a FrameStream of stream_k handles: every result must be the first one's
-        FrameStream<T> fs(model, stream_k);
+        FrameStream<T> fs(model, stream_k, 0, 1 << 16, conv_mode);
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         std::vector<Candidate> first, cur;
         size_t got = 0;
@@ -124,18 +126,19 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n]\n");
         return -1;
     }
     bool dbl = false, staged = false;
     float nms = -1.f, dnms = -1.f;
-    int top = 1 << 30, stream_k = 0, stream_n = 0;
+    int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--device-nms") && i + 1 < argc) dnms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
     }
     try {
@@ -145,8 +148,8 @@ int main(int argc, char **argv)
         std::vector<uint8_t> pix;
         Image im;
         if (!readPNM(argv[2], pix, im)) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n);
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

@@ -80,11 +80,15 @@ enum { PBD_CONV_EXACT = 0,   /* multiply and add rounded separately in the refer
                                 ROUNDS THE CALLER'S float scores to fp16 before the dynamic program (exact for scores that
                                 came from pbd_conv_pdf; arbitrary scores lose precision: tests/test_gpu_parity.py::
                                 test_mfma_f16_dp_min_rounds_its_input pins this) */
+enum { PBD_CONV_MFMA_F64 = 4 };  /* fp64 matrix cores (v_mfma_f64_16x16x4_f64), fp64 operands and fp64 accumulation:
+                                responses within fp64 rounding of the reference's summation order (~1e-13 relative),
+                                not bit-identical; every filter size the exact path takes; PBD_REAL_F64 only (pbd_create
+                                refuses it for PBD_REAL_F32 with PBD_ERR_UNSUPPORTED) */
 
 typedef struct pbd_config {
     int device;            /* HIP device ordinal */
     int real_type;         /* PBD_REAL_F32 (src/demo.cpp:85) or PBD_REAL_F64 (cells/detect.cpp:93) */
-    int conv_mode;         /* PBD_CONV_EXACT / PBD_CONV_FMA / PBD_CONV_MFMA / PBD_CONV_MFMA_F16 */
+    int conv_mode;         /* PBD_CONV_EXACT / PBD_CONV_FMA / PBD_CONV_MFMA / PBD_CONV_MFMA_F16 / PBD_CONV_MFMA_F64 */
     int max_batch;         /* frames per pbd_detect_batch* call (>= 1) */
     int max_candidates;    /* candidate capacity per batch */
     void *stream;          /* hipStream_t to run on (NULL: the library creates its own) */

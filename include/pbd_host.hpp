@@ -515,12 +515,16 @@ class PartsBasedDetector {
     std::string name_;
     pbd_handle *h_;
     int device_;
+    int conv_mode_;
     bool nms_;
     float overlap_;
     PartsBasedDetector(const PartsBasedDetector &);
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
-    explicit PartsBasedDetector(int device = 0) : h_(NULL), device_(device), nms_(false), overlap_(0.f) {}
+    // conv_mode: the convolution of every handle distributeModel() creates (PBD_CONV_*, include/pbd.h); new surface, the
+    // reference has only its exact convolution
+    explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT)
+        : h_(NULL), device_(device), conv_mode_(conv_mode), nms_(false), overlap_(0.f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -528,7 +532,7 @@ public:
     {   // src/PartsBasedDetector.cpp:102-127
         pbd_destroy(h_);
         h_ = NULL;
-        h_ = pbdbind::create<HostTraits<T> >(model, device_, PBD_CONV_EXACT, 1, 1 << 18);
+        h_ = pbdbind::create<HostTraits<T> >(model, device_, conv_mode_, 1, 1 << 18);
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         name_ = model.name();
     }
@@ -566,11 +570,13 @@ class FrameStream {
     FrameStream(const FrameStream &);
     FrameStream &operator=(const FrameStream &);
 public:
-    FrameStream(Model &model, int nhandles = 4, int device = 0, int capacity = 1 << 16) : submitted_(0), collected_(0), capacity_(capacity)
+    // conv_mode: the convolution of every handle (PBD_CONV_*, include/pbd.h)
+    FrameStream(Model &model, int nhandles = 4, int device = 0, int capacity = 1 << 16, int conv_mode = PBD_CONV_EXACT)
+        : submitted_(0), collected_(0), capacity_(capacity)
     {
         if (nhandles < 1) throw Error(PBD_ERR_INVALID, "FrameStream needs at least one handle");
         try {
-            for (int i = 0; i < nhandles; ++i) h_.push_back(pbdbind::create<HostTraits<T> >(model, device, PBD_CONV_EXACT, 1, capacity));
+            for (int i = 0; i < nhandles; ++i) h_.push_back(pbdbind::create<HostTraits<T> >(model, device, conv_mode, 1, capacity));
         } catch (...) {      // a later handle failed (out of memory): the earlier ones must not leak
             for (size_t i = 0; i < h_.size(); ++i) pbd_destroy(h_[i]);
             throw;

@@ -18,6 +18,7 @@ STATUS = {0: "PBD_OK", -1: "PBD_ERR_INVALID", -2: "PBD_ERR_UNSUPPORTED", -3: "PB
           -5: "PBD_ERR_STATE", -6: "PBD_ERR_NOMEM"}
 REAL_F32, REAL_F64 = 0, 1
 CONV_EXACT, CONV_FMA, CONV_MFMA, CONV_MFMA_F16 = 0, 1, 2, 3
+CONV_MFMA_F64 = 4          # fp64 matrix cores, REAL_F64 handles only (include/pbd.h)
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
 # options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
 DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3

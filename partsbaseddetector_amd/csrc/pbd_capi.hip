@@ -252,6 +252,7 @@ struct pbd_handle {
         int nunits = 0;
         DevTable<float> c31tab;      // [81][c31stride]: see pbd_kernels_conv.hip (channel 31)
         int c31stride = 0;
+        DevBuf wfrag64;              // PBD_CONV_MFMA_F64: the class's A-fragments (pbd_internal.h, f64_passes)
     };
     std::vector<ConvClass> conv_classes;
     DevBuf d_wrec;                   // bf16 hi/lo weight records of the matrix-core path
@@ -842,6 +843,30 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             HIPCHK(h, C.unit_f0.upload(uf0));
             HIPCHK(h, C.unit_ql.upload(uql));
         }
+        if (h->cfg.conv_mode == PBD_CONV_MFMA_F64) {
+            // A-fragments in the order k_conv_mfma_f64 reads them.  Pass ps (M-tiles [m0, m1)), channel block cb, tap, q-pair qp,
+            // M-tile m, q of the pair e, lane l: filter (m0 + m) * 16 + (l & 15), channel cb * CB + (l >> 4) * QN + qp * QS + e
+            // (lane group g supplies channels g QN .. g QN + QN - 1 of its cell); filters past nf are zero
+            const int QN = conv_mfma_f64_qn(C.K), CB = 4 * QN, QS = std::min(QN, 2), QP = QN / QS;
+            const int mtiles = (C.nf + 15) / 16, passes = f64_passes(mtiles);
+            std::vector<double> wf((size_t)mtiles * 8 * KK * 64, 0.0);
+            size_t o = 0;
+            for (int ps = 0; ps < passes; ++ps) {
+                const int m0 = f64_pass_begin(ps, mtiles, passes), mb = f64_pass_begin(ps + 1, mtiles, passes) - m0;
+                for (int cb = 0; cb < 32 / CB; ++cb)
+                    for (int t = 0; t < KK; ++t)
+                        for (int qp = 0; qp < QP; ++qp)
+                            for (int m = 0; m < mb; ++m)
+                                for (int e = 0; e < QS; ++e)
+                                    for (int l = 0; l < 64; ++l, ++o) {
+                                        const int fl = (m0 + m) * 16 + (l & 15);
+                                        const int c = cb * CB + (l >> 4) * QN + qp * QS + e;
+                                        if (fl < C.nf) wf[o] = (double)static_cast<const R *>(filters[ids[fl]])[(size_t)t * 32 + c];
+                                    }
+            }
+            HIPCHK(h, C.wfrag64.ensure(wf.size() * sizeof(double)));
+            HIPCHK(h, hipMemcpy(C.wfrag64.p, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
     }
     const int Fpad = (nfilters + kConvQ - 1) / kConvQ * kConvQ;
     if (mfma) {
@@ -1234,6 +1259,7 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
         cp.units_per_block = wgs >= 1024 ? std::max(C.nunits, 1) : std::max(1, (int)((long long)C.nunits * wgs / 1024));
         if (h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16)
             launch_conv_mfma(cp, h->d_wrec.p, h->cfg.conv_mode == PBD_CONV_MFMA_F16, nb, st);
+        else if (h->cfg.conv_mode == PBD_CONV_MFMA_F64) launch_conv_mfma_f64(cp, C.wfrag64.as<double>(), nb, st);
         else launch_conv(cp, nb, h->f64, st);
     }
 }
@@ -1685,6 +1711,8 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
         *out = nullptr;
         if (config->real_type != PBD_REAL_F32 && config->real_type != PBD_REAL_F64)
             return fail(nullptr, PBD_ERR_UNSUPPORTED, "real_type %d: PBD_REAL_F32 or PBD_REAL_F64", config->real_type);
+        if (config->conv_mode == PBD_CONV_MFMA_F64 && config->real_type != PBD_REAL_F64)
+            return fail(nullptr, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA_F64 needs PBD_REAL_F64 (fp64 operands and accumulation)");
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev < 1)

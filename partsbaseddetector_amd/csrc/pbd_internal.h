@@ -303,6 +303,17 @@ int conv_mfma_occupancy(bool f16);
 // PBD_CONV_MFMA_F16: 80 B fp16 records, one MFMA per product tile
 void launch_conv_mfma(const ConvParams &p, const void *wrec, bool f16, int nframes, hipStream_t s);
 constexpr int kMfmaFilterBlock = 160, kMfmaRecBytes = 144, kMfmaRecBytesF16 = 80;
+// PBD_CONV_MFMA_F64 (pbd_kernels_conv_mfma_f64.hip).  A size class of nf filters is ceil(nf / 16) M-tiles, split into
+// f64_passes() passes (grid y) of at most kF64MaxMB M-tiles; pass i covers M-tiles [f64_pass_begin(i), f64_pass_begin(i + 1)).
+// wfrag: the class's A-fragments, [pass][channel block][tap][q-pair][M-tile of the pass][q of the pair][lane] doubles
+// (upload_filters_t); the channel block of a filter size is conv_mfma_f64_qn(): 4 * qn channels per block
+constexpr int kF64MaxMB = 4;
+constexpr size_t kF64LdsTarget = 80 * 1024;   // haloed tile per workgroup: two workgroups per CU (160 KB of LDS)
+inline int f64_passes(int mtiles) { return (mtiles + kF64MaxMB - 1) / kF64MaxMB; }
+__host__ __device__ inline int f64_pass_begin(int pass, int mtiles, int passes) { return pass * mtiles / passes; }
+int conv_mfma_f64_qn(int ksize);
+size_t conv_mfma_f64_lds(int ksize, int qn);
+void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes, hipStream_t s);
 // the distance-transform passes' launch choices a handle may force (pbd_debug_set_option); the defaults decide per launch
 struct DtOptions {
     int lane_shift = -1;          // 0..6: 64 >> lane_shift rows (columns) per wave; -1: by the launch's size
