@@ -11,6 +11,8 @@ from scipy import signal
 from partsbaseddetector_amd import model as M
 from partsbaseddetector_amd import synth
 
+import dt_hard_planes as H
+
 
 # ---------------------------------------------------------------------------------- geometry
 def test_pyramid_plan_matches_survey_appendix_b(oracle):
@@ -255,6 +257,51 @@ def test_dt_against_brute_force(oracle, seed, shape, w, os):
     quirk = np.take_along_axis(iyr, Ix, axis=1)
     assert np.mean(Iy == quirk) > 0.98
     assert Ix.min() >= 0 and Ix.max() < shape[1] and Iy.min() >= 0 and Iy.max() < shape[0]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("kind", ["constant", "quantised", "spikes"])
+@pytest.mark.parametrize("shape,w,os", [((9, 40), (0.25, 0.0, 0.015625, 0.0), (0, 0)),
+                                        ((33, 17), (0.015625, 0.5, 0.25, 0.0), (3, -2)),
+                                        ((3, 300), (0.0625, -0.25, 0.0625, 0.125), (-4, 1)),
+                                        ((70, 2), (0.25, 0.0, 0.0625, -0.5), (1, 4)),
+                                        ((1, 65), (0.015625, 0.0, 0.015625, 0.0), (2, 0))])
+def test_dt_exact_on_hard_planes(oracle, kind, shape, w, os, dtype):
+    """The planes that drive the GPU transforms into deep envelopes, long pop runs and exact ties (tests/dt_hard_planes.py), with
+    power-of-two coefficients: every intermediate value is exact, so the oracle's transform equals the O(N^2) maximum bit for
+    bit, and each pointer attains it -- the row pointer the row maximum, the column pointer (IyRaw[m][Ix[m][n]], the reference's
+    composition) the maximum of the column it was read from.  Which of several equal maxima is returned is the envelope's
+    choice, so the indices are not compared with the brute force's argmax."""
+    rng = np.random.default_rng(len(kind) * 7 + shape[0])
+    score = (H.plane(kind, rng, *shape) if kind != "quantised" else rng.integers(-3, 4, shape) * 0.25).astype(dtype)
+    ax, bx, ay, by = (-float(np.float32(v)) for v in w)
+    out, Ix, Iy = oracle.dt(score, ax, bx, ay, by, os[0], os[1])
+    ref, _, _ = _dt_brute(score, ax, bx, ay, by, os[0], os[1])
+    assert np.array_equal(out, ref.astype(dtype))
+    M_, N_ = shape
+    m, n = np.mgrid[0:M_, 0:N_]
+    dx = (os[0] + n - Ix).astype(np.float64)
+    row_at_ptr = ax * dx * dx + bx * dx + score.astype(np.float64)[m, Ix]
+    row_max = (ax * (os[0] + n[:, :, None] - np.arange(N_)) ** 2 + bx * (os[0] + n[:, :, None] - np.arange(N_))
+               + score.astype(np.float64)[:, None, :]).max(axis=2)
+    assert np.array_equal(row_at_ptr, row_max)
+    dy = (os[1] + m - Iy).astype(np.float64)
+    col_at_ptr = ay * dy * dy + by * dy + row_max[Iy, Ix]                 # column Ix[m][n], source row Iy[m][n]
+    assert np.array_equal(col_at_ptr, ref[m, Ix])                         # the maximum of that column at output row m
+    _, ptr, st = H.replay_rows(score, ax, bx, os[0], dtype)
+    assert np.array_equal(ptr, Ix)                                        # the replay the GPU tests measure with is computeRow
+
+
+def test_hard_planes_reach_deep_envelopes_and_ties(oracle):
+    """The replay's statistics on the planes the GPU tests use: constant rows keep every element (depth = N), spikes pop more
+    than a cooperative window at once, quantised planes with a power-of-two quadratic tie exactly in both comparisons."""
+    rng = np.random.default_rng(4)
+    _, _, st = H.replay_rows(H.plane("constant", rng, 2, 600), -0.01, -0.0, 0)
+    assert st["depth"].min() == 600 and st["maxpop"].max() == 0
+    _, _, st = H.replay_rows(H.plane("spikes", rng, 8, 256), -0.01, -0.0, 0)
+    assert st["maxpop"].max() >= 16
+    _, _, st = H.replay_rows(rng.integers(-3, 4, (8, 64)).astype(np.float32), -0.25, -0.0, 1)
+    assert st["scan_tie"].any() and st["read_tie"].any()
 
 
 def test_dt_quirk_differs_from_true_argmax(oracle):
