@@ -4,9 +4,11 @@
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
-//            [--stream HANDLES FRAMES] [--conv-mode N]
+//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
+//   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
+//           in ONE detectBatch call, and each image's candidates are printed, in order, as a single run prints them
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -16,6 +18,38 @@
 #include "pbd_host.hpp"
 
 using namespace pbdhost;
+
+// what a run prints for one image's candidates (the reference's demo: count, sort, optional NMS, the best ones)
+static void report(std::vector<Candidate> &candidates, const Image &im, bool staged, float nms, float dnms, int top)
+{
+    std::printf("Number of candidates: %zu\n", candidates.size());
+    if (dnms >= 0 && !staged) std::printf("After device NMS: %zu\n", candidates.size());   // already sorted (stably) and suppressed
+    else Candidate::sort(candidates);
+    if (nms >= 0) {
+        Candidate::nonMaximaSuppression(im.rows, im.cols, candidates, nms);
+        std::printf("After NMS: %zu\n", candidates.size());
+    }
+    for (size_t i = 0; i < candidates.size() && (int)i < top; ++i) {
+        const Candidate &c = candidates[i];
+        std::printf("cand %d %d %d %d %.9g", c.level, c.component(), c.root_y, c.root_x, (double)c.score());
+        for (size_t p = 0; p < c.parts().size(); ++p)
+            std::printf(" %d,%d,%d,%d", c.parts()[p].x, c.parts()[p].y, c.parts()[p].width, c.parts()[p].height);
+        std::printf("\n");
+    }
+}
+
+// the first image and the --also images through one detectBatch call; one report per image, in order
+template <typename T>
+static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, float nms, float dnms, int top, int conv_mode)
+{
+    PartsBasedDetector<T> pbd(0, conv_mode, (int)ims.size());
+    if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
+    pbd.distributeModel(model);
+    std::vector<std::vector<Candidate> > candidates;
+    pbd.detectBatch(ims, candidates);
+    for (size_t i = 0; i < ims.size(); ++i) report(candidates[i], ims[i], false, nms, dnms, top);
+    return 0;
+}
 
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
@@ -73,20 +107,7 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         pbd.distributeModel(model);
         pbd.detect(im, candidates);
     }
-    std::printf("Number of candidates: %zu\n", candidates.size());
-    if (dnms >= 0 && !staged) std::printf("After device NMS: %zu\n", candidates.size());   // already sorted (stably) and suppressed
-    else Candidate::sort(candidates);
-    if (nms >= 0) {
-        Candidate::nonMaximaSuppression(im.rows, im.cols, candidates, nms);
-        std::printf("After NMS: %zu\n", candidates.size());
-    }
-    for (size_t i = 0; i < candidates.size() && (int)i < top; ++i) {
-        const Candidate &c = candidates[i];
-        std::printf("cand %d %d %d %d %.9g", c.level, c.component(), c.root_y, c.root_x, (double)c.score());
-        for (size_t p = 0; p < c.parts().size(); ++p)
-            std::printf(" %d,%d,%d,%d", c.parts()[p].x, c.parts()[p].y, c.parts()[p].width, c.parts()[p].height);
-        std::printf("\n");
-    }
+    report(candidates, im, staged, nms, dnms, top);
     return 0;
 }
 
@@ -126,12 +147,13 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]...\n");
         return -1;
     }
     bool dbl = false, staged = false;
     float nms = -1.f, dnms = -1.f;
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
+    std::vector<const char *> also;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
@@ -140,6 +162,11 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
+        else if (!std::strcmp(argv[i], "--also") && i + 1 < argc) also.push_back(argv[++i]);
+    }
+    if (!also.empty() && (staged || stream_k > 0)) {
+        std::fprintf(stderr, "--also runs one detectBatch call: not with --staged or --stream\n");
+        return -1;
     }
     try {
         FileStorageModel model;
@@ -148,6 +175,15 @@ int main(int argc, char **argv)
         std::vector<uint8_t> pix;
         Image im;
         if (!readPNM(argv[2], pix, im)) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
+        if (!also.empty()) {
+            std::vector<std::vector<uint8_t> > pixels(also.size() + 1);
+            std::vector<Image> ims(also.size() + 1);
+            pixels[0].swap(pix);
+            ims[0] = im;
+            for (size_t k = 0; k < also.size(); ++k)
+                if (!readPNM(also[k], pixels[k + 1], ims[k + 1])) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
+            return dbl ? run_batch<double>(model, ims, nms, dnms, top, conv_mode) : run_batch<float>(model, ims, nms, dnms, top, conv_mode);
+        }
         return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode)
                    : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode);
     } catch (const Error &e) {

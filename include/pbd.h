@@ -191,7 +191,7 @@ int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacit
 int pbd_detect(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes,
                int32_t *cand, int capacity, int *ncand);
 /* The same for an image of any accepted depth (depth_code as in pbd_features_pyramid); pbd_detect is depth_code 0.
- * The batch entry points take 8-bit frames. */
+ * The equal-size batch entry points take 8-bit frames; pbd_detect_frames* (below) take every depth. */
 int pbd_detect_typed(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes,
                      int depth_code, int32_t *cand, int capacity, int *ncand);
 /* New surface (the reference has no batch API): nframes equally-sized frames, results identical to
@@ -231,6 +231,36 @@ int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames
 int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, int capacity);
 /* the hipStream_t every kernel of this handle runs on (pbd_config.stream, or the library's own) */
 void *pbd_stream(const pbd_handle *h);
+
+/* ---- frames of different sizes in one call (new surface, as the batch API).
+ * A frame: `data` is a host pointer (pbd_detect_frames) or a device pointer (the _device forms), rows x cols pixels of
+ * `channels` interleaved values of the call's depth, rows `stride_bytes` apart (>= cols * channels * element size).  A
+ * _device frame may be a REGION of a larger device image -- its first pixel, and that image's pitch as stride_bytes: it is
+ * read in place, without a copy, and gives what pbd_detect gives on the cropped image (boxes in the region's coordinates).
+ * A _device frame's pointer and stride_bytes are multiples of the element size (2, 4 or 8 bytes for 16U / 32F / 64F).
+ * Result: exactly the records of nframes separate pbd_detect_typed calls, one per frame, concatenated; `frame` = index in the
+ * call (+ frame_offset for _device_out), order (frame, level, component, root_y, root_x), `level` = level of that frame's own
+ * pyramid.  One `channels` (1 or 3) and one depth_code (as pbd_features_pyramid; all four for every form) per call.
+ * nframes <= max_batch, PBD_ERR_CAPACITY, payload word 0, pbd_set_nms (each frame within its own Rect(0, 0, cols, rows)) and
+ * the NaN / Inf refusal of host 32F / 64F frames (naming the frame) behave as in the batch calls above.  A frame too small to
+ * plan or with a pitch below its row size is PBD_ERR_INVALID, naming its index, before anything is enqueued.  With level
+ * sharding on (world > 1): PBD_ERR_UNSUPPORTED; while a batch is in flight: PBD_ERR_STATE.
+ * After a mixed call, pbd_get_stage / pbd_get_pyramid_image address (frame in the call, level of that frame's pyramid),
+ * pbd_argmin_device_out re-emits the mixed list, and pbd_dp_argmin (DynamicProgram::argmin over ONE image's scales) returns
+ * PBD_ERR_STATE.  There is no pipelined _submit / _wait form for mixed frames. */
+typedef struct pbd_frame {
+    const void *data;
+    int rows, cols;
+    size_t stride_bytes;
+} pbd_frame;
+int pbd_detect_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code,
+                      int32_t *cand, int capacity, int *ncand);
+/* the same for frames in device memory; cand is a HOST buffer */
+int pbd_detect_frames_device(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code,
+                             int32_t *cand, int capacity, int *ncand);
+/* the same with the list left on the device in the caller's payload, asynchronous (as pbd_detect_batch_device_out) */
+int pbd_detect_frames_device_out(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code,
+                                 int frame_offset, int32_t *d_payload, int capacity);
 
 /* ---- staged read-back of the last pbd_detect* call (tests, profiling) ----
  * A stage is readable only if the last computation produced it: after pbd_conv_set_filters the responses and DP

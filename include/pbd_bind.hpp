@@ -285,5 +285,37 @@ inline void detect(pbd_handle *h, const typename Tr::Image &im, std::vector<type
     unpack_candidates<Tr>(h, buf, n, candidates);
 }
 
+// Frames of any sizes in one call (new surface: pbd_detect_frames; the reference has no batch API): candidates[i] receives
+// what detect(images[i]) gives.  The images share one depth and one channel count; any accepted depth.
+template <class Tr>
+inline void detect_batch(pbd_handle *h, const std::vector<typename Tr::Image> &images,
+                         std::vector<std::vector<typename Tr::Candidate> > &candidates, int capacity)
+{
+    const size_t nf = images.size();
+    candidates.assign(nf, std::vector<typename Tr::Candidate>());
+    if (nf == 0) return;
+    std::vector<pbd_frame> frames(nf);
+    for (size_t i = 0; i < nf; ++i) {
+        const typename Tr::Image &im = images[i];
+        if (Tr::img_channels(im) != Tr::img_channels(images[0]) || Tr::img_depth(im) != Tr::img_depth(images[0]))
+            Tr::fail(PBD_ERR_INVALID, "pbd: detect_batch: every image of one call has the first image's depth and channel count");
+        frames[i].data = Tr::img_data(im);
+        frames[i].rows = Tr::img_rows(im);
+        frames[i].cols = Tr::img_cols(im);
+        frames[i].stride_bytes = Tr::img_step(im);
+    }
+    std::vector<int32_t> buf((size_t)capacity * pbd_candidate_stride(h) + 1);
+    int n = 0;
+    check<Tr>(h, pbd_detect_frames(h, (int)nf, &frames[0], Tr::img_channels(images[0]), Tr::img_depth(images[0]), &buf[0], capacity,
+                                   &n));
+    const int stride = pbd_candidate_stride(h);
+    for (int i = 0; i < n; ++i) {
+        const int32_t *r = &buf[(size_t)i * stride];
+        pbd_candidate_hdr hd;
+        for (int w = 0; w < 8; ++w) reinterpret_cast<int32_t *>(&hd)[w] = r[w];
+        Tr::candidate(candidates[hd.frame], hd, r + 8);
+    }
+}
+
 }  // namespace pbdbind
 #endif  // PBD_BIND_HPP_

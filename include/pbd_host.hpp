@@ -516,6 +516,7 @@ class PartsBasedDetector {
     pbd_handle *h_;
     int device_;
     int conv_mode_;
+    int max_batch_;
     bool nms_;
     float overlap_;
     PartsBasedDetector(const PartsBasedDetector &);
@@ -523,8 +524,9 @@ class PartsBasedDetector {
 public:
     // conv_mode: the convolution of every handle distributeModel() creates (PBD_CONV_*, include/pbd.h); new surface, the
     // reference has only its exact convolution
-    explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT)
-        : h_(NULL), device_(device), conv_mode_(conv_mode), nms_(false), overlap_(0.f) {}
+    // max_batch: the most images one detectBatch() call takes
+    explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
+        : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -532,7 +534,7 @@ public:
     {   // src/PartsBasedDetector.cpp:102-127
         pbd_destroy(h_);
         h_ = NULL;
-        h_ = pbdbind::create<HostTraits<T> >(model, device_, conv_mode_, 1, 1 << 18);
+        h_ = pbdbind::create<HostTraits<T> >(model, device_, conv_mode_, max_batch_, 1 << 18);
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         name_ = model.name();
     }
@@ -551,6 +553,12 @@ public:
     {
         if (!h_) throw Error(PBD_ERR_STATE, "detect() before distributeModel()");
         pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
+    }
+    // new surface: images of any sizes (one depth, one channel count) in one call; candidates[i] = detect(images[i])
+    void detectBatch(const std::vector<Image> &images, std::vector<std::vector<Candidate> > &candidates)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "detectBatch() before distributeModel()");
+        pbdbind::detect_batch<HostTraits<T> >(h_, images, candidates, 1 << 18);
     }
 };
 

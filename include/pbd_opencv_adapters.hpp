@@ -121,4 +121,12 @@ inline void hipDetect(pbd_handle *h, const cv::Mat &im, vectorCandidate &candida
     pbdbind::detect<CvTraits<T> >(h, im, candidates, 1 << 16);
 }
 
+// detect() of several images of any sizes (one depth, one channel count) in one call: candidates[i] = detect(images[i]).
+// The handle takes up to its max_batch images (Handle's constructor).  PartsBasedDetector<T>::detectBatch is this call.
+template <typename T>
+inline void hipDetectBatch(pbd_handle *h, const vectorMat &images, std::vector<vectorCandidate> &candidates)
+{
+    pbdbind::detect_batch<CvTraits<T> >(h, images, candidates, 1 << 18);
+}
+
 }  // namespace pbd_adapters

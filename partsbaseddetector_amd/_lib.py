@@ -34,7 +34,7 @@ SYMBOLS = [
     "pbd_num_ptr_slots", "pbd_ptr_slot", "pbd_dp_min", "pbd_dp_argmin", "pbd_detect", "pbd_detect_batch",
     "pbd_detect_batch_device", "pbd_detect_typed", "pbd_detect_batch_submit", "pbd_detect_batch_wait",
     "pbd_detect_batch_device_submit", "pbd_detect_batch_device_out", "pbd_argmin_device_out", "pbd_stream", "pbd_get_stage", "pbd_profile_enable", "pbd_profile_reset", "pbd_profile_read",
-    "pbd_kernel_name", "pbd_synchronize",
+    "pbd_kernel_name", "pbd_synchronize", "pbd_detect_frames", "pbd_detect_frames_device", "pbd_detect_frames_device_out",
 ]
 
 
@@ -56,6 +56,19 @@ class CModel(C.Structure):
         ("biasid", C.POINTER(C.c_int)), ("defid", C.POINTER(C.c_int)),
         ("thresh", C.c_float), ("sbin", C.c_int), ("interval", C.c_int), ("norient", C.c_int),
     ]
+
+
+class CFrame(C.Structure):
+    """pbd_frame: one frame of a mixed-size call (host pointer, or device pointer for the _device forms)."""
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("stride_bytes", C.c_size_t)]
+
+
+def frame_array(descs):
+    """(pbd_frame[]) from (pointer, rows, cols, stride_bytes) tuples."""
+    arr = (CFrame * len(descs))()
+    for i, (p, r, c, st) in enumerate(descs):
+        arr[i].data, arr[i].rows, arr[i].cols, arr[i].stride_bytes = p, r, c, st
+    return arr
 
 
 class CConfig(C.Structure):
@@ -116,6 +129,12 @@ def load():
     lib.pbd_detect_batch_device_submit.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.pbd_detect_batch_device_out.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.pbd_argmin_device_out.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.pbd_detect_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_detect_frames_device.argtypes = lib.pbd_detect_frames.argtypes
+    lib.pbd_detect_frames_device_out.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_int]
+    lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]
     lib.pbd_stream.restype = C.c_void_p
     lib.pbd_get_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

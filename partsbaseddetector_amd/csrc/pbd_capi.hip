@@ -164,6 +164,37 @@ struct Plan {
     DevTable<long long> d_stk_row_off, d_stk_col_off;
     long long stk_per_jf = 0;
     DevTable<float> d_scales;
+    // host copies of the resize tables (image plans): mixed plans are assembled from them
+    std::vector<ResizeTabX> htabx;
+    std::vector<ResizeTabY> htaby;
+    std::vector<ResizeTabXf> htabxf;
+    std::vector<ResizeTabYf> htabyf;
+
+    // ---- kind 2: a mixed-size call planned as ONE virtual frame whose level table is the frames' own pyramids, concatenated
+    // frame-major (key_dims = rows, cols of every frame in call order).  Every stage after the pyramid runs over it unchanged.
+    int mixed_frames = 0;
+    std::vector<int> lv_frame, lv_local;    // per virtual level: frame of the call, level of that frame's pyramid
+    std::vector<int> frame_lv0;             // [mixed_frames + 1] first virtual level of each frame
+    DevTable<int> d_lv_frame, d_lv_local;
+    // pyramid launches: launch 0 = every frame's resized levels, launch k >= 1 = octave k of every frame; launch k's levels are
+    // run_lev[lev0[k] ..], its n[k] + 1 pixel offsets run_off[off0[k] ..]
+    std::vector<int> run_lev, run_lev0, run_n;
+    std::vector<long long> run_off, run_off0, run_npix;
+    DevTable<int> d_run_lev;
+    DevTable<long long> d_run_off;
+    // post-processing: per frame {rows, cols}, global-canvas word offset; the frames of each canvas kind
+    std::vector<int2> fdim;
+    std::vector<long long> fcanvas;
+    std::vector<int> post_lds, post_glb;
+    size_t post_lds_words = 0, post_glb_words = 0;
+    DevTable<int2> d_fdim;
+    DevTable<long long> d_fcanvas;
+    DevTable<int> d_post_lds, d_post_glb;
+    // dynamic program in groups of whole frames when the virtual frame's scratch exceeds the budget: sub-plans whose cell
+    // offsets start at 0 (cell0 = the group's first cell in the virtual frame), built for `chunk_budget`
+    size_t chunk_budget = 0;
+    std::vector<std::unique_ptr<Plan>> chunk_plans;
+    std::vector<long long> chunk_cell0;
 };
 
 struct Group {   // DT jobs of the parts of one tree depth + combine jobs of their parents
@@ -282,6 +313,10 @@ struct pbd_handle {
     DevBuf tmp, dt, IxRaw, IyRaw, stk, scales_tmp, find_blk;
     DevBuf post_ws;                  // workspace of the post-processing stage (pbd_kernels_post.hip)
     DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
+    // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
+    HostBuf fd_host;
+    DevBuf fd_dev;
+    Event fd_copied;
 
     // A candidate list on its way out.  The device side is the "payload" the find / walk kernels write: word 0 = roots
     // found, then the records, already in (frame, level, component, y, x) order.  The host side is a pinned mirror: the
@@ -543,19 +578,22 @@ void cache_plan(pbd_handle *h, std::unique_ptr<Plan> P)
     }
 }
 
-int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
+// The host side of an image plan (no device work): level table, scales and resize tables of an unsharded rows x cols frame.
+// PBD_OK, or PBD_ERR_INVALID with the reason in `err`.
+int image_plan_host(int rows, int cols, int sbin, int interval, Plan &Pr, std::string &err)
 {
-    for (auto &p : h->plans)
-        if (p->kind == 0 && p->rows == rows && p->cols == cols) { *out = p.get(); return PBD_OK; }
+    Plan *P = &Pr;
+    char buf[160];
     std::vector<int> lr, lc;
     std::vector<float> scales;
-    const int n = plan_pyramid(rows, cols, h->sbin, h->interval, lr, lc, scales);
-    if (n <= 0)
-        return fail(h, PBD_ERR_INVALID, "frame %dx%d too small for sbin %d / interval %d (nscales %d)", rows, cols,
-                    h->sbin, h->interval, n);
-    auto P = std::make_unique<Plan>();
+    const int n = plan_pyramid(rows, cols, sbin, interval, lr, lc, scales);
+    if (n <= 0) {
+        snprintf(buf, sizeof buf, "frame %dx%d too small for sbin %d / interval %d (nscales %d)", rows, cols, sbin, interval, n);
+        err = buf;
+        return PBD_ERR_INVALID;
+    }
     P->kind = 0; P->rows = rows; P->cols = cols;
-    P->nlevels = n; P->scales = scales; P->interval = h->interval;
+    P->nlevels = n; P->scales = scales; P->interval = interval;
     P->lv.resize(n);
     std::vector<ResizeTabX> tabx;
     std::vector<ResizeTabY> taby;
@@ -565,19 +603,23 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
     for (int l = 0; l < n; ++l) {
         LevelDesc &d = P->lv[l];
         d.img_rows = lr[l]; d.img_cols = lc[l];
-        if (d.img_rows < 4 || d.img_cols < 4) return fail(h, PBD_ERR_INVALID, "pyramid level %d is %dx%d", l, lr[l], lc[l]);
-        d.blk_cols = (int)roundf((float)lc[l] / (float)h->sbin);   // HOGFeatures.cpp:174
-        d.blk_rows = (int)roundf((float)lr[l] / (float)h->sbin);
+        if (d.img_rows < 4 || d.img_cols < 4) {
+            snprintf(buf, sizeof buf, "pyramid level %d is %dx%d", l, lr[l], lc[l]);
+            err = buf;
+            return PBD_ERR_INVALID;
+        }
+        d.blk_cols = (int)roundf((float)lc[l] / (float)sbin);   // HOGFeatures.cpp:174
+        d.blk_rows = (int)roundf((float)lr[l] / (float)sbin);
         d.cols = std::max(d.blk_cols - 2, 0);
         d.rows = std::max(d.blk_rows - 2, 0);
-        d.src_level = l >= h->interval ? l - h->interval : -1;
+        d.src_level = l >= interval ? l - interval : -1;
         d.img_off = pix; d.blk_off = blk; d.cell_off = cell;
         d.tab_x = d.tab_y = 0;
         pix += (long long)lr[l] * lc[l];
         blk += (long long)d.blk_rows * d.blk_cols;
         cell += (long long)d.rows * d.cols;
-        if (l == h->interval - 1) P->npix_resized = pix;
-        if (l < h->interval) {
+        if (l == interval - 1) P->npix_resized = pix;
+        if (l < interval) {
             // cv::resize INTER_LINEAR 8U coefficient tables (OpenCV imgwarp.cpp)
             const double scale_x = 1. / ((double)lc[l] / cols), scale_y = 1. / ((double)lr[l] / rows);
             d.tab_x = (int)tabx.size();
@@ -602,41 +644,15 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
             }
         }
     }
-    if (h->shard_world > 1) {
-        // Level sharding (SURVEY 8e, secondary partitioning): levels are independent through HOG, convolution and DP, so
-        // one frame can be split over GPUs by giving each a subset of the levels.  Longest-processing-time assignment
-        // over the cell counts (level 0 alone is 13 % of a VGA frame): levels by decreasing size, each to the rank
-        // with the least work so far.  Levels of other ranks keep their pyramid image here (a pyrDown chain may run
-        // through them) but get empty block / feature maps, so every later stage skips them.
-        std::vector<int> order(n);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            return (long long)P->lv[a].rows * P->lv[a].cols > (long long)P->lv[b].rows * P->lv[b].cols;
-        });
-        std::vector<long long> load(h->shard_world, 0);
-        std::vector<int> owner(n, 0);
-        for (int l : order) {
-            const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            owner[l] = r;
-            load[r] += (long long)P->lv[l].rows * P->lv[l].cols;
-        }
-        blk = 0; cell = 0;
-        for (int l = 0; l < n; ++l) {
-            LevelDesc &d = P->lv[l];
-            if (owner[l] != h->shard_rank) d.blk_rows = d.blk_cols = d.rows = d.cols = 0;
-            d.blk_off = blk; d.cell_off = cell;
-            blk += (long long)d.blk_rows * d.blk_cols;
-            cell += (long long)d.rows * d.cols;
-        }
-    }
     P->pix_per_frame = pix; P->blk_per_frame = blk; P->cell_per_frame = cell;
     if (P->npix_resized == 0) P->npix_resized = pix;
-    HIPCHK(h, P->d_tabx.upload(tabx));
-    HIPCHK(h, P->d_taby.upload(taby));
-    HIPCHK(h, P->d_tabxf.upload(tabxf));
-    HIPCHK(h, P->d_tabyf.upload(tabyf));
-    HIPCHK(h, finish_plan_tables(*P, h->sbin));
-    // HOG coordinate table grows with the largest frame seen
+    P->htabx = std::move(tabx); P->htaby = std::move(taby); P->htabxf = std::move(tabxf); P->htabyf = std::move(tabyf);
+    return PBD_OK;
+}
+
+// the HOG coordinate table grows with the largest frame seen
+int grow_coord(pbd_handle *h, int rows, int cols)
+{
     const int need = std::max(rows, cols) + 4 * h->sbin + 8;
     if (need > h->coord_n) {
         // HOGFeatures.cpp:252-259: yp = ((T)y+0.5)/(T)sbin - 0.5; iyp = floor(yp); vy0 = yp-iyp; vy1 = 1.0-vy0
@@ -664,6 +680,54 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
         }
         h->coord_n = need;
     }
+    return PBD_OK;
+}
+
+int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
+{
+    for (auto &p : h->plans)
+        if (p->kind == 0 && p->rows == rows && p->cols == cols) { *out = p.get(); return PBD_OK; }
+    auto P = std::make_unique<Plan>();
+    {
+        std::string err;
+        if (int rc = image_plan_host(rows, cols, h->sbin, h->interval, *P, err)) return fail(h, rc, "%s", err.c_str());
+    }
+    const int n = P->nlevels;
+    long long blk = P->blk_per_frame, cell = P->cell_per_frame;
+    if (h->shard_world > 1) {
+        // Level sharding (SURVEY 8e, secondary partitioning): levels are independent through HOG, convolution and DP, so
+        // one frame can be split over GPUs by giving each a subset of the levels.  Longest-processing-time assignment
+        // over the cell counts (level 0 alone is 13 % of a VGA frame): levels by decreasing size, each to the rank
+        // with the least work so far.  Levels of other ranks keep their pyramid image here (a pyrDown chain may run
+        // through them) but get empty block / feature maps, so every later stage skips them.
+        std::vector<int> order(n);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+            return (long long)P->lv[a].rows * P->lv[a].cols > (long long)P->lv[b].rows * P->lv[b].cols;
+        });
+        std::vector<long long> load(h->shard_world, 0);
+        std::vector<int> owner(n, 0);
+        for (int l : order) {
+            const int r = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+            owner[l] = r;
+            load[r] += (long long)P->lv[l].rows * P->lv[l].cols;
+        }
+        blk = 0; cell = 0;
+        for (int l = 0; l < n; ++l) {
+            LevelDesc &d = P->lv[l];
+            if (owner[l] != h->shard_rank) d.blk_rows = d.blk_cols = d.rows = d.cols = 0;
+            d.blk_off = blk; d.cell_off = cell;
+            blk += (long long)d.blk_rows * d.blk_cols;
+            cell += (long long)d.rows * d.cols;
+        }
+    }
+    P->blk_per_frame = blk; P->cell_per_frame = cell;
+    HIPCHK(h, P->d_tabx.upload(P->htabx));
+    HIPCHK(h, P->d_taby.upload(P->htaby));
+    HIPCHK(h, P->d_tabxf.upload(P->htabxf));
+    HIPCHK(h, P->d_tabyf.upload(P->htabyf));
+    HIPCHK(h, finish_plan_tables(*P, h->sbin));
+    if (int rc = grow_coord(h, rows, cols)) return rc;
     *out = P.get();
     cache_plan(h, std::move(P));
     return PBD_OK;
@@ -695,6 +759,123 @@ int get_dims_plan(pbd_handle *h, int nlevels, const int *rows, const int *cols, 
     HIPCHK(h, finish_plan_tables(*P, h->sbin));
     *out = P.get();
     cache_plan(h, std::move(P));
+    return PBD_OK;
+}
+
+// ---- mixed-size plans ----------------------------------------------------------------------------
+// Appends frame Q (an unsharded image plan) to the virtual frame M: its levels, scales and resize tables, with every offset
+// shifted past the frames already in M.  Host only.
+void mixed_append(Plan &M, const Plan &Q)
+{
+    const int lv0 = M.nlevels, f = M.mixed_frames;
+    const int tx0 = (int)M.htabx.size(), ty0 = (int)M.htaby.size();
+    if (M.frame_lv0.empty()) M.frame_lv0.push_back(0);
+    for (int l = 0; l < Q.nlevels; ++l) {
+        LevelDesc d = Q.lv[l];
+        d.img_off += M.pix_per_frame; d.blk_off += M.blk_per_frame; d.cell_off += M.cell_per_frame;
+        if (d.src_level >= 0) d.src_level += lv0;
+        else { d.tab_x += tx0; d.tab_y += ty0; }
+        M.lv.push_back(d);
+        M.scales.push_back(Q.scales[l]);
+        M.lv_frame.push_back(f);
+        M.lv_local.push_back(l);
+    }
+    M.htabx.insert(M.htabx.end(), Q.htabx.begin(), Q.htabx.end());
+    M.htaby.insert(M.htaby.end(), Q.htaby.begin(), Q.htaby.end());
+    M.htabxf.insert(M.htabxf.end(), Q.htabxf.begin(), Q.htabxf.end());
+    M.htabyf.insert(M.htabyf.end(), Q.htabyf.begin(), Q.htabyf.end());
+    M.nlevels += Q.nlevels;
+    M.pix_per_frame += Q.pix_per_frame; M.blk_per_frame += Q.blk_per_frame; M.cell_per_frame += Q.cell_per_frame;
+    M.frame_lv0.push_back(M.nlevels);
+    M.fdim.push_back(make_int2(Q.rows, Q.cols));
+    M.key_dims.push_back(Q.rows); M.key_dims.push_back(Q.cols);
+    M.mixed_frames += 1;
+}
+
+// After the last mixed_append: the pyramid launches (every frame's resized levels in one, then one per octave over every frame)
+// and the post-processing tables.  Host only.
+void mixed_finish(Plan &M, int interval)
+{
+    M.kind = 2; M.interval = interval;
+    M.npix_resized = 0;
+    int octaves = 0;
+    for (int f = 0; f < M.mixed_frames; ++f)
+        octaves = std::max(octaves, (M.frame_lv0[f + 1] - M.frame_lv0[f] + interval - 1) / interval);
+    for (int k = 0; k < octaves; ++k) {
+        M.run_lev0.push_back((int)M.run_lev.size());
+        M.run_off0.push_back((long long)M.run_off.size());
+        long long pix = 0;
+        int n = 0;
+        for (int f = 0; f < M.mixed_frames; ++f)
+            for (int l = M.frame_lv0[f] + k * interval; l < std::min(M.frame_lv0[f] + (k + 1) * interval, M.frame_lv0[f + 1]); ++l) {
+                M.run_lev.push_back(l);
+                M.run_off.push_back(pix);
+                pix += (long long)M.lv[l].img_rows * M.lv[l].img_cols;
+                ++n;
+            }
+        M.run_off.push_back(pix);
+        M.run_n.push_back(n);
+        M.run_npix.push_back(pix);
+    }
+    M.fcanvas.assign(M.mixed_frames, 0);
+    for (int f = 0; f < M.mixed_frames; ++f) {
+        const int r = M.fdim[f].x, c = M.fdim[f].y;
+        if (post_canvas_in_lds(r, c)) {
+            M.post_lds.push_back(f);
+            M.post_lds_words = std::max(M.post_lds_words, post_canvas_words(r, c));
+        } else {
+            M.post_glb.push_back(f);
+            M.fcanvas[f] = (long long)M.post_glb_words;
+            M.post_glb_words += post_canvas_words(r, c);
+        }
+    }
+}
+
+// the mixed plan of one call's frame sizes (rows[f] x cols[f], call order), built from the cached image plans of its sizes
+int get_mixed_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
+{
+    std::vector<int> key;
+    for (int f = 0; f < nframes; ++f) { key.push_back(rows[f]); key.push_back(cols[f]); }
+    for (auto &p : h->plans)
+        if (p->kind == 2 && p->key_dims == key) { *out = p.get(); return PBD_OK; }
+    auto M = std::make_unique<Plan>();
+    // every frame's tables: those of a cached image plan of its size, else built on the host only (a mixed call never uses an
+    // image plan's device tables, and sizes seen only here do not take the equal-size path's places in the plan cache)
+    std::map<std::pair<int, int>, std::unique_ptr<Plan>> built;
+    for (int f = 0; f < nframes; ++f) {
+        const Plan *Q = nullptr;
+        for (auto &p : h->plans)
+            if (p->kind == 0 && p->rows == rows[f] && p->cols == cols[f]) { Q = p.get(); break; }
+        if (!Q) {
+            std::unique_ptr<Plan> &B = built[std::make_pair(rows[f], cols[f])];
+            if (!B) {
+                B = std::make_unique<Plan>();
+                std::string err;
+                if (int rc = image_plan_host(rows[f], cols[f], h->sbin, h->interval, *B, err))
+                    return fail(h, rc, "frame %d: %s", f, err.c_str());
+            }
+            Q = B.get();
+        }
+        mixed_append(*M, *Q);
+    }
+    for (int f = 0; f < nframes; ++f)
+        if (int rc = grow_coord(h, rows[f], cols[f])) return rc;
+    mixed_finish(*M, h->interval);
+    HIPCHK(h, M->d_tabx.upload(M->htabx));
+    HIPCHK(h, M->d_taby.upload(M->htaby));
+    HIPCHK(h, M->d_tabxf.upload(M->htabxf));
+    HIPCHK(h, M->d_tabyf.upload(M->htabyf));
+    HIPCHK(h, M->d_lv_frame.upload(M->lv_frame));
+    HIPCHK(h, M->d_lv_local.upload(M->lv_local));
+    HIPCHK(h, M->d_run_lev.upload(M->run_lev));
+    HIPCHK(h, M->d_run_off.upload(M->run_off));
+    HIPCHK(h, M->d_fdim.upload(M->fdim));
+    HIPCHK(h, M->d_fcanvas.upload(M->fcanvas));
+    HIPCHK(h, M->d_post_lds.upload(M->post_lds));
+    HIPCHK(h, M->d_post_glb.upload(M->post_glb));
+    HIPCHK(h, finish_plan_tables(*M, h->sbin));
+    *out = M.get();
+    cache_plan(h, std::move(M));
     return PBD_OK;
 }
 
@@ -1169,6 +1350,8 @@ int alloc_features(pbd_handle *h, Plan &P, int nframes, int cn, int depth)
     return PBD_OK;
 }
 
+void launch_hog_stage(pbd_handle *h, Plan &P, int cn, int depth, int f0, int nb, hipStream_t st);
+
 void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int depth, int f0, int nb, hipStream_t st)
 {
     PyrParams pp{};
@@ -1187,6 +1370,11 @@ void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int d
         ProfScope ps(h, PBD_K_PYRDOWN, st);
         launch_pyrdown_range(pp, nb, first, last, base, end - base, st);
     }
+    launch_hog_stage(h, P, cn, depth, f0, nb, st);
+}
+
+void launch_hog_stage(pbd_handle *h, Plan &P, int cn, int depth, int f0, int nb, hipStream_t st)
+{
     HogParams hp{};
     hp.lv = P.d_lv.p; hp.nlevels = P.nlevels; hp.cn = cn; hp.sbin = h->sbin; hp.frame0 = f0;
     hp.pix_per_frame = P.pix_per_frame; hp.blk_per_frame = P.blk_per_frame; hp.cell_per_frame = P.cell_per_frame;
@@ -1202,6 +1390,25 @@ void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int d
         ProfScope ps(h, PBD_K_HOG_FEAT, st);
         launch_hog_feat(hp, nb, h->f64, st);
     }
+}
+
+// the pyramid and HOG features of a mixed plan's virtual frame; d_fd = the call's FrameDesc table (device)
+void launch_features_mixed(pbd_handle *h, Plan &P, const FrameDesc *d_fd, int cn, int depth, hipStream_t st)
+{
+    PyrParams pp{};
+    pp.lv = P.d_lv.p; pp.nlevels = P.nlevels; pp.interval = P.interval; pp.cn = cn; pp.frame0 = 0;
+    pp.pyr = h->pyr.as<uint8_t>();
+    pp.tabx = P.d_tabx.p; pp.taby = P.d_taby.p; pp.depth = depth; pp.tabxf = P.d_tabxf.p; pp.tabyf = P.d_tabyf.p;
+    pp.fd = d_fd; pp.lv_frame = P.d_lv_frame.p;
+    for (size_t k = 0; k < P.run_n.size(); ++k) {
+        pp.run_lev = P.d_run_lev.p + P.run_lev0[k];
+        pp.run_off = P.d_run_off.p + P.run_off0[k];
+        pp.nruns = P.run_n[k];
+        pp.pix_per_frame = P.run_npix[k];   // the launch's pixel count
+        if (k == 0) { ProfScope ps(h, PBD_K_RESIZE, st); launch_resize_runs(pp, st); }
+        else { ProfScope ps(h, PBD_K_PYRDOWN, st); launch_pyrdown_runs(pp, st); }
+    }
+    launch_hog_stage(h, P, cn, depth, 0, 1, st);
 }
 
 int ensure_seg_tiles(pbd_handle *h, Plan &P, int nb)
@@ -1265,17 +1472,28 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
 }
 
 // frames per DP chunk so that the chunk scratch stays within the budget
+// DP scratch budget per chunk; a handle's DP_BUDGET_MB debug option lets the tests force several chunks on a small batch
+size_t dp_budget(const pbd_handle *h)
+{
+    return h->dp_budget_mb > 0 ? (size_t)h->dp_budget_mb << 20 : (size_t)8 << 30;
+}
+
+// bytes of DP scratch for `cells` cells and `stk` stack records per job (12 B / cell-job + 16 B / two stack entries, float)
+size_t dp_scratch_bytes(const pbd_handle *h, long long cells, long long stk)
+{
+    const size_t JG = (size_t)std::max(h->JGmax, 1);
+    return (size_t)cells * JG * (6 + 2 * h->rs) + (size_t)stk * JG * (h->f64 ? kStkPairF64 : kStkPairF32);
+}
+
 int dp_chunk_frames(pbd_handle *h, Plan &P, int want)
 {
-    const size_t per_frame = (size_t)P.cell_per_frame * std::max(h->JGmax, 1);
-    const size_t stk_per_frame = (size_t)P.stk_per_jf * std::max(h->JGmax, 1);
-    // bytes of scratch per chunk (12 B / cell-job + 16 B / two stack entries); a handle's DP_BUDGET_MB debug option lets
-    // the tests force several chunks on a small batch
-    const size_t budget = h->dp_budget_mb > 0 ? (size_t)h->dp_budget_mb << 20 : (size_t)8 << 30;
+    const size_t per_frame = dp_scratch_bytes(h, P.cell_per_frame, P.stk_per_jf), budget = dp_budget(h);
     int chunk = std::max(want, 1);
-    while (chunk > 1 && (per_frame * (6 + 2 * h->rs) + stk_per_frame * (h->f64 ? kStkPairF64 : kStkPairF32)) * chunk > budget) chunk = (chunk + 1) / 2;
+    while (chunk > 1 && per_frame * chunk > budget) chunk = (chunk + 1) / 2;
     return chunk;
 }
+
+int alloc_dp_scratch(pbd_handle *h, Plan &P, int chunk);
 
 int alloc_dp(pbd_handle *h, Plan &P, int nframes, int chunk)
 {
@@ -1286,19 +1504,28 @@ int alloc_dp(pbd_handle *h, Plan &P, int nframes, int chunk)
     HIPCHK(h, h->Ik.ensure(std::max<size_t>((size_t)nframes * cpf * NSa, 16)));
     HIPCHK(h, h->rootv.ensure(std::max<size_t>((size_t)nframes * cpf * h->NC * h->rs, 16)));
     HIPCHK(h, h->rooti.ensure(std::max<size_t>((size_t)nframes * cpf * h->NC * sizeof(int), 16)));
+    // the transform's pointer planes are kept for the whole batch (one plane per (part, mixture)): the walk composes Ix / Iy from them
+    HIPCHK(h, h->IxRaw.ensure(std::max<size_t>((size_t)nframes * cpf * std::max(h->totmix, 1) * pes, 16) + 32));
+    HIPCHK(h, h->IyRaw.ensure(std::max<size_t>((size_t)nframes * cpf * std::max(h->totmix, 1) * pes, 16) + 32));
+    return alloc_dp_scratch(h, P, chunk);
+}
+
+// the dynamic program's per-chunk scratch for `chunk` frames of plan P
+int alloc_dp_scratch(pbd_handle *h, Plan &P, int chunk)
+{
+    const size_t cpf = (size_t)P.cell_per_frame;
     const size_t per_frame = cpf * std::max(h->JGmax, 1);
     const size_t stk_per_frame = (size_t)P.stk_per_jf * std::max(h->JGmax, 1);
     HIPCHK(h, h->tmp.ensure(std::max<size_t>(per_frame * chunk * h->rs, 16)));
     HIPCHK(h, h->dt.ensure(std::max<size_t>(per_frame * chunk * h->rs, 16) + 32));            // + slack: the combine step reads whole cell groups
-    // the transform's pointer planes are kept for the whole batch (one plane per (part, mixture)): the walk composes Ix / Iy from them
-    HIPCHK(h, h->IxRaw.ensure(std::max<size_t>((size_t)nframes * cpf * std::max(h->totmix, 1) * pes, 16) + 32));
-    HIPCHK(h, h->IyRaw.ensure(std::max<size_t>((size_t)nframes * cpf * std::max(h->totmix, 1) * pes, 16) + 32));
     HIPCHK(h, h->stk.ensure(std::max<size_t>(stk_per_frame * chunk * (h->f64 ? kStkPairF64 : kStkPairF32), 16)));
     return PBD_OK;
 }
 
 // dynamic program for frames [f0, f0+nb), nb <= the chunk size given to alloc_dp
-void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
+// (cell0: a mixed plan's group of whole frames, run as sub-plan P whose cell offsets start at 0 -- the whole-batch buffers are
+// addressed from the group's first cell of the virtual frame)
+void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st, long long cell0 = 0)
 {
     DpParams dp{};
     dp.lv = P.d_lv.p; dp.nlevels = P.nlevels; dp.F = h->F; dp.NS = h->NS; dp.NC = h->NC; dp.NM = h->NM;
@@ -1314,6 +1541,16 @@ void launch_dp_chunk(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
     dp.nrows_flat = P.nrows_flat; dp.ncols_flat = P.ncols_flat; dp.longest = P.longest;
     dp.rootv = h->rootv.p; dp.rooti = h->rooti.as<int>(); dp.rjobs = h->d_rjobs.p;
     dp.frame0 = f0;
+    if (cell0) {
+        const size_t c0 = (size_t)cell0, pes = P.ptr8 ? 1 : 2;
+        dp.resp = h->resp.as<char>() + c0 * h->F * h->resp_es;
+        dp.acc = h->acc.as<char>() + c0 * h->NM * h->rs;
+        dp.Ik = h->Ik.as<uint8_t>() + c0 * h->NS;
+        dp.IxRaw = h->IxRaw.as<char>() + c0 * h->totmix * pes;
+        dp.IyRaw = h->IyRaw.as<char>() + c0 * h->totmix * pes;
+        dp.rootv = h->rootv.as<char>() + c0 * h->NC * h->rs;
+        dp.rooti = h->rooti.as<int>() + c0 * h->NC;
+    }
     for (auto &g : h->groups) {
         dp.JG = (int)g.jobs.size();
         dp.jobs = g.d_jobs.p; dp.cjobs = g.d_cjobs.p; dp.childs = g.d_childs.p;
@@ -1366,6 +1603,7 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     ap.walk = h->d_walk.p; ap.walk_off = h->d_walk_off.p;
     ap.max_parts = h->max_parts; ap.stride = stride(h); ap.capacity = std::max(capacity, 0);
     ap.payload = d_payload; ap.frame_offset = frame_offset;
+    if (P.kind == 2) { ap.lv_frame = P.d_lv_frame.p; ap.lv_local = P.d_lv_local.p; }
     ap.ntotal = (long long)nframes * P.cell_per_frame * h->NC;
     ap.nblk = (int)std::max<long long>((ap.ntotal + argmin_find_span() - 1) / argmin_find_span(), 1);
     HIPCHK(h, h->find_blk.ensure((size_t)ap.nblk * sizeof(int)));
@@ -1380,7 +1618,7 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
 // `frame` fields, nframes frames of rows x cols) into d_out = int32[1 + out_cap * stride]: word 0 = kept count (-1 when more
 // than in_cap candidates were found), then the kept records frame by frame, `frame` + frame_offset.  No host synchronisation.
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
-                 int32_t *d_out, int out_cap, hipStream_t st)
+                 int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr)
 {
     PostParams pp{};
     pp.in = d_in; pp.in_cap = std::max(in_cap, 1);
@@ -1390,7 +1628,8 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
     // workspace: key, frame, perm, slot [in_cap] | box [in_cap] int4 | fkept [nframes] | global canvases (frames too big for LDS)
     const size_t n = (size_t)pp.in_cap, a4 = (4 * n * sizeof(int) + 15) & ~(size_t)15;
     const size_t fk = ((size_t)nframes * sizeof(int) + 15) & ~(size_t)15;
-    const size_t canvas = post_canvas_in_lds(rows, cols) ? 0 : (size_t)nframes * post_canvas_words(rows, cols) * sizeof(uint32_t);
+    const size_t canvas = mixed ? mixed->post_glb_words * sizeof(uint32_t)
+                                : post_canvas_in_lds(rows, cols) ? 0 : (size_t)nframes * post_canvas_words(rows, cols) * sizeof(uint32_t);
     HIPCHK(h, h->post_ws.ensure(a4 + n * sizeof(int4) + fk + canvas));
     char *ws = h->post_ws.as<char>();
     pp.key = reinterpret_cast<float *>(ws); pp.frame = reinterpret_cast<int *>(ws) + n;
@@ -1398,6 +1637,12 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
     pp.box = reinterpret_cast<int4 *>(ws + a4);
     pp.fkept = reinterpret_cast<int *>(ws + a4 + n * sizeof(int4));
     pp.canvas = canvas ? reinterpret_cast<uint32_t *>(ws + a4 + n * sizeof(int4) + fk) : nullptr;
+    if (mixed) {   // every frame with its own size and canvas kind
+        pp.fdim = mixed->d_fdim.p; pp.fcanvas = mixed->d_fcanvas.p;
+        launch_postprocess_mixed(pp, mixed->d_post_lds.p, (int)mixed->post_lds.size(), mixed->post_lds_words, mixed->d_post_glb.p,
+                                 (int)mixed->post_glb.size(), st);
+        return PBD_OK;
+    }
     launch_postprocess(pp, st);
     return PBD_OK;
 }
@@ -1413,8 +1658,8 @@ int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_
     cb.nms = post;
     if (post) {
         HIPCHK(h, cb.post.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-        if (int rc = enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, cb.payload.as<int32_t>(), cap, 0, cb.post.as<int32_t>(),
-                                  cap, st))
+        if (int rc = enqueue_post(h, P.kind == 2 ? P.mixed_frames : nframes, P.rows, P.cols, h->nms_overlap, cb.payload.as<int32_t>(),
+                                  cap, 0, cb.post.as<int32_t>(), cap, st, P.kind == 2 ? &P : nullptr))
             return rc;
     }
     cb.copied = std::min(h->cand_guess, cap);
@@ -1471,8 +1716,8 @@ int enqueue_argmin_out(pbd_handle *h, Plan &P, int nframes, int frame_offset, in
     const int cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride(h) + 1) * sizeof(int32_t)));
     if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream)) return rc;
-    return enqueue_post(h, nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap, frame_offset, d_payload, capacity,
-                        h->stream);
+    return enqueue_post(h, P.kind == 2 ? P.mixed_frames : nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap,
+                        frame_offset, d_payload, capacity, h->stream, P.kind == 2 ? &P : nullptr);
 }
 
 // Frames of a call: on the host (`host[i]`, rows `stride` bytes apart; uploaded to h->frames by enqueue_features) or
@@ -1580,6 +1825,150 @@ int read_responses(pbd_handle *h, void *dst, const void *src, size_t n)
     return PBD_OK;
 }
 
+// ---- mixed-size calls (pbd_detect_frames*) -------------------------------------------------------------------------------
+// the dynamic program of a mixed plan: the whole virtual frame in one pass when its scratch fits the budget, else in groups
+// of whole frames (sub-plans built once per budget)
+int run_dp_mixed(pbd_handle *h, Plan &P)
+{
+    const size_t budget = dp_budget(h);
+    auto scratch = [&](long long cells, long long stk) { return dp_scratch_bytes(h, cells, stk); };
+    if (int rc = alloc_dp(h, P, 1, 0)) return rc;   // the whole-batch buffers (scratch below)
+    if (scratch(P.cell_per_frame, P.stk_per_jf) <= budget || P.mixed_frames == 1) {
+        if (int rc = alloc_dp_scratch(h, P, 1)) return rc;
+        launch_dp_chunk(h, P, 0, 1, h->stream);
+    } else {
+        if (P.chunk_budget != budget) {
+            // groups of consecutive frames, greedily, by an estimate (cells, and the stack share of the virtual frame's)
+            std::vector<std::unique_ptr<Plan>> plans;
+            std::vector<long long> cell0s;
+            int f = 0;
+            while (f < P.mixed_frames) {
+                int g = f + 1;
+                auto cells = [&](int a, int b) {
+                    const int l0 = P.frame_lv0[a], l1 = P.frame_lv0[b];
+                    return (l1 < P.nlevels ? P.lv[l1].cell_off : P.cell_per_frame) - P.lv[l0].cell_off;
+                };
+                auto est = [&](int a, int b) {
+                    const long long c = cells(a, b);
+                    return scratch(c, P.cell_per_frame ? (long long)((double)P.stk_per_jf * c / P.cell_per_frame) + 64 : 0);
+                };
+                while (g < P.mixed_frames && est(f, g + 1) <= budget) ++g;
+                auto S = std::make_unique<Plan>();
+                const int l0 = P.frame_lv0[f], l1 = P.frame_lv0[g];
+                const long long c0 = P.lv[l0].cell_off;
+                S->kind = 3; S->interval = P.interval; S->nlevels = l1 - l0;
+                S->lv.assign(P.lv.begin() + l0, P.lv.begin() + l1);
+                for (LevelDesc &d : S->lv) d.cell_off -= c0;
+                S->cell_per_frame = cells(f, g);
+                HIPCHK(h, finish_plan_tables(*S, h->sbin));
+                S->ptr8 = P.ptr8;        // the pointer planes' element size is the whole call's
+                plans.push_back(std::move(S));
+                cell0s.push_back(c0);
+                f = g;
+            }
+            P.chunk_plans = std::move(plans);
+            P.chunk_cell0 = std::move(cell0s);
+            P.chunk_budget = budget;
+        }
+        for (auto &S : P.chunk_plans)
+            if (int rc = alloc_dp_scratch(h, *S, 1)) return rc;
+        for (size_t i = 0; i < P.chunk_plans.size(); ++i) launch_dp_chunk(h, *P.chunk_plans[i], 0, 1, h->stream, P.chunk_cell0[i]);
+    }
+    HIPCHK(h, hipGetLastError());
+    h->res.dp = true;
+    return PBD_OK;
+}
+
+// every check of a mixed-size call before anything is enqueued; *plan = its mixed plan
+int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan)
+{
+    if (h->shard_world > 1)
+        return fail(h, PBD_ERR_UNSUPPORTED, "mixed-size calls with level sharding (world %d): pbd_set_level_shard(h, 0, 1) first",
+                    h->shard_world);
+    if (int rc = check_batch(h, nframes)) return rc;
+    if (!depth_size(depth))
+        return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth);
+    if (cn != 1 && cn != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", cn);
+    std::vector<int> rows(nframes), cols(nframes);
+    for (int f = 0; f < nframes; ++f) {
+        const pbd_frame &fr = frames[f];
+        if (!fr.data || fr.rows < 1 || fr.cols < 1 || fr.rows > 32000 || fr.cols > 32000)
+            return fail(h, PBD_ERR_INVALID, "frame %d: %dx%d at %p", f, fr.rows, fr.cols, fr.data);
+        const size_t row_bytes = (size_t)fr.cols * cn * depth_size(depth);
+        if (fr.stride_bytes < row_bytes) return fail(h, PBD_ERR_INVALID, "frame %d: stride %zu < row bytes %zu", f, fr.stride_bytes, row_bytes);
+        if (!host && (reinterpret_cast<uintptr_t>(fr.data) % depth_size(depth) || fr.stride_bytes % depth_size(depth)))
+            return fail(h, PBD_ERR_INVALID, "frame %d: device pointer %p / stride %zu not a multiple of the %zu-byte element", f, fr.data,
+                        fr.stride_bytes, depth_size(depth));
+        if (host && (depth == kDepth32F || depth == kDepth64F)) {   // as check_frames: non-finite input is an error
+            const size_t n = (size_t)fr.cols * cn;
+            for (int y = 0; y < fr.rows; ++y) {
+                const char *row = static_cast<const char *>(fr.data) + (size_t)y * fr.stride_bytes;
+                bool ok = true;
+                if (depth == kDepth32F) { const float *q = reinterpret_cast<const float *>(row); for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(q[k]); }
+                else { const double *q = reinterpret_cast<const double *>(row); for (size_t k = 0; k < n; ++k) ok = ok && std::isfinite(q[k]); }
+                if (!ok) return fail(h, PBD_ERR_INVALID, "frame %d, row %d holds a NaN or Inf pixel", f, y);
+            }
+        }
+        rows[f] = fr.rows; cols[f] = fr.cols;
+    }
+    if (int rc = check_bank(h)) return rc;
+    return get_mixed_plan(h, nframes, rows.data(), cols.data(), plan);
+}
+
+// pyramid -> HOG -> convolution -> dynamic program of a mixed-size call that passed check_frames_mixed (no host synchronisation)
+int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host)
+{
+    h->res = Resident{&P, 1, cn, depth};
+    const size_t es = depth_size(depth);
+    std::vector<FrameDesc> fd(nframes);
+    if (host) {   // the frames go to the handle's frame buffer, packed, each with its own dense rows
+        size_t total = 0;
+        for (int f = 0; f < nframes; ++f) total += (size_t)frames[f].rows * frames[f].cols * cn * es;
+        HIPCHK(h, h->frames.ensure(total + 4));
+        size_t off = 0;
+        for (int f = 0; f < nframes; ++f) {
+            const size_t row_bytes = (size_t)frames[f].cols * cn * es;
+            uint8_t *dst = h->frames.as<uint8_t>() + off;
+            HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, frames[f].data, frames[f].stride_bytes, row_bytes, frames[f].rows,
+                                       hipMemcpyHostToDevice, h->stream));
+            fd[f] = FrameDesc{dst, frames[f].rows, frames[f].cols, (long long)row_bytes};
+            off += row_bytes * frames[f].rows;
+        }
+    } else {
+        for (int f = 0; f < nframes; ++f)
+            fd[f] = FrameDesc{static_cast<const uint8_t *>(frames[f].data), frames[f].rows, frames[f].cols, (long long)frames[f].stride_bytes};
+    }
+    const size_t fd_bytes = fd.size() * sizeof(FrameDesc);
+    if (h->fd_copied.p) HIPCHK(h, hipEventSynchronize(h->fd_copied.p));   // the previous call's table has left the staging buffer
+    else HIPCHK(h, hipEventCreateWithFlags(&h->fd_copied.p, hipEventDisableTiming));
+    HIPCHK(h, h->fd_host.ensure(fd_bytes, fd_bytes * 2 + 256));
+    HIPCHK(h, h->fd_dev.ensure(fd_bytes));
+    memcpy(h->fd_host.p, fd.data(), fd_bytes);
+    HIPCHK(h, hipMemcpyAsync(h->fd_dev.p, h->fd_host.p, fd_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->fd_copied.p, h->stream));
+    if (int rc = alloc_features(h, P, 1, cn, depth)) return rc;
+    launch_features_mixed(h, P, h->fd_dev.as<FrameDesc>(), cn, depth, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->res.features = h->res.c31_zero = true;
+    if (int rc = run_conv(h, P, 1)) return rc;
+    return run_dp_mixed(h, P);
+}
+
+// a (frame, level) of the resident result -> (frame index into the buffers, level of the plan); mixed plans: frame 0, the
+// frame's level in the virtual table
+bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
+{
+    const Plan &P = *r.plan;
+    if (P.kind == 2) {
+        if (frame < 0 || frame >= P.mixed_frames || level < 0 || level >= P.frame_lv0[frame + 1] - P.frame_lv0[frame]) return false;
+        *bf = 0; *bl = P.frame_lv0[frame] + level;
+        return true;
+    }
+    if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return false;
+    *bf = frame; *bl = level;
+    return true;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1617,6 +2006,31 @@ int pbd_debug_seg_tiles(int nlevels, const int *rows, const int *cols, int nb, i
         static_assert(sizeof(ConvSegTile) == 16 * sizeof(int), "a tile record is 16 ints");
         for (size_t i = 0; i < tiles.size() && (int)i < capacity; ++i) memcpy(out + 16 * i, &tiles[i], sizeof(ConvSegTile));
         return (int)tiles.size();
+    });
+}
+
+// the virtual level table of a mixed-size call (host-only, no GPU needed): frames of rows[f] x cols[f] in call order, for a
+// model of `sbin` / `interval`; out[i] = {frame, local level, img_rows, img_cols, rows, cols, cell_off} = 7 ints per level
+// (cell_off fits an int for every frame size accepted); returns the level count, or PBD_ERR_INVALID (a frame too small)
+int pbd_debug_mixed_plan(int sbin, int interval, int nframes, const int *rows, const int *cols, int *out, int capacity)
+{
+    return guarded(nullptr, [&]() -> int {
+        if (nframes < 1 || sbin < 2 || interval < 1 || !rows || !cols) return PBD_ERR_INVALID;
+        Plan M;
+        for (int f = 0; f < nframes; ++f) {
+            Plan Q;
+            std::string err;
+            if (rows[f] < 1 || cols[f] < 1 || image_plan_host(rows[f], cols[f], sbin, interval, Q, err)) return PBD_ERR_INVALID;
+            mixed_append(M, Q);
+        }
+        mixed_finish(M, interval);
+        for (int l = 0; l < M.nlevels && l < capacity; ++l) {
+            const LevelDesc &d = M.lv[l];
+            int *o = out + 7 * (size_t)l;
+            o[0] = M.lv_frame[l]; o[1] = M.lv_local[l]; o[2] = d.img_rows; o[3] = d.img_cols; o[4] = d.rows; o[5] = d.cols;
+            o[6] = (int)d.cell_off;
+        }
+        return M.nlevels;
     });
 }
 
@@ -1843,9 +2257,9 @@ int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst)
 {
     return entry(h, dst, kIdle, [&]() -> int {
         const Resident &r = h->res;
-        if (!r.plan || r.plan->kind != 0 || !r.features) return fail(h, PBD_ERR_STATE, "no pyramid has been computed");
+        if (!r.plan || (r.plan->kind != 0 && r.plan->kind != 2) || !r.features) return fail(h, PBD_ERR_STATE, "no pyramid has been computed");
         const Plan &P = *r.plan;
-        if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
+        if (!resident_level(r, frame, level, &frame, &level)) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
         const LevelDesc &d = P.lv[level];
         const size_t es = depth_size(r.depth);
         HIPCHK(h, hipMemcpyAsync(dst, h->pyr.as<uint8_t>() + ((size_t)frame * P.pix_per_frame + d.img_off) * r.cn * es,
@@ -1979,6 +2393,8 @@ int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacit
 {
     return entry(h, scales && cand && ncand, kIdle, [&]() -> int {
         if (!h->res.plan || !h->res.dp) return fail(h, PBD_ERR_STATE, "argmin() before min()");
+        if (h->res.plan->kind == 2)
+            return fail(h, PBD_ERR_STATE, "argmin() after a mixed-size call: DynamicProgram::argmin takes the scales of one image");
         Plan &P = *h->res.plan;
         HIPCHK(h, h->scales_tmp.ensure(sizeof(float) * PBD_MAX_LEVELS));
         HIPCHK(h, hipMemcpyAsync(h->scales_tmp.p, scales, sizeof(float) * P.nlevels, hipMemcpyHostToDevice, h->stream));
@@ -2101,9 +2517,46 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
 {
     return entry(h, d_payload, kIdle, [&]() -> int {
         const Resident &r = h->res;
-        if (!r.plan || !r.dp || r.plan->kind != 0) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
+        if (!r.plan || !r.dp || (r.plan->kind != 0 && r.plan->kind != 2)) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
         if (int rc = enqueue_argmin_out(h, *r.plan, r.frames, frame_offset, d_payload, capacity)) return rc;
+        HIPCHK(h, hipGetLastError());
+        return PBD_OK;
+    });
+}
+
+// Mixed-size calls (new surface): nframes frames of any sizes, planned as one virtual frame.  See include/pbd.h.
+int pbd_detect_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int32_t *cand, int capacity,
+                      int *ncand)
+{
+    return entry(h, frames && cand && ncand, kIdle, [&]() -> int {
+        Plan *P = nullptr;
+        if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, true, &P)) return rc;
+        if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, true)) return rc;
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, cand, capacity, ncand);
+    });
+}
+
+int pbd_detect_frames_device(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int32_t *cand,
+                             int capacity, int *ncand)
+{
+    return entry(h, frames && cand && ncand, kIdle, [&]() -> int {
+        Plan *P = nullptr;
+        if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, false, &P)) return rc;
+        if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, false)) return rc;
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, cand, capacity, ncand);
+    });
+}
+
+int pbd_detect_frames_device_out(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int frame_offset,
+                                 int32_t *d_payload, int capacity)
+{
+    return entry(h, frames && d_payload, kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        Plan *P = nullptr;
+        if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, false, &P)) return rc;
+        if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, false)) return rc;
+        if (int rc = enqueue_argmin_out(h, *P, 1, frame_offset, d_payload, capacity)) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
     });
@@ -2117,7 +2570,7 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
         const Resident &r = h->res;
         if (!r.plan) return fail(h, PBD_ERR_STATE, "nothing has been computed");
         const Plan &P = *r.plan;
-        if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
+        if (!resident_level(r, frame, level, &frame, &level)) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
         const LevelDesc &d = P.lv[level];
         const size_t hw = (size_t)d.rows * d.cols, cell = (size_t)frame * P.cell_per_frame + d.cell_off;
         const void *src = nullptr;

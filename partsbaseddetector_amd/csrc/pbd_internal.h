@@ -130,6 +130,13 @@ static_assert((size_t)(((kConvTH + kConvMaxK - 1) * (kConvTW + kConvMaxK - 1)) |
 constexpr int kConv3NW = PBD_CONV3_NW;   // waves per workgroup of k_conv3
 
 // ---- launch parameter blocks ---------------------------------------------------------------
+// one source frame of a mixed-size call: device pointer, size and row pitch in bytes (a region of a larger image reads it in place)
+struct FrameDesc {
+    const uint8_t *data;
+    int rows, cols;
+    long long pitch;
+};
+
 struct PyrParams {
     const LevelDesc *lv;
     int nlevels, interval, cn;
@@ -143,6 +150,14 @@ struct PyrParams {
     int depth;                    // kDepth8U (fixed-point resampling, the tables above) or 16U / 32F / 64F (tables below)
     const ResizeTabXf *tabxf;
     const ResizeTabYf *tabyf;
+    // mixed-size calls (one "virtual frame" whose levels are the frames' pyramids, frame-major; frame0 = 0, one grid row):
+    // the levels of one launch as runs of a flat pixel index (run i = level run_lev[i], pixels [run_off[i], run_off[i + 1])),
+    // and every frame's source image.  NULL on the equal-size path.
+    const int *run_lev;
+    const long long *run_off;
+    int nruns;
+    const FrameDesc *fd;
+    const int *lv_frame;          // [nlevels] frame of a virtual level
 };
 
 struct HogParams {
@@ -252,6 +267,8 @@ struct ArgminParams {
     int *blk; int nblk;           // hits per block of the find kernels, then their exclusive prefix sums
     long long ntotal;             // nframes * cell_per_frame * NC root cells
     int frame_offset;             // added to the `frame` field of every record (frames sharded over GPUs: global frame id)
+    // mixed-size calls: virtual level -> (frame of the call, level of that frame's pyramid); NULL: the record's own frame / level
+    const int *lv_frame, *lv_local;
 };
 
 // per-frame sort + non-maxima suppression of an argmin payload (pbd_set_nms; pbd_kernels_post.hip)
@@ -266,6 +283,11 @@ struct PostParams {
     uint32_t *canvas;             // nframes bit canvases of rows * wpr words when they do not fit in LDS
     int32_t *out; int out_cap;    // output payload: word 0 = kept count, then min(kept, out_cap) records
     int frame_offset;             // added to the `frame` field of every emitted record
+    // mixed-size calls: per frame {rows, cols} and the word offset of its canvas in `canvas` (NULL: the scalars above, canvas
+    // f at f * rows * wpr); `flist` = the frames of one k_post_nms launch (NULL: blockIdx.x), those of one canvas kind
+    const int2 *fdim;
+    const long long *fcanvas;
+    const int *flist;
 };
 
 // ---- kernel launches and their timing -------------------------------------------------------
@@ -293,6 +315,10 @@ inline void launch_k(F kernel, const dim3 &grid, const dim3 &block, unsigned lds
 void launch_resize(const PyrParams &p, int nframes, long long npix_resized, hipStream_t s);
 void launch_pyrdown_range(const PyrParams &p, int nframes, int first_level, int last_level, long long base,
                           long long npix, hipStream_t s);
+// mixed-size calls: the levels listed in p.run_lev / p.run_off (all resized levels of every frame, or one octave of every
+// frame), p.run_off[p.nruns] pixels, in one launch
+void launch_resize_runs(const PyrParams &p, hipStream_t s);
+void launch_pyrdown_runs(const PyrParams &p, hipStream_t s);
 // `f64` selects the reference's T=double instantiation (every real-typed buffer then holds doubles)
 void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s);
 void launch_hog_feat(const HogParams &p, int nframes, bool f64, hipStream_t s);
@@ -331,5 +357,9 @@ void launch_argmin_walk(const ArgminParams &p, bool f64, hipStream_t s);
 bool post_canvas_in_lds(int rows, int cols);
 size_t post_canvas_words(int rows, int cols);
 void launch_postprocess(const PostParams &p, hipStream_t s);
+// mixed-size calls: frames lds_frames[0..nlds) with their canvases in LDS (the largest lds_words words), glb_frames[0..nglb)
+// with theirs in p.canvas
+void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nlds, size_t lds_words, const int *glb_frames,
+                              int nglb, hipStream_t s);
 
 }  // namespace pbd

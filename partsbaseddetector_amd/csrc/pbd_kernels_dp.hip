@@ -1056,6 +1056,10 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
         rects[pidx * 4 + 3] = max(y1, y2) - ry;
     }
     rec[0] = frame + p.frame_offset;   // index within the batch -> global frame id of a sharded job (0 on one GPU)
+    if (p.lv_frame) {                  // mixed-size call: virtual level -> (frame of the call, level of its own pyramid)
+        rec[0] = p.lv_frame[l] + p.frame_offset;
+        rec[2] = p.lv_local[l];
+    }
     rec[6] = nparts;
     rec[7] = 0;
     }

@@ -39,12 +39,28 @@ __device__ __forceinline__ int px_ch(uint32_t v, int c) { return (int)((v >> (8 
 template <int OFF>
 __device__ __forceinline__ int find_level_blk(const LevelDesc *lv, int lo, int hi, long long idx, long long *s_off)
 {
+    // a mixed-size call's virtual frame may hold more levels than the LDS table: search global memory (uniform branch)
+    if (hi > PBD_MAX_LEVELS) return find_level<OFF>(lv, lo, hi, idx);
     for (int i = lo + (int)threadIdx.x; i < hi; i += (int)blockDim.x) s_off[i] = lv_off<OFF>(lv[i]);
     __syncthreads();
     while (hi - lo > 1) {
         int mid = (lo + hi) >> 1;
         if (s_off[mid] <= idx) lo = mid; else hi = mid;
     }
+    return lo;
+}
+
+// run of a mixed-size launch holding flat pixel `idx` (run_off non-decreasing, n runs); every thread of the block calls it
+__device__ __forceinline__ int find_run_blk(const long long *run_off, int n, long long idx, long long *s_off)
+{
+    int lo = 0, hi = n;
+    if (n <= PBD_MAX_LEVELS) {
+        for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) s_off[i] = run_off[i];
+        __syncthreads();
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= idx) lo = mid; else hi = mid; }
+        return lo;
+    }
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (run_off[mid] <= idx) lo = mid; else hi = mid; }
     return lo;
 }
 
@@ -314,6 +330,138 @@ void launch_pyrdown_range(const PyrParams &p, int nframes, int first_level, int 
     else if (p.depth == kDepth32F) PBD_LAUNCH((k_pyrdown_t<float, float>), grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
     else if (p.depth == kDepth64F) PBD_LAUNCH((k_pyrdown_t<double, double>), grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
     else PBD_LAUNCH(k_pyrdown, grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mixed-size calls (pbd_detect_frames*): the levels of the virtual frame come from different source frames.  One thread per
+// destination pixel of the launch's runs (run = one level); a resized level reads its own frame (pointer, size, pitch:
+// FrameDesc), with the per-frame tables its LevelDesc points into.  Same arithmetic per pixel as k_resize / k_resize_t /
+// k_pyrdown / k_pyrdown_t.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_resize_runs(PyrParams p)
+{
+    __shared__ long long s_off[PBD_MAX_LEVELS];
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = p.run_off[p.nruns];
+    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
+    if (idx >= npix) return;
+    const int l = p.run_lev[r];
+    const LevelDesc d = p.lv[l];
+    const FrameDesc fr = p.fd[p.lv_frame[l]];
+    const int local = (int)(idx - p.run_off[r]);
+    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
+    const ResizeTabX tx = p.tabx[d.tab_x + dx];
+    const ResizeTabY ty = p.taby[d.tab_y + dy];
+    const int cn = p.cn;
+    const uint8_t *S0 = fr.data + (size_t)ty.y0 * fr.pitch, *S1 = fr.data + (size_t)ty.y1 * fr.pitch;
+    const int sx = tx.sx, sx1 = sx + 1 < fr.cols ? sx + 1 : sx;
+    uint8_t *D = p.pyr + (d.img_off + local) * cn;
+    if (cn == 3) {
+        // the last pixel of every frame (region) is read bytewise: its 4th byte may lie past the caller's image
+        auto ld = [&](const uint8_t *row, int yy, int xx) {
+            return (yy == fr.rows - 1 && xx == fr.cols - 1) ? load_px3_bytes(row + xx * 3) : load_px3(row + xx * 3);
+        };
+        const uint32_t p00 = ld(S0, ty.y0, sx), p10 = ld(S1, ty.y1, sx), p01 = ld(S0, ty.y0, sx1), p11 = ld(S1, ty.y1, sx1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int r0 = px_ch(p00, c) * tx.a0 + px_ch(p01, c) * tx.a1;
+            const int r1 = px_ch(p10, c) * tx.a0 + px_ch(p11, c) * tx.a1;
+            D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+        }
+        return;
+    }
+    for (int c = 0; c < cn; ++c) {
+        const int r0 = S0[sx * cn + c] * tx.a0 + S0[sx1 * cn + c] * tx.a1;
+        const int r1 = S1[sx * cn + c] * tx.a0 + S1[sx1 * cn + c] * tx.a1;
+        D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+    }
+}
+
+template <typename PT, typename WT>
+__global__ __launch_bounds__(256) void k_resize_runs_t(PyrParams p)
+{
+    __shared__ long long s_off[PBD_MAX_LEVELS];
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = p.run_off[p.nruns];
+    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
+    if (idx >= npix) return;
+    const int l = p.run_lev[r];
+    const LevelDesc d = p.lv[l];
+    const FrameDesc fr = p.fd[p.lv_frame[l]];
+    const int local = (int)(idx - p.run_off[r]);
+    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
+    const ResizeTabXf tx = p.tabxf[d.tab_x + dx];
+    const ResizeTabYf ty = p.tabyf[d.tab_y + dy];
+    const int cn = p.cn;
+    const PT *S0 = reinterpret_cast<const PT *>(fr.data + (size_t)ty.y0 * fr.pitch);
+    const PT *S1 = reinterpret_cast<const PT *>(fr.data + (size_t)ty.y1 * fr.pitch);
+    PT *D = reinterpret_cast<PT *>(p.pyr) + (d.img_off + local) * cn;
+    for (int c = 0; c < cn; ++c) {
+        WT r0, r1;
+        if (tx.last) {
+            r0 = (WT)S0[tx.sx * cn + c] * (WT)1; r1 = (WT)S1[tx.sx * cn + c] * (WT)1;
+        } else {
+            r0 = (WT)S0[tx.sx * cn + c] * (WT)tx.a0 + (WT)S0[(tx.sx + 1) * cn + c] * (WT)tx.a1;
+            r1 = (WT)S1[tx.sx * cn + c] * (WT)tx.a0 + (WT)S1[(tx.sx + 1) * cn + c] * (WT)tx.a1;
+        }
+        D[c] = resize_cast<PT, WT>(r0 * (WT)ty.b0 + r1 * (WT)ty.b1);
+    }
+}
+
+void launch_resize_runs(const PyrParams &p, hipStream_t s)
+{
+    const long long npix = p.pix_per_frame;   // run_off[nruns] of this launch
+    if (p.nruns == 0 || npix == 0) return;
+    dim3 grid((unsigned)((npix + 255) / 256));
+    if (p.depth == kDepth16U) PBD_LAUNCH((k_resize_runs_t<uint16_t, float>), grid, dim3(256), 0, s, p);
+    else if (p.depth == kDepth32F) PBD_LAUNCH((k_resize_runs_t<float, float>), grid, dim3(256), 0, s, p);
+    else if (p.depth == kDepth64F) PBD_LAUNCH((k_resize_runs_t<double, double>), grid, dim3(256), 0, s, p);
+    else PBD_LAUNCH(k_resize_runs, grid, dim3(256), 0, s, p);
+}
+
+template <typename PT, typename WT, bool kInt>
+__global__ __launch_bounds__(256) void k_pyrdown_runs(PyrParams p)
+{
+    __shared__ long long s_off[PBD_MAX_LEVELS];
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = p.run_off[p.nruns];
+    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
+    if (idx >= npix) return;
+    const LevelDesc d = p.lv[p.run_lev[r]];
+    const LevelDesc sd = p.lv[d.src_level];
+    const int local = (int)(idx - p.run_off[r]);
+    const int y = local / d.img_cols, x = local - y * d.img_cols;
+    const int cn = p.cn;
+    const PT *S = reinterpret_cast<const PT *>(p.pyr) + sd.img_off * cn;
+    PT *D = reinterpret_cast<PT *>(p.pyr) + (d.img_off + local) * cn;
+    int xs[5], ys[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        xs[k] = reflect101(2 * x - 2 + k, sd.img_cols) * cn;
+        ys[k] = reflect101(2 * y - 2 + k, sd.img_rows);
+    }
+    for (int c = 0; c < cn; ++c) {
+        WT rr[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const PT *R = S + (size_t)ys[k] * sd.img_cols * cn + c;
+            rr[k] = (WT)R[xs[2]] * 6 + ((WT)R[xs[1]] + (WT)R[xs[3]]) * 4 + (WT)R[xs[0]] + (WT)R[xs[4]];
+        }
+        const WT v = rr[2] * 6 + (rr[1] + rr[3]) * 4 + rr[0] + rr[4];
+        if constexpr (kInt) D[c] = (PT)((v + 128) >> 8);        // 8U / 16U: (sum + 128) >> 8
+        else D[c] = pyr_finish<PT, WT>(v);
+    }
+}
+
+void launch_pyrdown_runs(const PyrParams &p, hipStream_t s)
+{
+    const long long npix = p.pix_per_frame;   // run_off[nruns] of this launch
+    if (p.nruns == 0 || npix == 0) return;
+    dim3 grid((unsigned)((npix + 255) / 256));
+    if (p.depth == kDepth16U) PBD_LAUNCH((k_pyrdown_runs<uint16_t, int, true>), grid, dim3(256), 0, s, p);
+    else if (p.depth == kDepth32F) PBD_LAUNCH((k_pyrdown_runs<float, float, false>), grid, dim3(256), 0, s, p);
+    else if (p.depth == kDepth64F) PBD_LAUNCH((k_pyrdown_runs<double, double, false>), grid, dim3(256), 0, s, p);
+    else PBD_LAUNCH((k_pyrdown_runs<uint8_t, int, true>), grid, dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------

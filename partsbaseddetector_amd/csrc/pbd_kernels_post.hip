@@ -70,7 +70,8 @@ __global__ __launch_bounds__(kPostThreads) void k_post_prep(PostParams p)
         }
     }
     // box & Rect(0, 0, cols, rows); an empty intersection is (0, 0, 0, 0)
-    long long x1 = max(x, 0LL), y1 = max(y, 0LL), x2 = min(x + w, (long long)p.cols), y2 = min(y + h, (long long)p.rows);
+    const int2 fs = p.fdim ? p.fdim[r[0]] : make_int2(p.rows, p.cols);   // the frame's own size (mixed-size calls)
+    long long x1 = max(x, 0LL), y1 = max(y, 0LL), x2 = min(x + w, (long long)fs.y), y2 = min(y + h, (long long)fs.x);
     if (x2 - x1 <= 0 || y2 - y1 <= 0) x1 = y1 = x2 = y2 = 0;
     p.box[i] = make_int4((int)x1, (int)y1, (int)x2, (int)y2);
 }
@@ -96,13 +97,13 @@ __global__ __launch_bounds__(post_nms_threads<kLds>()) void k_post_nms(PostParam
     constexpr int NT = post_nms_threads<kLds>(), kWaves = NT / 64, kUnroll = 4;
     extern __shared__ __attribute__((aligned(16))) uint32_t post_lds[];
     __shared__ int partial[2][kWaves];
-    const int f = blockIdx.x, tid = threadIdx.x;
+    const int f = p.flist ? p.flist[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
     if (post_overflow(p)) return;
     const int n = post_count(p);
     const int lo = post_lower_bound(p.frame, n, f), hi = post_lower_bound(p.frame, n, f + 1);
-    const int wpr = p.wpr;
-    const long long words = (long long)p.rows * wpr;
-    uint32_t *canvas = kLds ? post_lds : p.canvas + (size_t)f * words;
+    const int wpr = p.fdim ? (p.fdim[f].y + 31) / 32 : p.wpr;
+    const long long words = (long long)(p.fdim ? p.fdim[f].x : p.rows) * wpr;
+    uint32_t *canvas = kLds ? post_lds : p.canvas + (p.fcanvas ? (size_t)p.fcanvas[f] : (size_t)f * words);
     for (long long t = tid; t < words; t += NT) canvas[t] = 0u;
     __syncthreads();
     const double overlap = (double)p.overlap;      // the reference's `const float overlap`, widened in the comparison
@@ -216,6 +217,33 @@ void launch_postprocess(const PostParams &p, hipStream_t s)
         PBD_LAUNCH(k_post_nms<true>, dim3(p.nframes), dim3(post_nms_threads<true>()), lds, s, p);
     } else {
         PBD_LAUNCH(k_post_nms<false>, dim3(p.nframes), dim3(post_nms_threads<false>()), 0, s, p);
+    }
+    PBD_LAUNCH(k_post_emit, dim3(p.nframes), dim3(kPostThreads), 0, s, p);
+}
+
+void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nlds, size_t lds_words, const int *glb_frames,
+                              int nglb, hipStream_t s)
+{
+    const int rblocks = std::max((p.in_cap + kPostThreads - 1) / kPostThreads, 1);
+    PBD_LAUNCH(k_post_prep, dim3(rblocks), dim3(kPostThreads), 0, s, p);
+    PBD_LAUNCH(k_post_rank, dim3(rblocks), dim3(kPostThreads), 0, s, p);
+    // each frame is suppressed on a canvas of its own kind: one launch over the frames whose canvas fits in LDS, one over the rest
+    if (nlds > 0) {
+        static const bool lds_limit_set = [] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_post_nms<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kPostLdsCanvasMax);
+            return true;
+        }();
+        (void)lds_limit_set;
+        PostParams q = p;
+        q.flist = lds_frames;
+        const unsigned lds = (unsigned)std::max<size_t>(lds_words * sizeof(uint32_t), 16);
+        PBD_LAUNCH(k_post_nms<true>, dim3(nlds), dim3(post_nms_threads<true>()), lds, s, q);
+    }
+    if (nglb > 0) {
+        PostParams q = p;
+        q.flist = glb_frames;
+        PBD_LAUNCH(k_post_nms<false>, dim3(nglb), dim3(post_nms_threads<false>()), 0, s, q);
     }
     PBD_LAUNCH(k_post_emit, dim3(p.nframes), dim3(kPostThreads), 0, s, p);
 }

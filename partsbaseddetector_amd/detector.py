@@ -33,6 +33,7 @@ class Candidate:
     frame: int = 0
     level: int = 0
     root: tuple = (0, 0)
+    offset: tuple = (0, 0)   # (x, y) of the region the candidate was found in (detect_regions); boxes are region-relative
 
     def score(self) -> float:  # Candidate.hpp:82
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -349,7 +350,11 @@ class PartsBasedDetector:
         return self.hd.unpack_candidates(buf, n.value)
 
     def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
+        """Equally sized frames: pbd_detect_batch (8-bit, as before).  Frames of different sizes: pbd_detect_frames, one
+        call, the frames' dtype kept when it is one of the four depths (all frames share dtype and channel count)."""
         self._need()
+        if len({tuple(f.shape) for f in frames}) > 1:
+            return self.detect_frames(frames, capacity)
         fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None], np.uint8) for f in frames]
         rows, cols, cn = fr[0].shape
         assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
@@ -359,6 +364,69 @@ class PartsBasedDetector:
         self.hd.check(self.hd.lib.pbd_detect_batch(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn,
                                                    buf.ctypes.data, cap, C.byref(n)))
         return self.hd.unpack_candidates(buf, n.value)
+
+    def detect_frames(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
+        """pbd_detect_frames: frames of any sizes in one call; the records of one detect() per frame, concatenated,
+        `frame` = index in the list."""
+        self._need()
+        fr = [f if f.ndim == 3 else f[:, :, None] for f in frames]
+        dt = fr[0].dtype
+        if any(f.dtype != dt for f in fr):
+            raise PbdError(-1, "one call takes one image dtype: " + ", ".join(sorted({str(f.dtype) for f in fr})))
+        if dt not in _lib.DEPTH_CODE:
+            raise PbdError(-2, f"image dtype {dt}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
+        fr = [np.ascontiguousarray(f) for f in fr]
+        if len({f.shape[2] for f in fr}) != 1:
+            raise PbdError(-1, "one call takes one channel count")
+        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        cap = capacity or self.hd.max_candidates
+        buf = np.zeros(cap * self.hd.stride, np.int32)
+        n = C.c_int()
+        self.hd.check(self.hd.lib.pbd_detect_frames(self.hd.h, len(fr), descs, fr[0].shape[2], _lib.DEPTH_CODE[dt],
+                                                    buf.ctypes.data, cap, C.byref(n)))
+        return self.hd.unpack_candidates(buf, n.value)
+
+    def detect_regions(self, image, rects, capacity: Optional[int] = None) -> List[Candidate]:
+        """Regions (x, y, w, h) of one device image -- a torch uint8 tensor, HWC (or HW), on this detector's device -- in
+        one pbd_detect_frames_device call, read in place.  The work is ordered behind torch's current stream.  Each
+        candidate carries `frame` = index of its region and `offset` = (x, y) of that region: its boxes are in the region's
+        coordinates (as detect(im(roi))), offset them to map into the image."""
+        import torch
+        self._need()
+        if image.dtype != torch.uint8 or image.device.type != "cuda" or image.dim() not in (2, 3):
+            raise PbdError(-1, "detect_regions takes a uint8 HWC (or HW) tensor on the GPU")
+        if image.device.index != self._kw["device"]:
+            raise PbdError(-1, f"the tensor is on {image.device}, this detector on cuda:{self._kw['device']}")
+        H, W = image.shape[0], image.shape[1]
+        cn = image.shape[2] if image.dim() == 3 else 1
+        if image.stride(-1) != 1 or (image.dim() == 3 and image.stride(1) != cn):
+            raise PbdError(-1, "detect_regions needs interleaved pixels (a row may have any pitch)")
+        pitch = image.stride(0)
+        descs = []
+        for (x, y, w, h) in rects:
+            if not (0 <= x and 0 <= y and w > 0 and h > 0 and x + w <= W and y + h <= H):
+                raise PbdError(-1, f"region {(x, y, w, h)} outside the {W}x{H} image")
+            descs.append((image.data_ptr() + y * pitch + x * cn, h, w, pitch))
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(image.device))
+        torch.cuda.ExternalStream(self.hd.stream_ptr(), device=image.device).wait_event(ev)
+        cap = capacity or self.hd.max_candidates
+        buf = np.zeros(cap * self.hd.stride, np.int32)
+        n = C.c_int()
+        self.hd.check(self.hd.lib.pbd_detect_frames_device(self.hd.h, len(descs), _lib.frame_array(descs), cn, 0,
+                                                           buf.ctypes.data, cap, C.byref(n)))
+        out = self.hd.unpack_candidates(buf, n.value)
+        for c in out:
+            c.offset = (int(rects[c.frame][0]), int(rects[c.frame][1]))
+        return out
+
+    def detect_frames_device_out(self, descs, cn: int, frame_offset: int, d_payload_ptr: int, capacity: int,
+                                 depth_code: int = 0) -> None:
+        """pbd_detect_frames_device_out: frames (device pointer, rows, cols, pitch) of any sizes, the candidate list left on
+        the device as detect_batch_device_out leaves it; asynchronous on the handle's stream"""
+        self._need()
+        self.hd.check(self.hd.lib.pbd_detect_frames_device_out(self.hd.h, len(descs), _lib.frame_array(descs), cn, depth_code,
+                                                               frame_offset, d_payload_ptr, capacity))
 
     def submit_batch(self, frames: Sequence[np.ndarray]) -> None:
         """pbd_detect_batch_submit: stage + transfer + enqueue the whole path for `frames` without waiting (at most

@@ -284,6 +284,15 @@ class DeviceBatchGather:
         self.g.begin_device(self.stream)
         return prev
 
+    def submit_frames(self, descs, cn: int, frame_offset: int, root_only: bool = False):
+        """``submit`` for frames of different sizes: descs = (device pointer, rows, cols, pitch) per frame of this rank's
+        share (pbd_detect_frames_device_out); the records' `frame` = frame_offset + index in descs."""
+        pay = self.g.payload
+        self.det.detect_frames_device_out(descs, cn, frame_offset, pay.data_ptr(), self.g.cap_full)
+        prev = self.g.finish(root_only) if self.g.pending else None
+        self.g.begin_device(self.stream)
+        return prev
+
     def collect(self, root_only: bool = False):
         return self.g.finish(root_only) if self.g.pending else None
 
