@@ -4,11 +4,13 @@
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
-//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...]
+//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
 //           in ONE detectBatch call, and each image's candidates are printed, in order, as a single run prints them
+//   --depth: a depth map (PGM, 8- or 16-bit, any size): after the candidate lines, one line "box3d x y z height width depth"
+//           per listed candidate, Candidate::boundingBox3D(im, depth) (PartsBasedDetector::boundingBoxes3D, on the device)
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -53,7 +55,7 @@ static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, flo
 
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
-               int conv_mode)
+               int conv_mode, const Image *depth)
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -108,6 +110,15 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         pbd.detect(im, candidates);
     }
     report(candidates, im, staged, nms, dnms, top);
+    if (depth) {
+        if (!pbd.handle()) pbd.distributeModel(model);
+        const std::vector<Candidate> listed(candidates.begin(), candidates.begin() + std::min<size_t>(candidates.size(), (size_t)top));
+        std::vector<Rect3d> boxes;
+        pbd.boundingBoxes3D(im, *depth, listed, boxes);
+        for (size_t i = 0; i < boxes.size(); ++i)
+            std::printf("box3d %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
+                        boxes[i].depth);
+    }
     return 0;
 }
 
@@ -147,13 +158,14 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]...\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm]\n");
         return -1;
     }
     bool dbl = false, staged = false;
     float nms = -1.f, dnms = -1.f;
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
     std::vector<const char *> also;
+    const char *depth_path = NULL;
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
@@ -163,9 +175,14 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--also") && i + 1 < argc) also.push_back(argv[++i]);
+        else if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depth_path = argv[++i];
     }
     if (!also.empty() && (staged || stream_k > 0)) {
         std::fprintf(stderr, "--also runs one detectBatch call: not with --staged or --stream\n");
+        return -1;
+    }
+    if (!also.empty() && depth_path) {
+        std::fprintf(stderr, "--depth takes the one image of a single run: not with --also\n");
         return -1;
     }
     try {
@@ -184,8 +201,15 @@ int main(int argc, char **argv)
                 if (!readPNM(also[k], pixels[k + 1], ims[k + 1])) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
             return dbl ? run_batch<double>(model, ims, nms, dnms, top, conv_mode) : run_batch<float>(model, ims, nms, dnms, top, conv_mode);
         }
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode);
+        std::vector<uint8_t> dpix;
+        Image depth;
+        if (depth_path && (!readPNM(depth_path, dpix, depth) || depth.channels != 1)) {
+            std::fprintf(stderr, "Depth map not found, or not a PGM\n");
+            return -1;
+        }
+        const Image *dp = depth_path ? &depth : NULL;
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

@@ -160,6 +160,39 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world);
  * rank's levels is not suppression of the union. */
 int pbd_set_nms(pbd_handle *h, int enable, float overlap);
 
+/* 3-D boxes from a depth image (new surface; opt-in, nothing else calls it): the callers' next step after the suppression above,
+ * Candidate::boundingBox3D(im, depth) of every kept candidate (the first step of PointCloudClusterer::computeBoundingBoxes:
+ * cells/detect.cpp:224-255, ros/Node.cpp:183-206, include/PointCloudClusterer.hpp:53-77; include/Candidate.hpp:140-216).
+ * out[6*i .. 6*i+5] = {x, y, z, height, width, depth} of record i (Rect3d member order, include/Rect3.hpp:53-64).
+ * depth[f] is frame f's depth image: one channel, depth_code 0 (8U), 2 (16U), 5 (32F) or 6 (64F), one code per call, any pitch;
+ * im_rows[f] x im_cols[f] is the size of the colour frame the records of frame f were detected in (the depth image may have
+ * another size).  A record's frame index is its `frame` field minus frame_offset.  Records are this handle's
+ * (pbd_candidate_stride), e.g. what any pbd_detect* call returned, with or without pbd_set_nms.  Per record:
+ *   boxes    parts[n] & Rect(0, 0, cols, rows) for each part, then boundingBoxNorm() & the same: centroids cvRound((tl + br) * 0.5),
+ *            cv::meanStdDev of them in double, Rect(xmean - 1.5 xstd, ymean - 1.5 ystd, 3 xstd, 3 ystd) truncated
+ *   scale    x, y, width, height each truncated after the multiplication by dcols / (double)cols or drows / (double)rows
+ *   samples  the depth under every box, in box order (overlaps counted twice), as float; valid: != 0 and not NaN (Inf counts).
+ *            If the first box of non-zero area has no valid sample: the NaN box {NaN, NaN, NaN, 0, 0, 0}.  If every box has zero
+ *            area the reference fails an OpenCV assertion; here that is the NaN box too
+ *   result   the sorted samples resized to 400 (cv::resize INTER_LINEAR, float), filtered with the 35-tap derivative of
+ *            getGaussianKernel(35, 4); from index 200 walk up and down while |d| <= 0.035: z = p[dmin], depth = p[dmax] - z
+ *            (in double); x, y, width, height: boundingBox(), the unclipped hull of the parts
+ * pbd_boxes3d: host records and depth images, host output, synchronous.  PBD_ERR_INVALID, naming the index, before anything is
+ * enqueued: a depth_code other than the four, a non-positive size, a pitch below the row size, a depth image of more than
+ * 2^31 / (max parts + 1) pixels, a record whose frame index is outside 0..nframes-1 or whose nparts is outside 1..max parts.
+ * PBD_ERR_STATE while a batch is in flight.
+ * pbd_boxes3d_device: d_depth[f].data are device pointers (a frame may be a region of a larger device image, read in place, as
+ * the _device frames of pbd_detect_frames_device: pointer and pitch multiples of the element size); the records are the
+ * payload d_payload (word 0 = count, as pbd_detect_batch_device_out leaves it): min(max(word 0, 0), capacity) records are
+ * read, so a -1 payload (a suppression overflow) writes nothing; d_out = double[6 * capacity] on the device.  Asynchronous on
+ * pbd_stream().  A record whose frame index is out of range or whose nparts is outside 1..max parts gets six NaNs.
+ * Neither call touches the resident detect result (pbd_get_stage, pbd_argmin_device_out read it as before). */
+struct pbd_frame;   /* defined with pbd_detect_frames below */
+int pbd_boxes3d(pbd_handle *h, int nframes, const struct pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
+                const int32_t *cand, int ncand, int frame_offset, double *out);
+int pbd_boxes3d_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code, const int *im_rows,
+                       const int *im_cols, const int32_t *d_payload, int capacity, int frame_offset, double *d_out);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -187,7 +220,8 @@ int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, con
 int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacity, int *ncand);
 
 /* ---- PartsBasedDetector<T>::detect (include/PartsBasedDetector.hpp:172-173, src/PartsBasedDetector.cpp:69-95).
- * `depth` of the 3-argument overload is ignored by the reference (:91-93) and has no parameter here. */
+ * `depth` of the 3-argument overload is ignored by the reference (:91-93) and has no parameter here; the callers' use of the
+ * depth image after detection, Candidate::boundingBox3D, is pbd_boxes3d (next to pbd_set_nms). */
 int pbd_detect(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes,
                int32_t *cand, int capacity, int *ncand);
 /* The same for an image of any accepted depth (depth_code as in pbd_features_pyramid); pbd_detect is depth_code 0.

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <limits>
 #include <map>
@@ -79,6 +80,12 @@ struct Image {   // image view: rows x cols x channels, BGR interleaved when cha
     size_t step;   // bytes between rows (cv::Mat::step)
     int depth;     // cv::Mat::depth(): 0 = 8U, 2 = 16U, 5 = 32F, 6 = 64F (src/HOGFeatures.cpp:136-146)
     Image() : data(NULL), rows(0), cols(0), channels(0), step(0), depth(0) {}
+};
+
+// include/Rect3.hpp:53-64: a 3-D box in the reference's member order (x, y, z, height, width, depth)
+struct Rect3d {
+    double x, y, z, height, width, depth;
+    Rect3d() : x(0), y(0), z(0), height(0), width(0), depth(0) {}
 };
 
 class Candidate {
@@ -554,6 +561,38 @@ public:
         if (!h_) throw Error(PBD_ERR_STATE, "detect() before distributeModel()");
         pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
     }
+    // Candidate::boundingBox3D(im, depth) of every candidate (include/Candidate.hpp:140-216), on the device (pbd_boxes3d): the
+    // callers' next step after detect + suppression (cells/detect.cpp:224-255).  `im` gives the colour frame's size, `depth` is
+    // one channel of any accepted depth and any size; every candidate is taken as one of this frame.
+    void boundingBoxes3D(const Image &im, const Image &depth, const std::vector<Candidate> &candidates, std::vector<Rect3d> &boxes)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "boundingBoxes3D() before distributeModel()");
+        if (depth.channels != 1) throw Error(PBD_ERR_INVALID, "the depth image has one channel");
+        const int stride = pbd_candidate_stride(h_);
+        std::vector<int32_t> rec(candidates.size() * (size_t)stride + 1, 0);
+        for (size_t i = 0; i < candidates.size(); ++i) {
+            int32_t *r = &rec[i * stride];
+            const Candidate &c = candidates[i];
+            const float score = c.score();
+            r[1] = c.component_; r[2] = c.level; r[3] = c.root_x; r[4] = c.root_y;
+            std::memcpy(&r[5], &score, sizeof score);
+            r[6] = (int32_t)c.parts_.size();
+            for (size_t k = 0; k < c.parts_.size() && 8 + 4 * k + 3 < (size_t)stride; ++k) {
+                r[8 + 4 * k] = c.parts_[k].x; r[9 + 4 * k] = c.parts_[k].y;
+                r[10 + 4 * k] = c.parts_[k].width; r[11 + 4 * k] = c.parts_[k].height;
+            }
+        }
+        pbd_frame fr;
+        fr.data = depth.data; fr.rows = depth.rows; fr.cols = depth.cols; fr.stride_bytes = depth.step;
+        std::vector<double> out(candidates.size() * 6 + 1);
+        pbdbind::check<HostTraits<T> >(h_, pbd_boxes3d(h_, 1, &fr, depth.depth, &im.rows, &im.cols, rec.data(), (int)candidates.size(), 0, out.data()));
+        boxes.resize(candidates.size());
+        for (size_t i = 0; i < candidates.size(); ++i) {
+            const double *o = &out[6 * i];
+            boxes[i].x = o[0]; boxes[i].y = o[1]; boxes[i].z = o[2];
+            boxes[i].height = o[3]; boxes[i].width = o[4]; boxes[i].depth = o[5];
+        }
+    }
     // new surface: images of any sizes (one depth, one channel count) in one call; candidates[i] = detect(images[i])
     void detectBatch(const std::vector<Image> &images, std::vector<std::vector<Candidate> > &candidates)
     {
@@ -620,20 +659,29 @@ public:
     }
 };
 
-// binary PGM (P5) / PPM (P6, stored RGB -> returned BGR as cv::imread does)
+// binary PGM (P5) / PPM (P6, stored RGB -> returned BGR as cv::imread does); a PGM of maxval 65535 (big-endian samples, a
+// depth map) is returned as 16U (depth 2) in native byte order
 inline bool readPNM(const std::string &path, std::vector<uint8_t> &pix, Image &im)
 {
     std::ifstream in(path.c_str(), std::ios::binary);
     std::string magic;
     int w = 0, h = 0, maxv = 0;
-    if (!(in >> magic >> w >> h >> maxv) || maxv != 255 || (magic != "P5" && magic != "P6")) return false;
+    if (!(in >> magic >> w >> h >> maxv) || (magic != "P5" && magic != "P6")) return false;
+    const bool wide = magic == "P5" && maxv == 65535;
+    if (maxv != 255 && !wide) return false;
     in.get();
     const int cn = magic == "P6" ? 3 : 1;
-    pix.resize((size_t)w * h * cn);
+    const size_t es = wide ? 2 : 1;
+    pix.resize((size_t)w * h * cn * es);
     in.read(reinterpret_cast<char *>(pix.data()), (std::streamsize)pix.size());
     if (!in) return false;
     if (cn == 3) for (size_t i = 0; i < pix.size(); i += 3) std::swap(pix[i], pix[i + 2]);
-    im.data = pix.data(); im.rows = h; im.cols = w; im.channels = cn; im.step = (size_t)w * cn; im.depth = 0;
+    if (wide)
+        for (size_t i = 0; i < pix.size(); i += 2) {
+            const uint16_t v = (uint16_t)(pix[i] << 8 | pix[i + 1]);
+            std::memcpy(&pix[i], &v, 2);
+        }
+    im.data = pix.data(); im.rows = h; im.cols = w; im.channels = cn; im.step = (size_t)w * cn * es; im.depth = wide ? 2 : 0;
     return true;
 }
 

@@ -5,7 +5,7 @@ as hand-written HIP kernels for gfx950 behind the C ABI in include/pbd.h, with a
 the reference's IFeatures / IConvolutionEngine / DynamicProgram / PartsBasedDetector interface.
 """
 from .model import Model, FlatModel, synthetic_model, synthetic_person_model, synthetic_face_model, synthetic_tiny_model  # noqa: F401
-from .synth import synthetic_frame  # noqa: F401
+from .synth import synthetic_frame, synthetic_depth  # noqa: F401
 
 
 def __getattr__(name):

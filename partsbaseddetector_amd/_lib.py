@@ -35,6 +35,7 @@ SYMBOLS = [
     "pbd_detect_batch_device", "pbd_detect_typed", "pbd_detect_batch_submit", "pbd_detect_batch_wait",
     "pbd_detect_batch_device_submit", "pbd_detect_batch_device_out", "pbd_argmin_device_out", "pbd_stream", "pbd_get_stage", "pbd_profile_enable", "pbd_profile_reset", "pbd_profile_read",
     "pbd_kernel_name", "pbd_synchronize", "pbd_detect_frames", "pbd_detect_frames_device", "pbd_detect_frames_device_out",
+    "pbd_boxes3d", "pbd_boxes3d_device",
 ]
 
 
@@ -133,6 +134,9 @@ def load():
     lib.pbd_detect_frames_device.argtypes = lib.pbd_detect_frames.argtypes
     lib.pbd_detect_frames_device_out.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                  C.c_int]
+    lib.pbd_boxes3d.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                C.c_int, C.c_int, C.c_void_p]
+    lib.pbd_boxes3d_device.argtypes = lib.pbd_boxes3d.argtypes
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

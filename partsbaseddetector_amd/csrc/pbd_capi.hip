@@ -313,6 +313,11 @@ struct pbd_handle {
     DevBuf tmp, dt, IxRaw, IyRaw, stk, scales_tmp, find_blk;
     DevBuf post_ws;                  // workspace of the post-processing stage (pbd_kernels_post.hip)
     DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
+    // pbd_boxes3d*: the frame table (staged in pinned memory, rewritten only once its previous copy has completed); the host
+    // form's depth images, records and boxes.  Never the detect path's buffers: the resident result stays readable.
+    HostBuf b3_tab_host;
+    DevBuf b3_tab, b3_depth, b3_rec, b3_out;
+    Event b3_tab_copied;
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -1954,6 +1959,87 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     return run_dp_mixed(h, P);
 }
 
+// ---- 3-D boxes from a depth image (pbd_boxes3d*; pbd_kernels_depth.hip)
+// the derivative-of-Gaussian taps of Candidate::boundingBox3D (include/Candidate.hpp:190-193), once, with the C library's exp:
+//   g = getGaussianKernel(35, 4, CV_32F): t_i = exp(scale2X * x_i * x_i), x_i = i - 17, scale2X = -0.5 / 16; cf_i = (float)t_i,
+//       sum += cf_i in double, then cf_i = (float)(cf_i * (1. / sum))
+//   dog = filter2D(g, -1, [-1 0 1]^T): correlation, BORDER_REFLECT_101, s = 0; s += k * x per non-zero tap, in float
+const float *boxes3d_taps()
+{
+    static const struct Taps {
+        float v[kB3Taps];
+        Taps()
+        {
+            float g[kB3Taps];
+            const double scale2X = -0.5 / (4.0 * 4.0);
+            double sum = 0;
+            for (int i = 0; i < kB3Taps; ++i) {
+                const double x = i - (kB3Taps - 1) * 0.5;
+                g[i] = (float)exp(scale2X * x * x);
+                sum += g[i];
+            }
+            sum = 1. / sum;
+            for (int i = 0; i < kB3Taps; ++i) g[i] = (float)(g[i] * sum);
+            for (int i = 0; i < kB3Taps; ++i) {
+                const int a = i == 0 ? 1 : i - 1, b = i == kB3Taps - 1 ? kB3Taps - 2 : i + 1;
+                float s = 0.f;
+                s = s + -1.f * g[a];
+                s = s + 1.f * g[b];
+                v[i] = s;
+            }
+        }
+    } taps;
+    return taps.v;
+}
+
+// every check of a pbd_boxes3d* call's frames before anything is enqueued
+int check_boxes3d_frames(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
+                         bool host)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    if (!depth_size(depth_code))
+        return fail(h, PBD_ERR_INVALID, "depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F)", depth_code);
+    const size_t es = depth_size(depth_code);
+    for (int f = 0; f < nframes; ++f) {
+        const pbd_frame &d = depth[f];
+        if (!d.data || d.rows < 1 || d.cols < 1 || im_rows[f] < 1 || im_cols[f] < 1)
+            return fail(h, PBD_ERR_INVALID, "frame %d: depth %dx%d at %p, colour frame %dx%d", f, d.rows, d.cols, d.data, im_rows[f],
+                        im_cols[f]);
+        // every box lies inside the depth image: the samples of one record (boxes counted with their overlaps) fit an int
+        if ((unsigned long long)kB3MaxBoxes * (unsigned long long)d.rows * (unsigned long long)d.cols >= (1ull << 31))
+            return fail(h, PBD_ERR_INVALID, "frame %d: depth image %dx%d too large", f, d.rows, d.cols);
+        if (d.stride_bytes < (size_t)d.cols * es)
+            return fail(h, PBD_ERR_INVALID, "frame %d: stride %zu < row bytes %zu", f, d.stride_bytes, (size_t)d.cols * es);
+        if (!host && (reinterpret_cast<uintptr_t>(d.data) % es || d.stride_bytes % es))
+            return fail(h, PBD_ERR_INVALID, "frame %d: device pointer %p / stride %zu not a multiple of the %zu-byte element", f, d.data,
+                        d.stride_bytes, es);
+    }
+    return PBD_OK;
+}
+
+// the frame table to the device (through the pinned staging buffer) and the kernel, on the handle's stream
+int enqueue_boxes3d(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, const int32_t *d_payload, int capacity,
+                    int frame_offset, double *d_out)
+{
+    const size_t bytes = tab.size() * sizeof(Box3dFrame);
+    if (h->b3_tab_copied.p) HIPCHK(h, hipEventSynchronize(h->b3_tab_copied.p));   // the previous call's table has left the staging buffer
+    else HIPCHK(h, hipEventCreateWithFlags(&h->b3_tab_copied.p, hipEventDisableTiming));
+    HIPCHK(h, h->b3_tab_host.ensure(bytes, bytes * 2 + 256));
+    HIPCHK(h, h->b3_tab.ensure(bytes));
+    memcpy(h->b3_tab_host.p, tab.data(), bytes);
+    HIPCHK(h, hipMemcpyAsync(h->b3_tab.p, h->b3_tab_host.p, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->b3_tab_copied.p, h->stream));
+    Boxes3dParams bp{};
+    bp.in = d_payload; bp.in_cap = capacity;
+    bp.stride = stride(h); bp.max_parts = h->max_parts;
+    bp.frames = h->b3_tab.as<Box3dFrame>(); bp.nframes = (int)tab.size(); bp.frame_offset = frame_offset;
+    bp.depth = depth_code; bp.out = d_out;
+    memcpy(bp.dog, boxes3d_taps(), sizeof bp.dog);
+    launch_boxes3d(bp, capacity, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // a (frame, level) of the resident result -> (frame index into the buffers, level of the plan); mixed plans: frame 0, the
 // frame's level in the virtual table
 bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
@@ -2522,6 +2608,64 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
         if (int rc = enqueue_argmin_out(h, *r.plan, r.frames, frame_offset, d_payload, capacity)) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
+    });
+}
+
+// Candidate::boundingBox3D(im, depth) per record (include/Candidate.hpp:140-216).  See include/pbd.h.
+int pbd_boxes3d(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
+                const int32_t *cand, int ncand, int frame_offset, double *out)
+{
+    return entry(h, depth && im_rows && im_cols && (ncand <= 0 || (cand && out)), kIdle, [&]() -> int {
+        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+        if (int rc = check_boxes3d_frames(h, nframes, depth, depth_code, im_rows, im_cols, true)) return rc;
+        const int stride = ::stride(h);
+        for (int i = 0; i < ncand; ++i) {
+            const int32_t *r = cand + (size_t)i * stride;
+            const long long f = (long long)r[0] - frame_offset;
+            if (f < 0 || f >= nframes)
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
+            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
+        }
+        if (ncand == 0) return PBD_OK;
+        // the depth images, packed with dense rows, into the handle's own buffer
+        const size_t es = depth_size(depth_code);
+        size_t total = 0;
+        for (int f = 0; f < nframes; ++f) total += (size_t)depth[f].rows * depth[f].cols * es;
+        HIPCHK(h, h->b3_depth.ensure(total + 8));
+        HIPCHK(h, h->b3_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+        HIPCHK(h, h->b3_out.ensure((size_t)ncand * 6 * sizeof(double)));
+        std::vector<Box3dFrame> tab(nframes);
+        size_t off = 0;
+        for (int f = 0; f < nframes; ++f) {
+            const size_t row_bytes = (size_t)depth[f].cols * es;
+            uint8_t *dst = h->b3_depth.as<uint8_t>() + off;
+            HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, depth[f].data, depth[f].stride_bytes, row_bytes, depth[f].rows,
+                                       hipMemcpyHostToDevice, h->stream));
+            tab[f] = Box3dFrame{dst, depth[f].rows, depth[f].cols, (long long)row_bytes, im_rows[f], im_cols[f]};
+            off += row_bytes * depth[f].rows;
+        }
+        HIPCHK(h, hipMemcpyAsync(h->b3_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->b3_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 h->stream));
+        if (int rc = enqueue_boxes3d(h, tab, depth_code, h->b3_rec.as<int32_t>(), ncand, frame_offset, h->b3_out.as<double>())) return rc;
+        HIPCHK(h, hipMemcpyAsync(out, h->b3_out.p, (size_t)ncand * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_boxes3d_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, const int *im_rows, const int *im_cols,
+                       const int32_t *d_payload, int capacity, int frame_offset, double *d_out)
+{
+    return entry(h, d_depth && im_rows && im_cols && d_payload && (capacity <= 0 || d_out), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_boxes3d_frames(h, nframes, d_depth, depth_code, im_rows, im_cols, false)) return rc;
+        if (capacity == 0) return PBD_OK;
+        std::vector<Box3dFrame> tab(nframes);
+        for (int f = 0; f < nframes; ++f)
+            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
+                                (long long)d_depth[f].stride_bytes, im_rows[f], im_cols[f]};
+        return enqueue_boxes3d(h, tab, depth_code, d_payload, capacity, frame_offset, d_out);
     });
 }
 

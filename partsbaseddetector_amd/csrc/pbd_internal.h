@@ -290,6 +290,29 @@ struct PostParams {
     const int *flist;
 };
 
+// 3-D box of each record from a depth image (pbd_boxes3d; pbd_kernels_depth.hip)
+constexpr int kB3Taps = 35;                   // getGaussianKernel(35, 4) filtered with [-1 0 1]^T (include/Candidate.hpp:190-193)
+constexpr int kB3MaxBoxes = kWalkMaxParts + 1;   // the parts, then boundingBoxNorm()
+constexpr int kB3MaxGrid = 2048;              // workgroups of one launch (one record each, grid-stride over the rest)
+// one depth frame: device pointer, size and row pitch in bytes (a region of a larger image reads it in place), and the size of
+// the colour frame its records were detected in
+struct Box3dFrame {
+    const uint8_t *data;
+    int rows, cols;
+    long long pitch;
+    int im_rows, im_cols;
+};
+struct Boxes3dParams {
+    const int32_t *in;            // payload: word 0 = records (negative: none), then the records
+    int in_cap;                   // records the payload holds: min(max(word 0, 0), in_cap) are read
+    int stride, max_parts;
+    const Box3dFrame *frames;     // [nframes]; a record's frame is its `frame` field - frame_offset
+    int nframes, frame_offset;
+    int depth;                    // kDepth8U / 16U / 32F / 64F, one per call
+    double *out;                  // [record][6]: x, y, z, height, width, depth (Rect3d member order, include/Rect3.hpp:53-64)
+    float dog[kB3Taps];           // the derivative-of-Gaussian taps, computed on the host (boxes3d_taps)
+};
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -361,5 +384,7 @@ void launch_postprocess(const PostParams &p, hipStream_t s);
 // with theirs in p.canvas
 void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nlds, size_t lds_words, const int *glb_frames,
                               int nglb, hipStream_t s);
+// `grid` workgroups (capped at kB3MaxGrid), each computing one record at a time
+void launch_boxes3d(const Boxes3dParams &p, int grid, hipStream_t s);
 
 }  // namespace pbd

@@ -5,13 +5,14 @@ C ABI (include/pbd.h).  Same names and argument meaning as the reference:
     IConvolutionEngine / Spatial...       include/IConvolutionEngine.hpp:44-68, src/SpatialConvolutionEngine.cpp
     DynamicProgram<T>                     include/DynamicProgram.hpp:74-75, src/DynamicProgram.cpp
     PartsBasedDetector<T>                 include/PartsBasedDetector.hpp:152-175, src/PartsBasedDetector.cpp
-    Candidate                             include/Candidate.hpp:56-99
+    Candidate                             include/Candidate.hpp:56-216
 
 Every compute call runs HIP kernels through libpbd_hip.so; nothing here computes on the CPU.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -55,6 +56,70 @@ class Candidate:
                 x, y = x1, y1
         return x, y, w, h
 
+    def boundingBoxNorm(self):
+        """Candidate.hpp:117-130: Rect(mean - 1.5 std, 3 std) of the part centroids, as (x, y, w, h).  A centroid is
+        cvRound((tl + br) * 0.5) (half to even); cv::meanStdDev sums in double; the double -> int conversions truncate."""
+        s = [0.0, 0.0]
+        sq = [0.0, 0.0]
+        for x, y, w, h in (tuple(int(v) for v in r) for r in self.parts):
+            for c, v in enumerate((float(round((2 * x + w) * 0.5)), float(round((2 * y + h) * 0.5)))):
+                s[c] += v
+                sq[c] += v * v
+        scale = 1.0 / len(self.parts)
+        mean = [s[c] * scale for c in range(2)]
+        std = [math.sqrt(max(sq[c] * scale - mean[c] * mean[c], 0.0)) for c in range(2)]
+        return int(mean[0] - 1.5 * std[0]), int(mean[1] - 1.5 * std[1]), int(3 * std[0]), int(3 * std[1])
+
+    def boundingBox3D(self, im_shape, depth: np.ndarray) -> tuple:
+        """Candidate.hpp:140-216 on the host, in numpy: (x, y, z, height, width, depth) (Rect3d member order, Rect3.hpp:53-64).
+        `im_shape` = (rows, cols) of the colour frame, `depth` a 2-D uint8 / uint16 / float32 / float64 image of any size.
+        The yardstick of pbd_boxes3d (include/pbd.h states the contract); it restates cv::resize INTER_LINEAR (float), cv::filter2D
+        (float, BORDER_REFLECT_101, zero taps skipped) and getGaussianKernel.  Where the reference fails an OpenCV assertion
+        (every box of zero area) the result is the NaN box, as on the device."""
+        rows, cols = int(im_shape[0]), int(im_shape[1])
+        drows, dcols = depth.shape[:2]
+        sx, sy = dcols / float(cols), drows / float(rows)
+        nan_box = (math.nan, math.nan, math.nan, 0.0, 0.0, 0.0)
+        boxes = [_rect_and(tuple(int(v) for v in r), (0, 0, cols, rows)) for r in self.parts]
+        boxes.append(_rect_and(self.boundingBoxNorm(), (0, 0, cols, rows)))
+        chunks, m = [], 0
+        for x, y, w, h in boxes:
+            x, y, w, h = _rect_and((int(x * sx), int(y * sy), int(w * sx), int(h * sy)), (0, 0, dcols, drows))
+            if w <= 0 or h <= 0:
+                continue                                      # part.empty()
+            v = depth[y:y + h, x:x + w].astype(np.float32).ravel()    # Mat_<float> assignment: 64F rounds to nearest
+            v = v[(v != 0) & ~np.isnan(v)]
+            chunks.append(v)
+            m += v.size
+            if m == 0:
+                return nan_box                                # the first non-empty box held no valid sample
+        if m == 0:
+            return nan_box
+        S = np.sort(np.concatenate(chunks))
+        p = _resize_linear_400(S)
+        d = np.zeros(400, np.float32)
+        idx = np.arange(400)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for t, k in enumerate(_dog_taps()):
+                if k == 0:
+                    continue
+                j = np.abs(idx + t - 17)
+                j = np.where(j >= 400, 2 * 399 - j, j)
+                d = d + k * p[j]
+        mid = 200
+        dmax = dmin = mid
+        for m_ in range(mid, 400):
+            if float(abs(d[m_])) > 0.035:
+                break
+            dmax = m_
+        for m_ in range(mid, -1, -1):
+            if float(abs(d[m_])) > 0.035:
+                break
+            dmin = m_
+        bx, by, bw, bh = self.boundingBox()
+        z0, z1 = float(p[dmin]), float(p[dmax])
+        return float(bx), float(by), z0, float(bh), float(bw), z1 - z0
+
     @staticmethod
     def nonMaximaSuppression(im_shape, candidates: List["Candidate"], overlap: float = 0.0) -> None:
         """Candidate.hpp:277-304: greedy paint-the-canvas suppression on the bounding boxes, in the given
@@ -77,6 +142,46 @@ class Candidate:
             candidates[keep] = cand
             keep += 1
         del candidates[keep:]
+
+
+def _rect_and(a, b):
+    """cv::Rect operator& of (x, y, w, h) tuples: an empty intersection is (0, 0, 0, 0)"""
+    x1, y1 = max(a[0], b[0]), max(a[1], b[1])
+    w, h = min(a[0] + a[2], b[0] + b[2]) - x1, min(a[1] + a[3], b[1] + b[3]) - y1
+    return (x1, y1, w, h) if w > 0 and h > 0 else (0, 0, 0, 0)
+
+
+def _dog_taps() -> np.ndarray:
+    """filter2D(getGaussianKernel(35, 4, CV_32F), [-1 0 1]^T) (include/Candidate.hpp:190-193), float32[35]"""
+    g = np.zeros(35, np.float32)
+    total = 0.0
+    for i in range(35):
+        x = i - 17.0
+        g[i] = np.float32(math.exp(-0.5 / 16.0 * x * x))
+        total += float(g[i])
+    total = 1.0 / total
+    for i in range(35):
+        g[i] = np.float32(float(g[i]) * total)
+    dog = np.zeros(35, np.float32)
+    for i in range(35):
+        a, b = (1 if i == 0 else i - 1), (33 if i == 34 else i + 1)
+        dog[i] = (np.float32(0) + np.float32(-1) * g[a]) + np.float32(1) * g[b]
+    return dog
+
+
+def _resize_linear_400(S: np.ndarray) -> np.ndarray:
+    """cv::resize(S, Size(1, 400), INTER_LINEAR) of a sorted float32 column: p = S[r0] * (1 - fy) + S[r1] * fy in float32"""
+    M = S.size
+    if M == 400:
+        return S.copy()
+    scale = 1.0 / (400.0 / M)
+    fy = ((np.arange(400) + 0.5) * scale - 0.5).astype(np.float32)
+    sy = np.floor(fy)
+    fy = (fy - sy).astype(np.float32)
+    sy = sy.astype(np.int64)
+    r0, r1 = np.clip(sy, 0, M - 1), np.clip(sy + 1, 0, M - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return S[r0] * (np.float32(1) - fy) + S[r1] * fy
 
 
 class Handle:
@@ -159,6 +264,43 @@ class Handle:
             out.append(Candidate(parts=r[8:8 + 4 * npart].reshape(npart, 4).copy(), confidence=conf,
                                  component=int(r[1]), frame=int(r[0]), level=int(r[2]), root=(int(r[3]), int(r[4]))))
         return out
+
+    def pack_candidates(self, candidates: Sequence[Candidate]) -> np.ndarray:
+        """records (n, stride) int32 of Candidate objects (the layout unpack_candidates reads)"""
+        rec = np.zeros((len(candidates), self.stride), np.int32)
+        for i, c in enumerate(candidates):
+            parts = np.asarray(c.parts, np.int32).reshape(-1, 4)
+            rec[i, :8] = (c.frame, c.component, c.level, c.root[0], c.root[1], 0, len(parts), 0)
+            rec[i, 5] = np.float32(c.score()).view(np.int32)
+            rec[i, 8:8 + parts.size] = parts.ravel()
+        return rec
+
+    def boxes3d(self, depths: Sequence[np.ndarray], im_shapes, records: np.ndarray, frame_offset: int = 0) -> np.ndarray:
+        """pbd_boxes3d: Candidate::boundingBox3D of every record (n, stride) on the device, (n, 6) float64 in Rect3d member
+        order.  depths[f]: 2-D depth image of frame f (one dtype for the call, rows of any pitch); im_shapes[f] = (rows, cols)
+        of the colour frame; a record's frame index is its `frame` field - frame_offset."""
+        dt = np.dtype(depths[0].dtype)
+        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
+            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
+        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
+        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        rec = np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
+        out = np.zeros((len(rec), 6), np.float64)
+        self.check(self.lib.pbd_boxes3d(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
+                                        rec.ctypes.data if rec.size else None, len(rec), frame_offset,
+                                        out.ctypes.data if out.size else None))
+        return out
+
+    def boxes3d_device(self, descs, depth_code: int, im_shapes, d_payload_ptr: int, capacity: int, frame_offset: int,
+                       d_out_ptr: int) -> None:
+        """pbd_boxes3d_device: the records of a device payload (as detect_batch_device_out leaves it), depth frames
+        (device pointer, rows, cols, pitch), boxes into double[6 * capacity] at d_out_ptr; asynchronous on the handle's stream"""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        self.check(self.lib.pbd_boxes3d_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
+                                               _lib.ptr(ic, C.c_int), d_payload_ptr, capacity, frame_offset, d_out_ptr))
 
     def profile(self, on=True):
         """on: False / 0 off, True / 1 every kernel, 2 the convolution only (pbd_profile_enable)"""
@@ -348,6 +490,18 @@ class PartsBasedDetector:
                                                        _lib.DEPTH_CODE[im.dtype], buf.ctypes.data, cap, C.byref(n)))
         self.features_._scales = self.hd.plan(rows, cols)["scales"]
         return self.hd.unpack_candidates(buf, n.value)
+
+    def boundingBoxes3D(self, candidates: Sequence[Candidate], depths, im_shapes) -> np.ndarray:
+        """Candidate::boundingBox3D(im, depth) of every candidate, on the device (pbd_boxes3d): (n, 6) float64 rows
+        {x, y, z, height, width, depth} (Rect3d member order).  `depths` / `im_shapes`: the depth image and the colour frame's
+        (rows, cols) of every frame index the candidates carry (a single image / shape for one frame).  Equal to
+        [c.boundingBox3D(im_shapes[c.frame], depths[c.frame]) for c in candidates], bit for bit."""
+        self._need()
+        if isinstance(depths, np.ndarray):
+            depths = [depths]
+        if len(im_shapes) and np.isscalar(im_shapes[0]):
+            im_shapes = [im_shapes]
+        return self.hd.boxes3d(list(depths), list(im_shapes), self.hd.pack_candidates(candidates))
 
     def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
         """Equally sized frames: pbd_detect_batch (8-bit, as before).  Frames of different sizes: pbd_detect_frames, one

@@ -83,3 +83,52 @@ def synthetic_frame(seed: int, rows: int = 480, cols: int = 640, channels: int =
 # 1-based parent table of the 26-part person tree (parent < child as asserted
 # in matlab/detection/detect_fast.m:76)
 PERSON_PA = [0, 1, 2, 3, 4, 5, 6, 3, 8, 9, 10, 11, 12, 13, 2, 15, 16, 17, 18, 15, 20, 21, 22, 23, 24, 25]
+
+
+def synthetic_depth(seed: int, rows: int = 480, cols: int = 640, dtype=np.uint16, holes: bool = True, inf: bool = False) -> np.ndarray:
+    """Deterministic depth image (rows, cols) of `dtype` (uint8, uint16, float32 or float64) for the 3-D box stage.
+
+    A tilted background plane (millimetres, about 2-4 m), 6 nearer blobs (rectangles at 0.6-1.8 m with a gentle slope of their
+    own), +-3 mm noise; with `holes`, 24 rectangles of missing depth (0), and for the float types NaN in every other hole;
+    with `inf`, a few pixels of +Inf and -Inf (float types only).  Float images hold metres (millimetres / 1000, one correctly
+    rounded division).  Integer arithmetic otherwise, so the same seed gives the same image everywhere."""
+    dtype = np.dtype(dtype)
+    y = np.arange(rows, dtype=np.int64)[:, None]
+    x = np.arange(cols, dtype=np.int64)[None, :]
+    prm = randint(seed, 4, 0, 1000, stream=11)
+    z = 2000 + prm[0] + ((y * (1 + prm[1] % 3) * 1000) // max(rows, 1)) + ((x * (prm[2] % 5)) * 200) // max(cols, 1)
+    z = np.broadcast_to(z, (rows, cols)).copy()
+    blob = uniform_u32(seed, 6 * 6, stream=12).reshape(6, 6)
+    for b in blob:
+        by, bx = int(b[0] % rows), int(b[1] % cols)
+        bh, bw = 4 + int(b[2] % max(rows // 3, 1)), 4 + int(b[3] % max(cols // 4, 1))
+        near = 600 + int(b[4] % 1200)
+        slope = int(b[5] % 7) - 3
+        yy = np.arange(by, min(by + bh, rows), dtype=np.int64)[:, None]
+        z[by:by + bh, bx:bx + bw] = near + slope * (yy - by)
+    z = z + (uniform_u32(seed, rows * cols, stream=13) % 7 - 3).reshape(rows, cols)
+    hole = np.zeros((rows, cols), np.int8)
+    if holes:
+        hr = uniform_u32(seed, 24 * 4, stream=14).reshape(24, 4)
+        for k, r in enumerate(hr):
+            hy, hx = int(r[0] % rows), int(r[1] % cols)
+            hh, hw = 1 + int(r[2] % max(rows // 12, 1)), 1 + int(r[3] % max(cols // 12, 1))
+            hole[hy:hy + hh, hx:hx + hw] = 1 + (k & 1)
+    if dtype == np.uint8:
+        out = np.clip(z // 16, 1, 255).astype(np.uint8)
+    elif dtype == np.uint16:
+        out = np.clip(z, 1, 65535).astype(np.uint16)
+    elif dtype in (np.float32, np.float64):
+        out = (z.astype(np.float64) / 1000.0).astype(dtype)
+    else:
+        raise ValueError(f"depth dtype {dtype}: uint8, uint16, float32 or float64")
+    out[hole == 1] = 0
+    if dtype.kind == "f":
+        out[hole == 2] = np.nan
+        if inf:
+            pts = uniform_u32(seed, 16, stream=15)
+            for k in range(8):
+                out[int(pts[2 * k] % rows), int(pts[2 * k + 1] % cols)] = np.inf if k & 1 else -np.inf
+    else:
+        out[hole == 2] = 0
+    return out
