@@ -4,13 +4,18 @@
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
-//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm]
+//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
 //           in ONE detectBatch call, and each image's candidates are printed, in order, as a single run prints them
-//   --depth: a depth map (PGM, 8- or 16-bit, any size): after the candidate lines, one line "box3d x y z height width depth"
+//   --depth: a depth map (PGM, 8- or 16-bit, or grey PFM, float; any size): after the candidate lines, one line "box3d x y z height width depth"
 //           per listed candidate, Candidate::boundingBox3D(im, depth) (PartsBasedDetector::boundingBoxes3D, on the device)
+//   --camera FX,FY,CX,CY: with --depth, the rest of PointCloudClusterer on the device.  The depth map's values become float
+//           unscaled (as cv_bridge's TYPE_32FC1 conversion; a grey PFM map is float already), the cloud is back-projected from
+//           it (NaN where the depth is 0 or not finite);
+//           then per listed candidate: "box3d_cam x y z height width depth", "centres N x y z ..." (the part centres), and
+//           "object SIZE x y z" (the kept cluster's size and centroid)
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -53,9 +58,50 @@ static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, flo
     return 0;
 }
 
+// the depth map as float, unscaled; the organized cloud back-projected from it (x = ray(c, r) * d, rounded to float; NaN where
+// d is 0 or not finite); camera boxes, part centres and one kept cluster per listed candidate
+template <typename T>
+static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Image &depth, const pbd_pinhole &cam,
+                         const std::vector<Candidate> &listed)
+{
+    std::vector<float> df((size_t)depth.rows * depth.cols), cloud(df.size() * 3);
+    for (int r = 0; r < depth.rows; ++r)
+        for (int c = 0; c < depth.cols; ++c) {
+            const uint8_t *row = static_cast<const uint8_t *>(depth.data) + r * depth.step;
+            const float d = depth.depth == 5 ? reinterpret_cast<const float *>(row)[c]
+                            : depth.depth == 2 ? (float)reinterpret_cast<const uint16_t *>(row)[c] : (float)row[c];
+            df[(size_t)r * depth.cols + c] = d;
+            float *p = &cloud[((size_t)r * depth.cols + c) * 3];
+            if (d == 0 || !std::isfinite(d)) {
+                p[0] = p[1] = p[2] = std::numeric_limits<float>::quiet_NaN();
+                continue;
+            }
+            const double rx = (((double)c - cam.cx) - cam.tx) / cam.fx, ry = (((double)r - cam.cy) - cam.ty) / cam.fy;
+            p[0] = (float)(rx * (double)d); p[1] = (float)(ry * (double)d); p[2] = d;
+        }
+    Image dimg;
+    dimg.data = df.data(); dimg.rows = depth.rows; dimg.cols = depth.cols; dimg.channels = 1;
+    dimg.step = (size_t)depth.cols * sizeof(float); dimg.depth = 5;
+    std::vector<Rect3d> boxes;
+    std::vector<std::vector<Point3f> > centres;
+    pbd.computeBoundingBoxes(im, dimg, cam, listed, boxes, centres);
+    pbd_cloud pc;
+    pc.data = cloud.data(); pc.rows = depth.rows; pc.cols = depth.cols; pc.point_stride = 12; pc.row_stride = (size_t)depth.cols * 12;
+    std::vector<std::vector<int> > clusters;
+    std::vector<Point3f> objects;
+    pbd.clusterObjects(pc, boxes, clusters, objects);
+    for (size_t i = 0; i < boxes.size(); ++i) {
+        std::printf("box3d_cam %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
+                    boxes[i].depth);
+        std::printf("centres %zu", centres[i].size());
+        for (size_t j = 0; j < centres[i].size(); ++j) std::printf(" %.9g %.9g %.9g", centres[i][j].x, centres[i][j].y, centres[i][j].z);
+        std::printf("\nobject %zu %.9g %.9g %.9g\n", clusters[i].size(), objects[i].x, objects[i].y, objects[i].z);
+    }
+}
+
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
-               int conv_mode, const Image *depth)
+               int conv_mode, const Image *depth, const pbd_pinhole *camera)
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -118,6 +164,7 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         for (size_t i = 0; i < boxes.size(); ++i)
             std::printf("box3d %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
                         boxes[i].depth);
+        if (camera) camera_lines(pbd, im, *depth, *camera, listed);
     }
     return 0;
 }
@@ -158,7 +205,7 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -166,6 +213,8 @@ int main(int argc, char **argv)
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
     std::vector<const char *> also;
     const char *depth_path = NULL;
+    bool have_camera = false;
+    pbd_pinhole camera = {0, 0, 0, 0, 0, 0};
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
@@ -176,9 +225,17 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--also") && i + 1 < argc) also.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depth_path = argv[++i];
+        else if (!std::strcmp(argv[i], "--camera") && i + 1 < argc) {
+            have_camera = std::sscanf(argv[++i], "%lf,%lf,%lf,%lf", &camera.fx, &camera.fy, &camera.cx, &camera.cy) == 4;
+            if (!have_camera) { std::fprintf(stderr, "--camera takes fx,fy,cx,cy\n"); return -1; }
+        }
     }
     if (!also.empty() && (staged || stream_k > 0)) {
         std::fprintf(stderr, "--also runs one detectBatch call: not with --staged or --stream\n");
+        return -1;
+    }
+    if (have_camera && !depth_path) {
+        std::fprintf(stderr, "--camera needs --depth\n");
         return -1;
     }
     if (!also.empty() && depth_path) {
@@ -203,13 +260,14 @@ int main(int argc, char **argv)
         }
         std::vector<uint8_t> dpix;
         Image depth;
-        if (depth_path && (!readPNM(depth_path, dpix, depth) || depth.channels != 1)) {
-            std::fprintf(stderr, "Depth map not found, or not a PGM\n");
+        if (depth_path && !readPFM(depth_path, dpix, depth) && (!readPNM(depth_path, dpix, depth) || depth.channels != 1)) {
+            std::fprintf(stderr, "Depth map not found, or not a PGM or grey PFM\n");
             return -1;
         }
         const Image *dp = depth_path ? &depth : NULL;
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp);
+        const pbd_pinhole *cp = have_camera ? &camera : NULL;
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

@@ -193,6 +193,81 @@ int pbd_boxes3d(pbd_handle *h, int nframes, const struct pbd_frame *depth, int d
 int pbd_boxes3d_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code, const int *im_rows,
                        const int *im_cols, const int32_t *d_payload, int capacity, int frame_offset, double *d_out);
 
+/* Camera boxes and part centres (new surface; opt-in): the rest of PointCloudClusterer::computeBoundingBoxes
+ * (include/PointCloudClusterer.hpp:53-153; cells/detect.cpp:224-275, ros/Node.cpp:183-230).
+ * Pinhole model, this library's contract: ray(u, v) = (((u - cx) - tx) / fx, ((v - cy) - ty) / fy, 1.0) in double, which is
+ * image_geometry's PinholeCameraModel::projectPixelTo3dRay as the ROS node binds it (ros/Node.cpp:210).  The ECTO cell's
+ * image_pipeline projector (cells/detect.cpp:193-200) is not pinned.  One pbd_pinhole per frame; a non-finite or zero fx / fy
+ * is PBD_ERR_INVALID naming the frame.
+ * Per record (frame index = frame - frame_offset, as pbd_boxes3d), in double unless said otherwise:
+ *   cube     what pbd_boxes3d computes for the record.  A NaN in any of its six values skips the record (the reference's
+ *            `continue`): camera box {0,0,0,0,0,0}, ncentres 0, dense 1
+ *   box      tl = ray(cube.x, cube.y) * cube.z, br = ray(cube.x + cube.width, cube.y + cube.height) * (cube.z + cube.depth);
+ *            out = Rect3d(tl, br) = {tl.x, tl.y, tl.z, br.y - tl.y, br.x - tl.x, br.z - tl.z} (Rect3d member order)
+ *   centres  part j: part &= Rect(0, 0, im_cols, im_rows) (empty -> Rect()); centre pixel (x + w/2, y + h/2), int division;
+ *            avg = double sum of the float depth samples in row-major order, / (w*h) when w*h != 0; the point is
+ *            ray(centre) * avg with each component rounded to float (pcl::PointXYZ).  An empty part gives ray(0,0) * 0.0
+ *            (signed zeros).  dense = 0 when any component of any centre is NaN; ncentres = nparts
+ *   samples  PBD_PARTS_LITERAL (the default, a reference quirk kept as the Iy composition quirk is): rows x .. x+h-1, columns
+ *            y .. y+w-1, the reference's transposed loop (:111-120).  PBD_PARTS_XY: rows y .. y+h-1, columns x .. x+w-1, the box
+ *            in its own orientation.  Project decision: a non-empty part whose sample rectangle leaves the depth image (the
+ *            reference reads outside it, undefined behaviour) has the centre {NaN, NaN, NaN}
+ * The depth images must be 32F (depth_code 5, what the reference reads, :113); any other code is PBD_ERR_UNSUPPORTED.
+ * Outputs: box double[6*n], centres float[3*max_parts*n] (record i, part j at 3*(i*max_parts + j)), ncentres int32[n], dense
+ * int32[n].  pbd_boxes3d_camera: host records / images / outputs, synchronous; centres past ncentres are 0.
+ * pbd_boxes3d_camera_device: the payload and depth frames as pbd_boxes3d_device, device outputs of `capacity` records, only the
+ * min(max(word 0, 0), capacity) records written (centres past ncentres untouched); asynchronous on pbd_stream().
+ * Validation, PBD_ERR_STATE and the resident result as pbd_boxes3d. */
+typedef struct pbd_pinhole { double fx, fy, cx, cy, tx, ty; } pbd_pinhole;
+enum { PBD_PARTS_LITERAL = 0, PBD_PARTS_XY = 1 };
+int pbd_boxes3d_camera(pbd_handle *h, int nframes, const struct pbd_frame *depth, int depth_code, const int *im_rows,
+                       const int *im_cols, const pbd_pinhole *cams, int parts_mode, const int32_t *cand, int ncand, int frame_offset,
+                       double *box, float *centres, int32_t *ncentres, int32_t *dense);
+int pbd_boxes3d_camera_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code, const int *im_rows,
+                              const int *im_cols, const pbd_pinhole *cams, int parts_mode, const int32_t *d_payload, int capacity,
+                              int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres, int32_t *d_dense);
+
+/* Object clusters (new surface; opt-in): PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:157-293).
+ * Plane removal (organizedMultiplaneSegmentation, off by default at ros/Node.hpp:145) stays with the caller, who then passes
+ * the resulting unorganized cloud.
+ * pbd_cloud: x, y, z are the first three floats of every point (a pcl::PointXYZ / PointXYZRGB buffer as it is); point (r, c)
+ * at data + r * row_stride + c * point_stride, index r * cols + c; rows == 1 is an unorganized cloud.  Refused
+ * (PBD_ERR_INVALID, naming the cloud): a non-positive size, rows * cols >= 2^31, point_stride < 12, row_stride below the
+ * row's bytes (rows > 1), and on the device a pointer or stride not a multiple of 4.
+ * Per box (camera boxes as pbd_boxes3d_camera writes them; frame = the box's cloud):
+ *   gate     volume = width * height * depth; if volume >= 1e-6: x -= width * 0.1 (y, z likewise), width *= 1.2 (height,
+ *            depth likewise); min = (float)(x, y, z), max = (float)(x + width, y + height, z + depth).  Otherwise no points
+ *   crop     pcl::CropBox on a cloud taken as not dense: the finite points with min <= p <= max on all three axes, in float,
+ *            in ascending index order
+ *   edges    library definition (PCL's organized / kd-tree boundary convention is not pinned): two cropped points are
+ *            neighbours iff (double)d2 <= (double)0.01f * (double)0.01f, d2 = ((dx*dx + dy*dy) + dz*dz) in fp32, each
+ *            operation rounded separately
+ *   cluster  the connected components (min size 1); the largest is kept.  Project decision: on a size tie the one whose
+ *            smallest point index is lowest (the reference leaves ties to an unstable std::sort, :253-260)
+ *   centre   pcl::compute3DCentroid: three fp32 sums in ascending index order, each / (float)count; NaN x3 without a cluster
+ *   output   centres float[3*n]; counts int32[n] (the kept cluster's size, 0 without one); indices: the kept clusters' point
+ *            indices in ascending order, box after box (the caller gathers the points, as ExtractIndices copies them)
+ * pbd_cluster_objects: host clouds, boxes double[6*nboxes] and frames[nboxes] (cloud index; outside 0..nclouds-1 is
+ * PBD_ERR_INVALID naming the box); synchronous.  *needed = the total of counts; when it exceeds index_capacity:
+ * PBD_ERR_CAPACITY and no output is written.  More than 2^29 cropped points in one call: PBD_ERR_INVALID.
+ * pbd_cluster_objects_device: device clouds (a region of a larger buffer is read in place), the boxes' frames from the payload
+ * (box i's frame = record i's frame - frame_offset; min(max(word 0, 0), capacity) boxes; a frame outside 0..nclouds-1: no
+ * points), d_boxes double[6*capacity].  crop_capacity bounds the cropped points of all boxes together (at most 2^29, above
+ * that PBD_ERR_INVALID; the handle's workspace, about 52 bytes per point, grows to it), index_capacity the output indices.  d_status int64[2] = {cropped points, output indices}; status[1] is -1
+ * when the crop overflowed, and then every box has count 0 and a NaN centre; when status[1] > index_capacity the indices are
+ * not written.  Nothing is written out of bounds.  Asynchronous on pbd_stream(), no host synchronisation.
+ * PBD_ERR_STATE while a batch is in flight; the resident detect result is not touched. */
+typedef struct pbd_cloud {
+    const void *data;
+    int rows, cols;
+    size_t point_stride, row_stride;
+} pbd_cloud;
+int pbd_cluster_objects(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const double *boxes, const int *frames, int nboxes,
+                        float *centres, int32_t *counts, int32_t *indices, int index_capacity, int *needed);
+int pbd_cluster_objects_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const int32_t *d_payload, int capacity,
+                               int frame_offset, const double *d_boxes, int crop_capacity, int index_capacity, float *d_centres,
+                               int32_t *d_counts, int32_t *d_indices, long long *d_status);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -305,7 +380,11 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
 
 /* ---- per-kernel timing with HIP events on the library's stream (bench.py roofline) ---- */
 enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CONV, PBD_K_DT_ROWS,
-       PBD_K_DT_COLS, PBD_K_DP_COMBINE, PBD_K_DP_ROOT, PBD_K_ARGMIN, PBD_K_COUNT };
+       PBD_K_DT_COLS, PBD_K_DP_COMBINE, PBD_K_DP_ROOT, PBD_K_ARGMIN,
+       /* pbd_boxes3d_camera*, pbd_cluster_objects*; k_cl_crop_scan / k_cl_grid_scan time the three k_cl_scan_* kernels of that scan */
+       PBD_K_CAMERA_BOXES, PBD_K_CL_CROP_COUNT, PBD_K_CL_CROP_SCAN, PBD_K_CL_CROP_SCATTER, PBD_K_CL_CLEAR, PBD_K_CL_GRID_COUNT,
+       PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST, PBD_K_CL_SELECT, PBD_K_CL_OUT,
+       PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */
 int pbd_profile_enable(pbd_handle *h, int on);

@@ -88,6 +88,12 @@ struct Rect3d {
     Rect3d() : x(0), y(0), z(0), height(0), width(0), depth(0) {}
 };
 
+// pcl::PointXYZ's coordinates
+struct Point3f {
+    float x, y, z;
+    Point3f() : x(0), y(0), z(0) {}
+};
+
 class Candidate {
 public:
     std::vector<Rect> parts_;
@@ -561,13 +567,9 @@ public:
         if (!h_) throw Error(PBD_ERR_STATE, "detect() before distributeModel()");
         pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
     }
-    // Candidate::boundingBox3D(im, depth) of every candidate (include/Candidate.hpp:140-216), on the device (pbd_boxes3d): the
-    // callers' next step after detect + suppression (cells/detect.cpp:224-255).  `im` gives the colour frame's size, `depth` is
-    // one channel of any accepted depth and any size; every candidate is taken as one of this frame.
-    void boundingBoxes3D(const Image &im, const Image &depth, const std::vector<Candidate> &candidates, std::vector<Rect3d> &boxes)
+    // this handle's records of frame 0 for the candidates (the layout pbd_detect returns)
+    std::vector<int32_t> records(const std::vector<Candidate> &candidates) const
     {
-        if (!h_) throw Error(PBD_ERR_STATE, "boundingBoxes3D() before distributeModel()");
-        if (depth.channels != 1) throw Error(PBD_ERR_INVALID, "the depth image has one channel");
         const int stride = pbd_candidate_stride(h_);
         std::vector<int32_t> rec(candidates.size() * (size_t)stride + 1, 0);
         for (size_t i = 0; i < candidates.size(); ++i) {
@@ -582,15 +584,95 @@ public:
                 r[10 + 4 * k] = c.parts_[k].width; r[11 + 4 * k] = c.parts_[k].height;
             }
         }
+        return rec;
+    }
+    static Rect3d rect3d(const double *o)
+    {
+        Rect3d b;
+        b.x = o[0]; b.y = o[1]; b.z = o[2]; b.height = o[3]; b.width = o[4]; b.depth = o[5];
+        return b;
+    }
+    // Candidate::boundingBox3D(im, depth) of every candidate (include/Candidate.hpp:140-216), on the device (pbd_boxes3d): the
+    // callers' next step after detect + suppression (cells/detect.cpp:224-255).  `im` gives the colour frame's size, `depth` is
+    // one channel of any accepted depth and any size; every candidate is taken as one of this frame.
+    void boundingBoxes3D(const Image &im, const Image &depth, const std::vector<Candidate> &candidates, std::vector<Rect3d> &boxes)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "boundingBoxes3D() before distributeModel()");
+        if (depth.channels != 1) throw Error(PBD_ERR_INVALID, "the depth image has one channel");
+        const std::vector<int32_t> rec = records(candidates);
         pbd_frame fr;
         fr.data = depth.data; fr.rows = depth.rows; fr.cols = depth.cols; fr.stride_bytes = depth.step;
         std::vector<double> out(candidates.size() * 6 + 1);
         pbdbind::check<HostTraits<T> >(h_, pbd_boxes3d(h_, 1, &fr, depth.depth, &im.rows, &im.cols, rec.data(), (int)candidates.size(), 0, out.data()));
         boxes.resize(candidates.size());
-        for (size_t i = 0; i < candidates.size(); ++i) {
-            const double *o = &out[6 * i];
-            boxes[i].x = o[0]; boxes[i].y = o[1]; boxes[i].z = o[2];
-            boxes[i].height = o[3]; boxes[i].width = o[4]; boxes[i].depth = o[5];
+        for (size_t i = 0; i < candidates.size(); ++i) boxes[i] = rect3d(&out[6 * i]);
+    }
+    // PointCloudClusterer::computeBoundingBoxes(candidates, rgb, depth, projecter, ...) (include/PointCloudClusterer.hpp:53-153)
+    // on the device (pbd_boxes3d_camera): every candidate's camera box and part centres.  `depth` is one 32F channel (the
+    // reference reads depth.ptr<float>); parts_mode PBD_PARTS_LITERAL is the reference's sample loop.  A candidate whose cube holds
+    // a NaN gets the zero box and no part centres, as the reference's `continue` leaves them; `dense` (optional) is each list's
+    // is_dense.
+    void computeBoundingBoxes(const Image &im, const Image &depth, const pbd_pinhole &camera, const std::vector<Candidate> &candidates,
+                              std::vector<Rect3d> &boxes, std::vector<std::vector<Point3f> > &part_centres,
+                              std::vector<bool> *dense = NULL, int parts_mode = PBD_PARTS_LITERAL)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "computeBoundingBoxes() before distributeModel()");
+        if (depth.channels != 1) throw Error(PBD_ERR_INVALID, "the depth image has one channel");
+        const std::vector<int32_t> rec = records(candidates);
+        const size_t n = candidates.size();
+        const int mp = (pbd_candidate_stride(h_) - 8) / 4;
+        pbd_frame fr;
+        fr.data = depth.data; fr.rows = depth.rows; fr.cols = depth.cols; fr.stride_bytes = depth.step;
+        std::vector<double> box(n * 6 + 1);
+        std::vector<float> cen(n * mp * 3 + 1);
+        std::vector<int32_t> nc(n + 1), dn(n + 1);
+        pbdbind::check<HostTraits<T> >(h_, pbd_boxes3d_camera(h_, 1, &fr, depth.depth, &im.rows, &im.cols, &camera, parts_mode, rec.data(),
+                                                              (int)n, 0, box.data(), cen.data(), nc.data(), dn.data()));
+        boxes.resize(n);
+        part_centres.assign(n, std::vector<Point3f>());
+        if (dense) dense->assign(n, true);
+        for (size_t i = 0; i < n; ++i) {
+            boxes[i] = rect3d(&box[6 * i]);
+            for (int j = 0; j < nc[i]; ++j) {
+                Point3f q;
+                const float *c = &cen[(i * mp + j) * 3];
+                q.x = c[0]; q.y = c[1]; q.z = c[2];
+                part_centres[i].push_back(q);
+            }
+            if (dense) (*dense)[i] = dn[i] != 0;
+        }
+    }
+    // PointCloudClusterer::clusterObjects(cloud, bounding_boxes, object_clusters, object_centers) (:157-293) on the device
+    // (pbd_cluster_objects): clusters[i] = the point indices of box i's kept cluster, ascending (gather the points from the
+    // cloud as ExtractIndices does); centres[i] its centroid, NaN without one.  `cloud`: x, y, z the first three floats of a point.
+    void clusterObjects(const pbd_cloud &cloud, const std::vector<Rect3d> &boxes, std::vector<std::vector<int> > &clusters,
+                        std::vector<Point3f> &centres)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "clusterObjects() before distributeModel()");
+        const size_t n = boxes.size();
+        std::vector<double> bx(n * 6 + 1);
+        for (size_t i = 0; i < n; ++i) {
+            double *o = &bx[6 * i];
+            o[0] = boxes[i].x; o[1] = boxes[i].y; o[2] = boxes[i].z; o[3] = boxes[i].height; o[4] = boxes[i].width; o[5] = boxes[i].depth;
+        }
+        std::vector<int> frames(n + 1, 0);
+        std::vector<float> cen(n * 3 + 1);
+        std::vector<int32_t> cnt(n + 1);
+        std::vector<int32_t> idx(1 << 16);
+        int needed = 0;
+        int rc = pbd_cluster_objects(h_, 1, &cloud, bx.data(), frames.data(), (int)n, cen.data(), cnt.data(), idx.data(), (int)idx.size(), &needed);
+        if (rc == PBD_ERR_CAPACITY) {
+            idx.resize((size_t)needed);
+            rc = pbd_cluster_objects(h_, 1, &cloud, bx.data(), frames.data(), (int)n, cen.data(), cnt.data(), idx.data(), (int)idx.size(), &needed);
+        }
+        pbdbind::check<HostTraits<T> >(h_, rc);
+        clusters.assign(n, std::vector<int>());
+        centres.resize(n);
+        size_t off = 0;
+        for (size_t i = 0; i < n; ++i) {
+            clusters[i].assign(idx.begin() + off, idx.begin() + off + cnt[i]);
+            off += cnt[i];
+            centres[i].x = cen[3 * i]; centres[i].y = cen[3 * i + 1]; centres[i].z = cen[3 * i + 2];
         }
     }
     // new surface: images of any sizes (one depth, one channel count) in one call; candidates[i] = detect(images[i])
@@ -658,6 +740,31 @@ public:
         pbdbind::unpack_candidates<HostTraits<T> >(h, buf, n, candidates);
     }
 };
+
+// grey PFM ("Pf", a float depth map): rows stored bottom to top, little-endian for a negative scale; returned as 32F (depth 5),
+// top row first, in native byte order
+inline bool readPFM(const std::string &path, std::vector<uint8_t> &pix, Image &im)
+{
+    std::ifstream in(path.c_str(), std::ios::binary);
+    std::string magic;
+    int w = 0, h = 0;
+    double scale = 0;
+    if (!(in >> magic >> w >> h >> scale) || magic != "Pf" || w < 1 || h < 1 || scale == 0) return false;
+    in.get();
+    const size_t row = (size_t)w * 4;
+    std::vector<uint8_t> raw(row * h);
+    in.read(reinterpret_cast<char *>(raw.data()), (std::streamsize)raw.size());
+    if (!in) return false;
+    pix.resize(raw.size());
+    const uint16_t one = 1;
+    const bool little = *reinterpret_cast<const uint8_t *>(&one) == 1;
+    for (int r = 0; r < h; ++r)
+        for (size_t k = 0; k < row; k += 4)
+            for (int b = 0; b < 4; ++b)
+                pix[r * row + k + b] = raw[(size_t)(h - 1 - r) * row + k + ((scale < 0) == little ? b : 3 - b)];
+    im.data = pix.data(); im.rows = h; im.cols = w; im.channels = 1; im.step = row; im.depth = 5;
+    return true;
+}
 
 // binary PGM (P5) / PPM (P6, stored RGB -> returned BGR as cv::imread does); a PGM of maxval 65535 (big-endian samples, a
 // depth map) is returned as 16U (depth 2) in native byte order

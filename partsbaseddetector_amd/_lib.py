@@ -25,7 +25,9 @@ DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3
 # cv::Mat::depth() codes of the image depths HOGFeatures::pyramid accepts (src/HOGFeatures.cpp:136-146)
 DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32): 5, np.dtype(np.float64): 6}
 KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows", "k_dt_cols", "k_dp_combine",
-           "k_dp_root", "k_argmin"]
+           "k_dp_root", "k_argmin", "k_camera_boxes", "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear",
+           "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out"]
+PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -35,7 +37,8 @@ SYMBOLS = [
     "pbd_detect_batch_device", "pbd_detect_typed", "pbd_detect_batch_submit", "pbd_detect_batch_wait",
     "pbd_detect_batch_device_submit", "pbd_detect_batch_device_out", "pbd_argmin_device_out", "pbd_stream", "pbd_get_stage", "pbd_profile_enable", "pbd_profile_reset", "pbd_profile_read",
     "pbd_kernel_name", "pbd_synchronize", "pbd_detect_frames", "pbd_detect_frames_device", "pbd_detect_frames_device_out",
-    "pbd_boxes3d", "pbd_boxes3d_device",
+    "pbd_boxes3d", "pbd_boxes3d_device", "pbd_boxes3d_camera", "pbd_boxes3d_camera_device", "pbd_cluster_objects",
+    "pbd_cluster_objects_device",
 ]
 
 
@@ -62,6 +65,33 @@ class CModel(C.Structure):
 class CFrame(C.Structure):
     """pbd_frame: one frame of a mixed-size call (host pointer, or device pointer for the _device forms)."""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("stride_bytes", C.c_size_t)]
+
+
+class CPinhole(C.Structure):
+    """pbd_pinhole: one frame's pinhole intrinsics"""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "tx", "ty")]
+
+
+class CCloud(C.Structure):
+    """pbd_cloud: one point cloud (x, y, z the first three floats of every point)"""
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("point_stride", C.c_size_t), ("row_stride", C.c_size_t)]
+
+
+def pinhole_array(cams):
+    """(pbd_pinhole[]) from objects with fx, fy, cx, cy, tx, ty"""
+    arr = (CPinhole * len(cams))()
+    for i, c in enumerate(cams):
+        for k in ("fx", "fy", "cx", "cy", "tx", "ty"):
+            setattr(arr[i], k, float(getattr(c, k)))
+    return arr
+
+
+def cloud_array(descs):
+    """(pbd_cloud[]) from (pointer, rows, cols, point_stride, row_stride) tuples"""
+    arr = (CCloud * len(descs))()
+    for i, (p, r, c, ps, rs) in enumerate(descs):
+        arr[i].data, arr[i].rows, arr[i].cols, arr[i].point_stride, arr[i].row_stride = p, r, c, ps, rs
+    return arr
 
 
 def frame_array(descs):
@@ -137,6 +167,14 @@ def load():
     lib.pbd_boxes3d.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                 C.c_int, C.c_int, C.c_void_p]
     lib.pbd_boxes3d_device.argtypes = lib.pbd_boxes3d.argtypes
+    lib.pbd_boxes3d_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                       C.POINTER(CPinhole), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+    lib.pbd_boxes3d_camera_device.argtypes = lib.pbd_boxes3d_camera.argtypes
+    lib.pbd_cluster_objects.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_cluster_objects_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

@@ -318,6 +318,15 @@ struct pbd_handle {
     HostBuf b3_tab_host;
     DevBuf b3_tab, b3_depth, b3_rec, b3_out;
     Event b3_tab_copied;
+    // pbd_boxes3d_camera*: the pinhole table (staged as the frame table), k_boxes3d's cubes, the host form's outputs
+    HostBuf cam_tab_host;
+    DevBuf cam_tab, cam_cube, cam_out;
+    Event cam_tab_copied;
+    // pbd_cluster_objects*: the cloud table (staged as above), the workspace, the host form's clouds, payload, boxes and outputs
+    HostBuf cl_tab_host;
+    DevBuf cl_tab, cl_ws, cl_cloud, cl_in, cl_out;
+    Event cl_tab_copied;
+    long long cl_crop_cap = 0;       // the host form's crop capacity so far (grows to what a call needed)
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -2040,6 +2049,181 @@ int enqueue_boxes3d(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth
     return PBD_OK;
 }
 
+// the host records of a pbd_boxes3d* call: frame index and part count of each
+int check_boxes3d_records(pbd_handle *h, int nframes, const int32_t *cand, int ncand, int frame_offset)
+{
+    const int stride = ::stride(h);
+    for (int i = 0; i < ncand; ++i) {
+        const int32_t *r = cand + (size_t)i * stride;
+        const long long f = (long long)r[0] - frame_offset;
+        if (f < 0 || f >= nframes)
+            return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
+        if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
+    }
+    return PBD_OK;
+}
+
+// the host forms' depth images (packed with dense rows) and records (as a payload) into the handle's own buffers
+int upload_boxes3d_host(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
+                        const int32_t *cand, int ncand, std::vector<Box3dFrame> &tab)
+{
+    const int stride = ::stride(h);
+    const size_t es = depth_size(depth_code);
+    size_t total = 0;
+    for (int f = 0; f < nframes; ++f) total += (size_t)depth[f].rows * depth[f].cols * es;
+    HIPCHK(h, h->b3_depth.ensure(total + 8));
+    HIPCHK(h, h->b3_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+    tab.resize(nframes);
+    size_t off = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const size_t row_bytes = (size_t)depth[f].cols * es;
+        uint8_t *dst = h->b3_depth.as<uint8_t>() + off;
+        HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, depth[f].data, depth[f].stride_bytes, row_bytes, depth[f].rows,
+                                   hipMemcpyHostToDevice, h->stream));
+        tab[f] = Box3dFrame{dst, depth[f].rows, depth[f].cols, (long long)row_bytes, im_rows[f], im_cols[f]};
+        off += row_bytes * depth[f].rows;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->b3_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->b3_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
+                             h->stream));
+    return PBD_OK;
+}
+
+// a small table to the device through pinned staging memory, which is rewritten only once its previous copy has completed
+int stage_table(pbd_handle *h, HostBuf &host, DevBuf &dev, Event &copied, const void *src, size_t bytes)
+{
+    if (copied.p) HIPCHK(h, hipEventSynchronize(copied.p));
+    else HIPCHK(h, hipEventCreateWithFlags(&copied.p, hipEventDisableTiming));
+    HIPCHK(h, host.ensure(bytes, bytes * 2 + 256));
+    HIPCHK(h, dev.ensure(bytes));
+    memcpy(host.p, src, bytes);
+    HIPCHK(h, hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(copied.p, h->stream));
+    return PBD_OK;
+}
+
+// ---- camera boxes and part centres (pbd_boxes3d_camera*; pbd_kernels_cloud.hip)
+int check_camera(pbd_handle *h, int nframes, int depth_code, const pbd_pinhole *cams, int parts_mode)
+{
+    if (depth_code != kDepth32F) return fail(h, PBD_ERR_UNSUPPORTED, "depth code %d: the part centres read 32F depth (5)", depth_code);
+    if (parts_mode != PBD_PARTS_LITERAL && parts_mode != PBD_PARTS_XY)
+        return fail(h, PBD_ERR_INVALID, "parts mode %d: PBD_PARTS_LITERAL (0) or PBD_PARTS_XY (1)", parts_mode);
+    for (int f = 0; f < nframes; ++f)
+        if (!std::isfinite(cams[f].fx) || !std::isfinite(cams[f].fy) || cams[f].fx == 0 || cams[f].fy == 0)
+            return fail(h, PBD_ERR_INVALID, "frame %d: fx %g, fy %g (finite, non-zero)", f, cams[f].fx, cams[f].fy);
+    return PBD_OK;
+}
+
+// k_boxes3d into the handle's cube buffer, then the camera kernel, on the handle's stream
+int enqueue_camera(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, const pbd_pinhole *cams, int parts_mode,
+                   const int32_t *d_payload, int capacity, int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres,
+                   int32_t *d_dense)
+{
+    static_assert(sizeof(pbd_pinhole) == sizeof(Pinhole), "pbd_pinhole is the kernels' Pinhole");
+    HIPCHK(h, h->cam_cube.ensure((size_t)capacity * 6 * sizeof(double)));
+    if (int rc = enqueue_boxes3d(h, tab, depth_code, d_payload, capacity, frame_offset, h->cam_cube.as<double>())) return rc;
+    if (int rc = stage_table(h, h->cam_tab_host, h->cam_tab, h->cam_tab_copied, cams, tab.size() * sizeof(Pinhole))) return rc;
+    CameraParams cp{};
+    cp.in = d_payload; cp.in_cap = capacity; cp.stride = stride(h); cp.max_parts = h->max_parts;
+    cp.frames = h->b3_tab.as<Box3dFrame>(); cp.cams = h->cam_tab.as<Pinhole>();
+    cp.nframes = (int)tab.size(); cp.frame_offset = frame_offset; cp.mode = parts_mode;
+    cp.cube = h->cam_cube.as<double>();
+    cp.box = d_box; cp.centres = d_centres; cp.ncentres = d_ncentres; cp.dense = d_dense;
+    {
+        ProfScope ps(h, PBD_K_CAMERA_BOXES, h->stream);
+        launch_camera_boxes(cp, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// ---- object clusters (pbd_cluster_objects*; pbd_kernels_cloud.hip)
+int check_clouds(pbd_handle *h, int nclouds, const pbd_cloud *c, bool host)
+{
+    if (nclouds < 1) return fail(h, PBD_ERR_INVALID, "nclouds %d", nclouds);
+    for (int f = 0; f < nclouds; ++f) {
+        if (!c[f].data || c[f].rows < 1 || c[f].cols < 1 || (long long)c[f].rows * c[f].cols >= (1LL << 31))
+            return fail(h, PBD_ERR_INVALID, "cloud %d: %dx%d at %p", f, c[f].rows, c[f].cols, c[f].data);
+        if (c[f].point_stride < 3 * sizeof(float))
+            return fail(h, PBD_ERR_INVALID, "cloud %d: point stride %zu < 12", f, c[f].point_stride);
+        const size_t row_bytes = (size_t)(c[f].cols - 1) * c[f].point_stride + 3 * sizeof(float);
+        if (c[f].rows > 1 && c[f].row_stride < row_bytes)
+            return fail(h, PBD_ERR_INVALID, "cloud %d: row stride %zu < row bytes %zu", f, c[f].row_stride, row_bytes);
+        if (!host && (reinterpret_cast<uintptr_t>(c[f].data) % 4 || c[f].point_stride % 4 || c[f].row_stride % 4))
+            return fail(h, PBD_ERR_INVALID, "cloud %d: device pointer %p / strides %zu, %zu not multiples of 4", f, c[f].data,
+                        c[f].point_stride, c[f].row_stride);
+    }
+    return PBD_OK;
+}
+
+// the clustering workspace for `capacity` boxes, clouds of at most maxpts points and crop_cap cropped points: the bucket table
+// (tcap buckets, a power of two >= 2 crop_cap), the scan partials, and one 256-byte aligned piece per array, in the order
+// enqueue_cluster carves them.  crop_cap <= kClMaxCrop keeps tcap, every bucket index and every count inside an int.
+constexpr long long kClMaxCrop = 1LL << 29;
+constexpr int kClPieces = 14;
+struct ClusterLayout {
+    int nchunks;
+    long long units, tcap, nparts, total;
+    long long sizes[kClPieces];
+};
+int cluster_layout(int capacity, long long maxpts, long long crop_cap, ClusterLayout &L)
+{
+    if (capacity < 0 || maxpts < 1 || crop_cap < 0 || crop_cap > kClMaxCrop) return PBD_ERR_INVALID;
+    L.nchunks = (int)((maxpts + kClChunk - 1) / kClChunk);
+    L.units = (long long)capacity * L.nchunks;
+    L.tcap = 2;
+    while (L.tcap < 2 * crop_cap) L.tcap <<= 1;
+    L.nparts = std::max(L.units + 1, L.tcap + 1) / (4 * 256) + 2;
+    const long long c = crop_cap;
+    const long long sizes[kClPieces] = {(L.units + 1) * 8, L.nparts * 8, c * 4, c * 4, c * 16, c * 4, c * 4, c * 4, c * 4, (L.tcap + 1) * 4,
+                                        (L.tcap + 1) * 4, (long long)capacity * 8, (long long)capacity * 8, 4 * 8};
+    L.total = 0;
+    for (int i = 0; i < kClPieces; ++i) {
+        L.sizes[i] = sizes[i];
+        L.total += (sizes[i] + 255) / 256 * 256;
+    }
+    return PBD_OK;
+}
+
+// the workspace (cluster_layout), the cloud table, and the fixed sequence of launches
+int enqueue_cluster(pbd_handle *h, const std::vector<CloudFrame> &tab, const int32_t *d_payload, int capacity, int rec_stride,
+                    int frame_offset, const double *d_boxes, int crop_cap, int index_cap, float *d_centres, int32_t *d_counts,
+                    int32_t *d_indices, long long *d_status)
+{
+    long long maxpts = 1;
+    for (const CloudFrame &c : tab) maxpts = std::max(maxpts, (long long)c.rows * c.cols);
+    ClusterLayout L;
+    if (cluster_layout(capacity, maxpts, crop_cap, L))
+        return fail(h, PBD_ERR_INVALID, "crop capacity %d (at most 2^29), capacity %d", crop_cap, capacity);
+    const int nchunks = L.nchunks;
+    const long long tcap = L.tcap, total = L.total;
+    const long long *sizes = L.sizes;
+    HIPCHK(h, h->cl_ws.ensure((size_t)total));
+    if (int rc = stage_table(h, h->cl_tab_host, h->cl_tab, h->cl_tab_copied, tab.data(), tab.size() * sizeof(CloudFrame))) return rc;
+    uint8_t *w = h->cl_ws.as<uint8_t>();
+    int piece = 0;
+    auto carve = [&]() { uint8_t *p = w; w += (sizes[piece++] + 255) / 256 * 256; return (void *)p; };
+    ClusterParams p{};
+    p.in = d_payload; p.in_cap = capacity; p.rec_stride = rec_stride; p.frame_offset = frame_offset;
+    p.clouds = h->cl_tab.as<CloudFrame>(); p.nclouds = (int)tab.size(); p.nchunks = nchunks;
+    p.boxes = d_boxes; p.crop_cap = crop_cap; p.index_cap = index_cap;
+    p.chunk_off = (long long *)carve(); p.part = (long long *)carve();
+    p.crop_idx = (int32_t *)carve(); p.crop_box = (int32_t *)carve(); p.crop_xyz = (float4 *)carve();
+    p.bucket = (int32_t *)carve(); p.parent = (int32_t *)carve(); p.csize = (int32_t *)carve(); p.sorted = (int32_t *)carve();
+    p.bstart = (int32_t *)carve(); p.bcur = (int32_t *)carve(); p.tcap = (int)tcap;      // <= 2^30 (cluster_layout)
+    p.best = (unsigned long long *)carve(); p.obase = (long long *)carve(); p.ntab = (long long *)carve();
+    p.centres = d_centres; p.counts = d_counts; p.indices = d_indices; p.status = d_status;
+    static const int ids[kClSteps] = {PBD_K_CL_CROP_COUNT, PBD_K_CL_CROP_SCAN, PBD_K_CL_CROP_SCATTER, PBD_K_CL_CLEAR, PBD_K_CL_GRID_COUNT,
+                                      PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST,
+                                      PBD_K_CL_SELECT, PBD_K_CL_OUT};
+    for (int step = 0; step < kClSteps; ++step) {
+        ProfScope ps(h, ids[step], h->stream);
+        launch_cluster_step(p, step, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // a (frame, level) of the resident result -> (frame index into the buffers, level of the plan); mixed plans: frame 0, the
 // frame's level in the virtual table
 bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
@@ -2064,6 +2248,16 @@ const char *pbd_version(void) { return "pbd-hip 0.1 (gfx950)"; }
 
 // diagnostics, not part of include/pbd.h
 int pbd_debug_conv_occupancy(int nw) { return nw == 5 ? conv_mfma_occupancy(false) : nw == 6 ? conv_mfma_occupancy(true) : conv_occupancy(nw); }
+// the clustering workspace of pbd_cluster_objects* (host-only, no GPU needed): out = {nchunks, units, tcap, nparts, total, the
+// 14 piece sizes}; PBD_ERR_INVALID for a crop capacity the calls refuse
+int pbd_debug_cluster_layout(int capacity, long long maxpts, long long crop_cap, long long *out)
+{
+    ClusterLayout L;
+    if (int rc = cluster_layout(capacity, maxpts, crop_cap, L)) return rc;
+    out[0] = L.nchunks; out[1] = L.units; out[2] = L.tcap; out[3] = L.nparts; out[4] = L.total;
+    for (int i = 0; i < kClPieces; ++i) out[5 + i] = L.sizes[i];
+    return PBD_OK;
+}
 // the convolution's tile cover of one rows x cols level (host-only, no GPU needed): out[i] = {shape, y0, x0}
 int pbd_debug_cover_level(int rows, int cols, int *out, int capacity)
 {
@@ -2618,35 +2812,11 @@ int pbd_boxes3d(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_co
     return entry(h, depth && im_rows && im_cols && (ncand <= 0 || (cand && out)), kIdle, [&]() -> int {
         if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
         if (int rc = check_boxes3d_frames(h, nframes, depth, depth_code, im_rows, im_cols, true)) return rc;
-        const int stride = ::stride(h);
-        for (int i = 0; i < ncand; ++i) {
-            const int32_t *r = cand + (size_t)i * stride;
-            const long long f = (long long)r[0] - frame_offset;
-            if (f < 0 || f >= nframes)
-                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
-            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
-        }
+        if (int rc = check_boxes3d_records(h, nframes, cand, ncand, frame_offset)) return rc;
         if (ncand == 0) return PBD_OK;
-        // the depth images, packed with dense rows, into the handle's own buffer
-        const size_t es = depth_size(depth_code);
-        size_t total = 0;
-        for (int f = 0; f < nframes; ++f) total += (size_t)depth[f].rows * depth[f].cols * es;
-        HIPCHK(h, h->b3_depth.ensure(total + 8));
-        HIPCHK(h, h->b3_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
         HIPCHK(h, h->b3_out.ensure((size_t)ncand * 6 * sizeof(double)));
-        std::vector<Box3dFrame> tab(nframes);
-        size_t off = 0;
-        for (int f = 0; f < nframes; ++f) {
-            const size_t row_bytes = (size_t)depth[f].cols * es;
-            uint8_t *dst = h->b3_depth.as<uint8_t>() + off;
-            HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, depth[f].data, depth[f].stride_bytes, row_bytes, depth[f].rows,
-                                       hipMemcpyHostToDevice, h->stream));
-            tab[f] = Box3dFrame{dst, depth[f].rows, depth[f].cols, (long long)row_bytes, im_rows[f], im_cols[f]};
-            off += row_bytes * depth[f].rows;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->b3_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->b3_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 h->stream));
+        std::vector<Box3dFrame> tab;
+        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, im_rows, im_cols, cand, ncand, tab)) return rc;
         if (int rc = enqueue_boxes3d(h, tab, depth_code, h->b3_rec.as<int32_t>(), ncand, frame_offset, h->b3_out.as<double>())) return rc;
         HIPCHK(h, hipMemcpyAsync(out, h->b3_out.p, (size_t)ncand * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2666,6 +2836,152 @@ int pbd_boxes3d_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int
             tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
                                 (long long)d_depth[f].stride_bytes, im_rows[f], im_cols[f]};
         return enqueue_boxes3d(h, tab, depth_code, d_payload, capacity, frame_offset, d_out);
+    });
+}
+
+// PointCloudClusterer::computeBoundingBoxes after boundingBox3D (include/PointCloudClusterer.hpp:53-153).  See include/pbd.h.
+int pbd_boxes3d_camera(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
+                       const pbd_pinhole *cams, int parts_mode, const int32_t *cand, int ncand, int frame_offset, double *box,
+                       float *centres, int32_t *ncentres, int32_t *dense)
+{
+    return entry(h, depth && im_rows && im_cols && cams && (ncand <= 0 || (cand && box && centres && ncentres && dense)), kIdle,
+                 [&]() -> int {
+        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+        if (depth_code != kDepth32F) return check_camera(h, nframes, depth_code, cams, parts_mode);
+        if (int rc = check_boxes3d_frames(h, nframes, depth, depth_code, im_rows, im_cols, true)) return rc;
+        if (int rc = check_camera(h, nframes, depth_code, cams, parts_mode)) return rc;
+        if (int rc = check_boxes3d_records(h, nframes, cand, ncand, frame_offset)) return rc;
+        if (ncand == 0) return PBD_OK;
+        const size_t nb = (size_t)ncand * 6 * sizeof(double), nc = (size_t)ncand * h->max_parts * 3 * sizeof(float),
+                     ni = (size_t)ncand * sizeof(int32_t);
+        HIPCHK(h, h->cam_out.ensure(nb + nc + 2 * ni));
+        uint8_t *o = h->cam_out.as<uint8_t>();
+        std::vector<Box3dFrame> tab;
+        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, im_rows, im_cols, cand, ncand, tab)) return rc;
+        HIPCHK(h, hipMemsetAsync(o + nb, 0, nc, h->stream));
+        if (int rc = enqueue_camera(h, tab, depth_code, cams, parts_mode, h->b3_rec.as<int32_t>(), ncand, frame_offset, (double *)o,
+                                    (float *)(o + nb), (int32_t *)(o + nb + nc), (int32_t *)(o + nb + nc + ni))) return rc;
+        HIPCHK(h, hipMemcpyAsync(box, o, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(centres, o + nb, nc, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ncentres, o + nb + nc, ni, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dense, o + nb + nc + ni, ni, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_boxes3d_camera_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, const int *im_rows,
+                              const int *im_cols, const pbd_pinhole *cams, int parts_mode, const int32_t *d_payload, int capacity,
+                              int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres, int32_t *d_dense)
+{
+    return entry(h, d_depth && im_rows && im_cols && cams && d_payload && (capacity <= 0 || (d_box && d_centres && d_ncentres && d_dense)),
+                 kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (depth_code != kDepth32F) return check_camera(h, nframes, depth_code, cams, parts_mode);
+        if (int rc = check_boxes3d_frames(h, nframes, d_depth, depth_code, im_rows, im_cols, false)) return rc;
+        if (int rc = check_camera(h, nframes, depth_code, cams, parts_mode)) return rc;
+        if (capacity == 0) return PBD_OK;
+        std::vector<Box3dFrame> tab(nframes);
+        for (int f = 0; f < nframes; ++f)
+            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
+                                (long long)d_depth[f].stride_bytes, im_rows[f], im_cols[f]};
+        return enqueue_camera(h, tab, depth_code, cams, parts_mode, d_payload, capacity, frame_offset, d_box, d_centres, d_ncentres,
+                              d_dense);
+    });
+}
+
+// PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:157-293).  See include/pbd.h.
+int pbd_cluster_objects(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const double *boxes, const int *frames, int nboxes,
+                        float *centres, int32_t *counts, int32_t *indices, int index_capacity, int *needed)
+{
+    return entry(h, clouds && needed && (nboxes <= 0 || (boxes && frames && centres && counts)) && (index_capacity <= 0 || indices),
+                 kIdle, [&]() -> int {
+        *needed = 0;
+        if (nboxes < 0 || index_capacity < 0) return fail(h, PBD_ERR_INVALID, "nboxes %d, index capacity %d", nboxes, index_capacity);
+        if (int rc = check_clouds(h, nclouds, clouds, true)) return rc;
+        for (int i = 0; i < nboxes; ++i)
+            if (frames[i] < 0 || frames[i] >= nclouds) return fail(h, PBD_ERR_INVALID, "box %d: frame %d outside 0..%d", i, frames[i], nclouds - 1);
+        if (nboxes == 0) return PBD_OK;
+        // the clouds' x, y, z, packed
+        size_t total = 0;
+        for (int f = 0; f < nclouds; ++f) total += (size_t)clouds[f].rows * clouds[f].cols;
+        std::vector<float> packed(total * 3);
+        std::vector<CloudFrame> tab(nclouds);
+        HIPCHK(h, h->cl_cloud.ensure(total * 12 + 16));
+        size_t off = 0;
+        for (int f = 0; f < nclouds; ++f) {
+            const pbd_cloud &c = clouds[f];
+            for (int r = 0; r < c.rows; ++r)
+                for (int k = 0; k < c.cols; ++k)
+                    memcpy(&packed[(off + (size_t)r * c.cols + k) * 3],
+                           static_cast<const uint8_t *>(c.data) + r * c.row_stride + k * c.point_stride, 12);
+            tab[f] = CloudFrame{h->cl_cloud.as<uint8_t>() + off * 12, c.rows, c.cols, 12, (long long)c.cols * 12};
+            off += (size_t)c.rows * c.cols;
+        }
+        HIPCHK(h, hipMemcpyAsync(h->cl_cloud.p, packed.data(), total * 12, hipMemcpyHostToDevice, h->stream));
+        // the boxes and a payload of stride 1 holding the frames
+        const size_t bb = (size_t)nboxes * 6 * sizeof(double), pb = ((size_t)nboxes + 1) * sizeof(int32_t);
+        HIPCHK(h, h->cl_in.ensure(bb + pb + 16));
+        std::vector<int32_t> pay(nboxes + 1);
+        pay[0] = nboxes;
+        for (int i = 0; i < nboxes; ++i) pay[i + 1] = frames[i];
+        HIPCHK(h, hipMemcpyAsync(h->cl_in.p, boxes, bb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->cl_in.as<uint8_t>() + bb, pay.data(), pb, hipMemcpyHostToDevice, h->stream));
+        const double *d_boxes = h->cl_in.as<double>();
+        const int32_t *d_pay = reinterpret_cast<const int32_t *>(h->cl_in.as<uint8_t>() + bb);
+        // outputs: centres, counts, status, then the indices (at most the cropped points)
+        long long crop_cap = std::max<long long>(h->cl_crop_cap, 1 << 16);
+        long long status[2] = {0, 0};
+        for (int pass = 0; pass < 2; ++pass) {
+            const size_t oc = (size_t)nboxes * 12, on = (size_t)nboxes * 4;
+            HIPCHK(h, h->cl_out.ensure(oc + on + 16 + 16 + (size_t)crop_cap * 4));
+            uint8_t *o = h->cl_out.as<uint8_t>();
+            long long *d_status = reinterpret_cast<long long *>(o + (oc + on + 15) / 16 * 16);
+            int32_t *d_idx = reinterpret_cast<int32_t *>(d_status + 2);
+            if (int rc = enqueue_cluster(h, tab, d_pay, nboxes, 1, 0, d_boxes, (int)crop_cap, (int)crop_cap, (float *)o,
+                                         (int32_t *)(o + oc), d_idx, d_status)) return rc;
+            HIPCHK(h, hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (status[0] <= crop_cap) {
+                h->cl_crop_cap = std::max(h->cl_crop_cap, crop_cap);
+                if (status[1] > index_capacity) {
+                    *needed = (int)status[1];
+                    return fail(h, PBD_ERR_CAPACITY, "the kept clusters hold %lld indices, capacity %d", status[1], index_capacity);
+                }
+                *needed = (int)status[1];
+                HIPCHK(h, hipMemcpyAsync(centres, o, oc, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipMemcpyAsync(counts, o + oc, on, hipMemcpyDeviceToHost, h->stream));
+                if (status[1] > 0) HIPCHK(h, hipMemcpyAsync(indices, d_idx, (size_t)status[1] * 4, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                return PBD_OK;
+            }
+            if (status[0] > kClMaxCrop) return fail(h, PBD_ERR_INVALID, "%lld cropped points (at most 2^29)", status[0]);
+            crop_cap = status[0];                      // the first pass counted them all: the second fits
+        }
+        return fail(h, PBD_ERR_HIP, "cropped points changed between two passes");
+    });
+}
+
+int pbd_cluster_objects_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const int32_t *d_payload, int capacity,
+                               int frame_offset, const double *d_boxes, int crop_capacity, int index_capacity, float *d_centres,
+                               int32_t *d_counts, int32_t *d_indices, long long *d_status)
+{
+    return entry(h, d_clouds && d_payload && d_status && (capacity <= 0 || (d_boxes && d_centres && d_counts)) &&
+                    (index_capacity <= 0 || d_indices), kIdle, [&]() -> int {
+        if (capacity < 0 || crop_capacity < 0 || index_capacity < 0 || crop_capacity > kClMaxCrop)
+            return fail(h, PBD_ERR_INVALID, "capacity %d, crop capacity %d (at most 2^29), index capacity %d", capacity, crop_capacity,
+                        index_capacity);
+        if (int rc = check_clouds(h, nclouds, d_clouds, false)) return rc;
+        if (capacity == 0) {
+            HIPCHK(h, hipMemsetAsync(d_status, 0, 2 * sizeof(long long), h->stream));
+            return PBD_OK;
+        }
+        std::vector<CloudFrame> tab(nclouds);
+        for (int f = 0; f < nclouds; ++f)
+            tab[f] = CloudFrame{static_cast<const uint8_t *>(d_clouds[f].data), d_clouds[f].rows, d_clouds[f].cols,
+                                (long long)d_clouds[f].point_stride, (long long)d_clouds[f].row_stride};
+        return enqueue_cluster(h, tab, d_payload, capacity, stride(h), frame_offset, d_boxes, crop_capacity, index_capacity, d_centres,
+                               d_counts, d_indices, d_status);
     });
 }
 
@@ -2773,7 +3089,10 @@ int pbd_profile_read(pbd_handle *h, int k, double *total_ms, int *launches)
 const char *pbd_kernel_name(int k)
 {
     static const char *names[PBD_K_COUNT] = {"k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows",
-                                             "k_dt_cols", "k_dp_combine", "k_dp_root", "k_argmin"};
+                                             "k_dt_cols", "k_dp_combine", "k_dp_root", "k_argmin", "k_camera_boxes",
+                                             "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear", "k_cl_grid_count",
+                                             "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select",
+                                             "k_cl_out"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

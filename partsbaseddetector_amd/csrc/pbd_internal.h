@@ -313,6 +313,54 @@ struct Boxes3dParams {
     float dog[kB3Taps];           // the derivative-of-Gaussian taps, computed on the host (boxes3d_taps)
 };
 
+// camera boxes and part centres of each record (pbd_boxes3d_camera; pbd_kernels_cloud.hip)
+enum { kPartsLiteral = 0, kPartsXY = 1 };     // PBD_PARTS_LITERAL / PBD_PARTS_XY
+struct Pinhole { double fx, fy, cx, cy, tx, ty; };   // pbd_pinhole
+struct CameraParams {
+    const int32_t *in;            // the payload of k_boxes3d
+    int in_cap, stride, max_parts;
+    const Box3dFrame *frames;     // the depth frames (32F) and colour sizes
+    const Pinhole *cams;          // [nframes]
+    int nframes, frame_offset, mode;
+    const double *cube;           // [record][6]: what k_boxes3d wrote
+    double *box;                  // [record][6]: the camera box, Rect3d member order
+    float *centres;               // [record][max_parts][3]
+    int32_t *ncentres, *dense;    // [record]
+};
+
+// object clusters of camera boxes in point clouds (pbd_cluster_objects; pbd_kernels_cloud.hip)
+constexpr int kClChunk = 1024;                // points of one crop block (4 rounds of 256)
+constexpr int kClMaxGrid = 4096;              // workgroups of a grid-stride launch
+struct CloudFrame {                           // pbd_cloud, the point pointer and strides as read on the device
+    const uint8_t *data;
+    int rows, cols;
+    long long point_stride, row_stride;
+};
+struct ClusterParams {
+    const int32_t *in;            // payload: word 0 = boxes (negative: none); box i's frame = in[1 + i * rec_stride] - frame_offset
+    int in_cap, rec_stride, frame_offset;
+    const CloudFrame *clouds;
+    int nclouds, nchunks;         // chunks of kClChunk points per box (the largest cloud's)
+    const double *boxes;          // [box][6] camera boxes, Rect3d member order
+    int crop_cap, index_cap;
+    // workspace (pbd_capi.hip sizes it from crop_cap / boxes / nchunks)
+    long long *chunk_off;         // [in_cap * nchunks + 1]: cropped points per chunk, then their exclusive scan
+    long long *part;              // scan partials
+    int32_t *crop_idx, *crop_box; // [crop_cap]: the point index and the box of every cropped point
+    float4 *crop_xyz;             // [crop_cap]
+    int32_t *bucket, *parent, *csize;   // [crop_cap]: hash bucket, union-find parent, component size (roots)
+    int32_t *sorted;              // [crop_cap]: cropped points in bucket order
+    int32_t *bstart, *bcur;       // [tcap + 1]: bucket starts, scatter cursors
+    int tcap;                     // buckets allocated (power of two >= 2 crop_cap)
+    unsigned long long *best;     // [in_cap]: (size << 32) | ~root of the kept cluster
+    long long *obase;             // [in_cap]: first output index of every box
+    long long *ntab;              // [4]: cropped total, bucket count, (boxes of the payload) * nchunks, -
+    // outputs
+    float *centres;               // [box][3]
+    int32_t *counts, *indices;
+    long long *status;            // [2]: cropped points, output indices (-1: the crop overflowed)
+};
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -386,5 +434,11 @@ void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nl
                               int nglb, hipStream_t s);
 // `grid` workgroups (capped at kB3MaxGrid), each computing one record at a time
 void launch_boxes3d(const Boxes3dParams &p, int grid, hipStream_t s);
+// camera boxes and part centres of p.in's records (after launch_boxes3d wrote p.cube)
+void launch_camera_boxes(const CameraParams &p, hipStream_t s);
+// one step of the clustering (kClStep*, launched in this order); nothing is read back
+enum { kClStepCropCount = 0, kClStepCropScan, kClStepCropScatter, kClStepClear, kClStepGridCount, kClStepGridScan, kClStepGridScatter,
+       kClStepHook, kClStepLabel, kClStepBest, kClStepSelect, kClStepOut, kClSteps };
+void launch_cluster_step(const ClusterParams &p, int step, hipStream_t s);
 
 }  // namespace pbd

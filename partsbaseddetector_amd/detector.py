@@ -202,6 +202,7 @@ class Handle:
         self.max_batch = max_batch
         self.max_candidates = max_candidates
         self.stride = self.lib.pbd_candidate_stride(self.h)
+        self.max_parts = (self.stride - 8) // 4         # part boxes a record holds (pbd_candidate_stride)
 
     def close(self):
         if getattr(self, "h", None):
@@ -301,6 +302,85 @@ class Handle:
         ic = np.array([int(s[1]) for s in im_shapes], np.int32)
         self.check(self.lib.pbd_boxes3d_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
                                                _lib.ptr(ic, C.c_int), d_payload_ptr, capacity, frame_offset, d_out_ptr))
+
+    def boxes3d_camera(self, depths: Sequence[np.ndarray], im_shapes, cameras, records: np.ndarray, parts_mode: int = 0,
+                       frame_offset: int = 0):
+        """pbd_boxes3d_camera: camera boxes (n, 6) float64, part centres (n, max_parts, 3) float32 (0 past ncentres), ncentres (n,)
+        and dense (n,) int32 of the records (n, stride); depths[f] float32 2-D, cameras[f] with fx, fy, cx, cy, tx, ty."""
+        dt = np.dtype(depths[0].dtype)
+        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
+            raise PbdError(-1, "one depth dtype per call")
+        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
+        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        rec = np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
+        n = len(rec)
+        box = np.zeros((n, 6))
+        cen = np.zeros((n, self.max_parts, 3), np.float32)
+        nc = np.zeros(n, np.int32)
+        dn = np.zeros(n, np.int32)
+        ptr = (lambda a: a.ctypes.data if n else None)
+        self.check(self.lib.pbd_boxes3d_camera(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
+                                               _lib.pinhole_array(cameras), parts_mode, ptr(rec), n, frame_offset, ptr(box), ptr(cen),
+                                               ptr(nc), ptr(dn)))
+        return box, cen, nc, dn
+
+    def boxes3d_camera_device(self, descs, depth_code: int, im_shapes, cameras, parts_mode: int, d_payload_ptr: int, capacity: int,
+                              frame_offset: int, d_box_ptr: int, d_centres_ptr: int, d_ncentres_ptr: int, d_dense_ptr: int) -> None:
+        """pbd_boxes3d_camera_device: the records of a device payload, depth frames (device pointer, rows, cols, pitch), device
+        outputs of `capacity` records; asynchronous on the handle's stream"""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        self.check(self.lib.pbd_boxes3d_camera_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
+                                                      _lib.ptr(ic, C.c_int), _lib.pinhole_array(cameras), parts_mode, d_payload_ptr,
+                                                      capacity, frame_offset, d_box_ptr, d_centres_ptr, d_ncentres_ptr, d_dense_ptr))
+
+    @staticmethod
+    def cloud_desc(cloud: np.ndarray):
+        """(pointer, rows, cols, point_stride, row_stride) of a float32 cloud (rows, cols, k) or (n, k), k >= 3, of any strides"""
+        if cloud.dtype != np.float32 or cloud.ndim not in (2, 3) or cloud.shape[-1] < 3 or cloud.strides[-1] != 4:
+            raise PbdError(-1, "a cloud is float32 (rows, cols, k) or (n, k) with k >= 3 and the floats of a point contiguous")
+        if cloud.ndim == 2:
+            return cloud.ctypes.data, 1, cloud.shape[0], cloud.strides[0], cloud.shape[0] * cloud.strides[0]
+        return cloud.ctypes.data, cloud.shape[0], cloud.shape[1], cloud.strides[1], cloud.strides[0]
+
+    def cluster_objects(self, clouds: Sequence[np.ndarray], boxes: np.ndarray, frames, index_capacity: Optional[int] = None):
+        """pbd_cluster_objects: (centres (n, 3) float32, counts (n,) int32, indices int32 (the kept clusters, box after box)).
+        With index_capacity below the total: PbdError PBD_ERR_CAPACITY; its `needed` attribute holds the total."""
+        descs = _lib.cloud_array([self.cloud_desc(c) for c in clouds])
+        bx = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6)
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        n = len(bx)
+        if len(fr) != n:
+            raise PbdError(-1, "one frame per box")
+        cap = sum(c.shape[0] * (c.shape[1] if c.ndim == 3 else 1) for c in clouds) * max(n, 1) if index_capacity is None else index_capacity
+        cap = min(cap, 2 ** 31 - 1)
+        cen = np.zeros((n, 3), np.float32)
+        cnt = np.zeros(n, np.int32)
+        need = C.c_int()
+        idx = np.zeros(max(min(cap, 1 << 22), 1) if index_capacity is None else max(cap, 1), np.int32)
+        rc = self.lib.pbd_cluster_objects(self.h, len(clouds), descs, bx.ctypes.data if n else None, fr.ctypes.data if n else None, n,
+                                          cen.ctypes.data if n else None, cnt.ctypes.data if n else None, idx.ctypes.data,
+                                          len(idx) if index_capacity is None else cap, C.byref(need))
+        if rc == -4 and index_capacity is None:          # our own guess was short: once more with the total
+            idx = np.zeros(max(need.value, 1), np.int32)
+            rc = self.lib.pbd_cluster_objects(self.h, len(clouds), descs, bx.ctypes.data, fr.ctypes.data, n, cen.ctypes.data,
+                                              cnt.ctypes.data, idx.ctypes.data, len(idx), C.byref(need))
+        if rc != 0:
+            err = PbdError(rc, self.lib.pbd_last_error(self.h).decode())
+            err.needed = need.value
+            raise err
+        return cen, cnt, idx[:need.value].copy()
+
+    def cluster_objects_device(self, cloud_descs, d_payload_ptr: int, capacity: int, frame_offset: int, d_boxes_ptr: int,
+                               crop_capacity: int, index_capacity: int, d_centres_ptr: int, d_counts_ptr: int, d_indices_ptr: int,
+                               d_status_ptr: int) -> None:
+        """pbd_cluster_objects_device: device clouds ((pointer, rows, cols, point_stride, row_stride) tuples), the boxes' frames from
+        the payload, device boxes / outputs; status int64[2] = {cropped points, output indices or -1}; asynchronous"""
+        self.check(self.lib.pbd_cluster_objects_device(self.h, len(cloud_descs), _lib.cloud_array(cloud_descs), d_payload_ptr, capacity,
+                                                       frame_offset, d_boxes_ptr, crop_capacity, index_capacity, d_centres_ptr,
+                                                       d_counts_ptr, d_indices_ptr, d_status_ptr))
 
     def profile(self, on=True):
         """on: False / 0 off, True / 1 every kernel, 2 the convolution only (pbd_profile_enable)"""
@@ -502,6 +582,33 @@ class PartsBasedDetector:
         if len(im_shapes) and np.isscalar(im_shapes[0]):
             im_shapes = [im_shapes]
         return self.hd.boxes3d(list(depths), list(im_shapes), self.hd.pack_candidates(candidates))
+
+    def computeBoundingBoxes(self, candidates: Sequence[Candidate], depths, im_shapes, cameras, parts_mode: int = _lib.PARTS_LITERAL):
+        """PointCloudClusterer::computeBoundingBoxes on the device (pbd_boxes3d_camera): (boxes (n, 6) float64, centres
+        (n, max_parts, 3) float32, ncentres (n,) int32, dense (n,) int32), indexed by candidate.  depths (float32), im_shapes and
+        cameras (pointcloud.PinholeCamera) per frame index the candidates carry (single values for one frame).  Equal bit for bit
+        to pointcloud.PointCloudClusterer.computeBoundingBoxes."""
+        self._need()
+        if isinstance(depths, np.ndarray):
+            depths = [depths]
+        if len(im_shapes) and np.isscalar(im_shapes[0]):
+            im_shapes = [im_shapes]
+        if hasattr(cameras, "fx"):
+            cameras = [cameras]
+        return self.hd.boxes3d_camera(list(depths), list(im_shapes), list(cameras), self.hd.pack_candidates(candidates), parts_mode)
+
+    def clusterObjects(self, clouds, boxes, frames=None):
+        """PointCloudClusterer::clusterObjects on the device (pbd_cluster_objects): (centres (n, 3) float32, [ascending point
+        indices of each box's kept cluster]).  clouds: float32 (rows, cols, k) or (n, k) per frame; boxes (n, 6) camera boxes;
+        frames[i] the cloud of box i (all 0 by default).  Equal to pointcloud.PointCloudClusterer.clusterObjects."""
+        self._need()
+        if isinstance(clouds, np.ndarray):
+            clouds = [clouds]
+        boxes = np.asarray(boxes, np.float64).reshape(-1, 6)
+        frames = np.zeros(len(boxes), np.int32) if frames is None else np.asarray(frames, np.int32)
+        cen, cnt, idx = self.hd.cluster_objects(list(clouds), boxes, frames)
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        return cen, [idx[off[i]:off[i + 1]].astype(np.int64) for i in range(len(boxes))]
 
     def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
         """Equally sized frames: pbd_detect_batch (8-bit, as before).  Frames of different sizes: pbd_detect_frames, one
