@@ -4,7 +4,8 @@
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
-//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]]
+//            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
+//            [--remove-planes]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
@@ -16,6 +17,8 @@
 //           it (NaN where the depth is 0 or not finite);
 //           then per listed candidate: "box3d_cam x y z height width depth", "centres N x y z ..." (the part centres), and
 //           "object SIZE x y z" (the kept cluster's size and centroid)
+//   --remove-planes: with --camera, organizedMultiplaneSegmentation before the clustering (the callers' remove_planes option):
+//           "plane K a b c d INLIERS" per plane, "kept N" (the reduced cloud's points), then the lines above on the reduced cloud
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -62,7 +65,7 @@ static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, flo
 // d is 0 or not finite); camera boxes, part centres and one kept cluster per listed candidate
 template <typename T>
 static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Image &depth, const pbd_pinhole &cam,
-                         const std::vector<Candidate> &listed)
+                         const std::vector<Candidate> &listed, bool remove_planes)
 {
     std::vector<float> df((size_t)depth.rows * depth.cols), cloud(df.size() * 3);
     for (int r = 0; r < depth.rows; ++r)
@@ -89,6 +92,16 @@ static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Imag
     pc.data = cloud.data(); pc.rows = depth.rows; pc.cols = depth.cols; pc.point_stride = 12; pc.row_stride = (size_t)depth.cols * 12;
     std::vector<std::vector<int> > clusters;
     std::vector<Point3f> objects;
+    std::vector<float> reduced;
+    if (remove_planes) {                 // organizedMultiplaneSegmentation first, as the callers with remove_planes set
+        std::vector<int> kept, labels, inliers;
+        std::vector<std::array<float, 4> > planes;
+        pbd.organizedMultiplaneSegmentation(pc, reduced, kept, labels, planes, inliers);
+        for (size_t k = 0; k < planes.size(); ++k)
+            std::printf("plane %zu %.9g %.9g %.9g %.9g %d\n", k, planes[k][0], planes[k][1], planes[k][2], planes[k][3], inliers[k]);
+        std::printf("kept %zu\n", kept.size());
+        pc = PartsBasedDetector<T>::reducedCloud(reduced);
+    }
     pbd.clusterObjects(pc, boxes, clusters, objects);
     for (size_t i = 0; i < boxes.size(); ++i) {
         std::printf("box3d_cam %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
@@ -101,7 +114,7 @@ static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Imag
 
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
-               int conv_mode, const Image *depth, const pbd_pinhole *camera)
+               int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes)
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -164,7 +177,7 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         for (size_t i = 0; i < boxes.size(); ++i)
             std::printf("box3d %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
                         boxes[i].depth);
-        if (camera) camera_lines(pbd, im, *depth, *camera, listed);
+        if (camera) camera_lines(pbd, im, *depth, *camera, listed, remove_planes);
     }
     return 0;
 }
@@ -205,7 +218,7 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -213,11 +226,12 @@ int main(int argc, char **argv)
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
     std::vector<const char *> also;
     const char *depth_path = NULL;
-    bool have_camera = false;
+    bool have_camera = false, remove_planes = false;
     pbd_pinhole camera = {0, 0, 0, 0, 0, 0};
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
+        else if (!std::strcmp(argv[i], "--remove-planes")) remove_planes = true;
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--device-nms") && i + 1 < argc) dnms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
@@ -232,6 +246,10 @@ int main(int argc, char **argv)
     }
     if (!also.empty() && (staged || stream_k > 0)) {
         std::fprintf(stderr, "--also runs one detectBatch call: not with --staged or --stream\n");
+        return -1;
+    }
+    if (remove_planes && !have_camera) {
+        std::fprintf(stderr, "--remove-planes needs --depth and --camera\n");
         return -1;
     }
     if (have_camera && !depth_path) {
@@ -266,8 +284,8 @@ int main(int argc, char **argv)
         }
         const Image *dp = depth_path ? &depth : NULL;
         const pbd_pinhole *cp = have_camera ? &camera : NULL;
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp);
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

@@ -228,8 +228,8 @@ int pbd_boxes3d_camera_device(pbd_handle *h, int nframes, const struct pbd_frame
                               int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres, int32_t *d_dense);
 
 /* Object clusters (new surface; opt-in): PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:157-293).
- * Plane removal (organizedMultiplaneSegmentation, off by default at ros/Node.hpp:145) stays with the caller, who then passes
- * the resulting unorganized cloud.
+ * With plane removal (organizedMultiplaneSegmentation, off by default at ros/Node.hpp:145) the caller passes the reduced,
+ * unorganized cloud pbd_remove_planes* writes (below); the indices then refer to that cloud, as in the reference.
  * pbd_cloud: x, y, z are the first three floats of every point (a pcl::PointXYZ / PointXYZRGB buffer as it is); point (r, c)
  * at data + r * row_stride + c * point_stride, index r * cols + c; rows == 1 is an unorganized cloud.  Refused
  * (PBD_ERR_INVALID, naming the cloud): a non-positive size, rows * cols >= 2^31, point_stride < 12, row_stride below the
@@ -267,6 +267,83 @@ int pbd_cluster_objects(pbd_handle *h, int nclouds, const pbd_cloud *clouds, con
 int pbd_cluster_objects_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const int32_t *d_payload, int capacity,
                                int frame_offset, const double *d_boxes, int crop_capacity, int index_capacity, float *d_centres,
                                int32_t *d_counts, int32_t *d_indices, long long *d_status);
+
+/* Plane removal (new surface; opt-in): PointCloudClusterer::organizedMultiplaneSegmentation (include/PointCloudClusterer.hpp:
+ * 294-336): IntegralImageNormalEstimation (AVERAGE_3D_GRADIENT), OrganizedMultiPlaneSegmentation::segmentAndRefine, and
+ * ExtractIndices(negative) of every plane's inliers.  PCL is not pinned: this is the library's own restatement of the algorithm
+ * with the reference's parameters, and every deviation is named here.  P(r, c) is the point at row r, column c of an organized
+ * pbd_cloud, z its third coordinate; a point is finite when x, y and z are.  Every float / double operation below is rounded
+ * on its own, in the order written (no contraction).  s = smoothing_size / 2.
+ *   normals  dx(r,c) = P(r,c+1) - P(r,c-1), dy(r,c) = P(r+1,c) - P(r-1,c) in fp32.  Depth edge: a pixel not finite, or with a
+ *            4-neighbour q not finite or |z(q) - z(p)| > depth_change_factor * z(p).  The window is rows r-s..r+s, columns
+ *            c-s..c+s.  Project decision: the normal is NaN unless s+1 <= r <= rows-s-2 and s+1 <= c <= cols-s-2 (the window and
+ *            the one-pixel ring its gradients read lie in the image; PCL shrinks the window near the border instead) and no
+ *            window pixel is a depth edge.  Otherwise: each window row summed left to right from 0, those row sums summed top to
+ *            bottom from 0, each / (float)((2s+1)^2) -> mx (from dx), my (from dy); n = cross(my, mx) = (my.y*mx.z - my.z*mx.y,
+ *            my.z*mx.x - my.x*mx.z, my.x*mx.y - my.y*mx.x); n /= sqrt((n.x*n.x + n.y*n.y) + n.z*n.z) (three divides); if
+ *            (n.x*P.x + n.y*P.y) + n.z*P.z > 0 then n = -n.  d(p) = (n.x*P.x + n.y*P.y) + n.z*P.z after the flip
+ *   segments p is joined to its left and its upper neighbour q when q is finite, |d(p) - d(q)| < distance_threshold * (z(p)*z(p))
+ *            (PlaneCoefficientComparator, depth dependent, the current point's z) and (n(p).x*n(q).x + n(p).y*n(q).y) +
+ *            n(p).z*n(q).z > (float)cos(angular_threshold).  A NaN normal fails; a point that is not finite is in no segment.
+ *            Segments are the connected components, numbered by their smallest point index
+ *   planes   a segment of more than min_inliers points whose curvature is below max_curvature, in segment order.  Moments
+ *            {x, y, z, xx, xy, xz, yy, yz, zz} in double ((double)x * (double)y): per image row the segment's points left to
+ *            right from 0, those row partials top to bottom from 0; mean m = sum / count; covariance c_ij = m_ij - m_i * m_j.
+ *            Smallest eigenpair: 8 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) from V = I (a pair with a_pq == 0 is skipped;
+ *            theta = (a_qq - a_pp) / (2 a_pq), t = 1 / (|theta| + sqrt(theta*theta + 1)) negated when theta < 0,
+ *            c = 1 / sqrt(t*t + 1), s = t*c; A <- J^T (A J), V <- V J, each updated column / row entry c*u - s*v and s*u + c*v);
+ *            lambda = the smallest diagonal entry (the first on a tie), its column of V the eigenvector (a, b, c), no other sign
+ *            convention.  curvature = lambda / ((c_xx + c_yy) + c_zz).  d = -((a*m_x + b*m_y) + c*m_z); all four negated when
+ *            ((-m_x)*a + (-m_y)*b) + (-m_z)*c < 0; rounded to float (pcl::ModelCoefficients)
+ *   refine   (refine = 1; PCL's refine, two in-place raster passes of the label image with PlaneRefinementComparator).  Forward:
+ *            rows 0..rows-2 top to bottom, columns 0..cols-2 left to right; at each current cell the right neighbour, then the
+ *            lower one; `continue` when the current or the right label is negative, and before the lower check when the lower
+ *            label is.  Backward: the same on the image turned by 180 degrees (rows rows-1..1, columns cols-1..1, left then
+ *            upper neighbour).  Project decision: the backward columns stop at 1 (column 0 has no left neighbour).  A neighbour is
+ *            absorbed when the current label is a plane's segment, the neighbour's is not, and
+ *            |((a*x + b*y) + c*z) + d| < distance_threshold * (z(current)*z(current)) on the neighbour's point in fp32; it takes
+ *            the plane's label and may absorb cells later in the pass.  As a recurrence in a pass's own coordinates (o = the
+ *            labels at the pass's start; whether a label is negative never changes, so the right label's test reads o):
+ *              M(r,c) = F(r-1,c) if r >= 1, c <= cols-2, F(r-1,c) is a plane, o(r-1,c+1) >= 0, o(r,c) >= 0 is no plane and
+ *                       P(r,c) is absorbed with z(r-1,c); else o(r,c)
+ *              F(r,c) = F(r,c-1) if c >= 1, r <= rows-2, F(r,c-1) is a plane, M(r,c) >= 0 is no plane and P(r,c) is absorbed
+ *                       with z(r,c-1); else M(r,c)
+ *            so a pass is a wavefront over the anti-diagonals r + c
+ *   output   removed = every point whose final label is a plane.  The reduced cloud: every other point, NaN points included, as
+ *            xyz float triples in ascending index order (ExtractIndices, negative): an unorganized cloud
+ * Parameters: pbd_plane_params; NULL is the reference's call (smoothing 10, depth change 0.02, distance 0.02, angle 3 degrees =
+ * 3.0 * M_PI / 180.0, curvature 0.001, min inliers 1000, refine 1).  refine = 0 is segment() alone.
+ * Outputs, cloud i of n_i = rows * cols points at base_i = n_0 + ... + n_(i-1) of the point-indexed arrays:
+ *   points   float[3 * total]: the reduced cloud (nkept[i] points) at 3 * base_i, then NaN points up to n_i: {points + 3 * base_i,
+ *            rows 1, cols n_i, point_stride 12, row_stride 12 * n_i} is a pbd_cloud pbd_cluster_objects* read as it is (a NaN
+ *            point is never cropped); kept int32[total]: the kept points' original indices, then -1; nkept int32[nclouds];
+ *   labels   int32[total]: the plane's index, or -1
+ *   planes   float[4 * plane_capacity * nclouds] (cloud i, plane k at 4 * (i * plane_capacity + k)): a, b, c, d; inliers
+ *            int32[plane_capacity * nclouds] after refinement; nplanes int32[nclouds]
+ * Refused (PBD_ERR_INVALID, naming the cloud): rows < 2 or cols < 2, the pbd_cloud rules above, 2^31 or more points in one call;
+ * and parameters outside smoothing 2..128, min_inliers >= 0, refine 0 / 1, finite thresholds.
+ * pbd_remove_planes: host clouds and outputs, synchronous; *needed = the most planes of one cloud; above plane_capacity:
+ * PBD_ERR_CAPACITY and no output is written.
+ * pbd_remove_planes_device: device clouds (a region of a larger buffer is read in place), device outputs; d_status int64[2] =
+ * {kept points of all clouds, the most planes of one cloud}; nplanes[i] may exceed plane_capacity, and then only the first
+ * plane_capacity planes of the cloud are written (labels still name every plane).  Asynchronous on pbd_stream(), no host
+ * synchronisation; the handle's workspace (about 80 bytes per point) grows to the call.
+ * PBD_ERR_STATE while a batch is in flight; the resident detect result is not touched. */
+typedef struct pbd_plane_params {
+    int smoothing_size;          /* 10: the window half size is smoothing_size / 2 */
+    float depth_change_factor;   /* 0.02 */
+    float distance_threshold;    /* 0.02 (the comparators' and the refinement's) */
+    double angular_threshold;    /* radians, 3 degrees; the comparator uses (float)cos(angular_threshold) */
+    double max_curvature;        /* 0.001 */
+    int min_inliers;             /* 1000: a plane has more points than this */
+    int refine;                  /* 1: segmentAndRefine, 0: segment */
+} pbd_plane_params;
+int pbd_remove_planes(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const pbd_plane_params *params, float *points,
+                      int32_t *kept, int32_t *nkept, int32_t *labels, float *planes, int32_t *inliers, int32_t *nplanes,
+                      int plane_capacity, int *needed);
+int pbd_remove_planes_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const pbd_plane_params *params, float *d_points,
+                             int32_t *d_kept, int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers,
+                             int32_t *d_nplanes, int plane_capacity, long long *d_status);
 
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already

@@ -24,6 +24,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <array>
 #include <vector>
 
 #include "pbd.h"
@@ -674,6 +675,47 @@ public:
             off += cnt[i];
             centres[i].x = cen[3 * i]; centres[i].y = cen[3 * i + 1]; centres[i].z = cen[3 * i + 2];
         }
+    }
+    // PointCloudClusterer::organizedMultiplaneSegmentation(cloud, cloud_no_plane) (:294-336) on the device (pbd_remove_planes):
+    // cloud_no_plane = every point of no plane, NaN points included, as xyz triples in ascending index order (pass
+    // reducedCloud(cloud_no_plane) to clusterObjects); kept[i] = its original index; labels = the plane index of every point or
+    // -1; planes = {a, b, c, d} per plane; inliers = each plane's points.  `params` NULL: the reference's call.
+    void organizedMultiplaneSegmentation(const pbd_cloud &cloud, std::vector<float> &cloud_no_plane, std::vector<int> &kept,
+                                         std::vector<int> &labels, std::vector<std::array<float, 4> > &planes, std::vector<int> &inliers,
+                                         const pbd_plane_params *params = NULL)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "organizedMultiplaneSegmentation() before distributeModel()");
+        const size_t n = (size_t)std::max(cloud.rows, 0) * (size_t)std::max(cloud.cols, 0);
+        std::vector<float> pts(n * 3 + 3);
+        std::vector<int32_t> kp(n + 1), lab(n + 1);
+        int32_t nkept = 0, nplanes = 0;
+        int cap = 16, needed = 0;
+        std::vector<float> pl;
+        std::vector<int32_t> in;
+        int rc = PBD_ERR_CAPACITY;
+        for (int pass = 0; pass < 2 && rc == PBD_ERR_CAPACITY; ++pass) {
+            if (pass) cap = needed;
+            pl.assign((size_t)cap * 4 + 4, 0.f);
+            in.assign((size_t)cap + 1, 0);
+            rc = pbd_remove_planes(h_, 1, &cloud, params, pts.data(), kp.data(), &nkept, lab.data(), pl.data(), in.data(), &nplanes, cap,
+                                   &needed);
+        }
+        pbdbind::check<HostTraits<T> >(h_, rc);
+        cloud_no_plane.assign(pts.begin(), pts.begin() + (size_t)nkept * 3);
+        kept.assign(kp.begin(), kp.begin() + nkept);
+        labels.assign(lab.begin(), lab.begin() + n);
+        planes.resize(nplanes);
+        inliers.assign(in.begin(), in.begin() + nplanes);
+        for (int k = 0; k < nplanes; ++k)
+            for (int j = 0; j < 4; ++j) planes[k][j] = pl[4 * k + j];
+    }
+    // the unorganized pbd_cloud of organizedMultiplaneSegmentation's output
+    static pbd_cloud reducedCloud(const std::vector<float> &cloud_no_plane)
+    {
+        pbd_cloud c;
+        c.data = cloud_no_plane.data(); c.rows = 1; c.cols = (int)(cloud_no_plane.size() / 3);
+        c.point_stride = 12; c.row_stride = cloud_no_plane.size() * sizeof(float);
+        return c;
     }
     // new surface: images of any sizes (one depth, one channel count) in one call; candidates[i] = detect(images[i])
     void detectBatch(const std::vector<Image> &images, std::vector<std::vector<Candidate> > &candidates)

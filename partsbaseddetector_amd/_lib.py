@@ -38,7 +38,7 @@ SYMBOLS = [
     "pbd_detect_batch_device_submit", "pbd_detect_batch_device_out", "pbd_argmin_device_out", "pbd_stream", "pbd_get_stage", "pbd_profile_enable", "pbd_profile_reset", "pbd_profile_read",
     "pbd_kernel_name", "pbd_synchronize", "pbd_detect_frames", "pbd_detect_frames_device", "pbd_detect_frames_device_out",
     "pbd_boxes3d", "pbd_boxes3d_device", "pbd_boxes3d_camera", "pbd_boxes3d_camera_device", "pbd_cluster_objects",
-    "pbd_cluster_objects_device",
+    "pbd_cluster_objects_device", "pbd_remove_planes", "pbd_remove_planes_device",
 ]
 
 
@@ -75,6 +75,22 @@ class CPinhole(C.Structure):
 class CCloud(C.Structure):
     """pbd_cloud: one point cloud (x, y, z the first three floats of every point)"""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("point_stride", C.c_size_t), ("row_stride", C.c_size_t)]
+
+
+class CPlaneParams(C.Structure):
+    """pbd_plane_params (pointcloud.PlaneParams)"""
+    _fields_ = [("smoothing_size", C.c_int), ("depth_change_factor", C.c_float), ("distance_threshold", C.c_float),
+                ("angular_threshold", C.c_double), ("max_curvature", C.c_double), ("min_inliers", C.c_int), ("refine", C.c_int)]
+
+
+def plane_params(q):
+    """a CPlaneParams from an object with PlaneParams' fields, or None (the reference's call)"""
+    if q is None:
+        return None
+    out = CPlaneParams()
+    for name, _ in CPlaneParams._fields_:
+        setattr(out, name, getattr(q, name))
+    return C.pointer(out)
 
 
 def pinhole_array(cams):
@@ -175,6 +191,10 @@ def load():
                                         C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.pbd_cluster_objects_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pbd_remove_planes.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.POINTER(CPlaneParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_remove_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.POINTER(CPlaneParams), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

@@ -327,6 +327,10 @@ struct pbd_handle {
     DevBuf cl_tab, cl_ws, cl_cloud, cl_in, cl_out;
     Event cl_tab_copied;
     long long cl_crop_cap = 0;       // the host form's crop capacity so far (grows to what a call needed)
+    // pbd_remove_planes*: the cloud table (staged as above), the workspace, the host form's packed clouds and outputs
+    HostBuf pl_tab_host;
+    DevBuf pl_tab, pl_ws, pl_cloud, pl_out;
+    Event pl_tab_copied;
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -2224,6 +2228,120 @@ int enqueue_cluster(pbd_handle *h, const std::vector<CloudFrame> &tab, const int
     return PBD_OK;
 }
 
+// ---- plane removal (pbd_remove_planes*; pbd_kernels_planes.hip)
+// the reference's call (include/PointCloudClusterer.hpp:294-336 with PCL's defaults): see include/pbd.h
+pbd_plane_params plane_defaults()
+{
+    pbd_plane_params q;
+    q.smoothing_size = 10;
+    q.depth_change_factor = 0.02f;
+    q.distance_threshold = 0.02f;
+    q.angular_threshold = 3.0 * M_PI / 180.0;
+    q.max_curvature = 0.001;
+    q.min_inliers = 1000;
+    q.refine = 1;
+    return q;
+}
+
+int check_plane_params(pbd_handle *h, const pbd_plane_params &q)
+{
+    if (q.smoothing_size < 2 || q.smoothing_size > 128 || q.min_inliers < 0 || !std::isfinite(q.depth_change_factor) ||
+        !std::isfinite(q.distance_threshold) || !std::isfinite(q.angular_threshold) || !std::isfinite(q.max_curvature) ||
+        (q.refine != 0 && q.refine != 1))
+        return fail(h, PBD_ERR_INVALID, "plane parameters: smoothing size %d (2..128), min inliers %d (>= 0), refine %d (0 or 1), "
+                    "every threshold finite", q.smoothing_size, q.min_inliers, q.refine);
+    return PBD_OK;
+}
+
+// organized clouds: the pbd_cloud rules, rows >= 2 and cols >= 2, and fewer than 2^31 points in the whole call
+int check_organized(pbd_handle *h, int nclouds, const pbd_cloud *c, bool host)
+{
+    if (int rc = check_clouds(h, nclouds, c, host)) return rc;
+    long long total = 0;
+    for (int f = 0; f < nclouds; ++f) {
+        if (c[f].rows < 2 || c[f].cols < 2)
+            return fail(h, PBD_ERR_INVALID, "cloud %d: %dx%d is not organized (rows and cols >= 2)", f, c[f].rows, c[f].cols);
+        total += (long long)c[f].rows * c[f].cols;
+    }
+    if (total >= (1LL << 31)) return fail(h, PBD_ERR_INVALID, "the clouds of one call hold %lld points (below 2^31)", total);
+    return PBD_OK;
+}
+
+// the plane-removal workspace: one 256-byte aligned piece per array, in the order enqueue_planes carves them.  cand_cap bounds the
+// segments above min_inliers: at most points / (min_inliers + 1) per cloud
+constexpr int kPlPieces = 17;
+struct PlaneLayout {
+    long long cand_cap, total;
+    long long sizes[kPlPieces];
+};
+void plane_layout(int nclouds, long long npts, long long nrows, long long cand_cap, PlaneLayout &L)
+{
+    const long long n = npts, c = cand_cap + 1, tiles = (n + 1023) / 1024 + 2;
+    const long long sizes[kPlPieces] = {n * 16, n * 16, n * 16, n * 16, n * 4, n * 4, (n + 1) * 4, n * 4, tiles * 8, c * 4, c * 4,
+                                        c * 4, c * 16, c * 16, ((long long)nclouds + 1) * 4, (long long)nclouds * 4, 2 * nrows * 8};
+    L.cand_cap = cand_cap;
+    L.total = 0;
+    for (int i = 0; i < kPlPieces; ++i) {
+        L.sizes[i] = sizes[i];
+        L.total += (sizes[i] + 255) / 256 * 256;
+    }
+}
+
+// the workspace, the cloud table and the fixed sequence of launches; outputs as pbd_remove_planes_device
+int enqueue_planes(pbd_handle *h, const std::vector<PlaneCloud> &tab, const pbd_plane_params &q, float *d_points, int32_t *d_kept,
+                   int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers, int32_t *d_nplanes, int plane_cap,
+                   long long *d_status)
+{
+    const int nclouds = (int)tab.size() - 1;
+    long long cand_cap = 0, nrows = 0;
+    for (int i = 0; i < nclouds; ++i) {
+        cand_cap += (long long)tab[i].rows * tab[i].cols / ((long long)q.min_inliers + 1);
+        nrows += tab[i].rows;
+    }
+    const long long npts = tab[nclouds].base;
+    PlaneLayout L;
+    plane_layout(nclouds, npts, nrows, cand_cap, L);
+    HIPCHK(h, h->pl_ws.ensure((size_t)L.total));
+    if (int rc = stage_table(h, h->pl_tab_host, h->pl_tab, h->pl_tab_copied, tab.data(), tab.size() * sizeof(PlaneCloud))) return rc;
+    uint8_t *w = h->pl_ws.as<uint8_t>();
+    int piece = 0;
+    auto carve = [&]() { uint8_t *ptr = w; w += (L.sizes[piece++] + 255) / 256 * 256; return (void *)ptr; };
+    PlaneParams p{};
+    p.clouds = h->pl_tab.as<PlaneCloud>(); p.nclouds = nclouds; p.npts = npts;
+    p.half = q.smoothing_size / 2;
+    p.depth_change = q.depth_change_factor; p.dist_thr = q.distance_threshold;
+    p.cos_thr = (float)cos(q.angular_threshold);
+    p.max_curv = q.max_curvature; p.min_inliers = q.min_inliers;
+    p.plane_cap = plane_cap; p.cand_cap = (int)std::min<long long>(cand_cap, INT32_MAX);
+    p.xyz = (float4 *)carve(); p.rsx = (float4 *)carve(); p.rsy = (float4 *)carve(); p.nrm = (float4 *)carve();
+    p.parent = (int32_t *)carve(); p.csize = (int32_t *)carve(); p.flag = (int32_t *)carve(); p.lab = (int32_t *)carve();
+    p.part = (long long *)carve();
+    p.cand_root = (int32_t *)carve(); p.cand_plane = (int32_t *)carve(); p.plane_cnt = (int32_t *)carve();
+    p.cand_coef = (float4 *)carve(); p.plane_coef = (float4 *)carve();
+    p.cbase = (int32_t *)carve(); p.np = (int32_t *)carve(); p.xch = (int2 *)carve();
+    p.points = d_points; p.kept = d_kept; p.nkept = d_nkept; p.labels = d_labels; p.planes = d_planes; p.inliers = d_inliers;
+    p.nplanes = d_nplanes; p.status = d_status;
+    for (int step = 0; step < kPlSteps; ++step)
+        if (step != kPlStepRefine || q.refine) launch_planes_step(p, step, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// the cloud table of a call: every cloud's place in the concatenation, one closing entry holding the point total
+std::vector<PlaneCloud> plane_table(int nclouds, const pbd_cloud *c)
+{
+    std::vector<PlaneCloud> tab(nclouds + 1);
+    long long base = 0, rbase = 0;
+    for (int f = 0; f < nclouds; ++f) {
+        tab[f] = PlaneCloud{static_cast<const uint8_t *>(c[f].data), c[f].rows, c[f].cols, (long long)c[f].point_stride,
+                            (long long)c[f].row_stride, base, rbase};
+        base += (long long)c[f].rows * c[f].cols;
+        rbase += c[f].rows;
+    }
+    tab[nclouds] = PlaneCloud{nullptr, 0, 0, 0, 0, base, rbase};
+    return tab;
+}
+
 // a (frame, level) of the resident result -> (frame index into the buffers, level of the plan); mixed plans: frame 0, the
 // frame's level in the virtual table
 bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
@@ -2982,6 +3100,79 @@ int pbd_cluster_objects_device(pbd_handle *h, int nclouds, const pbd_cloud *d_cl
                                 (long long)d_clouds[f].point_stride, (long long)d_clouds[f].row_stride};
         return enqueue_cluster(h, tab, d_payload, capacity, stride(h), frame_offset, d_boxes, crop_capacity, index_capacity, d_centres,
                                d_counts, d_indices, d_status);
+    });
+}
+
+// PointCloudClusterer::organizedMultiplaneSegmentation (include/PointCloudClusterer.hpp:294-336).  See include/pbd.h.
+int pbd_remove_planes(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const pbd_plane_params *params, float *points, int32_t *kept,
+                      int32_t *nkept, int32_t *labels, float *planes, int32_t *inliers, int32_t *nplanes, int plane_capacity, int *needed)
+{
+    return entry(h, clouds && points && kept && nkept && labels && nplanes && needed && (plane_capacity <= 0 || (planes && inliers)),
+                 kIdle, [&]() -> int {
+        *needed = 0;
+        const pbd_plane_params q = params ? *params : plane_defaults();
+        if (plane_capacity < 0) return fail(h, PBD_ERR_INVALID, "plane capacity %d", plane_capacity);
+        if (int rc = check_plane_params(h, q)) return rc;
+        if (int rc = check_organized(h, nclouds, clouds, true)) return rc;
+        // the clouds' x, y, z, packed
+        std::vector<pbd_cloud> packed_desc(nclouds);
+        size_t total = 0;
+        for (int f = 0; f < nclouds; ++f) total += (size_t)clouds[f].rows * clouds[f].cols;
+        std::vector<float> packed(total * 3);
+        HIPCHK(h, h->pl_cloud.ensure(total * 12 + 16));
+        size_t off = 0;
+        for (int f = 0; f < nclouds; ++f) {
+            const pbd_cloud &c = clouds[f];
+            for (int r = 0; r < c.rows; ++r)
+                for (int k = 0; k < c.cols; ++k)
+                    memcpy(&packed[(off + (size_t)r * c.cols + k) * 3],
+                           static_cast<const uint8_t *>(c.data) + r * c.row_stride + k * c.point_stride, 12);
+            packed_desc[f] = pbd_cloud{h->pl_cloud.as<uint8_t>() + off * 12, c.rows, c.cols, 12, (size_t)c.cols * 12};
+            off += (size_t)c.rows * c.cols;
+        }
+        HIPCHK(h, hipMemcpyAsync(h->pl_cloud.p, packed.data(), total * 12, hipMemcpyHostToDevice, h->stream));
+        // outputs: status, counts, then points, kept, labels, planes, inliers
+        const size_t cap = (size_t)std::max(plane_capacity, 0);
+        const size_t o_stat = 0, o_nk = 16, o_np = o_nk + (size_t)nclouds * 4, o_pts = (o_np + (size_t)nclouds * 4 + 15) / 16 * 16,
+                     o_kept = o_pts + total * 12, o_lab = o_kept + total * 4, o_pl = (o_lab + total * 4 + 15) / 16 * 16,
+                     o_in = o_pl + (size_t)nclouds * cap * 16, o_end = o_in + (size_t)nclouds * cap * 4;
+        HIPCHK(h, h->pl_out.ensure(o_end + 16));
+        uint8_t *o = h->pl_out.as<uint8_t>();
+        if (int rc = enqueue_planes(h, plane_table(nclouds, packed_desc.data()), q, (float *)(o + o_pts), (int32_t *)(o + o_kept),
+                                    (int32_t *)(o + o_nk), (int32_t *)(o + o_lab), (float *)(o + o_pl), (int32_t *)(o + o_in),
+                                    (int32_t *)(o + o_np), (int)cap, (long long *)(o + o_stat))) return rc;
+        long long status[2] = {0, 0};
+        HIPCHK(h, hipMemcpyAsync(status, o + o_stat, sizeof status, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *needed = (int)status[1];
+        if (status[1] > plane_capacity)
+            return fail(h, PBD_ERR_CAPACITY, "a cloud holds %lld planes, capacity %d", status[1], plane_capacity);
+        HIPCHK(h, hipMemcpyAsync(nkept, o + o_nk, (size_t)nclouds * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nplanes, o + o_np, (size_t)nclouds * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(points, o + o_pts, total * 12, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(kept, o + o_kept, total * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(labels, o + o_lab, total * 4, hipMemcpyDeviceToHost, h->stream));
+        if (cap) {
+            HIPCHK(h, hipMemcpyAsync(planes, o + o_pl, (size_t)nclouds * cap * 16, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(inliers, o + o_in, (size_t)nclouds * cap * 4, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_remove_planes_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const pbd_plane_params *params, float *d_points,
+                             int32_t *d_kept, int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers,
+                             int32_t *d_nplanes, int plane_capacity, long long *d_status)
+{
+    return entry(h, d_clouds && d_points && d_kept && d_nkept && d_labels && d_nplanes && d_status &&
+                    (plane_capacity <= 0 || (d_planes && d_inliers)), kIdle, [&]() -> int {
+        const pbd_plane_params q = params ? *params : plane_defaults();
+        if (plane_capacity < 0) return fail(h, PBD_ERR_INVALID, "plane capacity %d", plane_capacity);
+        if (int rc = check_plane_params(h, q)) return rc;
+        if (int rc = check_organized(h, nclouds, d_clouds, false)) return rc;
+        return enqueue_planes(h, plane_table(nclouds, d_clouds), q, d_points, d_kept, d_nkept, d_labels, d_planes, d_inliers, d_nplanes,
+                              plane_capacity, d_status);
     });
 }
 

@@ -361,6 +361,42 @@ struct ClusterParams {
     long long *status;            // [2]: cropped points, output indices (-1: the crop overflowed)
 };
 
+// organized multi-plane segmentation of organized clouds (pbd_remove_planes; pbd_kernels_planes.hip)
+constexpr int kPlRefLds = 4096;               // rows whose refinement exchange lives in LDS (larger clouds: p.xch)
+struct PlaneCloud {                           // pbd_cloud as read on the device, and where it sits in the call's concatenation
+    const uint8_t *data;
+    int rows, cols;
+    long long point_stride, row_stride;
+    long long base;               // first point (sum of the earlier clouds' points)
+    long long rbase;              // first row (sum of the earlier clouds' rows): the cloud's slice of xch
+};
+struct PlaneParams {
+    const PlaneCloud *clouds;     // [nclouds + 1]: the last entry's base is the call's point total
+    int nclouds;
+    long long npts;               // points of all clouds
+    int half;                     // window half size s = smoothing size / 2
+    float depth_change, dist_thr, cos_thr;
+    double max_curv;
+    int min_inliers, plane_cap, cand_cap;
+    // workspace (pbd_capi.hip sizes it: plane_layout)
+    float4 *xyz;                  // [npts] the points
+    float4 *rsx, *rsy;            // [npts] row sums of the x / y gradients (w of rsx: 1 when the row window holds a depth edge)
+    float4 *nrm;                  // [npts] normal and d = n . P
+    int32_t *parent, *csize;      // [npts] union-find parent (final: the root), component size (roots)
+    int32_t *flag;                // [npts + 1] flags, then their exclusive scan
+    int32_t *lab;                 // [npts] working labels: plane index, -2 a finite point of no plane, -1 not finite
+    long long *part;              // scan partials
+    int32_t *cand_root, *cand_plane, *plane_cnt;   // [cand_cap]
+    float4 *cand_coef, *plane_coef;                // [cand_cap]
+    int32_t *cbase, *np;          // [nclouds + 1] first candidate of every cloud, [nclouds] planes of every cloud
+    int2 *xch;                    // [2 * rows of all clouds] the refinement wavefront's exchange of clouds taller than kPlRefLds
+    // outputs
+    float *points;                // [npts][3] cloud i at base_i: kept points, then NaN points
+    int32_t *kept, *nkept, *labels, *inliers, *nplanes;
+    float *planes;                // [nclouds][plane_cap][4]
+    long long *status;            // [2]: kept points of all clouds, most planes of one cloud
+};
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -440,5 +476,9 @@ void launch_camera_boxes(const CameraParams &p, hipStream_t s);
 enum { kClStepCropCount = 0, kClStepCropScan, kClStepCropScatter, kClStepClear, kClStepGridCount, kClStepGridScan, kClStepGridScatter,
        kClStepHook, kClStepLabel, kClStepBest, kClStepSelect, kClStepOut, kClSteps };
 void launch_cluster_step(const ClusterParams &p, int step, hipStream_t s);
+// organized multi-plane segmentation (kPlStep*, launched in this order; refine = 0 skips kPlStepRefine); nothing is read back
+enum { kPlStepLoad = 0, kPlStepRowSums, kPlStepNormals, kPlStepHook, kPlStepSize, kPlStepCand, kPlStepCandScan, kPlStepCandList,
+       kPlStepMoments, kPlStepPlanes, kPlStepLabel, kPlStepRefine, kPlStepFinal, kPlStepKeptScan, kPlStepKept, kPlStepOut, kPlSteps };
+void launch_planes_step(const PlaneParams &p, int step, hipStream_t s);
 
 }  // namespace pbd

@@ -382,6 +382,57 @@ class Handle:
                                                        frame_offset, d_boxes_ptr, crop_capacity, index_capacity, d_centres_ptr,
                                                        d_counts_ptr, d_indices_ptr, d_status_ptr))
 
+    def remove_planes(self, clouds: Sequence[np.ndarray], params=None, plane_capacity: Optional[int] = None):
+        """pbd_remove_planes on organized float32 clouds (rows, cols, k): per cloud (reduced cloud (nkept, 3) float32, kept
+        indices int32, labels (rows, cols) int32, planes (nplanes, 4) float32, inliers (nplanes,) int32).  With plane_capacity
+        below a cloud's plane count: PbdError PBD_ERR_CAPACITY; its `needed` attribute holds the count."""
+        for c in clouds:
+            if c.ndim != 3:
+                raise PbdError(-1, "pbd_remove_planes takes organized clouds (rows, cols, k)")
+        descs = _lib.cloud_array([self.cloud_desc(c) for c in clouds])
+        sizes = [c.shape[0] * c.shape[1] for c in clouds]
+        total = sum(sizes)
+        nc = len(clouds)
+        pts = np.zeros((max(total, 1), 3), np.float32)
+        kept = np.zeros(max(total, 1), np.int32)
+        labels = np.zeros(max(total, 1), np.int32)
+        nkept = np.zeros(max(nc, 1), np.int32)
+        nplanes = np.zeros(max(nc, 1), np.int32)
+        need = C.c_int()
+
+        def run(cap):
+            planes = np.zeros((max(nc * cap, 1), 4), np.float32)
+            inl = np.zeros(max(nc * cap, 1), np.int32)
+            rc = self.lib.pbd_remove_planes(self.h, nc, descs, _lib.plane_params(params), pts.ctypes.data, kept.ctypes.data,
+                                            nkept.ctypes.data, labels.ctypes.data, planes.ctypes.data, inl.ctypes.data,
+                                            nplanes.ctypes.data, cap, C.byref(need))
+            return rc, planes, inl
+
+        cap = 64 if plane_capacity is None else plane_capacity
+        rc, planes, inl = run(cap)
+        if rc == -4 and plane_capacity is None:          # our own guess was short: once more with the count
+            cap = need.value
+            rc, planes, inl = run(cap)
+        if rc != 0:
+            err = PbdError(rc, self.lib.pbd_last_error(self.h).decode())
+            err.needed = need.value
+            raise err
+        out, base = [], 0
+        for i, c in enumerate(clouds):
+            n, k, npl = sizes[i], int(nkept[i]), int(nplanes[i])
+            out.append((pts[base:base + k].copy(), kept[base:base + k].copy(), labels[base:base + n].reshape(c.shape[:2]).copy(),
+                        planes[i * cap:i * cap + npl].copy(), inl[i * cap:i * cap + npl].copy()))
+            base += n
+        return out
+
+    def remove_planes_device(self, cloud_descs, params, d_points_ptr: int, d_kept_ptr: int, d_nkept_ptr: int, d_labels_ptr: int,
+                             d_planes_ptr: int, d_inliers_ptr: int, d_nplanes_ptr: int, plane_capacity: int, d_status_ptr: int) -> None:
+        """pbd_remove_planes_device: device clouds ((pointer, rows, cols, point_stride, row_stride) tuples), device outputs;
+        status int64[2] = {kept points, the most planes of one cloud}; asynchronous"""
+        self.check(self.lib.pbd_remove_planes_device(self.h, len(cloud_descs), _lib.cloud_array(cloud_descs), _lib.plane_params(params),
+                                                     d_points_ptr, d_kept_ptr, d_nkept_ptr, d_labels_ptr, d_planes_ptr, d_inliers_ptr,
+                                                     d_nplanes_ptr, plane_capacity, d_status_ptr))
+
     def profile(self, on=True):
         """on: False / 0 off, True / 1 every kernel, 2 the convolution only (pbd_profile_enable)"""
         self.check(self.lib.pbd_profile_enable(self.h, int(on)))
@@ -519,18 +570,27 @@ class PartsBasedDetector:
     """PartsBasedDetector<float> (include/PartsBasedDetector.hpp:152-175)."""
 
     def __init__(self, device: int = 0, conv_mode: int = _lib.CONV_EXACT, max_batch: int = 1,
-                 max_candidates: int = 1 << 18, stream: Optional[int] = None, dtype=np.float32, nms: Optional[float] = None):
+                 max_candidates: int = 1 << 18, stream: Optional[int] = None, dtype=np.float32, nms: Optional[float] = None,
+                 remove_planes: bool = False):
         """dtype: the reference's template parameter T (float32 as src/demo.cpp:85, float64 as the ECTO/ROS callers).
         nms: overlap of the per-frame sort + non-maxima suppression run on the device after every detect (Handle.set_nms;
-        the callers' post-step, 0.1 in cells/detect.cpp:238 -- config.max_overlap); None: the raw candidate list."""
+        the callers' post-step, 0.1 in cells/detect.cpp:238 -- config.max_overlap); None: the raw candidate list.
+        remove_planes: what clusterObjects does when not told (config.DetectorConfig.remove_planes; fromConfig sets it)."""
         self._kw = dict(device=device, conv_mode=conv_mode, max_batch=max_batch, max_candidates=max_candidates,
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
         self._nms = nms
+        self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
         self.hd: Optional[Handle] = None
         self._name = ""
 
     def name(self) -> str:
         return self._name
+
+    @classmethod
+    def fromConfig(cls, cfg, **kw) -> "PartsBasedDetector":
+        """a detector for a parsed .by_parts pipeline (config.DetectorConfig): its remove_planes option makes clusterObjects
+        remove the planes first, as the ECTO cell does (cells/detect.cpp:263-273)"""
+        return cls(remove_planes=cfg.remove_planes, **kw)
 
     def distributeModel(self, model: Model) -> None:
         """src/PartsBasedDetector.cpp:102-127: creates the feature / convolution engines and the DP."""
@@ -597,13 +657,27 @@ class PartsBasedDetector:
             cameras = [cameras]
         return self.hd.boxes3d_camera(list(depths), list(im_shapes), list(cameras), self.hd.pack_candidates(candidates), parts_mode)
 
-    def clusterObjects(self, clouds, boxes, frames=None):
+    def removePlanes(self, cloud, params=None):
+        """PointCloudClusterer::organizedMultiplaneSegmentation on the device (pbd_remove_planes): (cloud_no_planes (k, 3) float32,
+        kept indices (k,) int64, labels (rows, cols) int32 (plane index or -1), planes (n, 4) float32).  cloud: an organized
+        float32 (rows, cols, k) cloud; params: pointcloud.PlaneParams or None (the reference's call).  Equal bit for bit to
+        pointcloud.PointCloudClusterer.organizedMultiplaneSegmentation."""
+        self._need()
+        pts, kept, labels, planes, _ = self.hd.remove_planes([cloud], params)[0]
+        return pts, kept.astype(np.int64), labels, planes
+
+    def clusterObjects(self, clouds, boxes, frames=None, remove_planes: Optional[bool] = None):
         """PointCloudClusterer::clusterObjects on the device (pbd_cluster_objects): (centres (n, 3) float32, [ascending point
         indices of each box's kept cluster]).  clouds: float32 (rows, cols, k) or (n, k) per frame; boxes (n, 6) camera boxes;
-        frames[i] the cloud of box i (all 0 by default).  Equal to pointcloud.PointCloudClusterer.clusterObjects."""
+        frames[i] the cloud of box i (all 0 by default).  Equal to pointcloud.PointCloudClusterer.clusterObjects.
+        remove_planes (the callers' option; None: the detector's own, False unless set from config.DetectorConfig.remove_planes):
+        the organized clouds go through removePlanes first, as in the reference, and the indices then refer to the reduced
+        clouds."""
         self._need()
         if isinstance(clouds, np.ndarray):
             clouds = [clouds]
+        if self.remove_planes if remove_planes is None else remove_planes:
+            clouds = [r[0] for r in self.hd.remove_planes(list(clouds))]
         boxes = np.asarray(boxes, np.float64).reshape(-1, 6)
         frames = np.zeros(len(boxes), np.int32) if frames is None else np.asarray(frames, np.int32)
         cen, cnt, idx = self.hd.cluster_objects(list(clouds), boxes, frames)

@@ -3,14 +3,16 @@ states them for pbd_boxes3d_camera and pbd_cluster_objects:
 
     PinholeCamera                                  image_geometry's PinholeCameraModel::projectPixelTo3dRay (ros/Node.cpp:210)
     PointCloudClusterer.computeBoundingBoxes       :53-153, after Candidate::boundingBox3D
-    PointCloudClusterer.clusterObjects             :157-293 (plane removal stays with the caller)
+    PointCloudClusterer.clusterObjects             :157-293, on the full cloud or the reduced cloud of plane removal
+    PointCloudClusterer.organizedMultiplaneSegmentation  :294-336, as include/pbd.h states it for pbd_remove_planes
     cloud_from_depth                               an organized float32 cloud back-projected from a float depth image
 
 These run on the host, in numpy, and are what the device results are compared with bit for bit.  The device forms are
-PartsBasedDetector.computeBoundingBoxes / .clusterObjects (detector.py).
+PartsBasedDetector.computeBoundingBoxes / .clusterObjects / .removePlanes (detector.py).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import List, Sequence, Tuple
 
@@ -20,6 +22,21 @@ PARTS_LITERAL, PARTS_XY = 0, 1
 RADIUS = np.float32(0.01)                     # setClusterTolerance(0.010) (:213), as the float PCL keeps
 RADIUS2 = float(RADIUS) * float(RADIUS)       # (double)0.01f * (double)0.01f, exact
 CELL_INV = np.float32(50.0)                   # 2 cm cells: 1 / edge
+
+
+@dataclass(frozen=True)
+class PlaneParams:
+    """pbd_plane_params; the defaults are the reference's call (PCL's defaults, include/PointCloudClusterer.hpp:294-336)"""
+    smoothing_size: int = 10
+    depth_change_factor: float = 0.02
+    distance_threshold: float = 0.02
+    angular_threshold: float = 3.0 * math.pi / 180.0
+    max_curvature: float = 0.001
+    min_inliers: int = 1000
+    refine: int = 1
+
+
+JACOBI_SWEEPS = 8
 
 
 @dataclass(frozen=True)
@@ -240,6 +257,39 @@ class PointCloudClusterer:
         return centroid(P[members]), idx[members]
 
     @staticmethod
+    def organizedMultiplaneSegmentation(cloud, params: PlaneParams = None):
+        """(cloud_no_planes (k, 3) float32, kept (k,) int64 original indices, labels (rows, cols) int32 (plane index or -1),
+        planes (n, 4) float32 {a, b, c, d}) of an organized cloud (rows, cols, >= 3) float32; the inlier counts are
+        np.bincount(labels[labels >= 0], minlength=n).  Follows include/pbd.h's contract op by op."""
+        q = params or PlaneParams()
+        c = np.asarray(cloud)
+        if c.dtype != np.float32 or c.ndim != 3 or c.shape[2] < 3 or c.shape[0] < 2 or c.shape[1] < 2:
+            raise ValueError("an organized float32 cloud (rows >= 2, cols >= 2, >= 3 floats per point)")
+        P = np.ascontiguousarray(c[:, :, :3])
+        H, W = P.shape[:2]
+        fin = np.isfinite(P).all(axis=2)
+        n, d = plane_normals(P, q.smoothing_size // 2, q.depth_change_factor)
+        root = plane_segments(P, n, d, q.distance_threshold, q.angular_threshold)
+        size = np.bincount(root[fin.ravel()], minlength=H * W)
+        cand = np.nonzero((size > q.min_inliers) & fin.ravel() & (root == np.arange(H * W)))[0]
+        planes = []
+        lab = np.where(fin, -2, -1).astype(np.int64).ravel()
+        for r in cand:
+            coef, curv = plane_fit(P, (root == r).reshape(H, W), int(size[r]))
+            if curv < q.max_curvature:
+                lab[(root == r)] = len(planes)
+                planes.append(coef)
+        planes = np.array(planes, np.float32).reshape(-1, 4)
+        lab = lab.reshape(H, W)
+        if q.refine and len(planes):
+            lab = plane_refine_pass(lab, P, planes, q.distance_threshold)
+            lab = plane_refine_pass(lab[::-1, ::-1], P[::-1, ::-1], planes, q.distance_threshold)[::-1, ::-1]
+        lab = np.ascontiguousarray(lab)
+        kept = np.nonzero(lab.ravel() < 0)[0]
+        labels = np.where(lab >= 0, lab, -1).astype(np.int32)
+        return P.reshape(-1, 3)[kept].copy(), kept.astype(np.int64), labels, planes
+
+    @staticmethod
     def clusterObjects(clouds, boxes, frames) -> Tuple[np.ndarray, List[np.ndarray]]:
         """every box: (centres (n, 3) float32, [ascending point indices of the kept cluster]); box i is cropped from
         clouds[frames[i]]"""
@@ -261,3 +311,209 @@ def centroid(P: np.ndarray) -> np.ndarray:
 def gather(cloud, indices) -> np.ndarray:
     """the points of `indices` (ExtractIndices::filter), (k, 3) float32"""
     return _xyz(cloud)[np.asarray(indices, np.int64)]
+
+
+# ---- plane removal (include/pbd.h, pbd_remove_planes); every float32 / float64 operation rounded on its own, in order
+_F = np.float32
+
+
+def plane_normals(P: np.ndarray, s: int, depth_change: float):
+    """(normals (rows, cols, 3) float32, d (rows, cols) float32): NaN off the valid window or where it holds a depth edge"""
+    H, W = P.shape[:2]
+    x, y, z = P[..., 0], P[..., 1], P[..., 2]
+    fin = np.isfinite(P).all(axis=2)
+    edge = np.ones((H, W), bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = _F(depth_change) * z
+        e = ~fin[1:-1, 1:-1]
+        zc, tc = z[1:-1, 1:-1], t[1:-1, 1:-1]
+        for sl in ((slice(1, -1), slice(0, -2)), (slice(1, -1), slice(2, None)), (slice(0, -2), slice(1, -1)),
+                   (slice(2, None), slice(1, -1))):
+            e |= ~fin[sl] | (np.abs(z[sl] - zc) > tc)
+        edge[1:-1, 1:-1] = e
+        dx = np.full_like(P, np.nan)
+        dy = np.full_like(P, np.nan)
+        dx[:, 1:-1] = P[:, 2:] - P[:, :-2]
+        dy[1:-1] = P[2:] - P[:-2]
+        N = np.full((H, W, 3), np.nan, np.float32)
+        D = np.full((H, W), np.nan, np.float32)
+        r0, r1, c0, c1 = s + 1, H - s - 1, s + 1, W - s - 1          # valid centres: [r0, r1) x [c0, c1)
+        if r1 <= r0 or c1 <= c0:
+            return N, D
+        # row sums over columns c-s .. c+s for rows 1 .. H-2, left to right from 0
+        rsx = np.zeros((H - 2, c1 - c0, 3), np.float32)
+        rsy = np.zeros((H - 2, c1 - c0, 3), np.float32)
+        redge = np.zeros((H - 2, c1 - c0), bool)
+        for k in range(-s, s + 1):
+            rsx = rsx + dx[1:-1, c0 + k:c1 + k]
+            rsy = rsy + dy[1:-1, c0 + k:c1 + k]
+            redge |= edge[1:-1, c0 + k:c1 + k]
+        # the row sums of rows r-s .. r+s, top to bottom from 0
+        sx = np.zeros((r1 - r0, c1 - c0, 3), np.float32)
+        sy = np.zeros((r1 - r0, c1 - c0, 3), np.float32)
+        wedge = np.zeros((r1 - r0, c1 - c0), bool)
+        for k in range(-s, s + 1):
+            sx = sx + rsx[r0 - 1 + k:r1 - 1 + k]
+            sy = sy + rsy[r0 - 1 + k:r1 - 1 + k]
+            wedge |= redge[r0 - 1 + k:r1 - 1 + k]
+        area = _F((2 * s + 1) * (2 * s + 1))
+        mx, my = sx / area, sy / area
+        nx = my[..., 1] * mx[..., 2] - my[..., 2] * mx[..., 1]
+        ny = my[..., 2] * mx[..., 0] - my[..., 0] * mx[..., 2]
+        nz = my[..., 0] * mx[..., 1] - my[..., 1] * mx[..., 0]
+        ln = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        nx, ny, nz = nx / ln, ny / ln, nz / ln
+        px, py, pz = x[r0:r1, c0:c1], y[r0:r1, c0:c1], z[r0:r1, c0:c1]
+        flip = ((nx * px + ny * py) + nz * pz) > 0
+        nx, ny, nz = np.where(flip, -nx, nx), np.where(flip, -ny, ny), np.where(flip, -nz, nz)
+        dd = (nx * px + ny * py) + nz * pz
+        nan = _F(np.nan)
+        N[r0:r1, c0:c1] = np.where(wedge[..., None], nan, np.stack([nx, ny, nz], axis=-1))
+        D[r0:r1, c0:c1] = np.where(wedge, nan, dd)
+    return N, D
+
+
+def plane_join(zp, np_, dp, fq, nq, dq, dist: float, cos_thr):
+    """PlaneCoefficientComparator(p, q): q finite, |d(p) - d(q)| < dist * (z(p) * z(p)), n(p) . n(q) > cos_thr (arrays)"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        near = np.abs(dp - dq) < _F(dist) * (zp * zp)
+        dot = (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2]
+        return fq & near & (dot > cos_thr)
+
+
+def plane_segments(P, N, D, dist: float, angle: float) -> np.ndarray:
+    """the segment of every point as the smallest point index of its component (rows * cols,) int64 (non-finite: itself)"""
+    H, W = P.shape[:2]
+    fin = np.isfinite(P).all(axis=2)
+    cos_thr = _F(math.cos(angle))
+    z = P[..., 2]
+    idx = np.arange(H * W).reshape(H, W)
+    left = fin[:, 1:] & plane_join(z[:, 1:], N[:, 1:], D[:, 1:], fin[:, :-1], N[:, :-1], D[:, :-1], dist, cos_thr)
+    up = fin[1:] & plane_join(z[1:], N[1:], D[1:], fin[:-1], N[:-1], D[:-1], dist, cos_thr)
+    ea = np.concatenate([idx[:, 1:][left], idx[1:][up]])
+    eb = np.concatenate([idx[:, :-1][left], idx[:-1][up]])
+    return min_label_components(H * W, ea, eb)
+
+
+def min_label_components(n: int, ea: np.ndarray, eb: np.ndarray) -> np.ndarray:
+    """the smallest node of every node's connected component (edges ea[i] - eb[i])"""
+    lab = np.arange(n)
+    if not len(ea):
+        return lab
+    while True:
+        prev = lab.copy()
+        la, lb = lab[ea], lab[eb]
+        mn = np.minimum(la, lb)
+        for t in (ea, eb, la, lb):
+            np.minimum.at(lab, t, mn)
+        while True:
+            nxt = lab[lab]
+            if np.array_equal(nxt, lab):
+                break
+            lab = nxt
+        if np.array_equal(lab, prev):
+            return lab
+
+
+def jacobi3(A):
+    """cyclic Jacobi sweeps on a symmetric 3x3 (lists of Python floats, modified in place); returns V"""
+    V = [[1.0 if i == k else 0.0 for k in range(3)] for i in range(3)]
+    for _ in range(JACOBI_SWEEPS):
+        for p, q in ((0, 1), (0, 2), (1, 2)):
+            apq = A[p][q]
+            if apq == 0.0:
+                continue
+            theta = (A[q][q] - A[p][p]) / (2.0 * apq)
+            t = 1.0 / (abs(theta) + math.sqrt(theta * theta + 1.0))
+            if theta < 0.0:
+                t = -t
+            c = 1.0 / math.sqrt(t * t + 1.0)
+            s = t * c
+            for k in range(3):
+                akp, akq = A[k][p], A[k][q]
+                A[k][p], A[k][q] = c * akp - s * akq, s * akp + c * akq
+            for k in range(3):
+                apk, aqk = A[p][k], A[q][k]
+                A[p][k], A[q][k] = c * apk - s * aqk, s * apk + c * aqk
+            for k in range(3):
+                vkp, vkq = V[k][p], V[k][q]
+                V[k][p], V[k][q] = c * vkp - s * vkq, s * vkp + c * vkq
+    return V
+
+
+def plane_fit(P, mask, count: int):
+    """(coefficients float32[4], curvature) of the points of `mask` (rows, cols): moments per row left to right, rows top to
+    bottom, the Jacobi eigenpair"""
+    x, y, z = (np.where(mask, P[..., k].astype(np.float64), 0.0) for k in range(3))
+    vals = (x, y, z, x * x, x * y, x * z, y * y, y * z, z * z)
+    tot = []
+    for v in vals:
+        rows = np.add.accumulate(np.concatenate([np.zeros((v.shape[0], 1)), v], axis=1), axis=1)[:, -1]
+        tot.append(float(np.add.accumulate(np.concatenate([[0.0], rows]))[-1]))
+    n = float(count)
+    m = [t / n for t in tot]
+    xx, xy, xz = m[3] - m[0] * m[0], m[4] - m[0] * m[1], m[5] - m[0] * m[2]
+    yy, yz, zz = m[6] - m[1] * m[1], m[7] - m[1] * m[2], m[8] - m[2] * m[2]
+    A = [[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]
+    V = jacobi3(A)
+    k = 0
+    if A[1][1] < A[k][k]:
+        k = 1
+    if A[2][2] < A[k][k]:
+        k = 2
+    tr = (xx + yy) + zz
+    curv = _ieee_div(A[k][k], tr)
+    a, b, c = V[0][k], V[1][k], V[2][k]
+    d = -((a * m[0] + b * m[1]) + c * m[2])
+    if ((-m[0]) * a + (-m[1]) * b) + (-m[2]) * c < 0.0:
+        a, b, c, d = -a, -b, -c, -d
+    return np.array([a, b, c, d], np.float64).astype(np.float32), curv
+
+
+def _ieee_div(a: float, b: float) -> float:
+    """a / b with IEEE semantics for b == 0"""
+    if b != 0.0:
+        return a / b
+    if a == 0.0 or math.isnan(a):
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def plane_absorb(coef, pts, zc, dist: float):
+    """|((a x + b y) + c z) + d| < dist * (zc * zc) in float32 (coef (k, 4), pts (k, 3))"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        dd = ((coef[:, 0] * pts[:, 0] + coef[:, 1] * pts[:, 1]) + coef[:, 2] * pts[:, 2]) + coef[:, 3]
+        return np.abs(dd) < _F(dist) * (zc * zc)
+
+
+def plane_refine_pass(lab, P, planes, dist: float) -> np.ndarray:
+    """one forward refinement pass (include/pbd.h's recurrence, one anti-diagonal at a time); labels -1 / -2 / plane index"""
+    H, W = lab.shape
+    o = np.array(lab, np.int64)
+    F = o.copy()
+    fin = np.isfinite(P).all(axis=2)
+    for t in range(H + W - 1):
+        r = np.arange(max(0, t - W + 1), min(H - 1, t) + 1)
+        c = t - r
+        m = o[r, c].copy()
+        sel = (r >= 1) & (c <= W - 2) & (m == -2)
+        if sel.any():
+            rs, cs = r[sel], c[sel]
+            u = F[rs - 1, cs]
+            ok = (u >= 0) & fin[rs - 1, cs + 1]
+            ok[ok] = plane_absorb(planes[u[ok]], P[rs[ok], cs[ok]], P[rs[ok] - 1, cs[ok], 2], dist)
+            mm = m[sel]
+            mm[ok] = u[ok]
+            m[sel] = mm
+        f = m.copy()
+        sel = (c >= 1) & (r <= H - 2) & (m == -2)
+        if sel.any():
+            rs, cs = r[sel], c[sel]
+            lft = F[rs, cs - 1]
+            ok = lft >= 0
+            ok[ok] = plane_absorb(planes[lft[ok]], P[rs[ok], cs[ok]], P[rs[ok], cs[ok] - 1, 2], dist)
+            ff = f[sel]
+            ff[ok] = lft[ok]
+            f[sel] = ff
+        F[r, c] = f
+    return F
