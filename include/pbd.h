@@ -70,18 +70,28 @@ typedef struct pbd_model {
 
 enum { PBD_REAL_F32 = 0, PBD_REAL_F64 = 1 };
 enum { PBD_CONV_EXACT = 0,   /* multiply and add rounded separately in the reference's order: bit-identical responses */
-       PBD_CONV_FMA = 1,     /* fused multiply-add: responses within 1e-4, not bit-identical */
+       PBD_CONV_FMA = 1,     /* fused multiply-add: responses within 1e-4 on unit-scale inputs, not bit-identical.
+                                Relative to M = sum |w| |f| over the response's window (border cells included) and
+                                K = k*k*32 products, every response is within 8 sqrt(K) u M of the exact sum, u = 2^-24
+                                (float) or 2^-53 (double; against the reference's own double sum: twice that) -- under
+                                0.02 of that bound observed (tests/conv_reference.py, tests/test_gpu_conv_modes.py) */
        PBD_CONV_MFMA = 2,    /* matrix cores, bf16 hi/lo operand split (3 MFMAs per product tile), fp32 accumulation:
-                                responses within 1e-4 (~1e-6 observed), not bit-identical; 5x5 filters, PBD_REAL_F32 only */
+                                responses within 1e-4 on unit-scale inputs, not bit-identical; every response within
+                                8 sqrt(3K) 2^-24 M of the exact sum of hi*hi + hi*lo + lo*hi (lo*lo, ~2^-16 of a product,
+                                is not computed) -- under 0.04 of that bound observed, RMS relative error ~2^-26;
+                                5x5 filters, PBD_REAL_F32 only */
        PBD_CONV_MFMA_F16 = 3 }; /* matrix cores, operands rounded once to fp16 (1 MFMA per product tile), fp32 accumulation:
                                 the 1e-4 bar does not hold (~1e-3 observed on unit-scale scores); same restrictions.
+                                Every response is within 8 sqrt(K) 2^-24 M of the exact sum of the fp16 operands'
+                                products, plus half an fp16 ulp of the result (the response's own rounding).
                                 In this mode the RESPONSES live on the device as fp16 (BASELINE configs[4] "fp16 responses"):
                                 pbd_conv_pdf returns them widened to float, |v| >= 65520 saturates to +-inf, and pbd_dp_min
                                 ROUNDS THE CALLER'S float scores to fp16 before the dynamic program (exact for scores that
                                 came from pbd_conv_pdf; arbitrary scores lose precision: tests/test_gpu_parity.py::
                                 test_mfma_f16_dp_min_rounds_its_input pins this) */
 enum { PBD_CONV_MFMA_F64 = 4 };  /* fp64 matrix cores (v_mfma_f64_16x16x4_f64), fp64 operands and fp64 accumulation:
-                                responses within fp64 rounding of the reference's summation order (~1e-13 relative),
+                                responses within fp64 rounding of the reference's summation order (~1e-13 relative;
+                                within 2 * 8 sqrt(K) 2^-53 M of the reference's double responses, as PBD_CONV_FMA),
                                 not bit-identical; every filter size the exact path takes; PBD_REAL_F64 only (pbd_create
                                 refuses it for PBD_REAL_F32 with PBD_ERR_UNSUPPORTED) */
 
