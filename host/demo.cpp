@@ -5,7 +5,7 @@
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
-//            [--remove-planes]]
+//            [--remove-planes] [--depth-consistency ZFACTOR]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
@@ -19,6 +19,8 @@
 //           "object SIZE x y z" (the kept cluster's size and centroid)
 //   --remove-planes: with --camera, organizedMultiplaneSegmentation before the clustering (the callers' remove_planes option):
 //           "plane K a b c d INLIERS" per plane, "kept N" (the reduced cloud's points), then the lines above on the reduced cloud
+//   --depth-consistency ZFACTOR: with --depth, one line "depth_consistency zfactor Z: kept K dropped D" (filterCandidatesByDepth
+//           on the unsuppressed list, on the device), then the candidates of detect(im, depth) with setDepthConsistency on
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -114,7 +116,7 @@ static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Imag
 
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
-               int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes)
+               int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes, float dcz)
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -164,6 +166,18 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         conv.pdf(pyramid, pdf);
         dp.min(pdf, rootv, rooti, model.ncomponents());
         dp.argmin(features.scales(), candidates);
+    } else if (depth && dcz >= 0) {
+        // filterCandidatesByDepth on the unsuppressed list (its counts), then the chain detect(im, depth) runs with the setting on
+        PartsBasedDetector<T> raw(0, conv_mode);
+        raw.distributeModel(model);
+        std::vector<Candidate> all, kept;
+        raw.detect(im, all);
+        kept = all;
+        raw.filterCandidatesByDepth(*depth, kept, dcz);
+        std::printf("depth_consistency zfactor %g: kept %zu dropped %zu\n", dcz, kept.size(), all.size() - kept.size());
+        pbd.distributeModel(model);
+        pbd.setDepthConsistency(true, dcz);
+        pbd.detect(im, *depth, candidates);
     } else {
         pbd.distributeModel(model);
         pbd.detect(im, candidates);
@@ -218,7 +232,7 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -226,6 +240,7 @@ int main(int argc, char **argv)
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
     std::vector<const char *> also;
     const char *depth_path = NULL;
+    float dcz = -1.f;
     bool have_camera = false, remove_planes = false;
     pbd_pinhole camera = {0, 0, 0, 0, 0, 0};
     for (int i = 3; i < argc; ++i) {
@@ -239,6 +254,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--also") && i + 1 < argc) also.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depth_path = argv[++i];
+        else if (!std::strcmp(argv[i], "--depth-consistency") && i + 1 < argc) dcz = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--camera") && i + 1 < argc) {
             have_camera = std::sscanf(argv[++i], "%lf,%lf,%lf,%lf", &camera.fx, &camera.fy, &camera.cx, &camera.cy) == 4;
             if (!have_camera) { std::fprintf(stderr, "--camera takes fx,fy,cx,cy\n"); return -1; }
@@ -250,6 +266,10 @@ int main(int argc, char **argv)
     }
     if (remove_planes && !have_camera) {
         std::fprintf(stderr, "--remove-planes needs --depth and --camera\n");
+        return -1;
+    }
+    if (dcz >= 0 && (!depth_path || staged || stream_k > 0)) {
+        std::fprintf(stderr, "--depth-consistency needs --depth, not with --staged or --stream\n");
         return -1;
     }
     if (have_camera && !depth_path) {
@@ -284,8 +304,8 @@ int main(int argc, char **argv)
         }
         const Image *dp = depth_path ? &depth : NULL;
         const pbd_pinhole *cp = have_camera ? &camera : NULL;
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes);
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

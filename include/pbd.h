@@ -355,6 +355,66 @@ int pbd_remove_planes_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clou
                              int32_t *d_kept, int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers,
                              int32_t *d_nplanes, int plane_capacity, long long *d_status);
 
+/* Depth consistency (new surface; opt-in): SearchSpacePruning<T>::filterCandidatesByDepth(parts, candidates, depth, zfactor)
+ * (src/SearchSpacePruning.cpp:73-95), the step detect(im, depth) documents ("used for depth consistency and search space
+ * pruning", src/PartsBasedDetector.cpp:65) and leaves commented out (:91-93, zfactor 0.03).  It runs before the callers' sort and
+ * suppression: chain it with pbd_suppress* below.  Records are this handle's, unsuppressed (pbd_set_nms off); a record's frame index
+ * is its `frame` field minus frame_offset, as pbd_boxes3d; the model tables are the handle's.  T is the handle's real type.
+ * depth[f]: frame f's depth image, one channel, depth_code 0 (8U), 2 (16U), 5 (32F) or 6 (64F), one code per call, any pitch.
+ *   samples  part j's box (x, y, w, h of component-local part j of the record) in the depth image's own coordinates, unscaled (as
+ *            the reference reads depth(child)), & Rect(0, 0, dcols, drows) in 64-bit arithmetic.  Project decision: the reference's
+ *            ROI throws cv::Exception for a box that leaves the image.  Every pixel of the clipped box is one sample, zeros
+ *            included, converted to T (8U / 16U exactly, 64F to float rounded to nearest).  Project decision: a NaN sample reads as
+ *            0 (ROS depth marks "no reading" with NaN; std::nth_element over NaN is undefined)
+ *   median   M = the clipped area; the sample at 0-based index M / 2 of the samples sorted ascending (nth_element(first, first +
+ *            M/2, last): the upper median for even M), exact; -0.0 == +0.0.  An empty clipped box has no median
+ *   edges    for p = 1 .. nparts-1, q = parentid[c][p] (component-local), mc / mq the medians of parts p / q: the record is
+ *            rejected when both exist, mc > 0, mq > 0 and (double)std::abs(mc - mq) > std::sqrt((double)ax*ax + (double)ay*ay) *
+ *            (double)zfactor, the subtraction and abs in T, (ax, ay) = anchors[defid[mix_offset[gp] + 0]] (part.anchor(0), the
+ *            mixture-0 anchor).  A NaN difference (Inf - Inf) does not reject.  The order of the edges does not matter (the
+ *            reference's `break` is an optimisation)
+ *   one part project decision: a record of a one-part component is kept (the reference's `size_t p = nparts-1; p >= 1` loop drops
+ *            every such record, a defect)
+ *   output   the kept records in input order (a stable compaction), byte-identical to their input, `frame` fields unchanged
+ * pbd_depth_consistency: host records and images, synchronous.  *nout = the kept count; above `capacity` the first `capacity`
+ * records are written and the call returns PBD_ERR_CAPACITY.  out == cand (in place) is allowed.
+ * pbd_depth_consistency_device: d_depth[f].data are device pointers (a frame may be a region of a larger image, read in place);
+ * the records are the payload d_payload (word 0 = count, capacity records); d_out = int32[1 + out_capacity * stride]: word 0 = the
+ * kept count, which may exceed out_capacity (then the first out_capacity records are written).  An input word 0 that is negative
+ * (a suppression overflow) or > capacity (a truncated list) gives word 0 = -1 and no records: a filtered truncated list is never
+ * mistaken for a complete one.  A record whose frame index is out of range, whose component is unknown or whose nparts is not its
+ * component's part count (1..max parts) is dropped.  d_out must not overlap d_payload.  Asynchronous on pbd_stream(), no host
+ * synchronisation; the handle's workspace grows with capacity (about 12 bytes per part of a record), never with the samples.
+ * Refused with PBD_ERR_INVALID, naming the index, before anything is enqueued: a depth_code other than the four, a non-positive
+ * size, an image of 2^31 pixels or more, a pitch below the row bytes, on the device a pointer or pitch not a multiple of the
+ * element size; in the host form a record whose frame index, component or nparts is bad as above; a NaN zfactor (any other
+ * zfactor, infinities included, is taken as given).  PBD_ERR_STATE while a batch is in flight.  The resident detect result is not
+ * touched. */
+int pbd_depth_consistency(pbd_handle *h, int nframes, const struct pbd_frame *depth, int depth_code, float zfactor,
+                          const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity, int *nout);
+int pbd_depth_consistency_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code, float zfactor,
+                                 const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
+
+/* Suppression of a caller's list (new surface): exactly the pbd_set_nms stage above -- per frame the stable score sort, then the
+ * greedy painted-canvas suppression -- applied to any records of this handle, e.g. after pbd_depth_consistency, or to the merged
+ * lists of level-sharded handles (pbd_set_nms itself stays refused with sharding: one rank's levels are not the union).
+ * A record's frame is `frame` - frame_offset and has its own Rect(0, 0, im_cols[f], im_rows[f]) (1..65536 each).  Records must
+ * be grouped by ascending frame.  Output: frame by frame, each frame's kept records in sorted order, `frame` fields unchanged.
+ * pbd_suppress: host records, synchronous; a record whose frame index is out of range, lower than its predecessor's, or whose
+ * nparts is outside 1..max parts is PBD_ERR_INVALID naming the record; *nout = the kept count, above `capacity` the first `capacity`
+ * records and PBD_ERR_CAPACITY.  In place (out == cand) is allowed.
+ * pbd_suppress_device: the payload and output as pbd_depth_consistency_device (word 0 = kept count, may exceed out_capacity; an
+ * input word 0 that is negative or > capacity gives -1).  Project decision: a device list with a frame index out of range or not
+ * grouped ascending also gives word 0 = -1.  capacity must be at least 1 (PBD_ERR_INVALID otherwise; out_capacity may be 0).
+ * Asynchronous on pbd_stream() while the list of frame sizes is that of the previous pbd_suppress* call; a new list of frame
+ * sizes synchronises the stream and uploads its small canvas tables first (both forms).  A NaN overlap or a bad size is
+ * PBD_ERR_INVALID; PBD_ERR_STATE while a batch is in flight;
+ * the resident detect result is not touched. */
+int pbd_suppress(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap,
+                 const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity, int *nout);
+int pbd_suppress_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap,
+                        const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -382,8 +442,9 @@ int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, con
 int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacity, int *ncand);
 
 /* ---- PartsBasedDetector<T>::detect (include/PartsBasedDetector.hpp:172-173, src/PartsBasedDetector.cpp:69-95).
- * `depth` of the 3-argument overload is ignored by the reference (:91-93) and has no parameter here; the callers' use of the
- * depth image after detection, Candidate::boundingBox3D, is pbd_boxes3d (next to pbd_set_nms). */
+ * `depth` of the 3-argument overload has no parameter here: the reference ignores it (:91-93), and the opt-in filter it leaves
+ * commented out is pbd_depth_consistency, chained by the callers' detect(im, depth) when they turn it on; the callers' later use of
+ * the depth image, Candidate::boundingBox3D, is pbd_boxes3d (next to pbd_set_nms). */
 int pbd_detect(pbd_handle *h, const void *img, int rows, int cols, int channels, size_t stride_bytes,
                int32_t *cand, int capacity, int *ncand);
 /* The same for an image of any accepted depth (depth_code as in pbd_features_pyramid); pbd_detect is depth_code 0.
@@ -471,6 +532,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        /* pbd_boxes3d_camera*, pbd_cluster_objects*; k_cl_crop_scan / k_cl_grid_scan time the three k_cl_scan_* kernels of that scan */
        PBD_K_CAMERA_BOXES, PBD_K_CL_CROP_COUNT, PBD_K_CL_CROP_SCAN, PBD_K_CL_CROP_SCATTER, PBD_K_CL_CLEAR, PBD_K_CL_GRID_COUNT,
        PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST, PBD_K_CL_SELECT, PBD_K_CL_OUT,
+       /* pbd_depth_consistency*; k_dc_select times its three size classes, k_dc_compact the decision and the compaction */
+       PBD_K_DC_CLASSIFY, PBD_K_DC_SELECT, PBD_K_DC_COMPACT,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

@@ -285,6 +285,45 @@ inline void detect(pbd_handle *h, const typename Tr::Image &im, std::vector<type
     unpack_candidates<Tr>(h, buf, n, candidates);
 }
 
+// SearchSpacePruning<T>::filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-95) on the device (pbd_depth_consistency) over
+// n records of this handle in `buf`, in place: n becomes the kept count, the kept records stay in order.  `depth` is one channel
+// of any accepted depth; every record is taken as one of this frame (frame field 0).
+template <class Tr>
+inline void depth_consistency(pbd_handle *h, const typename Tr::Image &depth, float zfactor, std::vector<int32_t> &buf, int &n)
+{
+    if (Tr::img_channels(depth) != 1) Tr::fail(PBD_ERR_INVALID, "pbd: depth_consistency: the depth image has one channel");
+    pbd_frame fr;
+    fr.data = Tr::img_data(depth); fr.rows = Tr::img_rows(depth); fr.cols = Tr::img_cols(depth); fr.stride_bytes = Tr::img_step(depth);
+    int kept = 0;
+    check<Tr>(h, pbd_depth_consistency(h, 1, &fr, Tr::img_depth(depth), zfactor, n ? &buf[0] : NULL, n, 0, n ? &buf[0] : NULL, n, &kept));
+    n = kept;
+}
+
+// Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of n records of one rows x cols frame in `buf`, on the
+// device (pbd_suppress, the pbd_set_nms stage), in place: n becomes the kept count
+template <class Tr>
+inline void suppress(pbd_handle *h, int rows, int cols, float overlap, std::vector<int32_t> &buf, int &n)
+{
+    int kept = 0;
+    check<Tr>(h, pbd_suppress(h, 1, &rows, &cols, overlap, n ? &buf[0] : NULL, n, 0, n ? &buf[0] : NULL, n, &kept));
+    n = kept;
+}
+
+// detect(im, depth) with the depth filter on: the unsuppressed list (the handle's pbd_set_nms must be off), the filter, then --
+// overlap >= 0 -- the suppression, in the reference's order (src/PartsBasedDetector.cpp:91-93, then cells/detect.cpp:237-238)
+template <class Tr>
+inline void detect_depth(pbd_handle *h, const typename Tr::Image &im, const typename Tr::Image &depth, float zfactor, float overlap,
+                         std::vector<typename Tr::Candidate> &candidates, int capacity)
+{
+    std::vector<int32_t> buf((size_t)capacity * pbd_candidate_stride(h) + 1);
+    int n = 0;
+    check<Tr>(h, pbd_detect_typed(h, Tr::img_data(im), Tr::img_rows(im), Tr::img_cols(im), Tr::img_channels(im),
+                                  Tr::img_step(im), Tr::img_depth(im), &buf[0], capacity, &n));
+    depth_consistency<Tr>(h, depth, zfactor, buf, n);
+    if (overlap >= 0) suppress<Tr>(h, Tr::img_rows(im), Tr::img_cols(im), overlap, buf, n);
+    unpack_candidates<Tr>(h, buf, n, candidates);
+}
+
 // Frames of any sizes in one call (new surface: pbd_detect_frames; the reference has no batch API): candidates[i] receives
 // what detect(images[i]) gives.  The images share one depth and one channel count; any accepted depth.
 template <class Tr>

@@ -533,6 +533,8 @@ class PartsBasedDetector {
     int max_batch_;
     bool nms_;
     float overlap_;
+    bool depth_on_;
+    float zfactor_;
     PartsBasedDetector(const PartsBasedDetector &);
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
@@ -540,7 +542,8 @@ public:
     // reference has only its exact convolution
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
-        : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f) {}
+        : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f),
+          depth_on_(false), zfactor_(0.03f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -561,12 +564,63 @@ public:
         nms_ = overlap >= 0;
         overlap_ = overlap;
     }
+    // new surface: detect(im, depth, candidates) runs filterCandidatesByDepth(depth, ., zfactor) on the unsuppressed list, before
+    // the suppression -- the reference's commented-out call (src/PartsBasedDetector.cpp:91-93).  Off by default (depth ignored, as
+    // in the reference); kept across distributeModel().
+    void setDepthConsistency(bool on, float zfactor = 0.03f)
+    {
+        if (on && zfactor != zfactor) throw Error(PBD_ERR_INVALID, "zfactor is NaN");
+        depth_on_ = on;
+        zfactor_ = zfactor;
+    }
     void detect(const Image &im, std::vector<Candidate> &candidates) { detect(im, Image(), candidates); }
-    void detect(const Image &im, const Image & /*depth: ignored by the reference too, src/PartsBasedDetector.cpp:91-93*/,
-                std::vector<Candidate> &candidates)
+    // `depth` is ignored, as by the reference (src/PartsBasedDetector.cpp:91-93), unless setDepthConsistency(true) and it is not
+    // empty (the reference's `if (!depth.empty())`)
+    void detect(const Image &im, const Image &depth, std::vector<Candidate> &candidates)
     {
         if (!h_) throw Error(PBD_ERR_STATE, "detect() before distributeModel()");
-        pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
+        if (!depth_on_ || !depth.data || depth.rows < 1 || depth.cols < 1) {
+            pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
+            return;
+        }
+        if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, false, overlap_);   // the filter reads the unsuppressed list
+        try {
+            pbdbind::detect_depth<HostTraits<T> >(h_, im, depth, zfactor_, nms_ ? overlap_ : -1.f, candidates, 1 << 18);
+        } catch (...) {
+            if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
+            throw;
+        }
+        if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
+    }
+    // SearchSpacePruning<T>::filterCandidatesByDepth(parts, candidates, depth, zfactor) (src/SearchSpacePruning.cpp:73-95) on the
+    // device (pbd_depth_consistency): the candidates whose parts agree in depth, in order.  `depth` is one channel of any accepted
+    // depth, read in its own coordinates; every candidate is taken as one of this frame.
+    void filterCandidatesByDepth(const Image &depth, std::vector<Candidate> &candidates, float zfactor = 0.03f)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "filterCandidatesByDepth() before distributeModel()");
+        std::vector<int32_t> rec = records(candidates);
+        const std::vector<int32_t> in = rec;
+        int n = (int)candidates.size();
+        pbdbind::depth_consistency<HostTraits<T> >(h_, depth, zfactor, rec, n);
+        const size_t stride = (size_t)pbd_candidate_stride(h_);
+        std::vector<Candidate> kept;
+        for (size_t i = 0, k = 0; i < candidates.size() && k < (size_t)n; ++i)   // the kept records are the input's, in order
+            if (std::memcmp(&in[i * stride], &rec[k * stride], stride * sizeof(int32_t)) == 0) {
+                kept.push_back(candidates[i]);
+                ++k;
+            }
+        candidates.swap(kept);
+    }
+    // Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) on the device (pbd_suppress), for a list built
+    // elsewhere (e.g. after filterCandidatesByDepth); every candidate is taken as one of this rows x cols frame
+    void suppress(const Image &im, std::vector<Candidate> &candidates, float overlap)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "suppress() before distributeModel()");
+        std::vector<int32_t> rec = records(candidates);
+        int n = (int)candidates.size();
+        pbdbind::suppress<HostTraits<T> >(h_, im.rows, im.cols, overlap, rec, n);
+        candidates.clear();
+        pbdbind::unpack_candidates<HostTraits<T> >(h_, rec, n, candidates);
     }
     // this handle's records of frame 0 for the candidates (the layout pbd_detect returns)
     std::vector<int32_t> records(const std::vector<Candidate> &candidates) const

@@ -14,6 +14,7 @@
 
 #include <opencv2/core/core.hpp>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -127,6 +128,61 @@ template <typename T>
 inline void hipDetectBatch(pbd_handle *h, const vectorMat &images, std::vector<vectorCandidate> &candidates)
 {
     pbdbind::detect_batch<CvTraits<T> >(h, images, candidates, 1 << 18);
+}
+
+// the records (pbd_candidate_stride words each) of candidates of one frame: component, score, parts (the layout pbd_detect returns).
+// A template over the candidate type, so that only the calls below instantiate it.
+template <class Cand>
+inline void hipRecords(pbd_handle *h, std::vector<Cand> &candidates, std::vector<int32_t> &rec)
+{
+    const size_t stride = (size_t)pbd_candidate_stride(h);
+    rec.assign(candidates.size() * stride + 1, 0);
+    for (size_t i = 0; i < candidates.size(); ++i) {
+        int32_t *r = &rec[i * stride];
+        const std::vector<cv::Rect> &parts = candidates[i].parts();
+        const float score = candidates[i].score();
+        r[1] = candidates[i].component();
+        std::memcpy(&r[5], &score, sizeof score);
+        r[6] = (int32_t)parts.size();
+        for (size_t k = 0; k < parts.size() && 8 + 4 * k + 3 < stride; ++k) {
+            r[8 + 4 * k] = parts[k].x; r[9 + 4 * k] = parts[k].y; r[10 + 4 * k] = parts[k].width; r[11 + 4 * k] = parts[k].height;
+        }
+    }
+}
+
+// SearchSpacePruning<T>::filterCandidatesByDepth(parts_, candidates, depth, zfactor) on the device (pbd_depth_consistency): what
+// the commented-out call of PartsBasedDetector<T>::detect would do (src/PartsBasedDetector.cpp:91-93, zfactor 0.03).  The kept
+// candidates stay in order; `depth` is one channel of any accepted depth; every candidate is one of this frame.
+template <typename T>
+inline void hipFilterCandidatesByDepth(pbd_handle *h, std::vector<typename CvTraits<T>::Candidate> &candidates, const cv::Mat &depth,
+                                       float zfactor)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    const std::vector<int32_t> in(rec);
+    int n = (int)candidates.size();
+    pbdbind::depth_consistency<CvTraits<T> >(h, depth, zfactor, rec, n);
+    const size_t stride = (size_t)pbd_candidate_stride(h);
+    std::vector<typename CvTraits<T>::Candidate> kept;
+    for (size_t i = 0, k = 0; i < candidates.size() && k < (size_t)n; ++i)   // the kept records are the input's, in order
+        if (std::memcmp(&in[i * stride], &rec[k * stride], stride * sizeof(int32_t)) == 0) {
+            kept.push_back(candidates[i]);
+            ++k;
+        }
+    candidates.swap(kept);
+}
+
+// Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) on the device (pbd_suppress, the pbd_set_nms stage)
+// for a list built elsewhere, e.g. after hipFilterCandidatesByDepth; every candidate is one of this frame
+template <typename T>
+inline void hipSuppress(pbd_handle *h, const cv::Mat &im, std::vector<typename CvTraits<T>::Candidate> &candidates, float overlap)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    int n = (int)candidates.size();
+    pbdbind::suppress<CvTraits<T> >(h, im.rows, im.cols, overlap, rec, n);
+    candidates.clear();
+    pbdbind::unpack_candidates<CvTraits<T> >(h, rec, n, candidates);
 }
 
 }  // namespace pbd_adapters

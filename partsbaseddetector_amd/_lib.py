@@ -26,7 +26,8 @@ DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3
 DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32): 5, np.dtype(np.float64): 6}
 KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows", "k_dt_cols", "k_dp_combine",
            "k_dp_root", "k_argmin", "k_camera_boxes", "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear",
-           "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out"]
+           "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out",
+           "k_dc_classify", "k_dc_select", "k_dc_compact"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -38,7 +39,8 @@ SYMBOLS = [
     "pbd_detect_batch_device_submit", "pbd_detect_batch_device_out", "pbd_argmin_device_out", "pbd_stream", "pbd_get_stage", "pbd_profile_enable", "pbd_profile_reset", "pbd_profile_read",
     "pbd_kernel_name", "pbd_synchronize", "pbd_detect_frames", "pbd_detect_frames_device", "pbd_detect_frames_device_out",
     "pbd_boxes3d", "pbd_boxes3d_device", "pbd_boxes3d_camera", "pbd_boxes3d_camera_device", "pbd_cluster_objects",
-    "pbd_cluster_objects_device", "pbd_remove_planes", "pbd_remove_planes_device",
+    "pbd_cluster_objects_device", "pbd_remove_planes", "pbd_remove_planes_device", "pbd_depth_consistency",
+    "pbd_depth_consistency_device", "pbd_suppress", "pbd_suppress_device",
 ]
 
 
@@ -195,6 +197,14 @@ def load():
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.pbd_remove_planes_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CCloud), C.POINTER(CPlaneParams), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pbd_depth_consistency.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_depth_consistency_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_float, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_void_p, C.c_int]
+    lib.pbd_suppress.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_suppress_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int]
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

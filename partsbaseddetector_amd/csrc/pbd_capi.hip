@@ -137,7 +137,8 @@ inline short sat_short_round(float v)
 
 struct Plan {
     // key
-    int kind = 0;   // 0: from image size, 1: from explicit feature-map sizes
+    int kind = 0;   // 0: from image size, 1: from explicit feature-map sizes, 2: mixed sizes (below), 3: a group of a mixed plan's
+                    // frames for the dynamic program, 4: only the suppression's canvas tables of a list of frame sizes (pbd_suppress*)
     int rows = 0, cols = 0;         // the geometry does not depend on the channel count (offsets are in pixels)
     std::vector<int> key_dims;
     // geometry
@@ -331,6 +332,16 @@ struct pbd_handle {
     HostBuf pl_tab_host;
     DevBuf pl_tab, pl_ws, pl_cloud, pl_out;
     Event pl_tab_copied;
+    // pbd_depth_consistency*: the frame table (staged as above), the model's edge tables (built on first use), the workspace,
+    // the host form's depth images, records and output
+    HostBuf dc_tab_host;
+    DevBuf dc_tab, dc_ws, dc_depth, dc_rec, dc_out;
+    Event dc_tab_copied;
+    DevTable<int> dc_part_offset, dc_parent;
+    DevTable<double> dc_norm;
+    // pbd_suppress*: the canvas plan of the last list of frame sizes, the check flag, the host form's records and output
+    std::unique_ptr<Plan> sup_plan;
+    DevBuf sup_bad, sup_in, sup_out;
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -810,6 +821,8 @@ void mixed_append(Plan &M, const Plan &Q)
     M.mixed_frames += 1;
 }
 
+void post_canvas_plan(Plan &M);
+
 // After the last mixed_append: the pyramid launches (every frame's resized levels in one, then one per octave over every frame)
 // and the post-processing tables.  Host only.
 void mixed_finish(Plan &M, int interval)
@@ -835,7 +848,16 @@ void mixed_finish(Plan &M, int interval)
         M.run_n.push_back(n);
         M.run_npix.push_back(pix);
     }
+    post_canvas_plan(M);
+}
+
+// the suppression stage's per-frame tables of a list of frame sizes (M.fdim, M.mixed_frames): each frame's canvas in LDS or at
+// its offset in the global workspace.  Host only.
+void post_canvas_plan(Plan &M)
+{
     M.fcanvas.assign(M.mixed_frames, 0);
+    M.post_lds.clear(); M.post_glb.clear();
+    M.post_lds_words = M.post_glb_words = 0;
     for (int f = 0; f < M.mixed_frames; ++f) {
         const int r = M.fdim[f].x, c = M.fdim[f].y;
         if (post_canvas_in_lds(r, c)) {
@@ -1635,10 +1657,13 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
 // ---- post-processing (pbd_set_nms): per-frame sort + suppression of the payload d_in (capacity in_cap records, frame-local
 // `frame` fields, nframes frames of rows x cols) into d_out = int32[1 + out_cap * stride]: word 0 = kept count (-1 when more
 // than in_cap candidates were found), then the kept records frame by frame, `frame` + frame_offset.  No host synchronisation.
+// pbd_suppress*: `in_offset` is subtracted from the input's `frame` fields and `bad` (zeroed here) turns on the list's check.
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
-                 int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr)
+                 int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr, int in_offset = 0, int *bad = nullptr)
 {
     PostParams pp{};
+    pp.in_offset = in_offset; pp.bad = bad;
+    if (bad) HIPCHK(h, hipMemsetAsync(bad, 0, sizeof(int), st));
     pp.in = d_in; pp.in_cap = std::max(in_cap, 1);
     pp.stride = stride(h); pp.max_parts = h->max_parts; pp.nframes = nframes;
     pp.rows = rows; pp.cols = cols; pp.wpr = (cols + 31) / 32; pp.overlap = overlap;
@@ -2103,6 +2128,154 @@ int stage_table(pbd_handle *h, HostBuf &host, DevBuf &dev, Event &copied, const 
     memcpy(host.p, src, bytes);
     HIPCHK(h, hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipEventRecord(copied.p, h->stream));
+    return PBD_OK;
+}
+
+// ---- depth consistency (pbd_depth_consistency*; pbd_kernels_consistency.hip)
+// the model's tables the decision reads, uploaded on first use: part offsets, component-local parents, and per part the norm of
+// its mixture-0 anchor, std::sqrt((double)ax*ax + (double)ay*ay) (part.anchor(0): src/SearchSpacePruning.cpp:83)
+int dc_model_tables(pbd_handle *h)
+{
+    if (h->dc_norm.p) return PBD_OK;
+    const int totparts = (int)h->parentid.size();
+    std::vector<double> norm(std::max(totparts, 1), 0.0);
+    for (int c = 0; c < h->NC; ++c)
+        for (int gp = h->part_offset[c] + 1; gp < h->part_offset[c + 1]; ++gp) {
+            const int d = h->defid[h->mix_offset[gp]];
+            if (d < 0 || 2 * (size_t)d + 1 >= h->anchors.size()) continue;
+            const double ax = h->anchors[2 * (size_t)d], ay = h->anchors[2 * (size_t)d + 1];
+            norm[gp] = std::sqrt(ax * ax + ay * ay);
+        }
+    HIPCHK(h, h->dc_part_offset.upload(h->part_offset));
+    HIPCHK(h, h->dc_parent.upload(h->parentid));
+    HIPCHK(h, h->dc_norm.upload(norm));
+    return PBD_OK;
+}
+
+// every check of a pbd_depth_consistency* call's images and zfactor before anything is enqueued
+int check_dc_frames(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, float zfactor, bool host)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    if (!depth_size(depth_code))
+        return fail(h, PBD_ERR_INVALID, "depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F)", depth_code);
+    if (std::isnan(zfactor)) return fail(h, PBD_ERR_INVALID, "zfactor is NaN");
+    const size_t es = depth_size(depth_code);
+    for (int f = 0; f < nframes; ++f) {
+        const pbd_frame &d = depth[f];
+        if (!d.data || d.rows < 1 || d.cols < 1) return fail(h, PBD_ERR_INVALID, "frame %d: depth %dx%d at %p", f, d.rows, d.cols, d.data);
+        if ((long long)d.rows * d.cols >= (1LL << 31)) return fail(h, PBD_ERR_INVALID, "frame %d: depth image %dx%d too large", f, d.rows, d.cols);
+        if (d.stride_bytes < (size_t)d.cols * es)
+            return fail(h, PBD_ERR_INVALID, "frame %d: stride %zu < row bytes %zu", f, d.stride_bytes, (size_t)d.cols * es);
+        if (!host && (reinterpret_cast<uintptr_t>(d.data) % es || d.stride_bytes % es))
+            return fail(h, PBD_ERR_INVALID, "frame %d: device pointer %p / stride %zu not a multiple of the %zu-byte element", f, d.data,
+                        d.stride_bytes, es);
+    }
+    return PBD_OK;
+}
+
+// the host form's records: frame index, component and part count of each
+int check_dc_records(pbd_handle *h, int nframes, const int32_t *cand, int ncand, int frame_offset)
+{
+    const int stride = ::stride(h);
+    for (int i = 0; i < ncand; ++i) {
+        const int32_t *r = cand + (size_t)i * stride;
+        const long long f = (long long)r[0] - frame_offset;
+        if (f < 0 || f >= nframes)
+            return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
+        if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
+        const int np = h->part_offset[r[1] + 1] - h->part_offset[r[1]];
+        if (r[6] != np || r[6] < 1 || r[6] > h->max_parts)
+            return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (component %d has %d)", i, r[6], r[1], np);
+    }
+    return PBD_OK;
+}
+
+// the frame table and the filter's kernels on the handle's stream: payload d_in (capacity records) -> d_out (out_cap records)
+int enqueue_dc(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, float zfactor, const int32_t *d_in, int capacity,
+               int frame_offset, int32_t *d_out, int out_cap)
+{
+    if (int rc = dc_model_tables(h)) return rc;
+    const int cap = std::max(capacity, 0);
+    const long long tasks = std::max<long long>((long long)cap * h->max_parts, 1);
+    if (tasks >= (1LL << 30)) return fail(h, PBD_ERR_INVALID, "capacity %d: %lld parts (below 2^30)", capacity, tasks);
+    const int blocks = dc_record_blocks(cap);
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t s_med = al(tasks * sizeof(double)), s_queue = al(tasks * sizeof(int)), s_qn = 256,
+                 s_flag = al((size_t)blocks * 256 * sizeof(int)), s_blk = al((size_t)blocks * sizeof(int));
+    HIPCHK(h, h->dc_ws.ensure(s_med + s_queue + s_qn + s_flag + s_blk));
+    if (int rc = stage_table(h, h->dc_tab_host, h->dc_tab, h->dc_tab_copied, tab.data(), tab.size() * sizeof(Box3dFrame))) return rc;
+    uint8_t *w = h->dc_ws.as<uint8_t>();
+    DcParams p{};
+    p.in = d_in; p.in_cap = cap; p.stride = stride(h); p.max_parts = h->max_parts;
+    p.frames = h->dc_tab.as<Box3dFrame>(); p.nframes = (int)tab.size(); p.frame_offset = frame_offset;
+    p.depth = depth_code; p.NC = h->NC;
+    p.part_offset = h->dc_part_offset.p; p.parent = h->dc_parent.p; p.norm = h->dc_norm.p; p.zfactor = zfactor;
+    p.med = reinterpret_cast<double *>(w); w += s_med;
+    p.queue = reinterpret_cast<int *>(w); w += s_queue;
+    p.qn = reinterpret_cast<int *>(w); w += s_qn;
+    p.flag = reinterpret_cast<int *>(w); w += s_flag;
+    p.blk = reinterpret_cast<int *>(w);
+    p.task_cap = tasks;
+    p.out = d_out; p.out_cap = std::max(out_cap, 0);
+    HIPCHK(h, hipMemsetAsync(p.qn, 0, 8 * sizeof(int), h->stream));
+    static const int ids[kDcSteps] = {PBD_K_DC_CLASSIFY, PBD_K_DC_SELECT, PBD_K_DC_COMPACT};
+    for (int step = 0; step < kDcSteps; ++step) {
+        ProfScope ps(h, ids[step], h->stream);
+        launch_depth_consistency(p, h->f64, step, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// ---- suppression of a caller's list (pbd_suppress*): the canvas tables of its frame sizes, kept for the next call of the
+// same sizes
+int get_suppress_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    std::vector<int> key;
+    for (int f = 0; f < nframes; ++f) {
+        if (rows[f] < 1 || cols[f] < 1 || rows[f] > 65536 || cols[f] > 65536)
+            return fail(h, PBD_ERR_INVALID, "frame %d: size %dx%d (1..65536)", f, rows[f], cols[f]);
+        key.push_back(rows[f]); key.push_back(cols[f]);
+    }
+    if (h->sup_plan && h->sup_plan->key_dims == key) { *out = h->sup_plan.get(); return PBD_OK; }
+    if (h->sup_plan) HIPCHK(h, hipStreamSynchronize(h->stream));   // the previous tables may still be read
+    auto M = std::make_unique<Plan>();
+    M->kind = 4; M->key_dims = key; M->mixed_frames = nframes;
+    for (int f = 0; f < nframes; ++f) M->fdim.push_back(make_int2(rows[f], cols[f]));
+    post_canvas_plan(*M);
+    h->sup_plan.reset();
+    HIPCHK(h, M->d_fdim.upload(M->fdim));
+    HIPCHK(h, M->d_fcanvas.upload(M->fcanvas));
+    HIPCHK(h, M->d_post_lds.upload(M->post_lds));
+    HIPCHK(h, M->d_post_glb.upload(M->post_glb));
+    h->sup_plan = std::move(M);
+    *out = h->sup_plan.get();
+    return PBD_OK;
+}
+
+// the host forms: records into a payload of the handle's (word 0 = ncand), then, after `run` enqueued the stage into `dout`,
+// the kept count and min(kept, capacity) records back into out
+template <class Run>
+int host_list_call(pbd_handle *h, DevBuf &din, DevBuf &dout, const int32_t *cand, int ncand, int32_t *out, int capacity, int *nout,
+                   Run run)
+{
+    const size_t stride = (size_t)::stride(h);
+    HIPCHK(h, din.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+    HIPCHK(h, dout.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+    HIPCHK(h, hipMemcpyAsync(din.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (ncand) HIPCHK(h, hipMemcpyAsync(din.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
+                                        h->stream));
+    if (int rc = run(din.as<int32_t>(), dout.as<int32_t>())) return rc;
+    int kept = 0;
+    HIPCHK(h, hipMemcpyAsync(&kept, dout.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    const int nret = std::min(std::max(kept, 0), capacity);
+    if (nret > 0)
+        HIPCHK(h, hipMemcpy(out, dout.as<int32_t>() + 1, (size_t)nret * stride * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *nout = kept;
+    if (kept > capacity) return fail(h, PBD_ERR_CAPACITY, "%d records kept, capacity %d", kept, capacity);
     return PBD_OK;
 }
 
@@ -2957,6 +3130,83 @@ int pbd_boxes3d_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int
     });
 }
 
+// SearchSpacePruning<T>::filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-95).  See include/pbd.h.
+int pbd_depth_consistency(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, float zfactor, const int32_t *cand, int ncand,
+                          int frame_offset, int32_t *out, int capacity, int *nout)
+{
+    return entry(h, depth && nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
+        if (int rc = check_dc_frames(h, nframes, depth, depth_code, zfactor, true)) return rc;
+        if (int rc = check_dc_records(h, nframes, cand, ncand, frame_offset)) return rc;
+        if (ncand == 0) return PBD_OK;
+        // the depth images packed with dense rows (the pbd_boxes3d host form's buffers)
+        const std::vector<int> ones(nframes, 1);
+        std::vector<Box3dFrame> tab;
+        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, ones.data(), ones.data(), cand, 0, tab)) return rc;
+        return host_list_call(h, h->dc_rec, h->dc_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_dc(h, tab, depth_code, zfactor, din, ncand, frame_offset, dout, ncand);
+        });
+    });
+}
+
+int pbd_depth_consistency_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, float zfactor,
+                                 const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity)
+{
+    return entry(h, d_depth && d_payload && d_out, kIdle, [&]() -> int {
+        if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
+        if (int rc = check_dc_frames(h, nframes, d_depth, depth_code, zfactor, false)) return rc;
+        std::vector<Box3dFrame> tab(nframes);
+        for (int f = 0; f < nframes; ++f)
+            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
+                                (long long)d_depth[f].stride_bytes, 0, 0};
+        return enqueue_dc(h, tab, depth_code, zfactor, d_payload, capacity, frame_offset, d_out, out_capacity);
+    });
+}
+
+// Candidate::sort + Candidate::nonMaximaSuppression of a caller's list (the pbd_set_nms stage).  See include/pbd.h.
+int pbd_suppress(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap, const int32_t *cand, int ncand,
+                 int frame_offset, int32_t *out, int capacity, int *nout)
+{
+    return entry(h, im_rows && im_cols && nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        Plan *P = nullptr;
+        if (int rc = get_suppress_plan(h, nframes, im_rows, im_cols, &P)) return rc;
+        const int stride = ::stride(h);
+        for (int i = 0; i < ncand; ++i) {
+            const int32_t *r = cand + (size_t)i * stride;
+            const long long f = (long long)r[0] - frame_offset;
+            const long long g = i > 0 ? (long long)cand[(size_t)(i - 1) * stride] - frame_offset : 0;
+            if (f < 0 || f >= nframes || f < g)
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d or below the previous record's", i,
+                            r[0], frame_offset, nframes - 1);
+            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
+        }
+        if (ncand == 0) return PBD_OK;
+        return host_list_call(h, h->sup_in, h->sup_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_post(h, nframes, 0, 0, overlap, din, ncand, 0, dout, ncand, h->stream, P, frame_offset);
+        });
+    });
+}
+
+int pbd_suppress_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap, const int32_t *d_payload,
+                        int capacity, int frame_offset, int32_t *d_out, int out_capacity)
+{
+    return entry(h, im_rows && im_cols && d_payload && d_out, kIdle, [&]() -> int {
+        if (capacity < 1 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d (>= 1), out_capacity %d", capacity, out_capacity);
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        Plan *P = nullptr;
+        if (int rc = get_suppress_plan(h, nframes, im_rows, im_cols, &P)) return rc;
+        HIPCHK(h, h->sup_bad.ensure(sizeof(int)));
+        if (int rc = enqueue_post(h, nframes, 0, 0, overlap, d_payload, capacity, 0, d_out, out_capacity, h->stream, P, frame_offset,
+                                  h->sup_bad.as<int>())) return rc;
+        HIPCHK(h, hipGetLastError());
+        return PBD_OK;
+    });
+}
+
 // PointCloudClusterer::computeBoundingBoxes after boundingBox3D (include/PointCloudClusterer.hpp:53-153).  See include/pbd.h.
 int pbd_boxes3d_camera(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
                        const pbd_pinhole *cams, int parts_mode, const int32_t *cand, int ncand, int frame_offset, double *box,
@@ -3283,7 +3533,7 @@ const char *pbd_kernel_name(int k)
                                              "k_dt_cols", "k_dp_combine", "k_dp_root", "k_argmin", "k_camera_boxes",
                                              "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear", "k_cl_grid_count",
                                              "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select",
-                                             "k_cl_out"};
+                                             "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

@@ -288,6 +288,10 @@ struct PostParams {
     const int2 *fdim;
     const long long *fcanvas;
     const int *flist;
+    // pbd_suppress*: a record's frame is its `frame` field - in_offset; `bad` (NULL: not checked) is set on the device when word 0
+    // is negative or a frame index is out of range or not grouped ascending -- then, as on an overflow, word 0 = -1
+    int in_offset;
+    int *bad;
 };
 
 // 3-D box of each record from a depth image (pbd_boxes3d; pbd_kernels_depth.hip)
@@ -397,6 +401,43 @@ struct PlaneParams {
     long long *status;            // [2]: kept points of all clouds, most planes of one cloud
 };
 
+// cv::Rect operator& in 64 bits (an empty intersection is Rect()); pbd_kernels_depth.hip, pbd_kernels_consistency.hip
+__device__ inline void rect_and64(long long &x, long long &y, long long &w, long long &h, long long bx, long long by, long long bw,
+                                  long long bh)
+{
+    const long long x1 = x > bx ? x : bx, y1 = y > by ? y : by;
+    w = (x + w < bx + bw ? x + w : bx + bw) - x1;
+    h = (y + h < by + bh ? y + h : by + bh) - y1;
+    x = x1; y = y1;
+    if (w <= 0 || h <= 0) x = y = w = h = 0;
+}
+
+// depth consistency of each record's parts (pbd_depth_consistency*; pbd_kernels_consistency.hip)
+constexpr int kDcWaveKeys = 1024;     // samples of a median one wave holds in registers
+constexpr int kDcBlockKeys = 4096;    // samples of a median one 256-thread workgroup holds in registers; larger boxes stream
+constexpr int kDcMaxGrid = 4096;
+struct DcParams {
+    const int32_t *in;            // payload: word 0 = records (negative or > in_cap: output word 0 = -1), then the records
+    int in_cap;
+    int stride, max_parts;
+    const Box3dFrame *frames;     // [nframes] depth images (im_rows / im_cols unused); a record's frame is `frame` - frame_offset
+    int nframes, frame_offset;
+    int depth;                    // kDepth8U / 16U / 32F / 64F, one per call
+    int NC;
+    const int *part_offset;       // [NC + 1]
+    const int *parent;            // [totparts] component-local parent (root -1)
+    const double *norm;           // [totparts] norm of the part's mixture-0 anchor (root 0)
+    float zfactor;
+    // workspace: a median per (record, part) (NaN: empty box), one work list of task_cap entries in three class segments
+    // (qn[0..2] their lengths, qn[3..5] the placing cursors), a kept flag per record, a kept count per 256 records
+    double *med;
+    int *queue, *qn;
+    long long task_cap;
+    int *flag, *blk;
+    int32_t *out; int out_cap;    // output payload: word 0 = kept count, then min(kept, out_cap) records
+};
+enum { kDcStepClassify = 0, kDcStepSelect, kDcStepCompact, kDcSteps };
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -470,6 +511,9 @@ void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nl
                               int nglb, hipStream_t s);
 // `grid` workgroups (capped at kB3MaxGrid), each computing one record at a time
 void launch_boxes3d(const Boxes3dParams &p, int grid, hipStream_t s);
+// one step of the depth-consistency filter (kDcStep*, in this order); dc_record_blocks: workgroups of the compaction (p.blk entries)
+void launch_depth_consistency(const DcParams &p, bool f64, int step, hipStream_t s);
+int dc_record_blocks(int in_cap);
 // camera boxes and part centres of p.in's records (after launch_boxes3d wrote p.cube)
 void launch_camera_boxes(const CameraParams &p, hipStream_t s);
 // one step of the clustering (kClStep*, launched in this order); nothing is read back

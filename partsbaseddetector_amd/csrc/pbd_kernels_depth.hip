@@ -45,16 +45,6 @@ template <int D> __device__ inline float b3_load(const uint8_t *row, int x)
     return (float)reinterpret_cast<const double *>(row)[x];
 }
 
-// cv::Rect operator& in 64-bit (an empty intersection is Rect())
-__device__ inline void b3_and(long long &x, long long &y, long long &w, long long &h, long long bx, long long by, long long bw, long long bh)
-{
-    const long long x1 = max(x, bx), y1 = max(y, by);
-    w = min(x + w, bx + bw) - x1;
-    h = min(y + h, by + bh) - y1;
-    x = x1; y = y1;
-    if (w <= 0 || h <= 0) x = y = w = h = 0;
-}
-
 struct B3Shared {
     union {
         uint32_t hist[kB3MaxRanks * kB3Bins];    // select: per needed rank, 16 counters of the next digit (row = first rank of its prefix)
@@ -203,12 +193,12 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
                     x = (int)__dsub_rn(mean[0], __dmul_rn(1.5, sd[0])); y = (int)__dsub_rn(mean[1], __dmul_rn(1.5, sd[1]));
                     w = (int)__dmul_rn(3., sd[0]); h = (int)__dmul_rn(3., sd[1]);
                 }
-                b3_and(x, y, w, h, 0, 0, cols, rows);
+                rect_and64(x, y, w, h, 0, 0, cols, rows);
                 // scaled to the depth image, each member truncated; the reference's depth(r) asserts inside the image, which
                 // the intersection below makes explicit (it changes nothing the reference computes)
                 long long dx = (int)__dmul_rn((double)x, sx), dyy = (int)__dmul_rn((double)y, sy);
                 long long dw = (int)__dmul_rn((double)w, sx), dh = (int)__dmul_rn((double)h, sy);
-                b3_and(dx, dyy, dw, dh, 0, 0, fr.cols, fr.rows);
+                rect_and64(dx, dyy, dw, dh, 0, 0, fr.cols, fr.rows);
                 if (dw <= 0 || dh <= 0) continue;   // part.empty(): skipped
                 S.box[nb++] = make_int4((int)dx, (int)dyy, (int)dw, (int)dh);
             }

@@ -23,7 +23,7 @@ constexpr int kPostThreads = 256;
 template <bool kLds> constexpr int post_nms_threads() { return kLds ? 256 : 1024; }
 constexpr size_t kPostLdsCanvasMax = 128 * 1024;   // bytes of bit canvas held in LDS (160 KiB per CU on gfx950)
 
-__device__ inline bool post_overflow(const PostParams &p) { return p.in[0] > p.in_cap; }
+__device__ inline bool post_overflow(const PostParams &p) { return p.in[0] > p.in_cap || (p.bad && *p.bad); }
 __device__ inline int post_count(const PostParams &p) { return max(min(p.in[0], p.in_cap), 0); }
 
 // first index in [0, n) whose frame is >= f (the list is grouped by ascending frame)
@@ -47,13 +47,25 @@ __device__ inline bool post_ahead(float a, int ia, float b, int ib)
     return ia < ib;
 }
 
+// pbd_suppress*: a caller's list is checked first (word 0 >= 0, every frame index in range, grouped ascending)
+__global__ __launch_bounds__(kPostThreads) void k_post_check(PostParams p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && p.in[0] < 0) *p.bad = 1;
+    if (i >= post_count(p) || p.in[0] > p.in_cap) return;
+    const long long f = (long long)p.in[1 + (size_t)i * p.stride] - p.in_offset;
+    const long long g = i > 0 ? (long long)p.in[1 + (size_t)(i - 1) * p.stride] - p.in_offset : 0;
+    if (f < 0 || f >= p.nframes || f < g) *p.bad = 1;
+}
+
 __global__ __launch_bounds__(kPostThreads) void k_post_prep(PostParams p)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (post_overflow(p) || i >= post_count(p)) return;
     const int32_t *r = p.in + 1 + (size_t)i * p.stride;
     p.key[i] = __int_as_float(r[5]);
-    p.frame[i] = r[0];
+    const int f = r[0] - p.in_offset;
+    p.frame[i] = f;
     const int np = min(max(r[6], 0), p.max_parts);
     // Candidate::boundingBox: fold of cv::Rect operator| over the parts (an empty left side takes the right side, an empty
     // right side is skipped); 64-bit so that x + w cannot wrap
@@ -70,7 +82,7 @@ __global__ __launch_bounds__(kPostThreads) void k_post_prep(PostParams p)
         }
     }
     // box & Rect(0, 0, cols, rows); an empty intersection is (0, 0, 0, 0)
-    const int2 fs = p.fdim ? p.fdim[r[0]] : make_int2(p.rows, p.cols);   // the frame's own size (mixed-size calls)
+    const int2 fs = p.fdim ? p.fdim[f] : make_int2(p.rows, p.cols);   // the frame's own size (mixed-size calls)
     long long x1 = max(x, 0LL), y1 = max(y, 0LL), x2 = min(x + w, (long long)fs.y), y2 = min(y + h, (long long)fs.x);
     if (x2 - x1 <= 0 || y2 - y1 <= 0) x1 = y1 = x2 = y2 = 0;
     p.box[i] = make_int4((int)x1, (int)y1, (int)x2, (int)y2);
@@ -225,6 +237,7 @@ void launch_postprocess_mixed(const PostParams &p, const int *lds_frames, int nl
                               int nglb, hipStream_t s)
 {
     const int rblocks = std::max((p.in_cap + kPostThreads - 1) / kPostThreads, 1);
+    if (p.bad) PBD_LAUNCH(k_post_check, dim3(rblocks), dim3(kPostThreads), 0, s, p);
     PBD_LAUNCH(k_post_prep, dim3(rblocks), dim3(kPostThreads), 0, s, p);
     PBD_LAUNCH(k_post_rank, dim3(rblocks), dim3(kPostThreads), 0, s, p);
     // each frame is suppressed on a canvas of its own kind: one launch over the frames whose canvas fits in LDS, one over the rest

@@ -203,6 +203,7 @@ class Handle:
         self.max_candidates = max_candidates
         self.stride = self.lib.pbd_candidate_stride(self.h)
         self.max_parts = (self.stride - 8) // 4         # part boxes a record holds (pbd_candidate_stride)
+        self.nms_overlap = None                          # the overlap of set_nms (None: off)
 
     def close(self):
         if getattr(self, "h", None):
@@ -236,6 +237,7 @@ class Handle:
             self.check(self.lib.pbd_set_nms(self.h, 0, 0.0))
         else:
             self.check(self.lib.pbd_set_nms(self.h, 1, float(overlap)))
+        self.nms_overlap = overlap
 
     def set_debug_option(self, option: int, value: int) -> None:
         """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
@@ -302,6 +304,56 @@ class Handle:
         ic = np.array([int(s[1]) for s in im_shapes], np.int32)
         self.check(self.lib.pbd_boxes3d_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
                                                _lib.ptr(ic, C.c_int), d_payload_ptr, capacity, frame_offset, d_out_ptr))
+
+    def _records(self, records) -> np.ndarray:
+        return np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
+
+    def depth_consistency(self, depths: Sequence[np.ndarray], records: np.ndarray, zfactor: float = 0.03, frame_offset: int = 0,
+                          capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_depth_consistency: the records (n, stride) that SearchSpacePruning::filterCandidatesByDepth keeps, in input order,
+        computed on the device.  depths[f]: the 2-D depth image of frame index f (one dtype per call, rows of any pitch)."""
+        dt = np.dtype(depths[0].dtype)
+        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
+            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
+        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
+        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(self.lib.pbd_depth_consistency(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], float(zfactor),
+                                                  rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap,
+                                                  C.byref(n)))
+        return out[:n.value].copy()
+
+    def depth_consistency_device(self, descs, depth_code: int, zfactor: float, d_payload_ptr: int, capacity: int, frame_offset: int,
+                                 d_out_ptr: int, out_capacity: int) -> None:
+        """pbd_depth_consistency_device: the records of a device payload, depth frames (device pointer, rows, cols, pitch), the kept
+        records into the payload at d_out_ptr (word 0 = kept count, -1 for an overflowed input); asynchronous"""
+        self.check(self.lib.pbd_depth_consistency_device(self.h, len(descs), _lib.frame_array(descs), depth_code, float(zfactor),
+                                                         d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
+
+    def suppress(self, im_shapes, overlap: float, records: np.ndarray, frame_offset: int = 0,
+                 capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_suppress: per frame Candidate.sort + Candidate.nonMaximaSuppression((rows, cols), ., overlap) of records grouped by
+        ascending frame (the pbd_set_nms stage on a caller's list); im_shapes[f] = (rows, cols) of frame index f"""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(self.lib.pbd_suppress(self.h, len(ir), _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), float(overlap),
+                                         rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def suppress_device(self, im_shapes, overlap: float, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
+                        out_capacity: int) -> None:
+        """pbd_suppress_device: suppress_device's payload in, the kept records into the payload at d_out_ptr; asynchronous"""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        self.check(self.lib.pbd_suppress_device(self.h, len(ir), _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), float(overlap),
+                                                d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
 
     def boxes3d_camera(self, depths: Sequence[np.ndarray], im_shapes, cameras, records: np.ndarray, parts_mode: int = 0,
                        frame_offset: int = 0):
@@ -579,6 +631,7 @@ class PartsBasedDetector:
         self._kw = dict(device=device, conv_mode=conv_mode, max_batch=max_batch, max_candidates=max_candidates,
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
         self._nms = nms
+        self._zfactor: Optional[float] = None      # setDepthConsistency: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
         self.hd: Optional[Handle] = None
         self._name = ""
@@ -597,6 +650,7 @@ class PartsBasedDetector:
         if self.hd is not None:
             self.hd.close()
         self.hd = Handle(model, **self._kw)
+        self._dc_pays = None
         if self._nms is not None:
             self.hd.set_nms(self._nms)
         self._name = getattr(model, "name", "")
@@ -608,8 +662,95 @@ class PartsBasedDetector:
         if self.hd is None:
             raise PbdError(-5, "detect() before distributeModel()")
 
+    def setDepthConsistency(self, zfactor: Optional[float] = 0.03) -> None:
+        """detect(im, depth) then runs filterCandidatesByDepth(., depth, zfactor) before the suppression, as the reference's
+        commented-out call would (src/PartsBasedDetector.cpp:91-93); None: off (the default, depth ignored)"""
+        if zfactor is not None and math.isnan(zfactor):
+            raise PbdError(-1, "zfactor is NaN")
+        self._zfactor = None if zfactor is None else float(zfactor)
+
+    def filterCandidatesByDepth(self, candidates: Sequence[Candidate], depths, zfactor: float = 0.03) -> List[Candidate]:
+        """SearchSpacePruning::filterCandidatesByDepth on the device (pbd_depth_consistency): the candidates whose parts agree in
+        depth with their parents, in order.  depths: the depth image of every frame index the candidates carry (one image for one
+        frame).  Equal to consistency.filter_records."""
+        self._need()
+        if isinstance(depths, np.ndarray):
+            depths = [depths]
+        cands = list(candidates)
+        if not cands:
+            return []
+        rec = self.hd.pack_candidates(cands)
+        kept = self.hd.depth_consistency(list(depths), rec, zfactor)
+        keep, k = [], 0
+        for i, c in enumerate(cands):          # the kept records are the input's, in order
+            if k < len(kept) and np.array_equal(kept[k], rec[i]):
+                keep.append(c)
+                k += 1
+        return keep
+
+    def suppress(self, candidates: Sequence[Candidate], im_shapes, overlap: float) -> List[Candidate]:
+        """Candidate.sort + Candidate.nonMaximaSuppression per frame, on the device (pbd_suppress): candidates grouped by
+        ascending frame; im_shapes[f] = (rows, cols) of frame index f (one shape for one frame)"""
+        self._need()
+        if len(im_shapes) and np.isscalar(im_shapes[0]):
+            im_shapes = [im_shapes]
+        cands = list(candidates)
+        if not cands:
+            return []
+        kept = self.hd.suppress(list(im_shapes), overlap, self.hd.pack_candidates(cands))
+        return self.hd.unpack_candidates(kept.ravel(), len(kept))
+
+    def _detect_depth(self, im: np.ndarray, depth: np.ndarray, capacity: Optional[int]) -> List[Candidate]:
+        """detect(im, depth) with setDepthConsistency on: the unsuppressed list, the filter, then the handle's suppression (if
+        any), each on the device, the lists passed in device payloads"""
+        import torch
+        rows, cols, cn = im.shape
+        dev = torch.device("cuda", self._kw["device"])
+        d_im = torch.from_numpy(np.ascontiguousarray(im)).to(dev)
+        dd = np.ascontiguousarray(depth)
+        if dd.dtype not in _lib.DEPTH_CODE or dd.ndim != 2:
+            raise PbdError(-1, "the depth image is a 2-D uint8, uint16, float32 or float64 array")
+        d_depth = torch.from_numpy(dd).to(dev)
+        torch.cuda.synchronize(dev)
+        cap = capacity or self.hd.max_candidates
+        words = 1 + self.hd.max_candidates * self.hd.stride
+        pays = getattr(self, "_dc_pays", None)     # the three payloads live with the detector, allocated once per handle
+        if pays is None or pays[0].numel() != words or pays[0].device != dev:
+            pays = self._dc_pays = [torch.empty(words, dtype=torch.int32, device=dev) for _ in range(3)]
+        overlap = self.hd.nms_overlap
+        if overlap is not None:
+            self.hd.set_nms(None)
+        try:
+            self.hd.check(self.hd.lib.pbd_detect_frames_device_out(
+                self.hd.h, 1, _lib.frame_array([(d_im.data_ptr(), rows, cols, cols * cn * im.dtype.itemsize)]), cn,
+                _lib.DEPTH_CODE[im.dtype], 0, pays[0].data_ptr(), self.hd.max_candidates))
+        finally:
+            if overlap is not None:
+                self.hd.set_nms(overlap)
+        self.hd.depth_consistency_device([(d_depth.data_ptr(), dd.shape[0], dd.shape[1], dd.strides[0])], _lib.DEPTH_CODE[dd.dtype],
+                                         self._zfactor, pays[0].data_ptr(), self.hd.max_candidates, 0, pays[1].data_ptr(),
+                                         self.hd.max_candidates)
+        out = pays[1]
+        if overlap is not None:
+            self.hd.suppress_device([(rows, cols)], overlap, pays[1].data_ptr(), self.hd.max_candidates, 0, pays[2].data_ptr(),
+                                    self.hd.max_candidates)
+            out = pays[2]
+        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
+        found = int(out[0].item())
+        if found < 0:
+            raise PbdError(-4, f"more than max_candidates ({self.hd.max_candidates}) candidates were found before the filter")
+        n = min(found, cap)
+        buf = out[1:1 + n * self.hd.stride].cpu().numpy()
+        self.features_._scales = self.hd.plan(rows, cols)["scales"]
+        if found > cap:
+            raise PbdError(-4, f"{found} candidates kept, capacity {cap}")
+        return self.hd.unpack_candidates(buf, n)
+
     def detect(self, im: np.ndarray, depth: Optional[np.ndarray] = None, capacity: Optional[int] = None) -> List[Candidate]:
-        """detect(im[, depth], candidates); `depth` is ignored exactly as in the reference (:91-93)."""
+        """detect(im[, depth], candidates).  `depth` is ignored as in the reference (:91-93) unless setDepthConsistency(zfactor)
+        is on: then the unsuppressed candidates go through filterCandidatesByDepth(depth, zfactor) and then the suppression of
+        the detector's `nms` overlap (if any), in the reference's order, on the device.  depth=None skips the filter
+        (the reference's `if (!depth.empty())`)."""
         self._need()
         if im.dtype not in _lib.DEPTH_CODE:
             raise PbdError(-2, f"image dtype {im.dtype}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
@@ -619,6 +760,8 @@ class PartsBasedDetector:
         if not (im.strides[2] == es and im.strides[1] == im.shape[2] * es):
             im = np.ascontiguousarray(im)
         rows, cols, cn = im.shape
+        if self._zfactor is not None and depth is not None:
+            return self._detect_depth(im, depth, capacity)
         cap = capacity or self.hd.max_candidates
         buf = np.zeros(cap * self.hd.stride, np.int32)
         n = C.c_int()
