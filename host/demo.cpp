@@ -5,7 +5,7 @@
 //
 //   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
-//            [--remove-planes] [--depth-consistency ZFACTOR]]
+//            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
@@ -21,6 +21,10 @@
 //           "plane K a b c d INLIERS" per plane, "kept N" (the reduced cloud's points), then the lines above on the reduced cloud
 //   --depth-consistency ZFACTOR: with --depth, one line "depth_consistency zfactor Z: kept K dropped D" (filterCandidatesByDepth
 //           on the unsuppressed list, on the device), then the candidates of detect(im, depth) with setDepthConsistency on
+//   --mask: Candidate::mask of the listed candidates (after --top), on the device, written as a binary PGM; one line "mask K"
+//           (the labelled pixels); --masked: the image & (mask != 0) (the ROS node's mask topic), a binary PPM (PGM for grey)
+//   --poses: with --camera, one line per listed candidate after its "object" line: "pose COUNT x y z qx qy qz qw" (messagePoses
+//           on the part centres, on the device; COUNT 0 is the node's "Centroid not found")
 //   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
 #include <chrono>
 #include <cstdlib>
@@ -67,7 +71,7 @@ static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, flo
 // d is 0 or not finite); camera boxes, part centres and one kept cluster per listed candidate
 template <typename T>
 static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Image &depth, const pbd_pinhole &cam,
-                         const std::vector<Candidate> &listed, bool remove_planes)
+                         const std::vector<Candidate> &listed, bool remove_planes, bool poses)
 {
     std::vector<float> df((size_t)depth.rows * depth.cols), cloud(df.size() * 3);
     for (int r = 0; r < depth.rows; ++r)
@@ -89,7 +93,11 @@ static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Imag
     dimg.step = (size_t)depth.cols * sizeof(float); dimg.depth = 5;
     std::vector<Rect3d> boxes;
     std::vector<std::vector<Point3f> > centres;
-    pbd.computeBoundingBoxes(im, dimg, cam, listed, boxes, centres);
+    std::vector<bool> dense;
+    pbd.computeBoundingBoxes(im, dimg, cam, listed, boxes, centres, &dense);
+    std::vector<int32_t> pcount;
+    std::vector<float> ppos, pquat, pev;
+    if (poses) pbd.partPoses(centres, dense, pcount, ppos, pquat, pev);
     pbd_cloud pc;
     pc.data = cloud.data(); pc.rows = depth.rows; pc.cols = depth.cols; pc.point_stride = 12; pc.row_stride = (size_t)depth.cols * 12;
     std::vector<std::vector<int> > clusters;
@@ -111,12 +119,29 @@ static void camera_lines(PartsBasedDetector<T> &pbd, const Image &im, const Imag
         std::printf("centres %zu", centres[i].size());
         for (size_t j = 0; j < centres[i].size(); ++j) std::printf(" %.9g %.9g %.9g", centres[i][j].x, centres[i][j].y, centres[i][j].z);
         std::printf("\nobject %zu %.9g %.9g %.9g\n", clusters[i].size(), objects[i].x, objects[i].y, objects[i].z);
+        if (poses)
+            std::printf("pose %d %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", pcount[i], ppos[3 * i], ppos[3 * i + 1], ppos[3 * i + 2], pquat[4 * i],
+                        pquat[4 * i + 1], pquat[4 * i + 2], pquat[4 * i + 3]);
     }
+}
+
+// a binary PGM (channels 1) or PPM (channels 3: BGR pixels, written as the RGB a PPM stores) of rows x cols interleaved bytes
+static bool writePNM(const char *path, const uint8_t *data, int rows, int cols, int channels)
+{
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return false;
+    std::fprintf(f, "P%d\n%d %d\n255\n", channels == 3 ? 6 : 5, cols, rows);
+    std::vector<uint8_t> out(data, data + (size_t)rows * cols * channels);
+    if (channels == 3)
+        for (size_t i = 0; i < out.size(); i += 3) std::swap(out[i], out[i + 2]);
+    const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    return std::fclose(f) == 0 && ok;
 }
 
 template <typename T>
 static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
-               int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes, float dcz)
+               int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes, float dcz, const char *mask_path,
+               const char *masked_path, bool poses)
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -191,7 +216,21 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
         for (size_t i = 0; i < boxes.size(); ++i)
             std::printf("box3d %.17g %.17g %.17g %.17g %.17g %.17g\n", boxes[i].x, boxes[i].y, boxes[i].z, boxes[i].height, boxes[i].width,
                         boxes[i].depth);
-        if (camera) camera_lines(pbd, im, *depth, *camera, listed, remove_planes);
+        if (camera) camera_lines(pbd, im, *depth, *camera, listed, remove_planes, poses);
+    }
+    if (mask_path) {                     // Candidate::mask and the masked image of the listed candidates
+        if (!pbd.handle()) pbd.distributeModel(model);
+        const std::vector<Candidate> listed(candidates.begin(), candidates.begin() + std::min<size_t>(candidates.size(), (size_t)top));
+        std::vector<uint8_t> labels, masked;
+        pbd.mask(im, listed, labels, masked_path ? &masked : NULL);
+        size_t on = 0;
+        for (size_t i = 0; i < labels.size(); ++i) on += labels[i] != 0;
+        std::printf("mask %zu\n", on);
+        if (!writePNM(mask_path, labels.data(), im.rows, im.cols, 1) ||
+            (masked_path && !writePNM(masked_path, masked.data(), im.rows, im.cols, im.channels))) {
+            std::fprintf(stderr, "cannot write the mask\n");
+            return -1;
+        }
     }
     return 0;
 }
@@ -232,7 +271,7 @@ static int dump_model(const FileStorageModel &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -241,12 +280,16 @@ int main(int argc, char **argv)
     std::vector<const char *> also;
     const char *depth_path = NULL;
     float dcz = -1.f;
-    bool have_camera = false, remove_planes = false;
+    const char *mask_path = NULL, *masked_path = NULL;
+    bool have_camera = false, remove_planes = false, poses = false;
     pbd_pinhole camera = {0, 0, 0, 0, 0, 0};
     for (int i = 3; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--double")) dbl = true;
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
         else if (!std::strcmp(argv[i], "--remove-planes")) remove_planes = true;
+        else if (!std::strcmp(argv[i], "--poses")) poses = true;
+        else if (!std::strcmp(argv[i], "--mask") && i + 1 < argc) mask_path = argv[++i];
+        else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked_path = argv[++i];
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--device-nms") && i + 1 < argc) dnms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
@@ -266,6 +309,18 @@ int main(int argc, char **argv)
     }
     if (remove_planes && !have_camera) {
         std::fprintf(stderr, "--remove-planes needs --depth and --camera\n");
+        return -1;
+    }
+    if (poses && !have_camera) {
+        std::fprintf(stderr, "--poses needs --depth and --camera\n");
+        return -1;
+    }
+    if (masked_path && !mask_path) {
+        std::fprintf(stderr, "--masked needs --mask\n");
+        return -1;
+    }
+    if (mask_path && !also.empty()) {
+        std::fprintf(stderr, "--mask takes the one image of a single run: not with --also\n");
         return -1;
     }
     if (dcz >= 0 && (!depth_path || staged || stream_k > 0)) {
@@ -304,8 +359,10 @@ int main(int argc, char **argv)
         }
         const Image *dp = depth_path ? &depth : NULL;
         const pbd_pinhole *cp = have_camera ? &camera : NULL;
-        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz)
-                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz);
+        return dbl ? run<double>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz, mask_path,
+                                 masked_path, poses)
+                   : run<float>(model, im, staged, nms, dnms, top, stream_k, stream_n, conv_mode, dp, cp, remove_planes, dcz, mask_path,
+                                masked_path, poses);
     } catch (const Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code, e.what());
         return -2;

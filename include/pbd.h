@@ -415,6 +415,73 @@ int pbd_suppress(pbd_handle *h, int nframes, const int *im_rows, const int *im_c
 int pbd_suppress_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap,
                         const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
 
+/* Candidate mask (new surface; opt-in): Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) and the ROS node's
+ * masked colour frame `rgb & (mask != 0)` (ros/Messages.cpp:157-174, topic <name>/mask), for records of this handle spanning
+ * several frames.  A record's frame index is `frame` - frame_offset (as pbd_boxes3d); frame f is im_rows[f] x im_cols[f]
+ * (1..65536 each).  Records must be grouped by ascending frame (what pbd_suppress* produces); n is a record's 0-based position
+ * among its frame's records in list order.
+ *   box      boundingBox(): the hull of the record's nparts part rectangles under cv::Rect operator| (an empty accumulator takes
+ *            the next rectangle as it is; an empty rectangle adds nothing), & Rect(0, 0, im_cols, im_rows); an empty
+ *            intersection paints nothing
+ *   label    min(1 + n_first, 255), n_first the smallest n whose box covers the pixel (setTo(n+1, mask == 0) with
+ *            saturate_cast<uchar>); 0 where no box covers it.  Records from n = 254 on all paint 255 where nothing earlier did:
+ *            lists of any length (an unsuppressed list) are valid
+ *   masked   for 8-bit frames of `channels` 1, 3 or 4 interleaved bytes (the reference's case is 3, BGR): every byte of a pixel
+ *            & (label != 0 ? 0xFF : 0).  masked[f] == colour[f] with the same pitch (in place) is allowed; otherwise the two
+ *            must not overlap
+ * Outputs, per frame: labels[f], uint8 rows x cols at label_pitch[f] bytes, and masked[f] at masked_pitch[f]; `labels` or
+ * `masked` NULL omits that output (colour / colour_pitch / channels are then not read).  Pitches are at least the row's bytes.
+ * pbd_candidate_mask: host records, frames and outputs, synchronous.  PBD_ERR_INVALID naming the index: a record whose frame
+ * index is out of range or below its predecessor's, or whose nparts is outside 1..max parts; a frame whose size is outside
+ * 1..65536 or whose pitch is below its row bytes; channels other than 1, 3 or 4 (with masked given).
+ * pbd_candidate_mask_device: the records of the payload d_payload (word 0 = count, capacity records: what
+ * pbd_detect_batch_device_out / pbd_suppress_device leave), device frames read in place (a frame may be a region of a larger
+ * device image), device outputs.  Frame sizes and pitches are host arguments, validated as above.  Asynchronous on
+ * pbd_stream(), no host synchronisation; the handle's workspace grows with capacity and nframes.  d_status int32[1]: the
+ * record count, or -1 for a bad list -- a word 0 that is negative (a suppression overflow) or > capacity (a truncated list), a
+ * frame index out of range or not grouped ascending, or (project decision) an nparts outside 1..max parts -- and then no
+ * output is written.  The kernels' work is bounded by the tiles times the records scanned until a tile is covered, never by
+ * pixels x records.
+ * PBD_ERR_STATE while a batch is in flight; the resident detect result is not touched. */
+int pbd_candidate_mask(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *cand, int ncand,
+                       int frame_offset, uint8_t *const *labels, const size_t *label_pitch, int channels, const uint8_t *const *colour,
+                       const size_t *colour_pitch, uint8_t *const *masked, const size_t *masked_pitch);
+int pbd_candidate_mask_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *d_payload,
+                              int capacity, int frame_offset, uint8_t *const *d_labels, const size_t *label_pitch, int channels,
+                              const uint8_t *const *d_colour, const size_t *colour_pitch, uint8_t *const *d_masked,
+                              const size_t *masked_pitch, int32_t *d_status);
+
+/* Part-centre poses (new surface; opt-in): PartsBasedDetectorNode::messagePoses (ros/Messages.cpp:187-234, topic
+ * <name>/object_poses) per record, on what pbd_boxes3d_camera* writes: centres float[3*max_parts*n] (record i, part j at
+ * 3*(i*max_parts + j)), ncentres int32[n], dense int32[n].  PCL is not pinned; this is the library's contract, modelled on the
+ * plain single-pass pcl::computeMeanAndCovarianceMatrix.  Every operation below is rounded on its own, in the order written.
+ *   points   dense != 0: the first ncentres points, all of them (PCL's dense branch: an Inf point makes the result NaN);
+ *            otherwise only those whose x, y and z are finite.  count = the points used
+ *   moments  nine fp32 sums from 0 in point order: {xx, xy, xz, yy, yz, zz, x, y, z} (x*x etc. in fp32), each / (float)count.
+ *            position = (m_x, m_y, m_z); C_ab = m_ab - m_a * m_b in fp32 (C symmetric); then C_ab /= (float)count again: the
+ *            node's second division (covMat /= point_count, :212), kept on purpose
+ *   frame    C widened to double; 8 cyclic Jacobi sweeps exactly as the plane fit of pbd_remove_planes (above); eigenvalues the
+ *            diagonal in ascending order (pcl::eigen33's order), ties in index order.  Project decision (PCL's eigenvector signs
+ *            are not pinned): columns 0 and 1 are the eigenvectors of the two smallest, each negated when its largest-magnitude
+ *            component (the first on ties) is negative; column 2 = column 0 x column 1 in double, so the frame is a rotation
+ *   quat     Eigen's Quaternion(const Matrix3 &) in double on the frame m: trace (m00 + m11) + m22 > 0: t = sqrt(trace + 1),
+ *            w = 0.5 t, t = 0.5 / t, x = (m21 - m12) t, y = (m02 - m20) t, z = (m10 - m01) t; otherwise i = the largest diagonal
+ *            (0, then 1 if m11 > m00, then 2 if m22 > m_ii), j = (i+1)%3, k = (j+1)%3, t = sqrt(((m_ii - m_jj) - m_kk) + 1),
+ *            q_i = 0.5 t, t = 0.5 / t, w = (m_kj - m_jk) t, q_j = (m_ji + m_ij) t, q_k = (m_ki + m_ik) t.  Then each / sqrt(((x*x
+ *            + y*y) + z*z) + w*w) (normalize()), rounded to float
+ * Outputs per record: count int32 (0: "Centroid not found", the node's `continue`), position float[3], orientation float[4]
+ * {x, y, z, w} (Eigen's coefficient order and geometry_msgs/Quaternion's), eigenvalues float[3] ascending.  count 0: position,
+ * orientation and eigenvalues are NaN.  Project decision: an entry of C that is not finite makes the orientation and the
+ * eigenvalues NaN (the position stays the means).
+ * pbd_part_poses: host arrays of n records, synchronous; an ncentres outside 0..max parts is PBD_ERR_INVALID naming the record.
+ * pbd_part_poses_device: device arrays read in place, min(max(word 0, 0), capacity) records of d_payload (the payload the
+ * centres were computed from); an ncentres outside 0..max parts reads no point (count 0).  Asynchronous on pbd_stream().
+ * PBD_ERR_STATE while a batch is in flight; the resident detect result is not touched. */
+int pbd_part_poses(pbd_handle *h, int n, const float *centres, const int32_t *ncentres, const int32_t *dense, int32_t *count,
+                   float *position, float *orientation, float *eigenvalues);
+int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity, const float *d_centres, const int32_t *d_ncentres,
+                          const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -534,6 +601,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST, PBD_K_CL_SELECT, PBD_K_CL_OUT,
        /* pbd_depth_consistency*; k_dc_select times its three size classes, k_dc_compact the decision and the compaction */
        PBD_K_DC_CLASSIFY, PBD_K_DC_SELECT, PBD_K_DC_COMPACT,
+       /* pbd_candidate_mask* (k_mk_hull times k_mk_init and k_mk_hull), pbd_part_poses* */
+       PBD_K_MK_HULL, PBD_K_MK_TILE, PBD_K_PART_POSES,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

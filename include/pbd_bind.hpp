@@ -324,6 +324,46 @@ inline void detect_depth(pbd_handle *h, const typename Tr::Image &im, const type
     unpack_candidates<Tr>(h, buf, n, candidates);
 }
 
+// Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) and the ROS node's `rgb & (mask != 0)` (ros/Messages.cpp:
+// 157-174) on the device (pbd_candidate_mask) for n records of one frame of im's size in `buf`: the uint8 labels at `labels`
+// (label_pitch bytes a row) and, when `masked` is not NULL, im masked there (im's 8-bit channels, masked_pitch bytes a row;
+// masked may be im's own pixels).  Either output may be NULL.
+template <class Tr>
+inline void candidate_mask(pbd_handle *h, const typename Tr::Image &im, const std::vector<int32_t> &buf, int n, uint8_t *labels,
+                           size_t label_pitch, uint8_t *masked, size_t masked_pitch)
+{
+    if (masked && Tr::img_depth(im) != 0) Tr::fail(PBD_ERR_UNSUPPORTED, "pbd: candidate_mask: the masked frame is 8-bit");
+    const int rows = Tr::img_rows(im), cols = Tr::img_cols(im);
+    const uint8_t *colour = static_cast<const uint8_t *>(Tr::img_data(im));
+    const size_t colour_pitch = Tr::img_step(im);
+    check<Tr>(h, pbd_candidate_mask(h, 1, &rows, &cols, n ? &buf[0] : NULL, n, 0, labels ? &labels : NULL, labels ? &label_pitch : NULL,
+                                    Tr::img_channels(im), masked ? &colour : NULL, masked ? &colour_pitch : NULL,
+                                    masked ? &masked : NULL, masked ? &masked_pitch : NULL));
+}
+
+// PartsBasedDetectorNode::messagePoses (ros/Messages.cpp:187-234) on the device (pbd_part_poses) for n records' part centres as
+// pbd_boxes3d_camera writes them (record i, part j at centres[3 * (i * max_parts + j)]): count[n], position[3n],
+// orientation[4n] (x, y, z, w), eigenvalues[3n] (ascending); count 0 is the node's "Centroid not found"
+template <class Tr>
+inline void part_poses(pbd_handle *h, int n, const std::vector<float> &centres, const std::vector<int32_t> &ncentres,
+                       const std::vector<int32_t> &dense, std::vector<int32_t> &count, std::vector<float> &position,
+                       std::vector<float> &orientation, std::vector<float> &eigenvalues)
+{
+    const size_t mp = (size_t)(pbd_candidate_stride(h) - 8) / 4, un = n > 0 ? (size_t)n : 0;
+    if (n < 0 || centres.size() < un * mp * 3 || ncentres.size() < un || dense.size() < un)
+        Tr::fail(PBD_ERR_INVALID, "pbd: part_poses: n records need 3 * max_parts centres and one ncentres / dense each");
+    count.assign(un + 1, 0);
+    position.assign(3 * un + 1, 0.f);
+    orientation.assign(4 * un + 1, 0.f);
+    eigenvalues.assign(3 * un + 1, 0.f);
+    check<Tr>(h, pbd_part_poses(h, n, un ? &centres[0] : NULL, un ? &ncentres[0] : NULL, un ? &dense[0] : NULL, &count[0], &position[0],
+                                &orientation[0], &eigenvalues[0]));
+    count.resize(un);
+    position.resize(3 * un);
+    orientation.resize(4 * un);
+    eigenvalues.resize(3 * un);
+}
+
 // Frames of any sizes in one call (new surface: pbd_detect_frames; the reference has no batch API): candidates[i] receives
 // what detect(images[i]) gives.  The images share one depth and one channel count; any accepted depth.
 template <class Tr>

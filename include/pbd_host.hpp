@@ -697,6 +697,44 @@ public:
             if (dense) (*dense)[i] = dn[i] != 0;
         }
     }
+    // Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) on the device (pbd_candidate_mask): mask receives
+    // im.rows x im.cols uint8 labels (n+1 on the pixels of candidate n's boundingBox() no earlier candidate claimed, 255 from
+    // n = 254 on); with `masked`, also the ROS node's rgb & (mask != 0) (ros/Messages.cpp:157-174) of the 8-bit im, interleaved
+    // like im with dense rows
+    void mask(const Image &im, const std::vector<Candidate> &candidates, std::vector<uint8_t> &mask, std::vector<uint8_t> *masked = NULL)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "mask() before distributeModel()");
+        const std::vector<int32_t> rec = records(candidates);
+        const size_t npix = (size_t)(im.rows > 0 ? im.rows : 0) * (size_t)(im.cols > 0 ? im.cols : 0);
+        mask.assign(npix + 1, 0);
+        if (masked) masked->assign(npix * (size_t)(im.channels > 0 ? im.channels : 0) + 1, 0);
+        pbdbind::candidate_mask<HostTraits<T> >(h_, im, rec, (int)candidates.size(), &mask[0], (size_t)im.cols,
+                                                masked ? &(*masked)[0] : NULL, (size_t)im.cols * im.channels);
+        mask.resize(npix);
+        if (masked) masked->resize(masked->size() - 1);
+    }
+    // messagePoses (ros/Messages.cpp:187-234) on the device (pbd_part_poses) for the part centres computeBoundingBoxes returns:
+    // per candidate count (0: "Centroid not found", the node's `continue`), position (the centroid), orientation (x, y, z, w:
+    // the eigen-frame of the centres' spread) and eigenvalues (ascending)
+    void partPoses(const std::vector<std::vector<Point3f> > &part_centres, const std::vector<bool> &dense, std::vector<int32_t> &count,
+                   std::vector<float> &position, std::vector<float> &orientation, std::vector<float> &eigenvalues)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "partPoses() before distributeModel()");
+        const size_t n = part_centres.size(), mp = (size_t)(pbd_candidate_stride(h_) - 8) / 4;
+        if (dense.size() != n) throw Error(PBD_ERR_INVALID, "one dense flag per candidate");
+        std::vector<float> cen(n * mp * 3, 0.f);
+        std::vector<int32_t> nc(n), dn(n);
+        for (size_t i = 0; i < n; ++i) {
+            if (part_centres[i].size() > mp) throw Error(PBD_ERR_INVALID, "more part centres than the model's parts");
+            nc[i] = (int32_t)part_centres[i].size();
+            dn[i] = dense[i] ? 1 : 0;
+            for (size_t j = 0; j < part_centres[i].size(); ++j) {
+                float *c = &cen[(i * mp + j) * 3];
+                c[0] = part_centres[i][j].x; c[1] = part_centres[i][j].y; c[2] = part_centres[i][j].z;
+            }
+        }
+        pbdbind::part_poses<HostTraits<T> >(h_, (int)n, cen, nc, dn, count, position, orientation, eigenvalues);
+    }
     // PointCloudClusterer::clusterObjects(cloud, bounding_boxes, object_clusters, object_centers) (:157-293) on the device
     // (pbd_cluster_objects): clusters[i] = the point indices of box i's kept cluster, ascending (gather the points from the
     // cloud as ExtractIndices does); centres[i] its centroid, NaN without one.  `cloud`: x, y, z the first three floats of a point.

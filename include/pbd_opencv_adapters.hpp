@@ -185,4 +185,26 @@ inline void hipSuppress(pbd_handle *h, const cv::Mat &im, std::vector<typename C
     pbdbind::unpack_candidates<CvTraits<T> >(h, rec, n, candidates);
 }
 
+// Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) on the device (pbd_candidate_mask): mask becomes the
+// im.rows x im.cols CV_8U label image; every candidate is one of this frame
+template <typename T>
+inline void hipCandidateMask(pbd_handle *h, const cv::Mat &im, std::vector<typename CvTraits<T>::Candidate> &candidates, cv::Mat &mask)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    mask.create(im.rows, im.cols, CV_8U);
+    pbdbind::candidate_mask<CvTraits<T> >(h, im, rec, (int)candidates.size(), mask.ptr<uint8_t>(), mask.step, NULL, 0);
+}
+
+// messagePoses (ros/Messages.cpp:187-234) on the device (pbd_part_poses) for n candidates' part centres as pbd_boxes3d_camera
+// writes them (centres[3 * (i * max_parts + j)], ncentres, dense): count, position, orientation (x, y, z, w) and eigenvalues of
+// each, the node's PoseArray before its "Centroid not found" entries (count 0) are skipped
+template <typename T>
+inline void hipPartPoses(pbd_handle *h, int n, const std::vector<float> &centres, const std::vector<int32_t> &ncentres,
+                         const std::vector<int32_t> &dense, std::vector<int32_t> &count, std::vector<float> &position,
+                         std::vector<float> &orientation, std::vector<float> &eigenvalues)
+{
+    pbdbind::part_poses<CvTraits<T> >(h, n, centres, ncentres, dense, count, position, orientation, eigenvalues);
+}
+
 }  // namespace pbd_adapters

@@ -342,6 +342,13 @@ struct pbd_handle {
     // pbd_suppress*: the canvas plan of the last list of frame sizes, the check flag, the host form's records and output
     std::unique_ptr<Plan> sup_plan;
     DevBuf sup_bad, sup_in, sup_out;
+    // pbd_candidate_mask*: the frame table (staged as above), the workspace (hulls, frame ranges, the bad flag), the host form's
+    // records, frames and labels, and its status word
+    HostBuf mk_tab_host;
+    DevBuf mk_tab, mk_ws, mk_rec, mk_img;
+    Event mk_tab_copied;
+    // pbd_part_poses: the host form's inputs and outputs
+    DevBuf ps_buf;
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -2314,6 +2321,79 @@ int enqueue_camera(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_
     return PBD_OK;
 }
 
+// ---- candidate mask (pbd_candidate_mask*; pbd_kernels_publish.hip)
+// every check of a call's frames before anything is enqueued
+int check_mask_frames(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, uint8_t *const *labels, const size_t *label_pitch,
+                      int channels, const uint8_t *const *colour, const size_t *colour_pitch, uint8_t *const *masked,
+                      const size_t *masked_pitch)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    if (masked && channels != 1 && channels != 3 && channels != 4)
+        return fail(h, PBD_ERR_INVALID, "channels %d: 1, 3 or 4", channels);
+    if ((labels && !label_pitch) || (masked && (!masked_pitch || !colour || !colour_pitch)))
+        return fail(h, PBD_ERR_INVALID, "an output without its pitches or colour frames");
+    for (int f = 0; f < nframes; ++f) {
+        if (im_rows[f] < 1 || im_cols[f] < 1 || im_rows[f] > 65536 || im_cols[f] > 65536)
+            return fail(h, PBD_ERR_INVALID, "frame %d: size %dx%d (1..65536)", f, im_rows[f], im_cols[f]);
+        const size_t row = (size_t)im_cols[f];
+        if (labels && (!labels[f] || label_pitch[f] < row))
+            return fail(h, PBD_ERR_INVALID, "frame %d: labels %p, pitch %zu < row bytes %zu", f, (const void *)labels[f], label_pitch[f], row);
+        if (masked && (!masked[f] || !colour[f] || colour_pitch[f] < row * channels || masked_pitch[f] < row * channels))
+            return fail(h, PBD_ERR_INVALID, "frame %d: colour %p / masked %p, pitches %zu / %zu < row bytes %zu", f,
+                        (const void *)colour[f], (const void *)masked[f], colour_pitch[f], masked_pitch[f], row * channels);
+    }
+    return PBD_OK;
+}
+
+// the frame table (tile numbering filled in) to the device, then the hull and the tile kernels, on the handle's stream
+int enqueue_mask(pbd_handle *h, std::vector<MaskFrame> &tab, int channels, const int32_t *d_payload, int capacity, int frame_offset,
+                 int32_t *d_status)
+{
+    long long tiles = 0;
+    for (MaskFrame &fr : tab) {
+        fr.tile0 = (int)tiles;
+        tiles += mask_tiles(fr.rows, fr.cols);
+        if (tiles > 0x7fffffffll) return fail(h, PBD_ERR_INVALID, "%zu frames: 2^31 or more pixel tiles", tab.size());
+    }
+    if (int rc = stage_table(h, h->mk_tab_host, h->mk_tab, h->mk_tab_copied, tab.data(), tab.size() * sizeof(MaskFrame))) return rc;
+    const size_t hull_bytes = ((size_t)capacity * sizeof(int4) + 255) / 256 * 256;
+    HIPCHK(h, h->mk_ws.ensure(hull_bytes + (2 * tab.size() + 1) * sizeof(int32_t)));
+    MaskParams mp{};
+    mp.in = d_payload; mp.in_cap = capacity; mp.stride = stride(h); mp.max_parts = h->max_parts;
+    mp.frames = h->mk_tab.as<MaskFrame>(); mp.nframes = (int)tab.size(); mp.frame_offset = frame_offset;
+    mp.ntiles = (int)tiles; mp.channels = channels;
+    mp.hull = h->mk_ws.as<int4>();
+    mp.range = reinterpret_cast<int32_t *>(h->mk_ws.as<uint8_t>() + hull_bytes);
+    mp.bad = mp.range + 2 * tab.size();
+    mp.status = d_status;
+    {
+        ProfScope ps(h, PBD_K_MK_HULL, h->stream);
+        launch_mask(mp, kMkStepHull, h->stream);
+    }
+    {
+        ProfScope ps(h, PBD_K_MK_TILE, h->stream);
+        launch_mask(mp, kMkStepTile, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// ---- part-centre poses (pbd_part_poses*; pbd_kernels_publish.hip)
+int enqueue_poses(pbd_handle *h, const int32_t *d_word, int capacity, const float *d_centres, const int32_t *d_ncentres,
+                  const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues)
+{
+    PoseParams pp{};
+    pp.count_word = d_word; pp.cap = capacity; pp.max_parts = h->max_parts;
+    pp.centres = d_centres; pp.ncentres = d_ncentres; pp.dense = d_dense;
+    pp.count = d_count; pp.position = d_position; pp.orientation = d_orientation; pp.eigenvalues = d_eigenvalues;
+    {
+        ProfScope ps(h, PBD_K_PART_POSES, h->stream);
+        launch_part_poses(pp, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // ---- object clusters (pbd_cluster_objects*; pbd_kernels_cloud.hip)
 int check_clouds(pbd_handle *h, int nclouds, const pbd_cloud *c, bool host)
 {
@@ -3502,6 +3582,134 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
     });
 }
 
+// Candidate::mask (include/Candidate.hpp:306-331) and rgb & (mask != 0) (ros/Messages.cpp:157-174).  See include/pbd.h.
+int pbd_candidate_mask(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *cand, int ncand, int frame_offset,
+                       uint8_t *const *labels, const size_t *label_pitch, int channels, const uint8_t *const *colour,
+                       const size_t *colour_pitch, uint8_t *const *masked, const size_t *masked_pitch)
+{
+    return entry(h, im_rows && im_cols && (ncand <= 0 || cand), kIdle, [&]() -> int {
+        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+        if (int rc = check_mask_frames(h, nframes, im_rows, im_cols, labels, label_pitch, channels, colour, colour_pitch, masked,
+                                       masked_pitch)) return rc;
+        const int stride = ::stride(h);
+        for (int i = 0; i < ncand; ++i) {
+            const int32_t *r = cand + (size_t)i * stride;
+            const long long f = (long long)r[0] - frame_offset;
+            const long long g = i > 0 ? (long long)cand[(size_t)(i - 1) * stride] - frame_offset : 0;
+            if (f < 0 || f >= nframes || f < g)
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d or below the previous record's", i,
+                            r[0], frame_offset, nframes - 1);
+            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
+        }
+        if (!labels && !masked) return PBD_OK;
+        const int cn = masked ? channels : 0;
+        // the records as a payload, each frame's labels and colour packed with dense rows in the handle's own buffers
+        size_t lab_total = 0, img_total = 0;
+        for (int f = 0; f < nframes; ++f) {
+            lab_total += labels ? (size_t)im_rows[f] * im_cols[f] : 0;
+            img_total += (size_t)im_rows[f] * im_cols[f] * cn;
+        }
+        const size_t lab_bytes = (lab_total + 255) / 256 * 256;
+        HIPCHK(h, h->mk_img.ensure(lab_bytes + img_total + 256));
+        HIPCHK(h, h->mk_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+        HIPCHK(h, hipMemcpyAsync(h->mk_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        if (ncand) HIPCHK(h, hipMemcpyAsync(h->mk_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t),
+                                            hipMemcpyHostToDevice, h->stream));
+        std::vector<MaskFrame> tab(nframes);
+        uint8_t *lab = h->mk_img.as<uint8_t>(), *img = lab + lab_bytes;
+        for (int f = 0; f < nframes; ++f) {
+            const size_t lrow = (size_t)im_cols[f], crow = lrow * cn;
+            MaskFrame &fr = tab[f];
+            fr = MaskFrame{};
+            fr.rows = im_rows[f]; fr.cols = im_cols[f];
+            if (labels) { fr.labels = lab; fr.label_pitch = (long long)lrow; lab += lrow * im_rows[f]; }
+            if (masked) {
+                HIPCHK(h, hipMemcpy2DAsync(img, crow, colour[f], colour_pitch[f], crow, im_rows[f], hipMemcpyHostToDevice, h->stream));
+                fr.colour = img; fr.masked = img; fr.colour_pitch = fr.masked_pitch = (long long)crow;
+                img += crow * im_rows[f];
+            }
+        }
+        if (int rc = enqueue_mask(h, tab, cn, h->mk_rec.as<int32_t>(), ncand, frame_offset, nullptr)) return rc;
+        for (int f = 0; f < nframes; ++f) {
+            if (labels)
+                HIPCHK(h, hipMemcpy2DAsync(labels[f], label_pitch[f], tab[f].labels, (size_t)im_cols[f], (size_t)im_cols[f], im_rows[f],
+                                           hipMemcpyDeviceToHost, h->stream));
+            if (masked) {
+                const size_t crow = (size_t)im_cols[f] * cn;
+                HIPCHK(h, hipMemcpy2DAsync(masked[f], masked_pitch[f], tab[f].masked, crow, crow, im_rows[f], hipMemcpyDeviceToHost,
+                                           h->stream));
+            }
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_candidate_mask_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *d_payload, int capacity,
+                              int frame_offset, uint8_t *const *d_labels, const size_t *label_pitch, int channels,
+                              const uint8_t *const *d_colour, const size_t *colour_pitch, uint8_t *const *d_masked,
+                              const size_t *masked_pitch, int32_t *d_status)
+{
+    return entry(h, im_rows && im_cols && d_payload && d_status, kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_mask_frames(h, nframes, im_rows, im_cols, d_labels, label_pitch, channels, d_colour, colour_pitch, d_masked,
+                                       masked_pitch)) return rc;
+        std::vector<MaskFrame> tab(nframes);
+        for (int f = 0; f < nframes; ++f) {
+            MaskFrame &fr = tab[f];
+            fr = MaskFrame{};
+            fr.rows = im_rows[f]; fr.cols = im_cols[f];
+            if (d_labels) { fr.labels = d_labels[f]; fr.label_pitch = (long long)label_pitch[f]; }
+            if (d_masked) {
+                fr.colour = d_colour[f]; fr.masked = d_masked[f];
+                fr.colour_pitch = (long long)colour_pitch[f]; fr.masked_pitch = (long long)masked_pitch[f];
+            }
+        }
+        return enqueue_mask(h, tab, d_masked ? channels : 0, d_payload, capacity, frame_offset, d_status);
+    });
+}
+
+// PartsBasedDetectorNode::messagePoses (ros/Messages.cpp:187-234) per record.  See include/pbd.h.
+int pbd_part_poses(pbd_handle *h, int n, const float *centres, const int32_t *ncentres, const int32_t *dense, int32_t *count,
+                   float *position, float *orientation, float *eigenvalues)
+{
+    return entry(h, n <= 0 || (centres && ncentres && dense && count && position && orientation && eigenvalues), kIdle, [&]() -> int {
+        if (n < 0) return fail(h, PBD_ERR_INVALID, "n %d", n);
+        for (int i = 0; i < n; ++i)
+            if (ncentres[i] < 0 || ncentres[i] > h->max_parts)
+                return fail(h, PBD_ERR_INVALID, "record %d: ncentres %d (0..%d)", i, ncentres[i], h->max_parts);
+        if (n == 0) return PBD_OK;
+        const size_t nc = (size_t)n * h->max_parts * 3 * sizeof(float), ni = (size_t)n * sizeof(int32_t), n3 = (size_t)n * 3 * sizeof(float),
+                     n4 = (size_t)n * 4 * sizeof(float);
+        HIPCHK(h, h->ps_buf.ensure(nc + 3 * ni + 2 * n3 + n4 + 256));
+        uint8_t *b = h->ps_buf.as<uint8_t>();
+        float *d_cen = (float *)b, *d_pos = (float *)(b + nc), *d_ori = (float *)(b + nc + n3), *d_ev = (float *)(b + nc + n3 + n4);
+        int32_t *d_nc = (int32_t *)(b + nc + 2 * n3 + n4), *d_dn = d_nc + n, *d_cnt = d_dn + n, *d_word = d_cnt + n;
+        HIPCHK(h, hipMemcpyAsync(d_word, &n, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_cen, centres, nc, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_nc, ncentres, ni, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_dn, dense, ni, hipMemcpyHostToDevice, h->stream));
+        if (int rc = enqueue_poses(h, d_word, n, d_cen, d_nc, d_dn, d_cnt, d_pos, d_ori, d_ev)) return rc;
+        HIPCHK(h, hipMemcpyAsync(count, d_cnt, ni, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(position, d_pos, n3, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(orientation, d_ori, n4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(eigenvalues, d_ev, n3, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity, const float *d_centres, const int32_t *d_ncentres,
+                          const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues)
+{
+    return entry(h, d_payload && (capacity <= 0 || (d_centres && d_ncentres && d_dense && d_count && d_position && d_orientation &&
+                                                    d_eigenvalues)), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (capacity == 0) return PBD_OK;
+        return enqueue_poses(h, d_payload, capacity, d_centres, d_ncentres, d_dense, d_count, d_position, d_orientation, d_eigenvalues);
+    });
+}
+
 int pbd_profile_enable(pbd_handle *h, int on)
 {
     return entry(h, true, kBusyOk, [&]() -> int {
@@ -3533,7 +3741,8 @@ const char *pbd_kernel_name(int k)
                                              "k_dt_cols", "k_dp_combine", "k_dp_root", "k_argmin", "k_camera_boxes",
                                              "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear", "k_cl_grid_count",
                                              "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select",
-                                             "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact"};
+                                             "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile",
+                                             "k_part_poses"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

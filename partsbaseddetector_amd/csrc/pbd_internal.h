@@ -525,4 +525,38 @@ enum { kPlStepLoad = 0, kPlStepRowSums, kPlStepNormals, kPlStepHook, kPlStepSize
        kPlStepMoments, kPlStepPlanes, kPlStepLabel, kPlStepRefine, kPlStepFinal, kPlStepKeptScan, kPlStepKept, kPlStepOut, kPlSteps };
 void launch_planes_step(const PlaneParams &p, int step, hipStream_t s);
 
+// candidate mask and masked frame (pbd_candidate_mask*; pbd_kernels_publish.hip)
+struct MaskFrame {
+    uint8_t *labels;              // rows x cols labels, label_pitch bytes apart (NULL: not written)
+    const uint8_t *colour;        // rows x cols pixels of `channels` bytes, colour_pitch apart (read only when masked is set)
+    uint8_t *masked;              // the masked frame (may be colour itself, same pitch); NULL: not written
+    long long label_pitch, colour_pitch, masked_pitch;
+    int rows, cols;
+    int tile0;                    // the frame's first tile in the call's numbering
+};
+struct MaskParams {
+    const int32_t *in;            // payload: word 0 = records (negative or > in_cap: a bad list), then the records
+    int in_cap, stride, max_parts;
+    const MaskFrame *frames;      // [nframes]; a record's frame is its `frame` field - frame_offset
+    int nframes, frame_offset, ntiles, channels;
+    int4 *hull;                   // [in_cap] workspace: each record's clipped hull x0, y0, x1, y1 (all 0: empty)
+    int32_t *range;               // [2 * nframes] workspace: each frame's first and end record
+    int32_t *bad;                 // [1] workspace: the list is bad
+    int32_t *status;              // the device form's status word (-1 or the record count); NULL: none
+};
+enum { kMkStepHull = 0, kMkStepTile };
+void launch_mask(const MaskParams &p, int step, hipStream_t s);
+long long mask_tiles(int rows, int cols);   // k_mk_tile's tiles of one frame
+
+// the part-centre pose of each record (pbd_part_poses*; pbd_kernels_publish.hip)
+struct PoseParams {
+    const int32_t *count_word;    // min(max(word 0, 0), cap) records
+    int cap, max_parts;
+    const float *centres;         // [record][max_parts][3]
+    const int32_t *ncentres, *dense;
+    int32_t *count;               // [record]
+    float *position, *orientation, *eigenvalues;   // [record][3], [record][4] (x, y, z, w), [record][3]
+};
+void launch_part_poses(const PoseParams &p, hipStream_t s);
+
 }  // namespace pbd

@@ -11,7 +11,7 @@
 //              the segments above min_inliers; an exclusive scan; k_pl_cand_list: the candidates in point order
 //   planes     k_pl_moments: one workgroup per candidate, one wave per image row: the row's nine double moments, left to right
 //              (ballot, then an ordered walk of the matching lanes through readlane), the row partials top to bottom, then the
-//              Jacobi eigenpair;
+//              Jacobi eigenpair (jacobi3, pbd_jacobi.h);
 //              k_pl_planes (one thread per cloud): plane numbers in candidate order; k_pl_label: the working label image
 //   refine     k_pl_refine, once per pass: one workgroup per cloud, one thread per row, one anti-diagonal per step (the
 //              recurrence of include/pbd.h); a row's label and z at the previous step go through LDS (clouds taller than
@@ -20,6 +20,7 @@
 //              indices in order, then the NaN fill), k_pl_out (counts, plane records, status)
 // Every float / double operation whose bits are compared is an explicitly rounded intrinsic, so none of them is contracted.
 #include "pbd_internal.h"
+#include "pbd_jacobi.h"
 
 #include <math.h>
 
@@ -36,7 +37,6 @@ constexpr int kMoThreads = 1024;                 // k_pl_moments: 16 waves, one 
 constexpr int kMoWaves = kMoThreads / 64;
 constexpr int kMoRows = 128;                     // row partials staged in LDS per round
 constexpr int kRefThreads = 1024;                // k_pl_refine: one workgroup per cloud
-constexpr int kJacobiSweeps = 8;
 
 __device__ inline float pl_qnan() { return __int_as_float(0x7fc00000); }
 __device__ inline bool pl_finite(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
@@ -343,37 +343,6 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_cand_list(PlaneParams p)
 }
 
 // cyclic Jacobi on the symmetric 3x3 A (double, + - * / sqrt only); V accumulates the rotations from the identity
-__device__ void pl_jacobi(double A[3][3], double V[3][3])
-{
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) V[i][k] = i == k ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep)
-        for (int pr = 0; pr < 3; ++pr) {
-            const int P = pr == 2 ? 1 : 0, Q = pr == 0 ? 1 : 2;     // (0,1), (0,2), (1,2)
-            const double apq = A[P][Q];
-            if (apq == 0.0) continue;
-            const double theta = __ddiv_rn(__dsub_rn(A[Q][Q], A[P][P]), __dmul_rn(2.0, apq));
-            double t = __ddiv_rn(1.0, __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-            if (theta < 0.0) t = -t;
-            const double cs = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), sn = __dmul_rn(t, cs);
-            for (int k = 0; k < 3; ++k) {                           // A J
-                const double akp = A[k][P], akq = A[k][Q];
-                A[k][P] = __dsub_rn(__dmul_rn(cs, akp), __dmul_rn(sn, akq));
-                A[k][Q] = __dadd_rn(__dmul_rn(sn, akp), __dmul_rn(cs, akq));
-            }
-            for (int k = 0; k < 3; ++k) {                           // J^T (A J)
-                const double apk = A[P][k], aqk = A[Q][k];
-                A[P][k] = __dsub_rn(__dmul_rn(cs, apk), __dmul_rn(sn, aqk));
-                A[Q][k] = __dadd_rn(__dmul_rn(sn, apk), __dmul_rn(cs, aqk));
-            }
-            for (int k = 0; k < 3; ++k) {                           // V J
-                const double vkp = V[k][P], vkq = V[k][Q];
-                V[k][P] = __dsub_rn(__dmul_rn(cs, vkp), __dmul_rn(sn, vkq));
-                V[k][Q] = __dadd_rn(__dmul_rn(sn, vkp), __dmul_rn(cs, vkq));
-            }
-        }
-}
-
 // one workgroup per candidate: the nine moments {x, y, z, xx, xy, xz, yy, yz, zz} in double, each row left to right, the row
 // partials top to bottom; mean, covariance, the smallest eigenpair, curvature and the plane
 __global__ __launch_bounds__(kMoThreads) void k_pl_moments(PlaneParams p)
@@ -427,7 +396,7 @@ __global__ __launch_bounds__(kMoThreads) void k_pl_moments(PlaneParams p)
             const double xz = __dsub_rn(m[5], __dmul_rn(m[0], m[2])), yy = __dsub_rn(m[6], __dmul_rn(m[1], m[1]));
             const double yz = __dsub_rn(m[7], __dmul_rn(m[1], m[2])), zz = __dsub_rn(m[8], __dmul_rn(m[2], m[2]));
             double A[3][3] = {{xx, xy, xz}, {xy, yy, yz}, {xz, yz, zz}}, V[3][3];
-            pl_jacobi(A, V);
+            jacobi3(A, V);
             int k = 0;
             if (A[1][1] < A[k][k]) k = 1;
             if (A[2][2] < A[k][k]) k = 2;

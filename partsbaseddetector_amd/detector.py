@@ -121,6 +121,14 @@ class Candidate:
         return float(bx), float(by), z0, float(bh), float(bw), z1 - z0
 
     @staticmethod
+    def mask(im_shape, candidates: Sequence["Candidate"]) -> np.ndarray:
+        """Candidate.hpp:320-331 on the host, in numpy: the CV_8U label image of `im_shape` = (rows, cols) in which label n+1 marks
+        the pixels of candidate n's boundingBox() that no earlier candidate claimed (255 from n = 254 on).  The yardstick of
+        pbd_candidate_mask (publish.candidate_mask)."""
+        from . import publish
+        return publish.candidate_mask(im_shape, [c.boundingBox() for c in candidates])
+
+    @staticmethod
     def nonMaximaSuppression(im_shape, candidates: List["Candidate"], overlap: float = 0.0) -> None:
         """Candidate.hpp:277-304: greedy paint-the-canvas suppression on the bounding boxes, in the given
         order (callers sort by score first: cells/detect.cpp:237-238, ros/Node.cpp:192-196).  In place."""
@@ -387,6 +395,68 @@ class Handle:
         self.check(self.lib.pbd_boxes3d_camera_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
                                                       _lib.ptr(ic, C.c_int), _lib.pinhole_array(cameras), parts_mode, d_payload_ptr,
                                                       capacity, frame_offset, d_box_ptr, d_centres_ptr, d_ncentres_ptr, d_dense_ptr))
+
+    def candidate_mask(self, im_shapes, records: np.ndarray, frames: Optional[Sequence[np.ndarray]] = None, frame_offset: int = 0,
+                       labels: bool = True, in_place: bool = False):
+        """pbd_candidate_mask: (labels, masked) of the records (n, stride) grouped by ascending frame; im_shapes[f] = (rows, cols) of
+        frame index f.  labels: uint8 (rows, cols) per frame (None when labels=False); masked: with `frames` (uint8 (rows, cols) or
+        (rows, cols, 1 | 3 | 4), any row pitch), each frame & (label != 0), written over the frames themselves when in_place."""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        nf = len(ir)
+        rec = self._records(records)
+        labs = [np.zeros((int(ir[f]), int(ic[f])), np.uint8) for f in range(nf)] if labels else None
+        lab_p = (C.c_void_p * nf)(*[a.ctypes.data for a in labs]) if labels else None
+        lab_s = (C.c_size_t * nf)(*[a.strides[0] for a in labs]) if labels else None
+        cn, col_p, col_s, out_p, out_s, outs = 0, None, None, None, None, None
+        if frames is not None:
+            if any(f.dtype != np.uint8 or f.strides[-1] != 1 or (f.ndim == 3 and f.strides[1] != f.shape[2]) for f in frames):
+                raise PbdError(-1, "frames are uint8 (rows, cols[, channels]) with interleaved channels")
+            cn = frames[0].shape[2] if frames[0].ndim == 3 else 1
+            outs = list(frames) if in_place else [np.zeros_like(f) for f in frames]
+            col_p = (C.c_void_p * nf)(*[f.ctypes.data for f in frames])
+            col_s = (C.c_size_t * nf)(*[f.strides[0] for f in frames])
+            out_p = (C.c_void_p * nf)(*[f.ctypes.data for f in outs])
+            out_s = (C.c_size_t * nf)(*[f.strides[0] for f in outs])
+        self.check(self.lib.pbd_candidate_mask(self.h, nf, _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
+                                               rec.ctypes.data if rec.size else None, len(rec), frame_offset, lab_p, lab_s, cn, col_p,
+                                               col_s, out_p, out_s))
+        return labs, outs
+
+    def candidate_mask_device(self, im_shapes, d_payload_ptr: int, capacity: int, frame_offset: int, label_descs=None, channels: int = 0,
+                              colour_descs=None, masked_descs=None, d_status_ptr: int = 0) -> None:
+        """pbd_candidate_mask_device: the records of a device payload; label_descs / colour_descs / masked_descs: (device pointer,
+        pitch) per frame, or None to omit that output; the record count or -1 into the int32 at d_status_ptr; asynchronous"""
+        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        nf = len(ir)
+        arr = (lambda d, k, t: None if d is None else (t * nf)(*[e[k] for e in d]))
+        self.check(self.lib.pbd_candidate_mask_device(self.h, nf, _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), d_payload_ptr, capacity,
+                                                      frame_offset, arr(label_descs, 0, C.c_void_p), arr(label_descs, 1, C.c_size_t),
+                                                      channels, arr(colour_descs, 0, C.c_void_p), arr(colour_descs, 1, C.c_size_t),
+                                                      arr(masked_descs, 0, C.c_void_p), arr(masked_descs, 1, C.c_size_t), d_status_ptr))
+
+    def part_poses(self, centres: np.ndarray, ncentres: np.ndarray, dense: np.ndarray):
+        """pbd_part_poses: (count (n,) int32, position (n, 3), orientation (n, 4) x, y, z, w, eigenvalues (n, 3)) float32 of what
+        boxes3d_camera returns: centres (n, max_parts, 3) float32, ncentres (n,), dense (n,)"""
+        nc = np.ascontiguousarray(ncentres, np.int32).reshape(-1)
+        n = len(nc)
+        cen = np.ascontiguousarray(centres, np.float32).reshape(n, self.max_parts, 3)
+        dn = np.ascontiguousarray(dense, np.int32).reshape(n)
+        cnt = np.zeros(n, np.int32)
+        pos = np.zeros((n, 3), np.float32)
+        ori = np.zeros((n, 4), np.float32)
+        ev = np.zeros((n, 3), np.float32)
+        ptr = (lambda a: a.ctypes.data if n else None)
+        self.check(self.lib.pbd_part_poses(self.h, n, ptr(cen), ptr(nc), ptr(dn), ptr(cnt), ptr(pos), ptr(ori), ptr(ev)))
+        return cnt, pos, ori, ev
+
+    def part_poses_device(self, d_payload_ptr: int, capacity: int, d_centres_ptr: int, d_ncentres_ptr: int, d_dense_ptr: int,
+                          d_count_ptr: int, d_position_ptr: int, d_orientation_ptr: int, d_eigenvalues_ptr: int) -> None:
+        """pbd_part_poses_device: boxes3d_camera_device's outputs in, per-record poses out (device arrays of `capacity` records);
+        asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_part_poses_device(self.h, d_payload_ptr, capacity, d_centres_ptr, d_ncentres_ptr, d_dense_ptr,
+                                                  d_count_ptr, d_position_ptr, d_orientation_ptr, d_eigenvalues_ptr))
 
     @staticmethod
     def cloud_desc(cloud: np.ndarray):
@@ -799,6 +869,27 @@ class PartsBasedDetector:
         if hasattr(cameras, "fx"):
             cameras = [cameras]
         return self.hd.boxes3d_camera(list(depths), list(im_shapes), list(cameras), self.hd.pack_candidates(candidates), parts_mode)
+
+    def mask(self, candidates: Sequence[Candidate], im_shapes, frames=None, in_place: bool = False):
+        """Candidate::mask per frame and the ROS node's masked frame `rgb & (mask != 0)`, on the device (pbd_candidate_mask):
+        candidates grouped by ascending frame; im_shapes[f] = (rows, cols) of frame index f (one shape for one frame).  Returns the
+        labels (one uint8 (rows, cols) per frame) and, when `frames` (uint8 colour frames of 1, 3 or 4 channels) are given, the
+        masked frames (written over `frames` when in_place).  Equal to publish.frame_masks / publish.masked_image."""
+        self._need()
+        if len(im_shapes) and np.isscalar(im_shapes[0]):
+            im_shapes = [im_shapes]
+        if isinstance(frames, np.ndarray):
+            frames = [frames]
+        rec = self.hd.pack_candidates(list(candidates))
+        labels, masked = self.hd.candidate_mask(list(im_shapes), rec, None if frames is None else list(frames), in_place=in_place)
+        return (labels, masked) if frames is not None else labels
+
+    def partPoses(self, centres: np.ndarray, ncentres: np.ndarray, dense: np.ndarray):
+        """messagePoses per candidate on the device (pbd_part_poses), from what computeBoundingBoxes returns: (count (n,) int32 --
+        0 for "Centroid not found", position (n, 3), orientation (n, 4) as x, y, z, w, eigenvalues (n, 3) ascending) float32.
+        Equal bit for bit to publish.part_poses."""
+        self._need()
+        return self.hd.part_poses(centres, ncentres, dense)
 
     def removePlanes(self, cloud, params=None):
         """PointCloudClusterer::organizedMultiplaneSegmentation on the device (pbd_remove_planes): (cloud_no_planes (k, 3) float32,
