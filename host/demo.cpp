@@ -1,9 +1,9 @@
 // demo.cpp -- command-line harness with the flow of the reference's src/demo.cpp:55-117:
-//   model file -> FileStorageModel::deserialize -> PartsBasedDetector<T>::distributeModel -> read image ->
+//   model file -> FileStorageModel / MatlabIOModel::deserialize -> PartsBasedDetector<T>::distributeModel -> read image ->
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
@@ -25,13 +25,16 @@
 //           (the labelled pixels); --masked: the image & (mask != 0) (the ROS node's mask topic), a binary PPM (PGM for grey)
 //   --poses: with --camera, one line per listed candidate after its "object" line: "pose COUNT x y z qx qy qz qw" (messagePoses
 //           on the part centres, on the device; COUNT 0 is the node's "Centroid not found")
-//   pbd_demo model.(yml|xml) --dump-model      (no GPU needed: prints what FileStorageModel::deserialize read)
+//   pbd_demo model.(yml|xml|mat) --dump-model  (no GPU needed: prints what the model reader read)
+// The model reader follows the extension, as the reference's demo chooses it (src/demo.cpp:63-77): .mat -> MatlabIOModel
+// (include/pbd_matlabio.hpp), any other -> FileStorageModel.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 
 #include "pbd_host.hpp"
+#include "pbd_matlabio.hpp"
 
 using namespace pbdhost;
 
@@ -56,7 +59,7 @@ static void report(std::vector<Candidate> &candidates, const Image &im, bool sta
 
 // the first image and the --also images through one detectBatch call; one report per image, in order
 template <typename T>
-static int run_batch(FileStorageModel &model, const std::vector<Image> &ims, float nms, float dnms, int top, int conv_mode)
+static int run_batch(Model &model, const std::vector<Image> &ims, float nms, float dnms, int top, int conv_mode)
 {
     PartsBasedDetector<T> pbd(0, conv_mode, (int)ims.size());
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
@@ -139,7 +142,7 @@ static bool writePNM(const char *path, const uint8_t *data, int rows, int cols, 
 }
 
 template <typename T>
-static int run(FileStorageModel &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
+static int run(Model &model, const Image &im, bool staged, float nms, float dnms, int top, int stream_k, int stream_n,
                int conv_mode, const Image *depth, const pbd_pinhole *camera, bool remove_planes, float dcz, const char *mask_path,
                const char *masked_path, bool poses)
 {
@@ -235,8 +238,8 @@ static int run(FileStorageModel &model, const Image &im, bool staged, float nms,
     return 0;
 }
 
-// every field FileStorageModel::deserialize fills, as text (doubles with 17 significant digits: exact round trip)
-static int dump_model(const FileStorageModel &m)
+// every field the model readers fill, as text (doubles with 17 significant digits: exact round trip)
+static int dump_model(const Model &m)
 {
     std::printf("name %s\ninterval %d\nthresh %.9g\nsbin %d\nnorient %d\nflen %d\n", m.name().c_str(), m.nscales(), (double)m.thresh(),
                 m.binsize(), m.norient(), m.flen());
@@ -336,8 +339,12 @@ int main(int argc, char **argv)
         return -1;
     }
     try {
-        FileStorageModel model;
-        if (!model.deserialize(argv[1])) { std::fprintf(stderr, "Error deserializing file\n"); return -1; }
+        const std::string mpath = argv[1];
+        const bool mat = mpath.size() >= 4 && mpath.compare(mpath.size() - 4, 4, ".mat") == 0;
+        FileStorageModel fs_model;
+        MatlabIOModel mat_model;
+        Model &model = mat ? static_cast<Model &>(mat_model) : static_cast<Model &>(fs_model);
+        if (!(mat ? mat_model.deserialize(mpath) : fs_model.deserialize(mpath))) { std::fprintf(stderr, "Error deserializing file\n"); return -1; }
         if (!std::strcmp(argv[2], "--dump-model")) return dump_model(model);
         std::vector<uint8_t> pix;
         Image im;

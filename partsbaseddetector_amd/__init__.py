@@ -6,6 +6,7 @@ the reference's IFeatures / IConvolutionEngine / DynamicProgram / PartsBasedDete
 """
 from .model import Model, FlatModel, synthetic_model, synthetic_person_model, synthetic_face_model, synthetic_tiny_model  # noqa: F401
 from .synth import synthetic_frame, synthetic_depth  # noqa: F401
+from .modelfile import load_model_file  # noqa: F401
 
 
 def __getattr__(name):

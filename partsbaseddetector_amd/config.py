@@ -14,6 +14,7 @@ from typing import List, Optional
 import yaml
 
 from . import filestorage
+from .modelfile import MODEL_EXTENSIONS, load_model_file
 from .model import Model
 
 
@@ -56,9 +57,12 @@ def load_by_parts(path: str) -> List[DetectorConfig]:
 def load_model(cfg: DetectorConfig, stand_in: Optional[Model] = None, search_dirs=()) -> Model:
     """The model a configuration names: the file itself, or a file of the same name in `search_dirs` (the
     configs hold absolute paths of the authors' machines), or -- the reference ships no model files: ``models/`` is an
-    empty submodule -- the given synthetic stand-in."""
+    empty submodule -- the given synthetic stand-in.  The reader follows the extension (load_model_file: a ``.mat`` file
+    needs no conversion); a file of any other extension is read as a FileStorage document."""
     for cand in [cfg.model_file] + [os.path.join(d, os.path.basename(cfg.model_file)) for d in search_dirs]:
         if os.path.exists(cand):
+            if os.path.splitext(cand)[1].lower() in MODEL_EXTENSIONS:
+                return load_model_file(cand)
             return filestorage.deserialize(cand)
     if stand_in is None:
         raise FileNotFoundError(f"model file {cfg.model_file} not found")
