@@ -482,6 +482,66 @@ int pbd_part_poses(pbd_handle *h, int n, const float *centres, const int32_t *nc
 int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity, const float *d_centres, const int32_t *d_ncentres,
                           const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues);
 
+/* Training examples (new surface; opt-in): the feature vector `ex` that the reference's Matlab training code builds from a
+ * detection (matlab/detection/detect.m backtrack with write, qp_write), so that w . ex reproduces the detection's score.
+ * The model vector: ONE parameter order per handle, values of T (the handle's real type), from the pbd_model the handle was
+ * created with:
+ *   w = [ biasw (nbias) | defw (ndefs x 4) | filters ]
+ *   bias b at b, deformation d at nbias + 4 d, filter f at nbias + 4 ndefs + filter_offset[f], each k x (k * flen) row-major as
+ *   pbd_model holds it; gaps between filters (a filter_offset table that does not pack them) are 0.
+ * The `.i` offsets of a Matlab model are not used (as in the .mat reader).  pbd_model_vector_len: the number of values;
+ * pbd_model_vector writes them to w (a host buffer of that many T).
+ * An example: the walk of a record (frame, level, component, root_x, root_y) through the resident back-pointer maps, with the
+ * pointer composition of pbd_detect*'s own walk (root mixture = the root's rooti, child position = Ix / Iy composed as the
+ * reference does, include/DistanceTransform.hpp:233-244).  Per part, in part order 0..nparts-1, the blocks:
+ *   bias    1 value = 1 at the bias the dynamic program added: the root's biasid of mixture 0 (src/DynamicProgram.cpp:163-170);
+ *           a child of mixture mm under parent mixture m: biasid[c][p][mm] + m
+ *   def     children only: 4 values {-dx*dx, -dx, -dy*dy, -dy}, dx = parent x + anchor x - x, dy likewise (the displacement
+ *           the distance transform charged), so defw . def is the deformation term the transform added
+ *   filter  the k x k x flen window of the feature map the convolution read for the part's response: cells x - k/2 .. and
+ *           y - k/2 .. (OpenCV's centred anchor), row-major, channel fastest; a cell outside the map holds the convolution's
+ *           border values: 0 on channels 0..flen-2, 1 on channel flen-1 (src/SpatialConvolutionEngine.cpp:146-156)
+ * A block's offset is its place in w; two blocks may share an offset (a filter id used twice), as the score counted it twice.
+ * Output per example i (record i of the caller's list), fixed strides reported by pbd_example_stride:
+ *   hdr     int32[hdr_words] = {i, component, nblocks, nvalues, (offset, length) x nblocks, 0 ...}
+ *   values  T[values]: the blocks' values concatenated in block order; values past nvalues are not written
+ * w . values equals the record's score up to rounding (DESIGN.md section 6h states the bound) whenever the composed pointers
+ * are the transform's true arg-max; where the reference's composition moved a part (a known quirk, reproduced on purpose)
+ * the example is that of the placement the record reports and w . values is at most the score.
+ * pbd_examples: host records (any subset of the last completed detect call's, in any order, with or without pbd_set_nms,
+ * pbd_detect_frames' included); a record's frame is its `frame` field - frame_offset.  PBD_ERR_INVALID, naming the record,
+ * when its frame, level, component or root position is outside the resident result (a level-sharded handle holds only its
+ * own levels); PBD_ERR_STATE without a resident detect result (none yet, after pbd_conv_set_filters or pbd_dp_min, or a bank
+ * whose filter sizes differ from the model's) or while a batch is in flight.  Synchronous.
+ * pbd_examples_device: the records of the payload d_payload (word 0 = count, as pbd_detect_batch_device_out leaves it):
+ * min(max(word 0, 0), capacity) examples, so a -1 payload writes nothing; a record outside the resident result gets the
+ * header {i, component, -1, 0, 0 ...} and no values.  d_hdr = int32[capacity * hdr_words], d_values = T[capacity * values] on
+ * the device.  Asynchronous on pbd_stream().  Neither call changes the resident result. */
+/* Latent positives (new surface; opt-in): detect(im, model, 0, bbox, overlap) of the reference's Matlab training code
+ * (matlab/learning/train.m poslatent; testoverlap, bbox.m).  Frames as pbd_detect_frames takes them (host pointers, mixed sizes,
+ * the four depths, nframes <= max_batch).  boxes = int32[nframes][nparts][4]: frame f's ground-truth box {x1, y1, x2, y2}
+ * (inclusive, as in Matlab) of every part index; mixtures = int32[nframes][nparts] fixed mixture of every part (-1 free), or NULL.
+ * Part p (of every component) at (x, y) of level l with mixture m keeps its response only when m is allowed and its record
+ * rectangle (src/DynamicProgram.cpp:238-241: xy1 = ((x, y) - (1, 1)) * scale, xy2 = xy1 + size(m) * scale - (1, 1), cvRound;
+ * the rectangle of min / max corners) passes inter / (area + barea - inter) > overlap, computed in double with inclusive (+1)
+ * areas; otherwise the response is replaced by -1e10 in T (Matlab's -INF, finite: -inf would put NaN into the transform's
+ * intersections).  The mask belongs to the (component, part, mixture): the call runs the model with one filter per
+ * (component, part, mixture) (filter ids shared by several parts are copied), the sequential schedule of shared ids does not
+ * apply, and the detect path of the handle is not touched.  Output per frame f: cand + f * pbd_candidate_stride() = the single
+ * highest-scoring root over all levels, components and positions (ties: the first in (level, component, y, x) order), as a
+ * normal record (`frame` = f, part boxes of the walk); found[f] = 1 iff its score > -5e9 (no masked term used).
+ * The call leaves a resident result: pbd_examples* then give the positives' feature vectors (offsets in this handle's model
+ * vector); pbd_get_stage / pbd_argmin_device_out / pbd_dp_argmin see no result until the next detect call.  pbd_set_nms does not
+ * apply.  PBD_ERR_UNSUPPORTED: components with different part counts, level sharding (world > 1), PBD_CONV_MFMA_F16.
+ * PBD_ERR_INVALID: a NaN overlap, and the frame refusals of pbd_detect_frames.  PBD_ERR_STATE while a batch is in flight. */
+int pbd_detect_latent(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
+                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found);
+int pbd_model_vector_len(const pbd_handle *h);
+int pbd_model_vector(pbd_handle *h, void *w);
+int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values);
+int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values);
+int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -603,6 +663,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_DC_CLASSIFY, PBD_K_DC_SELECT, PBD_K_DC_COMPACT,
        /* pbd_candidate_mask* (k_mk_hull times k_mk_init and k_mk_hull), pbd_part_poses* */
        PBD_K_MK_HULL, PBD_K_MK_TILE, PBD_K_PART_POSES,
+       /* pbd_examples*: the walk of every record, then the gather of its feature windows */
+       PBD_K_EX_WALK, PBD_K_EX_GATHER,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

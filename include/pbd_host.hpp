@@ -735,6 +735,31 @@ public:
         }
         pbdbind::part_poses<HostTraits<T> >(h_, (int)n, cen, nc, dn, count, position, orientation, eigenvalues);
     }
+    // the model vector w = [biasw | defw | filters] in T (pbd_model_vector): the parameter order of examples()
+    std::vector<T> modelVector()
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "modelVector() before distributeModel()");
+        std::vector<T> w((size_t)pbd_model_vector_len(h_) + 1);
+        pbdbind::check<HostTraits<T> >(h_, pbd_model_vector(h_, &w[0]));
+        w.resize(w.size() - 1);
+        return w;
+    }
+    // training examples of candidates of the last detect() (pbd_examples, include/pbd.h): hdr receives hdr_words int32 per
+    // candidate {index, component, nblocks, nvalues, (offset in modelVector(), length) x nblocks}, values `values` T per candidate
+    // (the blocks' values in order); w . x is the candidate's score when its parts sit at the transform's arg-max
+    void examples(const std::vector<Candidate> &candidates, std::vector<int32_t> &hdr, std::vector<T> &values, int &hdr_words,
+                  int &nvalues)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "examples() before distributeModel()");
+        pbdbind::check<HostTraits<T> >(h_, pbd_example_stride(h_, &hdr_words, &nvalues));
+        const std::vector<int32_t> rec = records(candidates);
+        const size_t n = candidates.size();
+        hdr.assign(n * (size_t)hdr_words + 1, 0);
+        values.assign(n * (size_t)nvalues + 1, T(0));
+        pbdbind::check<HostTraits<T> >(h_, pbd_examples(h_, n ? &rec[0] : NULL, (int)n, 0, &hdr[0], &values[0]));
+        hdr.resize(hdr.size() - 1);
+        values.resize(values.size() - 1);
+    }
     // PointCloudClusterer::clusterObjects(cloud, bounding_boxes, object_clusters, object_centers) (:157-293) on the device
     // (pbd_cluster_objects): clusters[i] = the point indices of box i's kept cluster, ascending (gather the points from the
     // cloud as ExtractIndices does); centres[i] its centroid, NaN without one.  `cloud`: x, y, z the first three floats of a point.
@@ -814,6 +839,36 @@ public:
     {
         if (!h_) throw Error(PBD_ERR_STATE, "detectBatch() before distributeModel()");
         pbdbind::detect_batch<HostTraits<T> >(h_, images, candidates, 1 << 18);
+    }
+    // latent positives (matlab/detection/detect.m with a bbox) on the device (pbd_detect_latent): per image the best candidate
+    // whose part p overlaps boxes[i][p] = {x1, y1, x2, y2} (inclusive) by more than `overlap`; mixtures[i][p] >= 0 fixes part p's
+    // mixture (empty: all free).  One candidate per image; found[i] = false when no placement passes.  One depth per call.
+    void detectLatent(const std::vector<Image> &images, const std::vector<std::vector<int32_t> > &boxes, float overlap,
+                      const std::vector<std::vector<int32_t> > &mixtures, std::vector<Candidate> &candidates, std::vector<bool> &found)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "detectLatent() before distributeModel()");
+        const size_t n = images.size();
+        if (n == 0 || boxes.size() != n || (!mixtures.empty() && mixtures.size() != n))
+            throw Error(PBD_ERR_INVALID, "detectLatent: one box list (and mixture list) per image");
+        const size_t np = boxes[0].size() / 4;
+        std::vector<pbd_frame> fr(n);
+        std::vector<int32_t> bx, mx;
+        for (size_t i = 0; i < n; ++i) {
+            if (boxes[i].size() != 4 * np || (!mixtures.empty() && mixtures[i].size() != np))
+                throw Error(PBD_ERR_INVALID, "detectLatent: four box values and one mixture per part");
+            fr[i].data = images[i].data; fr[i].rows = images[i].rows; fr[i].cols = images[i].cols; fr[i].stride_bytes = images[i].step;
+            bx.insert(bx.end(), boxes[i].begin(), boxes[i].end());
+            if (!mixtures.empty()) mx.insert(mx.end(), mixtures[i].begin(), mixtures[i].end());
+        }
+        const int stride = pbd_candidate_stride(h_);
+        std::vector<int32_t> rec(n * (size_t)stride), fnd(n);
+        bx.push_back(0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_detect_latent(h_, (int)n, &fr[0], images[0].channels, images[0].depth, &bx[0],
+                                                             mx.empty() ? NULL : &mx[0], overlap, &rec[0], &fnd[0]));
+        candidates.clear();
+        pbdbind::unpack_candidates<HostTraits<T> >(h_, rec, (int)n, candidates);
+        found.assign(n, false);
+        for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
     }
 };
 

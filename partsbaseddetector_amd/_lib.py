@@ -27,7 +27,8 @@ DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32
 KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows", "k_dt_cols", "k_dp_combine",
            "k_dp_root", "k_argmin", "k_camera_boxes", "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear",
            "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out",
-           "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile", "k_part_poses"]
+           "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile", "k_part_poses",
+           "k_ex_walk", "k_ex_gather"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -41,7 +42,8 @@ SYMBOLS = [
     "pbd_boxes3d", "pbd_boxes3d_device", "pbd_boxes3d_camera", "pbd_boxes3d_camera_device", "pbd_cluster_objects",
     "pbd_cluster_objects_device", "pbd_remove_planes", "pbd_remove_planes_device", "pbd_depth_consistency",
     "pbd_depth_consistency_device", "pbd_suppress", "pbd_suppress_device", "pbd_candidate_mask", "pbd_candidate_mask_device",
-    "pbd_part_poses", "pbd_part_poses_device",
+    "pbd_part_poses", "pbd_part_poses_device", "pbd_model_vector_len", "pbd_model_vector", "pbd_example_stride", "pbd_examples",
+    "pbd_examples_device", "pbd_detect_latent",
 ]
 
 
@@ -211,6 +213,13 @@ def load():
     lib.pbd_candidate_mask_device.argtypes = lib.pbd_candidate_mask.argtypes + [C.c_void_p]
     lib.pbd_part_poses.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
     lib.pbd_part_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.pbd_model_vector_len.argtypes = [C.c_void_p]
+    lib.pbd_model_vector.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pbd_example_stride.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.pbd_examples.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pbd_examples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pbd_detect_latent.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                      C.c_void_p, C.c_void_p]
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

@@ -191,6 +191,7 @@ struct Plan {
     DevTable<int2> d_fdim;
     DevTable<long long> d_fcanvas;
     DevTable<int> d_post_lds, d_post_glb;
+    DevTable<int> d_frame_lv0;              // frame_lv0 on the device (pbd_examples*, uploaded on first use)
     // dynamic program in groups of whole frames when the virtual frame's scratch exceeds the budget: sub-plans whose cell
     // offsets start at 0 (cell0 = the group's first cell in the virtual frame), built for `chunk_budget`
     size_t chunk_budget = 0;
@@ -244,6 +245,7 @@ struct Resident {
     int frames = 0, cn = 3, depth = kDepth8U;   // frames, channels and image depth of the pyramid
     bool features = false, resp = false, dp = false;   // the stages held, all for `plan`
     bool c31_zero = false;           // the features were written by the HOG kernels (channel 31 = 0), not uploaded by the caller
+    bool latent = false;             // pbd_detect_latent: the result lives in the handle's latent twin (pbd_examples* read it there)
     void drop_conv() { resp = dp = false; }   // the filter bank changed
     void clear() { *this = Resident{}; }
 };
@@ -349,6 +351,23 @@ struct pbd_handle {
     Event mk_tab_copied;
     // pbd_part_poses: the host form's inputs and outputs
     DevBuf ps_buf;
+    // pbd_model_vector / pbd_examples*: the model vector in T (built by build_model), the filter sizes and offsets of the model the
+    // handle was created with, the strides of an example, the walk's tables (uploaded on first use), the (record, part) workspace,
+    // the host form's records and outputs
+    std::vector<char> mvec;
+    std::vector<int> model_ksize;
+    std::vector<long long> model_foff;   // offset of filter f in the model vector
+    int nbias = 0, ndefs = 0, ex_hdr_words = 0, ex_values = 0;
+    DevTable<ExGm> ex_gm;
+    DevTable<int> ex_anchors;
+    DevTable<long long> ex_foff;
+    DevBuf ex_ws, ex_rec, ex_out;
+    // pbd_detect_latent: a second handle on the same stream whose model gives every (component, part, mixture) its own filter
+    // (the mask belongs to the (component, part, mixture), not to a shared filter), created on first use; the part -> mixture
+    // table of its bank, the call's boxes / mixtures and its payload.  The detect path of this handle never touches it.
+    std::unique_ptr<pbd_handle, void (*)(pbd_handle *)> lat{nullptr, pbd_destroy};
+    DevTable<int4> lat_gm;
+    DevBuf lat_in, lat_pay;
     // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
     HostBuf fd_host;
     DevBuf fd_dev;
@@ -1380,6 +1399,44 @@ int build_model(pbd_handle *h, const pbd_model *m)
     HIPCHK(h, h->d_walk.upload(h->walk));
     HIPCHK(h, h->d_walk_off.upload(h->walk_off));
     HIPCHK(h, h->d_biasw.upload(h->biasw));
+
+    // the model vector (pbd_model_vector) and the strides of an example (pbd_examples*)
+    h->nbias = m->nbias; h->ndefs = m->ndefs;
+    h->model_ksize.assign(m->filter_ksize, m->filter_ksize + m->nfilters);
+    const long long fbase = (long long)m->nbias + 4LL * m->ndefs;
+    long long len = fbase;
+    h->model_foff.assign(m->nfilters, 0);
+    for (int f = 0; f < m->nfilters; ++f) {
+        if (m->filter_offset[f] < 0) return fail(h, PBD_ERR_INVALID, "filter %d: negative filter_offset", f);
+        h->model_foff[f] = m->filter_offset[f];
+        len = std::max(len, fbase + m->filter_offset[f] + (long long)m->filter_ksize[f] * m->filter_ksize[f] * 32);
+    }
+    if (len > INT32_MAX) return fail(h, PBD_ERR_UNSUPPORTED, "model vector of %lld values (at most 2^31 - 1)", len);
+    h->mvec.assign((size_t)len * h->rs, 0);
+    auto put = [&](long long o, double v) {
+        if (h->f64) reinterpret_cast<double *>(h->mvec.data())[o] = v;
+        else reinterpret_cast<float *>(h->mvec.data())[o] = (float)v;
+    };
+    for (int b = 0; b < m->nbias; ++b) put(b, m->biasw[b]);
+    for (long long i = 0; i < 4LL * m->ndefs; ++i) put(m->nbias + i, m->defw[i]);
+    for (int f = 0; f < m->nfilters; ++f) {
+        const long long n = (long long)m->filter_ksize[f] * m->filter_ksize[f] * 32;
+        for (long long i = 0; i < n; ++i)
+            put(fbase + m->filter_offset[f] + i, h->f64 ? m->filters_f64[m->filter_offset[f] + i] : (double)m->filters_f32[m->filter_offset[f] + i]);
+    }
+    h->ex_hdr_words = 4 + 2 * (3 * h->max_parts - 1);
+    long long vmax = 0;
+    for (int c = 0; c < h->NC; ++c) {
+        long long v = 0;
+        for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp) {
+            int kmax = 0;
+            for (int gm = h->mix_offset[gp]; gm < h->mix_offset[gp + 1]; ++gm) kmax = std::max(kmax, m->filter_ksize[h->filterid[gm]]);
+            v += 1 + (gp > h->part_offset[c] ? 4 : 0) + (long long)kmax * kmax * 32;
+        }
+        vmax = std::max(vmax, v);
+    }
+    if (vmax > INT32_MAX / 2) return fail(h, PBD_ERR_UNSUPPORTED, "an example of %lld values", vmax);
+    h->ex_values = (int)((vmax + 3) / 4 * 4);
     return PBD_OK;
 }
 
@@ -1639,7 +1696,7 @@ int run_dp(pbd_handle *h, Plan &P, int nframes)
 // enqueues the find and walk kernels for the `nframes` frames of the device-resident DP result; the candidate list is
 // written to d_payload = int32[1 + capacity * stride] (see pbd_handle::CandBuf).  No host synchronisation.
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
-                   int capacity, hipStream_t st)
+                   int capacity, hipStream_t st, bool walk_only = false)
 {
     ArgminParams ap{};
     ap.lv = P.d_lv.p; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
@@ -1656,7 +1713,7 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     HIPCHK(h, h->find_blk.ensure((size_t)ap.nblk * sizeof(int)));
     ap.blk = h->find_blk.as<int>();
     ProfScope ps(h, PBD_K_ARGMIN, st);
-    launch_argmin_find(ap, h->f64, st);
+    if (!walk_only) launch_argmin_find(ap, h->f64, st);   // walk_only: the payload's records were written by the caller
     launch_argmin_walk(ap, h->f64, st);
     return PBD_OK;
 }
@@ -1966,7 +2023,8 @@ int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int 
 }
 
 // pyramid -> HOG -> convolution -> dynamic program of a mixed-size call that passed check_frames_mixed (no host synchronisation)
-int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host)
+int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
+                         const LatentParams *mask = nullptr)
 {
     h->res = Resident{&P, 1, cn, depth};
     const size_t es = depth_size(depth);
@@ -2001,6 +2059,13 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     HIPCHK(h, hipGetLastError());
     h->res.features = h->res.c31_zero = true;
     if (int rc = run_conv(h, P, 1)) return rc;
+    if (mask) {   // pbd_detect_latent: the responses of the latent bank, masked before the dynamic program
+        LatentParams lp = *mask;
+        lp.resp = h->resp.p; lp.lv = P.d_lv.p; lp.nlevels = P.nlevels; lp.F = h->F; lp.cell_per_frame = P.cell_per_frame;
+        lp.lv_frame = P.d_lv_frame.p; lp.scales = P.d_scales.p;
+        launch_latent_mask(lp, h->f64, h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
     return run_dp_mixed(h, P);
 }
 
@@ -2608,6 +2673,56 @@ bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
     if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return false;
     *bf = frame; *bl = level;
     return true;
+}
+
+// pbd_examples*: the resident result a record can be walked in (PBD_OK or the failure's status code)
+// the handle whose buffers hold the resident result: the latent twin after pbd_detect_latent
+pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->lat ? h->lat.get() : h; }
+
+int check_examples_state(pbd_handle *h)
+{
+    const Resident &r = resident_owner(h)->res;
+    if (!r.plan || (r.plan->kind != 0 && r.plan->kind != 2) || !r.features || !r.dp)
+        return fail(h, PBD_ERR_STATE, "no resident detect result (pbd_detect* computes one; pbd_dp_min and pbd_conv_set_filters leave none)");
+    if (!h->bank_matches_model || h->filter_ksize != h->model_ksize)
+        return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
+    return PBD_OK;
+}
+
+// the walk and the gather of min(max(word 0, 0), capacity) records of d_in into d_hdr / d_values, on the handle's stream
+int enqueue_examples(pbd_handle *h, const int32_t *d_in, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
+{
+    pbd_handle *o = resident_owner(h);   // its maps and features; the model tables (filter ids, offsets) stay this handle's
+    Plan &P = *o->res.plan;
+    if (!h->ex_gm.p) {
+        std::vector<ExGm> gm(h->totmix);
+        for (int i = 0; i < h->totmix; ++i) gm[i] = ExGm{h->filterid[i], h->biasid[i], h->defid[i], 0};
+        HIPCHK(h, h->ex_gm.upload(gm));
+        std::vector<int> anc(h->anchors);
+        anc.push_back(0);
+        HIPCHK(h, h->ex_anchors.upload(anc));
+        HIPCHK(h, h->ex_foff.upload(h->model_foff));
+    }
+    if (P.kind == 2 && !P.d_frame_lv0.p) HIPCHK(h, P.d_frame_lv0.upload(P.frame_lv0));
+    HIPCHK(h, h->ex_ws.ensure(std::max<size_t>((size_t)capacity * h->max_parts * sizeof(ExPart), 16)));
+    ExampleParams ep{};
+    ep.in = d_in; ep.in_cap = capacity; ep.stride = stride(h); ep.frame_offset = frame_offset;
+    ep.lv = P.d_lv.p; ep.nlevels = P.nlevels;
+    ep.nframes = P.kind == 2 ? P.mixed_frames : o->res.frames;
+    ep.frame_lv0 = P.kind == 2 ? P.d_frame_lv0.p : nullptr;
+    ep.cell_per_frame = P.cell_per_frame;
+    ep.NC = h->NC; ep.NS = h->NS; ep.NJ = h->totmix; ep.ptr8 = P.ptr8 ? 1 : 0; ep.flen = 32; ep.max_parts = h->max_parts;
+    ep.rooti = o->rooti.as<int>(); ep.IxRaw = o->IxRaw.p; ep.IyRaw = o->IyRaw.p; ep.Ik = o->Ik.as<uint8_t>();
+    ep.walk = h->d_walk.p; ep.walk_off = h->d_walk_off.p;
+    ep.gm = h->ex_gm.p; ep.anchors = h->ex_anchors.p; ep.foff = h->ex_foff.p; ep.nbias = h->nbias; ep.ndefs = h->ndefs;
+    ep.feat = o->feat.p;
+    ep.parts = h->ex_ws.as<ExPart>();
+    ep.hdr = d_hdr; ep.hdr_words = h->ex_hdr_words;
+    ep.values = d_values; ep.vstride = h->ex_values;
+    { ProfScope ps(h, PBD_K_EX_WALK, h->stream); launch_examples(ep, h->f64, 0, h->stream); }
+    { ProfScope ps(h, PBD_K_EX_GATHER, h->stream); launch_examples(ep, h->f64, 1, h->stream); }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
 }
 
 }  // namespace
@@ -3710,6 +3825,156 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
     });
 }
 
+// Training examples (matlab/detection/detect.m backtrack + qp_write).  See include/pbd.h.
+int pbd_model_vector_len(const pbd_handle *h) { return h ? (int)(h->mvec.size() / h->rs) : 0; }
+
+int pbd_model_vector(pbd_handle *h, void *w)
+{
+    return entry(h, w, kBusyOk, [&]() -> int {
+        memcpy(w, h->mvec.data(), h->mvec.size());
+        return PBD_OK;
+    });
+}
+
+int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values)
+{
+    if (!h || !hdr_words || !values) return PBD_ERR_INVALID;
+    *hdr_words = h->ex_hdr_words;
+    *values = h->ex_values;
+    return PBD_OK;
+}
+
+int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values)
+{
+    return entry(h, ncand <= 0 || (cand && hdr && values), kIdle, [&]() -> int {
+        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+        if (int rc = check_examples_state(h)) return rc;
+        const int stride = ::stride(h);
+        const Resident &res = resident_owner(h)->res;
+        const Plan &P = *res.plan;
+        for (int i = 0; i < ncand; ++i) {
+            const int32_t *r = cand + (size_t)i * stride;
+            const long long f = (long long)r[0] - frame_offset;
+            int bf = 0, bl = 0;
+            if (f < INT32_MIN || f > INT32_MAX || !resident_level(res, (int)f, r[2], &bf, &bl))
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d / level %d outside the resident result", i, r[0],
+                            frame_offset, r[2]);
+            const LevelDesc &d = P.lv[bl];
+            if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
+            if (r[3] < 0 || r[3] >= d.cols || r[4] < 0 || r[4] >= d.rows)
+                return fail(h, PBD_ERR_INVALID, "record %d: root (%d, %d) outside the %d x %d map of level %d%s", i, r[3], r[4], d.cols,
+                            d.rows, r[2], d.rows ? "" : " (a level of another rank)");
+        }
+        if (ncand == 0) return PBD_OK;
+        const size_t hb = (size_t)ncand * h->ex_hdr_words * sizeof(int32_t), vb = (size_t)ncand * h->ex_values * h->rs;
+        const size_t hb_al = (hb + 255) / 256 * 256;
+        HIPCHK(h, h->ex_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+        HIPCHK(h, h->ex_out.ensure(hb_al + vb));
+        HIPCHK(h, hipMemcpyAsync(h->ex_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->ex_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 h->stream));
+        int32_t *d_hdr = h->ex_out.as<int32_t>();
+        char *d_val = h->ex_out.as<char>() + hb_al;
+        if (int rc = enqueue_examples(h, h->ex_rec.as<int32_t>(), ncand, frame_offset, d_hdr, d_val)) return rc;
+        HIPCHK(h, hipMemcpyAsync(hdr, d_hdr, hb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(values, d_val, vb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+// Latent positives (matlab/detection/detect.m with a bbox: testoverlap masks, bbox.m fixed mixtures).  See include/pbd.h.
+int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
+                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
+{
+    return entry(h, frames && boxes && cand && found, kIdle, [&]() -> int {
+        if (h->shard_world > 1)
+            return fail(h, PBD_ERR_UNSUPPORTED, "latent detection with level sharding (world %d): the best root is over every level",
+                        h->shard_world);
+        const int nparts = h->part_offset[1] - h->part_offset[0];
+        for (int c = 1; c < h->NC; ++c)
+            if (h->part_offset[c + 1] - h->part_offset[c] != nparts)
+                return fail(h, PBD_ERR_UNSUPPORTED, "latent detection needs one part count in every component (component %d has %d, "
+                            "component 0 %d)", c, h->part_offset[c + 1] - h->part_offset[c], nparts);
+        if (h->resp_half) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection in PBD_CONV_MFMA_F16: -1e10 has no fp16 value");
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        if (int rc = check_bank(h)) return rc;
+        if (h->filter_ksize != h->model_ksize) return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's");
+        if (!h->lat) {   // the latent twin: the same model with one filter per (component, part, mixture), on this handle's stream
+            const int T = h->totmix;
+            std::vector<int> ks(T), fid(T);
+            std::vector<int64_t> off(T);
+            for (int gm = 0; gm < T; ++gm) {
+                fid[gm] = gm;
+                ks[gm] = h->model_ksize[h->filterid[gm]];
+                off[gm] = h->model_foff[h->filterid[gm]];
+            }
+            const size_t fbase = (size_t)h->nbias + 4 * (size_t)h->ndefs;
+            pbd_model m{};
+            m.ncomponents = h->NC; m.nfilters = T; m.flen = 32; m.filter_ksize = ks.data(); m.filter_offset = off.data();
+            if (h->f64) m.filters_f64 = reinterpret_cast<const double *>(h->mvec.data()) + fbase;
+            else m.filters_f32 = reinterpret_cast<const float *>(h->mvec.data()) + fbase;
+            m.nbias = h->nbias; m.biasw = h->biasw.data(); m.ndefs = h->ndefs; m.defw = h->defw.data(); m.anchors = h->anchors.data();
+            m.part_offset = h->part_offset.data(); m.parentid = h->parentid.data(); m.mix_offset = h->mix_offset.data();
+            m.filterid = fid.data(); m.biasid = h->biasid.data(); m.defid = h->defid.data();
+            m.thresh = h->thresh; m.sbin = h->sbin; m.interval = h->interval; m.norient = h->norient;
+            pbd_config cfg = h->cfg;
+            cfg.max_candidates = std::max(cfg.max_batch, 1);
+            cfg.stream = reinterpret_cast<void *>(h->stream.s);
+            pbd_handle *t = nullptr;
+            if (int rc = pbd_create(&m, &cfg, &t)) return fail(h, rc, "latent twin: %s", pbd_last_error(nullptr));
+            h->lat.reset(t);
+            std::vector<int4> gm(T);
+            for (int c = 0; c < h->NC; ++c)
+                for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)
+                    for (int g = h->mix_offset[gp]; g < h->mix_offset[gp + 1]; ++g)
+                        gm[g] = make_int4(gp - h->part_offset[c], g - h->mix_offset[gp], ks[g], 0);
+            HIPCHK(h, h->lat_gm.upload(gm));
+        }
+        pbd_handle *t = h->lat.get();
+        Plan *P = nullptr;
+        if (int rc = check_frames_mixed(t, nframes, frames, channels, depth_code, true, &P)) return fail(h, rc, "%s", t->err.c_str());
+        const size_t nb = (size_t)nframes * nparts;
+        HIPCHK(h, h->lat_in.ensure(nb * sizeof(int4) + nb * sizeof(int) + 64));
+        HIPCHK(h, hipMemcpyAsync(h->lat_in.p, boxes, nb * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        int *d_mix = reinterpret_cast<int *>(h->lat_in.as<char>() + nb * sizeof(int4));
+        if (mixtures) HIPCHK(h, hipMemcpyAsync(d_mix, mixtures, nb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (!P->d_frame_lv0.p) HIPCHK(h, P->d_frame_lv0.upload(P->frame_lv0));
+        const int stride = ::stride(h);
+        HIPCHK(h, h->lat_pay.ensure(((size_t)nframes * stride + 1) * sizeof(int32_t)));
+        h->res = Resident{};
+        h->res.latent = true;
+        LatentParams lp{};
+        lp.gmtab = h->lat_gm.p; lp.boxes = h->lat_in.as<int4>(); lp.mix = mixtures ? d_mix : nullptr; lp.nparts = nparts;
+        lp.overlap = (double)overlap;
+        if (int rc = enqueue_detect_mixed(t, *P, nframes, frames, channels, depth_code, true, &lp)) return fail(h, rc, "%s", t->err.c_str());
+        lp.rootv = t->rootv.p; lp.rooti = t->rooti.as<int>(); lp.lv = P->d_lv.p; lp.nlevels = P->nlevels;
+        lp.cell_per_frame = P->cell_per_frame; lp.frame_lv0 = P->d_frame_lv0.p; lp.nframes = nframes; lp.NC = h->NC;
+        lp.stride = stride; lp.payload = h->lat_pay.as<int32_t>();
+        launch_latent_best(lp, h->f64, h->stream);
+        if (int rc = enqueue_argmin(t, *P, 1, P->d_scales.p, 0, lp.payload, nframes, h->stream, true)) return fail(h, rc, "%s", t->err.c_str());
+        HIPCHK(h, hipMemcpyAsync(cand, lp.payload + 1, (size_t)nframes * stride * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+        for (int f = 0; f < nframes; ++f) {
+            float sc;
+            memcpy(&sc, &cand[(size_t)f * stride + 5], sizeof sc);
+            found[f] = sc > -5e9f ? 1 : 0;
+        }
+        return PBD_OK;
+    });
+}
+
+int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
+{
+    return entry(h, d_payload && (capacity <= 0 || (d_hdr && d_values)), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_examples_state(h)) return rc;
+        if (capacity == 0) return PBD_OK;
+        return enqueue_examples(h, d_payload, capacity, frame_offset, d_hdr, d_values);
+    });
+}
+
 int pbd_profile_enable(pbd_handle *h, int on)
 {
     return entry(h, true, kBusyOk, [&]() -> int {
@@ -3742,7 +4007,7 @@ const char *pbd_kernel_name(int k)
                                              "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear", "k_cl_grid_count",
                                              "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select",
                                              "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile",
-                                             "k_part_poses"};
+                                             "k_part_poses", "k_ex_walk", "k_ex_gather"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

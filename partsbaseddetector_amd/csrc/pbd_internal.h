@@ -559,4 +559,57 @@ struct PoseParams {
 };
 void launch_part_poses(const PoseParams &p, hipStream_t s);
 
+// training examples of records (pbd_examples*; pbd_kernels_examples.hip)
+struct ExPart {                   // one (example, part), written by the walk, read by the gather
+    long long cell;               // first cell of the part's level in `feat` (frame * cell_per_frame + cell_off)
+    long long dst;                // element offset of the filter block in `values`
+    int x, y, m, k;               // position, mixture and filter size (k = 0: no block)
+    int W, H, pad0, pad1;         // the level's feature map
+};
+struct ExGm { int filterid, biasid, defid, pad; };   // per (part, mixture) of the model
+struct ExampleParams {
+    const int32_t *in;            // payload: word 0 = records (negative: none), then the records
+    int in_cap, stride, frame_offset;
+    const LevelDesc *lv;
+    int nlevels, nframes;         // equal-size plans: frames of the batch
+    const int *frame_lv0;         // mixed plans: [nframes + 1] first virtual level of each frame (NULL: equal-size plan)
+    long long cell_per_frame;
+    int NC, NS, NJ, ptr8, flen, max_parts;
+    const int *rooti;
+    const void *IxRaw, *IyRaw; const uint8_t *Ik;   // see DpParams
+    const PartWalk *walk; const int *walk_off;
+    const ExGm *gm;
+    const int *anchors;           // [ndefs][2]
+    const long long *foff;        // [nfilters] offset of each filter in the model vector
+    int nbias, ndefs;
+    const void *feat;             // R [frames][cell_per_frame * flen]
+    ExPart *parts;                // [in_cap * max_parts] workspace
+    int32_t *hdr; int hdr_words;
+    void *values; int vstride;
+};
+void launch_examples(const ExampleParams &p, bool f64, int step, hipStream_t s);   // step 0: walk, 1: gather
+
+// latent positives (pbd_detect_latent; pbd_kernels_examples.hip).  The responses are those of the latent bank: one plane per
+// (component, part, mixture) = global mixture index gm, so a mask belongs to its (component, part, mixture).
+struct LatentParams {
+    void *resp;                   // R [cell_per_frame * F] of the call's virtual frame (mixed plan)
+    const LevelDesc *lv;
+    int nlevels, F;               // F = planes per cell block = (part, mixture) pairs of the model
+    long long cell_per_frame;
+    const int *lv_frame;          // virtual level -> frame of the call
+    const float *scales;          // [nlevels]
+    const int4 *gmtab;            // [F] {part index in its component, mixture, filter size, -}
+    const int4 *boxes;            // [nframes][nparts] ground truth {x1, y1, x2, y2}, inclusive
+    const int *mix;               // [nframes][nparts] fixed mixture or -1 (NULL: all free)
+    int nparts;
+    double overlap;
+    // the per-frame arg-max
+    const void *rootv; const int *rooti;
+    const int *frame_lv0;         // [nframes + 1]
+    int nframes, NC, stride;
+    int32_t *payload;             // word 0 = nframes, then one record per frame (as k_argmin_emit writes them, for the walk)
+};
+void launch_latent_mask(const LatentParams &p, bool f64, hipStream_t s);
+void launch_latent_best(const LatentParams &p, bool f64, hipStream_t s);
+
 }  // namespace pbd

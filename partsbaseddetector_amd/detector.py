@@ -316,6 +316,49 @@ class Handle:
     def _records(self, records) -> np.ndarray:
         return np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
 
+    def model_vector(self) -> np.ndarray:
+        """pbd_model_vector: w = [biasw | defw | filters] in T"""
+        w = np.zeros(self.lib.pbd_model_vector_len(self.h), self.dtype)
+        self.check(self.lib.pbd_model_vector(self.h, w.ctypes.data))
+        return w
+
+    def example_stride(self):
+        """pbd_example_stride: (int32 words of a header, values of T of an example)"""
+        a, b = C.c_int(), C.c_int()
+        self.check(self.lib.pbd_example_stride(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def examples(self, records: np.ndarray, frame_offset: int = 0):
+        """pbd_examples: (hdr (n, hdr_words) int32, values (n, values) T) of records (n, stride) of the last detect call"""
+        rec = self._records(records)
+        hw, vw = self.example_stride()
+        hdr = np.zeros((len(rec), hw), np.int32)
+        vals = np.zeros((len(rec), vw), self.dtype)
+        self.check(self.lib.pbd_examples(self.h, rec.ctypes.data if rec.size else None, len(rec), frame_offset,
+                                         hdr.ctypes.data if hdr.size else None, vals.ctypes.data if vals.size else None))
+        return hdr, vals
+
+    def detect_latent(self, frames, part_boxes, overlap: float, mixtures=None):
+        """pbd_detect_latent: (records (nframes, stride) int32, found (nframes,) int32) -- per frame the best root whose parts
+        overlap part_boxes[f][p] = (x1, y1, x2, y2) inclusive by more than `overlap`; mixtures[f][p]: fixed mixture or -1"""
+        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
+        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        boxes = np.ascontiguousarray(part_boxes, np.int32).reshape(len(fr), -1, 4)
+        mix = None if mixtures is None else np.ascontiguousarray(mixtures, np.int32).reshape(len(fr), boxes.shape[1])
+        if mix is not None and mix.shape != boxes.shape[:2]:
+            raise PbdError(-1, "one mixture per part box")
+        rec = np.zeros((len(fr), self.stride), np.int32)
+        found = np.zeros(len(fr), np.int32)
+        self.check(self.lib.pbd_detect_latent(self.h, len(fr), descs, fr[0].shape[2], _lib.DEPTH_CODE[fr[0].dtype], boxes.ctypes.data,
+                                              None if mix is None else mix.ctypes.data, float(overlap), rec.ctypes.data,
+                                              found.ctypes.data))
+        return rec, found
+
+    def examples_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
+        """pbd_examples_device: the examples of a device payload's records into int32[capacity * hdr_words] and
+        T[capacity * values] on the device; asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_examples_device(self.h, d_payload_ptr, capacity, frame_offset, d_hdr_ptr, d_values_ptr))
+
     def depth_consistency(self, depths: Sequence[np.ndarray], records: np.ndarray, zfactor: float = 0.03, frame_offset: int = 0,
                           capacity: Optional[int] = None) -> np.ndarray:
         """pbd_depth_consistency: the records (n, stride) that SearchSpacePruning::filterCandidatesByDepth keeps, in input order,
@@ -843,6 +886,44 @@ class PartsBasedDetector:
                                                        _lib.DEPTH_CODE[im.dtype], buf.ctypes.data, cap, C.byref(n)))
         self.features_._scales = self.hd.plan(rows, cols)["scales"]
         return self.hd.unpack_candidates(buf, n.value)
+
+    def modelVector(self) -> np.ndarray:
+        """the model vector w = [biasw | defw | filters] in T (include/pbd.h pbd_model_vector; Model.to_vector)"""
+        self._need()
+        return self.hd.model_vector()
+
+    def examples(self, candidates):
+        """training examples of candidates of the last detect call (Candidate objects or records (n, stride) int32), on the
+        device (pbd_examples): (hdr (n, hdr_words) int32, values (n, values) T).  examples.dot(hdr, values, w) gives w . x,
+        examples.densify(hdr, values, len(w)) the dense vectors."""
+        self._need()
+        if isinstance(candidates, np.ndarray):
+            rec = candidates
+        else:
+            cands = list(candidates)
+            rec = self.hd.pack_candidates(cands) if cands else np.zeros((0, self.hd.stride), np.int32)
+        return self.hd.examples(rec)
+
+    def examples_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
+        """pbd_examples_device on a device payload (as detect_batch_device_out / detect_frames_device_out leave it)"""
+        self._need()
+        self.hd.examples_device(d_payload_ptr, capacity, frame_offset, d_hdr_ptr, d_values_ptr)
+
+    def detectLatent(self, frames, part_boxes, overlap: float, mixtures=None):
+        """latent positives (matlab/detection/detect.m with a bbox) on the device (pbd_detect_latent): per frame the best-scoring
+        candidate whose every part p overlaps part_boxes[f][p] = (x1, y1, x2, y2) (inclusive) by more than `overlap`, with the
+        mixtures[f][p] >= 0 fixed.  Returns (candidates, found): one Candidate per frame, found[f] = False when no placement
+        passes (its candidate then scores below -5e9).  examples(candidates) afterwards gives the positives' feature vectors."""
+        self._need()
+        if isinstance(frames, np.ndarray) and frames.ndim in (2, 3) and (frames.ndim == 2 or frames.shape[2] in (1, 3)):
+            frames = [frames]
+        rec, found = self.hd.detect_latent(list(frames), part_boxes, overlap, mixtures)
+        return self.hd.unpack_candidates(rec.ravel(), len(rec)), found.astype(bool)
+
+    def exampleStride(self):
+        """(int32 words of an example's header, values of T of an example)"""
+        self._need()
+        return self.hd.example_stride()
 
     def boundingBoxes3D(self, candidates: Sequence[Candidate], depths, im_shapes) -> np.ndarray:
         """Candidate::boundingBox3D(im, depth) of every candidate, on the device (pbd_boxes3d): (n, 6) float64 rows

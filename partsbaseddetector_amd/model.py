@@ -87,6 +87,16 @@ class Model:
     def flatten(self) -> "FlatModel":
         return FlatModel(self)
 
+    def to_vector(self, dtype=np.float32) -> np.ndarray:
+        """the model vector w = [biasw | defw | filters] in T (pbd_model_vector, include/pbd.h)"""
+        from .examples import model_vector
+        return model_vector(self.flatten(), dtype)
+
+    def from_vector(self, w: np.ndarray) -> "Model":
+        """a copy of this model whose parameters are w (the inverse of to_vector; what distributeModel accepts)"""
+        from .examples import model_from_vector
+        return model_from_vector(self, w)
+
 
 class FlatModel:
     """Plain arrays in the layout both C interfaces take (include/pbd.h ``pbd_model`` and the
