@@ -30,6 +30,7 @@
 #define PBD_BIND_HPP_
 
 #include <stdint.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -394,6 +395,87 @@ inline void detect_batch(pbd_handle *h, const std::vector<typename Tr::Image> &i
         for (int w = 0; w < 8; ++w) reinterpret_cast<int32_t *>(&hd)[w] = r[w];
         Tr::candidate(candidates[hd.frame], hd, r + 8);
     }
+}
+
+// the training QP (pbd_qp_*): a failed call throws through Tr::fail with pbd_qp_last_error's text
+template <class Tr>
+inline void qp_check(pbd_qp *q, int rc)
+{
+    if (rc != PBD_OK) Tr::fail(rc, std::string("pbd: ") + pbd_qp_last_error(q));
+}
+
+template <class Tr>
+inline pbd_qp *qp_create(pbd_handle *h, int capacity, double C, double wpos)
+{
+    pbd_qp_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.capacity = capacity; cfg.C = C; cfg.wpos = wpos;
+    pbd_qp *q = NULL;
+    qp_check<Tr>(NULL, pbd_qp_create(h, &cfg, &q));
+    return q;
+}
+
+// qp_write of host examples (pbd_examples' hdr / values of handle h); ids: 5 int32 per example
+template <class Tr, typename T>
+inline int qp_add(pbd_qp *q, pbd_handle *h, const std::vector<int32_t> &hdr, const std::vector<T> &values,
+                  const std::vector<int32_t> &ids)
+{
+    int hw = 0, vw = 0;
+    check<Tr>(h, pbd_example_stride(h, &hw, &vw));
+    const size_t n = ids.size() / 5;
+    if (hdr.size() != n * (size_t)hw || values.size() != n * (size_t)vw)
+        Tr::fail(PBD_ERR_INVALID, "pbd: QP add: one header, one values row and five id words per example");
+    int taken = 0;
+    qp_check<Tr>(q, pbd_qp_add(q, h, (int)n, n ? &hdr[0] : NULL, n ? (const void *)&values[0] : NULL, n ? &ids[0] : NULL, &taken));
+    return taken;
+}
+
+template <class Tr>
+inline pbd_qp_info qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed)
+{
+    pbd_qp_info st;
+    memset(&st, 0, sizeof st);
+    qp_check<Tr>(q, pbd_qp_opt(q, tol, iter, seed, &st));
+    return st;
+}
+
+template <class Tr>
+inline pbd_qp_info qp_one(pbd_qp *q, const std::vector<int32_t> &order, uint64_t seed)
+{
+    pbd_qp_info st;
+    memset(&st, 0, sizeof st);
+    qp_check<Tr>(q, pbd_qp_one(q, order.empty() ? NULL : &order[0], (int)order.size(), seed, &st));
+    return st;
+}
+
+template <class Tr>
+inline pbd_qp_info qp_state(pbd_qp *q)
+{
+    pbd_qp_info st;
+    memset(&st, 0, sizeof st);
+    qp_check<Tr>(q, pbd_qp_state(q, &st, NULL, NULL, NULL));
+    return st;
+}
+
+template <class Tr>
+inline std::vector<double> qp_weights(pbd_qp *q)
+{
+    const pbd_qp_info st = qp_state<Tr>(q);
+    std::vector<double> w((size_t)st.len + 1);
+    qp_check<Tr>(q, pbd_qp_weights(q, &w[0]));
+    w.resize(w.size() - 1);
+    return w;
+}
+
+template <class Tr>
+inline std::vector<double> qp_scores(pbd_qp *q)
+{
+    const pbd_qp_info st = qp_state<Tr>(q);
+    std::vector<double> s((size_t)st.capacity + 1);
+    int n = 0;
+    qp_check<Tr>(q, pbd_qp_scores(q, &s[0], &n));
+    s.resize((size_t)n);
+    return s;
 }
 
 }  // namespace pbdbind

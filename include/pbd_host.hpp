@@ -524,6 +524,45 @@ public:
     }
 };
 
+// The training QP (include/pbd.h pbd_qp_*, matlab/learning/qp_*.m) over a device-resident example cache: created by
+// PartsBasedDetector::qp and independent of the detector afterwards (RAII; movable, not copyable).  Every call is synchronous.
+class QP {
+public:
+    explicit QP(pbd_qp *q = NULL) : q_(q) {}
+    ~QP() { if (q_) pbd_qp_destroy(q_); }
+    QP(QP &&o) : q_(o.q_) { o.q_ = NULL; }
+    QP &operator=(QP &&o) { std::swap(q_, o.q_); return *this; }
+    QP(const QP &) = delete;
+    QP &operator=(const QP &) = delete;
+    pbd_qp *get() const { return q_; }
+    // qp_write of examples of handle h (PartsBasedDetector::examples, handle()); ids: 5 words per example
+    // ({label, frame, level, root x, root y} is detect.m's); the number written
+    template <typename T>
+    int add(pbd_handle *h, const std::vector<int32_t> &hdr, const std::vector<T> &values, const std::vector<int32_t> &ids)
+    {
+        return pbdbind::qp_add<HostTraits<T> >(q_, h, hdr, values, ids);
+    }
+    void fix() { pbdbind::qp_check<HostTraits<float> >(q_, pbd_qp_fix(q_)); }
+    int prune()
+    {
+        int n = 0;
+        pbdbind::qp_check<HostTraits<float> >(q_, pbd_qp_prune(q_, &n));
+        return n;
+    }
+    // one pass; order: indices into the support-vector set (empty: the seeded order of include/pbd.h)
+    pbd_qp_info one(const std::vector<int32_t> &order = std::vector<int32_t>(), uint64_t seed = 0)
+    {
+        return pbdbind::qp_one<HostTraits<float> >(q_, order, seed);
+    }
+    pbd_qp_info opt(double tol = 0.05, int iter = 1000, uint64_t seed = 0) { return pbdbind::qp_opt<HostTraits<float> >(q_, tol, iter, seed); }
+    std::vector<double> weights() { return pbdbind::qp_weights<HostTraits<float> >(q_); }   // qp_w: the model vector
+    std::vector<double> scores() { return pbdbind::qp_scores<HostTraits<float> >(q_); }     // qp_scorepos
+    pbd_qp_info state() { return pbdbind::qp_state<HostTraits<float> >(q_); }
+
+private:
+    pbd_qp *q_;
+};
+
 template <typename T>
 class PartsBasedDetector {
     std::string name_;
@@ -759,6 +798,12 @@ public:
         pbdbind::check<HostTraits<T> >(h_, pbd_examples(h_, n ? &rec[0] : NULL, (int)n, 0, &hdr[0], &values[0]));
         hdr.resize(hdr.size() - 1);
         values.resize(values.size() - 1);
+    }
+    // a training QP of `capacity` examples of this detector's model layout (pbd_qp_create; Cpos = C * wpos, Cneg = C)
+    QP qp(int capacity, double C = 0.002, double wpos = 2.0)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "qp() before distributeModel()");
+        return QP(pbdbind::qp_create<HostTraits<T> >(h_, capacity, C, wpos));
     }
     // PointCloudClusterer::clusterObjects(cloud, bounding_boxes, object_clusters, object_centers) (:157-293) on the device
     // (pbd_cluster_objects): clusters[i] = the point indices of box i's kept cluster, ascending (gather the points from the

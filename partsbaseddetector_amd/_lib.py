@@ -28,7 +28,8 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_dp_root", "k_argmin", "k_camera_boxes", "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear",
            "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out",
            "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile", "k_part_poses",
-           "k_ex_walk", "k_ex_gather"]
+           "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
+           "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -43,7 +44,9 @@ SYMBOLS = [
     "pbd_cluster_objects_device", "pbd_remove_planes", "pbd_remove_planes_device", "pbd_depth_consistency",
     "pbd_depth_consistency_device", "pbd_suppress", "pbd_suppress_device", "pbd_candidate_mask", "pbd_candidate_mask_device",
     "pbd_part_poses", "pbd_part_poses_device", "pbd_model_vector_len", "pbd_model_vector", "pbd_example_stride", "pbd_examples",
-    "pbd_examples_device", "pbd_detect_latent",
+    "pbd_examples_device", "pbd_detect_latent", "pbd_qp_create", "pbd_qp_destroy", "pbd_qp_last_error", "pbd_qp_add",
+    "pbd_qp_add_device", "pbd_qp_fix", "pbd_qp_prune", "pbd_qp_one", "pbd_qp_opt", "pbd_qp_weights", "pbd_qp_scores", "pbd_qp_state",
+    "pbd_qp_entries",
 ]
 
 
@@ -121,6 +124,16 @@ def frame_array(descs):
     for i, (p, r, c, st) in enumerate(descs):
         arr[i].data, arr[i].rows, arr[i].cols, arr[i].stride_bytes = p, r, c, st
     return arr
+
+
+class CQpConfig(C.Structure):
+    _fields_ = [("capacity", C.c_int), ("C", C.c_double), ("wpos", C.c_double), ("stream", C.c_void_p), ("wreg", C.c_void_p),
+                ("w0", C.c_void_p), ("noneg", C.c_void_p), ("nnoneg", C.c_int)]
+
+
+class CQpInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "nsv", "nfix", "capacity", "len", "hdr_words", "values")] + \
+               [(n, C.c_double) for n in ("lb", "ub", "loss", "l")] + [(n, C.c_int) for n in ("lb_dropped", "passes", "converged", "pad")]
 
 
 class CConfig(C.Structure):
@@ -220,6 +233,22 @@ def load():
     lib.pbd_examples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pbd_detect_latent.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                       C.c_void_p, C.c_void_p]
+    lib.pbd_qp_create.argtypes = [C.c_void_p, C.POINTER(CQpConfig), C.POINTER(C.c_void_p)]
+    lib.pbd_qp_destroy.argtypes = [C.c_void_p]
+    lib.pbd_qp_destroy.restype = None
+    lib.pbd_qp_last_error.argtypes = [C.c_void_p]
+    lib.pbd_qp_last_error.restype = C.c_char_p
+    lib.pbd_qp_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.pbd_qp_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_void_p]
+    lib.pbd_qp_fix.argtypes = [C.c_void_p]
+    lib.pbd_qp_prune.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.pbd_qp_one.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(CQpInfo)]
+    lib.pbd_qp_opt.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.POINTER(CQpInfo)]
+    lib.pbd_qp_weights.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pbd_qp_scores.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.pbd_qp_state.argtypes = [C.c_void_p, C.POINTER(CQpInfo), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pbd_qp_entries.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

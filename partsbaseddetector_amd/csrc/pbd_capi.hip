@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <numeric>
@@ -4007,13 +4008,726 @@ const char *pbd_kernel_name(int k)
                                              "k_cl_crop_count", "k_cl_crop_scan", "k_cl_crop_scatter", "k_cl_clear", "k_cl_grid_count",
                                              "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select",
                                              "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile",
-                                             "k_part_poses", "k_ex_walk", "k_ex_gather"};
+                                             "k_part_poses", "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score",
+                                             "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
+                                             "k_qp_gather"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)
 {
     return entry(h, true, kBusyOk, [&]() -> int {
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// The training QP (matlab/learning/qp_*.m).  See include/pbd.h and DESIGN.md section 6i.  The kernels are in
+// pbd_kernels_qp.hip; the host keeps the ids, block tables and b of the entries (for the grouping, the refresh's entry lists
+// and l) and orders every call; all per-value work is on the device.
+struct pbd_qp {
+    std::string err;
+    int device = 0;
+    Stream stream;
+    int cap = 0, L = 0, V = 0, HW = 0, MB = 0, in_hw = 0;
+    uint64_t fp = 0;
+    double Cpos = 0, Cneg = 0;
+    DevBuf x, bm, hd, ids, b, d, a, sv, w, wraw, misc, stage, work, lc, scratch;
+    DevTable<double> wreg, w0;
+    DevTable<int> noneg, slot_of, slot_len;
+    std::vector<double> wreg_h, w0_h;
+    std::vector<int> slot_of_h, slot_len_h, slot_off_h;   // coordinate -> layout block; its length and offset
+    std::vector<int32_t> h_ids, h_hd;   // [n * 5], [n * HW]
+    std::vector<double> h_b;
+    int n = 0, nfix = 0, nnoneg = 0;
+    double lb = NAN, ub = NAN, loss = 0, l = 0, ww = 0;
+    bool have_lb = false;
+    int lb_dropped = 0, passes = 0, converged = 0;
+};
+
+namespace {
+
+constexpr size_t kQpPruneChunkBytes = size_t(256) << 20;   // prune's scratch: at most this much (or one entry) ...
+constexpr int kQpPruneChunkEntries = 256;                  // ... and at most this many entries per chunk
+
+int qp_fail(pbd_qp *q, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    try {
+        if (q) q->err = buf; else g_create_error = buf;
+    } catch (...) {
+    }
+    return code;
+}
+
+#define QPCHK(q, expr)                                                                              \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) {                                                                     \
+            (void)hipGetLastError();                                                                \
+            return qp_fail(q, e_ == hipErrorOutOfMemory ? PBD_ERR_NOMEM : PBD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
+                           hipGetErrorString(e_), __FILE__, __LINE__);                              \
+        }                                                                                           \
+    } while (0)
+
+template <class F>
+int qp_entry(pbd_qp *q, bool args_ok, F &&body) noexcept
+{
+    try {
+        if (!q || !args_ok) return PBD_ERR_INVALID;
+        (void)hipSetDevice(q->device);
+        return body();
+    } catch (const std::bad_alloc &) {
+        return qp_fail(q, PBD_ERR_NOMEM, "out of host memory");
+    } catch (const std::exception &e) {
+        return qp_fail(q, PBD_ERR_INVALID, "unexpected exception: %s", e.what());
+    } catch (...) {
+        return qp_fail(q, PBD_ERR_INVALID, "unexpected exception");
+    }
+}
+
+hipError_t qp_alloc(DevBuf &buf, size_t bytes)
+{
+    buf = DevBuf{};
+    const hipError_t e = hipMalloc(&buf.p, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) buf.size = std::max<size_t>(bytes, 16);
+    return e;
+}
+
+// the model-vector layout of a handle: every bias, deformation and filter block (offset, length), the example strides, and
+// its FNV-1a fingerprint
+struct QpLayout {
+    int L = 0, V = 0, in_hw = 0;
+    std::vector<std::pair<int, int> > blocks;
+    uint64_t fp = 0;
+};
+QpLayout qp_layout(const pbd_handle *h)
+{
+    QpLayout lay;
+    lay.L = (int)(h->mvec.size() / h->rs);
+    lay.V = h->ex_values;
+    lay.in_hw = h->ex_hdr_words;
+    for (int b = 0; b < h->nbias; ++b) lay.blocks.push_back({b, 1});
+    for (int d = 0; d < h->ndefs; ++d) lay.blocks.push_back({h->nbias + 4 * d, 4});
+    const long long fbase = (long long)h->nbias + 4LL * h->ndefs;
+    for (size_t f = 0; f < h->model_foff.size(); ++f)
+        lay.blocks.push_back({(int)(fbase + h->model_foff[f]), h->model_ksize[f] * h->model_ksize[f] * 32});
+    uint64_t v = 1469598103934665603ULL;
+    auto mix = [&](long long x) { for (int k = 0; k < 8; ++k) { v ^= (uint64_t)((x >> (8 * k)) & 0xff); v *= 1099511628211ULL; } };
+    mix(lay.L); mix(lay.V); mix(lay.in_hw); mix((long long)lay.blocks.size());
+    for (auto &b : lay.blocks) { mix(b.first); mix(b.second); }
+    lay.fp = v;
+    return lay;
+}
+
+QpCache qp_cache(pbd_qp *q)
+{
+    QpCache c{};
+    c.x = q->x.as<float>(); c.bm = q->bm.as<uint8_t>(); c.hd = q->hd.as<int32_t>(); c.ids = q->ids.as<int32_t>();
+    c.b = q->b.as<double>(); c.d = q->d.as<double>(); c.a = q->a.as<double>(); c.sv = q->sv.as<uint8_t>();
+    c.cap = q->cap; c.V = q->V; c.HW = q->HW; c.MB = q->MB;
+    c.w = q->w.as<double>(); c.wreg = q->wreg.p; c.w0 = q->w0.p;
+    c.noneg = q->noneg.p; c.nnoneg = q->nnoneg; c.L = q->L;
+    c.slot_of = q->slot_of.p; c.slot_len = q->slot_len.p;
+    return c;
+}
+
+// a header of pbd_examples' format: -1 marked invalid, 0 not a valid example for this layout, 1 valid
+int qp_header_ok(const pbd_qp *q, const int32_t *h)
+{
+    const int nb = h[2], nv = h[3];
+    if (nb == -1) return -1;
+    if (nb < 0 || nb > (q->in_hw - 4) / 2 || nb > q->MB || nv < 0 || nv > q->V) return 0;
+    long long tot = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int off = h[4 + 2 * b], len = h[5 + 2 * b];
+        if (off < 0 || off >= q->L) return 0;
+        const int s = q->slot_of_h[off];
+        if (s < 0 || q->slot_len_h[s] != len) return 0;
+        tot += len;
+    }
+    return tot == nv ? 1 : 0;
+}
+
+// the write of m examples already on the device (p's inputs set), then the host mirror of the new entries
+int qp_write(pbd_qp *q, QpWriteParams &p, bool f64, int *taken)
+{
+    p.c = qp_cache(q);
+    p.in_hw = q->in_hw; p.in_vs = q->V; p.n0 = q->n; p.Cpos = q->Cpos; p.Cneg = q->Cneg;
+    QPCHK(q, q->work.ensure((size_t)std::max(p.m, 1) * sizeof(int)));
+    p.slot = q->work.as<int>();
+    p.taken = q->misc.as<int>();
+    launch_qp_write(p, f64, q->stream);
+    QPCHK(q, hipGetLastError());
+    int t = 0;
+    QPCHK(q, hipMemcpyAsync(&t, p.taken, sizeof(int), hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    if (t < 0 || t > q->cap - q->n) return qp_fail(q, PBD_ERR_HIP, "the write reported %d entries", t);
+    const int n0 = q->n, n1 = q->n + t;
+    q->h_ids.resize((size_t)n1 * 5);
+    q->h_hd.resize((size_t)n1 * q->HW);
+    q->h_b.resize(n1);
+    if (t > 0) {
+        QPCHK(q, hipMemcpyAsync(&q->h_ids[(size_t)n0 * 5], q->ids.as<int32_t>() + (size_t)n0 * 5, (size_t)t * 5 * sizeof(int32_t),
+                                hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipMemcpyAsync(&q->h_hd[(size_t)n0 * q->HW], q->hd.as<int32_t>() + (size_t)n0 * q->HW,
+                                (size_t)t * q->HW * sizeof(int32_t), hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipMemcpyAsync(&q->h_b[n0], q->b.as<double>() + n0, (size_t)t * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
+    }
+    q->n = n1;
+    if (taken) *taken = t;
+    return PBD_OK;
+}
+
+// group numbers of the entries list[0..k) (ascending indices): equal ids share a group, groups numbered by first member
+std::vector<int> qp_groups(const pbd_qp *q, const std::vector<int> &list, int *ngroups)
+{
+    std::map<std::array<int32_t, 5>, int> seen;
+    std::vector<int> g(list.size());
+    for (size_t k = 0; k < list.size(); ++k) {
+        std::array<int32_t, 5> id;
+        for (int c = 0; c < 5; ++c) id[c] = q->h_ids[(size_t)list[k] * 5 + c];
+        auto it = seen.emplace(id, (int)seen.size()).first;
+        g[k] = it->second;
+    }
+    *ngroups = (int)seen.size();
+    return g;
+}
+
+// qp_refresh: w and l from a (lincomb's order), the clamps, lb
+int qp_refresh(pbd_qp *q)
+{
+    // every QP call works on q->stream (created non-blocking, or the caller's): the duals are read in its order, after all
+    // work queued before (prune's compaction in particular)
+    std::vector<double> a(q->n);
+    if (q->n) QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    std::vector<int> P;
+    for (int i = 0; i < q->n; ++i) if (a[i] > 0) P.push_back(i);
+    std::stable_sort(P.begin(), P.end(), [&](int u, int v) { return a[u] < a[v]; });
+    double l = 0.0;
+    for (int i : P) l = l + q->h_b[i] * a[i];
+    // the entries carrying each layout block, in P's order
+    const int nslots = (int)q->slot_len_h.size();
+    std::vector<std::vector<int2> > per(nslots);
+    for (int i : P) {
+        const int32_t *h = &q->h_hd[(size_t)i * q->HW];
+        for (int b = 0; b < h[0]; ++b) per[q->slot_of_h[h[2 + 3 * b]]].push_back(make_int2(i, h[4 + 3 * b]));
+    }
+    std::vector<QpTask> tasks;
+    std::vector<int2> ent;
+    for (int s = 0; s < nslots; ++s) {
+        if (per[s].empty()) continue;
+        const int begin = (int)ent.size();
+        ent.insert(ent.end(), per[s].begin(), per[s].end());
+        const int off = q->slot_off_h[s];
+        for (int c0 = 0; c0 < q->slot_len_h[s]; c0 += PBD_QP_LANES)
+            tasks.push_back(QpTask{off, c0, std::min(PBD_QP_LANES, q->slot_len_h[s] - c0), begin, (int)ent.size(), 0});
+    }
+    const size_t tb = (tasks.size() * sizeof(QpTask) + 255) / 256 * 256;
+    QPCHK(q, q->lc.ensure(tb + ent.size() * sizeof(int2) + 16));
+    if (!tasks.empty()) {
+        QPCHK(q, hipMemcpyAsync(q->lc.p, tasks.data(), tasks.size() * sizeof(QpTask), hipMemcpyHostToDevice, q->stream));
+        QPCHK(q, hipMemcpyAsync(q->lc.as<char>() + tb, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, q->stream));
+    }
+    QpLincombParams lp{};
+    lp.c = qp_cache(q);
+    lp.tasks = q->lc.as<QpTask>(); lp.ntasks = (int)tasks.size();
+    lp.ent = reinterpret_cast<const int2 *>(q->lc.as<char>() + tb);
+    lp.ww = q->misc.as<double>() + 1;
+    launch_qp_lincomb(lp, q->stream);
+    QPCHK(q, hipGetLastError());
+    double ww = 0;
+    QPCHK(q, hipMemcpyAsync(&ww, lp.ww, sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    const double lb = l - ww * 0.5;
+    if (q->have_lb && !(lb > q->lb - 1e-5)) q->lb_dropped = 1;
+    q->l = l; q->ww = ww; q->lb = lb; q->have_lb = true;
+    return PBD_OK;
+}
+
+// G = R(w . x) - b of every entry, then computeloss over the whole cache
+int qp_true_loss(pbd_qp *q, double *loss)
+{
+    QPCHK(q, q->work.ensure((size_t)std::max(q->n, 1) * sizeof(double)));
+    QpScoreParams sp{};
+    sp.c = qp_cache(q); sp.w = q->w.as<double>(); sp.first = 0; sp.count = q->n; sp.sub_b = 1; sp.scale = 1.0;
+    sp.out = q->work.as<double>();
+    launch_qp_score(sp, q->stream);
+    QPCHK(q, hipGetLastError());
+    std::vector<double> G(q->n);
+    if (q->n) QPCHK(q, hipMemcpyAsync(G.data(), sp.out, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    std::vector<int> all(q->n);
+    std::iota(all.begin(), all.end(), 0);
+    int ng = 0;
+    const std::vector<int> g = qp_groups(q, all, &ng);
+    std::vector<double> best(ng, 0.0);   // max(0, max slack) of every group
+    for (int i = 0; i < q->n; ++i) {
+        const double slack = -G[i];
+        if (slack > best[g[i]]) best[g[i]] = slack;
+    }
+    double s = 0.0;
+    for (int k = 0; k < ng; ++k) if (best[k] > 0) s = s + best[k];
+    *loss = s;
+    return PBD_OK;
+}
+
+uint64_t qp_splitmix64(uint64_t seed, uint64_t i)
+{
+    const uint64_t base = seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL;
+    uint64_t z = base + i * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+int qp_set_sv(pbd_qp *q, int count)
+{
+    if (count > 0) QPCHK(q, hipMemsetAsync(q->sv.p, 1, (size_t)count, q->stream));
+    return PBD_OK;
+}
+
+// qp_one: the pass over the support vectors, refresh, the fixed set's sv, lb and ub
+int qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed)
+{
+    std::vector<double> a(q->n);
+    std::vector<uint8_t> sv(q->n);
+    if (q->n) {
+        QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
+    }
+    std::vector<int> S;
+    for (int i = 0; i < q->n; ++i) if (sv[i]) S.push_back(i);
+    const int nsv = (int)S.size();
+    if (nsv == 0) return qp_fail(q, PBD_ERR_STATE, "no support vectors (empty cache)");
+    std::vector<int> perm(nsv);
+    if (order) {
+        if (norder != nsv) return qp_fail(q, PBD_ERR_INVALID, "order of %d indices, %d support vectors", norder, nsv);
+        std::vector<char> used(nsv, 0);
+        for (int k = 0; k < nsv; ++k) {
+            if (order[k] < 0 || order[k] >= nsv || used[order[k]]) return qp_fail(q, PBD_ERR_INVALID, "order is not a permutation of 0..%d", nsv - 1);
+            used[order[k]] = 1;
+            perm[k] = order[k];
+        }
+    } else {
+        std::vector<uint64_t> z(nsv);
+        for (int k = 0; k < nsv; ++k) z[k] = qp_splitmix64(seed, (uint64_t)k + 1);
+        std::iota(perm.begin(), perm.end(), 0);
+        std::stable_sort(perm.begin(), perm.end(), [&](int u, int v) { return z[u] < z[v]; });
+    }
+    int ng = 0;
+    const std::vector<int> gS = qp_groups(q, S, &ng);
+    std::vector<double> idC(ng, 0.0);
+    std::vector<int> idI(ng, -1);
+    for (int k = 0; k < nsv; ++k) {
+        idC[gS[k]] = idC[gS[k]] + a[S[k]];
+        if (a[S[k]] > 0) idI[gS[k]] = S[k];
+    }
+    std::vector<int> ord(nsv), gidx(nsv);
+    for (int k = 0; k < nsv; ++k) { ord[k] = S[perm[k]]; gidx[k] = gS[perm[k]]; }
+    // work: order, gidx (int), idC, err (double), idI (int)
+    const size_t o_ord = 0, o_g = o_ord + (size_t)nsv * 4, o_c = (o_g + (size_t)nsv * 4 + 7) / 8 * 8, o_e = o_c + (size_t)ng * 8,
+                 o_i = o_e + (size_t)ng * 8, tot = o_i + (size_t)ng * 4;
+    QPCHK(q, q->work.ensure(tot + 16));
+    char *wb = q->work.as<char>();
+    QPCHK(q, hipMemcpyAsync(wb + o_ord, ord.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
+    QPCHK(q, hipMemcpyAsync(wb + o_g, gidx.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
+    QPCHK(q, hipMemcpyAsync(wb + o_c, idC.data(), (size_t)ng * 8, hipMemcpyHostToDevice, q->stream));
+    QPCHK(q, hipMemsetAsync(wb + o_e, 0, (size_t)ng * 8, q->stream));
+    QPCHK(q, hipMemcpyAsync(wb + o_i, idI.data(), (size_t)ng * 4, hipMemcpyHostToDevice, q->stream));
+    QpPassParams pp{};
+    pp.c = qp_cache(q);
+    pp.order = reinterpret_cast<const int *>(wb + o_ord); pp.gidx = reinterpret_cast<const int *>(wb + o_g);
+    pp.nsteps = nsv; pp.ngroups = ng;
+    pp.idC = reinterpret_cast<double *>(wb + o_c); pp.err = reinterpret_cast<double *>(wb + o_e);
+    pp.idI = reinterpret_cast<int *>(wb + o_i);
+    pp.loss = q->misc.as<double>() + 2;
+    launch_qp_pass(pp, q->stream);
+    QPCHK(q, hipGetLastError());
+    double loss = 0;
+    QPCHK(q, hipMemcpyAsync(&loss, pp.loss, sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    if (int rc = qp_refresh(q)) return rc;
+    if (int rc = qp_set_sv(q, q->nfix)) return rc;
+    q->loss = loss;
+    q->ub = q->ww * 0.5 + loss;
+    return PBD_OK;
+}
+
+void qp_fill_state(const pbd_qp *q, pbd_qp_info *st, int nsv)
+{
+    if (!st) return;
+    *st = pbd_qp_info{};
+    st->n = q->n; st->nsv = nsv; st->nfix = q->nfix; st->capacity = q->cap; st->len = q->L; st->hdr_words = q->HW; st->values = q->V;
+    st->lb = q->lb; st->ub = q->ub; st->loss = q->loss; st->l = q->l;
+    st->lb_dropped = q->lb_dropped; st->passes = q->passes; st->converged = q->converged;
+}
+
+int qp_count_sv(pbd_qp *q, int *nsv)
+{
+    std::vector<uint8_t> sv(q->n);
+    if (q->n) QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+    QPCHK(q, hipStreamSynchronize(q->stream));
+    int k = 0;
+    for (uint8_t v : sv) k += v ? 1 : 0;
+    *nsv = k;
+    return PBD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbd_qp_create(const pbd_handle *h, const struct pbd_qp_config *cfg, pbd_qp **out)
+{
+    try {
+        if (!h || !cfg || !out) return qp_fail(nullptr, PBD_ERR_INVALID, "null argument");
+        *out = nullptr;
+        if (cfg->capacity <= 0) return qp_fail(nullptr, PBD_ERR_INVALID, "capacity %d (at least 1)", cfg->capacity);
+        const double C = cfg->C == 0 ? 0.002 : cfg->C, wpos = cfg->wpos == 0 ? 2.0 : cfg->wpos;
+        if (!(C > 0) || !std::isfinite(C) || !(wpos > 0) || !std::isfinite(wpos))
+            return qp_fail(nullptr, PBD_ERR_INVALID, "C %g and wpos %g must be finite and positive", cfg->C, cfg->wpos);
+        (void)hipSetDevice(h->cfg.device);
+        std::unique_ptr<pbd_qp> q(new pbd_qp);
+        q->device = h->cfg.device;
+        const QpLayout lay = qp_layout(h);
+        q->L = lay.L; q->V = lay.V; q->in_hw = lay.in_hw; q->fp = lay.fp;
+        q->MB = (lay.in_hw - 4) / 2;
+        if (q->MB > 256 || q->MB < 1) return qp_fail(nullptr, PBD_ERR_UNSUPPORTED, "examples of %d blocks (at most 256)", q->MB);
+        if (q->V % 4) return qp_fail(nullptr, PBD_ERR_INVALID, "example stride %d", q->V);
+        q->HW = 2 + 3 * q->MB;
+        q->cap = cfg->capacity;
+        q->Cpos = C * wpos; q->Cneg = C;
+        q->slot_of_h.assign(q->L, -1);
+        for (auto &b : lay.blocks) {
+            if (b.first < 0 || b.first + (long long)b.second > q->L)
+                return qp_fail(nullptr, PBD_ERR_INVALID, "layout block at %d of %d values outside w", b.first, b.second);
+            if (q->slot_of_h[b.first] < 0) {
+                q->slot_of_h[b.first] = (int)q->slot_len_h.size();
+                q->slot_len_h.push_back(b.second);
+                q->slot_off_h.push_back(b.first);
+            }
+        }
+        // model2vec's defaults in this vector order
+        q->wreg_h.assign(q->L, 1.0);
+        q->w0_h.assign(q->L, 0.0);
+        std::vector<int> nn;
+        if (cfg->wreg) q->wreg_h.assign(cfg->wreg, cfg->wreg + q->L);
+        else for (int c = 0; c < h->NC; ++c) q->wreg_h[h->biasid[h->mix_offset[h->part_offset[c]]]] = 0.01;
+        if (cfg->w0) q->w0_h.assign(cfg->w0, cfg->w0 + q->L);
+        else for (int d = 0; d < h->ndefs; ++d) { q->w0_h[h->nbias + 4 * d] = 0.01; q->w0_h[h->nbias + 4 * d + 2] = 0.01; }
+        if (cfg->noneg) {
+            if (cfg->nnoneg < 0) return qp_fail(nullptr, PBD_ERR_INVALID, "nnoneg %d", cfg->nnoneg);
+            for (int k = 0; k < cfg->nnoneg; ++k) {
+                if (cfg->noneg[k] < 0 || cfg->noneg[k] >= q->L) return qp_fail(nullptr, PBD_ERR_INVALID, "noneg index %d", cfg->noneg[k]);
+                nn.push_back(cfg->noneg[k]);
+            }
+        } else {
+            for (int d = 0; d < h->ndefs; ++d) { nn.push_back(h->nbias + 4 * d); nn.push_back(h->nbias + 4 * d + 2); }
+        }
+        for (int k = 0; k < q->L; ++k)
+            if (!std::isfinite(q->wreg_h[k]) || q->wreg_h[k] == 0 || !std::isfinite(q->w0_h[k]))
+                return qp_fail(nullptr, PBD_ERR_INVALID, "wreg / w0 at %d: %g / %g (finite, wreg nonzero)", k, q->wreg_h[k], q->w0_h[k]);
+        q->nnoneg = (int)nn.size();
+        if (cfg->stream) q->stream.borrow(reinterpret_cast<hipStream_t>(cfg->stream));
+        else QPCHK(nullptr, q->stream.create());
+        const size_t cap = (size_t)q->cap;
+        QPCHK(nullptr, qp_alloc(q->x, cap * q->V * sizeof(float)));
+        QPCHK(nullptr, qp_alloc(q->bm, cap * q->V));
+        QPCHK(nullptr, qp_alloc(q->hd, cap * q->HW * sizeof(int32_t)));
+        QPCHK(nullptr, qp_alloc(q->ids, cap * 5 * sizeof(int32_t)));
+        QPCHK(nullptr, qp_alloc(q->b, cap * sizeof(double)));
+        QPCHK(nullptr, qp_alloc(q->d, cap * sizeof(double)));
+        QPCHK(nullptr, qp_alloc(q->a, cap * sizeof(double)));
+        QPCHK(nullptr, qp_alloc(q->sv, cap));
+        QPCHK(nullptr, qp_alloc(q->w, (size_t)q->L * sizeof(double)));
+        QPCHK(nullptr, qp_alloc(q->wraw, (size_t)q->L * sizeof(double)));
+        QPCHK(nullptr, qp_alloc(q->misc, 4 * sizeof(double)));
+        QPCHK(nullptr, hipMemsetAsync(q->w.p, 0, (size_t)q->L * sizeof(double), q->stream));
+        QPCHK(nullptr, hipMemsetAsync(q->a.p, 0, cap * sizeof(double), q->stream));
+        QPCHK(nullptr, hipMemsetAsync(q->sv.p, 0, cap, q->stream));
+        QPCHK(nullptr, q->wreg.upload(q->wreg_h));
+        QPCHK(nullptr, q->w0.upload(q->w0_h));
+        if (!nn.empty()) QPCHK(nullptr, q->noneg.upload(nn));
+        QPCHK(nullptr, q->slot_of.upload(q->slot_of_h));
+        QPCHK(nullptr, q->slot_len.upload(q->slot_len_h));   // DevTable uploads are blocking copies
+        QPCHK(nullptr, hipStreamSynchronize(q->stream));
+        *out = q.release();
+        return PBD_OK;
+    } catch (const std::bad_alloc &) {
+        return qp_fail(nullptr, PBD_ERR_NOMEM, "out of host memory");
+    } catch (...) {
+        return qp_fail(nullptr, PBD_ERR_INVALID, "unexpected exception");
+    }
+}
+
+void pbd_qp_destroy(pbd_qp *q)
+{
+    if (!q) return;
+    (void)hipSetDevice(q->device);
+    (void)hipStreamSynchronize(q->stream);
+    delete q;
+}
+
+const char *pbd_qp_last_error(const pbd_qp *q) { return q ? q->err.c_str() : g_create_error.c_str(); }
+
+int pbd_qp_add(pbd_qp *q, const pbd_handle *h, int n, const int32_t *hdr, const void *values, const int32_t *ids, int *taken)
+{
+    return qp_entry(q, h && (n <= 0 || (hdr && values && ids)), [&]() -> int {
+        if (n < 0) return qp_fail(q, PBD_ERR_INVALID, "n %d", n);
+        if (qp_layout(h).fp != q->fp) return qp_fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
+        for (int e = 0; e < n; ++e)
+            if (qp_header_ok(q, hdr + (size_t)e * q->in_hw) == 0)
+                return qp_fail(q, PBD_ERR_INVALID, "example %d: a block that is not a block of the model vector, or bad counts", e);
+        if (taken) *taken = 0;
+        if (n == 0) return PBD_OK;
+        const size_t rs = h->rs;
+        const size_t hb = (size_t)n * q->in_hw * 4, vb = (size_t)n * q->V * rs, ib = (size_t)n * 5 * 4;
+        const size_t o_v = (hb + 255) / 256 * 256, o_i = o_v + (vb + 255) / 256 * 256;
+        QPCHK(q, q->stage.ensure(o_i + ib));
+        QPCHK(q, hipMemcpyAsync(q->stage.p, hdr, hb, hipMemcpyHostToDevice, q->stream));
+        QPCHK(q, hipMemcpyAsync(q->stage.as<char>() + o_v, values, vb, hipMemcpyHostToDevice, q->stream));
+        QPCHK(q, hipMemcpyAsync(q->stage.as<char>() + o_i, ids, ib, hipMemcpyHostToDevice, q->stream));
+        QpWriteParams p{};
+        p.in_hdr = q->stage.as<int32_t>();
+        p.in_values = q->stage.as<char>() + o_v;
+        p.in_ids = reinterpret_cast<const int32_t *>(q->stage.as<char>() + o_i);
+        p.m = n;
+        return qp_write(q, p, h->f64, taken);
+    });
+}
+
+int pbd_qp_add_device(pbd_qp *q, pbd_handle *h, const int32_t *d_payload, int capacity, const int32_t *d_hdr, const void *d_values,
+                      int label, int id_base, int32_t *d_taken)
+{
+    return qp_entry(q, h && d_payload && (capacity <= 0 || (d_hdr && d_values)), [&]() -> int {
+        if (capacity < 0) return qp_fail(q, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (qp_layout(h).fp != q->fp) return qp_fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
+        (void)hipSetDevice(q->device);
+        if (h->stream.s != q->stream.s) {   // the QP's stream waits for the handle's
+            Event ev;
+            QPCHK(q, hipEventCreateWithFlags(&ev.p, hipEventDisableTiming));
+            QPCHK(q, hipEventRecord(ev.p, h->stream));
+            QPCHK(q, hipStreamWaitEvent(q->stream, ev.p, 0));
+        }
+        QpWriteParams p{};
+        p.in_hdr = d_hdr; p.in_values = d_values; p.in_ids = nullptr;
+        p.payload = d_payload; p.rec_stride = ::stride(h); p.label = label; p.id_base = id_base;
+        p.m = capacity;
+        p.taken_user = d_taken;
+        if (capacity == 0) {
+            if (d_taken) QPCHK(q, hipMemsetAsync(d_taken, 0, sizeof(int32_t), q->stream));
+            QPCHK(q, hipStreamSynchronize(q->stream));
+            return PBD_OK;
+        }
+        return qp_write(q, p, h->f64, nullptr);
+    });
+}
+
+int pbd_qp_fix(pbd_qp *q)
+{
+    return qp_entry(q, true, [&]() -> int {
+        q->nfix = q->n;
+        if (int rc = qp_set_sv(q, q->n)) return rc;
+        QPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_prune(pbd_qp *q, int *n)
+{
+    return qp_entry(q, true, [&]() -> int {
+        q->lb_dropped = 0;
+        std::vector<double> a(q->n);
+        std::vector<uint8_t> sv(q->n);
+        if (q->n) {
+            QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+            QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+            QPCHK(q, hipStreamSynchronize(q->stream));
+        }
+        bool all = true;
+        for (uint8_t v : sv) all = all && v;
+        if (all) for (int i = 0; i < q->n; ++i) sv[i] = (a[i] > 0 || i < q->nfix) ? 1 : 0;
+        std::vector<int> I;
+        for (int i = 0; i < q->n; ++i) if (sv[i]) I.push_back(i);
+        const int n1 = (int)I.size();
+        if (n1 == 0) return qp_fail(q, PBD_ERR_STATE, "nothing to keep (empty cache)");
+        int first = 0;
+        while (first < n1 && I[first] == first) ++first;
+        // compaction in ascending chunks of at most `chunk` entries through a scratch buffer freed afterwards: a chunk's sources
+        // I[k] >= k lie at or past the chunk's own start and past every earlier chunk's destinations, so each chunk reads
+        // entries no earlier chunk has overwritten
+        const size_t V = q->V, HW = q->HW;
+        const size_t entry_bytes = V * 5 + HW * 4 + 20 + 3 * 8;
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)std::max(n1 - first, 1), kQpPruneChunkEntries),
+                                                                     kQpPruneChunkBytes / entry_bytes));
+        if (first < n1) {
+            const size_t c = (size_t)chunk;
+            const size_t o_x = 0, o_bm = o_x + c * V * 4, o_hd = (o_bm + c * V + 255) / 256 * 256, o_id = o_hd + c * HW * 4,
+                         o_b = (o_id + c * 20 + 255) / 256 * 256, o_d = o_b + c * 8, o_a = o_d + c * 8, tot = o_a + c * 8;
+            QPCHK(q, qp_alloc(q->scratch, tot));
+            QPCHK(q, q->work.ensure((size_t)(n1 - first) * sizeof(int)));
+            QPCHK(q, hipMemcpyAsync(q->work.p, &I[first], (size_t)(n1 - first) * sizeof(int), hipMemcpyHostToDevice, q->stream));
+            char *s = q->scratch.as<char>();
+            for (int k0 = first; k0 < n1; k0 += chunk) {
+                const size_t cnt = (size_t)std::min(chunk, n1 - k0), k = (size_t)k0;
+                QpGatherParams gp{};
+                gp.c = qp_cache(q); gp.src = q->work.as<int>() + (k0 - first); gp.count = (int)cnt; gp.dst0 = k0;
+                gp.x = reinterpret_cast<float *>(s + o_x); gp.bm = reinterpret_cast<uint8_t *>(s + o_bm);
+                gp.hd = reinterpret_cast<int32_t *>(s + o_hd); gp.ids = reinterpret_cast<int32_t *>(s + o_id);
+                gp.b = reinterpret_cast<double *>(s + o_b); gp.d = reinterpret_cast<double *>(s + o_d);
+                gp.a = reinterpret_cast<double *>(s + o_a);
+                launch_qp_gather(gp, q->stream);
+                QPCHK(q, hipGetLastError());
+                auto back = [&](void *dst, size_t off, size_t bytes) {
+                    return hipMemcpyAsync(dst, s + off, bytes, hipMemcpyDeviceToDevice, q->stream);
+                };
+                QPCHK(q, back(q->x.as<float>() + k * V, o_x, cnt * V * 4));
+                QPCHK(q, back(q->bm.as<uint8_t>() + k * V, o_bm, cnt * V));
+                QPCHK(q, back(q->hd.as<int32_t>() + k * HW, o_hd, cnt * HW * 4));
+                QPCHK(q, back(q->ids.as<int32_t>() + k * 5, o_id, cnt * 20));
+                QPCHK(q, back(q->b.as<double>() + k, o_b, cnt * 8));
+                QPCHK(q, back(q->d.as<double>() + k, o_d, cnt * 8));
+                QPCHK(q, back(q->a.as<double>() + k, o_a, cnt * 8));
+            }
+            QPCHK(q, hipStreamSynchronize(q->stream));
+            q->scratch = DevBuf{};
+        }
+        int nfix = 0;
+        for (int k = 0; k < n1; ++k) {
+            const int i = I[k];
+            if (i < q->nfix) ++nfix;
+            if (k != i) {
+                std::copy_n(&q->h_ids[(size_t)i * 5], 5, &q->h_ids[(size_t)k * 5]);
+                std::copy_n(&q->h_hd[(size_t)i * q->HW], q->HW, &q->h_hd[(size_t)k * q->HW]);
+                q->h_b[k] = q->h_b[i];
+            }
+        }
+        q->h_ids.resize((size_t)n1 * 5); q->h_hd.resize((size_t)n1 * q->HW); q->h_b.resize(n1);
+        q->n = n1; q->nfix = nfix;
+        if (q->cap > n1) QPCHK(q, hipMemsetAsync(q->sv.as<uint8_t>() + n1, 0, (size_t)(q->cap - n1), q->stream));
+        if (int rc = qp_set_sv(q, n1)) return rc;
+        if (int rc = qp_refresh(q)) return rc;
+        if (n) *n = n1;
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed, struct pbd_qp_info *state)
+{
+    return qp_entry(q, true, [&]() -> int {
+        q->lb_dropped = 0;
+        if (int rc = qp_one(q, order, norder, seed)) return rc;
+        q->passes = 1; q->converged = 0;
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed, struct pbd_qp_info *state)
+{
+    return qp_entry(q, true, [&]() -> int {
+        if (std::isnan(tol)) return qp_fail(q, PBD_ERR_INVALID, "tol is NaN");
+        if (iter < 0) return qp_fail(q, PBD_ERR_INVALID, "iter %d", iter);
+        if (q->n == 0) return qp_fail(q, PBD_ERR_STATE, "empty cache");
+        q->lb_dropped = 0; q->passes = 0; q->converged = 0;
+        if (int rc = qp_refresh(q)) return rc;
+        double loss = 0;
+        if (int rc = qp_true_loss(q, &loss)) return rc;
+        double ub = q->ww * 0.5 + loss;
+        if (int rc = qp_set_sv(q, q->n)) return rc;
+        for (int t = 0; t < iter; ++t) {
+            if (int rc = qp_one(q, nullptr, 0, seed + (uint64_t)t)) return rc;
+            q->passes = t + 1;
+            const double lb = q->lb, ub_est = ub < q->ub ? ub : q->ub;
+            if (lb > 0 && 1 - lb / ub_est < tol) {
+                if (int rc = qp_true_loss(q, &loss)) return rc;
+                const double u = q->ww * 0.5 + loss;
+                ub = u < ub ? u : ub;
+                if (1 - lb / ub < tol) { q->converged = 1; break; }
+                if (int rc = qp_set_sv(q, q->n)) return rc;
+            }
+        }
+        q->ub = ub;
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_weights(pbd_qp *q, double *w)
+{
+    return qp_entry(q, w != nullptr, [&]() -> int {
+        std::vector<double> v(q->L);
+        QPCHK(q, hipMemcpyAsync(v.data(), q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
+        for (int k = 0; k < q->L; ++k) w[k] = v[k] / q->wreg_h[k] + q->w0_h[k];
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_scores(pbd_qp *q, double *s, int *n)
+{
+    return qp_entry(q, s && n, [&]() -> int {
+        std::vector<int> pos;
+        for (int i = 0; i < q->n; ++i) if (q->h_ids[(size_t)i * 5] > 0) pos.push_back(i);
+        *n = (int)pos.size();
+        if (pos.empty()) return PBD_OK;
+        const size_t o_o = ((size_t)pos.size() * 4 + 255) / 256 * 256;
+        QPCHK(q, q->work.ensure(o_o + pos.size() * 8));
+        QPCHK(q, hipMemcpyAsync(q->work.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, q->stream));
+        QpCache c = qp_cache(q);
+        launch_qp_wraw(c, q->wraw.as<double>(), q->stream);
+        QpScoreParams sp{};
+        sp.c = c; sp.w = q->wraw.as<double>(); sp.list = q->work.as<int>(); sp.count = (int)pos.size(); sp.sub_b = 0; sp.scale = q->Cpos;
+        sp.out = reinterpret_cast<double *>(q->work.as<char>() + o_o);
+        launch_qp_score(sp, q->stream);
+        QPCHK(q, hipGetLastError());
+        QPCHK(q, hipMemcpyAsync(s, sp.out, pos.size() * 8, hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_state(pbd_qp *q, struct pbd_qp_info *state, double *a, uint8_t *sv, double *w)
+{
+    return qp_entry(q, true, [&]() -> int {
+        if (a && q->n) QPCHK(q, hipMemcpyAsync(a, q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        if (sv && q->n) QPCHK(q, hipMemcpyAsync(sv, q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+        if (w) QPCHK(q, hipMemcpyAsync(w, q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values, double *b, double *d, int32_t *ids)
+{
+    return qp_entry(q, true, [&]() -> int {
+        if (first < 0 || count < 0 || (long long)first + count > q->n)
+            return qp_fail(q, PBD_ERR_INVALID, "entries %d..%d of %d", first, first + count - 1, q->n);
+        const size_t f = first, c = count;
+        if (c == 0) return PBD_OK;
+        if (hdr) QPCHK(q, hipMemcpyAsync(hdr, q->hd.as<int32_t>() + f * q->HW, c * q->HW * 4, hipMemcpyDeviceToHost, q->stream));
+        if (values) QPCHK(q, hipMemcpyAsync(values, q->x.as<float>() + f * q->V, c * q->V * 4, hipMemcpyDeviceToHost, q->stream));
+        if (b) QPCHK(q, hipMemcpyAsync(b, q->b.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
+        if (d) QPCHK(q, hipMemcpyAsync(d, q->d.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
+        if (ids) QPCHK(q, hipMemcpyAsync(ids, q->ids.as<int32_t>() + f * 5, c * 20, hipMemcpyDeviceToHost, q->stream));
+        QPCHK(q, hipStreamSynchronize(q->stream));
         return PBD_OK;
     });
 }

@@ -612,4 +612,60 @@ struct LatentParams {
 void launch_latent_mask(const LatentParams &p, bool f64, hipStream_t s);
 void launch_latent_best(const LatentParams &p, bool f64, hipStream_t s);
 
+// the training QP (pbd_qp_*; pbd_kernels_qp.hip).  One cache entry i: x[i * V ..] float values in stored block order, bm[i * V ..]
+// the block of every value, hd[i * HW ..] = {nblocks, nvalues, (offset in w, length, first value) x nblocks}, ids[i * 5 ..],
+// b, d, a (double) and sv (uint8).  Every kernel runs PBD_QP_LANES threads per workgroup (the lanes of the header's reduction).
+struct QpCache {
+    float *x; uint8_t *bm; int32_t *hd; int32_t *ids;
+    double *b, *d, *a; uint8_t *sv;
+    int cap, V, HW, MB;           // capacity, values per entry, header words, most blocks of an entry (<= 256)
+    double *w; const double *wreg, *w0;
+    const int *noneg; int nnoneg, L;
+    const int *slot_of;           // [L] the layout block starting at a coordinate, -1 elsewhere
+    const int *slot_len;          // [layout blocks] its length
+};
+struct QpWriteParams {
+    QpCache c;
+    const int32_t *in_hdr; const void *in_values; int in_hw, in_vs;   // pbd_examples' format and strides
+    const int32_t *in_ids;        // [m][5] (pbd_qp_add), or NULL: ids from the payload's records
+    const int32_t *payload; int rec_stride, label, id_base;          // pbd_qp_add_device
+    int m, n0;                    // examples of the call (payload: its capacity), entries before the call
+    double Cpos, Cneg;
+    int *slot;                    // [m] entry of each example, -1: skipped
+    int *taken; int32_t *taken_user;
+};
+void launch_qp_write(const QpWriteParams &p, bool f64, hipStream_t s);
+struct QpPassParams {
+    QpCache c;
+    const int *order, *gidx;      // [nsteps] entry and group of every step
+    int nsteps, ngroups;
+    double *idC; int *idI; double *err;   // [ngroups]
+    double *loss;                 // out: the sum of err in group order
+};
+void launch_qp_pass(const QpPassParams &p, hipStream_t s);
+struct QpScoreParams {
+    QpCache c;
+    const double *w;              // the weights scored
+    const int *list; int first, count;   // entries list[k] (NULL: first + k)
+    int sub_b; double scale;      // out[k] = sub_b ? R(w . x) - b : R(w . x) / scale
+    double *out;
+};
+void launch_qp_score(const QpScoreParams &p, hipStream_t s);
+struct QpTask { int off, c0, n, begin, end, pad; };   // lincomb: coordinates off + c0 .. + n of one layout block
+struct QpLincombParams {
+    QpCache c;
+    const QpTask *tasks; int ntasks;
+    const int2 *ent;              // {entry, first value of the block in the entry}, ascending a within a task's range
+    double *ww;                   // out (k_qp_norm): R(w . w) after the non-negativity clamps
+};
+void launch_qp_lincomb(const QpLincombParams &p, hipStream_t s);   // w = 0, the sums, the clamps and R(w . w)
+void launch_qp_norm(const QpLincombParams &p, hipStream_t s);      // the clamps and R(w . w) only
+void launch_qp_wraw(const QpCache &c, double *out, hipStream_t s);   // out = w + w0 .* wreg
+struct QpGatherParams {
+    QpCache c;
+    const int *src; int count, dst0;    // entry src[k] -> dst0 + k
+    float *x; uint8_t *bm; int32_t *hd; int32_t *ids; double *b, *d, *a;   // scratch of `count` entries
+};
+void launch_qp_gather(const QpGatherParams &p, hipStream_t s);
+
 }  // namespace pbd

@@ -920,6 +920,14 @@ class PartsBasedDetector:
         rec, found = self.hd.detect_latent(list(frames), part_boxes, overlap, mixtures)
         return self.hd.unpack_candidates(rec.ravel(), len(rec)), found.astype(bool)
 
+    def qp(self, capacity: int, C: float = 0.002, wpos: float = 2.0, **kw):
+        """a training QP (include/pbd.h pbd_qp_*) over a device-resident cache of `capacity` examples of this detector's model
+        layout; Cpos = C * wpos, Cneg = C; wreg / w0 / noneg / stream as keywords (None: model2vec's defaults).  It outlives the
+        detector.  See partsbaseddetector_amd.qp.QP."""
+        self._need()
+        from .qp import QP
+        return QP(self.hd, capacity, C, wpos, **kw)
+
     def exampleStride(self):
         """(int32 words of an example's header, values of T of an example)"""
         self._need()
