@@ -1,105 +1,36 @@
-// pbd_capi.hip -- handle, plans, device workspace and the C entry points of include/pbd.h.
+// pbd_capi.hip -- create / destroy, plans, model tables, the detect stages and their C entry points (include/pbd.h), profiling
+// and the debug entry points.  The handle and the layer every entry point is written on: pbd_handle.h; the entry points that
+// work on a finished candidate list: pbd_capi_post.hip; training: pbd_capi_train.hip.
 //
 // Host logic restated from the reference for this path:
 //   pyramid geometry            src/HOGFeatures.cpp:95-127, include/HOGFeatures.hpp:74-81
 //   engine wiring               src/PartsBasedDetector.cpp:69-127
 //   Parts index tables          include/Parts.hpp:172-187
 // There is no CPU compute path: every stage runs as a HIP kernel (pbd_kernels_*.hip).
-#include "pbd_internal.h"
-
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <array>
-#include <map>
-#include <memory>
-#include <numeric>
-#include <new>
-#include <set>
-#include <stdexcept>
-#include <type_traits>
-#include <utility>
+#include "pbd_handle.h"
 
 using namespace pbd;
 
 namespace pbd {
 thread_local ProfHook *g_prof_hook = nullptr;
-}
-
-namespace {
-
 thread_local std::string g_create_error;
 
-// Move-only owner of one HIP resource: device memory (Free = hipFree), pinned host memory (hipHostFree), an event or a
-// stream.  `size` is the bytes or elements held (memory only).  The destructor frees the resource and ignores HIP errors:
-// nothing is left to report them to.
-template <typename T, auto Free>
-struct Owned {
-    T *p = nullptr;
-    size_t size = 0;
-    Owned() = default;
-    Owned(Owned &&o) noexcept { swap(o); }
-    Owned &operator=(Owned o) noexcept { swap(o); return *this; }   // `o` takes the old resource away and frees it
-    ~Owned() { if (p) (void)Free(p); }
-    void swap(Owned &o) noexcept { std::swap(p, o.p); std::swap(size, o.size); }
-};
-using Event = Owned<std::remove_pointer_t<hipEvent_t>, hipEventDestroy>;
-
-struct DevBuf : Owned<void, hipFree> {   // grow-only device workspace; growing does not keep the contents
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= size) return hipSuccess;
-        *this = DevBuf{};
-        const size_t want = bytes + bytes / 8 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) size = want;
-        return e;
+int fail(ErrCtx *h, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    try {
+        if (h) h->err = buf; else g_create_error = buf;
+    } catch (...) {   // the message itself could not be stored: the status code still goes out
     }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
+    return code;
+}
+}  // namespace pbd
 
-struct HostBuf : Owned<void, hipHostFree> {   // grow-only pinned host memory: below `bytes`, reallocated to `want`
-    hipError_t ensure(size_t bytes, size_t want)
-    {
-        if (bytes <= size) return hipSuccess;
-        *this = HostBuf{};
-        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) size = want;
-        return e;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
-template <typename T>
-struct DevTable : Owned<T, hipFree> {   // small immutable table uploaded once; `size` elements
-    hipError_t upload(const std::vector<T> &h)
-    {
-        *this = DevTable{};
-        if (h.empty()) return hipSuccess;
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&this->p), h.size() * sizeof(T));
-        if (e != hipSuccess) return e;
-        this->size = h.size();
-        return hipMemcpy(this->p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
-// A stream created here (and destroyed with its owner), or one borrowed from the caller (pbd_config.stream)
-struct Stream {
-    Owned<std::remove_pointer_t<hipStream_t>, hipStreamDestroy> own;   // null when borrowed
-    hipStream_t s = nullptr;
-    hipError_t create()
-    {
-        const hipError_t e = hipStreamCreateWithFlags(&own.p, hipStreamNonBlocking);
-        s = own.p;
-        return e;
-    }
-    void borrow(hipStream_t b) { s = b; }
-    operator hipStream_t() const { return s; }
-};
+namespace {
 
 // ---- pyramid geometry (host) -------------------------------------------------------------------
 // Overload resolution assumed for the reference's expressions: C++11 <cmath>, i.e. pow(float,float)
@@ -135,368 +66,6 @@ inline short sat_short_round(float v)
     long iv = lrint((double)v);
     return (short)(iv < -32768 ? -32768 : iv > 32767 ? 32767 : iv);
 }
-
-struct Plan {
-    // key
-    int kind = 0;   // 0: from image size, 1: from explicit feature-map sizes, 2: mixed sizes (below), 3: a group of a mixed plan's
-                    // frames for the dynamic program, 4: only the suppression's canvas tables of a list of frame sizes (pbd_suppress*)
-    int rows = 0, cols = 0;         // the geometry does not depend on the channel count (offsets are in pixels)
-    std::vector<int> key_dims;
-    // geometry
-    int nlevels = 0;
-    std::vector<LevelDesc> lv;
-    std::vector<float> scales;
-    long long pix_per_frame = 0, blk_per_frame = 0, cell_per_frame = 0, npix_resized = 0, quad_per_frame = 0;
-    int interval = 0;
-    int nrows_flat = 0, ncols_flat = 0;
-    bool ptr8 = false;              // no feature map side exceeds 256: positions fit uint8 (back-pointer planes at half the bytes)
-    int longest = 0;                // longest side of any feature map of the plan (rows / columns of the distance transform)
-    int ntiles = 0;
-    // device tables
-    DevTable<LevelDesc> d_lv;
-    DevTable<ResizeTabX> d_tabx;
-    DevTable<ResizeTabY> d_taby;
-    DevTable<ResizeTabXf> d_tabxf;   // the same mapping with float coefficients (16U / 32F / 64F images)
-    DevTable<ResizeTabYf> d_tabyf;
-    DevTable<ConvTile> d_tiles, d_shaped, d_htiles;
-    int nshaped[3] = {0, 0, 0}, nhtiles = 0;
-    // strip-sequence tiles of the exact 5 x 5 convolution, per number of frames in a launch (built on first use)
-    std::map<int, DevTable<ConvSegTile>> segtiles;
-    DevTable<int> d_row2level, d_rowoff, d_col2level, d_coloff;
-    DevTable<long long> d_stk_row_off, d_stk_col_off;
-    long long stk_per_jf = 0;
-    DevTable<float> d_scales;
-    // host copies of the resize tables (image plans): mixed plans are assembled from them
-    std::vector<ResizeTabX> htabx;
-    std::vector<ResizeTabY> htaby;
-    std::vector<ResizeTabXf> htabxf;
-    std::vector<ResizeTabYf> htabyf;
-
-    // ---- kind 2: a mixed-size call planned as ONE virtual frame whose level table is the frames' own pyramids, concatenated
-    // frame-major (key_dims = rows, cols of every frame in call order).  Every stage after the pyramid runs over it unchanged.
-    int mixed_frames = 0;
-    std::vector<int> lv_frame, lv_local;    // per virtual level: frame of the call, level of that frame's pyramid
-    std::vector<int> frame_lv0;             // [mixed_frames + 1] first virtual level of each frame
-    DevTable<int> d_lv_frame, d_lv_local;
-    // pyramid launches: launch 0 = every frame's resized levels, launch k >= 1 = octave k of every frame; launch k's levels are
-    // run_lev[lev0[k] ..], its n[k] + 1 pixel offsets run_off[off0[k] ..]
-    std::vector<int> run_lev, run_lev0, run_n;
-    std::vector<long long> run_off, run_off0, run_npix;
-    DevTable<int> d_run_lev;
-    DevTable<long long> d_run_off;
-    // post-processing: per frame {rows, cols}, global-canvas word offset; the frames of each canvas kind
-    std::vector<int2> fdim;
-    std::vector<long long> fcanvas;
-    std::vector<int> post_lds, post_glb;
-    size_t post_lds_words = 0, post_glb_words = 0;
-    DevTable<int2> d_fdim;
-    DevTable<long long> d_fcanvas;
-    DevTable<int> d_post_lds, d_post_glb;
-    DevTable<int> d_frame_lv0;              // frame_lv0 on the device (pbd_examples*, uploaded on first use)
-    // dynamic program in groups of whole frames when the virtual frame's scratch exceeds the budget: sub-plans whose cell
-    // offsets start at 0 (cell0 = the group's first cell in the virtual frame), built for `chunk_budget`
-    size_t chunk_budget = 0;
-    std::vector<std::unique_ptr<Plan>> chunk_plans;
-    std::vector<long long> chunk_cell0;
-};
-
-struct Group {   // DT jobs of the parts of one tree depth + combine jobs of their parents
-    std::vector<DtJob> jobs;
-    std::vector<ChildDesc> childs;
-    std::vector<CombineJob> cjobs;
-    std::vector<SeqCombineJob> sjobs;     // sequential schedule (shared filter ids): replaces childs / cjobs
-    DevTable<DtJob> d_jobs;
-    int bz_x = 0, bz_y = 0;               // all jobs: linear coefficient exactly -0.0 and a != 0 (DpParams::bz_x / bz_y)
-    DevTable<ChildDesc> d_childs;
-    DevTable<CombineJob> d_cjobs;
-    DevTable<SeqCombineJob> d_sjobs;
-};
-
-struct Prof {
-    int on = 0;                      // 0: off, 1: every kernel, 2: the convolution only (pbd_profile_enable)
-    struct Rec { int k; Event a, b; };
-    std::vector<Rec> recs;
-    std::vector<Event> pool;
-    double total[PBD_K_COUNT] = {0};
-    int launches[PBD_K_COUNT] = {0};
-    Event get()
-    {
-        Event e;
-        if (pool.empty()) { (void)hipEventCreate(&e.p); return e; }
-        e = std::move(pool.back());
-        pool.pop_back();
-        return e;
-    }
-    void flush()
-    {
-        for (auto &r : recs) {
-            (void)hipEventSynchronize(r.b.p);
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r.a.p, r.b.p) == hipSuccess) { total[r.k] += ms; launches[r.k] += 1; }
-            pool.push_back(std::move(r.a)); pool.push_back(std::move(r.b));
-        }
-        recs.clear();
-    }
-};
-
-// What the last computation left on the device, for the entry points that read it back.  An entry point replaces the
-// record where it starts enqueueing (after every check), so a refused call leaves the previous result readable.
-struct Resident {
-    Plan *plan = nullptr;
-    int frames = 0, cn = 3, depth = kDepth8U;   // frames, channels and image depth of the pyramid
-    bool features = false, resp = false, dp = false;   // the stages held, all for `plan`
-    bool c31_zero = false;           // the features were written by the HOG kernels (channel 31 = 0), not uploaded by the caller
-    bool latent = false;             // pbd_detect_latent: the result lives in the handle's latent twin (pbd_examples* read it there)
-    void drop_conv() { resp = dp = false; }   // the filter bank changed
-    void clear() { *this = Resident{}; }
-};
-
-}  // namespace
-
-struct pbd_handle {
-    pbd_config cfg{};
-    std::string err;
-    Stream stream;                   // every kernel of the handle
-
-    // model (host copies)
-    int NC = 0, F = 0, flen = 32, sbin = 4, interval = 10, norient = 18, NS = 0, NM = 0, max_parts = 0;
-    float thresh = 0.f;
-    int ksize = 0, Fpad = 0;
-    std::vector<int> filter_ksize, part_offset, parentid, mix_offset, filterid, biasid, defid, ptr_slot, anchors;
-    std::vector<float> biasw, defw;
-    std::vector<Group> groups;       // deepest first
-    std::vector<RootJob> rjobs;
-    std::vector<PartWalk> walk;
-    std::vector<int> walk_off;
-    int JGmax = 0;
-    int max_mix = 1;                 // largest number of mixtures of any part
-    bool filters_set = false;
-    bool seq_mode = false;           // a filter id occurs twice inside a component: sequential schedule, accumulators keyed by filter id
-    bool bank_matches_model = true;  // false after a setFilters() whose bank no longer covers the model's filter ids
-
-    // device model tables
-    // convolution bank: the filters grouped by size (one class in every known model; the reference builds one engine
-    // per filter and so takes any mix: src/SpatialConvolutionEngine.cpp:141-158)
-    struct ConvClass {
-        int K = 0, nf = 0, Fpad = 0;
-        DevBuf wts;                  // real-typed weights of the class
-        DevTable<int> fmap;          // class-local index -> filter id (empty when the class is the whole bank in order)
-        // k_conv3 (float, 5 x 5): the class cut into units of 2..8 filters, weights [unit][32][25][8]
-        DevBuf wts3;
-        DevTable<int> unit_f0, unit_ql, unit_woff;
-        int nunits = 0;
-        DevTable<float> c31tab;      // [81][c31stride]: see pbd_kernels_conv.hip (channel 31)
-        int c31stride = 0;
-        DevBuf wfrag64;              // PBD_CONV_MFMA_F64: the class's A-fragments (pbd_internal.h, f64_passes)
-    };
-    std::vector<ConvClass> conv_classes;
-    DevBuf d_wrec;                   // bf16 hi/lo weight records of the matrix-core path
-    DevTable<float> d_biasw;
-    DevTable<int> d_walk_off;
-    DevTable<RootJob> d_rjobs;
-    DevTable<PartWalk> d_walk;
-    DevBuf d_coord;                  // HogCoordT<R>[]
-    int coord_n = 0;
-    bool f64 = false;                // reference template parameter T = double
-    size_t rs = sizeof(float);       // sizeof(T)
-    bool resp_half = false;          // PBD_CONV_MFMA_F16: the responses live on the device as fp16 (BASELINE configs[4])
-    size_t resp_es = sizeof(float);  // bytes per response element on the device
-
-    // plans
-    std::vector<std::unique_ptr<Plan>> plans;
-    Resident res;
-    int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
-    bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
-    float nms_overlap = 0.f;
-    DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)
-    int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
-
-    // workspace
-    DevBuf frames, pyr, gmag, gori, hist, norm, feat, resp, acc, Ik, rootv, rooti;
-    int totmix = 0;                  // (part, mixture) pairs of the model = planes of IxRaw / IyRaw per cell block
-    DevBuf tmp, dt, IxRaw, IyRaw, stk, scales_tmp, find_blk;
-    DevBuf post_ws;                  // workspace of the post-processing stage (pbd_kernels_post.hip)
-    DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
-    // pbd_boxes3d*: the frame table (staged in pinned memory, rewritten only once its previous copy has completed); the host
-    // form's depth images, records and boxes.  Never the detect path's buffers: the resident result stays readable.
-    HostBuf b3_tab_host;
-    DevBuf b3_tab, b3_depth, b3_rec, b3_out;
-    Event b3_tab_copied;
-    // pbd_boxes3d_camera*: the pinhole table (staged as the frame table), k_boxes3d's cubes, the host form's outputs
-    HostBuf cam_tab_host;
-    DevBuf cam_tab, cam_cube, cam_out;
-    Event cam_tab_copied;
-    // pbd_cluster_objects*: the cloud table (staged as above), the workspace, the host form's clouds, payload, boxes and outputs
-    HostBuf cl_tab_host;
-    DevBuf cl_tab, cl_ws, cl_cloud, cl_in, cl_out;
-    Event cl_tab_copied;
-    long long cl_crop_cap = 0;       // the host form's crop capacity so far (grows to what a call needed)
-    // pbd_remove_planes*: the cloud table (staged as above), the workspace, the host form's packed clouds and outputs
-    HostBuf pl_tab_host;
-    DevBuf pl_tab, pl_ws, pl_cloud, pl_out;
-    Event pl_tab_copied;
-    // pbd_depth_consistency*: the frame table (staged as above), the model's edge tables (built on first use), the workspace,
-    // the host form's depth images, records and output
-    HostBuf dc_tab_host;
-    DevBuf dc_tab, dc_ws, dc_depth, dc_rec, dc_out;
-    Event dc_tab_copied;
-    DevTable<int> dc_part_offset, dc_parent;
-    DevTable<double> dc_norm;
-    // pbd_suppress*: the canvas plan of the last list of frame sizes, the check flag, the host form's records and output
-    std::unique_ptr<Plan> sup_plan;
-    DevBuf sup_bad, sup_in, sup_out;
-    // pbd_candidate_mask*: the frame table (staged as above), the workspace (hulls, frame ranges, the bad flag), the host form's
-    // records, frames and labels, and its status word
-    HostBuf mk_tab_host;
-    DevBuf mk_tab, mk_ws, mk_rec, mk_img;
-    Event mk_tab_copied;
-    // pbd_part_poses: the host form's inputs and outputs
-    DevBuf ps_buf;
-    // pbd_model_vector / pbd_examples*: the model vector in T (built by build_model), the filter sizes and offsets of the model the
-    // handle was created with, the strides of an example, the walk's tables (uploaded on first use), the (record, part) workspace,
-    // the host form's records and outputs
-    std::vector<char> mvec;
-    std::vector<int> model_ksize;
-    std::vector<long long> model_foff;   // offset of filter f in the model vector
-    int nbias = 0, ndefs = 0, ex_hdr_words = 0, ex_values = 0;
-    DevTable<ExGm> ex_gm;
-    DevTable<int> ex_anchors;
-    DevTable<long long> ex_foff;
-    DevBuf ex_ws, ex_rec, ex_out;
-    // pbd_detect_latent: a second handle on the same stream whose model gives every (component, part, mixture) its own filter
-    // (the mask belongs to the (component, part, mixture), not to a shared filter), created on first use; the part -> mixture
-    // table of its bank, the call's boxes / mixtures and its payload.  The detect path of this handle never touches it.
-    std::unique_ptr<pbd_handle, void (*)(pbd_handle *)> lat{nullptr, pbd_destroy};
-    DevTable<int4> lat_gm;
-    DevBuf lat_in, lat_pay;
-    // mixed-size calls: the FrameDesc table, staged in pinned memory (rewritten only once its previous copy has completed)
-    HostBuf fd_host;
-    DevBuf fd_dev;
-    Event fd_copied;
-
-    // A candidate list on its way out.  The device side is the "payload" the find / walk kernels write: word 0 = roots
-    // found, then the records, already in (frame, level, component, y, x) order.  The host side is a pinned mirror: the
-    // count and the first `guess` records (what the previous batch needed + 25 %) are copied by ONE asynchronous D2H
-    // enqueued right behind the walk kernel, so a steady stream of batches never waits for a count before it can ask for
-    // the records; a batch that outgrows the guess costs one more copy.
-    struct CandBuf {
-        DevBuf payload;
-        DevBuf post;                                      // the suppressed list when `nms` (then the read-back source)
-        bool nms = false;                                 // the stage was on when this list was enqueued
-        HostBuf host;
-        int copied = 0;                                   // records covered by the enqueued copy
-        const DevBuf &out() const { return nms ? post : payload; }
-        int32_t *words() const { return host.as<int32_t>(); }
-        hipError_t reserve(size_t words) { return host.ensure(words * 4, (words + words / 4 + 256) * 4); }
-    } cb;
-    int cand_guess = 1024;                                // records the next speculative copy covers (shared by every CandBuf)
-
-    // pipelined host entry points (pbd_detect_batch_submit / _wait): two batches may be in flight
-    struct Slot {
-        HostBuf pinned;                                   // host staging of the frames
-        DevBuf frames;
-        CandBuf cb;
-        Event copied, done;
-    } slot[2];
-    Stream stream_copy, stream_d2h;
-    long long nsubmitted = 0, nwaited = 0;
-
-    Prof prof;
-};
-
-namespace {
-
-int fail(pbd_handle *h, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    try {
-        if (h) h->err = buf; else g_create_error = buf;
-    } catch (...) {   // the message itself could not be stored: the status code still goes out
-    }
-    return code;
-}
-
-#define HIPCHK(h, expr)                                                                             \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            (void)hipGetLastError();   /* the error is reported through the status code, not left sticky */ \
-            return fail(h, e_ == hipErrorOutOfMemory ? PBD_ERR_NOMEM : PBD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-        }                                                                                           \
-    } while (0)
-
-// "No exception crosses this ABI" (include/pbd.h): every extern "C" body runs inside guarded().  The
-// reference's errors on this path are CV_Error / bool returns, never process death
-// (src/HOGFeatures.cpp:141-145, src/FileStorageModel.cpp:100-101).
-template <class F>
-int guarded(pbd_handle *h, F &&body) noexcept
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail(h, PBD_ERR_NOMEM, "out of host memory");
-    } catch (const std::length_error &e) {
-        return fail(h, PBD_ERR_NOMEM, "host allocation too large: %s", e.what());
-    } catch (const std::exception &e) {
-        return fail(h, PBD_ERR_INVALID, "unexpected exception: %s", e.what());
-    } catch (...) {
-        return fail(h, PBD_ERR_INVALID, "unexpected exception");
-    }
-}
-
-// The preamble of every entry point that takes a handle: a null handle or pointer argument (`args_ok` false) is
-// PBD_ERR_INVALID, then the handle's device is made current and, with kIdle, a call while a batch is in flight is refused.
-// The body then checks argument values and handle state before it enqueues or copies anything.
-enum InFlight { kBusyOk, kIdle };
-template <class F>
-int entry(pbd_handle *h, bool args_ok, InFlight need, F &&body) noexcept
-{
-    return guarded(h, [&]() -> int {
-        if (!h || !args_ok) return PBD_ERR_INVALID;
-        (void)hipSetDevice(h->cfg.device);
-        if (need == kIdle && h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
-        return body();
-    });
-}
-
-// shared checks (also check_frames below): PBD_OK (0) or the failure's status code
-int check_batch(pbd_handle *h, int nframes)
-{
-    if (nframes >= 1 && nframes <= h->cfg.max_batch) return PBD_OK;
-    return fail(h, PBD_ERR_INVALID, "nframes %d outside 1..max_batch %d", nframes, h->cfg.max_batch);
-}
-int check_bank(pbd_handle *h)
-{
-    if (h->bank_matches_model) return PBD_OK;
-    return fail(h, PBD_ERR_STATE, "the filter bank set by setFilters() (%d filters) does not cover the model's filter ids", h->F);
-}
-
-int stride(const pbd_handle *h) { return 8 + 4 * h->max_parts; }   // int32 words per candidate record
-
-// While a ProfScope is alive, every kernel launched by this thread is timed under kernel id `k` (see PBD_LAUNCH).
-struct ProfScope {
-    pbd_handle *h; int k; ProfHook hook; ProfHook *prev;
-    static void take(void *ctx, hipEvent_t *a, hipEvent_t *b)
-    {
-        ProfScope *self = static_cast<ProfScope *>(ctx);
-        Prof &prof = self->h->prof;
-        Prof::Rec r{self->k, prof.get(), prof.get()};
-        *a = r.a.p; *b = r.b.p;
-        prof.recs.push_back(std::move(r));
-    }
-    ProfScope(pbd_handle *h_, int k_, hipStream_t) : h(h_), k(k_), hook{this, &ProfScope::take}, prev(g_prof_hook)
-    {
-        if (h->prof.on == 1 || (h->prof.on == 2 && k == PBD_K_CONV)) g_prof_hook = &hook;
-    }
-    ~ProfScope() { g_prof_hook = prev; }
-    ProfScope(const ProfScope &) = delete;
-    ProfScope &operator=(const ProfScope &) = delete;
-};
 
 // ---- plan construction -------------------------------------------------------------------------
 // Cover a rows x cols level with 256-cell tiles of shape 32x8, 16x16 or 8x32 (shape k: 32>>k wide, 8<<k
@@ -848,7 +417,6 @@ void mixed_append(Plan &M, const Plan &Q)
     M.mixed_frames += 1;
 }
 
-void post_canvas_plan(Plan &M);
 
 // After the last mixed_append: the pyramid launches (every frame's resized levels in one, then one per octave over every frame)
 // and the post-processing tables.  Host only.
@@ -878,6 +446,10 @@ void mixed_finish(Plan &M, int interval)
     post_canvas_plan(M);
 }
 
+}  // namespace
+
+namespace pbd {
+
 // the suppression stage's per-frame tables of a list of frame sizes (M.fdim, M.mixed_frames): each frame's canvas in LDS or at
 // its offset in the global workspace.  Host only.
 void post_canvas_plan(Plan &M)
@@ -897,6 +469,10 @@ void post_canvas_plan(Plan &M)
         }
     }
 }
+
+}  // namespace pbd
+
+namespace {
 
 // the mixed plan of one call's frame sizes (rows[f] x cols[f], call order), built from the cached image plans of its sizes
 int get_mixed_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
@@ -1693,11 +1269,15 @@ int run_dp(pbd_handle *h, Plan &P, int nframes)
     return PBD_OK;
 }
 
+}  // namespace
+
+namespace pbd {
+
 // ---- argmin: find (ordered compaction) + walk into a device payload, then one D2H ---------------------------------
 // enqueues the find and walk kernels for the `nframes` frames of the device-resident DP result; the candidate list is
 // written to d_payload = int32[1 + capacity * stride] (see pbd_handle::CandBuf).  No host synchronisation.
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
-                   int capacity, hipStream_t st, bool walk_only = false)
+                   int capacity, hipStream_t st, bool walk_only)
 {
     ArgminParams ap{};
     ap.lv = P.d_lv.p; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
@@ -1724,7 +1304,7 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
 // than in_cap candidates were found), then the kept records frame by frame, `frame` + frame_offset.  No host synchronisation.
 // pbd_suppress*: `in_offset` is subtracted from the input's `frame` fields and `bad` (zeroed here) turns on the list's check.
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
-                 int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr, int in_offset = 0, int *bad = nullptr)
+                 int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed, int in_offset, int *bad)
 {
     PostParams pp{};
     pp.in_offset = in_offset; pp.bad = bad;
@@ -1757,6 +1337,11 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
 
 // find + walk into cb.payload (then, with `post`, the sort + suppression into cb.post) and the speculative read-back of
 // [count | first records], all on `st`
+
+}  // namespace pbd
+
+namespace {
+
 int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, bool post,
                             hipStream_t st)
 {
@@ -1987,6 +1572,10 @@ int run_dp_mixed(pbd_handle *h, Plan &P)
     return PBD_OK;
 }
 
+}  // namespace
+
+namespace pbd {
+
 // every check of a mixed-size call before anything is enqueued; *plan = its mixed plan
 int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan)
 {
@@ -2025,7 +1614,7 @@ int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int 
 
 // pyramid -> HOG -> convolution -> dynamic program of a mixed-size call that passed check_frames_mixed (no host synchronisation)
 int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
-                         const LatentParams *mask = nullptr)
+                         const LatentParams *mask)
 {
     h->res = Resident{&P, 1, cn, depth};
     const size_t es = depth_size(depth);
@@ -2047,16 +1636,9 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
         for (int f = 0; f < nframes; ++f)
             fd[f] = FrameDesc{static_cast<const uint8_t *>(frames[f].data), frames[f].rows, frames[f].cols, (long long)frames[f].stride_bytes};
     }
-    const size_t fd_bytes = fd.size() * sizeof(FrameDesc);
-    if (h->fd_copied.p) HIPCHK(h, hipEventSynchronize(h->fd_copied.p));   // the previous call's table has left the staging buffer
-    else HIPCHK(h, hipEventCreateWithFlags(&h->fd_copied.p, hipEventDisableTiming));
-    HIPCHK(h, h->fd_host.ensure(fd_bytes, fd_bytes * 2 + 256));
-    HIPCHK(h, h->fd_dev.ensure(fd_bytes));
-    memcpy(h->fd_host.p, fd.data(), fd_bytes);
-    HIPCHK(h, hipMemcpyAsync(h->fd_dev.p, h->fd_host.p, fd_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->fd_copied.p, h->stream));
+    if (int rc = h->fd_tab.stage(h, fd.data(), fd.size() * sizeof(FrameDesc))) return rc;
     if (int rc = alloc_features(h, P, 1, cn, depth)) return rc;
-    launch_features_mixed(h, P, h->fd_dev.as<FrameDesc>(), cn, depth, h->stream);
+    launch_features_mixed(h, P, h->fd_tab.as<FrameDesc>(), cn, depth, h->stream);
     HIPCHK(h, hipGetLastError());
     h->res.features = h->res.c31_zero = true;
     if (int rc = run_conv(h, P, 1)) return rc;
@@ -2070,663 +1652,7 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     return run_dp_mixed(h, P);
 }
 
-// ---- 3-D boxes from a depth image (pbd_boxes3d*; pbd_kernels_depth.hip)
-// the derivative-of-Gaussian taps of Candidate::boundingBox3D (include/Candidate.hpp:190-193), once, with the C library's exp:
-//   g = getGaussianKernel(35, 4, CV_32F): t_i = exp(scale2X * x_i * x_i), x_i = i - 17, scale2X = -0.5 / 16; cf_i = (float)t_i,
-//       sum += cf_i in double, then cf_i = (float)(cf_i * (1. / sum))
-//   dog = filter2D(g, -1, [-1 0 1]^T): correlation, BORDER_REFLECT_101, s = 0; s += k * x per non-zero tap, in float
-const float *boxes3d_taps()
-{
-    static const struct Taps {
-        float v[kB3Taps];
-        Taps()
-        {
-            float g[kB3Taps];
-            const double scale2X = -0.5 / (4.0 * 4.0);
-            double sum = 0;
-            for (int i = 0; i < kB3Taps; ++i) {
-                const double x = i - (kB3Taps - 1) * 0.5;
-                g[i] = (float)exp(scale2X * x * x);
-                sum += g[i];
-            }
-            sum = 1. / sum;
-            for (int i = 0; i < kB3Taps; ++i) g[i] = (float)(g[i] * sum);
-            for (int i = 0; i < kB3Taps; ++i) {
-                const int a = i == 0 ? 1 : i - 1, b = i == kB3Taps - 1 ? kB3Taps - 2 : i + 1;
-                float s = 0.f;
-                s = s + -1.f * g[a];
-                s = s + 1.f * g[b];
-                v[i] = s;
-            }
-        }
-    } taps;
-    return taps.v;
-}
-
-// every check of a pbd_boxes3d* call's frames before anything is enqueued
-int check_boxes3d_frames(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
-                         bool host)
-{
-    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
-    if (!depth_size(depth_code))
-        return fail(h, PBD_ERR_INVALID, "depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F)", depth_code);
-    const size_t es = depth_size(depth_code);
-    for (int f = 0; f < nframes; ++f) {
-        const pbd_frame &d = depth[f];
-        if (!d.data || d.rows < 1 || d.cols < 1 || im_rows[f] < 1 || im_cols[f] < 1)
-            return fail(h, PBD_ERR_INVALID, "frame %d: depth %dx%d at %p, colour frame %dx%d", f, d.rows, d.cols, d.data, im_rows[f],
-                        im_cols[f]);
-        // every box lies inside the depth image: the samples of one record (boxes counted with their overlaps) fit an int
-        if ((unsigned long long)kB3MaxBoxes * (unsigned long long)d.rows * (unsigned long long)d.cols >= (1ull << 31))
-            return fail(h, PBD_ERR_INVALID, "frame %d: depth image %dx%d too large", f, d.rows, d.cols);
-        if (d.stride_bytes < (size_t)d.cols * es)
-            return fail(h, PBD_ERR_INVALID, "frame %d: stride %zu < row bytes %zu", f, d.stride_bytes, (size_t)d.cols * es);
-        if (!host && (reinterpret_cast<uintptr_t>(d.data) % es || d.stride_bytes % es))
-            return fail(h, PBD_ERR_INVALID, "frame %d: device pointer %p / stride %zu not a multiple of the %zu-byte element", f, d.data,
-                        d.stride_bytes, es);
-    }
-    return PBD_OK;
-}
-
-// the frame table to the device (through the pinned staging buffer) and the kernel, on the handle's stream
-int enqueue_boxes3d(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, const int32_t *d_payload, int capacity,
-                    int frame_offset, double *d_out)
-{
-    const size_t bytes = tab.size() * sizeof(Box3dFrame);
-    if (h->b3_tab_copied.p) HIPCHK(h, hipEventSynchronize(h->b3_tab_copied.p));   // the previous call's table has left the staging buffer
-    else HIPCHK(h, hipEventCreateWithFlags(&h->b3_tab_copied.p, hipEventDisableTiming));
-    HIPCHK(h, h->b3_tab_host.ensure(bytes, bytes * 2 + 256));
-    HIPCHK(h, h->b3_tab.ensure(bytes));
-    memcpy(h->b3_tab_host.p, tab.data(), bytes);
-    HIPCHK(h, hipMemcpyAsync(h->b3_tab.p, h->b3_tab_host.p, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->b3_tab_copied.p, h->stream));
-    Boxes3dParams bp{};
-    bp.in = d_payload; bp.in_cap = capacity;
-    bp.stride = stride(h); bp.max_parts = h->max_parts;
-    bp.frames = h->b3_tab.as<Box3dFrame>(); bp.nframes = (int)tab.size(); bp.frame_offset = frame_offset;
-    bp.depth = depth_code; bp.out = d_out;
-    memcpy(bp.dog, boxes3d_taps(), sizeof bp.dog);
-    launch_boxes3d(bp, capacity, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// the host records of a pbd_boxes3d* call: frame index and part count of each
-int check_boxes3d_records(pbd_handle *h, int nframes, const int32_t *cand, int ncand, int frame_offset)
-{
-    const int stride = ::stride(h);
-    for (int i = 0; i < ncand; ++i) {
-        const int32_t *r = cand + (size_t)i * stride;
-        const long long f = (long long)r[0] - frame_offset;
-        if (f < 0 || f >= nframes)
-            return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
-        if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
-    }
-    return PBD_OK;
-}
-
-// the host forms' depth images (packed with dense rows) and records (as a payload) into the handle's own buffers
-int upload_boxes3d_host(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
-                        const int32_t *cand, int ncand, std::vector<Box3dFrame> &tab)
-{
-    const int stride = ::stride(h);
-    const size_t es = depth_size(depth_code);
-    size_t total = 0;
-    for (int f = 0; f < nframes; ++f) total += (size_t)depth[f].rows * depth[f].cols * es;
-    HIPCHK(h, h->b3_depth.ensure(total + 8));
-    HIPCHK(h, h->b3_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
-    tab.resize(nframes);
-    size_t off = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const size_t row_bytes = (size_t)depth[f].cols * es;
-        uint8_t *dst = h->b3_depth.as<uint8_t>() + off;
-        HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, depth[f].data, depth[f].stride_bytes, row_bytes, depth[f].rows,
-                                   hipMemcpyHostToDevice, h->stream));
-        tab[f] = Box3dFrame{dst, depth[f].rows, depth[f].cols, (long long)row_bytes, im_rows[f], im_cols[f]};
-        off += row_bytes * depth[f].rows;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->b3_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->b3_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
-                             h->stream));
-    return PBD_OK;
-}
-
-// a small table to the device through pinned staging memory, which is rewritten only once its previous copy has completed
-int stage_table(pbd_handle *h, HostBuf &host, DevBuf &dev, Event &copied, const void *src, size_t bytes)
-{
-    if (copied.p) HIPCHK(h, hipEventSynchronize(copied.p));
-    else HIPCHK(h, hipEventCreateWithFlags(&copied.p, hipEventDisableTiming));
-    HIPCHK(h, host.ensure(bytes, bytes * 2 + 256));
-    HIPCHK(h, dev.ensure(bytes));
-    memcpy(host.p, src, bytes);
-    HIPCHK(h, hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(copied.p, h->stream));
-    return PBD_OK;
-}
-
-// ---- depth consistency (pbd_depth_consistency*; pbd_kernels_consistency.hip)
-// the model's tables the decision reads, uploaded on first use: part offsets, component-local parents, and per part the norm of
-// its mixture-0 anchor, std::sqrt((double)ax*ax + (double)ay*ay) (part.anchor(0): src/SearchSpacePruning.cpp:83)
-int dc_model_tables(pbd_handle *h)
-{
-    if (h->dc_norm.p) return PBD_OK;
-    const int totparts = (int)h->parentid.size();
-    std::vector<double> norm(std::max(totparts, 1), 0.0);
-    for (int c = 0; c < h->NC; ++c)
-        for (int gp = h->part_offset[c] + 1; gp < h->part_offset[c + 1]; ++gp) {
-            const int d = h->defid[h->mix_offset[gp]];
-            if (d < 0 || 2 * (size_t)d + 1 >= h->anchors.size()) continue;
-            const double ax = h->anchors[2 * (size_t)d], ay = h->anchors[2 * (size_t)d + 1];
-            norm[gp] = std::sqrt(ax * ax + ay * ay);
-        }
-    HIPCHK(h, h->dc_part_offset.upload(h->part_offset));
-    HIPCHK(h, h->dc_parent.upload(h->parentid));
-    HIPCHK(h, h->dc_norm.upload(norm));
-    return PBD_OK;
-}
-
-// every check of a pbd_depth_consistency* call's images and zfactor before anything is enqueued
-int check_dc_frames(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, float zfactor, bool host)
-{
-    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
-    if (!depth_size(depth_code))
-        return fail(h, PBD_ERR_INVALID, "depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F)", depth_code);
-    if (std::isnan(zfactor)) return fail(h, PBD_ERR_INVALID, "zfactor is NaN");
-    const size_t es = depth_size(depth_code);
-    for (int f = 0; f < nframes; ++f) {
-        const pbd_frame &d = depth[f];
-        if (!d.data || d.rows < 1 || d.cols < 1) return fail(h, PBD_ERR_INVALID, "frame %d: depth %dx%d at %p", f, d.rows, d.cols, d.data);
-        if ((long long)d.rows * d.cols >= (1LL << 31)) return fail(h, PBD_ERR_INVALID, "frame %d: depth image %dx%d too large", f, d.rows, d.cols);
-        if (d.stride_bytes < (size_t)d.cols * es)
-            return fail(h, PBD_ERR_INVALID, "frame %d: stride %zu < row bytes %zu", f, d.stride_bytes, (size_t)d.cols * es);
-        if (!host && (reinterpret_cast<uintptr_t>(d.data) % es || d.stride_bytes % es))
-            return fail(h, PBD_ERR_INVALID, "frame %d: device pointer %p / stride %zu not a multiple of the %zu-byte element", f, d.data,
-                        d.stride_bytes, es);
-    }
-    return PBD_OK;
-}
-
-// the host form's records: frame index, component and part count of each
-int check_dc_records(pbd_handle *h, int nframes, const int32_t *cand, int ncand, int frame_offset)
-{
-    const int stride = ::stride(h);
-    for (int i = 0; i < ncand; ++i) {
-        const int32_t *r = cand + (size_t)i * stride;
-        const long long f = (long long)r[0] - frame_offset;
-        if (f < 0 || f >= nframes)
-            return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d", i, r[0], frame_offset, nframes - 1);
-        if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
-        const int np = h->part_offset[r[1] + 1] - h->part_offset[r[1]];
-        if (r[6] != np || r[6] < 1 || r[6] > h->max_parts)
-            return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (component %d has %d)", i, r[6], r[1], np);
-    }
-    return PBD_OK;
-}
-
-// the frame table and the filter's kernels on the handle's stream: payload d_in (capacity records) -> d_out (out_cap records)
-int enqueue_dc(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, float zfactor, const int32_t *d_in, int capacity,
-               int frame_offset, int32_t *d_out, int out_cap)
-{
-    if (int rc = dc_model_tables(h)) return rc;
-    const int cap = std::max(capacity, 0);
-    const long long tasks = std::max<long long>((long long)cap * h->max_parts, 1);
-    if (tasks >= (1LL << 30)) return fail(h, PBD_ERR_INVALID, "capacity %d: %lld parts (below 2^30)", capacity, tasks);
-    const int blocks = dc_record_blocks(cap);
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t s_med = al(tasks * sizeof(double)), s_queue = al(tasks * sizeof(int)), s_qn = 256,
-                 s_flag = al((size_t)blocks * 256 * sizeof(int)), s_blk = al((size_t)blocks * sizeof(int));
-    HIPCHK(h, h->dc_ws.ensure(s_med + s_queue + s_qn + s_flag + s_blk));
-    if (int rc = stage_table(h, h->dc_tab_host, h->dc_tab, h->dc_tab_copied, tab.data(), tab.size() * sizeof(Box3dFrame))) return rc;
-    uint8_t *w = h->dc_ws.as<uint8_t>();
-    DcParams p{};
-    p.in = d_in; p.in_cap = cap; p.stride = stride(h); p.max_parts = h->max_parts;
-    p.frames = h->dc_tab.as<Box3dFrame>(); p.nframes = (int)tab.size(); p.frame_offset = frame_offset;
-    p.depth = depth_code; p.NC = h->NC;
-    p.part_offset = h->dc_part_offset.p; p.parent = h->dc_parent.p; p.norm = h->dc_norm.p; p.zfactor = zfactor;
-    p.med = reinterpret_cast<double *>(w); w += s_med;
-    p.queue = reinterpret_cast<int *>(w); w += s_queue;
-    p.qn = reinterpret_cast<int *>(w); w += s_qn;
-    p.flag = reinterpret_cast<int *>(w); w += s_flag;
-    p.blk = reinterpret_cast<int *>(w);
-    p.task_cap = tasks;
-    p.out = d_out; p.out_cap = std::max(out_cap, 0);
-    HIPCHK(h, hipMemsetAsync(p.qn, 0, 8 * sizeof(int), h->stream));
-    static const int ids[kDcSteps] = {PBD_K_DC_CLASSIFY, PBD_K_DC_SELECT, PBD_K_DC_COMPACT};
-    for (int step = 0; step < kDcSteps; ++step) {
-        ProfScope ps(h, ids[step], h->stream);
-        launch_depth_consistency(p, h->f64, step, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// ---- suppression of a caller's list (pbd_suppress*): the canvas tables of its frame sizes, kept for the next call of the
-// same sizes
-int get_suppress_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
-{
-    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
-    std::vector<int> key;
-    for (int f = 0; f < nframes; ++f) {
-        if (rows[f] < 1 || cols[f] < 1 || rows[f] > 65536 || cols[f] > 65536)
-            return fail(h, PBD_ERR_INVALID, "frame %d: size %dx%d (1..65536)", f, rows[f], cols[f]);
-        key.push_back(rows[f]); key.push_back(cols[f]);
-    }
-    if (h->sup_plan && h->sup_plan->key_dims == key) { *out = h->sup_plan.get(); return PBD_OK; }
-    if (h->sup_plan) HIPCHK(h, hipStreamSynchronize(h->stream));   // the previous tables may still be read
-    auto M = std::make_unique<Plan>();
-    M->kind = 4; M->key_dims = key; M->mixed_frames = nframes;
-    for (int f = 0; f < nframes; ++f) M->fdim.push_back(make_int2(rows[f], cols[f]));
-    post_canvas_plan(*M);
-    h->sup_plan.reset();
-    HIPCHK(h, M->d_fdim.upload(M->fdim));
-    HIPCHK(h, M->d_fcanvas.upload(M->fcanvas));
-    HIPCHK(h, M->d_post_lds.upload(M->post_lds));
-    HIPCHK(h, M->d_post_glb.upload(M->post_glb));
-    h->sup_plan = std::move(M);
-    *out = h->sup_plan.get();
-    return PBD_OK;
-}
-
-// the host forms: records into a payload of the handle's (word 0 = ncand), then, after `run` enqueued the stage into `dout`,
-// the kept count and min(kept, capacity) records back into out
-template <class Run>
-int host_list_call(pbd_handle *h, DevBuf &din, DevBuf &dout, const int32_t *cand, int ncand, int32_t *out, int capacity, int *nout,
-                   Run run)
-{
-    const size_t stride = (size_t)::stride(h);
-    HIPCHK(h, din.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
-    HIPCHK(h, dout.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
-    HIPCHK(h, hipMemcpyAsync(din.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (ncand) HIPCHK(h, hipMemcpyAsync(din.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
-                                        h->stream));
-    if (int rc = run(din.as<int32_t>(), dout.as<int32_t>())) return rc;
-    int kept = 0;
-    HIPCHK(h, hipMemcpyAsync(&kept, dout.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    const int nret = std::min(std::max(kept, 0), capacity);
-    if (nret > 0)
-        HIPCHK(h, hipMemcpy(out, dout.as<int32_t>() + 1, (size_t)nret * stride * sizeof(int32_t), hipMemcpyDeviceToHost));
-    *nout = kept;
-    if (kept > capacity) return fail(h, PBD_ERR_CAPACITY, "%d records kept, capacity %d", kept, capacity);
-    return PBD_OK;
-}
-
-// ---- camera boxes and part centres (pbd_boxes3d_camera*; pbd_kernels_cloud.hip)
-int check_camera(pbd_handle *h, int nframes, int depth_code, const pbd_pinhole *cams, int parts_mode)
-{
-    if (depth_code != kDepth32F) return fail(h, PBD_ERR_UNSUPPORTED, "depth code %d: the part centres read 32F depth (5)", depth_code);
-    if (parts_mode != PBD_PARTS_LITERAL && parts_mode != PBD_PARTS_XY)
-        return fail(h, PBD_ERR_INVALID, "parts mode %d: PBD_PARTS_LITERAL (0) or PBD_PARTS_XY (1)", parts_mode);
-    for (int f = 0; f < nframes; ++f)
-        if (!std::isfinite(cams[f].fx) || !std::isfinite(cams[f].fy) || cams[f].fx == 0 || cams[f].fy == 0)
-            return fail(h, PBD_ERR_INVALID, "frame %d: fx %g, fy %g (finite, non-zero)", f, cams[f].fx, cams[f].fy);
-    return PBD_OK;
-}
-
-// k_boxes3d into the handle's cube buffer, then the camera kernel, on the handle's stream
-int enqueue_camera(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, const pbd_pinhole *cams, int parts_mode,
-                   const int32_t *d_payload, int capacity, int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres,
-                   int32_t *d_dense)
-{
-    static_assert(sizeof(pbd_pinhole) == sizeof(Pinhole), "pbd_pinhole is the kernels' Pinhole");
-    HIPCHK(h, h->cam_cube.ensure((size_t)capacity * 6 * sizeof(double)));
-    if (int rc = enqueue_boxes3d(h, tab, depth_code, d_payload, capacity, frame_offset, h->cam_cube.as<double>())) return rc;
-    if (int rc = stage_table(h, h->cam_tab_host, h->cam_tab, h->cam_tab_copied, cams, tab.size() * sizeof(Pinhole))) return rc;
-    CameraParams cp{};
-    cp.in = d_payload; cp.in_cap = capacity; cp.stride = stride(h); cp.max_parts = h->max_parts;
-    cp.frames = h->b3_tab.as<Box3dFrame>(); cp.cams = h->cam_tab.as<Pinhole>();
-    cp.nframes = (int)tab.size(); cp.frame_offset = frame_offset; cp.mode = parts_mode;
-    cp.cube = h->cam_cube.as<double>();
-    cp.box = d_box; cp.centres = d_centres; cp.ncentres = d_ncentres; cp.dense = d_dense;
-    {
-        ProfScope ps(h, PBD_K_CAMERA_BOXES, h->stream);
-        launch_camera_boxes(cp, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// ---- candidate mask (pbd_candidate_mask*; pbd_kernels_publish.hip)
-// every check of a call's frames before anything is enqueued
-int check_mask_frames(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, uint8_t *const *labels, const size_t *label_pitch,
-                      int channels, const uint8_t *const *colour, const size_t *colour_pitch, uint8_t *const *masked,
-                      const size_t *masked_pitch)
-{
-    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
-    if (masked && channels != 1 && channels != 3 && channels != 4)
-        return fail(h, PBD_ERR_INVALID, "channels %d: 1, 3 or 4", channels);
-    if ((labels && !label_pitch) || (masked && (!masked_pitch || !colour || !colour_pitch)))
-        return fail(h, PBD_ERR_INVALID, "an output without its pitches or colour frames");
-    for (int f = 0; f < nframes; ++f) {
-        if (im_rows[f] < 1 || im_cols[f] < 1 || im_rows[f] > 65536 || im_cols[f] > 65536)
-            return fail(h, PBD_ERR_INVALID, "frame %d: size %dx%d (1..65536)", f, im_rows[f], im_cols[f]);
-        const size_t row = (size_t)im_cols[f];
-        if (labels && (!labels[f] || label_pitch[f] < row))
-            return fail(h, PBD_ERR_INVALID, "frame %d: labels %p, pitch %zu < row bytes %zu", f, (const void *)labels[f], label_pitch[f], row);
-        if (masked && (!masked[f] || !colour[f] || colour_pitch[f] < row * channels || masked_pitch[f] < row * channels))
-            return fail(h, PBD_ERR_INVALID, "frame %d: colour %p / masked %p, pitches %zu / %zu < row bytes %zu", f,
-                        (const void *)colour[f], (const void *)masked[f], colour_pitch[f], masked_pitch[f], row * channels);
-    }
-    return PBD_OK;
-}
-
-// the frame table (tile numbering filled in) to the device, then the hull and the tile kernels, on the handle's stream
-int enqueue_mask(pbd_handle *h, std::vector<MaskFrame> &tab, int channels, const int32_t *d_payload, int capacity, int frame_offset,
-                 int32_t *d_status)
-{
-    long long tiles = 0;
-    for (MaskFrame &fr : tab) {
-        fr.tile0 = (int)tiles;
-        tiles += mask_tiles(fr.rows, fr.cols);
-        if (tiles > 0x7fffffffll) return fail(h, PBD_ERR_INVALID, "%zu frames: 2^31 or more pixel tiles", tab.size());
-    }
-    if (int rc = stage_table(h, h->mk_tab_host, h->mk_tab, h->mk_tab_copied, tab.data(), tab.size() * sizeof(MaskFrame))) return rc;
-    const size_t hull_bytes = ((size_t)capacity * sizeof(int4) + 255) / 256 * 256;
-    HIPCHK(h, h->mk_ws.ensure(hull_bytes + (2 * tab.size() + 1) * sizeof(int32_t)));
-    MaskParams mp{};
-    mp.in = d_payload; mp.in_cap = capacity; mp.stride = stride(h); mp.max_parts = h->max_parts;
-    mp.frames = h->mk_tab.as<MaskFrame>(); mp.nframes = (int)tab.size(); mp.frame_offset = frame_offset;
-    mp.ntiles = (int)tiles; mp.channels = channels;
-    mp.hull = h->mk_ws.as<int4>();
-    mp.range = reinterpret_cast<int32_t *>(h->mk_ws.as<uint8_t>() + hull_bytes);
-    mp.bad = mp.range + 2 * tab.size();
-    mp.status = d_status;
-    {
-        ProfScope ps(h, PBD_K_MK_HULL, h->stream);
-        launch_mask(mp, kMkStepHull, h->stream);
-    }
-    {
-        ProfScope ps(h, PBD_K_MK_TILE, h->stream);
-        launch_mask(mp, kMkStepTile, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// ---- part-centre poses (pbd_part_poses*; pbd_kernels_publish.hip)
-int enqueue_poses(pbd_handle *h, const int32_t *d_word, int capacity, const float *d_centres, const int32_t *d_ncentres,
-                  const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues)
-{
-    PoseParams pp{};
-    pp.count_word = d_word; pp.cap = capacity; pp.max_parts = h->max_parts;
-    pp.centres = d_centres; pp.ncentres = d_ncentres; pp.dense = d_dense;
-    pp.count = d_count; pp.position = d_position; pp.orientation = d_orientation; pp.eigenvalues = d_eigenvalues;
-    {
-        ProfScope ps(h, PBD_K_PART_POSES, h->stream);
-        launch_part_poses(pp, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// ---- object clusters (pbd_cluster_objects*; pbd_kernels_cloud.hip)
-int check_clouds(pbd_handle *h, int nclouds, const pbd_cloud *c, bool host)
-{
-    if (nclouds < 1) return fail(h, PBD_ERR_INVALID, "nclouds %d", nclouds);
-    for (int f = 0; f < nclouds; ++f) {
-        if (!c[f].data || c[f].rows < 1 || c[f].cols < 1 || (long long)c[f].rows * c[f].cols >= (1LL << 31))
-            return fail(h, PBD_ERR_INVALID, "cloud %d: %dx%d at %p", f, c[f].rows, c[f].cols, c[f].data);
-        if (c[f].point_stride < 3 * sizeof(float))
-            return fail(h, PBD_ERR_INVALID, "cloud %d: point stride %zu < 12", f, c[f].point_stride);
-        const size_t row_bytes = (size_t)(c[f].cols - 1) * c[f].point_stride + 3 * sizeof(float);
-        if (c[f].rows > 1 && c[f].row_stride < row_bytes)
-            return fail(h, PBD_ERR_INVALID, "cloud %d: row stride %zu < row bytes %zu", f, c[f].row_stride, row_bytes);
-        if (!host && (reinterpret_cast<uintptr_t>(c[f].data) % 4 || c[f].point_stride % 4 || c[f].row_stride % 4))
-            return fail(h, PBD_ERR_INVALID, "cloud %d: device pointer %p / strides %zu, %zu not multiples of 4", f, c[f].data,
-                        c[f].point_stride, c[f].row_stride);
-    }
-    return PBD_OK;
-}
-
-// the clustering workspace for `capacity` boxes, clouds of at most maxpts points and crop_cap cropped points: the bucket table
-// (tcap buckets, a power of two >= 2 crop_cap), the scan partials, and one 256-byte aligned piece per array, in the order
-// enqueue_cluster carves them.  crop_cap <= kClMaxCrop keeps tcap, every bucket index and every count inside an int.
-constexpr long long kClMaxCrop = 1LL << 29;
-constexpr int kClPieces = 14;
-struct ClusterLayout {
-    int nchunks;
-    long long units, tcap, nparts, total;
-    long long sizes[kClPieces];
-};
-int cluster_layout(int capacity, long long maxpts, long long crop_cap, ClusterLayout &L)
-{
-    if (capacity < 0 || maxpts < 1 || crop_cap < 0 || crop_cap > kClMaxCrop) return PBD_ERR_INVALID;
-    L.nchunks = (int)((maxpts + kClChunk - 1) / kClChunk);
-    L.units = (long long)capacity * L.nchunks;
-    L.tcap = 2;
-    while (L.tcap < 2 * crop_cap) L.tcap <<= 1;
-    L.nparts = std::max(L.units + 1, L.tcap + 1) / (4 * 256) + 2;
-    const long long c = crop_cap;
-    const long long sizes[kClPieces] = {(L.units + 1) * 8, L.nparts * 8, c * 4, c * 4, c * 16, c * 4, c * 4, c * 4, c * 4, (L.tcap + 1) * 4,
-                                        (L.tcap + 1) * 4, (long long)capacity * 8, (long long)capacity * 8, 4 * 8};
-    L.total = 0;
-    for (int i = 0; i < kClPieces; ++i) {
-        L.sizes[i] = sizes[i];
-        L.total += (sizes[i] + 255) / 256 * 256;
-    }
-    return PBD_OK;
-}
-
-// the workspace (cluster_layout), the cloud table, and the fixed sequence of launches
-int enqueue_cluster(pbd_handle *h, const std::vector<CloudFrame> &tab, const int32_t *d_payload, int capacity, int rec_stride,
-                    int frame_offset, const double *d_boxes, int crop_cap, int index_cap, float *d_centres, int32_t *d_counts,
-                    int32_t *d_indices, long long *d_status)
-{
-    long long maxpts = 1;
-    for (const CloudFrame &c : tab) maxpts = std::max(maxpts, (long long)c.rows * c.cols);
-    ClusterLayout L;
-    if (cluster_layout(capacity, maxpts, crop_cap, L))
-        return fail(h, PBD_ERR_INVALID, "crop capacity %d (at most 2^29), capacity %d", crop_cap, capacity);
-    const int nchunks = L.nchunks;
-    const long long tcap = L.tcap, total = L.total;
-    const long long *sizes = L.sizes;
-    HIPCHK(h, h->cl_ws.ensure((size_t)total));
-    if (int rc = stage_table(h, h->cl_tab_host, h->cl_tab, h->cl_tab_copied, tab.data(), tab.size() * sizeof(CloudFrame))) return rc;
-    uint8_t *w = h->cl_ws.as<uint8_t>();
-    int piece = 0;
-    auto carve = [&]() { uint8_t *p = w; w += (sizes[piece++] + 255) / 256 * 256; return (void *)p; };
-    ClusterParams p{};
-    p.in = d_payload; p.in_cap = capacity; p.rec_stride = rec_stride; p.frame_offset = frame_offset;
-    p.clouds = h->cl_tab.as<CloudFrame>(); p.nclouds = (int)tab.size(); p.nchunks = nchunks;
-    p.boxes = d_boxes; p.crop_cap = crop_cap; p.index_cap = index_cap;
-    p.chunk_off = (long long *)carve(); p.part = (long long *)carve();
-    p.crop_idx = (int32_t *)carve(); p.crop_box = (int32_t *)carve(); p.crop_xyz = (float4 *)carve();
-    p.bucket = (int32_t *)carve(); p.parent = (int32_t *)carve(); p.csize = (int32_t *)carve(); p.sorted = (int32_t *)carve();
-    p.bstart = (int32_t *)carve(); p.bcur = (int32_t *)carve(); p.tcap = (int)tcap;      // <= 2^30 (cluster_layout)
-    p.best = (unsigned long long *)carve(); p.obase = (long long *)carve(); p.ntab = (long long *)carve();
-    p.centres = d_centres; p.counts = d_counts; p.indices = d_indices; p.status = d_status;
-    static const int ids[kClSteps] = {PBD_K_CL_CROP_COUNT, PBD_K_CL_CROP_SCAN, PBD_K_CL_CROP_SCATTER, PBD_K_CL_CLEAR, PBD_K_CL_GRID_COUNT,
-                                      PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST,
-                                      PBD_K_CL_SELECT, PBD_K_CL_OUT};
-    for (int step = 0; step < kClSteps; ++step) {
-        ProfScope ps(h, ids[step], h->stream);
-        launch_cluster_step(p, step, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// ---- plane removal (pbd_remove_planes*; pbd_kernels_planes.hip)
-// the reference's call (include/PointCloudClusterer.hpp:294-336 with PCL's defaults): see include/pbd.h
-pbd_plane_params plane_defaults()
-{
-    pbd_plane_params q;
-    q.smoothing_size = 10;
-    q.depth_change_factor = 0.02f;
-    q.distance_threshold = 0.02f;
-    q.angular_threshold = 3.0 * M_PI / 180.0;
-    q.max_curvature = 0.001;
-    q.min_inliers = 1000;
-    q.refine = 1;
-    return q;
-}
-
-int check_plane_params(pbd_handle *h, const pbd_plane_params &q)
-{
-    if (q.smoothing_size < 2 || q.smoothing_size > 128 || q.min_inliers < 0 || !std::isfinite(q.depth_change_factor) ||
-        !std::isfinite(q.distance_threshold) || !std::isfinite(q.angular_threshold) || !std::isfinite(q.max_curvature) ||
-        (q.refine != 0 && q.refine != 1))
-        return fail(h, PBD_ERR_INVALID, "plane parameters: smoothing size %d (2..128), min inliers %d (>= 0), refine %d (0 or 1), "
-                    "every threshold finite", q.smoothing_size, q.min_inliers, q.refine);
-    return PBD_OK;
-}
-
-// organized clouds: the pbd_cloud rules, rows >= 2 and cols >= 2, and fewer than 2^31 points in the whole call
-int check_organized(pbd_handle *h, int nclouds, const pbd_cloud *c, bool host)
-{
-    if (int rc = check_clouds(h, nclouds, c, host)) return rc;
-    long long total = 0;
-    for (int f = 0; f < nclouds; ++f) {
-        if (c[f].rows < 2 || c[f].cols < 2)
-            return fail(h, PBD_ERR_INVALID, "cloud %d: %dx%d is not organized (rows and cols >= 2)", f, c[f].rows, c[f].cols);
-        total += (long long)c[f].rows * c[f].cols;
-    }
-    if (total >= (1LL << 31)) return fail(h, PBD_ERR_INVALID, "the clouds of one call hold %lld points (below 2^31)", total);
-    return PBD_OK;
-}
-
-// the plane-removal workspace: one 256-byte aligned piece per array, in the order enqueue_planes carves them.  cand_cap bounds the
-// segments above min_inliers: at most points / (min_inliers + 1) per cloud
-constexpr int kPlPieces = 17;
-struct PlaneLayout {
-    long long cand_cap, total;
-    long long sizes[kPlPieces];
-};
-void plane_layout(int nclouds, long long npts, long long nrows, long long cand_cap, PlaneLayout &L)
-{
-    const long long n = npts, c = cand_cap + 1, tiles = (n + 1023) / 1024 + 2;
-    const long long sizes[kPlPieces] = {n * 16, n * 16, n * 16, n * 16, n * 4, n * 4, (n + 1) * 4, n * 4, tiles * 8, c * 4, c * 4,
-                                        c * 4, c * 16, c * 16, ((long long)nclouds + 1) * 4, (long long)nclouds * 4, 2 * nrows * 8};
-    L.cand_cap = cand_cap;
-    L.total = 0;
-    for (int i = 0; i < kPlPieces; ++i) {
-        L.sizes[i] = sizes[i];
-        L.total += (sizes[i] + 255) / 256 * 256;
-    }
-}
-
-// the workspace, the cloud table and the fixed sequence of launches; outputs as pbd_remove_planes_device
-int enqueue_planes(pbd_handle *h, const std::vector<PlaneCloud> &tab, const pbd_plane_params &q, float *d_points, int32_t *d_kept,
-                   int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers, int32_t *d_nplanes, int plane_cap,
-                   long long *d_status)
-{
-    const int nclouds = (int)tab.size() - 1;
-    long long cand_cap = 0, nrows = 0;
-    for (int i = 0; i < nclouds; ++i) {
-        cand_cap += (long long)tab[i].rows * tab[i].cols / ((long long)q.min_inliers + 1);
-        nrows += tab[i].rows;
-    }
-    const long long npts = tab[nclouds].base;
-    PlaneLayout L;
-    plane_layout(nclouds, npts, nrows, cand_cap, L);
-    HIPCHK(h, h->pl_ws.ensure((size_t)L.total));
-    if (int rc = stage_table(h, h->pl_tab_host, h->pl_tab, h->pl_tab_copied, tab.data(), tab.size() * sizeof(PlaneCloud))) return rc;
-    uint8_t *w = h->pl_ws.as<uint8_t>();
-    int piece = 0;
-    auto carve = [&]() { uint8_t *ptr = w; w += (L.sizes[piece++] + 255) / 256 * 256; return (void *)ptr; };
-    PlaneParams p{};
-    p.clouds = h->pl_tab.as<PlaneCloud>(); p.nclouds = nclouds; p.npts = npts;
-    p.half = q.smoothing_size / 2;
-    p.depth_change = q.depth_change_factor; p.dist_thr = q.distance_threshold;
-    p.cos_thr = (float)cos(q.angular_threshold);
-    p.max_curv = q.max_curvature; p.min_inliers = q.min_inliers;
-    p.plane_cap = plane_cap; p.cand_cap = (int)std::min<long long>(cand_cap, INT32_MAX);
-    p.xyz = (float4 *)carve(); p.rsx = (float4 *)carve(); p.rsy = (float4 *)carve(); p.nrm = (float4 *)carve();
-    p.parent = (int32_t *)carve(); p.csize = (int32_t *)carve(); p.flag = (int32_t *)carve(); p.lab = (int32_t *)carve();
-    p.part = (long long *)carve();
-    p.cand_root = (int32_t *)carve(); p.cand_plane = (int32_t *)carve(); p.plane_cnt = (int32_t *)carve();
-    p.cand_coef = (float4 *)carve(); p.plane_coef = (float4 *)carve();
-    p.cbase = (int32_t *)carve(); p.np = (int32_t *)carve(); p.xch = (int2 *)carve();
-    p.points = d_points; p.kept = d_kept; p.nkept = d_nkept; p.labels = d_labels; p.planes = d_planes; p.inliers = d_inliers;
-    p.nplanes = d_nplanes; p.status = d_status;
-    for (int step = 0; step < kPlSteps; ++step)
-        if (step != kPlStepRefine || q.refine) launch_planes_step(p, step, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-// the cloud table of a call: every cloud's place in the concatenation, one closing entry holding the point total
-std::vector<PlaneCloud> plane_table(int nclouds, const pbd_cloud *c)
-{
-    std::vector<PlaneCloud> tab(nclouds + 1);
-    long long base = 0, rbase = 0;
-    for (int f = 0; f < nclouds; ++f) {
-        tab[f] = PlaneCloud{static_cast<const uint8_t *>(c[f].data), c[f].rows, c[f].cols, (long long)c[f].point_stride,
-                            (long long)c[f].row_stride, base, rbase};
-        base += (long long)c[f].rows * c[f].cols;
-        rbase += c[f].rows;
-    }
-    tab[nclouds] = PlaneCloud{nullptr, 0, 0, 0, 0, base, rbase};
-    return tab;
-}
-
-// a (frame, level) of the resident result -> (frame index into the buffers, level of the plan); mixed plans: frame 0, the
-// frame's level in the virtual table
-bool resident_level(const Resident &r, int frame, int level, int *bf, int *bl)
-{
-    const Plan &P = *r.plan;
-    if (P.kind == 2) {
-        if (frame < 0 || frame >= P.mixed_frames || level < 0 || level >= P.frame_lv0[frame + 1] - P.frame_lv0[frame]) return false;
-        *bf = 0; *bl = P.frame_lv0[frame] + level;
-        return true;
-    }
-    if (frame < 0 || frame >= r.frames || level < 0 || level >= P.nlevels) return false;
-    *bf = frame; *bl = level;
-    return true;
-}
-
-// pbd_examples*: the resident result a record can be walked in (PBD_OK or the failure's status code)
-// the handle whose buffers hold the resident result: the latent twin after pbd_detect_latent
-pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->lat ? h->lat.get() : h; }
-
-int check_examples_state(pbd_handle *h)
-{
-    const Resident &r = resident_owner(h)->res;
-    if (!r.plan || (r.plan->kind != 0 && r.plan->kind != 2) || !r.features || !r.dp)
-        return fail(h, PBD_ERR_STATE, "no resident detect result (pbd_detect* computes one; pbd_dp_min and pbd_conv_set_filters leave none)");
-    if (!h->bank_matches_model || h->filter_ksize != h->model_ksize)
-        return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
-    return PBD_OK;
-}
-
-// the walk and the gather of min(max(word 0, 0), capacity) records of d_in into d_hdr / d_values, on the handle's stream
-int enqueue_examples(pbd_handle *h, const int32_t *d_in, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
-{
-    pbd_handle *o = resident_owner(h);   // its maps and features; the model tables (filter ids, offsets) stay this handle's
-    Plan &P = *o->res.plan;
-    if (!h->ex_gm.p) {
-        std::vector<ExGm> gm(h->totmix);
-        for (int i = 0; i < h->totmix; ++i) gm[i] = ExGm{h->filterid[i], h->biasid[i], h->defid[i], 0};
-        HIPCHK(h, h->ex_gm.upload(gm));
-        std::vector<int> anc(h->anchors);
-        anc.push_back(0);
-        HIPCHK(h, h->ex_anchors.upload(anc));
-        HIPCHK(h, h->ex_foff.upload(h->model_foff));
-    }
-    if (P.kind == 2 && !P.d_frame_lv0.p) HIPCHK(h, P.d_frame_lv0.upload(P.frame_lv0));
-    HIPCHK(h, h->ex_ws.ensure(std::max<size_t>((size_t)capacity * h->max_parts * sizeof(ExPart), 16)));
-    ExampleParams ep{};
-    ep.in = d_in; ep.in_cap = capacity; ep.stride = stride(h); ep.frame_offset = frame_offset;
-    ep.lv = P.d_lv.p; ep.nlevels = P.nlevels;
-    ep.nframes = P.kind == 2 ? P.mixed_frames : o->res.frames;
-    ep.frame_lv0 = P.kind == 2 ? P.d_frame_lv0.p : nullptr;
-    ep.cell_per_frame = P.cell_per_frame;
-    ep.NC = h->NC; ep.NS = h->NS; ep.NJ = h->totmix; ep.ptr8 = P.ptr8 ? 1 : 0; ep.flen = 32; ep.max_parts = h->max_parts;
-    ep.rooti = o->rooti.as<int>(); ep.IxRaw = o->IxRaw.p; ep.IyRaw = o->IyRaw.p; ep.Ik = o->Ik.as<uint8_t>();
-    ep.walk = h->d_walk.p; ep.walk_off = h->d_walk_off.p;
-    ep.gm = h->ex_gm.p; ep.anchors = h->ex_anchors.p; ep.foff = h->ex_foff.p; ep.nbias = h->nbias; ep.ndefs = h->ndefs;
-    ep.feat = o->feat.p;
-    ep.parts = h->ex_ws.as<ExPart>();
-    ep.hdr = d_hdr; ep.hdr_words = h->ex_hdr_words;
-    ep.values = d_values; ep.vstride = h->ex_values;
-    { ProfScope ps(h, PBD_K_EX_WALK, h->stream); launch_examples(ep, h->f64, 0, h->stream); }
-    { ProfScope ps(h, PBD_K_EX_GATHER, h->stream); launch_examples(ep, h->f64, 1, h->stream); }
-    HIPCHK(h, hipGetLastError());
-    return PBD_OK;
-}
-
-}  // namespace
+}  // namespace pbd
 
 // ================================================================================================
 extern "C" {
@@ -2735,16 +1661,6 @@ const char *pbd_version(void) { return "pbd-hip 0.1 (gfx950)"; }
 
 // diagnostics, not part of include/pbd.h
 int pbd_debug_conv_occupancy(int nw) { return nw == 5 ? conv_mfma_occupancy(false) : nw == 6 ? conv_mfma_occupancy(true) : conv_occupancy(nw); }
-// the clustering workspace of pbd_cluster_objects* (host-only, no GPU needed): out = {nchunks, units, tcap, nparts, total, the
-// 14 piece sizes}; PBD_ERR_INVALID for a crop capacity the calls refuse
-int pbd_debug_cluster_layout(int capacity, long long maxpts, long long crop_cap, long long *out)
-{
-    ClusterLayout L;
-    if (int rc = cluster_layout(capacity, maxpts, crop_cap, L)) return rc;
-    out[0] = L.nchunks; out[1] = L.units; out[2] = L.tcap; out[3] = L.nparts; out[4] = L.total;
-    for (int i = 0; i < kClPieces; ++i) out[5 + i] = L.sizes[i];
-    return PBD_OK;
-}
 // the convolution's tile cover of one rows x cols level (host-only, no GPU needed): out[i] = {shape, y0, x0}
 int pbd_debug_cover_level(int rows, int cols, int *out, int capacity)
 {
@@ -2904,6 +1820,7 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
         if (e != hipSuccess) return fail(nullptr, PBD_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
         std::unique_ptr<pbd_handle, void (*)(pbd_handle *)> h(new pbd_handle, pbd_destroy);   // releases device memory on every exit
         h->cfg = *config;
+        h->device = config->device;
         h->f64 = config->real_type == PBD_REAL_F64;
         h->rs = h->f64 ? sizeof(double) : sizeof(float);
         h->resp_half = config->conv_mode == PBD_CONV_MFMA_F16 && !h->f64;
@@ -2929,7 +1846,7 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
 void pbd_destroy(pbd_handle *h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
+    (void)hipSetDevice(h->device);
     for (hipStream_t s : {h->stream.s, h->stream_copy.s, h->stream_d2h.s})   // work in flight ends before its memory is freed
         if (s) (void)hipStreamSynchronize(s);
     try {
@@ -3292,336 +2209,6 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
     });
 }
 
-// Candidate::boundingBox3D(im, depth) per record (include/Candidate.hpp:140-216).  See include/pbd.h.
-int pbd_boxes3d(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
-                const int32_t *cand, int ncand, int frame_offset, double *out)
-{
-    return entry(h, depth && im_rows && im_cols && (ncand <= 0 || (cand && out)), kIdle, [&]() -> int {
-        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
-        if (int rc = check_boxes3d_frames(h, nframes, depth, depth_code, im_rows, im_cols, true)) return rc;
-        if (int rc = check_boxes3d_records(h, nframes, cand, ncand, frame_offset)) return rc;
-        if (ncand == 0) return PBD_OK;
-        HIPCHK(h, h->b3_out.ensure((size_t)ncand * 6 * sizeof(double)));
-        std::vector<Box3dFrame> tab;
-        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, im_rows, im_cols, cand, ncand, tab)) return rc;
-        if (int rc = enqueue_boxes3d(h, tab, depth_code, h->b3_rec.as<int32_t>(), ncand, frame_offset, h->b3_out.as<double>())) return rc;
-        HIPCHK(h, hipMemcpyAsync(out, h->b3_out.p, (size_t)ncand * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_boxes3d_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, const int *im_rows, const int *im_cols,
-                       const int32_t *d_payload, int capacity, int frame_offset, double *d_out)
-{
-    return entry(h, d_depth && im_rows && im_cols && d_payload && (capacity <= 0 || d_out), kIdle, [&]() -> int {
-        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (int rc = check_boxes3d_frames(h, nframes, d_depth, depth_code, im_rows, im_cols, false)) return rc;
-        if (capacity == 0) return PBD_OK;
-        std::vector<Box3dFrame> tab(nframes);
-        for (int f = 0; f < nframes; ++f)
-            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
-                                (long long)d_depth[f].stride_bytes, im_rows[f], im_cols[f]};
-        return enqueue_boxes3d(h, tab, depth_code, d_payload, capacity, frame_offset, d_out);
-    });
-}
-
-// SearchSpacePruning<T>::filterCandidatesByDepth (src/SearchSpacePruning.cpp:73-95).  See include/pbd.h.
-int pbd_depth_consistency(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, float zfactor, const int32_t *cand, int ncand,
-                          int frame_offset, int32_t *out, int capacity, int *nout)
-{
-    return entry(h, depth && nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
-        *nout = 0;
-        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
-        if (int rc = check_dc_frames(h, nframes, depth, depth_code, zfactor, true)) return rc;
-        if (int rc = check_dc_records(h, nframes, cand, ncand, frame_offset)) return rc;
-        if (ncand == 0) return PBD_OK;
-        // the depth images packed with dense rows (the pbd_boxes3d host form's buffers)
-        const std::vector<int> ones(nframes, 1);
-        std::vector<Box3dFrame> tab;
-        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, ones.data(), ones.data(), cand, 0, tab)) return rc;
-        return host_list_call(h, h->dc_rec, h->dc_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
-            return enqueue_dc(h, tab, depth_code, zfactor, din, ncand, frame_offset, dout, ncand);
-        });
-    });
-}
-
-int pbd_depth_consistency_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, float zfactor,
-                                 const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity)
-{
-    return entry(h, d_depth && d_payload && d_out, kIdle, [&]() -> int {
-        if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
-        if (int rc = check_dc_frames(h, nframes, d_depth, depth_code, zfactor, false)) return rc;
-        std::vector<Box3dFrame> tab(nframes);
-        for (int f = 0; f < nframes; ++f)
-            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
-                                (long long)d_depth[f].stride_bytes, 0, 0};
-        return enqueue_dc(h, tab, depth_code, zfactor, d_payload, capacity, frame_offset, d_out, out_capacity);
-    });
-}
-
-// Candidate::sort + Candidate::nonMaximaSuppression of a caller's list (the pbd_set_nms stage).  See include/pbd.h.
-int pbd_suppress(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap, const int32_t *cand, int ncand,
-                 int frame_offset, int32_t *out, int capacity, int *nout)
-{
-    return entry(h, im_rows && im_cols && nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
-        *nout = 0;
-        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
-        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
-        Plan *P = nullptr;
-        if (int rc = get_suppress_plan(h, nframes, im_rows, im_cols, &P)) return rc;
-        const int stride = ::stride(h);
-        for (int i = 0; i < ncand; ++i) {
-            const int32_t *r = cand + (size_t)i * stride;
-            const long long f = (long long)r[0] - frame_offset;
-            const long long g = i > 0 ? (long long)cand[(size_t)(i - 1) * stride] - frame_offset : 0;
-            if (f < 0 || f >= nframes || f < g)
-                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d or below the previous record's", i,
-                            r[0], frame_offset, nframes - 1);
-            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
-        }
-        if (ncand == 0) return PBD_OK;
-        return host_list_call(h, h->sup_in, h->sup_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
-            return enqueue_post(h, nframes, 0, 0, overlap, din, ncand, 0, dout, ncand, h->stream, P, frame_offset);
-        });
-    });
-}
-
-int pbd_suppress_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap, const int32_t *d_payload,
-                        int capacity, int frame_offset, int32_t *d_out, int out_capacity)
-{
-    return entry(h, im_rows && im_cols && d_payload && d_out, kIdle, [&]() -> int {
-        if (capacity < 1 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d (>= 1), out_capacity %d", capacity, out_capacity);
-        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
-        Plan *P = nullptr;
-        if (int rc = get_suppress_plan(h, nframes, im_rows, im_cols, &P)) return rc;
-        HIPCHK(h, h->sup_bad.ensure(sizeof(int)));
-        if (int rc = enqueue_post(h, nframes, 0, 0, overlap, d_payload, capacity, 0, d_out, out_capacity, h->stream, P, frame_offset,
-                                  h->sup_bad.as<int>())) return rc;
-        HIPCHK(h, hipGetLastError());
-        return PBD_OK;
-    });
-}
-
-// PointCloudClusterer::computeBoundingBoxes after boundingBox3D (include/PointCloudClusterer.hpp:53-153).  See include/pbd.h.
-int pbd_boxes3d_camera(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code, const int *im_rows, const int *im_cols,
-                       const pbd_pinhole *cams, int parts_mode, const int32_t *cand, int ncand, int frame_offset, double *box,
-                       float *centres, int32_t *ncentres, int32_t *dense)
-{
-    return entry(h, depth && im_rows && im_cols && cams && (ncand <= 0 || (cand && box && centres && ncentres && dense)), kIdle,
-                 [&]() -> int {
-        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
-        if (depth_code != kDepth32F) return check_camera(h, nframes, depth_code, cams, parts_mode);
-        if (int rc = check_boxes3d_frames(h, nframes, depth, depth_code, im_rows, im_cols, true)) return rc;
-        if (int rc = check_camera(h, nframes, depth_code, cams, parts_mode)) return rc;
-        if (int rc = check_boxes3d_records(h, nframes, cand, ncand, frame_offset)) return rc;
-        if (ncand == 0) return PBD_OK;
-        const size_t nb = (size_t)ncand * 6 * sizeof(double), nc = (size_t)ncand * h->max_parts * 3 * sizeof(float),
-                     ni = (size_t)ncand * sizeof(int32_t);
-        HIPCHK(h, h->cam_out.ensure(nb + nc + 2 * ni));
-        uint8_t *o = h->cam_out.as<uint8_t>();
-        std::vector<Box3dFrame> tab;
-        if (int rc = upload_boxes3d_host(h, nframes, depth, depth_code, im_rows, im_cols, cand, ncand, tab)) return rc;
-        HIPCHK(h, hipMemsetAsync(o + nb, 0, nc, h->stream));
-        if (int rc = enqueue_camera(h, tab, depth_code, cams, parts_mode, h->b3_rec.as<int32_t>(), ncand, frame_offset, (double *)o,
-                                    (float *)(o + nb), (int32_t *)(o + nb + nc), (int32_t *)(o + nb + nc + ni))) return rc;
-        HIPCHK(h, hipMemcpyAsync(box, o, nb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(centres, o + nb, nc, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(ncentres, o + nb + nc, ni, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(dense, o + nb + nc + ni, ni, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_boxes3d_camera_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code, const int *im_rows,
-                              const int *im_cols, const pbd_pinhole *cams, int parts_mode, const int32_t *d_payload, int capacity,
-                              int frame_offset, double *d_box, float *d_centres, int32_t *d_ncentres, int32_t *d_dense)
-{
-    return entry(h, d_depth && im_rows && im_cols && cams && d_payload && (capacity <= 0 || (d_box && d_centres && d_ncentres && d_dense)),
-                 kIdle, [&]() -> int {
-        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (depth_code != kDepth32F) return check_camera(h, nframes, depth_code, cams, parts_mode);
-        if (int rc = check_boxes3d_frames(h, nframes, d_depth, depth_code, im_rows, im_cols, false)) return rc;
-        if (int rc = check_camera(h, nframes, depth_code, cams, parts_mode)) return rc;
-        if (capacity == 0) return PBD_OK;
-        std::vector<Box3dFrame> tab(nframes);
-        for (int f = 0; f < nframes; ++f)
-            tab[f] = Box3dFrame{static_cast<const uint8_t *>(d_depth[f].data), d_depth[f].rows, d_depth[f].cols,
-                                (long long)d_depth[f].stride_bytes, im_rows[f], im_cols[f]};
-        return enqueue_camera(h, tab, depth_code, cams, parts_mode, d_payload, capacity, frame_offset, d_box, d_centres, d_ncentres,
-                              d_dense);
-    });
-}
-
-// PointCloudClusterer::clusterObjects (include/PointCloudClusterer.hpp:157-293).  See include/pbd.h.
-int pbd_cluster_objects(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const double *boxes, const int *frames, int nboxes,
-                        float *centres, int32_t *counts, int32_t *indices, int index_capacity, int *needed)
-{
-    return entry(h, clouds && needed && (nboxes <= 0 || (boxes && frames && centres && counts)) && (index_capacity <= 0 || indices),
-                 kIdle, [&]() -> int {
-        *needed = 0;
-        if (nboxes < 0 || index_capacity < 0) return fail(h, PBD_ERR_INVALID, "nboxes %d, index capacity %d", nboxes, index_capacity);
-        if (int rc = check_clouds(h, nclouds, clouds, true)) return rc;
-        for (int i = 0; i < nboxes; ++i)
-            if (frames[i] < 0 || frames[i] >= nclouds) return fail(h, PBD_ERR_INVALID, "box %d: frame %d outside 0..%d", i, frames[i], nclouds - 1);
-        if (nboxes == 0) return PBD_OK;
-        // the clouds' x, y, z, packed
-        size_t total = 0;
-        for (int f = 0; f < nclouds; ++f) total += (size_t)clouds[f].rows * clouds[f].cols;
-        std::vector<float> packed(total * 3);
-        std::vector<CloudFrame> tab(nclouds);
-        HIPCHK(h, h->cl_cloud.ensure(total * 12 + 16));
-        size_t off = 0;
-        for (int f = 0; f < nclouds; ++f) {
-            const pbd_cloud &c = clouds[f];
-            for (int r = 0; r < c.rows; ++r)
-                for (int k = 0; k < c.cols; ++k)
-                    memcpy(&packed[(off + (size_t)r * c.cols + k) * 3],
-                           static_cast<const uint8_t *>(c.data) + r * c.row_stride + k * c.point_stride, 12);
-            tab[f] = CloudFrame{h->cl_cloud.as<uint8_t>() + off * 12, c.rows, c.cols, 12, (long long)c.cols * 12};
-            off += (size_t)c.rows * c.cols;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->cl_cloud.p, packed.data(), total * 12, hipMemcpyHostToDevice, h->stream));
-        // the boxes and a payload of stride 1 holding the frames
-        const size_t bb = (size_t)nboxes * 6 * sizeof(double), pb = ((size_t)nboxes + 1) * sizeof(int32_t);
-        HIPCHK(h, h->cl_in.ensure(bb + pb + 16));
-        std::vector<int32_t> pay(nboxes + 1);
-        pay[0] = nboxes;
-        for (int i = 0; i < nboxes; ++i) pay[i + 1] = frames[i];
-        HIPCHK(h, hipMemcpyAsync(h->cl_in.p, boxes, bb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cl_in.as<uint8_t>() + bb, pay.data(), pb, hipMemcpyHostToDevice, h->stream));
-        const double *d_boxes = h->cl_in.as<double>();
-        const int32_t *d_pay = reinterpret_cast<const int32_t *>(h->cl_in.as<uint8_t>() + bb);
-        // outputs: centres, counts, status, then the indices (at most the cropped points)
-        long long crop_cap = std::max<long long>(h->cl_crop_cap, 1 << 16);
-        long long status[2] = {0, 0};
-        for (int pass = 0; pass < 2; ++pass) {
-            const size_t oc = (size_t)nboxes * 12, on = (size_t)nboxes * 4;
-            HIPCHK(h, h->cl_out.ensure(oc + on + 16 + 16 + (size_t)crop_cap * 4));
-            uint8_t *o = h->cl_out.as<uint8_t>();
-            long long *d_status = reinterpret_cast<long long *>(o + (oc + on + 15) / 16 * 16);
-            int32_t *d_idx = reinterpret_cast<int32_t *>(d_status + 2);
-            if (int rc = enqueue_cluster(h, tab, d_pay, nboxes, 1, 0, d_boxes, (int)crop_cap, (int)crop_cap, (float *)o,
-                                         (int32_t *)(o + oc), d_idx, d_status)) return rc;
-            HIPCHK(h, hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (status[0] <= crop_cap) {
-                h->cl_crop_cap = std::max(h->cl_crop_cap, crop_cap);
-                if (status[1] > index_capacity) {
-                    *needed = (int)status[1];
-                    return fail(h, PBD_ERR_CAPACITY, "the kept clusters hold %lld indices, capacity %d", status[1], index_capacity);
-                }
-                *needed = (int)status[1];
-                HIPCHK(h, hipMemcpyAsync(centres, o, oc, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipMemcpyAsync(counts, o + oc, on, hipMemcpyDeviceToHost, h->stream));
-                if (status[1] > 0) HIPCHK(h, hipMemcpyAsync(indices, d_idx, (size_t)status[1] * 4, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                return PBD_OK;
-            }
-            if (status[0] > kClMaxCrop) return fail(h, PBD_ERR_INVALID, "%lld cropped points (at most 2^29)", status[0]);
-            crop_cap = status[0];                      // the first pass counted them all: the second fits
-        }
-        return fail(h, PBD_ERR_HIP, "cropped points changed between two passes");
-    });
-}
-
-int pbd_cluster_objects_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const int32_t *d_payload, int capacity,
-                               int frame_offset, const double *d_boxes, int crop_capacity, int index_capacity, float *d_centres,
-                               int32_t *d_counts, int32_t *d_indices, long long *d_status)
-{
-    return entry(h, d_clouds && d_payload && d_status && (capacity <= 0 || (d_boxes && d_centres && d_counts)) &&
-                    (index_capacity <= 0 || d_indices), kIdle, [&]() -> int {
-        if (capacity < 0 || crop_capacity < 0 || index_capacity < 0 || crop_capacity > kClMaxCrop)
-            return fail(h, PBD_ERR_INVALID, "capacity %d, crop capacity %d (at most 2^29), index capacity %d", capacity, crop_capacity,
-                        index_capacity);
-        if (int rc = check_clouds(h, nclouds, d_clouds, false)) return rc;
-        if (capacity == 0) {
-            HIPCHK(h, hipMemsetAsync(d_status, 0, 2 * sizeof(long long), h->stream));
-            return PBD_OK;
-        }
-        std::vector<CloudFrame> tab(nclouds);
-        for (int f = 0; f < nclouds; ++f)
-            tab[f] = CloudFrame{static_cast<const uint8_t *>(d_clouds[f].data), d_clouds[f].rows, d_clouds[f].cols,
-                                (long long)d_clouds[f].point_stride, (long long)d_clouds[f].row_stride};
-        return enqueue_cluster(h, tab, d_payload, capacity, stride(h), frame_offset, d_boxes, crop_capacity, index_capacity, d_centres,
-                               d_counts, d_indices, d_status);
-    });
-}
-
-// PointCloudClusterer::organizedMultiplaneSegmentation (include/PointCloudClusterer.hpp:294-336).  See include/pbd.h.
-int pbd_remove_planes(pbd_handle *h, int nclouds, const pbd_cloud *clouds, const pbd_plane_params *params, float *points, int32_t *kept,
-                      int32_t *nkept, int32_t *labels, float *planes, int32_t *inliers, int32_t *nplanes, int plane_capacity, int *needed)
-{
-    return entry(h, clouds && points && kept && nkept && labels && nplanes && needed && (plane_capacity <= 0 || (planes && inliers)),
-                 kIdle, [&]() -> int {
-        *needed = 0;
-        const pbd_plane_params q = params ? *params : plane_defaults();
-        if (plane_capacity < 0) return fail(h, PBD_ERR_INVALID, "plane capacity %d", plane_capacity);
-        if (int rc = check_plane_params(h, q)) return rc;
-        if (int rc = check_organized(h, nclouds, clouds, true)) return rc;
-        // the clouds' x, y, z, packed
-        std::vector<pbd_cloud> packed_desc(nclouds);
-        size_t total = 0;
-        for (int f = 0; f < nclouds; ++f) total += (size_t)clouds[f].rows * clouds[f].cols;
-        std::vector<float> packed(total * 3);
-        HIPCHK(h, h->pl_cloud.ensure(total * 12 + 16));
-        size_t off = 0;
-        for (int f = 0; f < nclouds; ++f) {
-            const pbd_cloud &c = clouds[f];
-            for (int r = 0; r < c.rows; ++r)
-                for (int k = 0; k < c.cols; ++k)
-                    memcpy(&packed[(off + (size_t)r * c.cols + k) * 3],
-                           static_cast<const uint8_t *>(c.data) + r * c.row_stride + k * c.point_stride, 12);
-            packed_desc[f] = pbd_cloud{h->pl_cloud.as<uint8_t>() + off * 12, c.rows, c.cols, 12, (size_t)c.cols * 12};
-            off += (size_t)c.rows * c.cols;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->pl_cloud.p, packed.data(), total * 12, hipMemcpyHostToDevice, h->stream));
-        // outputs: status, counts, then points, kept, labels, planes, inliers
-        const size_t cap = (size_t)std::max(plane_capacity, 0);
-        const size_t o_stat = 0, o_nk = 16, o_np = o_nk + (size_t)nclouds * 4, o_pts = (o_np + (size_t)nclouds * 4 + 15) / 16 * 16,
-                     o_kept = o_pts + total * 12, o_lab = o_kept + total * 4, o_pl = (o_lab + total * 4 + 15) / 16 * 16,
-                     o_in = o_pl + (size_t)nclouds * cap * 16, o_end = o_in + (size_t)nclouds * cap * 4;
-        HIPCHK(h, h->pl_out.ensure(o_end + 16));
-        uint8_t *o = h->pl_out.as<uint8_t>();
-        if (int rc = enqueue_planes(h, plane_table(nclouds, packed_desc.data()), q, (float *)(o + o_pts), (int32_t *)(o + o_kept),
-                                    (int32_t *)(o + o_nk), (int32_t *)(o + o_lab), (float *)(o + o_pl), (int32_t *)(o + o_in),
-                                    (int32_t *)(o + o_np), (int)cap, (long long *)(o + o_stat))) return rc;
-        long long status[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(status, o + o_stat, sizeof status, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *needed = (int)status[1];
-        if (status[1] > plane_capacity)
-            return fail(h, PBD_ERR_CAPACITY, "a cloud holds %lld planes, capacity %d", status[1], plane_capacity);
-        HIPCHK(h, hipMemcpyAsync(nkept, o + o_nk, (size_t)nclouds * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(nplanes, o + o_np, (size_t)nclouds * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(points, o + o_pts, total * 12, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(kept, o + o_kept, total * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(labels, o + o_lab, total * 4, hipMemcpyDeviceToHost, h->stream));
-        if (cap) {
-            HIPCHK(h, hipMemcpyAsync(planes, o + o_pl, (size_t)nclouds * cap * 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipMemcpyAsync(inliers, o + o_in, (size_t)nclouds * cap * 4, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_remove_planes_device(pbd_handle *h, int nclouds, const pbd_cloud *d_clouds, const pbd_plane_params *params, float *d_points,
-                             int32_t *d_kept, int32_t *d_nkept, int32_t *d_labels, float *d_planes, int32_t *d_inliers,
-                             int32_t *d_nplanes, int plane_capacity, long long *d_status)
-{
-    return entry(h, d_clouds && d_points && d_kept && d_nkept && d_labels && d_nplanes && d_status &&
-                    (plane_capacity <= 0 || (d_planes && d_inliers)), kIdle, [&]() -> int {
-        const pbd_plane_params q = params ? *params : plane_defaults();
-        if (plane_capacity < 0) return fail(h, PBD_ERR_INVALID, "plane capacity %d", plane_capacity);
-        if (int rc = check_plane_params(h, q)) return rc;
-        if (int rc = check_organized(h, nclouds, d_clouds, false)) return rc;
-        return enqueue_planes(h, plane_table(nclouds, d_clouds), q, d_points, d_kept, d_nkept, d_labels, d_planes, d_inliers, d_nplanes,
-                              plane_capacity, d_status);
-    });
-}
-
 // Mixed-size calls (new surface): nframes frames of any sizes, planned as one virtual frame.  See include/pbd.h.
 int pbd_detect_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int32_t *cand, int capacity,
                       int *ncand)
@@ -3698,284 +2285,6 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
     });
 }
 
-// Candidate::mask (include/Candidate.hpp:306-331) and rgb & (mask != 0) (ros/Messages.cpp:157-174).  See include/pbd.h.
-int pbd_candidate_mask(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *cand, int ncand, int frame_offset,
-                       uint8_t *const *labels, const size_t *label_pitch, int channels, const uint8_t *const *colour,
-                       const size_t *colour_pitch, uint8_t *const *masked, const size_t *masked_pitch)
-{
-    return entry(h, im_rows && im_cols && (ncand <= 0 || cand), kIdle, [&]() -> int {
-        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
-        if (int rc = check_mask_frames(h, nframes, im_rows, im_cols, labels, label_pitch, channels, colour, colour_pitch, masked,
-                                       masked_pitch)) return rc;
-        const int stride = ::stride(h);
-        for (int i = 0; i < ncand; ++i) {
-            const int32_t *r = cand + (size_t)i * stride;
-            const long long f = (long long)r[0] - frame_offset;
-            const long long g = i > 0 ? (long long)cand[(size_t)(i - 1) * stride] - frame_offset : 0;
-            if (f < 0 || f >= nframes || f < g)
-                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d outside 0..%d or below the previous record's", i,
-                            r[0], frame_offset, nframes - 1);
-            if (r[6] < 1 || r[6] > h->max_parts) return fail(h, PBD_ERR_INVALID, "record %d: nparts %d (1..%d)", i, r[6], h->max_parts);
-        }
-        if (!labels && !masked) return PBD_OK;
-        const int cn = masked ? channels : 0;
-        // the records as a payload, each frame's labels and colour packed with dense rows in the handle's own buffers
-        size_t lab_total = 0, img_total = 0;
-        for (int f = 0; f < nframes; ++f) {
-            lab_total += labels ? (size_t)im_rows[f] * im_cols[f] : 0;
-            img_total += (size_t)im_rows[f] * im_cols[f] * cn;
-        }
-        const size_t lab_bytes = (lab_total + 255) / 256 * 256;
-        HIPCHK(h, h->mk_img.ensure(lab_bytes + img_total + 256));
-        HIPCHK(h, h->mk_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
-        HIPCHK(h, hipMemcpyAsync(h->mk_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        if (ncand) HIPCHK(h, hipMemcpyAsync(h->mk_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t),
-                                            hipMemcpyHostToDevice, h->stream));
-        std::vector<MaskFrame> tab(nframes);
-        uint8_t *lab = h->mk_img.as<uint8_t>(), *img = lab + lab_bytes;
-        for (int f = 0; f < nframes; ++f) {
-            const size_t lrow = (size_t)im_cols[f], crow = lrow * cn;
-            MaskFrame &fr = tab[f];
-            fr = MaskFrame{};
-            fr.rows = im_rows[f]; fr.cols = im_cols[f];
-            if (labels) { fr.labels = lab; fr.label_pitch = (long long)lrow; lab += lrow * im_rows[f]; }
-            if (masked) {
-                HIPCHK(h, hipMemcpy2DAsync(img, crow, colour[f], colour_pitch[f], crow, im_rows[f], hipMemcpyHostToDevice, h->stream));
-                fr.colour = img; fr.masked = img; fr.colour_pitch = fr.masked_pitch = (long long)crow;
-                img += crow * im_rows[f];
-            }
-        }
-        if (int rc = enqueue_mask(h, tab, cn, h->mk_rec.as<int32_t>(), ncand, frame_offset, nullptr)) return rc;
-        for (int f = 0; f < nframes; ++f) {
-            if (labels)
-                HIPCHK(h, hipMemcpy2DAsync(labels[f], label_pitch[f], tab[f].labels, (size_t)im_cols[f], (size_t)im_cols[f], im_rows[f],
-                                           hipMemcpyDeviceToHost, h->stream));
-            if (masked) {
-                const size_t crow = (size_t)im_cols[f] * cn;
-                HIPCHK(h, hipMemcpy2DAsync(masked[f], masked_pitch[f], tab[f].masked, crow, crow, im_rows[f], hipMemcpyDeviceToHost,
-                                           h->stream));
-            }
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_candidate_mask_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, const int32_t *d_payload, int capacity,
-                              int frame_offset, uint8_t *const *d_labels, const size_t *label_pitch, int channels,
-                              const uint8_t *const *d_colour, const size_t *colour_pitch, uint8_t *const *d_masked,
-                              const size_t *masked_pitch, int32_t *d_status)
-{
-    return entry(h, im_rows && im_cols && d_payload && d_status, kIdle, [&]() -> int {
-        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (int rc = check_mask_frames(h, nframes, im_rows, im_cols, d_labels, label_pitch, channels, d_colour, colour_pitch, d_masked,
-                                       masked_pitch)) return rc;
-        std::vector<MaskFrame> tab(nframes);
-        for (int f = 0; f < nframes; ++f) {
-            MaskFrame &fr = tab[f];
-            fr = MaskFrame{};
-            fr.rows = im_rows[f]; fr.cols = im_cols[f];
-            if (d_labels) { fr.labels = d_labels[f]; fr.label_pitch = (long long)label_pitch[f]; }
-            if (d_masked) {
-                fr.colour = d_colour[f]; fr.masked = d_masked[f];
-                fr.colour_pitch = (long long)colour_pitch[f]; fr.masked_pitch = (long long)masked_pitch[f];
-            }
-        }
-        return enqueue_mask(h, tab, d_masked ? channels : 0, d_payload, capacity, frame_offset, d_status);
-    });
-}
-
-// PartsBasedDetectorNode::messagePoses (ros/Messages.cpp:187-234) per record.  See include/pbd.h.
-int pbd_part_poses(pbd_handle *h, int n, const float *centres, const int32_t *ncentres, const int32_t *dense, int32_t *count,
-                   float *position, float *orientation, float *eigenvalues)
-{
-    return entry(h, n <= 0 || (centres && ncentres && dense && count && position && orientation && eigenvalues), kIdle, [&]() -> int {
-        if (n < 0) return fail(h, PBD_ERR_INVALID, "n %d", n);
-        for (int i = 0; i < n; ++i)
-            if (ncentres[i] < 0 || ncentres[i] > h->max_parts)
-                return fail(h, PBD_ERR_INVALID, "record %d: ncentres %d (0..%d)", i, ncentres[i], h->max_parts);
-        if (n == 0) return PBD_OK;
-        const size_t nc = (size_t)n * h->max_parts * 3 * sizeof(float), ni = (size_t)n * sizeof(int32_t), n3 = (size_t)n * 3 * sizeof(float),
-                     n4 = (size_t)n * 4 * sizeof(float);
-        HIPCHK(h, h->ps_buf.ensure(nc + 3 * ni + 2 * n3 + n4 + 256));
-        uint8_t *b = h->ps_buf.as<uint8_t>();
-        float *d_cen = (float *)b, *d_pos = (float *)(b + nc), *d_ori = (float *)(b + nc + n3), *d_ev = (float *)(b + nc + n3 + n4);
-        int32_t *d_nc = (int32_t *)(b + nc + 2 * n3 + n4), *d_dn = d_nc + n, *d_cnt = d_dn + n, *d_word = d_cnt + n;
-        HIPCHK(h, hipMemcpyAsync(d_word, &n, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_cen, centres, nc, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_nc, ncentres, ni, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_dn, dense, ni, hipMemcpyHostToDevice, h->stream));
-        if (int rc = enqueue_poses(h, d_word, n, d_cen, d_nc, d_dn, d_cnt, d_pos, d_ori, d_ev)) return rc;
-        HIPCHK(h, hipMemcpyAsync(count, d_cnt, ni, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(position, d_pos, n3, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(orientation, d_ori, n4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(eigenvalues, d_ev, n3, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity, const float *d_centres, const int32_t *d_ncentres,
-                          const int32_t *d_dense, int32_t *d_count, float *d_position, float *d_orientation, float *d_eigenvalues)
-{
-    return entry(h, d_payload && (capacity <= 0 || (d_centres && d_ncentres && d_dense && d_count && d_position && d_orientation &&
-                                                    d_eigenvalues)), kIdle, [&]() -> int {
-        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (capacity == 0) return PBD_OK;
-        return enqueue_poses(h, d_payload, capacity, d_centres, d_ncentres, d_dense, d_count, d_position, d_orientation, d_eigenvalues);
-    });
-}
-
-// Training examples (matlab/detection/detect.m backtrack + qp_write).  See include/pbd.h.
-int pbd_model_vector_len(const pbd_handle *h) { return h ? (int)(h->mvec.size() / h->rs) : 0; }
-
-int pbd_model_vector(pbd_handle *h, void *w)
-{
-    return entry(h, w, kBusyOk, [&]() -> int {
-        memcpy(w, h->mvec.data(), h->mvec.size());
-        return PBD_OK;
-    });
-}
-
-int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values)
-{
-    if (!h || !hdr_words || !values) return PBD_ERR_INVALID;
-    *hdr_words = h->ex_hdr_words;
-    *values = h->ex_values;
-    return PBD_OK;
-}
-
-int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values)
-{
-    return entry(h, ncand <= 0 || (cand && hdr && values), kIdle, [&]() -> int {
-        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
-        if (int rc = check_examples_state(h)) return rc;
-        const int stride = ::stride(h);
-        const Resident &res = resident_owner(h)->res;
-        const Plan &P = *res.plan;
-        for (int i = 0; i < ncand; ++i) {
-            const int32_t *r = cand + (size_t)i * stride;
-            const long long f = (long long)r[0] - frame_offset;
-            int bf = 0, bl = 0;
-            if (f < INT32_MIN || f > INT32_MAX || !resident_level(res, (int)f, r[2], &bf, &bl))
-                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d / level %d outside the resident result", i, r[0],
-                            frame_offset, r[2]);
-            const LevelDesc &d = P.lv[bl];
-            if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
-            if (r[3] < 0 || r[3] >= d.cols || r[4] < 0 || r[4] >= d.rows)
-                return fail(h, PBD_ERR_INVALID, "record %d: root (%d, %d) outside the %d x %d map of level %d%s", i, r[3], r[4], d.cols,
-                            d.rows, r[2], d.rows ? "" : " (a level of another rank)");
-        }
-        if (ncand == 0) return PBD_OK;
-        const size_t hb = (size_t)ncand * h->ex_hdr_words * sizeof(int32_t), vb = (size_t)ncand * h->ex_values * h->rs;
-        const size_t hb_al = (hb + 255) / 256 * 256;
-        HIPCHK(h, h->ex_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
-        HIPCHK(h, h->ex_out.ensure(hb_al + vb));
-        HIPCHK(h, hipMemcpyAsync(h->ex_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->ex_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 h->stream));
-        int32_t *d_hdr = h->ex_out.as<int32_t>();
-        char *d_val = h->ex_out.as<char>() + hb_al;
-        if (int rc = enqueue_examples(h, h->ex_rec.as<int32_t>(), ncand, frame_offset, d_hdr, d_val)) return rc;
-        HIPCHK(h, hipMemcpyAsync(hdr, d_hdr, hb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(values, d_val, vb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-// Latent positives (matlab/detection/detect.m with a bbox: testoverlap masks, bbox.m fixed mixtures).  See include/pbd.h.
-int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
-                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
-{
-    return entry(h, frames && boxes && cand && found, kIdle, [&]() -> int {
-        if (h->shard_world > 1)
-            return fail(h, PBD_ERR_UNSUPPORTED, "latent detection with level sharding (world %d): the best root is over every level",
-                        h->shard_world);
-        const int nparts = h->part_offset[1] - h->part_offset[0];
-        for (int c = 1; c < h->NC; ++c)
-            if (h->part_offset[c + 1] - h->part_offset[c] != nparts)
-                return fail(h, PBD_ERR_UNSUPPORTED, "latent detection needs one part count in every component (component %d has %d, "
-                            "component 0 %d)", c, h->part_offset[c + 1] - h->part_offset[c], nparts);
-        if (h->resp_half) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection in PBD_CONV_MFMA_F16: -1e10 has no fp16 value");
-        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
-        if (int rc = check_bank(h)) return rc;
-        if (h->filter_ksize != h->model_ksize) return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's");
-        if (!h->lat) {   // the latent twin: the same model with one filter per (component, part, mixture), on this handle's stream
-            const int T = h->totmix;
-            std::vector<int> ks(T), fid(T);
-            std::vector<int64_t> off(T);
-            for (int gm = 0; gm < T; ++gm) {
-                fid[gm] = gm;
-                ks[gm] = h->model_ksize[h->filterid[gm]];
-                off[gm] = h->model_foff[h->filterid[gm]];
-            }
-            const size_t fbase = (size_t)h->nbias + 4 * (size_t)h->ndefs;
-            pbd_model m{};
-            m.ncomponents = h->NC; m.nfilters = T; m.flen = 32; m.filter_ksize = ks.data(); m.filter_offset = off.data();
-            if (h->f64) m.filters_f64 = reinterpret_cast<const double *>(h->mvec.data()) + fbase;
-            else m.filters_f32 = reinterpret_cast<const float *>(h->mvec.data()) + fbase;
-            m.nbias = h->nbias; m.biasw = h->biasw.data(); m.ndefs = h->ndefs; m.defw = h->defw.data(); m.anchors = h->anchors.data();
-            m.part_offset = h->part_offset.data(); m.parentid = h->parentid.data(); m.mix_offset = h->mix_offset.data();
-            m.filterid = fid.data(); m.biasid = h->biasid.data(); m.defid = h->defid.data();
-            m.thresh = h->thresh; m.sbin = h->sbin; m.interval = h->interval; m.norient = h->norient;
-            pbd_config cfg = h->cfg;
-            cfg.max_candidates = std::max(cfg.max_batch, 1);
-            cfg.stream = reinterpret_cast<void *>(h->stream.s);
-            pbd_handle *t = nullptr;
-            if (int rc = pbd_create(&m, &cfg, &t)) return fail(h, rc, "latent twin: %s", pbd_last_error(nullptr));
-            h->lat.reset(t);
-            std::vector<int4> gm(T);
-            for (int c = 0; c < h->NC; ++c)
-                for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)
-                    for (int g = h->mix_offset[gp]; g < h->mix_offset[gp + 1]; ++g)
-                        gm[g] = make_int4(gp - h->part_offset[c], g - h->mix_offset[gp], ks[g], 0);
-            HIPCHK(h, h->lat_gm.upload(gm));
-        }
-        pbd_handle *t = h->lat.get();
-        Plan *P = nullptr;
-        if (int rc = check_frames_mixed(t, nframes, frames, channels, depth_code, true, &P)) return fail(h, rc, "%s", t->err.c_str());
-        const size_t nb = (size_t)nframes * nparts;
-        HIPCHK(h, h->lat_in.ensure(nb * sizeof(int4) + nb * sizeof(int) + 64));
-        HIPCHK(h, hipMemcpyAsync(h->lat_in.p, boxes, nb * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-        int *d_mix = reinterpret_cast<int *>(h->lat_in.as<char>() + nb * sizeof(int4));
-        if (mixtures) HIPCHK(h, hipMemcpyAsync(d_mix, mixtures, nb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (!P->d_frame_lv0.p) HIPCHK(h, P->d_frame_lv0.upload(P->frame_lv0));
-        const int stride = ::stride(h);
-        HIPCHK(h, h->lat_pay.ensure(((size_t)nframes * stride + 1) * sizeof(int32_t)));
-        h->res = Resident{};
-        h->res.latent = true;
-        LatentParams lp{};
-        lp.gmtab = h->lat_gm.p; lp.boxes = h->lat_in.as<int4>(); lp.mix = mixtures ? d_mix : nullptr; lp.nparts = nparts;
-        lp.overlap = (double)overlap;
-        if (int rc = enqueue_detect_mixed(t, *P, nframes, frames, channels, depth_code, true, &lp)) return fail(h, rc, "%s", t->err.c_str());
-        lp.rootv = t->rootv.p; lp.rooti = t->rooti.as<int>(); lp.lv = P->d_lv.p; lp.nlevels = P->nlevels;
-        lp.cell_per_frame = P->cell_per_frame; lp.frame_lv0 = P->d_frame_lv0.p; lp.nframes = nframes; lp.NC = h->NC;
-        lp.stride = stride; lp.payload = h->lat_pay.as<int32_t>();
-        launch_latent_best(lp, h->f64, h->stream);
-        if (int rc = enqueue_argmin(t, *P, 1, P->d_scales.p, 0, lp.payload, nframes, h->stream, true)) return fail(h, rc, "%s", t->err.c_str());
-        HIPCHK(h, hipMemcpyAsync(cand, lp.payload + 1, (size_t)nframes * stride * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipGetLastError());
-        for (int f = 0; f < nframes; ++f) {
-            float sc;
-            memcpy(&sc, &cand[(size_t)f * stride + 5], sizeof sc);
-            found[f] = sc > -5e9f ? 1 : 0;
-        }
-        return PBD_OK;
-    });
-}
-
-int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
-{
-    return entry(h, d_payload && (capacity <= 0 || (d_hdr && d_values)), kIdle, [&]() -> int {
-        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (int rc = check_examples_state(h)) return rc;
-        if (capacity == 0) return PBD_OK;
-        return enqueue_examples(h, d_payload, capacity, frame_offset, d_hdr, d_values);
-    });
-}
-
 int pbd_profile_enable(pbd_handle *h, int on)
 {
     return entry(h, true, kBusyOk, [&]() -> int {
@@ -4017,717 +2326,6 @@ int pbd_synchronize(pbd_handle *h)
 {
     return entry(h, true, kBusyOk, [&]() -> int {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PBD_OK;
-    });
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// The training QP (matlab/learning/qp_*.m).  See include/pbd.h and DESIGN.md section 6i.  The kernels are in
-// pbd_kernels_qp.hip; the host keeps the ids, block tables and b of the entries (for the grouping, the refresh's entry lists
-// and l) and orders every call; all per-value work is on the device.
-struct pbd_qp {
-    std::string err;
-    int device = 0;
-    Stream stream;
-    int cap = 0, L = 0, V = 0, HW = 0, MB = 0, in_hw = 0;
-    uint64_t fp = 0;
-    double Cpos = 0, Cneg = 0;
-    DevBuf x, bm, hd, ids, b, d, a, sv, w, wraw, misc, stage, work, lc, scratch;
-    DevTable<double> wreg, w0;
-    DevTable<int> noneg, slot_of, slot_len;
-    std::vector<double> wreg_h, w0_h;
-    std::vector<int> slot_of_h, slot_len_h, slot_off_h;   // coordinate -> layout block; its length and offset
-    std::vector<int32_t> h_ids, h_hd;   // [n * 5], [n * HW]
-    std::vector<double> h_b;
-    int n = 0, nfix = 0, nnoneg = 0;
-    double lb = NAN, ub = NAN, loss = 0, l = 0, ww = 0;
-    bool have_lb = false;
-    int lb_dropped = 0, passes = 0, converged = 0;
-};
-
-namespace {
-
-constexpr size_t kQpPruneChunkBytes = size_t(256) << 20;   // prune's scratch: at most this much (or one entry) ...
-constexpr int kQpPruneChunkEntries = 256;                  // ... and at most this many entries per chunk
-
-int qp_fail(pbd_qp *q, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    try {
-        if (q) q->err = buf; else g_create_error = buf;
-    } catch (...) {
-    }
-    return code;
-}
-
-#define QPCHK(q, expr)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            (void)hipGetLastError();                                                                \
-            return qp_fail(q, e_ == hipErrorOutOfMemory ? PBD_ERR_NOMEM : PBD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
-                           hipGetErrorString(e_), __FILE__, __LINE__);                              \
-        }                                                                                           \
-    } while (0)
-
-template <class F>
-int qp_entry(pbd_qp *q, bool args_ok, F &&body) noexcept
-{
-    try {
-        if (!q || !args_ok) return PBD_ERR_INVALID;
-        (void)hipSetDevice(q->device);
-        return body();
-    } catch (const std::bad_alloc &) {
-        return qp_fail(q, PBD_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception &e) {
-        return qp_fail(q, PBD_ERR_INVALID, "unexpected exception: %s", e.what());
-    } catch (...) {
-        return qp_fail(q, PBD_ERR_INVALID, "unexpected exception");
-    }
-}
-
-hipError_t qp_alloc(DevBuf &buf, size_t bytes)
-{
-    buf = DevBuf{};
-    const hipError_t e = hipMalloc(&buf.p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) buf.size = std::max<size_t>(bytes, 16);
-    return e;
-}
-
-// the model-vector layout of a handle: every bias, deformation and filter block (offset, length), the example strides, and
-// its FNV-1a fingerprint
-struct QpLayout {
-    int L = 0, V = 0, in_hw = 0;
-    std::vector<std::pair<int, int> > blocks;
-    uint64_t fp = 0;
-};
-QpLayout qp_layout(const pbd_handle *h)
-{
-    QpLayout lay;
-    lay.L = (int)(h->mvec.size() / h->rs);
-    lay.V = h->ex_values;
-    lay.in_hw = h->ex_hdr_words;
-    for (int b = 0; b < h->nbias; ++b) lay.blocks.push_back({b, 1});
-    for (int d = 0; d < h->ndefs; ++d) lay.blocks.push_back({h->nbias + 4 * d, 4});
-    const long long fbase = (long long)h->nbias + 4LL * h->ndefs;
-    for (size_t f = 0; f < h->model_foff.size(); ++f)
-        lay.blocks.push_back({(int)(fbase + h->model_foff[f]), h->model_ksize[f] * h->model_ksize[f] * 32});
-    uint64_t v = 1469598103934665603ULL;
-    auto mix = [&](long long x) { for (int k = 0; k < 8; ++k) { v ^= (uint64_t)((x >> (8 * k)) & 0xff); v *= 1099511628211ULL; } };
-    mix(lay.L); mix(lay.V); mix(lay.in_hw); mix((long long)lay.blocks.size());
-    for (auto &b : lay.blocks) { mix(b.first); mix(b.second); }
-    lay.fp = v;
-    return lay;
-}
-
-QpCache qp_cache(pbd_qp *q)
-{
-    QpCache c{};
-    c.x = q->x.as<float>(); c.bm = q->bm.as<uint8_t>(); c.hd = q->hd.as<int32_t>(); c.ids = q->ids.as<int32_t>();
-    c.b = q->b.as<double>(); c.d = q->d.as<double>(); c.a = q->a.as<double>(); c.sv = q->sv.as<uint8_t>();
-    c.cap = q->cap; c.V = q->V; c.HW = q->HW; c.MB = q->MB;
-    c.w = q->w.as<double>(); c.wreg = q->wreg.p; c.w0 = q->w0.p;
-    c.noneg = q->noneg.p; c.nnoneg = q->nnoneg; c.L = q->L;
-    c.slot_of = q->slot_of.p; c.slot_len = q->slot_len.p;
-    return c;
-}
-
-// a header of pbd_examples' format: -1 marked invalid, 0 not a valid example for this layout, 1 valid
-int qp_header_ok(const pbd_qp *q, const int32_t *h)
-{
-    const int nb = h[2], nv = h[3];
-    if (nb == -1) return -1;
-    if (nb < 0 || nb > (q->in_hw - 4) / 2 || nb > q->MB || nv < 0 || nv > q->V) return 0;
-    long long tot = 0;
-    for (int b = 0; b < nb; ++b) {
-        const int off = h[4 + 2 * b], len = h[5 + 2 * b];
-        if (off < 0 || off >= q->L) return 0;
-        const int s = q->slot_of_h[off];
-        if (s < 0 || q->slot_len_h[s] != len) return 0;
-        tot += len;
-    }
-    return tot == nv ? 1 : 0;
-}
-
-// the write of m examples already on the device (p's inputs set), then the host mirror of the new entries
-int qp_write(pbd_qp *q, QpWriteParams &p, bool f64, int *taken)
-{
-    p.c = qp_cache(q);
-    p.in_hw = q->in_hw; p.in_vs = q->V; p.n0 = q->n; p.Cpos = q->Cpos; p.Cneg = q->Cneg;
-    QPCHK(q, q->work.ensure((size_t)std::max(p.m, 1) * sizeof(int)));
-    p.slot = q->work.as<int>();
-    p.taken = q->misc.as<int>();
-    launch_qp_write(p, f64, q->stream);
-    QPCHK(q, hipGetLastError());
-    int t = 0;
-    QPCHK(q, hipMemcpyAsync(&t, p.taken, sizeof(int), hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    if (t < 0 || t > q->cap - q->n) return qp_fail(q, PBD_ERR_HIP, "the write reported %d entries", t);
-    const int n0 = q->n, n1 = q->n + t;
-    q->h_ids.resize((size_t)n1 * 5);
-    q->h_hd.resize((size_t)n1 * q->HW);
-    q->h_b.resize(n1);
-    if (t > 0) {
-        QPCHK(q, hipMemcpyAsync(&q->h_ids[(size_t)n0 * 5], q->ids.as<int32_t>() + (size_t)n0 * 5, (size_t)t * 5 * sizeof(int32_t),
-                                hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipMemcpyAsync(&q->h_hd[(size_t)n0 * q->HW], q->hd.as<int32_t>() + (size_t)n0 * q->HW,
-                                (size_t)t * q->HW * sizeof(int32_t), hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipMemcpyAsync(&q->h_b[n0], q->b.as<double>() + n0, (size_t)t * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
-    }
-    q->n = n1;
-    if (taken) *taken = t;
-    return PBD_OK;
-}
-
-// group numbers of the entries list[0..k) (ascending indices): equal ids share a group, groups numbered by first member
-std::vector<int> qp_groups(const pbd_qp *q, const std::vector<int> &list, int *ngroups)
-{
-    std::map<std::array<int32_t, 5>, int> seen;
-    std::vector<int> g(list.size());
-    for (size_t k = 0; k < list.size(); ++k) {
-        std::array<int32_t, 5> id;
-        for (int c = 0; c < 5; ++c) id[c] = q->h_ids[(size_t)list[k] * 5 + c];
-        auto it = seen.emplace(id, (int)seen.size()).first;
-        g[k] = it->second;
-    }
-    *ngroups = (int)seen.size();
-    return g;
-}
-
-// qp_refresh: w and l from a (lincomb's order), the clamps, lb
-int qp_refresh(pbd_qp *q)
-{
-    // every QP call works on q->stream (created non-blocking, or the caller's): the duals are read in its order, after all
-    // work queued before (prune's compaction in particular)
-    std::vector<double> a(q->n);
-    if (q->n) QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    std::vector<int> P;
-    for (int i = 0; i < q->n; ++i) if (a[i] > 0) P.push_back(i);
-    std::stable_sort(P.begin(), P.end(), [&](int u, int v) { return a[u] < a[v]; });
-    double l = 0.0;
-    for (int i : P) l = l + q->h_b[i] * a[i];
-    // the entries carrying each layout block, in P's order
-    const int nslots = (int)q->slot_len_h.size();
-    std::vector<std::vector<int2> > per(nslots);
-    for (int i : P) {
-        const int32_t *h = &q->h_hd[(size_t)i * q->HW];
-        for (int b = 0; b < h[0]; ++b) per[q->slot_of_h[h[2 + 3 * b]]].push_back(make_int2(i, h[4 + 3 * b]));
-    }
-    std::vector<QpTask> tasks;
-    std::vector<int2> ent;
-    for (int s = 0; s < nslots; ++s) {
-        if (per[s].empty()) continue;
-        const int begin = (int)ent.size();
-        ent.insert(ent.end(), per[s].begin(), per[s].end());
-        const int off = q->slot_off_h[s];
-        for (int c0 = 0; c0 < q->slot_len_h[s]; c0 += PBD_QP_LANES)
-            tasks.push_back(QpTask{off, c0, std::min(PBD_QP_LANES, q->slot_len_h[s] - c0), begin, (int)ent.size(), 0});
-    }
-    const size_t tb = (tasks.size() * sizeof(QpTask) + 255) / 256 * 256;
-    QPCHK(q, q->lc.ensure(tb + ent.size() * sizeof(int2) + 16));
-    if (!tasks.empty()) {
-        QPCHK(q, hipMemcpyAsync(q->lc.p, tasks.data(), tasks.size() * sizeof(QpTask), hipMemcpyHostToDevice, q->stream));
-        QPCHK(q, hipMemcpyAsync(q->lc.as<char>() + tb, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, q->stream));
-    }
-    QpLincombParams lp{};
-    lp.c = qp_cache(q);
-    lp.tasks = q->lc.as<QpTask>(); lp.ntasks = (int)tasks.size();
-    lp.ent = reinterpret_cast<const int2 *>(q->lc.as<char>() + tb);
-    lp.ww = q->misc.as<double>() + 1;
-    launch_qp_lincomb(lp, q->stream);
-    QPCHK(q, hipGetLastError());
-    double ww = 0;
-    QPCHK(q, hipMemcpyAsync(&ww, lp.ww, sizeof(double), hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    const double lb = l - ww * 0.5;
-    if (q->have_lb && !(lb > q->lb - 1e-5)) q->lb_dropped = 1;
-    q->l = l; q->ww = ww; q->lb = lb; q->have_lb = true;
-    return PBD_OK;
-}
-
-// G = R(w . x) - b of every entry, then computeloss over the whole cache
-int qp_true_loss(pbd_qp *q, double *loss)
-{
-    QPCHK(q, q->work.ensure((size_t)std::max(q->n, 1) * sizeof(double)));
-    QpScoreParams sp{};
-    sp.c = qp_cache(q); sp.w = q->w.as<double>(); sp.first = 0; sp.count = q->n; sp.sub_b = 1; sp.scale = 1.0;
-    sp.out = q->work.as<double>();
-    launch_qp_score(sp, q->stream);
-    QPCHK(q, hipGetLastError());
-    std::vector<double> G(q->n);
-    if (q->n) QPCHK(q, hipMemcpyAsync(G.data(), sp.out, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    std::vector<int> all(q->n);
-    std::iota(all.begin(), all.end(), 0);
-    int ng = 0;
-    const std::vector<int> g = qp_groups(q, all, &ng);
-    std::vector<double> best(ng, 0.0);   // max(0, max slack) of every group
-    for (int i = 0; i < q->n; ++i) {
-        const double slack = -G[i];
-        if (slack > best[g[i]]) best[g[i]] = slack;
-    }
-    double s = 0.0;
-    for (int k = 0; k < ng; ++k) if (best[k] > 0) s = s + best[k];
-    *loss = s;
-    return PBD_OK;
-}
-
-uint64_t qp_splitmix64(uint64_t seed, uint64_t i)
-{
-    const uint64_t base = seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL;
-    uint64_t z = base + i * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-int qp_set_sv(pbd_qp *q, int count)
-{
-    if (count > 0) QPCHK(q, hipMemsetAsync(q->sv.p, 1, (size_t)count, q->stream));
-    return PBD_OK;
-}
-
-// qp_one: the pass over the support vectors, refresh, the fixed set's sv, lb and ub
-int qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed)
-{
-    std::vector<double> a(q->n);
-    std::vector<uint8_t> sv(q->n);
-    if (q->n) {
-        QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
-    }
-    std::vector<int> S;
-    for (int i = 0; i < q->n; ++i) if (sv[i]) S.push_back(i);
-    const int nsv = (int)S.size();
-    if (nsv == 0) return qp_fail(q, PBD_ERR_STATE, "no support vectors (empty cache)");
-    std::vector<int> perm(nsv);
-    if (order) {
-        if (norder != nsv) return qp_fail(q, PBD_ERR_INVALID, "order of %d indices, %d support vectors", norder, nsv);
-        std::vector<char> used(nsv, 0);
-        for (int k = 0; k < nsv; ++k) {
-            if (order[k] < 0 || order[k] >= nsv || used[order[k]]) return qp_fail(q, PBD_ERR_INVALID, "order is not a permutation of 0..%d", nsv - 1);
-            used[order[k]] = 1;
-            perm[k] = order[k];
-        }
-    } else {
-        std::vector<uint64_t> z(nsv);
-        for (int k = 0; k < nsv; ++k) z[k] = qp_splitmix64(seed, (uint64_t)k + 1);
-        std::iota(perm.begin(), perm.end(), 0);
-        std::stable_sort(perm.begin(), perm.end(), [&](int u, int v) { return z[u] < z[v]; });
-    }
-    int ng = 0;
-    const std::vector<int> gS = qp_groups(q, S, &ng);
-    std::vector<double> idC(ng, 0.0);
-    std::vector<int> idI(ng, -1);
-    for (int k = 0; k < nsv; ++k) {
-        idC[gS[k]] = idC[gS[k]] + a[S[k]];
-        if (a[S[k]] > 0) idI[gS[k]] = S[k];
-    }
-    std::vector<int> ord(nsv), gidx(nsv);
-    for (int k = 0; k < nsv; ++k) { ord[k] = S[perm[k]]; gidx[k] = gS[perm[k]]; }
-    // work: order, gidx (int), idC, err (double), idI (int)
-    const size_t o_ord = 0, o_g = o_ord + (size_t)nsv * 4, o_c = (o_g + (size_t)nsv * 4 + 7) / 8 * 8, o_e = o_c + (size_t)ng * 8,
-                 o_i = o_e + (size_t)ng * 8, tot = o_i + (size_t)ng * 4;
-    QPCHK(q, q->work.ensure(tot + 16));
-    char *wb = q->work.as<char>();
-    QPCHK(q, hipMemcpyAsync(wb + o_ord, ord.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
-    QPCHK(q, hipMemcpyAsync(wb + o_g, gidx.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
-    QPCHK(q, hipMemcpyAsync(wb + o_c, idC.data(), (size_t)ng * 8, hipMemcpyHostToDevice, q->stream));
-    QPCHK(q, hipMemsetAsync(wb + o_e, 0, (size_t)ng * 8, q->stream));
-    QPCHK(q, hipMemcpyAsync(wb + o_i, idI.data(), (size_t)ng * 4, hipMemcpyHostToDevice, q->stream));
-    QpPassParams pp{};
-    pp.c = qp_cache(q);
-    pp.order = reinterpret_cast<const int *>(wb + o_ord); pp.gidx = reinterpret_cast<const int *>(wb + o_g);
-    pp.nsteps = nsv; pp.ngroups = ng;
-    pp.idC = reinterpret_cast<double *>(wb + o_c); pp.err = reinterpret_cast<double *>(wb + o_e);
-    pp.idI = reinterpret_cast<int *>(wb + o_i);
-    pp.loss = q->misc.as<double>() + 2;
-    launch_qp_pass(pp, q->stream);
-    QPCHK(q, hipGetLastError());
-    double loss = 0;
-    QPCHK(q, hipMemcpyAsync(&loss, pp.loss, sizeof(double), hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    if (int rc = qp_refresh(q)) return rc;
-    if (int rc = qp_set_sv(q, q->nfix)) return rc;
-    q->loss = loss;
-    q->ub = q->ww * 0.5 + loss;
-    return PBD_OK;
-}
-
-void qp_fill_state(const pbd_qp *q, pbd_qp_info *st, int nsv)
-{
-    if (!st) return;
-    *st = pbd_qp_info{};
-    st->n = q->n; st->nsv = nsv; st->nfix = q->nfix; st->capacity = q->cap; st->len = q->L; st->hdr_words = q->HW; st->values = q->V;
-    st->lb = q->lb; st->ub = q->ub; st->loss = q->loss; st->l = q->l;
-    st->lb_dropped = q->lb_dropped; st->passes = q->passes; st->converged = q->converged;
-}
-
-int qp_count_sv(pbd_qp *q, int *nsv)
-{
-    std::vector<uint8_t> sv(q->n);
-    if (q->n) QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
-    QPCHK(q, hipStreamSynchronize(q->stream));
-    int k = 0;
-    for (uint8_t v : sv) k += v ? 1 : 0;
-    *nsv = k;
-    return PBD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pbd_qp_create(const pbd_handle *h, const struct pbd_qp_config *cfg, pbd_qp **out)
-{
-    try {
-        if (!h || !cfg || !out) return qp_fail(nullptr, PBD_ERR_INVALID, "null argument");
-        *out = nullptr;
-        if (cfg->capacity <= 0) return qp_fail(nullptr, PBD_ERR_INVALID, "capacity %d (at least 1)", cfg->capacity);
-        const double C = cfg->C == 0 ? 0.002 : cfg->C, wpos = cfg->wpos == 0 ? 2.0 : cfg->wpos;
-        if (!(C > 0) || !std::isfinite(C) || !(wpos > 0) || !std::isfinite(wpos))
-            return qp_fail(nullptr, PBD_ERR_INVALID, "C %g and wpos %g must be finite and positive", cfg->C, cfg->wpos);
-        (void)hipSetDevice(h->cfg.device);
-        std::unique_ptr<pbd_qp> q(new pbd_qp);
-        q->device = h->cfg.device;
-        const QpLayout lay = qp_layout(h);
-        q->L = lay.L; q->V = lay.V; q->in_hw = lay.in_hw; q->fp = lay.fp;
-        q->MB = (lay.in_hw - 4) / 2;
-        if (q->MB > 256 || q->MB < 1) return qp_fail(nullptr, PBD_ERR_UNSUPPORTED, "examples of %d blocks (at most 256)", q->MB);
-        if (q->V % 4) return qp_fail(nullptr, PBD_ERR_INVALID, "example stride %d", q->V);
-        q->HW = 2 + 3 * q->MB;
-        q->cap = cfg->capacity;
-        q->Cpos = C * wpos; q->Cneg = C;
-        q->slot_of_h.assign(q->L, -1);
-        for (auto &b : lay.blocks) {
-            if (b.first < 0 || b.first + (long long)b.second > q->L)
-                return qp_fail(nullptr, PBD_ERR_INVALID, "layout block at %d of %d values outside w", b.first, b.second);
-            if (q->slot_of_h[b.first] < 0) {
-                q->slot_of_h[b.first] = (int)q->slot_len_h.size();
-                q->slot_len_h.push_back(b.second);
-                q->slot_off_h.push_back(b.first);
-            }
-        }
-        // model2vec's defaults in this vector order
-        q->wreg_h.assign(q->L, 1.0);
-        q->w0_h.assign(q->L, 0.0);
-        std::vector<int> nn;
-        if (cfg->wreg) q->wreg_h.assign(cfg->wreg, cfg->wreg + q->L);
-        else for (int c = 0; c < h->NC; ++c) q->wreg_h[h->biasid[h->mix_offset[h->part_offset[c]]]] = 0.01;
-        if (cfg->w0) q->w0_h.assign(cfg->w0, cfg->w0 + q->L);
-        else for (int d = 0; d < h->ndefs; ++d) { q->w0_h[h->nbias + 4 * d] = 0.01; q->w0_h[h->nbias + 4 * d + 2] = 0.01; }
-        if (cfg->noneg) {
-            if (cfg->nnoneg < 0) return qp_fail(nullptr, PBD_ERR_INVALID, "nnoneg %d", cfg->nnoneg);
-            for (int k = 0; k < cfg->nnoneg; ++k) {
-                if (cfg->noneg[k] < 0 || cfg->noneg[k] >= q->L) return qp_fail(nullptr, PBD_ERR_INVALID, "noneg index %d", cfg->noneg[k]);
-                nn.push_back(cfg->noneg[k]);
-            }
-        } else {
-            for (int d = 0; d < h->ndefs; ++d) { nn.push_back(h->nbias + 4 * d); nn.push_back(h->nbias + 4 * d + 2); }
-        }
-        for (int k = 0; k < q->L; ++k)
-            if (!std::isfinite(q->wreg_h[k]) || q->wreg_h[k] == 0 || !std::isfinite(q->w0_h[k]))
-                return qp_fail(nullptr, PBD_ERR_INVALID, "wreg / w0 at %d: %g / %g (finite, wreg nonzero)", k, q->wreg_h[k], q->w0_h[k]);
-        q->nnoneg = (int)nn.size();
-        if (cfg->stream) q->stream.borrow(reinterpret_cast<hipStream_t>(cfg->stream));
-        else QPCHK(nullptr, q->stream.create());
-        const size_t cap = (size_t)q->cap;
-        QPCHK(nullptr, qp_alloc(q->x, cap * q->V * sizeof(float)));
-        QPCHK(nullptr, qp_alloc(q->bm, cap * q->V));
-        QPCHK(nullptr, qp_alloc(q->hd, cap * q->HW * sizeof(int32_t)));
-        QPCHK(nullptr, qp_alloc(q->ids, cap * 5 * sizeof(int32_t)));
-        QPCHK(nullptr, qp_alloc(q->b, cap * sizeof(double)));
-        QPCHK(nullptr, qp_alloc(q->d, cap * sizeof(double)));
-        QPCHK(nullptr, qp_alloc(q->a, cap * sizeof(double)));
-        QPCHK(nullptr, qp_alloc(q->sv, cap));
-        QPCHK(nullptr, qp_alloc(q->w, (size_t)q->L * sizeof(double)));
-        QPCHK(nullptr, qp_alloc(q->wraw, (size_t)q->L * sizeof(double)));
-        QPCHK(nullptr, qp_alloc(q->misc, 4 * sizeof(double)));
-        QPCHK(nullptr, hipMemsetAsync(q->w.p, 0, (size_t)q->L * sizeof(double), q->stream));
-        QPCHK(nullptr, hipMemsetAsync(q->a.p, 0, cap * sizeof(double), q->stream));
-        QPCHK(nullptr, hipMemsetAsync(q->sv.p, 0, cap, q->stream));
-        QPCHK(nullptr, q->wreg.upload(q->wreg_h));
-        QPCHK(nullptr, q->w0.upload(q->w0_h));
-        if (!nn.empty()) QPCHK(nullptr, q->noneg.upload(nn));
-        QPCHK(nullptr, q->slot_of.upload(q->slot_of_h));
-        QPCHK(nullptr, q->slot_len.upload(q->slot_len_h));   // DevTable uploads are blocking copies
-        QPCHK(nullptr, hipStreamSynchronize(q->stream));
-        *out = q.release();
-        return PBD_OK;
-    } catch (const std::bad_alloc &) {
-        return qp_fail(nullptr, PBD_ERR_NOMEM, "out of host memory");
-    } catch (...) {
-        return qp_fail(nullptr, PBD_ERR_INVALID, "unexpected exception");
-    }
-}
-
-void pbd_qp_destroy(pbd_qp *q)
-{
-    if (!q) return;
-    (void)hipSetDevice(q->device);
-    (void)hipStreamSynchronize(q->stream);
-    delete q;
-}
-
-const char *pbd_qp_last_error(const pbd_qp *q) { return q ? q->err.c_str() : g_create_error.c_str(); }
-
-int pbd_qp_add(pbd_qp *q, const pbd_handle *h, int n, const int32_t *hdr, const void *values, const int32_t *ids, int *taken)
-{
-    return qp_entry(q, h && (n <= 0 || (hdr && values && ids)), [&]() -> int {
-        if (n < 0) return qp_fail(q, PBD_ERR_INVALID, "n %d", n);
-        if (qp_layout(h).fp != q->fp) return qp_fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
-        for (int e = 0; e < n; ++e)
-            if (qp_header_ok(q, hdr + (size_t)e * q->in_hw) == 0)
-                return qp_fail(q, PBD_ERR_INVALID, "example %d: a block that is not a block of the model vector, or bad counts", e);
-        if (taken) *taken = 0;
-        if (n == 0) return PBD_OK;
-        const size_t rs = h->rs;
-        const size_t hb = (size_t)n * q->in_hw * 4, vb = (size_t)n * q->V * rs, ib = (size_t)n * 5 * 4;
-        const size_t o_v = (hb + 255) / 256 * 256, o_i = o_v + (vb + 255) / 256 * 256;
-        QPCHK(q, q->stage.ensure(o_i + ib));
-        QPCHK(q, hipMemcpyAsync(q->stage.p, hdr, hb, hipMemcpyHostToDevice, q->stream));
-        QPCHK(q, hipMemcpyAsync(q->stage.as<char>() + o_v, values, vb, hipMemcpyHostToDevice, q->stream));
-        QPCHK(q, hipMemcpyAsync(q->stage.as<char>() + o_i, ids, ib, hipMemcpyHostToDevice, q->stream));
-        QpWriteParams p{};
-        p.in_hdr = q->stage.as<int32_t>();
-        p.in_values = q->stage.as<char>() + o_v;
-        p.in_ids = reinterpret_cast<const int32_t *>(q->stage.as<char>() + o_i);
-        p.m = n;
-        return qp_write(q, p, h->f64, taken);
-    });
-}
-
-int pbd_qp_add_device(pbd_qp *q, pbd_handle *h, const int32_t *d_payload, int capacity, const int32_t *d_hdr, const void *d_values,
-                      int label, int id_base, int32_t *d_taken)
-{
-    return qp_entry(q, h && d_payload && (capacity <= 0 || (d_hdr && d_values)), [&]() -> int {
-        if (capacity < 0) return qp_fail(q, PBD_ERR_INVALID, "capacity %d", capacity);
-        if (qp_layout(h).fp != q->fp) return qp_fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
-        (void)hipSetDevice(q->device);
-        if (h->stream.s != q->stream.s) {   // the QP's stream waits for the handle's
-            Event ev;
-            QPCHK(q, hipEventCreateWithFlags(&ev.p, hipEventDisableTiming));
-            QPCHK(q, hipEventRecord(ev.p, h->stream));
-            QPCHK(q, hipStreamWaitEvent(q->stream, ev.p, 0));
-        }
-        QpWriteParams p{};
-        p.in_hdr = d_hdr; p.in_values = d_values; p.in_ids = nullptr;
-        p.payload = d_payload; p.rec_stride = ::stride(h); p.label = label; p.id_base = id_base;
-        p.m = capacity;
-        p.taken_user = d_taken;
-        if (capacity == 0) {
-            if (d_taken) QPCHK(q, hipMemsetAsync(d_taken, 0, sizeof(int32_t), q->stream));
-            QPCHK(q, hipStreamSynchronize(q->stream));
-            return PBD_OK;
-        }
-        return qp_write(q, p, h->f64, nullptr);
-    });
-}
-
-int pbd_qp_fix(pbd_qp *q)
-{
-    return qp_entry(q, true, [&]() -> int {
-        q->nfix = q->n;
-        if (int rc = qp_set_sv(q, q->n)) return rc;
-        QPCHK(q, hipStreamSynchronize(q->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_prune(pbd_qp *q, int *n)
-{
-    return qp_entry(q, true, [&]() -> int {
-        q->lb_dropped = 0;
-        std::vector<double> a(q->n);
-        std::vector<uint8_t> sv(q->n);
-        if (q->n) {
-            QPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-            QPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
-            QPCHK(q, hipStreamSynchronize(q->stream));
-        }
-        bool all = true;
-        for (uint8_t v : sv) all = all && v;
-        if (all) for (int i = 0; i < q->n; ++i) sv[i] = (a[i] > 0 || i < q->nfix) ? 1 : 0;
-        std::vector<int> I;
-        for (int i = 0; i < q->n; ++i) if (sv[i]) I.push_back(i);
-        const int n1 = (int)I.size();
-        if (n1 == 0) return qp_fail(q, PBD_ERR_STATE, "nothing to keep (empty cache)");
-        int first = 0;
-        while (first < n1 && I[first] == first) ++first;
-        // compaction in ascending chunks of at most `chunk` entries through a scratch buffer freed afterwards: a chunk's sources
-        // I[k] >= k lie at or past the chunk's own start and past every earlier chunk's destinations, so each chunk reads
-        // entries no earlier chunk has overwritten
-        const size_t V = q->V, HW = q->HW;
-        const size_t entry_bytes = V * 5 + HW * 4 + 20 + 3 * 8;
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)std::max(n1 - first, 1), kQpPruneChunkEntries),
-                                                                     kQpPruneChunkBytes / entry_bytes));
-        if (first < n1) {
-            const size_t c = (size_t)chunk;
-            const size_t o_x = 0, o_bm = o_x + c * V * 4, o_hd = (o_bm + c * V + 255) / 256 * 256, o_id = o_hd + c * HW * 4,
-                         o_b = (o_id + c * 20 + 255) / 256 * 256, o_d = o_b + c * 8, o_a = o_d + c * 8, tot = o_a + c * 8;
-            QPCHK(q, qp_alloc(q->scratch, tot));
-            QPCHK(q, q->work.ensure((size_t)(n1 - first) * sizeof(int)));
-            QPCHK(q, hipMemcpyAsync(q->work.p, &I[first], (size_t)(n1 - first) * sizeof(int), hipMemcpyHostToDevice, q->stream));
-            char *s = q->scratch.as<char>();
-            for (int k0 = first; k0 < n1; k0 += chunk) {
-                const size_t cnt = (size_t)std::min(chunk, n1 - k0), k = (size_t)k0;
-                QpGatherParams gp{};
-                gp.c = qp_cache(q); gp.src = q->work.as<int>() + (k0 - first); gp.count = (int)cnt; gp.dst0 = k0;
-                gp.x = reinterpret_cast<float *>(s + o_x); gp.bm = reinterpret_cast<uint8_t *>(s + o_bm);
-                gp.hd = reinterpret_cast<int32_t *>(s + o_hd); gp.ids = reinterpret_cast<int32_t *>(s + o_id);
-                gp.b = reinterpret_cast<double *>(s + o_b); gp.d = reinterpret_cast<double *>(s + o_d);
-                gp.a = reinterpret_cast<double *>(s + o_a);
-                launch_qp_gather(gp, q->stream);
-                QPCHK(q, hipGetLastError());
-                auto back = [&](void *dst, size_t off, size_t bytes) {
-                    return hipMemcpyAsync(dst, s + off, bytes, hipMemcpyDeviceToDevice, q->stream);
-                };
-                QPCHK(q, back(q->x.as<float>() + k * V, o_x, cnt * V * 4));
-                QPCHK(q, back(q->bm.as<uint8_t>() + k * V, o_bm, cnt * V));
-                QPCHK(q, back(q->hd.as<int32_t>() + k * HW, o_hd, cnt * HW * 4));
-                QPCHK(q, back(q->ids.as<int32_t>() + k * 5, o_id, cnt * 20));
-                QPCHK(q, back(q->b.as<double>() + k, o_b, cnt * 8));
-                QPCHK(q, back(q->d.as<double>() + k, o_d, cnt * 8));
-                QPCHK(q, back(q->a.as<double>() + k, o_a, cnt * 8));
-            }
-            QPCHK(q, hipStreamSynchronize(q->stream));
-            q->scratch = DevBuf{};
-        }
-        int nfix = 0;
-        for (int k = 0; k < n1; ++k) {
-            const int i = I[k];
-            if (i < q->nfix) ++nfix;
-            if (k != i) {
-                std::copy_n(&q->h_ids[(size_t)i * 5], 5, &q->h_ids[(size_t)k * 5]);
-                std::copy_n(&q->h_hd[(size_t)i * q->HW], q->HW, &q->h_hd[(size_t)k * q->HW]);
-                q->h_b[k] = q->h_b[i];
-            }
-        }
-        q->h_ids.resize((size_t)n1 * 5); q->h_hd.resize((size_t)n1 * q->HW); q->h_b.resize(n1);
-        q->n = n1; q->nfix = nfix;
-        if (q->cap > n1) QPCHK(q, hipMemsetAsync(q->sv.as<uint8_t>() + n1, 0, (size_t)(q->cap - n1), q->stream));
-        if (int rc = qp_set_sv(q, n1)) return rc;
-        if (int rc = qp_refresh(q)) return rc;
-        if (n) *n = n1;
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed, struct pbd_qp_info *state)
-{
-    return qp_entry(q, true, [&]() -> int {
-        q->lb_dropped = 0;
-        if (int rc = qp_one(q, order, norder, seed)) return rc;
-        q->passes = 1; q->converged = 0;
-        int nsv = 0;
-        if (int rc = qp_count_sv(q, &nsv)) return rc;
-        qp_fill_state(q, state, nsv);
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed, struct pbd_qp_info *state)
-{
-    return qp_entry(q, true, [&]() -> int {
-        if (std::isnan(tol)) return qp_fail(q, PBD_ERR_INVALID, "tol is NaN");
-        if (iter < 0) return qp_fail(q, PBD_ERR_INVALID, "iter %d", iter);
-        if (q->n == 0) return qp_fail(q, PBD_ERR_STATE, "empty cache");
-        q->lb_dropped = 0; q->passes = 0; q->converged = 0;
-        if (int rc = qp_refresh(q)) return rc;
-        double loss = 0;
-        if (int rc = qp_true_loss(q, &loss)) return rc;
-        double ub = q->ww * 0.5 + loss;
-        if (int rc = qp_set_sv(q, q->n)) return rc;
-        for (int t = 0; t < iter; ++t) {
-            if (int rc = qp_one(q, nullptr, 0, seed + (uint64_t)t)) return rc;
-            q->passes = t + 1;
-            const double lb = q->lb, ub_est = ub < q->ub ? ub : q->ub;
-            if (lb > 0 && 1 - lb / ub_est < tol) {
-                if (int rc = qp_true_loss(q, &loss)) return rc;
-                const double u = q->ww * 0.5 + loss;
-                ub = u < ub ? u : ub;
-                if (1 - lb / ub < tol) { q->converged = 1; break; }
-                if (int rc = qp_set_sv(q, q->n)) return rc;
-            }
-        }
-        q->ub = ub;
-        int nsv = 0;
-        if (int rc = qp_count_sv(q, &nsv)) return rc;
-        qp_fill_state(q, state, nsv);
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_weights(pbd_qp *q, double *w)
-{
-    return qp_entry(q, w != nullptr, [&]() -> int {
-        std::vector<double> v(q->L);
-        QPCHK(q, hipMemcpyAsync(v.data(), q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
-        for (int k = 0; k < q->L; ++k) w[k] = v[k] / q->wreg_h[k] + q->w0_h[k];
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_scores(pbd_qp *q, double *s, int *n)
-{
-    return qp_entry(q, s && n, [&]() -> int {
-        std::vector<int> pos;
-        for (int i = 0; i < q->n; ++i) if (q->h_ids[(size_t)i * 5] > 0) pos.push_back(i);
-        *n = (int)pos.size();
-        if (pos.empty()) return PBD_OK;
-        const size_t o_o = ((size_t)pos.size() * 4 + 255) / 256 * 256;
-        QPCHK(q, q->work.ensure(o_o + pos.size() * 8));
-        QPCHK(q, hipMemcpyAsync(q->work.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, q->stream));
-        QpCache c = qp_cache(q);
-        launch_qp_wraw(c, q->wraw.as<double>(), q->stream);
-        QpScoreParams sp{};
-        sp.c = c; sp.w = q->wraw.as<double>(); sp.list = q->work.as<int>(); sp.count = (int)pos.size(); sp.sub_b = 0; sp.scale = q->Cpos;
-        sp.out = reinterpret_cast<double *>(q->work.as<char>() + o_o);
-        launch_qp_score(sp, q->stream);
-        QPCHK(q, hipGetLastError());
-        QPCHK(q, hipMemcpyAsync(s, sp.out, pos.size() * 8, hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_state(pbd_qp *q, struct pbd_qp_info *state, double *a, uint8_t *sv, double *w)
-{
-    return qp_entry(q, true, [&]() -> int {
-        if (a && q->n) QPCHK(q, hipMemcpyAsync(a, q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-        if (sv && q->n) QPCHK(q, hipMemcpyAsync(sv, q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
-        if (w) QPCHK(q, hipMemcpyAsync(w, q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
-        int nsv = 0;
-        if (int rc = qp_count_sv(q, &nsv)) return rc;
-        qp_fill_state(q, state, nsv);
-        return PBD_OK;
-    });
-}
-
-int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values, double *b, double *d, int32_t *ids)
-{
-    return qp_entry(q, true, [&]() -> int {
-        if (first < 0 || count < 0 || (long long)first + count > q->n)
-            return qp_fail(q, PBD_ERR_INVALID, "entries %d..%d of %d", first, first + count - 1, q->n);
-        const size_t f = first, c = count;
-        if (c == 0) return PBD_OK;
-        if (hdr) QPCHK(q, hipMemcpyAsync(hdr, q->hd.as<int32_t>() + f * q->HW, c * q->HW * 4, hipMemcpyDeviceToHost, q->stream));
-        if (values) QPCHK(q, hipMemcpyAsync(values, q->x.as<float>() + f * q->V, c * q->V * 4, hipMemcpyDeviceToHost, q->stream));
-        if (b) QPCHK(q, hipMemcpyAsync(b, q->b.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
-        if (d) QPCHK(q, hipMemcpyAsync(d, q->d.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
-        if (ids) QPCHK(q, hipMemcpyAsync(ids, q->ids.as<int32_t>() + f * 5, c * 20, hipMemcpyDeviceToHost, q->stream));
-        QPCHK(q, hipStreamSynchronize(q->stream));
         return PBD_OK;
     });
 }

@@ -1,0 +1,875 @@
+// pbd_capi_train.hip -- the C entry points of training (include/pbd.h): the model vector, training examples of a resident detect
+// result, latent positives, and the QP over a device-resident example cache.
+// The handle and the layer they are written on: pbd_handle.h.
+#include "pbd_handle.h"
+
+using namespace pbd;
+
+namespace {
+
+// pbd_examples*: the resident result a record can be walked in (PBD_OK or the failure's status code)
+// the handle whose buffers hold the resident result: the latent twin after pbd_detect_latent
+pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->lat ? h->lat.get() : h; }
+
+int check_examples_state(pbd_handle *h)
+{
+    const Resident &r = resident_owner(h)->res;
+    if (!r.plan || (r.plan->kind != 0 && r.plan->kind != 2) || !r.features || !r.dp)
+        return fail(h, PBD_ERR_STATE, "no resident detect result (pbd_detect* computes one; pbd_dp_min and pbd_conv_set_filters leave none)");
+    if (!h->bank_matches_model || h->filter_ksize != h->model_ksize)
+        return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
+    return PBD_OK;
+}
+
+// the walk and the gather of min(max(word 0, 0), capacity) records of d_in into d_hdr / d_values, on the handle's stream
+int enqueue_examples(pbd_handle *h, const int32_t *d_in, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
+{
+    pbd_handle *o = resident_owner(h);   // its maps and features; the model tables (filter ids, offsets) stay this handle's
+    Plan &P = *o->res.plan;
+    if (!h->ex_gm.p) {
+        std::vector<ExGm> gm(h->totmix);
+        for (int i = 0; i < h->totmix; ++i) gm[i] = ExGm{h->filterid[i], h->biasid[i], h->defid[i], 0};
+        HIPCHK(h, h->ex_gm.upload(gm));
+        std::vector<int> anc(h->anchors);
+        anc.push_back(0);
+        HIPCHK(h, h->ex_anchors.upload(anc));
+        HIPCHK(h, h->ex_foff.upload(h->model_foff));
+    }
+    if (P.kind == 2 && !P.d_frame_lv0.p) HIPCHK(h, P.d_frame_lv0.upload(P.frame_lv0));
+    HIPCHK(h, h->ex_ws.ensure(std::max<size_t>((size_t)capacity * h->max_parts * sizeof(ExPart), 16)));
+    ExampleParams ep{};
+    ep.in = d_in; ep.in_cap = capacity; ep.stride = stride(h); ep.frame_offset = frame_offset;
+    ep.lv = P.d_lv.p; ep.nlevels = P.nlevels;
+    ep.nframes = P.kind == 2 ? P.mixed_frames : o->res.frames;
+    ep.frame_lv0 = P.kind == 2 ? P.d_frame_lv0.p : nullptr;
+    ep.cell_per_frame = P.cell_per_frame;
+    ep.NC = h->NC; ep.NS = h->NS; ep.NJ = h->totmix; ep.ptr8 = P.ptr8 ? 1 : 0; ep.flen = 32; ep.max_parts = h->max_parts;
+    ep.rooti = o->rooti.as<int>(); ep.IxRaw = o->IxRaw.p; ep.IyRaw = o->IyRaw.p; ep.Ik = o->Ik.as<uint8_t>();
+    ep.walk = h->d_walk.p; ep.walk_off = h->d_walk_off.p;
+    ep.gm = h->ex_gm.p; ep.anchors = h->ex_anchors.p; ep.foff = h->ex_foff.p; ep.nbias = h->nbias; ep.ndefs = h->ndefs;
+    ep.feat = o->feat.p;
+    ep.parts = h->ex_ws.as<ExPart>();
+    ep.hdr = d_hdr; ep.hdr_words = h->ex_hdr_words;
+    ep.values = d_values; ep.vstride = h->ex_values;
+    { ProfScope ps(h, PBD_K_EX_WALK, h->stream); launch_examples(ep, h->f64, 0, h->stream); }
+    { ProfScope ps(h, PBD_K_EX_GATHER, h->stream); launch_examples(ep, h->f64, 1, h->stream); }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+}  // namespace
+
+// ================================================================================================
+extern "C" {
+
+// Training examples (matlab/detection/detect.m backtrack + qp_write).  See include/pbd.h.
+int pbd_model_vector_len(const pbd_handle *h) { return h ? (int)(h->mvec.size() / h->rs) : 0; }
+
+int pbd_model_vector(pbd_handle *h, void *w)
+{
+    return entry(h, w, kBusyOk, [&]() -> int {
+        memcpy(w, h->mvec.data(), h->mvec.size());
+        return PBD_OK;
+    });
+}
+
+int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values)
+{
+    if (!h || !hdr_words || !values) return PBD_ERR_INVALID;
+    *hdr_words = h->ex_hdr_words;
+    *values = h->ex_values;
+    return PBD_OK;
+}
+
+int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values)
+{
+    return entry(h, ncand <= 0 || (cand && hdr && values), kIdle, [&]() -> int {
+        if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+        if (int rc = check_examples_state(h)) return rc;
+        const int stride = ::stride(h);
+        const Resident &res = resident_owner(h)->res;
+        const Plan &P = *res.plan;
+        for (int i = 0; i < ncand; ++i) {
+            const int32_t *r = cand + (size_t)i * stride;
+            const long long f = (long long)r[0] - frame_offset;
+            int bf = 0, bl = 0;
+            if (f < INT32_MIN || f > INT32_MAX || !resident_level(res, (int)f, r[2], &bf, &bl))
+                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d / level %d outside the resident result", i, r[0],
+                            frame_offset, r[2]);
+            const LevelDesc &d = P.lv[bl];
+            if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
+            if (r[3] < 0 || r[3] >= d.cols || r[4] < 0 || r[4] >= d.rows)
+                return fail(h, PBD_ERR_INVALID, "record %d: root (%d, %d) outside the %d x %d map of level %d%s", i, r[3], r[4], d.cols,
+                            d.rows, r[2], d.rows ? "" : " (a level of another rank)");
+        }
+        if (ncand == 0) return PBD_OK;
+        const size_t hb = (size_t)ncand * h->ex_hdr_words * sizeof(int32_t), vb = (size_t)ncand * h->ex_values * h->rs;
+        int32_t *d_hdr = nullptr;
+        char *d_val = nullptr;
+        HIPCHK(h, h->ex_rec.ensure(((size_t)ncand * stride + 1) * sizeof(int32_t)));
+        if (int rc = carve(h, h->ex_out, [&](Carve &c) { d_hdr = c.take<int32_t>(hb); d_val = c.take<char>(vb); })) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->ex_rec.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->ex_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 h->stream));
+        if (int rc = enqueue_examples(h, h->ex_rec.as<int32_t>(), ncand, frame_offset, d_hdr, d_val)) return rc;
+        HIPCHK(h, hipMemcpyAsync(hdr, d_hdr, hb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(values, d_val, vb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+// Latent positives (matlab/detection/detect.m with a bbox: testoverlap masks, bbox.m fixed mixtures).  See include/pbd.h.
+int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
+                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
+{
+    return entry(h, frames && boxes && cand && found, kIdle, [&]() -> int {
+        if (h->shard_world > 1)
+            return fail(h, PBD_ERR_UNSUPPORTED, "latent detection with level sharding (world %d): the best root is over every level",
+                        h->shard_world);
+        const int nparts = h->part_offset[1] - h->part_offset[0];
+        for (int c = 1; c < h->NC; ++c)
+            if (h->part_offset[c + 1] - h->part_offset[c] != nparts)
+                return fail(h, PBD_ERR_UNSUPPORTED, "latent detection needs one part count in every component (component %d has %d, "
+                            "component 0 %d)", c, h->part_offset[c + 1] - h->part_offset[c], nparts);
+        if (h->resp_half) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection in PBD_CONV_MFMA_F16: -1e10 has no fp16 value");
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        if (int rc = check_bank(h)) return rc;
+        if (h->filter_ksize != h->model_ksize) return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's");
+        if (!h->lat) {   // the latent twin: the same model with one filter per (component, part, mixture), on this handle's stream
+            const int T = h->totmix;
+            std::vector<int> ks(T), fid(T);
+            std::vector<int64_t> off(T);
+            for (int gm = 0; gm < T; ++gm) {
+                fid[gm] = gm;
+                ks[gm] = h->model_ksize[h->filterid[gm]];
+                off[gm] = h->model_foff[h->filterid[gm]];
+            }
+            const size_t fbase = (size_t)h->nbias + 4 * (size_t)h->ndefs;
+            pbd_model m{};
+            m.ncomponents = h->NC; m.nfilters = T; m.flen = 32; m.filter_ksize = ks.data(); m.filter_offset = off.data();
+            if (h->f64) m.filters_f64 = reinterpret_cast<const double *>(h->mvec.data()) + fbase;
+            else m.filters_f32 = reinterpret_cast<const float *>(h->mvec.data()) + fbase;
+            m.nbias = h->nbias; m.biasw = h->biasw.data(); m.ndefs = h->ndefs; m.defw = h->defw.data(); m.anchors = h->anchors.data();
+            m.part_offset = h->part_offset.data(); m.parentid = h->parentid.data(); m.mix_offset = h->mix_offset.data();
+            m.filterid = fid.data(); m.biasid = h->biasid.data(); m.defid = h->defid.data();
+            m.thresh = h->thresh; m.sbin = h->sbin; m.interval = h->interval; m.norient = h->norient;
+            pbd_config cfg = h->cfg;
+            cfg.max_candidates = std::max(cfg.max_batch, 1);
+            cfg.stream = reinterpret_cast<void *>(h->stream.s);
+            pbd_handle *t = nullptr;
+            if (int rc = pbd_create(&m, &cfg, &t)) return fail(h, rc, "latent twin: %s", pbd_last_error(nullptr));
+            h->lat.reset(t);
+            std::vector<int4> gm(T);
+            for (int c = 0; c < h->NC; ++c)
+                for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)
+                    for (int g = h->mix_offset[gp]; g < h->mix_offset[gp + 1]; ++g)
+                        gm[g] = make_int4(gp - h->part_offset[c], g - h->mix_offset[gp], ks[g], 0);
+            HIPCHK(h, h->lat_gm.upload(gm));
+        }
+        pbd_handle *t = h->lat.get();
+        Plan *P = nullptr;
+        if (int rc = check_frames_mixed(t, nframes, frames, channels, depth_code, true, &P)) return fail(h, rc, "%s", t->err.c_str());
+        const size_t nb = (size_t)nframes * nparts;
+        HIPCHK(h, h->lat_in.ensure(nb * sizeof(int4) + nb * sizeof(int) + 64));
+        HIPCHK(h, hipMemcpyAsync(h->lat_in.p, boxes, nb * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        int *d_mix = reinterpret_cast<int *>(h->lat_in.as<char>() + nb * sizeof(int4));
+        if (mixtures) HIPCHK(h, hipMemcpyAsync(d_mix, mixtures, nb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (!P->d_frame_lv0.p) HIPCHK(h, P->d_frame_lv0.upload(P->frame_lv0));
+        const int stride = ::stride(h);
+        HIPCHK(h, h->lat_pay.ensure(((size_t)nframes * stride + 1) * sizeof(int32_t)));
+        h->res = Resident{};
+        h->res.latent = true;
+        LatentParams lp{};
+        lp.gmtab = h->lat_gm.p; lp.boxes = h->lat_in.as<int4>(); lp.mix = mixtures ? d_mix : nullptr; lp.nparts = nparts;
+        lp.overlap = (double)overlap;
+        if (int rc = enqueue_detect_mixed(t, *P, nframes, frames, channels, depth_code, true, &lp)) return fail(h, rc, "%s", t->err.c_str());
+        lp.rootv = t->rootv.p; lp.rooti = t->rooti.as<int>(); lp.lv = P->d_lv.p; lp.nlevels = P->nlevels;
+        lp.cell_per_frame = P->cell_per_frame; lp.frame_lv0 = P->d_frame_lv0.p; lp.nframes = nframes; lp.NC = h->NC;
+        lp.stride = stride; lp.payload = h->lat_pay.as<int32_t>();
+        launch_latent_best(lp, h->f64, h->stream);
+        if (int rc = enqueue_argmin(t, *P, 1, P->d_scales.p, 0, lp.payload, nframes, h->stream, true)) return fail(h, rc, "%s", t->err.c_str());
+        HIPCHK(h, hipMemcpyAsync(cand, lp.payload + 1, (size_t)nframes * stride * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+        for (int f = 0; f < nframes; ++f) {
+            float sc;
+            memcpy(&sc, &cand[(size_t)f * stride + 5], sizeof sc);
+            found[f] = sc > -5e9f ? 1 : 0;
+        }
+        return PBD_OK;
+    });
+}
+
+int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)
+{
+    return entry(h, d_payload && (capacity <= 0 || (d_hdr && d_values)), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_examples_state(h)) return rc;
+        if (capacity == 0) return PBD_OK;
+        return enqueue_examples(h, d_payload, capacity, frame_offset, d_hdr, d_values);
+    });
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// The training QP (matlab/learning/qp_*.m).  See include/pbd.h and DESIGN.md section 6i.  The kernels are in
+// pbd_kernels_qp.hip; the host keeps the ids, block tables and b of the entries (for the grouping, the refresh's entry lists
+// and l) and orders every call; all per-value work is on the device.
+struct pbd_qp : pbd::ErrCtx {
+    Stream stream;
+    int cap = 0, L = 0, V = 0, HW = 0, MB = 0, in_hw = 0;
+    uint64_t fp = 0;
+    double Cpos = 0, Cneg = 0;
+    DevBuf x, bm, hd, ids, b, d, a, sv, w, wraw, misc, stage, work, lc, scratch;
+    DevTable<double> wreg, w0;
+    DevTable<int> noneg, slot_of, slot_len;
+    std::vector<double> wreg_h, w0_h;
+    std::vector<int> slot_of_h, slot_len_h, slot_off_h;   // coordinate -> layout block; its length and offset
+    std::vector<int32_t> h_ids, h_hd;   // [n * 5], [n * HW]
+    std::vector<double> h_b;
+    int n = 0, nfix = 0, nnoneg = 0;
+    double lb = NAN, ub = NAN, loss = 0, l = 0, ww = 0;
+    bool have_lb = false;
+    int lb_dropped = 0, passes = 0, converged = 0;
+};
+
+namespace {
+
+constexpr size_t kQpPruneChunkBytes = size_t(256) << 20;   // prune's scratch: at most this much (or one entry) ...
+constexpr int kQpPruneChunkEntries = 256;                  // ... and at most this many entries per chunk
+
+// the model-vector layout of a handle: every bias, deformation and filter block (offset, length), the example strides, and
+// its FNV-1a fingerprint
+struct QpLayout {
+    int L = 0, V = 0, in_hw = 0;
+    std::vector<std::pair<int, int> > blocks;
+    uint64_t fp = 0;
+};
+QpLayout qp_layout(const pbd_handle *h)
+{
+    QpLayout lay;
+    lay.L = (int)(h->mvec.size() / h->rs);
+    lay.V = h->ex_values;
+    lay.in_hw = h->ex_hdr_words;
+    for (int b = 0; b < h->nbias; ++b) lay.blocks.push_back({b, 1});
+    for (int d = 0; d < h->ndefs; ++d) lay.blocks.push_back({h->nbias + 4 * d, 4});
+    const long long fbase = (long long)h->nbias + 4LL * h->ndefs;
+    for (size_t f = 0; f < h->model_foff.size(); ++f)
+        lay.blocks.push_back({(int)(fbase + h->model_foff[f]), h->model_ksize[f] * h->model_ksize[f] * 32});
+    uint64_t v = 1469598103934665603ULL;
+    auto mix = [&](long long x) { for (int k = 0; k < 8; ++k) { v ^= (uint64_t)((x >> (8 * k)) & 0xff); v *= 1099511628211ULL; } };
+    mix(lay.L); mix(lay.V); mix(lay.in_hw); mix((long long)lay.blocks.size());
+    for (auto &b : lay.blocks) { mix(b.first); mix(b.second); }
+    lay.fp = v;
+    return lay;
+}
+
+QpCache qp_cache(pbd_qp *q)
+{
+    QpCache c{};
+    c.x = q->x.as<float>(); c.bm = q->bm.as<uint8_t>(); c.hd = q->hd.as<int32_t>(); c.ids = q->ids.as<int32_t>();
+    c.b = q->b.as<double>(); c.d = q->d.as<double>(); c.a = q->a.as<double>(); c.sv = q->sv.as<uint8_t>();
+    c.cap = q->cap; c.V = q->V; c.HW = q->HW; c.MB = q->MB;
+    c.w = q->w.as<double>(); c.wreg = q->wreg.p; c.w0 = q->w0.p;
+    c.noneg = q->noneg.p; c.nnoneg = q->nnoneg; c.L = q->L;
+    c.slot_of = q->slot_of.p; c.slot_len = q->slot_len.p;
+    return c;
+}
+
+// a header of pbd_examples' format: -1 marked invalid, 0 not a valid example for this layout, 1 valid
+int qp_header_ok(const pbd_qp *q, const int32_t *h)
+{
+    const int nb = h[2], nv = h[3];
+    if (nb == -1) return -1;
+    if (nb < 0 || nb > (q->in_hw - 4) / 2 || nb > q->MB || nv < 0 || nv > q->V) return 0;
+    long long tot = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int off = h[4 + 2 * b], len = h[5 + 2 * b];
+        if (off < 0 || off >= q->L) return 0;
+        const int s = q->slot_of_h[off];
+        if (s < 0 || q->slot_len_h[s] != len) return 0;
+        tot += len;
+    }
+    return tot == nv ? 1 : 0;
+}
+
+// the write of m examples already on the device (p's inputs set), then the host mirror of the new entries
+int qp_write(pbd_qp *q, QpWriteParams &p, bool f64, int *taken)
+{
+    p.c = qp_cache(q);
+    p.in_hw = q->in_hw; p.in_vs = q->V; p.n0 = q->n; p.Cpos = q->Cpos; p.Cneg = q->Cneg;
+    HIPCHK(q, q->work.ensure((size_t)std::max(p.m, 1) * sizeof(int)));
+    p.slot = q->work.as<int>();
+    p.taken = q->misc.as<int>();
+    launch_qp_write(p, f64, q->stream);
+    HIPCHK(q, hipGetLastError());
+    int t = 0;
+    HIPCHK(q, hipMemcpyAsync(&t, p.taken, sizeof(int), hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    if (t < 0 || t > q->cap - q->n) return fail(q, PBD_ERR_HIP, "the write reported %d entries", t);
+    const int n0 = q->n, n1 = q->n + t;
+    q->h_ids.resize((size_t)n1 * 5);
+    q->h_hd.resize((size_t)n1 * q->HW);
+    q->h_b.resize(n1);
+    if (t > 0) {
+        HIPCHK(q, hipMemcpyAsync(&q->h_ids[(size_t)n0 * 5], q->ids.as<int32_t>() + (size_t)n0 * 5, (size_t)t * 5 * sizeof(int32_t),
+                                hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipMemcpyAsync(&q->h_hd[(size_t)n0 * q->HW], q->hd.as<int32_t>() + (size_t)n0 * q->HW,
+                                (size_t)t * q->HW * sizeof(int32_t), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipMemcpyAsync(&q->h_b[n0], q->b.as<double>() + n0, (size_t)t * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+    }
+    q->n = n1;
+    if (taken) *taken = t;
+    return PBD_OK;
+}
+
+// group numbers of the entries list[0..k) (ascending indices): equal ids share a group, groups numbered by first member
+std::vector<int> qp_groups(const pbd_qp *q, const std::vector<int> &list, int *ngroups)
+{
+    std::map<std::array<int32_t, 5>, int> seen;
+    std::vector<int> g(list.size());
+    for (size_t k = 0; k < list.size(); ++k) {
+        std::array<int32_t, 5> id;
+        for (int c = 0; c < 5; ++c) id[c] = q->h_ids[(size_t)list[k] * 5 + c];
+        auto it = seen.emplace(id, (int)seen.size()).first;
+        g[k] = it->second;
+    }
+    *ngroups = (int)seen.size();
+    return g;
+}
+
+// qp_refresh: w and l from a (lincomb's order), the clamps, lb
+int qp_refresh(pbd_qp *q)
+{
+    // every QP call works on q->stream (created non-blocking, or the caller's): the duals are read in its order, after all
+    // work queued before (prune's compaction in particular)
+    std::vector<double> a(q->n);
+    if (q->n) HIPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    std::vector<int> P;
+    for (int i = 0; i < q->n; ++i) if (a[i] > 0) P.push_back(i);
+    std::stable_sort(P.begin(), P.end(), [&](int u, int v) { return a[u] < a[v]; });
+    double l = 0.0;
+    for (int i : P) l = l + q->h_b[i] * a[i];
+    // the entries carrying each layout block, in P's order
+    const int nslots = (int)q->slot_len_h.size();
+    std::vector<std::vector<int2> > per(nslots);
+    for (int i : P) {
+        const int32_t *h = &q->h_hd[(size_t)i * q->HW];
+        for (int b = 0; b < h[0]; ++b) per[q->slot_of_h[h[2 + 3 * b]]].push_back(make_int2(i, h[4 + 3 * b]));
+    }
+    std::vector<QpTask> tasks;
+    std::vector<int2> ent;
+    for (int s = 0; s < nslots; ++s) {
+        if (per[s].empty()) continue;
+        const int begin = (int)ent.size();
+        ent.insert(ent.end(), per[s].begin(), per[s].end());
+        const int off = q->slot_off_h[s];
+        for (int c0 = 0; c0 < q->slot_len_h[s]; c0 += PBD_QP_LANES)
+            tasks.push_back(QpTask{off, c0, std::min(PBD_QP_LANES, q->slot_len_h[s] - c0), begin, (int)ent.size(), 0});
+    }
+    QpTask *d_tasks = nullptr;
+    int2 *d_ent = nullptr;
+    if (int rc = carve(q, q->lc, [&](Carve &c) {
+            d_tasks = c.take<QpTask>(tasks.size() * sizeof(QpTask));
+            d_ent = c.take<int2>(ent.size() * sizeof(int2) + 16);
+        })) return rc;
+    if (!tasks.empty()) {
+        HIPCHK(q, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(QpTask), hipMemcpyHostToDevice, q->stream));
+        HIPCHK(q, hipMemcpyAsync(d_ent, ent.data(), ent.size() * sizeof(int2), hipMemcpyHostToDevice, q->stream));
+    }
+    QpLincombParams lp{};
+    lp.c = qp_cache(q);
+    lp.tasks = d_tasks; lp.ntasks = (int)tasks.size();
+    lp.ent = d_ent;
+    lp.ww = q->misc.as<double>() + 1;
+    launch_qp_lincomb(lp, q->stream);
+    HIPCHK(q, hipGetLastError());
+    double ww = 0;
+    HIPCHK(q, hipMemcpyAsync(&ww, lp.ww, sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    const double lb = l - ww * 0.5;
+    if (q->have_lb && !(lb > q->lb - 1e-5)) q->lb_dropped = 1;
+    q->l = l; q->ww = ww; q->lb = lb; q->have_lb = true;
+    return PBD_OK;
+}
+
+// G = R(w . x) - b of every entry, then computeloss over the whole cache
+int qp_true_loss(pbd_qp *q, double *loss)
+{
+    HIPCHK(q, q->work.ensure((size_t)std::max(q->n, 1) * sizeof(double)));
+    QpScoreParams sp{};
+    sp.c = qp_cache(q); sp.w = q->w.as<double>(); sp.first = 0; sp.count = q->n; sp.sub_b = 1; sp.scale = 1.0;
+    sp.out = q->work.as<double>();
+    launch_qp_score(sp, q->stream);
+    HIPCHK(q, hipGetLastError());
+    std::vector<double> G(q->n);
+    if (q->n) HIPCHK(q, hipMemcpyAsync(G.data(), sp.out, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    std::vector<int> all(q->n);
+    std::iota(all.begin(), all.end(), 0);
+    int ng = 0;
+    const std::vector<int> g = qp_groups(q, all, &ng);
+    std::vector<double> best(ng, 0.0);   // max(0, max slack) of every group
+    for (int i = 0; i < q->n; ++i) {
+        const double slack = -G[i];
+        if (slack > best[g[i]]) best[g[i]] = slack;
+    }
+    double s = 0.0;
+    for (int k = 0; k < ng; ++k) if (best[k] > 0) s = s + best[k];
+    *loss = s;
+    return PBD_OK;
+}
+
+uint64_t qp_splitmix64(uint64_t seed, uint64_t i)
+{
+    const uint64_t base = seed * 0x9E3779B97F4A7C15ULL + 0x1234567ULL;
+    uint64_t z = base + i * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+int qp_set_sv(pbd_qp *q, int count)
+{
+    if (count > 0) HIPCHK(q, hipMemsetAsync(q->sv.p, 1, (size_t)count, q->stream));
+    return PBD_OK;
+}
+
+// qp_one: the pass over the support vectors, refresh, the fixed set's sv, lb and ub
+int qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed)
+{
+    std::vector<double> a(q->n);
+    std::vector<uint8_t> sv(q->n);
+    if (q->n) {
+        HIPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+    }
+    std::vector<int> S;
+    for (int i = 0; i < q->n; ++i) if (sv[i]) S.push_back(i);
+    const int nsv = (int)S.size();
+    if (nsv == 0) return fail(q, PBD_ERR_STATE, "no support vectors (empty cache)");
+    std::vector<int> perm(nsv);
+    if (order) {
+        if (norder != nsv) return fail(q, PBD_ERR_INVALID, "order of %d indices, %d support vectors", norder, nsv);
+        std::vector<char> used(nsv, 0);
+        for (int k = 0; k < nsv; ++k) {
+            if (order[k] < 0 || order[k] >= nsv || used[order[k]]) return fail(q, PBD_ERR_INVALID, "order is not a permutation of 0..%d", nsv - 1);
+            used[order[k]] = 1;
+            perm[k] = order[k];
+        }
+    } else {
+        std::vector<uint64_t> z(nsv);
+        for (int k = 0; k < nsv; ++k) z[k] = qp_splitmix64(seed, (uint64_t)k + 1);
+        std::iota(perm.begin(), perm.end(), 0);
+        std::stable_sort(perm.begin(), perm.end(), [&](int u, int v) { return z[u] < z[v]; });
+    }
+    int ng = 0;
+    const std::vector<int> gS = qp_groups(q, S, &ng);
+    std::vector<double> idC(ng, 0.0);
+    std::vector<int> idI(ng, -1);
+    for (int k = 0; k < nsv; ++k) {
+        idC[gS[k]] = idC[gS[k]] + a[S[k]];
+        if (a[S[k]] > 0) idI[gS[k]] = S[k];
+    }
+    std::vector<int> ord(nsv), gidx(nsv);
+    for (int k = 0; k < nsv; ++k) { ord[k] = S[perm[k]]; gidx[k] = gS[perm[k]]; }
+    // work: order, gidx (int), idC, err (double), idI (int)
+    const size_t o_ord = 0, o_g = o_ord + (size_t)nsv * 4, o_c = (o_g + (size_t)nsv * 4 + 7) / 8 * 8, o_e = o_c + (size_t)ng * 8,
+                 o_i = o_e + (size_t)ng * 8, tot = o_i + (size_t)ng * 4;
+    HIPCHK(q, q->work.ensure(tot + 16));
+    char *wb = q->work.as<char>();
+    HIPCHK(q, hipMemcpyAsync(wb + o_ord, ord.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
+    HIPCHK(q, hipMemcpyAsync(wb + o_g, gidx.data(), (size_t)nsv * 4, hipMemcpyHostToDevice, q->stream));
+    HIPCHK(q, hipMemcpyAsync(wb + o_c, idC.data(), (size_t)ng * 8, hipMemcpyHostToDevice, q->stream));
+    HIPCHK(q, hipMemsetAsync(wb + o_e, 0, (size_t)ng * 8, q->stream));
+    HIPCHK(q, hipMemcpyAsync(wb + o_i, idI.data(), (size_t)ng * 4, hipMemcpyHostToDevice, q->stream));
+    QpPassParams pp{};
+    pp.c = qp_cache(q);
+    pp.order = reinterpret_cast<const int *>(wb + o_ord); pp.gidx = reinterpret_cast<const int *>(wb + o_g);
+    pp.nsteps = nsv; pp.ngroups = ng;
+    pp.idC = reinterpret_cast<double *>(wb + o_c); pp.err = reinterpret_cast<double *>(wb + o_e);
+    pp.idI = reinterpret_cast<int *>(wb + o_i);
+    pp.loss = q->misc.as<double>() + 2;
+    launch_qp_pass(pp, q->stream);
+    HIPCHK(q, hipGetLastError());
+    double loss = 0;
+    HIPCHK(q, hipMemcpyAsync(&loss, pp.loss, sizeof(double), hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    if (int rc = qp_refresh(q)) return rc;
+    if (int rc = qp_set_sv(q, q->nfix)) return rc;
+    q->loss = loss;
+    q->ub = q->ww * 0.5 + loss;
+    return PBD_OK;
+}
+
+void qp_fill_state(const pbd_qp *q, pbd_qp_info *st, int nsv)
+{
+    if (!st) return;
+    *st = pbd_qp_info{};
+    st->n = q->n; st->nsv = nsv; st->nfix = q->nfix; st->capacity = q->cap; st->len = q->L; st->hdr_words = q->HW; st->values = q->V;
+    st->lb = q->lb; st->ub = q->ub; st->loss = q->loss; st->l = q->l;
+    st->lb_dropped = q->lb_dropped; st->passes = q->passes; st->converged = q->converged;
+}
+
+int qp_count_sv(pbd_qp *q, int *nsv)
+{
+    std::vector<uint8_t> sv(q->n);
+    if (q->n) HIPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+    HIPCHK(q, hipStreamSynchronize(q->stream));
+    int k = 0;
+    for (uint8_t v : sv) k += v ? 1 : 0;
+    *nsv = k;
+    return PBD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbd_qp_create(const pbd_handle *h, const struct pbd_qp_config *cfg, pbd_qp **out)
+{
+    return guarded(nullptr, [&]() -> int {
+        if (!h || !cfg || !out) return fail(nullptr, PBD_ERR_INVALID, "null argument");
+        *out = nullptr;
+        if (cfg->capacity <= 0) return fail(nullptr, PBD_ERR_INVALID, "capacity %d (at least 1)", cfg->capacity);
+        const double C = cfg->C == 0 ? 0.002 : cfg->C, wpos = cfg->wpos == 0 ? 2.0 : cfg->wpos;
+        if (!(C > 0) || !std::isfinite(C) || !(wpos > 0) || !std::isfinite(wpos))
+            return fail(nullptr, PBD_ERR_INVALID, "C %g and wpos %g must be finite and positive", cfg->C, cfg->wpos);
+        (void)hipSetDevice(h->device);
+        std::unique_ptr<pbd_qp> q(new pbd_qp);
+        q->device = h->device;
+        const QpLayout lay = qp_layout(h);
+        q->L = lay.L; q->V = lay.V; q->in_hw = lay.in_hw; q->fp = lay.fp;
+        q->MB = (lay.in_hw - 4) / 2;
+        if (q->MB > 256 || q->MB < 1) return fail(nullptr, PBD_ERR_UNSUPPORTED, "examples of %d blocks (at most 256)", q->MB);
+        if (q->V % 4) return fail(nullptr, PBD_ERR_INVALID, "example stride %d", q->V);
+        q->HW = 2 + 3 * q->MB;
+        q->cap = cfg->capacity;
+        q->Cpos = C * wpos; q->Cneg = C;
+        q->slot_of_h.assign(q->L, -1);
+        for (auto &b : lay.blocks) {
+            if (b.first < 0 || b.first + (long long)b.second > q->L)
+                return fail(nullptr, PBD_ERR_INVALID, "layout block at %d of %d values outside w", b.first, b.second);
+            if (q->slot_of_h[b.first] < 0) {
+                q->slot_of_h[b.first] = (int)q->slot_len_h.size();
+                q->slot_len_h.push_back(b.second);
+                q->slot_off_h.push_back(b.first);
+            }
+        }
+        // model2vec's defaults in this vector order
+        q->wreg_h.assign(q->L, 1.0);
+        q->w0_h.assign(q->L, 0.0);
+        std::vector<int> nn;
+        if (cfg->wreg) q->wreg_h.assign(cfg->wreg, cfg->wreg + q->L);
+        else for (int c = 0; c < h->NC; ++c) q->wreg_h[h->biasid[h->mix_offset[h->part_offset[c]]]] = 0.01;
+        if (cfg->w0) q->w0_h.assign(cfg->w0, cfg->w0 + q->L);
+        else for (int d = 0; d < h->ndefs; ++d) { q->w0_h[h->nbias + 4 * d] = 0.01; q->w0_h[h->nbias + 4 * d + 2] = 0.01; }
+        if (cfg->noneg) {
+            if (cfg->nnoneg < 0) return fail(nullptr, PBD_ERR_INVALID, "nnoneg %d", cfg->nnoneg);
+            for (int k = 0; k < cfg->nnoneg; ++k) {
+                if (cfg->noneg[k] < 0 || cfg->noneg[k] >= q->L) return fail(nullptr, PBD_ERR_INVALID, "noneg index %d", cfg->noneg[k]);
+                nn.push_back(cfg->noneg[k]);
+            }
+        } else {
+            for (int d = 0; d < h->ndefs; ++d) { nn.push_back(h->nbias + 4 * d); nn.push_back(h->nbias + 4 * d + 2); }
+        }
+        for (int k = 0; k < q->L; ++k)
+            if (!std::isfinite(q->wreg_h[k]) || q->wreg_h[k] == 0 || !std::isfinite(q->w0_h[k]))
+                return fail(nullptr, PBD_ERR_INVALID, "wreg / w0 at %d: %g / %g (finite, wreg nonzero)", k, q->wreg_h[k], q->w0_h[k]);
+        q->nnoneg = (int)nn.size();
+        if (cfg->stream) q->stream.borrow(reinterpret_cast<hipStream_t>(cfg->stream));
+        else HIPCHK(nullptr, q->stream.create());
+        const size_t cap = (size_t)q->cap;
+        HIPCHK(nullptr, q->x.alloc_exact(cap * q->V * sizeof(float)));
+        HIPCHK(nullptr, q->bm.alloc_exact(cap * q->V));
+        HIPCHK(nullptr, q->hd.alloc_exact(cap * q->HW * sizeof(int32_t)));
+        HIPCHK(nullptr, q->ids.alloc_exact(cap * 5 * sizeof(int32_t)));
+        HIPCHK(nullptr, q->b.alloc_exact(cap * sizeof(double)));
+        HIPCHK(nullptr, q->d.alloc_exact(cap * sizeof(double)));
+        HIPCHK(nullptr, q->a.alloc_exact(cap * sizeof(double)));
+        HIPCHK(nullptr, q->sv.alloc_exact(cap));
+        HIPCHK(nullptr, q->w.alloc_exact((size_t)q->L * sizeof(double)));
+        HIPCHK(nullptr, q->wraw.alloc_exact((size_t)q->L * sizeof(double)));
+        HIPCHK(nullptr, q->misc.alloc_exact(4 * sizeof(double)));
+        HIPCHK(nullptr, hipMemsetAsync(q->w.p, 0, (size_t)q->L * sizeof(double), q->stream));
+        HIPCHK(nullptr, hipMemsetAsync(q->a.p, 0, cap * sizeof(double), q->stream));
+        HIPCHK(nullptr, hipMemsetAsync(q->sv.p, 0, cap, q->stream));
+        HIPCHK(nullptr, q->wreg.upload(q->wreg_h));
+        HIPCHK(nullptr, q->w0.upload(q->w0_h));
+        if (!nn.empty()) HIPCHK(nullptr, q->noneg.upload(nn));
+        HIPCHK(nullptr, q->slot_of.upload(q->slot_of_h));
+        HIPCHK(nullptr, q->slot_len.upload(q->slot_len_h));   // DevTable uploads are blocking copies
+        HIPCHK(nullptr, hipStreamSynchronize(q->stream));
+        *out = q.release();
+        return PBD_OK;
+    });
+}
+
+void pbd_qp_destroy(pbd_qp *q)
+{
+    if (!q) return;
+    (void)hipSetDevice(q->device);
+    (void)hipStreamSynchronize(q->stream);
+    delete q;
+}
+
+const char *pbd_qp_last_error(const pbd_qp *q) { return q ? q->err.c_str() : g_create_error.c_str(); }
+
+int pbd_qp_add(pbd_qp *q, const pbd_handle *h, int n, const int32_t *hdr, const void *values, const int32_t *ids, int *taken)
+{
+    return entry(q, h && (n <= 0 || (hdr && values && ids)), [&]() -> int {
+        if (n < 0) return fail(q, PBD_ERR_INVALID, "n %d", n);
+        if (qp_layout(h).fp != q->fp) return fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
+        for (int e = 0; e < n; ++e)
+            if (qp_header_ok(q, hdr + (size_t)e * q->in_hw) == 0)
+                return fail(q, PBD_ERR_INVALID, "example %d: a block that is not a block of the model vector, or bad counts", e);
+        if (taken) *taken = 0;
+        if (n == 0) return PBD_OK;
+        const size_t rs = h->rs;
+        const size_t hb = (size_t)n * q->in_hw * 4, vb = (size_t)n * q->V * rs, ib = (size_t)n * 5 * 4;
+        int32_t *d_hdr = nullptr, *d_ids = nullptr;
+        char *d_values = nullptr;
+        if (int rc = carve(q, q->stage, [&](Carve &c) {
+                d_hdr = c.take<int32_t>(hb); d_values = c.take<char>(vb); d_ids = c.take<int32_t>(ib);
+            })) return rc;
+        HIPCHK(q, hipMemcpyAsync(d_hdr, hdr, hb, hipMemcpyHostToDevice, q->stream));
+        HIPCHK(q, hipMemcpyAsync(d_values, values, vb, hipMemcpyHostToDevice, q->stream));
+        HIPCHK(q, hipMemcpyAsync(d_ids, ids, ib, hipMemcpyHostToDevice, q->stream));
+        QpWriteParams p{};
+        p.in_hdr = d_hdr; p.in_values = d_values; p.in_ids = d_ids;
+        p.m = n;
+        return qp_write(q, p, h->f64, taken);
+    });
+}
+
+int pbd_qp_add_device(pbd_qp *q, pbd_handle *h, const int32_t *d_payload, int capacity, const int32_t *d_hdr, const void *d_values,
+                      int label, int id_base, int32_t *d_taken)
+{
+    return entry(q, h && d_payload && (capacity <= 0 || (d_hdr && d_values)), [&]() -> int {
+        if (capacity < 0) return fail(q, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (qp_layout(h).fp != q->fp) return fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
+        (void)hipSetDevice(q->device);
+        if (h->stream.s != q->stream.s) {   // the QP's stream waits for the handle's
+            Event ev;
+            HIPCHK(q, hipEventCreateWithFlags(&ev.p, hipEventDisableTiming));
+            HIPCHK(q, hipEventRecord(ev.p, h->stream));
+            HIPCHK(q, hipStreamWaitEvent(q->stream, ev.p, 0));
+        }
+        QpWriteParams p{};
+        p.in_hdr = d_hdr; p.in_values = d_values; p.in_ids = nullptr;
+        p.payload = d_payload; p.rec_stride = ::stride(h); p.label = label; p.id_base = id_base;
+        p.m = capacity;
+        p.taken_user = d_taken;
+        if (capacity == 0) {
+            if (d_taken) HIPCHK(q, hipMemsetAsync(d_taken, 0, sizeof(int32_t), q->stream));
+            HIPCHK(q, hipStreamSynchronize(q->stream));
+            return PBD_OK;
+        }
+        return qp_write(q, p, h->f64, nullptr);
+    });
+}
+
+int pbd_qp_fix(pbd_qp *q)
+{
+    return entry(q, true, [&]() -> int {
+        q->nfix = q->n;
+        if (int rc = qp_set_sv(q, q->n)) return rc;
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_prune(pbd_qp *q, int *n)
+{
+    return entry(q, true, [&]() -> int {
+        q->lb_dropped = 0;
+        std::vector<double> a(q->n);
+        std::vector<uint8_t> sv(q->n);
+        if (q->n) {
+            HIPCHK(q, hipMemcpyAsync(a.data(), q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+            HIPCHK(q, hipMemcpyAsync(sv.data(), q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+            HIPCHK(q, hipStreamSynchronize(q->stream));
+        }
+        bool all = true;
+        for (uint8_t v : sv) all = all && v;
+        if (all) for (int i = 0; i < q->n; ++i) sv[i] = (a[i] > 0 || i < q->nfix) ? 1 : 0;
+        std::vector<int> I;
+        for (int i = 0; i < q->n; ++i) if (sv[i]) I.push_back(i);
+        const int n1 = (int)I.size();
+        if (n1 == 0) return fail(q, PBD_ERR_STATE, "nothing to keep (empty cache)");
+        int first = 0;
+        while (first < n1 && I[first] == first) ++first;
+        // compaction in ascending chunks of at most `chunk` entries through a scratch buffer freed afterwards: a chunk's sources
+        // I[k] >= k lie at or past the chunk's own start and past every earlier chunk's destinations, so each chunk reads
+        // entries no earlier chunk has overwritten
+        const size_t V = q->V, HW = q->HW;
+        const size_t entry_bytes = V * 5 + HW * 4 + 20 + 3 * 8;
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)std::max(n1 - first, 1), kQpPruneChunkEntries),
+                                                                     kQpPruneChunkBytes / entry_bytes));
+        if (first < n1) {
+            const size_t c = (size_t)chunk;
+            QpGatherParams gp{};   // a chunk's copies in three groups, each starting 256-aligned and packed inside: x bm, hd ids, b d a
+            if (int rc = carve(q, q->scratch, [&](Carve &w) {
+                    gp.x = w.take<float>(c * V * 4); gp.bm = w.take<uint8_t>(c * V, 1);
+                    gp.hd = w.take<int32_t>(c * HW * 4); gp.ids = w.take<int32_t>(c * 20, 1);
+                    gp.b = w.take<double>(c * 8); gp.d = w.take<double>(c * 8, 1); gp.a = w.take<double>(c * 8, 1);
+                }, true)) return rc;
+            HIPCHK(q, q->work.ensure((size_t)(n1 - first) * sizeof(int)));
+            HIPCHK(q, hipMemcpyAsync(q->work.p, &I[first], (size_t)(n1 - first) * sizeof(int), hipMemcpyHostToDevice, q->stream));
+            for (int k0 = first; k0 < n1; k0 += chunk) {
+                const size_t cnt = (size_t)std::min(chunk, n1 - k0), k = (size_t)k0;
+                gp.c = qp_cache(q); gp.src = q->work.as<int>() + (k0 - first); gp.count = (int)cnt; gp.dst0 = k0;
+                launch_qp_gather(gp, q->stream);
+                HIPCHK(q, hipGetLastError());
+                auto back = [&](void *dst, const void *src, size_t bytes) {
+                    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, q->stream);
+                };
+                HIPCHK(q, back(q->x.as<float>() + k * V, gp.x, cnt * V * 4));
+                HIPCHK(q, back(q->bm.as<uint8_t>() + k * V, gp.bm, cnt * V));
+                HIPCHK(q, back(q->hd.as<int32_t>() + k * HW, gp.hd, cnt * HW * 4));
+                HIPCHK(q, back(q->ids.as<int32_t>() + k * 5, gp.ids, cnt * 20));
+                HIPCHK(q, back(q->b.as<double>() + k, gp.b, cnt * 8));
+                HIPCHK(q, back(q->d.as<double>() + k, gp.d, cnt * 8));
+                HIPCHK(q, back(q->a.as<double>() + k, gp.a, cnt * 8));
+            }
+            HIPCHK(q, hipStreamSynchronize(q->stream));
+            q->scratch = DevBuf{};
+        }
+        int nfix = 0;
+        for (int k = 0; k < n1; ++k) {
+            const int i = I[k];
+            if (i < q->nfix) ++nfix;
+            if (k != i) {
+                std::copy_n(&q->h_ids[(size_t)i * 5], 5, &q->h_ids[(size_t)k * 5]);
+                std::copy_n(&q->h_hd[(size_t)i * q->HW], q->HW, &q->h_hd[(size_t)k * q->HW]);
+                q->h_b[k] = q->h_b[i];
+            }
+        }
+        q->h_ids.resize((size_t)n1 * 5); q->h_hd.resize((size_t)n1 * q->HW); q->h_b.resize(n1);
+        q->n = n1; q->nfix = nfix;
+        if (q->cap > n1) HIPCHK(q, hipMemsetAsync(q->sv.as<uint8_t>() + n1, 0, (size_t)(q->cap - n1), q->stream));
+        if (int rc = qp_set_sv(q, n1)) return rc;
+        if (int rc = qp_refresh(q)) return rc;
+        if (n) *n = n1;
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed, struct pbd_qp_info *state)
+{
+    return entry(q, true, [&]() -> int {
+        q->lb_dropped = 0;
+        if (int rc = qp_one(q, order, norder, seed)) return rc;
+        q->passes = 1; q->converged = 0;
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed, struct pbd_qp_info *state)
+{
+    return entry(q, true, [&]() -> int {
+        if (std::isnan(tol)) return fail(q, PBD_ERR_INVALID, "tol is NaN");
+        if (iter < 0) return fail(q, PBD_ERR_INVALID, "iter %d", iter);
+        if (q->n == 0) return fail(q, PBD_ERR_STATE, "empty cache");
+        q->lb_dropped = 0; q->passes = 0; q->converged = 0;
+        if (int rc = qp_refresh(q)) return rc;
+        double loss = 0;
+        if (int rc = qp_true_loss(q, &loss)) return rc;
+        double ub = q->ww * 0.5 + loss;
+        if (int rc = qp_set_sv(q, q->n)) return rc;
+        for (int t = 0; t < iter; ++t) {
+            if (int rc = qp_one(q, nullptr, 0, seed + (uint64_t)t)) return rc;
+            q->passes = t + 1;
+            const double lb = q->lb, ub_est = ub < q->ub ? ub : q->ub;
+            if (lb > 0 && 1 - lb / ub_est < tol) {
+                if (int rc = qp_true_loss(q, &loss)) return rc;
+                const double u = q->ww * 0.5 + loss;
+                ub = u < ub ? u : ub;
+                if (1 - lb / ub < tol) { q->converged = 1; break; }
+                if (int rc = qp_set_sv(q, q->n)) return rc;
+            }
+        }
+        q->ub = ub;
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_weights(pbd_qp *q, double *w)
+{
+    return entry(q, w != nullptr, [&]() -> int {
+        std::vector<double> v(q->L);
+        HIPCHK(q, hipMemcpyAsync(v.data(), q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        for (int k = 0; k < q->L; ++k) w[k] = v[k] / q->wreg_h[k] + q->w0_h[k];
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_scores(pbd_qp *q, double *s, int *n)
+{
+    return entry(q, s && n, [&]() -> int {
+        std::vector<int> pos;
+        for (int i = 0; i < q->n; ++i) if (q->h_ids[(size_t)i * 5] > 0) pos.push_back(i);
+        *n = (int)pos.size();
+        if (pos.empty()) return PBD_OK;
+        int *d_pos = nullptr;
+        double *d_out = nullptr;
+        if (int rc = carve(q, q->work, [&](Carve &c) { d_pos = c.take<int>(pos.size() * 4); d_out = c.take<double>(pos.size() * 8); }))
+            return rc;
+        HIPCHK(q, hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, q->stream));
+        QpCache c = qp_cache(q);
+        launch_qp_wraw(c, q->wraw.as<double>(), q->stream);
+        QpScoreParams sp{};
+        sp.c = c; sp.w = q->wraw.as<double>(); sp.list = d_pos; sp.count = (int)pos.size(); sp.sub_b = 0; sp.scale = q->Cpos;
+        sp.out = d_out;
+        launch_qp_score(sp, q->stream);
+        HIPCHK(q, hipGetLastError());
+        HIPCHK(q, hipMemcpyAsync(s, sp.out, pos.size() * 8, hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_state(pbd_qp *q, struct pbd_qp_info *state, double *a, uint8_t *sv, double *w)
+{
+    return entry(q, true, [&]() -> int {
+        if (a && q->n) HIPCHK(q, hipMemcpyAsync(a, q->a.p, (size_t)q->n * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        if (sv && q->n) HIPCHK(q, hipMemcpyAsync(sv, q->sv.p, (size_t)q->n, hipMemcpyDeviceToHost, q->stream));
+        if (w) HIPCHK(q, hipMemcpyAsync(w, q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        int nsv = 0;
+        if (int rc = qp_count_sv(q, &nsv)) return rc;
+        qp_fill_state(q, state, nsv);
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values, double *b, double *d, int32_t *ids)
+{
+    return entry(q, true, [&]() -> int {
+        if (first < 0 || count < 0 || (long long)first + count > q->n)
+            return fail(q, PBD_ERR_INVALID, "entries %d..%d of %d", first, first + count - 1, q->n);
+        const size_t f = first, c = count;
+        if (c == 0) return PBD_OK;
+        if (hdr) HIPCHK(q, hipMemcpyAsync(hdr, q->hd.as<int32_t>() + f * q->HW, c * q->HW * 4, hipMemcpyDeviceToHost, q->stream));
+        if (values) HIPCHK(q, hipMemcpyAsync(values, q->x.as<float>() + f * q->V, c * q->V * 4, hipMemcpyDeviceToHost, q->stream));
+        if (b) HIPCHK(q, hipMemcpyAsync(b, q->b.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
+        if (d) HIPCHK(q, hipMemcpyAsync(d, q->d.as<double>() + f, c * 8, hipMemcpyDeviceToHost, q->stream));
+        if (ids) HIPCHK(q, hipMemcpyAsync(ids, q->ids.as<int32_t>() + f * 5, c * 20, hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+}  // extern "C"

@@ -347,7 +347,7 @@ struct ClusterParams {
     int nclouds, nchunks;         // chunks of kClChunk points per box (the largest cloud's)
     const double *boxes;          // [box][6] camera boxes, Rect3d member order
     int crop_cap, index_cap;
-    // workspace (pbd_capi.hip sizes it from crop_cap / boxes / nchunks)
+    // workspace (pbd_capi_post.hip sizes it from crop_cap / boxes / nchunks: cluster_pieces)
     long long *chunk_off;         // [in_cap * nchunks + 1]: cropped points per chunk, then their exclusive scan
     long long *part;              // scan partials
     int32_t *crop_idx, *crop_box; // [crop_cap]: the point index and the box of every cropped point
@@ -382,7 +382,7 @@ struct PlaneParams {
     float depth_change, dist_thr, cos_thr;
     double max_curv;
     int min_inliers, plane_cap, cand_cap;
-    // workspace (pbd_capi.hip sizes it: plane_layout)
+    // workspace (pbd_capi_post.hip sizes it: plane_pieces)
     float4 *xyz;                  // [npts] the points
     float4 *rsx, *rsy;            // [npts] row sums of the x / y gradients (w of rsx: 1 when the row window holds a depth edge)
     float4 *nrm;                  // [npts] normal and d = n . P

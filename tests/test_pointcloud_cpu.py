@@ -240,7 +240,7 @@ def test_camera_box_and_cloud_from_depth():
     assert np.isnan(c[0, 1]).all() and np.isnan(c[1]).all()
 
 
-# ---- the clustering workspace (pbd_capi.hip: cluster_layout), host logic, no GPU needed -------------------------------------
+# ---- the clustering workspace (pbd_capi_post.hip: cluster_layout), host logic, no GPU needed -------------------------------------
 def test_cluster_workspace_layout_near_the_crop_limit():
     """The bucket table, the scan partials and every carved piece fit their int / index ranges up to the largest accepted crop
     capacity (2^29), and a larger one is refused before anything is sized."""

@@ -7,7 +7,7 @@ B=$R/partsbaseddetector_amd/csrc/build
 if [ "$1" = build ]; then
     FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt"
     /opt/rocm/bin/hipcc $FL -DPBD_DT_STATS -c -o $B/pbd_kernels_dp_stats.o $R/partsbaseddetector_amd/csrc/pbd_kernels_dp.hip &&
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/libpbd_dtstats.so $B/pbd_capi.o $B/pbd_kernels_features.o $B/pbd_kernels_conv.o $B/pbd_kernels_conv_mfma.o $B/pbd_kernels_dp_stats.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/libpbd_dtstats.so $B/pbd_capi.o $B/pbd_capi_post.o $B/pbd_capi_train.o $B/pbd_kernels_features.o $B/pbd_kernels_conv.o $B/pbd_kernels_conv_mfma.o $B/pbd_kernels_dp_stats.o
     exit $?
 fi
 # usage on the box: tools/dt_stats.sh run [rows cols frames]   (default 480 640 4)
