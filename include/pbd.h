@@ -746,7 +746,7 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
 /* ---- per-kernel timing with HIP events on the library's stream (bench.py roofline) ---- */
 enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CONV, PBD_K_DT_ROWS,
        PBD_K_DT_COLS, PBD_K_DP_COMBINE, PBD_K_DP_ROOT, PBD_K_ARGMIN,
-       /* pbd_boxes3d_camera*, pbd_cluster_objects*; k_cl_crop_scan / k_cl_grid_scan time the three k_cl_scan_* kernels of that scan */
+       /* pbd_boxes3d_camera*, pbd_cluster_objects*; k_cl_crop_scan / k_cl_grid_scan time the three k_scan_* kernels of that scan */
        PBD_K_CAMERA_BOXES, PBD_K_CL_CROP_COUNT, PBD_K_CL_CROP_SCAN, PBD_K_CL_CROP_SCATTER, PBD_K_CL_CLEAR, PBD_K_CL_GRID_COUNT,
        PBD_K_CL_GRID_SCAN, PBD_K_CL_GRID_SCATTER, PBD_K_CL_HOOK, PBD_K_CL_LABEL, PBD_K_CL_BEST, PBD_K_CL_SELECT, PBD_K_CL_OUT,
        /* pbd_depth_consistency*; k_dc_select times its three size classes, k_dc_compact the decision and the compaction */

@@ -401,17 +401,6 @@ struct PlaneParams {
     long long *status;            // [2]: kept points of all clouds, most planes of one cloud
 };
 
-// cv::Rect operator& in 64 bits (an empty intersection is Rect()); pbd_kernels_depth.hip, pbd_kernels_consistency.hip
-__device__ inline void rect_and64(long long &x, long long &y, long long &w, long long &h, long long bx, long long by, long long bw,
-                                  long long bh)
-{
-    const long long x1 = x > bx ? x : bx, y1 = y > by ? y : by;
-    w = (x + w < bx + bw ? x + w : bx + bw) - x1;
-    h = (y + h < by + bh ? y + h : by + bh) - y1;
-    x = x1; y = y1;
-    if (w <= 0 || h <= 0) x = y = w = h = 0;
-}
-
 // depth consistency of each record's parts (pbd_depth_consistency*; pbd_kernels_consistency.hip)
 constexpr int kDcWaveKeys = 1024;     // samples of a median one wave holds in registers
 constexpr int kDcBlockKeys = 4096;    // samples of a median one 256-thread workgroup holds in registers; larger boxes stream

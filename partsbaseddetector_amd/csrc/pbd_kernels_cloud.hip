@@ -7,18 +7,19 @@
 //
 // The clustering of every box is one fixed sequence of launches (no host loop, nothing read back), each a grid-stride loop:
 //   crop     k_cl_crop_count: cropped points of every (box, chunk of 1024 points of the box's cloud); an exclusive scan of those
-//            counts; k_cl_crop_scatter: the cropped points in ascending point order, box after box (index, box, xyz)
+//            counts (launch_scan, pbd_device.h, as is the grid's scan); k_cl_crop_scatter: the cropped points in ascending
+//            point order, box after box (index, box, xyz)
 //   grid     a hashed uniform grid of 2 cm cells: k_cl_grid_count (bucket of every cropped point, counts), a scan,
 //            k_cl_grid_scatter (points in bucket order).  2 cm is twice the radius, so two points within the radius lie in
 //            neighbouring cells whatever the rounding of x * 50; the grid only prunes, the exact predicate decides every edge
-//   cc       k_cl_hook: union-find over the 27 neighbouring cells (lock-free hooking of the larger root under the smaller, ECL-CC
-//            style, agent-scope atomics); k_cl_label: every point's root, component sizes.  A root is the smallest cropped
-//            position of its component, so labels do not depend on the order of the atomics
+//   cc       k_cl_hook: union-find over the 27 neighbouring cells (uf_unite, pbd_device.h: lock-free hooking of the larger root
+//            under the smaller, ECL-CC style, agent-scope atomics); k_cl_label: every point's root, component sizes.  A root
+//            is the smallest cropped position of its component, so labels do not depend on the order of the atomics
 //   select   k_cl_best: per box the largest component (ties: the smallest root = the smallest point index), one 64-bit atomicMax;
 //            k_cl_select: output counts and offsets (one workgroup); k_cl_out: one workgroup per box, the crop list filtered to
 //            the winner in order, and the centroid as three sequential fp32 sums over points staged in LDS
 // Every float / double operation whose bits are compared is an explicitly rounded intrinsic, so none of them is contracted.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 
 #include <math.h>
 
@@ -29,21 +30,8 @@ namespace {
 
 constexpr int kClThreads = 256;
 constexpr int kClWaves = kClThreads / 64;
-constexpr int kClTile = 4 * kClThreads;          // elements of one scan tile
-static_assert(kClChunk == kClTile, "a crop chunk is one scan tile of points");
+static_assert(kClThreads == kScanThreads && kClChunk == kScanTile, "a crop chunk is one scan tile of points");
 constexpr float kClCellInv = 50.f;              // 1 / (2 cm cell edge)
-
-__device__ inline float cl_qnan() { return __int_as_float(0x7fc00000); }
-
-// cv::Rect operator& in 64-bit (an empty intersection is Rect())
-__device__ inline void cl_and(long long &x, long long &y, long long &w, long long &h, long long bw, long long bh)
-{
-    const long long x1 = max(x, 0LL), y1 = max(y, 0LL);
-    w = min(x + w, bw) - x1;
-    h = min(y + h, bh) - y1;
-    x = x1; y = y1;
-    if (w <= 0 || h <= 0) x = y = w = h = 0;
-}
 
 // PinholeCameraModel::projectPixelTo3dRay without its z = 1
 __device__ inline void cam_ray(const Pinhole &c, double u, double v, double &rx, double &ry)
@@ -55,11 +43,11 @@ __device__ inline void cam_ray(const Pinhole &c, double u, double v, double &rx,
 __global__ __launch_bounds__(kClThreads) void k_camera_boxes(CameraParams p)
 {
     const int lane = threadIdx.x & 63;
-    const int n = max(min(p.in[0], p.in_cap), 0);
+    const int n = payload_count(p.in, p.in_cap);
     for (int i = blockIdx.x * kClWaves + (threadIdx.x >> 6); i < n; i += gridDim.x * kClWaves) {
         const int32_t *r = p.in + 1 + (size_t)i * p.stride;
-        const long long f = (long long)r[0] - p.frame_offset;
-        const int np = r[6];
+        const long long f = (long long)r[kRecFrame] - p.frame_offset;
+        const int np = r[kRecNparts];
         const double *cube = p.cube + 6 * (size_t)i;
         double *box = p.box + 6 * (size_t)i;
         bool skip = f < 0 || f >= p.nframes || np < 1 || np > p.max_parts;
@@ -83,15 +71,15 @@ __global__ __launch_bounds__(kClThreads) void k_camera_boxes(CameraParams p)
         }
         int dense = 1;
         for (int j = lane; j < np; j += 64) {
-            const int32_t *q = r + 8 + 4 * j;
+            const int32_t *q = record_part(r, j);
             long long x = q[0], y = q[1], w = q[2], h = q[3];
-            cl_and(x, y, w, h, fr.im_cols, fr.im_rows);
+            rect_and64(x, y, w, h, 0, 0, fr.im_cols, fr.im_rows);
             const double u = (double)(x + w / 2), v = (double)(y + h / 2);
             // literal: rows x .. x+h-1, columns y .. y+w-1 (PointCloudClusterer.hpp:111-120); XY: rows y.., columns x..
             const long long r0 = p.mode == kPartsLiteral ? x : y, c0 = p.mode == kPartsLiteral ? y : x;
             float o[3];
             if (w * h != 0 && (r0 + h > fr.rows || c0 + w > fr.cols)) {
-                o[0] = o[1] = o[2] = cl_qnan();          // the reference reads outside the depth image: a project decision
+                o[0] = o[1] = o[2] = qnan_f();          // the reference reads outside the depth image: a project decision
             } else {
                 double s = 0.0;
                 for (long long rr = r0; rr < r0 + h; ++rr) {
@@ -113,13 +101,13 @@ __global__ __launch_bounds__(kClThreads) void k_camera_boxes(CameraParams p)
 }
 
 // ---- clustering ---------------------------------------------------------------------------------------------------------------
-__device__ inline int cl_nbox(const ClusterParams &p) { return max(min(p.in[0], p.in_cap), 0); }
+__device__ inline int cl_nbox(const ClusterParams &p) { return payload_count(p.in, p.in_cap); }
 __device__ inline bool cl_overflow(const ClusterParams &p) { return p.ntab[0] > p.crop_cap; }
 
 // the box's cloud, or -1 (not a box of this call)
 __device__ inline int cl_frame(const ClusterParams &p, int b)
 {
-    const long long f = (long long)p.in[1 + (size_t)b * p.rec_stride] - p.frame_offset;
+    const long long f = (long long)p.in[1 + (size_t)b * p.rec_stride + kRecFrame] - p.frame_offset;
     return (f < 0 || f >= p.nclouds) ? -1 : (int)f;
 }
 
@@ -150,44 +138,6 @@ __device__ inline bool cl_inside(float3 v, const float *mn, const float *mx)
            v.z >= mn[2] && v.z <= mx[2];
 }
 
-// exclusive prefix of v over the workgroup and its total (lds: kClWaves words)
-template <typename T> __device__ inline T cl_block_scan(T v, T *lds, T &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int k = 0; k < kClWaves; ++k) {
-        if (k < w) base += lds[k];
-        tot += lds[k];
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
-}
-
-// the position of a flagged lane among the workgroup's flagged lanes, and their number
-__device__ inline int cl_block_rank(bool flag, int *lds, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) lds[w] = __popcll(m);
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < kClWaves; ++k) {
-        if (k < w) base += lds[k];
-        tot += lds[k];
-    }
-    __syncthreads();
-    total = tot;
-    return base + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 __global__ __launch_bounds__(kClThreads) void k_cl_crop_count(ClusterParams p)
 {
     __shared__ long long lds[kClWaves];
@@ -208,7 +158,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_crop_count(ClusterParams p)
             }
         }
         long long total;
-        cl_block_scan<long long>(cnt, lds, total);
+        block_scan<long long, kClWaves>(cnt, lds, total);
         if (threadIdx.x == 0) p.chunk_off[t] = total;
     }
 }
@@ -230,7 +180,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_crop_scatter(ClusterParams p)
             float3 v = make_float3(0.f, 0.f, 0.f);
             const bool in = idx < npts && cl_inside(v = cl_load(c, (int)idx), mn, mx);
             int tot;
-            const int rk = cl_block_rank(in, lds, tot);
+            const int rk = block_rank<kClWaves>(in, lds, tot);
             if (in && pos + rk < p.crop_cap) {
                 p.crop_idx[pos + rk] = (int)idx;
                 p.crop_box[pos + rk] = b;
@@ -241,83 +191,21 @@ __global__ __launch_bounds__(kClThreads) void k_cl_crop_scatter(ClusterParams p)
     }
 }
 
-// one scan tile's partial sum (n elements: n_dev ? *n_dev : n_host)
-template <typename T> __global__ __launch_bounds__(kClThreads) void k_cl_scan_part(const T *a, long long n_host, const long long *n_dev,
-                                                                              long long *part)
-{
-    __shared__ long long lds[kClWaves];
-    const long long n = n_dev ? *n_dev : n_host;
-    const long long tiles = (n + kClTile - 1) / kClTile;
-    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        long long s = 0;
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kClTile + threadIdx.x * 4 + k;
-            if (e < n) s += a[e];
-        }
-        long long total;
-        cl_block_scan<long long>(s, lds, total);
-        if (threadIdx.x == 0) part[t] = total;
+// thread 0 of the crop scan's top kernel: the total is the cropped point count (ntab[0], status[0]) and sets the bucket count
+// ntab[1]
+struct ClCropTotal {
+    long long *ntab, *status;
+    long long crop_cap;
+    int tcap;
+    __device__ void operator()(long long total) const
+    {
+        ntab[0] = total;
+        status[0] = total;
+        long long T = 1;
+        while (T < 2 * total) T <<= 1;
+        ntab[1] = total > crop_cap ? 0 : min(T, (long long)tcap);
     }
-}
-
-// the exclusive scan of the partials, in place, part[tiles] = the total (one workgroup).  crop: the total is the cropped point count
-// (ntab[0], status[0]) and sets the bucket count ntab[1]
-__global__ __launch_bounds__(kClThreads) void k_cl_scan_top(ClusterParams p, long long n_host, const long long *n_dev, bool crop)
-{
-    __shared__ long long lds[kClWaves];
-    const long long n = n_dev ? *n_dev : n_host;
-    const long long tiles = (n + kClTile - 1) / kClTile;
-    long long carry = 0;
-    for (long long t0 = 0; t0 < tiles; t0 += kClThreads) {
-        const long long t = t0 + threadIdx.x;
-        const long long v = t < tiles ? p.part[t] : 0;
-        long long total;
-        const long long ex = cl_block_scan<long long>(v, lds, total);
-        if (t < tiles) p.part[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        p.part[tiles] = carry;
-        if (crop) {
-            p.ntab[0] = carry;
-            p.status[0] = carry;
-            long long T = 1;
-            while (T < 2 * carry) T <<= 1;
-            p.ntab[1] = carry > p.crop_cap ? 0 : min(T, (long long)p.tcap);
-        }
-    }
-}
-
-// a[e] = exclusive prefix (and copy[e] the same), a[n] = the total
-template <typename T> __global__ __launch_bounds__(kClThreads) void k_cl_scan_add(T *a, T *copy, long long n_host, const long long *n_dev,
-                                                                             const long long *part)
-{
-    __shared__ long long lds[kClWaves];
-    const long long n = n_dev ? *n_dev : n_host;
-    const long long tiles = (n + kClTile - 1) / kClTile;
-    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        long long v[4], s = 0;
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kClTile + threadIdx.x * 4 + k;
-            v[k] = e < n ? (long long)a[e] : 0;
-            s += v[k];
-        }
-        long long total;
-        long long run = part[t] + cl_block_scan<long long>(s, lds, total);
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kClTile + threadIdx.x * 4 + k;
-            if (e < n) {
-                a[e] = (T)run;
-                if (copy) copy[e] = (T)run;
-            }
-            run += v[k];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a[n] = (T)part[tiles];
-        if (copy) copy[n] = (T)part[tiles];
-    }
-}
+};
 
 __device__ inline int cl_cell(float v)
 {
@@ -364,50 +252,6 @@ __global__ __launch_bounds__(kClThreads) void k_cl_grid_scatter(ClusterParams p)
         p.sorted[atomicAdd(&p.bcur[p.bucket[e]], 1)] = (int)e;
 }
 
-// parents are read and shortened with agent-scope relaxed accesses; only the compare-and-swap on a root hooks.  A stale read
-// returns an older ancestor (parent[x] <= x always), which delays nothing but speed
-__device__ inline int cl_ld(int32_t *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void cl_st(int32_t *a, int v) { __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline int cl_find(int32_t *parent, int x)
-{
-    int cur = cl_ld(parent + x);
-    if (cur != x) {
-        int next, prev = x;
-        while (cur > (next = cl_ld(parent + cur))) {
-            cl_st(parent + prev, next);
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
-// the root without shortening the path: k_cl_best writes every point's final root, and a shortening store racing with that
-// write could put back an intermediate ancestor
-__device__ inline int cl_root(const int32_t *parent, int x)
-{
-    int p;
-    while ((p = parent[x]) != x) x = p;
-    return x;
-}
-
-__device__ inline void cl_unite(int32_t *parent, int a, int b)
-{
-    int ra = cl_find(parent, a), rb = cl_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) {
-            const int ret = atomicCAS(parent + rb, rb, ra);
-            if (ret == rb) return;
-            rb = ret;
-        } else {
-            const int ret = atomicCAS(parent + ra, ra, rb);
-            if (ret == ra) return;
-            ra = ret;
-        }
-    }
-}
-
 // the edge predicate: ((dx*dx + dy*dy) + dz*dz) in fp32, every operation rounded, <= 0.01f^2 in double
 __device__ inline bool cl_edge(float4 a, float4 b)
 {
@@ -433,7 +277,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_hook(ClusterParams p)
                     for (int s = p.bstart[bk]; s < s1; ++s) {
                         const int q = p.sorted[s];
                         if (q >= e || p.crop_box[q] != b) continue;
-                        if (cl_edge(v, p.crop_xyz[q])) cl_unite(p.parent, (int)e, q);
+                        if (cl_edge(v, p.crop_xyz[q])) uf_unite(p.parent, (int)e, q);
                     }
                 }
     }
@@ -444,7 +288,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_label(ClusterParams p)
     if (cl_overflow(p)) return;
     const long long m = p.ntab[0];
     for (long long e = blockIdx.x * (long long)kClThreads + threadIdx.x; e < m; e += (long long)gridDim.x * kClThreads) {
-        const int root = cl_find(p.parent, (int)e);
+        const int root = uf_find(p.parent, (int)e);
         atomicAdd(&p.csize[root], 1);
     }
 }
@@ -454,7 +298,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_best(ClusterParams p)
     if (cl_overflow(p)) return;
     const long long m = p.ntab[0];
     for (long long e = blockIdx.x * (long long)kClThreads + threadIdx.x; e < m; e += (long long)gridDim.x * kClThreads) {
-        const int root = cl_root(p.parent, (int)e);
+        const int root = uf_root(p.parent, (int)e);
         p.parent[e] = root;                             // every label final for k_cl_out
         if (root == e)
             atomicMax(&p.best[p.crop_box[e]], ((unsigned long long)(uint32_t)p.csize[e] << 32) | (0xffffffffu - (uint32_t)e));
@@ -472,7 +316,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_select(ClusterParams p)
         const int b = b0 + threadIdx.x;
         const long long cnt = (b < n && !ovf) ? (long long)(p.best[b] >> 32) : 0;
         long long total;
-        const long long ex = cl_block_scan<long long>(cnt, lds, total);
+        const long long ex = block_scan<long long, kClWaves>(cnt, lds, total);
         if (b < n) {
             p.obase[b] = carry + ex;
             p.counts[b] = (int32_t)cnt;
@@ -496,7 +340,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_out(ClusterParams p)
         const long long cnt = ovf ? 0 : (long long)(p.best[b] >> 32);
         float *cen = p.centres + 3 * (size_t)b;
         if (cnt == 0) {
-            if (threadIdx.x < 3) cen[threadIdx.x] = cl_qnan();
+            if (threadIdx.x < 3) cen[threadIdx.x] = qnan_f();
             continue;
         }
         const int winner = (int)(0xffffffffu - (uint32_t)p.best[b]);
@@ -507,7 +351,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl_out(ClusterParams p)
             const long long e = s + threadIdx.x;
             const bool in = e < e1 && p.parent[e] == winner;
             int tot;
-            const int rk = cl_block_rank(in, lds, tot);
+            const int rk = block_rank<kClWaves>(in, lds, tot);
             if (in) {
                 if (write) p.indices[o + rk] = p.crop_idx[e];
                 stage[rk] = p.crop_xyz[e];
@@ -548,21 +392,15 @@ void launch_cluster_step(const ClusterParams &p, int step, hipStream_t s)
     switch (step) {
     case kClStepCropCount: PBD_LAUNCH(k_cl_crop_count, dim3(cl_grid(units, 1)), blk, 0, s, p); break;
     case kClStepCropScan:
-        PBD_LAUNCH(k_cl_scan_part<long long>, dim3(cl_grid(units, kClTile)), blk, 0, s, (const long long *)p.chunk_off, 0LL,
-                   (const long long *)(p.ntab + 2), p.part);
-        PBD_LAUNCH(k_cl_scan_top, dim3(1), blk, 0, s, p, 0LL, (const long long *)(p.ntab + 2), true);
-        PBD_LAUNCH(k_cl_scan_add<long long>, dim3(cl_grid(units, kClTile)), blk, 0, s, p.chunk_off, (long long *)nullptr, 0LL,
-                   (const long long *)(p.ntab + 2), (const long long *)p.part);
+        launch_scan<long long>(p.chunk_off, (long long *)nullptr, 0LL, (const long long *)(p.ntab + 2), p.part,
+                               cl_grid(units, kScanTile), ClCropTotal{p.ntab, p.status, p.crop_cap, p.tcap}, s);
         break;
     case kClStepCropScatter: PBD_LAUNCH(k_cl_crop_scatter, dim3(cl_grid(units, 1)), blk, 0, s, p); break;
     case kClStepClear: PBD_LAUNCH(k_cl_clear, dim3(cl_grid(std::max<long long>(p.tcap, p.in_cap) + 1)), blk, 0, s, p); break;
     case kClStepGridCount: PBD_LAUNCH(k_cl_grid_count, dim3(cl_grid(p.crop_cap)), blk, 0, s, p); break;
     case kClStepGridScan:
-        PBD_LAUNCH(k_cl_scan_part<int32_t>, dim3(cl_grid(p.tcap, kClTile)), blk, 0, s, (const int32_t *)p.bstart, 0LL,
-                   (const long long *)(p.ntab + 1), p.part);
-        PBD_LAUNCH(k_cl_scan_top, dim3(1), blk, 0, s, p, 0LL, (const long long *)(p.ntab + 1), false);
-        PBD_LAUNCH(k_cl_scan_add<int32_t>, dim3(cl_grid(p.tcap, kClTile)), blk, 0, s, p.bstart, p.bcur, 0LL,
-                   (const long long *)(p.ntab + 1), (const long long *)p.part);
+        launch_scan<long long>(p.bstart, p.bcur, 0LL, (const long long *)(p.ntab + 1), p.part, cl_grid(p.tcap, kScanTile),
+                               ScanNoTop{}, s);
         break;
     case kClStepGridScatter: PBD_LAUNCH(k_cl_grid_scatter, dim3(cl_grid(p.crop_cap)), blk, 0, s, p); break;
     case kClStepHook: PBD_LAUNCH(k_cl_hook, dim3(cl_grid(p.crop_cap)), blk, 0, s, p); break;

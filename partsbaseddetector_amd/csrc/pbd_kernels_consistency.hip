@@ -7,7 +7,7 @@
 //                   the others go to their size class's segment of one work list (a counting pass, then a placing pass)
 //   k_dc_select     per size class, an exact radix select of the element at rank M / 2 over order-preserving integer keys (8,
 //                   16, 32 or 64 bits by depth code and T), one 8-bit digit per pass, 256 LDS counters updated once per distinct
-//                   digit of a wave (wave-aggregated):
+//                   digit of a wave (wave_add_by_key, pbd_device.h):
 //                     M <= 1024   one wave per median, the keys loaded once into registers (16 per lane)
 //                     M <= 4096   one 256-thread workgroup per median, the keys in registers
 //                     larger      one 1024-thread workgroup per median, every pass reading the box of the depth image in place
@@ -15,7 +15,7 @@
 //   k_dc_emit       the kept records, byte for byte, in input order (a stable compaction) into the output payload
 // No host synchronisation; the workspace grows with the records (a median and a work-list entry per part), never with the
 // samples, and the depth images are read where the caller put them.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 
 #include <algorithm>
 
@@ -23,6 +23,7 @@ namespace pbd {
 namespace {
 
 constexpr int kDcThreads = 256;       // classify / decide / emit; also the register class of up to kDcBlockKeys
+constexpr int kDcWaves = kDcThreads / 64;
 constexpr int kDcKeysPerThread = 16;
 constexpr int kDcStreamThreads = 1024;
 static_assert(kDcWaveKeys == 64 * kDcKeysPerThread && kDcBlockKeys == kDcThreads * kDcKeysPerThread, "size classes");
@@ -41,24 +42,18 @@ template <int D, bool F64> __device__ inline unsigned long long dc_key(const uin
     if (D == kDepth16U) return reinterpret_cast<const uint16_t *>(row)[x];
     if (D == kDepth64F && F64) {
         double v = reinterpret_cast<const double *>(row)[x];
-        v = v != v ? 0.0 : __dadd_rn(v, 0.0);
-        const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+        return double_key(v != v ? 0.0 : __dadd_rn(v, 0.0));
     }
     float v = D == kDepth32F ? reinterpret_cast<const float *>(row)[x] : (float)reinterpret_cast<const double *>(row)[x];
-    v = v != v ? 0.f : __fadd_rn(v, 0.f);
-    const uint32_t b = __float_as_uint(v);
-    return (b >> 31) ? (uint32_t)~b : (b | 0x80000000u);
+    return float_key(v != v ? 0.f : __fadd_rn(v, 0.f));
 }
 
 // the median as a double (exact for every T)
 template <int D, bool F64> __device__ inline double dc_unkey(unsigned long long k)
 {
     if (D == kDepth8U || D == kDepth16U) return (double)k;
-    if (D == kDepth64F && F64)
-        return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-    const uint32_t u = (uint32_t)k;
-    return (double)__uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u);
+    if (D == kDepth64F && F64) return double_unkey(k);
+    return (double)float_unkey((uint32_t)k);
 }
 
 __device__ inline bool dc_overflow(const DcParams &p) { return p.in[0] < 0 || p.in[0] > p.in_cap; }
@@ -67,10 +62,10 @@ __device__ inline int dc_count(const DcParams &p) { return dc_overflow(p) ? 0 : 
 // a record of this call: frame index in range, a known component, nparts its component's part count (1..max parts)
 __device__ inline bool dc_record(const DcParams &p, const int32_t *r, int *frame, int *p0, int *np)
 {
-    const long long f = (long long)r[0] - p.frame_offset;
-    const int c = r[1];
+    const long long f = (long long)r[kRecFrame] - p.frame_offset;
+    const int c = r[kRecComponent];
     if (f < 0 || f >= p.nframes || c < 0 || c >= p.NC) return false;
-    const int n = r[6];
+    const int n = r[kRecNparts];
     if (n < 1 || n > p.max_parts || n != p.part_offset[c + 1] - p.part_offset[c]) return false;
     *frame = (int)f; *p0 = p.part_offset[c]; *np = n;
     return true;
@@ -79,7 +74,8 @@ __device__ inline bool dc_record(const DcParams &p, const int32_t *r, int *frame
 // part j of record r clipped to the depth image (cv::Rect operator& in 64 bits): x, y, w, h
 __device__ inline int4 dc_box(const int32_t *r, int j, const Box3dFrame &fr)
 {
-    long long x = r[8 + 4 * j], y = r[9 + 4 * j], w = r[10 + 4 * j], h = r[11 + 4 * j];
+    const int32_t *q = record_part(r, j);
+    long long x = q[0], y = q[1], w = q[2], h = q[3];
     rect_and64(x, y, w, h, 0, 0, fr.cols, fr.rows);
     return make_int4((int)x, (int)y, (int)w, (int)h);
 }
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(kDcThreads) void k_dc_classify(DcParams p)
             if (dc_record(p, r, &f, &p0, &np) && np >= 2 && j < np) {   // else no median is read (a one-part component keeps)
                 const int4 b = dc_box(r, j, p.frames[f]);
                 const long long M = (long long)b.z * b.w;
-                if (M == 0) { if (!kPlace) p.med[t] = __longlong_as_double(0x7ff8000000000000LL); }   // no median
+                if (M == 0) { if (!kPlace) p.med[t] = qnan_d(); }   // no median
                 else cls = M <= kDcWaveKeys ? 0 : M <= kDcBlockKeys ? 1 : 2;
             }
         }
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(kDcThreads) void k_dc_classify(DcParams p)
             int base = 0;
             if (lane == leader) base = atomicAdd(&p.qn[3 + k], __popcll(m));
             base = __shfl(base, leader, 64);
-            if (cls == k) p.queue[dc_seg(p, k) + base + __popcll(m & ((1ull << lane) - 1))] = (int)t;
+            if (cls == k) p.queue[dc_seg(p, k) + base + lane_rank(m)] = (int)t;
         }
     }
 }
@@ -129,19 +125,6 @@ struct DcSelShared {
     uint32_t hist[256];
     unsigned int digit, rem;
 };
-
-// one wave's contribution of `slot` (a bin, or -1) to the histogram: one LDS atomic per distinct bin of the wave
-__device__ inline void dc_hist_add(uint32_t *hist, int slot)
-{
-    unsigned long long active = __ballot(slot >= 0);
-    while (active) {
-        const int leader = __ffsll((long long)active) - 1;
-        const int t = __shfl(slot, leader, 64);
-        const unsigned long long same = __ballot(slot == t);
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[t], (uint32_t)__popcll(same));
-        active &= ~same;
-    }
-}
 
 // the key at rank `rank` of the keys `each` visits (each(fn) calls fn(key, valid) the same number of times in every lane of a
 // wave): KBITS / 8 passes, the bits above the pass's digit fixed by the passes before
@@ -157,17 +140,13 @@ __device__ unsigned long long dc_select(DcSelShared &S, unsigned int rank, Each 
         const int hs = shift + 8;
         each([&](unsigned long long k, bool valid) {
             const bool match = valid && (hs >= KBITS || (k >> hs) == (prefix >> hs));
-            dc_hist_add(S.hist, match ? (int)((k >> shift) & 255) : -1);
+            wave_add_by_key(S.hist, (int)((k >> shift) & 255), match);
         });
         __syncthreads();
         if (tid < 64) {   // wave 0: the bin in which the remaining rank falls (4 bins per lane, a wave prefix sum)
             const uint32_t c0 = S.hist[4 * lane], c1 = S.hist[4 * lane + 1], c2 = S.hist[4 * lane + 2], c3 = S.hist[4 * lane + 3];
             const unsigned int s = c0 + c1 + c2 + c3;
-            unsigned int incl = s;
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned int v = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += v;
-            }
+            const unsigned int incl = wave_incl_scan(s);
             const unsigned int excl = incl - s;
             if (excl <= rem && rem < incl) {
                 unsigned int r = rem - excl;
@@ -197,7 +176,7 @@ __global__ __launch_bounds__(NT) void k_dc_select_regs(DcParams p, int cls)
         const int t = p.queue[dc_seg(p, cls) + q];
         const int i = t / p.max_parts, j = t - i * p.max_parts;
         const int32_t *r = p.in + 1 + (size_t)i * p.stride;
-        const Box3dFrame fr = p.frames[r[0] - p.frame_offset];
+        const Box3dFrame fr = p.frames[r[kRecFrame] - p.frame_offset];
         const int4 b = dc_box(r, j, fr);
         const int M = b.z * b.w;
         unsigned long long key[kDcKeysPerThread];
@@ -230,7 +209,7 @@ __global__ __launch_bounds__(kDcStreamThreads) void k_dc_select_stream(DcParams 
         const int t = p.queue[dc_seg(p, 2) + q];
         const int i = t / p.max_parts, j = t - i * p.max_parts;
         const int32_t *r = p.in + 1 + (size_t)i * p.stride;
-        const Box3dFrame fr = p.frames[r[0] - p.frame_offset];
+        const Box3dFrame fr = p.frames[r[kRecFrame] - p.frame_offset];
         const int4 b = dc_box(r, j, fr);
         const long long M = (long long)b.z * b.w;
         const unsigned long long m = dc_select<kDcStreamThreads, KB>(S, (unsigned int)(M / 2), [&](auto fn) {
@@ -256,7 +235,7 @@ template <bool F64> __device__ inline double dc_absdiff(double a, double b)
 template <bool F64>
 __global__ __launch_bounds__(kDcThreads) void k_dc_decide(DcParams p)
 {
-    __shared__ int partial[kDcThreads / 64];
+    __shared__ int partial[kDcWaves];
     const int i = blockIdx.x * kDcThreads + threadIdx.x;
     const int n = dc_count(p);
     int keep = 0;
@@ -278,21 +257,14 @@ __global__ __launch_bounds__(kDcThreads) void k_dc_decide(DcParams p)
         }
     }
     p.flag[i] = keep;   // [blocks * kDcThreads]
-    int s = keep;
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < kDcThreads / 64; ++w) tot += partial[w];
-        p.blk[blockIdx.x] = tot;
-    }
+    const int tot = block_sum<kDcWaves, int>(keep, partial);
+    if (threadIdx.x == 0) p.blk[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(kDcThreads) void k_dc_emit(DcParams p)
 {
     __shared__ int dest[kDcThreads];
-    __shared__ int wsum[kDcThreads / 64], wtot[kDcThreads / 64];
+    __shared__ int wsum[kDcWaves], wtot[kDcWaves];
     __shared__ int base_s, total_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (dc_overflow(p)) {   // a suppression overflow or a truncated list: no complete list to filter
@@ -306,35 +278,23 @@ __global__ __launch_bounds__(kDcThreads) void k_dc_emit(DcParams p)
         total += c;
         before += b < (int)blockIdx.x ? c : 0;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        before += __shfl_xor(before, off, 64);
-        total += __shfl_xor(total, off, 64);
-    }
+    before = wave_sum(before);
+    total = wave_sum(total);
     if (lane == 0) { wsum[wave] = before; wtot[wave] = total; }
     __syncthreads();
     if (tid == 0) {
         int s = 0, t = 0;
-        for (int w = 0; w < kDcThreads / 64; ++w) { s += wsum[w]; t += wtot[w]; }
+        for (int w = 0; w < kDcWaves; ++w) { s += wsum[w]; t += wtot[w]; }
         base_s = s;
         total_s = t;
     }
-    __syncthreads();
+    __syncthreads();   // also ends tid 0's reads of wsum: the scan below writes it
     total = total_s;
     const int i = blockIdx.x * kDcThreads + tid;
     const int n = dc_count(p);
     const int keep = i < n ? p.flag[i] : 0;
-    // inclusive scan of keep over the block
-    int incl = keep;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int wbase = 0;
-    for (int w = 0; w < wave; ++w) wbase += wsum[w];
-    const int pos = base_s + wbase + incl - keep;
+    int nkeep;
+    const int pos = base_s + block_scan<int, kDcWaves>(keep, wsum, nkeep);
     dest[tid] = keep && pos < p.out_cap ? pos : -1;
     if (blockIdx.x == 0 && tid == 0) p.out[0] = total;
     __syncthreads();

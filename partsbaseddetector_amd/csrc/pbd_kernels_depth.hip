@@ -4,7 +4,7 @@
 //
 // One kernel, k_boxes3d, one workgroup per record (grid-stride over the records):
 //   geometry   the nparts + 1 boxes: parts & frame, boundingBoxNorm() & frame (Candidate.hpp:117-130), scaled to the depth image
-//   select     the values at the <= 800 ranks the resample reads, by an exact radix select over order-preserving uint32 keys of
+//   select     the values at the <= 800 ranks the resample reads, by an exact radix select over order-preserving uint32 keys (float_key) of
 //              the valid samples, 4 bits per pass, 8 passes, every pass reading the boxes of the depth image in place.  Pass 0
 //              also counts the samples (M) and the valid samples of the first non-empty box (the reference's early NaN box).
 //              Histograms live in LDS, one row of 16 counters per needed rank (ranks that share a key prefix share a row)
@@ -13,7 +13,7 @@
 //   walk       from the median out, until |d| > 0.035 (:197-205)
 // Nothing is gathered: no workspace grows with the number of samples, and a record of any size runs the same code.
 // Every float / double multiply and add is written with an explicitly rounded intrinsic, so none of them is contracted.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 
 #include <math.h>
 
@@ -27,14 +27,6 @@ constexpr int kB3Waves = kB3Threads / 64;
 constexpr int kB3Out = 400;                  // cv::Size(1, 400) (Candidate.hpp:186)
 constexpr int kB3MaxRanks = 2 * kB3Out;      // r0 and r1 of every output row
 constexpr int kB3Bits = 4, kB3Bins = 1 << kB3Bits, kB3Passes = 32 / kB3Bits;
-
-// order-preserving key of a float that is neither NaN nor 0 (flip all bits of a negative value, the sign bit of a positive one)
-__device__ inline uint32_t b3_key(float v)
-{
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ inline float b3_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // Mat_<float> assignment of one depth sample (8U / 16U exact, 64F rounded to nearest, 32F as is)
 template <int D> __device__ inline float b3_load(const uint8_t *row, int x)
@@ -62,21 +54,10 @@ struct B3Shared {
 };
 static_assert(sizeof(B3Shared) <= 65536, "the select's LDS fits one workgroup's static limit");
 
-// first index in rank-ordered pre[0, K) whose prefix is >= v
-__device__ inline int b3_lower(const uint32_t *pre, int K, uint32_t v)
-{
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (pre[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // one pass over every box: the digit at `shift` of every valid sample whose key prefix (the bits above `shift + 4`) is a needed
 // rank's prefix is counted in that prefix's row.  Pass 0 (all prefixes empty: one row) also counts M and the samples of box 0, the
 // first non-empty box.
-// Lanes of a wave that hit one counter add once (wave-aggregated LDS atomics: neighbouring depth samples mostly share a digit).
+// Lanes of a wave that hit one counter add once (wave_add_by_key: neighbouring depth samples mostly share a digit).
 template <int D>
 __device__ void b3_pass(B3Shared &S, const Box3dFrame &fr, int shift, bool first_pass)
 {
@@ -93,8 +74,8 @@ __device__ void b3_pass(B3Shared &S, const Box3dFrame &fr, int shift, bool first
                 int slot = -1;
                 if (x < r.z) {
                     const float v = b3_load<D>(row, r.x + x);
-                    if (v != 0.f && !(v != v)) {
-                        const uint32_t k = b3_key(v);
+                    if (v != 0.f && !(v != v)) {       // the valid samples: neither 0 nor NaN, which float_key asks for
+                        const uint32_t k = float_key(v);
                         const uint32_t kp = (uint32_t)((unsigned long long)k >> (shift + kB3Bits));
                         const int digit = (int)((k >> shift) & (kB3Bins - 1));
                         if (first_pass) {
@@ -102,27 +83,18 @@ __device__ void b3_pass(B3Shared &S, const Box3dFrame &fr, int shift, bool first
                             if (b == 0) ++nfirst;
                             slot = digit;
                         } else if (kp >= lo_pre && kp <= hi_pre) {
-                            const int i = b3_lower(S.pre, K, kp);
+                            const int i = lower_bound_i32(S.pre, K, kp);
                             if (i < K && S.pre[i] == kp) slot = i * kB3Bins + digit;
                         }
                     }
                 }
-                unsigned long long active = __ballot(slot >= 0);
-                while (active) {
-                    const int leader = __ffsll((long long)active) - 1;
-                    const int t = __shfl(slot, leader, 64);
-                    const unsigned long long same = __ballot(slot == t);
-                    if (lane == leader) atomicAdd(&S.hist[t], (uint32_t)__popcll(same));
-                    active &= ~same;
-                }
+                wave_add_by_key(S.hist, slot, slot >= 0);
             }
         }
     }
     if (first_pass) {
-        for (int off = 32; off > 0; off >>= 1) {
-            nvalid += __shfl_xor(nvalid, off, 64);
-            nfirst += __shfl_xor(nfirst, off, 64);
-        }
+        nvalid = wave_sum(nvalid);
+        nfirst = wave_sum(nfirst);
         if (lane == 0) {
             atomicAdd(&S.M, nvalid);
             atomicAdd(&S.first_valid, nfirst);
@@ -139,28 +111,18 @@ __device__ inline float b3_fy(int dy, double scale, int *sy)
     return __fsub_rn(fy, (float)s);
 }
 
-__device__ inline int b3_find(const int *rank, int K, int r)
-{
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (rank[mid] < r) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 template <int D>
 __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
 {
     __shared__ B3Shared S;
     const int tid = threadIdx.x;
-    const int n = max(min(p.in[0], p.in_cap), 0);
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const int n = payload_count(p.in, p.in_cap);
+    const double qnan = qnan_d();
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int32_t *r = p.in + 1 + (size_t)i * p.stride;
         double *out = p.out + 6 * (size_t)i;
-        const long long f = (long long)r[0] - p.frame_offset;
-        const int np = r[6];
+        const long long f = (long long)r[kRecFrame] - p.frame_offset;
+        const int np = r[kRecNparts];
         if (f < 0 || f >= p.nframes || np < 1 || np > p.max_parts) {   // not a record of this call: six NaNs
             if (tid < 6) out[tid] = qnan;
             continue;
@@ -173,7 +135,7 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
             // boundingBoxNorm: centroid = cvRound((tl + br) * 0.5) (half to even), cv::meanStdDev in double
             double s[2] = {0, 0}, sq[2] = {0, 0};
             for (int k = 0; k < np; ++k) {
-                const int *q = r + 8 + 4 * k;
+                const int32_t *q = record_part(r, k);
                 const double cx = rint((double)(2LL * q[0] + q[2]) * 0.5), cy = rint((double)(2LL * q[1] + q[3]) * 0.5);
                 s[0] = __dadd_rn(s[0], cx); sq[0] = __dadd_rn(sq[0], __dmul_rn(cx, cx));
                 s[1] = __dadd_rn(s[1], cy); sq[1] = __dadd_rn(sq[1], __dmul_rn(cy, cy));
@@ -188,7 +150,8 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
             for (int k = 0; k <= np; ++k) {
                 long long x, y, w, h;
                 if (k < np) {
-                    x = r[8 + 4 * k]; y = r[9 + 4 * k]; w = r[10 + 4 * k]; h = r[11 + 4 * k];
+                    const int32_t *q = record_part(r, k);
+                    x = q[0]; y = q[1]; w = q[2]; h = q[3];
                 } else {   // Rect(xmean - 1.5 xstd, ymean - 1.5 ystd, 3 xstd, 3 ystd): double -> int truncates
                     x = (int)__dsub_rn(mean[0], __dmul_rn(1.5, sd[0])); y = (int)__dsub_rn(mean[1], __dmul_rn(1.5, sd[1]));
                     w = (int)__dmul_rn(3., sd[0]); h = (int)__dmul_rn(3., sd[1]);
@@ -251,7 +214,7 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
             }
             uint32_t npre = 0; int nres = 0;
             if (tid < K) {
-                const int row = pass == 0 ? 0 : b3_lower(S.pre, K, S.pre[tid]);
+                const int row = pass == 0 ? 0 : lower_bound_i32(S.pre, K, S.pre[tid]);
                 int res = S.resid[tid], dg = 0;
                 for (; dg < kB3Bins - 1; ++dg) {
                     const int c = (int)S.hist[row * kB3Bins + dg];
@@ -269,13 +232,13 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
         if (tid < kB3Out) {
             float v;
             if (M == kB3Out) {
-                v = b3_unkey(S.pre[tid]);
+                v = float_unkey(S.pre[tid]);
             } else {
                 int sy;
                 const float fy = b3_fy(tid, scale, &sy);
                 const int last = (int)M - 1;
-                const float s0 = b3_unkey(S.pre[b3_find(S.rank, K, min(max(sy, 0), last))]);
-                const float s1 = b3_unkey(S.pre[b3_find(S.rank, K, min(max(sy + 1, 0), last))]);
+                const float s0 = float_unkey(S.pre[lower_bound_i32(S.rank, K, min(max(sy, 0), last))]);
+                const float s1 = float_unkey(S.pre[lower_bound_i32(S.rank, K, min(max(sy + 1, 0), last))]);
                 v = __fadd_rn(__fmul_rn(s0, __fsub_rn(1.f, fy)), __fmul_rn(s1, fy));
             }
             S.p[tid] = v;
@@ -300,18 +263,8 @@ __global__ __launch_bounds__(kB3Threads) void k_boxes3d(Boxes3dParams p)
             for (int m = mid; m < kB3Out; ++m) { if ((double)fabsf(S.d[m]) > 0.035) break; dmax = m; }
             for (int m = mid; m >= 0; --m) { if ((double)fabsf(S.d[m]) > 0.035) break; dmin = m; }
             // Rect3d(tl, br) with bb = boundingBox(), the unclipped hull (Candidate.hpp:105-111), in member order
-            long long x = 0, y = 0, w = 0, h = 0;
-            for (int k = 0; k < np; ++k) {
-                const long long bx = r[8 + 4 * k], by = r[9 + 4 * k], bw = r[10 + 4 * k], bh = r[11 + 4 * k];
-                if (w <= 0 || h <= 0) {
-                    x = bx; y = by; w = bw; h = bh;
-                } else if (bw > 0 && bh > 0) {
-                    const long long x1 = min(x, bx), y1 = min(y, by);
-                    w = max(x + w, bx + bw) - x1;
-                    h = max(y + h, by + bh) - y1;
-                    x = x1; y = y1;
-                }
-            }
+            long long x, y, w, h;
+            record_hull64(r, np, x, y, w, h);
             const double z0 = (double)S.p[dmin], z1 = (double)S.p[dmax];
             out[0] = (double)(int)x; out[1] = (double)(int)y; out[2] = z0;
             out[3] = (double)(int)h; out[4] = (double)(int)w; out[5] = __dsub_rn(z1, z0);

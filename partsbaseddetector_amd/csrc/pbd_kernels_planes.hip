@@ -6,9 +6,9 @@
 // cloud table.  One fixed sequence of launches, each a grid-stride loop (no host loop, nothing read back):
 //   normals    k_pl_load (the points, union-find roots), k_pl_rowsums (per pixel: the row window's gradient sums, left to right,
 //              and whether the row window holds a depth edge), k_pl_normals (the 2s+1 row sums top to bottom, the normal, d)
-//   segments   k_pl_hook: union-find over the left / upper comparator edges (lock-free hooking of the larger root under the
-//              smaller, agent-scope atomics, as k_cl_hook), k_pl_size: component sizes; k_pl_cand: final roots and the flags of
-//              the segments above min_inliers; an exclusive scan; k_pl_cand_list: the candidates in point order
+//   segments   k_pl_hook: union-find over the left / upper comparator edges (uf_unite, pbd_device.h, as k_cl_hook), k_pl_size:
+//              component sizes, one atomic per distinct root of a wave; k_pl_cand: final roots and the flags of the segments
+//              above min_inliers; an exclusive scan (launch_scan, pbd_device.h); k_pl_cand_list: the candidates in point order
 //   planes     k_pl_moments: one workgroup per candidate, one wave per image row: the row's nine double moments, left to right
 //              (ballot, then an ordered walk of the matching lanes through readlane), the row partials top to bottom, then the
 //              Jacobi eigenpair (jacobi3, pbd_jacobi.h);
@@ -19,7 +19,7 @@
 //   output     k_pl_final (output labels, inlier counts, kept flags), an exclusive scan, k_pl_kept (the kept points and their
 //              indices in order, then the NaN fill), k_pl_out (counts, plane records, status)
 // Every float / double operation whose bits are compared is an explicitly rounded intrinsic, so none of them is contracted.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 #include "pbd_jacobi.h"
 
 #include <math.h>
@@ -30,15 +30,13 @@ namespace pbd {
 namespace {
 
 constexpr int kPlThreads = 256;
-constexpr int kPlWaves = kPlThreads / 64;
-constexpr int kPlTile = 4 * kPlThreads;          // elements of one scan tile
+static_assert(kPlThreads == kScanThreads, "the scans of the flags run at the stage's workgroup size");
 constexpr int kPlMaxGrid = 4096;
 constexpr int kMoThreads = 1024;                 // k_pl_moments: 16 waves, one image row each at a time
 constexpr int kMoWaves = kMoThreads / 64;
 constexpr int kMoRows = 128;                     // row partials staged in LDS per round
 constexpr int kRefThreads = 1024;                // k_pl_refine: one workgroup per cloud
 
-__device__ inline float pl_qnan() { return __int_as_float(0x7fc00000); }
 __device__ inline bool pl_finite(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 
 // the cloud of a point of the concatenation (clouds[nclouds].base = npts)
@@ -60,19 +58,6 @@ __device__ inline float pl_dot3(float ax, float ay, float az, float bx, float by
 // the depth-dependent threshold t * (z * z)
 __device__ inline float pl_thr(float t, float z) { return __fmul_rn(t, __fmul_rn(z, z)); }
 
-// cnt[key] += 1 for every active lane with `on`: one atomic per distinct key of the wave (a plane's points share one counter)
-__device__ inline void pl_count(int32_t *cnt, int key, bool on)
-{
-    unsigned long long pending = __ballot(on);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int lk = __shfl(key, leader, 64);
-        const unsigned long long same = __ballot(on && key == lk) & pending;
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(cnt + lk, __popcll(same));
-        pending &= ~same;
-    }
-}
-
 // a lane's double, read by the whole wave (the lane index is wave-uniform)
 __device__ inline double pl_readlane(double v, int lane)
 {
@@ -80,27 +65,6 @@ __device__ inline double pl_readlane(double v, int lane)
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// exclusive prefix of v over the workgroup and its total (lds: kPlWaves words)
-__device__ inline int pl_block_scan(int v, int *lds, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int k = 0; k < kPlWaves; ++k) {
-        if (k < w) base += lds[k];
-        tot += lds[k];
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
 }
 
 __global__ __launch_bounds__(kPlThreads) void k_pl_load(PlaneParams p)
@@ -170,7 +134,7 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_normals(PlaneParams p)
         const int W = c.cols, H = c.rows;
         const int r = (int)(j / W), cc = (int)(j - (long long)r * W);
         const float4 v = p.xyz[e];
-        float4 out = make_float4(pl_qnan(), pl_qnan(), pl_qnan(), pl_qnan());
+        float4 out = make_float4(qnan_f(), qnan_f(), qnan_f(), qnan_f());
         if (r >= s + 1 && r <= H - s - 2 && cc >= s + 1 && cc <= W - s - 2) {
             float sx = 0.f, sy = 0.f, sz = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
             bool edge = false;
@@ -198,48 +162,6 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_normals(PlaneParams p)
     }
 }
 
-// union-find as k_cl_hook (pbd_kernels_cloud.hip): relaxed agent-scope reads and shortening stores, CAS hooks the larger root
-// under the smaller, so a root is the smallest point of its component
-__device__ inline int pl_ld(int32_t *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void pl_st(int32_t *a, int v) { __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline int pl_find(int32_t *parent, int x)
-{
-    int cur = pl_ld(parent + x);
-    if (cur != x) {
-        int next, prev = x;
-        while (cur > (next = pl_ld(parent + cur))) {
-            pl_st(parent + prev, next);
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
-__device__ inline int pl_root(const int32_t *parent, int x)
-{
-    int q;
-    while ((q = parent[x]) != x) x = q;
-    return x;
-}
-
-__device__ inline void pl_unite(int32_t *parent, int a, int b)
-{
-    int ra = pl_find(parent, a), rb = pl_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) {
-            const int ret = atomicCAS(parent + rb, rb, ra);
-            if (ret == rb) return;
-            rb = ret;
-        } else {
-            const int ret = atomicCAS(parent + ra, ra, rb);
-            if (ret == ra) return;
-            ra = ret;
-        }
-    }
-}
-
 // PlaneCoefficientComparator, depth dependent, z of the current point p; a NaN normal fails both tests
 __device__ inline bool pl_join(const PlaneParams &p, float4 vp, float4 np_, float4 vq, float4 nq)
 {
@@ -258,80 +180,25 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_hook(PlaneParams p)
         const int W = c.cols;
         const int r = (int)(j / W), cc = (int)(j - (long long)r * W);
         const float4 n = p.nrm[e];
-        if (cc >= 1 && pl_join(p, v, n, p.xyz[e - 1], p.nrm[e - 1])) pl_unite(p.parent, (int)e, (int)(e - 1));
-        if (r >= 1 && pl_join(p, v, n, p.xyz[e - W], p.nrm[e - W])) pl_unite(p.parent, (int)e, (int)(e - W));
+        if (cc >= 1 && pl_join(p, v, n, p.xyz[e - 1], p.nrm[e - 1])) uf_unite(p.parent, (int)e, (int)(e - 1));
+        if (r >= 1 && pl_join(p, v, n, p.xyz[e - W], p.nrm[e - W])) uf_unite(p.parent, (int)e, (int)(e - W));
     }
 }
 
 __global__ __launch_bounds__(kPlThreads) void k_pl_size(PlaneParams p)
 {
     for (long long e = blockIdx.x * (long long)kPlThreads + threadIdx.x; e < p.npts; e += (long long)gridDim.x * kPlThreads)
-        pl_count(p.csize, pl_find(p.parent, (int)e), true);
+        wave_add_by_key(p.csize, uf_find(p.parent, (int)e), true);
 }
 
 // every point's final root; flag = a root of a finite segment with more than min_inliers points
 __global__ __launch_bounds__(kPlThreads) void k_pl_cand(PlaneParams p)
 {
     for (long long e = blockIdx.x * (long long)kPlThreads + threadIdx.x; e < p.npts; e += (long long)gridDim.x * kPlThreads) {
-        const int root = pl_root(p.parent, (int)e);
+        const int root = uf_root(p.parent, (int)e);
         p.parent[e] = root;
         p.flag[e] = (root == e && pl_finite(p.xyz[e]) && p.csize[e] > p.min_inliers) ? 1 : 0;
     }
-}
-
-// exclusive scan of flag[0 .. npts) in place, flag[npts] = the total: tile sums, their scan (one workgroup), the tiles
-__global__ __launch_bounds__(kPlThreads) void k_pl_scan_part(PlaneParams p)
-{
-    __shared__ int lds[kPlWaves];
-    const long long tiles = (p.npts + kPlTile - 1) / kPlTile;
-    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        int s = 0;
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kPlTile + threadIdx.x * 4 + k;
-            if (e < p.npts) s += p.flag[e];
-        }
-        int total;
-        pl_block_scan(s, lds, total);
-        if (threadIdx.x == 0) p.part[t] = total;
-    }
-}
-
-__global__ __launch_bounds__(kPlThreads) void k_pl_scan_top(PlaneParams p)
-{
-    __shared__ int lds[kPlWaves];
-    const long long tiles = (p.npts + kPlTile - 1) / kPlTile;
-    long long carry = 0;
-    for (long long t0 = 0; t0 < tiles; t0 += kPlThreads) {
-        const long long t = t0 + threadIdx.x;
-        const int v = t < tiles ? (int)p.part[t] : 0;
-        int total;
-        const int ex = pl_block_scan(v, lds, total);
-        if (t < tiles) p.part[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) p.part[tiles] = carry;
-}
-
-__global__ __launch_bounds__(kPlThreads) void k_pl_scan_add(PlaneParams p)
-{
-    __shared__ int lds[kPlWaves];
-    const long long tiles = (p.npts + kPlTile - 1) / kPlTile;
-    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        int v[4], s = 0;
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kPlTile + threadIdx.x * 4 + k;
-            v[k] = e < p.npts ? p.flag[e] : 0;
-            s += v[k];
-        }
-        int total;
-        int run = (int)p.part[t] + pl_block_scan(s, lds, total);
-        for (int k = 0; k < 4; ++k) {
-            const long long e = t * kPlTile + threadIdx.x * 4 + k;
-            if (e < p.npts) p.flag[e] = run;
-            run += v[k];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) p.flag[p.npts] = (int)p.part[tiles];
 }
 
 __global__ __launch_bounds__(kPlThreads) void k_pl_cand_list(PlaneParams p)
@@ -504,7 +371,7 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_final(PlaneParams p)
 {
     for (long long e = blockIdx.x * (long long)kPlThreads + threadIdx.x; e < p.npts; e += (long long)gridDim.x * kPlThreads) {
         const int l = p.lab[e];
-        pl_count(p.plane_cnt, l >= 0 ? p.cbase[pl_cloud(p, e)] + l : 0, l >= 0);
+        wave_add_by_key(p.plane_cnt, l >= 0 ? p.cbase[pl_cloud(p, e)] + l : 0, l >= 0);
         p.labels[e] = l >= 0 ? l : -1;
         p.flag[e] = l < 0 ? 1 : 0;
     }
@@ -525,7 +392,7 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_kept(PlaneParams p)
         }
         if (j >= nk) {
             p.kept[e] = -1;
-            p.points[3 * e] = p.points[3 * e + 1] = p.points[3 * e + 2] = pl_qnan();
+            p.points[3 * e] = p.points[3 * e + 1] = p.points[3 * e + 2] = qnan_f();
         }
     }
 }
@@ -564,7 +431,6 @@ void launch_planes_step(const PlaneParams &p, int step, hipStream_t s)
 {
     const dim3 blk(kPlThreads);
     const int g = pl_grid(p.npts);
-    const int gt = pl_grid(p.npts, kPlTile);
     switch (step) {
     case kPlStepLoad: PBD_LAUNCH(k_pl_load, dim3(g), blk, 0, s, p); break;
     case kPlStepRowSums: PBD_LAUNCH(k_pl_rowsums, dim3(g), blk, 0, s, p); break;
@@ -574,9 +440,9 @@ void launch_planes_step(const PlaneParams &p, int step, hipStream_t s)
     case kPlStepCand: PBD_LAUNCH(k_pl_cand, dim3(g), blk, 0, s, p); break;
     case kPlStepCandScan:
     case kPlStepKeptScan:
-        PBD_LAUNCH(k_pl_scan_part, dim3(gt), blk, 0, s, p);
-        PBD_LAUNCH(k_pl_scan_top, dim3(1), blk, 0, s, p);
-        PBD_LAUNCH(k_pl_scan_add, dim3(gt), blk, 0, s, p);
+        // flag[0 .. npts) in place, flag[npts] = the total
+        launch_scan<int>(p.flag, (int32_t *)nullptr, p.npts, (const long long *)nullptr, p.part, pl_grid(p.npts, kScanTile),
+                         ScanNoTop{}, s);
         break;
     case kPlStepCandList: PBD_LAUNCH(k_pl_cand_list, dim3(g), blk, 0, s, p); break;
     case kPlStepMoments: PBD_LAUNCH(k_pl_moments, dim3(std::max(std::min(p.cand_cap, kPlMaxGrid), 1)), dim3(kMoThreads), 0, s, p); break;

@@ -10,7 +10,7 @@
 //                 of ceil(cols/32) words), in LDS when it fits, else in a per-frame slice of a global workspace
 //   k_post_emit   one workgroup per frame: the kept records, frame by frame, into the output payload
 // A found count above the input capacity makes the output's word 0 = -1 (suppression of a truncated list would differ).
-#include "pbd_internal.h"
+#include "pbd_device.h"
 
 #include <algorithm>
 
@@ -24,18 +24,7 @@ template <bool kLds> constexpr int post_nms_threads() { return kLds ? 256 : 1024
 constexpr size_t kPostLdsCanvasMax = 128 * 1024;   // bytes of bit canvas held in LDS (160 KiB per CU on gfx950)
 
 __device__ inline bool post_overflow(const PostParams &p) { return p.in[0] > p.in_cap || (p.bad && *p.bad); }
-__device__ inline int post_count(const PostParams &p) { return max(min(p.in[0], p.in_cap), 0); }
-
-// first index in [0, n) whose frame is >= f (the list is grouped by ascending frame)
-__device__ inline int post_lower_bound(const int *frame, int n, int f)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (frame[mid] < f) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+__device__ inline int post_count(const PostParams &p) { return payload_count(p.in, p.in_cap); }
 
 // does (a, ia) precede (b, ib)?  Descending score, equal scores by index (Python's stable list.sort on key -score).
 // NaN scores (never produced by the dynamic program) go last, by index, so that the ranks stay a permutation.
@@ -53,8 +42,8 @@ __global__ __launch_bounds__(kPostThreads) void k_post_check(PostParams p)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0 && p.in[0] < 0) *p.bad = 1;
     if (i >= post_count(p) || p.in[0] > p.in_cap) return;
-    const long long f = (long long)p.in[1 + (size_t)i * p.stride] - p.in_offset;
-    const long long g = i > 0 ? (long long)p.in[1 + (size_t)(i - 1) * p.stride] - p.in_offset : 0;
+    const long long f = (long long)p.in[1 + (size_t)i * p.stride + kRecFrame] - p.in_offset;
+    const long long g = i > 0 ? (long long)p.in[1 + (size_t)(i - 1) * p.stride + kRecFrame] - p.in_offset : 0;
     if (f < 0 || f >= p.nframes || f < g) *p.bad = 1;
 }
 
@@ -63,29 +52,16 @@ __global__ __launch_bounds__(kPostThreads) void k_post_prep(PostParams p)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (post_overflow(p) || i >= post_count(p)) return;
     const int32_t *r = p.in + 1 + (size_t)i * p.stride;
-    p.key[i] = __int_as_float(r[5]);
-    const int f = r[0] - p.in_offset;
+    p.key[i] = __int_as_float(r[kRecScore]);
+    const int f = r[kRecFrame] - p.in_offset;
     p.frame[i] = f;
-    const int np = min(max(r[6], 0), p.max_parts);
-    // Candidate::boundingBox: fold of cv::Rect operator| over the parts (an empty left side takes the right side, an empty
-    // right side is skipped); 64-bit so that x + w cannot wrap
-    long long x = 0, y = 0, w = 0, h = 0;
-    for (int k = 0; k < np; ++k) {
-        const long long bx = r[8 + 4 * k], by = r[9 + 4 * k], bw = r[10 + 4 * k], bh = r[11 + 4 * k];
-        if (w <= 0 || h <= 0) {
-            x = bx; y = by; w = bw; h = bh;
-        } else if (bw > 0 && bh > 0) {
-            const long long x1 = min(x, bx), y1 = min(y, by);
-            w = max(x + w, bx + bw) - x1;
-            h = max(y + h, by + bh) - y1;
-            x = x1; y = y1;
-        }
-    }
-    // box & Rect(0, 0, cols, rows); an empty intersection is (0, 0, 0, 0)
+    const int np = min(max(r[kRecNparts], 0), p.max_parts);
+    // Candidate::boundingBox & Rect(0, 0, cols, rows), as corners; an empty intersection is (0, 0, 0, 0)
+    long long x, y, w, h;
+    record_hull64(r, np, x, y, w, h);
     const int2 fs = p.fdim ? p.fdim[f] : make_int2(p.rows, p.cols);   // the frame's own size (mixed-size calls)
-    long long x1 = max(x, 0LL), y1 = max(y, 0LL), x2 = min(x + w, (long long)fs.y), y2 = min(y + h, (long long)fs.x);
-    if (x2 - x1 <= 0 || y2 - y1 <= 0) x1 = y1 = x2 = y2 = 0;
-    p.box[i] = make_int4((int)x1, (int)y1, (int)x2, (int)y2);
+    rect_and64(x, y, w, h, 0, 0, fs.y, fs.x);
+    p.box[i] = make_int4((int)x, (int)y, (int)(x + w), (int)(y + h));
 }
 
 __global__ __launch_bounds__(kPostThreads) void k_post_rank(PostParams p)
@@ -94,7 +70,7 @@ __global__ __launch_bounds__(kPostThreads) void k_post_rank(PostParams p)
     const int n = post_count(p);
     if (post_overflow(p) || i >= n) return;
     const int f = p.frame[i];
-    const int lo = post_lower_bound(p.frame, n, f), hi = post_lower_bound(p.frame, n, f + 1);
+    const int lo = lower_bound_i32(p.frame, n, f), hi = lower_bound_i32(p.frame, n, f + 1);
     const float ki = p.key[i];
     int rank = 0;
     for (int j = lo; j < hi; ++j) rank += post_ahead(p.key[j], j, ki, i) ? 1 : 0;
@@ -112,7 +88,7 @@ __global__ __launch_bounds__(post_nms_threads<kLds>()) void k_post_nms(PostParam
     const int f = p.flist ? p.flist[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
     if (post_overflow(p)) return;
     const int n = post_count(p);
-    const int lo = post_lower_bound(p.frame, n, f), hi = post_lower_bound(p.frame, n, f + 1);
+    const int lo = lower_bound_i32(p.frame, n, f), hi = lower_bound_i32(p.frame, n, f + 1);
     const int wpr = p.fdim ? (p.fdim[f].y + 31) / 32 : p.wpr;
     const long long words = (long long)(p.fdim ? p.fdim[f].x : p.rows) * wpr;
     uint32_t *canvas = kLds ? post_lds : p.canvas + (p.fcanvas ? (size_t)p.fcanvas[f] : (size_t)f * words);
@@ -149,14 +125,9 @@ __global__ __launch_bounds__(post_nms_threads<kLds>()) void k_post_nms(PostParam
 #pragma unroll
             for (int u = 0; u < kUnroll; ++u) cnt += __popc(v[u]);
         }
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-        const int buf = phase & 1;
+        const int buf = phase & 1;                 // two partial arrays in turn: a suppressed candidate's one barrier is enough
         ++phase;
-        if ((tid & 63) == 0) partial[buf][tid >> 6] = cnt;
-        __syncthreads();
-        long long boxsum = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) boxsum += partial[buf][w];
+        const long long boxsum = block_sum<kWaves, long long>(cnt, partial[buf]);
         const double ratio = (double)boxsum / ((double)bw * (double)bh);
         if (ratio > overlap) {
             if (tid == 0) p.slot[k] = -1;
@@ -191,7 +162,7 @@ __global__ __launch_bounds__(kPostThreads) void k_post_emit(PostParams p)
         total += c;
     }
     if (f == 0 && tid == 0) p.out[0] = total;
-    const int lo = post_lower_bound(p.frame, n, f), hi = post_lower_bound(p.frame, n, f + 1);
+    const int lo = lower_bound_i32(p.frame, n, f), hi = lower_bound_i32(p.frame, n, f + 1);
     const int stride = p.stride;
     const long long words = (long long)(hi - lo) * stride;
     for (long long t = tid; t < words; t += kPostThreads) {

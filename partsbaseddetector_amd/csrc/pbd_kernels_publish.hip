@@ -14,7 +14,7 @@
 //               pixels x records.  The labels, then the masked colour bytes, are written in the same pass.
 // Poses: k_part_poses, one thread per record (records number in the hundreds).
 // Every float / double operation whose bits are compared is an explicitly rounded intrinsic, so none of them is contracted.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 #include "pbd_jacobi.h"
 
 #include <math.h>
@@ -29,8 +29,6 @@ constexpr int kMkTileH = kMkThreads * kMkPix / kMkTileW;
 constexpr int kMkMaxGrid = 4096;
 constexpr int kPoseThreads = 64;
 
-__device__ inline float pb_qnan() { return __int_as_float(0x7fc00000); }
-
 __global__ __launch_bounds__(kMkThreads) void k_mk_init(MaskParams p)
 {
     for (int f = blockIdx.x * kMkThreads + threadIdx.x; f < p.nframes; f += gridDim.x * kMkThreads) {
@@ -43,7 +41,7 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_init(MaskParams p)
 // the record's frame index, or -1 when it is out of range
 __device__ inline long long mk_frame(const MaskParams &p, const int32_t *r)
 {
-    const long long f = (long long)r[0] - p.frame_offset;
+    const long long f = (long long)r[kRecFrame] - p.frame_offset;
     return f >= 0 && f < p.nframes ? f : -1;
 }
 
@@ -57,32 +55,19 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_hull(MaskParams p)
     for (int i = blockIdx.x * kMkThreads + threadIdx.x; i < n; i += gridDim.x * kMkThreads) {
         const int32_t *r = p.in + 1 + (size_t)i * p.stride;
         const long long f = mk_frame(p, r);
-        const int np = r[6];
-        const long long fprev = i > 0 ? (long long)p.in[1 + (size_t)(i - 1) * p.stride] - p.frame_offset : -1;
-        const long long fnext = i + 1 < n ? (long long)p.in[1 + (size_t)(i + 1) * p.stride] - p.frame_offset : -1;
+        const int np = r[kRecNparts];
+        const long long fprev = i > 0 ? (long long)p.in[1 + (size_t)(i - 1) * p.stride + kRecFrame] - p.frame_offset : -1;
+        const long long fnext = i + 1 < n ? (long long)p.in[1 + (size_t)(i + 1) * p.stride + kRecFrame] - p.frame_offset : -1;
         if (f < 0 || np < 1 || np > p.max_parts || (i > 0 && f < fprev)) {
             atomicOr(p.bad, 1);
             continue;
         }
-        // boundingBox(): the hull of the parts under cv::Rect operator| (an empty accumulator takes the next part as it is)
-        long long x = r[8], y = r[9], w = r[10], h = r[11];
-        for (int j = 0; j < np; ++j) {
-            const long long bx = r[8 + 4 * j], by = r[9 + 4 * j], bw = r[10 + 4 * j], bh = r[11 + 4 * j];
-            if (w <= 0 || h <= 0) {
-                x = bx; y = by; w = bw; h = bh;
-            } else if (bw > 0 && bh > 0) {
-                const long long x1 = min(x, bx), y1 = min(y, by);
-                w = max(x + w, bx + bw) - x1;
-                h = max(y + h, by + bh) - y1;
-                x = x1; y = y1;
-            }
-        }
-        // & Rect(0, 0, cols, rows); an empty intersection paints nothing (x1 <= x0)
+        // boundingBox() & Rect(0, 0, cols, rows), as corners; an empty intersection is (0, 0, 0, 0) and paints nothing
+        long long x, y, w, h;
+        record_hull64(r, np, x, y, w, h);
         const MaskFrame &fr = p.frames[f];
-        const long long x0 = max(x, 0ll), y0 = max(y, 0ll);
-        long long x1 = min(x + w, (long long)fr.cols), y1 = min(y + h, (long long)fr.rows);
-        if (w <= 0 || h <= 0 || x1 <= x0 || y1 <= y0) x1 = 0;
-        p.hull[i] = x1 > 0 ? make_int4((int)x0, (int)y0, (int)x1, (int)y1) : make_int4(0, 0, 0, 0);
+        rect_and64(x, y, w, h, 0, 0, fr.cols, fr.rows);
+        p.hull[i] = make_int4((int)x, (int)y, (int)(x + w), (int)(y + h));
         if (i == 0 || fprev != f) p.range[2 * f] = i;
         if (i + 1 == n || fnext != f) p.range[2 * f + 1] = i + 1;
     }
@@ -145,7 +130,7 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_tile(MaskParams p)
                 total += wcount[k];
             }
             if (hit) {
-                const int at = off + __popcll(m & ((1ull << lane) - 1));
+                const int at = off + lane_rank(m);
                 lh[at] = hb;
                 lr[at] = i - first;
             }
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_tile(MaskParams p)
 // messagePoses for one record: computeMeanAndCovarianceMatrix, covMat /= count, eigen33, Quaternion(evecs).normalize()
 __global__ __launch_bounds__(kPoseThreads) void k_part_poses(PoseParams p)
 {
-    const int n = min(max(p.count_word[0], 0), p.cap);
+    const int n = payload_count(p.count_word, p.cap);
     for (int i = blockIdx.x * kPoseThreads + threadIdx.x; i < n; i += gridDim.x * kPoseThreads) {
         int nc = p.ncentres[i];
         if (nc < 0 || nc > p.max_parts) nc = 0;
@@ -221,7 +206,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_part_poses(PoseParams p)
         }
         p.count[i] = cnt;
         float *pos = p.position + 3 * (size_t)i, *quat = p.orientation + 4 * (size_t)i, *ev = p.eigenvalues + 3 * (size_t)i;
-        const float qn = pb_qnan();
+        const float qn = qnan_f();
         if (cnt == 0) {                                  // "Centroid not found": the node's `continue`
             for (int k = 0; k < 3; ++k) { pos[k] = qn; ev[k] = qn; }
             for (int k = 0; k < 4; ++k) quat[k] = qn;

@@ -13,7 +13,7 @@
 // R(.) (include/pbd.h): lane l of the 1024 adds the products of values l, l + 1024, ... from +0.0, then a halving tree per
 // 64 lanes (one wavefront: __shfl_down), then a halving tree over the 16 wavefront sums.  Products are multiplies then adds:
 // the library is compiled with -ffp-contract=off.
-#include "pbd_internal.h"
+#include "pbd_device.h"
 
 namespace pbd {
 namespace {
@@ -126,17 +126,13 @@ __device__ bool example_valid(const QpWriteParams &p, int e)
 __global__ __launch_bounds__(kLanes) void k_qp_slots(QpWriteParams p)
 {
     __shared__ int wsum[kWaves + 1];
-    const int m = p.payload ? min(max(p.payload[0], 0), p.m) : p.m;
+    const int m = p.payload ? payload_count(p.payload, p.m) : p.m;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int base = 0;
     for (int e0 = 0; e0 < p.m; e0 += kLanes) {
         const int e = e0 + threadIdx.x;
         const int v = (e < m && example_valid(p, e)) ? 1 : 0;
-        int incl = v;   // inclusive scan inside the wavefront
-        for (int h = 1; h < 64; h <<= 1) {
-            const int t = __shfl_up(incl, h, 64);
-            if (lane >= h) incl += t;
-        }
+        const int incl = wave_incl_scan(v);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         int before = base;
