@@ -538,6 +538,38 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const struct pbd_frame *frames
                       const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found);
 int pbd_model_vector_len(const pbd_handle *h);
 int pbd_model_vector(pbd_handle *h, void *w);
+/* In-place model update (new surface; opt-in): model = vec2model(qp_w, model) of the reference's Matlab training code
+ * (matlab/learning/train.m after every qp_opt; matlab/detection/detect.m:148-151, 316-325) without a new handle.  DESIGN.md
+ * section 6j.  After a successful call the handle cannot be told apart from one that pbd_create builds, with the same config,
+ * from the same pbd_model with its parameters replaced by w (Model.from_vector(w)): pbd_model_vector, the records of
+ * pbd_detect*, pbd_get_stage, pbd_detect_latent and pbd_examples* are equal bit for bit, in every convolution mode and real type.
+ * Topology, anchors, filter sizes and offsets, sbin, interval, thresh, plans, buffers, pbd_set_nms, pbd_set_level_shard and the
+ * stream are not touched.  Rounding: that of pbd_create -- bias and deformation values to float32 (pbd_model holds them so),
+ * filters to T; an F64 source into an F32 handle is rounded once per value.
+ * pbd_set_model_vector: w = pbd_model_vector_len values of T on the host.
+ * pbd_set_model_vector_device: d_w = that many float (real_code PBD_REAL_F32) or double (PBD_REAL_F64) values on the handle's
+ *   device; the caller orders whatever wrote d_w before pbd_stream().
+ * pbd_qp_apply: w_k / wreg_k + w0_k formed in double on the device (pbd_qp_weights' expression), then rounded as above;
+ *   pbd_stream(h) waits for the QP's stream; nothing passes through the host.  Its message is pbd_qp_last_error(q).
+ * The work runs on pbd_stream(): a check kernel, then kernels that rebuild every weight-dependent table of the handle (the
+ * banks of each size class, the matrix-core fragments, the channel-31 border table, bias and deformation tables) and of its
+ * latent twin, if pbd_detect_latent has created one, from the one device vector.  The call returns after reading back one
+ * small status block (the refusal flag and the nbias + 4 ndefs float values the host keeps); in the device forms nothing of
+ * the size of the filter bank crosses to the host (pbd_model_vector after an update fetches the vector when asked).
+ * The resident detect result is dropped as after pbd_conv_set_filters: pbd_examples*, pbd_argmin_device_out and pbd_dp_argmin
+ * give PBD_ERR_STATE until the next detect call.
+ * Refusals, each leaving the handle unchanged: PBD_ERR_STATE while a batch is in flight, or after a pbd_conv_set_filters whose
+ * bank no longer matches the model's filters; PBD_ERR_INVALID for a deformation (of a non-root part) whose quadratic term,
+ * element 0 or 2, is zero once rounded to float32 (pbd_create's refusal, made on the device before anything is written), for
+ * a pbd_qp whose layout fingerprint differs from the handle's or that lives on another device, for NULL pointers and for a
+ * real_code that is neither PBD_REAL_F32 nor PBD_REAL_F64.
+ * A HIP failure after the kernels were queued (PBD_ERR_HIP from an update) leaves tables that may be half new: the handle then
+ * refuses every later update and detect call with PBD_ERR_STATE and must be destroyed.
+ * pbd_set_thresh: the model's thresh (train.m: model.thresh = the 5th percentile of qp_scorepos) for every later detect call;
+ * the resident result stays.  PBD_ERR_STATE while a batch is in flight. */
+int pbd_set_model_vector(pbd_handle *h, const void *w);
+int pbd_set_model_vector_device(pbd_handle *h, const void *d_w, int real_code);
+int pbd_set_thresh(pbd_handle *h, float thresh);
 int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values);
 int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values);
 int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values);
@@ -628,6 +660,7 @@ int pbd_qp_prune(pbd_qp *q, int *n);
 int pbd_qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed, struct pbd_qp_info *state);
 int pbd_qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed, struct pbd_qp_info *state);
 int pbd_qp_weights(pbd_qp *q, double *w);
+int pbd_qp_apply(pbd_qp *q, pbd_handle *h);   /* the in-place model update from the QP's weights: see pbd_set_model_vector */
 int pbd_qp_scores(pbd_qp *q, double *s, int *n);
 int pbd_qp_state(pbd_qp *q, struct pbd_qp_info *state, double *a, uint8_t *sv, double *w);
 int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values, double *b, double *d, int32_t *ids);

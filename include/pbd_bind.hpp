@@ -467,6 +467,26 @@ inline std::vector<double> qp_weights(pbd_qp *q)
     return w;
 }
 
+// the in-place model update (pbd_set_model_vector, pbd_set_thresh, pbd_qp_apply)
+template <class Tr, typename T>
+inline void set_model_vector(pbd_handle *h, const std::vector<T> &w)
+{
+    if (w.size() != (size_t)pbd_model_vector_len(h)) Tr::fail(PBD_ERR_INVALID, "pbd: a model vector of pbd_model_vector_len values");
+    check<Tr>(h, pbd_set_model_vector(h, w.empty() ? NULL : (const void *)&w[0]));
+}
+
+template <class Tr>
+inline void set_thresh(pbd_handle *h, float thresh)
+{
+    check<Tr>(h, pbd_set_thresh(h, thresh));
+}
+
+template <class Tr>
+inline void qp_apply(pbd_qp *q, pbd_handle *h)
+{
+    qp_check<Tr>(q, pbd_qp_apply(q, h));
+}
+
 template <class Tr>
 inline std::vector<double> qp_scores(pbd_qp *q)
 {

@@ -557,6 +557,8 @@ public:
     pbd_qp_info opt(double tol = 0.05, int iter = 1000, uint64_t seed = 0) { return pbdbind::qp_opt<HostTraits<float> >(q_, tol, iter, seed); }
     std::vector<double> weights() { return pbdbind::qp_weights<HostTraits<float> >(q_); }   // qp_w: the model vector
     std::vector<double> scores() { return pbdbind::qp_scores<HostTraits<float> >(q_); }     // qp_scorepos
+    // model = vec2model(qp_w, model) in place: handle h (PartsBasedDetector::handle()) takes weights(), on the device
+    void apply(pbd_handle *h) { pbdbind::qp_apply<HostTraits<float> >(q_, h); }
     pbd_qp_info state() { return pbdbind::qp_state<HostTraits<float> >(q_); }
 
 private:
@@ -782,6 +784,19 @@ public:
         pbdbind::check<HostTraits<T> >(h_, pbd_model_vector(h_, &w[0]));
         w.resize(w.size() - 1);
         return w;
+    }
+    // the in-place model update (pbd_set_model_vector): the detector's parameters become w (modelVector()'s order); afterwards
+    // it equals a detector given distributeModel() of the model with those parameters
+    void setModelVector(const std::vector<T> &w)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "setModelVector() before distributeModel()");
+        pbdbind::set_model_vector<HostTraits<T> >(h_, w);
+    }
+    // model.thresh for every later detect() (pbd_set_thresh)
+    void setThreshold(float thresh)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "setThreshold() before distributeModel()");
+        pbdbind::set_thresh<HostTraits<T> >(h_, thresh);
     }
     // training examples of candidates of the last detect() (pbd_examples, include/pbd.h): hdr receives hdr_words int32 per
     // candidate {index, component, nblocks, nvalues, (offset in modelVector(), length) x nblocks}, values `values` T per candidate

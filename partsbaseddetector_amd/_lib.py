@@ -46,7 +46,7 @@ SYMBOLS = [
     "pbd_part_poses", "pbd_part_poses_device", "pbd_model_vector_len", "pbd_model_vector", "pbd_example_stride", "pbd_examples",
     "pbd_examples_device", "pbd_detect_latent", "pbd_qp_create", "pbd_qp_destroy", "pbd_qp_last_error", "pbd_qp_add",
     "pbd_qp_add_device", "pbd_qp_fix", "pbd_qp_prune", "pbd_qp_one", "pbd_qp_opt", "pbd_qp_weights", "pbd_qp_scores", "pbd_qp_state",
-    "pbd_qp_entries",
+    "pbd_qp_entries", "pbd_set_model_vector", "pbd_set_model_vector_device", "pbd_set_thresh", "pbd_qp_apply",
 ]
 
 
@@ -228,6 +228,10 @@ def load():
     lib.pbd_part_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     lib.pbd_model_vector_len.argtypes = [C.c_void_p]
     lib.pbd_model_vector.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pbd_set_model_vector.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pbd_set_model_vector_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.pbd_set_thresh.argtypes = [C.c_void_p, C.c_float]
+    lib.pbd_qp_apply.argtypes = [C.c_void_p, C.c_void_p]
     lib.pbd_example_stride.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.pbd_examples.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pbd_examples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

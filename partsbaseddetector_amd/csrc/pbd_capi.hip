@@ -522,24 +522,7 @@ int get_mixed_plan(pbd_handle *h, int nframes, const int *rows, const int *cols,
     return PBD_OK;
 }
 
-// IEEE binary16 <-> float on the host (round to nearest even, what v_cvt_f16_f32 does)
-uint16_t host_f2h(float f)
-{
-    uint32_t u; memcpy(&u, &f, 4);
-    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-    const uint32_t ax = u & 0x7fffffffu;
-    if (ax > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                 // NaN
-    if (ax >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                // rounds to >= 65520: inf
-    if (ax < 0x33000001u) return sign;                                       // below half the smallest subnormal: 0
-    const int e = (int)(ax >> 23) - 127;
-    uint32_t m = (ax & 0x7fffffu) | 0x800000u;
-    int shift = e >= -14 ? 13 : 13 + (-14 - e);                              // bits dropped from the 24-bit significand
-    const uint32_t half = 1u << (shift - 1), rest = m & ((1u << shift) - 1);
-    uint32_t q = m >> shift;
-    if (rest > half || (rest == half && (q & 1u))) ++q;
-    const uint32_t bits = e >= -14 ? (((uint32_t)(e + 15) << 10) + (q - 0x400u)) : q;   // carry propagates into the exponent
-    return (uint16_t)(sign | bits);
-}
+// IEEE binary16 -> float on the host (host_f2h, the other direction: pbd_layout.h)
 float host_h2f(uint16_t hv)
 {
     const uint32_t sign = (uint32_t)(hv & 0x8000u) << 16;
@@ -614,15 +597,12 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
         // generic kernel (other sizes, T=double) [channel][tap][Fpad]
         const bool fast5 = (sizeof(R) == 4 && C.K == 5);
         const int KK = C.K * C.K;
-        std::vector<R> w((size_t)32 * KK * C.Fpad, (R)0);
-        for (int fl = 0; fl < C.nf; ++fl) {
-            const R *src = static_cast<const R *>(filters[ids[fl]]);
-            for (int t = 0; t < KK; ++t)
-                for (int c = 0; c < 32; ++c) {
-                    const R v = src[(size_t)t * 32 + c];
-                    if (fast5) w[(((size_t)(fl / kConvQ) * 32 + c) * KK + t) * kConvQ + (fl % kConvQ)] = v;
-                    else w[((size_t)c * KK + t) * C.Fpad + fl] = v;
-                }
+        // (every table below is filled in gather form from its one layout definition, pbd_layout.h: the in-place model update's
+        // kernels fill the same tables from the same definitions)
+        std::vector<R> w((size_t)generic_bank_size(KK, C.Fpad), (R)0);
+        for (size_t i = 0; i < w.size(); ++i) {
+            const WeightSrc s = fast5 ? group_bank_source((long long)i, KK, C.nf) : generic_bank_source((long long)i, KK, C.Fpad, C.nf);
+            if (s.f >= 0) w[i] = static_cast<const R *>(filters[ids[s.f]])[weight_at(s)];
         }
         HIPCHK(h, C.wts.ensure(w.size() * sizeof(R)));
         HIPCHK(h, hipMemcpy(C.wts.p, w.data(), w.size() * sizeof(R), hipMemcpyHostToDevice));
@@ -633,13 +613,12 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             C.nunits = (int)uf0.size();
             std::vector<int> uoff(C.nunits, 0);
             size_t tot = 0;
-            for (int u = 0; u < C.nunits; ++u) { uoff[u] = (int)tot; tot += (size_t)32 * KK * uql[u]; }
+            for (int u = 0; u < C.nunits; ++u) { uoff[u] = (int)tot; tot += (size_t)unit_size(KK, uql[u]); }
             std::vector<float> w3(tot + 16, 0.0f);       // (slack: the last tap row is fetched once more past the last channel)
             for (int u = 0; u < C.nunits; ++u)
-                for (int q = 0; q < uql[u] && uf0[u] + q < C.nf; ++q) {
-                    const R *src = static_cast<const R *>(filters[ids[uf0[u] + q]]);
-                    for (int t = 0; t < KK; ++t)
-                        for (int c = 0; c < 32; ++c) w3[uoff[u] + ((size_t)c * KK + t) * uql[u] + q] = (float)src[(size_t)t * 32 + c];
+                for (long long r = 0; r < unit_size(KK, uql[u]); ++r) {
+                    const WeightSrc s = unit_source(r, KK, uf0[u], uql[u], C.nf);
+                    if (s.f >= 0) w3[uoff[u] + r] = (float)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)];
                 }
             HIPCHK(h, C.unit_woff.upload(uoff));
             // channel 31 of a window that leaves the image: the reference's sum over the out-of-image taps (border value 1,
@@ -648,13 +627,12 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             C.c31stride = (C.nf + 15) & ~7;                     // a unit's 8 consecutive entries stay inside the row
             std::vector<float> tab((size_t)81 * C.c31stride, 0.0f);
             for (int cs = 0; cs < 81; ++cs) {
-                const int right = cs % 3, left = cs / 3 % 3, bot = cs / 9 % 3, top = cs / 27;
                 for (int fl = 0; fl < C.nf; ++fl) {
                     const R *src = static_cast<const R *>(filters[ids[fl]]);
                     float sum = 0.0f;
                     for (int i = 0; i < 5; ++i)
                         for (int j = 0; j < 5; ++j) {
-                            if (!(i < top || i > 4 - bot || j < left || j > 4 - right)) continue;
+                            if (!c31_tap_outside(cs, i, j)) continue;
                             const float w = (float)src[(size_t)(i * 5 + j) * 32 + 31];
                             if (w != 0.0f) sum = sum + w;
                         }
@@ -668,25 +646,14 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             HIPCHK(h, C.unit_ql.upload(uql));
         }
         if (h->cfg.conv_mode == PBD_CONV_MFMA_F64) {
-            // A-fragments in the order k_conv_mfma_f64 reads them.  Pass ps (M-tiles [m0, m1)), channel block cb, tap, q-pair qp,
-            // M-tile m, q of the pair e, lane l: filter (m0 + m) * 16 + (l & 15), channel cb * CB + (l >> 4) * QN + qp * QS + e
-            // (lane group g supplies channels g QN .. g QN + QN - 1 of its cell); filters past nf are zero
-            const int QN = conv_mfma_f64_qn(C.K), CB = 4 * QN, QS = std::min(QN, 2), QP = QN / QS;
+            // A-fragments in the order k_conv_mfma_f64 reads them (f64_frag_source: lane group g supplies channels g QN ..
+            // g QN + QN - 1 of its cell); filters past nf are zero
+            const int QN = conv_mfma_f64_qn(C.K);
             const int mtiles = (C.nf + 15) / 16, passes = f64_passes(mtiles);
-            std::vector<double> wf((size_t)mtiles * 8 * KK * 64, 0.0);
-            size_t o = 0;
-            for (int ps = 0; ps < passes; ++ps) {
-                const int m0 = f64_pass_begin(ps, mtiles, passes), mb = f64_pass_begin(ps + 1, mtiles, passes) - m0;
-                for (int cb = 0; cb < 32 / CB; ++cb)
-                    for (int t = 0; t < KK; ++t)
-                        for (int qp = 0; qp < QP; ++qp)
-                            for (int m = 0; m < mb; ++m)
-                                for (int e = 0; e < QS; ++e)
-                                    for (int l = 0; l < 64; ++l, ++o) {
-                                        const int fl = (m0 + m) * 16 + (l & 15);
-                                        const int c = cb * CB + (l >> 4) * QN + qp * QS + e;
-                                        if (fl < C.nf) wf[o] = (double)static_cast<const R *>(filters[ids[fl]])[(size_t)t * 32 + c];
-                                    }
+            std::vector<double> wf((size_t)f64_frag_size(KK, mtiles), 0.0);
+            for (size_t o = 0; o < wf.size(); ++o) {
+                const WeightSrc s = f64_frag_source((long long)o, KK, QN, mtiles, passes, C.nf);
+                if (s.f >= 0) wf[o] = (double)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)];
             }
             HIPCHK(h, C.wfrag64.ensure(wf.size() * sizeof(double)));
             HIPCHK(h, hipMemcpy(C.wfrag64.p, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -695,36 +662,15 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
     const int Fpad = (nfilters + kConvQ - 1) / kConvQ * kConvQ;
     if (mfma) {
         const bool f16 = h->cfg.conv_mode == PBD_CONV_MFMA_F16;
-        // bf16 mode: x = hi + lo with round-to-nearest-even; fp16 mode: one rounding
-        auto f2bf = [](float f) -> uint16_t {
-            uint32_t u; memcpy(&u, &f, 4);
-            if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            return (uint16_t)(u >> 16);
-        };
-        auto bf2f = [](uint16_t b) -> float { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
-        // A-operand fragments in the order the kernel consumes them: [pass][tap][k-step][M-tile][hi|lo][lane] x 8 values.
-        // Lane (r = lane & 31, hh = lane >> 5) of v_mfma_f32_32x32x16 holds row r (filter), k = hh*8 .. hh*8+7 (channels)
-        const int NV = f16 ? 1 : 2, MT = kMfmaFilterBlock / 32;
-        const int passes = (nfilters + kMfmaFilterBlock - 1) / kMfmaFilterBlock;
-        std::vector<uint16_t> rec((size_t)passes * K * K * 2 * MT * NV * 64 * 8, 0);
-        for (int ps = 0; ps < passes; ++ps)
-            for (int t = 0; t < K * K; ++t)
-                for (int kh = 0; kh < 2; ++kh)
-                    for (int mt = 0; mt < MT; ++mt)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int f = ps * kMfmaFilterBlock + mt * 32 + (lane & 31);
-                            if (f >= nfilters) continue;
-                            const float *src = reinterpret_cast<const float *>(filters[f]) + (size_t)t * 32 + kh * 16 + (lane >> 5) * 8;
-                            const size_t base = (((((size_t)ps * K * K + t) * 2 + kh) * MT + mt) * NV) * 64 * 8;
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = src[j];
-                                if (f16) { rec[base + (size_t)lane * 8 + j] = host_f2h(v); continue; }
-                                const uint16_t hi = f2bf(v);
-                                rec[base + (size_t)lane * 8 + j] = hi;
-                                rec[base + (size_t)(64 + lane) * 8 + j] = f2bf(v - bf2f(hi));
-                            }
-                        }
+        // bf16 mode: x = hi + lo with round-to-nearest-even; fp16 mode: one rounding (wrec_value).  A-operand fragments in the
+        // order the kernel consumes them (wrec_source)
+        const int NV = f16 ? 1 : 2;
+        std::vector<uint16_t> rec((size_t)wrec_size(K * K, NV, nfilters), 0);
+        for (size_t i = 0; i < rec.size(); ++i) {
+            int part = 0;
+            const WeightSrc s = wrec_source((long long)i, K * K, NV, nfilters, &part);
+            if (s.f >= 0) rec[i] = wrec_value(reinterpret_cast<const float *>(filters[s.f])[weight_at(s)], f16, part);
+        }
         HIPCHK(h, wrec.ensure(rec.size() * 2));
         HIPCHK(h, hipMemcpy(wrec.p, rec.data(), rec.size() * 2, hipMemcpyHostToDevice));
     }
@@ -855,8 +801,7 @@ int build_model(pbd_handle *h, const pbd_model *m)
         j.plane = plane;
         j.gm = gm;
         const int d = h->defid[gm];
-        const float *w = &h->defw[(size_t)d * 4];
-        j.ax = (double)(-w[0]); j.bx = (double)(-w[1]); j.ay = (double)(-w[2]); j.by = (double)(-w[3]);
+        set_quadratics(j, &h->defw[(size_t)d * 4]);
         j.osx = h->anchors[(size_t)d * 2]; j.osy = h->anchors[(size_t)d * 2 + 1];
         return j;
     };
@@ -935,13 +880,7 @@ int build_model(pbd_handle *h, const pbd_model *m)
     }
     for (auto &g : h->groups) {
         HIPCHK(h, g.d_jobs.upload(g.jobs));
-        // the usual deformation (w1 = w3 = +0.0f, so b = -0.0): the passes then run without the b terms
-        auto neg_zero = [](double v) { return v == 0.0 && std::signbit(v); };
-        g.bz_x = g.bz_y = 1;
-        for (const DtJob &j : g.jobs) {
-            if (!(neg_zero(j.bx) && j.ax != 0.0)) g.bz_x = 0;
-            if (!(neg_zero(j.by) && j.ay != 0.0)) g.bz_y = 0;
-        }
+        set_variant_flags(g);
         HIPCHK(h, g.d_childs.upload(g.childs));
         HIPCHK(h, g.d_cjobs.upload(g.cjobs));
         HIPCHK(h, g.d_sjobs.upload(g.sjobs));

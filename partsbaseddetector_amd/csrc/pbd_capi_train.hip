@@ -1,5 +1,5 @@
-// pbd_capi_train.hip -- the C entry points of training (include/pbd.h): the model vector, training examples of a resident detect
-// result, latent positives, and the QP over a device-resident example cache.
+// pbd_capi_train.hip -- the C entry points of training (include/pbd.h): the model vector and its in-place update, training
+// examples of a resident detect result, latent positives, and the QP over a device-resident example cache.
 // The handle and the layer they are written on: pbd_handle.h.
 #include "pbd_handle.h"
 
@@ -57,6 +57,140 @@ int enqueue_examples(pbd_handle *h, const int32_t *d_in, int capacity, int frame
     return PBD_OK;
 }
 
+
+// ---- in-place model update (the kernels: pbd_kernels_model.hip) ------------------------------------------
+// the host copy of the model vector, brought up to date with the device's after an update
+int sync_mvec(pbd_handle *h)
+{
+    if (!h->mvec_stale) return PBD_OK;
+    HIPCHK(h, hipMemcpyAsync(h->mvec.data(), h->d_mvec.p, h->mvec.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->mvec_stale = false;
+    return PBD_OK;
+}
+
+size_t mu_status_bytes(const pbd_handle *h) { return 4 * sizeof(int) + ((size_t)h->nbias + 4 * (size_t)h->ndefs) * sizeof(float); }
+
+// everything an update of h allocates or uploads (index tables on first use), so that nothing can fail once kernels are queued
+int mu_prepare(pbd_handle *h)
+{
+    HIPCHK(h, h->d_mvec.ensure(std::max<size_t>(h->mvec.size(), 16)));
+    HIPCHK(h, h->mu_status.ensure(mu_status_bytes(h)));
+    HIPCHK(h, h->mu_status_host.ensure(mu_status_bytes(h), mu_status_bytes(h)));
+    if (h->mu_foff.p) return PBD_OK;
+    std::vector<int> gm_def(h->totmix, -1), root_bias(h->NC, 0);
+    for (int c = 0; c < h->NC; ++c) {
+        const int p0 = h->part_offset[c];
+        root_bias[c] = h->biasid[h->mix_offset[p0]];
+        for (int gp = p0 + 1; gp < h->part_offset[c + 1]; ++gp)
+            for (int gm = h->mix_offset[gp]; gm < h->mix_offset[gp + 1]; ++gm) gm_def[gm] = h->defid[gm];
+    }
+    std::vector<MuJobRef> jobs;
+    for (Group &g : h->groups)
+        for (size_t j = 0; j < g.jobs.size(); ++j) jobs.push_back(MuJobRef{g.d_jobs.p + j, h->defid[g.jobs[j].gm], 0});
+    const long long fbase = (long long)h->nbias + 4LL * h->ndefs;
+    std::vector<long long> foff(h->model_foff);
+    for (long long &o : foff) o += fbase;
+    HIPCHK(h, h->mu_gm_def.upload(gm_def));
+    HIPCHK(h, h->mu_root_bias.upload(root_bias));
+    HIPCHK(h, h->mu_jobs.upload(jobs));
+    HIPCHK(h, h->mu_foff.upload(foff));   // last: its presence marks the set complete
+    return PBD_OK;
+}
+
+// the update's kernels for handle h on stream st: its tables from `src`, the refusal flag and the status values at `status`
+// (h's own block, or the block of the handle whose latent twin h is: the twin follows its owner's check)
+void mu_enqueue(pbd_handle *h, const MuSource &src, char *status, bool check, hipStream_t st)
+{
+    MuParams p{};
+    p.refused = reinterpret_cast<int *>(status);
+    p.st_bias = reinterpret_cast<float *>(status + 4 * sizeof(int));
+    p.st_def = p.st_bias + h->nbias;
+    p.L = (int)(h->mvec.size() / h->rs); p.nbias = h->nbias; p.ndefs = h->ndefs; p.totmix = h->totmix; p.NC = h->NC;
+    p.njobs = (int)h->mu_jobs.size;
+    p.gm_def = h->mu_gm_def.p; p.root_bias = h->mu_root_bias.p;
+    p.mvec = h->d_mvec.p; p.biasw = h->d_biasw.p; p.rjobs = h->d_rjobs.p; p.jobs = h->mu_jobs.p; p.foff = h->mu_foff.p;
+    if (check) launch_mu_check(p, src, st);
+    launch_mu_vector(p, src, h->f64, st);
+    launch_mu_tables(p, h->f64, st);
+    const bool mfma = h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16;
+    for (pbd_handle::ConvClass &C : h->conv_classes) {
+        MuClassParams cp{};
+        cp.refused = p.refused; cp.mvec = p.mvec; cp.foff = p.foff; cp.fmap = C.fmap.p;
+        cp.K = C.K; cp.nf = C.nf; cp.Fpad = C.Fpad; cp.group_layout = (!h->f64 && C.K == 5) ? 1 : 0;
+        cp.wts = C.wts.p;
+        cp.wts3 = C.wts3.as<float>(); cp.unit_f0 = C.unit_f0.p; cp.unit_ql = C.unit_ql.p; cp.unit_woff = C.unit_woff.p;
+        cp.nunits = C.nunits;
+        cp.c31tab = C.c31tab.p; cp.c31stride = C.c31stride;
+        cp.wfrag64 = C.wfrag64.as<double>(); cp.qn = cp.wfrag64 ? conv_mfma_f64_qn(C.K) : 0;
+        if (mfma) { cp.wrec = h->d_wrec.as<uint16_t>(); cp.wrec_f16 = h->cfg.conv_mode == PBD_CONV_MFMA_F16; cp.nfilters = h->F; }
+        launch_mu_class(cp, h->f64, st);
+    }
+}
+
+// the host's copies after a successful update: bias and deformation values, the root biases, the jobs' quadratics and the
+// groups' variant flags by build_model's own predicate; the host model vector is behind until someone asks for it
+void mu_finish(pbd_handle *h, const float *bias, const float *def)
+{
+    h->biasw.assign(bias, bias + h->nbias);
+    h->defw.assign(def, def + 4 * (size_t)h->ndefs);
+    for (int c = 0; c < h->NC; ++c) h->rjobs[c].bias = h->biasw[h->biasid[h->mix_offset[h->part_offset[c]]]];
+    for (Group &g : h->groups) {
+        for (DtJob &j : g.jobs) set_quadratics(j, &h->defw[(size_t)h->defid[j.gm] * 4]);
+        set_variant_flags(g);
+    }
+    h->mvec_stale = true;
+    h->res.drop_conv();   // the resident responses and maps were the old weights'
+}
+
+// the host-side refusals of an update: nothing is staged, queued or allocated before they pass
+int check_update_state(pbd_handle *h)
+{
+    if (h->broken) return fail(h, PBD_ERR_STATE, "an earlier model update failed half way: the handle must be destroyed");
+    if (h->nsubmitted != h->nwaited) return fail(h, PBD_ERR_STATE, "a submitted batch has not been waited for");
+    if (int rc = check_bank(h)) return rc;
+    if (h->filter_ksize != h->model_ksize)
+        return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
+    if (h->lat && h->lat->mvec.size() > h->mvec.size())
+        return fail(h, PBD_ERR_STATE, "the latent twin's model vector is longer than the handle's");
+    return PBD_OK;
+}
+
+// The update of h from `src` (pbd_model_vector_len values on the device, readable in h's stream order).  Every check that
+// can refuse comes before the first kernel except the deformation check, which runs first on the device and gates the rest.
+int update_model(pbd_handle *h, const MuSource &src)
+{
+    if (int rc = check_update_state(h)) return rc;
+    pbd_handle *t = h->lat.get();
+    if (int rc = mu_prepare(h)) return rc;
+    if (t)
+        if (int rc = mu_prepare(t)) return fail(h, rc, "latent twin: %s", t->err.c_str());
+    char *status = h->mu_status.as<char>();
+    HIPCHK(h, hipMemsetAsync(status, 0, 4 * sizeof(int), h->stream));
+    mu_enqueue(h, src, status, true, h->stream);
+    // the twin's filter gm is the block of filterid[gm] (its own offsets say so), bias and deformation values are the handle's
+    if (t) mu_enqueue(t, MuSource{h->d_mvec.p, nullptr, nullptr, h->f64 ? kMuSrcF64 : kMuSrcF32}, status, false, h->stream);
+    // From here to the read-back a HIP failure leaves device tables that may be new beside host copies that are old: the handle
+    // is marked broken, and every later update and every call that needs the model (check_bank) refuses it with PBD_ERR_STATE.
+    const char *host = h->mu_status_host.as<char>();
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->mu_status_host.p, status, mu_status_bytes(h), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->broken = true;
+        if (t) t->broken = true;
+        return fail(h, PBD_ERR_HIP, "the model update failed on the device (%s): the handle's tables are undefined and it must be destroyed",
+                    hipGetErrorString(e));
+    }
+    if (*reinterpret_cast<const int *>(host))
+        return fail(h, PBD_ERR_INVALID, "a deformation's quadratic term (element 0 or 2) is zero in float32");
+    const float *bias = reinterpret_cast<const float *>(host + 4 * sizeof(int)), *def = bias + h->nbias;
+    mu_finish(h, bias, def);
+    if (t) mu_finish(t, bias, def);
+    return PBD_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -68,7 +202,39 @@ int pbd_model_vector_len(const pbd_handle *h) { return h ? (int)(h->mvec.size() 
 int pbd_model_vector(pbd_handle *h, void *w)
 {
     return entry(h, w, kBusyOk, [&]() -> int {
+        if (int rc = sync_mvec(h)) return rc;
         memcpy(w, h->mvec.data(), h->mvec.size());
+        return PBD_OK;
+    });
+}
+
+// In-place model update.  See include/pbd.h and DESIGN.md section 6j.
+int pbd_set_model_vector_device(pbd_handle *h, const void *d_w, int real_code)
+{
+    return entry(h, d_w, kIdle, [&]() -> int {
+        if (real_code != PBD_REAL_F32 && real_code != PBD_REAL_F64)
+            return fail(h, PBD_ERR_INVALID, "real_code %d: PBD_REAL_F32 or PBD_REAL_F64", real_code);
+        return update_model(h, MuSource{d_w, nullptr, nullptr, real_code == PBD_REAL_F64 ? kMuSrcF64 : kMuSrcF32});
+    });
+}
+
+int pbd_set_model_vector(pbd_handle *h, const void *w)
+{
+    return entry(h, w, kIdle, [&]() -> int {
+        if (int rc = check_update_state(h)) return rc;
+        HIPCHK(h, h->mu_src.ensure(std::max<size_t>(h->mvec.size(), 16)));
+        HIPCHK(h, hipMemcpyAsync(h->mu_src.p, w, h->mvec.size(), hipMemcpyHostToDevice, h->stream));
+        const int rc = update_model(h, MuSource{h->mu_src.p, nullptr, nullptr, h->f64 ? kMuSrcF64 : kMuSrcF32});
+        if (rc != PBD_OK) (void)hipStreamSynchronize(h->stream);   // w is the caller's again when the call returns
+        return rc;
+    });
+}
+
+int pbd_set_thresh(pbd_handle *h, float thresh)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        h->thresh = thresh;
+        if (h->lat) h->lat->thresh = thresh;
         return PBD_OK;
     });
 }
@@ -146,6 +312,7 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
                 off[gm] = h->model_foff[h->filterid[gm]];
             }
             const size_t fbase = (size_t)h->nbias + 4 * (size_t)h->ndefs;
+            if (int rc = sync_mvec(h)) return rc;   // after an in-place update the twin starts from the new weights
             pbd_model m{};
             m.ncomponents = h->NC; m.nfilters = T; m.flen = 32; m.filter_ksize = ks.data(); m.filter_offset = off.data();
             if (h->f64) m.filters_f64 = reinterpret_cast<const double *>(h->mvec.data()) + fbase;
@@ -812,6 +979,22 @@ int pbd_qp_weights(pbd_qp *q, double *w)
         HIPCHK(q, hipMemcpyAsync(v.data(), q->w.p, (size_t)q->L * sizeof(double), hipMemcpyDeviceToHost, q->stream));
         HIPCHK(q, hipStreamSynchronize(q->stream));
         for (int k = 0; k < q->L; ++k) w[k] = v[k] / q->wreg_h[k] + q->w0_h[k];
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_apply(pbd_qp *q, pbd_handle *h)
+{
+    return entry(q, h != nullptr, [&]() -> int {
+        if (h->device != q->device) return fail(q, PBD_ERR_INVALID, "the QP lives on device %d, the handle on device %d", q->device, h->device);
+        if (qp_layout(h).fp != q->fp) return fail(q, PBD_ERR_INVALID, "the handle's model-vector layout differs from the QP's");
+        if (h->stream.s != q->stream.s) {   // the handle's stream waits for the QP's
+            Event ev;
+            HIPCHK(q, hipEventCreateWithFlags(&ev.p, hipEventDisableTiming));
+            HIPCHK(q, hipEventRecord(ev.p, q->stream));
+            HIPCHK(q, hipStreamWaitEvent(h->stream, ev.p, 0));
+        }
+        if (int rc = update_model(h, MuSource{q->w.p, q->wreg.p, q->w0.p, kMuSrcQp})) return fail(q, rc, "%s", h->err.c_str());
         return PBD_OK;
     });
 }

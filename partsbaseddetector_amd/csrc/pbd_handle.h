@@ -208,6 +208,22 @@ struct Group {   // DT jobs of the parts of one tree depth + combine jobs of the
     DevTable<SeqCombineJob> d_sjobs;
 };
 
+// Quadratic(-w0, -w1), Quadratic(-w2, -w3) of a deformation's four float32 values (-(+0.0f) is -0.0)
+inline void set_quadratics(DtJob &j, const float *w)
+{
+    j.ax = (double)(-w[0]); j.bx = (double)(-w[1]); j.ay = (double)(-w[2]); j.by = (double)(-w[3]);
+}
+// the usual deformation (w1 = w3 = +0.0f, so b = -0.0): the group's passes then run without the b terms
+inline void set_variant_flags(Group &g)
+{
+    auto neg_zero = [](double v) { return v == 0.0 && std::signbit(v); };
+    g.bz_x = g.bz_y = 1;
+    for (const DtJob &j : g.jobs) {
+        if (!(neg_zero(j.bx) && j.ax != 0.0)) g.bz_x = 0;
+        if (!(neg_zero(j.by) && j.ay != 0.0)) g.bz_y = 0;
+    }
+}
+
 struct Prof {
     int on = 0;                      // 0: off, 1: every kernel, 2: the convolution only (pbd_profile_enable)
     struct Rec { int k; Event a, b; };
@@ -360,6 +376,18 @@ struct Handle : ErrCtx {
     DevTable<int> ex_anchors;
     DevTable<long long> ex_foff;
     DevBuf ex_ws, ex_rec, ex_out;
+    // pbd_set_model_vector* / pbd_qp_apply: the model vector on the device (T; written by the first update, from then on the
+    // source of every weight table), whether the host copy `mvec` is behind it (brought up to date on demand: sync_mvec), the
+    // update's index tables (built on first use), the host form's vector, and the status block {refused, -, -, -, biasw, defw}
+    // with its pinned mirror
+    DevBuf d_mvec;
+    bool mvec_stale = false;
+    bool broken = false;             // a model update failed after its kernels were queued: check_bank refuses the handle
+    DevTable<int> mu_gm_def, mu_root_bias;
+    DevTable<MuJobRef> mu_jobs;
+    DevTable<long long> mu_foff;
+    DevBuf mu_src, mu_status;
+    HostBuf mu_status_host;
     // pbd_detect_latent: a second handle on the same stream whose model gives every (component, part, mixture) its own filter
     // (the mask belongs to the (component, part, mixture), not to a shared filter), created on first use; the part -> mixture
     // table of its bank, the call's boxes / mixtures and its payload.  The detect path of this handle never touches it.
@@ -494,6 +522,7 @@ inline int check_batch(pbd_handle *h, int nframes)
 }
 inline int check_bank(pbd_handle *h)
 {
+    if (h->broken) return fail(h, PBD_ERR_STATE, "an earlier model update failed half way: the handle must be destroyed");
     if (h->bank_matches_model) return PBD_OK;
     return fail(h, PBD_ERR_STATE, "the filter bank set by setFilters() (%d filters) does not cover the model's filter ids", h->F);
 }

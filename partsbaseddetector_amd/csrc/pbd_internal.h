@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/pbd.h"
+#include "pbd_layout.h"
 
 namespace pbd {
 
@@ -465,15 +466,14 @@ int conv_mfma_occupancy(bool f16);
 // matrix-core path (pbd_kernels_conv_mfma.hip); wrec: [pass][tap][160 filters][144 B] bf16 hi/lo records
 // PBD_CONV_MFMA_F16: 80 B fp16 records, one MFMA per product tile
 void launch_conv_mfma(const ConvParams &p, const void *wrec, bool f16, int nframes, hipStream_t s);
-constexpr int kMfmaFilterBlock = 160, kMfmaRecBytes = 144, kMfmaRecBytesF16 = 80;
+constexpr int kMfmaFilterBlock = kWrecFilterBlock, kMfmaRecBytes = 144, kMfmaRecBytesF16 = 80;
 // PBD_CONV_MFMA_F64 (pbd_kernels_conv_mfma_f64.hip).  A size class of nf filters is ceil(nf / 16) M-tiles, split into
 // f64_passes() passes (grid y) of at most kF64MaxMB M-tiles; pass i covers M-tiles [f64_pass_begin(i), f64_pass_begin(i + 1)).
-// wfrag: the class's A-fragments, [pass][channel block][tap][q-pair][M-tile of the pass][q of the pair][lane] doubles
-// (upload_filters_t); the channel block of a filter size is conv_mfma_f64_qn(): 4 * qn channels per block
+// wfrag: the class's A-fragments in the order of f64_frag_source (pbd_layout.h); the channel block of a filter size is
+// conv_mfma_f64_qn(): 4 * qn channels per block
 constexpr int kF64MaxMB = 4;
 constexpr size_t kF64LdsTarget = 80 * 1024;   // haloed tile per workgroup: two workgroups per CU (160 KB of LDS)
 inline int f64_passes(int mtiles) { return (mtiles + kF64MaxMB - 1) / kF64MaxMB; }
-__host__ __device__ inline int f64_pass_begin(int pass, int mtiles, int passes) { return pass * mtiles / passes; }
 int conv_mfma_f64_qn(int ksize);
 size_t conv_mfma_f64_lds(int ksize, int qn);
 void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes, hipStream_t s);
@@ -656,5 +656,40 @@ struct QpGatherParams {
     float *x; uint8_t *bm; int32_t *hd; int32_t *ids; double *b, *d, *a;   // scratch of `count` entries
 };
 void launch_qp_gather(const QpGatherParams &p, hipStream_t s);
+
+// in-place model update (pbd_set_model_vector*, pbd_qp_apply; pbd_kernels_model.hip).  Every kernel returns at once when
+// *refused is set (k_mu_check found a deformation whose quadratic term rounds to zero), so a refused call writes nothing.
+enum { kMuSrcF32 = 0, kMuSrcF64 = 1, kMuSrcQp = 2 };
+struct MuSource {                 // the new vector: L values of float / double, or the QP's w_k / wreg_k + w0_k in double
+    const void *w;
+    const double *wreg, *w0;
+    int code;
+};
+struct MuJobRef { DtJob *job; int def; int pad; };   // a distance-transform job of any group and its deformation
+struct MuParams {
+    int *refused;                 // word 0 of the status block
+    float *st_bias, *st_def;      // the status block's copy of the float32 bias and deformation values
+    int L, nbias, ndefs, totmix, NC, njobs;
+    const int *gm_def;            // [totmix] the deformation of a non-root (part, mixture), -1 for a root's
+    const int *root_bias;         // [NC]
+    void *mvec;                   // R [L] the handle's model vector on the device
+    float *biasw; RootJob *rjobs; const MuJobRef *jobs;
+    const long long *foff;        // [nfilters] offset of filter f in the model vector
+};
+struct MuClassParams {            // one size class of the bank
+    const int *refused;
+    const void *mvec; const long long *foff;
+    const int *fmap;              // class-local index -> filter id (NULL: identity)
+    int K, nf, Fpad, group_layout;
+    void *wts;
+    float *wts3; const int *unit_f0, *unit_ql, *unit_woff; int nunits;
+    float *c31tab; int c31stride;
+    double *wfrag64; int qn;
+    uint16_t *wrec; int wrec_f16, nfilters;   // the matrix-core records (one class, filter ids in order)
+};
+void launch_mu_check(const MuParams &p, const MuSource &src, hipStream_t s);
+void launch_mu_vector(const MuParams &p, const MuSource &src, bool f64, hipStream_t s);   // mvec, the status block's values
+void launch_mu_tables(const MuParams &p, bool f64, hipStream_t s);                        // d_biasw, root biases, DtJobs
+void launch_mu_class(const MuClassParams &p, bool f64, hipStream_t s);                    // every table of the class that is set
 
 }  // namespace pbd

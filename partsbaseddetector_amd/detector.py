@@ -212,6 +212,8 @@ class Handle:
         self.stride = self.lib.pbd_candidate_stride(self.h)
         self.max_parts = (self.stride - 8) // 4         # part boxes a record holds (pbd_candidate_stride)
         self.nms_overlap = None                          # the overlap of set_nms (None: off)
+        self._model_stale = False                        # set_model_vector* / set_thresh: `flat` is behind the handle
+        self._thresh = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -321,6 +323,42 @@ class Handle:
         w = np.zeros(self.lib.pbd_model_vector_len(self.h), self.dtype)
         self.check(self.lib.pbd_model_vector(self.h, w.ctypes.data))
         return w
+
+    def set_model_vector(self, w) -> None:
+        """pbd_set_model_vector: the handle's parameters become w (model_vector()'s order, rounded to T), in place: afterwards
+        the handle equals a new one created from Model.from_vector(w).  The resident detect result is dropped."""
+        w = np.ascontiguousarray(w, self.dtype).ravel()
+        n = self.lib.pbd_model_vector_len(self.h)
+        if len(w) != n:
+            raise PbdError(-1, f"model vector of {len(w)} values, this handle's has {n}")
+        self.check(self.lib.pbd_set_model_vector(self.h, w.ctypes.data))
+        self._model_stale = True
+
+    def set_model_vector_device(self, d_w_ptr: int, dtype) -> None:
+        """pbd_set_model_vector_device: the same from model_vector_len float32 / float64 values on the handle's device (the
+        caller orders their producer before stream_ptr()); nothing of the bank's size crosses to the host"""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise PbdError(-1, f"dtype {dt}: float32 or float64")
+        self.check(self.lib.pbd_set_model_vector_device(self.h, d_w_ptr, _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64))
+        self._model_stale = True
+
+    def set_thresh(self, thresh: float) -> None:
+        """pbd_set_thresh: the model's threshold for every later detect call"""
+        self.check(self.lib.pbd_set_thresh(self.h, float(thresh)))
+        self._thresh = float(np.float32(thresh))
+        self._model_stale = True
+
+    def current_model(self):
+        """the Model the handle holds now: the one it was created from, with the parameters of the last update (fetched from
+        the handle when asked, not at the update) and the last set_thresh"""
+        if self._model_stale:
+            m = self.flat.model.from_vector(self.model_vector())
+            if self._thresh is not None:
+                m.thresh = self._thresh
+            self.flat = m.flatten()
+            self._model_stale = False
+        return self.flat.model
 
     def example_stride(self):
         """pbd_example_stride: (int32 words of a header, values of T of an example)"""
@@ -919,6 +957,36 @@ class PartsBasedDetector:
             frames = [frames]
         rec, found = self.hd.detect_latent(list(frames), part_boxes, overlap, mixtures)
         return self.hd.unpack_candidates(rec.ravel(), len(rec)), found.astype(bool)
+
+    def updateModel(self, w_or_qp) -> None:
+        """model = vec2model(qp_w, model) in place (matlab/learning/train.m after qp_opt): the detector's parameters become a model
+        vector w (a numpy array in modelVector()'s order, or a torch tensor on the detector's device) or the weights of a training
+        QP (QP.apply: nothing passes through the host).  Afterwards the detector equals one given
+        distributeModel(model.from_vector(w)); model() returns that model."""
+        self._need()
+        from .qp import QP
+        if isinstance(w_or_qp, QP):
+            w_or_qp.apply(self.hd)
+            return
+        import torch
+        if isinstance(w_or_qp, torch.Tensor):
+            t = w_or_qp.contiguous()
+            if not t.is_cuda or t.dtype not in (torch.float32, torch.float64) or t.numel() != self.hd.lib.pbd_model_vector_len(self.hd.h):
+                raise PbdError(-1, "a float32 / float64 device tensor of model_vector_len values")
+            torch.cuda.current_stream(t.device).synchronize()
+            self.hd.set_model_vector_device(t.data_ptr(), np.float32 if t.dtype == torch.float32 else np.float64)
+            return
+        self.hd.set_model_vector(w_or_qp)
+
+    def setThreshold(self, thresh: float) -> None:
+        """model.thresh = thresh (train.m: the 5th percentile of qp_scorepos) for every later detect call"""
+        self._need()
+        self.hd.set_thresh(thresh)
+
+    def model(self) -> Model:
+        """the Model the detector holds now (after updateModel / setThreshold: the updated one)"""
+        self._need()
+        return self.hd.current_model()
 
     def qp(self, capacity: int, C: float = 0.002, wpos: float = 2.0, **kw):
         """a training QP (include/pbd.h pbd_qp_*) over a device-resident cache of `capacity` examples of this detector's model

@@ -520,6 +520,12 @@ class QP:
         self.check(self.lib.pbd_qp_weights(self.q, w.ctypes.data))
         return w
 
+    def apply(self, handle) -> None:
+        """pbd_qp_apply: the handle's parameters become weights() (rounded to its T), in place and on the device: afterwards the
+        handle equals a new one created from Model.from_vector(weights())"""
+        self.check(self.lib.pbd_qp_apply(self.q, handle.h))
+        handle._model_stale = True
+
     def scores(self) -> np.ndarray:
         """qp_scorepos: the raw scores of the cached positives, ascending cache index"""
         s = np.zeros(max(self.capacity, 1))
