@@ -679,7 +679,8 @@ def test_filter_shared_inside_a_component(det_mod, oracle, dtype):
 def test_image_depths_16u_32f_64f(det_mod, oracle, IT):
     """HOGFeatures::pyramid on the other depths it accepts (src/HOGFeatures.cpp:136-146: features<uint16_t|float|double>),
     for T = float and T = double, colour and grey: level images, features of every level and the end-to-end candidates
-    bit for bit against the oracle (the resampling of these depths is third-party arithmetic, restated: unpinned)."""
+    bit for bit against the oracle (the resampling of these depths is third-party arithmetic, restated; the oracle's is held to a
+    float64 statement of it in tests/test_oracle_cpu.py)."""
     from partsbaseddetector_amd import _lib
     rng = np.random.default_rng(11)
     for cn in (3, 1):

@@ -3,7 +3,8 @@
 The reference ships no golden vectors for this path and cannot be built here (SURVEY.md section 4 /
 8c: "parity unpinned"), so the restatement is cross-checked by code with a different structure:
 brute-force max-plus distance transform, scipy correlation, a scatter-form float64 HOG, an integer
-numpy pyrDown, and a brute-force tree max-sum for the dynamic program."""
+numpy pyrDown, and a brute-force tree max-sum for the dynamic program.  The HOG and resampling references and
+the frames they are run on live in tests/hog_hard_frames.py, shared with the GPU tests of the same kernels."""
 import numpy as np
 import pytest
 from scipy import signal
@@ -12,6 +13,7 @@ from partsbaseddetector_amd import model as M
 from partsbaseddetector_amd import synth
 
 import dt_hard_planes as H
+import hog_hard_frames as F
 
 
 # ---------------------------------------------------------------------------------- geometry
@@ -59,35 +61,6 @@ def test_resize_identity_and_bilinear(oracle):
     assert np.abs(out.astype(np.float64) - ref).max() <= 1.01
 
 
-def _resize_u8_numpy(im, dh, dw):
-    """SURVEY Appendix E's 8-bit INTER_LINEAR algorithm written again, vectorised and from the text alone (fixed point, 11
-    coefficient bits, horizontal pass in int, vertical pass ((b * (r >> 4)) >> 16 twice) + 2 >> 2) -- an independent statement
-    of the same published algorithm, not a second opinion on OpenCV itself (which nothing here can provide)."""
-    sh, sw = im.shape[:2]
-
-    def coef(dn, sn):
-        scale = 1.0 / (float(dn) / float(sn))
-        f = ((np.arange(dn, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
-        s0 = np.floor(f).astype(np.int64)
-        f = (f - s0.astype(np.float32)).astype(np.float32)
-        lo, hi = s0 < 0, s0 >= sn - 1
-        f = np.where(lo | hi, np.float32(0), f)
-        s0 = np.where(lo, 0, np.where(hi, sn - 1, s0))
-        a0 = np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int64)      # cvRound: half to even, as np.rint
-        a1 = np.rint(f * np.float32(2048)).astype(np.int64)
-        return s0, np.minimum(s0 + 1, sn - 1), a0, a1
-
-    if (dh, dw) == (sh, sw):
-        return im.copy()
-    sx0, sx1, a0, a1 = coef(dw, sw)
-    sy0, sy1, b0, b1 = coef(dh, sh)
-    S = im.astype(np.int64)
-    R = S[:, sx0] * a0[None, :, None] + S[:, sx1] * a1[None, :, None]              # every source row, horizontally
-    r0, r1 = R[sy0], R[sy1]
-    out = (((b0[:, None, None] * (r0 >> 4)) >> 16) + ((b1[:, None, None] * (r1 >> 4)) >> 16) + 2) >> 2
-    return out.astype(np.uint8)
-
-
 @pytest.mark.parametrize("shape,dst", [((61, 83), (44, 59)), ((61, 83), (58, 80)), ((97, 131), (49, 66)), ((240, 320), (224, 299)),
                                        ((50, 61), (37, 45))])
 @pytest.mark.parametrize("cn", [3, 1])
@@ -96,7 +69,7 @@ def test_resize_u8_against_an_independent_integer_formulation(oracle, shape, dst
     if im.ndim == 2:
         im = im[:, :, None]
     got = oracle.resize_linear_u8(im if cn == 3 else im[:, :, 0], dst[0], dst[1])
-    want = _resize_u8_numpy(im, dst[0], dst[1])
+    want = F.resize_u8_reference(im, dst[0], dst[1])
     assert np.array_equal(np.asarray(got).reshape(want.shape), want)
 
 
@@ -104,75 +77,15 @@ def test_pyrdown_integer_formulation(oracle):
     for shape, cn in [((37, 52), 3), ((40, 41), 1), ((5, 4), 3)]:
         im = synth.synthetic_frame(9, shape[0], shape[1], cn, kind="noise")
         got = oracle.pyrdown_u8(im)
-        pad = np.pad(im.astype(np.int64), ((2, 3), (2, 3), (0, 0)), mode="reflect")   # numpy reflect == REFLECT_101
-        k = np.array([1, 4, 6, 4, 1], np.int64)
-        dr, dc = (shape[0] + 1) // 2, (shape[1] + 1) // 2
-        acc = np.zeros((dr, dc, cn), np.int64)
-        for i in range(5):
-            for j in range(5):
-                acc += k[i] * k[j] * pad[i:i + 2 * dr:2, j:j + 2 * dc:2]
-        assert np.array_equal(got, ((acc + 128) >> 8).astype(np.uint8))
+        assert np.array_equal(got, F.pyrdown_reference(im))        # the padded form, tests/hog_hard_frames.py
 
 
 # ---------------------------------------------------------------------------------- HOG
-def _hog_scatter_f64(im, sbin=4):
-    """Scatter-form restatement in float64 following the published algorithm (matlab/mex/features.cc
-    as adapted by src/HOGFeatures.cpp); independent code, used only for a tolerance comparison."""
-    rows, cols, cn = im.shape
-    bh, bw = int(np.floor(rows / sbin + 0.5)), int(np.floor(cols / sbin + 0.5))
-    hist = np.zeros((bh, bw, 18))
-    uu = np.array([1.000, 0.9397, 0.7660, 0.5000, 0.1736, -0.1736, -0.5000, -0.7660, -0.9397])
-    vv = np.array([0.000, 0.3420, 0.6428, 0.8660, 0.9848, 0.9848, 0.8660, 0.6428, 0.3420])
-    f = im.astype(np.float64)
-    for y in range(1, bh * sbin - 1):
-        ys = min(y, rows - 2)
-        for x in range(1, bw * sbin - 1):
-            xs = min(x, cols - 2)
-            dy = f[ys + 1, xs] - f[ys - 1, xs]
-            dx = f[ys, xs + 1] - f[ys, xs - 1]
-            v = dx * dx + dy * dy
-            if cn == 3:
-                c = 2                     # start from channel 2, prefer 1, then 0 on strictly larger magnitude
-                if v[1] > v[c]: c = 1
-                if v[0] > v[c]: c = 0
-            else:
-                c = 0
-            dxc, dyc, vc = dx[c], dy[c], v[c]
-            dots = uu * dxc + vv * dyc
-            best, bo = 0.0, 0
-            for o in range(9):
-                if dots[o] > best: best, bo = dots[o], o
-                elif -dots[o] > best: best, bo = -dots[o], o + 9
-            yp, xp = (y + 0.5) / sbin - 0.5, (x + 0.5) / sbin - 0.5
-            iy, ix = int(np.floor(yp)), int(np.floor(xp))
-            vy0, vx0 = yp - iy, xp - ix
-            mag = np.sqrt(vc)
-            for (yy, wy) in ((iy, 1 - vy0), (iy + 1, vy0)):
-                for (xx, wx) in ((ix, 1 - vx0), (ix + 1, vx0)):
-                    if 0 <= yy < bh and 0 <= xx < bw:
-                        hist[yy, xx, bo] += wy * wx * mag
-    norm = ((hist[:, :, :9] + hist[:, :, 9:]) ** 2).sum(axis=2)
-    oh, ow = max(bh - 2, 0), max(bw - 2, 0)
-    feat = np.zeros((oh, ow, 32))
-    for y in range(oh):
-        for x in range(ow):
-            ns = []
-            for (yy, xx) in ((y + 1, x + 1), (y, x + 1), (y + 1, x), (y, x)):
-                ns.append(1.0 / np.sqrt(norm[yy, xx] + norm[yy, xx + 1] + norm[yy + 1, xx] + norm[yy + 1, xx + 1] + 1e-4))
-            h = hist[y + 1, x + 1]
-            hs = np.stack([np.minimum(h * n, 0.2) for n in ns])
-            feat[y, x, :18] = 0.5 * hs.sum(axis=0)
-            s = h[:9] + h[9:]
-            feat[y, x, 18:27] = 0.5 * np.stack([np.minimum(s * n, 0.2) for n in ns]).sum(axis=0)
-            feat[y, x, 27:31] = 0.2357 * hs.sum(axis=1)
-    return feat.reshape(oh, ow * 32)
-
-
 @pytest.mark.parametrize("shape,cn", [((50, 61), 3), ((47, 38), 1)])
 def test_hog_against_scatter_form(oracle, shape, cn):
     im = synth.synthetic_frame(2, shape[0], shape[1], cn)
     got = oracle.hog_features(im, 4)
-    ref = _hog_scatter_f64(im, 4)
+    ref, _ = F.hog_reference_f64(im, 4)
     assert got.shape == ref.shape
     assert np.abs(got.astype(np.float64) - ref).max() < 2e-5
     assert not got.reshape(got.shape[0], -1, 32)[:, :, 31].any()        # truncation channel is 0 (:338)
@@ -479,3 +392,192 @@ def test_float_resize_against_numpy(oracle):
                 r1 = np.float32(src[y1, sx, 0] * a0) + np.float32(src[y1, sx + 1, 0] * a1)
             want[dy, dx] = np.float32(r0 * b0) + np.float32(r1 * b1)
     assert np.array_equal(dst[:, :, 0], want)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the front end on hard frames: the oracle against tests/hog_hard_frames.py's float64 / integer references
+# (tests/test_gpu_feature_variants.py ties every kernel variant to the oracle bit for bit on the same frames)
+# ---------------------------------------------------------------------------------------------------
+HARD_SHAPE = (97, 131)            # odd, no multiple of any sbin used; 24 x 33 blocks at sbin 4, 12 x 16 at sbin 8
+GENUINE_SEED = 64                 # the genuine-range frames of this seed hold no pixel next to a bisector (asserted below)
+NEAR_TIE = 1e-6                   # relative float64 margin under which a float32 snap may choose the other orientation
+
+# Largest |oracle.hog_features - hog_reference_f64| over every frame of _hog_frames() (8-bit kinds, the same values stored as
+# uint16 / float32 / float64, the genuine-range frames), both channel counts, measured on the CPU, and the bar = 4 x measured.
+# The deviation is rounding accumulated over the 4 sbin^2 window terms (T = float: also the weights k / sbin, inexact in
+# float32 unless sbin is a power of two); 4 x leaves room for other seeds.  No number here comes from a GPU.
+#   (sbin, T):        measured     bar
+HOG_BARS = {
+    (2, "float32"): (8.26e-08, 3.3e-07), (2, "float64"): (1.67e-16, 6.7e-16),
+    (3, "float32"): (2.25e-06, 9.0e-06), (3, "float64"): (2.23e-16, 8.9e-16),
+    (4, "float32"): (1.03e-07, 4.1e-07), (4, "float64"): (2.23e-16, 8.9e-16),
+    (5, "float32"): (1.92e-06, 7.7e-06), (5, "float64"): (3.34e-16, 1.3e-15),
+    (6, "float32"): (1.02e-06, 4.1e-06), (6, "float64"): (2.78e-16, 1.1e-15),
+    (8, "float32"): (1.02e-07, 4.1e-07), (8, "float64"): (2.78e-16, 1.1e-15),
+}
+# Typed resize (16U / 32F / 64F): largest |oracle level - resize_linear_reference| over the resized levels, relative to the
+# frame's largest |pixel| (16U: in units, after the round; one unit is the bar), and 4 x that.  The float pyrDown, against
+# the float64 sum / 256, likewise (the taps are exact, the 24 additions round).  Every integer pyrDown is exact: no bar.
+#   dtype:            resize measured, bar      pyrDown measured, bar
+RESAMPLE_BARS = {
+    "uint16": (1, 1, 0, 0),
+    "float32": (1.15e-07, 4.6e-07, 1.53e-07, 6.1e-07),
+    "float64": (0.0, 0.0, 5.55e-16, 2.2e-15),          # the double resize is the reference's own sequence of operations: equal
+}
+
+_hog_ref_cache = {}
+
+
+def _hog_ref(key, im, sbin):
+    if (key, sbin) not in _hog_ref_cache:
+        _hog_ref_cache[key, sbin] = F.hog_reference_f64(im, sbin)
+    return _hog_ref_cache[key, sbin]
+
+
+def _hog_frames(cn):
+    """name -> (frame, genuine): the 8-bit kinds (near_bisector also as three 200 x 200 frames: the 3072 pairs with the smallest
+    margin), the scene and noise stored as the wider types, and the genuine-range frames"""
+    out = {name: (im, False) for name, im in F.frames_u8(40, *HARD_SHAPE, cn).items()}
+    for part in range(3):
+        out[f"near_bisector_200_{part}"] = (F.near_bisector(200, 200, cn, part), False)
+    for IT in (np.uint16, np.float32, np.float64):
+        for name in ("scene", "noise", "vertical"):
+            out[f"{name}_as_{IT.__name__}"] = (out[name][0].astype(IT), False)
+        for name, im in F.frames_genuine(IT, GENUINE_SEED, *HARD_SHAPE, cn).items():
+            out[f"{name}_{IT.__name__}"] = (im, True)
+    return out
+
+
+def hog_deviation(oracle, sbin, T, cn):
+    """largest deviation of the compared cells over _hog_frames(cn), per frame: {name: (deviation, cells left out, cells)}"""
+    res = {}
+    for name, (im, genuine) in _hog_frames(cn).items():
+        if name == "texture_float64" and T == np.float32:
+            continue        # by construction every gradient of it is within 2^-22 of an 8-bit one: all near-ties in float32
+        ref, margin = _hog_ref((name, cn), im, sbin)
+        got = oracle.hog_features(im, sbin, dtype=T)
+        assert got.dtype == T and got.shape == ref.shape, (name, got.shape, ref.shape)
+        d = np.abs(got.astype(np.float64) - ref).reshape(ref.shape[0], -1, 32).max(axis=2)
+        # integer gradients (every frame that is not `genuine`) need no exclusion, nor does T = double against float64
+        skip = F.cells_fed_by(margin, NEAR_TIE) if genuine and T == np.float32 else np.zeros(d.shape, bool)
+        res[name] = (float(d[~skip].max()) if (~skip).any() else 0.0, int(skip.sum()), int(skip.size))
+    return res
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+@pytest.mark.parametrize("sbin", F.SBINS)
+def test_hog_on_hard_frames_against_float64_reference(oracle, sbin, T, cn):
+    """oracle.hog_features at every bin size pbd_create accepts a model for, both real types, grey and colour, on the hard
+    frames: every cell within HOG_BARS of the float64 scatter form.  On integer gradients the float32 and the float64 snap
+    choose the same orientation (test_integer_gradients_snap_alike), so every cell is compared; on the genuine-range frames
+    a cell is left out for T = float only when a pixel feeding it lies within 1e-6 (relative) of a bisector, and at most
+    0.5 % of a frame's cells are."""
+    measured, bar = HOG_BARS[sbin, np.dtype(T).name]
+    assert bar <= 4.05 * measured
+    for name, (dev, left_out, cells) in hog_deviation(oracle, sbin, T, cn).items():
+        assert left_out <= 0.005 * cells, (name, left_out, cells)
+        assert dev <= bar, (name, dev, bar)
+
+
+def test_integer_gradients_snap_alike():
+    """All 261 121 8-bit gradient pairs: the float32 scan and the float64 scan choose the same orientation, and the only exact
+    ties are the 511 pairs with dx == 0 (dots 4 and 5; (0, 0) ties everything), which the strict `>` resolves to 4 / 13."""
+    dy, dx = np.mgrid[-255:256, -255:256]
+    dx, dy = dx.ravel(), dy.ravel()
+
+    def scan(R):
+        best, ori = np.zeros(dx.size, R), np.zeros(dx.size, np.int64)
+        for k in range(9):
+            dot = R(F.UU[k]) * dx.astype(R) + R(F.VV[k]) * dy.astype(R)
+            up, down = dot > best, ~(dot > best) & (-dot > best)
+            best = np.where(up, dot, np.where(down, -dot, best))
+            ori = np.where(up, k, np.where(down, k + 9, ori))
+        return ori
+
+    o32, o64 = scan(np.float32), scan(np.float64)
+    assert np.array_equal(o32, o64)
+    ori, best, gap = F.snap_f64(dx.astype(np.float64), dy.astype(np.float64))
+    assert np.array_equal(ori, o64)
+    assert np.array_equal(gap == 0, dx == 0) and np.count_nonzero(gap == 0) == 511
+    assert set(o64[(dx == 0) & (dy > 0)]) == {4} and set(o64[(dx == 0) & (dy < 0)]) == {13}
+
+
+def test_hard_frames_hold_what_they_are_for():
+    """the frames' own claims, so that a change to a builder cannot quietly empty a case"""
+    rows, cols = HARD_SHAPE
+    ext = F.extremes(rows, cols, 3)
+    assert set(np.unique(ext)) == {0, 255}
+    d = ext[1:-1, 2:].astype(int) - ext[1:-1, :-2]
+    assert (d == 255).any() and (d == -255).any() and (d == 0).any()
+    ver = F.vertical(3, rows, cols, 1)[:, :, 0].astype(int)
+    dx, dy = ver[1:-1, 2:] - ver[1:-1, :-2], ver[2:, 1:-1] - ver[:-2, 1:-1]
+    assert np.mean((dx == 0) & (dy != 0)) > 0.5 and ((dx == 0) & (dy > 0)).any() and ((dx == 0) & (dy < 0)).any()
+    tie = F.channel_ties(rows, cols).astype(int)
+    dx, dy = tie[1:-1, 2:] - tie[1:-1, :-2], tie[2:, 1:-1] - tie[:-2, 1:-1]
+    v = dx * dx + dy * dy
+    all3 = (v[:, :, 0] == v[:, :, 1]) & (v[:, :, 1] == v[:, :, 2]) & (v[:, :, 0] > 0)
+    assert all3.sum() >= 40 and len({(int(a), int(b)) for a, b in zip(dx[all3][:, 2], dy[all3][:, 2])}) >= 6
+    for hi, lo in ((2, 1), (2, 0), (1, 0), (1, 2), (0, 2), (0, 1)):          # two channels tie above the third, each way
+        other = 3 - hi - lo
+        assert ((v[:, :, hi] == v[:, :, other]) & (v[:, :, lo] < v[:, :, hi]) & (v[:, :, lo] > 0)).any() or \
+               ((v[:, :, hi] == v[:, :, lo]) & (v[:, :, other] < v[:, :, hi]) & (v[:, :, other] > 0)).any()
+    pairs = F.near_bisector_pairs()
+    assert (pairs[:510, 0] == 0).all() and (pairs[510:3072, 0] != 0).all()
+    nb = F.near_bisector(200, 200, 1, 1)[:, :, 0].astype(int)                # part 1: past the exact ties
+    dx, dy = nb[1:-1, 2:] - nb[1:-1, :-2], nb[2:, 1:-1] - nb[:-2, 1:-1]
+    _, best, gap = F.snap_f64(dx.astype(float), dy.astype(float))
+    centre = (dx != 0) & (dy != 0)
+    assert centre.sum() >= 1000 and np.sort(gap[centre] / best[centre])[999] < 1e-3
+    for IT in (np.float32, np.float64):
+        g = F.frames_genuine(IT, GENUINE_SEED, rows, cols, 3)
+        assert 0 <= g["unit"].min() and g["unit"].max() <= 1.001 and g["wide"].min() < -900 and g["wide"].max() > 900
+    g16 = F.frames_genuine(np.uint16, GENUINE_SEED, rows, cols, 3)["full"]
+    assert g16.min() == 0 and g16.max() == 65535
+
+
+def resample_deviation(oracle, im, exact_first=False):
+    """(resize deviation, pyrDown deviation) of oracle.pyramid_images(im, 4, 3) against the references, level by level; exact
+    comparisons are asserted here (exact_first: level 3, the pyrDown of the frame itself, of an 8-bit-valued float frame)"""
+    imgs, _ = oracle.pyramid_images(im, 4, 3)
+    assert len(imgs) > 3 and imgs[0].dtype == im.dtype
+    scale = 1.0 if im.dtype.kind == "u" else float(np.abs(im).max())
+    dev_r = dev_p = 0.0
+    for l, got in enumerate(imgs):
+        if l < 3:
+            if im.dtype == np.uint8:
+                assert np.array_equal(got, F.resize_u8_reference(im, *got.shape[:2])), l
+            elif l == 0:
+                assert np.array_equal(got, im)                           # the same size: the image itself
+            else:
+                ref = F.resize_linear_reference(im, *got.shape[:2])
+                dev_r = max(dev_r, float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max()) / scale)
+        else:
+            ref = F.pyrdown_reference(imgs[l - 3])
+            if im.dtype.kind == "u" or (exact_first and l == 3):
+                assert np.array_equal(got, ref), l
+            else:
+                dev_p = max(dev_p, float(np.abs(got.astype(np.float64) - ref).max()) / scale)
+    return dev_r, dev_p
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+@pytest.mark.parametrize("IT", [np.uint8, np.uint16, np.float32, np.float64])
+def test_pyramid_images_of_every_depth_against_the_references(oracle, IT, cn):
+    """oracle.pyramid_images, interval 3, one shape.  8U: resized levels and pyrDown levels integer-exact.  16U: pyrDown
+    integer-exact, resize within one unit of the float64 bilinear value rounded half to even.  32F / 64F: the pyrDown of an
+    8-bit-valued frame itself exactly (every sum and the final * 1/256 are exact); the pyrDown of resized levels and of
+    genuine-range frames, and the resize, within RESAMPLE_BARS."""
+    frames = F.frames_u8(40, *HARD_SHAPE, cn)
+    if IT == np.uint8:
+        for name, im in frames.items():
+            resample_deviation(oracle, im)
+        return
+    r_meas, r_bar, p_meas, p_bar = RESAMPLE_BARS[np.dtype(IT).name]
+    assert r_bar <= 4.05 * r_meas and p_bar <= 4.05 * p_meas
+    for name in ("scene", "noise", "extremes"):
+        dev_r, dev_p = resample_deviation(oracle, frames[name].astype(IT), exact_first=True)
+        assert dev_r <= r_bar and dev_p <= p_bar, (name, dev_r, dev_p)
+    for name, im in F.frames_genuine(IT, GENUINE_SEED, *HARD_SHAPE, cn).items():
+        dev_r, dev_p = resample_deviation(oracle, im)
+        assert dev_r <= r_bar and dev_p <= p_bar, (name, dev_r, dev_p)
