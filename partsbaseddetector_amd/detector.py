@@ -761,8 +761,8 @@ class DynamicProgram:
 
     def argmin(self, scales: np.ndarray, capacity: Optional[int] = None) -> List[Candidate]:
         """argmin(parts, rootv, rooti, scales, Ix, Iy, Ik, candidates) on the result of the last min()."""
-        cap = capacity or self.hd.max_candidates
-        buf = np.zeros(cap * self.hd.stride, np.int32)
+        cap = self.hd.max_candidates if capacity is None else capacity     # 0 is a capacity: nothing fits, PBD_ERR_CAPACITY
+        buf = np.zeros(max(cap, 1) * self.hd.stride, np.int32)
         n = C.c_int()
         sc = np.ascontiguousarray(scales, np.float32)
         self.hd.check(self.hd.lib.pbd_dp_argmin(self.hd.h, _lib.ptr(sc, C.c_float), buf.ctypes.data, cap, C.byref(n)))
