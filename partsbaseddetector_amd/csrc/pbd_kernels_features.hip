@@ -3,26 +3,168 @@
 // Replaces HOGFeatures<T>::pyramid / features<uint8_t> (reference src/HOGFeatures.cpp:95-341) for
 // T=float.  All arithmetic is ordered exactly as the reference's; the file is compiled with
 // -ffp-contract=off so no multiply-add is fused.
+//
+// Every per-pixel operation is stated once, as a device function; the kernels differ in how a thread finds its pixel
+// (Frames / Runs below), in how many pixels a lane takes and in where the results go.
 #include "pbd_internal.h"
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace pbd {
 
-// level containing flat element `idx` for the offsets selected by OFF (0 img, 1 blk, 2 cell)
+// ------------------------------------------------------------------------------------------------
+// Where a thread works.  The flat index of a launch runs over the elements (OFF: 0 image pixels, 1 blocks, 2 cells) of a
+// range of levels; the level comes from a search of the levels' offsets, (y, x) from the level's width.
+// ------------------------------------------------------------------------------------------------
 template <int OFF>
 __device__ __forceinline__ long long lv_off(const LevelDesc &d)
 {
     return OFF == 0 ? d.img_off : (OFF == 1 ? d.blk_off : d.cell_off);
 }
 template <int OFF>
-__device__ __forceinline__ int find_level(const LevelDesc *lv, int lo, int hi, long long idx)
-{   // largest l in [lo, hi) with off(l) <= idx  (offsets are non-decreasing)
+__device__ __forceinline__ int lv_width(const LevelDesc &d)
+{
+    return OFF == 0 ? d.img_cols : (OFF == 1 ? d.blk_cols : d.cols);
+}
+
+// largest i in [lo, hi) with off[i] <= idx  (offsets are non-decreasing)
+template <typename Off>
+__device__ __forceinline__ int last_not_above(int lo, int hi, long long idx, Off off)
+{
     while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (lv_off<OFF>(lv[mid]) <= idx) lo = mid; else hi = mid;
+        const int mid = (lo + hi) >> 1;
+        if (off(mid) <= idx) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// Block-cooperative search, every thread of the block must call it: the candidate offsets go to LDS in ONE memory round
+// trip and the search runs there.  (The per-thread search in global memory is six DEPENDENT loads -- ~4000 cycles before a
+// wave's first useful instruction -- and was what bounded these short kernels.)  A mixed-size call's virtual frame may hold
+// more levels, and its first launch more runs, than the LDS table: those search global memory (uniform branch).
+template <typename Off>
+__device__ __forceinline__ int last_not_above_blk(int lo, int hi, long long idx, Off off)
+{
+    __shared__ long long s_off[PBD_MAX_LEVELS];
+    if (hi > PBD_MAX_LEVELS) return last_not_above(lo, hi, idx, off);
+    for (int i = lo + (int)threadIdx.x; i < hi; i += (int)blockDim.x) s_off[i] = off(i);
+    __syncthreads();
+    return last_not_above(lo, hi, idx, [&](int i) { return s_off[i]; });
+}
+
+// level of [lo, hi) containing flat element `idx`
+template <int OFF>
+__device__ __forceinline__ int find_level_blk(const LevelDesc *lv, int lo, int hi, long long idx)
+{
+    return last_not_above_blk(lo, hi, idx, [&](int i) { return lv_off<OFF>(lv[i]); });
+}
+
+// the level's descriptor and the element's (y, x) inside it
+struct LevelCell {
+    LevelDesc d;
+    int y, x;
+};
+template <int OFF>
+__device__ __forceinline__ LevelCell level_cell(const LevelDesc *lv, int l, long long idx)
+{
+    LevelCell c;
+    c.d = lv[l];
+    const int local = (int)(idx - lv_off<OFF>(c.d));
+    c.y = local / lv_width<OFF>(c.d);
+    c.x = local - c.y * lv_width<OFF>(c.d);
+    return c;
+}
+
+// A pixel of a pyramid level under construction, and what it is computed from.
+struct SrcImage {               // a caller's frame or region: pitch in bytes
+    const uint8_t *base;
+    int rows, cols;
+    long long pitch;
+};
+template <typename PT> __device__ __forceinline__ const PT *src_row(const SrcImage &im, int y)
+{
+    return reinterpret_cast<const PT *>(im.base + (size_t)y * im.pitch);
+}
+template <typename PT>
+struct Site {
+    LevelDesc d;                // the level
+    int l, y, x;                // its index, the pixel inside it
+    PT *dst;                    // the pixel in the pyramid buffer
+    SrcImage src;               // resized levels: the image the level is sampled from
+    const PT *down;             // pyrDown levels: the image of the source level d.src_level, ...
+    int down_rows, down_cols;   // ... its size
+};
+
+// Equal-size calls: grid row = frame of the launch, flat index + base = pixel offset in the frame's pyramid, over the levels
+// [first, last); the source is the dense frame, a frame's pyramid starts at pixel frame * pix_per_frame.
+struct Frames {
+    int first, last;
+    long long base, npix;
+    __device__ __forceinline__ int search(const PyrParams &p, long long idx) const { return find_level_blk<0>(p.lv, first, last, idx + base); }
+    __device__ __forceinline__ int level(const PyrParams &, int k) const { return k; }
+    __device__ __forceinline__ int local(const PyrParams &, int, long long idx, const LevelDesc &d) const { return (int)(idx + base - d.img_off); }
+    __device__ __forceinline__ size_t pix0(const PyrParams &p) const { return (size_t)(p.frame0 + blockIdx.y) * p.pix_per_frame; }
+    __device__ __forceinline__ SrcImage source(const PyrParams &p, int, int px_bytes) const
+    {
+        return SrcImage{p.frames + (size_t)(p.frame0 + blockIdx.y) * p.rows * p.cols * px_bytes, p.rows, p.cols, (long long)p.cols * px_bytes};
+    }
+};
+
+// Mixed-size calls (pbd_detect_frames*): the levels of the virtual frame come from different source frames.  The launch's
+// levels are runs of the flat index (run k = level run_lev[k], pixels [run_off[k], run_off[k + 1])); a resized level reads
+// its own frame (pointer, size, pitch: FrameDesc), with the per-frame tables its LevelDesc points into; one pyramid.
+struct Runs {
+    long long npix;             // run_off[nruns]
+    __device__ __forceinline__ int search(const PyrParams &p, long long idx) const
+    {
+        return last_not_above_blk(0, p.nruns, idx, [&](int i) { return p.run_off[i]; });
+    }
+    __device__ __forceinline__ int level(const PyrParams &p, int k) const { return p.run_lev[k]; }
+    __device__ __forceinline__ int local(const PyrParams &p, int k, long long idx, const LevelDesc &) const { return (int)(idx - p.run_off[k]); }
+    __device__ __forceinline__ size_t pix0(const PyrParams &) const { return 0; }
+    __device__ __forceinline__ SrcImage source(const PyrParams &p, int l, int) const
+    {
+        const FrameDesc fr = p.fd[p.lv_frame[l]];
+        return SrcImage{fr.data, fr.rows, fr.cols, fr.pitch};
+    }
+};
+
+// the site of flat pixel idx in the search's result k (a level or a run) ...
+template <typename PT, typename Where>
+__device__ __forceinline__ void site_at(const PyrParams &p, const Where &w, int k, long long idx, Site<PT> &s)
+{
+    s.l = w.level(p, k);
+    s.d = p.lv[s.l];
+    const int local = w.local(p, k, idx, s.d);
+    s.y = local / s.d.img_cols; s.x = local - s.y * s.d.img_cols;
+    s.dst = reinterpret_cast<PT *>(p.pyr) + (w.pix0(p) + s.d.img_off + local) * p.cn;
+}
+// ... and of flat pixel idx, false past the launch's last pixel; every thread of the block must call it
+template <typename PT, typename Where>
+__device__ __forceinline__ bool locate(const PyrParams &p, const Where &w, long long idx, Site<PT> &s)
+{
+    const int k = w.search(p, idx);
+    if (idx >= w.npix) return false;
+    site_at(p, w, k, idx, s);
+    return true;
+}
+template <typename PT, typename Where>
+__device__ __forceinline__ void locate_down(const PyrParams &p, const Where &w, Site<PT> &s)
+{
+    const LevelDesc sd = p.lv[s.d.src_level];
+    s.down = reinterpret_cast<const PT *>(p.pyr) + (w.pix0(p) + sd.img_off) * p.cn;
+    s.down_rows = sd.img_rows; s.down_cols = sd.img_cols;
+}
+
+// depth code of an image -> its pixel type, as f(PT{})
+template <typename F> void for_depth(int depth, F &&f)
+{
+    if (depth == kDepth16U) f(uint16_t{});
+    else if (depth == kDepth32F) f(float{});
+    else if (depth == kDepth64F) f(double{});
+    else f(uint8_t{});
 }
 
 // The three bytes of a BGR pixel in one (unaligned) 32-bit load: byte loads cost a full memory instruction
@@ -33,105 +175,97 @@ __device__ __forceinline__ uint32_t load_px3(const uint8_t *q) { return *reinter
 __device__ __forceinline__ uint32_t load_px3_bytes(const uint8_t *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16); }
 __device__ __forceinline__ int px_ch(uint32_t v, int c) { return (int)((v >> (8 * c)) & 0xffu); }
 
-// Block-cooperative variant: the offsets of the candidate levels go to LDS in ONE memory round trip and the
-// search runs there.  (The per-thread search above is six DEPENDENT global loads -- ~4000 cycles before a wave's
-// first useful instruction -- and was what bounded these short kernels.)  Every thread of the block must call it.
-template <int OFF>
-__device__ __forceinline__ int find_level_blk(const LevelDesc *lv, int lo, int hi, long long idx, long long *s_off)
-{
-    // a mixed-size call's virtual frame may hold more levels than the LDS table: search global memory (uniform branch)
-    if (hi > PBD_MAX_LEVELS) return find_level<OFF>(lv, lo, hi, idx);
-    for (int i = lo + (int)threadIdx.x; i < hi; i += (int)blockDim.x) s_off[i] = lv_off<OFF>(lv[i]);
-    __syncthreads();
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (s_off[mid] <= idx) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// run of a mixed-size launch holding flat pixel `idx` (run_off non-decreasing, n runs); every thread of the block calls it
-__device__ __forceinline__ int find_run_blk(const long long *run_off, int n, long long idx, long long *s_off)
-{
-    int lo = 0, hi = n;
-    if (n <= PBD_MAX_LEVELS) {
-        for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) s_off[i] = run_off[i];
-        __syncthreads();
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= idx) lo = mid; else hi = mid; }
-        return lo;
-    }
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (run_off[mid] <= idx) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // ------------------------------------------------------------------------------------------------
 // cv::resize, INTER_LINEAR, 8-bit (call site src/HOGFeatures.cpp:116).  Coefficient tables are
 // built on the host (pbd_plan.cpp); here: horizontal pass in int, vertical pass
-// ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2 >> 2.  One thread per destination pixel.
+// ((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2 >> 2.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_resize(PyrParams p, long long npix)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, 0, p.interval, idx, s_off);
-    if (idx >= npix) return;
-    const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.img_off);
-    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
-    const ResizeTabX tx = p.tabx[d.tab_x + dx];
-    const ResizeTabY ty = p.taby[d.tab_y + dy];
-    const int cn = p.cn;
-    const uint8_t *src = p.frames + (size_t)frame * p.rows * p.cols * cn;
-    const uint8_t *S0 = src + (size_t)ty.y0 * p.cols * cn, *S1 = src + (size_t)ty.y1 * p.cols * cn;
-    const int sx = tx.sx, sx1 = sx + 1 < p.cols ? sx + 1 : sx;
-    uint8_t *D = p.pyr + ((size_t)frame * p.pix_per_frame + d.img_off + local) * cn;
-    if (cn == 3) {
-        // the last pixel of the caller's frame is read bytewise (no 4th byte to touch)
-        auto ld = [&](const uint8_t *row, int yy, int xx) {
-            return (yy == p.rows - 1 && xx == p.cols - 1) ? load_px3_bytes(row + xx * 3) : load_px3(row + xx * 3);
-        };
-        const uint32_t p00 = ld(S0, ty.y0, sx), p10 = ld(S1, ty.y1, sx), p01 = ld(S0, ty.y0, sx1), p11 = ld(S1, ty.y1, sx1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int r0 = px_ch(p00, c) * tx.a0 + px_ch(p01, c) * tx.a1;
-            const int r1 = px_ch(p10, c) * tx.a0 + px_ch(p11, c) * tx.a1;
-            D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-        }
-        return;
-    }
-    for (int c = 0; c < cn; ++c) {
-        const int r0 = S0[sx * cn + c] * tx.a0 + S0[sx1 * cn + c] * tx.a1;
-        const int r1 = S1[sx * cn + c] * tx.a0 + S1[sx1 * cn + c] * tx.a1;
-        D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-    }
+__device__ __forceinline__ int resize_fix(int s00, int s01, int s10, int s11, const ResizeTabX &tx, const ResizeTabY &ty)
+{   // one channel from its four taps s<row><column>
+    const int r0 = s00 * tx.a0 + s01 * tx.a1;
+    const int r1 = s10 * tx.a0 + s11 * tx.a1;
+    return (((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2;
 }
 
-// Four consecutive destination pixels per thread (8-bit BGR, the hot case): the 12 result bytes leave as three 4-byte
-// stores instead of twelve 1-byte ones and the row coefficients are fetched once.  Quads that run over the end of a
-// level row fall back to pixel-by-pixel byte stores.  Same arithmetic per pixel as k_resize.
-__device__ __forceinline__ uint32_t resize_px3(const PyrParams &p, const uint8_t *S0, const uint8_t *S1, const ResizeTabY &ty, const ResizeTabX &tx)
+// a packed BGR pixel; the last pixel of the source (frame or region) is read bytewise: its 4th byte may lie past the image
+// (S0, S1: its rows ty.y0, ty.y1; rows x cols: its size)
+__device__ __forceinline__ uint32_t resize_px3(const uint8_t *S0, const uint8_t *S1, int rows, int cols, const ResizeTabY &ty, const ResizeTabX &tx)
 {
-    auto ld = [&](const uint8_t *row, int yy, int xx) {     // the last pixel of the caller's frame is read bytewise
-        return (yy == p.rows - 1 && xx == p.cols - 1) ? load_px3_bytes(row + xx * 3) : load_px3(row + xx * 3);
+    auto ld = [&](const uint8_t *row, int yy, int xx) {
+        return (yy == rows - 1 && xx == cols - 1) ? load_px3_bytes(row + xx * 3) : load_px3(row + xx * 3);
     };
-    const int sx = tx.sx, sx1 = sx + 1 < p.cols ? sx + 1 : sx;
+    const int sx = tx.sx, sx1 = sx + 1 < cols ? sx + 1 : sx;
     const uint32_t p00 = ld(S0, ty.y0, sx), p10 = ld(S1, ty.y1, sx), p01 = ld(S0, ty.y0, sx1), p11 = ld(S1, ty.y1, sx1);
     uint32_t out = 0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int r0 = px_ch(p00, c) * tx.a0 + px_ch(p01, c) * tx.a1;
-        const int r1 = px_ch(p10, c) * tx.a0 + px_ch(p11, c) * tx.a1;
-        out |= (uint32_t)(uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2) << (8 * c);
-    }
+    for (int c = 0; c < 3; ++c)
+        out |= (uint32_t)(uint8_t)resize_fix(px_ch(p00, c), px_ch(p01, c), px_ch(p10, c), px_ch(p11, c), tx, ty) << (8 * c);
     return out;
 }
 
+// The other depths (16U, 32F, 64F): cv::resize keeps float coefficients and works in float (double for 64F);
+// D = S[sx]*a0 + S[sx+1]*a1 (exactly S[sx] at the last column), dst = cast(R0*b0 + R1*b1), cast = cvRound + clamp for
+// 16U (third-party arithmetic restated from OpenCV's generic code path; unpinned, as for 8-bit).
+template <typename PT> struct ResizeWork { typedef float type; };
+template <> struct ResizeWork<double> { typedef double type; };
+
+template <typename PT, typename WT> __device__ __forceinline__ PT resize_cast(WT v)
+{
+    if constexpr (std::is_same<PT, uint16_t>::value) {
+        const int iv = __float2int_rn(v);
+        return (uint16_t)(iv < 0 ? 0 : iv > 65535 ? 65535 : iv);
+    } else return v;
+}
+
+template <typename PT>
+__device__ __forceinline__ PT resize_typed(const PT *S0, const PT *S1, int cn, int c, const ResizeTabXf &tx, const ResizeTabYf &ty)
+{
+    typedef typename ResizeWork<PT>::type WT;
+    WT r0, r1;
+    if (tx.last) {
+        r0 = (WT)S0[tx.sx * cn + c] * (WT)1; r1 = (WT)S1[tx.sx * cn + c] * (WT)1;
+    } else {
+        r0 = (WT)S0[tx.sx * cn + c] * (WT)tx.a0 + (WT)S0[(tx.sx + 1) * cn + c] * (WT)tx.a1;
+        r1 = (WT)S1[tx.sx * cn + c] * (WT)tx.a0 + (WT)S1[(tx.sx + 1) * cn + c] * (WT)tx.a1;
+    }
+    return resize_cast<PT, WT>(r0 * (WT)ty.b0 + r1 * (WT)ty.b1);
+}
+
+// One thread per destination pixel of the resized levels.
+template <typename PT, typename Where>
+__global__ __launch_bounds__(256) void k_resize(PyrParams p, Where w)
+{
+    Site<PT> s;
+    if (!locate(p, w, (long long)blockIdx.x * blockDim.x + threadIdx.x, s)) return;
+    s.src = w.source(p, s.l, p.cn * (int)sizeof(PT));
+    const int cn = p.cn;
+    if constexpr (std::is_same<PT, uint8_t>::value) {
+        const ResizeTabX tx = p.tabx[s.d.tab_x + s.x];
+        const ResizeTabY ty = p.taby[s.d.tab_y + s.y];
+        const uint8_t *S0 = src_row<uint8_t>(s.src, ty.y0), *S1 = src_row<uint8_t>(s.src, ty.y1);
+        if (cn == 3) {
+            const uint32_t v = resize_px3(S0, S1, s.src.rows, s.src.cols, ty, tx);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s.dst[c] = (uint8_t)px_ch(v, c);
+            return;
+        }
+        const int sx = tx.sx * cn, sx1 = (tx.sx + 1 < s.src.cols ? tx.sx + 1 : tx.sx) * cn;
+        for (int c = 0; c < cn; ++c) s.dst[c] = (uint8_t)resize_fix(S0[sx + c], S0[sx1 + c], S1[sx + c], S1[sx1 + c], tx, ty);
+    } else {
+        const ResizeTabXf tx = p.tabxf[s.d.tab_x + s.x];
+        const ResizeTabYf ty = p.tabyf[s.d.tab_y + s.y];
+        const PT *S0 = src_row<PT>(s.src, ty.y0), *S1 = src_row<PT>(s.src, ty.y1);
+        for (int c = 0; c < cn; ++c) s.dst[c] = resize_typed<PT>(S0, S1, cn, c, tx, ty);
+    }
+}
+
+// Four consecutive destination pixels per thread (8-bit BGR frames of one size, the hot case): the 12 result bytes leave as
+// three 4-byte stores instead of twelve 1-byte ones and the row coefficients are fetched once.  Quads that run over the end
+// of a level row fall back to pixel-by-pixel byte stores.
 __global__ __launch_bounds__(256) void k_resize4(PyrParams p, long long npix)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
     const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const int l = find_level_blk<0>(p.lv, 0, p.interval, min(idx, npix - 1), s_off);
+    const int l = find_level_blk<0>(p.lv, 0, p.interval, min(idx, npix - 1));
     if (idx >= npix) return;
     const int frame = p.frame0 + blockIdx.y;
     const LevelDesc d = p.lv[l];
@@ -144,7 +278,7 @@ __global__ __launch_bounds__(256) void k_resize4(PyrParams p, long long npix)
         const uint8_t *S0 = src + (size_t)ty.y0 * p.cols * 3, *S1 = src + (size_t)ty.y1 * p.cols * 3;
         uint32_t q[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = resize_px3(p, S0, S1, ty, p.tabx[d.tab_x + dx + i]);
+        for (int i = 0; i < 4; ++i) q[i] = resize_px3(S0, S1, p.rows, p.cols, ty, p.tabx[d.tab_x + dx + i]);
         u32_unaligned *o = reinterpret_cast<u32_unaligned *>(D);
         o[0] = q[0] | (q[1] << 24);
         o[1] = (q[1] >> 8) | (q[2] << 16);
@@ -160,68 +294,34 @@ __global__ __launch_bounds__(256) void k_resize4(PyrParams p, long long npix)
         const int loc = (int)(pi - di.img_off);
         const int y = loc / di.img_cols, x = loc - y * di.img_cols;
         const ResizeTabY ty = p.taby[di.tab_y + y];
-        const uint32_t v = resize_px3(p, src + (size_t)ty.y0 * p.cols * 3, src + (size_t)ty.y1 * p.cols * 3, ty, p.tabx[di.tab_x + x]);
+        const uint32_t v = resize_px3(src + (size_t)ty.y0 * p.cols * 3, src + (size_t)ty.y1 * p.cols * 3, p.rows, p.cols, ty, p.tabx[di.tab_x + x]);
         D[3 * i] = (uint8_t)v; D[3 * i + 1] = (uint8_t)(v >> 8); D[3 * i + 2] = (uint8_t)(v >> 16);
-    }
-}
-
-// The other depths (16U, 32F, 64F): cv::resize keeps float coefficients and works in float (double for 64F);
-// D = S[sx]*a0 + S[sx+1]*a1 (exactly S[sx] at the last column), dst = cast(R0*b0 + R1*b1), cast = cvRound + clamp for
-// 16U (third-party arithmetic restated from OpenCV's generic code path; unpinned, as for 8-bit).
-template <typename PT, typename WT> __device__ __forceinline__ PT resize_cast(WT v);
-template <> __device__ __forceinline__ uint16_t resize_cast<uint16_t, float>(float v)
-{
-    const int iv = __float2int_rn(v);
-    return (uint16_t)(iv < 0 ? 0 : iv > 65535 ? 65535 : iv);
-}
-template <> __device__ __forceinline__ float resize_cast<float, float>(float v) { return v; }
-template <> __device__ __forceinline__ double resize_cast<double, double>(double v) { return v; }
-
-template <typename PT, typename WT>
-__global__ __launch_bounds__(256) void k_resize_t(PyrParams p, long long npix)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, 0, p.interval, idx, s_off);
-    if (idx >= npix) return;
-    const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.img_off);
-    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
-    const ResizeTabXf tx = p.tabxf[d.tab_x + dx];
-    const ResizeTabYf ty = p.tabyf[d.tab_y + dy];
-    const int cn = p.cn;
-    const PT *src = reinterpret_cast<const PT *>(p.frames) + (size_t)frame * p.rows * p.cols * cn;
-    const PT *S0 = src + (size_t)ty.y0 * p.cols * cn, *S1 = src + (size_t)ty.y1 * p.cols * cn;
-    PT *D = reinterpret_cast<PT *>(p.pyr) + ((size_t)frame * p.pix_per_frame + d.img_off + local) * cn;
-    for (int c = 0; c < cn; ++c) {
-        WT r0, r1;
-        if (tx.last) {
-            r0 = (WT)S0[tx.sx * cn + c] * (WT)1; r1 = (WT)S1[tx.sx * cn + c] * (WT)1;
-        } else {
-            r0 = (WT)S0[tx.sx * cn + c] * (WT)tx.a0 + (WT)S0[(tx.sx + 1) * cn + c] * (WT)tx.a1;
-            r1 = (WT)S1[tx.sx * cn + c] * (WT)tx.a0 + (WT)S1[(tx.sx + 1) * cn + c] * (WT)tx.a1;
-        }
-        D[c] = resize_cast<PT, WT>(r0 * (WT)ty.b0 + r1 * (WT)ty.b1);
     }
 }
 
 void launch_resize(const PyrParams &p, int nframes, long long npix, hipStream_t s)
 {
-    dim3 grid((unsigned)((npix + 255) / 256), nframes);
-    if (p.depth == kDepth16U) PBD_LAUNCH((k_resize_t<uint16_t, float>), grid, dim3(256), 0, s, p, npix);
-    else if (p.depth == kDepth32F) PBD_LAUNCH((k_resize_t<float, float>), grid, dim3(256), 0, s, p, npix);
-    else if (p.depth == kDepth64F) PBD_LAUNCH((k_resize_t<double, double>), grid, dim3(256), 0, s, p, npix);
-    else if (p.cn == 3) {
+    if (p.depth == kDepth8U && p.cn == 3) {
         dim3 grid4((unsigned)((npix + 1023) / 1024), nframes);
         PBD_LAUNCH(k_resize4, grid4, dim3(256), 0, s, p, npix);
-    } else PBD_LAUNCH(k_resize, grid, dim3(256), 0, s, p, npix);
+        return;
+    }
+    dim3 grid((unsigned)((npix + 255) / 256), nframes);
+    for_depth(p.depth, [&](auto t) { PBD_LAUNCH((k_resize<decltype(t), Frames>), grid, dim3(256), 0, s, p, Frames{0, p.interval, 0, npix}); });
+}
+
+void launch_resize_runs(const PyrParams &p, hipStream_t s)
+{
+    const long long npix = p.pix_per_frame;   // run_off[nruns] of this launch
+    if (p.nruns == 0 || npix == 0) return;
+    dim3 grid((unsigned)((npix + 255) / 256));
+    for_depth(p.depth, [&](auto t) { PBD_LAUNCH((k_resize<decltype(t), Runs>), grid, dim3(256), 0, s, p, Runs{npix}); });
 }
 
 // ------------------------------------------------------------------------------------------------
-// cv::pyrDown, 8-bit (call site src/HOGFeatures.cpp:122): [1 4 6 4 1] x [1 4 6 4 1],
-// BORDER_REFLECT_101, (sum + 128) >> 8.  One thread per destination pixel of the levels
-// [first_level, last_level), whose sources are the levels `interval` below.
+// cv::pyrDown (call site src/HOGFeatures.cpp:122): [1 4 6 4 1] x [1 4 6 4 1], BORDER_REFLECT_101.
+// 8U / 16U in int, (sum + 128) >> 8; 32F / 64F the same taps in the pixel type, row = s2*6 + (s1+s3)*4 + s0 + s4,
+// dst = (r2*6 + (r1+r3)*4 + r0 + r4) * (1/256).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -236,16 +336,74 @@ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 
-__global__ __launch_bounds__(256) void k_pyrdown(PyrParams p, int first_level, int last_level, long long base, long long npix)
+template <typename PT> struct PyrWork { typedef PT type; };
+template <> struct PyrWork<uint8_t> { typedef int type; };
+template <> struct PyrWork<uint16_t> { typedef int type; };
+template <typename F> __device__ __forceinline__ auto pyr_taps(F s) { return s(2) * 6 + (s(1) + s(3)) * 4 + s(0) + s(4); }   // s(i): tap i
+__device__ __forceinline__ int pyr_finish(int v) { return (v + 128) >> 8; }
+__device__ __forceinline__ float pyr_finish(float v) { return v * (1.f / 256.f); }
+__device__ __forceinline__ double pyr_finish(double v) { return v * (1. / 256.); }
+
+// destination pixel (y, x) from the source level image S (rows x cols x cn) into D
+template <typename PT>
+__device__ __forceinline__ void pyrdown_pixel(const PT *S, int rows, int cols, int cn, int y, int x, PT *D)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
+    typedef typename PyrWork<PT>::type WT;
+    int xs[5], ys[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        xs[k] = reflect101(2 * x - 2 + k, cols) * cn;
+        ys[k] = reflect101(2 * y - 2 + k, rows);
+    }
+    if constexpr (std::is_same<PT, uint8_t>::value) if (cn == 3) {
+        int r[5][3];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint8_t *R = S + (size_t)ys[k] * cols * 3;
+            uint32_t q[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) q[i] = load_px3(R + xs[i]);      // source levels live in the pyramid buffer (slack at its end)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[k][c] = pyr_taps([&](int i) { return px_ch(q[i], c); });
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) D[c] = (uint8_t)pyr_finish(pyr_taps([&](int k) { return r[k][c]; }));
+        return;
+    }
+    for (int c = 0; c < cn; ++c) {
+        WT r[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const PT *R = S + (size_t)ys[k] * cols * cn + c;
+            r[k] = pyr_taps([&](int i) { return (WT)R[xs[i]]; });
+        }
+        D[c] = (PT)pyr_finish(pyr_taps([&](int k) { return r[k]; }));
+    }
+}
+
+// One thread per destination pixel of the launch's levels, whose sources are the levels `interval` below.
+template <typename PT, typename Where>
+__global__ __launch_bounds__(256) void k_pyrdown(PyrParams p, Where w)
+{
+    Site<PT> s;
+    if (!locate(p, w, (long long)blockIdx.x * blockDim.x + threadIdx.x, s)) return;
+    locate_down(p, w, s);
+    pyrdown_pixel<PT>(s.down, s.down_rows, s.down_cols, p.cn, s.y, s.x, s.dst);
+}
+
+// The hot instantiation (8-bit frames of one size) keeps its body written out, with the shared taps and finish: through the Site
+// and pyrdown_pixel the same statements compile to other instructions (four more SGPRs, byte extracts for sub-dword selects)
+// and the kernel runs 2 % slower (profiles/refactor_features/README.md).
+template <>
+__global__ __launch_bounds__(256) void k_pyrdown<uint8_t, Frames>(PyrParams p, Frames w)
+{
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, first_level, last_level, idx + base, s_off);
-    if (idx >= npix) return;
+    const int l = find_level_blk<0>(p.lv, w.first, w.last, idx + w.base);
+    if (idx >= w.npix) return;
     const int frame = p.frame0 + blockIdx.y;
     const LevelDesc d = p.lv[l];
     const LevelDesc sd = p.lv[d.src_level];
-    const int local = (int)(idx + base - d.img_off);
+    const int local = (int)(idx + w.base - d.img_off);
     const int y = local / d.img_cols, x = local - y * d.img_cols;
     const int cn = p.cn;
     const uint8_t *S = p.pyr + ((size_t)frame * p.pix_per_frame + sd.img_off) * cn;
@@ -265,11 +423,10 @@ __global__ __launch_bounds__(256) void k_pyrdown(PyrParams p, int first_level, i
 #pragma unroll
             for (int i = 0; i < 5; ++i) q[i] = load_px3(R + xs[i]);      // source levels live in the pyramid buffer (slack at its end)
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-                r[k][c] = px_ch(q[2], c) * 6 + (px_ch(q[1], c) + px_ch(q[3], c)) * 4 + px_ch(q[0], c) + px_ch(q[4], c);
+            for (int c = 0; c < 3; ++c) r[k][c] = pyr_taps([&](int i) { return px_ch(q[i], c); });
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) D[c] = (uint8_t)((r[2][c] * 6 + (r[1][c] + r[3][c]) * 4 + r[0][c] + r[4][c] + 128) >> 8);
+        for (int c = 0; c < 3; ++c) D[c] = (uint8_t)pyr_finish(pyr_taps([&](int k) { return r[k][c]; }));
         return;
     }
     for (int c = 0; c < cn; ++c) {
@@ -277,48 +434,9 @@ __global__ __launch_bounds__(256) void k_pyrdown(PyrParams p, int first_level, i
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const uint8_t *R = S + (size_t)ys[k] * sd.img_cols * cn + c;
-            r[k] = R[xs[2]] * 6 + (R[xs[1]] + R[xs[3]]) * 4 + R[xs[0]] + R[xs[4]];
+            r[k] = pyr_taps([&](int i) { return (int)R[xs[i]]; });
         }
-        D[c] = (uint8_t)((r[2] * 6 + (r[1] + r[3]) * 4 + r[0] + r[4] + 128) >> 8);
-    }
-}
-
-// The other depths: 16U integer as 8-bit; 32F / 64F the same taps in the pixel type, row = s2*6 + (s1+s3)*4 + s0 + s4,
-// dst = (r2*6 + (r1+r3)*4 + r0 + r4) * (1/256).
-template <typename PT, typename WT> __device__ __forceinline__ PT pyr_finish(WT v);
-template <> __device__ __forceinline__ uint16_t pyr_finish<uint16_t, int>(int v) { return (uint16_t)((v + 128) >> 8); }
-template <> __device__ __forceinline__ float pyr_finish<float, float>(float v) { return v * (1.f / 256.f); }
-template <> __device__ __forceinline__ double pyr_finish<double, double>(double v) { return v * (1. / 256.); }
-
-template <typename PT, typename WT>
-__global__ __launch_bounds__(256) void k_pyrdown_t(PyrParams p, int first_level, int last_level, long long base, long long npix)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, first_level, last_level, idx + base, s_off);
-    if (idx >= npix) return;
-    const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const LevelDesc sd = p.lv[d.src_level];
-    const int local = (int)(idx + base - d.img_off);
-    const int y = local / d.img_cols, x = local - y * d.img_cols;
-    const int cn = p.cn;
-    const PT *S = reinterpret_cast<const PT *>(p.pyr) + ((size_t)frame * p.pix_per_frame + sd.img_off) * cn;
-    PT *D = reinterpret_cast<PT *>(p.pyr) + ((size_t)frame * p.pix_per_frame + d.img_off + local) * cn;
-    int xs[5], ys[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        xs[k] = reflect101(2 * x - 2 + k, sd.img_cols) * cn;
-        ys[k] = reflect101(2 * y - 2 + k, sd.img_rows);
-    }
-    for (int c = 0; c < cn; ++c) {
-        WT r[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const PT *R = S + (size_t)ys[k] * sd.img_cols * cn + c;
-            r[k] = (WT)R[xs[2]] * 6 + ((WT)R[xs[1]] + (WT)R[xs[3]]) * 4 + (WT)R[xs[0]] + (WT)R[xs[4]];
-        }
-        D[c] = pyr_finish<PT, WT>(r[2] * 6 + (r[1] + r[3]) * 4 + r[0] + r[4]);
+        D[c] = (uint8_t)pyr_finish(pyr_taps([&](int k) { return r[k]; }));
     }
 }
 
@@ -326,131 +444,8 @@ void launch_pyrdown_range(const PyrParams &p, int nframes, int first_level, int 
                           long long npix, hipStream_t s)
 {
     dim3 grid((unsigned)((npix + 255) / 256), nframes);
-    if (p.depth == kDepth16U) PBD_LAUNCH((k_pyrdown_t<uint16_t, int>), grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
-    else if (p.depth == kDepth32F) PBD_LAUNCH((k_pyrdown_t<float, float>), grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
-    else if (p.depth == kDepth64F) PBD_LAUNCH((k_pyrdown_t<double, double>), grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
-    else PBD_LAUNCH(k_pyrdown, grid, dim3(256), 0, s, p, first_level, last_level, base, npix);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Mixed-size calls (pbd_detect_frames*): the levels of the virtual frame come from different source frames.  One thread per
-// destination pixel of the launch's runs (run = one level); a resized level reads its own frame (pointer, size, pitch:
-// FrameDesc), with the per-frame tables its LevelDesc points into.  Same arithmetic per pixel as k_resize / k_resize_t /
-// k_pyrdown / k_pyrdown_t.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_resize_runs(PyrParams p)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long npix = p.run_off[p.nruns];
-    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
-    if (idx >= npix) return;
-    const int l = p.run_lev[r];
-    const LevelDesc d = p.lv[l];
-    const FrameDesc fr = p.fd[p.lv_frame[l]];
-    const int local = (int)(idx - p.run_off[r]);
-    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
-    const ResizeTabX tx = p.tabx[d.tab_x + dx];
-    const ResizeTabY ty = p.taby[d.tab_y + dy];
-    const int cn = p.cn;
-    const uint8_t *S0 = fr.data + (size_t)ty.y0 * fr.pitch, *S1 = fr.data + (size_t)ty.y1 * fr.pitch;
-    const int sx = tx.sx, sx1 = sx + 1 < fr.cols ? sx + 1 : sx;
-    uint8_t *D = p.pyr + (d.img_off + local) * cn;
-    if (cn == 3) {
-        // the last pixel of every frame (region) is read bytewise: its 4th byte may lie past the caller's image
-        auto ld = [&](const uint8_t *row, int yy, int xx) {
-            return (yy == fr.rows - 1 && xx == fr.cols - 1) ? load_px3_bytes(row + xx * 3) : load_px3(row + xx * 3);
-        };
-        const uint32_t p00 = ld(S0, ty.y0, sx), p10 = ld(S1, ty.y1, sx), p01 = ld(S0, ty.y0, sx1), p11 = ld(S1, ty.y1, sx1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int r0 = px_ch(p00, c) * tx.a0 + px_ch(p01, c) * tx.a1;
-            const int r1 = px_ch(p10, c) * tx.a0 + px_ch(p11, c) * tx.a1;
-            D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-        }
-        return;
-    }
-    for (int c = 0; c < cn; ++c) {
-        const int r0 = S0[sx * cn + c] * tx.a0 + S0[sx1 * cn + c] * tx.a1;
-        const int r1 = S1[sx * cn + c] * tx.a0 + S1[sx1 * cn + c] * tx.a1;
-        D[c] = (uint8_t)((((ty.b0 * (r0 >> 4)) >> 16) + ((ty.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-    }
-}
-
-template <typename PT, typename WT>
-__global__ __launch_bounds__(256) void k_resize_runs_t(PyrParams p)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long npix = p.run_off[p.nruns];
-    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
-    if (idx >= npix) return;
-    const int l = p.run_lev[r];
-    const LevelDesc d = p.lv[l];
-    const FrameDesc fr = p.fd[p.lv_frame[l]];
-    const int local = (int)(idx - p.run_off[r]);
-    const int dy = local / d.img_cols, dx = local - dy * d.img_cols;
-    const ResizeTabXf tx = p.tabxf[d.tab_x + dx];
-    const ResizeTabYf ty = p.tabyf[d.tab_y + dy];
-    const int cn = p.cn;
-    const PT *S0 = reinterpret_cast<const PT *>(fr.data + (size_t)ty.y0 * fr.pitch);
-    const PT *S1 = reinterpret_cast<const PT *>(fr.data + (size_t)ty.y1 * fr.pitch);
-    PT *D = reinterpret_cast<PT *>(p.pyr) + (d.img_off + local) * cn;
-    for (int c = 0; c < cn; ++c) {
-        WT r0, r1;
-        if (tx.last) {
-            r0 = (WT)S0[tx.sx * cn + c] * (WT)1; r1 = (WT)S1[tx.sx * cn + c] * (WT)1;
-        } else {
-            r0 = (WT)S0[tx.sx * cn + c] * (WT)tx.a0 + (WT)S0[(tx.sx + 1) * cn + c] * (WT)tx.a1;
-            r1 = (WT)S1[tx.sx * cn + c] * (WT)tx.a0 + (WT)S1[(tx.sx + 1) * cn + c] * (WT)tx.a1;
-        }
-        D[c] = resize_cast<PT, WT>(r0 * (WT)ty.b0 + r1 * (WT)ty.b1);
-    }
-}
-
-void launch_resize_runs(const PyrParams &p, hipStream_t s)
-{
-    const long long npix = p.pix_per_frame;   // run_off[nruns] of this launch
-    if (p.nruns == 0 || npix == 0) return;
-    dim3 grid((unsigned)((npix + 255) / 256));
-    if (p.depth == kDepth16U) PBD_LAUNCH((k_resize_runs_t<uint16_t, float>), grid, dim3(256), 0, s, p);
-    else if (p.depth == kDepth32F) PBD_LAUNCH((k_resize_runs_t<float, float>), grid, dim3(256), 0, s, p);
-    else if (p.depth == kDepth64F) PBD_LAUNCH((k_resize_runs_t<double, double>), grid, dim3(256), 0, s, p);
-    else PBD_LAUNCH(k_resize_runs, grid, dim3(256), 0, s, p);
-}
-
-template <typename PT, typename WT, bool kInt>
-__global__ __launch_bounds__(256) void k_pyrdown_runs(PyrParams p)
-{
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long npix = p.run_off[p.nruns];
-    const int r = find_run_blk(p.run_off, p.nruns, min(idx, npix - 1), s_off);
-    if (idx >= npix) return;
-    const LevelDesc d = p.lv[p.run_lev[r]];
-    const LevelDesc sd = p.lv[d.src_level];
-    const int local = (int)(idx - p.run_off[r]);
-    const int y = local / d.img_cols, x = local - y * d.img_cols;
-    const int cn = p.cn;
-    const PT *S = reinterpret_cast<const PT *>(p.pyr) + sd.img_off * cn;
-    PT *D = reinterpret_cast<PT *>(p.pyr) + (d.img_off + local) * cn;
-    int xs[5], ys[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        xs[k] = reflect101(2 * x - 2 + k, sd.img_cols) * cn;
-        ys[k] = reflect101(2 * y - 2 + k, sd.img_rows);
-    }
-    for (int c = 0; c < cn; ++c) {
-        WT rr[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const PT *R = S + (size_t)ys[k] * sd.img_cols * cn + c;
-            rr[k] = (WT)R[xs[2]] * 6 + ((WT)R[xs[1]] + (WT)R[xs[3]]) * 4 + (WT)R[xs[0]] + (WT)R[xs[4]];
-        }
-        const WT v = rr[2] * 6 + (rr[1] + rr[3]) * 4 + rr[0] + rr[4];
-        if constexpr (kInt) D[c] = (PT)((v + 128) >> 8);        // 8U / 16U: (sum + 128) >> 8
-        else D[c] = pyr_finish<PT, WT>(v);
-    }
+    const Frames w{first_level, last_level, base, npix};
+    for_depth(p.depth, [&](auto t) { PBD_LAUNCH((k_pyrdown<decltype(t), Frames>), grid, dim3(256), 0, s, p, w); });
 }
 
 void launch_pyrdown_runs(const PyrParams &p, hipStream_t s)
@@ -458,100 +453,43 @@ void launch_pyrdown_runs(const PyrParams &p, hipStream_t s)
     const long long npix = p.pix_per_frame;   // run_off[nruns] of this launch
     if (p.nruns == 0 || npix == 0) return;
     dim3 grid((unsigned)((npix + 255) / 256));
-    if (p.depth == kDepth16U) PBD_LAUNCH((k_pyrdown_runs<uint16_t, int, true>), grid, dim3(256), 0, s, p);
-    else if (p.depth == kDepth32F) PBD_LAUNCH((k_pyrdown_runs<float, float, false>), grid, dim3(256), 0, s, p);
-    else if (p.depth == kDepth64F) PBD_LAUNCH((k_pyrdown_runs<double, double, false>), grid, dim3(256), 0, s, p);
-    else PBD_LAUNCH((k_pyrdown_runs<uint8_t, int, true>), grid, dim3(256), 0, s, p);
+    for_depth(p.depth, [&](auto t) { PBD_LAUNCH((k_pyrdown<decltype(t), Runs>), grid, dim3(256), 0, s, p, Runs{npix}); });
 }
 
 // ------------------------------------------------------------------------------------------------
-// HOG cell histograms, gather form (R = reference template parameter T).  One thread per block (cell of
-// the `blocks` grid): it walks the source pixels that the reference's scatter loop
-// (src/HOGFeatures.cpp:202-267) adds into this block, in the same raster order, so every bin sees the
-// same sequence of additions.  Bins are 18 registers; the selected bin is updated through predicated
-// adds of +0, which leave a non-negative sum unchanged.  Also writes the block energy (:270-283).
+// HOG gradients: per image pixel, the snapped orientation (0..17) and the gradient magnitude of the strongest
+// colour channel (src/HOGFeatures.cpp:205-260; R = reference template parameter T).
 // ------------------------------------------------------------------------------------------------
 template <typename R> __device__ __forceinline__ R real_sqrt(R v);
 template <> __device__ __forceinline__ float real_sqrt<float>(float v) { return sqrtf(v); }
 template <> __device__ __forceinline__ double real_sqrt<double>(double v) { return sqrt(v); }
 
-// Pass 1: per image pixel, the snapped orientation (0..17) and the gradient magnitude of the strongest
-// colour channel (src/HOGFeatures.cpp:205-260).  Every pixel feeds four blocks, so this part is done once
-// per pixel instead of once per (pixel, block).
-template <typename R>
-__global__ __launch_bounds__(256) void k_hog_grad(HogParams p)
+// The difference of two pixels is taken in the pixel type (integers promote to int, float / double subtract as such) and
+// then converted to T (features<uint8_t|uint16_t|float|double>, src/HOGFeatures.cpp:136-146).
+template <typename R, typename PT> __device__ __forceinline__ R pix_diff(PT a, PT b)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, 0, p.nlevels, idx, s_off);
-    if (idx >= p.pix_per_frame) return;
-    const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.img_off);
-    const int rows = d.img_rows, cols = d.img_cols;
-    const int ys = local / cols, xs = local - ys * cols;
-    const size_t o = (size_t)frame * p.pix_per_frame + idx;
-    if (xs < 1 || ys < 1 || xs > cols - 2 || ys > rows - 2) return;     // never sampled (clamped to cols-2 / rows-2)
-    const int cn = p.cn;
-    const uint8_t *im = p.pyr + ((size_t)frame * p.pix_per_frame + d.img_off) * cn;
-    const size_t stride = (size_t)cols * cn;
-    const R uu[9] = {(R)1.000, (R)0.9397, (R)0.7660, (R)0.5000, (R)0.1736, (R)-0.1736, (R)-0.5000, (R)-0.7660, (R)-0.9397};
-    const R vv[9] = {(R)0.000, (R)0.3420, (R)0.6428, (R)0.8660, (R)0.9848, (R)0.9848, (R)0.8660, (R)0.6428, (R)0.3420};
-    R dx, dy, v;
-    if (cn == 1) {
-        const uint8_t *s = im + xs + (size_t)ys * stride;
-        dy = (R)((int)s[stride] - (int)*(s - stride));
-        dx = (R)((int)s[1] - (int)s[-1]);
-        v = dx * dx + dy * dy;
-    } else {
-        const uint8_t *s = im + 3 * xs + (size_t)ys * stride;
-        const uint32_t pd = load_px3(s + stride), pu = load_px3(s - stride), pr = load_px3(s + 3), pl = load_px3(s - 3);
-        const R dyb = (R)(px_ch(pd, 0) - px_ch(pu, 0));
-        const R dxb = (R)(px_ch(pr, 0) - px_ch(pl, 0));
-        const R vb = dxb * dxb + dyb * dyb;
-        const R dyg = (R)(px_ch(pd, 1) - px_ch(pu, 1));
-        const R dxg = (R)(px_ch(pr, 1) - px_ch(pl, 1));
-        const R vg = dxg * dxg + dyg * dyg;
-        dy = (R)(px_ch(pd, 2) - px_ch(pu, 2));
-        dx = (R)(px_ch(pr, 2) - px_ch(pl, 2));
-        v = dx * dx + dy * dy;
-        if (vg > v) { v = vg; dx = dxg; dy = dyg; }
-        if (vb > v) { v = vb; dx = dxb; dy = dyb; }
-    }
-    R best_dot = (R)0;
-    int best_o = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const R dot = uu[k] * dx + vv[k] * dy;
-        if (dot > best_dot) { best_dot = dot; best_o = k; }
-        else if (-dot > best_dot) { best_dot = -dot; best_o = k + 9; }
-    }
-    static_cast<R *>(p.gmag)[o] = real_sqrt<R>(v);
-    p.gori[o] = (uint8_t)best_o;
+    if constexpr (std::is_integral<PT>::value) return (R)((int)a - (int)b);
+    else return (R)(a - b);
 }
 
-// Four consecutive pixels per thread (8-bit BGR, the hot case): when the four share an image row and are all interior,
-// the rows above / below come in as one 16-byte load each and the row itself as 16 + 4 bytes (10 memory instructions
-// per four pixels instead of 24), the results leave as one 16-byte and one 4-byte store.  Same arithmetic per pixel.
-typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ int px_byte(const u32x4_u &v, uint32_t extra, int b)
-{   // byte b (compile-time) of the 20 bytes {v, extra}
-    const uint32_t w = b < 16 ? v[b >> 2] : extra;
-    return (int)((w >> (8 * (b & 3))) & 0xffu);
-}
-
+// src/HOGFeatures.cpp:217-237: the strongest channel, third channel first, then G, then B, each only on strictly larger
 template <typename R>
-__device__ __forceinline__ void hog_grad_pixel(R dxb, R dyb, R dxg, R dyg, R dxr, R dyr, R &mag, int &ori)
-{   // src/HOGFeatures.cpp:217-260: strongest channel (third channel first, then G, then B), 18-way orientation snap
-    const R uu[9] = {(R)1.000, (R)0.9397, (R)0.7660, (R)0.5000, (R)0.1736, (R)-0.1736, (R)-0.5000, (R)-0.7660, (R)-0.9397};
-    const R vv[9] = {(R)0.000, (R)0.3420, (R)0.6428, (R)0.8660, (R)0.9848, (R)0.9848, (R)0.8660, (R)0.6428, (R)0.3420};
+__device__ __forceinline__ void hog_pick(R dxb, R dyb, R dxg, R dyg, R dxr, R dyr, R &dx, R &dy, R &v)
+{
     const R vb = dxb * dxb + dyb * dyb;
     const R vg = dxg * dxg + dyg * dyg;
-    R dx = dxr, dy = dyr;
-    R v = dx * dx + dy * dy;
+    dx = dxr; dy = dyr;
+    v = dx * dx + dy * dy;
     if (vg > v) { v = vg; dx = dxg; dy = dyg; }
     if (vb > v) { v = vb; dx = dxb; dy = dyb; }
+}
+
+// src/HOGFeatures.cpp:239-250: 18-way orientation snap
+template <typename R>
+__device__ __forceinline__ int hog_snap(R dx, R dy)
+{
+    const R uu[9] = {(R)1.000, (R)0.9397, (R)0.7660, (R)0.5000, (R)0.1736, (R)-0.1736, (R)-0.5000, (R)-0.7660, (R)-0.9397};
+    const R vv[9] = {(R)0.000, (R)0.3420, (R)0.6428, (R)0.8660, (R)0.9848, (R)0.9848, (R)0.8660, (R)0.6428, (R)0.3420};
     // The reference's scan, k ascending: "if (dot > best) {best = dot; o = k} else if (-dot > best) {best = -dot; o = k + 9}".
     // best is never negative, so at most one of the two tests can pass and the pair is "|dot| > best" with the sign of dot
     // choosing k or k + 9 (a NaN fails every test in both forms).  The tables are antisymmetric / symmetric about k = 4.5
@@ -586,46 +524,113 @@ __device__ __forceinline__ void hog_grad_pixel(R dxb, R dyb, R dxg, R dyg, R dxr
             if (ad > best_dot) { best_dot = ad; best_o = dot < (R)0 ? k + 9 : k; }
         }
     }
-    mag = real_sqrt<R>(v);
-    ori = best_o;
+    return best_o;
 }
 
-__global__ __launch_bounds__(256) void k_hog_grad4(HogParams p)
+template <typename R>
+__device__ __forceinline__ void hog_grad_pixel(R dxb, R dyb, R dxg, R dyg, R dxr, R dyr, R &mag, int &ori)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    const int l = find_level_blk<0>(p.lv, 0, p.nlevels, min(idx, p.pix_per_frame - 1), s_off);
+    R dx, dy, v;
+    hog_pick<R>(dxb, dyb, dxg, dyg, dxr, dyr, dx, dy, v);
+    ori = hog_snap<R>(dx, dy);
+    mag = real_sqrt<R>(v);
+}
+
+// interior pixel s of a three-channel image (stride elements per row); 8-bit pixels come in as one 32-bit load each
+template <typename R, typename PT>
+__device__ __forceinline__ void hog_grad_px3(const PT *s, size_t stride, R &mag, int &ori)
+{
+    R dx[3], dy[3];
+    if constexpr (std::is_same<PT, uint8_t>::value) {
+        const uint32_t pd = load_px3(s + stride), pu = load_px3(s - stride), pr = load_px3(s + 3), pl = load_px3(s - 3);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { dx[c] = (R)(px_ch(pr, c) - px_ch(pl, c)); dy[c] = (R)(px_ch(pd, c) - px_ch(pu, c)); }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { dx[c] = pix_diff<R, PT>(s[3 + c], *(s - 3 + c)); dy[c] = pix_diff<R, PT>(s[c + stride], *(s + c - stride)); }
+    }
+    hog_grad_pixel<R>(dx[0], dy[0], dx[1], dy[1], dx[2], dy[2], mag, ori);
+}
+
+// Pass 1 of the two-pass form, one thread per image pixel.  Every pixel feeds four blocks, so this part is done once
+// per pixel instead of once per (pixel, block).
+template <typename R, typename PT>
+__global__ __launch_bounds__(256) void k_hog_grad(HogParams p)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int l = find_level_blk<0>(p.lv, 0, p.nlevels, idx);
     if (idx >= p.pix_per_frame) return;
     const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.img_off);
-    const int rows = d.img_rows, cols = d.img_cols;
-    const int ys = local / cols, xs = local - ys * cols;
+    const LevelCell c = level_cell<0>(p.lv, l, idx);
+    const int rows = c.d.img_rows, cols = c.d.img_cols, ys = c.y, xs = c.x;
+    const size_t o = (size_t)frame * p.pix_per_frame + idx;
+    if (xs < 1 || ys < 1 || xs > cols - 2 || ys > rows - 2) return;     // never sampled (clamped to cols-2 / rows-2)
+    const int cn = p.cn;
+    const PT *im = reinterpret_cast<const PT *>(p.pyr) + ((size_t)frame * p.pix_per_frame + c.d.img_off) * cn;
+    const size_t stride = (size_t)cols * cn;
+    R mag;
+    int ori;
+    if (cn == 1) {
+        const PT *s = im + xs + (size_t)ys * stride;
+        const R dy = pix_diff<R, PT>(s[stride], *(s - stride));
+        const R dx = pix_diff<R, PT>(s[1], s[-1]);
+        ori = hog_snap<R>(dx, dy);
+        mag = real_sqrt<R>(dx * dx + dy * dy);
+    } else hog_grad_px3<R, PT>(im + 3 * xs + (size_t)ys * stride, stride, mag, ori);
+    static_cast<R *>(p.gmag)[o] = mag;
+    p.gori[o] = (uint8_t)ori;
+}
+
+// Four consecutive interior pixels of one row of an 8-bit BGR image, s the first: the rows above / below come in as one
+// 16-byte load each and the row itself as 16 + 4 bytes (10 memory instructions per four pixels instead of 24 with results),
+// the results are packed for one 16-byte and one 4-byte store.
+typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
+typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ int px_byte(const u32x4_u &v, uint32_t extra, int b)
+{   // byte b (compile-time) of the 20 bytes {v, extra}
+    const uint32_t w = b < 16 ? v[b >> 2] : extra;
+    return (int)((w >> (8 * (b & 3))) & 0xffu);
+}
+__device__ __forceinline__ void hog_grad_quad(const uint8_t *s, size_t stride, f32x4_u &mg, uint32_t &og)
+{
+    const u32x4_u up = *reinterpret_cast<const u32x4_u *>(s - stride), dn = *reinterpret_cast<const u32x4_u *>(s + stride);
+    const u32x4_u mid = *reinterpret_cast<const u32x4_u *>(s - 3);
+    const uint32_t mid2 = *reinterpret_cast<const u32_unaligned *>(s + 13);       // bytes 16..19 of the row window
+    og = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        // pixel i: up / down at bytes 3i+c, left at window bytes 3i+c, right at 3(i+2)+c
+        float m; int oo;
+        hog_grad_pixel<float>((float)(px_byte(mid, mid2, 3 * (i + 2) + 0) - px_byte(mid, mid2, 3 * i + 0)),
+                              (float)(px_byte(dn, 0, 3 * i + 0) - px_byte(up, 0, 3 * i + 0)),
+                              (float)(px_byte(mid, mid2, 3 * (i + 2) + 1) - px_byte(mid, mid2, 3 * i + 1)),
+                              (float)(px_byte(dn, 0, 3 * i + 1) - px_byte(up, 0, 3 * i + 1)),
+                              (float)(px_byte(mid, mid2, 3 * (i + 2) + 2) - px_byte(mid, mid2, 3 * i + 2)),
+                              (float)(px_byte(dn, 0, 3 * i + 2) - px_byte(up, 0, 3 * i + 2)), m, oo);
+        mg[i] = m;
+        og |= (uint32_t)oo << (8 * i);
+    }
+}
+
+// Pass 1, four consecutive pixels per thread (8-bit BGR, T = float): quads that share an image row and are all interior take
+// hog_grad_quad, the others go pixel by pixel.
+__global__ __launch_bounds__(256) void k_hog_grad4(HogParams p)
+{
+    const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int l = find_level_blk<0>(p.lv, 0, p.nlevels, min(idx, p.pix_per_frame - 1));
+    if (idx >= p.pix_per_frame) return;
+    const int frame = p.frame0 + blockIdx.y;
+    const LevelCell c = level_cell<0>(p.lv, l, idx);
+    const int rows = c.d.img_rows, cols = c.d.img_cols, ys = c.y, xs = c.x;
     const size_t o = (size_t)frame * p.pix_per_frame + idx;
     float *gmag = static_cast<float *>(p.gmag);
-    const bool fast = local + 3 < rows * cols && xs >= 1 && xs + 3 <= cols - 2 && ys >= 1 && ys <= rows - 2;
+    const bool fast = ys * cols + xs + 3 < rows * cols && xs >= 1 && xs + 3 <= cols - 2 && ys >= 1 && ys <= rows - 2;
     if (fast) {
-        const uint8_t *im = p.pyr + ((size_t)frame * p.pix_per_frame + d.img_off) * 3;
+        const uint8_t *im = p.pyr + ((size_t)frame * p.pix_per_frame + c.d.img_off) * 3;
         const size_t stride = (size_t)cols * 3;
-        const uint8_t *s = im + 3 * xs + (size_t)ys * stride;
-        const u32x4_u up = *reinterpret_cast<const u32x4_u *>(s - stride), dn = *reinterpret_cast<const u32x4_u *>(s + stride);
-        const u32x4_u mid = *reinterpret_cast<const u32x4_u *>(s - 3);
-        const uint32_t mid2 = *reinterpret_cast<const u32_unaligned *>(s + 13);       // bytes 16..19 of the row window
         f32x4_u mg;
-        uint32_t og = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            // pixel i: up / down at bytes 3i+c, left at window bytes 3i+c, right at 3(i+2)+c
-            float m; int oo;
-            hog_grad_pixel<float>((float)(px_byte(mid, mid2, 3 * (i + 2) + 0) - px_byte(mid, mid2, 3 * i + 0)),
-                                  (float)(px_byte(dn, 0, 3 * i + 0) - px_byte(up, 0, 3 * i + 0)),
-                                  (float)(px_byte(mid, mid2, 3 * (i + 2) + 1) - px_byte(mid, mid2, 3 * i + 1)),
-                                  (float)(px_byte(dn, 0, 3 * i + 1) - px_byte(up, 0, 3 * i + 1)),
-                                  (float)(px_byte(mid, mid2, 3 * (i + 2) + 2) - px_byte(mid, mid2, 3 * i + 2)),
-                                  (float)(px_byte(dn, 0, 3 * i + 2) - px_byte(up, 0, 3 * i + 2)), m, oo);
-            mg[i] = m;
-            og |= (uint32_t)oo << (8 * i);
-        }
+        uint32_t og;
+        hog_grad_quad(im + 3 * xs + (size_t)ys * stride, stride, mg, og);
         *reinterpret_cast<f32x4_u *>(gmag + o) = mg;
         *reinterpret_cast<u32_unaligned *>(p.gori + o) = og;
         return;
@@ -636,92 +641,118 @@ __global__ __launch_bounds__(256) void k_hog_grad4(HogParams p)
         if (pi >= p.pix_per_frame) return;
         int li = l;
         while (li + 1 < p.nlevels && p.lv[li + 1].img_off <= pi) ++li;
-        const LevelDesc di = p.lv[li];
-        const int loc = (int)(pi - di.img_off);
-        const int r2 = di.img_rows, c2 = di.img_cols;
-        const int y = loc / c2, x = loc - y * c2;
+        const LevelCell ci = level_cell<0>(p.lv, li, pi);
+        const int r2 = ci.d.img_rows, c2 = ci.d.img_cols, y = ci.y, x = ci.x;
         if (x < 1 || y < 1 || x > c2 - 2 || y > r2 - 2) continue;     // never sampled (clamped to cols-2 / rows-2)
-        const uint8_t *im = p.pyr + ((size_t)frame * p.pix_per_frame + di.img_off) * 3;
+        const uint8_t *im = p.pyr + ((size_t)frame * p.pix_per_frame + ci.d.img_off) * 3;
         const size_t stride = (size_t)c2 * 3;
-        const uint8_t *s = im + 3 * x + (size_t)y * stride;
-        const uint32_t pd = load_px3(s + stride), pu = load_px3(s - stride), pr = load_px3(s + 3), pl = load_px3(s - 3);
         float m; int oo;
-        hog_grad_pixel<float>((float)(px_ch(pr, 0) - px_ch(pl, 0)), (float)(px_ch(pd, 0) - px_ch(pu, 0)),
-                              (float)(px_ch(pr, 1) - px_ch(pl, 1)), (float)(px_ch(pd, 1) - px_ch(pu, 1)),
-                              (float)(px_ch(pr, 2) - px_ch(pl, 2)), (float)(px_ch(pd, 2) - px_ch(pu, 2)), m, oo);
+        hog_grad_px3<float, uint8_t>(im + 3 * x + (size_t)y * stride, stride, m, oo);
         gmag[(size_t)frame * p.pix_per_frame + pi] = m;
         p.gori[(size_t)frame * p.pix_per_frame + pi] = (uint8_t)oo;
     }
 }
 
-// The same for 16U / 32F / 64F pixels (features<uint16_t|float|double>, src/HOGFeatures.cpp:136-146): the difference is
-// taken in the pixel type (integers promote to int, float / double subtract as such) and then converted to T.
-template <typename R, typename PT> __device__ __forceinline__ R pix_diff(PT a, PT b);
-template <> __device__ __forceinline__ float pix_diff<float, uint16_t>(uint16_t a, uint16_t b) { return (float)((int)a - (int)b); }
-template <> __device__ __forceinline__ double pix_diff<double, uint16_t>(uint16_t a, uint16_t b) { return (double)((int)a - (int)b); }
-template <> __device__ __forceinline__ float pix_diff<float, float>(float a, float b) { return a - b; }
-template <> __device__ __forceinline__ double pix_diff<double, float>(float a, float b) { return (double)(a - b); }
-template <> __device__ __forceinline__ float pix_diff<float, double>(double a, double b) { return (float)(a - b); }
-template <> __device__ __forceinline__ double pix_diff<double, double>(double a, double b) { return a - b; }
-
-template <typename R, typename PT>
-__global__ __launch_bounds__(256) void k_hog_grad_t(HogParams p)
+// ------------------------------------------------------------------------------------------------
+// HOG cell histograms, gather form.  One thread per block (cell of the `blocks` grid): it walks the source pixels that
+// the reference's scatter loop (src/HOGFeatures.cpp:202-267) adds into this block, in the same raster order, and adds
+// (wy*wx)*mag into the bin of the pixel's orientation, so every bin sees the same sequence of additions.  The 18 bins of a
+// thread live in LDS ([18][BS], BS threads: the thread always hits bank tid % 32), so the update is one read-add-write
+// instead of 18 predicated register adds.
+// ------------------------------------------------------------------------------------------------
+// pixels with ip in {b-1, b}: (y+0.5)/sbin - 0.5 in [b-1, b+1), i.e. y in [sbin*b - sbin/2 - 0.5, sbin*b + 3*sbin/2 - 0.5);
+// one extra pixel either side, the table test of the walk decides
+struct HogWindow { int ylo, yhi, xlo, xhi; };
+__device__ __forceinline__ HogWindow hog_window(int sbin, int by, int bx, int vish, int visw)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<0>(p.lv, 0, p.nlevels, idx, s_off);
-    if (idx >= p.pix_per_frame) return;
-    const int frame = p.frame0 + blockIdx.y;
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.img_off);
-    const int rows = d.img_rows, cols = d.img_cols;
-    const int ys = local / cols, xs = local - ys * cols;
-    const size_t o = (size_t)frame * p.pix_per_frame + idx;
-    if (xs < 1 || ys < 1 || xs > cols - 2 || ys > rows - 2) return;
-    const int cn = p.cn;
-    const PT *im = reinterpret_cast<const PT *>(p.pyr) + ((size_t)frame * p.pix_per_frame + d.img_off) * cn;
-    const size_t stride = (size_t)cols * cn;
-    const R uu[9] = {(R)1.000, (R)0.9397, (R)0.7660, (R)0.5000, (R)0.1736, (R)-0.1736, (R)-0.5000, (R)-0.7660, (R)-0.9397};
-    const R vv[9] = {(R)0.000, (R)0.3420, (R)0.6428, (R)0.8660, (R)0.9848, (R)0.9848, (R)0.8660, (R)0.6428, (R)0.3420};
-    R dx, dy, v;
-    if (cn == 1) {
-        const PT *s = im + xs + (size_t)ys * stride;
-        dy = pix_diff<R, PT>(s[stride], *(s - stride));
-        dx = pix_diff<R, PT>(s[1], s[-1]);
-        v = dx * dx + dy * dy;
-    } else {
-        const PT *s = im + 3 * xs + (size_t)ys * stride;
-        const R dyb = pix_diff<R, PT>(s[stride], *(s - stride));
-        const R dxb = pix_diff<R, PT>(s[3], s[-3]);
-        const R vb = dxb * dxb + dyb * dyb;
-        const R dyg = pix_diff<R, PT>(s[1 + stride], *(s + 1 - stride));
-        const R dxg = pix_diff<R, PT>(s[4], s[-2]);
-        const R vg = dxg * dxg + dyg * dyg;
-        dy = pix_diff<R, PT>(s[2 + stride], *(s + 2 - stride));
-        dx = pix_diff<R, PT>(s[5], s[-1]);
-        v = dx * dx + dy * dy;
-        if (vg > v) { v = vg; dx = dxg; dy = dyg; }
-        if (vb > v) { v = vb; dx = dxb; dy = dyb; }
-    }
-    R best_dot = (R)0;
-    int best_o = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const R dot = uu[k] * dx + vv[k] * dy;
-        if (dot > best_dot) { best_dot = dot; best_o = k; }
-        else if (-dot > best_dot) { best_dot = -dot; best_o = k + 9; }
-    }
-    static_cast<R *>(p.gmag)[o] = real_sqrt<R>(v);
-    p.gori[o] = (uint8_t)best_o;
+    HogWindow w;
+    w.ylo = sbin * by - (sbin + 1) / 2 - 1; w.yhi = sbin * by + (3 * sbin + 1) / 2 + 1;
+    w.xlo = sbin * bx - (sbin + 1) / 2 - 1; w.xhi = sbin * bx + (3 * sbin + 1) / 2 + 1;
+    if (w.ylo < 1) w.ylo = 1;
+    if (w.xlo < 1) w.xlo = 1;
+    if (w.yhi > vish - 1) w.yhi = vish - 1;
+    if (w.xhi > visw - 1) w.xhi = visw - 1;
+    return w;
 }
 
-// Pass 2: one thread per block walks its source pixels in raster order and adds (wy*wx)*mag into the bin
-// of the pixel's orientation.  The 18 bins of a thread live in LDS ([18][256], the thread always hits bank
-// tid % 32), so the update is one read-add-write instead of 18 predicated register adds; the sequence of
-// float additions per bin is the reference's.  Also writes the block energy (:270-283).
-// SB = compile-time sbin (4, 8) or 0 for any: with a known sbin the x weights of the thread's window are fetched
-// once into registers instead of once per source pixel (the coordinate-table loads were most of the kernel's
-// memory requests: lanes are blocks, their table entries sbin apart).
+// where the walk reads magnitude and orientation of image position (y, x): the planes of pass 1 ...
+template <typename R>
+struct HogPlanes {
+    const R *mag;
+    const uint8_t *ori;
+    int cols;
+    __device__ __forceinline__ int col(int x) const { return x; }
+    __device__ __forceinline__ size_t row(int y) const { return (size_t)y * cols; }
+    __device__ __forceinline__ R mag_at(size_t g) const { return mag[g]; }
+    __device__ __forceinline__ int ori_at(size_t g) const { return (int)ori[g]; }
+};
+// ... or a workgroup's LDS tile, LW cells per row, cell (0, 0) = image position (oy, ox)
+template <int LW>
+struct HogLdsTile {
+    const float *mag;
+    const uint8_t *ori;
+    int oy, ox;
+    __device__ __forceinline__ int col(int x) const { return x - ox; }
+    __device__ __forceinline__ int row(int y) const { return (y - oy) * LW; }
+    __device__ __forceinline__ float mag_at(int g) const { return mag[g]; }
+    __device__ __forceinline__ int ori_at(int g) const { return (int)ori[g]; }
+};
+
+// The walk for a compile-time sbin SB: the x weights of the thread's window are fetched once into registers instead of once
+// per source pixel (the coordinate-table loads were most of the kernel's memory requests: lanes are blocks, their table
+// entries sbin apart).  h: the thread's bins, BS apart.
+template <typename R, int SB, int BS, typename Src>
+__device__ __forceinline__ void hog_walk(const HogCoordT<R> *coord, const HogWindow &w, int by, int bx, int rows, int cols, const Src &src, R *h)
+{
+    constexpr int NX = 2 * SB + 2;                         // window width before clamping
+    const int x0 = SB * bx - (SB + 1) / 2 - 1;
+    R wxs[NX];
+    int xoff[NX];                                           // source column, -1: this x does not feed the block
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+        const int x = x0 + i;
+        xoff[i] = -1; wxs[i] = (R)0;
+        if (x >= w.xlo && x < w.xhi) {
+            const HogCoordT<R> cx = coord[x];
+            if (cx.ip == bx) { wxs[i] = cx.v1; xoff[i] = src.col(x < cols - 2 ? x : cols - 2); }            // this block is (., ixp): weight vx1
+            else if (cx.ip + 1 == bx) { wxs[i] = cx.v0; xoff[i] = src.col(x < cols - 2 ? x : cols - 2); }   // (., ixp+1): weight vx0
+        }
+    }
+    for (int y = w.ylo; y < w.yhi; ++y) {
+        const HogCoordT<R> cy = coord[y];
+        R wy;
+        if (cy.ip == by) wy = cy.v1;
+        else if (cy.ip + 1 == by) wy = cy.v0;
+        else continue;
+        const auto rowg = src.row(y < rows - 2 ? y : rows - 2);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            if (xoff[i] < 0) continue;
+            const auto g = rowg + xoff[i];
+            const R contrib = (wy * wxs[i]) * src.mag_at(g);
+            R *bin = h + src.ori_at(g) * BS;
+            *bin = *bin + contrib;
+        }
+    }
+}
+
+// the block's 18 bins and its energy (src/HOGFeatures.cpp:270-283)
+template <typename R, int BS>
+__device__ __forceinline__ void hog_hist_store(const R *h, R *hist, R *norm, long long blk_per_frame)
+{
+    R hv[18];
+#pragma unroll
+    for (int o = 0; o < 18; ++o) { hv[o] = h[o * BS]; hist[(size_t)o * blk_per_frame] = hv[o]; }
+    R e = (R)0;
+#pragma unroll
+    for (int o = 0; o < 9; ++o) {
+        const R t = hv[o] + hv[o + 9];
+        e += t * t;
+    }
+    *norm = e;
+}
+
+// Pass 2 of the two-pass form.  SB = compile-time sbin (4, 8) or 0 for any.
 template <typename R, int SB>
 __global__ __launch_bounds__(256) void k_hog_hist(HogParams p)
 {
@@ -730,71 +761,30 @@ __global__ __launch_bounds__(256) void k_hog_hist(HogParams p)
     const bool active = idx0 < p.blk_per_frame;
     const long long idx = active ? idx0 : p.blk_per_frame - 1;
     const int frame = p.frame0 + blockIdx.y;
-    __shared__ long long s_off[PBD_MAX_LEVELS];
-    const int l = find_level_blk<1>(p.lv, 0, p.nlevels, idx, s_off);
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.blk_off);
-    const int by = local / d.blk_cols, bx = local - by * d.blk_cols;
+    const LevelCell c = level_cell<1>(p.lv, find_level_blk<1>(p.lv, 0, p.nlevels, idx), idx);
+    const LevelDesc &d = c.d;
+    const int by = c.y, bx = c.x;
     const int sbin = p.sbin;
     const int rows = d.img_rows, cols = d.img_cols;
-    const int vish = d.blk_rows * sbin, visw = d.blk_cols * sbin;
-    const R *gmag = static_cast<const R *>(p.gmag) + (size_t)frame * p.pix_per_frame + d.img_off;
-    const uint8_t *gori = p.gori + (size_t)frame * p.pix_per_frame + d.img_off;
+    const HogPlanes<R> src{static_cast<const R *>(p.gmag) + (size_t)frame * p.pix_per_frame + d.img_off,
+                           p.gori + (size_t)frame * p.pix_per_frame + d.img_off, cols};
     const HogCoordT<R> *coord = static_cast<const HogCoordT<R> *>(p.coord);
     R *h = bins + threadIdx.x;
 #pragma unroll
     for (int o = 0; o < 18; ++o) h[o * 256] = (R)0;
+    HogWindow w = hog_window(sbin, by, bx, d.blk_rows * sbin, d.blk_cols * sbin);
+    if (!active) w.yhi = w.ylo;
 
-    // pixels with ip in {b-1, b}: (y+0.5)/sbin - 0.5 in [b-1, b+1), i.e. y in [sbin*b - sbin/2 - 0.5, sbin*b + 3*sbin/2 - 0.5);
-    // one extra pixel either side, the table test below decides
-    int ylo = sbin * by - (sbin + 1) / 2 - 1, yhi = sbin * by + (3 * sbin + 1) / 2 + 1;
-    int xlo = sbin * bx - (sbin + 1) / 2 - 1, xhi = sbin * bx + (3 * sbin + 1) / 2 + 1;
-    if (ylo < 1) ylo = 1;
-    if (xlo < 1) xlo = 1;
-    if (yhi > vish - 1) yhi = vish - 1;
-    if (xhi > visw - 1) xhi = visw - 1;
-    if (!active) yhi = ylo;
-
-    if constexpr (SB > 0) {
-        constexpr int NX = 2 * SB + 2;                         // window width before clamping
-        const int x0 = SB * bx - (SB + 1) / 2 - 1;
-        R wxs[NX];
-        int xoff[NX];                                           // source column, -1: this x does not feed the block
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const int x = x0 + i;
-            xoff[i] = -1; wxs[i] = (R)0;
-            if (x >= xlo && x < xhi) {
-                const HogCoordT<R> cx = coord[x];
-                if (cx.ip == bx) { wxs[i] = cx.v1; xoff[i] = x < cols - 2 ? x : cols - 2; }
-                else if (cx.ip + 1 == bx) { wxs[i] = cx.v0; xoff[i] = x < cols - 2 ? x : cols - 2; }
-            }
-        }
-        for (int y = ylo; y < yhi; ++y) {
-            const HogCoordT<R> cy = coord[y];
-            R wy;
-            if (cy.ip == by) wy = cy.v1;
-            else if (cy.ip + 1 == by) wy = cy.v0;
-            else continue;
-            const size_t rowg = (size_t)(y < rows - 2 ? y : rows - 2) * cols;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                if (xoff[i] < 0) continue;
-                const size_t g = rowg + xoff[i];
-                const R contrib = (wy * wxs[i]) * gmag[g];
-                R *bin = h + (int)gori[g] * 256;
-                *bin = *bin + contrib;
-            }
-        }
-    } else
-    for (int y = ylo; y < yhi; ++y) {
+    if constexpr (SB > 0) hog_walk<R, SB, 256>(coord, w, by, bx, rows, cols, src, h);
+    else
+    for (int y = w.ylo; y < w.yhi; ++y) {
         const HogCoordT<R> cy = coord[y];
         R wy;
         if (cy.ip == by) wy = cy.v1;            // this block is (iyp, .): weight vy1
         else if (cy.ip + 1 == by) wy = cy.v0;   // this block is (iyp+1, .): weight vy0
         else continue;
         const int ys = y < rows - 2 ? y : rows - 2;
-        for (int x = xlo; x < xhi; ++x) {
+        for (int x = w.xlo; x < w.xhi; ++x) {
             const HogCoordT<R> cx = coord[x];
             R wx;
             if (cx.ip == bx) wx = cx.v1;
@@ -803,23 +793,14 @@ __global__ __launch_bounds__(256) void k_hog_hist(HogParams p)
             const int xs = x < cols - 2 ? x : cols - 2;
             const size_t g = (size_t)ys * cols + xs;
             // the four scatter lines multiply (vy?*vx?) first, then by v; products commute
-            const R contrib = (wy * wx) * gmag[g];
-            R *bin = h + (int)gori[g] * 256;
+            const R contrib = (wy * wx) * src.mag[g];
+            R *bin = h + (int)src.ori[g] * 256;
             *bin = *bin + contrib;
         }
     }
     if (!active) return;
-    R *hist = static_cast<R *>(p.hist) + (size_t)frame * 18 * p.blk_per_frame + idx;
-    R hv[18];
-#pragma unroll
-    for (int o = 0; o < 18; ++o) { hv[o] = h[o * 256]; hist[(size_t)o * p.blk_per_frame] = hv[o]; }
-    R e = (R)0;
-#pragma unroll
-    for (int o = 0; o < 9; ++o) {
-        const R t = hv[o] + hv[o + 9];
-        e += t * t;
-    }
-    static_cast<R *>(p.norm)[(size_t)frame * p.blk_per_frame + idx] = e;
+    hog_hist_store<R, 256>(h, static_cast<R *>(p.hist) + (size_t)frame * 18 * p.blk_per_frame + idx,
+                           static_cast<R *>(p.norm) + (size_t)frame * p.blk_per_frame + idx, p.blk_per_frame);
 }
 
 // Fused form of the two passes for the hot case (8-bit BGR frames, T = float, sbin 4 or 8): one workgroup = one tile of
@@ -853,23 +834,9 @@ __global__ __launch_bounds__(TBX * TBY) void k_hog_tile(HogParams p)
         if (y < 1 || y > rows - 2) continue;                       // never sampled (positions are clamped to rows-2 / cols-2)
         const uint8_t *s = im + 3 * x + (size_t)y * stride;
         if (x >= 1 && x + 3 <= cols - 2 && (long long)y * cols + x + 3 < npix) {
-            const u32x4_u up = *reinterpret_cast<const u32x4_u *>(s - stride), dn = *reinterpret_cast<const u32x4_u *>(s + stride);
-            const u32x4_u mid = *reinterpret_cast<const u32x4_u *>(s - 3);
-            const uint32_t mid2 = *reinterpret_cast<const u32_unaligned *>(s + 13);
             f32x4_u mg;
-            uint32_t og = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float m; int oo;
-                hog_grad_pixel<float>((float)(px_byte(mid, mid2, 3 * (i + 2) + 0) - px_byte(mid, mid2, 3 * i + 0)),
-                                      (float)(px_byte(dn, 0, 3 * i + 0) - px_byte(up, 0, 3 * i + 0)),
-                                      (float)(px_byte(mid, mid2, 3 * (i + 2) + 1) - px_byte(mid, mid2, 3 * i + 1)),
-                                      (float)(px_byte(dn, 0, 3 * i + 1) - px_byte(up, 0, 3 * i + 1)),
-                                      (float)(px_byte(mid, mid2, 3 * (i + 2) + 2) - px_byte(mid, mid2, 3 * i + 2)),
-                                      (float)(px_byte(dn, 0, 3 * i + 2) - px_byte(up, 0, 3 * i + 2)), m, oo);
-                mg[i] = m;
-                og |= (uint32_t)oo << (8 * i);
-            }
+            uint32_t og;
+            hog_grad_quad(s, stride, mg, og);
             *reinterpret_cast<f32x4_u *>(s_mag + py * LW + px) = mg;
             *reinterpret_cast<uint32_t *>(s_ori + py * LW + px) = og;
         } else {
@@ -877,12 +844,8 @@ __global__ __launch_bounds__(TBX * TBY) void k_hog_tile(HogParams p)
             for (int i = 0; i < 4; ++i) {
                 const int xi = x + i;
                 if (xi < 1 || xi > cols - 2) continue;
-                const uint8_t *si = s + 3 * i;
-                const uint32_t pd = load_px3(si + stride), pu = load_px3(si - stride), pr = load_px3(si + 3), pl = load_px3(si - 3);
                 float m; int oo;
-                hog_grad_pixel<float>((float)(px_ch(pr, 0) - px_ch(pl, 0)), (float)(px_ch(pd, 0) - px_ch(pu, 0)),
-                                      (float)(px_ch(pr, 1) - px_ch(pl, 1)), (float)(px_ch(pd, 1) - px_ch(pu, 1)),
-                                      (float)(px_ch(pr, 2) - px_ch(pl, 2)), (float)(px_ch(pd, 2) - px_ch(pu, 2)), m, oo);
+                hog_grad_px3<float, uint8_t>(s + 3 * i, stride, m, oo);
                 s_mag[py * LW + px + i] = m;
                 s_ori[py * LW + px + i] = (uint8_t)oo;
             }
@@ -891,85 +854,36 @@ __global__ __launch_bounds__(TBX * TBY) void k_hog_tile(HogParams p)
     __syncthreads();
     const int by = tile.y0 + t / TBX, bx = tile.x0 + t % TBX;
     if (by >= d.blk_rows || bx >= d.blk_cols) return;
-    const int vish = d.blk_rows * SB, visw = d.blk_cols * SB;
-    const HogCoordT<float> *coord = static_cast<const HogCoordT<float> *>(p.coord);
     float *h = bins + t;
 #pragma unroll
     for (int o = 0; o < 18; ++o) h[o * NT] = 0.0f;
-    int ylo = SB * by - (SB + 1) / 2 - 1, yhi = SB * by + (3 * SB + 1) / 2 + 1;
-    int xlo = SB * bx - (SB + 1) / 2 - 1, xhi = SB * bx + (3 * SB + 1) / 2 + 1;
-    if (ylo < 1) ylo = 1;
-    if (xlo < 1) xlo = 1;
-    if (yhi > vish - 1) yhi = vish - 1;
-    if (xhi > visw - 1) xhi = visw - 1;
-    constexpr int NX = 2 * SB + 2;                             // window width before clamping
-    const int x0 = SB * bx - (SB + 1) / 2 - 1;
-    float wxs[NX];
-    int xoff[NX];                                               // LDS column, -1: this x does not feed the block
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-        const int x = x0 + i;
-        xoff[i] = -1; wxs[i] = 0.0f;
-        if (x >= xlo && x < xhi) {
-            const HogCoordT<float> cx = coord[x];
-            if (cx.ip == bx) { wxs[i] = cx.v1; xoff[i] = (x < cols - 2 ? x : cols - 2) - ox; }
-            else if (cx.ip + 1 == bx) { wxs[i] = cx.v0; xoff[i] = (x < cols - 2 ? x : cols - 2) - ox; }
-        }
-    }
-    for (int y = ylo; y < yhi; ++y) {
-        const HogCoordT<float> cy = coord[y];
-        float wy;
-        if (cy.ip == by) wy = cy.v1;
-        else if (cy.ip + 1 == by) wy = cy.v0;
-        else continue;
-        const int rowg = ((y < rows - 2 ? y : rows - 2) - oy) * LW;
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            if (xoff[i] < 0) continue;
-            const int g = rowg + xoff[i];
-            const float contrib = (wy * wxs[i]) * s_mag[g];
-            float *bin = h + (int)s_ori[g] * NT;
-            *bin = *bin + contrib;
-        }
-    }
+    hog_walk<float, SB, NT>(static_cast<const HogCoordT<float> *>(p.coord), hog_window(SB, by, bx, d.blk_rows * SB, d.blk_cols * SB),
+                            by, bx, rows, cols, HogLdsTile<LW>{s_mag, s_ori, oy, ox}, h);
     const long long idx = d.blk_off + (long long)by * d.blk_cols + bx;
-    float *hist = static_cast<float *>(p.hist) + (size_t)frame * 18 * p.blk_per_frame + idx;
-    float hv[18];
-#pragma unroll
-    for (int o = 0; o < 18; ++o) { hv[o] = h[o * NT]; hist[(size_t)o * p.blk_per_frame] = hv[o]; }
-    float e = 0.0f;
-#pragma unroll
-    for (int o = 0; o < 9; ++o) {
-        const float tt = hv[o] + hv[o + 9];
-        e += tt * tt;
-    }
-    static_cast<float *>(p.norm)[(size_t)frame * p.blk_per_frame + idx] = e;
+    hog_hist_store<float, NT>(h, static_cast<float *>(p.hist) + (size_t)frame * 18 * p.blk_per_frame + idx,
+                              static_cast<float *>(p.norm) + (size_t)frame * p.blk_per_frame + idx, p.blk_per_frame);
 }
 
 void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s)
 {
-    if (!f64 && p.depth == kDepth8U && p.cn == 3 && (p.sbin == 4 || p.sbin == 8)) {
+    const bool bgr8 = !f64 && p.depth == kDepth8U && p.cn == 3;
+    if (bgr8 && (p.sbin == 4 || p.sbin == 8)) {
         if (p.nhtiles == 0) return;
         dim3 grid((unsigned)p.nhtiles, nframes);
         if (p.sbin == 4) PBD_LAUNCH((k_hog_tile<4, kHogTBX, 16>), grid, dim3(kHogTBX * 16), 0, s, p);
         else PBD_LAUNCH((k_hog_tile<8, kHogTBX, 8>), grid, dim3(kHogTBX * 8), 0, s, p);
         return;
     }
-    dim3 gridp((unsigned)((p.pix_per_frame + 255) / 256), nframes);
-#define PBD_GRAD(PT)                                                                            \
-    do {                                                                                        \
-        if (f64) PBD_LAUNCH((k_hog_grad_t<double, PT>), gridp, dim3(256), 0, s, p);     \
-        else PBD_LAUNCH((k_hog_grad_t<float, PT>), gridp, dim3(256), 0, s, p);          \
-    } while (0)
-    if (p.depth == kDepth16U) PBD_GRAD(uint16_t);
-    else if (p.depth == kDepth32F) PBD_GRAD(float);
-    else if (p.depth == kDepth64F) PBD_GRAD(double);
-    else if (f64) PBD_LAUNCH(k_hog_grad<double>, gridp, dim3(256), 0, s, p);
-    else if (p.cn == 3) {
+    if (bgr8) {
         dim3 grid4((unsigned)((p.pix_per_frame + 1023) / 1024), nframes);
         PBD_LAUNCH(k_hog_grad4, grid4, dim3(256), 0, s, p);
-    } else PBD_LAUNCH(k_hog_grad<float>, gridp, dim3(256), 0, s, p);
-#undef PBD_GRAD
+    } else {
+        dim3 gridp((unsigned)((p.pix_per_frame + 255) / 256), nframes);
+        for_depth(p.depth, [&](auto t) {
+            if (f64) PBD_LAUNCH((k_hog_grad<double, decltype(t)>), gridp, dim3(256), 0, s, p);
+            else PBD_LAUNCH((k_hog_grad<float, decltype(t)>), gridp, dim3(256), 0, s, p);
+        });
+    }
     dim3 grid((unsigned)((p.blk_per_frame + 255) / 256), nframes);
     if (f64) PBD_LAUNCH((k_hog_hist<double, 0>), grid, dim3(256), 0, s, p);
     else if (p.sbin == 4) PBD_LAUNCH((k_hog_hist<float, 4>), grid, dim3(256), 0, s, p);
@@ -991,9 +905,8 @@ __device__ __forceinline__ R hog_norm(const R *n, int stride)
 template <typename R>
 __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
 {
-    __shared__ long long s_off[PBD_MAX_LEVELS];
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int l = find_level_blk<2>(p.lv, 0, p.nlevels, idx, s_off);
+    const int l = find_level_blk<2>(p.lv, 0, p.nlevels, idx);
     // float: the 32 values of a cell leave through LDS so that a store instruction writes 1 KB of consecutive addresses (a
     // block's 256 cells are consecutive in the feature buffer); written straight from the registers every 16-byte store of a
     // wave touched 64 different 128-byte lines
@@ -1004,9 +917,9 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
     if (!VIA_LDS && !valid) return;
     const int frame = p.frame0 + blockIdx.y;
     if (valid) {
-    const LevelDesc d = p.lv[l];
-    const int local = (int)(idx - d.cell_off);
-    const int y = local / d.cols, x = local - y * d.cols;
+    const LevelCell c = level_cell<2>(p.lv, l, idx);
+    const LevelDesc &d = c.d;
+    const int y = c.y, x = c.x;
     const int bw = d.blk_cols;
     const R *norm = static_cast<const R *>(p.norm) + (size_t)frame * p.blk_per_frame + d.blk_off;
     const R n1 = hog_norm<R>(norm + (size_t)(y + 1) * bw + (x + 1), bw);
@@ -1069,8 +982,6 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
         }
     }
 }
-
-
 
 void launch_hog_feat(const HogParams &p, int nframes, bool f64, hipStream_t s)
 {

@@ -221,7 +221,7 @@ MIXED += [("8U", 3, "f32", 8), ("8U", 3, "f32", 3), ("64F", 3, "f64", 8), ("16U"
 
 @pytest.mark.parametrize("depth,cn,real,sbin", MIXED, ids=lambda v: str(v))
 def test_mixed_size_call_planes_equal_the_oracle(det_mod, oracle, depth, cn, real, sbin):
-    """Four frames of different shapes and content in one pbd_detect_frames call (k_resize_runs*, k_pyrdown_runs*, the HOG
+    """Four frames of different shapes and content in one pbd_detect_frames call (k_resize<PT, Runs>, k_pyrdown<PT, Runs>, the HOG
     kernels over the call's virtual level table): every frame's level images (pbd_get_pyramid_image(h, f, l)) and features
     equal the oracle's of that frame alone, for every depth and both real types."""
     IT, T = DEPTHS[depth], REALS[real]
@@ -237,6 +237,36 @@ def test_mixed_size_call_planes_equal_the_oracle(det_mod, oracle, depth, cn, rea
         assert det.detect_frames(frames) == []
         for f, (im, shape) in enumerate(zip(frames, shapes)):
             imgs_want, feats_want, _ = oracle_planes(oracle, flat, T, ("mixed", depth, cn, shape, f), im)
+            imgs, feats = resident_planes(det.hd, f, shape[0], shape[1], cn, IT)
+            compare_planes(f"{depth} cn{cn} {real} sbin{sbin} frame {f} {shape}", imgs, imgs_want, feats, feats_want)
+    finally:
+        det.hd.close()
+
+
+MANY_SHAPES = [(69, 32), (32, 69), (70, 35), (75, 33)]      # small accepted shapes around SHAPES[4][0], the smallest
+MANY = 44                                                    # 44 frames x 3 resized levels = 132 > 128 = _lib.MAX_LEVELS
+
+
+@pytest.mark.parametrize("depth,cn,real,sbin", [("8U", 3, "f32", 4), ("32F", 1, "f64", 4)], ids=lambda v: str(v))
+def test_mixed_call_with_more_levels_than_the_lds_table(det_mod, oracle, depth, cn, real, sbin):
+    """One pbd_detect_frames call whose first pyramid launch holds more runs, and whose virtual frame more levels, than the
+    kernels' LDS offset table (PBD_MAX_LEVELS): the run search and the level search of every kernel take their global-memory
+    branch.  Every frame's level images and features equal the oracle's of that frame alone."""
+    IT, T = DEPTHS[depth], REALS[real]
+    model = model_for(sbin)
+    flat = model.flatten()
+    shapes = [MANY_SHAPES[i % len(MANY_SHAPES)] for i in range(MANY)]
+    frames = batch_contents(depth, cn, shapes, MANY)
+    det = det_mod.PartsBasedDetector(device=0, max_batch=MANY, dtype=T)
+    det.distributeModel(model)
+    try:
+        nlev = [det.hd.plan(*sh)["nlevels"] for sh in shapes]
+        assert all(n >= INTERVAL for n in nlev)
+        assert sum(min(n, INTERVAL) for n in nlev) > _lib.MAX_LEVELS     # runs of launch 0: every frame's resized levels
+        assert sum(nlev) > _lib.MAX_LEVELS                   # levels of the virtual frame
+        assert det.detect_frames(frames) == []
+        for f, (im, shape) in enumerate(zip(frames, shapes)):
+            imgs_want, feats_want, _ = oracle_planes(oracle, flat, T, ("many", depth, cn, shape, f), im)
             imgs, feats = resident_planes(det.hd, f, shape[0], shape[1], cn, IT)
             compare_planes(f"{depth} cn{cn} {real} sbin{sbin} frame {f} {shape}", imgs, imgs_want, feats, feats_want)
     finally:

@@ -17,7 +17,7 @@ import tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import build  # noqa: E402
 
-FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp"]
+FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp", "features"]
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 RENAMED = {
@@ -26,7 +26,17 @@ RENAMED = {
     "k_cl_scan_top": ["k_scan_top<long long, ClCropTotal>", "k_scan_top<long long, ScanNoTop>"],
     "k_pl_scan_part": ["k_scan_part<int, int>"], "k_pl_scan_top": ["k_scan_top<int, ScanNoTop>"],
     "k_pl_scan_add": ["k_scan_add<int, int>"],
+    "k_resize": ["k_resize<unsigned char, Frames>"], "k_resize_runs": ["k_resize<unsigned char, Runs>"],
+    "k_pyrdown": ["k_pyrdown<unsigned char, Frames>"], "k_pyrdown_runs<unsigned char, int, true>": ["k_pyrdown<unsigned char, Runs>"],
+    "k_hog_grad<float>": ["k_hog_grad<float, unsigned char>"], "k_hog_grad<double>": ["k_hog_grad<double, unsigned char>"],
 }
+for _pt, _rw, _pw in (("unsigned short", "float", "int"), ("float", "float", "float"), ("double", "double", "double")):
+    RENAMED["k_resize_t<%s, %s>" % (_pt, _rw)] = ["k_resize<%s, Frames>" % _pt]
+    RENAMED["k_resize_runs_t<%s, %s>" % (_pt, _rw)] = ["k_resize<%s, Runs>" % _pt]
+    RENAMED["k_pyrdown_t<%s, %s>" % (_pt, _pw)] = ["k_pyrdown<%s, Frames>" % _pt]
+    RENAMED["k_pyrdown_runs<%s, %s, %s>" % (_pt, _pw, "true" if _pw == "int" else "false")] = ["k_pyrdown<%s, Runs>" % _pt]
+    for _r in ("float", "double"):
+        RENAMED["k_hog_grad_t<%s, %s>" % (_r, _pt)] = ["k_hog_grad<%s, %s>" % (_r, _pt)]
 
 
 def compile_tree(tree, out):
