@@ -573,6 +573,63 @@ int pbd_set_thresh(pbd_handle *h, float thresh);
 int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values);
 int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values);
 int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values);
+/* Warped positives (new surface; opt-in): poswarp of the reference's Matlab training code (matlab/learning/train.m:131-162 with
+ * matlab/learning/warppos.m, subarray.m and qp_poswrite), the examples every training run starts from (trainmodel.m:19-40 trains
+ * each part mixture as a one-part model on them).  DESIGN.md section 6k.  Each annotated box is padded by one cell, cropped with
+ * edge replication, resized to (k + 2) * sbin pixels, and its HOG written as an example in pbd_examples' format.  No train()
+ * loop, no flipping: those stay with the caller.
+ * Frames as pbd_detect_frames takes them: host pointers (pbd_warp_positives) or device pointers (the _device form), mixed sizes,
+ * one `channels` (1 or 3) and one depth_code (all four) per call; a _device frame may be a region of a larger device image, read
+ * in place through its pitch, its pointer and stride_bytes multiples of the element size.  A frame only has to be 1 x 1 or
+ * larger (no pyramid of it is planned) and nframes is not bound by max_batch.
+ * boxes = int32[nboxes][5] = {frame, x1, y1, x2, y2}, always a host array; 0-based inclusive corners as the boxes of
+ * pbd_detect_latent.  Several boxes may name one frame, in any order; a frame may have no box.
+ * Window of box i, with k = filter_ksize[filter], s = sbin, width = x2 - x1 + 1, height = y2 - y1 + 1:
+ *   padx = s * width / (k * s), pady = s * height / (k * s), left to right in double (warppos.m:21-22);
+ *   in Matlab's 1-based coordinates X1 = round((x1 + 1) - padx), X2 = round((x2 + 1) + padx), Y1 and Y2 likewise, round = halves
+ *   away from zero (Matlab's); the 0-based window is columns X1-1 .. X2-1, rows Y1-1 .. Y2-1, and its pixel (r, c) is the frame's
+ *   pixel (clamp(Y1-1+r, 0, rows-1), clamp(X1-1+c, 0, cols-1)): subarray(im, Y1, Y2, X1, X2, 1).  rows and cols are the frame's
+ *   own (a region of a larger image is clamped at the region, not at its parent).
+ * Patch: the window resized to P x P, P = (k + 2) * s, by this library's cv::resize INTER_LINEAR restatement with the
+ *   coefficient arithmetic of a resized pyramid level of the same depth (source size = the window's, destination size = P).  No
+ *   crop is materialised: the taps index the window and the clamp maps them into the frame.
+ * Features: HOGFeatures<T>::features(patch) at sbin; blocks = k + 2 exactly, so the result is k x k x flen, row-major, channel
+ *   fastest: the layout of a filter in the model vector.
+ * Project decisions: Matlab's imresize(..., 'bilinear') is not reproduced (toolbox code that antialiases when shrinking and
+ *   works in double; nothing here can pin it), nor is the double-precision mex features.cc.  The example holds what this detector
+ *   computes on that patch, so a filter trained on it meets the same features at detection time.  A one-channel frame is used as
+ *   the handle's HOG uses one (Matlab's repmat to three equal channels gives the same gradients).
+ * Skip rule: with skip_small != 0 a box with (double)width * height < ((double)k * s)^2 is skipped (train.m:135-143 with
+ *   minsize = prod(model.maxsize * model.sbin)).
+ * Example of a kept box i, pbd_examples' format and strides (pbd_example_stride):
+ *   hdr = {i, 0, nblocks, nvalues, (offset, length) x nblocks, 0 ...}; with bias >= 0 the blocks are (bias, 1) holding 1, then
+ *   (nbias + 4 ndefs + filter_offset[filter], k * k * flen) holding the features (qp_poswrite's order); with bias == -1 only the
+ *   filter block.  Values past nvalues are not written.
+ * A skipped box gets hdr = {i, 0, -1, 0, 0 ...} and no values: the invalid marker pbd_qp_add_device skips.
+ * pbd_warp_positives: hdr int32[nboxes][hdr_words], values T[nboxes][values] and kept int32[nboxes] (1 / 0) on the host.
+ *   Synchronous.
+ * pbd_warp_positives_device: d_hdr / d_values as pbd_examples_device; d_payload = int32[1 + capacity * pbd_candidate_stride()],
+ *   word 0 = nboxes, record i = {frame = id_offset + i, component 0, level 0, root_x 0, root_y 0, score 0, nparts 0, 0, zeros},
+ *   so that pbd_qp_add_device(q, h, d_payload, capacity, d_hdr, d_values, 1, id_base, ...) writes the ids
+ *   {1, id_base + id_offset + i, 0, 0, 0} (ex.id = [1 id 0 0 0]).  nboxes > capacity: PBD_ERR_CAPACITY before anything is
+ *   enqueued.  Asynchronous on pbd_stream() (the call returns once its tap tables, 28 P bytes per kept box for 8-bit frames
+ *   and 40 P for the other depths, are staged in pinned memory and the kernels are enqueued).
+ * Refused before anything is enqueued, naming the offending index, the handle unchanged: PBD_ERR_INVALID for a filter outside
+ *   0..nfilters-1, a bias outside -1..nbias-1, a box whose frame index is outside 0..nframes-1 or with x2 < x1 or y2 < y1 or a
+ *   coordinate outside +-2^24 (the tap positions are floats), the frame refusals of pbd_detect_frames (a NULL or empty frame, a
+ *   pitch below the row, channels other than 1 or 3, a misaligned device frame; PBD_ERR_UNSUPPORTED for another depth_code) and
+ *   its NaN / Inf refusal for host 32F / 64F frames, NULL pointers with nboxes > 0, nboxes < 0; PBD_ERR_STATE while a batch is
+ *   in flight or after a pbd_conv_set_filters whose bank no longer matches the model.  nboxes == 0 is PBD_OK (the device
+ *   payload's word 0 is then 0).
+ * The call works in the handle's pyramid and HOG workspaces, so the resident detect result is dropped as after
+ * pbd_conv_set_filters: pbd_get_stage, pbd_examples*, pbd_argmin_device_out and pbd_dp_argmin give PBD_ERR_STATE until the next
+ * detect call (a refused call and a call with nboxes == 0 leave it).  The detect path itself is untouched: a detect call gives
+ * the same bytes before and after. */
+int pbd_warp_positives(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, int nboxes,
+                       const int32_t *boxes, int filter, int bias, int skip_small, int32_t *hdr, void *values, int32_t *kept);
+int pbd_warp_positives_device(pbd_handle *h, int nframes, const struct pbd_frame *d_frames, int channels, int depth_code, int nboxes,
+                              const int32_t *boxes, int filter, int bias, int skip_small, int id_offset, int32_t *d_payload,
+                              int capacity, int32_t *d_hdr, void *d_values);
 
 /* ---- Training QP (new surface; opt-in): the dual coordinate-descent solver of the reference's Matlab training code
  * (matlab/learning/qp_write.m, qp_one.m with oct/qp_one_sparse.cc, qp_opt.m, qp_refresh.m with oct/lincomb.cc, qp_prune.m,
@@ -791,6 +848,9 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        /* the training QP (pbd_qp_*): named for traces; a pbd_qp has no profile and a handle's profile does not see them */
        PBD_K_QP_WRITE, PBD_K_QP_SCORE, PBD_K_QP_PASS, PBD_K_QP_LINCOMB, PBD_K_QP_SLOTS, PBD_K_QP_NORM, PBD_K_QP_WRAW,
        PBD_K_QP_GATHER,
+       /* pbd_warp_positives*: the patches of the kept boxes, then every box's example (the HOG of the patches is timed under
+          k_hog_hist / k_hog_feat) */
+       PBD_K_WARP, PBD_K_WARP_EMIT,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

@@ -930,6 +930,50 @@ public:
         found.assign(n, false);
         for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
     }
+    // warped positives (matlab/learning/train.m poswarp, warppos.m, qp_poswrite) on the device (pbd_warp_positives): boxes holds
+    // five values per box, {image, x1, y1, x2, y2} (0-based, inclusive); each box is padded by one cell, cropped with edge
+    // replication, resized to (k + 2) * sbin pixels and its HOG written as the example [bias = 1 | filter block] of filter
+    // `filter` (bias -1: the filter block alone) in examples()' format.  kept[i] = false: skipped as smaller than the filter's
+    // pixels (skipSmall), its header marked invalid (hdr[2] = -1).  One depth and one channel count per call.
+    void warpPositives(const std::vector<Image> &images, const std::vector<int32_t> &boxes, int filter, int bias, bool skipSmall,
+                       std::vector<int32_t> &hdr, std::vector<T> &values, std::vector<bool> &kept, int &hdr_words, int &nvalues)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "warpPositives() before distributeModel()");
+        if (boxes.size() % 5) throw Error(PBD_ERR_INVALID, "warpPositives: five values per box {image, x1, y1, x2, y2}");
+        pbdbind::check<HostTraits<T> >(h_, pbd_example_stride(h_, &hdr_words, &nvalues));
+        const size_t n = boxes.size() / 5, nf = images.size();
+        std::vector<pbd_frame> fr(nf + 1);
+        for (size_t i = 0; i < nf; ++i) {
+            fr[i].data = images[i].data; fr[i].rows = images[i].rows; fr[i].cols = images[i].cols; fr[i].stride_bytes = images[i].step;
+        }
+        hdr.assign(n * (size_t)hdr_words + 1, 0);
+        values.assign(n * (size_t)nvalues + 1, T(0));
+        std::vector<int32_t> kp(n + 1, 0), bx(boxes);
+        bx.push_back(0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_warp_positives(h_, (int)nf, &fr[0], nf ? images[0].channels : 3, nf ? images[0].depth : 0,
+                                                              (int)n, &bx[0], filter, bias, skipSmall ? 1 : 0, &hdr[0], &values[0], &kp[0]));
+        hdr.resize(hdr.size() - 1);
+        values.resize(values.size() - 1);
+        kept.assign(n, false);
+        for (size_t i = 0; i < n; ++i) kept[i] = kp[i] != 0;
+    }
+    // the device form (pbd_warp_positives_device): d_frames are device frames (a region of a larger image is read in place
+    // through its pitch), the examples and the payload (word 0 = boxes, record i = {idOffset + i, 0 ...}) stay on the device for
+    // QP::addDevice / pbd_qp_add_device; asynchronous on the detector's stream
+    void warpPositivesDevice(const std::vector<pbd_frame> &d_frames, int channels, int depth, const std::vector<int32_t> &boxes,
+                             int filter, int bias, bool skipSmall, int idOffset, int32_t *d_payload, int capacity, int32_t *d_hdr,
+                             T *d_values)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "warpPositivesDevice() before distributeModel()");
+        if (boxes.size() % 5) throw Error(PBD_ERR_INVALID, "warpPositivesDevice: five values per box {frame, x1, y1, x2, y2}");
+        std::vector<pbd_frame> fr(d_frames);
+        fr.push_back(pbd_frame());
+        std::vector<int32_t> bx(boxes);
+        bx.push_back(0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_warp_positives_device(h_, (int)d_frames.size(), &fr[0], channels, depth,
+                                                                     (int)(boxes.size() / 5), &bx[0], filter, bias, skipSmall ? 1 : 0,
+                                                                     idOffset, d_payload, capacity, d_hdr, d_values));
+    }
 };
 
 // A stream of single frames over K handles (K HIP streams + workspaces) of one GPU, fed round-robin -- new surface: the

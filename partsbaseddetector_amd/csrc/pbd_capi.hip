@@ -61,12 +61,6 @@ int plan_pyramid(int rows, int cols, int sbin, int interval, std::vector<int> &l
     return n;
 }
 
-inline short sat_short_round(float v)
-{
-    long iv = lrint((double)v);
-    return (short)(iv < -32768 ? -32768 : iv > 32767 ? 32767 : iv);
-}
-
 // ---- plan construction -------------------------------------------------------------------------
 // Cover a rows x cols level with 256-cell tiles of shape 32x8, 16x16 or 8x32 (shape k: 32>>k wide, 8<<k
 // high) so that the fewest lanes compute cells outside the level: a dynamic program over the columns picks
@@ -245,28 +239,11 @@ int image_plan_host(int rows, int cols, int sbin, int interval, Plan &Pr, std::s
         cell += (long long)d.rows * d.cols;
         if (l == interval - 1) P->npix_resized = pix;
         if (l < interval) {
-            // cv::resize INTER_LINEAR 8U coefficient tables (OpenCV imgwarp.cpp)
-            const double scale_x = 1. / ((double)lc[l] / cols), scale_y = 1. / ((double)lr[l] / rows);
+            // cv::resize INTER_LINEAR coefficient tables (resize_taps_x / _y, pbd_handle.h)
             d.tab_x = (int)tabx.size();
             d.tab_y = (int)taby.size();
-            for (int dx = 0; dx < lc[l]; ++dx) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)floorf(fx);
-                fx -= (float)sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                const int last = sx >= cols - 1;
-                if (last) { fx = 0; sx = cols - 1; }
-                tabx.push_back({sx, sat_short_round((1.f - fx) * 2048), sat_short_round(fx * 2048)});
-                tabxf.push_back({sx, last, 1.f - fx, fx});
-            }
-            for (int dy = 0; dy < lr[l]; ++dy) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = (int)floorf(fy);
-                fy -= (float)sy;
-                const int y0 = std::min(std::max(sy, 0), rows - 1), y1 = std::min(std::max(sy + 1, 0), rows - 1);
-                taby.push_back({y0, y1, sat_short_round((1.f - fy) * 2048), sat_short_round(fy * 2048)});
-                tabyf.push_back({y0, y1, 1.f - fy, fy});
-            }
+            resize_taps_x(cols, lc[l], tabx, tabxf);
+            resize_taps_y(rows, lr[l], taby, tabyf);
         }
     }
     P->pix_per_frame = pix; P->blk_per_frame = blk; P->cell_per_frame = cell;
@@ -1522,10 +1499,18 @@ int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int 
         return fail(h, PBD_ERR_UNSUPPORTED, "mixed-size calls with level sharding (world %d): pbd_set_level_shard(h, 0, 1) first",
                     h->shard_world);
     if (int rc = check_batch(h, nframes)) return rc;
+    if (int rc = check_frame_descs(h, nframes, frames, cn, depth, host)) return rc;
+    std::vector<int> rows(nframes), cols(nframes);
+    for (int f = 0; f < nframes; ++f) { rows[f] = frames[f].rows; cols[f] = frames[f].cols; }
+    if (int rc = check_bank(h)) return rc;
+    return get_mixed_plan(h, nframes, rows.data(), cols.data(), plan);
+}
+
+int check_frame_descs(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host)
+{
     if (!depth_size(depth))
         return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth);
     if (cn != 1 && cn != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", cn);
-    std::vector<int> rows(nframes), cols(nframes);
     for (int f = 0; f < nframes; ++f) {
         const pbd_frame &fr = frames[f];
         if (!fr.data || fr.rows < 1 || fr.cols < 1 || fr.rows > 32000 || fr.cols > 32000)
@@ -1545,19 +1530,14 @@ int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int 
                 if (!ok) return fail(h, PBD_ERR_INVALID, "frame %d, row %d holds a NaN or Inf pixel", f, y);
             }
         }
-        rows[f] = fr.rows; cols[f] = fr.cols;
     }
-    if (int rc = check_bank(h)) return rc;
-    return get_mixed_plan(h, nframes, rows.data(), cols.data(), plan);
+    return PBD_OK;
 }
 
-// pyramid -> HOG -> convolution -> dynamic program of a mixed-size call that passed check_frames_mixed (no host synchronisation)
-int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
-                         const LatentParams *mask)
+int frame_descs(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, std::vector<FrameDesc> &fd)
 {
-    h->res = Resident{&P, 1, cn, depth};
     const size_t es = depth_size(depth);
-    std::vector<FrameDesc> fd(nframes);
+    fd.resize(nframes);
     if (host) {   // the frames go to the handle's frame buffer, packed, each with its own dense rows
         size_t total = 0;
         for (int f = 0; f < nframes; ++f) total += (size_t)frames[f].rows * frames[f].cols * cn * es;
@@ -1575,6 +1555,16 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
         for (int f = 0; f < nframes; ++f)
             fd[f] = FrameDesc{static_cast<const uint8_t *>(frames[f].data), frames[f].rows, frames[f].cols, (long long)frames[f].stride_bytes};
     }
+    return PBD_OK;
+}
+
+// pyramid -> HOG -> convolution -> dynamic program of a mixed-size call that passed check_frames_mixed (no host synchronisation)
+int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
+                         const LatentParams *mask)
+{
+    h->res = Resident{&P, 1, cn, depth};
+    std::vector<FrameDesc> fd;
+    if (int rc = frame_descs(h, nframes, frames, cn, depth, host, fd)) return rc;
     if (int rc = h->fd_tab.stage(h, fd.data(), fd.size() * sizeof(FrameDesc))) return rc;
     if (int rc = alloc_features(h, P, 1, cn, depth)) return rc;
     launch_features_mixed(h, P, h->fd_tab.as<FrameDesc>(), cn, depth, h->stream);
@@ -1590,6 +1580,43 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     }
     return run_dp_mixed(h, P);
 }
+
+// Warped positives: n kept boxes are the n levels of one virtual frame, each a P x P image that no pyramid kernel writes
+// (src_level -1, no resize tables: k_warp fills them), so the HOG stage runs over them as over any plan's levels.
+int warp_plan(pbd_handle *h, int n, int P, int cn, int depth, Plan **out)
+{
+    const std::vector<int> key{n, P};
+    if (!h->wp_plan || h->wp_plan->key_dims != key) {
+        auto W = std::make_unique<Plan>();
+        W->kind = 1; W->key_dims = key; W->nlevels = n; W->interval = h->interval;
+        W->lv.resize(n);
+        W->scales.assign(n, 1.f);
+        const int blk = (int)roundf((float)P / (float)h->sbin);   // HOGFeatures.cpp:174: k + 2 exactly
+        for (int l = 0; l < n; ++l) {
+            LevelDesc &d = W->lv[l];
+            memset(&d, 0, sizeof d);
+            d.img_rows = d.img_cols = P;
+            d.blk_rows = d.blk_cols = blk;
+            d.rows = d.cols = std::max(blk - 2, 0);
+            d.src_level = -1;
+            d.img_off = (long long)l * P * P;
+            d.blk_off = (long long)l * blk * blk;
+            d.cell_off = (long long)l * d.rows * d.cols;
+        }
+        W->pix_per_frame = (long long)n * P * P;
+        W->npix_resized = W->pix_per_frame;
+        W->blk_per_frame = (long long)n * blk * blk;
+        W->cell_per_frame = n ? W->lv[n - 1].cell_off + (long long)W->lv[n - 1].rows * W->lv[n - 1].cols : 0;
+        HIPCHK(h, finish_plan_tables(*W, h->sbin));
+        h->wp_plan = std::move(W);
+    }
+    if (int rc = grow_coord(h, P, P)) return rc;
+    if (int rc = alloc_features(h, *h->wp_plan, 1, cn, depth)) return rc;
+    *out = h->wp_plan.get();
+    return PBD_OK;
+}
+
+void warp_hog(pbd_handle *h, Plan &W, int cn, int depth) { launch_hog_stage(h, W, cn, depth, 0, 1, h->stream); }
 
 }  // namespace pbd
 
@@ -2258,7 +2285,7 @@ const char *pbd_kernel_name(int k)
                                              "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile",
                                              "k_part_poses", "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score",
                                              "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
-                                             "k_qp_gather"};
+                                             "k_qp_gather", "k_warp", "k_warp_emit"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

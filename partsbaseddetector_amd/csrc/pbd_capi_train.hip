@@ -191,10 +191,172 @@ int update_model(pbd_handle *h, const MuSource &src)
     return PBD_OK;
 }
 
+// ---- warped positives (the kernels: pbd_kernels_warp.hip) -----------------------------------------------
+// Both forms of pbd_warp_positives.  Host form: `kept` set, d_payload NULL, hdr / values host buffers.  Device form: kept NULL,
+// hdr / values device buffers.  Every refusal comes before the first copy or kernel.
+int warp_positives(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, int nboxes, const int32_t *boxes, int filter,
+                   int bias, int skip_small, bool host, int id_offset, int32_t *d_payload, int capacity, int32_t *hdr, void *values,
+                   int32_t *kept)
+{
+    if (nboxes < 0 || nframes < 0) return fail(h, PBD_ERR_INVALID, "nboxes %d, nframes %d", nboxes, nframes);
+    if (!host) {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (nboxes > capacity) return fail(h, PBD_ERR_CAPACITY, "%d boxes, the payload holds %d records", nboxes, capacity);
+    }
+    if (int rc = check_bank(h)) return rc;
+    if (h->filter_ksize != h->model_ksize)
+        return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
+    const int nfilters = (int)h->model_ksize.size();
+    if (filter < 0 || filter >= nfilters) return fail(h, PBD_ERR_INVALID, "filter %d outside 0..%d", filter, nfilters - 1);
+    if (bias < -1 || bias >= h->nbias) return fail(h, PBD_ERR_INVALID, "bias %d outside -1..%d", bias, h->nbias - 1);
+    if (int rc = check_frame_descs(h, frames ? nframes : 0, frames, cn, depth, host)) return rc;   // frames may be NULL without boxes
+    const int k = h->model_ksize[filter], s = h->sbin, P = (k + 2) * s;
+    if ((bias >= 0 ? 1 : 0) + k * k * 32 > h->ex_values)   // a filter no part uses may be larger than any example
+        return fail(h, PBD_ERR_INVALID, "filter %d (%d x %d) does not fit an example of %d values", filter, k, k, h->ex_values);
+    constexpr int kCoordMax = 1 << 24;   // the tap positions of the resize are floats
+    for (int i = 0; i < nboxes; ++i) {
+        const int32_t *b = boxes + 5 * (size_t)i;
+        if (b[0] < 0 || b[0] >= nframes) return fail(h, PBD_ERR_INVALID, "box %d: frame %d outside 0..%d", i, b[0], nframes - 1);
+        if (b[3] < b[1] || b[4] < b[2]) return fail(h, PBD_ERR_INVALID, "box %d: (%d, %d) .. (%d, %d) is empty", i, b[1], b[2], b[3], b[4]);
+        for (int c = 1; c < 5; ++c)
+            if (b[c] < -kCoordMax || b[c] > kCoordMax) return fail(h, PBD_ERR_INVALID, "box %d: coordinate %d outside +-2^24", i, b[c]);
+    }
+    if (nboxes == 0) {
+        if (d_payload) HIPCHK(h, hipMemsetAsync(d_payload, 0, sizeof(int32_t), h->stream));
+        return PBD_OK;
+    }
+    // the kept boxes and their windows (warppos.m:21-26 in Matlab's 1-based coordinates; round() rounds halves away from zero)
+    std::vector<int> slot(nboxes, -1), box_frame;
+    struct Win { int x0, y0, w, h; };   // 0-based first column / row, size
+    std::vector<Win> wins;
+    const double minsize = ((double)k * s) * ((double)k * s);
+    for (int i = 0; i < nboxes; ++i) {
+        const int32_t *b = boxes + 5 * (size_t)i;
+        const double width = (double)b[3] - b[1] + 1, height = (double)b[4] - b[2] + 1;
+        const bool keep = !(skip_small && width * height < minsize);
+        if (kept) kept[i] = keep ? 1 : 0;
+        if (!keep) continue;
+        const double padx = (double)s * width / ((double)k * s), pady = (double)s * height / ((double)k * s);
+        const long long X1 = (long long)round(((double)b[1] + 1) - padx), X2 = (long long)round(((double)b[3] + 1) + padx);
+        const long long Y1 = (long long)round(((double)b[2] + 1) - pady), Y2 = (long long)round(((double)b[4] + 1) + pady);
+        slot[i] = (int)wins.size();
+        wins.push_back(Win{(int)(X1 - 1), (int)(Y1 - 1), (int)(X2 - X1 + 1), (int)(Y2 - Y1 + 1)});
+        box_frame.push_back(b[0]);
+    }
+    const int nkept = (int)wins.size();
+    if ((long long)nkept * P * P > INT32_MAX) return fail(h, PBD_ERR_INVALID, "%d kept boxes of %d x %d pixels: more than 2^31 pixels in one call", nkept, P, P);
+
+    // From here on the handle's pyramid and HOG workspaces are this call's: the resident detect result is gone.
+    h->res.clear();
+    std::vector<FrameDesc> fd;
+    if (int rc = frame_descs(h, nframes, frames, cn, depth, host, fd)) return rc;
+    Plan *W = nullptr;
+    if (nkept)
+        if (int rc = warp_plan(h, nkept, P, cn, depth, &W)) return rc;
+
+    // one staged block: frames, box -> frame, box -> kept index, column taps, column and row coefficients
+    const bool fix = depth == kDepth8U;
+    const size_t cxs = fix ? sizeof(ResizeTabX) : sizeof(ResizeTabXf), cys = fix ? sizeof(ResizeTabY) : sizeof(ResizeTabYf);
+    size_t off = 0;
+    auto piece = [&](size_t bytes) { off = Carve::up(off, 256); const size_t o = off; off += bytes; return o; };
+    const size_t o_fd = piece(fd.size() * sizeof(FrameDesc)), o_bf = piece((size_t)nkept * sizeof(int)), o_slot = piece((size_t)nboxes * sizeof(int)),
+                 o_tap = piece((size_t)nkept * P * sizeof(WarpTap)), o_cx = piece((size_t)nkept * P * cxs), o_cy = piece((size_t)nkept * P * cys);
+    std::vector<uint8_t> blob(off, 0);
+    memcpy(blob.data() + o_fd, fd.data(), fd.size() * sizeof(FrameDesc));
+    if (nkept) memcpy(blob.data() + o_bf, box_frame.data(), (size_t)nkept * sizeof(int));
+    memcpy(blob.data() + o_slot, slot.data(), (size_t)nboxes * sizeof(int));
+    std::vector<ResizeTabX> tx; std::vector<ResizeTabXf> txf; std::vector<ResizeTabY> ty; std::vector<ResizeTabYf> tyf;
+    for (int j = 0; j < nkept; ++j) {
+        const Win &w = wins[j];
+        const pbd_frame &fr = frames[box_frame[j]];
+        auto cx = [&](long long v) { return (int)std::min<long long>(std::max<long long>(v, 0), fr.cols - 1); };
+        auto cy = [&](long long v) { return (int)std::min<long long>(std::max<long long>(v, 0), fr.rows - 1); };
+        tx.clear(); txf.clear(); ty.clear(); tyf.clear();
+        resize_taps_x(w.w, P, tx, txf);   // source = the window, destination = the patch
+        resize_taps_y(w.h, P, ty, tyf);
+        WarpTap *tap = reinterpret_cast<WarpTap *>(blob.data() + o_tap) + (size_t)j * P;
+        for (int d = 0; d < P; ++d) {
+            const int sx = tx[d].sx, sx1 = sx + 1 < w.w ? sx + 1 : sx;   // the second tap; none past the window's last column
+            tap[d] = WarpTap{cx((long long)w.x0 + sx), cx((long long)w.x0 + sx1)};
+            ty[d].y0 = tyf[d].y0 = cy((long long)w.y0 + ty[d].y0);
+            ty[d].y1 = tyf[d].y1 = cy((long long)w.y0 + ty[d].y1);
+        }
+        if (fix) {
+            memcpy(blob.data() + o_cx + (size_t)j * P * cxs, tx.data(), P * cxs);
+            memcpy(blob.data() + o_cy + (size_t)j * P * cys, ty.data(), P * cys);
+        } else {
+            memcpy(blob.data() + o_cx + (size_t)j * P * cxs, txf.data(), P * cxs);
+            memcpy(blob.data() + o_cy + (size_t)j * P * cys, tyf.data(), P * cys);
+        }
+    }
+    int32_t *d_hdr = hdr;
+    char *d_val = static_cast<char *>(values);
+    const size_t hb = (size_t)nboxes * h->ex_hdr_words * sizeof(int32_t), vrow = (size_t)h->ex_values * h->rs;
+    if (host)
+        if (int rc = carve(h, h->wp_out, [&](Carve &c) { d_hdr = c.take<int32_t>(hb); d_val = c.take<char>(vrow * nboxes); })) return rc;
+    if (int rc = h->wp_tab.stage(h, blob.data(), blob.size())) return rc;
+    const uint8_t *tb = h->wp_tab.as<uint8_t>();
+    WarpParams wp{};
+    wp.fd = reinterpret_cast<const FrameDesc *>(tb + o_fd);
+    wp.box_frame = reinterpret_cast<const int *>(tb + o_bf);
+    wp.slot = reinterpret_cast<const int *>(tb + o_slot);
+    wp.tapx = reinterpret_cast<const WarpTap *>(tb + o_tap);
+    wp.cx = tb + o_cx; wp.cy = tb + o_cy;
+    wp.nkept = nkept; wp.P = P; wp.cn = cn; wp.depth = depth;
+    wp.pyr = h->pyr.as<uint8_t>();
+    wp.nboxes = nboxes; wp.bias = bias;
+    wp.filter_off = (int)((long long)h->nbias + 4LL * h->ndefs + h->model_foff[filter]);
+    wp.filter_len = k * k * 32;
+    wp.feat = h->feat.p;
+    wp.hdr = d_hdr; wp.hdr_words = h->ex_hdr_words;
+    wp.values = d_val; wp.vstride = h->ex_values;
+    wp.payload = d_payload; wp.rec_stride = stride(h); wp.id_offset = id_offset;
+    if (nkept) {
+        { ProfScope ps(h, PBD_K_WARP, h->stream); launch_warp(wp, h->stream); }
+        warp_hog(h, *W, cn, depth);
+    }
+    { ProfScope ps(h, PBD_K_WARP_EMIT, h->stream); launch_warp_emit(wp, h->f64, h->stream); }
+    HIPCHK(h, hipGetLastError());
+    if (!host) return PBD_OK;
+    HIPCHK(h, hipMemcpyAsync(hdr, d_hdr, hb, hipMemcpyDeviceToHost, h->stream));
+    // the values of every run of kept boxes, nvalues per row: nothing past nvalues and no row of a skipped box is written
+    const size_t nvb = (size_t)((bias >= 0 ? 1 : 0) + k * k * 32) * h->rs;
+    for (int i = 0; i < nboxes;) {
+        if (slot[i] < 0) { ++i; continue; }
+        int e = i;
+        while (e < nboxes && slot[e] >= 0) ++e;
+        HIPCHK(h, hipMemcpy2DAsync(static_cast<char *>(values) + vrow * i, vrow, d_val + vrow * i, vrow, nvb, (size_t)(e - i),
+                                   hipMemcpyDeviceToHost, h->stream));
+        i = e;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PBD_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
 extern "C" {
+
+// Warped positives (matlab/learning/train.m poswarp, warppos.m, qp_poswrite).  See include/pbd.h.
+int pbd_warp_positives(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int nboxes,
+                       const int32_t *boxes, int filter, int bias, int skip_small, int32_t *hdr, void *values, int32_t *kept)
+{
+    return entry(h, nboxes <= 0 || (frames && boxes && hdr && values && kept), kIdle, [&]() -> int {
+        return warp_positives(h, nframes, frames, channels, depth_code, nboxes, boxes, filter, bias, skip_small, true, 0, nullptr, 0, hdr,
+                              values, kept);
+    });
+}
+
+int pbd_warp_positives_device(pbd_handle *h, int nframes, const pbd_frame *d_frames, int channels, int depth_code, int nboxes,
+                              const int32_t *boxes, int filter, int bias, int skip_small, int id_offset, int32_t *d_payload,
+                              int capacity, int32_t *d_hdr, void *d_values)
+{
+    return entry(h, d_payload && (nboxes <= 0 || (d_frames && boxes && d_hdr && d_values)), kIdle, [&]() -> int {
+        return warp_positives(h, nframes, d_frames, channels, depth_code, nboxes, boxes, filter, bias, skip_small, false, id_offset,
+                              d_payload, capacity, d_hdr, d_values, nullptr);
+    });
+}
 
 // Training examples (matlab/detection/detect.m backtrack + qp_write).  See include/pbd.h.
 int pbd_model_vector_len(const pbd_handle *h) { return h ? (int)(h->mvec.size() / h->rs) : 0; }

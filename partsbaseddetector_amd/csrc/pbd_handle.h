@@ -196,6 +196,42 @@ struct Plan {
     std::vector<long long> chunk_cell0;
 };
 
+// cv::resize INTER_LINEAR coefficient tables of one axis (OpenCV imgwarp.cpp), appended to `fix` (8-bit
+// fixed point) and `flt` (16U / 32F / 64F): destination index 0..dst-1 from a source of `src` elements.  Columns: the first tap
+// sx (the second is sx + 1; `last`: sx is the last source column and the only tap); rows: the two taps, clamped to the source.
+// The resized pyramid levels and the warped positives' patches are built from these and nothing else.
+inline short sat_short_round(float v)
+{
+    long iv = lrint((double)v);
+    return (short)(iv < -32768 ? -32768 : iv > 32767 ? 32767 : iv);
+}
+inline void resize_taps_x(int src, int dst, std::vector<ResizeTabX> &fix, std::vector<ResizeTabXf> &flt)
+{
+    const double scale_x = 1. / ((double)dst / src);
+    for (int dx = 0; dx < dst; ++dx) {
+        float fx = (float)((dx + 0.5) * scale_x - 0.5);
+        int sx = (int)floorf(fx);
+        fx -= (float)sx;
+        if (sx < 0) { fx = 0; sx = 0; }
+        const int last = sx >= src - 1;
+        if (last) { fx = 0; sx = src - 1; }
+        fix.push_back({sx, sat_short_round((1.f - fx) * 2048), sat_short_round(fx * 2048)});
+        flt.push_back({sx, last, 1.f - fx, fx});
+    }
+}
+inline void resize_taps_y(int src, int dst, std::vector<ResizeTabY> &fix, std::vector<ResizeTabYf> &flt)
+{
+    const double scale_y = 1. / ((double)dst / src);
+    for (int dy = 0; dy < dst; ++dy) {
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        int sy = (int)floorf(fy);
+        fy -= (float)sy;
+        const int y0 = std::min(std::max(sy, 0), src - 1), y1 = std::min(std::max(sy + 1, 0), src - 1);
+        fix.push_back({y0, y1, sat_short_round((1.f - fy) * 2048), sat_short_round(fy * 2048)});
+        flt.push_back({y0, y1, 1.f - fy, fy});
+    }
+}
+
 struct Group {   // DT jobs of the parts of one tree depth + combine jobs of their parents
     std::vector<DtJob> jobs;
     std::vector<ChildDesc> childs;
@@ -396,6 +432,11 @@ struct Handle : ErrCtx {
     DevBuf lat_in, lat_pay;
     // mixed-size calls: the FrameDesc table
     StagedTable fd_tab;
+    // pbd_warp_positives*: the plan whose levels are the kept boxes' patches (rebuilt when the kept count or the patch size
+    // changes), the call's tables (frames, boxes, taps and coefficients in one staged block), the host form's outputs
+    std::unique_ptr<Plan> wp_plan;
+    StagedTable wp_tab;
+    DevBuf wp_out;
 
     // A candidate list on its way out.  The device side is the "payload" the find / walk kernels write: word 0 = roots
     // found, then the records, already in (frame, level, component, y, x) order.  The host side is a pinned mirror: the
@@ -573,6 +614,14 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
 int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan);
 int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
                          const LatentParams *mask = nullptr);
+// the depth, channel and per-frame checks of a mixed-size call (no plan is made); the frames' descriptors on the device side:
+// host frames are packed into the handle's frame buffer (copies enqueued on its stream), device frames are read in place
+int check_frame_descs(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host);
+int frame_descs(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, std::vector<FrameDesc> &fd);
+// pbd_warp_positives*: the plan of n patches of P x P pixels (h->wp_plan) with the pyramid and HOG workspaces sized for it;
+// the HOG stage over the patches k_warp wrote into h->pyr
+int warp_plan(pbd_handle *h, int n, int P, int cn, int depth, Plan **out);
+void warp_hog(pbd_handle *h, Plan &W, int cn, int depth);
 
 }  // namespace pbd
 

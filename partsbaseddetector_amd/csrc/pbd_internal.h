@@ -601,6 +601,32 @@ struct LatentParams {
 void launch_latent_mask(const LatentParams &p, bool f64, hipStream_t s);
 void launch_latent_best(const LatentParams &p, bool f64, hipStream_t s);
 
+// warped positives (pbd_warp_positives*; pbd_kernels_warp.hip).  Kept box j is level j of a plan of `nkept` P x P level images
+// (image j at pixel j * P * P of the pyramid buffer, its k x k cells at cell j * k * k of the feature buffer): k_warp writes the
+// images, the HOG launches of the detect path turn them into features, k_warp_emit writes every box's example.
+struct WarpTap { int i0, i1; };   // the two source columns of a destination column: window taps, clamped into the frame
+struct WarpParams {
+    const FrameDesc *fd;          // the call's frames
+    const int *box_frame;         // [nkept] frame of kept box j
+    const WarpTap *tapx;          // [nkept][P]
+    const void *cx, *cy;          // [nkept][P] coefficients: ResizeTabX / ResizeTabY (8U) or ResizeTabXf / ResizeTabYf; the y0, y1
+                                  // of cy are the two source rows, clamped into the frame; sx of cx is not used
+    int nkept, P, cn, depth;
+    uint8_t *pyr;                 // [nkept][P][P][cn] elements of the image depth
+    // k_warp_emit
+    int nboxes;
+    const int *slot;              // [nboxes] the kept index j of box i, -1: skipped
+    int bias;                     // the bias block's offset in w, -1: none
+    int filter_off, filter_len;   // the filter block in w: nbias + 4 ndefs + filter_offset[filter], k * k * flen
+    const void *feat;             // R [nkept][filter_len]
+    int32_t *hdr; int hdr_words;
+    void *values; int vstride;
+    int32_t *payload;             // word 0 = nboxes, then record i (NULL: the host form, no payload)
+    int rec_stride, id_offset;
+};
+void launch_warp(const WarpParams &p, hipStream_t s);
+void launch_warp_emit(const WarpParams &p, bool f64, hipStream_t s);
+
 // the training QP (pbd_qp_*; pbd_kernels_qp.hip).  One cache entry i: x[i * V ..] float values in stored block order, bm[i * V ..]
 // the block of every value, hd[i * HW ..] = {nblocks, nvalues, (offset in w, length, first value) x nblocks}, ids[i * 5 ..],
 // b, d, a (double) and sv (uint8).  Every kernel runs PBD_QP_LANES threads per workgroup (the lanes of the header's reduction).

@@ -397,6 +397,37 @@ class Handle:
         T[capacity * values] on the device; asynchronous on the handle's stream"""
         self.check(self.lib.pbd_examples_device(self.h, d_payload_ptr, capacity, frame_offset, d_hdr_ptr, d_values_ptr))
 
+    def warp_positives(self, frames, boxes, filter: int = 0, bias: int = 0, skip_small: bool = True):
+        """pbd_warp_positives: (hdr (n, hdr_words) int32, values (n, values) T, kept (n,) int32) of boxes (n, 5) = frame, x1, y1,
+        x2, y2 (0-based, inclusive) in `frames` (arrays of one dtype and channel count, any sizes): every box padded by one cell,
+        cropped with edge replication, resized to (k + 2) * sbin pixels, its HOG as the example [bias = 1 | filter block];
+        a box skipped as too small has hdr[2] = -1.  Values past nvalues and the rows of skipped boxes stay 0.  The resident
+        detect result is dropped."""
+        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
+        if fr and (any(f.dtype != fr[0].dtype or f.shape[2] != fr[0].shape[2] for f in fr) or fr[0].dtype not in _lib.DEPTH_CODE):
+            raise PbdError(-1, "one dtype (uint8, uint16, float32 or float64) and one channel count per call")
+        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        bx = np.ascontiguousarray(boxes, np.int32).reshape(-1, 5)
+        hw, vw = self.example_stride()
+        hdr = np.zeros((len(bx), hw), np.int32)
+        vals = np.zeros((len(bx), vw), self.dtype)
+        kept = np.zeros(len(bx), np.int32)
+        self.check(self.lib.pbd_warp_positives(self.h, len(fr), descs, fr[0].shape[2] if fr else 3,
+                                               _lib.DEPTH_CODE[fr[0].dtype] if fr else 0, len(bx), bx.ctypes.data if bx.size else None,
+                                               filter, bias, 1 if skip_small else 0, hdr.ctypes.data if hdr.size else None,
+                                               vals.ctypes.data if vals.size else None, kept.ctypes.data if kept.size else None))
+        return hdr, vals, kept
+
+    def warp_positives_device(self, descs, cn: int, depth_code: int, boxes, filter: int, bias: int, skip_small: bool, id_offset: int,
+                              d_payload_ptr: int, capacity: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
+        """pbd_warp_positives_device: frames (device pointer, rows, cols, pitch), boxes (n, 5) on the host; the examples into
+        int32[capacity * hdr_words] / T[capacity * values] and the payload int32[1 + capacity * stride] (word 0 = n, record i =
+        {id_offset + i, 0 ...}) on the device, ready for QP.add_device; asynchronous on the handle's stream"""
+        bx = np.ascontiguousarray(boxes, np.int32).reshape(-1, 5)
+        self.check(self.lib.pbd_warp_positives_device(self.h, len(descs), _lib.frame_array(descs), cn, depth_code, len(bx),
+                                                      bx.ctypes.data if bx.size else None, filter, bias, 1 if skip_small else 0,
+                                                      id_offset, d_payload_ptr, capacity, d_hdr_ptr, d_values_ptr))
+
     def depth_consistency(self, depths: Sequence[np.ndarray], records: np.ndarray, zfactor: float = 0.03, frame_offset: int = 0,
                           capacity: Optional[int] = None) -> np.ndarray:
         """pbd_depth_consistency: the records (n, stride) that SearchSpacePruning::filterCandidatesByDepth keeps, in input order,
@@ -957,6 +988,28 @@ class PartsBasedDetector:
             frames = [frames]
         rec, found = self.hd.detect_latent(list(frames), part_boxes, overlap, mixtures)
         return self.hd.unpack_candidates(rec.ravel(), len(rec)), found.astype(bool)
+
+    def warpPositives(self, frames, boxes, filter: int = 0, bias: int = 0, skip_small: bool = True):
+        """warped positives (matlab/learning/train.m poswarp with warppos.m and qp_poswrite) on the device (pbd_warp_positives):
+        boxes (n, 5) = frame, x1, y1, x2, y2 (0-based, inclusive) in `frames`; each is padded by one cell, cropped with edge
+        replication, resized to (k + 2) * sbin pixels with the detector's own resampler, and its HOG written as the example
+        [bias = 1 | filter block] of filter `filter` (bias -1: the filter block alone).  Returns (hdr (n, hdr_words) int32, values
+        (n, values) T, kept (n,) bool); with skip_small a box smaller than the filter's pixels is skipped (hdr[2] = -1).  The
+        examples go to QP.add as they are.  No flipping and no train() loop: those stay with the caller."""
+        self._need()
+        if isinstance(frames, np.ndarray) and frames.ndim in (2, 3) and (frames.ndim == 2 or frames.shape[2] in (1, 3)):
+            frames = [frames]
+        hdr, vals, kept = self.hd.warp_positives(list(frames), boxes, filter, bias, skip_small)
+        return hdr, vals, kept.astype(bool)
+
+    def warpPositives_device(self, descs, cn: int, depth_code: int, boxes, filter: int, bias: int, skip_small: bool, id_offset: int,
+                             d_payload_ptr: int, capacity: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
+        """pbd_warp_positives_device: frames already on the device as (pointer, rows, cols, pitch) -- regions of larger images
+        included --, the examples and the payload left on the device for QP.add_device(hd, d_payload, capacity, d_hdr, d_values,
+        1, id_base), which gives example i the id {1, id_base + id_offset + i, 0, 0, 0}; asynchronous on the detector's stream"""
+        self._need()
+        self.hd.warp_positives_device(descs, cn, depth_code, boxes, filter, bias, skip_small, id_offset, d_payload_ptr, capacity,
+                                      d_hdr_ptr, d_values_ptr)
 
     def updateModel(self, w_or_qp) -> None:
         """model = vec2model(qp_w, model) in place (matlab/learning/train.m after qp_opt): the detector's parameters become a model
