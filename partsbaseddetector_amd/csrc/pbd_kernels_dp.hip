@@ -10,7 +10,8 @@
 // processed one depth at a time; a part's input is its raw response plus its children's messages
 // added in descending child order, which is the order the reference accumulates them in
 // (src/DynamicProgram.cpp:95,154-156).  Compiled with -ffp-contract=off.
-#include "pbd_internal.h"
+#include "pbd_device.h"
+#include "pbd_dp.h"
 
 #include <math.h>
 
@@ -56,9 +57,6 @@ __device__ __forceinline__ R quad_val(double a, double b, int x, R y)
     if (BZ) return (R)(a * (double)__mul24(x, x) + (double)y);
     return (R)((a * (double)__mul24(x, x) + b * (double)x) + (double)y);     // |x| < 2^16
 }
-template <typename R> struct RealLimits;
-template <> struct RealLimits<float> { static __device__ __forceinline__ float inf() { return INFINITY; } };
-template <> struct RealLimits<double> { static __device__ __forceinline__ double inf() { return (double)INFINITY; } };
 
 // ------------------------------------------------------------------------------------------------
 // One 1-D transform per thread, streamed in chunks of CH elements.
@@ -92,10 +90,6 @@ constexpr int kDtCH = PBD_DT_CH;   // elements per streamed chunk of the rows pa
 #define PBD_DT_CHC 16
 #endif
 constexpr int kDtCHC = PBD_DT_CHC;  // ... of the columns pass
-#ifndef PBD_DT_WAVES
-#define PBD_DT_WAVES 1
-#endif
-constexpr int kDtWaves = PBD_DT_WAVES;   // waves per workgroup of the DT passes (each wave = 64 rows / columns)
 #ifndef PBD_DT_RING
 #define PBD_DT_RING 8
 #endif
@@ -103,7 +97,7 @@ constexpr int kDtT = PBD_DT_RING;    // ring entries per lane (power of two)
 
 // LDS layout of a wave's ring: [slot][z: 64 x R | s: 64 x R | v: 64 x int]; one address per lane, the rest
 // are immediate offsets.
-// NARROW (launches that do not fill the chip, see k_dt_rows: the wave uses its first L = 64 >> lane_shift lanes only): the same
+// NARROW (launches that do not fill the chip, see k_dt_pass: the wave uses its first L = 64 >> lane_shift lanes only): the same
 // 6 KB hold kDtT << lane_shift entries per lane, laid out [slot][z: L x R | s: L x R | v: L x int] -- with 16 lanes the ring is
 // 32 deep, with 4 lanes 128: rows of a VGA pyramid never spill, and a wave alone on its SIMD no longer waits for the memory
 // round trips of the spill / reload paths.  The geometry is then a run-time value (three more integer registers).
@@ -163,7 +157,7 @@ struct DtRing {
     }
 };
 
-// Position chunks (the read-out's pointers, the columns pass's carried pointers) are kept EPW to a 32-bit register: 4 when the
+// Position chunks (the read-out's pointers) are kept EPW to a 32-bit register: 4 when the
 // positions are bytes (uint8 planes), 1 otherwise -- sixteen-element chunks then cost 4 registers instead of 16 each, which is
 // what keeps the columns pass at 6 waves per SIMD without shortening its chunks (8-element chunks were 4 % faster than
 // unpacked 16-element ones but moved 1.5x the bytes: every 128-byte line of a column was fetched four times instead of twice).
@@ -179,11 +173,9 @@ template <int EPW> __device__ __forceinline__ void dt_put(int *w, int i, int v) 
     else w[i / EPW] |= v << (BITS * (i % EPW));
 }
 
-// AUX: the read-out additionally streams an int chunk per output chunk (prefetched one chunk ahead, q
-// descending) and hands it to `store` -- the columns pass uses it to carry the rows pass's pointers along.
-template <typename R, bool AUX, bool BZ, int CH, int EPW, bool NARROW, class LoadChunk, class StoreChunk, class AuxChunk>
-__device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, DtRing<R, NARROW> ring, LoadChunk load, StoreChunk store,
-                                          AuxChunk aux)
+// load(q0, buf) fetches elements [q0, q0 + CH) of the line (0 past its end), store(q0, out, ptr) takes their results
+template <typename R, bool BZ, int CH, int EPW, bool NARROW, class LoadChunk, class StoreChunk>
+__device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, DtRing<R, NARROW> ring, LoadChunk load, StoreChunk store)
 {
     R cur[CH], nxt[CH];
     load(0, cur);
@@ -216,13 +208,8 @@ __device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, Dt
     // read-out, q descending
     const int nch = (N + CH - 1) / CH;
     constexpr int NW = CH / EPW;
-    int aux_cur[NW], aux_nxt[NW];
-#pragma unroll
-    for (int i = 0; i < NW; ++i) { aux_cur[i] = 0; aux_nxt[i] = 0; }
-    if (AUX) aux((nch - 1) * CH, aux_cur);
     for (int cidx = nch - 1; cidx >= 0; --cidx) {
         const int q0 = cidx * CH;
-        if (AUX && cidx > 0) aux(q0 - CH, aux_nxt);
         R out[CH];
         int ptr[NW];
 #pragma unroll
@@ -243,109 +230,120 @@ __device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, Dt
                 dt_put<EPW>(ptr, i, vk);
             }
         }
-        store(q0, out, ptr, aux_cur);
-        if (AUX) {
-#pragma unroll
-            for (int i = 0; i < NW; ++i) aux_cur[i] = aux_nxt[i];
-        }
+        store(q0, out, ptr);
     }
 }
 
 typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef short v8s_u __attribute__((ext_vector_type(8), aligned(2)));
 typedef _Float16 v8h_u __attribute__((ext_vector_type(8), aligned(2)));
-typedef unsigned vchw_u __attribute__((ext_vector_type(PBD_DT_CHC / 4), aligned(1)));
 static_assert(kDtCHC % 8 == 0 && kDtCH % 8 == 0, "int16 pointers and fp16 responses are read 8 at a time");
 
-// ---- rows pass: thread = (flat row, job, frame); each lane streams its own row with 16-byte accesses ----
-// RH: the responses are fp16 (PBD_CONV_MFMA_F16); a template parameter so that the default kernels carry none of it
-// PT: element type of the position planes (uint8_t when no map side exceeds 256, else int16_t)
-template <typename R, bool RH, typename PT, bool BZ, bool NARROW>
-__global__ __launch_bounds__(64 * kDtWaves) void k_dt_rows(DpParams p)
+// ---- the two passes ---------------------------------------------------------------------------------------------------------
+// rows pass (COLS = false): a line is row y of a level, read from the job's score plane (the part's response, fp16 when RH, or
+// its accumulated score).  Both outputs go out TRANSPOSED ([x][y]): lanes are adjacent rows y, so every store instruction writes
+// whole lines.  The columns pass reads its column of values back with wide per-lane loads; the pointers go straight to their
+// persistent plane (IxRaw, kept transposed: only the candidates' walk and pbd_dp_min's read-back ever index it) -- the columns
+// pass used to carry them along (a load, 16 extracts and 16 byte stores per chunk, 8 registers) only to transpose them for the
+// combine step, which no longer reads them.
+// columns pass (COLS = true): a line is column x of the rows pass's transposed values, contiguous; lanes are adjacent columns,
+// so the [y][x] outputs (dt, IyRaw) are coalesced.
+template <typename R, typename PT> struct DtLine {
+    ScoreSrc<R> src;              // element q of the line is src[q]
+    int N;
+    R *outv; PT *outp;            // element q's value and position go to outv[q * ostr], outp[q * ostr]
+    int ostr;
+    double a, b;                  // the job's quadratic along the line, and its anchor
+    int os;
+    size_t stk;                   // first record of the (job, frame)'s spill stack; a wave's lanes own columns of it
+};
+// line idx of level l = flat line `flat` of the plan, for job j and frame fl of the chunk
+template <typename R, bool RH, typename PT, bool COLS>
+__device__ __forceinline__ DtLine<R, PT> dt_line(const DpParams &p, int flat, int j, int fl)
 {
-    constexpr int EPW = 4 / (int)sizeof(PT);
-    // grid = (job, frame, wave of 64 flat rows): the wave index is the SLOWEST dimension, so the long rows of
-    // the large levels are dispatched first and the tail of the launch is made of short ones
-    // lane_shift (0 .. 6): a group of 64 flat rows is spread over 1 .. 64 waves that use their first 64 .. 1 lanes only.
-    // A launch that does not fill the chip anyway (one frame, a few 1080p frames) then runs as more, narrower waves: the wave's
-    // pop loops iterate for the slowest of a few lanes instead of 64, and the launch takes what its longest rows take (launch_dt_rows).
-    static_assert(kDtWaves == 1, "one wave per workgroup");
-    const int sh = p.lane_shift, lanep = threadIdx.x;
-    if (lanep >= (64 >> sh)) return;
-    const int wv = (int)blockIdx.z >> sh, lane = (((int)blockIdx.z & ((1 << sh) - 1)) << (6 - sh)) + lanep;
-    if (wv * 64 >= p.nrows_flat) return;
-    const int r = wv * 64 + lane;
-    const bool active = r < p.nrows_flat;
-    const int rr = active ? r : p.nrows_flat - 1;
-    const int j = blockIdx.x, fl = blockIdx.y, frame = p.frame0 + fl;
-    const int l = p.row2level[rr];
+    const int l = (COLS ? p.col2level : p.row2level)[flat];
     const LevelDesc d = p.lv[l];
-    const int y = rr - p.rowoff[l];
-    const int W = d.cols;
-    const size_t HW = (size_t)d.rows * W;
+    const int idx = flat - (COLS ? p.coloff : p.rowoff)[l];
     const DtJob job = p.jobs[j];
-    const R *src = (job.from_acc ? static_cast<const R *>(p.acc) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NM
-                                 : static_cast<const R *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F) +
-                   (size_t)job.plane * HW + (size_t)y * W;
-    // fp16 responses (PBD_CONV_MFMA_F16): a leaf part's input is read as halves, same element index
-    const bool hsrc = RH && !job.from_acc;
-    const _Float16 *srch = static_cast<const _Float16 *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F +
-                           (size_t)job.plane * HW + (size_t)y * W;
-    // both outputs go out TRANSPOSED ([x][y]): lanes are adjacent rows y, so every store instruction writes whole lines.  The
-    // columns pass reads its column of values back with wide per-lane loads; the pointers go straight to their persistent plane
-    // (IxRaw, kept transposed: only the candidates' walk and pbd_dp_min's read-back ever index it) -- the columns pass used to
-    // carry them along (a load, 16 extracts and 16 byte stores per chunk, 8 registers) only to transpose them for the combine
-    // step, which no longer reads them
-    const int Hl = d.rows;
-    const size_t jb = ((size_t)fl * p.cell_per_frame + d.cell_off) * p.JG + (size_t)j * HW;
-    R *tmpT = static_cast<R *>(p.tmp) + jb + (size_t)y;
-    PT *ixT = static_cast<PT *>(p.IxRaw) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NJ + (size_t)job.gm * HW + (size_t)y;
-    __shared__ __attribute__((aligned(16))) char ring_mem[kDtWaves * kDtT * DtRing<R, NARROW>::kSlotBytes];
-    DtRing<R, NARROW> ring = DtRing<R, NARROW>::make(ring_mem, lanep, sh,
-                                     reinterpret_cast<StkPairT<R> *>(p.stk) +
-                                         ((size_t)(fl * p.JG + j) * p.stk_per_jf + p.stk_row_off[wv]) + lane, job.ax, job.bx);
-    const int N = active ? W : 0;
-    if (N == 0) return;
-    auto load = [&](int q0, R *buf) {
-        if (hsrc) {
-            if (q0 + kDtCH <= N) {
+    const LevelPlanes<DpParams> pl(p, d, p.frame0 + fl, fl);
+    const size_t jo = (size_t)j * pl.HW, go = (size_t)job.gm * pl.HW;
+    const size_t stk = (size_t)(fl * p.JG + j) * p.stk_per_jf;
+    if (COLS) return {{pl.tmp<R>(jo + (size_t)idx * d.rows), nullptr}, d.rows, pl.dt<R>(jo + idx), pl.iy<PT>(go + idx), d.cols,
+                      job.ay, job.by, job.osy, stk};
+    return {pl.score<R>(job.from_acc, RH, job.plane, (size_t)idx * d.cols), d.cols, pl.tmp<R>(jo + idx), pl.ix<PT>(go + idx), d.rows,
+            job.ax, job.bx, job.osx, stk};
+}
+
+// elements [q0, q0 + CH) of a line, 0 past its end: 16-byte accesses while the chunk is whole
+template <typename R, int CH>
+__device__ __forceinline__ void dt_load_chunk(const ScoreSrc<R> &src, int N, int q0, R *buf)
+{
+    if (src.h) {
+        if (q0 + CH <= N) {
 #pragma unroll
-                for (int v = 0; v < kDtCH / 8; ++v) {
-                    const v8h_u a0 = *reinterpret_cast<const v8h_u *>(srch + q0 + 8 * v);
+            for (int v = 0; v < CH / 8; ++v) {
+                const v8h_u a0 = *reinterpret_cast<const v8h_u *>(src.h + q0 + 8 * v);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) buf[8 * v + e] = (R)(float)a0[e];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < kDtCH; ++i) buf[i] = (q0 + i < N) ? (R)(float)srch[q0 + i] : (R)0;
-            }
-        } else if (sizeof(R) == 4 && q0 + kDtCH <= N) {
-            const float *srcf = reinterpret_cast<const float *>(src);
-#pragma unroll
-            for (int v = 0; v < kDtCH / 4; ++v) {
-                const v4f_u a0 = *reinterpret_cast<const v4f_u *>(srcf + q0 + 4 * v);
-                buf[4 * v] = a0.x; buf[4 * v + 1] = a0.y; buf[4 * v + 2] = a0.z; buf[4 * v + 3] = a0.w;
+                for (int e = 0; e < 8; ++e) buf[8 * v + e] = (R)(float)a0[e];
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < kDtCH; ++i) buf[i] = (q0 + i < N) ? src[q0 + i] : (R)0;
+            for (int i = 0; i < CH; ++i) buf[i] = (q0 + i < N) ? (R)(float)src.h[q0 + i] : (R)0;
         }
-    };
-    auto store = [&](int q0, const R *out, const int *ptr, const int *) {
-        // the element pointers advance by additions (a 64-bit multiply per store is a quarter-rate instruction)
-        R *tp = tmpT + (size_t)q0 * Hl;
-        PT *ip = ixT + (size_t)q0 * Hl;
+    } else if (sizeof(R) == 4 && q0 + CH <= N) {
+        const float *srcf = reinterpret_cast<const float *>(src.v);
 #pragma unroll
-        for (int i = 0; i < kDtCH; ++i) {
-            if (q0 + i < N) { *tp = out[i]; *ip = (PT)dt_get<EPW>(ptr, i); }
-            tp += Hl; ip += Hl;
+        for (int v = 0; v < CH / 4; ++v) {
+            const v4f_u a0 = *reinterpret_cast<const v4f_u *>(srcf + q0 + 4 * v);
+            buf[4 * v] = a0.x; buf[4 * v + 1] = a0.y; buf[4 * v + 2] = a0.z; buf[4 * v + 3] = a0.w;
         }
-    };
-    auto noaux = [](int, int *) {};
-    dt_stream<R, false, BZ, kDtCH, EPW, NARROW>(N, job.ax, job.bx, job.osx, ring, load, store, noaux);
+    } else {
+#pragma unroll
+        for (int i = 0; i < CH; ++i) buf[i] = (q0 + i < N) ? src.v[q0 + i] : (R)0;
+    }
+}
+// their results, ostr elements apart; the element pointers advance by additions (a 64-bit multiply per store is a quarter-rate
+// instruction)
+template <typename R, typename PT, int CH>
+__device__ __forceinline__ void dt_store_chunk(const DtLine<R, PT> &ln, int q0, const R *out, const int *ptr)
+{
+    R *vp = ln.outv + (size_t)q0 * ln.ostr;
+    PT *pp = ln.outp + (size_t)q0 * ln.ostr;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        if (q0 + i < ln.N) { *vp = out[i]; *pp = (PT)dt_get<4 / (int)sizeof(PT)>(ptr, i); }
+        vp += ln.ostr; pp += ln.ostr;
+    }
 }
 
-// Rows (columns) per wave of a pass: 64 when the launch fills the chip (1024 SIMDs), else 32 .. 1 -- see k_dt_rows.
+// thread = (flat line, job, frame); each lane streams its own line.  One wave per workgroup.
+// RH: the responses are fp16 (PBD_CONV_MFMA_F16); a template parameter so that the default kernels carry none of it
+// PT: element type of the position planes (uint8_t when no map side exceeds 256, else int16_t)
+// grid = (job, frame, wave of 64 flat lines): the wave index is the SLOWEST dimension, so the long lines of the large levels
+// are dispatched first and the tail of the launch is made of short ones.
+// lane_shift (0 .. 6): a group of 64 flat lines is spread over 1 .. 64 waves that use their first 64 .. 1 lanes only.  A launch
+// that does not fill the chip anyway (one frame, a few 1080p frames) then runs as more, narrower waves: the wave's pop loops
+// iterate for the slowest of a few lanes instead of 64, and the launch takes what its longest lines take (launch_dt_pass).
+// The columns pass is held to the occupancy its packed position chunks buy (dt_get); the rows pass is left to the compiler.
+template <typename R, bool RH, typename PT, bool BZ, bool NARROW, bool COLS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(COLS && sizeof(R) == 4 ? (sizeof(PT) == 1 && !NARROW ? 6 : 5) : 1)))
+void k_dt_pass(DpParams p)
+{
+    constexpr int EPW = 4 / (int)sizeof(PT), CH = COLS ? kDtCHC : kDtCH;
+    const int sh = p.lane_shift, lanep = threadIdx.x;
+    if (lanep >= (64 >> sh)) return;
+    const int wv = (int)blockIdx.z >> sh, lane = (((int)blockIdx.z & ((1 << sh) - 1)) << (6 - sh)) + lanep;
+    const int flat = wv * 64 + lane;
+    if (flat >= (COLS ? p.ncols_flat : p.nrows_flat)) return;
+    const DtLine<R, PT> ln = dt_line<R, RH, PT, COLS>(p, flat, blockIdx.x, blockIdx.y);
+    __shared__ __attribute__((aligned(16))) char ring_mem[kDtT * DtRing<R, NARROW>::kSlotBytes];
+    DtRing<R, NARROW> ring = DtRing<R, NARROW>::make(ring_mem, lanep, sh, reinterpret_cast<StkPairT<R> *>(p.stk) + ln.stk +
+                                                                              (COLS ? p.stk_col_off : p.stk_row_off)[wv] + lane, ln.a, ln.b);
+    dt_stream<R, BZ, CH, EPW, NARROW>(ln.N, ln.a, ln.b, ln.os, ring,
+                                      [&](int q0, R *buf) { dt_load_chunk<R, CH>(ln.src, ln.N, q0, buf); },
+                                      [&](int q0, const R *out, const int *ptr) { dt_store_chunk<R, PT, CH>(ln, q0, out, ptr); });
+}
+
+// Lines per wave of a pass: 64 when the launch fills the chip (1024 SIMDs), else 32 .. 1 -- see k_dt_pass.
 static int dt_lane_shift(const DtOptions &o, long long waves64)
 {
     if (o.lane_shift >= 0) return o.lane_shift;
@@ -358,101 +356,38 @@ template <bool COLS> static void launch_dt_coop(const DpParams &p, int coop_g, i
 static bool dt_coop_fits(int longest);
 static int dt_coop_min_shift();
 
-void launch_dt_rows(const DpParams &p0, const DtOptions &o, int nframes, bool f64, hipStream_t s)
+// the template arguments a launcher picks at run time, as tags handed to a generic lambda
+template <class F> static void for_flag(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void for_real(bool f64, F &&f) { if (f64) f(double{}); else f(float{}); }
+template <class F> static void for_ptr(bool ptr8, F &&f) { if (ptr8) f(uint8_t{}); else f(int16_t{}); }
+
+template <bool COLS>
+static void launch_dt_pass(const DpParams &p0, const DtOptions &o, int nframes, bool f64, hipStream_t s)
 {
-    if (p0.JG == 0 || p0.nrows_flat == 0) return;
-    const int nwv = (p0.nrows_flat + 63) / 64;
+    const int nflat = COLS ? p0.ncols_flat : p0.nrows_flat;
+    if (p0.JG == 0 || nflat == 0) return;
+    const int nwv = (nflat + 63) / 64;
     DpParams p = p0;
     p.lane_shift = dt_lane_shift(o, (long long)p.JG * nframes * nwv);
-    if (o.coop && p.lane_shift >= dt_coop_min_shift() && !f64 && !p.resp_half && p.ptr8 && dt_coop_fits(p.longest)) { launch_dt_coop<false>(p, o.coop_g, nframes, p.nrows_flat, p.bz_x != 0, s); return; }
-    dim3 grid(p.JG, nframes, nwv << p.lane_shift);
-#define PBD_ROWS(PT, BZ)                                                                                              \
-    do {                                                                                                              \
-        if (f64 && p.lane_shift > 0) PBD_LAUNCH((k_dt_rows<double, false, PT, BZ, true>), grid, dim3(64 * kDtWaves), 0, s, p); \
-        else if (f64) PBD_LAUNCH((k_dt_rows<double, false, PT, BZ, false>), grid, dim3(64 * kDtWaves), 0, s, p);          \
-        else if (p.resp_half) PBD_LAUNCH((k_dt_rows<float, true, PT, BZ, false>), grid, dim3(64 * kDtWaves), 0, s, p); \
-        else if (p.lane_shift > 0) PBD_LAUNCH((k_dt_rows<float, false, PT, BZ, true>), grid, dim3(64 * kDtWaves), 0, s, p); \
-        else PBD_LAUNCH((k_dt_rows<float, false, PT, BZ, false>), grid, dim3(64 * kDtWaves), 0, s, p);               \
-    } while (0)
-    if (p.ptr8) { if (p.bz_x) PBD_ROWS(uint8_t, true); else PBD_ROWS(uint8_t, false); }
-    else { if (p.bz_x) PBD_ROWS(int16_t, true); else PBD_ROWS(int16_t, false); }
-#undef PBD_ROWS
-}
-
-// ---- columns pass: thread = (flat column, job, frame); lanes are adjacent columns -> coalesced ----
-template <typename R, typename PT, bool BZ, bool NARROW>
-__global__ __launch_bounds__(64 * kDtWaves) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? (sizeof(PT) == 1 && !NARROW ? 6 : 5) : 1)))
-void k_dt_cols(DpParams p)
-{
-    constexpr int EPW = 4 / (int)sizeof(PT);
-    const int sh = p.lane_shift, lanep = threadIdx.x;                                      // as in the rows pass
-    if (lanep >= (64 >> sh)) return;
-    const int wv = (int)blockIdx.z >> sh, lane = (((int)blockIdx.z & ((1 << sh) - 1)) << (6 - sh)) + lanep;   // longest columns first
-    const int cidx = wv * 64 + lane;
-    if (cidx >= p.ncols_flat) return;
-    const int j = blockIdx.x, fl = blockIdx.y;
-    const int l = p.col2level[cidx];
-    const LevelDesc d = p.lv[l];
-    const int x = cidx - p.coloff[l];
-    const int H = d.rows, W = d.cols;
-    const size_t HW = (size_t)H * W;
-    const DtJob job = p.jobs[j];
-    const size_t jbase = ((size_t)fl * p.cell_per_frame + d.cell_off) * p.JG + (size_t)j * HW;
-    const R *tmpT = static_cast<const R *>(p.tmp) + jbase + (size_t)x * H;     // this lane's column, contiguous
-    R *dt = static_cast<R *>(p.dt) + jbase + x;
-    PT *iyr = static_cast<PT *>(p.IyRaw) + ((size_t)(p.frame0 + fl) * p.cell_per_frame + d.cell_off) * p.NJ + (size_t)job.gm * HW + x;
-    __shared__ __attribute__((aligned(16))) char ring_mem[kDtWaves * kDtT * DtRing<R, NARROW>::kSlotBytes];
-    DtRing<R, NARROW> ring = DtRing<R, NARROW>::make(ring_mem, lanep, sh,
-                                     reinterpret_cast<StkPairT<R> *>(p.stk) +
-                                         ((size_t)(fl * p.JG + j) * p.stk_per_jf + p.stk_col_off[wv]) + lane, job.ay, job.by);
-    auto load = [&](int q0, R *buf) {
-        if (sizeof(R) == 4 && q0 + kDtCHC <= H) {
-            const float *srcf = reinterpret_cast<const float *>(tmpT);
-#pragma unroll
-            for (int v = 0; v < kDtCHC / 4; ++v) {
-                const v4f_u a0 = *reinterpret_cast<const v4f_u *>(srcf + q0 + 4 * v);
-                buf[4 * v] = a0.x; buf[4 * v + 1] = a0.y; buf[4 * v + 2] = a0.z; buf[4 * v + 3] = a0.w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < kDtCHC; ++i) buf[i] = (q0 + i < H) ? tmpT[q0 + i] : (R)0;
+    const bool bz = (COLS ? p.bz_y : p.bz_x) != 0, rh = !COLS && !f64 && p.resp_half;   // fp16 responses: the rows pass reads them
+    if (o.coop && p.lane_shift >= dt_coop_min_shift() && !f64 && !rh && p.ptr8 && dt_coop_fits(p.longest)) {
+        launch_dt_coop<COLS>(p, o.coop_g, nframes, nflat, bz, s);
+        return;
+    }
+    const dim3 grid(p.JG, nframes, nwv << p.lane_shift);
+    for_ptr(p.ptr8 != 0, [&](auto pt) { for_flag(bz, [&](auto z) {
+        using PT = decltype(pt);
+        constexpr bool BZ = decltype(z)::value;
+        if constexpr (!COLS) {      // fp16 responses: the rows pass only, and never with the deeper ring of NARROW
+            if (rh) { PBD_LAUNCH((k_dt_pass<float, true, PT, BZ, false, false>), grid, dim3(64), 0, s, p); return; }
         }
-    };
-    auto noaux = [](int, int *) {};
-    auto store = [&](int q0, const R *out, const int *ptr, const int *) {
-        R *dp = dt + (size_t)q0 * W;
-        PT *yp = iyr + (size_t)q0 * W;
-#pragma unroll
-        for (int i = 0; i < kDtCHC; ++i) {
-            if (q0 + i < H) {
-                *dp = out[i];
-                *yp = (PT)dt_get<EPW>(ptr, i);
-            }
-            dp += W; yp += W;
-        }
-    };
-    dt_stream<R, false, BZ, kDtCHC, EPW, NARROW>(H, job.ay, job.by, job.osy, ring, load, store, noaux);
+        for_real(f64, [&](auto r) { for_flag(p.lane_shift > 0, [&](auto nw) {
+            PBD_LAUNCH((k_dt_pass<decltype(r), false, PT, BZ, decltype(nw)::value, COLS>), grid, dim3(64), 0, s, p);
+        }); });
+    }); });
 }
-
-void launch_dt_cols(const DpParams &p0, const DtOptions &o, int nframes, bool f64, hipStream_t s)
-{
-    if (p0.JG == 0 || p0.ncols_flat == 0) return;
-    const int nwv = (p0.ncols_flat + 63) / 64;
-    DpParams p = p0;
-    p.lane_shift = dt_lane_shift(o, (long long)p.JG * nframes * nwv);
-    if (o.coop && p.lane_shift >= dt_coop_min_shift() && !f64 && p.ptr8 && dt_coop_fits(p.longest)) { launch_dt_coop<true>(p, o.coop_g, nframes, p.ncols_flat, p.bz_y != 0, s); return; }
-    dim3 grid(p.JG, nframes, nwv << p.lane_shift);
-#define PBD_COLS(PT, BZ)                                                                                   \
-    do {                                                                                                   \
-        if (f64 && p.lane_shift > 0) PBD_LAUNCH((k_dt_cols<double, PT, BZ, true>), grid, dim3(64 * kDtWaves), 0, s, p); \
-        else if (f64) PBD_LAUNCH((k_dt_cols<double, PT, BZ, false>), grid, dim3(64 * kDtWaves), 0, s, p);      \
-        else if (p.lane_shift > 0) PBD_LAUNCH((k_dt_cols<float, PT, BZ, true>), grid, dim3(64 * kDtWaves), 0, s, p); \
-        else PBD_LAUNCH((k_dt_cols<float, PT, BZ, false>), grid, dim3(64 * kDtWaves), 0, s, p);           \
-    } while (0)
-    if (p.ptr8) { if (p.bz_y) PBD_COLS(uint8_t, true); else PBD_COLS(uint8_t, false); }
-    else { if (p.bz_y) PBD_COLS(int16_t, true); else PBD_COLS(int16_t, false); }
-#undef PBD_COLS
-}
+void launch_dt_rows(const DpParams &p, const DtOptions &o, int nframes, bool f64, hipStream_t s) { launch_dt_pass<false>(p, o, nframes, f64, s); }
+void launch_dt_cols(const DpParams &p, const DtOptions &o, int nframes, bool f64, hipStream_t s) { launch_dt_pass<true>(p, o, nframes, f64, s); }
 
 // ---- wavefront-cooperative form of a pass: FOUR rows (columns) per wave, sixteen lanes each --------------------------------
 // For launches of so few rows that narrow waves of eight lanes or fewer would be used (one frame: lane_shift >= 3).  A narrow wave is
@@ -478,26 +413,12 @@ __global__ __launch_bounds__(64) void k_dt_coop(DpParams p)
     const int r = (int)blockIdx.z * kCoopRows + grp;
     const bool active = r < nflat;
     const int rr = active ? r : nflat - 1;
-    const int j = blockIdx.x, fl = blockIdx.y, frame = p.frame0 + fl;
-    const int l = (COLS ? p.col2level : p.row2level)[rr];
-    const LevelDesc d = p.lv[l];
-    const int idx = rr - (COLS ? p.coloff : p.rowoff)[l];          // y of the row / x of the column
-    const int H = d.rows, W = d.cols;
-    const size_t HW = (size_t)H * W;
-    const DtJob job = p.jobs[j];
-    const int N = active ? (COLS ? H : W) : 0;
-    const double a = COLS ? job.ay : job.ax, b = COLS ? job.by : job.bx;
-    const int os0 = COLS ? job.osy : job.osx;
-    const size_t jb = ((size_t)fl * p.cell_per_frame + d.cell_off) * p.JG + (size_t)j * HW;
-    const float *src;
-    if (COLS) src = static_cast<const float *>(p.tmp) + jb + (size_t)idx * H;
-    else src = (job.from_acc ? static_cast<const float *>(p.acc) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NM
-                             : static_cast<const float *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F) +
-               (size_t)job.plane * HW + (size_t)idx * W;
-    // outputs: element q at out + q * ostr (rows pass: transposed planes [x][y]; columns pass: [y][x])
-    const int ostr = COLS ? W : H;
-    float *outv = (COLS ? static_cast<float *>(p.dt) : static_cast<float *>(p.tmp)) + jb + idx;
-    PT *outp = static_cast<PT *>(COLS ? p.IyRaw : p.IxRaw) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NJ + (size_t)job.gm * HW + idx;
+    const DtLine<float, PT> ln = dt_line<float, false, PT, COLS>(p, rr, blockIdx.x, blockIdx.y);   // (never fp16 responses: launch_dt_pass)
+    const int N = active ? ln.N : 0, os0 = ln.os, ostr = ln.ostr;
+    const double a = ln.a, b = ln.b;
+    const float *src = ln.src.v;
+    float *outv = ln.outv;
+    PT *outp = ln.outp;
     const int maxn = p.longest;
     float *zs = reinterpret_cast<float *>(coop_mem) + (size_t)grp * 3 * maxn, *ys = zs + maxn;
     int *vs = reinterpret_cast<int *>(ys + maxn);
@@ -639,7 +560,7 @@ __device__ __forceinline__ void store_cells(T *dst, int n, const T *src)
 }
 
 // MAXM: compile-time bound on the mixtures per part of the model (register arrays are sized by it)
-template <typename R, int kCpt, int MAXM, bool RH, typename PT>
+template <typename R, int kCpt, int MAXM, bool RH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MAXM <= 6 && sizeof(R) == 4 ? 4 : 1)))
 void k_dp_combine(DpParams p)
 {
@@ -649,33 +570,29 @@ void k_dp_combine(DpParams p)
     if (qidx >= p.quad_per_frame) return;
     const int fl = blockIdx.z, frame = p.frame0 + fl;
     const CombineJob cj = p.cjobs[blockIdx.y];
-    int lo = 0, hi = p.nlevels;
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].quad_off <= qidx) lo = mid; else hi = mid; }
-    const LevelDesc d = p.lv[lo];
-    const int W = d.cols;
-    const int HWi = d.rows * W;
+    const LevelDesc d = p.lv[level_of<&LevelDesc::quad_off>(p.lv, 0, p.nlevels, qidx)];
+    const int HWi = d.rows * d.cols;
     const size_t HW = (size_t)HWi;
     const int local = (int)(qidx - d.quad_off) * 4 + (int)(gidx % SUB) * kCpt;
     if (local >= HWi) return;
     const int n = min(kCpt, HWi - local);
-    const R *resp = static_cast<const R *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F + local;
-    const R *dtp = static_cast<const R *>(p.dt);
-    const size_t gbase0 = ((size_t)fl * p.cell_per_frame + d.cell_off) * p.JG;
-    const size_t pbase = ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NS + local;
+    const LevelPlanes<DpParams> pl(p, d, frame, fl);
+    const R *dtp = pl.dt<R>();
+    uint8_t *ik = pl.Ik(local);
     R accv[MAXM][kCpt];
 #pragma unroll
     for (int pm = 0; pm < MAXM; ++pm) {
 #pragma unroll
         for (int e = 0; e < kCpt; ++e) accv[pm][e] = (R)0;
         if (pm < cj.npar) {
+            const ScoreSrc<R> rs = pl.score<R>(false, RH, cj.filter[pm], local);
             if constexpr (RH) {
                 _Float16 hv[kCpt];
-                load_cells<_Float16, kCpt>(reinterpret_cast<const _Float16 *>(p.resp) +
-                                               ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F + local + (size_t)cj.filter[pm] * HW, n, hv);
+                load_cells<_Float16, kCpt>(rs.h, n, hv);
 #pragma unroll
                 for (int e = 0; e < kCpt; ++e) accv[pm][e] = (R)(float)hv[e];
             } else {
-                load_cells<R, kCpt>(resp + (size_t)cj.filter[pm] * HW, n, accv[pm]);
+                load_cells<R, kCpt>(rs.v, n, accv[pm]);
             }
         }
     }
@@ -694,7 +611,7 @@ void k_dp_combine(DpParams p)
 #pragma unroll
             for (int k = 0; k < MAXM; ++k) cd.bias_off[k] = ci[3 + k];
         }
-        const size_t gbase = gbase0 + (size_t)cd.job_begin * HW;
+        const R *dtc = dtp + (size_t)cd.job_begin * HW;
         float bw[MAXM][MAXM]; // bias(mm)[pm]
 #pragma unroll
         for (int mm = 0; mm < MAXM; ++mm)
@@ -708,7 +625,7 @@ void k_dp_combine(DpParams p)
             // a mixture the child does not have scores -inf: it can never win the strict `>` below, so the selection loop
             // needs no `mm < nmix` test (a uniform branch per candidate, i.e. 144 basic blocks per child with their copies)
             for (int e = 0; e < kCpt; ++e) dtv[mm][e] = -RealLimits<R>::inf();
-            if (mm < cd.nmix) load_cells_wide<R, kCpt>(dtp + gbase + (size_t)mm * HW + local, dtv[mm]);
+            if (mm < cd.nmix) load_cells_wide<R, kCpt>(dtc + (size_t)mm * HW + local, dtv[mm]);
         }
 #pragma unroll
         for (int pm = 0; pm < MAXM; ++pm) {
@@ -720,7 +637,8 @@ void k_dp_combine(DpParams p)
                 int bi[kCpt];
 #pragma unroll
                 for (int e = 0; e < kCpt; ++e) bi[e] = 0;
-                if (cd.nmix == 1) {     // K == 1 copies (Math::reduceMax)
+                // reduce_max (pbd_dp.h) over registers: K == 1 copies, else its pick step on every padded mixture
+                if (cd.nmix == 1) {
 #pragma unroll
                     for (int e = 0; e < kCpt; ++e) best[e] = dtv[0][e] + (R)bw[0][pm];
                 } else {
@@ -728,12 +646,7 @@ void k_dp_combine(DpParams p)
                     for (int e = 0; e < kCpt; ++e) {
                         best[e] = -RealLimits<R>::inf();
 #pragma unroll
-                        for (int mm = 0; mm < MAXM; ++mm) {
-                            const R wv = dtv[mm][e] + (R)bw[mm][pm];
-                            const bool t = wv > best[e];
-                            best[e] = t ? wv : best[e];
-                            bi[e] = t ? mm : bi[e];
-                        }
+                        for (int mm = 0; mm < MAXM; ++mm) pick_max<R>(dtv[mm][e] + (R)bw[mm][pm], mm, best[e], bi[e]);
                     }
                 }
 #pragma unroll
@@ -741,12 +654,11 @@ void k_dp_combine(DpParams p)
                     oik[e] = (uint8_t)bi[e];
                     accv[pm][e] = accv[pm][e] + best[e];
                 }
-                const size_t o = pbase + (size_t)(cd.slot + pm) * HW;
-                store_cells<uint8_t, kCpt>(p.Ik + o, n, oik);
+                store_cells<uint8_t, kCpt>(ik + (size_t)(cd.slot + pm) * HW, n, oik);
             }
         }
     }
-    R *acc = static_cast<R *>(p.acc) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NM + local;
+    R *acc = pl.acc<R>(local);
 #pragma unroll
     for (int pm = 0; pm < MAXM; ++pm)
         if (pm < cj.npar) store_cells<R, kCpt>(acc + (size_t)(cj.acc_plane + pm) * HW, n, accv[pm]);
@@ -756,69 +668,43 @@ void launch_dp_combine(const DpParams &p, int ncjobs, int nframes, bool f64, hip
 {
     if (ncjobs == 0 || p.quad_per_frame == 0) return;
     const dim3 g2((unsigned)((p.quad_per_frame * 2 + 255) / 256), ncjobs, nframes), g4((unsigned)((p.quad_per_frame + 255) / 256), ncjobs, nframes);
-#define PBD_COMBINE(M)                                                                      \
-    do {                                                                                    \
-        if (p.ptr8) {                                                                                                      \
-            if (f64) PBD_LAUNCH((k_dp_combine<double, 2, M, false, uint8_t>), g2, dim3(256), 0, s, p);            \
-            else if (p.resp_half) PBD_LAUNCH((k_dp_combine<float, 4, M, true, uint8_t>), g4, dim3(256), 0, s, p); \
-            else PBD_LAUNCH((k_dp_combine<float, 4, M, false, uint8_t>), g4, dim3(256), 0, s, p);                 \
-        } else {                                                                                                           \
-            if (f64) PBD_LAUNCH((k_dp_combine<double, 2, M, false, int16_t>), g2, dim3(256), 0, s, p);            \
-            else if (p.resp_half) PBD_LAUNCH((k_dp_combine<float, 4, M, true, int16_t>), g4, dim3(256), 0, s, p); \
-            else PBD_LAUNCH((k_dp_combine<float, 4, M, false, int16_t>), g4, dim3(256), 0, s, p);                 \
-        }                                                                                                                  \
-    } while (0)
-    if (p.max_mix <= 2) PBD_COMBINE(2);
-    else if (p.max_mix <= 4) PBD_COMBINE(4);
-    else if (p.max_mix <= 6) PBD_COMBINE(6);
-    else if (p.max_mix <= 8) PBD_COMBINE(8);
-    else PBD_COMBINE(16);
-#undef PBD_COMBINE
+    auto launch = [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (f64) PBD_LAUNCH((k_dp_combine<double, 2, M, false>), g2, dim3(256), 0, s, p);
+        else if (p.resp_half) PBD_LAUNCH((k_dp_combine<float, 4, M, true>), g4, dim3(256), 0, s, p);
+        else PBD_LAUNCH((k_dp_combine<float, 4, M, false>), g4, dim3(256), 0, s, p);
+    };
+    if (p.max_mix <= 2) launch(std::integral_constant<int, 2>{});
+    else if (p.max_mix <= 4) launch(std::integral_constant<int, 4>{});
+    else if (p.max_mix <= 6) launch(std::integral_constant<int, 6>{});
+    else if (p.max_mix <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
 }
 
 // ---- combine, sequential schedule: thread = one cell, block.y = one (component, part) of the step -------------
 // For every parent mixture pm, in order: weighted[mm] = score_dt[mm] + bias(mm)[pm]; reduceMax; winning mixture -> Ik;
 // then `parent.score[pm] += max` IN PLACE on the accumulator keyed by the parent mixture's filter id,
 // which starts as a copy of the raw response the first time it is touched (src/DynamicProgram.cpp:134-156).
-template <typename R, typename PT>
+template <typename R>
 __global__ __launch_bounds__(256) void k_dp_combine_seq(DpParams p)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= p.cell_per_frame) return;
-    const int fl = blockIdx.z, frame = p.frame0 + fl;
+    const int fl = blockIdx.z;
     const SeqCombineJob sj = p.sjobs[blockIdx.y];
-    int lo = 0, hi = p.nlevels;
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].cell_off <= idx) lo = mid; else hi = mid; }
-    const LevelDesc d = p.lv[lo];
-    const int W = d.cols;
-    const int local = (int)(idx - d.cell_off);
-    const size_t HW = (size_t)d.rows * W;
-    const size_t gbase = ((size_t)fl * p.cell_per_frame + d.cell_off) * p.JG + (size_t)sj.job_begin * HW;
-    const size_t pbase = ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NS + local;
-    const R *respp = static_cast<const R *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F + local;
-    R *accp = static_cast<R *>(p.acc) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NM + local;
-    const R *dtp = static_cast<const R *>(p.dt) + gbase + local;
+    const LevelDesc d = p.lv[level_of(p.lv, 0, p.nlevels, idx)];
+    const size_t local = (size_t)(idx - d.cell_off);
+    const LevelPlanes<DpParams> pl(p, d, p.frame0 + fl, fl);
+    const size_t HW = pl.HW;
+    const R *dtp = pl.dt<R>((size_t)sj.job_begin * HW + local);
     R dtv[kMaxMix];
     for (int mm = 0; mm < sj.nmix; ++mm) dtv[mm] = dtp[(size_t)mm * HW];
     for (int pm = 0; pm < sj.npar; ++pm) {
-        R best;
-        int bi = 0;
-        if (sj.nmix == 1) {
-            best = dtv[0] + (R)p.biasw[sj.bias_off[0] + pm];
-        } else {
-            best = -RealLimits<R>::inf();
-            for (int mm = 0; mm < sj.nmix; ++mm) {
-                const R wv = dtv[mm] + (R)p.biasw[sj.bias_off[mm] + pm];
-                if (wv > best) { bi = mm; best = wv; }
-            }
-        }
-        const size_t o = pbase + (size_t)(sj.slot + pm) * HW;
-        p.Ik[o] = (uint8_t)bi;
-        R *t = accp + (size_t)sj.target[pm] * HW;
-        const R base = !sj.init[pm] ? *t
-                       : (sizeof(R) == 4 && p.resp_half)
-                             ? (R)(float)(reinterpret_cast<const _Float16 *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F + local)[(size_t)sj.filter[pm] * HW]
-                             : respp[(size_t)sj.filter[pm] * HW];
+        int bi;
+        const R best = reduce_max<R>(sj.nmix, [&](int mm) { return dtv[mm] + (R)p.biasw[sj.bias_off[mm] + pm]; }, bi);
+        *pl.Ik((size_t)(sj.slot + pm) * HW + local) = (uint8_t)bi;
+        R *t = pl.acc<R>((size_t)sj.target[pm] * HW + local);
+        const R base = !sj.init[pm] ? *t : pl.score<R>(false, sizeof(R) == 4 && p.resp_half, sj.filter[pm], local)[0];
         *t = base + best;
     }
 }
@@ -827,13 +713,7 @@ void launch_dp_combine_seq(const DpParams &p, int nsjobs, int nframes, bool f64,
 {
     if (nsjobs == 0 || p.cell_per_frame == 0) return;
     dim3 grid((unsigned)((p.cell_per_frame + 255) / 256), nsjobs, nframes);
-    if (p.ptr8) {
-        if (f64) PBD_LAUNCH((k_dp_combine_seq<double, uint8_t>), grid, dim3(256), 0, s, p);
-        else PBD_LAUNCH((k_dp_combine_seq<float, uint8_t>), grid, dim3(256), 0, s, p);
-    } else {
-        if (f64) PBD_LAUNCH((k_dp_combine_seq<double, int16_t>), grid, dim3(256), 0, s, p);
-        else PBD_LAUNCH((k_dp_combine_seq<float, int16_t>), grid, dim3(256), 0, s, p);
-    }
+    for_real(f64, [&](auto r) { PBD_LAUNCH(k_dp_combine_seq<decltype(r)>, grid, dim3(256), 0, s, p); });
 }
 
 // ---- root: rootv = max over root mixtures of (accumulated score + bias) ----------------------------
@@ -844,41 +724,22 @@ __global__ __launch_bounds__(256) void k_dp_root(DpParams p)
     if (idx >= p.cell_per_frame) return;
     const int c = blockIdx.y, fl = blockIdx.z, frame = p.frame0 + fl;
     const RootJob rj = p.rjobs[c];
-    int lo = 0, hi = p.nlevels;
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].cell_off <= idx) lo = mid; else hi = mid; }
-    const LevelDesc d = p.lv[lo];
-    const int local = (int)(idx - d.cell_off);
-    const size_t HW = (size_t)d.rows * d.cols;
-    const R *accp = static_cast<const R *>(p.acc) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NM;
-    const R *respp = static_cast<const R *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F;
-    const _Float16 *resph = static_cast<const _Float16 *>(p.resp) + ((size_t)frame * p.cell_per_frame + d.cell_off) * p.F;
+    const LevelDesc d = p.lv[level_of(p.lv, 0, p.nlevels, idx)];
+    const size_t local = (size_t)(idx - d.cell_off);
+    const LevelPlanes<DpParams> pl(p, d, frame);
     const bool rh = sizeof(R) == 4 && p.resp_half;
-    auto score = [&](int mm) -> R {
-        const size_t o = (size_t)rj.plane[mm] * HW + local;
-        return ((rj.from_acc >> mm) & 1) ? accp[o] : rh ? (R)(float)resph[o] : respp[o];
-    };
-    R best;
-    int bi = 0;
-    if (rj.nmix == 1) {
-        best = score(0) + (R)rj.bias;
-    } else {
-        best = -RealLimits<R>::inf();
-        for (int mm = 0; mm < rj.nmix; ++mm) {
-            const R wv = score(mm) + (R)rj.bias;
-            if (wv > best) { bi = mm; best = wv; }
-        }
-    }
-    const size_t o = ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NC + (size_t)c * HW + local;
-    static_cast<R *>(p.rootv)[o] = best;
-    p.rooti[o] = bi;
+    int bi;
+    const R best = reduce_max<R>(rj.nmix, [&](int mm) { return pl.score<R>((rj.from_acc >> mm) & 1, rh, rj.plane[mm], local)[0] + (R)rj.bias; }, bi);
+    const size_t o = (size_t)c * pl.HW + local;
+    *pl.rootv<R>(o) = best;
+    *pl.rooti(o) = bi;
 }
 
 void launch_dp_root(const DpParams &p, int nframes, bool f64, hipStream_t s)
 {
     if (p.cell_per_frame == 0) return;
     dim3 grid((unsigned)((p.cell_per_frame + 255) / 256), p.NC, nframes);
-    if (f64) PBD_LAUNCH(k_dp_root<double>, grid, dim3(256), 0, s, p);
-    else PBD_LAUNCH(k_dp_root<float>, grid, dim3(256), 0, s, p);
+    for_real(f64, [&](auto r) { PBD_LAUNCH(k_dp_root<decltype(r)>, grid, dim3(256), 0, s, p); });
 }
 
 // ---- argmin ------------------------------------------------------------------------------------
@@ -905,23 +766,13 @@ __device__ __forceinline__ int find_hits(const ArgminParams &p, long long base, 
     return c;
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
 template <typename R>
 __global__ __launch_bounds__(kFindBlock) void k_argmin_count(ArgminParams p)
 {
     bool hit[kFindEPT];
     const int c = find_hits<R>(p, (long long)blockIdx.x * kFindSpan + threadIdx.x * kFindEPT, hit);
     __shared__ int wsum[kFindBlock / 64];
-    const int lane = threadIdx.x & 63, incl = wave_incl_scan(c, lane);
+    const int lane = threadIdx.x & 63, incl = wave_incl_scan(c);
     if (lane == 63) wsum[threadIdx.x >> 6] = incl;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -943,7 +794,7 @@ __global__ __launch_bounds__(1024) void k_argmin_scan(ArgminParams p)
     for (int b0 = 0; b0 < p.nblk; b0 += 1024) {
         const int b = b0 + threadIdx.x;
         const int v = b < p.nblk ? p.blk[b] : 0;
-        const int incl = wave_incl_scan(v, lane);
+        const int incl = wave_incl_scan(v);
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
         int off = carry_s;
@@ -963,7 +814,7 @@ __global__ __launch_bounds__(kFindBlock) void k_argmin_emit(ArgminParams p)
     const long long base = (long long)blockIdx.x * kFindSpan + threadIdx.x * kFindEPT;
     const int c = find_hits<R>(p, base, hit);
     __shared__ int wsum[kFindBlock / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, incl = wave_incl_scan(c, lane);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, incl = wave_incl_scan(c);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
     if (c == 0) return;
@@ -977,36 +828,18 @@ __global__ __launch_bounds__(kFindBlock) void k_argmin_emit(ArgminParams p)
         if (mine >= p.capacity) continue;                      // word 0 still carries the true count: the caller sees the overflow
         const long long o = base + e;
         const int frame = (int)(o / per_frame);
-        const long long rem = o - (long long)frame * per_frame;
-        int lo = 0, hi = p.nlevels;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].cell_off * p.NC <= rem) lo = mid; else hi = mid; }
-        const LevelDesc d = p.lv[lo];
-        const int HWi = d.rows * d.cols;
-        const int rem2 = (int)(rem - d.cell_off * p.NC);
-        const int comp = rem2 / HWi, local = rem2 - comp * HWi;
-        int32_t *rec = p.payload + 1 + (size_t)mine * p.stride;
-        rec[0] = frame; rec[1] = comp; rec[2] = lo;
-        rec[3] = local % d.cols; rec[4] = local / d.cols;
-        rec[5] = __float_as_int((float)static_cast<const R *>(p.rootv)[o]);   // Candidate::confidence_ is float for every T (include/Candidate.hpp:72)
-        rec[6] = 0;
-        rec[7] = p.rooti[o];   // root mixture, consumed by the walk kernel
+        root_record(p.payload + 1 + (size_t)mine * p.stride, p.lv, 0, p.nlevels, p.NC, frame, o - (long long)frame * per_frame,
+                    static_cast<const R *>(p.rootv)[o], p.rooti[o]);
     }
 }
 
 void launch_argmin_find(const ArgminParams &p, bool f64, hipStream_t s)
 {   // p.nblk = ceil(p.ntotal / kFindSpan) >= 1; p.blk holds nblk ints
-    if (f64) PBD_LAUNCH(k_argmin_count<double>, dim3(p.nblk), dim3(kFindBlock), 0, s, p);
-    else PBD_LAUNCH(k_argmin_count<float>, dim3(p.nblk), dim3(kFindBlock), 0, s, p);
+    for_real(f64, [&](auto r) { PBD_LAUNCH(k_argmin_count<decltype(r)>, dim3(p.nblk), dim3(kFindBlock), 0, s, p); });
     PBD_LAUNCH(k_argmin_scan, dim3(1), dim3(1024), 0, s, p);
-    if (f64) PBD_LAUNCH(k_argmin_emit<double>, dim3(p.nblk), dim3(kFindBlock), 0, s, p);
-    else PBD_LAUNCH(k_argmin_emit<float>, dim3(p.nblk), dim3(kFindBlock), 0, s, p);
+    for_real(f64, [&](auto r) { PBD_LAUNCH(k_argmin_emit<decltype(r)>, dim3(p.nblk), dim3(kFindBlock), 0, s, p); });
 }
 int argmin_find_span() { return kFindSpan; }
-
-template <typename R> __device__ __forceinline__ int round_mul(int a, R s);
-// cv::Point_<int> * T -> saturate_cast<int>(a*s) = cvRound: round half to even
-template <> __device__ __forceinline__ int round_mul<float>(int a, float s) { return __float2int_rn((float)a * s); }
-template <> __device__ __forceinline__ int round_mul<double>(int a, double s) { return __double2int_rn((double)a * s); }
 
 // walk: one thread per candidate follows Ix/Iy/Ik from the root (src/DynamicProgram.cpp:218-244).  The number of
 // candidates is read from word 0 of the payload (the host never needs it to launch this); the grid strides over
@@ -1022,13 +855,10 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
     int32_t *rec = p.payload + 1 + (size_t)i * p.stride;
     const int frame = rec[0], c = rec[1], l = rec[2];
     const LevelDesc d = p.lv[l];
-    const int W = d.cols;
-    const size_t HW = (size_t)d.rows * W;
+    const LevelPlanes<ArgminParams> pl(p, d, frame);
     const R scale = (R)p.scales[l];   // T scale = scales[n] (vectorf), src/DynamicProgram.cpp:199
     const PartWalk *walk = p.walk + p.walk_off[c];
     const int nparts = p.walk_off[c + 1] - p.walk_off[c];
-    const size_t pbase = ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NS;
-    const size_t jbase = ((size_t)frame * p.cell_per_frame + d.cell_off) * p.NJ;
     int32_t *rects = rec + 8;
     for (int pidx = 0; pidx < nparts; ++pidx) {
         int x, y, m;
@@ -1037,23 +867,16 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
         } else {
             const PartWalk w = walk[pidx];
             const int par = visited[w.parent][threadIdx.x];
-            const int px = par & 0xffff, py = par >> 16, pm = visited_m[w.parent][threadIdx.x];
-            // Ix = IxRaw[k][py][px], Iy = IyRaw[k][py][Ix] with k = the winning mixture (the reference's composition)
-            m = p.Ik[pbase + (size_t)(w.slot + pm) * HW + (size_t)py * W + px];
-            const size_t jo = jbase + (size_t)(w.mix0 + m) * HW;
-            x = static_cast<const PT *>(p.IxRaw)[jo + (size_t)px * d.rows + py];      // IxRaw is kept transposed ([x][y])
-            y = static_cast<const PT *>(p.IyRaw)[jo + (size_t)py * W + x];
+            const WalkPos ch = walk_child<PT>(pl, w, par & 0xffff, par >> 16, visited_m[w.parent][threadIdx.x]);
+            x = ch.x; y = ch.y; m = ch.m;
         }
         visited[pidx][threadIdx.x] = x | (y << 16);
         visited_m[pidx][threadIdx.x] = (uint8_t)m;
-        const int ks = walk[pidx].ksize[m];
-        const int x1 = round_mul<R>(x - 1, scale), y1 = round_mul<R>(y - 1, scale);
-        const int x2 = x1 + round_mul<R>(ks, scale) - 1, y2 = y1 + round_mul<R>(ks, scale) - 1;
-        const int rx = min(x1, x2), ry = min(y1, y2);
-        rects[pidx * 4 + 0] = rx;
-        rects[pidx * 4 + 1] = ry;
-        rects[pidx * 4 + 2] = max(x1, x2) - rx;
-        rects[pidx * 4 + 3] = max(y1, y2) - ry;
+        const PartRect r = part_rect<R>(x, y, walk[pidx].ksize[m], scale);
+        rects[pidx * 4 + 0] = r.x1;
+        rects[pidx * 4 + 1] = r.y1;
+        rects[pidx * 4 + 2] = r.x2 - r.x1;
+        rects[pidx * 4 + 3] = r.y2 - r.y1;
     }
     rec[0] = frame + p.frame_offset;   // index within the batch -> global frame id of a sharded job (0 on one GPU)
     if (p.lv_frame) {                  // mixed-size call: virtual level -> (frame of the call, level of its own pyramid)
@@ -1068,13 +891,9 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
 void launch_argmin_walk(const ArgminParams &p, bool f64, hipStream_t s)
 {
     const int blocks = std::max(std::min((p.capacity + 63) / 64, 2048), 1);
-    if (p.ptr8) {
-        if (f64) PBD_LAUNCH((k_argmin_walk<double, uint8_t>), dim3(blocks), dim3(64), 0, s, p);
-        else PBD_LAUNCH((k_argmin_walk<float, uint8_t>), dim3(blocks), dim3(64), 0, s, p);
-    } else {
-        if (f64) PBD_LAUNCH((k_argmin_walk<double, int16_t>), dim3(blocks), dim3(64), 0, s, p);
-        else PBD_LAUNCH((k_argmin_walk<float, int16_t>), dim3(blocks), dim3(64), 0, s, p);
-    }
+    for_real(f64, [&](auto r) { for_ptr(p.ptr8 != 0, [&](auto pt) {
+        PBD_LAUNCH((k_argmin_walk<decltype(r), decltype(pt)>), dim3(blocks), dim3(64), 0, s, p);
+    }); });
 }
 
 }  // namespace pbd

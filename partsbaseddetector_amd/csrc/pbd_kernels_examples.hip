@@ -4,13 +4,13 @@
 //
 // Two launches over the records of a payload (word 0 = count, read on the device):
 //   k_ex_walk    one thread per record: the checks of the record against the resident result, the walk through the resident
-//                back-pointer maps with the composition of k_argmin_walk, the header, the bias and deformation values, and one
+//                back-pointer maps (walk_child, as the candidates' walk), the header, the bias and deformation values, and one
 //                ExPart per (record, part) for the gather
 //   k_ex_gather  one wavefront per (record, part): the k x k x flen feature window, read as 16-byte chunks (a cell is 32 values,
 //                so a chunk never straddles two cells and every source chunk is 16-byte aligned) and written as 16-byte chunks at
 //                the block's place in the value row (dword aligned: the blocks before it have odd lengths).  A chunk outside the
 //                feature map is filled with the convolution's border values without a read.
-#include "pbd_internal.h"
+#include "pbd_dp.h"
 
 namespace pbd {
 namespace {
@@ -57,10 +57,7 @@ __global__ __launch_bounds__(kExWalkThreads) void k_ex_walk(ExampleParams p)
             for (int q = 0; q < p.max_parts; ++q) parts[q].k = 0;
             continue;
         }
-        const int W = d.cols;
-        const size_t HW = (size_t)d.rows * W;
-        const size_t cellb = (size_t)bf * p.cell_per_frame + d.cell_off;
-        const size_t pbase = cellb * p.NS, jbase = cellb * p.NJ;
+        const LevelPlanes<ExampleParams> pl(p, d, bf);
         const PartWalk *walk = p.walk + p.walk_off[c];
         const int nparts = p.walk_off[c + 1] - p.walk_off[c];
         R *vals = static_cast<R *>(p.values) + (size_t)i * p.vstride;
@@ -71,15 +68,12 @@ __global__ __launch_bounds__(kExWalkThreads) void k_ex_walk(ExampleParams p)
             int x, y, m, pm = 0, px = 0, py = 0;
             if (pidx == 0) {
                 x = rx; y = ry;
-                m = p.rooti[cellb * p.NC + (size_t)c * HW + (size_t)ry * W + rx];
+                m = *pl.rooti((size_t)c * pl.HW + (size_t)ry * d.cols + rx);
             } else {
                 const ExPart &par = parts[w.parent];
                 px = par.x; py = par.y; pm = par.m;
-                // Ix = IxRaw[k][py][px], Iy = IyRaw[k][py][Ix] with k = the winning mixture: k_argmin_walk's composition
-                m = p.Ik[pbase + (size_t)(w.slot + pm) * HW + (size_t)py * W + px];
-                const size_t jo = jbase + (size_t)(w.mix0 + m) * HW;
-                x = static_cast<const PT *>(p.IxRaw)[jo + (size_t)px * d.rows + py];   // IxRaw is kept transposed ([x][y])
-                y = static_cast<const PT *>(p.IyRaw)[jo + (size_t)py * W + x];
+                const WalkPos ch = walk_child<PT>(pl, w, px, py, pm);
+                x = ch.x; y = ch.y; m = ch.m;
             }
             const ExGm g = p.gm[w.mix0 + m];
             // bias: the root's is that of mixture 0 for every root mixture (src/DynamicProgram.cpp:163-170); a child's is
@@ -104,8 +98,8 @@ __global__ __launch_bounds__(kExWalkThreads) void k_ex_walk(ExampleParams p)
             hdr[5 + 2 * nb] = k * k * kExFlen;
             ++nb;
             ExPart e{};
-            e.cell = (long long)cellb; e.dst = (long long)i * p.vstride + nv;
-            e.x = x; e.y = y; e.m = m; e.k = k; e.W = W; e.H = d.rows;
+            e.cell = (long long)pl.cell; e.dst = (long long)i * p.vstride + nv;
+            e.x = x; e.y = y; e.m = m; e.k = k; e.W = d.cols; e.H = d.rows;
             parts[pidx] = e;
             nv += (long long)k * k * kExFlen;
         }
@@ -152,11 +146,6 @@ __global__ __launch_bounds__(64 * kExGatherWaves) void k_ex_gather(ExampleParams
 }
 
 // ---- latent positives (pbd_detect_latent) --------------------------------------------------------------------------------
-template <typename R> __device__ __forceinline__ int lat_round_mul(int a, R s);
-// cv::Point_<int> * T -> saturate_cast<int>(a*s) = cvRound: round half to even (as k_argmin_walk)
-template <> __device__ __forceinline__ int lat_round_mul<float>(int a, float s) { return __float2int_rn((float)a * s); }
-template <> __device__ __forceinline__ int lat_round_mul<double>(int a, double s) { return __double2int_rn((double)a * s); }
-
 // one thread per response value of the latent bank: the plane of (part p, mixture m) at (x, y) of level l keeps its value only
 // when m is allowed and the part's record rectangle (src/DynamicProgram.cpp:238-241) overlaps the frame's box of part p by more
 // than `overlap` (testoverlap: inclusive areas, in double); otherwise it becomes -1e10 (Matlab's -INF, finite)
@@ -165,8 +154,7 @@ __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
 {
     const long long total = p.cell_per_frame * p.F;
     for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long long)gridDim.x * blockDim.x) {
-        int lo = 0, hi = p.nlevels;
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].cell_off * p.F <= o) lo = mid; else hi = mid; }
+        const int lo = level_of(p.lv, 0, p.nlevels, o, p.F);
         const LevelDesc d = p.lv[lo];
         const int HW = d.rows * d.cols;
         if (HW == 0) continue;
@@ -177,10 +165,8 @@ __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
         const int f = p.lv_frame[lo];
         bool keep = !p.mix || p.mix[f * p.nparts + g.x] < 0 || p.mix[f * p.nparts + g.x] == g.y;
         if (keep) {
-            const R scale = (R)p.scales[lo];
-            const int x1 = lat_round_mul<R>(x - 1, scale), y1 = lat_round_mul<R>(y - 1, scale);
-            const int x2 = x1 + lat_round_mul<R>(g.z, scale) - 1, y2 = y1 + lat_round_mul<R>(g.z, scale) - 1;
-            const long long rx1 = min(x1, x2), ry1 = min(y1, y2), rx2 = max(x1, x2), ry2 = max(y1, y2);
+            const PartRect r = part_rect<R>(x, y, g.z, (R)p.scales[lo]);
+            const long long rx1 = r.x1, ry1 = r.y1, rx2 = r.x2, ry2 = r.y2;
             const int4 b = p.boxes[f * p.nparts + g.x];
             const long long iw = max(0LL, min(rx2, (long long)b.z) - max(rx1, (long long)b.x) + 1);
             const long long ih = max(0LL, min(ry2, (long long)b.w) - max(ry1, (long long)b.y) + 1);
@@ -194,7 +180,7 @@ __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
 }
 
 // one workgroup per frame: the highest root score over the frame's levels, components and positions; on a tie the first in
-// (level, component, y, x) order.  Writes the frame's record header as k_argmin_emit does (virtual frame 0, virtual level)
+// (level, component, y, x) order.  Writes the frame's record header as k_argmin_emit does (root_record: virtual frame 0, virtual level)
 template <typename R>
 __global__ __launch_bounds__(256) void k_latent_best(LatentParams p)
 {
@@ -222,17 +208,7 @@ __global__ __launch_bounds__(256) void k_latent_best(LatentParams p)
     }
     if (threadIdx.x != 0) return;
     const long long o = si[0];
-    int lo = p.frame_lv0[f], hi = p.frame_lv0[f + 1];
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (p.lv[mid].cell_off * p.NC <= o) lo = mid; else hi = mid; }
-    const LevelDesc d = p.lv[lo];
-    const int HW = d.rows * d.cols;
-    const int rem = (int)(o - d.cell_off * p.NC);
-    const int comp = rem / HW, local = rem - comp * HW;
-    int32_t *rec = p.payload + 1 + (size_t)f * p.stride;
-    rec[0] = 0; rec[1] = comp; rec[2] = lo; rec[3] = local % d.cols; rec[4] = local / d.cols;
-    rec[5] = __float_as_int((float)rv[o]);
-    rec[6] = 0;
-    rec[7] = p.rooti[o];
+    root_record(p.payload + 1 + (size_t)f * p.stride, p.lv, p.frame_lv0[f], p.frame_lv0[f + 1], p.NC, 0, o, rv[o], p.rooti[o]);
     if (f == 0) p.payload[0] = p.nframes;
 }
 

@@ -1,4 +1,4 @@
-"""Every distance-transform kernel variant (k_dt_rows, k_dt_cols, k_dt_coop in pbd_kernels_dp.hip) against the oracle, bit for
+"""Every distance-transform kernel variant (k_dt_pass for rows and columns, k_dt_coop in pbd_kernels_dp.hip) against the oracle, bit for
 bit, on full planes of hard inputs.
 
 pbd_dp_min runs under each launch setting Handle.set_debug_option can force -- rows per wave (lane_shift 0..6: wide ring,

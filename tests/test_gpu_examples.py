@@ -104,6 +104,29 @@ def test_person_model_subset_any_order(dtype):
         hd.close()
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_wide_map_int16_planes_bit_for_bit(dtype):
+    """A map wider than 256 cells: the position planes are int16, so the walk of pbd_examples is k_ex_walk<R, int16_t>, which
+    no other frame of this file or of test_gpu_latent.py reaches.  36 x 1100 pixels: the tiny model's pyramid plan refuses a
+    frame of 24 or 32 rows at that width (level 0 is 7 x 273 cells); seed and threshold were chosen with the oracle so that a few
+    hundred records pass and some of them walk to a part beyond column 255, where a wrong index into the transposed IxRaw
+    plane cannot give the right position."""
+    model = M.synthetic_tiny_model(thresh=0.8)
+    flat = model.flatten()
+    im = synth.synthetic_frame(13, 36, 1100)
+    hd = detector.Handle(model, device=0, real_type=REAL[dtype], max_candidates=1 << 12)
+    try:
+        assert int(hd.plan(36, 1100)["feat_cols"].max()) > 256
+        rec = records(hd, [im])
+        assert 100 <= len(rec) <= 600
+        check_against_yardstick(hd, flat, [im], rec, dtype, some_exact=False)
+        fm = E.FrameMaps(flat, im, dtype)
+        walked = [fm.placement(int(r[2]), int(r[1]), int(r[3]), int(r[4])) for r in rec]
+        assert any(x >= 256 for pl in walked for (x, _, _) in pl[1:])
+    finally:
+        hd.close()
+
+
 def test_multi_component_mixed_batch_and_nms():
     model = M.synthetic_face_model(nparts=7, ncomponents=3, thresh=-100.0)
     flat = model.flatten()

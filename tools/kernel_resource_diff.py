@@ -17,7 +17,7 @@ import tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import build  # noqa: E402
 
-FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp", "features"]
+FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp", "features", "dp", "examples"]
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 RENAMED = {
@@ -37,6 +37,20 @@ for _pt, _rw, _pw in (("unsigned short", "float", "int"), ("float", "float", "fl
     RENAMED["k_pyrdown_runs<%s, %s, %s>" % (_pt, _pw, "true" if _pw == "int" else "false")] = ["k_pyrdown<%s, Runs>" % _pt]
     for _r in ("float", "double"):
         RENAMED["k_hog_grad_t<%s, %s>" % (_r, _pt)] = ["k_hog_grad<%s, %s>" % (_r, _pt)]
+
+_tf = ("false", "true")
+for _pt in ("unsigned char", "short"):
+    for _bz in _tf:
+        for _nw in _tf:
+            for _r, _rh in (("float", "false"), ("float", "true"), ("double", "false")):      # the two passes are one kernel
+                RENAMED["k_dt_rows<%s, %s, %s, %s, %s>" % (_r, _rh, _pt, _bz, _nw)] = ["k_dt_pass<%s, %s, %s, %s, %s, false>" % (_r, _rh, _pt, _bz, _nw)]
+            for _r in ("float", "double"):
+                RENAMED["k_dt_cols<%s, %s, %s, %s>" % (_r, _pt, _bz, _nw)] = ["k_dt_pass<%s, false, %s, %s, %s, true>" % (_r, _pt, _bz, _nw)]
+    for _m in (2, 4, 6, 8, 16):                 # the combine kernels no longer carry the position planes' type
+        for _r, _c, _rh in (("float", 4, "false"), ("float", 4, "true"), ("double", 2, "false")):
+            RENAMED["k_dp_combine<%s, %d, %d, %s, %s>" % (_r, _c, _m, _rh, _pt)] = ["k_dp_combine<%s, %d, %d, %s>" % (_r, _c, _m, _rh)]
+    for _r in ("float", "double"):
+        RENAMED["k_dp_combine_seq<%s, %s>" % (_r, _pt)] = ["k_dp_combine_seq<%s>" % _r]
 
 
 def compile_tree(tree, out):

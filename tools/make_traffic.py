@@ -22,8 +22,11 @@ for ctr, mode in (("fetch", "exact"), ("write", "exact"), ("fetch", "mfma"), ("w
     for r in csv.DictReader(open(f)):
         if mode == "mfma" and "k_conv_mfma" not in r["Kernel_Name"]:
             continue        # the other kernels are identical in both modes: take them from the exact run
+        kname = r["Kernel_Name"]
+        if "k_dt_pass<" in kname:       # one kernel for both passes: the last template argument is COLS
+            kname = ("k_dt_cols<" if ", true>(" in kname else "k_dt_rows<") + kname
         for pat, key in names.items():
-            if (pat in r["Kernel_Name"]) if pat.endswith("<") else (pat + "<" in r["Kernel_Name"] or pat + "(" in r["Kernel_Name"]):
+            if (pat in kname) if pat.endswith("<") else (pat + "<" in kname or pat + "(" in kname):
                 acc[key][r["Counter_Name"]] += float(r["Counter_Value"])
                 if ctr == "fetch":
                     acc[key]["launches"] += 1
