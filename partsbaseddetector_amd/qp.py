@@ -151,6 +151,7 @@ class QPRef:
         self.have_lb = False
         self.lb_dropped = self.passes = self.converged = 0
         self.branches: List[str] = []     # per step of the last pass: "plain", "pair" or "none" (for the tests)
+        self.detail: List[frozenset] = []  # per step of the last pass: the labels of _step that applied
 
     @property
     def n(self) -> int:
@@ -237,8 +238,10 @@ class QPRef:
         self.w[e.idx] = self.w[e.idx] + da * e.x.astype(np.float64)
 
     def _clamp(self):
+        """the non-negativity clamps; whether any coordinate changed"""
         v = self.w[self.noneg]
         self.w[self.noneg] = np.where(v < 0, 0.0, v)
+        return bool(np.any(v < 0))
 
     def groups(self, members: Sequence[int]):
         """group numbers of members (ascending indices) by first appearance, and their count"""
@@ -248,8 +251,21 @@ class QPRef:
         return g, len(seen)
 
     # -- qp_refresh
+    def _refresh_order(self):
+        """the entries with a > 0 in ascending a, equal a by index: lincomb's order"""
+        return sorted((i for i in range(self.n) if self.a[i] > 0), key=lambda i: (self.a[i], i))
+
+    def refresh_tasks(self):
+        """(offset, first coordinate, count) of the refresh's work items as the device forms them: every layout block that an
+        entry with a > 0 carries, in pieces of at most 1024 coordinates.  A restatement of the host's split for the tests' own
+        bookkeeping (which inputs make a block span two items); it is not compared with the device: what guards the split is the
+        byte comparison of w"""
+        used = {off for i in self._refresh_order() for off, ln, st in self.e[i].blocks}
+        return [(off, c0, min(LANES, ln - c0)) for off, ln in sorted(self.lay.slot_len.items()) if off in used
+                for c0 in range(0, ln, LANES)]
+
     def refresh(self):
-        P = sorted((i for i in range(self.n) if self.a[i] > 0), key=lambda i: (self.a[i], i))
+        P = self._refresh_order()
         l = 0.0
         for i in P:
             l = l + self.e[i].b * self.a[i]
@@ -278,7 +294,7 @@ class QPRef:
             idC[gS[k]] = idC[gS[k]] + self.a[i]
             if self.a[i] > 0:
                 idI[gS[k]] = i
-        self.branches = []
+        self.branches, self.detail = [], []
         for k in perm:
             i, j = S[int(k)], gS[int(k)]
             self._step(i, j, idC, idI, err)
@@ -291,49 +307,158 @@ class QPRef:
         self.loss = loss
         self.ub = self.ww * 0.5 + loss
 
+    # -- one step of qp_one_sparse.cc.  Every comparison and every bound is one method, so that a test can restate a single rule
+    # (tests/test_qp_hard_cpu.py); _step records in self.detail which of them applied.  The arithmetic and its order are the
+    # mex file's.  Labels: plain_free / plain_floor0 / plain_cap_maxA; pair_up_free / pair_up_bound_1-Ai / pair_up_bound_A2 (dA > 0);
+    # pair_down_free / pair_down_bound_-Ai / pair_down_bound_A2-1 (dA <= 0); pair_G_zeroed; pair_small_G; none_lower; none_upper;
+    # i2_is_i; sv_clear; err_raised; G_is_0; clamp_changed_w_plain / _pair; pair_blocks_i2_lacks / _i2_extra / _shifted.  A bound's
+    # label applies when the unbounded value reaches the bound and the result equals it: equal bounds give both labels.
+    EPS = 1e-12
+
+    def _is_lower(self, Ai, G):          # at the lower bound with a gradient that pushes further down
+        return Ai == 0 and G >= 0
+
+    def _is_upper(self, Ci, G):          # in a saturated group with a gradient that pushes further up
+        return self._saturated(Ci) and G <= 0
+
+    def _saturated(self, Ci):
+        return Ci >= 1
+
+    def _pair_saturated(self, Ci):       # the paired path's own "Ci >= 1"
+        return self._saturated(Ci)
+
+    def _clears_sv(self, Ai, G):         # strict: an entry at 0 with G == 0 stays a support vector
+        return Ai == 0 and G > 0
+
+    def _moves(self, G):
+        return G > self.EPS or G < -self.EPS
+
+    def _other(self, i2, i):
+        return i2 != i
+
+    def _pair_zeroes_G(self, Ai, G):
+        return Ai == 0 and G > 0
+
+    def _pair_zeroed_G(self, G):
+        return 0.0
+
+    def _plain_floor(self, x):
+        return _max(x, 0.0)
+
+    def _plain_cap(self, x, maxA):
+        return _min(x, maxA)
+
+    def _pair_up_own(self, dA, Ai):      # dA > 0: a[i] <= 1
+        return _min(dA, 1.0 - Ai)
+
+    def _pair_up_other(self, dA, A2):    # dA > 0: a[i2] >= 0
+        return _min(dA, A2)
+
+    def _pair_down_own(self, dA, Ai):    # dA <= 0: a[i] >= 0
+        return _max(dA, -Ai)
+
+    def _pair_down_other(self, dA, A2):  # dA <= 0: a[i2] <= 1
+        return _max(dA, A2 - 1.0)
+
+    def _plain_update(self, dA, i):
+        self._axpy(dA, i)
+        return self._clamp()
+
+    def _pair_update(self, dA, i, i2):
+        self._axpy(dA, i)
+        self._axpy(-dA, i2)
+        return self._clamp()
+
+    def _note_err(self, err, j, G, det):
+        if -G > err[j]:
+            err[j] = -G
+            det.add("err_raised")
+
+    def _note_err_late(self, err, j, G, det):
+        pass
+
+    def _note_idI(self, idI, j, i):
+        if self.a[i] > 0:
+            idI[j] = i
+
+    def _pair_blocks(self, i, i2, det):
+        b1 = {off: st for off, ln, st in self.e[i].blocks}
+        b2 = {off: st for off, ln, st in self.e[i2].blocks}
+        if any(off not in b2 for off in b1):
+            det.add("pair_blocks_i2_lacks")
+        if any(off not in b1 for off in b2):
+            det.add("pair_blocks_i2_extra")
+        if any(off in b2 and b2[off] != st for off, st in b1.items()):
+            det.add("pair_blocks_shifted")
+
     def _step(self, i, j, idC, idI, err):
         a = self.a
+        det = set()
         Ai = _max(_min(a[i], 1.0), 0.0)
         a[i] = Ai
         Ci = _max(_min(idC[j], 1.0), Ai)
         G = self.wx(i) - self.e[i].b
         PG = G
-        if (Ai == 0 and G >= 0) or (Ci >= 1 and G <= 0):
+        if G == 0:
+            det.add("G_is_0")
+        lower, upper = self._is_lower(Ai, G), self._is_upper(Ci, G)
+        if lower or upper:
             PG = 0.0
-        if -G > err[j]:
-            err[j] = -G
-        if Ai == 0 and G > 0:
+        self._note_err(err, j, G, det)
+        if self._clears_sv(Ai, G):
             self.sv[i] = 0
+            det.add("sv_clear")
         i2 = idI[j]
+        if i2 == i:
+            det.add("i2_is_i")
         branch = "none"
-        if Ci >= 1 and G < -1e-12 and Ai < 1 and i2 != i and i2 >= 0:
+        if self._pair_saturated(Ci) and G < -self.EPS and Ai < 1 and self._other(i2, i) and i2 >= 0:
+            self._pair_blocks(i, i2, det)
             G = G - (self.wx(i2) - self.e[i2].b)
-            if Ai == 0 and G > 0:
-                G = 0.0
+            if self._pair_zeroes_G(Ai, G):
+                G = self._pair_zeroed_G(G)
                 self.sv[i] = 0
-            if G > 1e-12 or G < -1e-12:
+                det.update(("pair_G_zeroed", "sv_clear"))
+            if self._moves(G):
+                A2 = a[i2]
                 dA = _div(-G, self.e[i].d + self.e[i2].d - 2.0 * self.xx(i, i2))
                 if dA > 0:
-                    dA = _min(_min(dA, 1.0 - Ai), a[i2])
+                    own, other = 1.0 - Ai, A2
+                    raw, dA = dA, self._pair_up_other(self._pair_up_own(dA, Ai), A2)
+                    hit = [n for n, b in (("pair_up_bound_1-Ai", own), ("pair_up_bound_A2", other)) if raw >= b and dA == b]
+                    det.update(hit or ["pair_up_free"])
                 else:
-                    dA = _max(_max(dA, -Ai), a[i2] - 1.0)
+                    own, other = -Ai, A2 - 1.0
+                    raw, dA = dA, self._pair_down_other(self._pair_down_own(dA, Ai), A2)
+                    hit = [n for n, b in (("pair_down_bound_-Ai", own), ("pair_down_bound_A2-1", other)) if raw <= b and dA == b]
+                    det.update(hit or ["pair_down_free"])
                 a[i] = Ai + dA
                 a[i2] = a[i2] - dA
-                self._axpy(dA, i)
-                self._axpy(-dA, i2)
-                self._clamp()
+                if self._pair_update(dA, i, i2):
+                    det.add("clamp_changed_w_pair")
                 branch = "pair"
-        elif PG > 1e-12 or PG < -1e-12:
+            else:
+                det.add("pair_small_G")
+        elif self._moves(PG):
             maxA = 1.0 - (Ci - Ai)
-            a[i] = _min(_max(Ai - _div(G, self.e[i].d), 0.0), maxA)
+            raw = Ai - _div(G, self.e[i].d)
+            a[i] = self._plain_cap(self._plain_floor(raw), maxA)
+            hit = [n for n, ok in (("plain_floor0", raw <= 0.0 and a[i] == 0.0), ("plain_cap_maxA", raw >= maxA and a[i] == maxA)) if ok]
+            det.update(hit or ["plain_free"])
             dA = a[i] - Ai
             idC[j] = _min(_max(Ci + dA, 0.0), 1.0)
-            self._axpy(dA, i)
-            self._clamp()
+            if self._plain_update(dA, i):
+                det.add("clamp_changed_w_plain")
             branch = "plain"
-        if a[i] > 0:
-            idI[j] = i
+        else:
+            if lower:
+                det.add("none_lower")
+            if upper:
+                det.add("none_upper")
+        self._note_err_late(err, j, G, det)
+        self._note_idI(idI, j, i)
         self.branches.append(branch)
+        self.detail.append(frozenset(det))
 
     # -- qp_opt
     def true_loss(self) -> float:
