@@ -152,7 +152,9 @@ __global__ __launch_bounds__(kPlThreads) void k_pl_normals(PlaneParams p)
                 float nx = __fsub_rn(__fmul_rn(myy, mxz), __fmul_rn(myz, mxy));
                 float ny = __fsub_rn(__fmul_rn(myz, mxx), __fmul_rn(myx, mxz));
                 float nz = __fsub_rn(__fmul_rn(myx, mxy), __fmul_rn(myy, mxx));
-                const float len = __fsqrt_rn(pl_dot3(nx, ny, nz, nx, ny, nz));
+                // sqrtf is the correctly rounded root; __fsqrt_rn is the native one here (an ulp off on some inputs), and
+                // an ulp in a normal decides a join whose dot product sits at cos_thr (tests/cloud_hard_scenes.py, joins)
+                const float len = sqrtf(pl_dot3(nx, ny, nz, nx, ny, nz));
                 nx = __fdiv_rn(nx, len); ny = __fdiv_rn(ny, len); nz = __fdiv_rn(nz, len);
                 if (pl_dot3(nx, ny, nz, v.x, v.y, v.z) > 0.f) { nx = -nx; ny = -ny; nz = -nz; }
                 out = make_float4(nx, ny, nz, pl_dot3(nx, ny, nz, v.x, v.y, v.z));

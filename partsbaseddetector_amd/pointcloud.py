@@ -39,6 +39,84 @@ class PlaneParams:
 JACOBI_SWEEPS = 8
 
 
+# ---- the contract's comparisons and choices, each stated once.  The yardsticks below call them by name, so a test can swap a
+# single one (tests/test_cloud_hard_cpu.py) and show that some input notices; none of them holds arithmetic of its own.
+def edge_tolerance(t_centre, t_neighbour):
+    """the depth-edge test |z(q) - z(p)| > depth_change * z compares with the z of the centre p"""
+    return t_centre
+
+
+def join_depth(z_current, z_neighbour):
+    """the join threshold dist * z * z takes the z of the current point"""
+    return z_current
+
+
+def absorb_depth(z_from, z_absorbed):
+    """the absorb threshold dist * z * z takes the z of the neighbour the plane comes from"""
+    return z_from
+
+
+def join_near(distance, threshold):
+    """the join's distance test is strict"""
+    return distance < threshold
+
+
+def absorb_near(distance, threshold):
+    """the absorb's distance test is strict"""
+    return distance < threshold
+
+
+def parallel(dot, cos_thr):
+    """the angular test is strict"""
+    return dot > cos_thr
+
+
+def refine_upper_column(c, W):
+    """the last column takes no label from above"""
+    return c <= W - 2
+
+
+def refine_upper_right(fin, r, c):
+    """taking a label from above needs (r-1, c+1) finite (callers hold c <= W-2 unless refine_upper_column is changed)"""
+    return fin[r - 1, np.minimum(c + 1, fin.shape[1] - 1)]
+
+
+def refine_left_row(r, H):
+    """the last row takes no label from the left"""
+    return r <= H - 2
+
+
+REFINE_ORDER = ("upper", "left")              # a point both neighbours would absorb takes the upper one's plane
+
+
+def moment_total(v):
+    """one moment of a segment: each row left to right from 0, then the row sums top to bottom from 0 (v: (rows, cols) doubles)"""
+    rows = np.add.accumulate(np.concatenate([np.zeros((v.shape[0], 1)), v], axis=1), axis=1)[:, -1]
+    return float(np.add.accumulate(np.concatenate([[0.0], rows]))[-1])
+
+
+def inside(p, lo, hi):
+    """the faces of the crop box are inside"""
+    return (p >= lo).all(axis=1) & (p <= hi).all(axis=1)
+
+
+def within_radius(d2):
+    """a pair at the radius exactly is an edge"""
+    return d2.astype(np.float64) <= RADIUS2
+
+
+def neighbour_cells():
+    """the 27 cells around a point's own, as 13 directions, their opposites implied (each unordered pair of cells once), and
+    the cell itself"""
+    offs = [(dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1)]
+    return [o for o in offs if o > (0, 0, 0)] + [(0, 0, 0)]
+
+
+def largest(size):
+    """the largest component; ties: the smallest first index"""
+    return int(np.flatnonzero(size == size.max())[0])
+
+
 @dataclass(frozen=True)
 class PinholeCamera:
     fx: float
@@ -160,7 +238,7 @@ class PointCloudClusterer:
         if g is None:
             return np.zeros(0, np.int64)
         p = _xyz(cloud)
-        ok = np.isfinite(p).all(axis=1) & (p >= g[0]).all(axis=1) & (p <= g[1]).all(axis=1)
+        ok = np.isfinite(p).all(axis=1) & inside(p, g[0], g[1])
         return np.nonzero(ok)[0]
 
     @staticmethod
@@ -179,9 +257,7 @@ class PointCloudClusterer:
         skey = key[order]
         ukey, ustart, ucount = np.unique(skey, return_index=True, return_counts=True)
         ea, eb = [], []
-        offs = [(dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1)]
-        offs = [o for o in offs if o > (0, 0, 0)] + [(0, 0, 0)]          # each unordered cell pair once
-        for dx, dy, dz in offs:
+        for dx, dy, dz in neighbour_cells():                             # each unordered cell pair once
             nk = ukey + (dx * span[1] + dy) * span[2] + dz
             pos = np.searchsorted(ukey, nk)
             pos = np.minimum(pos, len(ukey) - 1)
@@ -202,7 +278,7 @@ class PointCloudClusterer:
                 a, b = a[keep], b[keep]
             dd = P[a] - P[b]
             d2 = (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2]
-            e = d2.astype(np.float64) <= RADIUS2
+            e = within_radius(d2)
             ea.append(a[e])
             eb.append(b[e])
         if not ea:
@@ -252,7 +328,7 @@ class PointCloudClusterer:
         P = _xyz(cloud)[idx]
         lab = PointCloudClusterer.components(P)
         size = np.bincount(lab, minlength=len(P))
-        best = int(np.flatnonzero(size == size.max())[0])        # the largest; ties: the smallest first index
+        best = largest(size)
         members = np.nonzero(lab == best)[0]
         return centroid(P[members]), idx[members]
 
@@ -282,8 +358,7 @@ class PointCloudClusterer:
         planes = np.array(planes, np.float32).reshape(-1, 4)
         lab = lab.reshape(H, W)
         if q.refine and len(planes):
-            lab = plane_refine_pass(lab, P, planes, q.distance_threshold)
-            lab = plane_refine_pass(lab[::-1, ::-1], P[::-1, ::-1], planes, q.distance_threshold)[::-1, ::-1]
+            lab = plane_refine(lab, P, planes, q.distance_threshold)
         lab = np.ascontiguousarray(lab)
         kept = np.nonzero(lab.ravel() < 0)[0]
         labels = np.where(lab >= 0, lab, -1).astype(np.int32)
@@ -329,7 +404,7 @@ def plane_normals(P: np.ndarray, s: int, depth_change: float):
         zc, tc = z[1:-1, 1:-1], t[1:-1, 1:-1]
         for sl in ((slice(1, -1), slice(0, -2)), (slice(1, -1), slice(2, None)), (slice(0, -2), slice(1, -1)),
                    (slice(2, None), slice(1, -1))):
-            e |= ~fin[sl] | (np.abs(z[sl] - zc) > tc)
+            e |= ~fin[sl] | (np.abs(z[sl] - zc) > edge_tolerance(tc, t[sl]))
         edge[1:-1, 1:-1] = e
         dx = np.full_like(P, np.nan)
         dy = np.full_like(P, np.nan)
@@ -373,12 +448,13 @@ def plane_normals(P: np.ndarray, s: int, depth_change: float):
     return N, D
 
 
-def plane_join(zp, np_, dp, fq, nq, dq, dist: float, cos_thr):
+def plane_join(zp, np_, dp, fq, nq, dq, dist: float, cos_thr, zq=None):
     """PlaneCoefficientComparator(p, q): q finite, |d(p) - d(q)| < dist * (z(p) * z(p)), n(p) . n(q) > cos_thr (arrays)"""
     with np.errstate(invalid="ignore", over="ignore"):
-        near = np.abs(dp - dq) < _F(dist) * (zp * zp)
+        zt = join_depth(zp, zq)
+        near = join_near(np.abs(dp - dq), _F(dist) * (zt * zt))
         dot = (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2]
-        return fq & near & (dot > cos_thr)
+        return fq & near & parallel(dot, cos_thr)
 
 
 def plane_segments(P, N, D, dist: float, angle: float) -> np.ndarray:
@@ -388,8 +464,8 @@ def plane_segments(P, N, D, dist: float, angle: float) -> np.ndarray:
     cos_thr = _F(math.cos(angle))
     z = P[..., 2]
     idx = np.arange(H * W).reshape(H, W)
-    left = fin[:, 1:] & plane_join(z[:, 1:], N[:, 1:], D[:, 1:], fin[:, :-1], N[:, :-1], D[:, :-1], dist, cos_thr)
-    up = fin[1:] & plane_join(z[1:], N[1:], D[1:], fin[:-1], N[:-1], D[:-1], dist, cos_thr)
+    left = fin[:, 1:] & plane_join(z[:, 1:], N[:, 1:], D[:, 1:], fin[:, :-1], N[:, :-1], D[:, :-1], dist, cos_thr, z[:, :-1])
+    up = fin[1:] & plane_join(z[1:], N[1:], D[1:], fin[:-1], N[:-1], D[:-1], dist, cos_thr, z[:-1])
     ea = np.concatenate([idx[:, 1:][left], idx[1:][up]])
     eb = np.concatenate([idx[:, :-1][left], idx[:-1][up]])
     return min_label_components(H * W, ea, eb)
@@ -446,10 +522,7 @@ def plane_fit(P, mask, count: int):
     bottom, the Jacobi eigenpair"""
     x, y, z = (np.where(mask, P[..., k].astype(np.float64), 0.0) for k in range(3))
     vals = (x, y, z, x * x, x * y, x * z, y * y, y * z, z * z)
-    tot = []
-    for v in vals:
-        rows = np.add.accumulate(np.concatenate([np.zeros((v.shape[0], 1)), v], axis=1), axis=1)[:, -1]
-        tot.append(float(np.add.accumulate(np.concatenate([[0.0], rows]))[-1]))
+    tot = [moment_total(v) for v in vals]
     n = float(count)
     m = [t / n for t in tot]
     xx, xy, xz = m[3] - m[0] * m[0], m[4] - m[0] * m[1], m[5] - m[0] * m[2]
@@ -483,7 +556,14 @@ def plane_absorb(coef, pts, zc, dist: float):
     """|((a x + b y) + c z) + d| < dist * (zc * zc) in float32 (coef (k, 4), pts (k, 3))"""
     with np.errstate(invalid="ignore", over="ignore"):
         dd = ((coef[:, 0] * pts[:, 0] + coef[:, 1] * pts[:, 1]) + coef[:, 2] * pts[:, 2]) + coef[:, 3]
-        return np.abs(dd) < _F(dist) * (zc * zc)
+        zt = absorb_depth(zc, pts[:, 2])
+        return absorb_near(np.abs(dd), _F(dist) * (zt * zt))
+
+
+def plane_refine(lab, P, planes, dist: float) -> np.ndarray:
+    """the forward pass, then the backward pass: the forward pass on the image turned by 180 degrees"""
+    lab = plane_refine_pass(lab, P, planes, dist)
+    return plane_refine_pass(lab[::-1, ::-1], P[::-1, ::-1], planes, dist)[::-1, ::-1]
 
 
 def plane_refine_pass(lab, P, planes, dist: float) -> np.ndarray:
@@ -496,24 +576,23 @@ def plane_refine_pass(lab, P, planes, dist: float) -> np.ndarray:
         r = np.arange(max(0, t - W + 1), min(H - 1, t) + 1)
         c = t - r
         m = o[r, c].copy()
-        sel = (r >= 1) & (c <= W - 2) & (m == -2)
-        if sel.any():
+        for step in REFINE_ORDER:
+            if step == "upper":
+                sel = (r >= 1) & refine_upper_column(c, W) & (m == -2)
+                dr, dc = 1, 0
+            else:
+                sel = (c >= 1) & refine_left_row(r, H) & (m == -2)
+                dr, dc = 0, 1
+            if not sel.any():
+                continue
             rs, cs = r[sel], c[sel]
-            u = F[rs - 1, cs]
-            ok = (u >= 0) & fin[rs - 1, cs + 1]
-            ok[ok] = plane_absorb(planes[u[ok]], P[rs[ok], cs[ok]], P[rs[ok] - 1, cs[ok], 2], dist)
+            src = F[rs - dr, cs - dc]
+            ok = src >= 0
+            if step == "upper":
+                ok &= refine_upper_right(fin, rs, cs)
+            ok[ok] = plane_absorb(planes[src[ok]], P[rs[ok], cs[ok]], P[rs[ok] - dr, cs[ok] - dc, 2], dist)
             mm = m[sel]
-            mm[ok] = u[ok]
+            mm[ok] = src[ok]
             m[sel] = mm
-        f = m.copy()
-        sel = (c >= 1) & (r <= H - 2) & (m == -2)
-        if sel.any():
-            rs, cs = r[sel], c[sel]
-            lft = F[rs, cs - 1]
-            ok = lft >= 0
-            ok[ok] = plane_absorb(planes[lft[ok]], P[rs[ok], cs[ok]], P[rs[ok], cs[ok] - 1, 2], dist)
-            ff = f[sel]
-            ff[ok] = lft[ok]
-            f[sel] = ff
-        F[r, c] = f
+        F[r, c] = m
     return F
