@@ -21,7 +21,8 @@ def samples(depth: np.ndarray, box, dtype) -> np.ndarray:
     x2, y2 = min(x + w, dcols), min(y + h, drows)
     if x2 - x1 <= 0 or y2 - y1 <= 0:
         return np.zeros(0, dtype)
-    s = np.asarray(depth[y1:y2, x1:x2]).astype(dtype).ravel()
+    with np.errstate(over="ignore"):                  # a double beyond FLT_MAX rounds to Inf
+        s = np.asarray(depth[y1:y2, x1:x2]).astype(dtype).ravel()
     s[np.isnan(s)] = 0
     return s
 

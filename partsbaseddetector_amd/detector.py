@@ -76,10 +76,31 @@ class Candidate:
         The yardstick of pbd_boxes3d (include/pbd.h states the contract); it restates cv::resize INTER_LINEAR (float), cv::filter2D
         (float, BORDER_REFLECT_101, zero taps skipped) and getGaussianKernel.  Where the reference fails an OpenCV assertion
         (every box of zero area) the result is the NaN box, as on the device."""
+        st = self.boundingBox3D_steps(im_shape, depth)
+        if st is None:
+            return (math.nan, math.nan, math.nan, 0.0, 0.0, 0.0)
+        p = st["p"]
+        bx, by, bw, bh = self.boundingBox()
+        z0, z1 = float(p[st["dmin"]]), float(p[st["dmax"]])
+        return float(bx), float(by), z0, float(bh), float(bw), z1 - z0
+
+    def boundingBox3D_steps(self, im_shape, depth: np.ndarray) -> Optional[dict]:
+        """boundingBox3D's intermediate results: S (the valid samples, ascending), p (the 400 resampled points), d (the filtered
+        points) and the rows dmin, dmax at which the walk from the median ends; None for the NaN box"""
+        S = self._samples3d(im_shape, depth)
+        if S is None:
+            return None
+        p = _resize_linear_400(S)
+        d = _dog_filter_400(p)
+        dmin, dmax = _walk_400(d)
+        return {"S": S, "p": p, "d": d, "dmin": dmin, "dmax": dmax}
+
+    def _samples3d(self, im_shape, depth: np.ndarray) -> Optional[np.ndarray]:
+        """the valid samples (neither 0 nor NaN as float32) of the part boxes and boundingBoxNorm(), sorted; None where the
+        reference returns the NaN box (the first non-empty box holds no valid sample) or every box is empty"""
         rows, cols = int(im_shape[0]), int(im_shape[1])
         drows, dcols = depth.shape[:2]
         sx, sy = dcols / float(cols), drows / float(rows)
-        nan_box = (math.nan, math.nan, math.nan, 0.0, 0.0, 0.0)
         boxes = [_rect_and(tuple(int(v) for v in r), (0, 0, cols, rows)) for r in self.parts]
         boxes.append(_rect_and(self.boundingBoxNorm(), (0, 0, cols, rows)))
         chunks, m = [], 0
@@ -92,33 +113,10 @@ class Candidate:
             chunks.append(v)
             m += v.size
             if m == 0:
-                return nan_box                                # the first non-empty box held no valid sample
+                return None                                   # the first non-empty box held no valid sample
         if m == 0:
-            return nan_box
-        S = np.sort(np.concatenate(chunks))
-        p = _resize_linear_400(S)
-        d = np.zeros(400, np.float32)
-        idx = np.arange(400)
-        with np.errstate(invalid="ignore", over="ignore"):
-            for t, k in enumerate(_dog_taps()):
-                if k == 0:
-                    continue
-                j = np.abs(idx + t - 17)
-                j = np.where(j >= 400, 2 * 399 - j, j)
-                d = d + k * p[j]
-        mid = 200
-        dmax = dmin = mid
-        for m_ in range(mid, 400):
-            if float(abs(d[m_])) > 0.035:
-                break
-            dmax = m_
-        for m_ in range(mid, -1, -1):
-            if float(abs(d[m_])) > 0.035:
-                break
-            dmin = m_
-        bx, by, bw, bh = self.boundingBox()
-        z0, z1 = float(p[dmin]), float(p[dmax])
-        return float(bx), float(by), z0, float(bh), float(bw), z1 - z0
+            return None
+        return np.sort(np.concatenate(chunks))
 
     @staticmethod
     def mask(im_shape, candidates: Sequence["Candidate"]) -> np.ndarray:
@@ -175,6 +173,35 @@ def _dog_taps() -> np.ndarray:
         a, b = (1 if i == 0 else i - 1), (33 if i == 34 else i + 1)
         dog[i] = (np.float32(0) + np.float32(-1) * g[a]) + np.float32(1) * g[b]
     return dog
+
+
+def _dog_filter_400(p: np.ndarray) -> np.ndarray:
+    """cv::filter2D(p, -1, dog) of the 400 points: float32, BORDER_REFLECT_101, zero taps skipped, taps added in order"""
+    d = np.zeros(400, np.float32)
+    idx = np.arange(400)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t, k in enumerate(_dog_taps()):
+            if k == 0:
+                continue
+            j = np.abs(idx + t - 17)
+            j = np.where(j >= 400, 2 * 399 - j, j)
+            d = d + k * p[j]
+    return d
+
+
+def _walk_400(d: np.ndarray):
+    """Candidate.hpp:197-205: from row 200 out, the last rows (dmin, dmax) before |d| > 0.035"""
+    mid = 200
+    dmax = dmin = mid
+    for m_ in range(mid, 400):
+        if float(abs(d[m_])) > 0.035:
+            break
+        dmax = m_
+    for m_ in range(mid, -1, -1):
+        if float(abs(d[m_])) > 0.035:
+            break
+        dmin = m_
+    return dmin, dmax
 
 
 def _resize_linear_400(S: np.ndarray) -> np.ndarray:
