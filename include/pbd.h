@@ -415,6 +415,87 @@ int pbd_suppress(pbd_handle *h, int nframes, const int *im_rows, const int *im_c
 int pbd_suppress_device(pbd_handle *h, int nframes, const int *im_rows, const int *im_cols, float overlap,
                         const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
 
+/* ---- Testing a model (new surface; opt-in): the reference's Matlab test code on the device -- matlab/detection/testmodel.m,
+ * testmodel_gtbox.m, nms.m, bestoverlap.m and matlab/evaluation/eval_pck.m, eval_apk.m, VOCap.m.  DESIGN.md section 6l.
+ * Shared by the four calls:
+ *   records  this handle's (pbd_candidate_stride); a record's frame is its `frame` field - frame_offset.  Every record is read
+ *            with the model's part count nparts; a model whose components differ in part count is PBD_ERR_UNSUPPORTED (Matlab's
+ *            box matrix has one width).  The _device forms read min(max(word 0, 0), capacity) records of a payload, are
+ *            asynchronous on pbd_stream() and take the ground truth from HOST arrays, as frame sizes are elsewhere
+ *   corners  of part j: x1 = x, y1 = y, x2 = x + w, y2 = y + h, the two points the reference built the cv::Rect from
+ *            (src/DynamicProgram.cpp:238-242): detect.m's corners rounded and shifted by one.  Areas are inclusive,
+ *            (x2 - x1 + 1) * (y2 - y1 + 1), as in pbd_detect_latent.  Every formula depends on coordinate differences only, so
+ *            0-based and 1-based coordinates give the same result.  Centre of part j: (.5 * x1 + .5 * x2, .5 * y1 + .5 * y2)
+ *   numbers  all arithmetic is double, each operation rounded on its own in the order written, division and sqrt correctly
+ *            rounded; min(a, b) is b < a ? b : a and max(a, b) is b > a ? b : a; no special cases beyond the ones stated (a
+ *            record with a negative size follows IEEE)
+ *   state    PBD_ERR_STATE while a batch is in flight; the resident detect result is not touched; nframes is 1..65535 and a
+ *            list holds fewer than 2^30 parts (capacity * nparts), PBD_ERR_INVALID otherwise
+ *
+ * pbd_part_nms: nms.m per frame, the paper's suppression -- NOT the painted canvas of pbd_set_nms / pbd_suppress.  Records
+ * grouped by ascending frame.  max_boxes is 1..1000 (Matlab's constant is 1000; PBD_ERR_INVALID otherwise).  Per frame:
+ *   cut      with more than max_boxes records the list becomes its max_boxes highest scores in descending order, ties in list
+ *            order (Matlab's stable sort(.., 'descend')); the list is reordered, as boxes(I(1:1000), :).  Otherwise it stays
+ *   order    [vals, I] = sort(s) ascending and stable, taken from the end: the highest score first, among equal scores the LAST
+ *            of the current list first; -0.0 and +0.0 tie
+ *   boxes    b = 0 .. nparts of a record: its parts, then the hull min x1, min y1, max x2, max y2
+ *   test     w = min(x2_i, x2_j) - max(x1_i, x1_j) + 1, 0 if negative, h likewise; o_b = (w * h) / area_i[b]; pick i removes
+ *            every remaining j with max_b o_b > (double)overlap (a NaN o_b never does).  The divisor is the PICKER's area
+ *   project decisions  the pick itself always leaves (Matlab loops forever when overlap >= 1); a NaN overlap is
+ *            PBD_ERR_INVALID; NaN scores sort last, in list order, in the cut and in the pick order alike
+ * Output as pbd_suppress*: frame by frame the kept records in pick order, unchanged.  pbd_part_nms: host records (a frame index
+ * out of range or below its predecessor's, or nparts outside 1..max parts, is PBD_ERR_INVALID naming the record); *nout = the
+ * kept count, above `capacity` the first `capacity` records and PBD_ERR_CAPACITY.  pbd_part_nms_device: d_out = int32[1 +
+ * out_capacity * stride], word 0 = the kept count (may exceed out_capacity), or -1 for an input word 0 that is negative or above
+ * capacity and for a list that is not grouped by ascending frame inside 0..nframes-1.  The workspace holds 128 KB per frame for
+ * max_boxes = 1000 (a 1000 x 1000 bit matrix) plus 40 bytes per (frame, max_boxes) and 8 per record. */
+int pbd_part_nms(pbd_handle *h, int nframes, float overlap, int max_boxes, const int32_t *cand, int ncand, int frame_offset,
+                 int32_t *out, int capacity, int *nout);
+int pbd_part_nms_device(pbd_handle *h, int nframes, float overlap, int max_boxes, const int32_t *d_payload, int capacity,
+                        int frame_offset, int32_t *d_out, int out_capacity);
+/* pbd_best_overlap: bestoverlap.m per frame, the step after detect_fast in testmodel_gtbox.m.  Records in any order.
+ * gtbox = double[nframes][4] on the host, {x1, y1, x2, y2} inclusive; a NaN anywhere in a row: the frame has no ground truth
+ * (Matlab's isempty(gtbox)).  A record passes when, with bx1 .. by2 the hull of its part CENTRES, w = min(x2, bx2) - max(x1, bx1)
+ * + 1 (0 if negative), h likewise, (w * h) / gtarea > (double)overlap.  The passing record of the highest score wins, the FIRST
+ * in list order among equals (Matlab's max); -0.0 and +0.0 tie.  Project decision: a record with a NaN score is never chosen.
+ * Output as pbd_detect_latent: record f at out + f * stride and found[f]; a frame where nothing is found has found[f] = 0 and a
+ * record of zeros.  The device form writes d_out and d_found, ignores records whose frame is out of range (the host form refuses
+ * them) and takes lists of any length (the kernel strides over them).  A NaN overlap is PBD_ERR_INVALID. */
+int pbd_best_overlap(pbd_handle *h, int nframes, const double *gtbox, float overlap, const int32_t *cand, int ncand, int frame_offset,
+                     int32_t *out, int32_t *found);
+int pbd_best_overlap_device(pbd_handle *h, int nframes, const double *gtbox, float overlap, const int32_t *d_payload, int capacity,
+                            int frame_offset, int32_t *d_out, int32_t *d_found);
+/* pbd_eval_pck: eval_pck.m on pbd_best_overlap's output: rec = int32[nframes][stride], found[nframes] (device pointers in the
+ * device form), gt_points = double[nframes][nparts][2] and scale = double[nframes] on the host.  dist[p][f] = sqrt(dx * dx +
+ * dy * dy) with d = centre - gt; a hit is dist < thresh * scale[f], strict; pck[p] = (double)hits / (double)nframes.  Project
+ * decisions: a frame that is not found has dist = +Inf and is a miss; a NaN distance is a miss and is written as the quiet NaN
+ * 0x7ff8000000000000 whatever its source.  Outputs pck[nparts] and, unless NULL,
+ * dist[nparts][nframes].  Two quirks of the reference are NOT reproduced: its `nargin < 4` test always sets thresh = 0.5, and it
+ * multiplies by the LAST frame's scale for every frame (a caller who wants that passes the last scale in every entry). */
+int pbd_eval_pck(pbd_handle *h, int nframes, const int32_t *rec, const int32_t *found, const double *gt_points, const double *scale,
+                 double thresh, double *pck, double *dist);
+int pbd_eval_pck_device(pbd_handle *h, int nframes, const int32_t *d_rec, const int32_t *d_found, const double *gt_points,
+                        const double *scale, double thresh, double *d_pck, double *d_dist);
+/* pbd_eval_apk: eval_apk.m + VOCap.m for every part at once, on any list (typically pbd_part_nms's over a test set).  On the
+ * host: gt_offset = int32[nframes + 1] (frame f's instances are gt_offset[f] .. gt_offset[f + 1] - 1; gt_offset[0] = 0,
+ * non-decreasing), G = gt_offset[nframes], gt_points = double[G][nparts][2], gt_scale = double[G].  G == 0 is PBD_ERR_INVALID
+ * (recall would be 0 / 0).  One order is shared by all parts: score descending, stable, NaN last.  Per part p and rank n of a
+ * record of frame f: without ground truth in f the record is a false positive; otherwise d_g = sqrt(dx * dx + dy * dy) / scale_g
+ * over the frame's instances, distmin the minimum and jmin its FIRST occurrence, NaN entries ignored (all NaN: a false positive);
+ * the record is a true positive iff distmin <= thresh and no earlier rank of this frame with distmin <= thresh had the same jmin
+ * (the gt.det flag).  rec[n] = tpcum / (double)G, prec[n] = tpcum / (double)(n + 1).  VOCap: the running maximum of
+ * [0; prec; 0] from the end, mrec = [0; rec; 1], ap = the sum of (mrec(i) - mrec(i-1)) * mpre(i) over the i where mrec changes,
+ * from 0.0 in ascending i, each product and addition rounded on its own.  Outputs apk[nparts] and, unless NULL, prec and rec
+ * = double[nparts][capacity] (ncand for the host form), the first n of each row written.  An empty list gives apk = 0.  The
+ * device form writes *d_status = the record count, or -1 for a word 0 that is negative or above capacity, and then nothing else;
+ * a record whose frame is out of range is a false positive there (the host form refuses it).  The order costs one comparison
+ * per pair of records. */
+int pbd_eval_apk(pbd_handle *h, int nframes, const int32_t *gt_offset, const double *gt_points, const double *gt_scale, double thresh,
+                 const int32_t *cand, int ncand, int frame_offset, double *apk, double *prec, double *rec);
+int pbd_eval_apk_device(pbd_handle *h, int nframes, const int32_t *gt_offset, const double *gt_points, const double *gt_scale,
+                        double thresh, const int32_t *d_payload, int capacity, int frame_offset, double *d_apk, double *d_prec,
+                        double *d_rec, int32_t *d_status);
+
 /* Candidate mask (new surface; opt-in): Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) and the ROS node's
  * masked colour frame `rgb & (mask != 0)` (ros/Messages.cpp:157-174, topic <name>/mask), for records of this handle spanning
  * several frames.  A record's frame index is `frame` - frame_offset (as pbd_boxes3d); frame f is im_rows[f] x im_cols[f]
@@ -851,6 +932,10 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        /* pbd_warp_positives*: the patches of the kept boxes, then every box's example (the HOG of the patches is timed under
           k_hog_hist / k_hog_feat) */
        PBD_K_WARP, PBD_K_WARP_EMIT,
+       /* pbd_part_nms* (k_ev_nms_select times the check, the cut and the pick ranks), pbd_best_overlap*, pbd_eval_pck*,
+          pbd_eval_apk* (k_ev_apk_rank times the keys and the order) */
+       PBD_K_EV_NMS_SELECT, PBD_K_EV_NMS_PAIRS, PBD_K_EV_NMS_GREEDY, PBD_K_EV_NMS_EMIT, PBD_K_EV_BEST, PBD_K_EV_PCK,
+       PBD_K_EV_APK_RANK, PBD_K_EV_APK_CLOSE, PBD_K_EV_APK_AP,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

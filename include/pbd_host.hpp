@@ -930,6 +930,84 @@ public:
         found.assign(n, false);
         for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
     }
+    // ---- testing a model on the device (include/pbd.h "Testing a model"): matlab/detection/nms.m, bestoverlap.m and
+    // matlab/evaluation/eval_pck.m, eval_apk.m + VOCap.m.  Candidates carry their frame in `frame` (0 .. nframes-1).
+    // records() with every candidate's own frame
+    std::vector<int32_t> frameRecords(const std::vector<Candidate> &candidates) const
+    {
+        std::vector<int32_t> rec = records(candidates);
+        const size_t stride = (size_t)pbd_candidate_stride(h_);
+        for (size_t i = 0; i < candidates.size(); ++i) rec[i * stride] = candidates[i].frame;
+        return rec;
+    }
+    // nms.m per frame (pbd_part_nms): candidates grouped by ascending frame; the kept ones, frame by frame, in pick order
+    std::vector<Candidate> partNMS(const std::vector<Candidate> &candidates, int nframes, float overlap = 0.3f, int max_boxes = 1000)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "partNMS() before distributeModel()");
+        std::vector<int32_t> rec = frameRecords(candidates);
+        int n = 0;
+        pbdbind::check<HostTraits<T> >(h_, pbd_part_nms(h_, nframes, overlap, max_boxes, &rec[0], (int)candidates.size(), 0, &rec[0],
+                                                        (int)candidates.size(), &n));
+        std::vector<Candidate> kept;
+        pbdbind::unpack_candidates<HostTraits<T> >(h_, rec, n, kept);
+        return kept;
+    }
+    // bestoverlap.m per frame (pbd_best_overlap): gtboxes holds {x1, y1, x2, y2} per frame (a NaN: no ground truth); best[f] is
+    // frame f's highest-scoring candidate whose part-centre hull covers more than `overlap` of the box, where found[f]
+    void bestOverlap(const std::vector<Candidate> &candidates, const std::vector<double> &gtboxes, float overlap,
+                     std::vector<Candidate> &best, std::vector<bool> &found)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "bestOverlap() before distributeModel()");
+        const size_t n = gtboxes.size() / 4;
+        if (n == 0 || gtboxes.size() != 4 * n) throw Error(PBD_ERR_INVALID, "bestOverlap: four ground-truth values per frame");
+        std::vector<int32_t> rec = frameRecords(candidates);
+        std::vector<int32_t> out(n * (size_t)pbd_candidate_stride(h_)), fnd(n);
+        pbdbind::check<HostTraits<T> >(h_, pbd_best_overlap(h_, (int)n, &gtboxes[0], overlap, &rec[0], (int)candidates.size(), 0, &out[0],
+                                                            &fnd[0]));
+        best.clear();
+        pbdbind::unpack_candidates<HostTraits<T> >(h_, out, (int)n, best);
+        found.assign(n, false);
+        for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
+    }
+    // eval_pck.m (pbd_eval_pck) on bestOverlap's output: gt_points = [frame][part][2], scale = [frame]; pck per part and, when
+    // asked for, dist = [part][frame]
+    std::vector<double> evalPCK(const std::vector<Candidate> &best, const std::vector<bool> &found, const std::vector<double> &gt_points,
+                                const std::vector<double> &scale, double thresh = 0.5, std::vector<double> *dist = NULL)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "evalPCK() before distributeModel()");
+        const size_t n = best.size(), np = (size_t)(pbd_candidate_stride(h_) - 8) / 4;
+        if (n == 0 || found.size() != n || scale.size() != n || gt_points.size() != n * np * 2)
+            throw Error(PBD_ERR_INVALID, "evalPCK: one candidate, flag and scale per frame, two values per part of a frame");
+        std::vector<int32_t> rec = frameRecords(best), fnd(n);
+        for (size_t i = 0; i < n; ++i) fnd[i] = found[i] ? 1 : 0;
+        std::vector<double> pck(np);
+        if (dist) dist->assign(np * n, 0.0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_eval_pck(h_, (int)n, &rec[0], &fnd[0], &gt_points[0], &scale[0], thresh, &pck[0],
+                                                        dist ? &(*dist)[0] : NULL));
+        return pck;
+    }
+    // eval_apk.m + VOCap.m (pbd_eval_apk) for every part: frame f's instances are gt_offset[f] .. gt_offset[f + 1] - 1 of
+    // gt_points = [instance][part][2] and gt_scale = [instance]; apk per part and, when asked for, prec / rec = [part][candidate]
+    std::vector<double> evalAPK(const std::vector<Candidate> &candidates, const std::vector<int32_t> &gt_offset,
+                                const std::vector<double> &gt_points, const std::vector<double> &gt_scale, double thresh = 0.5,
+                                std::vector<double> *prec = NULL, std::vector<double> *rec = NULL)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "evalAPK() before distributeModel()");
+        const size_t n = candidates.size(), np = (size_t)(pbd_candidate_stride(h_) - 8) / 4;
+        if (gt_offset.size() < 2 || gt_offset.back() < 0 || gt_scale.size() != (size_t)gt_offset.back() ||
+            gt_points.size() != gt_scale.size() * np * 2)
+            throw Error(PBD_ERR_INVALID, "evalAPK: gt_offset has nframes + 1 entries, the last one counts the instances");
+        std::vector<int32_t> records_ = frameRecords(candidates);
+        std::vector<double> apk(np), none(1);
+        if (prec) prec->assign(np * n + 1, 0.0);
+        if (rec) rec->assign(np * n + 1, 0.0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_eval_apk(h_, (int)gt_offset.size() - 1, &gt_offset[0], gt_points.empty() ? &none[0] : &gt_points[0],
+                                                        gt_scale.empty() ? &none[0] : &gt_scale[0], thresh, &records_[0], (int)n, 0, &apk[0],
+                                                        prec ? &(*prec)[0] : NULL, rec ? &(*rec)[0] : NULL));
+        if (prec) prec->resize(np * n);
+        if (rec) rec->resize(np * n);
+        return apk;
+    }
     // warped positives (matlab/learning/train.m poswarp, warppos.m, qp_poswrite) on the device (pbd_warp_positives): boxes holds
     // five values per box, {image, x1, y1, x2, y2} (0-based, inclusive); each box is padded by one cell, cropped with edge
     // replication, resized to (k + 2) * sbin pixels and its HOG written as the example [bias = 1 | filter block] of filter

@@ -29,7 +29,9 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_cl_grid_count", "k_cl_grid_scan", "k_cl_grid_scatter", "k_cl_hook", "k_cl_label", "k_cl_best", "k_cl_select", "k_cl_out",
            "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile", "k_part_poses",
            "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
-           "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit"]
+           "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
+           "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
+           "k_ev_apk_close", "k_ev_apk_ap"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -47,7 +49,8 @@ SYMBOLS = [
     "pbd_examples_device", "pbd_detect_latent", "pbd_qp_create", "pbd_qp_destroy", "pbd_qp_last_error", "pbd_qp_add",
     "pbd_qp_add_device", "pbd_qp_fix", "pbd_qp_prune", "pbd_qp_one", "pbd_qp_opt", "pbd_qp_weights", "pbd_qp_scores", "pbd_qp_state",
     "pbd_qp_entries", "pbd_set_model_vector", "pbd_set_model_vector_device", "pbd_set_thresh", "pbd_qp_apply",
-    "pbd_warp_positives", "pbd_warp_positives_device",
+    "pbd_warp_positives", "pbd_warp_positives_device", "pbd_part_nms", "pbd_part_nms_device", "pbd_best_overlap",
+    "pbd_best_overlap_device", "pbd_eval_pck", "pbd_eval_pck_device", "pbd_eval_apk", "pbd_eval_apk_device",
 ]
 
 
@@ -240,6 +243,16 @@ def load():
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_warp_positives_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pbd_part_nms.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                 C.POINTER(C.c_int)]
+    lib.pbd_part_nms_device.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.pbd_best_overlap.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pbd_best_overlap_device.argtypes = lib.pbd_best_overlap.argtypes
+    lib.pbd_eval_pck.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.pbd_eval_pck_device.argtypes = lib.pbd_eval_pck.argtypes
+    lib.pbd_eval_apk.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pbd_eval_apk_device.argtypes = lib.pbd_eval_apk.argtypes + [C.c_void_p]
     lib.pbd_detect_latent.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                       C.c_void_p, C.c_void_p]
     lib.pbd_qp_create.argtypes = [C.c_void_p, C.POINTER(CQpConfig), C.POINTER(C.c_void_p)]

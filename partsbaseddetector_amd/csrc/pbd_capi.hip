@@ -2285,7 +2285,9 @@ const char *pbd_kernel_name(int k)
                                              "k_cl_out", "k_dc_classify", "k_dc_select", "k_dc_compact", "k_mk_hull", "k_mk_tile",
                                              "k_part_poses", "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score",
                                              "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
-                                             "k_qp_gather", "k_warp", "k_warp_emit"};
+                                             "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
+                                             "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
+                                             "k_ev_apk_close", "k_ev_apk_ap"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

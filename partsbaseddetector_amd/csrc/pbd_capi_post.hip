@@ -1,5 +1,6 @@
 // pbd_capi_post.hip -- the C entry points that work on a finished candidate list (include/pbd.h): 3-D boxes, depth consistency,
-// suppression of a caller's list, camera boxes, candidate masks, part poses, object clusters, plane removal.
+// suppression of a caller's list, camera boxes, candidate masks, part poses, object clusters, plane removal, and testing a model
+// (part NMS, best overlap, PCK, APK).
 // The handle and the layer they are written on: pbd_handle.h.
 #include "pbd_handle.h"
 
@@ -581,6 +582,153 @@ std::vector<PlaneCloud> plane_table(int nclouds, const pbd_cloud *c)
     return tab;
 }
 
+
+// ---- testing a model (pbd_part_nms*, pbd_best_overlap*, pbd_eval_pck*, pbd_eval_apk*; pbd_kernels_eval.hip)
+// the one part count of the model's components (Matlab's box matrix has one width)
+int eval_nparts(pbd_handle *h, int *nparts)
+{
+    const int np = h->part_offset[1] - h->part_offset[0];
+    for (int c = 1; c < h->NC; ++c)
+        if (h->part_offset[c + 1] - h->part_offset[c] != np)
+            return fail(h, PBD_ERR_UNSUPPORTED, "component %d has %d parts, component 0 has %d: the evaluation reads one part count", c,
+                        h->part_offset[c + 1] - h->part_offset[c], np);
+    *nparts = np;
+    return PBD_OK;
+}
+
+int check_eval_list(pbd_handle *h, int nframes, int capacity, int nparts)
+{
+    if (nframes < 1 || nframes > 65535) return fail(h, PBD_ERR_INVALID, "nframes %d (1..65535)", nframes);
+    if (capacity < 0 || (long long)capacity * std::max(nparts, 1) >= (1LL << 30))
+        return fail(h, PBD_ERR_INVALID, "capacity %d: %d-part records (below 2^30 parts)", capacity, nparts);
+    return PBD_OK;
+}
+
+// the workspace and the four steps of the part NMS on the handle's stream: payload d_in (capacity records) -> d_out
+int enqueue_part_nms(pbd_handle *h, int nframes, float overlap, int max_boxes, const int32_t *d_in, int capacity, int frame_offset,
+                     int32_t *d_out, int out_cap)
+{
+    EvalNmsParams p{};
+    if (int rc = eval_nparts(h, &p.nparts)) return rc;
+    p.row_words = (max_boxes + 63) / 64;
+    const size_t cap = (size_t)std::max(capacity, 1), ranks = (size_t)nframes * max_boxes;
+    if (int rc = carve(h, h->ev_ws, [&](Carve &c) {
+            p.frame = c.take<int32_t>(cap * 4); p.key = c.take<uint32_t>(cap * 4); p.bad = c.take<int32_t>(256);
+            p.order = c.take<int32_t>(ranks * 4); p.hull = c.take<double>(ranks * 4 * 8);
+            p.bits = c.take<unsigned long long>(ranks * p.row_words * 8); p.slot = c.take<int32_t>(ranks * 4);
+            p.fm = c.take<int32_t>((size_t)nframes * 4); p.fkept = c.take<int32_t>((size_t)nframes * 4);
+        })) return rc;
+    p.in = d_in; p.in_cap = capacity; p.stride = stride(h); p.nframes = nframes; p.frame_offset = frame_offset;
+    p.max_boxes = max_boxes; p.overlap = overlap; p.out = d_out; p.out_cap = std::max(out_cap, 0);
+    HIPCHK(h, hipMemsetAsync(p.bad, 0, sizeof(int32_t), h->stream));
+    static const int ids[kEvNmsSteps] = {PBD_K_EV_NMS_SELECT, PBD_K_EV_NMS_PAIRS, PBD_K_EV_NMS_GREEDY, PBD_K_EV_NMS_EMIT};
+    for (int step = 0; step < kEvNmsSteps; ++step) {
+        ProfScope ps(h, ids[step], h->stream);
+        launch_eval_nms(p, step, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+int check_part_nms(pbd_handle *h, float overlap, int max_boxes)
+{
+    if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+    if (max_boxes < 1 || max_boxes > kEvMaxBoxes) return fail(h, PBD_ERR_INVALID, "max_boxes %d (1..%d)", max_boxes, kEvMaxBoxes);
+    return PBD_OK;
+}
+
+// the ground-truth boxes through the staging buffer, then the two kernels
+int enqueue_best_overlap(pbd_handle *h, int nframes, const double *gtbox, float overlap, const int32_t *d_in, int capacity,
+                         int frame_offset, int32_t *d_out, int32_t *d_found)
+{
+    EvalBestParams p{};
+    if (int rc = eval_nparts(h, &p.nparts)) return rc;
+    if (int rc = carve(h, h->ev_ws, [&](Carve &c) { p.best = c.take<unsigned long long>((size_t)nframes * 8); })) return rc;
+    if (int rc = h->ev_tab.stage(h, gtbox, (size_t)nframes * 4 * sizeof(double))) return rc;
+    p.in = d_in; p.in_cap = capacity; p.stride = stride(h); p.nframes = nframes; p.frame_offset = frame_offset; p.overlap = overlap;
+    p.gtbox = h->ev_tab.as<double>(); p.out = d_out; p.found = d_found;
+    HIPCHK(h, hipMemsetAsync(p.best, 0, (size_t)nframes * 8, h->stream));
+    {
+        ProfScope ps(h, PBD_K_EV_BEST, h->stream);
+        launch_eval_best(p, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+int enqueue_pck(pbd_handle *h, int nframes, const int32_t *d_rec, const int32_t *d_found, const double *gt_points, const double *scale,
+                double thresh, double *d_pck, double *d_dist)
+{
+    EvalPckParams p{};
+    if (int rc = eval_nparts(h, &p.nparts)) return rc;
+    const size_t ngt = (size_t)nframes * p.nparts * 2;
+    std::vector<double> tab(ngt + nframes);
+    memcpy(tab.data(), gt_points, ngt * sizeof(double));
+    memcpy(tab.data() + ngt, scale, (size_t)nframes * sizeof(double));
+    if (int rc = h->ev_tab.stage(h, tab.data(), tab.size() * sizeof(double))) return rc;
+    p.rec = d_rec; p.found = d_found; p.stride = stride(h); p.nframes = nframes;
+    p.gt = h->ev_tab.as<double>(); p.scale = p.gt + ngt; p.thresh = thresh; p.pck = d_pck; p.dist = d_dist;
+    {
+        ProfScope ps(h, PBD_K_EV_PCK, h->stream);
+        launch_eval_pck(p, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+int check_apk_gt(pbd_handle *h, int nframes, const int32_t *gt_offset, int nparts)
+{
+    if (gt_offset[0] != 0) return fail(h, PBD_ERR_INVALID, "gt_offset[0] %d (0)", gt_offset[0]);
+    for (int f = 0; f < nframes; ++f)
+        if (gt_offset[f + 1] < gt_offset[f]) return fail(h, PBD_ERR_INVALID, "gt_offset[%d] %d below gt_offset[%d] %d", f + 1, gt_offset[f + 1], f, gt_offset[f]);
+    const int G = gt_offset[nframes];
+    if (G < 1) return fail(h, PBD_ERR_INVALID, "no ground-truth instance: recall is 0 / 0");
+    if ((long long)G * nparts >= (1LL << 30)) return fail(h, PBD_ERR_INVALID, "%d instances of %d parts (below 2^30 points)", G, nparts);
+    return PBD_OK;
+}
+
+int enqueue_apk(pbd_handle *h, int nframes, const int32_t *gt_offset, const double *gt_points, const double *gt_scale, double thresh,
+                const int32_t *d_in, int capacity, int frame_offset, double *d_apk, double *d_prec, double *d_rec, int32_t *d_status)
+{
+    EvalApkParams p{};
+    if (int rc = eval_nparts(h, &p.nparts)) return rc;
+    p.G = gt_offset[nframes];
+    p.list_cap = std::max(std::min(capacity, p.G), 1);
+    const size_t cap = (size_t)std::max(capacity, 1), np = (size_t)p.nparts, ngt = (size_t)p.G * np * 2;
+    if (int rc = carve(h, h->ev_ws, [&](Carve &c) {
+            p.key = c.take<uint32_t>(cap * 4); p.order = c.take<int32_t>(cap * 4); p.close = c.take<int32_t>(cap * np * 4);
+            p.first = c.take<int32_t>((size_t)p.G * np * 4); p.tplist = c.take<int32_t>(np * p.list_cap * 4);
+            p.mp = c.take<double>(np * p.list_cap * 8);
+        })) return rc;
+    // one staged block: the points, the scales, the offsets
+    std::vector<double> tab(ngt + p.G + (nframes + 2) / 2);
+    memcpy(tab.data(), gt_points, ngt * sizeof(double));
+    memcpy(tab.data() + ngt, gt_scale, (size_t)p.G * sizeof(double));
+    memcpy(tab.data() + ngt + p.G, gt_offset, ((size_t)nframes + 1) * sizeof(int32_t));
+    if (int rc = h->ev_tab.stage(h, tab.data(), tab.size() * sizeof(double))) return rc;
+    p.gt = h->ev_tab.as<double>(); p.gscale = p.gt + ngt; p.gt_offset = reinterpret_cast<const int32_t *>(p.gscale + p.G);
+    p.in = d_in; p.in_cap = capacity; p.stride = stride(h); p.nframes = nframes; p.frame_offset = frame_offset; p.thresh = thresh;
+    p.apk = d_apk; p.prec = d_prec; p.rec = d_rec; p.status = d_status;
+    HIPCHK(h, hipMemsetAsync(p.first, 0x7f, (size_t)p.G * np * 4, h->stream));   // 0x7f7f7f7f: above every rank
+    static const int ids[kEvApkSteps] = {PBD_K_EV_APK_RANK, PBD_K_EV_APK_CLOSE, PBD_K_EV_APK_AP};
+    for (int step = 0; step < kEvApkSteps; ++step) {
+        ProfScope ps(h, ids[step], h->stream);
+        launch_eval_apk(p, step, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// the host records of a call as a payload in h->ev_in (word 0 = ncand)
+int upload_eval_list(pbd_handle *h, const int32_t *cand, int ncand)
+{
+    const size_t words = (size_t)ncand * stride(h);
+    HIPCHK(h, h->ev_in.ensure((words + 1) * sizeof(int32_t)));
+    HIPCHK(h, hipMemcpyAsync(h->ev_in.p, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (ncand) HIPCHK(h, hipMemcpyAsync(h->ev_in.as<int32_t>() + 1, cand, words * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    return PBD_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -996,6 +1144,145 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
         if (capacity == 0) return PBD_OK;
         return enqueue_poses(h, d_payload, capacity, d_centres, d_ncentres, d_dense, d_count, d_position, d_orientation, d_eigenvalues);
+    });
+}
+
+// nms.m per frame (matlab/detection/nms.m).  See include/pbd.h.
+int pbd_part_nms(pbd_handle *h, int nframes, float overlap, int max_boxes, const int32_t *cand, int ncand, int frame_offset,
+                 int32_t *out, int capacity, int *nout)
+{
+    return entry(h, nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_part_nms(h, overlap, max_boxes)) return rc;
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, ncand, np)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecAscending)) return rc;
+        if (ncand == 0) return PBD_OK;
+        return host_list_call(h, h->ev_in, h->ev_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_part_nms(h, nframes, overlap, max_boxes, din, ncand, frame_offset, dout, ncand);
+        });
+    });
+}
+
+int pbd_part_nms_device(pbd_handle *h, int nframes, float overlap, int max_boxes, const int32_t *d_payload, int capacity,
+                        int frame_offset, int32_t *d_out, int out_capacity)
+{
+    return entry(h, d_payload && d_out, kIdle, [&]() -> int {
+        if (out_capacity < 0) return fail(h, PBD_ERR_INVALID, "out_capacity %d", out_capacity);
+        if (int rc = check_part_nms(h, overlap, max_boxes)) return rc;
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, capacity, np)) return rc;
+        return enqueue_part_nms(h, nframes, overlap, max_boxes, d_payload, capacity, frame_offset, d_out, out_capacity);
+    });
+}
+
+// bestoverlap.m per frame (matlab/detection/bestoverlap.m).  See include/pbd.h.
+int pbd_best_overlap(pbd_handle *h, int nframes, const double *gtbox, float overlap, const int32_t *cand, int ncand, int frame_offset,
+                     int32_t *out, int32_t *found)
+{
+    return entry(h, gtbox && out && found && (ncand <= 0 || cand), kIdle, [&]() -> int {
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, ncand, np)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecPlain)) return rc;
+        const size_t rec_bytes = (size_t)nframes * stride(h) * sizeof(int32_t), fnd_bytes = (size_t)nframes * sizeof(int32_t);
+        HIPCHK(h, h->ev_out.ensure(rec_bytes + fnd_bytes));
+        int32_t *d_out = h->ev_out.as<int32_t>(), *d_found = d_out + (size_t)nframes * stride(h);
+        if (int rc = upload_eval_list(h, cand, ncand)) return rc;
+        if (int rc = enqueue_best_overlap(h, nframes, gtbox, overlap, h->ev_in.as<int32_t>(), ncand, frame_offset, d_out, d_found)) return rc;
+        HIPCHK(h, hipMemcpyAsync(out, d_out, rec_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(found, d_found, fnd_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_best_overlap_device(pbd_handle *h, int nframes, const double *gtbox, float overlap, const int32_t *d_payload, int capacity,
+                            int frame_offset, int32_t *d_out, int32_t *d_found)
+{
+    return entry(h, gtbox && d_payload && d_out && d_found, kIdle, [&]() -> int {
+        if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, capacity, np)) return rc;
+        return enqueue_best_overlap(h, nframes, gtbox, overlap, d_payload, capacity, frame_offset, d_out, d_found);
+    });
+}
+
+// eval_pck.m (matlab/evaluation/eval_pck.m).  See include/pbd.h.
+int pbd_eval_pck(pbd_handle *h, int nframes, const int32_t *rec, const int32_t *found, const double *gt_points, const double *scale,
+                 double thresh, double *pck, double *dist)
+{
+    return entry(h, rec && found && gt_points && scale && pck, kIdle, [&]() -> int {
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, nframes, np)) return rc;
+        const size_t rec_bytes = (size_t)nframes * stride(h) * sizeof(int32_t), fnd_bytes = (size_t)nframes * sizeof(int32_t),
+                     pck_bytes = (size_t)np * sizeof(double), dist_bytes = (size_t)np * nframes * sizeof(double);
+        HIPCHK(h, h->ev_in.ensure(rec_bytes + fnd_bytes));
+        HIPCHK(h, h->ev_out.ensure(pck_bytes + dist_bytes));
+        int32_t *d_rec = h->ev_in.as<int32_t>(), *d_found = d_rec + (size_t)nframes * stride(h);
+        double *d_pck = h->ev_out.as<double>(), *d_dist = d_pck + np;
+        HIPCHK(h, hipMemcpyAsync(d_rec, rec, rec_bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_found, found, fnd_bytes, hipMemcpyHostToDevice, h->stream));
+        if (int rc = enqueue_pck(h, nframes, d_rec, d_found, gt_points, scale, thresh, d_pck, dist ? d_dist : nullptr)) return rc;
+        HIPCHK(h, hipMemcpyAsync(pck, d_pck, pck_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (dist) HIPCHK(h, hipMemcpyAsync(dist, d_dist, dist_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_eval_pck_device(pbd_handle *h, int nframes, const int32_t *d_rec, const int32_t *d_found, const double *gt_points,
+                        const double *scale, double thresh, double *d_pck, double *d_dist)
+{
+    return entry(h, d_rec && d_found && gt_points && scale && d_pck, kIdle, [&]() -> int {
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, nframes, np)) return rc;
+        return enqueue_pck(h, nframes, d_rec, d_found, gt_points, scale, thresh, d_pck, d_dist);
+    });
+}
+
+// eval_apk.m + VOCap.m (matlab/evaluation).  See include/pbd.h.
+int pbd_eval_apk(pbd_handle *h, int nframes, const int32_t *gt_offset, const double *gt_points, const double *gt_scale, double thresh,
+                 const int32_t *cand, int ncand, int frame_offset, double *apk, double *prec, double *rec)
+{
+    return entry(h, gt_offset && gt_points && gt_scale && apk && (ncand <= 0 || cand), kIdle, [&]() -> int {
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, ncand, np)) return rc;
+        if (int rc = check_apk_gt(h, nframes, gt_offset, np)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecPlain)) return rc;
+        const size_t apk_bytes = (size_t)np * sizeof(double), pr_bytes = (size_t)np * ncand * sizeof(double);
+        HIPCHK(h, h->ev_out.ensure(256 + apk_bytes + 2 * pr_bytes));
+        double *d_apk = h->ev_out.as<double>() + 32, *d_prec = d_apk + np, *d_rec = d_prec + (size_t)np * ncand;
+        if (int rc = upload_eval_list(h, cand, ncand)) return rc;
+        if (int rc = enqueue_apk(h, nframes, gt_offset, gt_points, gt_scale, thresh, h->ev_in.as<int32_t>(), ncand, frame_offset, d_apk,
+                                 prec ? d_prec : nullptr, rec ? d_rec : nullptr, h->ev_out.as<int32_t>())) return rc;
+        HIPCHK(h, hipMemcpyAsync(apk, d_apk, apk_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (prec && ncand) HIPCHK(h, hipMemcpyAsync(prec, d_prec, pr_bytes, hipMemcpyDeviceToHost, h->stream));
+        if (rec && ncand) HIPCHK(h, hipMemcpyAsync(rec, d_rec, pr_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_eval_apk_device(pbd_handle *h, int nframes, const int32_t *gt_offset, const double *gt_points, const double *gt_scale,
+                        double thresh, const int32_t *d_payload, int capacity, int frame_offset, double *d_apk, double *d_prec,
+                        double *d_rec, int32_t *d_status)
+{
+    return entry(h, gt_offset && gt_points && gt_scale && d_payload && d_apk && d_status, kIdle, [&]() -> int {
+        int np;
+        if (int rc = eval_nparts(h, &np)) return rc;
+        if (int rc = check_eval_list(h, nframes, capacity, np)) return rc;
+        if (int rc = check_apk_gt(h, nframes, gt_offset, np)) return rc;
+        return enqueue_apk(h, nframes, gt_offset, gt_points, gt_scale, thresh, d_payload, capacity, frame_offset, d_apk, d_prec, d_rec,
+                           d_status);
     });
 }
 

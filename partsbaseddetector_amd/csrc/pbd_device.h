@@ -1,7 +1,7 @@
 // pbd_device.h (private) -- the device idioms the post-detection stage kernels share, one definition each: the lock-free
 // union-find, the wave / workgroup scan, rank and sum, the device-wide exclusive scan, the wave-aggregated atomic add, the
 // order-preserving keys, and the candidate record's words, hull and count.  The stage files (pbd_kernels_cloud / planes /
-// consistency / depth / post / publish / qp .hip) keep only what is their own.  All integer arithmetic here is exact, so a
+// consistency / depth / post / publish / qp / eval .hip) keep only what is their own.  All integer arithmetic here is exact, so a
 // caller's result does not depend on which of these it is built from.
 #pragma once
 

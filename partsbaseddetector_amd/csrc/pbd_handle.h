@@ -401,6 +401,10 @@ struct Handle : ErrCtx {
     DevBuf mk_ws, mk_rec, mk_img;
     // pbd_part_poses: the host form's inputs and outputs
     DevBuf ps_buf;
+    // pbd_part_nms* / pbd_best_overlap* / pbd_eval_pck* / pbd_eval_apk*: the ground truth of a call (staged as the frame
+    // tables), the workspace, the host forms' inputs and outputs
+    StagedTable ev_tab;
+    DevBuf ev_ws, ev_in, ev_out;
     // pbd_model_vector / pbd_examples*: the model vector in T (built by build_model), the filter sizes and offsets of the model the
     // handle was created with, the strides of an example, the walk's tables (uploaded on first use), the (record, part) workspace,
     // the host form's records and outputs

@@ -548,6 +548,60 @@ struct PoseParams {
 };
 void launch_part_poses(const PoseParams &p, hipStream_t s);
 
+// testing a model (pbd_part_nms*, pbd_best_overlap*, pbd_eval_pck*, pbd_eval_apk*; pbd_kernels_eval.hip)
+constexpr int kEvMaxBoxes = 1000;   // nms.m's cut, the largest max_boxes
+struct EvalNmsParams {
+    const int32_t *in;            // payload: word 0 = records (negative or > in_cap: a bad list), then the records
+    int in_cap, stride, nparts, nframes, frame_offset, max_boxes;
+    int row_words;                // ceil(max_boxes / 64): 64-bit words of a row of the suppression matrix
+    float overlap;
+    int32_t *frame;               // [in_cap] workspace: each record's frame index
+    uint32_t *key;                // [in_cap] ordered score keys
+    int32_t *bad;                 // [1] the list is bad (zeroed by the caller)
+    int32_t *order;               // [nframes][max_boxes] record index by pick rank
+    double *hull;                 // [nframes][max_boxes][4] x1, y1, x2, y2 of the rank's hull
+    unsigned long long *bits;     // [nframes][max_boxes][row_words]: bit j of row i = pick rank i removes rank j (j > i)
+    int32_t *slot;                // [nframes][max_boxes] position among the frame's kept records, or -1
+    int32_t *fm, *fkept;          // [nframes] records after the cut, records kept
+    int32_t *out; int out_cap;    // output payload: word 0 = kept count (-1: bad list), then min(kept, out_cap) records
+};
+enum { kEvNmsSelect = 0, kEvNmsPairs, kEvNmsGreedy, kEvNmsEmit, kEvNmsSteps };
+void launch_eval_nms(const EvalNmsParams &p, int step, hipStream_t s);
+struct EvalBestParams {
+    const int32_t *in;
+    int in_cap, stride, nparts, nframes, frame_offset;
+    float overlap;
+    const double *gtbox;          // [nframes][4] x1, y1, x2, y2 (a NaN: no ground truth)
+    unsigned long long *best;     // [nframes] workspace, zeroed by the caller
+    int32_t *out, *found;         // [nframes][stride], [nframes]
+};
+void launch_eval_best(const EvalBestParams &p, hipStream_t s);
+struct EvalPckParams {
+    const int32_t *rec, *found;   // [nframes][stride], [nframes]
+    int stride, nparts, nframes;
+    const double *gt, *scale;     // [nframes][nparts][2], [nframes]
+    double thresh;
+    double *pck, *dist;           // [nparts], [nparts][nframes] or NULL
+};
+void launch_eval_pck(const EvalPckParams &p, hipStream_t s);
+struct EvalApkParams {
+    const int32_t *in;
+    int in_cap, stride, nparts, nframes, frame_offset, G, list_cap;
+    const int32_t *gt_offset;     // [nframes + 1]
+    const double *gt, *gscale;    // [G][nparts][2], [G]
+    double thresh;
+    uint32_t *key;                // [in_cap] workspace
+    int32_t *order;               // [in_cap] record index by rank
+    int32_t *close;               // [in_cap][nparts] the instance within thresh of (rank, part), or -1
+    int32_t *first;               // [G][nparts] earliest rank that is close to the instance (set to a large value by the caller)
+    int32_t *tplist;              // [nparts][list_cap] ranks of the true positives
+    double *mp;                   // [nparts][list_cap] their running maximum of the precision from the end
+    double *apk, *prec, *rec;     // [nparts], [nparts][in_cap] or NULL
+    int32_t *status;              // record count, or -1 for a bad count
+};
+enum { kEvApkRank = 0, kEvApkClose, kEvApkAp, kEvApkSteps };
+void launch_eval_apk(const EvalApkParams &p, int step, hipStream_t s);
+
 // training examples of records (pbd_examples*; pbd_kernels_examples.hip)
 struct ExPart {                   // one (example, part), written by the walk, read by the gather
     long long cell;               // first cell of the part's level in `feat` (frame * cell_per_frame + cell_off)

@@ -502,6 +502,108 @@ class Handle:
         self.check(self.lib.pbd_suppress_device(self.h, len(ir), _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), float(overlap),
                                                 d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
 
+    # ---- testing a model (include/pbd.h; the numpy yardstick is evaluation.py) ----------------------
+    def eval_nparts(self) -> int:
+        """the one part count the evaluation calls read every record with"""
+        po = self.flat.part_offset
+        return int(po[1] - po[0])
+
+    def part_nms(self, nframes: int, overlap: float, records: np.ndarray, max_boxes: int = 1000, frame_offset: int = 0,
+                 capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_part_nms: matlab/detection/nms.m per frame of records grouped by ascending frame; the kept records, frame by
+        frame, in pick order"""
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(self.lib.pbd_part_nms(self.h, nframes, float(overlap), max_boxes, rec.ctypes.data if rec.size else None, len(rec),
+                                         frame_offset, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def part_nms_device(self, nframes: int, overlap: float, max_boxes: int, d_payload_ptr: int, capacity: int, frame_offset: int,
+                        d_out_ptr: int, out_capacity: int) -> None:
+        """pbd_part_nms_device: a device payload in, the kept records into the payload at d_out_ptr (word 0 = kept count, -1 for
+        a bad list); asynchronous"""
+        self.check(self.lib.pbd_part_nms_device(self.h, nframes, float(overlap), max_boxes, d_payload_ptr, capacity, frame_offset,
+                                                d_out_ptr, out_capacity))
+
+    def best_overlap(self, gtboxes, overlap: float, records: np.ndarray, frame_offset: int = 0):
+        """pbd_best_overlap: matlab/detection/bestoverlap.m per frame.  gtboxes (nframes, 4) float64 x1, y1, x2, y2 (a NaN row:
+        no ground truth) -> records (nframes, stride), found (nframes,) int32"""
+        gt = np.ascontiguousarray(gtboxes, np.float64).reshape(-1, 4)
+        rec = self._records(records)
+        out = np.zeros((len(gt), self.stride), np.int32)
+        found = np.zeros(len(gt), np.int32)
+        self.check(self.lib.pbd_best_overlap(self.h, len(gt), gt.ctypes.data, float(overlap), rec.ctypes.data if rec.size else None,
+                                             len(rec), frame_offset, out.ctypes.data, found.ctypes.data))
+        return out, found
+
+    def best_overlap_device(self, gtboxes, overlap: float, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
+                            d_found_ptr: int) -> None:
+        """pbd_best_overlap_device: a device payload in, int32[nframes][stride] at d_out_ptr and int32[nframes] at d_found_ptr;
+        asynchronous"""
+        gt = np.ascontiguousarray(gtboxes, np.float64).reshape(-1, 4)
+        self.check(self.lib.pbd_best_overlap_device(self.h, len(gt), gt.ctypes.data, float(overlap), d_payload_ptr, capacity,
+                                                    frame_offset, d_out_ptr, d_found_ptr))
+
+    def _pck_args(self, nframes: int, gt_points, scale):
+        gt = np.ascontiguousarray(gt_points, np.float64)
+        sc = np.ascontiguousarray(scale, np.float64)
+        if gt.size != nframes * self.eval_nparts() * 2 or sc.size != nframes:
+            raise PbdError(-1, f"gt_points is (nframes, {self.eval_nparts()}, 2) and scale (nframes,)")
+        return gt, sc
+
+    def eval_pck(self, records: np.ndarray, found, gt_points, scale, thresh: float = 0.5, want_dist: bool = True):
+        """pbd_eval_pck: matlab/evaluation/eval_pck.m on one record per frame (best_overlap's output) -> pck (nparts,), dist
+        (nparts, nframes) or None"""
+        rec = self._records(records)
+        fnd = np.ascontiguousarray(found, np.int32)
+        gt, sc = self._pck_args(len(rec), gt_points, scale)
+        npart = self.eval_nparts()
+        pck = np.zeros(npart)
+        dist = np.zeros((npart, len(rec))) if want_dist else None
+        self.check(self.lib.pbd_eval_pck(self.h, len(rec), rec.ctypes.data, fnd.ctypes.data, gt.ctypes.data, sc.ctypes.data,
+                                         float(thresh), pck.ctypes.data, dist.ctypes.data if want_dist else None))
+        return pck, dist
+
+    def eval_pck_device(self, nframes: int, d_rec_ptr: int, d_found_ptr: int, gt_points, scale, thresh: float, d_pck_ptr: int,
+                        d_dist_ptr: Optional[int]) -> None:
+        """pbd_eval_pck_device: best_overlap_device's outputs in, double[nparts] at d_pck_ptr and, unless None,
+        double[nparts][nframes] at d_dist_ptr; asynchronous"""
+        gt, sc = self._pck_args(nframes, gt_points, scale)
+        self.check(self.lib.pbd_eval_pck_device(self.h, nframes, d_rec_ptr, d_found_ptr, gt.ctypes.data, sc.ctypes.data, float(thresh),
+                                                d_pck_ptr, d_dist_ptr))
+
+    def _apk_args(self, gt_offset, gt_points, gt_scale):
+        off = np.ascontiguousarray(gt_offset, np.int32)
+        gt = np.ascontiguousarray(gt_points, np.float64)
+        sc = np.ascontiguousarray(gt_scale, np.float64)
+        if len(off) < 2 or gt.size != int(off[-1]) * self.eval_nparts() * 2 or sc.size != int(off[-1]):
+            raise PbdError(-1, f"gt_offset is (nframes + 1,), gt_points (G, {self.eval_nparts()}, 2) and gt_scale (G,), G = gt_offset[-1]")
+        return off, gt, sc
+
+    def eval_apk(self, records: np.ndarray, gt_offset, gt_points, gt_scale, thresh: float = 0.5, frame_offset: int = 0,
+                 want_curves: bool = True):
+        """pbd_eval_apk: matlab/evaluation/eval_apk.m + VOCap.m for every part -> apk (nparts,), prec, rec (nparts, n) or None"""
+        rec = self._records(records)
+        off, gt, sc = self._apk_args(gt_offset, gt_points, gt_scale)
+        npart = self.eval_nparts()
+        apk = np.zeros(npart)
+        prec = np.zeros((npart, len(rec))) if want_curves else None
+        rcl = np.zeros((npart, len(rec))) if want_curves else None
+        self.check(self.lib.pbd_eval_apk(self.h, len(off) - 1, off.ctypes.data, gt.ctypes.data, sc.ctypes.data, float(thresh),
+                                         rec.ctypes.data if rec.size else None, len(rec), frame_offset, apk.ctypes.data,
+                                         prec.ctypes.data if want_curves else None, rcl.ctypes.data if want_curves else None))
+        return apk, prec, rcl
+
+    def eval_apk_device(self, gt_offset, gt_points, gt_scale, thresh: float, d_payload_ptr: int, capacity: int, frame_offset: int,
+                        d_apk_ptr: int, d_prec_ptr: Optional[int], d_rec_ptr: Optional[int], d_status_ptr: int) -> None:
+        """pbd_eval_apk_device: a device payload in, double[nparts] at d_apk_ptr, unless None double[nparts][capacity] at
+        d_prec_ptr / d_rec_ptr, the record count (or -1) at d_status_ptr; asynchronous"""
+        off, gt, sc = self._apk_args(gt_offset, gt_points, gt_scale)
+        self.check(self.lib.pbd_eval_apk_device(self.h, len(off) - 1, off.ctypes.data, gt.ctypes.data, sc.ctypes.data, float(thresh),
+                                                d_payload_ptr, capacity, frame_offset, d_apk_ptr, d_prec_ptr, d_rec_ptr, d_status_ptr))
+
     def boxes3d_camera(self, depths: Sequence[np.ndarray], im_shapes, cameras, records: np.ndarray, parts_mode: int = 0,
                        frame_offset: int = 0):
         """pbd_boxes3d_camera: camera boxes (n, 6) float64, part centres (n, max_parts, 3) float32 (0 past ncentres), ncentres (n,)
@@ -908,6 +1010,104 @@ class PartsBasedDetector:
             return []
         kept = self.hd.suppress(list(im_shapes), overlap, self.hd.pack_candidates(cands))
         return self.hd.unpack_candidates(kept.ravel(), len(kept))
+
+    # ---- testing a model: matlab/detection/testmodel.m, testmodel_gtbox.m and matlab/evaluation ----------------------
+    def partNMS(self, candidates: Sequence[Candidate], overlap: float = 0.3, max_boxes: int = 1000) -> List[Candidate]:
+        """nms.m per frame, on the device (pbd_part_nms): candidates grouped by ascending frame (0, 1, ...); the kept ones, frame
+        by frame, in pick order.  Not Candidate.nonMaximaSuppression: see include/pbd.h"""
+        self._need()
+        cands = list(candidates)
+        if not cands:
+            return []
+        nframes = max(c.frame for c in cands) + 1
+        kept = self.hd.part_nms(nframes, overlap, self.hd.pack_candidates(cands), max_boxes)
+        return self.hd.unpack_candidates(kept.ravel(), len(kept))
+
+    def bestOverlap(self, candidates: Sequence[Candidate], gtboxes, overlap: float = 0.3) -> List[Optional[Candidate]]:
+        """bestoverlap.m per frame, on the device (pbd_best_overlap): per row of gtboxes (x1, y1, x2, y2; NaN: none) the highest
+        scoring candidate of that frame whose part-centre hull covers more than `overlap` of the box, or None"""
+        self._need()
+        rec, found = self.hd.best_overlap(gtboxes, overlap, self.hd.pack_candidates(list(candidates)))
+        return self._found(rec, found)
+
+    def _found(self, rec: np.ndarray, found) -> List[Optional[Candidate]]:
+        rec = rec.reshape(-1, self.hd.stride)
+        return [self.hd.unpack_candidates(rec[f], 1)[0] if found[f] else None for f in range(len(rec))]
+
+    def evalPCK(self, poses: Sequence[Optional[Candidate]], gt_points, scale, thresh: float = 0.5):
+        """eval_pck.m on the device (pbd_eval_pck): poses[f] is frame f's candidate or None (bestOverlap's output) -> pck
+        (nparts,), dist (nparts, nframes)"""
+        self._need()
+        found = np.array([c is not None for c in poses], np.int32)
+        blank = Candidate(parts=np.zeros((self.hd.eval_nparts(), 4), np.int32), confidence=np.zeros(1, np.float32), component=0)
+        rec = self.hd.pack_candidates([c if c is not None else blank for c in poses])
+        return self.hd.eval_pck(rec, found, gt_points, scale, thresh)
+
+    def evalAPK(self, candidates: Sequence[Candidate], gt_offset, gt_points, gt_scale, thresh: float = 0.5):
+        """eval_apk.m + VOCap.m on the device (pbd_eval_apk) -> apk (nparts,), prec, rec (nparts, n)"""
+        self._need()
+        return self.hd.eval_apk(self.hd.pack_candidates(list(candidates)), gt_offset, gt_points, gt_scale, thresh)
+
+    def _unsuppressed_payload(self, frames: Sequence[np.ndarray]):
+        """the frames' unsuppressed list (the handle's own suppression off) in a device payload of the detector's; the list
+        never reaches the host"""
+        import torch
+        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
+        dt = fr[0].dtype
+        if dt not in _lib.DEPTH_CODE or any(f.dtype != dt or f.shape[2] != fr[0].shape[2] for f in fr):
+            raise PbdError(-1, "one call takes one image dtype (uint8, uint16, float32, float64) and one channel count")
+        dev = torch.device("cuda", self._kw["device"])
+        d_fr = [torch.from_numpy(f).to(dev) for f in fr]
+        torch.cuda.synchronize(dev)
+        words = 1 + self.hd.max_candidates * self.hd.stride
+        pays = getattr(self, "_ev_pays", None)
+        if pays is None or pays[0].numel() != words or pays[0].device != dev:
+            pays = self._ev_pays = [torch.empty(words, dtype=torch.int32, device=dev) for _ in range(2)]
+        overlap = self.hd.nms_overlap
+        if overlap is not None:
+            self.hd.set_nms(None)
+        try:
+            descs = [(t.data_ptr(), f.shape[0], f.shape[1], f.strides[0]) for t, f in zip(d_fr, fr)]
+            self.hd.check(self.hd.lib.pbd_detect_frames_device_out(self.hd.h, len(fr), _lib.frame_array(descs), fr[0].shape[2],
+                                                                   _lib.DEPTH_CODE[dt], 0, pays[0].data_ptr(), self.hd.max_candidates))
+        finally:
+            if overlap is not None:
+                self.hd.set_nms(overlap)
+        return pays, d_fr
+
+    def testModel(self, frames: Sequence[np.ndarray], overlap: float = 0.3, max_boxes: int = 1000) -> List[Candidate]:
+        """testmodel.m: detect_fast at the model's threshold, then nms(box, overlap), per frame (nframes <= max_batch).  The
+        unsuppressed list stays on the device (pbd_detect_frames_device_out -> pbd_part_nms_device); only the kept records
+        reach the host"""
+        self._need()
+        pays, keep = self._unsuppressed_payload(frames)
+        cap = self.hd.max_candidates
+        self.hd.part_nms_device(len(frames), overlap, max_boxes, pays[0].data_ptr(), cap, 0, pays[1].data_ptr(), cap)
+        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
+        kept = int(pays[1][0].item())
+        if kept < 0:
+            raise PbdError(-4, f"more than max_candidates ({cap}) candidates were found before the suppression")
+        buf = pays[1][1:1 + kept * self.hd.stride].cpu().numpy()
+        return self.hd.unpack_candidates(buf, kept)
+
+    def testModelGtbox(self, frames: Sequence[np.ndarray], gtboxes, overlap: float = 0.3) -> List[Optional[Candidate]]:
+        """testmodel_gtbox.m: detect_fast at the model's threshold, then bestoverlap(box, gtbox, overlap), per frame; gtboxes
+        (nframes, 4) x1, y1, x2, y2 (the caller's [min(x) min(y) max(x) max(y)] of the annotated points).  The unsuppressed list
+        stays on the device; one record per frame reaches the host"""
+        import torch
+        self._need()
+        pays, keep = self._unsuppressed_payload(frames)
+        n = len(frames)
+        out = torch.zeros(n * (self.hd.stride + 1), dtype=torch.int32, device=pays[0].device)
+        torch.cuda.synchronize(out.device)
+        self.hd.best_overlap_device(gtboxes, overlap, pays[0].data_ptr(), self.hd.max_candidates, 0, out.data_ptr(),
+                                    out.data_ptr() + 4 * n * self.hd.stride)
+        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
+        if int(pays[0][0].item()) > self.hd.max_candidates:
+            raise PbdError(-4, f"more than max_candidates ({self.hd.max_candidates}) candidates were found")
+        host = out.cpu().numpy()
+        rec, found = host[:n * self.hd.stride], host[n * self.hd.stride:]
+        return self._found(rec, found)
 
     def _detect_depth(self, im: np.ndarray, depth: np.ndarray, capacity: Optional[int]) -> List[Candidate]:
         """detect(im, depth) with setDepthConsistency on: the unsuppressed list, the filter, then the handle's suppression (if
