@@ -3,10 +3,11 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
+//   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
 //           in ONE detectBatch call, and each image's candidates are printed, in order, as a single run prints them
@@ -39,6 +40,8 @@
 using namespace pbdhost;
 
 // what a run prints for one image's candidates (the reference's demo: count, sort, optional NMS, the best ones)
+static int g_walk = PBD_WALK_REFERENCE;   // --walk
+
 static void report(std::vector<Candidate> &candidates, const Image &im, bool staged, float nms, float dnms, int top)
 {
     std::printf("Number of candidates: %zu\n", candidates.size());
@@ -63,6 +66,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
 {
     PartsBasedDetector<T> pbd(0, conv_mode, (int)ims.size());
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
+    pbd.setWalk(g_walk);
     pbd.distributeModel(model);
     std::vector<std::vector<Candidate> > candidates;
     pbd.detectBatch(ims, candidates);
@@ -148,6 +152,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
 {
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
+    pbd.setWalk(g_walk);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
         // the image stream_n times through a FrameStream of stream_k handles: every result must be the first one's
@@ -274,7 +279,7 @@ static int dump_model(const Model &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -295,6 +300,12 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked_path = argv[++i];
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--device-nms") && i + 1 < argc) dnms = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--walk") && i + 1 < argc) {
+            ++i;
+            if (!std::strcmp(argv[i], "argmax")) g_walk = PBD_WALK_ARGMAX;
+            else if (!std::strcmp(argv[i], "reference")) g_walk = PBD_WALK_REFERENCE;
+            else { std::fprintf(stderr, "--walk takes reference or argmax\n"); return -1; }
+        }
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }

@@ -169,6 +169,21 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world);
  * submit); PBD_ERR_UNSUPPORTED together with level sharding (world > 1), in either order of the two calls: suppression of one
  * rank's levels is not suppression of the union. */
 int pbd_set_nms(pbd_handle *h, int enable, float overlap);
+/* The walk from a root to its parts (new surface, opt-in).  A child's mixture is m = Ik[slot + pm][py][px] in both modes; with k
+ * the plane of that mixture:
+ *   PBD_WALK_REFERENCE (the default): x = IxRaw[k][py][px], y = IyRaw[k][py][x] -- the reference's composed pointers
+ *     Iy[y][x] = IyRaw[y][Ix[y][x]] (include/DistanceTransform.hpp:233-244).  The placement is usually NOT the one the score was
+ *     taken at, so w . x of its example is below the score.
+ *   PBD_WALK_ARGMAX: y = IyRaw[k][py][px], x = IxRaw[k][y][px] -- the arg-max of the two passes in the order they ran (the
+ *     column pass reads the row pass's output).  w . x of the example equals the score to rounding, the identity detect.m:139-145
+ *     asserts and a latent SVM needs of its negative constraints.
+ * The mode governs every walk the handle enqueues afterwards: the part boxes of all pbd_detect* records (and so what pbd_set_nms
+ * suppresses), pbd_argmin_device_out and pbd_dp_argmin (the resident result is re-walked in the mode current at the call; it is
+ * not dropped: the planes are the same), pbd_examples*, and pbd_detect_latent, whose latent twin follows its handle.  Roots,
+ * scores, record order and pbd_dp_min's read-back (the reference's composed Ix / Iy) are the same in both modes.
+ * Another mode: PBD_ERR_INVALID; while a batch is in flight: PBD_ERR_STATE. */
+enum { PBD_WALK_REFERENCE = 0, PBD_WALK_ARGMAX = 1 };
+int pbd_set_walk(pbd_handle *h, int mode);
 
 /* 3-D boxes from a depth image (new surface; opt-in, nothing else calls it): the callers' next step after the suppression above,
  * Candidate::boundingBox3D(im, depth) of every kept candidate (the first step of PointCloudClusterer::computeBoundingBoxes:
@@ -588,7 +603,8 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
  *   values  T[values]: the blocks' values concatenated in block order; values past nvalues are not written
  * w . values equals the record's score up to rounding (DESIGN.md section 6h states the bound) whenever the composed pointers
  * are the transform's true arg-max; where the reference's composition moved a part (a known quirk, reproduced on purpose)
- * the example is that of the placement the record reports and w . values is at most the score.
+ * the example is that of the placement the record reports and w . values is at most the score.  In PBD_WALK_ARGMAX
+ * (pbd_set_walk) the walk is the arg-max and the identity holds for every record.
  * pbd_examples: host records (any subset of the last completed detect call's, in any order, with or without pbd_set_nms,
  * pbd_detect_frames' included); a record's frame is its `frame` field - frame_offset.  PBD_ERR_INVALID, naming the record,
  * when its frame, level, component or root position is outside the resident result (a level-sharded handle holds only its
@@ -657,8 +673,8 @@ int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, i
 /* Warped positives (new surface; opt-in): poswarp of the reference's Matlab training code (matlab/learning/train.m:131-162 with
  * matlab/learning/warppos.m, subarray.m and qp_poswrite), the examples every training run starts from (trainmodel.m:19-40 trains
  * each part mixture as a one-part model on them).  DESIGN.md section 6k.  Each annotated box is padded by one cell, cropped with
- * edge replication, resized to (k + 2) * sbin pixels, and its HOG written as an example in pbd_examples' format.  No train()
- * loop, no flipping: those stay with the caller.
+ * edge replication, resized to (k + 2) * sbin pixels, and its HOG written as an example in pbd_examples' format.  No
+ * flipping: that stays with the caller (the train() loop over these calls is partsbaseddetector_amd/train.py).
  * Frames as pbd_detect_frames takes them: host pointers (pbd_warp_positives) or device pointers (the _device form), mixed sizes,
  * one `channels` (1 or 3) and one depth_code (all four) per call; a _device frame may be a region of a larger device image, read
  * in place through its pitch, its pointer and stride_bytes multiples of the element size.  A frame only has to be 1 x 1 or
@@ -770,6 +786,18 @@ int pbd_warp_positives_device(pbd_handle *h, int nframes, const struct pbd_frame
  * pbd_qp_state: the counters and bounds (struct pbd_qp_info); a (double[n]), sv (uint8[n]) and w (double[len]) when not NULL.
  * pbd_qp_entries: entries first..first+count-1: hdr int32[count][hdr_words], values float[count][values] (past nvalues 0),
  *   b, d double[count], ids int32[count][5]; any pointer may be NULL.
+ * pbd_qp_clear: train.m:75's qp.n = 0 for the next iteration: n = 0, nfix = 0, l = loss = 0, lb = ub = NaN, passes, converged
+ *   and lb_dropped 0, a = 0 and sv = 0 on every slot, the host tables emptied -- the state after pbd_qp_create.  w is left as it
+ *   is; the next refresh rebuilds it.  New slots start at a = 0, as always (the stale qp.a of train.m is not reproduced).
+ * pbd_qp_add_loss_device: detect.m:135's qp.ub = qp.ub + Cneg * max(1 + score, 0) for the records of a payload, the quantity
+ *   that decides whether mining re-optimises (detect.m:148-152).  Over the m = min(max(word 0, 0), capacity) records PRESENT in
+ *   d_payload -- whether pbd_qp_add_device wrote them into the cache or dropped them for lack of room, as detect.m:133-136 counts
+ *   them -- ub = ub + Cl * R(h) with h_j = max(0, 1 - y * score_j) in double, score_j = record j's float score widened, y = +1
+ *   and Cl = Cpos when label > 0, else y = -1 and Cl = Cneg, and R the reduction above with record j on lane j mod
+ *   PBD_QP_LANES.  *added (may be NULL) receives the addend Cl * R(h).  PBD_ERR_STATE while ub is NaN (no pbd_qp_opt /
+ *   pbd_qp_one since create or clear).  The records are those of the handle the QP was created from (its record stride).  The
+ *   call runs on the QP's stream; a QP on the stream of the handle it was created from is thereby ordered behind the payload's
+ *   producer, a QP on another stream waits for the device first (the call does not name the producing handle).
  * Every call is synchronous.  Errors: PBD_ERR_INVALID for bad arguments, PBD_ERR_STATE for an empty cache or pass set; the
  * message is pbd_qp_last_error(q). */
 #define PBD_QP_LANES 1024
@@ -794,6 +822,8 @@ int pbd_qp_add(pbd_qp *q, const pbd_handle *h, int n, const int32_t *hdr, const 
 int pbd_qp_add_device(pbd_qp *q, pbd_handle *h, const int32_t *d_payload, int capacity, const int32_t *d_hdr, const void *d_values,
                       int label, int id_base, int32_t *d_taken);
 int pbd_qp_fix(pbd_qp *q);
+int pbd_qp_clear(pbd_qp *q);
+int pbd_qp_add_loss_device(pbd_qp *q, const int32_t *d_payload, int capacity, int label, double *added);
 int pbd_qp_prune(pbd_qp *q, int *n);
 int pbd_qp_one(pbd_qp *q, const int32_t *order, int norder, uint64_t seed, struct pbd_qp_info *state);
 int pbd_qp_opt(pbd_qp *q, double tol, int iter, uint64_t seed, struct pbd_qp_info *state);
@@ -936,6 +966,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
           pbd_eval_apk* (k_ev_apk_rank times the keys and the order) */
        PBD_K_EV_NMS_SELECT, PBD_K_EV_NMS_PAIRS, PBD_K_EV_NMS_GREEDY, PBD_K_EV_NMS_EMIT, PBD_K_EV_BEST, PBD_K_EV_PCK,
        PBD_K_EV_APK_RANK, PBD_K_EV_APK_CLOSE, PBD_K_EV_APK_AP,
+       /* pbd_qp_add_loss_device (named for traces, as the other QP kernels) */
+       PBD_K_QP_HINGE,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

@@ -543,6 +543,16 @@ public:
         return pbdbind::qp_add<HostTraits<T> >(q_, h, hdr, values, ids);
     }
     void fix() { pbdbind::qp_check<HostTraits<float> >(q_, pbd_qp_fix(q_)); }
+    // train.m:75's qp.n = 0: an empty cache again, the bounds NaN as after create (pbd_qp_clear)
+    void clear() { pbdbind::qp_check<HostTraits<float> >(q_, pbd_qp_clear(q_)); }
+    // detect.m:135: ub += Cl * R(max(0, 1 - y * score)) over the records present in a device payload of the detector the QP
+    // was created from (pbd_qp_add_loss_device); the addend
+    double addLoss(const int32_t *d_payload, int capacity, int label = -1)
+    {
+        double added = 0;
+        pbdbind::qp_check<HostTraits<float> >(q_, pbd_qp_add_loss_device(q_, d_payload, capacity, label, &added));
+        return added;
+    }
     int prune()
     {
         int n = 0;
@@ -574,6 +584,7 @@ class PartsBasedDetector {
     int max_batch_;
     bool nms_;
     float overlap_;
+    int walk_;
     bool depth_on_;
     float zfactor_;
     PartsBasedDetector(const PartsBasedDetector &);
@@ -583,7 +594,7 @@ public:
     // reference has only its exact convolution
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
-        : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f),
+        : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
           depth_on_(false), zfactor_(0.03f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
@@ -594,6 +605,7 @@ public:
         h_ = NULL;
         h_ = pbdbind::create<HostTraits<T> >(model, device_, conv_mode_, max_batch_, 1 << 18);
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
+        if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
         name_ = model.name();
     }
     // new surface: detect() returns Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of what it
@@ -604,6 +616,15 @@ public:
         if (h_) pbdbind::set_nms<HostTraits<T> >(h_, overlap >= 0, overlap);
         nms_ = overlap >= 0;
         overlap_ = overlap;
+    }
+    // new surface: how a root is walked to its parts from now on (pbd_set_walk): PBD_WALK_REFERENCE, the reference's composed
+    // back-pointers (the default), or PBD_WALK_ARGMAX, the placement the score was taken at -- part boxes, examples() and
+    // detectLatent() follow it.  Kept across distributeModel().
+    void setWalk(int mode)
+    {
+        if (mode != PBD_WALK_REFERENCE && mode != PBD_WALK_ARGMAX) throw Error(PBD_ERR_INVALID, "walk mode");
+        if (h_) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, mode));
+        walk_ = mode;
     }
     // new surface: detect(im, depth, candidates) runs filterCandidatesByDepth(depth, ., zfactor) on the unsuppressed list, before
     // the suppression -- the reference's commented-out call (src/PartsBasedDetector.cpp:91-93).  Off by default (depth ignored, as

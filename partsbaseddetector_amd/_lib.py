@@ -18,6 +18,7 @@ STATUS = {0: "PBD_OK", -1: "PBD_ERR_INVALID", -2: "PBD_ERR_UNSUPPORTED", -3: "PB
           -5: "PBD_ERR_STATE", -6: "PBD_ERR_NOMEM"}
 REAL_F32, REAL_F64 = 0, 1
 CONV_EXACT, CONV_FMA, CONV_MFMA, CONV_MFMA_F16 = 0, 1, 2, 3
+WALK_REFERENCE, WALK_ARGMAX = 0, 1   # pbd_set_walk
 CONV_MFMA_F64 = 4          # fp64 matrix cores, REAL_F64 handles only (include/pbd.h)
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
 # options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
@@ -31,7 +32,7 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
            "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
            "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-           "k_ev_apk_close", "k_ev_apk_ap"]
+           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -51,6 +52,7 @@ SYMBOLS = [
     "pbd_qp_entries", "pbd_set_model_vector", "pbd_set_model_vector_device", "pbd_set_thresh", "pbd_qp_apply",
     "pbd_warp_positives", "pbd_warp_positives_device", "pbd_part_nms", "pbd_part_nms_device", "pbd_best_overlap",
     "pbd_best_overlap_device", "pbd_eval_pck", "pbd_eval_pck_device", "pbd_eval_apk", "pbd_eval_apk_device",
+    "pbd_set_walk", "pbd_qp_clear", "pbd_qp_add_loss_device",
 ]
 
 
@@ -173,6 +175,7 @@ def load():
     lib.pbd_ptr_slot.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_level_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    lib.pbd_set_walk.argtypes = [C.c_void_p, C.c_int]
     lib.pbd_debug_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_debug_postprocess.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
                                           C.POINTER(C.c_int)]
@@ -264,6 +267,8 @@ def load():
     lib.pbd_qp_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_void_p]
     lib.pbd_qp_fix.argtypes = [C.c_void_p]
+    lib.pbd_qp_clear.argtypes = [C.c_void_p]
+    lib.pbd_qp_add_loss_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.pbd_qp_prune.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.pbd_qp_one.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(CQpInfo)]
     lib.pbd_qp_opt.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint64, C.POINTER(CQpInfo)]

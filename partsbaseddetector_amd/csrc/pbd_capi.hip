@@ -1200,6 +1200,7 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     ap.cell_per_frame = P.cell_per_frame;
     ap.rootv = h->rootv.p; ap.rooti = h->rooti.as<int>();
     ap.IxRaw = h->IxRaw.p; ap.IyRaw = h->IyRaw.p; ap.NJ = h->totmix; ap.Ik = h->Ik.as<uint8_t>(); ap.ptr8 = P.ptr8 ? 1 : 0;
+    ap.walk_mode = h->walk_mode;
     ap.thresh = h->thresh; ap.scales = d_scales;
     ap.walk = h->d_walk.p; ap.walk_off = h->d_walk_off.p;
     ap.max_parts = h->max_parts; ap.stride = stride(h); ap.capacity = std::max(capacity, 0);
@@ -1864,6 +1865,16 @@ int pbd_set_nms(pbd_handle *h, int enable, float overlap)
     });
 }
 
+int pbd_set_walk(pbd_handle *h, int mode)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (mode != PBD_WALK_REFERENCE && mode != PBD_WALK_ARGMAX) return fail(h, PBD_ERR_INVALID, "walk mode %d", mode);
+        h->walk_mode = mode;              // the resident result stays: the planes do not depend on the walk
+        if (h->lat) h->lat->walk_mode = mode;
+        return PBD_OK;
+    });
+}
+
 int pbd_pyramid_plan(pbd_handle *h, int rows, int cols, int *nlevels, int *img_rows, int *img_cols, int *feat_rows,
                      int *feat_cols, float *scales)
 {
@@ -2287,7 +2298,7 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-                                             "k_ev_apk_close", "k_ev_apk_ap"};
+                                             "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

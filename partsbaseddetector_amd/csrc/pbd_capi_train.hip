@@ -44,6 +44,7 @@ int enqueue_examples(pbd_handle *h, const int32_t *d_in, int capacity, int frame
     ep.frame_lv0 = P.kind == 2 ? P.d_frame_lv0.p : nullptr;
     ep.cell_per_frame = P.cell_per_frame;
     ep.NC = h->NC; ep.NS = h->NS; ep.NJ = h->totmix; ep.ptr8 = P.ptr8 ? 1 : 0; ep.flen = 32; ep.max_parts = h->max_parts;
+    ep.walk_mode = h->walk_mode;
     ep.rooti = o->rooti.as<int>(); ep.IxRaw = o->IxRaw.p; ep.IyRaw = o->IyRaw.p; ep.Ik = o->Ik.as<uint8_t>();
     ep.walk = h->d_walk.p; ep.walk_off = h->d_walk_off.p;
     ep.gm = h->ex_gm.p; ep.anchors = h->ex_anchors.p; ep.foff = h->ex_foff.p; ep.nbias = h->nbias; ep.ndefs = h->ndefs;
@@ -489,6 +490,7 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
             pbd_handle *t = nullptr;
             if (int rc = pbd_create(&m, &cfg, &t)) return fail(h, rc, "latent twin: %s", pbd_last_error(nullptr));
             h->lat.reset(t);
+            t->walk_mode = h->walk_mode;
             std::vector<int4> gm(T);
             for (int c = 0; c < h->NC; ++c)
                 for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)
@@ -549,6 +551,8 @@ int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, i
 struct pbd_qp : pbd::ErrCtx {
     Stream stream;
     int cap = 0, L = 0, V = 0, HW = 0, MB = 0, in_hw = 0;
+    int rec_stride = 0;            // record words of the handle the QP was created from
+    hipStream_t src_stream = nullptr;   // that handle's stream, compared only (the handle may be gone)
     uint64_t fp = 0;
     double Cpos = 0, Cneg = 0;
     DevBuf x, bm, hd, ids, b, d, a, sv, w, wraw, misc, stage, work, lc, scratch;
@@ -875,6 +879,7 @@ int pbd_qp_create(const pbd_handle *h, const struct pbd_qp_config *cfg, pbd_qp *
         const QpLayout lay = qp_layout(h);
         q->L = lay.L; q->V = lay.V; q->in_hw = lay.in_hw; q->fp = lay.fp;
         q->MB = (lay.in_hw - 4) / 2;
+        q->rec_stride = ::stride(h); q->src_stream = h->stream.s;
         if (q->MB > 256 || q->MB < 1) return fail(nullptr, PBD_ERR_UNSUPPORTED, "examples of %d blocks (at most 256)", q->MB);
         if (q->V % 4) return fail(nullptr, PBD_ERR_INVALID, "example stride %d", q->V);
         q->HW = 2 + 3 * q->MB;
@@ -1009,6 +1014,42 @@ int pbd_qp_fix(pbd_qp *q)
         q->nfix = q->n;
         if (int rc = qp_set_sv(q, q->n)) return rc;
         HIPCHK(q, hipStreamSynchronize(q->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_clear(pbd_qp *q)
+{
+    return entry(q, true, [&]() -> int {
+        HIPCHK(q, hipMemsetAsync(q->a.p, 0, (size_t)q->cap * sizeof(double), q->stream));
+        HIPCHK(q, hipMemsetAsync(q->sv.p, 0, (size_t)q->cap, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        q->h_ids.clear(); q->h_hd.clear(); q->h_b.clear();
+        q->n = 0; q->nfix = 0;
+        q->lb = NAN; q->ub = NAN; q->loss = 0; q->l = 0; q->ww = 0;
+        q->have_lb = false;
+        q->lb_dropped = 0; q->passes = 0; q->converged = 0;
+        return PBD_OK;
+    });
+}
+
+int pbd_qp_add_loss_device(pbd_qp *q, const int32_t *d_payload, int capacity, int label, double *added)
+{
+    return entry(q, d_payload != nullptr, [&]() -> int {
+        if (capacity < 0) return fail(q, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (std::isnan(q->ub)) return fail(q, PBD_ERR_STATE, "no upper bound yet (pbd_qp_opt or pbd_qp_one first)");
+        if (q->stream.s != q->src_stream) HIPCHK(q, hipDeviceSynchronize());   // the producer's stream is not known here
+        QpHingeParams p{};
+        p.payload = d_payload; p.capacity = capacity; p.rec_stride = q->rec_stride;
+        p.y = label > 0 ? 1.0 : -1.0; p.Cl = label > 0 ? q->Cpos : q->Cneg;
+        p.out = q->misc.as<double>() + 3;
+        launch_qp_hinge(p, q->stream);
+        HIPCHK(q, hipGetLastError());
+        double add = 0;
+        HIPCHK(q, hipMemcpyAsync(&add, p.out, sizeof(double), hipMemcpyDeviceToHost, q->stream));
+        HIPCHK(q, hipStreamSynchronize(q->stream));
+        q->ub = q->ub + add;
+        if (added) *added = add;
         return PBD_OK;
     });
 }

@@ -87,14 +87,21 @@ template <typename R, class Score> __device__ __forceinline__ R reduce_max(int n
 // ---- back-tracking (src/DynamicProgram.cpp:218-244) ---------------------------------------------------------------------------
 // a child's position and mixture from its parent's: m = Ik[slot + pm][py][px], x = IxRaw[k][py][px], y = IyRaw[k][py][x] with k
 // the plane of the winning mixture m -- the reference's composition Iy[y][x] = IyRaw[y][Ix[y][x]]
-// (include/DistanceTransform.hpp:233-244), made here for the walked cells only
+// (include/DistanceTransform.hpp:233-244), made here for the walked cells only.
+// argmax (PBD_WALK_ARGMAX, pbd_set_walk): the placement the score was taken at.  The column pass ran over the row pass's output,
+// so its pointer comes first: y = IyRaw[k][py][px], then x = IxRaw[k][y][px] -- the same two loads in the other order.
 struct WalkPos { int x, y, m; };
 template <typename PT, class P>
-__device__ __forceinline__ WalkPos walk_child(const LevelPlanes<P> &pl, const PartWalk &w, int px, int py, int pm)
+__device__ __forceinline__ WalkPos walk_child(const LevelPlanes<P> &pl, const PartWalk &w, int px, int py, int pm, bool argmax = false)
 {
     const LevelDesc &d = pl.d;
     const int m = *pl.Ik((size_t)(w.slot + pm) * pl.HW + (size_t)py * d.cols + px);
     const size_t jo = (size_t)(w.mix0 + m) * pl.HW;
+    if (argmax) {
+        const int y = *pl.template iy<PT>(jo + (size_t)py * d.cols + px);
+        const int x = *pl.template ix<PT>(jo + (size_t)px * d.rows + y);
+        return {x, y, m};
+    }
     const int x = *pl.template ix<PT>(jo + (size_t)px * d.rows + py);      // IxRaw is kept transposed ([x][y])
     const int y = *pl.template iy<PT>(jo + (size_t)py * d.cols + x);
     return {x, y, m};

@@ -361,6 +361,7 @@ struct Handle : ErrCtx {
     std::vector<std::unique_ptr<Plan>> plans;
     Resident res;
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
+    int walk_mode = 0;               // PBD_WALK_* (pbd_set_walk), read when a walk is enqueued; the latent twin follows its handle
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;
     DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)

@@ -257,6 +257,7 @@ struct ArgminParams {
     const void *IxRaw, *IyRaw; const uint8_t *Ik;     // see DpParams
     int NJ;
     int ptr8;
+    int walk_mode;                // PBD_WALK_* of the handle at enqueue (walk_child)
     float thresh;
     const float *scales;          // [nlevels]
     const PartWalk *walk;         // all components concatenated
@@ -618,6 +619,7 @@ struct ExampleParams {
     const int *frame_lv0;         // mixed plans: [nframes + 1] first virtual level of each frame (NULL: equal-size plan)
     long long cell_per_frame;
     int NC, NS, NJ, ptr8, flen, max_parts;
+    int walk_mode;                // PBD_WALK_* of the handle at the call (walk_child)
     const int *rooti;
     const void *IxRaw, *IyRaw; const uint8_t *Ik;   // see DpParams
     const PartWalk *walk; const int *walk_off;
@@ -736,6 +738,12 @@ struct QpGatherParams {
     float *x; uint8_t *bm; int32_t *hd; int32_t *ids; double *b, *d, *a;   // scratch of `count` entries
 };
 void launch_qp_gather(const QpGatherParams &p, hipStream_t s);
+struct QpHingeParams {            // pbd_qp_add_loss_device
+    const int32_t *payload; int capacity, rec_stride;
+    double y, Cl;                 // +1 / Cpos or -1 / Cneg
+    double *out;                  // [1] Cl * R(max(0, 1 - y * score)) over the records present
+};
+void launch_qp_hinge(const QpHingeParams &p, hipStream_t s);
 
 // in-place model update (pbd_set_model_vector*, pbd_qp_apply; pbd_kernels_model.hip).  Every kernel returns at once when
 // *refused is set (k_mu_check found a deformation whose quadratic term rounds to zero), so a refused call writes nothing.

@@ -867,7 +867,7 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
         } else {
             const PartWalk w = walk[pidx];
             const int par = visited[w.parent][threadIdx.x];
-            const WalkPos ch = walk_child<PT>(pl, w, par & 0xffff, par >> 16, visited_m[w.parent][threadIdx.x]);
+            const WalkPos ch = walk_child<PT>(pl, w, par & 0xffff, par >> 16, visited_m[w.parent][threadIdx.x], p.walk_mode == PBD_WALK_ARGMAX);
             x = ch.x; y = ch.y; m = ch.m;
         }
         visited[pidx][threadIdx.x] = x | (y << 16);

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kExWalkThreads) void k_ex_walk(ExampleParams p)
             } else {
                 const ExPart &par = parts[w.parent];
                 px = par.x; py = par.y; pm = par.m;
-                const WalkPos ch = walk_child<PT>(pl, w, px, py, pm);
+                const WalkPos ch = walk_child<PT>(pl, w, px, py, pm, p.walk_mode == PBD_WALK_ARGMAX);
                 x = ch.x; y = ch.y; m = ch.m;
             }
             const ExGm g = p.gm[w.mix0 + m];

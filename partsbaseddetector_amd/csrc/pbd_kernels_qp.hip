@@ -9,6 +9,7 @@
 //   k_qp_lincomb  one workgroup per (layout block, 1024 coordinates): refresh's w, each coordinate summed over its entries in
 //                 ascending a; then k_qp_norm (one workgroup): the non-negativity clamps and R(w . w)
 //   k_qp_gather   one workgroup per kept entry: prune's compaction into scratch (copied back by the host in order)
+//   k_qp_hinge    one workgroup: Cl * R(max(0, 1 - y * score)) over a payload's records (the mining bound, detect.m:135)
 //
 // R(.) (include/pbd.h): lane l of the 1024 adds the products of values l, l + 1024, ... from +0.0, then a halving tree per
 // 64 lanes (one wavefront: __shfl_down), then a halving tree over the 16 wavefront sums.  Products are multiplies then adds:
@@ -401,7 +402,25 @@ __global__ __launch_bounds__(256) void k_qp_gather(QpGatherParams p)
     if (threadIdx.x == 0) { p.b[k] = c.b[i]; p.d[k] = c.d[i]; p.a[k] = c.a[i]; }
 }
 
+// ---- the mining bound ------------------------------------------------------------------------------------------------------
+// one workgroup: record j of the payload on lane j mod 1024, each lane adding its hinges in ascending j from +0.0, then R's trees
+__global__ __launch_bounds__(kLanes) void k_qp_hinge(QpHingeParams p)
+{
+    __shared__ double red[kWaves + 1];
+    const int m = payload_count(p.payload, p.capacity);
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < m; j += kLanes) {
+        const double score = (double)__int_as_float(p.payload[1 + (size_t)j * p.rec_stride + 5]);
+        const double h = 1.0 - p.y * score;
+        acc = acc + (h > 0.0 ? h : 0.0);
+    }
+    const double s = reduce1(acc, red);
+    if (threadIdx.x == 0) p.out[0] = p.Cl * s;
+}
+
 }  // namespace
+
+void launch_qp_hinge(const QpHingeParams &p, hipStream_t s) { PBD_LAUNCH(k_qp_hinge, dim3(1), dim3(kLanes), 0, s, p); }
 
 void launch_qp_write(const QpWriteParams &p, bool f64, hipStream_t s)
 {

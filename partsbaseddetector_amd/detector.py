@@ -276,6 +276,11 @@ class Handle:
             self.check(self.lib.pbd_set_nms(self.h, 1, float(overlap)))
         self.nms_overlap = overlap
 
+    def set_walk(self, mode: int) -> None:
+        """pbd_set_walk: _lib.WALK_REFERENCE (the default: the reference's composed back-pointers) or _lib.WALK_ARGMAX (the
+        placement the score was taken at) for every walk the handle makes afterwards: part boxes, examples, latent positives"""
+        self.check(self.lib.pbd_set_walk(self.h, int(mode)))
+
     def set_debug_option(self, option: int, value: int) -> None:
         """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
         one.  _lib.DT_LANE_SHIFT: 0..6, 64 >> value rows per wave of the distance transform (-1); _lib.DT_COOP: 0, never
@@ -942,6 +947,7 @@ class PartsBasedDetector:
         self._kw = dict(device=device, conv_mode=conv_mode, max_batch=max_batch, max_candidates=max_candidates,
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
         self._nms = nms
+        self._walk = "reference"
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
         self.hd: Optional[Handle] = None
@@ -964,6 +970,8 @@ class PartsBasedDetector:
         self._dc_pays = None
         if self._nms is not None:
             self.hd.set_nms(self._nms)
+        if self._walk != "reference":
+            self.hd.set_walk(self.WALKS[self._walk])
         self._name = getattr(model, "name", "")
         self.features_ = HOGFeatures(self.hd)
         self.convolution_engine_ = SpatialConvolutionEngine(self.hd)
@@ -972,6 +980,18 @@ class PartsBasedDetector:
     def _need(self):
         if self.hd is None:
             raise PbdError(-5, "detect() before distributeModel()")
+
+    WALKS = {"reference": _lib.WALK_REFERENCE, "argmax": _lib.WALK_ARGMAX}
+
+    def setWalk(self, walk: str) -> None:
+        """how a root is walked to its parts from now on (pbd_set_walk; kept across distributeModel): "reference", the reference's
+        composed back-pointers (the default), or "argmax", the placement the score was taken at, so that w . x of every example
+        equals its score to rounding -- what training needs (detect.m:139-145)"""
+        if walk not in self.WALKS:
+            raise PbdError(-1, f"walk {walk!r}: 'reference' or 'argmax'")
+        if self.hd is not None:
+            self.hd.set_walk(self.WALKS[walk])
+        self._walk = walk
 
     def setDepthConsistency(self, zfactor: Optional[float] = 0.03) -> None:
         """detect(im, depth) then runs filterCandidatesByDepth(., depth, zfactor) before the suppression, as the reference's
@@ -1222,7 +1242,7 @@ class PartsBasedDetector:
         replication, resized to (k + 2) * sbin pixels with the detector's own resampler, and its HOG written as the example
         [bias = 1 | filter block] of filter `filter` (bias -1: the filter block alone).  Returns (hdr (n, hdr_words) int32, values
         (n, values) T, kept (n,) bool); with skip_small a box smaller than the filter's pixels is skipped (hdr[2] = -1).  The
-        examples go to QP.add as they are.  No flipping and no train() loop: those stay with the caller."""
+        examples go to QP.add as they are.  No flipping: that stays with the caller (the loop over these calls is train.train)."""
         self._need()
         if isinstance(frames, np.ndarray) and frames.ndim in (2, 3) and (frames.ndim == 2 or frames.shape[2] in (1, 3)):
             frames = [frames]

@@ -6,6 +6,10 @@ under the part's filter, each at its place in the model vector, so that ``w . x`
 
 Nothing here runs on the GPU.  The walk reads back-pointer maps in the layout ``oracle.dp_min`` returns them (Ix, Iy already
 composed as the reference composes them, Ik, rooti), so the oracle's dynamic program is the reference for the walk.
+
+The arg-max walk (pbd_set_walk, PBD_WALK_ARGMAX) needs the two passes' own pointers, which ``oracle.dp_min`` does not return:
+``raw_maps`` restates DynamicProgram::min over ``oracle.dt`` called one row and one column at a time (a length-1 pass is the
+identity), and ``compose`` puts the reference's composition back so that the restatement is pinned on ``oracle.dp_min`` itself.
 """
 from __future__ import annotations
 
@@ -76,9 +80,11 @@ def strides(flat) -> Tuple[int, int]:
     return hdr_words, (vmax + 3) // 4 * 4
 
 
-def walk(flat, c: int, x: int, y: int, Ix, Iy, Ik, rooti) -> List[Tuple[int, int, int]]:
+def walk(flat, c: int, x: int, y: int, Ix, Iy, Ik, rooti, argmax: bool = False) -> List[Tuple[int, int, int]]:
     """(x, y, mixture) of every part of component c from the root at (x, y): src/DynamicProgram.cpp:218-244 on the maps of
-    oracle.dp_min (composed Ix / Iy, Ik per pointer slot; rooti of the component)"""
+    oracle.dp_min (composed Ix / Iy, Ik per pointer slot; rooti of the component).  argmax: Ix / Iy are raw_maps' IxRaw / IyRaw
+    (one plane per global mixture) and a child sits where its score was taken: y = IyRaw[k][py][px], x = IxRaw[k][y][px] with
+    k the plane of the winning mixture (the column pass ran over the row pass's output, so its pointer comes first)"""
     p0 = int(flat.part_offset[c])
     out = []
     for p in range(int(flat.part_offset[c + 1]) - p0):
@@ -87,8 +93,106 @@ def walk(flat, c: int, x: int, y: int, Ix, Iy, Ik, rooti) -> List[Tuple[int, int
             continue
         px, py, pm = out[int(flat.parentid[p0 + p])]
         s = int(flat.ptr_slot[p0 + p]) + pm
-        out.append((int(Ix[s, py, px]), int(Iy[s, py, px]), int(Ik[s, py, px])))
+        m = int(Ik[s, py, px])
+        if argmax:
+            k = int(flat.mix_offset[p0 + p]) + m
+            cy = int(Iy[k, py, px])
+            out.append((int(Ix[k, cy, px]), cy, m))
+        else:
+            out.append((int(Ix[s, py, px]), int(Iy[s, py, px]), m))
     return out
+
+
+_walk = walk   # for the functions below whose `walk` argument names the mode
+
+
+def dt_raw(oracle, score: np.ndarray, ax, bx, ay, by, osx: int, osy: int):
+    """(out, IxRaw, IyRaw) of one distance transform: the row pass as 1 x N calls of oracle.dt (osy = 0: the length-1 column
+    pass is the identity a 0 + b 0 + src), then the column pass as M x 1 calls on the row pass's output (osx = 0)"""
+    M, N = score.shape
+    tmp = np.empty_like(score)
+    IxRaw = np.empty((M, N), np.int32)
+    for m in range(M):
+        tmp[m:m + 1], IxRaw[m:m + 1], _ = oracle.dt(score[m:m + 1], ax, bx, ay, by, osx, 0)
+    out = np.empty_like(score)
+    IyRaw = np.empty((M, N), np.int32)
+    for n in range(N):
+        out[:, n:n + 1], _, IyRaw[:, n:n + 1] = oracle.dt(tmp[:, n:n + 1], ax, bx, ay, by, 0, osy)
+    return out, IxRaw, IyRaw
+
+
+def raw_maps(flat, c: int, resp: np.ndarray):
+    """DynamicProgram::min of component c on one level's responses (nfilters, H, W) of T, restated in numpy
+    (src/DynamicProgram.cpp:83-171): parts in descending order, a distance transform per child mixture (dt_raw), reduceMax
+    over the child's mixtures with strict > from -inf (one mixture: a copy), and parent += max into the parent's plane, kept per
+    filter id as the reference keeps it.  Returns IxRaw, IyRaw (totmix, H, W: one plane per global mixture, the two passes' own
+    pointers), Ik (nslots, H, W), rootv, rooti"""
+    from oracle import oracle
+    T = resp.dtype.type
+    _, H, W = resp.shape
+    p0, p1 = int(flat.part_offset[c]), int(flat.part_offset[c + 1])
+    totmix = int(flat.mix_offset[-1])
+    IxRaw = np.zeros((totmix, H, W), np.int32)
+    IyRaw = np.zeros((totmix, H, W), np.int32)
+    Ik = np.zeros((max(flat.nslots, 1), H, W), np.int32)
+    nc = {}
+    for gp in range(p1 - 1, p0, -1):
+        g0, g1 = int(flat.mix_offset[gp]), int(flat.mix_offset[gp + 1])
+        gpar = p0 + int(flat.parentid[gp])
+        sc = []
+        for gm in range(g0, g1):
+            f, d = int(flat.filterid[gm]), int(flat.defid[gm])
+            w = [float(v) for v in flat.defw[d]]
+            o, IxRaw[gm], IyRaw[gm] = dt_raw(oracle, np.ascontiguousarray(nc.get(f, resp[f])), -w[0], -w[1], -w[2], -w[3],
+                                             int(flat.anchors[d][0]), int(flat.anchors[d][1]))
+            sc.append(o)
+        for pm in range(int(flat.mix_offset[gpar + 1]) - int(flat.mix_offset[gpar])):
+            fp = int(flat.filterid[int(flat.mix_offset[gpar]) + pm])
+            if fp not in nc:
+                nc[fp] = np.array(resp[fp], copy=True)
+            if g1 - g0 == 1:
+                v = sc[0] + T(flat.biasw[int(flat.biasid[g0]) + pm])
+                best = np.zeros((H, W), np.int32)
+            else:
+                v = np.full((H, W), -np.inf, resp.dtype)
+                best = np.zeros((H, W), np.int32)
+                for mm in range(g1 - g0):
+                    wv = sc[mm] + T(flat.biasw[int(flat.biasid[g0 + mm]) + pm])
+                    t = wv > v
+                    best[t] = mm
+                    v = np.where(t, wv, v)
+            Ik[int(flat.ptr_slot[gp]) + pm] = best
+            nc[fp] = nc[fp] + v
+    g0, g1 = int(flat.mix_offset[p0]), int(flat.mix_offset[p0 + 1])
+    bias = T(flat.biasw[int(flat.biasid[g0])])
+    plane = lambda gm: nc.get(int(flat.filterid[gm]), resp[int(flat.filterid[gm])])
+    if g1 - g0 == 1:
+        rootv, rooti = plane(g0) + bias, np.zeros((H, W), np.int32)
+    else:
+        rootv, rooti = np.full((H, W), -np.inf, resp.dtype), np.zeros((H, W), np.int32)
+        for mm in range(g1 - g0):
+            wv = plane(g0 + mm) + bias
+            t = wv > rootv
+            rooti[t] = mm
+            rootv = np.where(t, wv, rootv)
+    return IxRaw, IyRaw, Ik, rootv.astype(resp.dtype), rooti
+
+
+def compose(flat, c: int, IxRaw, IyRaw, Ik):
+    """the Ix, Iy (nslots, H, W) oracle.dp_min returns, from raw_maps' planes: the winning mixture's IxRaw, and the reference's
+    composition Iy[y][x] = IyRaw[y][Ix[y][x]] (include/DistanceTransform.hpp:233-244)"""
+    Ix, Iy = np.zeros_like(Ik), np.zeros_like(Ik)
+    H = Ik.shape[1]
+    rows = np.arange(H)[:, None]
+    p0 = int(flat.part_offset[c])
+    for gp in range(p0 + 1, int(flat.part_offset[c + 1])):
+        gpar = p0 + int(flat.parentid[gp])
+        for pm in range(int(flat.mix_offset[gpar + 1]) - int(flat.mix_offset[gpar])):
+            s = int(flat.ptr_slot[gp]) + pm
+            k = int(flat.mix_offset[gp]) + Ik[s]
+            Ix[s] = np.take_along_axis(IxRaw, k[None], 0)[0]
+            Iy[s] = IyRaw[k, rows, Ix[s]]
+    return Ix, Iy
 
 
 def window(feat: np.ndarray, x: int, y: int, k: int, flen: int = FLEN) -> np.ndarray:
@@ -209,9 +313,9 @@ def placement_score(flat, resp: np.ndarray, c: int, placement) -> float:
 class FrameMaps:
     """the oracle's features, responses and per-component DP maps of one frame (computed on first use per level)"""
 
-    def __init__(self, flat, im: np.ndarray, dtype=np.float32):
+    def __init__(self, flat, im: np.ndarray, dtype=np.float32, walk: str = "reference"):
         from oracle import oracle
-        self.oracle, self.flat, self.dtype = oracle, flat, dtype
+        self.oracle, self.flat, self.dtype, self.walk = oracle, flat, dtype, walk
         self.feats, self.scales = oracle.features_pyramid(flat, im, dtype)
         self._resp, self._dp = {}, {}
 
@@ -220,18 +324,24 @@ class FrameMaps:
             self._resp[level] = self.oracle.responses(self.flat, self.feats[level])
         return self._resp[level]
 
-    def dp(self, level: int, c: int):
-        if (level, c) not in self._dp:
-            self._dp[(level, c)] = self.oracle.dp_min(self.flat, c, self.resp(level))
-        return self._dp[(level, c)]
+    def dp(self, level: int, c: int, walk: str = "reference"):
+        """oracle.dp_min's maps, or for walk "argmax" raw_maps' (IxRaw, IyRaw in place of Ix, Iy)"""
+        key = (level, c, walk == "argmax")
+        if key not in self._dp:
+            fn = raw_maps if walk == "argmax" else self.oracle.dp_min
+            self._dp[key] = fn(self.flat, c, self.resp(level))
+        return self._dp[key]
 
-    def placement(self, level: int, c: int, x: int, y: int):
-        Ix, Iy, Ik, _, rooti = self.dp(level, c)
-        return walk(self.flat, c, x, y, Ix, Iy, Ik, rooti)
+    def placement(self, level: int, c: int, x: int, y: int, walk: str = None):
+        walk = self.walk if walk is None else walk
+        Ix, Iy, Ik, _, rooti = self.dp(level, c, walk)
+        return _walk(self.flat, c, x, y, Ix, Iy, Ik, rooti, argmax=walk == "argmax")
 
 
-def examples_of_records(flat, frames: Sequence[FrameMaps], records: np.ndarray, frame_offset: int = 0, dtype=np.float32):
-    """(hdr, values) of records (n, stride) int32 as pbd_examples returns them; frames[f] holds the oracle's maps of frame f"""
+def examples_of_records(flat, frames: Sequence[FrameMaps], records: np.ndarray, frame_offset: int = 0, dtype=np.float32,
+                        walk: str = None):
+    """(hdr, values) of records (n, stride) int32 as pbd_examples returns them; frames[f] holds the oracle's maps of frame f;
+    walk "reference" / "argmax" (None: each frame's own mode)"""
     hdr_words, vstride = strides(flat)
     records = np.atleast_2d(np.asarray(records, np.int32))
     H = np.zeros((len(records), hdr_words), np.int32)
@@ -239,7 +349,7 @@ def examples_of_records(flat, frames: Sequence[FrameMaps], records: np.ndarray, 
     for i, r in enumerate(records):
         fm = frames[int(r[0]) - frame_offset]
         lvl, c, x, y = int(r[2]), int(r[1]), int(r[3]), int(r[4])
-        H[i], V[i] = example(flat, fm.feats[lvl], c, fm.placement(lvl, c, x, y), i, dtype)
+        H[i], V[i] = example(flat, fm.feats[lvl], c, fm.placement(lvl, c, x, y, walk), i, dtype)
     return H, V
 
 
@@ -308,10 +418,11 @@ def mask_responses(uflat, resp, scale, boxes, overlap, mixtures=None, dtype=np.f
     return out
 
 
-def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, dtype=np.float32):
+def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, dtype=np.float32, walk: str = "reference"):
     """the latent positive of one frame (pbd_detect_latent): dict(level, component, root_x, root_y, score (float), parts
     (nparts, 4) x, y, w, h, placement [(x, y, mixture)], found), walked through the oracle's maps of the masked responses of the
-    unique model; ties go to the first in (level, component, y, x) order"""
+    unique model (walk "argmax": raw_maps' of the best level and component); ties go to the first in (level, component, y, x)
+    order"""
     from oracle import oracle
     uflat = unique_model(model).flatten()
     feats, scales = oracle.features_pyramid(uflat, im, dtype)
@@ -322,9 +433,13 @@ def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, d
             Ix, Iy, Ik, rootv, rooti = oracle.dp_min(uflat, c, resp)
             i = int(np.argmax(rootv))       # first maximum in raster order
             if best is None or rootv.flat[i] > best[0]:
-                best = (rootv.flat[i], lvl, c, i % rootv.shape[1], i // rootv.shape[1], (Ix, Iy, Ik, rooti))
-    v, lvl, c, x, y, maps = best
-    pl = walk(uflat, c, x, y, *maps)
+                best = (rootv.flat[i], lvl, c, i % rootv.shape[1], i // rootv.shape[1], (Ix, Iy, Ik, rooti), resp)
+    v, lvl, c, x, y, maps, resp = best
+    if walk == "argmax":
+        IxRaw, IyRaw, Ik, _, rooti = raw_maps(uflat, c, resp)
+        pl = _walk(uflat, c, x, y, IxRaw, IyRaw, Ik, rooti, argmax=True)
+    else:
+        pl = _walk(uflat, c, x, y, *maps)
     parts = []
     for p, (px, py, m) in enumerate(pl):
         gm = int(uflat.mix_offset[uflat.part_offset[c] + p]) + m

@@ -213,6 +213,37 @@ class QPRef:
         self.a.append(0.0)
         self.sv.append(1)
 
+    # -- train.m:75 (qp.n = 0) and detect.m:135 (the mining bound)
+    def clear(self):
+        """pbd_qp_clear: the state after create, except w (the next refresh rebuilds it)"""
+        self.e, self.a, self.sv = [], [], []
+        self.nfix = 0
+        self.lb = self.ub = float("nan")
+        self.loss = self.l = self.ww = 0.0
+        self.have_lb = False
+        self.lb_dropped = self.passes = self.converged = 0
+
+    def _hinge(self, y: float, score: float) -> float:
+        h = 1.0 - y * score
+        return h if h > 0.0 else 0.0
+
+    def _loss_records(self, records):
+        """the records that count: every one present, written into the cache or dropped (detect.m:133-136)"""
+        return records
+
+    def add_loss(self, records, label: int) -> float:
+        """pbd_qp_add_loss_device: ub += Cl * R(max(0, 1 - y * score_j)) over records (n, stride) int32 as a payload holds them
+        (the float score in word 5); returns the addend"""
+        if self.ub != self.ub:
+            raise ValueError("no upper bound yet")
+        r = np.asarray(records, np.int32)
+        r = self._loss_records(r.reshape(len(r), -1) if r.size else np.zeros((0, 8), np.int32))
+        scores = np.ascontiguousarray(r[:, 5]).view(np.float32).astype(np.float64)
+        y = 1.0 if label > 0 else -1.0
+        added = (self.Cpos if label > 0 else self.Cneg) * self.R(np.array([self._hinge(y, float(s)) for s in scores]))
+        self.ub = self.ub + added
+        return added
+
     def fix(self):
         self.nfix = self.n
         for i in range(self.n):
@@ -621,6 +652,17 @@ class QP:
 
     def fix(self) -> None:
         self.check(self.lib.pbd_qp_fix(self.q))
+
+    def clear(self) -> None:
+        """pbd_qp_clear: an empty cache again (train.m:75), bounds NaN as after create"""
+        self.check(self.lib.pbd_qp_clear(self.q))
+
+    def add_loss_device(self, d_payload_ptr: int, capacity: int, label: int = -1) -> float:
+        """pbd_qp_add_loss_device: ub += Cl * R(max(0, 1 - y * score)) over the records present in a device payload of the
+        detector the QP was created from (detect.m:135); returns the addend"""
+        added = ct.c_double()
+        self.check(self.lib.pbd_qp_add_loss_device(self.q, d_payload_ptr, int(capacity), int(label), ct.byref(added)))
+        return added.value
 
     def prune(self) -> int:
         n = ct.c_int()
