@@ -833,6 +833,49 @@ int pbd_qp_scores(pbd_qp *q, double *s, int *n);
 int pbd_qp_state(pbd_qp *q, struct pbd_qp_info *state, double *a, uint8_t *sv, double *w);
 int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values, double *b, double *d, int32_t *ids);
 
+/* ---- part types of a flexible-mixtures model (new surface): clusterparts.m + k_means.m of the reference's Matlab training
+ * code (matlab/learning), and the anchors of buildmodel.m:68-70.  For each of nparts parts, `trials` independent k-means runs
+ * over the npos positives' offsets to the parent; the run with the smallest sum of distances gives the part's types.
+ * The handle supplies the stream, the workspace and the error text; nothing of its model is read.  All arithmetic is double,
+ * whatever the handle's T.  Matlab's rand is not reproduced: the starting points are splitmix64 draws (below), and the defined
+ * behaviour is partsbaseddetector_amd/trainmodel.py's cluster_parts_ref, which the device matches bit for bit.
+ * def: double[nparts][npos][2], each part's (x, y) per positive (data_def.m).  parent (HOST memory in both forms): 0-based,
+ * parent[0] = -1 (the root), 0 <= parent[p] < p for every other part.  K (HOST memory in both forms): the types of each part,
+ * 1..16.  PBD_ERR_INVALID: nparts < 2, npos < 1, trials < 1, max_iter < 1, nparts * trials above 2^20, a K outside 1..16, a
+ * parent table that breaks the order above.
+ * Data: X[n] = def[p][n] - def[parent[p]][n] per coordinate; for the root X[n] = def[c][n] - def[0][n] with c its
+ *   lowest-numbered child (clusterparts.m:9-14).
+ * Start of trial r of part p: centroid t = X[z mod npos], z = splitmix64 output number (p * trials + r) * 16 + t (0-based) of
+ *   partsbaseddetector_amd/synth.py's splitmix64(seed, nparts * trials * 16).  Draws may repeat, as ceil(rand * n) may.
+ * One iteration: D_t(n) = (0.0 + dx * dx) + dy * dy with dx = X[n].x - c_t.x, dy likewise, each operation rounded on its own.
+ *   The label of n is the first t whose D_t(n) is not NaN and is strictly below every earlier one (Matlab's min: NaN is skipped,
+ *   the first minimum wins) and z(n) that distance; a point whose distances are all NaN gets label 0 and z = NaN.  Then
+ *   c_t = R(x of the members) / count_t and likewise for y, R the reduction stated with the QP above (point n on lane n mod
+ *   PBD_QP_LANES, a point that is not a member adds nothing); a cluster without members gets a NaN centroid, so it never wins a
+ *   point again.
+ * End of a trial: labels start at -1, so the first iteration always changes one; the trial ends after the first iteration that
+ *   changes no label, or after max_iter iterations.  sumdist = R(z) of the last iteration.
+ * Pick (clusterparts.m:25-26): the first trial whose sumdist is not NaN and strictly below every earlier one; none: trial 0.
+ *   idx (0-based types), centres and counts are that trial's; centres of unused (t >= K) or empty types are NaN, their counts 0.
+ * Anchors (buildmodel.m:68-70, then zeroIndex): a type's centre is the mean of def[child] - def[parent] over its members, so
+ *   anchor = matlab_round(centre + 1.0) - 1 per coordinate, rounding halves away from zero (a centre of exactly -0.5 gives 0,
+ *   not round(-0.5) = -1), saturating at the int32 range.  The root's anchors and those of NaN centres are 0.
+ * Defined differently from the reference, on purpose: a type with one member keeps that member as its centre (Matlab's mean of
+ *   a 1 x 2 row collapses it to (x + y) / 2 in both coordinates), and max_iter exists.
+ * info[p]: the picked trial, its iterations and its sumdist.  sumdist_all / iters_all ([nparts][trials], either may be NULL):
+ *   every trial's.  pbd_cluster_parts is synchronous and takes host pointers; pbd_cluster_parts_device takes device pointers
+ *   (def and every output; parent and K stay on the host), is asynchronous on pbd_stream() and reads def in place. */
+struct pbd_cluster_info {
+    int32_t best_trial, iterations;
+    double sumdist;
+};
+int pbd_cluster_parts(pbd_handle *h, int nparts, int npos, const double *def, const int32_t *parent, const int32_t *K, int trials,
+                      int max_iter, uint64_t seed, int32_t *idx, double *centres, int32_t *counts, int32_t *anchors,
+                      struct pbd_cluster_info *info, double *sumdist_all, int32_t *iters_all);
+int pbd_cluster_parts_device(pbd_handle *h, int nparts, int npos, const double *d_def, const int32_t *parent, const int32_t *K,
+                             int trials, int max_iter, uint64_t seed, int32_t *d_idx, double *d_centres, int32_t *d_counts,
+                             int32_t *d_anchors, struct pbd_cluster_info *d_info, double *d_sumdist_all, int32_t *d_iters_all);
+
 /* ---- IConvolutionEngine (include/IConvolutionEngine.hpp:44-68), SpatialConvolutionEngine. */
 /* setFilters(filters): filters[f] is ksize[f] x (ksize[f]*flen) values of T.  pbd_create already
  * installs the model's filters; this replaces them (src/SpatialConvolutionEngine.cpp:133-159). */
@@ -968,6 +1011,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_EV_APK_RANK, PBD_K_EV_APK_CLOSE, PBD_K_EV_APK_AP,
        /* pbd_qp_add_loss_device (named for traces, as the other QP kernels) */
        PBD_K_QP_HINGE,
+       /* pbd_cluster_parts*: every (part, trial)'s k-means run, then the pick per part */
+       PBD_K_KM_TRIALS, PBD_K_KM_PICK,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

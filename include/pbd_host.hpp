@@ -575,6 +575,16 @@ private:
     pbd_qp *q_;
 };
 
+// what PartsBasedDetector::clusterParts returns (pbd_cluster_parts): rows of 16 types per part, unused or empty types NaN / 0
+struct PartClusters {
+    std::vector<int32_t> idx;                  // [part][positive] 0-based type
+    std::vector<double> centres;               // [part][16][2]
+    std::vector<int32_t> counts, anchors;      // [part][16], [part][16][2]
+    std::vector<pbd_cluster_info> info;        // [part] the picked trial
+    std::vector<double> sumdist_all;           // [part][trial]
+    std::vector<int32_t> iters_all;            // [part][trial]
+};
+
 template <typename T>
 class PartsBasedDetector {
     std::string name_;
@@ -1028,6 +1038,26 @@ public:
         if (prec) prec->resize(np * n);
         if (rec) rec->resize(np * n);
         return apk;
+    }
+    // new surface: clusterparts.m + k_means.m and buildmodel.m's anchors on the device (pbd_cluster_parts): the part types of a
+    // flexible-mixtures model by `trials` k-means restarts per part.  def = [part][positive][2] (data_def.m), parent = 0-based
+    // parents (root -1, parent < child), K = types per part (1..16).  The detector's model is not read.  trainmodel.m's pipeline
+    // around it is Python's (partsbaseddetector_amd/trainmodel.py), as train.m's is.
+    PartClusters clusterParts(const std::vector<double> &def, const std::vector<int32_t> &parent, const std::vector<int32_t> &K,
+                              int trials = 100, int max_iter = 1000, uint64_t seed = 0)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "clusterParts() before distributeModel()");
+        const size_t np = parent.size();
+        if (np < 2 || K.size() != np || def.empty() || def.size() % (2 * np) || trials < 1)
+            throw Error(PBD_ERR_INVALID, "clusterParts: def holds two values per part and positive, parent and K one per part");
+        const size_t n = def.size() / (2 * np);
+        PartClusters out;
+        out.idx.assign(np * n, 0); out.centres.assign(np * 32, 0.0); out.counts.assign(np * 16, 0); out.anchors.assign(np * 32, 0);
+        out.info.resize(np); out.sumdist_all.assign(np * (size_t)trials, 0.0); out.iters_all.assign(np * (size_t)trials, 0);
+        pbdbind::check<HostTraits<T> >(h_, pbd_cluster_parts(h_, (int)np, (int)n, &def[0], &parent[0], &K[0], trials, max_iter, seed,
+                                                             &out.idx[0], &out.centres[0], &out.counts[0], &out.anchors[0],
+                                                             &out.info[0], &out.sumdist_all[0], &out.iters_all[0]));
+        return out;
     }
     // warped positives (matlab/learning/train.m poswarp, warppos.m, qp_poswrite) on the device (pbd_warp_positives): boxes holds
     // five values per box, {image, x1, y1, x2, y2} (0-based, inclusive); each box is padded by one cell, cropped with edge

@@ -32,7 +32,7 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
            "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
            "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge"]
+           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -52,7 +52,7 @@ SYMBOLS = [
     "pbd_qp_entries", "pbd_set_model_vector", "pbd_set_model_vector_device", "pbd_set_thresh", "pbd_qp_apply",
     "pbd_warp_positives", "pbd_warp_positives_device", "pbd_part_nms", "pbd_part_nms_device", "pbd_best_overlap",
     "pbd_best_overlap_device", "pbd_eval_pck", "pbd_eval_pck_device", "pbd_eval_apk", "pbd_eval_apk_device",
-    "pbd_set_walk", "pbd_qp_clear", "pbd_qp_add_loss_device",
+    "pbd_set_walk", "pbd_qp_clear", "pbd_qp_add_loss_device", "pbd_cluster_parts", "pbd_cluster_parts_device",
 ]
 
 
@@ -140,6 +140,16 @@ class CQpConfig(C.Structure):
 class CQpInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "nsv", "nfix", "capacity", "len", "hdr_words", "values")] + \
                [(n, C.c_double) for n in ("lb", "ub", "loss", "l")] + [(n, C.c_int) for n in ("lb_dropped", "passes", "converged", "pad")]
+
+
+class CClusterInfo(C.Structure):
+    """pbd_cluster_info: the picked trial of one part"""
+    _fields_ = [("best_trial", C.c_int32), ("iterations", C.c_int32), ("sumdist", C.c_double)]
+
+
+CLUSTER_INFO_DTYPE = np.dtype([("best_trial", np.int32), ("iterations", np.int32), ("sumdist", np.float64)])
+MAX_MIX = 16               # kMaxMix: types per part; a row of pbd_cluster_parts' centres, counts and anchors
+KM_MAX_GRID = 2048         # workgroups of k_km_trials; more (part, trial) pairs are taken in a stride loop
 
 
 class CConfig(C.Structure):
@@ -276,6 +286,9 @@ def load():
     lib.pbd_qp_scores.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     lib.pbd_qp_state.argtypes = [C.c_void_p, C.POINTER(CQpInfo), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_qp_entries.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.pbd_cluster_parts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64] + \
+                                     [C.c_void_p] * 7
+    lib.pbd_cluster_parts_device.argtypes = lib.pbd_cluster_parts.argtypes
     lib.pbd_debug_mixed_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.c_int]
     lib.pbd_stream.argtypes = [C.c_void_p]

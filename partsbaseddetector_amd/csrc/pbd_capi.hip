@@ -2298,7 +2298,7 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-                                             "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge"};
+                                             "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

@@ -1259,3 +1259,116 @@ int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values,
 }
 
 }  // extern "C"
+
+// ---- part types by k-means (pbd_cluster_parts*; pbd_kernels_kmeans.hip)
+namespace {
+
+constexpr long long kKmMaxPairs = 1LL << 20;
+
+int check_cluster(pbd_handle *h, int nparts, int npos, const int32_t *parent, const int32_t *K, int trials, int max_iter, int *maxK)
+{
+    if (nparts < 2) return fail(h, PBD_ERR_INVALID, "nparts %d: a tree has a root and at least one child", nparts);
+    if (npos < 1 || trials < 1 || max_iter < 1)
+        return fail(h, PBD_ERR_INVALID, "npos %d, trials %d, max_iter %d (each at least 1)", npos, trials, max_iter);
+    if ((long long)nparts * trials > kKmMaxPairs)
+        return fail(h, PBD_ERR_INVALID, "%d parts x %d trials (at most %lld pairs)", nparts, trials, kKmMaxPairs);
+    *maxK = 1;
+    for (int p = 0; p < nparts; ++p) {
+        if (K[p] < 1 || K[p] > kMaxMix) return fail(h, PBD_ERR_INVALID, "part %d: K %d (1..%d)", p, K[p], kMaxMix);
+        *maxK = std::max(*maxK, (int)K[p]);
+        if (p == 0 ? parent[p] != -1 : (parent[p] < 0 || parent[p] >= p))
+            return fail(h, PBD_ERR_INVALID, "part %d: parent %d (part 0 is the root, -1; every other parent is in 0..part-1)", p, parent[p]);
+    }
+    return PBD_OK;
+}
+
+// the tables through the staging buffer, the workspace, the two kernels and the per-trial copies on the handle's stream
+int enqueue_cluster(pbd_handle *h, int nparts, int npos, const double *d_def, const int32_t *parent, const int32_t *K, int trials,
+                    int max_iter, uint64_t seed, int maxK, int32_t *d_idx, double *d_centres, int32_t *d_counts, int32_t *d_anchors,
+                    pbd_cluster_info *d_info, double *d_sumdist_all, int32_t *d_iters_all)
+{
+    const size_t pairs = (size_t)nparts * trials, nstart = pairs * kMaxMix;
+    static_assert(sizeof(KmPart) == 4 * sizeof(int32_t), "the staged block is one int32 array");
+    std::vector<int32_t> tab(4 * (size_t)nparts + nstart);
+    for (int p = 0; p < nparts; ++p) {   // the root reads its lowest-numbered child's offsets: part 1 (parent[1] is 0)
+        const KmPart kp = p == 0 ? KmPart{1, 0, K[p], 1} : KmPart{p, parent[p], K[p], 0};
+        memcpy(tab.data() + 4 * (size_t)p, &kp, sizeof kp);
+    }
+    int32_t *start = tab.data() + 4 * (size_t)nparts;
+    for (size_t i = 0; i < nstart; ++i) start[i] = (int32_t)(qp_splitmix64(seed, (uint64_t)i + 1) % (uint64_t)npos);
+    if (int rc = h->km_tab.stage(h, tab.data(), tab.size() * sizeof(int32_t))) return rc;
+    KmParams p{};
+    if (int rc = carve(h, h->km_ws, [&](Carve &c) {
+            p.sumdist = c.take<double>(pairs * sizeof(double));
+            p.cen = c.take<double>(pairs * kMaxMix * 2 * sizeof(double));
+            p.iters = c.take<int32_t>(pairs * sizeof(int32_t));
+            p.cnt = c.take<int32_t>(pairs * kMaxMix * sizeof(int32_t));
+            p.lab = c.take<uint8_t>(pairs * (size_t)npos);
+        })) return rc;
+    p.def = d_def;
+    p.parts = h->km_tab.as<KmPart>();
+    p.start = h->km_tab.as<int32_t>() + 4 * (size_t)nparts;
+    p.nparts = nparts; p.npos = npos; p.trials = trials; p.max_iter = max_iter;
+    p.idx = d_idx; p.centres = d_centres; p.counts = d_counts; p.anchors = d_anchors; p.info = d_info;
+    { ProfScope ps(h, PBD_K_KM_TRIALS, h->stream); launch_km_trials(p, maxK, h->stream); }
+    { ProfScope ps(h, PBD_K_KM_PICK, h->stream); launch_km_pick(p, h->stream); }
+    HIPCHK(h, hipGetLastError());
+    if (d_sumdist_all) HIPCHK(h, hipMemcpyAsync(d_sumdist_all, p.sumdist, pairs * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (d_iters_all) HIPCHK(h, hipMemcpyAsync(d_iters_all, p.iters, pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    return PBD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// clusterparts.m + k_means.m, and buildmodel.m's anchors.  See include/pbd.h.
+int pbd_cluster_parts(pbd_handle *h, int nparts, int npos, const double *def, const int32_t *parent, const int32_t *K, int trials,
+                      int max_iter, uint64_t seed, int32_t *idx, double *centres, int32_t *counts, int32_t *anchors,
+                      struct pbd_cluster_info *info, double *sumdist_all, int32_t *iters_all)
+{
+    return entry(h, def && parent && K && idx && centres && counts && anchors && info, kIdle, [&]() -> int {
+        int maxK;
+        if (int rc = check_cluster(h, nparts, npos, parent, K, trials, max_iter, &maxK)) return rc;
+        const size_t np = (size_t)nparts, pairs = np * trials, def_bytes = np * npos * 2 * sizeof(double);
+        HIPCHK(h, h->km_in.ensure(def_bytes));
+        int32_t *d_idx, *d_counts, *d_anchors, *d_its;
+        double *d_centres, *d_sd;
+        pbd_cluster_info *d_info;
+        if (int rc = carve(h, h->km_out, [&](Carve &c) {
+                d_centres = c.take<double>(np * kMaxMix * 2 * sizeof(double));
+                d_sd = c.take<double>(pairs * sizeof(double));
+                d_info = c.take<pbd_cluster_info>(np * sizeof(pbd_cluster_info));
+                d_idx = c.take<int32_t>(np * npos * sizeof(int32_t));
+                d_counts = c.take<int32_t>(np * kMaxMix * sizeof(int32_t));
+                d_anchors = c.take<int32_t>(np * kMaxMix * 2 * sizeof(int32_t));
+                d_its = c.take<int32_t>(pairs * sizeof(int32_t));
+            })) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->km_in.p, def, def_bytes, hipMemcpyHostToDevice, h->stream));
+        if (int rc = enqueue_cluster(h, nparts, npos, h->km_in.as<double>(), parent, K, trials, max_iter, seed, maxK, d_idx, d_centres,
+                                     d_counts, d_anchors, d_info, sumdist_all ? d_sd : nullptr, iters_all ? d_its : nullptr)) return rc;
+        HIPCHK(h, hipMemcpyAsync(idx, d_idx, np * npos * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(centres, d_centres, np * kMaxMix * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(counts, d_counts, np * kMaxMix * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(anchors, d_anchors, np * kMaxMix * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(info, d_info, np * sizeof(pbd_cluster_info), hipMemcpyDeviceToHost, h->stream));
+        if (sumdist_all) HIPCHK(h, hipMemcpyAsync(sumdist_all, d_sd, pairs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (iters_all) HIPCHK(h, hipMemcpyAsync(iters_all, d_its, pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_cluster_parts_device(pbd_handle *h, int nparts, int npos, const double *d_def, const int32_t *parent, const int32_t *K,
+                             int trials, int max_iter, uint64_t seed, int32_t *d_idx, double *d_centres, int32_t *d_counts,
+                             int32_t *d_anchors, struct pbd_cluster_info *d_info, double *d_sumdist_all, int32_t *d_iters_all)
+{
+    return entry(h, d_def && parent && K && d_idx && d_centres && d_counts && d_anchors && d_info, kIdle, [&]() -> int {
+        int maxK;
+        if (int rc = check_cluster(h, nparts, npos, parent, K, trials, max_iter, &maxK)) return rc;
+        return enqueue_cluster(h, nparts, npos, d_def, parent, K, trials, max_iter, seed, maxK, d_idx, d_centres, d_counts, d_anchors,
+                               d_info, d_sumdist_all, d_iters_all);
+    });
+}
+
+}  // extern "C"

@@ -1,8 +1,8 @@
 // pbd_device.h (private) -- the device idioms the post-detection stage kernels share, one definition each: the lock-free
 // union-find, the wave / workgroup scan, rank and sum, the device-wide exclusive scan, the wave-aggregated atomic add, the
-// order-preserving keys, and the candidate record's words, hull and count.  The stage files (pbd_kernels_cloud / planes /
-// consistency / depth / post / publish / qp / eval .hip) keep only what is their own.  All integer arithmetic here is exact, so a
-// caller's result does not depend on which of these it is built from.
+// order-preserving keys, the reduction R(.) of include/pbd.h, and the candidate record's words, hull and count.  The stage files
+// (pbd_kernels_cloud / planes / consistency / depth / post / publish / qp / eval / kmeans .hip) keep only what is their own.
+// All integer arithmetic here is exact, so a caller's result does not depend on which of these it is built from.
 #pragma once
 
 #include "pbd_internal.h"
@@ -177,6 +177,46 @@ template <int WAVES, typename A, typename T> __device__ inline A block_sum(T v, 
 #pragma unroll
     for (int k = 0; k < WAVES; ++k) s += lds[k];
     return s;
+}
+
+// ---- the reduction R(.) of include/pbd.h over one workgroup of PBD_QP_LANES threads (pbd_kernels_qp / kmeans .hip) --------------
+// The caller's lane-strided partial sums go in; a halving tree per 64 lanes (one wavefront: __shfl_down), then a halving tree
+// over the 16 wavefront sums.
+constexpr int kRLanes = PBD_QP_LANES;
+constexpr int kRWaves = kRLanes / 64;
+static_assert(kRLanes == 1024 && kRWaves == 16, "the reduction order of include/pbd.h");
+
+// R(v) of one value per thread; every thread receives the result.  red: 17 doubles of LDS.  Contains two barriers.
+__device__ inline double reduce1(double v, double *red)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (wave == 0) {
+        double s = lane < kRWaves ? red[lane] : 0.0;
+        for (int h = kRWaves / 2; h >= 1; h >>= 1) s = s + __shfl_down(s, h, 64);
+        if (lane == 0) red[kRWaves] = s;
+    }
+    __syncthreads();
+    return red[kRWaves];
+}
+
+// two reductions at once: red holds 34 doubles
+__device__ inline void reduce2(double u, double v, double *red, double *ru, double *rv)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int h = 32; h >= 1; h >>= 1) { u = u + __shfl_down(u, h, 64); v = v + __shfl_down(v, h, 64); }
+    if (lane == 0) { red[wave] = u; red[kRWaves + 1 + wave] = v; }
+    __syncthreads();
+    if (wave == 0) {
+        double s = lane < kRWaves ? red[lane] : 0.0, t = lane < kRWaves ? red[kRWaves + 1 + lane] : 0.0;
+        for (int h = kRWaves / 2; h >= 1; h >>= 1) { s = s + __shfl_down(s, h, 64); t = t + __shfl_down(t, h, 64); }
+        if (lane == 0) { red[kRWaves] = s; red[2 * kRWaves + 1] = t; }
+    }
+    __syncthreads();
+    *ru = red[kRWaves];
+    *rv = red[2 * kRWaves + 1];
 }
 
 // ---- lock-free union-find (ECL-CC style) ------------------------------------------------------------------------------------

@@ -435,6 +435,10 @@ struct Handle : ErrCtx {
     std::unique_ptr<pbd_handle, void (*)(pbd_handle *)> lat{nullptr, pbd_destroy};
     DevTable<int4> lat_gm;
     DevBuf lat_in, lat_pay;
+    // pbd_cluster_parts*: the call's tables (parts and starting points in one staged block), the per-pair workspace, the host
+    // form's offsets and outputs
+    StagedTable km_tab;
+    DevBuf km_ws, km_in, km_out;
     // mixed-size calls: the FrameDesc table
     StagedTable fd_tab;
     // pbd_warp_positives*: the plan whose levels are the kept boxes' patches (rebuilt when the kept count or the patch size

@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -744,6 +745,27 @@ struct QpHingeParams {            // pbd_qp_add_loss_device
     double *out;                  // [1] Cl * R(max(0, 1 - y * score)) over the records present
 };
 void launch_qp_hinge(const QpHingeParams &p, hipStream_t s);
+
+// part types by k-means (pbd_cluster_parts*; pbd_kernels_kmeans.hip).  A pair = (part, trial), pair = part * trials + trial.
+constexpr int kKmMaxGrid = 2048;     // workgroups of k_km_trials (one pair each, grid-stride over the rest)
+struct KmPart { int a, b, K, root; };   // X[n] = def[a][n] - def[b][n]; the part's types; 1 for the root (anchors 0)
+struct KmParams {
+    const double *def;            // [nparts][npos][2]
+    const KmPart *parts;          // [nparts]
+    const int32_t *start;         // [pairs][kMaxMix] the point each centroid starts at (the first K of a pair are read)
+    int nparts, npos, trials, max_iter;
+    // workspace, per pair
+    uint8_t *lab;                 // [pairs][npos] labels
+    double *sumdist; int32_t *iters;   // [pairs]
+    double *cen; int32_t *cnt;    // [pairs][kMaxMix][2], [pairs][kMaxMix]
+    // outputs (k_km_pick)
+    int32_t *idx;                 // [nparts][npos]
+    double *centres;              // [nparts][kMaxMix][2]
+    int32_t *counts, *anchors;    // [nparts][kMaxMix], [nparts][kMaxMix][2]
+    pbd_cluster_info *info;       // [nparts]
+};
+void launch_km_trials(const KmParams &p, int maxK, hipStream_t s);   // maxK: the largest K of the call
+void launch_km_pick(const KmParams &p, hipStream_t s);
 
 // in-place model update (pbd_set_model_vector*, pbd_qp_apply; pbd_kernels_model.hip).  Every kernel returns at once when
 // *refused is set (k_mu_check found a deformation whose quadratic term rounds to zero), so a refused call writes nothing.

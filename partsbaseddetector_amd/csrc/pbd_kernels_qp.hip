@@ -19,45 +19,11 @@
 namespace pbd {
 namespace {
 
-constexpr int kLanes = PBD_QP_LANES;
-constexpr int kWaves = kLanes / 64;
-static_assert(kLanes == 1024 && kWaves == 16, "the reduction order of include/pbd.h");
+constexpr int kLanes = kRLanes;      // reduce1 / reduce2: pbd_device.h
+constexpr int kWaves = kRWaves;
 
 __device__ __forceinline__ double dmin(double a, double b) { return a > b ? b : a; }   // MIN / MAX of qp_one_sparse.cc
 __device__ __forceinline__ double dmax(double a, double b) { return a < b ? b : a; }
-
-// R(v) of one value per thread; every thread receives the result.  red: 17 doubles of LDS.  Contains two barriers.
-__device__ double reduce1(double v, double *red)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    if (wave == 0) {
-        double s = lane < kWaves ? red[lane] : 0.0;
-        for (int h = kWaves / 2; h >= 1; h >>= 1) s = s + __shfl_down(s, h, 64);
-        if (lane == 0) red[kWaves] = s;
-    }
-    __syncthreads();
-    return red[kWaves];
-}
-
-// two reductions at once: red holds 34 doubles
-__device__ void reduce2(double u, double v, double *red, double *ru, double *rv)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int h = 32; h >= 1; h >>= 1) { u = u + __shfl_down(u, h, 64); v = v + __shfl_down(v, h, 64); }
-    if (lane == 0) { red[wave] = u; red[kWaves + 1 + wave] = v; }
-    __syncthreads();
-    if (wave == 0) {
-        double s = lane < kWaves ? red[lane] : 0.0, t = lane < kWaves ? red[kWaves + 1 + lane] : 0.0;
-        for (int h = kWaves / 2; h >= 1; h >>= 1) { s = s + __shfl_down(s, h, 64); t = t + __shfl_down(t, h, 64); }
-        if (lane == 0) { red[kWaves] = s; red[2 * kWaves + 1] = t; }
-    }
-    __syncthreads();
-    *ru = red[kWaves];
-    *rv = red[2 * kWaves + 1];
-}
 
 // an entry's header into LDS (3 words per block); the caller synchronises
 __device__ __forceinline__ int load_hdr(const QpCache &c, int i, int *tab, int *nv)

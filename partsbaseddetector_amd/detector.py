@@ -609,6 +609,46 @@ class Handle:
         self.check(self.lib.pbd_eval_apk_device(self.h, len(off) - 1, off.ctypes.data, gt.ctypes.data, sc.ctypes.data, float(thresh),
                                                 d_payload_ptr, capacity, frame_offset, d_apk_ptr, d_prec_ptr, d_rec_ptr, d_status_ptr))
 
+    @staticmethod
+    def _cluster_args(deffeat, parent, K):
+        d = np.ascontiguousarray(deffeat, np.float64)
+        pa = np.ascontiguousarray(parent, np.int32).ravel()
+        k = np.ascontiguousarray(K, np.int32).ravel()
+        if d.ndim != 3 or d.shape[2] != 2 or len(pa) != d.shape[0] or len(k) != d.shape[0]:
+            raise PbdError(-1, "def is (nparts, npos, 2), parent and K (nparts,)")
+        return d, pa, k
+
+    def cluster_parts(self, deffeat, parent, K, trials: int = 100, max_iter: int = 1000, seed: int = 0, want_all: bool = True) -> dict:
+        """pbd_cluster_parts: clusterparts.m + k_means.m on the device -> {"idx" (nparts, npos), "centres" (nparts, 16, 2),
+        "counts" (nparts, 16), "anchors" (nparts, 16, 2), "info" (nparts,) of _lib.CLUSTER_INFO_DTYPE, and with want_all
+        "sumdist_all", "iters_all" (nparts, trials)}"""
+        d, pa, k = self._cluster_args(deffeat, parent, K)
+        P, N, M = d.shape[0], d.shape[1], _lib.MAX_MIX
+        out = {"idx": np.zeros((P, N), np.int32), "centres": np.zeros((P, M, 2)), "counts": np.zeros((P, M), np.int32),
+               "anchors": np.zeros((P, M, 2), np.int32), "info": np.zeros(P, _lib.CLUSTER_INFO_DTYPE)}
+        if want_all:
+            out["sumdist_all"] = np.zeros((P, max(int(trials), 0)))
+            out["iters_all"] = np.zeros((P, max(int(trials), 0)), np.int32)
+        self.check(self.lib.pbd_cluster_parts(self.h, P, N, d.ctypes.data, pa.ctypes.data, k.ctypes.data, int(trials), int(max_iter),
+                                              int(seed), out["idx"].ctypes.data, out["centres"].ctypes.data, out["counts"].ctypes.data,
+                                              out["anchors"].ctypes.data, out["info"].ctypes.data,
+                                              out["sumdist_all"].ctypes.data if want_all else None,
+                                              out["iters_all"].ctypes.data if want_all else None))
+        return out
+
+    def cluster_parts_device(self, nparts: int, npos: int, d_def_ptr: int, parent, K, trials: int, max_iter: int, seed: int,
+                             d_idx_ptr: int, d_centres_ptr: int, d_counts_ptr: int, d_anchors_ptr: int, d_info_ptr: int,
+                             d_sumdist_all_ptr: Optional[int] = None, d_iters_all_ptr: Optional[int] = None) -> None:
+        """pbd_cluster_parts_device: double[nparts][npos][2] at d_def_ptr in, the outputs of cluster_parts at the device pointers
+        (info as {int32, int32, double} records); parent and K are host arrays; asynchronous"""
+        pa = np.ascontiguousarray(parent, np.int32).ravel()
+        k = np.ascontiguousarray(K, np.int32).ravel()
+        if len(pa) != nparts or len(k) != nparts:
+            raise PbdError(-1, "parent and K are (nparts,)")
+        self.check(self.lib.pbd_cluster_parts_device(self.h, nparts, npos, d_def_ptr, pa.ctypes.data, k.ctypes.data, int(trials),
+                                                     int(max_iter), int(seed), d_idx_ptr, d_centres_ptr, d_counts_ptr, d_anchors_ptr,
+                                                     d_info_ptr, d_sumdist_all_ptr, d_iters_all_ptr))
+
     def boxes3d_camera(self, depths: Sequence[np.ndarray], im_shapes, cameras, records: np.ndarray, parts_mode: int = 0,
                        frame_offset: int = 0):
         """pbd_boxes3d_camera: camera boxes (n, 6) float64, part centres (n, max_parts, 3) float32 (0 past ncentres), ncentres (n,)
@@ -1067,6 +1107,14 @@ class PartsBasedDetector:
         """eval_apk.m + VOCap.m on the device (pbd_eval_apk) -> apk (nparts,), prec, rec (nparts, n)"""
         self._need()
         return self.hd.eval_apk(self.hd.pack_candidates(list(candidates)), gt_offset, gt_points, gt_scale, thresh)
+
+    def clusterParts(self, deffeat, parent, K, trials: int = 100, max_iter: int = 1000, seed: int = 0) -> dict:
+        """clusterparts.m on the device (pbd_cluster_parts): the part types of a flexible-mixtures model by `trials` k-means
+        restarts per part over the positives' offsets to the parent, and buildmodel.m's anchors.  deffeat (nparts, npos, 2):
+        trainmodel.data_def's output; parent (nparts,): 0-based, root -1; K (nparts,): types per part, 1..16.  The detector's
+        model is not read.  -> Handle.cluster_parts' dict"""
+        self._need()
+        return self.hd.cluster_parts(deffeat, parent, K, trials, max_iter, seed)
 
     def _unsuppressed_payload(self, frames: Sequence[np.ndarray]):
         """the frames' unsuppressed list (the handle's own suppression off) in a device payload of the detector's; the list
