@@ -628,8 +628,11 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
  * highest-scoring root over all levels, components and positions (ties: the first in (level, component, y, x) order), as a
  * normal record (`frame` = f, part boxes of the walk); found[f] = 1 iff its score > -5e9 (no masked term used).
  * The call leaves a resident result: pbd_examples* then give the positives' feature vectors (offsets in this handle's model
- * vector); pbd_get_stage / pbd_argmin_device_out / pbd_dp_argmin see no result until the next detect call.  pbd_set_nms does not
- * apply.  PBD_ERR_UNSUPPORTED: components with different part counts, level sharding (world > 1), PBD_CONV_MFMA_F16.
+ * vector) and pbd_get_stage reads the stages of that run, addressed (frame, level) as after a mixed call: PBD_STAGE_RESPONSES is
+ * the MASKED responses, one plane per (component, part, mixture) in global mixture order; PBD_STAGE_ROOTV / _ROOTI are the
+ * dynamic program's on them and PBD_STAGE_FEATURES the frames' features.  pbd_argmin_device_out / pbd_dp_argmin see no result
+ * until the next detect call.  pbd_set_nms does not apply.
+ * PBD_ERR_UNSUPPORTED: components with different part counts, level sharding (world > 1), PBD_CONV_MFMA_F16.
  * PBD_ERR_INVALID: a NaN overlap, and the frame refusals of pbd_detect_frames.  PBD_ERR_STATE while a batch is in flight. */
 int pbd_detect_latent(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
                       const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found);
@@ -980,9 +983,11 @@ int pbd_detect_frames_device(pbd_handle *h, int nframes, const pbd_frame *frames
 int pbd_detect_frames_device_out(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code,
                                  int frame_offset, int32_t *d_payload, int capacity);
 
-/* ---- staged read-back of the last pbd_detect* call (tests, profiling) ----
+/* ---- staged read-back of the last pbd_detect* or pbd_detect_latent call (tests, profiling) ----
  * A stage is readable only if the last computation produced it: after pbd_conv_set_filters the responses and DP
  * results are gone, and after pbd_dp_min (which starts from uploaded responses) PBD_STAGE_FEATURES is PBD_ERR_STATE.
+ * After pbd_detect_latent the stages are those of its masked run (see there), whose responses have one plane per
+ * (component, part, mixture), not per filter; after a model update nothing of a latent result is readable.
  * A refused call leaves the previous result readable. */
 enum { PBD_STAGE_FEATURES = 0, PBD_STAGE_RESPONSES = 1, PBD_STAGE_ROOTV = 2, PBD_STAGE_ROOTI = 3 };
 int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, size_t dst_bytes);

@@ -2228,8 +2228,10 @@ void *pbd_stream(const pbd_handle *h) { return h ? reinterpret_cast<void *>(h->s
 int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, size_t dst_bytes)
 {
     return entry(h, dst, kIdle, [&]() -> int {
-        const Resident &r = h->res;
-        if (!r.plan) return fail(h, PBD_ERR_STATE, "nothing has been computed");
+        pbd_handle *o = resident_owner(h);   // after pbd_detect_latent the twin: its features, masked responses and root planes
+        const Resident &r = o->res;
+        // (a model update drops the twin's responses and maps: nothing of a latent result is readable then)
+        if (!r.plan || (o != h && !(r.resp && r.dp))) return fail(h, PBD_ERR_STATE, "nothing has been computed");
         const Plan &P = *r.plan;
         if (!resident_level(r, frame, level, &frame, &level)) return fail(h, PBD_ERR_INVALID, "frame/level out of range");
         const LevelDesc &d = P.lv[level];
@@ -2239,21 +2241,21 @@ int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, siz
         switch (stage) {
         case PBD_STAGE_FEATURES:
             if (!r.features) return fail(h, PBD_ERR_STATE, "features not computed");
-            src = h->feat.as<char>() + cell * 32 * h->rs; bytes = hw * 32 * h->rs; break;
+            src = o->feat.as<char>() + cell * 32 * h->rs; bytes = hw * 32 * h->rs; break;
         case PBD_STAGE_RESPONSES:
             if (!r.resp) return fail(h, PBD_ERR_STATE, "responses not computed");
-            src = h->resp.as<char>() + cell * h->F * h->resp_es; bytes = hw * h->F * h->rs; break;
+            src = o->resp.as<char>() + cell * o->F * o->resp_es; bytes = hw * o->F * h->rs; break;
         case PBD_STAGE_ROOTV:
             if (!r.dp) return fail(h, PBD_ERR_STATE, "dp not computed");
-            src = h->rootv.as<char>() + cell * h->NC * h->rs; bytes = hw * h->NC * h->rs; break;
+            src = o->rootv.as<char>() + cell * o->NC * h->rs; bytes = hw * o->NC * h->rs; break;
         case PBD_STAGE_ROOTI:
             if (!r.dp) return fail(h, PBD_ERR_STATE, "dp not computed");
-            src = h->rooti.as<int>() + cell * h->NC; bytes = hw * h->NC * sizeof(int); break;
+            src = o->rooti.as<int>() + cell * o->NC; bytes = hw * o->NC * sizeof(int); break;
         default: return fail(h, PBD_ERR_INVALID, "unknown stage %d", stage);
         }
         if (dst_bytes < bytes) return fail(h, PBD_ERR_INVALID, "destination holds %zu bytes, need %zu", dst_bytes, bytes);
         if (stage == PBD_STAGE_RESPONSES) {
-            if (int rc = read_responses(h, dst, src, hw * h->F)) return rc;
+            if (int rc = read_responses(h, dst, src, hw * o->F)) return rc;
         } else if (bytes) {
             HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
         }

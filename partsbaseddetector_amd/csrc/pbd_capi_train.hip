@@ -8,9 +8,6 @@ using namespace pbd;
 namespace {
 
 // pbd_examples*: the resident result a record can be walked in (PBD_OK or the failure's status code)
-// the handle whose buffers hold the resident result: the latent twin after pbd_detect_latent
-pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->lat ? h->lat.get() : h; }
-
 int check_examples_state(pbd_handle *h)
 {
     const Resident &r = resident_owner(h)->res;

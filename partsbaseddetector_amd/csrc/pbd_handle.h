@@ -614,6 +614,9 @@ inline bool resident_level(const Resident &r, int frame, int level, int *bf, int
     return true;
 }
 
+// the handle whose buffers hold the resident result: the latent twin after pbd_detect_latent (pbd_examples*, pbd_get_stage)
+inline pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->lat ? h->lat.get() : h; }
+
 // ---- defined in pbd_capi.hip, called from the other files of the entry layer (see the definitions)
 void post_canvas_plan(Plan &M);
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload, int capacity,

@@ -855,16 +855,19 @@ class Handle:
         return out
 
     def get_stage(self, stage: int, frame: int, level: int, rows: int, cols: int):
-        planes = {_lib.STAGE_FEATURES: None, _lib.STAGE_RESPONSES: self.flat.nfilters,
-                  _lib.STAGE_ROOTV: self.flat.ncomponents, _lib.STAGE_ROOTI: self.flat.ncomponents}[stage]
-        if stage == _lib.STAGE_FEATURES:
-            dst = np.empty((rows, cols * self.flat.flen), self.dtype)
-        elif stage == _lib.STAGE_ROOTI:
-            dst = np.empty((planes, rows, cols), np.int32)
-        else:
-            dst = np.empty((planes, rows, cols), self.dtype)
-        self.check(self.lib.pbd_get_stage(self.h, stage, frame, level, dst.ctypes.data, dst.nbytes))
-        return dst
+        """pbd_get_stage: one stage of one level of the resident result.  After detect_latent it is the latent run's, whose
+        responses have one plane per (component, part, mixture) where a detect call's have one per filter: the library refuses a
+        buffer sized for the filters then, and the read is made again with one sized for the mixtures."""
+        nc, totmix = self.flat.ncomponents, int(self.flat.mix_offset[-1])
+        shapes = {_lib.STAGE_FEATURES: [((rows, cols * self.flat.flen), self.dtype)],
+                  _lib.STAGE_RESPONSES: [((n, rows, cols), self.dtype) for n in sorted({self.flat.nfilters, totmix})],
+                  _lib.STAGE_ROOTV: [((nc, rows, cols), self.dtype)], _lib.STAGE_ROOTI: [((nc, rows, cols), np.int32)]}[stage]
+        for k, (shape, dtype) in enumerate(shapes):
+            dst = np.empty(shape, dtype)
+            rc = self.lib.pbd_get_stage(self.h, stage, frame, level, dst.ctypes.data, dst.nbytes)
+            if rc == _lib.PBD_OK or k + 1 == len(shapes) or b"destination holds" not in self.lib.pbd_last_error(self.h):
+                self.check(rc)
+                return dst
 
 
 class HOGFeatures:
