@@ -8,7 +8,9 @@
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
-//   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT
+//   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT.  0 exact, 1 fma,
+//           2 / 3 matrix cores bf16 / fp16 (5x5 banks), 4 fp64 matrix cores (--double), 5 / 6 matrix cores bf16 / fp16 for
+//           every filter size and mixed banks (PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY; not with --double)
 //   --also: one more image (repeatable; same channel count as the first): the first image and every --also image are detected
 //           in ONE detectBatch call, and each image's candidates are printed, in order, as a single run prints them
 //   --depth: a depth map (PGM, 8- or 16-bit, or grey PFM, float; any size): after the candidate lines, one line "box3d x y z height width depth"
@@ -279,7 +281,7 @@ static int dump_model(const Model &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--top n] [--staged] [--stream handles frames] [--conv-mode n] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;

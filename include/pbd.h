@@ -95,10 +95,26 @@ enum { PBD_CONV_MFMA_F64 = 4 };  /* fp64 matrix cores (v_mfma_f64_16x16x4_f64), 
                                 not bit-identical; every filter size the exact path takes; PBD_REAL_F64 only (pbd_create
                                 refuses it for PBD_REAL_F32 with PBD_ERR_UNSUPPORTED) */
 
+enum { PBD_CONV_MFMA_ANY = 5,       /* the arithmetic of PBD_CONV_MFMA for every filter size 1..31 and mixed banks */
+       PBD_CONV_MFMA_F16_ANY = 6 }; /* the arithmetic and the fp16 resident responses of PBD_CONV_MFMA_F16, likewise.
+                                Operands are emulated exactly as in modes 2 / 3.  bf16 mode: every fp32 operand is split
+                                x = hi + lo with round-to-nearest-even and hi*hi + hi*lo + lo*hi is accumulated in fp32 by
+                                v_mfma_f32_32x32x16_bf16.  fp16 mode: every operand is rounded once to fp16, one
+                                v_mfma_f32_32x32x16_f16 per product tile, fp32 accumulation; the response is stored as fp16
+                                and |v| >= 65520 becomes +-inf.  Bound: each response lies within 8 sqrt(n) 2^-24 M of the
+                                float64 sum of the emulated products, n = 3 k k 32 (bf16) or k k 32 (fp16, plus half an fp16
+                                ulp of the result), M = sum |w| |f| over the window, border cells included.  The constant
+                                border is 0, and 1 on channel 31; where M == 0 the response is exactly 0.  One launch per
+                                size class, the filter side a runtime value; an all-5x5 bank runs the kernel and weight
+                                records of modes 2 / 3, so mode 5 equals mode 2 and mode 6 equals mode 3 bit for bit there.
+                                PBD_REAL_F32 only: pbd_create refuses both for PBD_REAL_F64 with PBD_ERR_UNSUPPORTED
+                                (that real type has PBD_CONV_MFMA_F64).  pbd_detect_latent in mode 6 masks with the most negative
+                                finite fp16 value (see there); mode 3 keeps refusing it. */
+
 typedef struct pbd_config {
     int device;            /* HIP device ordinal */
     int real_type;         /* PBD_REAL_F32 (src/demo.cpp:85) or PBD_REAL_F64 (cells/detect.cpp:93) */
-    int conv_mode;         /* PBD_CONV_EXACT / PBD_CONV_FMA / PBD_CONV_MFMA / PBD_CONV_MFMA_F16 / PBD_CONV_MFMA_F64 */
+    int conv_mode;         /* PBD_CONV_EXACT / _FMA / _MFMA / _MFMA_F16 / _MFMA_F64 / _MFMA_ANY / _MFMA_F16_ANY */
     int max_batch;         /* frames per pbd_detect_batch* call (>= 1) */
     int max_candidates;    /* candidate capacity per batch */
     void *stream;          /* hipStream_t to run on (NULL: the library creates its own) */
@@ -622,7 +638,8 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
  * rectangle (src/DynamicProgram.cpp:238-241: xy1 = ((x, y) - (1, 1)) * scale, xy2 = xy1 + size(m) * scale - (1, 1), cvRound;
  * the rectangle of min / max corners) passes inter / (area + barea - inter) > overlap, computed in double with inclusive (+1)
  * areas; otherwise the response is replaced by -1e10 in T (Matlab's -INF, finite: -inf would put NaN into the transform's
- * intersections).  The mask belongs to the (component, part, mixture): the call runs the model with one filter per
+ * intersections).  PBD_CONV_MFMA_F16_ANY, whose responses are fp16, replaces it by -65504, the most negative finite fp16 value,
+ * and reports found[f] = 1 iff the score > -32752: right as long as the unmasked terms of a root sum to less than 32752.  The mask belongs to the (component, part, mixture): the call runs the model with one filter per
  * (component, part, mixture) (filter ids shared by several parts are copied), the sequential schedule of shared ids does not
  * apply, and the detect path of the handle is not touched.  Output per frame f: cand + f * pbd_candidate_stride() = the single
  * highest-scoring root over all levels, components and positions (ties: the first in (level, component, y, x) order), as a
@@ -632,7 +649,8 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
  * the MASKED responses, one plane per (component, part, mixture) in global mixture order; PBD_STAGE_ROOTV / _ROOTI are the
  * dynamic program's on them and PBD_STAGE_FEATURES the frames' features.  pbd_argmin_device_out / pbd_dp_argmin see no result
  * until the next detect call.  pbd_set_nms does not apply.
- * PBD_ERR_UNSUPPORTED: components with different part counts, level sharding (world > 1), PBD_CONV_MFMA_F16.
+ * PBD_ERR_UNSUPPORTED: components with different part counts, level sharding (world > 1), PBD_CONV_MFMA_F16 (mode 3; mode 6,
+ * PBD_CONV_MFMA_F16_ANY, is taken as said above).
  * PBD_ERR_INVALID: a NaN overlap, and the frame refusals of pbd_detect_frames.  PBD_ERR_STATE while a batch is in flight. */
 int pbd_detect_latent(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
                       const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found);

@@ -601,7 +601,8 @@ class PartsBasedDetector {
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
     // conv_mode: the convolution of every handle distributeModel() creates (PBD_CONV_*, include/pbd.h); new surface, the
-    // reference has only its exact convolution
+    // reference has only its exact convolution.  T = float: every mode but PBD_CONV_MFMA_F64 (PBD_CONV_MFMA / _F16 for all-5x5
+    // models, PBD_CONV_MFMA_ANY / _F16_ANY for any filter sizes); T = double: PBD_CONV_EXACT, PBD_CONV_FMA, PBD_CONV_MFMA_F64
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),

@@ -20,6 +20,8 @@ REAL_F32, REAL_F64 = 0, 1
 CONV_EXACT, CONV_FMA, CONV_MFMA, CONV_MFMA_F16 = 0, 1, 2, 3
 WALK_REFERENCE, WALK_ARGMAX = 0, 1   # pbd_set_walk
 CONV_MFMA_F64 = 4          # fp64 matrix cores, REAL_F64 handles only (include/pbd.h)
+CONV_MFMA_ANY = 5          # CONV_MFMA's arithmetic for every filter size 1..31 and mixed banks, REAL_F32 handles only
+CONV_MFMA_F16_ANY = 6      # CONV_MFMA_F16's arithmetic and fp16 resident responses, likewise
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
 # options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
 DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpbd_hip.so")
 SOURCES = ["pbd_capi.hip", "pbd_capi_post.hip", "pbd_capi_train.hip", "pbd_kernels_features.hip", "pbd_kernels_conv.hip",
-           "pbd_kernels_conv_mfma.hip", "pbd_kernels_conv_mfma_f64.hip", "pbd_kernels_dp.hip", "pbd_kernels_post.hip",
+           "pbd_kernels_conv_mfma.hip", "pbd_kernels_conv_mfma_f64.hip", "pbd_kernels_conv_mfma_any.hip", "pbd_kernels_dp.hip", "pbd_kernels_post.hip",
            "pbd_kernels_depth.hip", "pbd_kernels_cloud.hip", "pbd_kernels_planes.hip", "pbd_kernels_consistency.hip",
            "pbd_kernels_publish.hip", "pbd_kernels_examples.hip", "pbd_kernels_qp.hip", "pbd_kernels_model.hip",
            "pbd_kernels_warp.hip", "pbd_kernels_eval.hip", "pbd_kernels_kmeans.hip"]

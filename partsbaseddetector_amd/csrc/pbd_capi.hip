@@ -557,8 +557,9 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
         if (std::find(sizes.begin(), sizes.end(), ksize[f]) == sizes.end()) sizes.push_back(ksize[f]);
     const int K = ksize[0];
     const bool fast = (sizeof(R) == 4 && K == 5 && sizes.size() == 1);
-    const bool mfma = h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16;
-    if (mfma && !fast) return fail(h, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA / PBD_CONV_MFMA_F16 need 5x5 filters and PBD_REAL_F32");
+    const bool mfma = conv_is_matrix_f32(h->cfg.conv_mode), any = conv_is_any(h->cfg.conv_mode), f16 = conv_is_f16(h->cfg.conv_mode);
+    if (mfma && !any && !fast) return fail(h, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA / PBD_CONV_MFMA_F16 need 5x5 filters and PBD_REAL_F32");
+    const bool frags = any && !fast;     // (float handles only: pbd_create refuses the modes for PBD_REAL_F64) per-class A-fragments of k_conv_mfma_any; an all-5x5 bank keeps the records of modes 2 / 3
     // The new bank is built beside the old one and moved in only when every upload has succeeded: a failed setFilters()
     // (out of memory, an unsupported size) leaves the handle with its previous, complete bank.
     std::vector<pbd_handle::ConvClass> classes(sizes.size());
@@ -635,10 +636,23 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             HIPCHK(h, C.wfrag64.ensure(wf.size() * sizeof(double)));
             HIPCHK(h, hipMemcpy(C.wfrag64.p, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice));
         }
+        if (frags) {
+            // 16-bit A-fragments in the order k_conv_mfma_any reads them (any_frag_source), rounded as the records of modes
+            // 2 / 3 are (wrec_value); pad taps and filters past nf stay zero
+            const int NV = f16 ? 1 : 2, CB = conv_mfma_any_cb(C.K, f16);
+            HIPCHK(h, conv_mfma_any_prepare());
+            std::vector<uint16_t> wf((size_t)any_frag_size(KK, CB, NV, C.nf), 0);
+            for (size_t o = 0; o < wf.size(); ++o) {
+                int part = 0;
+                const WeightSrc s = any_frag_source((long long)o, KK, CB, NV, C.nf, &part);
+                if (s.f >= 0) wf[o] = wrec_value((float)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)], f16, part);
+            }
+            HIPCHK(h, C.wfrag16.ensure(wf.size() * 2));
+            HIPCHK(h, hipMemcpy(C.wfrag16.p, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
+        }
     }
     const int Fpad = (nfilters + kConvQ - 1) / kConvQ * kConvQ;
-    if (mfma) {
-        const bool f16 = h->cfg.conv_mode == PBD_CONV_MFMA_F16;
+    if (mfma && !frags) {
         // bf16 mode: x = hi + lo with round-to-nearest-even; fp16 mode: one rounding (wrec_value).  A-operand fragments in the
         // order the kernel consumes them (wrec_source)
         const int NV = f16 ? 1 : 2;
@@ -1033,7 +1047,7 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
     cp.shaped = P.d_shaped.p;
     for (int k = 0; k < 3; ++k) cp.nshaped[k] = P.nshaped[k];
     cp.segtiles = nullptr; cp.nsegtiles = 0;
-    if (!h->f64 && h->cfg.conv_mode != PBD_CONV_MFMA && h->cfg.conv_mode != PBD_CONV_MFMA_F16) {
+    if (!h->f64 && !conv_is_matrix_f32(h->cfg.conv_mode)) {
         const auto it = P.segtiles.find(nb);     // built by ensure_seg_tiles before the first launch of this many frames
         if (it != P.segtiles.end()) { cp.segtiles = it->second.p; cp.nsegtiles = (int)it->second.size; }
     }
@@ -1061,8 +1075,10 @@ void launch_conv_stage(pbd_handle *h, Plan &P, int f0, int nb, hipStream_t st)
         cp.unit_f0 = C.unit_f0.p; cp.unit_ql = C.unit_ql.p; cp.unit_woff = C.unit_woff.p; cp.nunits = C.nunits;
         cp.c31tab = C.c31tab.p; cp.c31stride = C.c31stride;
         cp.units_per_block = wgs >= 1024 ? std::max(C.nunits, 1) : std::max(1, (int)((long long)C.nunits * wgs / 1024));
-        if (h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16)
-            launch_conv_mfma(cp, h->d_wrec.p, h->cfg.conv_mode == PBD_CONV_MFMA_F16, nb, st);
+        if (conv_is_matrix_f32(h->cfg.conv_mode) && C.wfrag16.p)
+            launch_conv_mfma_any(cp, C.wfrag16.p, conv_is_f16(h->cfg.conv_mode), nb, st);
+        else if (conv_is_matrix_f32(h->cfg.conv_mode))
+            launch_conv_mfma(cp, h->d_wrec.p, conv_is_f16(h->cfg.conv_mode), nb, st);
         else if (h->cfg.conv_mode == PBD_CONV_MFMA_F64) launch_conv_mfma_f64(cp, C.wfrag64.as<double>(), nb, st);
         else launch_conv(cp, nb, h->f64, st);
     }
@@ -1575,7 +1591,7 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     if (mask) {   // pbd_detect_latent: the responses of the latent bank, masked before the dynamic program
         LatentParams lp = *mask;
         lp.resp = h->resp.p; lp.lv = P.d_lv.p; lp.nlevels = P.nlevels; lp.F = h->F; lp.cell_per_frame = P.cell_per_frame;
-        lp.lv_frame = P.d_lv_frame.p; lp.scales = P.d_scales.p;
+        lp.lv_frame = P.d_lv_frame.p; lp.scales = P.d_scales.p; lp.resp_half = h->resp_half ? 1 : 0;
         launch_latent_mask(lp, h->f64, h->stream);
         HIPCHK(h, hipGetLastError());
     }
@@ -1627,6 +1643,13 @@ extern "C" {
 const char *pbd_version(void) { return "pbd-hip 0.1 (gfx950)"; }
 
 // diagnostics, not part of include/pbd.h
+// k_conv_mfma_any at filter side `ksize`: what = 0 resident workgroups per CU, 1 LDS bytes per workgroup, 2 channels per staged block
+int pbd_debug_conv_any(int ksize, int f16, int what)
+{
+    if (ksize < 1 || ksize > kConvMaxK) return -1;
+    const int cb = conv_mfma_any_cb(ksize, f16 != 0);
+    return what == 0 ? conv_mfma_any_occupancy(ksize, f16 != 0) : what == 1 ? (int)conv_mfma_any_lds(ksize, cb, f16 != 0) : cb;
+}
 int pbd_debug_conv_occupancy(int nw) { return nw == 5 ? conv_mfma_occupancy(false) : nw == 6 ? conv_mfma_occupancy(true) : conv_occupancy(nw); }
 // the convolution's tile cover of one rows x cols level (host-only, no GPU needed): out[i] = {shape, y0, x0}
 int pbd_debug_cover_level(int rows, int cols, int *out, int capacity)
@@ -1777,6 +1800,8 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
             return fail(nullptr, PBD_ERR_UNSUPPORTED, "real_type %d: PBD_REAL_F32 or PBD_REAL_F64", config->real_type);
         if (config->conv_mode == PBD_CONV_MFMA_F64 && config->real_type != PBD_REAL_F64)
             return fail(nullptr, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA_F64 needs PBD_REAL_F64 (fp64 operands and accumulation)");
+        if (conv_is_any(config->conv_mode) && config->real_type != PBD_REAL_F32)
+            return fail(nullptr, PBD_ERR_UNSUPPORTED, "PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY need PBD_REAL_F32; PBD_REAL_F64 has PBD_CONV_MFMA_F64");
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev < 1)
@@ -1790,7 +1815,7 @@ int pbd_create(const pbd_model *model, const pbd_config *config, pbd_handle **ou
         h->device = config->device;
         h->f64 = config->real_type == PBD_REAL_F64;
         h->rs = h->f64 ? sizeof(double) : sizeof(float);
-        h->resp_half = config->conv_mode == PBD_CONV_MFMA_F16 && !h->f64;
+        h->resp_half = conv_is_f16(config->conv_mode) && !h->f64;
         h->resp_es = h->resp_half ? 2 : h->rs;
         if (h->cfg.max_batch < 1) h->cfg.max_batch = 1;
         if (h->cfg.max_candidates < 1) h->cfg.max_candidates = 65536;

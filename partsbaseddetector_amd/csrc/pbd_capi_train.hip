@@ -111,7 +111,7 @@ void mu_enqueue(pbd_handle *h, const MuSource &src, char *status, bool check, hi
     if (check) launch_mu_check(p, src, st);
     launch_mu_vector(p, src, h->f64, st);
     launch_mu_tables(p, h->f64, st);
-    const bool mfma = h->cfg.conv_mode == PBD_CONV_MFMA || h->cfg.conv_mode == PBD_CONV_MFMA_F16;
+    const bool mfma = conv_is_matrix_f32(h->cfg.conv_mode), f16 = conv_is_f16(h->cfg.conv_mode);
     for (pbd_handle::ConvClass &C : h->conv_classes) {
         MuClassParams cp{};
         cp.refused = p.refused; cp.mvec = p.mvec; cp.foff = p.foff; cp.fmap = C.fmap.p;
@@ -121,7 +121,8 @@ void mu_enqueue(pbd_handle *h, const MuSource &src, char *status, bool check, hi
         cp.nunits = C.nunits;
         cp.c31tab = C.c31tab.p; cp.c31stride = C.c31stride;
         cp.wfrag64 = C.wfrag64.as<double>(); cp.qn = cp.wfrag64 ? conv_mfma_f64_qn(C.K) : 0;
-        if (mfma) { cp.wrec = h->d_wrec.as<uint16_t>(); cp.wrec_f16 = h->cfg.conv_mode == PBD_CONV_MFMA_F16; cp.nfilters = h->F; }
+        if (mfma) { cp.wrec = h->d_wrec.as<uint16_t>(); cp.wrec_f16 = f16; cp.nfilters = h->F; }
+        if (mfma && C.wfrag16.p) { cp.wfrag16 = C.wfrag16.as<uint16_t>(); cp.any_cb = conv_mfma_any_cb(C.K, f16); }
         launch_mu_class(cp, h->f64, st);
     }
 }
@@ -458,7 +459,9 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
             if (h->part_offset[c + 1] - h->part_offset[c] != nparts)
                 return fail(h, PBD_ERR_UNSUPPORTED, "latent detection needs one part count in every component (component %d has %d, "
                             "component 0 %d)", c, h->part_offset[c + 1] - h->part_offset[c], nparts);
-        if (h->resp_half) return fail(h, PBD_ERR_UNSUPPORTED, "latent detection in PBD_CONV_MFMA_F16: -1e10 has no fp16 value");
+        // (PBD_CONV_MFMA_F16_ANY masks its fp16 responses with the most negative finite half, kLatentMaskHalf)
+        if (h->resp_half && !conv_is_any(h->cfg.conv_mode))
+            return fail(h, PBD_ERR_UNSUPPORTED, "latent detection in PBD_CONV_MFMA_F16: -1e10 has no fp16 value");
         if (std::isnan(overlap)) return fail(h, PBD_ERR_INVALID, "overlap is NaN");
         if (int rc = check_bank(h)) return rc;
         if (h->filter_ksize != h->model_ksize) return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's");
@@ -523,7 +526,7 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
         for (int f = 0; f < nframes; ++f) {
             float sc;
             memcpy(&sc, &cand[(size_t)f * stride + 5], sizeof sc);
-            found[f] = sc > -5e9f ? 1 : 0;
+            found[f] = sc > (h->resp_half ? kLatentFoundHalf : -5e9f) ? 1 : 0;
         }
         return PBD_OK;
     });

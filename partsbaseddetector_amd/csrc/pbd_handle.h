@@ -343,6 +343,8 @@ struct Handle : ErrCtx {
         DevTable<float> c31tab;      // [81][c31stride]: see pbd_kernels_conv.hip (channel 31)
         int c31stride = 0;
         DevBuf wfrag64;              // PBD_CONV_MFMA_F64: the class's A-fragments (pbd_internal.h, f64_passes)
+        DevBuf wfrag16;              // PBD_CONV_MFMA_ANY / _F16_ANY: the class's 16-bit A-fragments (any_frag_source); empty for
+                                     // an all-5x5 bank, which keeps the records of modes 2 / 3 (d_wrec)
     };
     std::vector<ConvClass> conv_classes;
     DevBuf d_wrec;                   // bf16 hi/lo weight records of the matrix-core path
@@ -354,7 +356,7 @@ struct Handle : ErrCtx {
     int coord_n = 0;
     bool f64 = false;                // reference template parameter T = double
     size_t rs = sizeof(float);       // sizeof(T)
-    bool resp_half = false;          // PBD_CONV_MFMA_F16: the responses live on the device as fp16 (BASELINE configs[4])
+    bool resp_half = false;          // conv_is_f16(mode): the responses live on the device as fp16 (BASELINE configs[4])
     size_t resp_es = sizeof(float);  // bytes per response element on the device
 
     // plans

@@ -479,6 +479,31 @@ inline int f64_passes(int mtiles) { return (mtiles + kF64MaxMB - 1) / kF64MaxMB;
 int conv_mfma_f64_qn(int ksize);
 size_t conv_mfma_f64_lds(int ksize, int qn);
 void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes, hipStream_t s);
+// PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY (pbd_kernels_conv_mfma_any.hip): the float matrix-core path for any filter side, one
+// launch per size class.  wfrag: the class's A-fragments in the order of any_frag_source (pbd_layout.h).  The haloed 32 x 8
+// tile is staged in blocks of conv_mfma_any_cb() channels: the largest of 32 / 16 / 8 whose tile fits kAnyLdsTarget (two
+// workgroups per CU); 8 channels of the widest filter take 113 KB (bf16) and leave one.
+constexpr size_t kAnyLdsTarget = 80 * 1024;
+constexpr int kAnyMaxDevices = 64;
+inline size_t conv_mfma_any_lds(int ksize, int cb, bool f16)
+{
+    return (size_t)(kConvTW + ksize - 1) * (kConvTH + ksize - 1) * (cb * (f16 ? 2 : 4) + 16);
+}
+inline int conv_mfma_any_cb(int ksize, bool f16)
+{
+    int cb = 32;
+    while (cb > 8 && conv_mfma_any_lds(ksize, cb, f16) > kAnyLdsTarget) cb /= 2;
+    return cb;
+}
+static_assert((size_t)(kConvTW + kConvMaxK - 1) * (kConvTH + kConvMaxK - 1) * (8 * 4 + 16) <= 160 * 1024,
+              "8 channels of the widest filter's tile fit the CU's LDS");
+int conv_mfma_any_occupancy(int ksize, bool f16);
+hipError_t conv_mfma_any_prepare();   // the kernels' dynamic LDS limit on the current device, once; before the first launch
+void launch_conv_mfma_any(const ConvParams &p, const void *wfrag, bool f16, int nframes, hipStream_t s);
+// the convolution modes by what they imply (every site that used to compare with the enum values asks these)
+inline bool conv_is_f16(int mode) { return mode == PBD_CONV_MFMA_F16 || mode == PBD_CONV_MFMA_F16_ANY; }        // fp16 operands and resident responses
+inline bool conv_is_matrix_f32(int mode) { return mode == PBD_CONV_MFMA || mode == PBD_CONV_MFMA_ANY || conv_is_f16(mode); }   // float handle, matrix cores
+inline bool conv_is_any(int mode) { return mode == PBD_CONV_MFMA_ANY || mode == PBD_CONV_MFMA_F16_ANY; }         // every filter size
 // the distance-transform passes' launch choices a handle may force (pbd_debug_set_option); the defaults decide per launch
 struct DtOptions {
     int lane_shift = -1;          // 0..6: 64 >> lane_shift rows (columns) per wave; -1: by the launch's size
@@ -644,6 +669,7 @@ struct LatentParams {
     long long cell_per_frame;
     const int *lv_frame;          // virtual level -> frame of the call
     const float *scales;          // [nlevels]
+    int resp_half;                // resp holds fp16 (conv_is_f16): the mask value is kLatentMaskHalf
     const int4 *gmtab;            // [F] {part index in its component, mixture, filter size, -}
     const int4 *boxes;            // [nframes][nparts] ground truth {x1, y1, x2, y2}, inclusive
     const int *mix;               // [nframes][nparts] fixed mixture or -1 (NULL: all free)
@@ -655,6 +681,9 @@ struct LatentParams {
     int nframes, NC, stride;
     int32_t *payload;             // word 0 = nframes, then one record per frame (as k_argmin_emit writes them, for the walk)
 };
+// A masked response is -1e10 in T (Matlab's -INF, finite).  fp16 resident responses hold the most negative finite half instead;
+// a root score that uses a masked term is then below kLatentFoundHalf as long as its other terms sum to less than 32752.
+constexpr float kLatentMaskHalf = -65504.0f, kLatentFoundHalf = -32752.0f;
 void launch_latent_mask(const LatentParams &p, bool f64, hipStream_t s);
 void launch_latent_best(const LatentParams &p, bool f64, hipStream_t s);
 
@@ -796,6 +825,7 @@ struct MuClassParams {            // one size class of the bank
     float *c31tab; int c31stride;
     double *wfrag64; int qn;
     uint16_t *wrec; int wrec_f16, nfilters;   // the matrix-core records (one class, filter ids in order)
+    uint16_t *wfrag16; int any_cb;            // PBD_CONV_MFMA_*_ANY: the class's A-fragments, their channel block (wrec_f16: fp16)
 };
 void launch_mu_check(const MuParams &p, const MuSource &src, hipStream_t s);
 void launch_mu_vector(const MuParams &p, const MuSource &src, bool f64, hipStream_t s);   // mvec, the status block's values

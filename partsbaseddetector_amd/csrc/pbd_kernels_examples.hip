@@ -148,8 +148,9 @@ __global__ __launch_bounds__(64 * kExGatherWaves) void k_ex_gather(ExampleParams
 // ---- latent positives (pbd_detect_latent) --------------------------------------------------------------------------------
 // one thread per response value of the latent bank: the plane of (part p, mixture m) at (x, y) of level l keeps its value only
 // when m is allowed and the part's record rectangle (src/DynamicProgram.cpp:238-241) overlaps the frame's box of part p by more
-// than `overlap` (testoverlap: inclusive areas, in double); otherwise it becomes -1e10 (Matlab's -INF, finite)
-template <typename R>
+// than `overlap` (testoverlap: inclusive areas, in double); otherwise it becomes -1e10 (Matlab's -INF, finite), or
+// kLatentMaskHalf where the responses are fp16 (RH)
+template <typename R, bool RH = false>
 __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
 {
     const long long total = p.cell_per_frame * p.F;
@@ -175,7 +176,10 @@ __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
             const double barea = (double)((long long)b.z - b.x + 1) * (double)((long long)b.w - b.y + 1);
             keep = inter / (area + barea - inter) > p.overlap;
         }
-        if (!keep) static_cast<R *>(p.resp)[o] = (R)-1e10;
+        if (!keep) {
+            if constexpr (RH) static_cast<_Float16 *>(p.resp)[o] = (_Float16)kLatentMaskHalf;
+            else static_cast<R *>(p.resp)[o] = (R)-1e10;
+        }
     }
 }
 
@@ -219,6 +223,7 @@ void launch_latent_mask(const LatentParams &p, bool f64, hipStream_t s)
     const long long total = p.cell_per_frame * p.F;
     const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((total + 255) / 256, 65536)));
     if (f64) PBD_LAUNCH(k_latent_mask<double>, grid, dim3(256), 0, s, p);
+    else if (p.resp_half) PBD_LAUNCH((k_latent_mask<float, true>), grid, dim3(256), 0, s, p);
     else PBD_LAUNCH(k_latent_mask<float>, grid, dim3(256), 0, s, p);
 }
 

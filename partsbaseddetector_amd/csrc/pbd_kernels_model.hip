@@ -133,6 +133,18 @@ __global__ __launch_bounds__(kB) void k_mu_wrec(MuClassParams p)
     if (s.f >= 0) p.wrec[i] = wrec_value(mu_weight<float>(p, s), p.wrec_f16 != 0, part);
 }
 
+// the A-fragments of one size class of PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY (pad slots stay zero)
+__global__ __launch_bounds__(kB) void k_mu_wfrag16(MuClassParams p)
+{
+    if (*p.refused) return;
+    const int KK = p.K * p.K, NV = p.wrec_f16 ? 1 : 2;
+    const long long i = (long long)blockIdx.x * kB + threadIdx.x;
+    if (i >= any_frag_size(KK, p.any_cb, NV, p.nf)) return;
+    int part = 0;
+    const WeightSrc s = any_frag_source(i, KK, p.any_cb, NV, p.nf, &part);
+    if (s.f >= 0) p.wfrag16[i] = wrec_value(mu_weight<float>(p, s), p.wrec_f16 != 0, part);
+}
+
 inline dim3 blocks(long long n) { return dim3((unsigned)((n + kB - 1) / kB)); }
 
 }  // namespace
@@ -186,7 +198,9 @@ template <typename R> static void launch_mu_class_t(const MuClassParams &p, hipS
 void launch_mu_class(const MuClassParams &p, bool f64, hipStream_t s)
 {
     if (f64) launch_mu_class_t<double>(p, s); else launch_mu_class_t<float>(p, s);
-    if (p.wrec && !f64 && p.nfilters > 0)
+    if (p.wfrag16 && !f64 && p.nf > 0)
+        PBD_LAUNCH(k_mu_wfrag16, blocks(any_frag_size(p.K * p.K, p.any_cb, p.wrec_f16 ? 1 : 2, p.nf)), dim3(kB), 0, s, p);
+    else if (p.wrec && !f64 && p.nfilters > 0)
         PBD_LAUNCH(k_mu_wrec, blocks(wrec_size(p.K * p.K, p.wrec_f16 ? 1 : 2, p.nfilters)), dim3(kB), 0, s, p);
 }
 

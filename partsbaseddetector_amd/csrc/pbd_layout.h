@@ -95,6 +95,45 @@ PBD_HD inline WeightSrc wrec_source(long long i, int KK, int NV, int nfilters, i
     return WeightSrc{f < nfilters ? f : -1, t, kh * 16 + (lane >> 5) * 8 + j};
 }
 
+// PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY: the 16-bit A-fragments of ONE size class of nf filters (any side), mtiles =
+// ceil(nf / 32) M-tiles in any_passes() passes split as f64_pass_begin splits them.  The kernel stages the features in blocks
+// of CB = 32, 16 or 8 channels; one STEP is one 16-deep k-slice of v_mfma_f32_32x32x16: a tap x 16 channels (CB >= 16), or two
+// taps x 8 channels (CB = 8; the second tap of the last step is a pad when KK is odd).  Order:
+// [pass][channel block][step][M-tile of the pass][hi | lo][lane][8]; lane (r = lane & 31, hh = lane >> 5) holds class-local
+// filter (M-tile) * 32 + r and
+//   CB = 32: tap step / 2, channels (step & 1) * 16 + hh * 8 .. + 7          (2 KK steps)
+//   CB = 16: tap step,     channels cb * 16 + hh * 8 .. + 7                  (KK steps per block)
+//   CB =  8: tap 2 step + hh, channels cb * 8 .. + 7                         (ceil(KK / 2) steps per block)
+// NV = 2 values per weight (bf16 hi, lo) or 1 (fp16); *part = 0: hi (or the fp16 value), 1: lo.
+constexpr int kAnyMaxMB = 4;
+PBD_HD inline int any_passes(int mtiles) { return (mtiles + kAnyMaxMB - 1) / kAnyMaxMB; }
+PBD_HD inline int any_steps(int KK, int CB) { return CB == 32 ? 2 * KK : CB == 16 ? KK : (KK + 1) / 2; }
+PBD_HD inline long long any_frag_size(int KK, int CB, int NV, int nf)
+{
+    return (long long)((nf + 31) / 32) * (32 / CB) * any_steps(KK, CB) * NV * 64 * 8;
+}
+PBD_HD inline WeightSrc any_frag_source(long long i, int KK, int CB, int NV, int nf, int *part)
+{
+    const int mtiles = (nf + 31) / 32, passes = any_passes(mtiles), steps = any_steps(KK, CB);
+    const long long per_tile = (long long)(32 / CB) * steps * NV * 64 * 8;
+    const int mi = (int)(i / per_tile);
+    int ps = 0;
+    while (ps + 1 < passes && f64_pass_begin(ps + 1, mtiles, passes) <= mi) ++ps;
+    const int m0 = f64_pass_begin(ps, mtiles, passes), mb = f64_pass_begin(ps + 1, mtiles, passes) - m0;
+    long long r = i - m0 * per_tile;
+    const int j = (int)(r % 8); r /= 8;
+    const int lane = (int)(r % 64); r /= 64;
+    *part = (int)(r % NV); r /= NV;
+    const int m = (int)(r % mb); r /= mb;
+    const int s = (int)(r % steps), cb = (int)(r / steps);
+    const int hh = lane >> 5, fl = (m0 + m) * 32 + (lane & 31);
+    int t, c;
+    if (CB == 32) { t = s >> 1; c = (s & 1) * 16 + hh * 8 + j; }
+    else if (CB == 16) { t = s; c = cb * 16 + hh * 8 + j; }
+    else { t = 2 * s + hh; c = cb * 8 + j; }
+    return WeightSrc{fl < nf && t < KK ? fl : -1, t < KK ? t : 0, c};
+}
+
 // ---- the 16-bit roundings of those records (integer arithmetic: the same bits on the host and on the device) ---------------
 PBD_HD inline uint32_t f32_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 PBD_HD inline float bits_f32(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
