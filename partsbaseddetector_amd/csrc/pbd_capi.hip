@@ -9,6 +9,8 @@
 // There is no CPU compute path: every stage runs as a HIP kernel (pbd_kernels_*.hip).
 #include "pbd_handle.h"
 
+#include <mutex>
+
 using namespace pbd;
 
 namespace pbd {
@@ -545,6 +547,35 @@ void conv_units(int nf, int nw, std::vector<int> &f0, std::vector<int> &ql)
     if (bc) { f0.push_back(f); ql.push_back(2 * bc); f += 2 * bc; }
 }
 
+// The dynamic-LDS limit of every convolution kernel that asks for more than the default (the six k_conv_mfma_any and the three
+// k_conv_mfma_f64 variants), raised on the CURRENT device: hipFuncSetAttribute acts on that device's copy of a kernel.  Once per
+// device and process, never per launch (handles launch concurrently), and before any launch: upload_filters_t calls it and
+// reports a failure as its own.
+static hipError_t conv_prepare_device()
+{
+    constexpr int kMaxDevices = 64;
+    static std::once_flag once[kMaxDevices];
+    static hipError_t result[kMaxDevices];
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;   // (more devices than the flag table holds)
+    std::call_once(once[dev], [dev] {
+        const hipError_t e = conv_mfma_any_set_lds_limits();
+        result[dev] = e ? e : conv_mfma_f64_set_lds_limits();
+    });
+    return result[dev];
+}
+
+// One packed weight table: n entries, entry i = value(i) (a gather from its layout definition, pbd_layout.h), to `buf`
+template <typename V, typename Fn>
+hipError_t upload_table(DevBuf &buf, long long n, Fn &&value)
+{
+    std::vector<V> tab((size_t)n);
+    for (size_t i = 0; i < tab.size(); ++i) tab[i] = value((long long)i);
+    if (hipError_t e = buf.ensure(tab.size() * sizeof(V))) return e;
+    return hipMemcpy(buf.p, tab.data(), tab.size() * sizeof(V), hipMemcpyHostToDevice);
+}
+
 template <typename R>
 int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, const int *ksize)
 {
@@ -627,28 +658,24 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
             // A-fragments in the order k_conv_mfma_f64 reads them (f64_frag_source: lane group g supplies channels g QN ..
             // g QN + QN - 1 of its cell); filters past nf are zero
             const int QN = conv_mfma_f64_qn(C.K);
-            const int mtiles = (C.nf + 15) / 16, passes = f64_passes(mtiles);
-            std::vector<double> wf((size_t)f64_frag_size(KK, mtiles), 0.0);
-            for (size_t o = 0; o < wf.size(); ++o) {
-                const WeightSrc s = f64_frag_source((long long)o, KK, QN, mtiles, passes, C.nf);
-                if (s.f >= 0) wf[o] = (double)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)];
-            }
-            HIPCHK(h, C.wfrag64.ensure(wf.size() * sizeof(double)));
-            HIPCHK(h, hipMemcpy(C.wfrag64.p, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice));
+            const int mtiles = (C.nf + 15) / 16, passes = mfma_passes(mtiles);
+            HIPCHK(h, conv_prepare_device());
+            HIPCHK(h, upload_table<double>(C.wfrag64, f64_frag_size(KK, mtiles), [&](long long o) {
+                const WeightSrc s = f64_frag_source(o, KK, QN, mtiles, passes, C.nf);
+                return s.f >= 0 ? (double)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)] : 0.0;
+            }));
         }
         if (frags) {
             // 16-bit A-fragments in the order k_conv_mfma_any reads them (any_frag_source), rounded as the records of modes
             // 2 / 3 are (wrec_value); pad taps and filters past nf stay zero
             const int NV = f16 ? 1 : 2, CB = conv_mfma_any_cb(C.K, f16);
-            HIPCHK(h, conv_mfma_any_prepare());
-            std::vector<uint16_t> wf((size_t)any_frag_size(KK, CB, NV, C.nf), 0);
-            for (size_t o = 0; o < wf.size(); ++o) {
+            HIPCHK(h, conv_prepare_device());
+            HIPCHK(h, upload_table<uint16_t>(C.wfrag16, any_frag_size(KK, CB, NV, C.nf), [&](long long o) {
                 int part = 0;
-                const WeightSrc s = any_frag_source((long long)o, KK, CB, NV, C.nf, &part);
-                if (s.f >= 0) wf[o] = wrec_value((float)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)], f16, part);
-            }
-            HIPCHK(h, C.wfrag16.ensure(wf.size() * 2));
-            HIPCHK(h, hipMemcpy(C.wfrag16.p, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
+                const WeightSrc s = any_frag_source(o, KK, CB, NV, C.nf, &part);
+                if (s.f < 0) return (uint16_t)0;
+                return wrec_value((float)static_cast<const R *>(filters[ids[s.f]])[weight_at(s)], f16, part);
+            }));
         }
     }
     const int Fpad = (nfilters + kConvQ - 1) / kConvQ * kConvQ;
@@ -656,14 +683,11 @@ int upload_filters_t(pbd_handle *h, int nfilters, const void *const *filters, co
         // bf16 mode: x = hi + lo with round-to-nearest-even; fp16 mode: one rounding (wrec_value).  A-operand fragments in the
         // order the kernel consumes them (wrec_source)
         const int NV = f16 ? 1 : 2;
-        std::vector<uint16_t> rec((size_t)wrec_size(K * K, NV, nfilters), 0);
-        for (size_t i = 0; i < rec.size(); ++i) {
+        HIPCHK(h, upload_table<uint16_t>(wrec, wrec_size(K * K, NV, nfilters), [&](long long i) {
             int part = 0;
-            const WeightSrc s = wrec_source((long long)i, K * K, NV, nfilters, &part);
-            if (s.f >= 0) rec[i] = wrec_value(reinterpret_cast<const float *>(filters[s.f])[weight_at(s)], f16, part);
-        }
-        HIPCHK(h, wrec.ensure(rec.size() * 2));
-        HIPCHK(h, hipMemcpy(wrec.p, rec.data(), rec.size() * 2, hipMemcpyHostToDevice));
+            const WeightSrc s = wrec_source(i, K * K, NV, nfilters, &part);
+            return s.f >= 0 ? wrec_value(reinterpret_cast<const float *>(filters[s.f])[weight_at(s)], f16, part) : (uint16_t)0;
+        }));
     }
     // commit
     h->conv_classes = std::move(classes);

@@ -342,7 +342,7 @@ struct Handle : ErrCtx {
         int nunits = 0;
         DevTable<float> c31tab;      // [81][c31stride]: see pbd_kernels_conv.hip (channel 31)
         int c31stride = 0;
-        DevBuf wfrag64;              // PBD_CONV_MFMA_F64: the class's A-fragments (pbd_internal.h, f64_passes)
+        DevBuf wfrag64;              // PBD_CONV_MFMA_F64: the class's A-fragments (pbd_layout.h, f64_frag_source)
         DevBuf wfrag16;              // PBD_CONV_MFMA_ANY / _F16_ANY: the class's 16-bit A-fragments (any_frag_source); empty for
                                      // an all-5x5 bank, which keeps the records of modes 2 / 3 (d_wrec)
     };

@@ -469,13 +469,11 @@ int conv_mfma_occupancy(bool f16);
 // PBD_CONV_MFMA_F16: 80 B fp16 records, one MFMA per product tile
 void launch_conv_mfma(const ConvParams &p, const void *wrec, bool f16, int nframes, hipStream_t s);
 constexpr int kMfmaFilterBlock = kWrecFilterBlock, kMfmaRecBytes = 144, kMfmaRecBytesF16 = 80;
-// PBD_CONV_MFMA_F64 (pbd_kernels_conv_mfma_f64.hip).  A size class of nf filters is ceil(nf / 16) M-tiles, split into
-// f64_passes() passes (grid y) of at most kF64MaxMB M-tiles; pass i covers M-tiles [f64_pass_begin(i), f64_pass_begin(i + 1)).
+// PBD_CONV_MFMA_F64 (pbd_kernels_conv_mfma_f64.hip).  A size class of nf filters is ceil(nf / 16) M-tiles, split into passes
+// (grid y) by the pass rule of pbd_layout.h (mfma_passes, mfma_pass_begin).
 // wfrag: the class's A-fragments in the order of f64_frag_source (pbd_layout.h); the channel block of a filter size is
 // conv_mfma_f64_qn(): 4 * qn channels per block
-constexpr int kF64MaxMB = 4;
 constexpr size_t kF64LdsTarget = 80 * 1024;   // haloed tile per workgroup: two workgroups per CU (160 KB of LDS)
-inline int f64_passes(int mtiles) { return (mtiles + kF64MaxMB - 1) / kF64MaxMB; }
 int conv_mfma_f64_qn(int ksize);
 size_t conv_mfma_f64_lds(int ksize, int qn);
 void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes, hipStream_t s);
@@ -484,7 +482,6 @@ void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes,
 // tile is staged in blocks of conv_mfma_any_cb() channels: the largest of 32 / 16 / 8 whose tile fits kAnyLdsTarget (two
 // workgroups per CU); 8 channels of the widest filter take 113 KB (bf16) and leave one.
 constexpr size_t kAnyLdsTarget = 80 * 1024;
-constexpr int kAnyMaxDevices = 64;
 inline size_t conv_mfma_any_lds(int ksize, int cb, bool f16)
 {
     return (size_t)(kConvTW + ksize - 1) * (kConvTH + ksize - 1) * (cb * (f16 ? 2 : 4) + 16);
@@ -498,8 +495,11 @@ inline int conv_mfma_any_cb(int ksize, bool f16)
 static_assert((size_t)(kConvTW + kConvMaxK - 1) * (kConvTH + kConvMaxK - 1) * (8 * 4 + 16) <= 160 * 1024,
               "8 channels of the widest filter's tile fit the CU's LDS");
 int conv_mfma_any_occupancy(int ksize, bool f16);
-hipError_t conv_mfma_any_prepare();   // the kernels' dynamic LDS limit on the current device, once; before the first launch
 void launch_conv_mfma_any(const ConvParams &p, const void *wfrag, bool f16, int nframes, hipStream_t s);
+// The dynamic-LDS limit of every variant of k_conv_mfma_any / k_conv_mfma_f64, raised on the CURRENT device; their one caller
+// is conv_prepare_device (pbd_capi.hip)
+hipError_t conv_mfma_any_set_lds_limits();
+hipError_t conv_mfma_f64_set_lds_limits();
 // the convolution modes by what they imply (every site that used to compare with the enum values asks these)
 inline bool conv_is_f16(int mode) { return mode == PBD_CONV_MFMA_F16 || mode == PBD_CONV_MFMA_F16_ANY; }        // fp16 operands and resident responses
 inline bool conv_is_matrix_f32(int mode) { return mode == PBD_CONV_MFMA || mode == PBD_CONV_MFMA_ANY || conv_is_f16(mode); }   // float handle, matrix cores

@@ -6,27 +6,19 @@
 //
 //   out[filter][pixel] = sum_{tap, channel} W[filter][tap][channel] * F[pixel + tap][channel]      (K = 800)
 //
-// Every fp32 operand is split into two bf16 terms, x = hi + lo (hi = bf16(x), lo = bf16(x - hi)), and
-// hi*hi + hi*lo + lo*hi is accumulated in fp32 by v_mfma_f32_32x32x16_bf16: 16 significant bits per
-// operand, relative product error ~2^-16, three MFMAs per fp32 MAC tile instead of one.
-//
-// Mapping: see conv_mfma_tile below.
+// The bf16 split x = hi + lo, the tile stager and the product step are pbd_conv_mfma16.h's, shared with the any-size kernel
+// (pbd_kernels_conv_mfma_any.hip).  Mapping: see conv_mfma_tile below.
 //
 // PBD_CONV_MFMA_F16 (BASELINE.json configs[4], SURVEY.md section 8(d) "Config 5"): the same contraction with
 // every operand rounded once to fp16 and ONE v_mfma_f32_32x32x16_f16 per product tile, fp32 accumulation.
 // Records are 80 bytes (32 fp16 + 16 pad, again conflict-free for the 16-byte fragment reads), a third of
 // the matrix-core work and 35 KB of LDS per workgroup.
 // The 1e-4 score bar does NOT hold in this mode; tests report the error and the detection agreement.
-#include "pbd_internal.h"
+#include "pbd_conv_mfma16.h"
 
 #include <type_traits>
 
 namespace pbd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMfmaFB = 160;           // filters per pass (5 M-tiles of 32)
 
@@ -60,51 +52,8 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams &p, const u32x4 
     const int t = threadIdx.x;
     const float *feat = featp + ((size_t)frame * p.cell_per_frame + d.cell_off) * 32;
 
-    // ---- stage the feature tile: fp32 -> (hi, lo) bf16 or fp16; thread = (cell, 8-channel group); the loads of a
-    // batch of UB tasks are issued together (one exposed memory latency per batch instead of one per task)
-    {
-        constexpr int NTASK = NCELL * 4, NTHR = 256, UB = 4;
-        for (int base = 0; base < NTASK; base += NTHR * UB) {
-            float4 va[UB], vb[UB];
-            bool inside[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int idx = base + u * NTHR + t;
-                const int ci = idx >> 2, cg = idx & 3;
-                const int cy = ci / PW, cx = ci - cy * PW;
-                const int gy = tile.y0 + cy - a, gx = tile.x0 + cx - a;
-                inside[u] = idx < NTASK && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                va[u] = vb[u] = float4{0.f, 0.f, 0.f, 0.f};
-                if (inside[u]) {
-                    const float4 *src = reinterpret_cast<const float4 *>(feat + ((size_t)gy * W + gx) * 32 + cg * 8);
-                    va[u] = src[0]; vb[u] = src[1];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                const int idx = base + u * NTHR + t;
-                if (idx >= NTASK) continue;
-                const int ci = idx >> 2, cg = idx & 3;
-                float v[8] = {va[u].x, va[u].y, va[u].z, va[u].w, vb[u].x, vb[u].y, vb[u].z, vb[u].w};
-                if (!inside[u] && cg == 3) v[7] = 1.0f;        // constant border: 1 on channel 31 (SpatialConvolutionEngine.cpp:153-156)
-                if constexpr (F16) {
-                    f16x8 hv;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) hv[j] = (_Float16)v[j];
-                    *reinterpret_cast<f16x8 *>(sm_f + ci * kRec + cg * 16) = hv;
-                } else {
-                    bf16x8 hi, lo;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        hi[j] = (__bf16)v[j];
-                        lo[j] = (__bf16)(v[j] - (float)hi[j]);
-                    }
-                    *reinterpret_cast<bf16x8 *>(sm_f + ci * kRec + cg * 16) = hi;
-                    *reinterpret_cast<bf16x8 *>(sm_f + ci * kRec + 64 + cg * 16) = lo;
-                }
-            }
-        }
-    }
+    // ---- stage the feature tile: all 32 channels of a cell in one record, the lo half 64 bytes on
+    mfma16_stage_tile<F16, 4>(feat, sm_f, tile.x0, tile.y0, H, W, a, PW, NCELL, 0, kRec, 64);
     __syncthreads();
 
     const int lane = t & 63;
@@ -128,12 +77,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams &p, const u32x4 
         const u32x4 *wsrc = wfrag + ((size_t)pass * (K * K * 2) * MT + m0) * NV * 64 + lane;
         const int celln = cell0 + n0 * kNStep;
         f32x16 acc[MB][NB];
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-            for (int n = 0; n < NB; ++n)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[mi][n][e] = 0.0f;
+        mfma16_clear(acc);
         u32x4 wq[PF][MB][NV];
 #pragma unroll
         for (int j = 0; j < PF; ++j)
@@ -161,27 +105,7 @@ __device__ __forceinline__ void conv_mfma_tile(const ConvParams &p, const u32x4 
                 const int sidx = s0 + j;
                 const unsigned char *bnext = b_addr(min(sidx + 1, NSTEP - 1));
 #pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    if constexpr (F16) {
-                        const f16x8 bf = __builtin_bit_cast(f16x8, bq[n][0]);
-#pragma unroll
-                        for (int mi = 0; mi < MB; ++mi)
-                            acc[mi][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wq[j][mi][0]), bf, acc[mi][n], 0, 0, 0);
-                    } else {
-                        const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[n][0]), bl = __builtin_bit_cast(bf16x8, bq[n][1]);
-#pragma unroll
-                        for (int mi = 0; mi < MB; ++mi)
-                            acc[mi][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq[j][mi][0]), bh, acc[mi][n], 0, 0, 0);
-#pragma unroll
-                        for (int mi = 0; mi < MB; ++mi)
-                            acc[mi][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq[j][mi][0]), bl, acc[mi][n], 0, 0, 0);
-#pragma unroll
-                        for (int mi = 0; mi < MB; ++mi)
-                            acc[mi][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wq[j][mi][1]), bh, acc[mi][n], 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int v = 0; v < NV; ++v) bq[n][v] = *reinterpret_cast<const u32x4 *>(bnext + n * kNStep + v * 64);
-                }
+                for (int n = 0; n < NB; ++n) mfma16_products<F16>(acc, n, wq[j], bq[n], bnext + n * kNStep, 64);
                 const int snext = min(sidx + PF, NSTEP - 1);
 #pragma unroll
                 for (int mi = 0; mi < MB; ++mi)
@@ -251,11 +175,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvParams p, const u32x4 
     else conv_mfma_tile<K, F16, 2>(p, wfrag, featp, respp, sm_f, tile);
 }
 
+// the kernel of a mode: fn(k_conv_mfma<5, F16>)
+template <typename Fn> static void with_variant(bool f16, Fn &&fn)
+{
+    if (f16) fn(k_conv_mfma<5, true>); else fn(k_conv_mfma<5, false>);
+}
+
 int conv_mfma_occupancy(bool f16)
 {   // resident workgroups per CU (diagnostics)
     int n = -1;
-    if (f16) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_conv_mfma<5, true>, 256, 0);
-    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_conv_mfma<5, false>, 256, 0);
+    with_variant(f16, [&](auto k) { (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0); });
     return n;
 }
 
@@ -264,13 +193,10 @@ void launch_conv_mfma(const ConvParams &p, const void *wrec, bool f16, int nfram
     const int nt = p.nshaped[0] + p.nshaped[1] + p.nshaped[2];
     if (nt == 0 || p.F == 0) return;
     const int passes = (p.F + kMfmaFB - 1) / kMfmaFB;
-    dim3 grid(nt, passes, nframes);
-    if (f16)
-        PBD_LAUNCH((k_conv_mfma<5, true>), grid, dim3(256), 0, s, p, static_cast<const u32x4 *>(wrec),
-                           static_cast<const float *>(p.feat), static_cast<float *>(p.resp));
-    else
-        PBD_LAUNCH((k_conv_mfma<5, false>), grid, dim3(256), 0, s, p, static_cast<const u32x4 *>(wrec),
-                           static_cast<const float *>(p.feat), static_cast<float *>(p.resp));
+    with_variant(f16, [&](auto k) {
+        PBD_LAUNCH(k, dim3(nt, passes, nframes), dim3(256), 0, s, p, static_cast<const u32x4 *>(wrec),
+                   static_cast<const float *>(p.feat), static_cast<float *>(p.resp));
+    });
 }
 
 }  // namespace pbd

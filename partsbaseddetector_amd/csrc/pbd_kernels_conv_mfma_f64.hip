@@ -14,7 +14,7 @@
 //   A: lane l holds A[l & 15][l >> 4]      B: lane l holds B[l >> 4][l & 15]      (one double per lane)
 //   D: four doubles per lane, register r holds D[row = (l >> 4) + 4 r][col = l & 15]
 //
-// Workgroup = one 32 x 8 tile of the uniform tiling (ConvParams::tiles) of one level / frame x one PASS of mb <= kF64MaxMB
+// Workgroup = one 32 x 8 tile of the uniform tiling (ConvParams::tiles) of one level / frame x one PASS of mb <= kMfmaMaxMB
 // M-tiles (16 filters each), four waves.  Wave w owns tile rows 2w, 2w + 1 = four N-tiles, and all mb M-tiles of the pass:
 // mb x 4 accumulators of 16 x 16 (8 VGPRs each), so every weight fragment feeds four MFMAs and every feature fragment mb.
 //   Features: the haloed tile sits in LDS in channel blocks of CB = 4 QN channels (16, 8 or 4: the largest whose tile stays
@@ -165,10 +165,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma_f64(ConvParams p, const do
     const int frame = p.frame0 + blockIdx.z;
     const LevelDesc d = p.lv[tile.level];
     const double *feat = static_cast<const double *>(p.feat) + ((size_t)frame * p.cell_per_frame + d.cell_off) * 32;
-    const int m0 = f64_pass_begin(blockIdx.y, mtiles, passes), mb = f64_pass_begin(blockIdx.y + 1, mtiles, passes) - m0;
+    const int m0 = mfma_pass_begin(blockIdx.y, mtiles, passes), mb = mfma_pass_begin(blockIdx.y + 1, mtiles, passes) - m0;
     // a pass's fragments start after those of the M-tiles before it: 8 K^2 fragments of 64 doubles per M-tile
     const double *wpass = wfrag + (size_t)m0 * 8 * p.ksize * p.ksize * 64;
-    static_assert(kF64MaxMB == 4, "the dispatch below covers pass sizes 1..4");
+    static_assert(kMfmaMaxMB == 4, "the dispatch below covers pass sizes 1..4");
     switch (mb) {
     case 4: conv_mfma_f64_pass<QN, 4>(p, wpass, m0, feat, smraw, tile, d, frame); break;
     case 3: conv_mfma_f64_pass<QN, 3>(p, wpass, m0, feat, smraw, tile, d, frame); break;
@@ -189,28 +189,33 @@ int conv_mfma_f64_qn(int ksize)
     return qn;
 }
 
-template <int QN>
-static void launch_f64(const ConvParams &p, const double *wfrag, int mtiles, int passes, int nframes, hipStream_t s)
+// the kernel of a channel block: fn(k_conv_mfma_f64<qn>)
+template <typename Fn> static void with_variant(int qn, Fn &&fn)
 {
-    static const bool lds_limit_set = [] {   // once: the largest tile this block size is chosen for (kConvMaxK at QN = 1)
-        const size_t cap = QN == 1 ? conv_mfma_f64_lds(kConvMaxK, 1) : kF64LdsTarget;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_mfma_f64<QN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
-        return true;
-    }();
-    (void)lds_limit_set;
-    PBD_LAUNCH((k_conv_mfma_f64<QN>), dim3(p.ntiles, passes, nframes), dim3(256), (unsigned)conv_mfma_f64_lds(p.ksize, QN), s, p,
-               wfrag, mtiles, passes);
+    if (qn == 4) fn(k_conv_mfma_f64<4>); else if (qn == 2) fn(k_conv_mfma_f64<2>); else fn(k_conv_mfma_f64<1>);
+}
+
+hipError_t conv_mfma_f64_set_lds_limits()
+{   // per variant, the largest tile its block size is chosen for: the widest filter at QN = 1, the target otherwise
+    hipError_t e = hipSuccess;
+    for (int qn = 4; qn >= 1; qn /= 2)
+        with_variant(qn, [&](auto k) {
+            const size_t cap = qn == 1 ? conv_mfma_f64_lds(kConvMaxK, 1) : kF64LdsTarget;
+            if (!e)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+        });
+    return e;
 }
 
 void launch_conv_mfma_f64(const ConvParams &p, const double *wfrag, int nframes, hipStream_t s)
 {
     if (p.ntiles == 0 || p.nf == 0) return;
-    const int mtiles = (p.nf + 15) / 16, passes = f64_passes(mtiles);
-    switch (conv_mfma_f64_qn(p.ksize)) {
-    case 4: launch_f64<4>(p, wfrag, mtiles, passes, nframes, s); break;
-    case 2: launch_f64<2>(p, wfrag, mtiles, passes, nframes, s); break;
-    default: launch_f64<1>(p, wfrag, mtiles, passes, nframes, s); break;
-    }
+    const int mtiles = (p.nf + 15) / 16, passes = mfma_passes(mtiles);
+    const int qn = conv_mfma_f64_qn(p.ksize);
+    with_variant(qn, [&](auto k) {
+        PBD_LAUNCH(k, dim3(p.ntiles, passes, nframes), dim3(256), (unsigned)conv_mfma_f64_lds(p.ksize, qn), s, p, wfrag, mtiles,
+                   passes);
+    });
 }
 
 }  // namespace pbd

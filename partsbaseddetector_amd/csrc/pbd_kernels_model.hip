@@ -190,7 +190,7 @@ template <typename R> static void launch_mu_class_t(const MuClassParams &p, hipS
     }
     if (p.c31tab) PBD_LAUNCH(k_mu_c31<R>, blocks(81LL * p.nf), dim3(kB), 0, s, p);
     if (p.wfrag64) {
-        const int mtiles = (p.nf + 15) / 16, passes = f64_passes(mtiles);
+        const int mtiles = (p.nf + 15) / 16, passes = mfma_passes(mtiles);
         PBD_LAUNCH(k_mu_frag64<R>, blocks(f64_frag_size(KK, mtiles)), dim3(kB), 0, s, p, mtiles, passes);
     }
 }

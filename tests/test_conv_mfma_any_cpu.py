@@ -23,8 +23,8 @@ void map_any(long long n, int KK, int CB, int NV, int nf, int *out)
 { for (long long i = 0; i < n; ++i) { int part = 0; WeightSrc s = any_frag_source(i, KK, CB, NV, nf, &part); out[4*i] = s.f; out[4*i+1] = s.t; out[4*i+2] = s.c; out[4*i+3] = part; } }
 long long size_any(int KK, int CB, int NV, int nf) { return any_frag_size(KK, CB, NV, nf); }
 int steps_any(int KK, int CB) { return any_steps(KK, CB); }
-int passes_any(int mtiles) { return any_passes(mtiles); }
-int pass_begin(int ps, int mtiles, int passes) { return f64_pass_begin(ps, mtiles, passes); }
+int passes_any(int mtiles) { return mfma_passes(mtiles); }
+int pass_begin(int ps, int mtiles, int passes) { return mfma_pass_begin(ps, mtiles, passes); }
 }
 '''
 

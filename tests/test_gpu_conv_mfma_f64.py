@@ -200,6 +200,34 @@ def test_every_entry_point(det_mod):
     det.hd.close()
 
 
+def test_handles_on_two_devices_in_one_process(det_mod, oracle):
+    """The dynamic-LDS limit is a per-device property of a kernel: a handle on device 0, then one on device 1, in one process,
+    both within TOL of the oracle.  19 x 19 filters (4-channel blocks, 61 KB per tile) and 7 x 7 filters (16-channel blocks,
+    75 KB: above the 64 KB a kernel may ask for by default)."""
+    import ctypes as C
+    from partsbaseddetector_amd import _lib
+    ndev = C.c_int(0)
+    assert _lib.load().hipGetDeviceCount(C.byref(ndev)) == 0
+    if ndev.value < 2:
+        pytest.skip("one device visible")
+    flat = M.synthetic_tiny_model().flatten()
+    rng = np.random.default_rng(19)
+    feat = rng.random((40, 41 * 32)) * 0.4
+    filters = [rng.standard_normal((k, k * 32)) * 0.1 for k in (19, 19, 7)]
+    want = [oracle.conv(feat, w) for w in filters]
+    for device in (0, 1):
+        hd = det_mod.Handle(flat, device=device, real_type=_lib.REAL_F64, conv_mode=_lib.CONV_MFMA_F64)
+        conv = det_mod.SpatialConvolutionEngine(hd)
+        conv.setFilters(filters)
+        got = conv.pdf([feat])[0]
+        assert got.shape == (3, 40, 41)
+        for f in range(3):
+            err = float(np.abs(got[f] - want[f]).max())
+            print(f"device {device} filter {f}: max |response - reference| = {err:.3g}")
+            assert err <= TOL, (device, f, err)
+        hd.close()
+
+
 def test_set_filters_on_a_handle_in_this_mode(det_mod, oracle):
     """Replacing the bank with another size mix works; a refused bank (33 x 33) keeps the old responses bit for bit."""
     from partsbaseddetector_amd._lib import PbdError

@@ -31,7 +31,7 @@ long long size_generic(int KK, int Fpad) { return generic_bank_size(KK, Fpad); }
 long long size_unit(int KK, int ql) { return unit_size(KK, ql); }
 long long size_frag64(int KK, int mtiles) { return f64_frag_size(KK, mtiles); }
 long long size_wrec(int KK, int NV, int nfilters) { return wrec_size(KK, NV, nfilters); }
-int pass_begin(int ps, int mtiles, int passes) { return f64_pass_begin(ps, mtiles, passes); }
+int pass_begin(int ps, int mtiles, int passes) { return mfma_pass_begin(ps, mtiles, passes); }
 int tap_outside(int cs, int i, int j) { return c31_tap_outside(cs, i, j) ? 1 : 0; }
 unsigned value16(float v, int f16, int part) { return wrec_value(v, f16 != 0, part); }
 int weight_place(int t, int c) { WeightSrc s = {0, t, c}; return weight_at(s); }

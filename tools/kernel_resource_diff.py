@@ -17,7 +17,8 @@ import tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from partsbaseddetector_amd import build  # noqa: E402
 
-FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp", "features", "dp", "examples"]
+FILES = ["cloud", "planes", "consistency", "depth", "post", "publish", "qp", "features", "dp", "examples", "conv_mfma",
+         "conv_mfma_any", "conv_mfma_f64"]
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 RENAMED = {
