@@ -3,11 +3,13 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
+//   --root-nms SZ: only the roots that are grid maxima of their score plane within SZ cells are walked and listed
+//           (pbd_set_root_nms: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales)); not with --staged
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT.  0 exact, 1 fma,
 //           2 / 3 matrix cores bf16 / fp16 (5x5 banks), 4 fp64 matrix cores (--double), 5 / 6 matrix cores bf16 / fp16 for
 //           every filter size and mixed banks (PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY; not with --double)
@@ -43,6 +45,7 @@ using namespace pbdhost;
 
 // what a run prints for one image's candidates (the reference's demo: count, sort, optional NMS, the best ones)
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
+static int g_root_nms = 0;                // --root-nms
 
 static void report(std::vector<Candidate> &candidates, const Image &im, bool staged, float nms, float dnms, int top)
 {
@@ -69,6 +72,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
     PartsBasedDetector<T> pbd(0, conv_mode, (int)ims.size());
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     pbd.setWalk(g_walk);
+    pbd.setRootNMS(g_root_nms);
     pbd.distributeModel(model);
     std::vector<std::vector<Candidate> > candidates;
     pbd.detectBatch(ims, candidates);
@@ -155,11 +159,13 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     PartsBasedDetector<T> pbd(0, conv_mode);
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     pbd.setWalk(g_walk);
+    pbd.setRootNMS(g_root_nms);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
         // the image stream_n times through a FrameStream of stream_k handles: every result must be the first one's
         FrameStream<T> fs(model, stream_k, 0, 1 << 16, conv_mode);
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
+        fs.setRootNMS(g_root_nms);
         std::vector<Candidate> first, cur;
         size_t got = 0;
         bool same = true;
@@ -281,7 +287,7 @@ static int dump_model(const Model &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -308,6 +314,7 @@ int main(int argc, char **argv)
             else if (!std::strcmp(argv[i], "reference")) g_walk = PBD_WALK_REFERENCE;
             else { std::fprintf(stderr, "--walk takes reference or argmax\n"); return -1; }
         }
+        else if (!std::strcmp(argv[i], "--root-nms") && i + 1 < argc) g_root_nms = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }

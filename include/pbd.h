@@ -201,6 +201,51 @@ int pbd_set_nms(pbd_handle *h, int enable, float overlap);
 enum { PBD_WALK_REFERENCE = 0, PBD_WALK_ARGMAX = 1 };
 int pbd_set_walk(pbd_handle *h, int mode);
 
+/* Grid maxima of a set of planes (new surface; opt-in): nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp:84-129,
+ * include/nms.hpp), the block NMS of Neubeck and Van Gool the reference's detect() calls on rootv between min and argmin and leaves
+ * commented out (ssp_.nonMaxSuppression(rootv, scales), src/PartsBasedDetector.cpp:86).
+ * Planes are packed row-major without padding: plane i (rows[i] x cols[i], M x N below) starts at the sum of rows * cols of the
+ * planes before it; `mask` (NULL: none) and `dst` have the same layout; dst receives 0 or 255 in every byte.  rows / cols are
+ * host arrays in both forms.  A plane with rows * cols == 0 is legal and produces nothing.  real_code is PBD_REAL_F32 or
+ * PBD_REAL_F64, whatever the handle's T: the handle gives the stream, the workspace and the error text only.
+ *   eligible      an element that is not NaN and, with a mask, whose mask byte is non-zero
+ *   blocks        of (sz + 1) x (sz + 1) elements start at every multiple of sz + 1; the last one in each direction is clipped
+ *   candidate     a block's largest eligible element, among equal ones the first in raster order (cv::minMaxLoc)
+ *   neighbourhood rows cy - sz .. cy + sz, columns cx - sz .. cx + sz around the candidate (cy, cx), clipped to the plane, MINUS the
+ *                 cells of the candidate's own block; only eligible elements count
+ *   result        dst = 255 at the candidate iff it is strictly greater than every such neighbour, compared in the plane's own
+ *                 type; every other byte is 0.  At most one maximum per block.
+ * Decisions where OpenCV's behaviour cannot be pinned from here:
+ *   empty block   a block without an eligible element has no maximum (minMaxLoc would report (-1, -1) and the reference would
+ *                 write out of bounds)
+ *   empty neighbourhood  beats nothing: the candidate is kept (OpenCV returns 0 for an empty mask, which would drop every lone
+ *                 maximum with a negative score)
+ *   NaN           is never eligible.  +0.0 and -0.0 tie; +Inf against +Inf ties (a tie drops the candidate, and inside a block the
+ *                 first of the tied wins)
+ *   unmasked      a larger neighbour that is not eligible is ignored, as mask.mul(blockmask) does
+ *   These follow the code, not the doc comment of nms.cpp: a constant plane that fits in one block has one maximum, at (0, 0); a
+ *   ramp has one, at its far edge; a constant plane spanning several blocks has one, at (0, 0), whose clipped window is its own
+ *   block (every other block's candidate ties with a neighbour).  sz = 0 is legal: blocks of 1 x 1, and every
+ *   eligible element is kept.  There is no upper bound on sz other than 32767.
+ * PBD_ERR_INVALID: sz < 0 or sz > 32767, a negative nplanes / rows / cols, another real_code, or NULL src / dst / rows / cols with
+ * nplanes > 0.  PBD_ERR_STATE while a batch is in flight.  The resident detect result is not touched.
+ * pbd_grid_nms: host planes, synchronous.  pbd_grid_nms_device: device planes (d_src aligned to its element), asynchronous on
+ * pbd_stream(). */
+int pbd_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *src, const uint8_t *mask,
+                 int sz, uint8_t *dst);
+int pbd_grid_nms_device(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *d_src,
+                        const uint8_t *d_mask, int sz, uint8_t *d_dst);
+/* Root NMS (opt-in; sz = 0, off, on a new handle): with sz in 1..32767 every later detect call first runs the step above over every
+ * rootv plane of the call -- one per (frame, level, component) -- with eligibility `rootv > (T)thresh`, the find's own expression
+ * (NaN is false), and the find additionally requires the plane's byte.  Result: the same records, fewer of them, in the same
+ * (frame, level, component, y, x) order; scores, part boxes and every other word are untouched, and word 0 of a device payload is
+ * the kept count.  max_candidates, the caller's capacity, PBD_ERR_CAPACITY and pbd_set_nms see only the kept list.
+ * Applies to every entry point pbd_set_nms lists, and to pbd_detect_frames / _device / _device_out.  NOT to pbd_dp_argmin
+ * (DynamicProgram::argmin: the reference's call sat in detect, outside it), pbd_examples*' re-walks, or pbd_detect_latent, which
+ * has its own best-root search.  Level sharding is allowed: the step is per level, so the union over the ranks is the unsharded
+ * result.  Another sz: PBD_ERR_INVALID; while a batch is in flight: PBD_ERR_STATE (the setting is latched at submit). */
+int pbd_set_root_nms(pbd_handle *h, int sz);
+
 /* 3-D boxes from a depth image (new surface; opt-in, nothing else calls it): the callers' next step after the suppression above,
  * Candidate::boundingBox3D(im, depth) of every kept candidate (the first step of PointCloudClusterer::computeBoundingBoxes:
  * cells/detect.cpp:224-255, ros/Node.cpp:183-206, include/PointCloudClusterer.hpp:53-77; include/Candidate.hpp:140-216).
@@ -1036,6 +1081,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_QP_HINGE,
        /* pbd_cluster_parts*: every (part, trial)'s k-means run, then the pick per part */
        PBD_K_KM_TRIALS, PBD_K_KM_PICK,
+       /* pbd_grid_nms* / pbd_set_root_nms: the grid maxima of a set of planes */
+       PBD_K_GRID_NMS,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

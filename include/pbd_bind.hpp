@@ -249,6 +249,25 @@ inline void set_nms(pbd_handle *h, bool enable, float overlap)
     check<Tr>(h, pbd_set_nms(h, enable ? 1 : 0, overlap));
 }
 
+// pbd_set_root_nms: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) before
+// every later walk of this handle: only the roots that are grid maxima within sz cells are returned; sz = 0: off
+template <class Tr>
+inline void set_root_nms(pbd_handle *h, int sz)
+{
+    check<Tr>(h, pbd_set_root_nms(h, sz));
+}
+
+// nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp:84-129) on the device (pbd_grid_nms) for one plane of T: dst receives
+// rows x cols bytes of 0 / 255, rows dense; mask: NULL, or rows x cols bytes, rows dense
+template <class Tr>
+inline void grid_nms(pbd_handle *h, const typename Tr::Mat &src, int sz, const uint8_t *mask, uint8_t *dst)
+{
+    typedef typename Tr::Real T;
+    const typename Tr::Mat s = Tr::real_continuous(src);
+    const int rows = Tr::rows(s), cols = Tr::cols(s);
+    check<Tr>(h, pbd_grid_nms(h, 1, &rows, &cols, RealCode<T>::value, Tr::cptr(s), mask, sz, dst));
+}
+
 // pbd_candidate records -> the host's Candidates (include/Candidate.hpp:56-80)
 template <class Tr>
 inline void unpack_candidates(pbd_handle *h, const std::vector<int32_t> &buf, int n, std::vector<typename Tr::Candidate> &out)

@@ -595,6 +595,7 @@ class PartsBasedDetector {
     bool nms_;
     float overlap_;
     int walk_;
+    int root_nms_;
     bool depth_on_;
     float zfactor_;
     PartsBasedDetector(const PartsBasedDetector &);
@@ -606,7 +607,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          depth_on_(false), zfactor_(0.03f) {}
+          root_nms_(0), depth_on_(false), zfactor_(0.03f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -617,6 +618,7 @@ public:
         h_ = pbdbind::create<HostTraits<T> >(model, device_, conv_mode_, max_batch_, 1 << 18);
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
+        if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
         name_ = model.name();
     }
     // new surface: detect() returns Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of what it
@@ -636,6 +638,25 @@ public:
         if (mode != PBD_WALK_REFERENCE && mode != PBD_WALK_ARGMAX) throw Error(PBD_ERR_INVALID, "walk mode");
         if (h_) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, mode));
         walk_ = mode;
+    }
+    // new surface: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) from now on
+    // (pbd_set_root_nms): only the roots that are grid maxima of their rootv plane within sz cells are walked and returned;
+    // sz = 0 turns it off (the default).  Kept across distributeModel().
+    void setRootNMS(int sz)
+    {
+        if (sz < 0 || sz > 32767) throw Error(PBD_ERR_INVALID, "root NMS window: 0 (off) or 1..32767");
+        if (h_) pbdbind::set_root_nms<HostTraits<T> >(h_, sz);
+        root_nms_ = sz;
+    }
+    // nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp:84-129) on the device (pbd_grid_nms): dst becomes src.rows x src.cols
+    // bytes of 0 / 255; mask: empty, or that many bytes
+    void gridNMS(const MatT<T> &src, int sz, std::vector<uint8_t> &dst, const std::vector<uint8_t> &mask = std::vector<uint8_t>())
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "gridNMS() before distributeModel()");
+        const size_t n = (size_t)src.rows * src.cols;
+        if (!mask.empty() && mask.size() != n) throw Error(PBD_ERR_INVALID, "gridNMS: the mask has the plane's size");
+        dst.assign(n, 0);
+        pbdbind::grid_nms<HostTraits<T> >(h_, src, sz, mask.empty() ? NULL : &mask[0], n ? &dst[0] : NULL);
     }
     // new surface: detect(im, depth, candidates) runs filterCandidatesByDepth(depth, ., zfactor) on the unsuppressed list, before
     // the suppression -- the reference's commented-out call (src/PartsBasedDetector.cpp:91-93).  Off by default (depth ignored, as
@@ -1139,6 +1160,11 @@ public:
     void setNonMaximaSuppression(float overlap)
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_nms<HostTraits<T> >(h_[i], overlap >= 0, overlap);
+    }
+    // every handle keeps only the grid maxima of its root scores (PartsBasedDetector::setRootNMS); nothing may be pending
+    void setRootNMS(int sz)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_root_nms<HostTraits<T> >(h_[i], sz);
     }
     size_t pending() const { return submitted_ - collected_; }
     bool full() const { return pending() >= h_.size(); }        // the handle the next frame would go to still holds a result

@@ -185,6 +185,30 @@ inline void hipSuppress(pbd_handle *h, const cv::Mat &im, std::vector<typename C
     pbdbind::unpack_candidates<CvTraits<T> >(h, rec, n, candidates);
 }
 
+// nonMaximaSuppression(src, sz, dst, mask) (include/nms.hpp, src/nms.cpp:84-129) on the device (pbd_grid_nms): the reference's
+// parameters behind the handle.  src: one channel; CV_32F and CV_64F are compared in their own type, every other depth as CV_64F
+// (exact for the integer depths).  dst becomes the CV_8U plane of 0 / 255; mask: empty, or CV_8U of src's size.
+inline void hipGridNMS(pbd_handle *h, const cv::Mat &src, int sz, cv::Mat &dst, const cv::Mat mask = cv::Mat())
+{
+    const bool masked = mask.data != NULL && mask.rows > 0 && mask.cols > 0;
+    if (src.channels() != 1 || (masked && (mask.rows != src.rows || mask.cols != src.cols || mask.depth() != CV_8U || mask.channels() != 1)))
+        CV_Error(CV_StsError, "pbd: hipGridNMS: one channel, and a CV_8U mask of the same size");
+    const cv::Mat m = masked && !mask.isContinuous() ? mask.clone() : mask;
+    dst.create(src.rows, src.cols, CV_8U);
+    const uint8_t *mp = masked ? m.ptr<uint8_t>(0) : NULL;
+    uint8_t *dp = src.rows > 0 && src.cols > 0 ? dst.ptr<uint8_t>(0) : NULL;
+    if (src.depth() == CV_32F) pbdbind::grid_nms<CvTraits<float> >(h, src, sz, mp, dp);
+    else pbdbind::grid_nms<CvTraits<double> >(h, src, sz, mp, dp);
+}
+
+// PartsBasedDetector<T>::detect's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) for every
+// later hipDetect / hipDetectBatch of this handle (pbd_set_root_nms): sz = 0 turns it off
+template <typename T>
+inline void hipSetRootNMS(pbd_handle *h, int sz)
+{
+    pbdbind::set_root_nms<CvTraits<T> >(h, sz);
+}
+
 // Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) on the device (pbd_candidate_mask): mask becomes the
 // im.rows x im.cols CV_8U label image; every candidate is one of this frame
 template <typename T>

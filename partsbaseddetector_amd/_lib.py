@@ -24,7 +24,8 @@ CONV_MFMA_ANY = 5          # CONV_MFMA's arithmetic for every filter size 1..31 
 CONV_MFMA_F16_ANY = 6      # CONV_MFMA_F16's arithmetic and fp16 resident responses, likewise
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
 # options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
-DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB = 0, 1, 2, 3
+DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB, GRID_NMS_LANES = 0, 1, 2, 3, 4
+GRID_NMS_WAVE_SZ = 7       # kGnWaveSz: k_grid_nms runs one lane per block below this sz, one wave per block from it on
 # cv::Mat::depth() codes of the image depths HOGFeatures::pyramid accepts (src/HOGFeatures.cpp:136-146)
 DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32): 5, np.dtype(np.float64): 6}
 KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_rows", "k_dt_cols", "k_dp_combine",
@@ -34,7 +35,7 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
            "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
            "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick"]
+           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick", "k_grid_nms"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -55,6 +56,7 @@ SYMBOLS = [
     "pbd_warp_positives", "pbd_warp_positives_device", "pbd_part_nms", "pbd_part_nms_device", "pbd_best_overlap",
     "pbd_best_overlap_device", "pbd_eval_pck", "pbd_eval_pck_device", "pbd_eval_apk", "pbd_eval_apk_device",
     "pbd_set_walk", "pbd_qp_clear", "pbd_qp_add_loss_device", "pbd_cluster_parts", "pbd_cluster_parts_device",
+    "pbd_grid_nms", "pbd_grid_nms_device", "pbd_set_root_nms",
 ]
 
 
@@ -188,6 +190,10 @@ def load():
     lib.pbd_set_level_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
     lib.pbd_set_walk.argtypes = [C.c_void_p, C.c_int]
+    lib.pbd_set_root_nms.argtypes = [C.c_void_p, C.c_int]
+    lib.pbd_grid_nms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p]
+    lib.pbd_grid_nms_device.argtypes = lib.pbd_grid_nms.argtypes
     lib.pbd_debug_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_debug_postprocess.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
                                           C.POINTER(C.c_int)]

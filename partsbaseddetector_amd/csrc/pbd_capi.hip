@@ -1232,10 +1232,42 @@ namespace pbd {
 // ---- argmin: find (ordered compaction) + walk into a device payload, then one D2H ---------------------------------
 // enqueues the find and walk kernels for the `nframes` frames of the device-resident DP result; the candidate list is
 // written to d_payload = int32[1 + capacity * stride] (see pbd_handle::CandBuf).  No host synchronisation.
+// pbd_set_root_nms: the grid maxima of every (frame, level, component) plane of rootv among the cells above the threshold, a
+// byte per root cell in h->gn_max.  The planes of one frame are cut into blocks once per plan and sz.
+static int enqueue_root_nms(pbd_handle *h, Plan &P, int nframes, int sz, hipStream_t st)
+{
+    if (P.gn_sz != sz) {
+        std::vector<GnPlane> tab;
+        long long blocks = 0;
+        for (int l = 0; l < P.nlevels; ++l)
+            for (int c = 0; c < h->NC; ++c) {
+                const LevelDesc &d = P.lv[l];
+                const long long HW = (long long)d.rows * d.cols;
+                tab.push_back(grid_nms_plane(d.cell_off * h->NC + c * HW, d.rows, d.cols, sz, &blocks));
+            }
+        if (P.d_gn.p) HIPCHK(h, hipStreamSynchronize(st));   // the previous table may still be read
+        HIPCHK(h, P.d_gn.upload(tab));
+        P.gn_sz = sz; P.gn_blocks = blocks;
+    }
+    const long long per_frame = P.cell_per_frame * h->NC;
+    HIPCHK(h, h->gn_max.ensure(std::max<size_t>((size_t)nframes * per_frame, 16)));
+    GridNmsParams gp{};
+    gp.planes = P.d_gn.p; gp.nplanes = (int)P.d_gn.size; gp.nframes = nframes;
+    gp.frame_stride = per_frame; gp.blocks_per_frame = P.gn_blocks;
+    gp.src = h->rootv.p; gp.use_thresh = 1; gp.thresh = h->thresh; gp.sz = sz; gp.dst = h->gn_max.as<uint8_t>();
+    ProfScope ps(h, PBD_K_GRID_NMS, st);
+    launch_grid_nms(gp, h->f64, grid_nms_lanes(sz, h->gn_lanes), st);
+    return PBD_OK;
+}
+
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
-                   int capacity, hipStream_t st, bool walk_only)
+                   int capacity, hipStream_t st, bool walk_only, int root_nms)
 {
     ArgminParams ap{};
+    if (root_nms > 0 && !walk_only) {
+        if (int rc = enqueue_root_nms(h, P, nframes, root_nms, st)) return rc;
+        ap.root_max = h->gn_max.as<uint8_t>();
+    }
     ap.lv = P.d_lv.p; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
     ap.cell_per_frame = P.cell_per_frame;
     ap.rootv = h->rootv.p; ap.rooti = h->rooti.as<int>();
@@ -1300,11 +1332,11 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
 namespace {
 
 int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, bool post,
-                            hipStream_t st)
+                            int root_nms, hipStream_t st)
 {
     const int stride = ::stride(h), cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-    if (int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st)) return rc;
+    if (int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st, false, root_nms)) return rc;
     cb.nms = post;
     if (post) {
         HIPCHK(h, cb.post.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
@@ -1349,9 +1381,10 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
     return PBD_OK;
 }
 
-int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, int32_t *cand, int capacity, int *ncand)
+int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, int root_nms, int32_t *cand, int capacity,
+               int *ncand)
 {
-    if (int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, h->stream)) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, root_nms, h->stream)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return argmin_deliver(h, h->cb, h->stream, cand, capacity, ncand);
@@ -1362,10 +1395,11 @@ int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool 
 // the caller's
 int enqueue_argmin_out(pbd_handle *h, Plan &P, int nframes, int frame_offset, int32_t *d_payload, int capacity)
 {
-    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.p, frame_offset, d_payload, capacity, h->stream);
+    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.p, frame_offset, d_payload, capacity, h->stream, false, h->root_nms);
     const int cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride(h) + 1) * sizeof(int32_t)));
-    if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream)) return rc;
+    if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream, false, h->root_nms))
+        return rc;
     return enqueue_post(h, P.kind == 2 ? P.mixed_frames : nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap,
                         frame_offset, d_payload, capacity, h->stream, P.kind == 2 ? &P : nullptr);
 }
@@ -1456,7 +1490,7 @@ int detect_sync(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int c
     Plan *P = nullptr;
     if (int rc = check_detect(h, nframes, src, rows, cols, cn, depth, &P)) return rc;
     if (int rc = enqueue_detect(h, *P, nframes, src, cn, depth)) return rc;
-    return run_argmin(h, *P, nframes, P->d_scales.p, h->nms, cand, capacity, ncand);
+    return run_argmin(h, *P, nframes, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
 }
 
 // copies n responses from the device to dst as T; in PBD_CONV_MFMA_F16 mode the device holds fp16, widened to float here
@@ -1785,7 +1819,8 @@ int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *reco
 
 // forces one of the handle's launch choices (tests: every distance-transform variant, DP chunking on small batches);
 // each option's default value restores the automatic choice
-enum { PBD_DEBUG_DT_LANE_SHIFT = 0, PBD_DEBUG_DT_COOP = 1, PBD_DEBUG_DT_COOP_G = 2, PBD_DEBUG_DP_BUDGET_MB = 3 };
+enum { PBD_DEBUG_DT_LANE_SHIFT = 0, PBD_DEBUG_DT_COOP = 1, PBD_DEBUG_DT_COOP_G = 2, PBD_DEBUG_DP_BUDGET_MB = 3,
+       PBD_DEBUG_GRID_NMS_LANES = 4 };
 int pbd_debug_set_option(pbd_handle *h, int option, int value)
 {
     return entry(h, true, kIdle, [&]() -> int {
@@ -1805,6 +1840,10 @@ int pbd_debug_set_option(pbd_handle *h, int option, int value)
         case PBD_DEBUG_DP_BUDGET_MB:    // DP scratch per chunk of frames in MB; 0: 8 GB
             if (value < 0) break;
             h->dp_budget_mb = value;
+            return PBD_OK;
+        case PBD_DEBUG_GRID_NMS_LANES:  // 1 or 64 lanes per block of k_grid_nms; 0: by the window size
+            if (value != 0 && value != 1 && value != 64) break;
+            h->gn_lanes = value;
             return PBD_OK;
         default:
             return fail(h, PBD_ERR_INVALID, "debug option %d unknown", option);
@@ -1910,6 +1949,15 @@ int pbd_set_nms(pbd_handle *h, int enable, float overlap)
                         "levels is not suppression of the union", h->shard_world);
         h->nms = enable != 0;
         h->nms_overlap = overlap;
+        return PBD_OK;
+    });
+}
+
+int pbd_set_root_nms(pbd_handle *h, int sz)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (sz < 0 || sz > 32767) return fail(h, PBD_ERR_INVALID, "root NMS window %d (0: off, 1..32767)", sz);
+        h->root_nms = sz;                 // the resident result stays: the planes do not depend on it
         return PBD_OK;
     });
 }
@@ -2108,7 +2156,7 @@ int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacit
         Plan &P = *h->res.plan;
         HIPCHK(h, h->scales_tmp.ensure(sizeof(float) * PBD_MAX_LEVELS));
         HIPCHK(h, hipMemcpyAsync(h->scales_tmp.p, scales, sizeof(float) * P.nlevels, hipMemcpyHostToDevice, h->stream));
-        return run_argmin(h, P, h->res.frames, h->scales_tmp.as<float>(), false, cand, capacity, ncand);   // no suppression (DynamicProgram::argmin)
+        return run_argmin(h, P, h->res.frames, h->scales_tmp.as<float>(), false, 0, cand, capacity, ncand);   // no suppression, no root NMS (DynamicProgram::argmin)
     });
 }
 
@@ -2148,7 +2196,7 @@ static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, Plan &P, int nfram
 {
     if (!S.done.p) HIPCHK(h, hipEventCreateWithFlags(&S.done.p, hipEventDisableTiming));
     if (int rc = enqueue_detect(h, P, nframes, FrameSrc{nullptr, 0, d_frames}, channels, kDepth8U)) return rc;
-    if (int rc = enqueue_argmin_readback(h, P, nframes, P.d_scales.p, S.cb, h->nms, h->stream)) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, P.d_scales.p, S.cb, h->nms, h->root_nms, h->stream)) return rc;
     HIPCHK(h, hipEventRecord(S.done.p, h->stream));
     HIPCHK(h, hipGetLastError());
     h->nsubmitted += 1;
@@ -2243,7 +2291,7 @@ int pbd_detect_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int c
         Plan *P = nullptr;
         if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, true, &P)) return rc;
         if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, true)) return rc;
-        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, cand, capacity, ncand);
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
     });
 }
 
@@ -2254,7 +2302,7 @@ int pbd_detect_frames_device(pbd_handle *h, int nframes, const pbd_frame *frames
         Plan *P = nullptr;
         if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, false, &P)) return rc;
         if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, false)) return rc;
-        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, cand, capacity, ncand);
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
     });
 }
 
@@ -2349,7 +2397,8 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_pass", "k_qp_lincomb", "k_qp_slots", "k_qp_norm", "k_qp_wraw",
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-                                             "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick"};
+                                             "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick",
+                                             "k_grid_nms"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

@@ -212,6 +212,49 @@ int enqueue_dc(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code
     return PBD_OK;
 }
 
+// ---- grid maxima of a caller's planes (pbd_grid_nms*; pbd_kernels_gridnms.hip)
+// every check of a call; *total = the elements of all planes
+int check_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *src, const void *dst,
+                   int sz, long long *total)
+{
+    if (nplanes < 0) return fail(h, PBD_ERR_INVALID, "nplanes %d", nplanes);
+    if (nplanes > 0 && (!rows || !cols || !src || !dst))
+        return fail(h, PBD_ERR_INVALID, "a null pointer: rows %p, cols %p, src %p, dst %p", (const void *)rows, (const void *)cols, src, dst);
+    if (sz < 0 || sz > 32767) return fail(h, PBD_ERR_INVALID, "window size %d (0..32767)", sz);
+    if (real_code != PBD_REAL_F32 && real_code != PBD_REAL_F64)
+        return fail(h, PBD_ERR_INVALID, "real_code %d: PBD_REAL_F32 or PBD_REAL_F64", real_code);
+    *total = 0;
+    for (int i = 0; i < nplanes; ++i) {
+        if (rows[i] < 0 || cols[i] < 0) return fail(h, PBD_ERR_INVALID, "plane %d: size %dx%d", i, rows[i], cols[i]);
+        *total += (long long)rows[i] * cols[i];
+    }
+    return PBD_OK;
+}
+
+// the plane table to the device and the kernel, on the handle's stream
+int enqueue_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *d_src,
+                     const uint8_t *d_mask, int sz, uint8_t *d_dst)
+{
+    std::vector<GnPlane> tab(nplanes);
+    long long off = 0, blocks = 0;
+    for (int i = 0; i < nplanes; ++i) {
+        tab[i] = grid_nms_plane(off, rows[i], cols[i], sz, &blocks);
+        off += (long long)rows[i] * cols[i];
+    }
+    if (blocks == 0) return PBD_OK;
+    if (int rc = h->gn_tab.stage(h, tab.data(), tab.size() * sizeof(GnPlane))) return rc;
+    GridNmsParams gp{};
+    gp.planes = h->gn_tab.as<GnPlane>(); gp.nplanes = nplanes; gp.nframes = 1;
+    gp.frame_stride = off; gp.blocks_per_frame = blocks;
+    gp.src = d_src; gp.mask = d_mask; gp.sz = sz; gp.dst = d_dst;
+    {
+        ProfScope ps(h, PBD_K_GRID_NMS, h->stream);
+        launch_grid_nms(gp, real_code == PBD_REAL_F64, grid_nms_lanes(sz, h->gn_lanes), h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // ---- suppression of a caller's list (pbd_suppress*): the canvas tables of its frame sizes, kept for the next call of the
 // same sizes
 int get_suppress_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
@@ -804,6 +847,44 @@ int pbd_depth_consistency_device(pbd_handle *h, int nframes, const pbd_frame *d_
         if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
         if (int rc = check_depth_frames(h, nframes, d_depth, depth_code, false, nullptr, nullptr, &zfactor)) return rc;
         return enqueue_dc(h, depth_table(nframes, d_depth), depth_code, zfactor, d_payload, capacity, frame_offset, d_out, out_capacity);
+    });
+}
+
+// nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp:84-129) over a set of planes.  See include/pbd.h.
+int pbd_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *src, const uint8_t *mask,
+                 int sz, uint8_t *dst)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        long long total = 0;
+        if (int rc = check_grid_nms(h, nplanes, rows, cols, real_code, src, dst, sz, &total)) return rc;
+        if (total == 0) return PBD_OK;
+        const size_t n = (size_t)total, es = real_code == PBD_REAL_F64 ? sizeof(double) : sizeof(float);
+        HIPCHK(h, h->gn_src.ensure(n * es));
+        HIPCHK(h, h->gn_dst.ensure(n));
+        HIPCHK(h, hipMemcpyAsync(h->gn_src.p, src, n * es, hipMemcpyHostToDevice, h->stream));
+        if (mask) {
+            HIPCHK(h, h->gn_mask.ensure(n));
+            HIPCHK(h, hipMemcpyAsync(h->gn_mask.p, mask, n, hipMemcpyHostToDevice, h->stream));
+        }
+        if (int rc = enqueue_grid_nms(h, nplanes, rows, cols, real_code, h->gn_src.p, mask ? h->gn_mask.as<uint8_t>() : nullptr, sz,
+                                      h->gn_dst.as<uint8_t>())) return rc;
+        HIPCHK(h, hipMemcpyAsync(dst, h->gn_dst.p, n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_grid_nms_device(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *d_src,
+                        const uint8_t *d_mask, int sz, uint8_t *d_dst)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        long long total = 0;
+        if (int rc = check_grid_nms(h, nplanes, rows, cols, real_code, d_src, d_dst, sz, &total)) return rc;
+        const size_t es = real_code == PBD_REAL_F64 ? sizeof(double) : sizeof(float);
+        if (reinterpret_cast<uintptr_t>(d_src) % es)
+            return fail(h, PBD_ERR_INVALID, "device pointer %p not a multiple of the %zu-byte element", d_src, es);
+        if (total == 0) return PBD_OK;
+        return enqueue_grid_nms(h, nplanes, rows, cols, real_code, d_src, d_mask, sz, d_dst);
     });
 }
 

@@ -189,6 +189,10 @@ struct Plan {
     DevTable<long long> d_fcanvas;
     DevTable<int> d_post_lds, d_post_glb;
     DevTable<int> d_frame_lv0;              // frame_lv0 on the device (pbd_examples*, uploaded on first use)
+    // pbd_set_root_nms: the (level, component) planes of one frame's rootv cut into blocks of gn_sz + 1 (rebuilt when sz changes)
+    int gn_sz = 0;
+    long long gn_blocks = 0;
+    DevTable<GnPlane> d_gn;
     // dynamic program in groups of whole frames when the virtual frame's scratch exceeds the budget: sub-plans whose cell
     // offsets start at 0 (cell0 = the group's first cell in the virtual frame), built for `chunk_budget`
     size_t chunk_budget = 0;
@@ -366,6 +370,8 @@ struct Handle : ErrCtx {
     int walk_mode = 0;               // PBD_WALK_* (pbd_set_walk), read when a walk is enqueued; the latent twin follows its handle
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;
+    int root_nms = 0;                // grid NMS of the root scores before the find (pbd_set_root_nms): window size, 0 = off; read at enqueue
+    int gn_lanes = 0;                // forced lanes per block of k_grid_nms, 1 or 64; 0: by sz (pbd_debug_set_option)
     DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)
     int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
 
@@ -374,6 +380,11 @@ struct Handle : ErrCtx {
     int totmix = 0;                  // (part, mixture) pairs of the model = planes of IxRaw / IyRaw per cell block
     DevBuf tmp, dt, IxRaw, IyRaw, stk, scales_tmp, find_blk;
     DevBuf post_ws;                  // workspace of the post-processing stage (pbd_kernels_post.hip)
+    // grid NMS: the detect path's byte per root cell (pbd_set_root_nms); pbd_grid_nms*: the plane table (staged as the tables
+    // below), the host form's planes, masks and bytes
+    DevBuf gn_max;
+    StagedTable gn_tab;
+    DevBuf gn_src, gn_mask, gn_dst;
     DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
     // pbd_boxes3d*: the frame table (staged in pinned memory, rewritten only once its previous copy has completed); the host
     // form's depth images, records and boxes.  Never the detect path's buffers: the resident result stays readable.
@@ -622,7 +633,7 @@ inline pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->la
 // ---- defined in pbd_capi.hip, called from the other files of the entry layer (see the definitions)
 void post_canvas_plan(Plan &M);
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload, int capacity,
-                   hipStream_t st, bool walk_only = false);
+                   hipStream_t st, bool walk_only = false, int root_nms = 0);
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
                  int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr, int in_offset = 0, int *bad = nullptr);
 int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan);

@@ -272,6 +272,7 @@ struct ArgminParams {
     int frame_offset;             // added to the `frame` field of every record (frames sharded over GPUs: global frame id)
     // mixed-size calls: virtual level -> (frame of the call, level of that frame's pyramid); NULL: the record's own frame / level
     const int *lv_frame, *lv_local;
+    const uint8_t *root_max;      // pbd_set_root_nms: a byte per root cell, laid out as rootv; a hit also needs it non-zero (NULL: off)
 };
 
 // per-frame sort + non-maxima suppression of an argmin payload (pbd_set_nms; pbd_kernels_post.hip)
@@ -430,6 +431,34 @@ struct DcParams {
 };
 enum { kDcStepClassify = 0, kDcStepSelect, kDcStepCompact, kDcSteps };
 
+// grid maxima of a set of planes (pbd_grid_nms*, pbd_set_root_nms; pbd_kernels_gridnms.hip)
+struct GnPlane {
+    long long off;                // first element of the plane in src / mask / dst (of a frame)
+    long long blk0;               // blocks of the planes before it (an empty plane shares its successor's)
+    int rows, cols;
+    int nbx, pad;                 // blocks per row of blocks: ceil(cols / (sz + 1))
+};
+struct GridNmsParams {
+    const GnPlane *planes;        // [nplanes] the planes of one frame
+    int nplanes, nframes;         // every frame has the same planes, frame_stride elements apart
+    long long frame_stride, blocks_per_frame;
+    const void *src;              // R
+    const uint8_t *mask;          // NULL: every element that is not NaN is eligible
+    int use_thresh;               // the detect path: eligible = src > (R)thresh, no mask
+    float thresh;
+    int sz;
+    uint8_t *dst;                 // 0 / 255, every byte of every plane written
+};
+// plane `off`, rows x cols, cut into blocks of sz + 1: its table entry; *blocks = the blocks so far, advanced by the plane's
+inline GnPlane grid_nms_plane(long long off, int rows, int cols, int sz, long long *blocks)
+{
+    const long long bs = (long long)sz + 1, nbx = (cols + bs - 1) / bs, nby = (rows + bs - 1) / bs;
+    const GnPlane g{off, *blocks, rows, cols, (int)nbx, 0};
+    *blocks += nbx * nby;
+    return g;
+}
+constexpr int kGnWaveSz = 7;      // sz below it: one lane per block; from it on: one wave per block (profiles/grid_nms/README.md)
+
 // ---- kernel launches and their timing -------------------------------------------------------
 // Every kernel of the library is launched through PBD_LAUNCH.  While a profiling scope is open on the calling thread
 // (pbd_profile_enable; bench.py's roofline figures) the launch carries a start / stop event pair of its own
@@ -530,6 +559,9 @@ void launch_boxes3d(const Boxes3dParams &p, int grid, hipStream_t s);
 // one step of the depth-consistency filter (kDcStep*, in this order); dc_record_blocks: workgroups of the compaction (p.blk entries)
 void launch_depth_consistency(const DcParams &p, bool f64, int step, hipStream_t s);
 int dc_record_blocks(int in_cap);
+// the grid maxima of p's planes; lanes per block: grid_nms_lanes(sz, forced) = 1 or 64 (forced: 0 = by sz)
+int grid_nms_lanes(int sz, int forced);
+void launch_grid_nms(const GridNmsParams &p, bool f64, int lanes, hipStream_t s);
 // camera boxes and part centres of p.in's records (after launch_boxes3d wrote p.cube)
 void launch_camera_boxes(const CameraParams &p, hipStream_t s);
 // one step of the clustering (kClStep*, launched in this order); nothing is read back

@@ -281,11 +281,47 @@ class Handle:
         placement the score was taken at) for every walk the handle makes afterwards: part boxes, examples, latent positives"""
         self.check(self.lib.pbd_set_walk(self.h, int(mode)))
 
+    def set_root_nms(self, sz: int) -> None:
+        """pbd_set_root_nms: every detect* call of this handle keeps only the roots that are grid maxima of their (frame, level,
+        component) plane of rootv among the cells above the threshold (gridnms.grid_nms_ref(rootv, sz, rootv > thresh)), before
+        the walk; 0: off (the default)"""
+        self.check(self.lib.pbd_set_root_nms(self.h, int(sz)))
+
+    def grid_nms(self, planes: Sequence[np.ndarray], sz: int, masks: Optional[Sequence[Optional[np.ndarray]]] = None) -> List[np.ndarray]:
+        """pbd_grid_nms: nonMaximaSuppression(plane, sz, dst, mask) of every plane (2-D, all float32 or all float64, any sizes, empty
+        ones included), one launch; masks: None, or one uint8 / bool plane per plane.  Returns the uint8 planes of 0 / 255.
+        Equal to gridnms.grid_nms_ref."""
+        planes = [np.ascontiguousarray(a) for a in planes]
+        dt = planes[0].dtype if planes else np.dtype(np.float32)
+        if dt not in (np.float32, np.float64) or any(a.dtype != dt or a.ndim != 2 for a in planes):
+            raise PbdError(-1, "grid_nms: 2-D planes of one dtype, float32 or float64")
+        if masks is not None and (len(masks) != len(planes) or any(np.shape(m) != a.shape for m, a in zip(masks, planes))):
+            raise PbdError(-1, "grid_nms: one mask of its plane's shape per plane")
+        rows = np.array([a.shape[0] for a in planes], np.int32)
+        cols = np.array([a.shape[1] for a in planes], np.int32)
+        src = np.concatenate([a.ravel() for a in planes]) if planes else np.zeros(0, dt)
+        msk = None if masks is None else np.concatenate([(np.asarray(m) != 0).astype(np.uint8).ravel() for m in masks] or [np.zeros(0, np.uint8)])
+        dst = np.zeros(src.size, np.uint8)
+        self.check(self.lib.pbd_grid_nms(self.h, len(planes), _lib.ptr(rows, C.c_int), _lib.ptr(cols, C.c_int),
+                                         _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64, src.ctypes.data,
+                                         None if msk is None else msk.ctypes.data, int(sz), dst.ctypes.data))
+        off = np.concatenate([[0], np.cumsum(rows.astype(np.int64) * cols)])
+        return [dst[off[i]:off[i + 1]].reshape(a.shape) for i, a in enumerate(planes)]
+
+    def grid_nms_device(self, rows: Sequence[int], cols: Sequence[int], real_code: int, d_src_ptr: int, d_mask_ptr: Optional[int],
+                        sz: int, d_dst_ptr: int) -> None:
+        """pbd_grid_nms_device: the packed planes at d_src_ptr (rows[i] x cols[i] each, REAL_F32 or REAL_F64), the optional packed
+        mask bytes, the packed result bytes; asynchronous on the handle's stream"""
+        r = np.asarray(rows, np.int32)
+        c = np.asarray(cols, np.int32)
+        self.check(self.lib.pbd_grid_nms_device(self.h, len(r), _lib.ptr(r, C.c_int), _lib.ptr(c, C.c_int), int(real_code),
+                                                d_src_ptr or None, d_mask_ptr or None, int(sz), d_dst_ptr or None))
+
     def set_debug_option(self, option: int, value: int) -> None:
         """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
         one.  _lib.DT_LANE_SHIFT: 0..6, 64 >> value rows per wave of the distance transform (-1); _lib.DT_COOP: 0, never
         its cooperative kernel (1); _lib.DT_COOP_G: 4 or 8 rows per wave of that kernel (0); _lib.DP_BUDGET_MB: > 0, the
-        dynamic program's scratch per chunk of frames (0: 8 GB)."""
+        dynamic program's scratch per chunk of frames (0: 8 GB); _lib.GRID_NMS_LANES: 1 or 64 lanes per block of k_grid_nms (0: by sz)."""
         self.check(self.lib.pbd_debug_set_option(self.h, option, value))
 
     # ---- helpers -------------------------------------------------------------------------------
@@ -991,6 +1027,7 @@ class PartsBasedDetector:
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
         self._nms = nms
         self._walk = "reference"
+        self._root_nms = 0                         # setRootNMS: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
         self.hd: Optional[Handle] = None
@@ -1015,6 +1052,8 @@ class PartsBasedDetector:
             self.hd.set_nms(self._nms)
         if self._walk != "reference":
             self.hd.set_walk(self.WALKS[self._walk])
+        if self._root_nms:
+            self.hd.set_root_nms(self._root_nms)
         self._name = getattr(model, "name", "")
         self.features_ = HOGFeatures(self.hd)
         self.convolution_engine_ = SpatialConvolutionEngine(self.hd)
@@ -1035,6 +1074,21 @@ class PartsBasedDetector:
         if self.hd is not None:
             self.hd.set_walk(self.WALKS[walk])
         self._walk = walk
+
+    def setRootNMS(self, sz: int) -> None:
+        """the reference's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) from now on
+        (pbd_set_root_nms; kept across distributeModel): only the roots that are grid maxima of their plane within a window of sz
+        cells are walked and returned; 0: off (the default).  train() / trainmodel() never turn it on: mining needs every violator"""
+        if not 0 <= int(sz) <= 32767:
+            raise PbdError(-1, f"root NMS window {sz}: 0 (off) or 1..32767")
+        if self.hd is not None:
+            self.hd.set_root_nms(int(sz))
+        self._root_nms = int(sz)
+
+    def gridNMS(self, src: np.ndarray, sz: int, mask: Optional[np.ndarray] = None) -> np.ndarray:
+        """nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp) on the device: the uint8 plane of 0 / 255 (pbd_grid_nms)"""
+        self._need()
+        return self.hd.grid_nms([src], sz, None if mask is None else [mask])[0]
 
     def setDepthConsistency(self, zfactor: Optional[float] = 0.03) -> None:
         """detect(im, depth) then runs filterCandidatesByDepth(., depth, zfactor) before the suppression, as the reference's
@@ -1622,6 +1676,11 @@ class DetectorPool:
         out = self._lane(self._collected).wait_batch(capacity, raw)
         self._collected += 1
         return out
+
+    def setRootNMS(self, sz: int) -> None:
+        """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setRootNMS(sz)
 
     def close(self) -> None:
         for d in self.dets:

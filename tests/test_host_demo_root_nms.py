@@ -1,0 +1,54 @@
+"""host/pbd_demo --root-nms SZ (PartsBasedDetector<T>::setRootNMS, include/pbd_host.hpp): the usage text names the flag (no GPU
+needed), and on the GPU the demo lists the candidates Python's setRootNMS gives."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from partsbaseddetector_amd import filestorage as FS
+from partsbaseddetector_amd import model as M, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEMO = os.path.join(ROOT, "host", "pbd_demo")
+
+
+@pytest.fixture(scope="module")
+def demo():
+    from partsbaseddetector_amd import build
+    build.build_hip()
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "host")])
+    return DEMO
+
+
+def test_usage_names_the_flag(demo):
+    r = subprocess.run([demo], capture_output=True, text=True)
+    assert r.returncode != 0 and "--root-nms" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [[], ["--double"], ["--stream", "2", "3"]], ids=["float", "double", "stream"])
+def test_demo_lists_what_python_keeps(demo, tmp_path, flags):
+    from partsbaseddetector_amd import detector
+    model = M.synthetic_tiny_model(thresh=0.6)
+    im = synth.synthetic_frame(31, 120, 150, 3)
+    mpath, ipath = str(tmp_path / "model.yml"), str(tmp_path / "frame.ppm")
+    FS.serialize(model, mpath)
+    with open(ipath, "wb") as fh:
+        fh.write(b"P6\n%d %d\n255\n" % (im.shape[1], im.shape[0]))
+        fh.write(np.ascontiguousarray(im[:, :, ::-1]).tobytes())          # PPM stores RGB; the demo hands BGR to detect()
+    det = detector.PartsBasedDetector(device=0, dtype=np.float64 if "--double" in flags else np.float32)
+    det.distributeModel(FS.deserialize(mpath))
+    try:
+        full = det.detect(im)
+        det.setRootNMS(2)
+        want = det.detect(im)
+    finally:
+        det.hd.close()
+    assert 1 <= len(want) <= len(full) // 2
+    r = subprocess.run([demo, mpath, ipath, "--root-nms", "2", "--top", "100000"] + flags, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("cand ")]
+    assert f"Number of candidates: {len(want)}" in r.stdout and len(got) == len(want)
+    key = sorted(((c.level, c.component, c.root[1], c.root[0]), c.parts.ravel().tolist()) for c in want)
+    assert sorted(((int(t[1]), int(t[2]), int(t[3]), int(t[4])), [int(v) for p in t[6:] for v in p.split(",")]) for t in got) == key
