@@ -67,12 +67,21 @@ __device__ __forceinline__ R quad_val(double a, double b, int x, R y)
 //   * when a lane's ring is full its two oldest entries (2p, 2p+1) are spilled TOGETHER, as one 16-byte record
 //     {s[2p], s[2p+1], z[2p], v[2p] | v[2p+1] << 16}, to the wave-private, lane-interleaved global stack
 //     ([p][lane]); z[2p+1] is the intersection of the two, recomputed on reload with the same expression on the
-//     same operands (bit-identical).  A lane spills about once per ten elements, but with 64 independent lanes
-//     the WAVE runs the spill and reload paths about once per element (tools/dt_stats.sh: 0.78 and 1.17
-//     executions per element, 8 and 5 lanes active), each a memory round trip the whole wave waits for: what
-//     counts is the NUMBER of requests, which pairing halves (a 6-byte s/v split over two stores was slower; so
-//     was carrying z[2p+1] in a second 4-byte array to save the 24-instruction recomputation: rows pass 8.6 ->
-//     9.1 ms on the same box);
+//     same operands (bit-identical).  A lane spills about once per ten elements, but with 64 independent lanes,
+//     every lane for itself, the WAVE ran the spill and reload paths about once per element (tools/dt_stats.sh:
+//     0.78 and 1.17 executions per element, 8 and 5 lanes active), each a memory round trip the whole wave waits
+//     for: what counts is the NUMBER of requests, which pairing halves (a 6-byte s/v split over two stores was
+//     slower; so was carrying z[2p+1] in a second 4-byte array to save the 24-instruction recomputation: rows
+//     pass 8.6 -> 9.1 ms on the same box);
+//   * so the ring is serviced for the WHOLE WAVE: which entries sit in the ring and which on the stack shows in no
+//     result.  When one lane's ring is full, every lane that holds at least kDtHigh entries spills its oldest pair
+//     in the same pass through the path (push_below); at an element boundary, when one lane has drained its ring over
+//     spilled pairs, every lane with spilled pairs and at most kDtLow entries -- in the read-out, where the stack only
+//     shrinks: every lane with room for a pair -- takes its next pair back in one pass (service_reload).  pop() keeps
+//     its own reload for the lane that pops more entries inside one element than its ring holds.  lo stays even, a
+//     pair is reloaded only into a ring with room for two and only while lo > 0, and a lane never has more entries
+//     on the stack than its line has elements (the host's stack size).  The wave then runs each path once per five
+//     to twelve elements (tools/dt_wave_sim.py, profiles/dt_ring_service/README.md);
 //   * the read-out walks q downwards and POPS: since z[1..ktop] is strictly increasing,
 //     "k = 0; while (z[k+1] < os) k++" (DistanceTransform.hpp:172-178, q ascending) selects the same
 //     k(q) = max{k : z[k] < os(q)} as "k = ktop; while (!(z[k] < os)) k--" with q descending;
@@ -94,6 +103,22 @@ constexpr int kDtCHC = PBD_DT_CHC;  // ... of the columns pass
 #define PBD_DT_RING 8
 #endif
 constexpr int kDtT = PBD_DT_RING;    // ring entries per lane (power of two)
+// Whole-wave ring service (dt_stream's header).  Entries are counted below the lane's top.
+#ifndef PBD_DT_HIGH
+#define PBD_DT_HIGH 6
+#endif
+#ifndef PBD_DT_LOW
+#define PBD_DT_LOW 2
+#endif
+#ifndef PBD_DT_LOW_RO
+#define PBD_DT_LOW_RO 6
+#endif
+constexpr int kDtHigh = PBD_DT_HIGH;    // a spill pass takes every lane that holds at least this many entries after its push
+constexpr int kDtLow = PBD_DT_LOW;      // a reload pass of the forward scan takes every lane with at most this many (and spilled pairs)
+constexpr int kDtLowRO = PBD_DT_LOW_RO; // ... of the read-out, where the stack only shrinks: any lane with room for a pair
+// kDtHigh = kDtT + 1 and kDtLow = kDtLowRO = -1 give the lane-by-lane service back (every lane for itself, in-loop reloads only)
+static_assert(kDtHigh >= 3 && kDtHigh <= kDtT + 1, "a spilling lane has its oldest pair in the ring; a lane over the ring always spills");
+static_assert(kDtLow <= kDtT - 2 && kDtLowRO <= kDtT - 2, "a pair is only reloaded into a ring with room for two entries");
 
 // LDS layout of a wave's ring: [slot][z: 64 x R | s: 64 x R | v: 64 x int]; one address per lane, the rest
 // are immediate offsets.
@@ -116,16 +141,43 @@ struct DtRing {
     __device__ __forceinline__ R &z(int slot) { return *reinterpret_cast<R *>(zs + off(slot)); }
     __device__ __forceinline__ R &s(int slot) { return *reinterpret_cast<R *>(zs + off(slot) + (NARROW ? soff : 64 * (int)sizeof(R))); }
     __device__ __forceinline__ int &v(int slot) { return *reinterpret_cast<int *>(vp + off(slot)); }
+    // the service thresholds at this ring's depth: the same distance from full (a deeper NARROW ring keeps kDtLow as it is)
+    __device__ __forceinline__ int high() const { return T() - (kDtT - kDtHigh); }
+    __device__ __forceinline__ int low_readout() const { return kDtLowRO < 0 ? -1 : T() - (kDtT - kDtLowRO); }
     __device__ __forceinline__ void push_below(int idx, R zk, R sk, int vk)
     {   // entry `idx` (the old top) moves under a new top
         const int slot = slot_of(idx);
-        if (idx - lo >= T()) {   // ring full: spill its two oldest entries lo, lo + 1 as one record
-            DT_STAT(3);
-            const int sl = slot_of(lo);
-            g[(size_t)(lo >> 1) * 64] = StkPairT<R>{s(sl), s(sl + 1), z(sl), (unsigned)v(sl) | ((unsigned)v(sl + 1) << 16)};
-            lo += 2;
+        const int n = idx - lo + 1;     // entries below the new top
+        if (__any(n > T())) {   // a ring of the wave is full: every lane that holds at least high() entries spills its two oldest,
+            if (n >= high()) {  // lo and lo + 1, as one record, in this one pass (high() <= T() + 1: the full lane is among them)
+                DT_STAT(3);
+                const int sl = slot_of(lo);
+                g[(size_t)(lo >> 1) * 64] = StkPairT<R>{s(sl), s(sl + 1), z(sl), (unsigned)v(sl) | ((unsigned)v(sl + 1) << 16)};
+                lo += 2;
+            }
         }
         z(slot) = zk; s(slot) = sk; v(slot) = vk;
+    }
+    // Element boundary, top = entry k: when a lane of the wave has drained its ring over spilled pairs -- at most `drained` entries
+    // left: none in the read-out, where its next pop would take the reload path of pop() alone, and one in the forward scan, whose
+    // every element ends with a push --, every lane with spilled pairs and at most `low` (<= T() - 2) ring entries takes its next
+    // pair (lo-2, lo-1) back in this one pass; both entries go into the ring, the upper one with its z recomputed as in pop().
+    template <bool BZ>
+    __device__ __forceinline__ void service_reload(int k, int drained, int low)
+    {
+        const int n = k - lo;
+        if (__any(n <= drained && lo > 0)) {
+            if (n <= low && lo > 0) {
+                DT_STAT(7);
+                const StkPairT<R> e = g[(size_t)((lo - 2) >> 1) * 64];
+                const int va = (int)(e.vv & 0xffffu), vb = (int)(e.vv >> 16);
+                const int sl = slot_of(lo - 2);
+                z(sl) = e.za; s(sl) = e.sa; v(sl) = va;
+                z(sl + 1) = BZ ? quad_isect<R, true>(a, b, va, vb, e.sa, e.sb) : quad_isect<R, false>(a, b, va, vb, e.sa, e.sb);
+                s(sl + 1) = e.sb; v(sl + 1) = vb;
+                lo -= 2;
+            }
+        }
     }
     template <bool BZ>
     __device__ __forceinline__ void pop(int idx, R &zk, R &sk, int &vk)
@@ -190,6 +242,7 @@ __device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, Dt
             if (q >= 1 && q < N) {
                 const R sq = cur[i];
                 DT_STAT(0);
+                ring.template service_reload<BZ>(k, 1, kDtLow);
                 R s = quad_isect<R, BZ>(a, b, vk, q, sk, sq);
                 while (s <= zk && k > 0) {
                     DT_STAT(1);
@@ -221,6 +274,7 @@ __device__ __forceinline__ void dt_stream(int N, double a, double b, int os0, Dt
             if (q < N) {
                 const R osf = (R)(os0 + q);
                 DT_STAT(5);
+                ring.template service_reload<BZ>(k, 0, ring.low_readout());
                 while (!(zk < osf)) {   // z[0] = -inf ends the walk
                     DT_STAT(2);
                     --k;
