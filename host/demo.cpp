@@ -5,7 +5,7 @@
 //
 //   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
-//            [--remove-planes] [--depth-consistency ZFACTOR] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
+//            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
 //   --root-nms SZ: only the roots that are grid maxima of their score plane within SZ cells are walked and listed
@@ -28,6 +28,10 @@
 //           on the unsuppressed list, on the device), then the candidates of detect(im, depth) with setDepthConsistency on
 //   --mask: Candidate::mask of the listed candidates (after --top), on the device, written as a binary PGM; one line "mask K"
 //           (the labelled pixels); --masked: the image & (mask != 0) (the ROS node's mask topic), a binary PPM (PGM for grey)
+//   --depth-prune FX,WIDTH,TOL: with --depth (a map of the image's size), only the roots whose box width agrees with the depth under
+//           it are walked and listed (pbd_set_depth_prune + pbd_bind_depth: FX in pixels, WIDTH of the root footprint in the map's
+//           units, relative tolerance TOL); with --depth-consistency the chain is prune -> filter -> suppression; with --stream
+//           every submitted frame carries the map; not with --staged
 //   --poses: with --camera, one line per listed candidate after its "object" line: "pose COUNT x y z qx qy qz qw" (messagePoses
 //           on the part centres, on the device; COUNT 0 is the node's "Centroid not found")
 //   pbd_demo model.(yml|xml|mat) --dump-model  (no GPU needed: prints what the model reader read)
@@ -46,6 +50,8 @@ using namespace pbdhost;
 // what a run prints for one image's candidates (the reference's demo: count, sort, optional NMS, the best ones)
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
+static bool g_prune = false;              // --depth-prune fx,width,tol
+static float g_prune_fx = 0.f, g_prune_width = 0.f, g_prune_tol = 0.f;
 
 static void report(std::vector<Candidate> &candidates, const Image &im, bool staged, float nms, float dnms, int top)
 {
@@ -160,12 +166,14 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
+    if (g_prune) pbd.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
         // the image stream_n times through a FrameStream of stream_k handles: every result must be the first one's
         FrameStream<T> fs(model, stream_k, 0, 1 << 16, conv_mode);
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         fs.setRootNMS(g_root_nms);
+        if (g_prune) fs.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
         std::vector<Candidate> first, cur;
         size_t got = 0;
         bool same = true;
@@ -187,7 +195,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         const auto t0 = std::chrono::steady_clock::now();
         for (int i = 0; i < stream_n; ++i) {
             while (fs.full()) collect();
-            fs.submit(im);
+            if (g_prune && depth) fs.submit(im, *depth); else fs.submit(im);
         }
         while (fs.pending()) collect();
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -221,7 +229,8 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         pbd.detect(im, *depth, candidates);
     } else {
         pbd.distributeModel(model);
-        pbd.detect(im, candidates);
+        if (g_prune && depth) pbd.detect(im, *depth, candidates);   // binds the map for this call
+        else pbd.detect(im, candidates);
     }
     report(candidates, im, staged, nms, dnms, top);
     if (depth) {
@@ -287,7 +296,7 @@ static int dump_model(const Model &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -321,6 +330,11 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--also") && i + 1 < argc) also.push_back(argv[++i]);
         else if (!std::strcmp(argv[i], "--depth") && i + 1 < argc) depth_path = argv[++i];
         else if (!std::strcmp(argv[i], "--depth-consistency") && i + 1 < argc) dcz = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--depth-prune") && i + 1 < argc) {
+            char tail = 0;
+            g_prune = std::sscanf(argv[++i], "%f,%f,%f%c", &g_prune_fx, &g_prune_width, &g_prune_tol, &tail) == 3;
+            if (!g_prune) { std::fprintf(stderr, "--depth-prune takes fx,width,tol\n"); return -1; }
+        }
         else if (!std::strcmp(argv[i], "--camera") && i + 1 < argc) {
             have_camera = std::sscanf(argv[++i], "%lf,%lf,%lf,%lf", &camera.fx, &camera.fy, &camera.cx, &camera.cy) == 4;
             if (!have_camera) { std::fprintf(stderr, "--camera takes fx,fy,cx,cy\n"); return -1; }
@@ -348,6 +362,10 @@ int main(int argc, char **argv)
     }
     if (dcz >= 0 && (!depth_path || staged || stream_k > 0)) {
         std::fprintf(stderr, "--depth-consistency needs --depth, not with --staged or --stream\n");
+        return -1;
+    }
+    if (g_prune && (!depth_path || staged)) {
+        std::fprintf(stderr, "--depth-prune needs --depth, not with --staged\n");
         return -1;
     }
     if (have_camera && !depth_path) {

@@ -471,6 +471,55 @@ int pbd_depth_consistency(pbd_handle *h, int nframes, const struct pbd_frame *de
 int pbd_depth_consistency_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code, float zfactor,
                                  const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
 
+/* Scale-depth pruning of roots (new surface; opt-in): the intent of SearchSpacePruning<T>::filterResponseByDepth
+ * (src/SearchSpacePruning.cpp:47-70), the other step detect(im, depth) leaves commented out (src/PartsBasedDetector.cpp:86-93).  The
+ * stub is unfinished; its comments ask for "a mask of plausible depths given the object size and the scale of the image" and it
+ * computes Z = fx * X / scales[n].  The arithmetic below is the project's decision, stated here once:
+ *   plausible(rect, depth, fx, width, tol) -> bool
+ *   rect   (x, y, w, h), the root part's rectangle of a record: words 8..11, what the walk writes for part 0
+ *   depth  the frame's depth image: one channel, depth_code 0 (8U), 2 (16U), 5 (32F) or 6 (64F), any pitch, the SAME rows x cols
+ *          as the colour frame of the record
+ *   fx     focal length in pixels; width: the physical width of the root filter's footprint in the depth image's units; tol: a
+ *          relative tolerance.  All float, widened to double.  fx and width finite and > 0, tol finite and >= 0; anything else is
+ *          PBD_ERR_INVALID
+ *   1. w <= 0: true.
+ *   2. x1 = max(x, 0), y1 = max(y, 0), x2 = min(x + w, cols), y2 = min(y + h, rows) (64-bit); x2 - x1 <= 0 or y2 - y1 <= 0: true.
+ *   3. nine samples, i, j in {0, 1, 2}: px_i = x1 + ((2 i + 1) * (x2 - x1)) / 6, py_j = y1 + ((2 j + 1) * (y2 - y1)) / 6 (integer
+ *      division), d = (double)depth[py_j][px_i]; a sample is valid when d > 0 && d < +inf (NaN, zeros, negatives and Inf are holes).
+ *   4. Z = ((double)fx * (double)width) / (double)w -- w the rectangle's own width, not the clipped one.
+ *   5. a valid sample is in band when fabs(d - Z) <= (double)tol * Z, in double, no contraction.
+ *   6. true when no sample is valid (unknown depth never prunes) or any valid sample is in band; false otherwise.
+ * The result does not depend on the handle's T.
+ * pbd_set_depth_prune(h, cfg): cfg = NULL turns it off (the default).  Kept across model updates; PBD_ERR_STATE while a batch is in
+ * flight (the setting is latched at submit); the resident result stays.
+ * pbd_bind_depth / pbd_bind_depth_device: attach the depth images of the NEXT call of any entry point pbd_set_root_nms lists, or
+ * of pbd_argmin_device_out (which so re-emits the resident list under another depth or other parameters without running the dynamic
+ * program again).  That call consumes the binding.  With pruning on, it first writes a byte per root cell -- above the threshold
+ * and plausible, the rectangle built from the cell, the root mixture's filter size and the level's scale exactly as the walk would
+ * -- and the find additionally requires the byte: the same records, fewer of them, in the same order.  With pbd_set_root_nms on as
+ * well, the grid maxima are taken among the plausible cells above the threshold only.  max_candidates, the caller's capacity,
+ * PBD_ERR_CAPACITY, payload word 0 and pbd_set_nms see only the kept list.  Level sharding is allowed (the test is per cell).
+ *   nframes == 0 unbinds.  Pruning on and nothing bound: no pruning, as detect(im) without depth.  Bound and pruning off: the
+ *   binding is dropped unused.  If the binding's nframes or a frame's rows x cols differ from the call's frames, the call returns
+ *   PBD_ERR_INVALID naming the frame, nothing is enqueued and the binding is dropped.
+ *   The host form copies the images now, into a buffer of the handle (on pbd_stream(), behind the work already queued).  The device
+ *   form reads them in place: they must stay valid until the call's work has run (until _wait for the pipelined form); a frame may
+ *   be a region of a larger image.  Both may be called while a batch is in flight.  Refusals as pbd_depth_consistency*'s images.
+ *   NOT applied by pbd_dp_argmin, pbd_detect_latent, or the trainers' re-walks, for the reason root NMS is not.
+ * pbd_depth_prune / pbd_depth_prune_device: the same decision per record of a caller's list, the rectangle taken from the record
+ * (no model and no scales are read).  Conventions of pbd_depth_consistency* above, word for word: frame_offset, in place allowed
+ * for the host form, *nout / word 0 = the kept count (which may exceed the capacity), an input word 0 that is negative or > capacity
+ * gives -1, a record whose frame index is out of range or whose nparts is outside 1..max parts is dropped (host form: refused), no
+ * host synchronisation in the device form, the resident result untouched, PBD_ERR_STATE while a batch is in flight. */
+typedef struct pbd_depth_prune_cfg { float fx, width, tol; } pbd_depth_prune_cfg;
+int pbd_set_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg);
+int pbd_bind_depth(pbd_handle *h, int nframes, const struct pbd_frame *depth, int depth_code);
+int pbd_bind_depth_device(pbd_handle *h, int nframes, const struct pbd_frame *d_depth, int depth_code);
+int pbd_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, const struct pbd_frame *depth, int depth_code,
+                    const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity, int *nout);
+int pbd_depth_prune_device(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, const struct pbd_frame *d_depth, int depth_code,
+                           const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
+
 /* Suppression of a caller's list (new surface): exactly the pbd_set_nms stage above -- per frame the stable score sort, then the
  * greedy painted-canvas suppression -- applied to any records of this handle, e.g. after pbd_depth_consistency, or to the merged
  * lists of level-sharded handles (pbd_set_nms itself stays refused with sharding: one rank's levels are not the union).
@@ -1083,6 +1132,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_KM_TRIALS, PBD_K_KM_PICK,
        /* pbd_grid_nms* / pbd_set_root_nms: the grid maxima of a set of planes */
        PBD_K_GRID_NMS,
+       /* pbd_set_depth_prune / pbd_depth_prune*: the plausibility test of the root cells, or of a list's records */
+       PBD_K_DEPTH_PRUNE,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

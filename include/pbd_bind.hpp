@@ -319,6 +319,50 @@ inline void depth_consistency(pbd_handle *h, const typename Tr::Image &depth, fl
     n = kept;
 }
 
+// pbd_set_depth_prune: the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93,
+// src/SearchSpacePruning.cpp:47-70) before every later walk of this handle that has a depth image bound (bind_depth): only the
+// roots whose box width agrees with the depth under it are returned.  fx: focal length in pixels, width: the root footprint's
+// physical width in the depth image's units, tol: relative tolerance; on = false: off
+template <class Tr>
+inline void set_depth_prune(pbd_handle *h, bool on, float fx, float width, float tol)
+{
+    pbd_depth_prune_cfg cfg;
+    cfg.fx = fx; cfg.width = width; cfg.tol = tol;
+    check<Tr>(h, pbd_set_depth_prune(h, on ? &cfg : NULL));
+}
+
+inline pbd_frame depth_frame(const void *data, int rows, int cols, size_t step)
+{
+    pbd_frame fr;
+    fr.data = data; fr.rows = rows; fr.cols = cols; fr.stride_bytes = step;
+    return fr;
+}
+
+// pbd_bind_depth: `depth` (one channel of any accepted depth, the frame's rows x cols) for the NEXT detect call of this handle,
+// copied now
+template <class Tr>
+inline void bind_depth(pbd_handle *h, const typename Tr::Image &depth)
+{
+    if (Tr::img_channels(depth) != 1) Tr::fail(PBD_ERR_INVALID, "pbd: bind_depth: the depth image has one channel");
+    const pbd_frame fr = depth_frame(Tr::img_data(depth), Tr::img_rows(depth), Tr::img_cols(depth), Tr::img_step(depth));
+    check<Tr>(h, pbd_bind_depth(h, 1, &fr, Tr::img_depth(depth)));
+}
+
+// pbd_depth_prune over n records of this handle in `buf`, in place: n becomes the kept count, the kept records stay in order;
+// every record is taken as one of this frame (frame field 0)
+template <class Tr>
+inline void depth_prune(pbd_handle *h, const typename Tr::Image &depth, float fx, float width, float tol, std::vector<int32_t> &buf,
+                        int &n)
+{
+    if (Tr::img_channels(depth) != 1) Tr::fail(PBD_ERR_INVALID, "pbd: depth_prune: the depth image has one channel");
+    const pbd_frame fr = depth_frame(Tr::img_data(depth), Tr::img_rows(depth), Tr::img_cols(depth), Tr::img_step(depth));
+    pbd_depth_prune_cfg cfg;
+    cfg.fx = fx; cfg.width = width; cfg.tol = tol;
+    int kept = 0;
+    check<Tr>(h, pbd_depth_prune(h, &cfg, 1, &fr, Tr::img_depth(depth), n ? &buf[0] : NULL, n, 0, n ? &buf[0] : NULL, n, &kept));
+    n = kept;
+}
+
 // Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of n records of one rows x cols frame in `buf`, on the
 // device (pbd_suppress, the pbd_set_nms stage), in place: n becomes the kept count
 template <class Tr>

@@ -14,6 +14,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -598,6 +599,8 @@ class PartsBasedDetector {
     int root_nms_;
     bool depth_on_;
     float zfactor_;
+    bool prune_on_;
+    float prune_fx_, prune_width_, prune_tol_;
     PartsBasedDetector(const PartsBasedDetector &);
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
@@ -607,7 +610,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), depth_on_(false), zfactor_(0.03f) {}
+          root_nms_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -619,6 +622,7 @@ public:
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
         if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
+        if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
         name_ = model.name();
     }
     // new surface: detect() returns Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of what it
@@ -667,13 +671,52 @@ public:
         depth_on_ = on;
         zfactor_ = zfactor;
     }
+    // new surface: the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93) from
+    // now on (pbd_set_depth_prune): detect(im, depth, candidates) walks and returns only the roots whose box width agrees with the
+    // depth under it -- fx in pixels, width of the root footprint in depth units, relative tolerance tol.  Off by default; kept
+    // across distributeModel().  With setDepthConsistency as well: prune at the roots, then the consistency filter, then the
+    // suppression.
+    void setDepthPrune(bool on, float fx = 0.f, float width = 0.f, float tol = 0.3f)
+    {
+        if (on && !(fx > 0 && fx <= FLT_MAX && width > 0 && width <= FLT_MAX && tol >= 0 && tol <= FLT_MAX))
+            throw Error(PBD_ERR_INVALID, "depth prune: fx and width finite and > 0, tol finite and >= 0");
+        if (h_) pbdbind::set_depth_prune<HostTraits<T> >(h_, on, fx, width, tol);
+        prune_on_ = on; prune_fx_ = fx; prune_width_ = width; prune_tol_ = tol;
+    }
+    // pbd_bind_depth: the depth image (im's rows x cols) of the NEXT detect / detectBatch call of one frame; detect(im, depth, .)
+    // calls it when setDepthPrune is on
+    void bindDepth(const Image &depth)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "bindDepth() before distributeModel()");
+        pbdbind::bind_depth<HostTraits<T> >(h_, depth);
+    }
+    // the candidates whose root box agrees with the depth under it, in order, decided on the device (pbd_depth_prune): for a list
+    // built elsewhere; every candidate is taken as one of this frame
+    void depthPrune(const Image &depth, std::vector<Candidate> &candidates, float fx, float width, float tol = 0.3f)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "depthPrune() before distributeModel()");
+        std::vector<int32_t> rec = records(candidates);
+        const std::vector<int32_t> in = rec;
+        int n = (int)candidates.size();
+        pbdbind::depth_prune<HostTraits<T> >(h_, depth, fx, width, tol, rec, n);
+        const size_t stride = (size_t)pbd_candidate_stride(h_);
+        std::vector<Candidate> kept;
+        for (size_t i = 0, k = 0; i < candidates.size() && k < (size_t)n; ++i)   // the kept records are the input's, in order
+            if (std::memcmp(&in[i * stride], &rec[k * stride], stride * sizeof(int32_t)) == 0) {
+                kept.push_back(candidates[i]);
+                ++k;
+            }
+        candidates.swap(kept);
+    }
     void detect(const Image &im, std::vector<Candidate> &candidates) { detect(im, Image(), candidates); }
-    // `depth` is ignored, as by the reference (src/PartsBasedDetector.cpp:91-93), unless setDepthConsistency(true) and it is not
-    // empty (the reference's `if (!depth.empty())`)
+    // `depth` is ignored, as by the reference (src/PartsBasedDetector.cpp:91-93), unless it is not empty (the reference's `if
+    // (!depth.empty())`) and setDepthPrune(true) and / or setDepthConsistency(true) ask for it
     void detect(const Image &im, const Image &depth, std::vector<Candidate> &candidates)
     {
         if (!h_) throw Error(PBD_ERR_STATE, "detect() before distributeModel()");
-        if (!depth_on_ || !depth.data || depth.rows < 1 || depth.cols < 1) {
+        const bool has_depth = depth.data && depth.rows >= 1 && depth.cols >= 1;
+        if (prune_on_ && has_depth) pbdbind::bind_depth<HostTraits<T> >(h_, depth);
+        if (!depth_on_ || !has_depth) {
             pbdbind::detect<HostTraits<T> >(h_, im, candidates, 1 << 16);
             return;
         }
@@ -1166,8 +1209,21 @@ public:
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_root_nms<HostTraits<T> >(h_[i], sz);
     }
+    // every handle prunes the roots of a frame submitted with its depth image (PartsBasedDetector::setDepthPrune); nothing may be
+    // pending
+    void setDepthPrune(bool on, float fx = 0.f, float width = 0.f, float tol = 0.3f)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_depth_prune<HostTraits<T> >(h_[i], on, fx, width, tol);
+    }
     size_t pending() const { return submitted_ - collected_; }
     bool full() const { return pending() >= h_.size(); }        // the handle the next frame would go to still holds a result
+    // the frame with its depth image (one channel, the frame's size; copied before submit() returns), for setDepthPrune
+    void submit(const Image &im, const Image &depth)
+    {
+        if (full()) throw Error(PBD_ERR_STATE, "FrameStream::submit(): every handle holds an uncollected frame; call next() first");
+        if (depth.data && depth.rows >= 1 && depth.cols >= 1) pbdbind::bind_depth<HostTraits<T> >(h_[submitted_ % h_.size()], depth);
+        submit(im);
+    }
     void submit(const Image &im)
     {
         if (full()) throw Error(PBD_ERR_STATE, "FrameStream::submit(): every handle holds an uncollected frame; call next() first");

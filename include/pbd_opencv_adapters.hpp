@@ -185,6 +185,26 @@ inline void hipSuppress(pbd_handle *h, const cv::Mat &im, std::vector<typename C
     pbdbind::unpack_candidates<CvTraits<T> >(h, rec, n, candidates);
 }
 
+// SearchSpacePruning<T>::filterResponseByDepth(pdfs, fsizes, depth, scales, X, fx) (include/SearchSpacePruning.hpp:56,
+// src/SearchSpacePruning.cpp:47-70; the call PartsBasedDetector<T>::detect leaves commented out) for the NEXT hipDetect of this
+// handle: the stub's own parameters behind the handle.  The responses, their sizes and the scales stay on the device, so pdfs,
+// fsizes and scales are not read; `depth` (one channel, the image's size) is bound, and the roots whose box width disagrees with
+// fx * X / width-in-pixels by more than tol are not walked (pbd_set_depth_prune + pbd_bind_depth: scores are untouched, records
+// are removed).  X in the depth image's units.  hipSetDepthPrune<T>(h, false) turns the setting off again.
+template <typename T>
+inline void hipSetDepthPrune(pbd_handle *h, bool on, float fx = 0.f, float X = 0.f, float tol = 0.3f)
+{
+    pbdbind::set_depth_prune<CvTraits<T> >(h, on, fx, X, tol);
+}
+template <typename T, class Pdfs, class Sizes>      // vector2DMat, std::vector<cv::Size>: templates, so that neither is named here
+inline void hipDepthPrune(pbd_handle *h, Pdfs &pdfs, const Sizes &fsizes, const cv::Mat &depth, const vectorf &scales, const float X,
+                          const float fx, const float tol = 0.3f)
+{
+    (void)pdfs; (void)fsizes; (void)scales;
+    pbdbind::set_depth_prune<CvTraits<T> >(h, true, fx, X, tol);
+    pbdbind::bind_depth<CvTraits<T> >(h, depth);
+}
+
 // nonMaximaSuppression(src, sz, dst, mask) (include/nms.hpp, src/nms.cpp:84-129) on the device (pbd_grid_nms): the reference's
 // parameters behind the handle.  src: one channel; CV_32F and CV_64F are compared in their own type, every other depth as CV_64F
 // (exact for the integer depths).  dst becomes the CV_8U plane of 0 / 255; mask: empty, or CV_8U of src's size.

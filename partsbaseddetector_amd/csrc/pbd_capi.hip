@@ -1234,7 +1234,8 @@ namespace pbd {
 // written to d_payload = int32[1 + capacity * stride] (see pbd_handle::CandBuf).  No host synchronisation.
 // pbd_set_root_nms: the grid maxima of every (frame, level, component) plane of rootv among the cells above the threshold, a
 // byte per root cell in h->gn_max.  The planes of one frame are cut into blocks once per plan and sz.
-static int enqueue_root_nms(pbd_handle *h, Plan &P, int nframes, int sz, hipStream_t st)
+// `root_ok` (pbd_set_depth_prune; NULL: off): only the cells whose byte is set are eligible.
+static int enqueue_root_nms(pbd_handle *h, Plan &P, int nframes, int sz, const uint8_t *root_ok, hipStream_t st)
 {
     if (P.gn_sz != sz) {
         std::vector<GnPlane> tab;
@@ -1254,20 +1255,16 @@ static int enqueue_root_nms(pbd_handle *h, Plan &P, int nframes, int sz, hipStre
     GridNmsParams gp{};
     gp.planes = P.d_gn.p; gp.nplanes = (int)P.d_gn.size; gp.nframes = nframes;
     gp.frame_stride = per_frame; gp.blocks_per_frame = P.gn_blocks;
-    gp.src = h->rootv.p; gp.use_thresh = 1; gp.thresh = h->thresh; gp.sz = sz; gp.dst = h->gn_max.as<uint8_t>();
+    gp.src = h->rootv.p; gp.use_thresh = 1; gp.thresh = h->thresh; gp.mask = root_ok; gp.sz = sz; gp.dst = h->gn_max.as<uint8_t>();
     ProfScope ps(h, PBD_K_GRID_NMS, st);
     launch_grid_nms(gp, h->f64, grid_nms_lanes(sz, h->gn_lanes), st);
     return PBD_OK;
 }
 
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
-                   int capacity, hipStream_t st, bool walk_only, int root_nms)
+                   int capacity, hipStream_t st, bool walk_only, RootSel sel)
 {
     ArgminParams ap{};
-    if (root_nms > 0 && !walk_only) {
-        if (int rc = enqueue_root_nms(h, P, nframes, root_nms, st)) return rc;
-        ap.root_max = h->gn_max.as<uint8_t>();
-    }
     ap.lv = P.d_lv.p; ap.nlevels = P.nlevels; ap.NS = h->NS; ap.NC = h->NC; ap.nframes = nframes;
     ap.cell_per_frame = P.cell_per_frame;
     ap.rootv = h->rootv.p; ap.rooti = h->rooti.as<int>();
@@ -1282,9 +1279,34 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     ap.nblk = (int)std::max<long long>((ap.ntotal + argmin_find_span() - 1) / argmin_find_span(), 1);
     HIPCHK(h, h->find_blk.ensure((size_t)ap.nblk * sizeof(int)));
     ap.blk = h->find_blk.as<int>();
+    if (sel.prune && !walk_only) {   // pbd_set_depth_prune with the depth images claim_depth took for this call
+        pbd_handle::DepthBind call;   // used once: the next call binds again
+        std::swap(call, h->dpr_call);
+        if (int rc = h->dpr_tab.stage(h, call.tab.data(), call.tab.size() * sizeof(Box3dFrame))) return rc;
+        HIPCHK(h, h->dpr_ok.ensure(std::max<size_t>((size_t)ap.ntotal, 16)));
+        const DepthPruneRoots a{h->dpr_tab.as<Box3dFrame>(), call.depth, h->dprune_rule, h->dpr_ok.as<uint8_t>()};
+        ProfScope ps(h, PBD_K_DEPTH_PRUNE, st);
+        launch_depth_prune_roots(ap, a, h->f64, st);
+        ap.root_ok = a.ok;
+    }
+    if (sel.nms > 0 && !walk_only) {
+        if (int rc = enqueue_root_nms(h, P, nframes, sel.nms, ap.root_ok, st)) return rc;
+        ap.root_max = h->gn_max.as<uint8_t>();
+    }
     ProfScope ps(h, PBD_K_ARGMIN, st);
     if (!walk_only) launch_argmin_find(ap, h->f64, st);   // walk_only: the payload's records were written by the caller
     launch_argmin_walk(ap, h->f64, st);
+    return PBD_OK;
+}
+
+// pbd_set_depth_prune / pbd_depth_prune*: the rule's parameters widened, or PBD_ERR_INVALID (include/pbd.h: fx and width finite
+// and > 0, tol finite and >= 0)
+int depth_prune_rule(pbd_handle *h, const pbd_depth_prune_cfg &cfg, DepthPruneRule *rule)
+{
+    if (!(std::isfinite(cfg.fx) && cfg.fx > 0 && std::isfinite(cfg.width) && cfg.width > 0 && std::isfinite(cfg.tol) && cfg.tol >= 0))
+        return fail(h, PBD_ERR_INVALID, "depth prune: fx %g, width %g (finite, > 0), tol %g (finite, >= 0)", (double)cfg.fx,
+                    (double)cfg.width, (double)cfg.tol);
+    *rule = DepthPruneRule{(double)cfg.fx, (double)cfg.width, (double)cfg.tol};
     return PBD_OK;
 }
 
@@ -1332,11 +1354,11 @@ int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, 
 namespace {
 
 int enqueue_argmin_readback(pbd_handle *h, Plan &P, int nframes, const float *d_scales, pbd_handle::CandBuf &cb, bool post,
-                            int root_nms, hipStream_t st)
+                            RootSel sel, hipStream_t st)
 {
     const int stride = ::stride(h), cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, cb.payload.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
-    if (int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st, false, root_nms)) return rc;
+    if (int rc = enqueue_argmin(h, P, nframes, d_scales, 0, cb.payload.as<int32_t>(), cap, st, false, sel)) return rc;
     cb.nms = post;
     if (post) {
         HIPCHK(h, cb.post.ensure(((size_t)cap * stride + 1) * sizeof(int32_t)));
@@ -1381,10 +1403,10 @@ int argmin_deliver(pbd_handle *h, pbd_handle::CandBuf &cb, hipStream_t st, int32
     return PBD_OK;
 }
 
-int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, int root_nms, int32_t *cand, int capacity,
+int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool post, RootSel sel, int32_t *cand, int capacity,
                int *ncand)
 {
-    if (int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, root_nms, h->stream)) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, d_scales, h->cb, post, sel, h->stream)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     return argmin_deliver(h, h->cb, h->stream, cand, capacity, ncand);
@@ -1395,13 +1417,42 @@ int run_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, bool 
 // the caller's
 int enqueue_argmin_out(pbd_handle *h, Plan &P, int nframes, int frame_offset, int32_t *d_payload, int capacity)
 {
-    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.p, frame_offset, d_payload, capacity, h->stream, false, h->root_nms);
+    if (!h->nms) return enqueue_argmin(h, P, nframes, P.d_scales.p, frame_offset, d_payload, capacity, h->stream, false, root_sel(h));
     const int cap = std::max(h->cfg.max_candidates, 1);
     HIPCHK(h, h->cb.payload.ensure(((size_t)cap * stride(h) + 1) * sizeof(int32_t)));
-    if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream, false, h->root_nms))
+    if (int rc = enqueue_argmin(h, P, nframes, P.d_scales.p, 0, h->cb.payload.as<int32_t>(), cap, h->stream, false, root_sel(h)))
         return rc;
     return enqueue_post(h, P.kind == 2 ? P.mixed_frames : nframes, P.rows, P.cols, h->nms_overlap, h->cb.payload.as<int32_t>(), cap,
                         frame_offset, d_payload, capacity, h->stream, P.kind == 2 ? &P : nullptr);
+}
+
+// The first step of every entry point pbd_bind_depth* lists: the call consumes the binding.  Pruning off: dropped unused; a
+// binding whose frame count or sizes differ from the call's (size(f) = {rows, cols} of frame f) is refused and dropped; else
+// it becomes h->dpr_call, which the call's enqueue_argmin uses (root_sel).  A call refused later leaves it to the next claim.
+template <class Size> int claim_depth(pbd_handle *h, int nframes, Size size)
+{
+    pbd_handle::DepthBind b;
+    std::swap(b, h->dpr_bound);
+    h->dpr_call = pbd_handle::DepthBind{};
+    if (b.tab.empty() || !h->dprune) return PBD_OK;
+    if ((int)b.tab.size() != nframes)
+        return fail(h, PBD_ERR_INVALID, "%d depth images are bound, the call has %d frames", (int)b.tab.size(), nframes);
+    for (int f = 0; f < nframes; ++f) {
+        const std::pair<int, int> s = size(f);
+        if (b.tab[f].rows != s.first || b.tab[f].cols != s.second)
+            return fail(h, PBD_ERR_INVALID, "frame %d: the bound depth image is %dx%d, the frame %dx%d", f, b.tab[f].rows, b.tab[f].cols,
+                        s.first, s.second);
+    }
+    h->dpr_call = std::move(b);
+    return PBD_OK;
+}
+int claim_depth(pbd_handle *h, int nframes, int rows, int cols)
+{
+    return claim_depth(h, nframes, [&](int) { return std::make_pair(rows, cols); });
+}
+int claim_depth(pbd_handle *h, int nframes, const pbd_frame *frames)
+{
+    return claim_depth(h, nframes, [&](int f) { return std::make_pair(frames[f].rows, frames[f].cols); });
 }
 
 // Frames of a call: on the host (`host[i]`, rows `stride` bytes apart; uploaded to h->frames by enqueue_features) or
@@ -1488,9 +1539,10 @@ int detect_sync(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int c
                 int *ncand)
 {
     Plan *P = nullptr;
+    if (int rc = claim_depth(h, nframes, rows, cols)) return rc;
     if (int rc = check_detect(h, nframes, src, rows, cols, cn, depth, &P)) return rc;
     if (int rc = enqueue_detect(h, *P, nframes, src, cn, depth)) return rc;
-    return run_argmin(h, *P, nframes, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
+    return run_argmin(h, *P, nframes, P->d_scales.p, h->nms, root_sel(h), cand, capacity, ncand);
 }
 
 // copies n responses from the device to dst as T; in PBD_CONV_MFMA_F16 mode the device holds fp16, widened to float here
@@ -1962,6 +2014,16 @@ int pbd_set_root_nms(pbd_handle *h, int sz)
     });
 }
 
+int pbd_set_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (!cfg) { h->dprune = false; return PBD_OK; }
+        if (int rc = depth_prune_rule(h, *cfg, &h->dprune_rule)) return rc;   // (a refused cfg leaves the setting as it was)
+        h->dprune = true;                 // the resident result stays: it does not depend on the setting
+        return PBD_OK;
+    });
+}
+
 int pbd_set_walk(pbd_handle *h, int mode)
 {
     return entry(h, true, kIdle, [&]() -> int {
@@ -2156,7 +2218,7 @@ int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacit
         Plan &P = *h->res.plan;
         HIPCHK(h, h->scales_tmp.ensure(sizeof(float) * PBD_MAX_LEVELS));
         HIPCHK(h, hipMemcpyAsync(h->scales_tmp.p, scales, sizeof(float) * P.nlevels, hipMemcpyHostToDevice, h->stream));
-        return run_argmin(h, P, h->res.frames, h->scales_tmp.as<float>(), false, 0, cand, capacity, ncand);   // no suppression, no root NMS (DynamicProgram::argmin)
+        return run_argmin(h, P, h->res.frames, h->scales_tmp.as<float>(), false, RootSel{}, cand, capacity, ncand);   // no suppression, no root NMS (DynamicProgram::argmin)
     });
 }
 
@@ -2196,7 +2258,7 @@ static int submit_enqueue(pbd_handle *h, pbd_handle::Slot &S, Plan &P, int nfram
 {
     if (!S.done.p) HIPCHK(h, hipEventCreateWithFlags(&S.done.p, hipEventDisableTiming));
     if (int rc = enqueue_detect(h, P, nframes, FrameSrc{nullptr, 0, d_frames}, channels, kDepth8U)) return rc;
-    if (int rc = enqueue_argmin_readback(h, P, nframes, P.d_scales.p, S.cb, h->nms, h->root_nms, h->stream)) return rc;
+    if (int rc = enqueue_argmin_readback(h, P, nframes, P.d_scales.p, S.cb, h->nms, root_sel(h), h->stream)) return rc;
     HIPCHK(h, hipEventRecord(S.done.p, h->stream));
     HIPCHK(h, hipGetLastError());
     h->nsubmitted += 1;
@@ -2209,6 +2271,7 @@ int pbd_detect_batch_submit(pbd_handle *h, int nframes, const void *const *imgs,
     return entry(h, imgs, kBusyOk, [&]() -> int {
         if (h->nsubmitted - h->nwaited >= 2) return fail(h, PBD_ERR_STATE, "two batches are already in flight: call pbd_detect_batch_wait first");
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, rows, cols)) return rc;
         if (int rc = check_detect(h, nframes, FrameSrc{imgs, stride_bytes, nullptr}, rows, cols, channels, kDepth8U, &P)) return rc;
         const size_t row_bytes = (size_t)cols * channels, frame_bytes = row_bytes * rows, bytes = frame_bytes * nframes;
         pbd_handle::Slot &S = h->slot[h->nsubmitted & 1];
@@ -2235,6 +2298,7 @@ int pbd_detect_batch_device_submit(pbd_handle *h, int nframes, const void *d_fra
     return entry(h, d_frames, kBusyOk, [&]() -> int {
         if (h->nsubmitted - h->nwaited >= 2) return fail(h, PBD_ERR_STATE, "two batches are already in flight: call pbd_detect_batch_wait first");
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, rows, cols)) return rc;
         if (int rc = check_detect(h, nframes, FrameSrc{nullptr, 0, d_frames}, rows, cols, channels, kDepth8U, &P)) return rc;
         return submit_enqueue(h, h->slot[h->nsubmitted & 1], *P, nframes, d_frames, channels);
     });
@@ -2263,6 +2327,7 @@ int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
         const FrameSrc src{nullptr, 0, d_frames};
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, rows, cols)) return rc;
         if (int rc = check_detect(h, nframes, src, rows, cols, channels, kDepth8U, &P)) return rc;
         if (int rc = enqueue_detect(h, *P, nframes, src, channels, kDepth8U)) return rc;
         if (int rc = enqueue_argmin_out(h, *P, nframes, frame_offset, d_payload, capacity)) return rc;
@@ -2277,6 +2342,9 @@ int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, i
         const Resident &r = h->res;
         if (!r.plan || !r.dp || (r.plan->kind != 0 && r.plan->kind != 2)) return fail(h, PBD_ERR_STATE, "no detect result is resident on the device");
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        const Plan &RP = *r.plan;   // the resident frames' sizes: a mixed plan's own, else the plan's for every frame
+        if (int rc = RP.kind == 2 ? claim_depth(h, RP.mixed_frames, [&](int f) { return std::make_pair(RP.fdim[f].x, RP.fdim[f].y); })
+                                  : claim_depth(h, r.frames, RP.rows, RP.cols)) return rc;
         if (int rc = enqueue_argmin_out(h, *r.plan, r.frames, frame_offset, d_payload, capacity)) return rc;
         HIPCHK(h, hipGetLastError());
         return PBD_OK;
@@ -2289,9 +2357,10 @@ int pbd_detect_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int c
 {
     return entry(h, frames && cand && ncand, kIdle, [&]() -> int {
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, frames)) return rc;
         if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, true, &P)) return rc;
         if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, true)) return rc;
-        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, root_sel(h), cand, capacity, ncand);
     });
 }
 
@@ -2300,9 +2369,10 @@ int pbd_detect_frames_device(pbd_handle *h, int nframes, const pbd_frame *frames
 {
     return entry(h, frames && cand && ncand, kIdle, [&]() -> int {
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, frames)) return rc;
         if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, false, &P)) return rc;
         if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, false)) return rc;
-        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, h->root_nms, cand, capacity, ncand);
+        return run_argmin(h, *P, 1, P->d_scales.p, h->nms, root_sel(h), cand, capacity, ncand);
     });
 }
 
@@ -2312,6 +2382,7 @@ int pbd_detect_frames_device_out(pbd_handle *h, int nframes, const pbd_frame *fr
     return entry(h, frames && d_payload, kIdle, [&]() -> int {
         if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
         Plan *P = nullptr;
+        if (int rc = claim_depth(h, nframes, frames)) return rc;
         if (int rc = check_frames_mixed(h, nframes, frames, channels, depth_code, false, &P)) return rc;
         if (int rc = enqueue_detect_mixed(h, *P, nframes, frames, channels, depth_code, false)) return rc;
         if (int rc = enqueue_argmin_out(h, *P, 1, frame_offset, d_payload, capacity)) return rc;
@@ -2398,7 +2469,7 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
                                              "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick",
-                                             "k_grid_nms"};
+                                             "k_grid_nms", "k_depth_prune"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

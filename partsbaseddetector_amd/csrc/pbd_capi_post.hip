@@ -212,6 +212,31 @@ int enqueue_dc(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code
     return PBD_OK;
 }
 
+// ---- scale-depth pruning of a caller's list (pbd_depth_prune*; pbd_kernels_depthprune.hip)
+// the frame table, the decision per record and the depth-consistency filter's compaction on the handle's stream: payload d_in
+// (capacity records) -> d_out (out_cap records)
+int enqueue_depth_prune(pbd_handle *h, const std::vector<Box3dFrame> &tab, int depth_code, const DepthPruneRule &rule,
+                        const int32_t *d_in, int capacity, int frame_offset, int32_t *d_out, int out_cap)
+{
+    const int cap = std::max(capacity, 0), blocks = dc_record_blocks(cap);
+    DcParams p{};
+    if (int rc = carve(h, h->dpl_ws, [&](Carve &c) {
+            p.flag = c.take<int>((size_t)blocks * 256 * sizeof(int));
+            p.blk = c.take<int>((size_t)blocks * sizeof(int));
+        })) return rc;
+    if (int rc = h->dpl_tab.stage(h, tab.data(), tab.size() * sizeof(Box3dFrame))) return rc;
+    p.in = d_in; p.in_cap = cap; p.stride = stride(h); p.max_parts = h->max_parts;
+    p.frames = h->dpl_tab.as<Box3dFrame>(); p.nframes = (int)tab.size(); p.frame_offset = frame_offset;
+    p.depth = depth_code;
+    p.out = d_out; p.out_cap = std::max(out_cap, 0);
+    {
+        ProfScope ps(h, PBD_K_DEPTH_PRUNE, h->stream);
+        launch_depth_prune_records(p, rule, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // ---- grid maxima of a caller's planes (pbd_grid_nms*; pbd_kernels_gridnms.hip)
 // every check of a call; *total = the elements of all planes
 int check_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *cols, int real_code, const void *src, const void *dst,
@@ -847,6 +872,80 @@ int pbd_depth_consistency_device(pbd_handle *h, int nframes, const pbd_frame *d_
         if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
         if (int rc = check_depth_frames(h, nframes, d_depth, depth_code, false, nullptr, nullptr, &zfactor)) return rc;
         return enqueue_dc(h, depth_table(nframes, d_depth), depth_code, zfactor, d_payload, capacity, frame_offset, d_out, out_capacity);
+    });
+}
+
+// The depth images of the next detect call (pbd_set_depth_prune).  See include/pbd.h.
+int pbd_bind_depth(pbd_handle *h, int nframes, const pbd_frame *depth, int depth_code)
+{
+    return entry(h, nframes == 0 || depth, kBusyOk, [&]() -> int {
+        h->dpr_bound = pbd_handle::DepthBind{};
+        if (nframes == 0) return PBD_OK;
+        if (int rc = check_depth_frames(h, nframes, depth, depth_code, true)) return rc;
+        // dense rows in a buffer of the binding's own, behind the work already queued (a batch in flight may still read it)
+        const size_t es = depth_size(depth_code);
+        size_t total = 0;
+        for (int f = 0; f < nframes; ++f) total += (size_t)depth[f].rows * depth[f].cols * es;
+        HIPCHK(h, h->dpr_depth.ensure(total + 8));
+        std::vector<pbd_frame> packed(nframes);
+        size_t off = 0;
+        for (int f = 0; f < nframes; ++f) {
+            const size_t row_bytes = (size_t)depth[f].cols * es;
+            uint8_t *dst = h->dpr_depth.as<uint8_t>() + off;
+            HIPCHK(h, hipMemcpy2DAsync(dst, row_bytes, depth[f].data, depth[f].stride_bytes, row_bytes, depth[f].rows,
+                                       hipMemcpyHostToDevice, h->stream));
+            packed[f] = pbd_frame{dst, depth[f].rows, depth[f].cols, row_bytes};
+            off += row_bytes * depth[f].rows;
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));   // "copied now": the caller's images may go when the call returns
+        h->dpr_bound.tab = depth_table(nframes, packed.data());
+        h->dpr_bound.depth = depth_code;
+        return PBD_OK;
+    });
+}
+
+int pbd_bind_depth_device(pbd_handle *h, int nframes, const pbd_frame *d_depth, int depth_code)
+{
+    return entry(h, nframes == 0 || d_depth, kBusyOk, [&]() -> int {
+        h->dpr_bound = pbd_handle::DepthBind{};
+        if (nframes == 0) return PBD_OK;
+        if (int rc = check_depth_frames(h, nframes, d_depth, depth_code, false)) return rc;
+        h->dpr_bound.tab = depth_table(nframes, d_depth);
+        h->dpr_bound.depth = depth_code;
+        return PBD_OK;
+    });
+}
+
+// plausible(rect, depth, fx, width, tol) per record of a caller's list.  See include/pbd.h.
+int pbd_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, const pbd_frame *depth, int depth_code,
+                    const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity, int *nout)
+{
+    return entry(h, cfg && depth && nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
+        DepthPruneRule rule;
+        if (int rc = depth_prune_rule(h, *cfg, &rule)) return rc;
+        if (int rc = check_depth_frames(h, nframes, depth, depth_code, true)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecPlain)) return rc;
+        if (ncand == 0) return PBD_OK;
+        std::vector<Box3dFrame> tab;   // the depth images packed with dense rows (the pbd_boxes3d host form's buffer)
+        if (int rc = upload_depth_host(h, nframes, depth, depth_code, nullptr, nullptr, tab)) return rc;
+        return host_list_call(h, h->dc_rec, h->dc_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_depth_prune(h, tab, depth_code, rule, din, ncand, frame_offset, dout, ncand);
+        });
+    });
+}
+
+int pbd_depth_prune_device(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, const pbd_frame *d_depth, int depth_code,
+                           const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity)
+{
+    return entry(h, cfg && d_depth && d_payload && d_out, kIdle, [&]() -> int {
+        if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
+        DepthPruneRule rule;
+        if (int rc = depth_prune_rule(h, *cfg, &rule)) return rc;
+        if (int rc = check_depth_frames(h, nframes, d_depth, depth_code, false)) return rc;
+        return enqueue_depth_prune(h, depth_table(nframes, d_depth), depth_code, rule, d_payload, capacity, frame_offset, d_out,
+                                   out_capacity);
     });
 }
 

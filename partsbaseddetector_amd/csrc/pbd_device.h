@@ -31,6 +31,10 @@ __device__ inline const int32_t *record_part(const int32_t *r, int k) { return r
 
 // records of a device payload (word 0 = the count found, which may exceed the capacity or be a negative status)
 __device__ inline int payload_count(const int32_t *in, int in_cap) { return max(min(in[0], in_cap), 0); }
+// the list filters (pbd_depth_consistency*, pbd_depth_prune*): a negative or too-large word 0 is no complete list -- no record is
+// read and the output's word 0 is -1
+__device__ inline bool dc_overflow(const DcParams &p) { return p.in[0] < 0 || p.in[0] > p.in_cap; }
+__device__ inline int dc_count(const DcParams &p) { return dc_overflow(p) ? 0 : p.in[0]; }
 
 // cv::Rect operator& in 64 bits (an empty intersection is Rect())
 __device__ inline void rect_and64(long long &x, long long &y, long long &w, long long &h, long long bx, long long by, long long bw,

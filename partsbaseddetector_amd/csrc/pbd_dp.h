@@ -122,20 +122,27 @@ template <typename R> __device__ __forceinline__ PartRect part_rect(int x, int y
     return {min(x1, x2), min(y1, y2), max(x1, x2), max(y1, y2)};
 }
 
-// the header of a root's record from its index `rem` into the frame's rootv block ([level][component][y][x]; levels [l0, l1)):
-// frame, component, level, x, y, the score as float (Candidate::confidence_ is float for every T, include/Candidate.hpp:72),
-// no parts yet, and the root's mixture for the walk
-template <typename R>
-__device__ __forceinline__ void root_record(int32_t *rec, const LevelDesc *lv, int l0, int l1, int NC, int frame, long long rem, R score,
-                                            int mixture)
+// the root cell at index `rem` of a frame's rootv block ([level][component][y][x]; levels [l0, l1))
+struct RootCell { int level, comp, x, y; };
+__device__ __forceinline__ RootCell root_cell(const LevelDesc *lv, int l0, int l1, int NC, long long rem)
 {
     const int l = level_of(lv, l0, l1, rem, NC);
     const LevelDesc d = lv[l];
     const int HW = d.rows * d.cols;
     const int rem2 = (int)(rem - d.cell_off * NC);
     const int comp = rem2 / HW, local = rem2 - comp * HW;
-    rec[0] = frame; rec[1] = comp; rec[2] = l;
-    rec[3] = local % d.cols; rec[4] = local / d.cols;
+    return {l, comp, local % d.cols, local / d.cols};
+}
+
+// the header of a root's record from its index `rem` into the frame's rootv block: frame, component, level, x, y, the score as
+// float (Candidate::confidence_ is float for every T, include/Candidate.hpp:72), no parts yet, and the root's mixture for the walk
+template <typename R>
+__device__ __forceinline__ void root_record(int32_t *rec, const LevelDesc *lv, int l0, int l1, int NC, int frame, long long rem, R score,
+                                            int mixture)
+{
+    const RootCell rc = root_cell(lv, l0, l1, NC, rem);
+    rec[0] = frame; rec[1] = rc.comp; rec[2] = rc.level;
+    rec[3] = rc.x; rec[4] = rc.y;
     rec[5] = __float_as_int((float)score);
     rec[6] = 0;
     rec[7] = mixture;

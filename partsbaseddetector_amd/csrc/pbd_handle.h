@@ -372,7 +372,19 @@ struct Handle : ErrCtx {
     float nms_overlap = 0.f;
     int root_nms = 0;                // grid NMS of the root scores before the find (pbd_set_root_nms): window size, 0 = off; read at enqueue
     int gn_lanes = 0;                // forced lanes per block of k_grid_nms, 1 or 64; 0: by sz (pbd_debug_set_option)
-    DtOptions dt_opt;                // forced distance-transform launch choices (pbd_debug_set_option)
+    // scale-depth pruning of the roots before the find (pbd_set_depth_prune; read at enqueue) and the depth images bound to the
+    // next detect call (pbd_bind_depth*): their frame table, the host form's copies, the byte per root cell.  claim_depth moves
+    // a binding that fits the call into `dpr_call` (on the device: dpr_tab); enqueue_argmin uses it once
+    bool dprune = false;
+    DepthPruneRule dprune_rule{};
+    struct DepthBind { std::vector<Box3dFrame> tab; int depth = 0; } dpr_bound, dpr_call;
+    StagedTable dpr_tab;
+    DevBuf dpr_depth, dpr_ok;
+    // pbd_depth_prune*: the frame table, the workspace (flags and block counts); the host form shares pbd_depth_consistency's
+    // image, record and output buffers
+    StagedTable dpl_tab;
+    DevBuf dpl_ws;
+    DtOptions dt_opt;               // forced distance-transform launch choices (pbd_debug_set_option)
     int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
 
     // workspace
@@ -632,10 +644,16 @@ inline pbd_handle *resident_owner(pbd_handle *h) { return h->res.latent && h->la
 
 // ---- defined in pbd_capi.hip, called from the other files of the entry layer (see the definitions)
 void post_canvas_plan(Plan &M);
+// what restricts the roots a find lists beyond the threshold: the window of pbd_set_root_nms (0: off) and whether the depth images
+// claimed for the call (h->dpr_call) prune them (pbd_set_depth_prune).  The detect entry points pass root_sel(h); DynamicProgram::
+// argmin, the latent search and the trainers' re-walks pass none
+struct RootSel { int nms = 0; bool prune = false; };
+inline RootSel root_sel(const pbd_handle *h) { return {h->root_nms, !h->dpr_call.tab.empty()}; }
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload, int capacity,
-                   hipStream_t st, bool walk_only = false, int root_nms = 0);
+                   hipStream_t st, bool walk_only = false, RootSel sel = {});
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
                  int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr, int in_offset = 0, int *bad = nullptr);
+int depth_prune_rule(pbd_handle *h, const pbd_depth_prune_cfg &cfg, DepthPruneRule *rule);
 int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan);
 int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
                          const LatentParams *mask = nullptr);

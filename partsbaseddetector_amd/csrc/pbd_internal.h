@@ -273,6 +273,7 @@ struct ArgminParams {
     // mixed-size calls: virtual level -> (frame of the call, level of that frame's pyramid); NULL: the record's own frame / level
     const int *lv_frame, *lv_local;
     const uint8_t *root_max;      // pbd_set_root_nms: a byte per root cell, laid out as rootv; a hit also needs it non-zero (NULL: off)
+    const uint8_t *root_ok;       // pbd_set_depth_prune: likewise, the cells whose box size agrees with the depth image (NULL: off)
 };
 
 // per-frame sort + non-maxima suppression of an argmin payload (pbd_set_nms; pbd_kernels_post.hip)
@@ -444,7 +445,7 @@ struct GridNmsParams {
     long long frame_stride, blocks_per_frame;
     const void *src;              // R
     const uint8_t *mask;          // NULL: every element that is not NaN is eligible
-    int use_thresh;               // the detect path: eligible = src > (R)thresh, no mask
+    int use_thresh;               // the detect path: eligible = src > (R)thresh; with a mask, those of them whose byte is non-zero
     float thresh;
     int sz;
     uint8_t *dst;                 // 0 / 255, every byte of every plane written
@@ -457,6 +458,15 @@ inline GnPlane grid_nms_plane(long long off, int rows, int cols, int sz, long lo
     *blocks += nbx * nby;
     return g;
 }
+// scale-depth plausibility of a root box (pbd_set_depth_prune, pbd_depth_prune*; pbd_kernels_depthprune.hip)
+struct DepthPruneRule { double fx, width, tol; };   // pbd_depth_prune_cfg, widened
+struct DepthPruneRoots {          // the plane form, next to the call's ArgminParams
+    const Box3dFrame *frames;     // [frames of the call] depth images; a mixed-size call's virtual level gives the frame
+    int depth;                    // kDepth8U / 16U / 32F / 64F
+    DepthPruneRule rule;
+    uint8_t *ok;                  // 1 / 0 per root cell, laid out as rootv; every byte written
+};
+
 constexpr int kGnWaveSz = 7;      // sz below it: one lane per block; from it on: one wave per block (profiles/grid_nms/README.md)
 
 // ---- kernel launches and their timing -------------------------------------------------------
@@ -559,6 +569,12 @@ void launch_boxes3d(const Boxes3dParams &p, int grid, hipStream_t s);
 // one step of the depth-consistency filter (kDcStep*, in this order); dc_record_blocks: workgroups of the compaction (p.blk entries)
 void launch_depth_consistency(const DcParams &p, bool f64, int step, hipStream_t s);
 int dc_record_blocks(int in_cap);
+// the compaction alone: the records whose p.flag is set (p.blk: their count per dc_record_blocks block) into p.out, in order
+void launch_dc_emit(const DcParams &p, hipStream_t s);
+// p.root_ok's bytes for every root cell of the call (a.ok): above the threshold and plausible under a.rule
+void launch_depth_prune_roots(const ArgminParams &p, const DepthPruneRoots &a, bool f64, hipStream_t s);
+// the record form: p.flag / p.blk from each record's root rectangle (p.in, p.frames, p.depth), then launch_dc_emit
+void launch_depth_prune_records(const DcParams &p, const DepthPruneRule &rule, hipStream_t s);
 // the grid maxima of p's planes; lanes per block: grid_nms_lanes(sz, forced) = 1 or 64 (forced: 0 = by sz)
 int grid_nms_lanes(int sz, int forced);
 void launch_grid_nms(const GridNmsParams &p, bool f64, int lanes, hipStream_t s);

@@ -56,9 +56,6 @@ template <int D, bool F64> __device__ inline double dc_unkey(unsigned long long 
     return (double)float_unkey((uint32_t)k);
 }
 
-__device__ inline bool dc_overflow(const DcParams &p) { return p.in[0] < 0 || p.in[0] > p.in_cap; }
-__device__ inline int dc_count(const DcParams &p) { return dc_overflow(p) ? 0 : p.in[0]; }
-
 // a record of this call: frame index in range, a known component, nparts its component's part count (1..max parts)
 __device__ inline bool dc_record(const DcParams &p, const int32_t *r, int *frame, int *p0, int *np)
 {
@@ -332,6 +329,11 @@ void launch_dc_select_t(const DcParams &p, int ntask, hipStream_t s)
 
 int dc_record_blocks(int in_cap) { return std::max((in_cap + kDcThreads - 1) / kDcThreads, 1); }
 
+void launch_dc_emit(const DcParams &p, hipStream_t s)
+{
+    PBD_LAUNCH(k_dc_emit, dim3(dc_record_blocks(p.in_cap)), dim3(kDcThreads), 0, s, p);
+}
+
 void launch_depth_consistency(const DcParams &p, bool f64, int step, hipStream_t s)
 {
     const long long ntask = (long long)std::max(p.in_cap, 0) * p.max_parts;
@@ -350,7 +352,7 @@ void launch_depth_consistency(const DcParams &p, bool f64, int step, hipStream_t
         const int blocks = dc_record_blocks(p.in_cap);
         if (f64) PBD_LAUNCH(k_dc_decide<true>, dim3(blocks), dim3(kDcThreads), 0, s, p);
         else PBD_LAUNCH(k_dc_decide<false>, dim3(blocks), dim3(kDcThreads), 0, s, p);
-        PBD_LAUNCH(k_dc_emit, dim3(blocks), dim3(kDcThreads), 0, s, p);
+        launch_dc_emit(p, s);
         break;
     }
     }

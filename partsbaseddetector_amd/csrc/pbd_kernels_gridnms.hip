@@ -10,7 +10,8 @@
 //       3. the block's bytes of dst are written: 255 at a kept candidate, 0 elsewhere -- the blocks tile the plane, so dst needs no
 //          clearing pass
 //     Elig says which cells take part: every one that is not NaN, those with a non-zero mask byte, or those above a threshold
-//     (the detect path: `rootv > thresh`, the find's own expression, so no mask plane is ever written).
+//     (the detect path: `rootv > thresh`, the find's own expression, so no mask plane is ever written; with pbd_set_depth_prune
+//     those above the threshold whose byte of the plausibility plane is set).
 // Nothing is staged in LDS and nothing depends on sz but the loops' lengths: any sz runs.  The grid is capped; the groups
 // stride over the (frame, plane, block) triples.
 #include "pbd_device.h"
@@ -34,6 +35,11 @@ struct GnMask {
 template <typename R> struct GnAbove {
     R thresh;
     __device__ bool operator()(R v, size_t) const { return v > thresh; }   // NaN compares false
+};
+template <typename R> struct GnAboveMask {   // pbd_set_depth_prune with root NMS: the plausible cells above the threshold
+    R thresh;
+    const uint8_t *mask;
+    __device__ bool operator()(R v, size_t i) const { return v > thresh && mask[i] != 0; }
 };
 
 // the better of two block candidates: an eligible one over none, the larger value, then the earlier cell
@@ -143,7 +149,8 @@ void launch_grid_nms(const GridNmsParams &p, bool f64, int lanes, hipStream_t s)
     if (p.blocks_per_frame <= 0 || p.nframes <= 0) return;
     auto run = [&](auto r) {
         using R = decltype(r);
-        if (p.use_thresh) gn_launch<R>(p, GnAbove<R>{(R)p.thresh}, lanes, s);
+        if (p.use_thresh && p.mask) gn_launch<R>(p, GnAboveMask<R>{(R)p.thresh, p.mask}, lanes, s);
+        else if (p.use_thresh) gn_launch<R>(p, GnAbove<R>{(R)p.thresh}, lanes, s);
         else if (p.mask) gn_launch<R>(p, GnMask{p.mask}, lanes, s);
         else gn_launch<R>(p, GnAll{}, lanes, s);
     };

@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -520,6 +520,58 @@ class Handle:
         records into the payload at d_out_ptr (word 0 = kept count, -1 for an overflowed input); asynchronous"""
         self.check(self.lib.pbd_depth_consistency_device(self.h, len(descs), _lib.frame_array(descs), depth_code, float(zfactor),
                                                          d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
+
+    @staticmethod
+    def _depth_frames(depths: Sequence[np.ndarray]):
+        """(arrays kept alive, pbd_frame[], depth code) of 2-D depth images of one dtype, rows of any pitch"""
+        dt = np.dtype(depths[0].dtype)
+        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
+            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
+        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
+        return ds, _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds]), _lib.DEPTH_CODE[dt]
+
+    @staticmethod
+    def _prune_cfg(fx: float, width: float, tol: float):
+        return C.byref(_lib.CDepthPruneCfg(float(fx), float(width), float(tol)))
+
+    def set_depth_prune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
+        """pbd_set_depth_prune: with depth images bound (bind_depth), every detect* call of this handle lists only the roots whose
+        rectangle is depthprune.plausible(rect, depth, fx, width, tol); fx None: off (the default)"""
+        self.check(self.lib.pbd_set_depth_prune(self.h, None if fx is None else self._prune_cfg(fx, width, tol)))
+
+    def bind_depth(self, depths: Optional[Sequence[np.ndarray]]) -> None:
+        """pbd_bind_depth: the depth images (one per frame, the frame's rows x cols) of the NEXT detect* call or argmin_device_out,
+        copied now; None or []: unbind"""
+        if not depths:
+            self.check(self.lib.pbd_bind_depth(self.h, 0, None, 0))
+            return
+        ds, descs, code = self._depth_frames(depths)
+        self.check(self.lib.pbd_bind_depth(self.h, len(ds), descs, code))
+
+    def bind_depth_device(self, descs, depth_code: int) -> None:
+        """pbd_bind_depth_device: the same for depth frames (device pointer, rows, cols, pitch) read in place by the next call"""
+        self.check(self.lib.pbd_bind_depth_device(self.h, len(descs), _lib.frame_array(descs) if len(descs) else None, depth_code))
+
+    def depth_prune(self, depths: Sequence[np.ndarray], records: np.ndarray, fx: float, width: float, tol: float,
+                    frame_offset: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_depth_prune: the records (n, stride) whose root rectangle is plausible in their frame's depth image, in input order,
+        decided on the device (equal to depthprune.filter_records)"""
+        ds, descs, code = self._depth_frames(depths)
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(self.lib.pbd_depth_prune(self.h, self._prune_cfg(fx, width, tol), len(ds), descs, code,
+                                            rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap,
+                                            C.byref(n)))
+        return out[:n.value].copy()
+
+    def depth_prune_device(self, descs, depth_code: int, fx: float, width: float, tol: float, d_payload_ptr: int, capacity: int,
+                           frame_offset: int, d_out_ptr: int, out_capacity: int) -> None:
+        """pbd_depth_prune_device: the records of a device payload, depth frames (device pointer, rows, cols, pitch), the kept
+        records into the payload at d_out_ptr (word 0 = kept count, -1 for an overflowed input); asynchronous"""
+        self.check(self.lib.pbd_depth_prune_device(self.h, self._prune_cfg(fx, width, tol), len(descs), _lib.frame_array(descs),
+                                                   depth_code, d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
 
     def suppress(self, im_shapes, overlap: float, records: np.ndarray, frame_offset: int = 0,
                  capacity: Optional[int] = None) -> np.ndarray:
@@ -1029,6 +1081,7 @@ class PartsBasedDetector:
         self._walk = "reference"
         self._root_nms = 0                         # setRootNMS: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
+        self._dprune: Optional[Tuple[float, float, float]] = None   # setDepthPrune: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
         self.hd: Optional[Handle] = None
         self._name = ""
@@ -1054,6 +1107,8 @@ class PartsBasedDetector:
             self.hd.set_walk(self.WALKS[self._walk])
         if self._root_nms:
             self.hd.set_root_nms(self._root_nms)
+        if self._dprune is not None:
+            self.hd.set_depth_prune(*self._dprune)
         self._name = getattr(model, "name", "")
         self.features_ = HOGFeatures(self.hd)
         self.convolution_engine_ = SpatialConvolutionEngine(self.hd)
@@ -1089,6 +1144,43 @@ class PartsBasedDetector:
         """nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp) on the device: the uint8 plane of 0 / 255 (pbd_grid_nms)"""
         self._need()
         return self.hd.grid_nms([src], sz, None if mask is None else [mask])[0]
+
+    def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
+        """the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93) from now on
+        (pbd_set_depth_prune; kept across distributeModel): a call that is given depth images -- detect(im, depth), depths= of
+        detect_batch / detect_frames / submit_batch, depth= of detect_regions -- walks and returns only the roots whose box width
+        agrees with the depth under it (depthprune.plausible: fx in pixels, width of the root footprint in depth units, relative
+        tolerance tol); fx None: off (the default).  Without depth images nothing is pruned."""
+        cfg = None if fx is None else (float(fx), float(width), float(tol))
+        if cfg is not None and not (all(math.isfinite(v) for v in cfg) and cfg[0] > 0 and cfg[1] > 0 and cfg[2] >= 0):
+            raise PbdError(-1, f"depth prune: fx {fx}, width {width} (finite, > 0), tol {tol} (finite, >= 0)")
+        if self.hd is not None:
+            self.hd.set_depth_prune(*(cfg or (None,)))
+        self._dprune = cfg
+
+    def _bind(self, depths) -> None:
+        """the depth images of the next detect call, when pruning is on and the caller gave any"""
+        if self._dprune is not None and depths is not None:
+            self.hd.bind_depth([np.asarray(d) for d in depths])
+
+    def depthPrune(self, candidates: Sequence[Candidate], depths, fx: float, width: float, tol: float = 0.3) -> List[Candidate]:
+        """the candidates whose root box agrees with the depth under it, in order, decided on the device (pbd_depth_prune).
+        depths: the depth image of every frame index the candidates carry (one image for one frame).  Equal to
+        depthprune.filter_records."""
+        self._need()
+        if isinstance(depths, np.ndarray):
+            depths = [depths]
+        cands = list(candidates)
+        if not cands:
+            return []
+        rec = self.hd.pack_candidates(cands)
+        kept = self.hd.depth_prune(list(depths), rec, fx, width, tol)
+        keep, k = [], 0
+        for i, c in enumerate(cands):          # the kept records are the input's, in order
+            if k < len(kept) and np.array_equal(kept[k], rec[i]):
+                keep.append(c)
+                k += 1
+        return keep
 
     def setDepthConsistency(self, zfactor: Optional[float] = 0.03) -> None:
         """detect(im, depth) then runs filterCandidatesByDepth(., depth, zfactor) before the suppression, as the reference's
@@ -1255,6 +1347,8 @@ class PartsBasedDetector:
         if overlap is not None:
             self.hd.set_nms(None)
         try:
+            if self._dprune is not None:           # prune at the roots, then the consistency filter, then the suppression
+                self.hd.bind_depth_device([(d_depth.data_ptr(), dd.shape[0], dd.shape[1], dd.strides[0])], _lib.DEPTH_CODE[dd.dtype])
             self.hd.check(self.hd.lib.pbd_detect_frames_device_out(
                 self.hd.h, 1, _lib.frame_array([(d_im.data_ptr(), rows, cols, cols * cn * im.dtype.itemsize)]), cn,
                 _lib.DEPTH_CODE[im.dtype], 0, pays[0].data_ptr(), self.hd.max_candidates))
@@ -1284,7 +1378,8 @@ class PartsBasedDetector:
         """detect(im[, depth], candidates).  `depth` is ignored as in the reference (:91-93) unless setDepthConsistency(zfactor)
         is on: then the unsuppressed candidates go through filterCandidatesByDepth(depth, zfactor) and then the suppression of
         the detector's `nms` overlap (if any), in the reference's order, on the device.  depth=None skips the filter
-        (the reference's `if (!depth.empty())`)."""
+        (the reference's `if (!depth.empty())`).  With setDepthPrune on, `depth` (the frame's rows x cols) also prunes the roots
+        before the walk: prune -> consistency filter -> suppression."""
         self._need()
         if im.dtype not in _lib.DEPTH_CODE:
             raise PbdError(-2, f"image dtype {im.dtype}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
@@ -1299,6 +1394,7 @@ class PartsBasedDetector:
         cap = capacity or self.hd.max_candidates
         buf = np.zeros(cap * self.hd.stride, np.int32)
         n = C.c_int()
+        self._bind(None if depth is None else [depth])
         if im.dtype == np.uint8:
             self.hd.check(self.hd.lib.pbd_detect(self.hd.h, im.ctypes.data, rows, cols, cn, im.strides[0], buf.ctypes.data,
                                                  cap, C.byref(n)))
@@ -1480,25 +1576,27 @@ class PartsBasedDetector:
         off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         return cen, [idx[off[i]:off[i + 1]].astype(np.int64) for i in range(len(boxes))]
 
-    def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
+    def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None, depths=None) -> List[Candidate]:
         """Equally sized frames: pbd_detect_batch (8-bit, as before).  Frames of different sizes: pbd_detect_frames, one
-        call, the frames' dtype kept when it is one of the four depths (all frames share dtype and channel count)."""
+        call, the frames' dtype kept when it is one of the four depths (all frames share dtype and channel count).
+        depths: one depth image per frame, for setDepthPrune."""
         self._need()
         if len({tuple(f.shape) for f in frames}) > 1:
-            return self.detect_frames(frames, capacity)
+            return self.detect_frames(frames, capacity, depths)
         fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None], np.uint8) for f in frames]
         rows, cols, cn = fr[0].shape
         assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
         cap = capacity or self.hd.max_candidates
         buf = np.zeros(cap * self.hd.stride, np.int32)
         n = C.c_int()
+        self._bind(depths)
         self.hd.check(self.hd.lib.pbd_detect_batch(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn,
                                                    buf.ctypes.data, cap, C.byref(n)))
         return self.hd.unpack_candidates(buf, n.value)
 
-    def detect_frames(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
+    def detect_frames(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None, depths=None) -> List[Candidate]:
         """pbd_detect_frames: frames of any sizes in one call; the records of one detect() per frame, concatenated,
-        `frame` = index in the list."""
+        `frame` = index in the list.  depths: one depth image per frame (its rows x cols), for setDepthPrune."""
         self._need()
         fr = [f if f.ndim == 3 else f[:, :, None] for f in frames]
         dt = fr[0].dtype
@@ -1513,15 +1611,18 @@ class PartsBasedDetector:
         cap = capacity or self.hd.max_candidates
         buf = np.zeros(cap * self.hd.stride, np.int32)
         n = C.c_int()
+        self._bind(depths)
         self.hd.check(self.hd.lib.pbd_detect_frames(self.hd.h, len(fr), descs, fr[0].shape[2], _lib.DEPTH_CODE[dt],
                                                     buf.ctypes.data, cap, C.byref(n)))
         return self.hd.unpack_candidates(buf, n.value)
 
-    def detect_regions(self, image, rects, capacity: Optional[int] = None) -> List[Candidate]:
+    def detect_regions(self, image, rects, capacity: Optional[int] = None, depth=None) -> List[Candidate]:
         """Regions (x, y, w, h) of one device image -- a torch uint8 tensor, HWC (or HW), on this detector's device -- in
         one pbd_detect_frames_device call, read in place.  The work is ordered behind torch's current stream.  Each
         candidate carries `frame` = index of its region and `offset` = (x, y) of that region: its boxes are in the region's
-        coordinates (as detect(im(roi))), offset them to map into the image."""
+        coordinates (as detect(im(roi))), offset them to map into the image.  depth: the image's depth map, a 2-D torch tensor
+        (uint8, int16 bits of uint16, float32 or float64) of the image's rows x cols on the same device, for setDepthPrune: every
+        region reads its own part of it in place."""
         import torch
         self._need()
         if image.dtype != torch.uint8 or image.device.type != "cuda" or image.dim() not in (2, 3):
@@ -1544,6 +1645,13 @@ class PartsBasedDetector:
         cap = capacity or self.hd.max_candidates
         buf = np.zeros(cap * self.hd.stride, np.int32)
         n = C.c_int()
+        if self._dprune is not None and depth is not None:
+            codes = {torch.uint8: 0, torch.int16: 2, torch.float32: 5, torch.float64: 6}
+            if depth.dtype not in codes or depth.device != image.device or depth.dim() != 2 or tuple(depth.shape) != (H, W) \
+                    or depth.stride(1) != 1:
+                raise PbdError(-1, "detect_regions: depth is a 2-D tensor of the image's rows x cols on its device")
+            es, dp = depth.element_size(), depth.stride(0) * depth.element_size()
+            self.hd.bind_depth_device([(depth.data_ptr() + y * dp + x * es, h, w, dp) for (x, y, w, h) in rects], codes[depth.dtype])
         self.hd.check(self.hd.lib.pbd_detect_frames_device(self.hd.h, len(descs), _lib.frame_array(descs), cn, 0,
                                                            buf.ctypes.data, cap, C.byref(n)))
         out = self.hd.unpack_candidates(buf, n.value)
@@ -1559,13 +1667,15 @@ class PartsBasedDetector:
         self.hd.check(self.hd.lib.pbd_detect_frames_device_out(self.hd.h, len(descs), _lib.frame_array(descs), cn, depth_code,
                                                                frame_offset, d_payload_ptr, capacity))
 
-    def submit_batch(self, frames: Sequence[np.ndarray]) -> None:
+    def submit_batch(self, frames: Sequence[np.ndarray], depths=None) -> None:
         """pbd_detect_batch_submit: stage + transfer + enqueue the whole path for `frames` without waiting (at most
-        two batches in flight); `wait_batch` returns the results in submission order."""
+        two batches in flight); `wait_batch` returns the results in submission order.  depths: one depth image per frame, for
+        setDepthPrune (copied before the call returns)."""
         self._need()
         fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None], np.uint8) for f in frames]
         rows, cols, cn = fr[0].shape
         assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
+        self._bind(depths)
         self.hd.check(self.hd.lib.pbd_detect_batch_submit(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn))
 
     def wait_batch(self, capacity: Optional[int] = None, raw: bool = False):
@@ -1663,10 +1773,11 @@ class DetectorPool:
         self._lane(self._submitted).submit_batch_device(d_frames_ptr, nframes, rows, cols, cn)
         self._submitted += 1
 
-    def submit_batch(self, frames: Sequence[np.ndarray]) -> None:
+    def submit_batch(self, frames: Sequence[np.ndarray], depths=None) -> None:
+        """depths: one depth image per frame, bound on the lane that takes the batch (setDepthPrune)"""
         if self.ready_before_next_submit:
             raise PbdError(-5, "DetectorPool: every lane holds an uncollected batch; call wait_batch() first")
-        self._lane(self._submitted).submit_batch(frames)
+        self._lane(self._submitted).submit_batch(frames, depths)
         self._submitted += 1
 
     def wait_batch(self, capacity: Optional[int] = None, raw: bool = False):
@@ -1681,6 +1792,11 @@ class DetectorPool:
         """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""
         for d in self.dets:
             d.setRootNMS(sz)
+
+    def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
+        """PartsBasedDetector.setDepthPrune on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setDepthPrune(fx, width, tol)
 
     def close(self) -> None:
         for d in self.dets:
