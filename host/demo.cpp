@@ -3,13 +3,15 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
 //   --root-nms SZ: only the roots that are grid maxima of their score plane within SZ cells are walked and listed
 //           (pbd_set_root_nms: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales)); not with --staged
+//   --top-k K: at most K candidates per image: only the K best roots among those the threshold (and --root-nms, --depth-prune) leave
+//           are walked and listed (pbd_set_top_k); not with --staged
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT.  0 exact, 1 fma,
 //           2 / 3 matrix cores bf16 / fp16 (5x5 banks), 4 fp64 matrix cores (--double), 5 / 6 matrix cores bf16 / fp16 for
 //           every filter size and mixed banks (PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY; not with --double)
@@ -50,6 +52,7 @@ using namespace pbdhost;
 // what a run prints for one image's candidates (the reference's demo: count, sort, optional NMS, the best ones)
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
+static int g_top_k = 0;                   // --top-k
 static bool g_prune = false;              // --depth-prune fx,width,tol
 static float g_prune_fx = 0.f, g_prune_width = 0.f, g_prune_tol = 0.f;
 
@@ -79,6 +82,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
+    pbd.setTopK(g_top_k);
     pbd.distributeModel(model);
     std::vector<std::vector<Candidate> > candidates;
     pbd.detectBatch(ims, candidates);
@@ -166,6 +170,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     if (dnms >= 0) pbd.setNonMaximaSuppression(dnms);
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
+    pbd.setTopK(g_top_k);
     if (g_prune) pbd.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
@@ -173,6 +178,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         FrameStream<T> fs(model, stream_k, 0, 1 << 16, conv_mode);
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         fs.setRootNMS(g_root_nms);
+        fs.setTopK(g_top_k);
         if (g_prune) fs.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
         std::vector<Candidate> first, cur;
         size_t got = 0;
@@ -296,7 +302,7 @@ static int dump_model(const Model &m)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
         return -1;
     }
     bool dbl = false, staged = false;
@@ -324,6 +330,13 @@ int main(int argc, char **argv)
             else { std::fprintf(stderr, "--walk takes reference or argmax\n"); return -1; }
         }
         else if (!std::strcmp(argv[i], "--root-nms") && i + 1 < argc) g_root_nms = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--top-k") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d%c", &g_top_k, &tail) != 1 || g_top_k < 0 || g_top_k > (1 << 30)) {
+                std::fprintf(stderr, "--top-k takes a count, 0 (off) or 1..1073741824\n");
+                return -1;
+            }
+        }
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }
@@ -366,6 +379,10 @@ int main(int argc, char **argv)
     }
     if (g_prune && (!depth_path || staged)) {
         std::fprintf(stderr, "--depth-prune needs --depth, not with --staged\n");
+        return -1;
+    }
+    if (g_top_k && staged) {
+        std::fprintf(stderr, "--top-k is not applied by the staged run: not with --staged\n");
         return -1;
     }
     if (have_camera && !depth_path) {

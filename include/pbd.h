@@ -183,7 +183,8 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world);
  * caller's capacity the behaviour is that of the unsuppressed list (truncation, PBD_ERR_CAPACITY, word 0 = kept count).
  * enable = 0: off.  A NaN overlap is PBD_ERR_INVALID; PBD_ERR_STATE while a batch is in flight (the setting is latched at
  * submit); PBD_ERR_UNSUPPORTED together with level sharding (world > 1), in either order of the two calls: suppression of one
- * rank's levels is not suppression of the union. */
+ * rank's levels is not suppression of the union.  With pbd_set_top_k on, K is taken before the suppression, so fewer than K may
+ * survive it; root NMS plus top-K is the combination that keeps K distinct objects. */
 int pbd_set_nms(pbd_handle *h, int enable, float overlap);
 /* The walk from a root to its parts (new surface, opt-in).  A child's mixture is m = Ik[slot + pm][py][px] in both modes; with k
  * the plane of that mixture:
@@ -519,6 +520,50 @@ int pbd_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, 
                     const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity, int *nout);
 int pbd_depth_prune_device(pbd_handle *h, const pbd_depth_prune_cfg *cfg, int nframes, const struct pbd_frame *d_depth, int depth_code,
                            const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out, int out_capacity);
+
+/* The K best of every segment (new surface; opt-in).  The rule, stated here once:
+ *   order        a is BETTER than b when value(a) > value(b), compared as numbers in the array's own type; if the values are equal, a
+ *                is better when its element index is smaller.  +0.0 and -0.0 tie; +Inf ties +Inf.
+ *   eligible     an element that is not NaN and, where a mask is given, whose mask byte is non-zero
+ *   selection    of each segment -- a contiguous range of elements -- the min(K, eligible) best eligible elements are kept and
+ *                nothing else.  The order is total, so the kept set is unique.
+ * pbd_top_k_cells / pbd_top_k_cells_device: nseg segments packed back to back, segment i of len[i] elements (a host array in both
+ * forms; 0 is legal); `mask` (NULL: none) and `dst` have the same layout; dst receives 0 or 255 in every byte.  real_code is
+ * PBD_REAL_F32 or PBD_REAL_F64, whatever the handle's T: the handle gives the stream, the workspace and the error text only.
+ * k >= 0; k == 0 keeps nothing.  PBD_ERR_INVALID: a negative k, nseg or len, a total above 2^31 - 1, another real_code, or NULL
+ * src / dst / len with work to do.  PBD_ERR_STATE while a batch is in flight.  The resident detect result is not touched.
+ * The host form is synchronous; the device form (d_src aligned to its element) is asynchronous on pbd_stream().  Two calls on the
+ * same input give the same bytes, and the cost does not depend on the values.
+ * pbd_set_top_k(h, k): k == 0 is off (the default on a new handle), 1 .. 2^30 on, anything else PBD_ERR_INVALID; PBD_ERR_STATE while
+ * a batch is in flight (the setting is latched at submit).  Kept across model updates; the resident result stays.  With it on, every
+ * later call of the entry points pbd_set_root_nms lists, and pbd_argmin_device_out (which so re-emits the resident list under
+ * another K without running the dynamic program again), runs the selection over rootv in the handle's T with one segment per frame:
+ * frame f of an equal-size batch is the root cells [f * cells * NC, (f + 1) * cells * NC) (cells: the root cells of one frame's
+ * levels), a frame of a mixed-size call the range of its own levels.  Eligible means `rootv > (T)thresh`, the find's own expression,
+ * and the byte of depth pruning and of root NMS where those are on: K is taken among the survivors of both.  The find additionally
+ * requires the new byte.  Result: the same records, fewer of them -- at most K per frame whatever the threshold and the scene --
+ * in the same (frame, level, component, y, x) order; every word of a kept record is untouched.  max_candidates, the caller's
+ * capacity, PBD_ERR_CAPACITY, payload word 0 and pbd_set_nms see only the kept list.  NOT applied by pbd_dp_argmin,
+ * pbd_detect_latent, or the trainers' re-walks, for the reason root NMS is not.  Level sharding is allowed: each rank keeps the K
+ * best of its own levels, so the union over the ranks contains the unsharded result, and pbd_top_k on the merged list put in
+ * (frame, level, component, y, x) order IS the unsharded result for T = float.  For T = double the records carry a float score, so
+ * only the detect-path form sees differences below float precision.
+ * pbd_top_k / pbd_top_k_device: per frame of a caller's list, the K best records by the record's float score (k >= 0, else
+ * PBD_ERR_INVALID).  A record with a NaN score is never kept, as the find never lists one; ties go to the earlier record of the
+ * list; the kept records come out in their input order.  Records must be grouped by ascending frame, as for pbd_suppress* (host
+ * form: refused otherwise).  Conventions of pbd_depth_prune* above, word for word: frame_offset, in place allowed for the host form,
+ * *nout / word 0 = the kept count (which may exceed the capacity), an input word 0 that is negative or > capacity gives -1, a record
+ * whose frame index is outside 0 .. nframes - 1 or whose nparts is outside 1..max parts is dropped and is nobody's rival (host form:
+ * refused), no host synchronisation in the device form, the resident result untouched, PBD_ERR_STATE while a batch is in flight. */
+int pbd_top_k_cells(pbd_handle *h, int nseg, const long long *len, int real_code, const void *src, const uint8_t *mask, int k,
+                    uint8_t *dst);
+int pbd_top_k_cells_device(pbd_handle *h, int nseg, const long long *len, int real_code, const void *d_src, const uint8_t *d_mask,
+                           int k, uint8_t *d_dst);
+int pbd_set_top_k(pbd_handle *h, int k);
+int pbd_top_k(pbd_handle *h, int nframes, int k, const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity,
+              int *nout);
+int pbd_top_k_device(pbd_handle *h, int nframes, int k, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out,
+                     int out_capacity);
 
 /* Suppression of a caller's list (new surface): exactly the pbd_set_nms stage above -- per frame the stable score sort, then the
  * greedy painted-canvas suppression -- applied to any records of this handle, e.g. after pbd_depth_consistency, or to the merged
@@ -1132,6 +1177,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_KM_TRIALS, PBD_K_KM_PICK,
        /* pbd_grid_nms* / pbd_set_root_nms: the grid maxima of a set of planes */
        PBD_K_GRID_NMS,
+       /* pbd_top_k_cells* / pbd_set_top_k / pbd_top_k*: the K best elements of every segment, or records of every frame */
+       PBD_K_TOP_K,
        /* pbd_set_depth_prune / pbd_depth_prune*: the plausibility test of the root cells, or of a list's records */
        PBD_K_DEPTH_PRUNE,
        PBD_K_COUNT };

@@ -268,6 +268,35 @@ inline void grid_nms(pbd_handle *h, const typename Tr::Mat &src, int sz, const u
     check<Tr>(h, pbd_grid_nms(h, 1, &rows, &cols, RealCode<T>::value, Tr::cptr(s), mask, sz, dst));
 }
 
+// pbd_set_top_k: at most k candidates per frame from every later walk of this handle -- the k best roots of the frame among those
+// the threshold and the other root filters leave; k = 0: off
+template <class Tr>
+inline void set_top_k(pbd_handle *h, int k)
+{
+    check<Tr>(h, pbd_set_top_k(h, k));
+}
+
+// pbd_top_k_cells for one segment, the elements of `src` in row-major order: dst receives rows x cols bytes of 0 / 255, 255 at the
+// k best elements that are not NaN (and whose mask byte is non-zero); mask: NULL, or rows x cols bytes, rows dense
+template <class Tr>
+inline void top_k_cells(pbd_handle *h, const typename Tr::Mat &src, int k, const uint8_t *mask, uint8_t *dst)
+{
+    typedef typename Tr::Real T;
+    const typename Tr::Mat s = Tr::real_continuous(src);
+    const long long len = (long long)Tr::rows(s) * Tr::cols(s);
+    check<Tr>(h, pbd_top_k_cells(h, 1, &len, RealCode<T>::value, Tr::cptr(s), mask, k, dst));
+}
+
+// pbd_top_k over n records of this handle in `buf`, in place: n becomes the kept count, the kept records stay in order; every
+// record is taken as one of this frame (frame field 0)
+template <class Tr>
+inline void top_k(pbd_handle *h, int k, std::vector<int32_t> &buf, int &n)
+{
+    int kept = 0;
+    check<Tr>(h, pbd_top_k(h, 1, k, n ? &buf[0] : NULL, n, 0, n ? &buf[0] : NULL, n, &kept));
+    n = kept;
+}
+
 // pbd_candidate records -> the host's Candidates (include/Candidate.hpp:56-80)
 template <class Tr>
 inline void unpack_candidates(pbd_handle *h, const std::vector<int32_t> &buf, int n, std::vector<typename Tr::Candidate> &out)

@@ -597,6 +597,7 @@ class PartsBasedDetector {
     float overlap_;
     int walk_;
     int root_nms_;
+    int top_k_;
     bool depth_on_;
     float zfactor_;
     bool prune_on_;
@@ -610,7 +611,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f) {}
+          root_nms_(0), top_k_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -622,6 +623,7 @@ public:
         if (nms_) pbdbind::set_nms<HostTraits<T> >(h_, true, overlap_);
         if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
         if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
+        if (top_k_) pbdbind::set_top_k<HostTraits<T> >(h_, top_k_);
         if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
         name_ = model.name();
     }
@@ -661,6 +663,43 @@ public:
         if (!mask.empty() && mask.size() != n) throw Error(PBD_ERR_INVALID, "gridNMS: the mask has the plane's size");
         dst.assign(n, 0);
         pbdbind::grid_nms<HostTraits<T> >(h_, src, sz, mask.empty() ? NULL : &mask[0], n ? &dst[0] : NULL);
+    }
+    // new surface: at most k candidates per frame from now on (pbd_set_top_k): only the k best roots of each frame -- by score, ties
+    // to the earlier cell -- among those the threshold, depth pruning and root NMS leave are walked and returned; k = 0 turns it
+    // off (the default).  Kept across distributeModel().
+    void setTopK(int k)
+    {
+        if (k < 0 || k > (1 << 30)) throw Error(PBD_ERR_INVALID, "top-K: 0 (off) or 1..2^30");
+        if (h_) pbdbind::set_top_k<HostTraits<T> >(h_, k);
+        top_k_ = k;
+    }
+    // the k best elements of src that are not NaN (and not masked out), ties to the smaller row-major index, selected on the device
+    // (pbd_top_k_cells): dst becomes src.rows x src.cols bytes of 0 / 255; mask: empty, or that many bytes
+    void topKCells(const MatT<T> &src, int k, std::vector<uint8_t> &dst, const std::vector<uint8_t> &mask = std::vector<uint8_t>())
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "topKCells() before distributeModel()");
+        const size_t n = (size_t)src.rows * src.cols;
+        if (!mask.empty() && mask.size() != n) throw Error(PBD_ERR_INVALID, "topKCells: the mask has the array's size");
+        dst.assign(n, 0);
+        pbdbind::top_k_cells<HostTraits<T> >(h_, src, k, mask.empty() ? NULL : &mask[0], n ? &dst[0] : NULL);
+    }
+    // the k best candidates by score, ties to the earlier one, in their input order, decided on the device (pbd_top_k): for a list
+    // built elsewhere; every candidate is taken as one of this frame
+    void topK(std::vector<Candidate> &candidates, int k)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "topK() before distributeModel()");
+        std::vector<int32_t> rec = records(candidates);
+        const std::vector<int32_t> in = rec;
+        int n = (int)candidates.size();
+        pbdbind::top_k<HostTraits<T> >(h_, k, rec, n);
+        const size_t stride = (size_t)pbd_candidate_stride(h_);
+        std::vector<Candidate> kept;
+        for (size_t i = 0, j = 0; i < candidates.size() && j < (size_t)n; ++i)   // the kept records are the input's, in order
+            if (std::memcmp(&in[i * stride], &rec[j * stride], stride * sizeof(int32_t)) == 0) {
+                kept.push_back(candidates[i]);
+                ++j;
+            }
+        candidates.swap(kept);
     }
     // new surface: detect(im, depth, candidates) runs filterCandidatesByDepth(depth, ., zfactor) on the unsuppressed list, before
     // the suppression -- the reference's commented-out call (src/PartsBasedDetector.cpp:91-93).  Off by default (depth ignored, as
@@ -1208,6 +1247,11 @@ public:
     void setRootNMS(int sz)
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_root_nms<HostTraits<T> >(h_[i], sz);
+    }
+    // every handle keeps at most k candidates per frame (PartsBasedDetector::setTopK); nothing may be pending
+    void setTopK(int k)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_top_k<HostTraits<T> >(h_[i], k);
     }
     // every handle prunes the roots of a frame submitted with its depth image (PartsBasedDetector::setDepthPrune); nothing may be
     // pending

@@ -229,6 +229,51 @@ inline void hipSetRootNMS(pbd_handle *h, int sz)
     pbdbind::set_root_nms<CvTraits<T> >(h, sz);
 }
 
+// At most k candidates per frame from every later hipDetect / hipDetectBatch of this handle (pbd_set_top_k): the k best roots of
+// the frame among those the threshold and the other root filters leave; k = 0 turns it off
+template <typename T>
+inline void hipSetTopK(pbd_handle *h, int k)
+{
+    pbdbind::set_top_k<CvTraits<T> >(h, k);
+}
+
+// The k best elements of src on the device (pbd_top_k_cells): a larger value is better, of equal values the one earlier in
+// row-major order; NaN and masked-out elements take no part.  src: one channel; CV_32F and CV_64F are compared in their own type,
+// every other depth as CV_64F (exact for the integer depths).  dst becomes the CV_8U array of 0 / 255; mask: empty, or CV_8U of
+// src's size.
+inline void hipTopK(pbd_handle *h, const cv::Mat &src, int k, cv::Mat &dst, const cv::Mat mask = cv::Mat())
+{
+    const bool masked = mask.data != NULL && mask.rows > 0 && mask.cols > 0;
+    if (src.channels() != 1 || (masked && (mask.rows != src.rows || mask.cols != src.cols || mask.depth() != CV_8U || mask.channels() != 1)))
+        CV_Error(CV_StsError, "pbd: hipTopK: one channel, and a CV_8U mask of the same size");
+    const cv::Mat m = masked && !mask.isContinuous() ? mask.clone() : mask;
+    dst.create(src.rows, src.cols, CV_8U);
+    const uint8_t *mp = masked ? m.ptr<uint8_t>(0) : NULL;
+    uint8_t *dp = src.rows > 0 && src.cols > 0 ? dst.ptr<uint8_t>(0) : NULL;
+    if (src.depth() == CV_32F) pbdbind::top_k_cells<CvTraits<float> >(h, src, k, mp, dp);
+    else pbdbind::top_k_cells<CvTraits<double> >(h, src, k, mp, dp);
+}
+
+// The k best candidates of one frame by score on the device (pbd_top_k), ties to the earlier one, in their input order: for a list
+// built elsewhere
+template <typename T>
+inline void hipTopK(pbd_handle *h, std::vector<typename CvTraits<T>::Candidate> &candidates, int k)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    const std::vector<int32_t> in(rec);
+    int n = (int)candidates.size();
+    pbdbind::top_k<CvTraits<T> >(h, k, rec, n);
+    const size_t stride = (size_t)pbd_candidate_stride(h);
+    std::vector<typename CvTraits<T>::Candidate> kept;
+    for (size_t i = 0, j = 0; i < candidates.size() && j < (size_t)n; ++i)   // the kept records are the input's, in order
+        if (std::memcmp(&in[i * stride], &rec[j * stride], stride * sizeof(int32_t)) == 0) {
+            kept.push_back(candidates[i]);
+            ++j;
+        }
+    candidates.swap(kept);
+}
+
 // Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) on the device (pbd_candidate_mask): mask becomes the
 // im.rows x im.cols CV_8U label image; every candidate is one of this frame
 template <typename T>

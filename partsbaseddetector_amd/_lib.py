@@ -35,7 +35,7 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_ex_walk", "k_ex_gather", "k_qp_write", "k_qp_score", "k_qp_pass", "k_qp_lincomb",
            "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
            "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
-           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick", "k_grid_nms", "k_depth_prune"]
+           "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick", "k_grid_nms", "k_top_k", "k_depth_prune"]
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -57,6 +57,7 @@ SYMBOLS = [
     "pbd_best_overlap_device", "pbd_eval_pck", "pbd_eval_pck_device", "pbd_eval_apk", "pbd_eval_apk_device",
     "pbd_set_walk", "pbd_qp_clear", "pbd_qp_add_loss_device", "pbd_cluster_parts", "pbd_cluster_parts_device",
     "pbd_grid_nms", "pbd_grid_nms_device", "pbd_set_root_nms",
+    "pbd_top_k_cells", "pbd_top_k_cells_device", "pbd_set_top_k", "pbd_top_k", "pbd_top_k_device",
     "pbd_set_depth_prune", "pbd_bind_depth", "pbd_bind_depth_device", "pbd_depth_prune", "pbd_depth_prune_device",
 ]
 
@@ -248,6 +249,11 @@ def load():
                                           C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.pbd_depth_consistency_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_float, C.c_void_p, C.c_int,
                                                  C.c_int, C.c_void_p, C.c_int]
+    lib.pbd_set_top_k.argtypes = [C.c_void_p, C.c_int]
+    lib.pbd_top_k_cells.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.pbd_top_k_cells_device.argtypes = lib.pbd_top_k_cells.argtypes
+    lib.pbd_top_k.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.pbd_top_k_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.pbd_set_depth_prune.argtypes = [C.c_void_p, C.POINTER(CDepthPruneCfg)]
     lib.pbd_bind_depth.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int]
     lib.pbd_bind_depth_device.argtypes = lib.pbd_bind_depth.argtypes

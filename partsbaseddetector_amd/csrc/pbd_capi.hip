@@ -9,6 +9,7 @@
 // There is no CPU compute path: every stage runs as a HIP kernel (pbd_kernels_*.hip).
 #include "pbd_handle.h"
 
+#include <limits.h>
 #include <mutex>
 
 using namespace pbd;
@@ -1261,6 +1262,51 @@ static int enqueue_root_nms(pbd_handle *h, Plan &P, int nframes, int sz, const u
     return PBD_OK;
 }
 
+int top_k_workspace(pbd_handle *h, TopKParams &p, hipStream_t st)
+{
+    if (int rc = carve(h, h->tk_ws, [&](Carve &c) {
+            p.hist = c.take<int>((size_t)p.nseg * 256 * sizeof(int));
+            p.state = c.take<TopKSeg>((size_t)p.nseg * sizeof(TopKSeg));
+            p.tcnt = c.take<int>((size_t)(p.ntiles + 1) * sizeof(int));
+            p.part = c.take<long long>((size_t)top_k_scan_parts(p.ntiles) * sizeof(long long));
+        })) return rc;
+    HIPCHK(h, hipMemsetAsync(p.hist, 0, (size_t)p.nseg * 256 * sizeof(int), st));   // (a grown workspace holds anything)
+    return PBD_OK;
+}
+
+// pbd_set_top_k: the k best root cells of every frame of the call among those above the threshold whose bytes in `root_ok` and
+// `root_max` (NULL: off) are set, a byte per root cell in h->tk_keep.  Equal frames are equal segments; a mixed plan's frames are
+// the ranges of their own virtual levels, tabulated once per plan.
+static int enqueue_top_k(pbd_handle *h, Plan &P, int nframes, int k, const uint8_t *root_ok, const uint8_t *root_max, hipStream_t st)
+{
+    const long long per_frame = P.cell_per_frame * h->NC, total = per_frame * nframes;
+    if (total > INT_MAX) return fail(h, PBD_ERR_INVALID, "top-K: %lld root cells in the call (at most 2^31 - 1)", total);
+    TopKParams tp{};
+    if (P.kind == 2) {
+        if (!P.d_tk.p) {
+            std::vector<TopKTab> tab(P.mixed_frames + 1);
+            long long tiles = 0;
+            for (int f = 0; f <= P.mixed_frames; ++f) {
+                const long long off = f < P.mixed_frames ? P.lv[P.frame_lv0[f]].cell_off * h->NC : per_frame;
+                if (f > 0) tiles += top_k_tiles(off - tab[f - 1].off);
+                tab[f] = TopKTab{off, tiles};
+            }
+            HIPCHK(h, P.d_tk.upload(tab));
+            P.tk_tiles = tiles;
+        }
+        tp.tab = P.d_tk.p; tp.nseg = P.mixed_frames; tp.ntiles = P.tk_tiles;
+    } else {
+        tp.nseg = nframes; tp.ulen = per_frame; tp.utiles = top_k_tiles(per_frame); tp.ntiles = tp.utiles * nframes;
+    }
+    HIPCHK(h, h->tk_keep.ensure(std::max<size_t>((size_t)total, 16)));
+    if (int rc = top_k_workspace(h, tp, st)) return rc;
+    tp.k = k; tp.src = h->rootv.p; tp.use_thresh = 1; tp.thresh = h->thresh; tp.mask = root_ok; tp.mask2 = root_max;
+    tp.dst = h->tk_keep.as<uint8_t>();
+    ProfScope ps(h, PBD_K_TOP_K, st);
+    launch_top_k(tp, h->f64, st);
+    return PBD_OK;
+}
+
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
                    int capacity, hipStream_t st, bool walk_only, RootSel sel)
 {
@@ -1292,6 +1338,10 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     if (sel.nms > 0 && !walk_only) {
         if (int rc = enqueue_root_nms(h, P, nframes, sel.nms, ap.root_ok, st)) return rc;
         ap.root_max = h->gn_max.as<uint8_t>();
+    }
+    if (sel.top > 0 && !walk_only && ap.ntotal > 0) {
+        if (int rc = enqueue_top_k(h, P, nframes, sel.top, ap.root_ok, ap.root_max, st)) return rc;
+        ap.root_top = h->tk_keep.as<uint8_t>();
     }
     ProfScope ps(h, PBD_K_ARGMIN, st);
     if (!walk_only) launch_argmin_find(ap, h->f64, st);   // walk_only: the payload's records were written by the caller
@@ -2014,6 +2064,15 @@ int pbd_set_root_nms(pbd_handle *h, int sz)
     });
 }
 
+int pbd_set_top_k(pbd_handle *h, int k)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (k < 0 || k > (1 << 30)) return fail(h, PBD_ERR_INVALID, "top-K %d (0: off, 1..2^30)", k);
+        h->top_k = k;                     // the resident result stays: the planes do not depend on it
+        return PBD_OK;
+    });
+}
+
 int pbd_set_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg)
 {
     return entry(h, true, kIdle, [&]() -> int {
@@ -2469,7 +2528,7 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
                                              "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick",
-                                             "k_grid_nms", "k_depth_prune"};
+                                             "k_grid_nms", "k_top_k", "k_depth_prune"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

@@ -280,6 +280,79 @@ int enqueue_grid_nms(pbd_handle *h, int nplanes, const int *rows, const int *col
     return PBD_OK;
 }
 
+// ---- the K best elements of a caller's segments (pbd_top_k_cells*; pbd_kernels_topk.hip)
+// every check of a call; *total = the elements of all segments
+int check_top_k_cells(pbd_handle *h, int nseg, const long long *len, int real_code, const void *src, const void *dst, int k,
+                      long long *total)
+{
+    if (nseg < 0 || k < 0) return fail(h, PBD_ERR_INVALID, "nseg %d, k %d", nseg, k);
+    if (real_code != PBD_REAL_F32 && real_code != PBD_REAL_F64)
+        return fail(h, PBD_ERR_INVALID, "real_code %d: PBD_REAL_F32 or PBD_REAL_F64", real_code);
+    if (nseg > 0 && !len) return fail(h, PBD_ERR_INVALID, "a null pointer: len");
+    *total = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (len[i] < 0) return fail(h, PBD_ERR_INVALID, "segment %d: length %lld", i, len[i]);
+        *total += len[i];
+        if (*total > INT_MAX) return fail(h, PBD_ERR_INVALID, "more than 2^31 - 1 elements up to segment %d", i);
+    }
+    if (*total > 0 && (!src || !dst)) return fail(h, PBD_ERR_INVALID, "a null pointer: src %p, dst %p", src, dst);
+    return PBD_OK;
+}
+
+// the segment table to the device and the selection's kernels, on the handle's stream
+int enqueue_top_k_cells(pbd_handle *h, int nseg, const long long *len, int real_code, const void *d_src, const uint8_t *d_mask,
+                        int k, uint8_t *d_dst)
+{
+    std::vector<TopKTab> tab(nseg + 1);
+    long long off = 0, tiles = 0;
+    for (int i = 0; i < nseg; ++i) {
+        tab[i] = TopKTab{off, tiles};
+        off += len[i]; tiles += top_k_tiles(len[i]);
+    }
+    tab[nseg] = TopKTab{off, tiles};
+    if (int rc = h->tk_tab.stage(h, tab.data(), tab.size() * sizeof(TopKTab))) return rc;
+    TopKParams tp{};
+    tp.tab = h->tk_tab.as<TopKTab>(); tp.nseg = nseg; tp.k = k; tp.ntiles = tiles;
+    tp.src = d_src; tp.mask = d_mask; tp.dst = d_dst;
+    if (int rc = top_k_workspace(h, tp, h->stream)) return rc;
+    {
+        ProfScope ps(h, PBD_K_TOP_K, h->stream);
+        launch_top_k(tp, real_code == PBD_REAL_F64, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// ---- the K best records of every frame of a caller's list (pbd_top_k*)
+int check_top_k_list(pbd_handle *h, int nframes, int k)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    if (k < 0) return fail(h, PBD_ERR_INVALID, "k %d", k);
+    return PBD_OK;
+}
+
+// the rank of every record and the depth-consistency filter's compaction on the handle's stream: payload d_in (capacity records)
+// -> d_out (out_cap records)
+int enqueue_top_k_list(pbd_handle *h, int nframes, int k, const int32_t *d_in, int capacity, int frame_offset, int32_t *d_out,
+                       int out_cap)
+{
+    const int cap = std::max(capacity, 0), blocks = dc_record_blocks(cap);
+    DcParams p{};
+    if (int rc = carve(h, h->tkl_ws, [&](Carve &c) {
+            p.flag = c.take<int>((size_t)blocks * 256 * sizeof(int));
+            p.blk = c.take<int>((size_t)blocks * sizeof(int));
+        })) return rc;
+    p.in = d_in; p.in_cap = cap; p.stride = stride(h); p.max_parts = h->max_parts;
+    p.nframes = nframes; p.frame_offset = frame_offset;
+    p.out = d_out; p.out_cap = std::max(out_cap, 0);
+    {
+        ProfScope ps(h, PBD_K_TOP_K, h->stream);
+        launch_top_k_records(p, k, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // ---- suppression of a caller's list (pbd_suppress*): the canvas tables of its frame sizes, kept for the next call of the
 // same sizes
 int get_suppress_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
@@ -984,6 +1057,70 @@ int pbd_grid_nms_device(pbd_handle *h, int nplanes, const int *rows, const int *
             return fail(h, PBD_ERR_INVALID, "device pointer %p not a multiple of the %zu-byte element", d_src, es);
         if (total == 0) return PBD_OK;
         return enqueue_grid_nms(h, nplanes, rows, cols, real_code, d_src, d_mask, sz, d_dst);
+    });
+}
+
+// The K best elements of every segment of a packed array.  See include/pbd.h.
+int pbd_top_k_cells(pbd_handle *h, int nseg, const long long *len, int real_code, const void *src, const uint8_t *mask, int k,
+                    uint8_t *dst)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        long long total = 0;
+        if (int rc = check_top_k_cells(h, nseg, len, real_code, src, dst, k, &total)) return rc;
+        if (total == 0) return PBD_OK;
+        const size_t n = (size_t)total, es = real_code == PBD_REAL_F64 ? sizeof(double) : sizeof(float);
+        HIPCHK(h, h->tk_src.ensure(n * es));
+        HIPCHK(h, h->tk_dst.ensure(n));
+        HIPCHK(h, hipMemcpyAsync(h->tk_src.p, src, n * es, hipMemcpyHostToDevice, h->stream));
+        if (mask) {
+            HIPCHK(h, h->tk_mask.ensure(n));
+            HIPCHK(h, hipMemcpyAsync(h->tk_mask.p, mask, n, hipMemcpyHostToDevice, h->stream));
+        }
+        if (int rc = enqueue_top_k_cells(h, nseg, len, real_code, h->tk_src.p, mask ? h->tk_mask.as<uint8_t>() : nullptr, k,
+                                         h->tk_dst.as<uint8_t>())) return rc;
+        HIPCHK(h, hipMemcpyAsync(dst, h->tk_dst.p, n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return PBD_OK;
+    });
+}
+
+int pbd_top_k_cells_device(pbd_handle *h, int nseg, const long long *len, int real_code, const void *d_src, const uint8_t *d_mask,
+                           int k, uint8_t *d_dst)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        long long total = 0;
+        if (int rc = check_top_k_cells(h, nseg, len, real_code, d_src, d_dst, k, &total)) return rc;
+        const size_t es = real_code == PBD_REAL_F64 ? sizeof(double) : sizeof(float);
+        if (reinterpret_cast<uintptr_t>(d_src) % es)
+            return fail(h, PBD_ERR_INVALID, "device pointer %p not a multiple of the %zu-byte element", d_src, es);
+        if (total == 0) return PBD_OK;
+        return enqueue_top_k_cells(h, nseg, len, real_code, d_src, d_mask, k, d_dst);
+    });
+}
+
+// The K best records of every frame of a caller's list.  See include/pbd.h.
+int pbd_top_k(pbd_handle *h, int nframes, int k, const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity,
+              int *nout)
+{
+    return entry(h, nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
+        if (int rc = check_top_k_list(h, nframes, k)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecAscending)) return rc;
+        if (ncand == 0) return PBD_OK;
+        return host_list_call(h, h->tkl_in, h->tkl_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_top_k_list(h, nframes, k, din, ncand, frame_offset, dout, ncand);
+        });
+    });
+}
+
+int pbd_top_k_device(pbd_handle *h, int nframes, int k, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out,
+                     int out_capacity)
+{
+    return entry(h, d_payload && d_out, kIdle, [&]() -> int {
+        if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
+        if (int rc = check_top_k_list(h, nframes, k)) return rc;
+        return enqueue_top_k_list(h, nframes, k, d_payload, capacity, frame_offset, d_out, out_capacity);
     });
 }
 

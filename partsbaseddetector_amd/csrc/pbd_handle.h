@@ -193,6 +193,9 @@ struct Plan {
     int gn_sz = 0;
     long long gn_blocks = 0;
     DevTable<GnPlane> d_gn;
+    // pbd_set_top_k on a mixed plan: the frames' ranges of the virtual frame's root cells as segments (built on first use)
+    long long tk_tiles = 0;
+    DevTable<TopKTab> d_tk;
     // dynamic program in groups of whole frames when the virtual frame's scratch exceeds the budget: sub-plans whose cell
     // offsets start at 0 (cell0 = the group's first cell in the virtual frame), built for `chunk_budget`
     size_t chunk_budget = 0;
@@ -371,6 +374,7 @@ struct Handle : ErrCtx {
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;
     int root_nms = 0;                // grid NMS of the root scores before the find (pbd_set_root_nms): window size, 0 = off; read at enqueue
+    int top_k = 0;                   // the K best roots of each frame before the find (pbd_set_top_k): 0 = off; read at enqueue
     int gn_lanes = 0;                // forced lanes per block of k_grid_nms, 1 or 64; 0: by sz (pbd_debug_set_option)
     // scale-depth pruning of the roots before the find (pbd_set_depth_prune; read at enqueue) and the depth images bound to the
     // next detect call (pbd_bind_depth*): their frame table, the host form's copies, the byte per root cell.  claim_depth moves
@@ -397,6 +401,13 @@ struct Handle : ErrCtx {
     DevBuf gn_max;
     StagedTable gn_tab;
     DevBuf gn_src, gn_mask, gn_dst;
+    // top-K: the detect path's byte per root cell (pbd_set_top_k) and the selection's workspace (histograms, segment states, tile
+    // counts); pbd_top_k_cells*: the segment table (staged as the tables below), the host form's values, masks and bytes;
+    // pbd_top_k*: the workspace (flags and block counts), the host form's records and output
+    DevBuf tk_keep, tk_ws;
+    StagedTable tk_tab;
+    DevBuf tk_src, tk_mask, tk_dst;
+    DevBuf tkl_ws, tkl_in, tkl_out;
     DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
     // pbd_boxes3d*: the frame table (staged in pinned memory, rewritten only once its previous copy has completed); the host
     // form's depth images, records and boxes.  Never the detect path's buffers: the resident result stays readable.
@@ -647,13 +658,15 @@ void post_canvas_plan(Plan &M);
 // what restricts the roots a find lists beyond the threshold: the window of pbd_set_root_nms (0: off) and whether the depth images
 // claimed for the call (h->dpr_call) prune them (pbd_set_depth_prune).  The detect entry points pass root_sel(h); DynamicProgram::
 // argmin, the latent search and the trainers' re-walks pass none
-struct RootSel { int nms = 0; bool prune = false; };
-inline RootSel root_sel(const pbd_handle *h) { return {h->root_nms, !h->dpr_call.tab.empty()}; }
+struct RootSel { int nms = 0; bool prune = false; int top = 0; };   // top: the K of pbd_set_top_k (0: off)
+inline RootSel root_sel(const pbd_handle *h) { return {h->root_nms, !h->dpr_call.tab.empty(), h->top_k}; }
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload, int capacity,
                    hipStream_t st, bool walk_only = false, RootSel sel = {});
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,
                  int32_t *d_out, int out_cap, hipStream_t st, const Plan *mixed = nullptr, int in_offset = 0, int *bad = nullptr);
 int depth_prune_rule(pbd_handle *h, const pbd_depth_prune_cfg &cfg, DepthPruneRule *rule);
+// the selection's workspace carved from h->tk_ws for p.nseg segments and p.ntiles tiles, its histograms zeroed on `st`
+int top_k_workspace(pbd_handle *h, TopKParams &p, hipStream_t st);
 int check_frames_mixed(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, bool host, Plan **plan);
 int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *frames, int cn, int depth, bool host,
                          const LatentParams *mask = nullptr);

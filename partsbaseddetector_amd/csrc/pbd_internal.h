@@ -274,6 +274,7 @@ struct ArgminParams {
     const int *lv_frame, *lv_local;
     const uint8_t *root_max;      // pbd_set_root_nms: a byte per root cell, laid out as rootv; a hit also needs it non-zero (NULL: off)
     const uint8_t *root_ok;       // pbd_set_depth_prune: likewise, the cells whose box size agrees with the depth image (NULL: off)
+    const uint8_t *root_top;      // pbd_set_top_k: likewise, the K best cells of each frame among those the two above leave (NULL: off)
 };
 
 // per-frame sort + non-maxima suppression of an argmin payload (pbd_set_nms; pbd_kernels_post.hip)
@@ -467,6 +468,32 @@ struct DepthPruneRoots {          // the plane form, next to the call's ArgminPa
     uint8_t *ok;                  // 1 / 0 per root cell, laid out as rootv; every byte written
 };
 
+// the K best elements of every segment of a packed array (pbd_top_k_cells*, pbd_set_top_k; pbd_kernels_topk.hip)
+constexpr int kTkTile = 1024;     // elements per tile; every segment is cut into tiles of its own
+struct TopKTab {                  // [nseg + 1]: a segment's first element and first tile; entry nseg holds the totals
+    long long off, tile0;
+};
+struct TopKSeg {                  // a segment's selection so far: the key digits fixed, the elements still to take among the
+    unsigned long long prefix;    // keys that share them.  After the last pass: the pivot key and the pivot-valued elements kept
+    int need, done, pad;          // done: settled in pass 0 (K = 0 or K >= eligible)
+};
+struct TopKParams {
+    const TopKTab *tab;           // NULL: nseg segments of ulen elements and utiles tiles each (the detect path's equal frames)
+    int nseg, k;
+    long long ulen, utiles, ntiles;
+    const void *src;              // R
+    const uint8_t *mask;          // NULL: every element that is not NaN is eligible
+    const uint8_t *mask2;         // the detect path: a second byte plane (root NMS after depth pruning)
+    int use_thresh;               // the detect path: eligible = src > (R)thresh, and the mask bytes where given
+    float thresh;
+    uint8_t *dst;                 // 0 / 255, every byte written
+    int *hist;                    // [nseg * 256] zero on entry and on exit
+    TopKSeg *state;               // [nseg]
+    int *tcnt;                    // [ntiles + 1]
+    long long *part;              // [top_k_scan_parts(ntiles)]
+};
+inline long long top_k_tiles(long long len) { return (len + kTkTile - 1) / kTkTile; }
+
 constexpr int kGnWaveSz = 7;      // sz below it: one lane per block; from it on: one wave per block (profiles/grid_nms/README.md)
 
 // ---- kernel launches and their timing -------------------------------------------------------
@@ -578,6 +605,12 @@ void launch_depth_prune_records(const DcParams &p, const DepthPruneRule &rule, h
 // the grid maxima of p's planes; lanes per block: grid_nms_lanes(sz, forced) = 1 or 64 (forced: 0 = by sz)
 int grid_nms_lanes(int sz, int forced);
 void launch_grid_nms(const GridNmsParams &p, bool f64, int lanes, hipStream_t s);
+// the K best eligible elements of every segment of p (4 passes for float, 8 for double, then the ordered mark); the long longs of
+// p.part
+long long top_k_scan_parts(long long ntiles);
+void launch_top_k(const TopKParams &p, bool f64, hipStream_t s);
+// the record form: p.flag / p.blk from each record's rank among its frame's records by score, then launch_dc_emit
+void launch_top_k_records(const DcParams &p, int k, hipStream_t s);
 // camera boxes and part centres of p.in's records (after launch_boxes3d wrote p.cube)
 void launch_camera_boxes(const CameraParams &p, hipStream_t s);
 // one step of the clustering (kClStep*, launched in this order); nothing is read back

@@ -817,6 +817,7 @@ __device__ __forceinline__ int find_hits(const ArgminParams &p, long long base, 
         hit[e] = o < p.ntotal && rv[o] > (R)p.thresh;       // NaN compares false, as in the reference's `rootv > thresh` mask
         if (p.root_max) hit[e] = hit[e] && p.root_max[o];   // pbd_set_root_nms: only the grid maxima (pbd_kernels_gridnms.hip)
         if (p.root_ok) hit[e] = hit[e] && p.root_ok[o];     // pbd_set_depth_prune: only the plausible roots (pbd_kernels_depthprune.hip)
+        if (p.root_top) hit[e] = hit[e] && p.root_top[o];   // pbd_set_top_k: only the K best of the frame (pbd_kernels_topk.hip)
         c += hit[e] ? 1 : 0;
     }
     return c;

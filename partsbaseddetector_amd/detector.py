@@ -317,6 +317,56 @@ class Handle:
         self.check(self.lib.pbd_grid_nms_device(self.h, len(r), _lib.ptr(r, C.c_int), _lib.ptr(c, C.c_int), int(real_code),
                                                 d_src_ptr or None, d_mask_ptr or None, int(sz), d_dst_ptr or None))
 
+    def set_top_k(self, k: int) -> None:
+        """pbd_set_top_k: every detect* call of this handle keeps only the k best roots of each frame among the cells the threshold
+        and the other root filters leave (topk.top_k_cells_ref over the frame's rootv), before the walk; 0: off (the default)"""
+        self.check(self.lib.pbd_set_top_k(self.h, int(k)))
+
+    def top_k_cells(self, segments: Sequence[np.ndarray], k: int, masks: Optional[Sequence[Optional[np.ndarray]]] = None) -> List[np.ndarray]:
+        """pbd_top_k_cells: the k best eligible elements of every segment (1-D after ravel, all float32 or all float64, any lengths,
+        empty ones included), one launch sequence; masks: None, or one uint8 / bool array per segment.  Returns the uint8 arrays of
+        0 / 255 in the segments' shapes.  Equal to topk.top_k_cells_ref."""
+        segs = [np.ascontiguousarray(a) for a in segments]
+        dt = segs[0].dtype if segs else np.dtype(np.float32)
+        if dt not in (np.float32, np.float64) or any(a.dtype != dt for a in segs):
+            raise PbdError(-1, "top_k_cells: segments of one dtype, float32 or float64")
+        if masks is not None and (len(masks) != len(segs) or any(np.shape(m) != a.shape for m, a in zip(masks, segs))):
+            raise PbdError(-1, "top_k_cells: one mask of its segment's shape per segment")
+        ln = np.array([a.size for a in segs], np.int64)
+        src = np.concatenate([a.ravel() for a in segs]) if segs else np.zeros(0, dt)
+        msk = None if masks is None else np.concatenate([(np.asarray(m) != 0).astype(np.uint8).ravel() for m in masks] or [np.zeros(0, np.uint8)])
+        dst = np.zeros(src.size, np.uint8)
+        self.check(self.lib.pbd_top_k_cells(self.h, len(segs), _lib.ptr(ln, C.c_longlong), _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64,
+                                            src.ctypes.data, None if msk is None else msk.ctypes.data, int(k), dst.ctypes.data))
+        off = np.concatenate([[0], np.cumsum(ln)])
+        return [dst[off[i]:off[i + 1]].reshape(a.shape) for i, a in enumerate(segs)]
+
+    def top_k_cells_device(self, lengths: Sequence[int], real_code: int, d_src_ptr: int, d_mask_ptr: Optional[int], k: int,
+                           d_dst_ptr: int) -> None:
+        """pbd_top_k_cells_device: the packed segments at d_src_ptr (lengths[i] elements each, REAL_F32 or REAL_F64), the optional
+        packed mask bytes, the packed result bytes; asynchronous on the handle's stream"""
+        ln = np.asarray(lengths, np.int64)
+        self.check(self.lib.pbd_top_k_cells_device(self.h, len(ln), _lib.ptr(ln, C.c_longlong), int(real_code), d_src_ptr or None,
+                                                   d_mask_ptr or None, int(k), d_dst_ptr or None))
+
+    def top_k(self, nframes: int, k: int, records: np.ndarray, frame_offset: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_top_k: per frame the k best records (n, stride) by score, ties to the earlier record, in input order; the records are
+        grouped by ascending frame (equal to topk.top_k_records_ref)"""
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(self.lib.pbd_top_k(self.h, int(nframes), int(k), rec.ctypes.data if rec.size else None, len(rec), frame_offset,
+                                      out.ctypes.data, cap, C.byref(n)))
+        return out[:min(n.value, cap)].copy()
+
+    def top_k_device(self, nframes: int, k: int, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
+                     out_capacity: int) -> None:
+        """pbd_top_k_device: the records of a device payload, the kept records into the payload at d_out_ptr (word 0 = kept count,
+        -1 for an overflowed input); asynchronous"""
+        self.check(self.lib.pbd_top_k_device(self.h, int(nframes), int(k), d_payload_ptr, capacity, frame_offset, d_out_ptr,
+                                             out_capacity))
+
     def set_debug_option(self, option: int, value: int) -> None:
         """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
         one.  _lib.DT_LANE_SHIFT: 0..6, 64 >> value rows per wave of the distance transform (-1); _lib.DT_COOP: 0, never
@@ -1080,6 +1130,7 @@ class PartsBasedDetector:
         self._nms = nms
         self._walk = "reference"
         self._root_nms = 0                         # setRootNMS: off
+        self._top_k = 0                            # setTopK: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
         self._dprune: Optional[Tuple[float, float, float]] = None   # setDepthPrune: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
@@ -1107,6 +1158,8 @@ class PartsBasedDetector:
             self.hd.set_walk(self.WALKS[self._walk])
         if self._root_nms:
             self.hd.set_root_nms(self._root_nms)
+        if self._top_k:
+            self.hd.set_top_k(self._top_k)
         if self._dprune is not None:
             self.hd.set_depth_prune(*self._dprune)
         self._name = getattr(model, "name", "")
@@ -1144,6 +1197,38 @@ class PartsBasedDetector:
         """nonMaximaSuppression(src, sz, dst, mask) (src/nms.cpp) on the device: the uint8 plane of 0 / 255 (pbd_grid_nms)"""
         self._need()
         return self.hd.grid_nms([src], sz, None if mask is None else [mask])[0]
+
+    def setTopK(self, k: int) -> None:
+        """at most k detections per frame from now on (pbd_set_top_k; kept across distributeModel): only the k best roots of each
+        frame -- by score, ties to the earlier cell in (level, component, y, x) order -- among those the threshold, depth pruning and
+        root NMS leave are walked and returned; 0: off (the default).  train() / trainmodel() never turn it on"""
+        if not 0 <= int(k) <= 1 << 30:
+            raise PbdError(-1, f"top-K {k}: 0 (off) or 1..2^30")
+        if self.hd is not None:
+            self.hd.set_top_k(int(k))
+        self._top_k = int(k)
+
+    def topKCells(self, values: np.ndarray, k: int, mask: Optional[np.ndarray] = None) -> np.ndarray:
+        """the uint8 array of 0 / 255 in values' shape: 255 at the k best elements that are not NaN (and not masked out), ties to
+        the smaller index, selected on the device (pbd_top_k_cells)"""
+        self._need()
+        return self.hd.top_k_cells([values], k, None if mask is None else [mask])[0]
+
+    def topK(self, candidates: Sequence[Candidate], k: int) -> List[Candidate]:
+        """per frame index the k best candidates by score, ties to the earlier one, in input order, decided on the device
+        (pbd_top_k); the candidates are grouped by ascending frame.  Equal to topk.top_k_records_ref."""
+        self._need()
+        cands = list(candidates)
+        if not cands:
+            return []
+        rec = self.hd.pack_candidates(cands)
+        kept = self.hd.top_k(int(rec[:, 0].max()) + 1, k, rec)
+        keep, j = [], 0
+        for i, c in enumerate(cands):          # the kept records are the input's, in order
+            if j < len(kept) and np.array_equal(kept[j], rec[i]):
+                keep.append(c)
+                j += 1
+        return keep
 
     def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93) from now on
@@ -1792,6 +1877,11 @@ class DetectorPool:
         """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""
         for d in self.dets:
             d.setRootNMS(sz)
+
+    def setTopK(self, k: int) -> None:
+        """PartsBasedDetector.setTopK on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setTopK(k)
 
     def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """PartsBasedDetector.setDepthPrune on every lane (no batch may be pending)"""
