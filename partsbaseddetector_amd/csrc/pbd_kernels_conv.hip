@@ -9,7 +9,8 @@
 // == x).  FMA mode fuses multiply and add (scores within 1e-4, not bit-identical).
 //
 // Two kernels: k_conv3 (float, 5 x 5 filters -- every known model: strip-sequence tiles staged channel-planar in LDS,
-// weights through the scalar unit, packed multiply / add) and k_conv_generic (any filter size 1..7, T = float or double).
+// weights through the scalar unit, packed multiply / add) and k_conv_generic (any filter size 1..kConvMaxK = 31, T = float or
+// double; a 5 x 5 class of a float bank runs on k_conv3 also when the bank holds other sizes beside it).
 // Out-of-image cells are materialised with the reference's constant border (0, but 1 for the last channel:
 // src/SpatialConvolutionEngine.cpp:147-156).  Compiled with -ffp-contract=off.
 #include "pbd_internal.h"
