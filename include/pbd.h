@@ -85,7 +85,8 @@ enum { PBD_CONV_EXACT = 0,   /* multiply and add rounded separately in the refer
                                 Every response is within 8 sqrt(K) 2^-24 M of the exact sum of the fp16 operands'
                                 products, plus half an fp16 ulp of the result (the response's own rounding).
                                 In this mode the RESPONSES live on the device as fp16 (BASELINE configs[4] "fp16 responses"):
-                                pbd_conv_pdf returns them widened to float, |v| >= 65520 saturates to +-inf, and pbd_dp_min
+                                pbd_conv_pdf returns them widened to float, |v| >= 65520 saturates to +-inf (accepted by the
+                                dynamic program: see "Non-finite scores" at pbd_dp_min), and pbd_dp_min
                                 ROUNDS THE CALLER'S float scores to fp16 before the dynamic program (exact for scores that
                                 came from pbd_conv_pdf; arbitrary scores lose precision: tests/test_gpu_parity.py::
                                 test_mfma_f16_dp_min_rounds_its_input pins this) */
@@ -1050,7 +1051,24 @@ int pbd_num_ptr_slots(const pbd_handle *h);   /* back-pointer maps per (level): 
 int pbd_ptr_slot(const pbd_handle *h, int component, int part); /* slot of (part, parent mixture 0) */
 /* min(parts, scores, Ix, Iy, Ik, rootv, rooti) (src/DynamicProgram.cpp:67-173).
  * resp[l]: nfilters planes; Ix/Iy/Ik[l]: pbd_num_ptr_slots planes of int32 (plane slot(part)+m =
- * reference Ix[l][c][part][m]); rootv[l]/rooti[l]: ncomponents planes. */
+ * reference Ix[l][c][part][m]); rootv[l]/rooti[l]: ncomponents planes.
+ *
+ * Non-finite scores.  Every intersection z the distance transform's forward scan pushes is the reference's, in every kernel
+ * variant: a NaN z (from Inf - Inf: two neighbouring equal infinities along a line; or from a NaN score) is pushed, and since
+ * s <= NaN is false nothing beneath it is popped again.
+ *   1. +-Inf and NaN scores are accepted here, and the fp16 responses of PBD_CONV_MFMA_F16 / _F16_ANY that saturated to +-inf are
+ *      accepted by the detect path; nothing is refused.
+ *   2. While NO NaN intersection forms anywhere in the dynamic program (isolated -Inf cells in lines that keep a finite cell,
+ *      isolated +Inf cells, saturated fp16 responses of that shape), every output -- Ix, Iy, Ik, rootv, rooti -- equals the
+ *      reference's bit for bit, under every launch choice.
+ *   3. Where a NaN intersection forms (a masked REGION of -Inf, neighbouring +Inf, NaN scores), the read-out of position q takes
+ *      entry max{k : z[k] < os + q} of the line's envelope, a comparison with NaN being false.  This is a decision of this
+ *      library, not the reference's answer: the reference's loop walks up from entry 0 ("while (z[k+1] < os) k++") and stops
+ *      below the first NaN whatever lies above it, an artefact of the direction of that loop; walking down from the top finds
+ *      the entries above the NaN that do cover q.  Every kernel variant gives this one answer, so a plane gives the same
+ *      pointers alone and in a batch.  NaN values in rootv stand at the same places on every path; their sign and payload are
+ *      unspecified.  Where rule 2 applies, rule 3 selects the reference's entry.
+ * To mask a region and stay within rule 2, use a large finite negative score as pbd_detect_latent does (-1e10). */
 int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, const void *const *resp,
                int32_t *const *Ix, int32_t *const *Iy, int32_t *const *Ik, void *const *rootv,
                int32_t *const *rooti);

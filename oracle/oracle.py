@@ -62,7 +62,33 @@ def lib():
         _LIB.pbdo_detect_f64.restype = C.c_int
         _LIB.pbdo_detect_d_f32.restype = C.c_int
         _LIB.pbdo_detect_d_f64.restype = C.c_int
+        _LIB.pbdo_nan_isect.restype = C.c_longlong
     return _LIB
+
+
+# ---- the distance transform's read-out rule and its count of NaN intersections -----------------------------------------------
+# "reference": the reference's loop (k = 0; while (z[k+1] < os) k++), the default.  "max": entry max{k : z[k] < os + q} with
+# comparisons against NaN false -- the project's rule for envelopes that hold a NaN intersection (include/pbd.h, pbd_dp_min).
+READOUTS = {"reference": 0, "max": 1}
+
+
+class _readout:
+    """dt, dp_min and detect run under the given rule and count the NaN intersections their forward scans push (nan_isect())."""
+
+    def __init__(self, rule):
+        self.rule = READOUTS[rule]
+
+    def __enter__(self):
+        lib().pbdo_set_dt_readout(self.rule)
+        lib().pbdo_nan_isect_reset()
+
+    def __exit__(self, *exc):
+        lib().pbdo_set_dt_readout(READOUTS["reference"])
+
+
+def nan_isect() -> int:
+    """NaN intersections pushed by the forward scans of the last dt / dp_min / detect call."""
+    return int(lib().pbdo_nan_isect())
 
 
 def c_model(flat):
@@ -183,7 +209,7 @@ def conv(feat, filt, flen=32):
     return resp
 
 
-def dt(score, ax, bx, ay, by, osx, osy):
+def dt(score, ax, bx, ay, by, osx, osy, readout="reference"):
     dtype = score.dtype
     score = np.ascontiguousarray(score)
     M, N = score.shape
@@ -192,12 +218,13 @@ def dt(score, ax, bx, ay, by, osx, osy):
     Iy = np.empty((M, N), np.int32)
     fn = lib().pbdo_dt_f32 if dtype == np.float32 else lib().pbdo_dt_f64
     ct = C.c_float if dtype == np.float32 else C.c_double
-    fn(_p(score, ct), M, N, C.c_double(ax), C.c_double(bx), C.c_double(ay), C.c_double(by), osx, osy, _p(out, ct),
-       _p(Ix, C.c_int), _p(Iy, C.c_int))
+    with _readout(readout):
+        fn(_p(score, ct), M, N, C.c_double(ax), C.c_double(bx), C.c_double(ay), C.c_double(by), osx, osy, _p(out, ct),
+           _p(Ix, C.c_int), _p(Iy, C.c_int))
     return out, Ix, Iy
 
 
-def dp_min(flat, c, responses):
+def dp_min(flat, c, responses, readout="reference"):
     """responses (nfilters, H, W) -> Ix, Iy, Ik (nslots, H, W) int32, rootv (H, W), rooti (H, W)."""
     dtype = responses.dtype
     responses = np.ascontiguousarray(responses)
@@ -211,8 +238,9 @@ def dp_min(flat, c, responses):
     cm = c_model(flat)
     fn = lib().pbdo_dp_min_f32 if dtype == np.float32 else lib().pbdo_dp_min_f64
     ct = C.c_float if dtype == np.float32 else C.c_double
-    fn(C.byref(cm), c, _p(responses, ct), H, W, _p(Ix, C.c_int), _p(Iy, C.c_int), _p(Ik, C.c_int), _p(rootv, ct),
-       _p(rooti, C.c_int))
+    with _readout(readout):
+        fn(C.byref(cm), c, _p(responses, ct), H, W, _p(Ix, C.c_int), _p(Iy, C.c_int), _p(Ik, C.c_int), _p(rootv, ct),
+           _p(rooti, C.c_int))
     return Ix, Iy, Ik, rootv, rooti
 
 
@@ -281,7 +309,7 @@ def responses(flat, feat):
     return resp
 
 
-def detect(flat, im, dtype=np.float32, capacity=200000, want_stage_ms=False):
+def detect(flat, im, dtype=np.float32, capacity=200000, want_stage_ms=False, readout="reference"):
     """PartsBasedDetector<T>::detect -> list of candidate dicts sorted by (level, component, y, x)."""
     im, depth = _image(im)
     r, c, cn = im.shape
@@ -291,7 +319,8 @@ def detect(flat, im, dtype=np.float32, capacity=200000, want_stage_ms=False):
     ms = (C.c_double * 5)()
     cm = c_model(flat)
     fn = lib().pbdo_detect_d_f32 if dtype == np.float32 else lib().pbdo_detect_d_f64
-    n = fn(C.byref(cm), C.c_void_p(im.ctypes.data), depth, r, c, cn, C.c_size_t(c * cn), hdr, _p(rects, C.c_int), mp, capacity, ms)
+    with _readout(readout):
+        n = fn(C.byref(cm), C.c_void_p(im.ctypes.data), depth, r, c, cn, C.c_size_t(c * cn), hdr, _p(rects, C.c_int), mp, capacity, ms)
     if n < 0:
         raise RuntimeError(f"oracle detect failed ({n})")
     cands = _unpack(hdr, rects, n, mp)

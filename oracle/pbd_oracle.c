@@ -354,6 +354,15 @@ int pbdo_ptr_slots(const pbdo_model *m, int *ptr_slot)
     return total;
 }
 
+/* Read-out rule of the distance transform (pbd_oracle.h) and the count of NaN intersections the forward scans pushed since the
+ * last reset; both are process-wide, the count is added to atomically (detect runs its transforms under OpenMP). */
+static int pbdo_dt_readout = PBDO_READOUT_REFERENCE;
+static long long pbdo_nan_isect_count = 0;
+void pbdo_set_dt_readout(int rule) { pbdo_dt_readout = rule == PBDO_READOUT_MAX ? PBDO_READOUT_MAX : PBDO_READOUT_REFERENCE; }
+int pbdo_get_dt_readout(void) { return pbdo_dt_readout; }
+void pbdo_nan_isect_reset(void) { pbdo_nan_isect_count = 0; }
+long long pbdo_nan_isect(void) { return pbdo_nan_isect_count; }
+
 /* ---- T = float ---- */
 #define REAL float
 #define FN(x) x##_f32

@@ -117,7 +117,18 @@ void pbdo_hog_features_f64(const uint8_t *im, int rows, int cols, int cn, size_t
 void pbdo_conv_f32(const float *feat, int H, int W, int flen, const float *filt, int k, float *resp);
 void pbdo_conv_f64(const double *feat, int H, int W, int flen, const double *filt, int k, double *resp);
 
-/* ---- distance transform: include/DistanceTransform.hpp:89-105,152-245 ---- */
+/* ---- distance transform: include/DistanceTransform.hpp:89-105,152-245 ----
+ * Read-out rule of every transform run after the call (pbdo_dt, pbdo_dp_min, pbdo_detect):
+ *   PBDO_READOUT_REFERENCE  the reference's loop, "k = 0; while (z[k+1] < os) k++" (:172-178) -- the default;
+ *   PBDO_READOUT_MAX        entry max{k : z[k] < os + q}, a comparison with NaN being false: the project's rule for envelopes
+ *                           that hold a NaN intersection (include/pbd.h, pbd_dp_min).  The two agree wherever z[1..top] is
+ *                           non-decreasing and NaN-free.
+ * pbdo_nan_isect: how many intersections the forward scans have pushed as NaN since pbdo_nan_isect_reset. */
+enum { PBDO_READOUT_REFERENCE = 0, PBDO_READOUT_MAX = 1 };
+void pbdo_set_dt_readout(int rule);
+int pbdo_get_dt_readout(void);
+void pbdo_nan_isect_reset(void);
+long long pbdo_nan_isect(void);
 void pbdo_dt_f32(const float *in, int M, int N, double ax, double bx, double ay, double by,
                  int osx, int osy, float *out, int *Ix, int *Iy);
 void pbdo_dt_f64(const double *in, int M, int N, double ax, double bx, double ay, double by,

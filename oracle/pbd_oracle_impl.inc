@@ -256,6 +256,7 @@ static void FN(dt_row)(const REAL *src, REAL *dst, int *ptr, int N, double a, do
                        int *v, REAL *z)
 { /* :152-182 */
     int k = 0;
+    long long nan_pushed = 0; /* intersections pushed as NaN: a later s <= z[k] is false, so such an entry is never popped */
     v[0] = 0;
     z[0] = -(REAL)INFINITY;
     z[1] = (REAL)INFINITY;
@@ -269,6 +270,22 @@ static void FN(dt_row)(const REAL *src, REAL *dst, int *ptr, int N, double a, do
         v[k] = q;
         z[k] = s;
         z[k + 1] = (REAL)INFINITY;
+        nan_pushed += (s != s);
+    }
+    if (nan_pushed) {
+#pragma omp atomic
+        pbdo_nan_isect_count += nan_pushed;
+    }
+    if (pbdo_dt_readout == PBDO_READOUT_MAX) {
+        /* the project's rule for envelopes that hold a NaN intersection (include/pbd.h, pbd_dp_min): position q takes entry
+         * max{k : z[k] < os + q}, a comparison with NaN being false.  That set shrinks as q falls, so one walk down from the
+         * top serves every q; z[0] = -inf ends it.  Where z[1..top] is non-decreasing and NaN-free this is the loop below. */
+        for (int q = N - 1; q >= 0; --q) {
+            while (!(z[k] < (REAL)(os + q))) k--;
+            dst[q] = (REAL)FN(quad_val)(a, b, os + q - v[k], (double)src[v[k]]);
+            ptr[q] = v[k];
+        }
+        return;
     }
     k = 0;
     for (int q = 0; q < N; ++q) {

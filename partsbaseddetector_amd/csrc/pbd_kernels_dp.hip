@@ -84,7 +84,9 @@ __device__ __forceinline__ R quad_val(double a, double b, int x, R y)
 //     to twelve elements (tools/dt_wave_sim.py, profiles/dt_ring_service/README.md);
 //   * the read-out walks q downwards and POPS: since z[1..ktop] is strictly increasing,
 //     "k = 0; while (z[k+1] < os) k++" (DistanceTransform.hpp:172-178, q ascending) selects the same
-//     k(q) = max{k : z[k] < os(q)} as "k = ktop; while (!(z[k] < os)) k--" with q descending;
+//     k(q) = max{k : z[k] < os(q)} as "k = ktop; while (!(z[k] < os)) k--" with q descending; where z[] holds a NaN (Inf - Inf, a
+//     NaN score) the two differ, and max{k : z[k] < os(q)} with comparisons against NaN false is the library's rule for every
+//     variant (include/pbd.h, pbd_dp_min, "Non-finite scores");
 //   * source values are prefetched one chunk ahead and results leave in whole chunks.
 // The arithmetic per element is exactly computeRow's (DistanceTransform.hpp:152-182).
 // ------------------------------------------------------------------------------------------------
@@ -453,7 +455,8 @@ void launch_dt_cols(const DpParams &p, const DtOptions &o, int nframes, bool f64
 // false, i.e. the new top is the highest entry that stays (ballot + find-first-bit) and the pushed z is that entry's
 // intersection.  No pop loop, no divergence: about 95 instructions per element for four rows, whatever the data.  The read-out is
 // a binary search of the (increasing) z of the finished envelope in LDS for sixteen positions of a row at a time:
-// max{k : z[k] < os + q}, what the reference's "while (z[k+1] < os) k++" selects.  Outputs as in the plain passes.
+// max{k : z[k] < os + q}, what the reference's "while (z[k+1] < os) k++" selects.  A row that pushed a NaN z has no such order
+// and takes the same entry by a walk down from its top (include/pbd.h, pbd_dp_min, rule 3).  Outputs as in the plain passes.
 // G rows per wave, W = 64 / G lanes each (G = 4: window of 16 entries; G = 8: window of 8 -- half the waves for launches that
 // would otherwise need more than one round of them, at the price of more fetches of a lower block)
 template <bool BZ, typename PT, bool COLS, int G>
@@ -517,10 +520,22 @@ __global__ __launch_bounds__(64) void k_dt_coop(DpParams p)
         cur = nxt;
     }
     // ---- read-out: sixteen positions of the row at a time
+    // A NaN z (Inf - Inf, a NaN score) that the scan pushed is still there -- no later s <= NaN pops it -- and leaves z[] without
+    // an order to search.  The row's lanes look through its finished envelope once (every kCoopW-th entry each; the scan itself
+    // carries nothing for this) and share what they found.
+    bool znan = false;
+    if (N > 0) for (int e = sub; e <= k; e += kCoopW) znan |= zs[e] != zs[e];
+    znan = ((unsigned)(__ballot(znan) >> gl0) & ((1u << kCoopW) - 1u)) != 0;
+    const bool anynan = __any(znan);
     for (int p0 = 0; p0 < Nmax; p0 += kCoopW) {
         const int pq = p0 + sub;
         const float osf = (float)(os0 + pq);
         int lo = 0, hi = k;
+        if (anynan) {
+            // such a row walks down from its top to the first entry with z < os + q, a comparison with NaN being false:
+            // max{k : z[k] < os + q} as dt_stream's read-out takes it (include/pbd.h, pbd_dp_min); z[0] = -inf ends the walk
+            if (znan) { lo = k; while (!(zs[lo] < osf)) --lo; hi = lo; }
+        }
         while (__any(lo < hi)) {
             const int mid = (lo + hi + 1) >> 1;
             const bool lt = zs[mid] < osf;

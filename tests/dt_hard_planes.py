@@ -1,7 +1,8 @@
 """Score planes and models that drive the distance transform (include/DistanceTransform.hpp:152-182, computeRow) into the paths
 ordinary data barely reaches -- deep envelopes, long pop runs, exact ties -- and a replay of computeRow that measures what a
 plane does to it.  Shared by tests/test_gpu_dt_planes.py (every kernel variant against the oracle) and tests/test_oracle_cpu.py
-(the oracle against brute force on the same planes)."""
+(the oracle against brute force on the same planes); the planes with infinite and NaN scores by tests/test_gpu_dt_nonfinite.py and
+tests/test_dt_nonfinite_cpu.py."""
 import numpy as np
 
 from partsbaseddetector_amd import model as M
@@ -44,6 +45,80 @@ def level_scores(nfilters, dims, seed, dtype=np.float32, big=1e20):
     for l, (h, w, kind) in enumerate(dims):
         out.append(np.stack([plane(kind or KINDS[(f + l) % len(KINDS)], rng, h, w, big) for f in range(nfilters)]).astype(dtype))
     return out
+
+
+# ---- planes with infinite and NaN scores (include/pbd.h, pbd_dp_min: "Non-finite scores") -----------------------------------
+# Class F: no NaN intersection forms anywhere in the dynamic program, so every output is the reference's.  Class N: one does.
+# Which class a plane falls into is measured by the callers (the oracle's count of NaN intersections), not assumed here.
+NONFINITE_F = ("neg_holes", "pos_spikes", "f16_sat")
+NONFINITE_N = ("neg_region", "pos_pair", "nan_cells")
+F16_SAT = 7e4       # finite in float, beyond fp16's largest finite value (65504; from 65520 on it rounds to infinity)
+
+
+def _holes(rng, h, w, density=0.15):
+    """Isolated cells of an (h, w) plane, never two neighbouring along a row, so every row of two or more cells keeps another
+    cell (a single-cell row gets none); with the first cell of the first row and the last cell of the last row among them."""
+    m = rng.random((h, w)) < density
+    if w < 2:
+        return np.zeros((h, w), bool)
+    m[0, 0] = True
+    for x in range(1, w):
+        m[:, x] &= ~m[:, x - 1]
+    if w > 2 or h > 1:
+        m[h - 1, w - 2], m[h - 1, w - 1] = False, True
+    return m
+
+
+def nonfinite_plane(kind, rng, h, w, spike=True, base="quantised"):
+    """One (h, w) float64 plane of `base` kind ("quantised": exact in fp16 too) with the non-finite cells of `kind`.
+    neg_holes: isolated -Inf cells (_holes).  pos_spikes: ONE +Inf cell when `spike` -- its row leaves the rows pass all +Inf, and
+    a second such row anywhere in the plane would meet it in every column as Inf - Inf.  f16_sat: the same cells as those two
+    kinds, at -+7e4: finite here, infinite once rounded to fp16.  neg_region: a rectangle of -Inf of 3 x 3 cells or more and one
+    whole row and one whole column of -Inf (all clipped to the plane): a mask.  pos_pair: two +Inf neighbouring in a row and two
+    in a column.  nan_cells: isolated NaN cells, the first cell of a row and the last cell of a row among them."""
+    p = plane(base, rng, h, w)
+    if kind in ("neg_holes", "f16_sat"):
+        p[_holes(rng, h, w)] = -np.inf if kind == "neg_holes" else -F16_SAT
+    if kind in ("pos_spikes", "f16_sat") and spike:
+        y, x = int(rng.integers(0, h)), int(rng.integers(0, w))
+        if kind == "pos_spikes" or p[y, x] != -F16_SAT:
+            p[y, x] = np.inf if kind == "pos_spikes" else F16_SAT
+    if kind == "neg_region":
+        y0, x0 = int(rng.integers(0, max(h - 3, 1))), int(rng.integers(0, max(w - 3, 1)))
+        p[y0:y0 + 3 + int(rng.integers(0, 3)), x0:x0 + 3 + int(rng.integers(0, 5))] = -np.inf
+        p[int(rng.integers(0, h)), :] = -np.inf
+        p[:, int(rng.integers(0, w))] = -np.inf
+    if kind == "pos_pair":
+        y, x = int(rng.integers(0, h)), int(rng.integers(0, max(w - 1, 1)))
+        p[y, x:x + 2] = np.inf
+        y, x = int(rng.integers(0, max(h - 1, 1))), int(rng.integers(0, w))
+        p[y:y + 2, x] = np.inf
+    if kind == "nan_cells":
+        p[_holes(rng, h, w, 0.04)] = np.nan         # sparse: no pop run crosses a NaN entry, and some should be long
+    if kind not in NONFINITE_F + NONFINITE_N:
+        raise ValueError(kind)
+    return p
+
+
+def root_child_filters(flat):
+    """Filter ids of the mixtures of every part whose parent is its component's root."""
+    out = set()
+    for c in range(flat.ncomponents):
+        p0, p1 = int(flat.part_offset[c]), int(flat.part_offset[c + 1])
+        for g in range(p0 + 1, p1):
+            if int(flat.parentid[g]) == 0:
+                out |= {int(flat.filterid[gm]) for gm in range(int(flat.mix_offset[g]), int(flat.mix_offset[g + 1]))}
+    return out
+
+
+def nonfinite_scores(flat, kind, dims, seed, dtype=np.float32):
+    """dims: [(h, w, base kind)] -> per level (nfilters, h, w) planes of the given non-finite kind.  The +Inf cell of pos_spikes and f16_sat
+    goes to every other filter of the parts that are children of a root only: such a part's transform is +Inf everywhere, its
+    parent's accumulated plane with it, and one generation higher a transform would run on rows of +Inf alone."""
+    rng = np.random.default_rng(seed)
+    spiked = root_child_filters(flat)
+    return [np.stack([nonfinite_plane(kind, rng, h, w, spike=f in spiked and (f + l) % 2 == 0, base=base)
+                      for f in range(flat.nfilters)]).astype(dtype) for l, (h, w, base) in enumerate(dims)]
 
 
 # ---- models: small trees whose deformations are set after the model is built ----------------------------------------------
@@ -96,11 +171,15 @@ def leaf_jobs(flat):
 
 
 # ---- replay of computeRow on every row of a plane at once, with what it did -------------------------------------------------
-def replay_rows(src, a, b, os0, R=np.float32):
+def replay_rows(src, a, b, os0, R=np.float32, readout="reference"):
     """computeRow (DistanceTransform.hpp:152-182) on each row of src (M, N), in the oracle's arithmetic (double intersection
-    rounded once to R).  Returns out (M, N) R, ptr (M, N) and per-row statistics: the deepest envelope (entries), the most
-    entries popped for one element, whether an exact tie s == z[k] decided a pop-loop test (k > 0) and whether z[k+1] == os
-    decided a read-out test."""
+    rounded once to R).  readout: "reference" is computeRow's own loop (k = 0; while (z[k+1] < os) k++); "max" takes entry
+    max{k : z[k] < os + q} of the finished envelope, a comparison with NaN being false (include/pbd.h, pbd_dp_min, rule 3) --
+    found by looking at every entry, not by a walk.  Returns out (M, N) R, ptr (M, N) and per-row statistics: the deepest
+    envelope (entries), the most entries popped for one element, whether an exact tie s == z[k] decided a pop-loop test (k > 0),
+    whether z[k+1] == os decided a read-out test, nan_isect, the number of intersections pushed as NaN, top, the index of the
+    finished envelope's top entry, and nan_floor, the index of its lowest entry with a NaN z (N + 2 where it has none)."""
+    assert readout in ("reference", "max"), readout
     src = np.ascontiguousarray(src, R)
     Mr, N = src.shape
     rows = np.arange(Mr)
@@ -112,6 +191,7 @@ def replay_rows(src, a, b, os0, R=np.float32):
     maxpop = np.zeros(Mr, np.int64)
     scan_tie = np.zeros(Mr, bool)
     read_tie = np.zeros(Mr, bool)
+    nan_isect = np.zeros(Mr, np.int64)
     s64 = src.astype(np.float64)
 
     def isect(v0, q, sel):
@@ -126,8 +206,9 @@ def replay_rows(src, a, b, os0, R=np.float32):
         live = np.ones(Mr, bool)
         while True:
             zk = z[rows, k]
-            scan_tie |= live & (k > 0) & (s == zk)
-            m = live & (s <= zk) & (k > 0)
+            with np.errstate(invalid="ignore"):
+                scan_tie |= live & (k > 0) & (s == zk)
+                m = live & (s <= zk) & (k > 0)
             if not m.any():
                 break
             k[m] -= 1
@@ -138,29 +219,41 @@ def replay_rows(src, a, b, os0, R=np.float32):
         v[rows, k] = q
         z[rows, k] = s
         z[rows, k + 1] = np.inf
+        nan_isect += np.isnan(s)
         depth = np.maximum(depth, k + 1)
         maxpop = np.maximum(maxpop, pops)
     out = np.empty((Mr, N), R)
     ptr = np.empty((Mr, N), np.int64)
+    ktop = k
     k = np.zeros(Mr, np.int64)
+    entry = np.arange(N + 2)
+    isnan = np.isnan(z) & (entry[None, :] <= ktop[:, None])
+    nan_floor = np.where(isnan.any(axis=1), isnan.argmax(axis=1), N + 2)
     for q in range(N):
         osf = R(os0 + q)
-        while True:
+        if readout == "max":
+            with np.errstate(invalid="ignore"):
+                below = (z < osf) & (entry[None, :] <= ktop[:, None])     # entries above the top are stale
+            k = N + 1 - np.argmax(below[:, ::-1], axis=1)                 # the last one; entry 0 (z = -inf) always qualifies
+        while readout == "reference":
             zn = z[rows, k + 1]
-            read_tie |= zn == osf
-            m = zn < osf
+            with np.errstate(invalid="ignore"):
+                read_tie |= zn == osf
+                m = zn < osf
             if not m.any():
                 break
             k[m] += 1
         vk = v[rows, k]
         x = np.float64(os0 + q) - vk
-        out[:, q] = ((a * (x * x) + b * x) + s64[rows, vk]).astype(R)
+        with np.errstate(invalid="ignore"):
+            out[:, q] = ((a * (x * x) + b * x) + s64[rows, vk]).astype(R)
         ptr[:, q] = vk
-    return out, ptr, {"depth": depth, "maxpop": maxpop, "scan_tie": scan_tie, "read_tie": read_tie}
+    return out, ptr, {"depth": depth, "maxpop": maxpop, "scan_tie": scan_tie, "read_tie": read_tie, "nan_isect": nan_isect,
+                      "top": ktop, "nan_floor": nan_floor}
 
 
-def replay_dt(score, ax, bx, ay, by, osx, osy, R=np.float32):
+def replay_dt(score, ax, bx, ay, by, osx, osy, R=np.float32, readout="reference"):
     """Both passes of one transform: the output (M, N) and the statistics of the rows pass and of the columns pass."""
-    tmp, _, st_r = replay_rows(score, ax, bx, osx, R)
-    out, _, st_c = replay_rows(tmp.T, ay, by, osy, R)
+    tmp, _, st_r = replay_rows(score, ax, bx, osx, R, readout)
+    out, _, st_c = replay_rows(tmp.T, ay, by, osy, R, readout)
     return out.T, st_r, st_c

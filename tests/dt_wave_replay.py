@@ -6,7 +6,8 @@ drained over spilled pairs (no entry left; in the forward scan, whose elements e
 
 The replay MOVES the entries (ring slots are poisoned when an entry leaves them, the stack has exactly the kernel's records), so
 a service that overwrote a live slot, reloaded into a full ring or lost a pair would show in the results; every service also
-checks the invariants it relies on.  plain_rows is computeRow (include/DistanceTransform.hpp:152-182) with nothing else.
+checks the invariants it relies on.  plain_rows is computeRow (include/DistanceTransform.hpp:152-182) with nothing else; its
+read-out is stated as the entry every kernel variant takes, max{k : z[k] < os + q} (computeRow's own wherever z[] holds no NaN).
 Shared by tests/test_dt_ring_service_cpu.py, tests/test_gpu_dt_ring_service.py and tools/dt_wave_sim.py."""
 import numpy as np
 
@@ -25,8 +26,8 @@ def _isect(a, b, x0, x1, y0, y1, R):
 
 
 def plain_rows(src, a, b, os0, R=np.float32):
-    """computeRow on every row of src (M, N).  Returns the finished envelope v (M, N), z (M, N), its top index (M,), and the
-    read-out's values (M, N) R and pointers (M, N)."""
+    """computeRow's forward scan on every row of src (M, N) and the read-out every kernel variant shares.  Returns the finished
+    envelope v (M, N), z (M, N), its top index (M,), and the read-out's values (M, N) R and pointers (M, N)."""
     src = np.ascontiguousarray(src, R)
     Mr, N = src.shape
     rows = np.arange(Mr)
@@ -50,17 +51,17 @@ def plain_rows(src, a, b, os0, R=np.float32):
     ktop = k.copy()
     out = np.empty((Mr, N), R)
     ptr = np.empty((Mr, N), np.int64)
-    k = np.zeros(Mr, np.int64)
+    entry = np.arange(N + 1)
     for q in range(N):
-        osf = R(os0 + q)
-        while True:
-            m = (k < ktop) & (z[rows, np.minimum(k + 1, ktop)] < osf)     # entries above the top are stale
-            if not m.any():
-                break
-            k[m] += 1
+        # the read-out of dt_stream (and of k_dt_coop): entry max{k : z[k] < os + q}, a comparison with NaN being false
+        # (include/pbd.h, pbd_dp_min); where z[1..top] is increasing it is the entry computeRow's walk up from 0 stops at
+        with np.errstate(invalid="ignore"):
+            below = (z < R(os0 + q)) & (entry[None, :] <= ktop[:, None])      # entries above the top are stale
+        k = N - np.argmax(below[:, ::-1], axis=1)
         vk = v[rows, k]
         x = np.float64(os0 + q) - vk
-        out[:, q] = ((a * (x * x) + b * x) + s64[rows, vk]).astype(R)
+        with np.errstate(invalid="ignore"):
+            out[:, q] = ((a * (x * x) + b * x) + s64[rows, vk]).astype(R)
         ptr[:, q] = vk
     return v, z[:, :N], ktop, out, ptr
 

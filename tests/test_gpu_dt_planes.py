@@ -44,7 +44,8 @@ def _inputs(handle, flat, set_name):
     """The score planes of one (handle, model, set): what the handle is given and what the oracle must be run on."""
     seed = {"u8": 101, "i16": 202}[set_name]
     if handle == "f16":
-        # fp16 responses: the wide planes keep to fp16's range (non-finite scores are out of scope)
+        # fp16 responses: the wide planes keep to fp16's range (scores that saturate to +-Inf, and infinite and NaN scores on
+        # every handle: tests/test_gpu_dt_nonfinite.py)
         given = H.level_scores(flat.nfilters, SETS[set_name], seed, np.float32, big=3e4)
         return given, [g.astype(np.float16).astype(np.float32) for g in given]
     given = H.level_scores(flat.nfilters, SETS[set_name], seed, np.float64 if handle == "f64" else np.float32)
