@@ -1099,7 +1099,14 @@ int pbd_detect_batch(pbd_handle *h, int nframes, const void *const *imgs, int ro
  * waiting; wait() returns the candidates of the oldest submitted batch (same records and order as pbd_detect_batch).
  * Up to two batches may be in flight -- submit(k+1), then wait(k) -- so that the host-side staging and the PCIe
  * transfer of batch k+1 overlap the kernels of batch k.  The synchronous entry points and the staged read-back
- * refuse to run (PBD_ERR_STATE) while a batch is in flight. */
+ * refuse to run (PBD_ERR_STATE) while a batch is in flight.
+ * pbd_detect_batch_wait releases the oldest batch's slot on EVERY return except the refusals that look at no batch: "no
+ * batch in flight" (PBD_ERR_STATE) and a null handle, cand or ncand (PBD_ERR_INVALID).  In particular a wait that returns
+ * PBD_ERR_CAPACITY -- more candidates than `capacity` or than pbd_config.max_candidates: the first min(capacity, max_candidates)
+ * records are delivered and counted in *ncand; or, with pbd_set_nms on, more than max_candidates before the suppression: *ncand = 0 -- has
+ * consumed its batch: the next wait returns the NEXT batch, and a caller that wants the rest of the list has to submit the
+ * frames again.  A caller that keeps a count of batches in flight (detector.DetectorPool, pbdhost::FrameStream) therefore
+ * counts a failed wait as a collected batch.  A refused submit enqueues nothing and leaves the batches in flight as they were. */
 int pbd_detect_batch_submit(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int channels,
                             size_t stride_bytes);
 int pbd_detect_batch_wait(pbd_handle *h, int32_t *cand, int capacity, int *ncand);

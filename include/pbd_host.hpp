@@ -1212,16 +1212,21 @@ public:
 // A stream of single frames over K handles (K HIP streams + workspaces) of one GPU, fed round-robin -- new surface: the
 // reference's callers run detect(im) one frame at a time (cells/detect.cpp:213, ros/Node.cpp:144), and one frame's kernels do
 // not fill an MI355X; frames on different handles overlap at kernel granularity (one 640x480 frame: 423 -> 525 frames/s with
-// four handles).  Results come back in submission order and are those of detect() on one handle.
+// four handles, measured by bench.py through the same scheme in Python, detector.DetectorPool; `pbd_demo --stream` prints this
+// class's own rate).  Results come back in submission order and are those of detect() on one handle.
 //     FrameStream<float> fs(model, 4);
 //     for (;;) { while (fs.full()) { fs.next(cands); use(cands); }   fs.submit(frame); }
 //     while (fs.pending()) { fs.next(cands); use(cands); }
 // Frames are 8-bit (pbd_detect_batch_submit); a submitted frame's pixels are copied before submit() returns.
+// A next() that throws (PBD_ERR_CAPACITY: the frame held more candidates than `capacity`) has consumed its frame: `candidates`
+// is left empty, and the following next() returns the following frame's list, from the next handle.  Only the "nothing
+// submitted" refusal consumes nothing.
 template <typename T>
 class FrameStream {
     std::vector<pbd_handle *> h_;
     size_t submitted_, collected_;
     int capacity_;
+    std::vector<int32_t> buf_;       // next()'s record buffer, kept between calls
     FrameStream(const FrameStream &);
     FrameStream &operator=(const FrameStream &);
 public:
@@ -1281,12 +1286,13 @@ public:
     {   // the oldest submitted frame's candidates
         if (!pending()) throw Error(PBD_ERR_STATE, "FrameStream::next(): nothing submitted");
         pbd_handle *h = h_[collected_ % h_.size()];
-        std::vector<int32_t> buf((size_t)capacity_ * pbd_candidate_stride(h) + 1);
+        buf_.resize((size_t)capacity_ * pbd_candidate_stride(h) + 1);      // sized once: every handle has the model's stride
         int n = 0;
-        pbdbind::check<HostTraits<T> >(h, pbd_detect_batch_wait(h, &buf[0], capacity_, &n));
-        ++collected_;
+        const int rc = pbd_detect_batch_wait(h, &buf_[0], capacity_, &n);
+        ++collected_;        // the wait has released the handle's slot, failed or not: the next call takes the next handle
         candidates.clear();
-        pbdbind::unpack_candidates<HostTraits<T> >(h, buf, n, candidates);
+        pbdbind::check<HostTraits<T> >(h, rc);
+        pbdbind::unpack_candidates<HostTraits<T> >(h, buf_, n, candidates);
     }
 };
 

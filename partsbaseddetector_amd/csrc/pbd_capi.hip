@@ -1520,6 +1520,8 @@ int check_frames(pbd_handle *h, int nframes, const FrameSrc &src, int rows, int 
         return fail(h, PBD_ERR_UNSUPPORTED, "image depth code %d: 0 (8U), 2 (16U), 5 (32F) or 6 (64F), src/HOGFeatures.cpp:136-146", depth);
     if (cn != 1 && cn != 3) return fail(h, PBD_ERR_INVALID, "channels %d (1 or 3, src/HOGFeatures.cpp:171)", cn);
     if (!src.host) return PBD_OK;
+    for (int i = 0; i < nframes; ++i)
+        if (!src.host[i]) return fail(h, PBD_ERR_INVALID, "frame %d is a null pointer", i);
     const size_t row_bytes = (size_t)cols * cn * depth_size(depth);
     if (src.stride < row_bytes) return fail(h, PBD_ERR_INVALID, "stride %zu < row bytes %zu", src.stride, row_bytes);
     // 32F / 64F images: a NaN or Inf pixel is refused.  The reference computes *something* deterministic from one (NaN

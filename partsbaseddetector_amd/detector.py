@@ -1815,7 +1815,8 @@ class DetectorPool:
     MI355X: one 640x480 frame per step 423 -> 525 detections/s with four handles, one 1920x1080 frame 83 -> 103 with three;
     batches that fill the chip (64 x 640x480, 8 x 1920x1080) gain nothing (profiles/r03_bench_*s*.json,
     profiles/r03_streams_*.txt).  Results come back in submission order; every batch is computed by exactly one handle, so
-    they are those of a single PartsBasedDetector.
+    they are those of a single PartsBasedDetector.  A wait_batch() that raises has consumed its batch: the batches behind it
+    on the other lanes stay collectable, in order.
 
         pool = DetectorPool(model, n=3, max_batch=64)
         for batch in stream:                       # frames resident on the device
@@ -1866,12 +1867,17 @@ class DetectorPool:
         self._submitted += 1
 
     def wait_batch(self, capacity: Optional[int] = None, raw: bool = False):
-        """the oldest uncollected batch's candidates (as PartsBasedDetector.wait_batch)"""
+        """the oldest uncollected batch's candidates (as PartsBasedDetector.wait_batch).
+
+        A wait that fails -- PbdError(-4): more candidates than `capacity`, or than max_candidates before the suppression --
+        has still released its lane's slot (pbd_detect_batch_wait, include/pbd.h), so that batch counts as collected: the
+        exception reaches the caller, its records beyond what fitted are gone, and the next wait_batch() returns the NEXT
+        batch from the next lane.  Only the pool's own "nothing submitted" refusal leaves the cursor where it was."""
         if not self.pending:
             raise PbdError(-5, "DetectorPool.wait_batch(): nothing submitted")
-        out = self._lane(self._collected).wait_batch(capacity, raw)
-        self._collected += 1
-        return out
+        lane = self._lane(self._collected)
+        self._collected += 1        # whatever the lane call does below: its slot is released, the cursor moves on
+        return lane.wait_batch(capacity, raw)
 
     def setRootNMS(self, sz: int) -> None:
         """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""

@@ -270,31 +270,75 @@ class DeviceBatchGather:
     ``submit`` enqueues the whole path of batch k (the candidate list goes into this batch's payload tensor, on the
     device), THEN finishes the gather of batch k-1 -- whose collective ran under batch k-1's successor being enqueued and is
     long complete -- and issues batch k's collective behind its kernels.  The detection kernels run on the detector's own
-    stream; the collective is ordered behind them with an event."""
+    stream; the collective is ordered behind them with an event.
+
+    Every ``submit`` issues exactly one collective, whatever fails on this rank (a rank that skipped it would leave all the
+    others blocked in all_gather_into_tensor until the RCCL timeout):
+
+    * the detect call of batch k raises ``PbdError`` (a refused argument, PBD_ERR_CAPACITY, ...): the rank writes -1 into word
+      0 of batch k's payload -- on the detector's stream, behind whatever the failed call had already enqueued -- and enters
+      the collective like the others.  ``submit`` still returns batch k-1's records; the ``finish()`` of batch k (in the next
+      ``submit`` or in ``collect``) raises ``RankFailed`` on EVERY rank, on this one chained to the ``PbdError``.
+    * the ``finish()`` of batch k-1 raises (``RankFailed``, ``OverflowError``): batch k's collective is issued first, then
+      the exception propagates.  Batch k is then in flight as after any ``submit``.
+
+    Over a gloo gatherer (CPU tensors: the tests' rehearsal, with a stand-in detector that fills ``g.payload``) there is no
+    stream to order behind and none is made."""
 
     def __init__(self, det, gatherer: CandidateGatherer):
-        import torch
         self.det, self.g = det, gatherer
-        self.stream = torch.cuda.ExternalStream(det.hd.stream_ptr(), device=gatherer.device)
+        self.stream = None
+        if gatherer.device.type == "cuda":
+            import torch
+            self.stream = torch.cuda.ExternalStream(det.hd.stream_ptr(), device=gatherer.device)
+        self._err = None                         # the PbdError of the batch whose gather is pending, if its detect call raised
+
+    def _flag_failed(self, pay):
+        """word 0 of this batch's payload = -1, ordered behind the kernels the failed call may have left on the detector's stream"""
+        if self.stream is not None:
+            with self.g.torch.cuda.stream(self.stream):
+                pay[:1].fill_(-1)
+        else:
+            pay[:1].fill_(-1)
+
+    def _finish(self, root_only: bool):
+        """the pending gather's records; a RankFailed names this rank's own error, if it had one"""
+        err, self._err = self._err, None
+        try:
+            return self.g.finish(root_only)
+        except RankFailed as rf:
+            if err is None:
+                raise
+            raise RankFailed(f"{rf}; this rank: {err}") from err
+
+    def _submit(self, enqueue, root_only: bool):
+        from ._lib import PbdError
+        pay = self.g.payload                     # not the tensor a pending gather is reading: the buffers alternate
+        err = None
+        try:
+            enqueue(pay)
+        except PbdError as e:
+            err = e
+            self._flag_failed(pay)
+        try:
+            prev = self._finish(root_only) if self.g.pending else None
+        finally:                                 # this batch's collective is issued whatever the previous batch's finish() did
+            self._err = err
+            self.g.begin_device(self.stream)
+        return prev
 
     def submit(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int, frame_offset: int, root_only: bool = False):
-        pay = self.g.payload                     # not the tensor a pending gather is reading: the buffers alternate
-        self.det.detect_batch_device_out(d_frames_ptr, nframes, rows, cols, cn, frame_offset, pay.data_ptr(), self.g.cap_full)
-        prev = self.g.finish(root_only) if self.g.pending else None
-        self.g.begin_device(self.stream)
-        return prev
+        return self._submit(lambda pay: self.det.detect_batch_device_out(d_frames_ptr, nframes, rows, cols, cn, frame_offset,
+                                                                         pay.data_ptr(), self.g.cap_full), root_only)
 
     def submit_frames(self, descs, cn: int, frame_offset: int, root_only: bool = False):
         """``submit`` for frames of different sizes: descs = (device pointer, rows, cols, pitch) per frame of this rank's
         share (pbd_detect_frames_device_out); the records' `frame` = frame_offset + index in descs."""
-        pay = self.g.payload
-        self.det.detect_frames_device_out(descs, cn, frame_offset, pay.data_ptr(), self.g.cap_full)
-        prev = self.g.finish(root_only) if self.g.pending else None
-        self.g.begin_device(self.stream)
-        return prev
+        return self._submit(lambda pay: self.det.detect_frames_device_out(descs, cn, frame_offset, pay.data_ptr(), self.g.cap_full),
+                            root_only)
 
     def collect(self, root_only: bool = False):
-        return self.g.finish(root_only) if self.g.pending else None
+        return self._finish(root_only) if self.g.pending else None
 
 
 def detect_level_sharded(det, im, gatherer: "CandidateGatherer", root_only: bool = False):

@@ -427,3 +427,151 @@ def test_several_gatherers_in_flight_round_robin():
         assert rec.shape == (n0 + n1, stride)
         assert np.array_equal(rec[:, 0], np.concatenate([np.arange(n0), np.arange(n1) + 50]))
         assert np.array_equal(rec[:, 2], np.concatenate([np.full(n0, 1000 * s), np.full(n1, 1000 * s + 100)]))
+
+
+class _StubDetector:
+    """stands in for a PartsBasedDetector over a gloo gatherer: its "kernels" are numpy writes into the payload tensor the
+    gatherer hands out (found at `g.payload`: the stub gets a pointer, like the detector); raises PbdError on request"""
+
+    def __init__(self, g, rank, stride, counts, fail_at=None):
+        self.g, self.rank, self.stride, self.counts, self.fail_at, self.batch = g, rank, stride, counts, fail_at, 0
+
+    def detect_batch_device_out(self, d_frames_ptr, nframes, rows, cols, cn, frame_offset, d_payload_ptr, capacity):
+        from partsbaseddetector_amd._lib import PbdError
+        b, self.batch = self.batch, self.batch + 1
+        assert d_payload_ptr == self.g.payload.data_ptr() and capacity == self.g.cap_full
+        p = self.g.payload.numpy()
+        n = self.counts[b]
+        p[0] = n                                              # what a call that fails late may already have written
+        m = min(n, capacity)
+        rec = p[1:1 + m * self.stride].reshape(m, self.stride)
+        rec[:] = 1000 * b + 100 * self.rank
+        rec[:, 0] = np.arange(m) + frame_offset
+        if b == self.fail_at:
+            raise PbdError(-4, f"batch {b} failed on rank {self.rank}")
+
+    def detect_frames_device_out(self, descs, cn, frame_offset, d_payload_ptr, capacity):
+        self.detect_batch_device_out(0, len(descs), 0, 0, cn, frame_offset, d_payload_ptr, capacity)
+
+
+def _want_stub(b, counts):
+    out = []
+    for rank, n in enumerate(counts):
+        r = np.full((n, 12), 1000 * b + 100 * rank, np.int32)
+        r[:, 0] = np.arange(n) + 50 * rank
+        out.append(r)
+    return np.concatenate(out)
+
+
+def _submit_failure_worker(rank, world, port, q, frames_form):
+    import torch.distributed as dist
+    from partsbaseddetector_amd import dist as pd
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    try:
+        stride = 12
+        g = pd.CandidateGatherer(stride, cap=16, device="cpu", cap_full=64)
+        det = _StubDetector(g, rank, stride, counts=[3 + rank, 5, 2 + 2 * rank], fail_at=1 if rank == 1 else None)
+        dg = pd.DeviceBatchGather(det, g)                     # no stream wrapper over a gloo gatherer
+        assert dg.stream is None
+
+        def submit():
+            if frames_form:
+                return dg.submit_frames([(0, 1, 1, 1)], 3, 50 * rank)
+            return dg.submit(0, 1, 1, 1, 3, 50 * rank)
+
+        log = []
+        log.append(("none", submit() is None))                # batch 0
+        log.append(("rec", submit().copy()))                  # batch 1: rank 1's detect raises inside; batch 0's records
+        try:
+            submit()                                          # batch 2: the finish() of batch 1
+            log.append(("no error", None))
+        except pd.RankFailed as e:
+            log.append(("failed", (str(e), type(e.__cause__).__name__)))
+        log.append(("rec", dg.collect().copy()))              # batch 2 was issued before the exception left submit()
+        log.append(("none", dg.collect() is None))
+        q.put((rank, log, g.collectives))
+    finally:
+        dist.destroy_process_group()
+
+
+def _run_world2(target, args, nresults=2):
+    import multiprocessing as mp
+    import queue
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=target, args=(r, 2, port, q) + args) for r in range(2)]
+    for p in procs:
+        p.start()
+    res, blocked = {}, False
+    try:
+        for _ in range(nresults):
+            got = q.get(timeout=60)                            # a rank left in the collective never answers
+            res[got[0]] = got[1:]
+    except queue.Empty:
+        blocked = True
+    for p in procs:
+        p.join(timeout=5 if blocked else 60)
+    alive = [p.is_alive() for p in procs]
+    for p in procs:
+        if p.is_alive():
+            p.terminate()
+            p.join(timeout=30)
+    assert not blocked and not any(alive), f"ranks answered: {sorted(res)}, still running: {alive}"
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    return res
+
+
+@pytest.mark.parametrize("frames_form", [False, True])
+def test_device_batch_gather_detect_failure_still_enters_the_collective(frames_form):
+    """DeviceBatchGather.submit / submit_frames: the detect call of batch 1 of 3 raises PbdError on rank 1.  That rank flags
+    its payload (-1 in word 0) and issues the batch's collective like rank 0: both ranks get batch 0's records from that very
+    submit, both get RankFailed for batch 1 (rank 1's chained to its PbdError), batch 2 gathers, both exit."""
+    res = _run_world2(_submit_failure_worker, (frames_form,))
+    for rank in range(2):
+        log, ncoll = res[rank]
+        assert [k for k, _ in log] == ["none", "rec", "failed", "rec", "none"], [k for k, _ in log]
+        assert log[0][1] and log[4][1]
+        assert np.array_equal(log[1][1], _want_stub(0, (3, 4)))
+        msg, cause = log[2][1]
+        assert "rank(s) [1]" in msg
+        assert (cause == "PbdError" and "batch 1 failed on rank 1" in msg) if rank == 1 else cause == "NoneType"
+        assert np.array_equal(log[3][1], _want_stub(2, (2, 4)))
+        assert ncoll == 3                                       # one collective per batch on both ranks, no more, no fewer
+
+
+def _finish_failure_worker(rank, world, port, q):
+    import torch.distributed as dist
+    from partsbaseddetector_amd import dist as pd
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    try:
+        stride = 12
+        g = pd.CandidateGatherer(stride, cap=16, device="cpu", cap_full=32)
+        # batch 0: rank 1 found 1000 candidates, the payload tensors hold 32 -> OverflowError from its finish(), on both ranks
+        det = _StubDetector(g, rank, stride, counts=[(4, 1000)[rank], 6, 1 + rank])
+        dg = pd.DeviceBatchGather(det, g)
+        log = [("none", dg.submit(0, 1, 1, 1, 3, 50 * rank) is None)]
+        try:
+            dg.submit(0, 1, 1, 1, 3, 50 * rank)               # finish(batch 0) raises; batch 1's collective is issued first
+            log.append(("no error", None))
+        except OverflowError as e:
+            log.append(("overflow", str(e)))
+        log.append(("pending", g.pending))
+        log.append(("rec", dg.submit(0, 1, 1, 1, 3, 50 * rank).copy()))    # batch 1's records, with batch 2 submitted
+        log.append(("rec", dg.collect().copy()))
+        q.put((rank, log, g.collectives))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_device_batch_gather_issues_the_collective_when_the_previous_finish_raises():
+    """the finish() of batch 0 raises OverflowError on both ranks, inside submit(batch 1): batch 1's collective is issued before
+    the exception propagates, so the ranks stay in step and batches 1 and 2 gather"""
+    res = _run_world2(_finish_failure_worker, ())
+    for rank in range(2):
+        log, ncoll = res[rank]
+        assert [k for k, _ in log] == ["none", "overflow", "pending", "rec", "rec"], [k for k, _ in log]
+        assert "raise max_candidates" in log[1][1] and log[2][1] is True
+        assert np.array_equal(log[3][1], _want_stub(1, (6, 6)))
+        assert np.array_equal(log[4][1], _want_stub(2, (1, 2)))
+        assert ncoll == 3

@@ -162,6 +162,22 @@ res["collectives"] = g.collectives
 res["cap_after"] = g.cap
 res["counts"] = [len(w) for w in want]
 
+# ---- a submit whose detect call is refused (nframes > max_batch: the argument check, nothing enqueued) still issues the batch's
+# collective, flagged: the following collect() raises RankFailed (chained to the PbdError), and one more good batch gathers ----
+res["refused_submit_returned_none"] = dg.submit(dev[0].data_ptr(), 5, 120, 150, 3, frame_offset=0, root_only=True) is None
+res["refused_pending"] = g.pending
+try:
+    dg.collect(root_only=True)
+    res["refused_collect"] = "no error"
+except pd.RankFailed as e:
+    res["refused_collect"] = "RankFailed from " + type(e.__cause__).__name__
+except Exception as e:
+    res["refused_collect"] = type(e).__name__
+first = dg.submit(dev[1].data_ptr(), 4, 120, 150, 3, frame_offset=100, root_only=True)
+rec = dg.collect(root_only=True)
+res["after_refusal_ok"] = first is None and norm(rec, 100) == want[1]
+res["collectives_after_refusal"] = g.collectives
+
 # ---- host-record path on cuda (pinned staging, H2D, collective, D2H) incl. overflow ----
 g3 = pd.CandidateGatherer(st, cap=2, device="cuda:0", force_collective=True)
 buf = np.zeros((1 << 12) * st, np.int32)
@@ -205,6 +221,10 @@ def test_rccl_world1_device_gather(tmp_path):
     assert res["grown"] == 1 and res["cap_after"] >= max(res["counts"]), res      # cap 4 -> grown once to fit every batch
     assert res["collectives"] == 4, res                                            # 3 batches + one repeat (found while batch 1 was already enqueued)
     assert res["host_ok"] and res["level_ok"] and res["restored"], res
+    # DeviceBatchGather.submit with a refused detect call: the rank still entered the collective, flagged
+    assert res["refused_submit_returned_none"] and res["refused_pending"], res
+    assert res["refused_collect"] == "RankFailed from PbdError", res
+    assert res["after_refusal_ok"] and res["collectives_after_refusal"] == 6, res   # one for the flagged batch, one for the good one
 
 
 @pytest.mark.gpu
