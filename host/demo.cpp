@@ -36,6 +36,9 @@
 //           every submitted frame carries the map; not with --staged
 //   --poses: with --camera, one line per listed candidate after its "object" line: "pose COUNT x y z qx qy qz qw" (messagePoses
 //           on the part centres, on the device; COUNT 0 is the node's "Centroid not found")
+//   --augment DEG[,mirror] OUT.ppm: no detection; the image's augmented copy rotate(mirror(image)) -- turned counter-clockwise by
+//           DEG degrees, nearest neighbour, zero outside (pbd_augment_frames) -- written as a binary PPM
+//           (PGM for grey) and one line "augment ROWS COLS"
 //   pbd_demo model.(yml|xml|mat) --dump-model  (no GPU needed: prints what the model reader read)
 // The model reader follows the extension, as the reference's demo chooses it (src/demo.cpp:63-77): .mat -> MatlabIOModel
 // (include/pbd_matlabio.hpp), any other -> FileStorageModel.
@@ -299,12 +302,33 @@ static int dump_model(const Model &m)
     return 0;
 }
 
+// --augment: the image's augmented copy, written as a PNM
+static int run_augment(Model &model, const Image &im, double degrees, bool mirror, const char *out_path)
+{
+    PartsBasedDetector<float> pbd(0, PBD_CONV_EXACT);
+    pbd.distributeModel(model);
+    pbd_augment job;
+    job.frame = 0; job.mirror = mirror ? 1 : 0; job.degrees = degrees;
+    std::vector<std::vector<unsigned char> > pixels;
+    std::vector<Image> out;
+    pbd.augmentFrames(std::vector<Image>(1, im), std::vector<pbd_augment>(1, job), pixels, out);
+    std::printf("augment %d %d\n", out[0].rows, out[0].cols);
+    if (!writePNM(out_path, pixels[0].data(), out[0].rows, out[0].cols, out[0].channels)) {
+        std::fprintf(stderr, "cannot write the augmented image\n");
+        return -1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
+    const char *augment_path = NULL;
+    double augment_deg = 0;
+    bool augment_mirror = false;
     bool dbl = false, staged = false;
     float nms = -1.f, dnms = -1.f;
     int top = 1 << 30, stream_k = 0, stream_n = 0, conv_mode = PBD_CONV_EXACT;
@@ -347,6 +371,13 @@ int main(int argc, char **argv)
             char tail = 0;
             g_prune = std::sscanf(argv[++i], "%f,%f,%f%c", &g_prune_fx, &g_prune_width, &g_prune_tol, &tail) == 3;
             if (!g_prune) { std::fprintf(stderr, "--depth-prune takes fx,width,tol\n"); return -1; }
+        }
+        else if (!std::strcmp(argv[i], "--augment") && i + 2 < argc) {
+            char word[8] = "", tail = 0;
+            const int got = std::sscanf(argv[++i], "%lf,%7[a-z]%c", &augment_deg, word, &tail);
+            augment_mirror = got == 2 && !std::strcmp(word, "mirror");
+            if (got < 1 || got > 2 || (got == 2 && !augment_mirror)) { std::fprintf(stderr, "--augment takes deg[,mirror] out.ppm\n"); return -1; }
+            augment_path = argv[++i];
         }
         else if (!std::strcmp(argv[i], "--camera") && i + 1 < argc) {
             have_camera = std::sscanf(argv[++i], "%lf,%lf,%lf,%lf", &camera.fx, &camera.fy, &camera.cx, &camera.cy) == 4;
@@ -404,6 +435,7 @@ int main(int argc, char **argv)
         std::vector<uint8_t> pix;
         Image im;
         if (!readPNM(argv[2], pix, im)) { std::fprintf(stderr, "Image not found, or invalid image format\n"); return -1; }
+        if (augment_path) return run_augment(model, im, augment_deg, augment_mirror, augment_path);
         if (!also.empty()) {
             std::vector<std::vector<uint8_t> > pixels(also.size() + 1);
             std::vector<Image> ims(also.size() + 1);

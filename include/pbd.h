@@ -834,8 +834,9 @@ int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, i
 /* Warped positives (new surface; opt-in): poswarp of the reference's Matlab training code (matlab/learning/train.m:131-162 with
  * matlab/learning/warppos.m, subarray.m and qp_poswrite), the examples every training run starts from (trainmodel.m:19-40 trains
  * each part mixture as a one-part model on them).  DESIGN.md section 6k.  Each annotated box is padded by one cell, cropped with
- * edge replication, resized to (k + 2) * sbin pixels, and its HOG written as an example in pbd_examples' format.  No
- * flipping: that stays with the caller (the train() loop over these calls is partsbaseddetector_amd/train.py).
+ * edge replication, resized to (k + 2) * sbin pixels, and its HOG written as an example in pbd_examples' format.  Mirrored
+ * and rotated copies are made by pbd_augment_frames* (below), not here (the train() loop over these calls
+ * is partsbaseddetector_amd/train.py).
  * Frames as pbd_detect_frames takes them: host pointers (pbd_warp_positives) or device pointers (the _device form), mixed sizes,
  * one `channels` (1 or 3) and one depth_code (all four) per call; a _device frame may be a region of a larger device image, read
  * in place through its pitch, its pointer and stride_bytes multiples of the element size.  A frame only has to be 1 x 1 or
@@ -888,6 +889,44 @@ int pbd_warp_positives(pbd_handle *h, int nframes, const struct pbd_frame *frame
 int pbd_warp_positives_device(pbd_handle *h, int nframes, const struct pbd_frame *d_frames, int channels, int depth_code, int nboxes,
                               const int32_t *boxes, int filter, int bias, int skip_small, int id_offset, int32_t *d_payload,
                               int capacity, int32_t *d_hdr, void *d_values);
+/* Augmented positives (new surface; opt-in): the rotated and mirrored copies the reference's training pipeline multiplies its
+ * positives by (matlab/globals.m:18-23 imrotate/ and imflip/, matlab/learning/map_rotate_points.m, train.m:130,165; the step
+ * itself, PARSE_data.m, is not in the reference).  DESIGN.md section 6r; the numpy yardstick is partsbaseddetector_amd/augment.py.
+ * A copy of a frame (rows x cols x channels, any of the four depths) is rotate(mirror(frame)):
+ *   mirror   column q becomes cols - 1 - q.
+ *   rotate   degrees == 0: none, the copy has the frame's size.  Otherwise (map_rotate_points.m:20-35) (c, s) = (cos, sin) of
+ *     degrees * pi / 180 in double, exactly {0, +-1} for multiples of 90; hA = ((rows - 1) / 2, (cols - 1) / 2); the corners
+ *     (-hAr, hAc) and (hAr, hAc) as row vectors times [c s; -s c]; hB = ceil(max|.| / 2) * 2 per axis; the copy is
+ *     (2 hBr + 1) x (2 hBc + 1).  Its pixel (R, Q) is the source's pixel (floor(r + 0.5), floor(q + 0.5)) with
+ *     r = (R - hBr) c + (Q - hBc) s + hAr, q = -((R - hBr) s) + (Q - hBc) c + hAc (every product rounded, sums left to right),
+ *     all bytes 0 outside the source: nearest neighbour, positive angles counter-clockwise.  imrotate's toolbox code is not
+ *     reproduced (bilinear and cropped rotation are out of scope).
+ * pbd_augment_plan: the copy's size and coef = {c, s}, the coefficients the kernel uses.  Pure host code.
+ * pbd_augment_points: npoints points {x, y} (0-based, real) of the frame mapped into the copy: x -> cols - 1 - x when mirror,
+ *   then the forward map of map_rotate_points.m:40.  xy_out may be xy.  Pure host code.  Both: PBD_ERR_INVALID for a size
+ *   outside 1..32000 or non-finite degrees.
+ * pbd_augment_frames*: njobs copies in ONE launch; job i = {frame, mirror, degrees} writes out[i].  Frames as
+ *   pbd_warp_positives* takes them (host or device pointers, mixed sizes and pitches, device regions of larger images, channels 1
+ *   or 3, the four depth codes); several jobs may name one frame, a frame may have no job.  Destination bytes beyond a row's
+ *   used width are not written.  pbd_augment_frames: host frames and destinations, synchronous.  pbd_augment_frames_device:
+ *   device frames and destinations (pointer and pitch multiples of the element size), asynchronous on pbd_stream().
+ * Refused before anything is enqueued, naming the offending index: PBD_ERR_INVALID for a job whose frame index is out of range,
+ *   non-finite degrees, a destination whose rows or cols differ from the plan's, whose pitch is below its row, that is NULL or
+ *   (device) misaligned, or that overlaps one of the call's frames; the frame refusals of pbd_detect_frames; PBD_ERR_STATE while
+ *   a batch is in flight.  njobs == 0 is PBD_OK.  The call has buffers of its own: the resident detect result and the detect
+ *   path are not touched. */
+struct pbd_augment { int32_t frame; int32_t mirror; double degrees; };
+int pbd_augment_plan(int rows, int cols, double degrees, int *out_rows, int *out_cols, double coef[2]);
+int pbd_augment_points(int rows, int cols, double degrees, int mirror, int npoints, const double *xy, double *xy_out);
+int pbd_augment_frames(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, int njobs,
+                       const struct pbd_augment *jobs, const struct pbd_frame *out);
+int pbd_augment_frames_device(pbd_handle *h, int nframes, const struct pbd_frame *d_frames, int channels, int depth_code, int njobs,
+                              const struct pbd_augment *jobs, const struct pbd_frame *d_out);
+/* pbd_detect_latent with device frame descriptors (pointer and pitch multiples of the element size; regions of larger device
+ * images included), read in place.  boxes, mixtures, cand and found stay host arrays and the call is synchronous; every refusal
+ * and the resident result afterwards are those of pbd_detect_latent (the NaN / Inf refusal reads host pixels and does not apply). */
+int pbd_detect_latent_device(pbd_handle *h, int nframes, const struct pbd_frame *d_frames, int channels, int depth_code,
+                             const int32_t *boxes, const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found);
 
 /* ---- Training QP (new surface; opt-in): the dual coordinate-descent solver of the reference's Matlab training code
  * (matlab/learning/qp_write.m, qp_one.m with oct/qp_one_sparse.cc, qp_opt.m, qp_refresh.m with oct/lincomb.cc, qp_prune.m,

@@ -1030,6 +1030,34 @@ public:
         return c;
     }
     // new surface: images of any sizes (one depth, one channel count) in one call; candidates[i] = detect(images[i])
+    // both forms of detectLatent
+    void latent(bool device, const std::vector<pbd_frame> &frames, int channels, int depth, const std::vector<std::vector<int32_t> > &boxes,
+                float overlap, const std::vector<std::vector<int32_t> > &mixtures, std::vector<Candidate> &candidates,
+                std::vector<bool> &found)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "detectLatent() before distributeModel()");
+        const size_t n = frames.size();
+        if (n == 0 || boxes.size() != n || (!mixtures.empty() && mixtures.size() != n))
+            throw Error(PBD_ERR_INVALID, "detectLatent: one box list (and mixture list) per image");
+        const size_t np = boxes[0].size() / 4;
+        std::vector<int32_t> bx, mx;
+        for (size_t i = 0; i < n; ++i) {
+            if (boxes[i].size() != 4 * np || (!mixtures.empty() && mixtures[i].size() != np))
+                throw Error(PBD_ERR_INVALID, "detectLatent: four box values and one mixture per part");
+            bx.insert(bx.end(), boxes[i].begin(), boxes[i].end());
+            if (!mixtures.empty()) mx.insert(mx.end(), mixtures[i].begin(), mixtures[i].end());
+        }
+        const int stride = pbd_candidate_stride(h_);
+        std::vector<int32_t> rec(n * (size_t)stride), fnd(n);
+        bx.push_back(0);
+        pbdbind::check<HostTraits<T> >(h_, (device ? pbd_detect_latent_device : pbd_detect_latent)(
+                                               h_, (int)n, &frames[0], channels, depth, &bx[0], mx.empty() ? NULL : &mx[0], overlap,
+                                               &rec[0], &fnd[0]));
+        candidates.clear();
+        pbdbind::unpack_candidates<HostTraits<T> >(h_, rec, (int)n, candidates);
+        found.assign(n, false);
+        for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
+    }
     void detectBatch(const std::vector<Image> &images, std::vector<std::vector<Candidate> > &candidates)
     {
         if (!h_) throw Error(PBD_ERR_STATE, "detectBatch() before distributeModel()");
@@ -1041,29 +1069,68 @@ public:
     void detectLatent(const std::vector<Image> &images, const std::vector<std::vector<int32_t> > &boxes, float overlap,
                       const std::vector<std::vector<int32_t> > &mixtures, std::vector<Candidate> &candidates, std::vector<bool> &found)
     {
-        if (!h_) throw Error(PBD_ERR_STATE, "detectLatent() before distributeModel()");
-        const size_t n = images.size();
-        if (n == 0 || boxes.size() != n || (!mixtures.empty() && mixtures.size() != n))
-            throw Error(PBD_ERR_INVALID, "detectLatent: one box list (and mixture list) per image");
-        const size_t np = boxes[0].size() / 4;
-        std::vector<pbd_frame> fr(n);
-        std::vector<int32_t> bx, mx;
-        for (size_t i = 0; i < n; ++i) {
-            if (boxes[i].size() != 4 * np || (!mixtures.empty() && mixtures[i].size() != np))
-                throw Error(PBD_ERR_INVALID, "detectLatent: four box values and one mixture per part");
+        std::vector<pbd_frame> fr(images.size());
+        for (size_t i = 0; i < images.size(); ++i) {
             fr[i].data = images[i].data; fr[i].rows = images[i].rows; fr[i].cols = images[i].cols; fr[i].stride_bytes = images[i].step;
-            bx.insert(bx.end(), boxes[i].begin(), boxes[i].end());
-            if (!mixtures.empty()) mx.insert(mx.end(), mixtures[i].begin(), mixtures[i].end());
         }
-        const int stride = pbd_candidate_stride(h_);
-        std::vector<int32_t> rec(n * (size_t)stride), fnd(n);
-        bx.push_back(0);
-        pbdbind::check<HostTraits<T> >(h_, pbd_detect_latent(h_, (int)n, &fr[0], images[0].channels, images[0].depth, &bx[0],
-                                                             mx.empty() ? NULL : &mx[0], overlap, &rec[0], &fnd[0]));
-        candidates.clear();
-        pbdbind::unpack_candidates<HostTraits<T> >(h_, rec, (int)n, candidates);
-        found.assign(n, false);
-        for (size_t i = 0; i < n; ++i) found[i] = fnd[i] != 0;
+        latent(false, fr, images.empty() ? 3 : images[0].channels, images.empty() ? 0 : images[0].depth, boxes, overlap, mixtures,
+               candidates, found);
+    }
+    // the same on frames already on the device (pbd_detect_latent_device): d_frames hold device pointers, regions of larger device
+    // images included (read in place through their pitch); boxes, mixtures and the result stay on the host; synchronous
+    void detectLatentDevice(const std::vector<pbd_frame> &d_frames, int channels, int depth,
+                            const std::vector<std::vector<int32_t> > &boxes, float overlap,
+                            const std::vector<std::vector<int32_t> > &mixtures, std::vector<Candidate> &candidates,
+                            std::vector<bool> &found)
+    {
+        latent(true, d_frames, channels, depth, boxes, overlap, mixtures, candidates, found);
+    }
+    // ---- augmented positives (include/pbd.h "Augmented positives"): rotated and mirrored copies.
+    // the size of the copy of a rows x cols frame turned by `degrees`, and the coefficients {cos, sin} the kernel uses
+    static void augmentPlan(int rows, int cols, double degrees, int &out_rows, int &out_cols, double coef[2])
+    {
+        const int rc = pbd_augment_plan(rows, cols, degrees, &out_rows, &out_cols, coef);
+        if (rc != PBD_OK) throw Error(rc, pbd_last_error(NULL));
+    }
+    // points {x, y, x, y ...} (0-based, real) of a rows x cols frame mapped into its copy (map_rotate_points.m 'ori2new' after the
+    // mirror).  In a mirrored copy the caller gives part p the mapped point of part perm[p].
+    static std::vector<double> augmentPoints(int rows, int cols, double degrees, bool mirror, const std::vector<double> &xy)
+    {
+        if (xy.size() % 2) throw Error(PBD_ERR_INVALID, "augmentPoints: two values per point {x, y}");
+        std::vector<double> in(xy), out(xy.size() + 1, 0.0);
+        in.push_back(0.0);
+        const int rc = pbd_augment_points(rows, cols, degrees, mirror ? 1 : 0, (int)(xy.size() / 2), &in[0], &out[0]);
+        if (rc != PBD_OK) throw Error(rc, pbd_last_error(NULL));
+        out.resize(xy.size());
+        return out;
+    }
+    // copy i = rotate(mirror(images[jobs[i].frame])) by jobs[i].degrees (counter-clockwise, nearest neighbour, zero outside), all
+    // in one launch (pbd_augment_frames): out[i] views pixels[i], dense rows.  One depth and one channel count per call.
+    void augmentFrames(const std::vector<Image> &images, const std::vector<pbd_augment> &jobs,
+                       std::vector<std::vector<unsigned char> > &pixels, std::vector<Image> &out)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "augmentFrames() before distributeModel()");
+        const size_t n = jobs.size(), nf = images.size();
+        const int cn = nf ? images[0].channels : 3, depth = nf ? images[0].depth : 0;
+        const size_t es = depth == 0 ? 1 : depth == 2 ? 2 : depth == 5 ? 4 : 8;
+        std::vector<pbd_frame> fr(nf + 1), dst(n + 1);
+        for (size_t i = 0; i < nf; ++i) {
+            fr[i].data = images[i].data; fr[i].rows = images[i].rows; fr[i].cols = images[i].cols; fr[i].stride_bytes = images[i].step;
+        }
+        pixels.assign(n, std::vector<unsigned char>());
+        out.assign(n, Image());
+        for (size_t i = 0; i < n; ++i) {
+            if (jobs[i].frame < 0 || (size_t)jobs[i].frame >= nf) throw Error(PBD_ERR_INVALID, "augmentFrames: a job names no image");
+            double coef[2];
+            augmentPlan(images[jobs[i].frame].rows, images[jobs[i].frame].cols, jobs[i].degrees, out[i].rows, out[i].cols, coef);
+            out[i].channels = cn; out[i].depth = depth; out[i].step = (size_t)out[i].cols * cn * es;
+            pixels[i].assign(out[i].step * out[i].rows, 0);
+            out[i].data = &pixels[i][0];
+            dst[i].data = out[i].data; dst[i].rows = out[i].rows; dst[i].cols = out[i].cols; dst[i].stride_bytes = out[i].step;
+        }
+        std::vector<pbd_augment> jb(jobs);
+        jb.push_back(pbd_augment());
+        pbdbind::check<HostTraits<T> >(h_, pbd_augment_frames(h_, (int)nf, &fr[0], cn, depth, (int)n, &jb[0], &dst[0]));
     }
     // ---- testing a model on the device (include/pbd.h "Testing a model"): matlab/detection/nms.m, bestoverlap.m and
     // matlab/evaluation/eval_pck.m, eval_apk.m + VOCap.m.  Candidates carry their frame in `frame` (0 .. nframes-1).

@@ -296,4 +296,21 @@ inline void hipPartPoses(pbd_handle *h, int n, const std::vector<float> &centres
     pbdbind::part_poses<CvTraits<T> >(h, n, centres, ncentres, dense, count, position, orientation, eigenvalues);
 }
 
+// A training positive's augmented copy on the device (pbd_augment_frames; include/pbd.h "Augmented positives"): dst becomes
+// rotate(mirror(im)), turned counter-clockwise by `degrees` (nearest neighbour, zero outside the source), of im's depth and
+// channel count (CV_8U, CV_16U, CV_32F or CV_64F; 1 or 3 channels).  The keypoints follow with pbd_augment_points.
+inline void hipAugmentFrames(pbd_handle *h, const cv::Mat &im, bool mirror, double degrees, cv::Mat &dst)
+{
+    int rows = 0, cols = 0;
+    double coef[2];
+    pbdbind::check<CvTraits<float> >(NULL, pbd_augment_plan(im.rows, im.cols, degrees, &rows, &cols, coef));
+    dst.create(rows, cols, im.depth() + ((im.channels() - 1) << 3));   // CV_MAKETYPE(depth, channels)
+    pbd_frame src, out;
+    src.data = im.data; src.rows = im.rows; src.cols = im.cols; src.stride_bytes = im.step;
+    out.data = dst.data; out.rows = dst.rows; out.cols = dst.cols; out.stride_bytes = dst.step;
+    pbd_augment job;
+    job.frame = 0; job.mirror = mirror ? 1 : 0; job.degrees = degrees;
+    pbdbind::check<CvTraits<float> >(h, pbd_augment_frames(h, 1, &src, im.channels(), im.depth(), 1, &job, &out));
+}
+
 }  // namespace pbd_adapters

@@ -59,6 +59,7 @@ SYMBOLS = [
     "pbd_grid_nms", "pbd_grid_nms_device", "pbd_set_root_nms",
     "pbd_top_k_cells", "pbd_top_k_cells_device", "pbd_set_top_k", "pbd_top_k", "pbd_top_k_device",
     "pbd_set_depth_prune", "pbd_bind_depth", "pbd_bind_depth_device", "pbd_depth_prune", "pbd_depth_prune_device",
+    "pbd_augment_plan", "pbd_augment_points", "pbd_augment_frames", "pbd_augment_frames_device", "pbd_detect_latent_device",
 ]
 
 
@@ -85,6 +86,19 @@ class CModel(C.Structure):
 class CFrame(C.Structure):
     """pbd_frame: one frame of a mixed-size call (host pointer, or device pointer for the _device forms)."""
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("stride_bytes", C.c_size_t)]
+
+
+class CAugment(C.Structure):
+    """pbd_augment: one copy of a call: the frame's index, mirror (0 / 1), degrees (counter-clockwise)"""
+    _fields_ = [("frame", C.c_int32), ("mirror", C.c_int32), ("degrees", C.c_double)]
+
+
+def augment_array(jobs):
+    """(pbd_augment[]) from (frame, mirror, degrees) tuples"""
+    arr = (CAugment * len(jobs))()
+    for i, (f, m, d) in enumerate(jobs):
+        arr[i].frame, arr[i].mirror, arr[i].degrees = int(f), 1 if m else 0, float(d)
+    return arr
 
 
 class CDepthPruneCfg(C.Structure):
@@ -295,6 +309,12 @@ def load():
     lib.pbd_eval_apk_device.argtypes = lib.pbd_eval_apk.argtypes + [C.c_void_p]
     lib.pbd_detect_latent.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                       C.c_void_p, C.c_void_p]
+    lib.pbd_detect_latent_device.argtypes = lib.pbd_detect_latent.argtypes
+    lib.pbd_augment_plan.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    lib.pbd_augment_points.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.pbd_augment_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.POINTER(CAugment),
+                                       C.POINTER(CFrame)]
+    lib.pbd_augment_frames_device.argtypes = lib.pbd_augment_frames.argtypes
     lib.pbd_qp_create.argtypes = [C.c_void_p, C.POINTER(CQpConfig), C.POINTER(C.c_void_p)]
     lib.pbd_qp_destroy.argtypes = [C.c_void_p]
     lib.pbd_qp_destroy.restype = None

@@ -332,10 +332,191 @@ int warp_positives(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, 
     return PBD_OK;
 }
 
+// ---- augmented positives (the kernel: pbd_kernels_augment.hip) --------------------------------------------
+// The geometry of one copy (matlab/learning/map_rotate_points.m:20-35): the coefficients, the half sizes of the source (hA) and
+// of the destination (hB), the destination's size.  Every product is rounded and the sums go left to right (this file is
+// compiled with -ffp-contract=off), so partsbaseddetector_amd/augment.py computes the same sizes from the same coefficients.
+struct AugGeom { int rotate, orows, ocols; double c, s, hAr, hAc, hBr, hBc; };
+constexpr int kAugMaxSide = 32000;   // a frame's largest side (check_frame_descs)
+
+bool augment_geom(int rows, int cols, double degrees, AugGeom *g)
+{
+    if (rows < 1 || cols < 1 || rows > kAugMaxSide || cols > kAugMaxSide || !std::isfinite(degrees)) return false;
+    *g = AugGeom{0, rows, cols, 1.0, 0.0, ((double)rows - 1) / 2, ((double)cols - 1) / 2, 0, 0};
+    if (degrees == 0) return true;
+    g->rotate = 1;
+    if (fmod(degrees, 90.0) == 0) {   // exact coefficients for the multiples of a quarter turn
+        static const double kC[4] = {1, 0, -1, 0}, kS[4] = {0, 1, 0, -1};
+        const int k = (int)((((long long)(fmod(degrees, 360.0) / 90.0)) % 4 + 4) % 4);
+        g->c = kC[k]; g->s = kS[k];
+    } else {
+        const double phi = degrees * M_PI / 180;
+        g->c = cos(phi); g->s = sin(phi);
+    }
+    // tformfwd([-hAr hAc; hAr hAc], [c s; -s c]): (u, v) -> (u c - v s, u s + v c)
+    const double u0 = -g->hAr, u1 = g->hAr, v = g->hAc;
+    const double mr = std::max(std::fabs(u0 * g->c - v * g->s), std::fabs(u1 * g->c - v * g->s));
+    const double mc = std::max(std::fabs(u0 * g->s + v * g->c), std::fabs(u1 * g->s + v * g->c));
+    g->hBr = ceil(mr / 2) * 2;
+    g->hBc = ceil(mc / 2) * 2;
+    g->orows = (int)(2 * g->hBr + 1);
+    g->ocols = (int)(2 * g->hBc + 1);
+    return true;
+}
+
+// the bytes [first, last) a frame's pixels occupy
+inline std::pair<uintptr_t, uintptr_t> frame_span(const pbd_frame &f, size_t px)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(f.data);
+    return {a, a + (size_t)(f.rows - 1) * f.stride_bytes + (size_t)f.cols * px};
+}
+
+// Both forms of pbd_augment_frames.  Every refusal comes before the first copy or kernel.
+int augment_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int cn, int depth, int njobs, const pbd_augment *jobs,
+                   const pbd_frame *out, bool host)
+{
+    if (njobs < 0 || nframes < 0) return fail(h, PBD_ERR_INVALID, "njobs %d, nframes %d", njobs, nframes);
+    if (int rc = check_frame_descs(h, frames ? nframes : 0, frames, cn, depth, host)) return rc;   // frames may be NULL without jobs
+    const size_t es = depth_size(depth), px = es * cn;
+    std::vector<AugGeom> geom(njobs);
+    long long ntiles = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const pbd_augment &a = jobs[i];
+        if (a.frame < 0 || a.frame >= nframes) return fail(h, PBD_ERR_INVALID, "job %d: frame %d outside 0..%d", i, a.frame, nframes - 1);
+        if (!std::isfinite(a.degrees)) return fail(h, PBD_ERR_INVALID, "job %d: degrees is not finite", i);
+        const pbd_frame &src = frames[a.frame], &o = out[i];
+        if (!augment_geom(src.rows, src.cols, a.degrees, &geom[i])) return fail(h, PBD_ERR_INVALID, "job %d: no plan", i);
+        if (!o.data) return fail(h, PBD_ERR_INVALID, "job %d: the destination is a null pointer", i);
+        if (o.rows != geom[i].orows || o.cols != geom[i].ocols)
+            return fail(h, PBD_ERR_INVALID, "job %d: destination %dx%d, the plan says %dx%d", i, o.rows, o.cols, geom[i].orows, geom[i].ocols);
+        if (o.stride_bytes < (size_t)o.cols * px)
+            return fail(h, PBD_ERR_INVALID, "job %d: destination stride %zu < row bytes %zu", i, o.stride_bytes, (size_t)o.cols * px);
+        if (!host && (reinterpret_cast<uintptr_t>(o.data) % es || o.stride_bytes % es))
+            return fail(h, PBD_ERR_INVALID, "job %d: destination pointer %p / stride %zu not a multiple of the %zu-byte element", i, o.data,
+                        o.stride_bytes, es);
+        const auto d = frame_span(o, px);
+        for (int f = 0; f < nframes; ++f) {
+            const auto s = frame_span(frames[f], px);
+            if (d.first < s.second && s.first < d.second) return fail(h, PBD_ERR_INVALID, "job %d: the destination overlaps frame %d", i, f);
+        }
+        ntiles += (long long)((o.rows + kAugTileRows - 1) / kAugTileRows) * ((o.cols + kAugTileCols - 1) / kAugTileCols);
+    }
+    if (ntiles > (1LL << 26)) return fail(h, PBD_ERR_INVALID, "%lld tiles in one call (at most 2^26)", ntiles);
+    if (njobs == 0) return PBD_OK;
+
+    // host form: the frames that have a job and every destination packed into the call's own buffer
+    std::vector<const uint8_t *> d_src(nframes, nullptr);
+    std::vector<long long> spitch(nframes, 0);
+    std::vector<uint8_t *> d_dst(njobs, nullptr);
+    if (host) {
+        std::vector<char> used(nframes, 0);
+        for (int i = 0; i < njobs; ++i) used[jobs[i].frame] = 1;
+        size_t off = 0;
+        std::vector<size_t> so(nframes, 0), dofs(njobs, 0);
+        for (int f = 0; f < nframes; ++f)
+            if (used[f]) { off = Carve::up(off, 256); so[f] = off; off += (size_t)frames[f].rows * frames[f].cols * px; }
+        for (int i = 0; i < njobs; ++i) { off = Carve::up(off, 256); dofs[i] = off; off += (size_t)out[i].rows * out[i].cols * px; }
+        HIPCHK(h, h->aug_buf.ensure(off + 16));
+        uint8_t *base = h->aug_buf.as<uint8_t>();
+        for (int f = 0; f < nframes; ++f) {
+            if (!used[f]) continue;
+            const size_t rb = (size_t)frames[f].cols * px;
+            HIPCHK(h, hipMemcpy2DAsync(base + so[f], rb, frames[f].data, frames[f].stride_bytes, rb, frames[f].rows, hipMemcpyHostToDevice,
+                                       h->stream));
+            d_src[f] = base + so[f];
+            spitch[f] = (long long)rb;
+        }
+        for (int i = 0; i < njobs; ++i) d_dst[i] = base + dofs[i];
+    } else {
+        for (int f = 0; f < nframes; ++f) { d_src[f] = static_cast<const uint8_t *>(frames[f].data); spitch[f] = (long long)frames[f].stride_bytes; }
+        for (int i = 0; i < njobs; ++i) d_dst[i] = static_cast<uint8_t *>(const_cast<void *>(out[i].data));
+    }
+
+    // one staged block: the job table, then the tile table over every destination
+    const size_t o_tiles = Carve::up((size_t)njobs * sizeof(AugJob), 256);
+    std::vector<uint8_t> blob(o_tiles + (size_t)ntiles * sizeof(AugTile), 0);
+    AugJob *J = reinterpret_cast<AugJob *>(blob.data());
+    AugTile *T = reinterpret_cast<AugTile *>(blob.data() + o_tiles);
+    long long nt = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const AugGeom &g = geom[i];
+        const int f = jobs[i].frame;
+        J[i] = AugJob{d_src[f], d_dst[i], spitch[f], host ? (long long)((size_t)out[i].cols * px) : (long long)out[i].stride_bytes,
+                      frames[f].rows, frames[f].cols, g.orows, g.ocols, jobs[i].mirror ? 1 : 0, g.rotate, g.c, g.s, g.hAr, g.hAc, g.hBr,
+                      g.hBc};
+        for (int y = 0; y < g.orows; y += kAugTileRows)
+            for (int x = 0; x < g.ocols; x += kAugTileCols) T[nt++] = AugTile{i, y, x};
+    }
+    if (int rc = h->aug_tab.stage(h, blob.data(), blob.size())) return rc;
+    AugParams ap{};
+    ap.jobs = h->aug_tab.as<AugJob>();
+    ap.tiles = reinterpret_cast<const AugTile *>(h->aug_tab.as<uint8_t>() + o_tiles);
+    ap.ntiles = (int)ntiles; ap.cn = cn; ap.depth = depth;
+    launch_augment(ap, h->stream);   // (no id in the handle's profile: the probe times the call with events on pbd_stream())
+    HIPCHK(h, hipGetLastError());
+    if (!host) return PBD_OK;
+    for (int i = 0; i < njobs; ++i) {   // the used width of every row only: bytes beyond it are the caller's
+        const size_t rb = (size_t)out[i].cols * px;
+        HIPCHK(h, hipMemcpy2DAsync(const_cast<void *>(out[i].data), out[i].stride_bytes, d_dst[i], rb, rb, out[i].rows, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PBD_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
 extern "C" {
+
+// Augmented positives: the plan and the points on the host, the frames on the device.  See include/pbd.h.
+int pbd_augment_plan(int rows, int cols, double degrees, int *out_rows, int *out_cols, double coef[2])
+{
+    return guarded(nullptr, [&]() -> int {
+        AugGeom g;
+        if (!out_rows || !out_cols || !coef) return fail(nullptr, PBD_ERR_INVALID, "pbd_augment_plan: a null output");
+        if (!augment_geom(rows, cols, degrees, &g))
+            return fail(nullptr, PBD_ERR_INVALID, "pbd_augment_plan: %dx%d (1..%d) by %g degrees (finite)", rows, cols, kAugMaxSide, degrees);
+        *out_rows = g.orows; *out_cols = g.ocols; coef[0] = g.c; coef[1] = g.s;
+        return PBD_OK;
+    });
+}
+
+int pbd_augment_points(int rows, int cols, double degrees, int mirror, int npoints, const double *xy, double *xy_out)
+{
+    return guarded(nullptr, [&]() -> int {
+        AugGeom g;
+        if (npoints < 0 || (npoints > 0 && (!xy || !xy_out))) return fail(nullptr, PBD_ERR_INVALID, "pbd_augment_points: npoints %d", npoints);
+        if (!augment_geom(rows, cols, degrees, &g))
+            return fail(nullptr, PBD_ERR_INVALID, "pbd_augment_points: %dx%d (1..%d) by %g degrees (finite)", rows, cols, kAugMaxSide, degrees);
+        for (int i = 0; i < npoints; ++i) {
+            double x = xy[2 * i], y = xy[2 * i + 1];
+            if (mirror) x = ((double)cols - 1) - x;
+            if (g.rotate) {   // map_rotate_points.m:40: tformfwd(p + loA, rotate) - loB with p = [y x]
+                const double u = y - g.hAr, v = x - g.hAc;
+                y = (u * g.c - v * g.s) + g.hBr;
+                x = (u * g.s + v * g.c) + g.hBc;
+            }
+            xy_out[2 * i] = x; xy_out[2 * i + 1] = y;
+        }
+        return PBD_OK;
+    });
+}
+
+int pbd_augment_frames(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int njobs,
+                       const pbd_augment *jobs, const pbd_frame *out)
+{
+    return entry(h, njobs <= 0 || (frames && jobs && out), kIdle, [&]() -> int {
+        return augment_frames(h, nframes, frames, channels, depth_code, njobs, jobs, out, true);
+    });
+}
+
+int pbd_augment_frames_device(pbd_handle *h, int nframes, const pbd_frame *d_frames, int channels, int depth_code, int njobs,
+                              const pbd_augment *jobs, const pbd_frame *d_out)
+{
+    return entry(h, njobs <= 0 || (d_frames && jobs && d_out), kIdle, [&]() -> int {
+        return augment_frames(h, nframes, d_frames, channels, depth_code, njobs, jobs, d_out, false);
+    });
+}
 
 // Warped positives (matlab/learning/train.m poswarp, warppos.m, qp_poswrite).  See include/pbd.h.
 int pbd_warp_positives(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, int nboxes,
@@ -447,8 +628,9 @@ int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset
 }
 
 // Latent positives (matlab/detection/detect.m with a bbox: testoverlap masks, bbox.m fixed mixtures).  See include/pbd.h.
-int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
-                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
+// Both forms: `host` says where enqueue_detect_mixed reads the frames (host pointers, or device pointers read in place).
+static int detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
+                         const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found, bool host)
 {
     return entry(h, frames && boxes && cand && found, kIdle, [&]() -> int {
         if (h->shard_world > 1)
@@ -500,7 +682,7 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
         }
         pbd_handle *t = h->lat.get();
         Plan *P = nullptr;
-        if (int rc = check_frames_mixed(t, nframes, frames, channels, depth_code, true, &P)) return fail(h, rc, "%s", t->err.c_str());
+        if (int rc = check_frames_mixed(t, nframes, frames, channels, depth_code, host, &P)) return fail(h, rc, "%s", t->err.c_str());
         const size_t nb = (size_t)nframes * nparts;
         HIPCHK(h, h->lat_in.ensure(nb * sizeof(int4) + nb * sizeof(int) + 64));
         HIPCHK(h, hipMemcpyAsync(h->lat_in.p, boxes, nb * sizeof(int4), hipMemcpyHostToDevice, h->stream));
@@ -514,7 +696,7 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
         LatentParams lp{};
         lp.gmtab = h->lat_gm.p; lp.boxes = h->lat_in.as<int4>(); lp.mix = mixtures ? d_mix : nullptr; lp.nparts = nparts;
         lp.overlap = (double)overlap;
-        if (int rc = enqueue_detect_mixed(t, *P, nframes, frames, channels, depth_code, true, &lp)) return fail(h, rc, "%s", t->err.c_str());
+        if (int rc = enqueue_detect_mixed(t, *P, nframes, frames, channels, depth_code, host, &lp)) return fail(h, rc, "%s", t->err.c_str());
         lp.rootv = t->rootv.p; lp.rooti = t->rooti.as<int>(); lp.lv = P->d_lv.p; lp.nlevels = P->nlevels;
         lp.cell_per_frame = P->cell_per_frame; lp.frame_lv0 = P->d_frame_lv0.p; lp.nframes = nframes; lp.NC = h->NC;
         lp.stride = stride; lp.payload = h->lat_pay.as<int32_t>();
@@ -530,6 +712,18 @@ int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int c
         }
         return PBD_OK;
     });
+}
+
+int pbd_detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, int channels, int depth_code, const int32_t *boxes,
+                      const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
+{
+    return detect_latent(h, nframes, frames, channels, depth_code, boxes, mixtures, overlap, cand, found, true);
+}
+
+int pbd_detect_latent_device(pbd_handle *h, int nframes, const pbd_frame *d_frames, int channels, int depth_code, const int32_t *boxes,
+                             const int32_t *mixtures, float overlap, int32_t *cand, int32_t *found)
+{
+    return detect_latent(h, nframes, d_frames, channels, depth_code, boxes, mixtures, overlap, cand, found, false);
 }
 
 int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values)

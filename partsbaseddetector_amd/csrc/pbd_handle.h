@@ -482,6 +482,10 @@ struct Handle : ErrCtx {
     std::unique_ptr<Plan> wp_plan;
     StagedTable wp_tab;
     DevBuf wp_out;
+    // pbd_augment_frames*: the call's job and tile tables (one staged block); the host form's packed sources and destinations.
+    // Buffers of their own: the call leaves the detect path's buffers and the resident result alone
+    StagedTable aug_tab;
+    DevBuf aug_buf;
 
     // A candidate list on its way out.  The device side is the "payload" the find / walk kernels write: word 0 = roots
     // found, then the records, already in (frame, level, component, y, x) order.  The host side is a pinned mirror: the

@@ -794,6 +794,25 @@ struct WarpParams {
 void launch_warp(const WarpParams &p, hipStream_t s);
 void launch_warp_emit(const WarpParams &p, bool f64, hipStream_t s);
 
+// augmented positives (pbd_augment_frames*; pbd_kernels_augment.hip).  A job is one destination image:
+// rotate(mirror(source)), nearest neighbour.  A tile is kAugTileCols consecutive pixels of kAugTileRows consecutive destination
+// rows of one job; the tile table runs over every job of the call.
+constexpr int kAugTileCols = 256, kAugTileRows = 8;
+struct AugJob {
+    const uint8_t *src; uint8_t *dst;
+    long long spitch, dpitch;     // bytes between rows
+    int srows, scols, drows, dcols;
+    int mirror, rotate;           // rotate 0: degrees == 0, the destination has the source's size and no coordinate is computed
+    double c, s, hAr, hAc, hBr, hBc;
+};
+struct AugTile { int job, y0, x0; };
+struct AugParams {
+    const AugJob *jobs;
+    const AugTile *tiles;
+    int ntiles, cn, depth;
+};
+void launch_augment(const AugParams &p, hipStream_t s);
+
 // the training QP (pbd_qp_*; pbd_kernels_qp.hip).  One cache entry i: x[i * V ..] float values in stored block order, bm[i * V ..]
 // the block of every value, hd[i * HW ..] = {nblocks, nvalues, (offset in w, length, first value) x nblocks}, ids[i * 5 ..],
 // b, d, a (double) and sv (uint8).  Every kernel runs PBD_QP_LANES threads per workgroup (the lanes of the header's reduction).

@@ -219,6 +219,34 @@ def _resize_linear_400(S: np.ndarray) -> np.ndarray:
         return S[r0] * (np.float32(1) - fy) + S[r1] * fy
 
 
+def is_device_frame(f) -> bool:
+    """a torch tensor on a GPU (anything else is taken as a host array)"""
+    return hasattr(f, "data_ptr") and hasattr(f, "is_cuda") and bool(f.is_cuda)
+
+
+def frame_dtype(f) -> np.dtype:
+    """the numpy dtype of a host array or a torch tensor"""
+    return np.dtype(str(f.dtype).replace("torch.", ""))
+
+
+def device_frames(tensors):
+    """(descriptors (pointer, rows, cols, pitch), channels, depth code) of torch tensors on the device, rows x cols [x cn] with
+    contiguous pixels: a view of a larger image is described in place, nothing is copied"""
+    if not tensors:
+        raise PbdError(-1, "no frames")
+    dt, cn = frame_dtype(tensors[0]), 1 if tensors[0].ndim == 2 else int(tensors[0].shape[2])
+    if dt not in _lib.DEPTH_CODE:
+        raise PbdError(-1, "frames are uint8, uint16, float32 or float64")
+    descs = []
+    for t in tensors:
+        if not is_device_frame(t) or t.ndim not in (2, 3) or frame_dtype(t) != dt or (1 if t.ndim == 2 else int(t.shape[2])) != cn:
+            raise PbdError(-1, "one call takes device tensors of one dtype and one channel count")
+        if (t.shape[1] > 1 and t.stride(1) != cn) or (t.ndim == 3 and cn > 1 and t.stride(2) != 1):
+            raise PbdError(-1, "a device frame must have contiguous pixels")
+        descs.append((t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(t.stride(0)) * t.element_size()))
+    return descs, cn, _lib.DEPTH_CODE[dt]
+
+
 class Handle:
     """Owns a pbd_handle (one handle = one host thread = one GPU)."""
 
@@ -509,6 +537,53 @@ class Handle:
                                               None if mix is None else mix.ctypes.data, float(overlap), rec.ctypes.data,
                                               found.ctypes.data))
         return rec, found
+
+    def detect_latent_device(self, descs, cn: int, depth_code: int, part_boxes, overlap: float, mixtures=None):
+        """pbd_detect_latent_device: detect_latent on frames already on the device as (pointer, rows, cols, pitch), regions of
+        larger images included; the boxes, the mixtures and the result are host arrays and the call is synchronous"""
+        boxes = np.ascontiguousarray(part_boxes, np.int32).reshape(len(descs), -1, 4)
+        mix = None if mixtures is None else np.ascontiguousarray(mixtures, np.int32).reshape(len(descs), boxes.shape[1])
+        rec = np.zeros((len(descs), self.stride), np.int32)
+        found = np.zeros(len(descs), np.int32)
+        self.check(self.lib.pbd_detect_latent_device(self.h, len(descs), _lib.frame_array(descs), cn, depth_code, boxes.ctypes.data,
+                                                     None if mix is None else mix.ctypes.data, float(overlap), rec.ctypes.data,
+                                                     found.ctypes.data))
+        return rec, found
+
+    def augment_plan(self, rows: int, cols: int, degrees: float):
+        """pbd_augment_plan: (out_rows, out_cols, (c, s)) of a rows x cols frame turned by `degrees`"""
+        r, c, coef = C.c_int(), C.c_int(), (C.c_double * 2)()
+        rc = self.lib.pbd_augment_plan(int(rows), int(cols), float(degrees), C.byref(r), C.byref(c), coef)
+        if rc != _lib.PBD_OK:
+            raise PbdError(rc, self.lib.pbd_last_error(None).decode())
+        return r.value, c.value, (coef[0], coef[1])
+
+    def augment_frames(self, frames, jobs, outs=None):
+        """pbd_augment_frames: the copies rotate(mirror(frames[f])) of jobs (n, 3) = (frame, mirror, degrees) as host arrays;
+        frames are arrays of one dtype and channel count, any sizes.  outs: destinations to write into (views with padded rows
+        allowed), else new arrays."""
+        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
+        if fr and (any(f.dtype != fr[0].dtype or f.shape[2] != fr[0].shape[2] for f in fr) or fr[0].dtype not in _lib.DEPTH_CODE):
+            raise PbdError(-1, "one dtype (uint8, uint16, float32 or float64) and one channel count per call")
+        jobs = [(int(f), bool(m), float(d)) for f, m, d in jobs]
+        if outs is None:
+            outs = []
+            for f, _, d in jobs:
+                if not 0 <= f < len(fr):
+                    raise PbdError(-1, f"frame {f} outside 0..{len(fr) - 1}")
+                r, c, _ = self.augment_plan(fr[f].shape[0], fr[f].shape[1], d)
+                outs.append(np.zeros((r, c, fr[f].shape[2]), fr[f].dtype))
+        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        odesc = _lib.frame_array([(o.ctypes.data, o.shape[0], o.shape[1], o.strides[0]) for o in outs])
+        self.check(self.lib.pbd_augment_frames(self.h, len(fr), descs, fr[0].shape[2] if fr else 3,
+                                               _lib.DEPTH_CODE[fr[0].dtype] if fr else 0, len(jobs), _lib.augment_array(jobs), odesc))
+        return outs
+
+    def augment_frames_device(self, descs, cn: int, depth_code: int, jobs, out_descs) -> None:
+        """pbd_augment_frames_device: frames and destinations as (device pointer, rows, cols, pitch); asynchronous on the
+        handle's stream"""
+        self.check(self.lib.pbd_augment_frames_device(self.h, len(descs), _lib.frame_array(descs), cn, depth_code, len(jobs),
+                                                      _lib.augment_array(jobs), _lib.frame_array(out_descs)))
 
     def examples_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
         """pbd_examples_device: the examples of a device payload's records into int32[capacity * hdr_words] and
@@ -1517,10 +1592,45 @@ class PartsBasedDetector:
         mixtures[f][p] >= 0 fixed.  Returns (candidates, found): one Candidate per frame, found[f] = False when no placement
         passes (its candidate then scores below -5e9).  examples(candidates) afterwards gives the positives' feature vectors."""
         self._need()
-        if isinstance(frames, np.ndarray) and frames.ndim in (2, 3) and (frames.ndim == 2 or frames.shape[2] in (1, 3)):
+        if (isinstance(frames, np.ndarray) or is_device_frame(frames)) and frames.ndim in (2, 3) and \
+                (frames.ndim == 2 or frames.shape[2] in (1, 3)):
             frames = [frames]
-        rec, found = self.hd.detect_latent(list(frames), part_boxes, overlap, mixtures)
+        frames = list(frames)
+        if frames and is_device_frame(frames[0]):   # torch tensors on the device, views of larger images included: read in place
+            import torch
+            descs, cn, code = device_frames(frames)
+            torch.cuda.synchronize(frames[0].device)
+            rec, found = self.hd.detect_latent_device(descs, cn, code, part_boxes, overlap, mixtures)
+        else:
+            rec, found = self.hd.detect_latent(frames, part_boxes, overlap, mixtures)
         return self.hd.unpack_candidates(rec.ravel(), len(rec)), found.astype(bool)
+
+    def augmentFrames(self, frames, jobs):
+        """rotated and mirrored copies on the device (pbd_augment_frames_device; the rule is
+        augment.rotate_ref): jobs = [(frame, mirror, degrees)], copy i = rotate(mirror(frames[frame])), all in one launch.
+        frames: numpy arrays (uploaded once) or torch tensors on the detector's device, one dtype and channel count, any sizes.
+        Returns one torch tensor per job on the device, rows x cols x channels (rows x cols for 2-D frames), ready for
+        detectLatent, train() and trainmodel()."""
+        import torch
+        self._need()
+        frames = list(frames)
+        dev = torch.device("cuda", self._kw["device"])
+        d_fr = [f if is_device_frame(f) else torch.from_numpy(np.array(f)).to(dev) for f in frames]   # np.array: writable, contiguous
+        jobs = [(int(f), bool(m), float(d)) for f, m, d in jobs]
+        if not jobs:
+            return []
+        descs, cn, code = device_frames(d_fr)
+        outs = []
+        for f, _, d in jobs:
+            if not 0 <= f < len(d_fr):
+                raise PbdError(-1, f"frame {f} outside 0..{len(d_fr) - 1}")
+            r, c, _ = self.hd.augment_plan(d_fr[f].shape[0], d_fr[f].shape[1], d)
+            outs.append(torch.empty((r, c) + tuple(d_fr[f].shape[2:]), dtype=d_fr[f].dtype, device=dev))
+        odesc = [(o.data_ptr(), o.shape[0], o.shape[1], o.stride(0) * o.element_size()) for o in outs]
+        torch.cuda.synchronize(dev)
+        self.hd.augment_frames_device(descs, cn, code, jobs, odesc)
+        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
+        return outs
 
     def warpPositives(self, frames, boxes, filter: int = 0, bias: int = 0, skip_small: bool = True):
         """warped positives (matlab/learning/train.m poswarp with warppos.m and qp_poswrite) on the device (pbd_warp_positives):
@@ -1528,7 +1638,7 @@ class PartsBasedDetector:
         replication, resized to (k + 2) * sbin pixels with the detector's own resampler, and its HOG written as the example
         [bias = 1 | filter block] of filter `filter` (bias -1: the filter block alone).  Returns (hdr (n, hdr_words) int32, values
         (n, values) T, kept (n,) bool); with skip_small a box smaller than the filter's pixels is skipped (hdr[2] = -1).  The
-        examples go to QP.add as they are.  No flipping: that stays with the caller (the loop over these calls is train.train)."""
+        examples go to QP.add as they are.  Mirrored and rotated copies are augmentFrames' (the loop over these calls is train.train)."""
         self._need()
         if isinstance(frames, np.ndarray) and frames.ndim in (2, 3) and (frames.ndim == 2 or frames.shape[2] in (1, 3)):
             frames = [frames]

@@ -112,8 +112,26 @@ def threshold_of(scores) -> float:
     return float(np.float32(r[int(math.ceil(THRESH_QUANTILE * len(r))) - 1]))
 
 
-def _frame(im: np.ndarray) -> np.ndarray:
+def _frame(im):
+    """rows x cols x channels of a host array or a device tensor (a view)"""
     return im if im.ndim == 3 else im[:, :, None]
+
+
+def _is_device(im) -> bool:
+    return hasattr(im, "data_ptr") and bool(getattr(im, "is_cuda", False))
+
+
+def positives_on_device(pos) -> bool:
+    """whether the positives' images are device tensors (all of them, or none)"""
+    dev = [_is_device(p["im"]) for p in pos]
+    if any(dev) and not all(dev):
+        raise ValueError("the positives' images are all host arrays or all device tensors")
+    return bool(dev) and dev[0]
+
+
+def host_positives(pos):
+    """the positives with every device tensor copied to a host array (the yardsticks work on host copies)"""
+    return [dict(p, im=p["im"].cpu().numpy()) if _is_device(p["im"]) else p for p in pos]
 
 
 def _new_iteration() -> dict:
@@ -142,6 +160,13 @@ def _detect_latent(hd, crops, boxes, overlap, mixtures):
     return rec, found
 
 
+def _detect_latent_device(hd, crops, boxes, overlap, mixtures):
+    """pbd_detect_latent_device on crops that are views of device tensors: regions read in place, nothing is copied or uploaded"""
+    from .detector import device_frames
+    descs, cn, code = device_frames(crops)
+    return hd.detect_latent_device(descs, cn, code, boxes, overlap, mixtures)
+
+
 def _mixtures(pos, idx, nparts):
     if not any(pos[i].get("mix") is not None for i in idx):
         return None
@@ -151,7 +176,8 @@ def _mixtures(pos, idx, nparts):
 def train(model, pos, neg, warp, iters: int = 1, C: float = 0.002, wpos: float = 2, capacity: Optional[int] = None,
           overlap: float = 0.6, neg_interval: int = 2, neg_batch: int = 1, tol: float = 0.05, max_passes: int = 1000, seed: int = 0,
           dtype=np.float32, device: int = 0, conv_mode: int = _lib.CONV_EXACT):
-    """train.m on the device: (the trained Model, info).  pos: [{"im": ndarray, "boxes": (nparts, 4) int, 0-based inclusive,
+    """train.m on the device: (the trained Model, info).  pos: [{"im": ndarray or a torch tensor on the device (an augmented
+    copy: its crops are read in place, nothing is uploaded again), "boxes": (nparts, 4) int, 0-based inclusive,
     "mix": optional (nparts,)}]; neg: frames of any sizes; warp: 1 for a one-part model (warped positives), 0 for latent
     positives.  capacity None: train.m's nmax, capped by the device's free memory.  info: per iteration ("iterations") and, at
     top level, of the last one: numpositives per component, skipped / notfound positives, per negative batch {first, found,
@@ -167,6 +193,8 @@ def train(model, pos, neg, warp, iters: int = 1, C: float = 0.002, wpos: float =
         raise ValueError("positives and negatives are needed")
     kmax, sbin = int(np.max(flat.filter_ksize)), int(flat.sbin)
     hw, vw = E.strides(flat)
+    if positives_on_device(pos):
+        torch.cuda.synchronize(pos[0]["im"].device)   # whatever made the tensors has finished before this call's stream reads them
     with torch.cuda.device(device):
         stream = torch.cuda.Stream()
         with torch.cuda.stream(stream):
@@ -202,7 +230,9 @@ def _train_device(torch, det, negdet, q, flat, pos, neg, warp, iters, capacity, 
     vals = torch.zeros(capacity * vw, dtype=tdt, device="cuda")
     up = lambda im: torch.from_numpy(np.ascontiguousarray(_frame(im))).cuda()
     d_neg = [up(im) for im in neg]
-    desc = lambda t: (t.data_ptr(), t.shape[0], t.shape[1], t.shape[1] * t.shape[2] * t.element_size())
+    desc = lambda t: (t.data_ptr(), t.shape[0], t.shape[1], t.stride(0) * t.element_size())
+    on_device = positives_on_device(pos)
+    pos_code = _lib.DEPTH_CODE[np.dtype(str(pos[0]["im"].dtype).replace("torch.", ""))]
     calls = 0
 
     def next_seed():
@@ -220,13 +250,13 @@ def _train_device(torch, det, negdet, q, flat, pos, neg, warp, iters, capacity, 
         q.clear()
         # -- positives
         if warp:
-            d_pos = [up(p["im"]) for p in pos]
+            d_pos = [_frame(p["im"]) if on_device else up(p["im"]) for p in pos]
             boxes = np.array([[i, *part_boxes(p)[0]] for i, p in enumerate(pos)], np.int32)
             if len(boxes) > capacity:
                 raise ValueError("more positives than the cache holds")
             gm = int(flat.mix_offset[0])
-            det.warpPositives_device([desc(t) for t in d_pos], d_pos[0].shape[2], _lib.DEPTH_CODE[np.dtype(_frame(pos[0]["im"]).dtype)],
-                                     boxes, int(flat.filterid[gm]), int(flat.biasid[gm]), True, 0, pay.data_ptr(), len(boxes),
+            det.warpPositives_device([desc(t) for t in d_pos], d_pos[0].shape[2], pos_code, boxes, int(flat.filterid[gm]),
+                                     int(flat.biasid[gm]), True, 0, pay.data_ptr(), len(boxes),
                                      hdr.data_ptr(), vals.data_ptr())
             q.add_device(det.hd, pay.data_ptr(), len(boxes), hdr.data_ptr(), vals.data_ptr(), 1, 0)
             k = int(flat.filter_ksize[flat.filterid[gm]])
@@ -237,7 +267,8 @@ def _train_device(torch, det, negdet, q, flat, pos, neg, warp, iters, capacity, 
             it["skipped"], batches = positive_batches(pos, kmax, sbin, min(max_batch, capacity))
             for idx in batches:
                 cb = [croppos(_frame(pos[i]["im"]), part_boxes(pos[i])) for i in idx]
-                rec, found = _detect_latent(det.hd, [c for c, _ in cb], [b for _, b in cb], overlap, _mixtures(pos, idx, nparts))
+                rec, found = (_detect_latent_device if on_device else _detect_latent)(det.hd, [c for c, _ in cb], [b for _, b in cb],
+                                                                                      overlap, _mixtures(pos, idx, nparts))
                 keep = np.nonzero(found)[0]
                 it["notfound"] += [idx[f] for f in range(len(idx)) if not found[f]]
                 if len(keep) == 0:
@@ -308,6 +339,7 @@ def train_ref(model, pos, neg, warp, iters: int = 1, C: float = 0.002, wpos: flo
     and warp.warp_examples for the positives, examples_of_records(walk="argmax"), QPRef and Model.from_vector.  The same
     (Model, info); capacity None: train.m's nmax without the device's cap."""
     from oracle import oracle
+    pos = host_positives(pos)
     flat = model.flatten()
     nparts = int(flat.part_offset[1] - flat.part_offset[0])
     if warp and (flat.ncomponents != 1 or nparts != 1):

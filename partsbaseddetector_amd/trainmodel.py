@@ -300,7 +300,25 @@ def check_types(idx, K) -> None:
 _DEVICE_ONLY = ("device", "conv_mode")
 
 
-def _pipeline(on_device: bool, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw):
+def augmented(on_device: bool, pos, pa, augment, device: int = 0):
+    """the positives multiplied by `augment` = {"degrees": (...), "mirror": perm or None} (augment.py), on
+    the device or in numpy, and info["augment"]: the copies per positive and the total"""
+    from . import augment as A
+    unknown = set(augment) - {"degrees", "mirror"}
+    if unknown:
+        raise ValueError(f"augment has no key {sorted(unknown)[0]!r}")
+    degrees, mirror = tuple(augment.get("degrees", ())), augment.get("mirror")
+    if mirror is not None:
+        mirror = A.check_mirror(mirror, pa)
+    for p in pos:
+        if p.get("points") is None:
+            raise ValueError("augmentation maps a positive's points: every positive needs \"points\"")
+    out = A.augment_positives(pos, degrees, mirror, device) if on_device else A.augment_positives_ref(pos, degrees, mirror)
+    return out, {"degrees": [float(d) for d in degrees], "mirror": None if mirror is None else [int(v) for v in mirror],
+                 "copies": len(A.copies(degrees, mirror)), "total": len(out)}
+
+
+def _pipeline(on_device: bool, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw, augment=None):
     from . import train as T
     if on_device:
         train_fn, kw = T.train, dict(train_kw)
@@ -311,11 +329,18 @@ def _pipeline(on_device: bool, pos, neg, K, pa, sbin, tsize, trials, seed, idx, 
     parent = parent_of(pa)
     if len(K) != len(parent):
         raise ValueError("K and pa differ in length")
+    aug_info = None
+    if augment is not None:
+        pos, aug_info = augmented(on_device, pos, pa, augment, train_kw.get("device", 0))
+    elif not on_device:
+        pos = T.host_positives(pos)
     pos = with_boxes(pos, pa)
     init = initmodel(pos, sbin, tsize)
     ksize = int(init.filtersw[0].shape[0])
     deff = data_def(pos, ksize)
     info = {"def": deff, "cluster": None}
+    if aug_info is not None:
+        info["augment"] = aug_info
     # 1. the part types
     if idx is None:
         if on_device:
@@ -362,19 +387,25 @@ def _pipeline(on_device: bool, pos, neg, K, pa, sbin, tsize, trials, seed, idx, 
 
 
 def trainmodel(pos, neg, K, pa, sbin, tsize: Optional[int] = None, trials: int = 100, seed: int = 0, idx=None, part_models=None,
-               cluster_max_iter: int = 1000, **train_kw):
-    """trainmodel.m on the device: (the trained Model, info).  pos: [{"im": ndarray, "points": (nparts, 2) pixel coordinates,
+               cluster_max_iter: int = 1000, augment: Optional[dict] = None, **train_kw):
+    """trainmodel.m on the device: (the trained Model, info).  pos: [{"im": ndarray or device tensor, "points": (nparts, 2) pixel coordinates,
     "boxes": optional (nparts, 4) int, 0-based inclusive (absent: point_to_box, rounded)}]; neg: frames; K: types per part; pa:
     Matlab's parent table (1-based, 0 for the root); sbin: the HOG cell; tsize: the filter side (None: initmodel's).  idx
     (nparts, npos) and part_models (one merged Model per part) skip a finished stage, in place of the Matlab file cache.  A
     type with no positive, or with none of at least a filter's pixels, raises ValueError.  seed: the clustering's and every
     train()'s.  train_kw: train()'s other keywords, the same for every call.  info: def, idx, centres, anchors, cluster
     (Handle.cluster_parts' dict, None with idx=), part_models, part_info ([part][type] train() infos, None with part_models=),
-    built (buildmodel's model), model1 and final1 (the fixed-type pass), final (the free pass)."""
-    return _pipeline(True, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw)
+    built (buildmodel's model), model1 and final1 (the fixed-type pass), final (the free pass).
+    augment = {"degrees": (...), "mirror": perm or None}: every positive is first multiplied on the device into its copies
+    mirror in (no, yes if a permutation of the parts is given) x degrees in (0, *degrees) (augment.augment_positives, DESIGN.md
+    section 6r); the copies stay on the device, carry mapped points and no boxes (point_to_box makes them), and the unchanged
+    pipeline runs on the extended list (idx= then has one column per copy).  info["augment"] = {degrees, mirror, copies (per
+    positive), total}.  None: no augmentation, no such key."""
+    return _pipeline(True, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw, augment)
 
 
 def trainmodel_ref(pos, neg, K, pa, sbin, tsize: Optional[int] = None, trials: int = 100, seed: int = 0, idx=None, part_models=None,
-                   cluster_max_iter: int = 1000, **train_kw):
-    """trainmodel() in numpy: cluster_parts_ref and train_ref (device and conv_mode keywords are ignored)"""
-    return _pipeline(False, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw)
+                   cluster_max_iter: int = 1000, augment: Optional[dict] = None, **train_kw):
+    """trainmodel() in numpy: augment_positives_ref, cluster_parts_ref and train_ref on host copies (device and conv_mode
+    keywords are ignored)"""
+    return _pipeline(False, pos, neg, K, pa, sbin, tsize, trials, seed, idx, part_models, cluster_max_iter, train_kw, augment)
