@@ -6,6 +6,7 @@
 //   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
+//            [--part-scores]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
 //   --root-nms SZ: only the roots that are grid maxima of their score plane within SZ cells are walked and listed
@@ -36,6 +37,9 @@
 //           every submitted frame carries the map; not with --staged
 //   --poses: with --camera, one line per listed candidate after its "object" line: "pose COUNT x y z qx qy qz qw" (messagePoses
 //           on the part centres, on the device; COUNT 0 is the node's "Centroid not found")
+//   --part-scores: after the candidate lines, one line per listed candidate and part, "part_score CANDIDATE PART x y m appearance
+//           message bias total" (pbd_part_scores, DESIGN.md section 6s: the part's cell and mixture in its level's map and the
+//           four values, floats as %a so that every bit shows); not with --staged, --stream or --also
 //   --augment DEG[,mirror] OUT.ppm: no detection; the image's augmented copy rotate(mirror(image)) -- turned counter-clockwise by
 //           DEG degrees, nearest neighbour, zero outside (pbd_augment_frames) -- written as a binary PPM
 //           (PGM for grey) and one line "augment ROWS COLS"
@@ -56,6 +60,7 @@ using namespace pbdhost;
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
 static int g_top_k = 0;                   // --top-k
+static bool g_part_scores = false;        // --part-scores
 static bool g_prune = false;              // --depth-prune fx,width,tol
 static float g_prune_fx = 0.f, g_prune_width = 0.f, g_prune_tol = 0.f;
 
@@ -252,6 +257,16 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
                         boxes[i].depth);
         if (camera) camera_lines(pbd, im, *depth, *camera, listed, remove_planes, poses);
     }
+    if (g_part_scores) {                 // the listed candidates' part scores; floats as %a: every bit
+        std::vector<Candidate> listed(candidates.begin(), candidates.begin() + std::min<size_t>(candidates.size(), (size_t)top));
+        std::vector<PartScore> scores;
+        pbd.partScores(listed, scores);
+        size_t j = 0;
+        for (size_t i = 0; i < listed.size(); ++i)
+            for (size_t p = 0; p < listed[i].confidence().size(); ++p, ++j)
+                std::printf("part_score %zu %zu %d %d %d %a %a %a %a\n", i, p, scores[j].x, scores[j].y, scores[j].m, scores[j].appearance,
+                            scores[j].message, scores[j].bias, scores[j].total);
+    }
     if (mask_path) {                     // Candidate::mask and the masked image of the listed candidates
         if (!pbd.handle()) pbd.distributeModel(model);
         const std::vector<Candidate> listed(candidates.begin(), candidates.begin() + std::min<size_t>(candidates.size(), (size_t)top));
@@ -323,7 +338,7 @@ static int run_augment(Model &model, const Image &im, double degrees, bool mirro
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--augment deg[,mirror] out.ppm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
     const char *augment_path = NULL;
@@ -343,6 +358,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--staged")) staged = true;
         else if (!std::strcmp(argv[i], "--remove-planes")) remove_planes = true;
         else if (!std::strcmp(argv[i], "--poses")) poses = true;
+        else if (!std::strcmp(argv[i], "--part-scores")) g_part_scores = true;
         else if (!std::strcmp(argv[i], "--mask") && i + 1 < argc) mask_path = argv[++i];
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked_path = argv[++i];
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
@@ -414,6 +430,10 @@ int main(int argc, char **argv)
     }
     if (g_top_k && staged) {
         std::fprintf(stderr, "--top-k is not applied by the staged run: not with --staged\n");
+        return -1;
+    }
+    if (g_part_scores && (staged || stream_k > 0 || !also.empty())) {
+        std::fprintf(stderr, "--part-scores reads the resident result of a single detect call: not with --staged, --stream or --also\n");
         return -1;
     }
     if (have_camera && !depth_path) {

@@ -122,7 +122,8 @@ typedef struct pbd_config {
 } pbd_config;
 
 /* One detection = one reference Candidate (include/Candidate.hpp:56-80): parts_ as x,y,w,h,
- * confidence_[0] = score (other confidences are 0: src/DynamicProgram.cpp:241-244), component_.
+ * confidence_[0] = score, component_.  The reference's walk leaves the other parts' confidences 0
+ * (src/DynamicProgram.cpp:241-244) and a record carries none; pbd_part_scores* compute them from the resident result.
  * A record is pbd_candidate_stride() int32 words: this header followed by max_parts x {x,y,w,h}. */
 typedef struct pbd_candidate_hdr {
     int32_t frame;      /* index within the batch */
@@ -831,6 +832,54 @@ int pbd_set_thresh(pbd_handle *h, float thresh);
 int pbd_example_stride(const pbd_handle *h, int *hdr_words, int *values);
 int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *hdr, void *values);
 int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_hdr, void *d_values);
+/* Part scores (new surface; opt-in): what the dynamic program added up for a record, per part, and the placement (cell and
+ * mixture of every part) it was added up at.  The reference's Candidate declares "bounding box and detection confidence for each
+ * part" (include/Candidate.hpp:54-72) and its walk fills only the root's; these calls give the rest.  DESIGN.md section 6s; the
+ * rule in numpy: partsbaseddetector_amd/partscores.py.
+ * A record (frame, component c, level l) and a placement (x_p, y_p, m_p), p = 0 .. nparts-1, of the resident result.  T is the
+ * handle's real type, gm(p) part p's global mixture index for m_p, f its filter id, d its deformation id:
+ *   appearance[p] = the resident response resp_l[f][y_p][x_p] of the call, whatever convolution mode produced it (fp16 resident
+ *                   responses, modes 3 and 6, widened to float)
+ *   bias[p]       = the root: biasw[biasid of the root's mixture 0] (src/DynamicProgram.cpp:163-170); a child:
+ *                   biasw[biasid[gm(p)] + m_parent]; float converted to T
+ *   total[p]      starts as appearance[p]; then for q = nparts-1 down to 1, in that order (the reference's descending child order):
+ *                   dx = x_parent + anchor_x[d] - x_q, dy likewise;
+ *                   r = Q(-w0, -w1, dx, total[q]), message[q] = Q(-w2, -w3, dy, r), where Q(a, b, d, y) = (T)(a * (double)(d * d)
+ *                   + b * (double)d + (double)y): the int square, double arithmetic left to right, ONE rounding to T per pass, as
+ *                   the transform's row and column passes round (include/DistanceTransform.hpp:102-104);
+ *                   total[parent] = total[parent] + (message[q] + bias[q]), both adds in T
+ *   message[0]    = total[0] + bias[0] in T
+ * Output per (record, part): T[4] = {appearance, message, bias, total}.  message[q] - total[q] is the deformation part q paid, to
+ * one rounding.
+ * Guarantees:
+ *  1. PBD_WALK_ARGMAX, a model in which no part that has children shares a filter id with another part of its component (every
+ *     model pbd_create is given by build_model / trainmodel()): for every record (float)message[0] has the bits of the record's
+ *     score, and total[p] is the value the dynamic program accumulated for part p at its cell.
+ *  2. PBD_WALK_REFERENCE: the values are those of the placement the record reports (the composed pointers may move a part off
+ *     the arg-max), and (float)message[0] is that placement's own score: at most the record's, below it where a part was moved.
+ *  3. Inner parts that share a filter id (the reference keys its accumulators by filter id, src/DynamicProgram.cpp:115-119,
+ *     154-156, so such a plane holds both parts' messages): the four values are still exactly the rule's; the equalities of (1)
+ *     are not promised.
+ * pbd_part_scores: host records, any subset in any order of the last completed detect call's (with or without pbd_set_nms,
+ * pbd_set_root_nms, pbd_set_depth_prune, pbd_set_top_k; pbd_detect_frames' and pbd_detect_latent's included: after the latter the
+ * responses are the masked ones of its one-filter-per-mixture run).  The placement is the walk's in the handle's walk mode
+ * (pbd_set_walk), as pbd_examples walks.  status = int32[ncand]: the record's parts; place = int32[ncand][max_parts][3] {x, y, m}
+ * (may be NULL); scores = T[ncand][max_parts][4].  Entries past a record's parts are not written.  Refusals are pbd_examples':
+ * PBD_ERR_INVALID naming the record, PBD_ERR_STATE without a resident result or while a batch is in flight.  Synchronous.
+ * pbd_part_scores_device: min(max(word 0, 0), capacity) records of the payload d_payload, so a -1 payload writes nothing; a
+ * record outside the resident result gets status -1 and nothing else.  Device arrays of `capacity` records (d_place may be NULL).
+ * Asynchronous on pbd_stream().
+ * pbd_score_placements / _device: the same values at placements the caller gives (place[i][0] is the root): frame, level and
+ * component are the record's, its root cell is ignored.  A placement with a cell outside the level's map or a mixture outside the
+ * part's range gets status -1 and no values; the other records of the call are not affected.
+ * No call changes the resident result. */
+int pbd_part_scores(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *status, int32_t *place, void *scores);
+int pbd_part_scores_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_status, int32_t *d_place,
+                           void *d_scores);
+int pbd_score_placements(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, const int32_t *place, int32_t *status,
+                         void *scores);
+int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, const int32_t *d_place,
+                                int32_t *d_status, void *d_scores);
 /* Warped positives (new surface; opt-in): poswarp of the reference's Matlab training code (matlab/learning/train.m:131-162 with
  * matlab/learning/warppos.m, subarray.m and qp_poswrite), the examples every training run starts from (trainmodel.m:19-40 trains
  * each part mixture as a one-part model on them).  DESIGN.md section 6k.  Each annotated box is padded by one cell, cropped with

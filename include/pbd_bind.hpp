@@ -457,6 +457,54 @@ inline void part_poses(pbd_handle *h, int n, const std::vector<float> &centres, 
     eigenvalues.resize(3 * un);
 }
 
+// One part of a record's part scores (pbd_part_scores / pbd_score_placements, include/pbd.h): its cell and mixture in the
+// level's map and the four values, held as double (exact for both real types)
+struct PartScore {
+    int x, y, m;
+    double appearance, message, bias, total;
+    PartScore() : x(0), y(0), m(0), appearance(0), message(0), bias(0), total(0) {}
+};
+
+// The part scores of n records of the last detect call in `rec`.  place NULL: pbd_part_scores, at the walk's placements;
+// else pbd_score_placements at (*place)[j].x / y / m, the records' parts one after another in record order, nparts[i] entries
+// for record i.  status[i] = the record's parts or -1; `out` receives the parts of every record with a status above 0, in
+// record order.
+template <class Tr>
+inline void part_scores(pbd_handle *h, const std::vector<int32_t> &rec, int n, const std::vector<int> &nparts,
+                        const std::vector<PartScore> *place, std::vector<int32_t> &status, std::vector<PartScore> &out)
+{
+    typedef typename Tr::Real Real;
+    const size_t mp = (size_t)(pbd_candidate_stride(h) - 8) / 4, un = n > 0 ? (size_t)n : 0;
+    std::vector<int32_t> pl(un * mp * 3 + 1, 0);
+    std::vector<Real> sc(un * mp * 4 + 1, Real(0));
+    status.assign(un + 1, 0);
+    if (place) {
+        size_t j = 0;
+        for (size_t i = 0; i < un; ++i) {
+            const size_t np = i < nparts.size() && nparts[i] > 0 ? (size_t)nparts[i] : 0;
+            if (np > mp || j + np > place->size()) Tr::fail(PBD_ERR_INVALID, "pbd: part_scores: one placement per part of every record");
+            for (size_t p = 0; p < np; ++p, ++j) {
+                int32_t *q = &pl[(i * mp + p) * 3];
+                q[0] = (*place)[j].x; q[1] = (*place)[j].y; q[2] = (*place)[j].m;
+            }
+        }
+        check<Tr>(h, pbd_score_placements(h, un ? &rec[0] : NULL, n, 0, &pl[0], &status[0], &sc[0]));
+    } else {
+        check<Tr>(h, pbd_part_scores(h, un ? &rec[0] : NULL, n, 0, &status[0], &pl[0], &sc[0]));
+    }
+    status.resize(un);
+    out.clear();
+    for (size_t i = 0; i < un; ++i)
+        for (size_t p = 0; status[i] > 0 && p < (size_t)status[i] && p < mp; ++p) {
+            PartScore s;
+            const int32_t *q = &pl[(i * mp + p) * 3];
+            const Real *v = &sc[(i * mp + p) * 4];
+            s.x = q[0]; s.y = q[1]; s.m = q[2];
+            s.appearance = (double)v[0]; s.message = (double)v[1]; s.bias = (double)v[2]; s.total = (double)v[3];
+            out.push_back(s);
+        }
+}
+
 // Frames of any sizes in one call (new surface: pbd_detect_frames; the reference has no batch API): candidates[i] receives
 // what detect(images[i]) gives.  The images share one depth and one channel count; any accepted depth.
 template <class Tr>

@@ -38,6 +38,8 @@ struct Error : std::runtime_error {
     Error(int c, const std::string &m) : std::runtime_error(m), code(c) {}
 };
 
+typedef pbdbind::PartScore PartScore;   // one part of a candidate's part scores (partScores, scorePlacements)
+
 // ---------------------------------------------------------------------------------------------- basics
 struct Rect {
     int x, y, width, height;
@@ -948,6 +950,37 @@ public:
         pbdbind::check<HostTraits<T> >(h_, pbd_examples(h_, n ? &rec[0] : NULL, (int)n, 0, &hdr[0], &values[0]));
         hdr.resize(hdr.size() - 1);
         values.resize(values.size() - 1);
+    }
+    // the score of each part of candidates of the last detect() (pbd_part_scores, include/pbd.h): `scores`
+    // receives every candidate's parts in candidate order (cell and mixture in the level's map; appearance, message, bias,
+    // total), and every candidate what the reference's record declares and never fills (include/Candidate.hpp:54-72):
+    // confidence_[p >= 1] = part p's appearance; confidence_[0] stays the score
+    void partScores(std::vector<Candidate> &candidates, std::vector<PartScore> &scores)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "partScores() before distributeModel()");
+        const std::vector<int32_t> rec = records(candidates);
+        std::vector<int32_t> status;
+        pbdbind::part_scores<HostTraits<T> >(h_, rec, (int)candidates.size(), std::vector<int>(), NULL, status, scores);
+        size_t j = 0;
+        for (size_t i = 0; i < candidates.size(); ++i) {
+            const size_t np = status[i] > 0 ? (size_t)status[i] : 0;
+            const float score = candidates[i].score();
+            candidates[i].confidence_.assign(np, 0.f);
+            for (size_t p = 0; p < np; ++p, ++j) candidates[i].confidence_[p] = p ? (float)scores[j].appearance : score;
+        }
+    }
+    // the same four values at placements the caller gives (pbd_score_placements): place holds x, y, m of every candidate's parts
+    // in candidate order (parts_.size() each, the root first), in the candidate's frame, level and component.  status[i] = the
+    // candidate's parts, or -1 for a placement outside the level's map or a part's mixtures; `scores` receives the parts of the
+    // candidates that have a status above 0
+    void scorePlacements(const std::vector<Candidate> &candidates, const std::vector<PartScore> &place, std::vector<int32_t> &status,
+                         std::vector<PartScore> &scores)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "scorePlacements() before distributeModel()");
+        const std::vector<int32_t> rec = records(candidates);
+        std::vector<int> nparts(candidates.size());
+        for (size_t i = 0; i < candidates.size(); ++i) nparts[i] = (int)candidates[i].parts_.size();
+        pbdbind::part_scores<HostTraits<T> >(h_, rec, (int)candidates.size(), nparts, &place, status, scores);
     }
     // a training QP of `capacity` examples of this detector's model layout (pbd_qp_create; Cpos = C * wpos, Cneg = C)
     QP qp(int capacity, double C = 0.002, double wpos = 2.0)

@@ -296,6 +296,19 @@ inline void hipPartPoses(pbd_handle *h, int n, const std::vector<float> &centres
     pbdbind::part_poses<CvTraits<T> >(h, n, centres, ncentres, dense, count, position, orientation, eigenvalues);
 }
 
+// The score of each part of candidates of the last hipDetect (pbd_part_scores; include/pbd.h "Part scores"): `scores` receives
+// every candidate's parts in candidate order -- cell and mixture in the level's map; appearance (the confidence the reference's
+// Candidate declares per part and never fills, include/Candidate.hpp:54-72), message, bias, total -- and status[i] candidate i's
+// parts
+template <typename T>
+inline void hipPartScores(pbd_handle *h, std::vector<typename CvTraits<T>::Candidate> &candidates, std::vector<int32_t> &status,
+                          std::vector<pbdbind::PartScore> &scores)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    pbdbind::part_scores<CvTraits<T> >(h, rec, (int)candidates.size(), std::vector<int>(), NULL, status, scores);
+}
+
 // A training positive's augmented copy on the device (pbd_augment_frames; include/pbd.h "Augmented positives"): dst becomes
 // rotate(mirror(im)), turned counter-clockwise by `degrees` (nearest neighbour, zero outside the source), of im's depth and
 // channel count (CV_8U, CV_16U, CV_32F or CV_64F; 1 or 3 channels).  The keypoints follow with pbd_augment_points.

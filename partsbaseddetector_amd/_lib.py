@@ -60,6 +60,7 @@ SYMBOLS = [
     "pbd_top_k_cells", "pbd_top_k_cells_device", "pbd_set_top_k", "pbd_top_k", "pbd_top_k_device",
     "pbd_set_depth_prune", "pbd_bind_depth", "pbd_bind_depth_device", "pbd_depth_prune", "pbd_depth_prune_device",
     "pbd_augment_plan", "pbd_augment_points", "pbd_augment_frames", "pbd_augment_frames_device", "pbd_detect_latent_device",
+    "pbd_part_scores", "pbd_part_scores_device", "pbd_score_placements", "pbd_score_placements_device",
 ]
 
 
@@ -293,6 +294,8 @@ def load():
     lib.pbd_example_stride.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.pbd_examples.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pbd_examples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    for fn in (lib.pbd_part_scores, lib.pbd_part_scores_device, lib.pbd_score_placements, lib.pbd_score_placements_device):
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_warp_positives.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_warp_positives_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,

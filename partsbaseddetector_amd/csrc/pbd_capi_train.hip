@@ -1,5 +1,5 @@
 // pbd_capi_train.hip -- the C entry points of training (include/pbd.h): the model vector and its in-place update, training
-// examples of a resident detect result, latent positives, and the QP over a device-resident example cache.
+// examples and part scores of a resident detect result, latent positives, and the QP over a device-resident example cache.
 // The handle and the layer they are written on: pbd_handle.h.
 #include "pbd_handle.h"
 
@@ -15,6 +15,125 @@ int check_examples_state(pbd_handle *h)
         return fail(h, PBD_ERR_STATE, "no resident detect result (pbd_detect* computes one; pbd_dp_min and pbd_conv_set_filters leave none)");
     if (!h->bank_matches_model || h->filter_ksize != h->model_ksize)
         return fail(h, PBD_ERR_STATE, "the filter bank's sizes differ from the model's: the model vector no longer describes it");
+    return PBD_OK;
+}
+
+// the host forms' check of records against the resident result (after check_examples_state): frame, level and component, and
+// with `root` the root cell; a failure names the record
+int check_resident_records(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, bool root)
+{
+    const int stride = ::stride(h);
+    const Resident &res = resident_owner(h)->res;
+    const Plan &P = *res.plan;
+    for (int i = 0; i < ncand; ++i) {
+        const int32_t *r = cand + (size_t)i * stride;
+        const long long f = (long long)r[0] - frame_offset;
+        int bf = 0, bl = 0;
+        if (f < INT32_MIN || f > INT32_MAX || !resident_level(res, (int)f, r[2], &bf, &bl))
+            return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d / level %d outside the resident result", i, r[0],
+                        frame_offset, r[2]);
+        const LevelDesc &d = P.lv[bl];
+        if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
+        if (root && (r[3] < 0 || r[3] >= d.cols || r[4] < 0 || r[4] >= d.rows))
+            return fail(h, PBD_ERR_INVALID, "record %d: root (%d, %d) outside the %d x %d map of level %d%s", i, r[3], r[4], d.cols,
+                        d.rows, r[2], d.rows ? "" : " (a level of another rank)");
+    }
+    return PBD_OK;
+}
+
+// ---- part scores (the kernels: pbd_kernels_partscores.hip) ----------------------------------------------
+// pbd_part_scores* / pbd_score_placements*: the state of pbd_examples*, and the responses the appearances are read from
+int check_part_scores_state(pbd_handle *h)
+{
+    if (int rc = check_examples_state(h)) return rc;
+    if (!resident_owner(h)->res.resp) return fail(h, PBD_ERR_STATE, "no resident responses");
+    return PBD_OK;
+}
+
+// The placements (the walk's, or d_place_in's checked) and the four values per part of min(max(word 0, 0), capacity) records of
+// d_in, on the handle's stream.  d_place NULL: the walk's placements stay in the handle's workspace
+int enqueue_part_scores(pbd_handle *h, const int32_t *d_in, int capacity, int frame_offset, const int32_t *d_place_in,
+                        int32_t *d_status, int32_t *d_place, void *d_scores)
+{
+    pbd_handle *o = resident_owner(h);   // its maps and responses, and the filter ids of its bank (the latent twin's differ)
+    Plan &P = *o->res.plan;
+    if (!o->sc_gm.p) {
+        std::vector<ExGm> gm(o->totmix);
+        for (int i = 0; i < o->totmix; ++i) gm[i] = ExGm{o->filterid[i], o->biasid[i], o->defid[i], 0};
+        std::vector<int> anc(o->anchors), nmix;
+        anc.push_back(0);
+        for (size_t gp = 0; gp + 1 < o->mix_offset.size(); ++gp) nmix.push_back(o->mix_offset[gp + 1] - o->mix_offset[gp]);
+        HIPCHK(h, o->sc_anchors.upload(anc));
+        HIPCHK(h, o->sc_nmix.upload(nmix));
+        HIPCHK(h, o->sc_gm.upload(gm));   // last: its presence marks the set complete
+    }
+    if (P.kind == 2 && !P.d_frame_lv0.p) HIPCHK(h, P.d_frame_lv0.upload(P.frame_lv0));
+    if (!d_place && !d_place_in) {
+        HIPCHK(h, h->sc_ws.ensure(std::max<size_t>((size_t)capacity * h->max_parts * 3 * sizeof(int32_t), 16)));
+        d_place = h->sc_ws.as<int32_t>();
+    }
+    std::vector<float> defw(o->defw);
+    defw.resize(defw.size() + 4, 0.f);
+    if (int rc = h->sc_defw.stage(h, defw.data(), defw.size() * sizeof(float))) return rc;
+    PartScoreParams pp{};
+    pp.in = d_in; pp.in_cap = capacity; pp.stride = stride(h); pp.frame_offset = frame_offset;
+    pp.lv = P.d_lv.p; pp.nlevels = P.nlevels;
+    pp.nframes = P.kind == 2 ? P.mixed_frames : o->res.frames;
+    pp.frame_lv0 = P.kind == 2 ? P.d_frame_lv0.p : nullptr;
+    pp.cell_per_frame = P.cell_per_frame;
+    pp.NC = o->NC; pp.NS = o->NS; pp.NJ = o->totmix; pp.ptr8 = P.ptr8 ? 1 : 0; pp.max_parts = h->max_parts;
+    pp.walk_mode = h->walk_mode;
+    pp.F = o->F; pp.NM = o->NM; pp.resp_half = o->resp_half ? 1 : 0;
+    pp.resp = o->resp.p; pp.acc = o->acc.p;
+    pp.rooti = o->rooti.as<int>(); pp.IxRaw = o->IxRaw.p; pp.IyRaw = o->IyRaw.p; pp.Ik = o->Ik.as<uint8_t>();
+    pp.walk = o->d_walk.p; pp.walk_off = o->d_walk_off.p; pp.part_nmix = o->sc_nmix.p;
+    pp.gm = o->sc_gm.p; pp.anchors = o->sc_anchors.p; pp.defw = h->sc_defw.as<float>(); pp.biasw = o->d_biasw.p;
+    pp.place_in = d_place_in; pp.status = d_status; pp.place = d_place; pp.scores = d_scores;
+    launch_part_scores(pp, h->f64, 0, h->stream);
+    launch_part_scores(pp, h->f64, 1, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
+// Both host forms: `place_in` NULL: pbd_part_scores (place may be NULL), else pbd_score_placements.  A record's status always
+// comes back; its placement and values only for the parts it has, so what lies past them, or belongs to a refused record, keeps
+// the caller's bytes
+int part_scores_host(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, const int32_t *place_in, int32_t *status,
+                     int32_t *place, void *scores)
+{
+    if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
+    if (int rc = check_part_scores_state(h)) return rc;
+    if (int rc = check_resident_records(h, cand, ncand, frame_offset, !place_in)) return rc;
+    if (ncand == 0) return PBD_OK;
+    const int stride = ::stride(h), mp = h->max_parts;
+    const size_t rb = ((size_t)ncand * stride + 1) * sizeof(int32_t), pb = (size_t)ncand * mp * 3 * sizeof(int32_t);
+    const size_t sb = (size_t)ncand * sizeof(int32_t), vb = (size_t)ncand * mp * 4 * h->rs;
+    int32_t *d_rec = nullptr, *d_pin = nullptr, *d_status = nullptr, *d_place = nullptr;
+    char *d_val = nullptr;
+    if (int rc = carve(h, h->sc_rec, [&](Carve &c) { d_rec = c.take<int32_t>(rb); d_pin = c.take<int32_t>(place_in ? pb : 0); }))
+        return rc;
+    if (int rc = carve(h, h->sc_out, [&](Carve &c) {
+            d_status = c.take<int32_t>(sb); d_place = c.take<int32_t>(place_in ? 0 : pb); d_val = c.take<char>(vb);
+        }))
+        return rc;
+    HIPCHK(h, hipMemcpyAsync(d_rec, &ncand, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_rec + 1, cand, rb - sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (place_in) HIPCHK(h, hipMemcpyAsync(d_pin, place_in, pb, hipMemcpyHostToDevice, h->stream));
+    if (int rc = enqueue_part_scores(h, d_rec, ncand, frame_offset, place_in ? d_pin : nullptr, d_status, place_in ? nullptr : d_place,
+                                     d_val))
+        return rc;
+    std::vector<char> hv(vb);
+    std::vector<int32_t> hp(place && !place_in ? pb / sizeof(int32_t) : 0);
+    HIPCHK(h, hipMemcpyAsync(status, d_status, sb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hv.data(), d_val, vb, hipMemcpyDeviceToHost, h->stream));
+    if (!hp.empty()) HIPCHK(h, hipMemcpyAsync(hp.data(), d_place, pb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < ncand; ++i) {
+        const int np = std::min(status[i], mp);
+        if (np <= 0) continue;
+        memcpy(static_cast<char *>(scores) + (size_t)i * mp * 4 * h->rs, hv.data() + (size_t)i * mp * 4 * h->rs, (size_t)np * 4 * h->rs);
+        if (!hp.empty()) memcpy(place + (size_t)i * mp * 3, hp.data() + (size_t)i * mp * 3, (size_t)np * 3 * sizeof(int32_t));
+    }
     return PBD_OK;
 }
 
@@ -595,21 +714,7 @@ int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset
         if (ncand < 0) return fail(h, PBD_ERR_INVALID, "ncand %d", ncand);
         if (int rc = check_examples_state(h)) return rc;
         const int stride = ::stride(h);
-        const Resident &res = resident_owner(h)->res;
-        const Plan &P = *res.plan;
-        for (int i = 0; i < ncand; ++i) {
-            const int32_t *r = cand + (size_t)i * stride;
-            const long long f = (long long)r[0] - frame_offset;
-            int bf = 0, bl = 0;
-            if (f < INT32_MIN || f > INT32_MAX || !resident_level(res, (int)f, r[2], &bf, &bl))
-                return fail(h, PBD_ERR_INVALID, "record %d: frame %d - frame_offset %d / level %d outside the resident result", i, r[0],
-                            frame_offset, r[2]);
-            const LevelDesc &d = P.lv[bl];
-            if (r[1] < 0 || r[1] >= h->NC) return fail(h, PBD_ERR_INVALID, "record %d: component %d (0..%d)", i, r[1], h->NC - 1);
-            if (r[3] < 0 || r[3] >= d.cols || r[4] < 0 || r[4] >= d.rows)
-                return fail(h, PBD_ERR_INVALID, "record %d: root (%d, %d) outside the %d x %d map of level %d%s", i, r[3], r[4], d.cols,
-                            d.rows, r[2], d.rows ? "" : " (a level of another rank)");
-        }
+        if (int rc = check_resident_records(h, cand, ncand, frame_offset, true)) return rc;
         if (ncand == 0) return PBD_OK;
         const size_t hb = (size_t)ncand * h->ex_hdr_words * sizeof(int32_t), vb = (size_t)ncand * h->ex_values * h->rs;
         int32_t *d_hdr = nullptr;
@@ -733,6 +838,43 @@ int pbd_examples_device(pbd_handle *h, const int32_t *d_payload, int capacity, i
         if (int rc = check_examples_state(h)) return rc;
         if (capacity == 0) return PBD_OK;
         return enqueue_examples(h, d_payload, capacity, frame_offset, d_hdr, d_values);
+    });
+}
+
+int pbd_part_scores(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, int32_t *status, int32_t *place, void *scores)
+{
+    return entry(h, ncand <= 0 || (cand && status && scores), kIdle, [&]() -> int {
+        return part_scores_host(h, cand, ncand, frame_offset, nullptr, status, place, scores);
+    });
+}
+
+int pbd_part_scores_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_status, int32_t *d_place,
+                           void *d_scores)
+{
+    return entry(h, d_payload && (capacity <= 0 || (d_status && d_scores)), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_part_scores_state(h)) return rc;
+        if (capacity == 0) return PBD_OK;
+        return enqueue_part_scores(h, d_payload, capacity, frame_offset, nullptr, d_status, d_place, d_scores);
+    });
+}
+
+int pbd_score_placements(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset, const int32_t *place, int32_t *status,
+                         void *scores)
+{
+    return entry(h, ncand <= 0 || (cand && place && status && scores), kIdle, [&]() -> int {
+        return part_scores_host(h, cand, ncand, frame_offset, place, status, nullptr, scores);
+    });
+}
+
+int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, const int32_t *d_place,
+                                int32_t *d_status, void *d_scores)
+{
+    return entry(h, d_payload && (capacity <= 0 || (d_place && d_status && d_scores)), kIdle, [&]() -> int {
+        if (capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d", capacity);
+        if (int rc = check_part_scores_state(h)) return rc;
+        if (capacity == 0) return PBD_OK;
+        return enqueue_part_scores(h, d_payload, capacity, frame_offset, d_place, d_status, nullptr, d_scores);
     });
 }
 

@@ -1,6 +1,7 @@
 // pbd_dp.h (private) -- the reference rules and buffer addresses the dynamic program's kernels share, one definition each:
 // the level of a flat index, the planes of a level's block in every buffer, Math::reduceMax, the back-pointer composition of a
-// walk, a part's rectangle and a root's record header.  pbd_kernels_dp.hip (detection) and pbd_kernels_examples.hip (the trainer)
+// walk, the value of a deformation's quadratic, a record's level in the resident result, a part's rectangle and a root's record
+// header.  pbd_kernels_dp.hip (detection), pbd_kernels_examples.hip (the trainer) and pbd_kernels_partscores.hip (part scores)
 // keep only what is their own; two consumers of a rule agree bit for bit because they run the same statement.
 #pragma once
 
@@ -82,6 +83,34 @@ template <typename R, class Score> __device__ __forceinline__ R reduce_max(int n
     R best = -RealLimits<R>::inf();
     for (int mm = 0; mm < n; ++mm) pick_max<R>(score(mm), mm, best, bi);
     return best;
+}
+
+// ---- Quadratic::operator()(x, y) (include/DistanceTransform.hpp:102-104) -------------------------------------------------------
+// a x^2 + b x + y: the int square, double arithmetic left to right, one rounding to T.  The transform's passes write it for every
+// cell; the part scores (pbd_kernels_partscores.hip) evaluate it at a placement's displacement.
+// BZ: the linear coefficient b is exactly -0.0 and a != 0 (see quad_isect of pbd_kernels_dp.hip: the value is the same)
+template <typename R, bool BZ>
+__device__ __forceinline__ R quad_val(double a, double b, int x, R y)
+{
+    if (BZ) return (R)(a * (double)__mul24(x, x) + (double)y);
+    return (R)((a * (double)__mul24(x, x) + b * (double)x) + (double)y);     // |x| < 2^16
+}
+
+// ---- a record's (frame, level) in the resident result ---------------------------------------------------------------------------
+// (frame of the buffers, level of the plan) of a record's frame f (its frame field less the call's frame_offset) and level l, or
+// {-1, -1} outside the result.  Mixed plans (frame_lv0 != NULL: [nframes + 1] first virtual level of each frame): frame 0, the
+// virtual level.  The host states the same in resident_level (pbd_handle.h)
+struct RecordLevel { int bf, vl; };
+__device__ __forceinline__ RecordLevel record_level(long long f, int l, int nframes, int nlevels, const int *frame_lv0)
+{
+    if (f >= 0 && f < nframes && l >= 0) {
+        if (frame_lv0) {
+            if (l < frame_lv0[f + 1] - frame_lv0[f]) return {0, frame_lv0[f] + l};
+        } else if (l < nlevels) {
+            return {(int)f, l};
+        }
+    }
+    return {-1, -1};
 }
 
 // ---- back-tracking (src/DynamicProgram.cpp:218-244) ---------------------------------------------------------------------------

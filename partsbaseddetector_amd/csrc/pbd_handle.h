@@ -453,6 +453,13 @@ struct Handle : ErrCtx {
     DevTable<int> ex_anchors;
     DevTable<long long> ex_foff;
     DevBuf ex_ws, ex_rec, ex_out;
+    // pbd_part_scores* / pbd_score_placements*: the model's tables (per (part, mixture) ids with this handle's filter ids,
+    // anchors, mixtures per part; uploaded on first use), the call's deformation weights (staged: a model update changes them),
+    // the placements when the caller takes none, the host form's records, placements and outputs
+    DevTable<ExGm> sc_gm;
+    DevTable<int> sc_anchors, sc_nmix;
+    StagedTable sc_defw;
+    DevBuf sc_ws, sc_rec, sc_out;
     // pbd_set_model_vector* / pbd_qp_apply: the model vector on the device (T; written by the first update, from then on the
     // source of every weight table), whether the host copy `mvec` is behind it (brought up to date on demand: sync_mvec), the
     // update's index tables (built on first use), the host form's vector, and the status block {refused, -, -, -, biasw, defw}

@@ -741,6 +741,34 @@ struct ExampleParams {
 };
 void launch_examples(const ExampleParams &p, bool f64, int step, hipStream_t s);   // step 0: walk, 1: gather
 
+// part scores of records (pbd_part_scores*, pbd_score_placements*; pbd_kernels_partscores.hip)
+struct PartScoreParams {
+    const int32_t *in;            // payload: word 0 = records (negative: none), then the records
+    int in_cap, stride, frame_offset;
+    const LevelDesc *lv;
+    int nlevels, nframes;         // equal-size plans: frames of the batch
+    const int *frame_lv0;         // mixed plans: [nframes + 1] first virtual level of each frame (NULL: equal-size plan)
+    long long cell_per_frame;
+    int NC, NS, NJ, ptr8, max_parts;
+    int walk_mode;                // PBD_WALK_* of the handle at the call (walk_child)
+    int F, NM, resp_half;         // planes per cell block of resp (NM: of acc, not read), resp holds fp16
+    const void *resp;             // the resident responses (see DpParams)
+    void *acc;                    // not read (LevelPlanes::score names it)
+    const int *rooti;
+    const void *IxRaw, *IyRaw; const uint8_t *Ik;   // see DpParams
+    const PartWalk *walk; const int *walk_off;
+    const int *part_nmix;         // [parts of the model] mixtures of a part, indexed as `walk`
+    const ExGm *gm;               // per (part, mixture): filter id in `resp`, bias id, deformation id
+    const int *anchors;           // [ndefs][2]
+    const float *defw;            // [ndefs][4]
+    const float *biasw;
+    const int32_t *place_in;      // pbd_score_placements*: [in_cap][max_parts][3] x, y, m given by the caller (NULL: the walk's)
+    int32_t *status;              // [in_cap] parts of the record, or -1
+    int32_t *place;               // [in_cap][max_parts][3]
+    void *scores;                 // R [in_cap][max_parts][4] appearance, message, bias, total
+};
+void launch_part_scores(const PartScoreParams &p, bool f64, int step, hipStream_t s);   // step 0: placements, 1: scores
+
 // latent positives (pbd_detect_latent; pbd_kernels_examples.hip).  The responses are those of the latent bank: one plane per
 // (component, part, mixture) = global mixture index gm, so a mask belongs to its (component, part, mixture).
 struct LatentParams {

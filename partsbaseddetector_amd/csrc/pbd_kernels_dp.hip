@@ -51,12 +51,7 @@ __device__ __forceinline__ R quad_isect(double a, double b, int x0, int x1, R y0
     const double num = BZ ? (y1 - y0) + a * sq : ((y1 - y0) - b * dd) + a * sq;
     return (R)(num / ((2 * a) * dd));
 }
-template <typename R, bool BZ>
-__device__ __forceinline__ R quad_val(double a, double b, int x, R y)
-{   // Quadratic::operator()(x, y), :103-105
-    if (BZ) return (R)(a * (double)__mul24(x, x) + (double)y);
-    return (R)((a * (double)__mul24(x, x) + b * (double)x) + (double)y);     // |x| < 2^16
-}
+// (Quadratic::operator()(x, y) is quad_val of pbd_dp.h: the part scores evaluate it at a placement)
 
 // ------------------------------------------------------------------------------------------------
 // One 1-D transform per thread, streamed in chunks of CH elements.

@@ -35,14 +35,8 @@ __global__ __launch_bounds__(kExWalkThreads) void k_ex_walk(ExampleParams p)
         int32_t *hdr = p.hdr + (size_t)i * p.hdr_words;
         ExPart *parts = p.parts + (size_t)i * p.max_parts;
         // (frame, level) of the record -> (frame of the buffers, level of the plan); mixed plans: frame 0, the virtual level
-        int bf = -1, vl = -1;
-        if (f >= 0 && f < p.nframes && l >= 0) {
-            if (p.frame_lv0) {
-                if (l < p.frame_lv0[f + 1] - p.frame_lv0[f]) { bf = 0; vl = p.frame_lv0[f] + l; }
-            } else if (l < p.nlevels) {
-                bf = (int)f; vl = l;
-            }
-        }
+        const RecordLevel rl = record_level(f, l, p.nframes, p.nlevels, p.frame_lv0);
+        const int bf = rl.bf, vl = rl.vl;
         bool ok = vl >= 0 && c >= 0 && c < p.NC;
         LevelDesc d{};
         if (ok) {

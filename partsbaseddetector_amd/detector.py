@@ -35,6 +35,7 @@ class Candidate:
     level: int = 0
     root: tuple = (0, 0)
     offset: tuple = (0, 0)   # (x, y) of the region the candidate was found in (detect_regions); boxes are region-relative
+    mixtures: np.ndarray = None   # the type (mixture) of every part, set by PartsBasedDetector.partScores
 
     def score(self) -> float:  # Candidate.hpp:82
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -521,6 +522,47 @@ class Handle:
         self.check(self.lib.pbd_examples(self.h, rec.ctypes.data if rec.size else None, len(rec), frame_offset,
                                          hdr.ctypes.data if hdr.size else None, vals.ctypes.data if vals.size else None))
         return hdr, vals
+
+    def part_scores(self, records: np.ndarray, frame_offset: int = 0, fill=0):
+        """pbd_part_scores: (status (n,) int32, place (n, max_parts, 3) int32 x, y, m, scores (n, max_parts, 4) T appearance,
+        message, bias, total) of records (n, stride) of the last detect call, at the walk's placement.  Entries past a record's
+        parts keep `fill`."""
+        rec = self._records(records)
+        mp = (self.stride - 8) // 4
+        status = np.full(len(rec), fill, np.int32)
+        place = np.full((len(rec), mp, 3), fill, np.int32)
+        scores = np.full((len(rec), mp, 4), fill, self.dtype)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self.check(self.lib.pbd_part_scores(self.h, ptr(rec), len(rec), frame_offset, ptr(status), ptr(place), ptr(scores)))
+        return status, place, scores
+
+    def score_placements(self, records: np.ndarray, place: np.ndarray, frame_offset: int = 0, fill=0):
+        """pbd_score_placements: (status (n,) int32, scores (n, max_parts, 4) T) of the placements place (n, max_parts, 3) x, y, m
+        (place[i][0] the root) in the frame, level and component of records (n, stride); a placement outside the map or the
+        part's mixtures has status -1 and keeps `fill`"""
+        rec = self._records(records)
+        mp = (self.stride - 8) // 4
+        place = np.ascontiguousarray(place, np.int32)
+        if place.shape != (len(rec), mp, 3):
+            raise PbdError(-1, f"placements of shape {place.shape}, expected {(len(rec), mp, 3)}")
+        status = np.full(len(rec), fill, np.int32)
+        scores = np.full((len(rec), mp, 4), fill, self.dtype)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self.check(self.lib.pbd_score_placements(self.h, ptr(rec), len(rec), frame_offset, ptr(place), ptr(status), ptr(scores)))
+        return status, scores
+
+    def part_scores_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_status_ptr: int, d_place_ptr,
+                           d_scores_ptr: int) -> None:
+        """pbd_part_scores_device: status int32[capacity], place int32[capacity * max_parts * 3] (or None) and scores
+        T[capacity * max_parts * 4] of a device payload's records; asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_part_scores_device(self.h, d_payload_ptr, capacity, frame_offset, d_status_ptr, d_place_ptr,
+                                                   d_scores_ptr))
+
+    def score_placements_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_place_ptr: int, d_status_ptr: int,
+                                d_scores_ptr: int) -> None:
+        """pbd_score_placements_device: score_placements on device arrays; asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_score_placements_device(self.h, d_payload_ptr, capacity, frame_offset, d_place_ptr, d_status_ptr,
+                                                        d_scores_ptr))
 
     def detect_latent(self, frames, part_boxes, overlap: float, mixtures=None):
         """pbd_detect_latent: (records (nframes, stride) int32, found (nframes,) int32) -- per frame the best root whose parts
@@ -1580,6 +1622,39 @@ class PartsBasedDetector:
             cands = list(candidates)
             rec = self.hd.pack_candidates(cands) if cands else np.zeros((0, self.hd.stride), np.int32)
         return self.hd.examples(rec)
+
+    def _candidate_records(self, candidates):
+        if isinstance(candidates, np.ndarray):
+            return candidates, []
+        cands = list(candidates)
+        return (self.hd.pack_candidates(cands) if cands else np.zeros((0, self.hd.stride), np.int32)), cands
+
+    def partScores(self, candidates):
+        """the score of each part of candidates of the last detect call (Candidate objects or records (n, stride) int32), on the
+        device (pbd_part_scores; the rule: partscores.py): (place (n, max_parts, 3) int32 x, y, mixture of
+        every part in its level's map, scores (n, max_parts, 4) T appearance, message, bias, total).  Candidate objects receive
+        what the reference's record declares and never fills (include/Candidate.hpp:54-72): `confidence` becomes nparts floats,
+        [0] still the score (score() reads it) and [p >= 1] part p's appearance, and `mixtures` the parts' types."""
+        self._need()
+        rec, cands = self._candidate_records(candidates)
+        status, place, scores = self.hd.part_scores(rec)
+        for i, c in enumerate(cands):
+            n = int(status[i])
+            conf = np.zeros(n, np.float32)
+            conf[0] = np.float32(c.score())
+            conf[1:] = scores[i, 1:n, 0].astype(np.float32)
+            c.confidence = conf
+            c.mixtures = place[i, :n, 2].copy()
+        return place, scores
+
+    def scorePlacements(self, candidates, place):
+        """the same four values at placements the caller gives (pbd_score_placements): place (n, max_parts, 3) x, y, mixture,
+        place[i][0] the root, in the frame, level and component of candidate i.  Returns (status (n,) int32: the parts, or -1 for
+        a placement outside the level's map or a part's mixtures, scores (n, max_parts, 4) T).  Scores a ground-truth pose
+        under the current weights."""
+        self._need()
+        rec, _ = self._candidate_records(candidates)
+        return self.hd.score_placements(rec, place)
 
     def examples_device(self, d_payload_ptr: int, capacity: int, frame_offset: int, d_hdr_ptr: int, d_values_ptr: int) -> None:
         """pbd_examples_device on a device payload (as detect_batch_device_out / detect_frames_device_out leave it)"""
