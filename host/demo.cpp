@@ -6,7 +6,7 @@
 //   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
-//            [--part-scores]
+//            [--part-scores] [--marginal-pose PART]
 //   --device-nms: the sort + suppression run on the device (pbd_set_nms) instead of on the host; --nms keeps its host meaning
 //   --walk argmax: part boxes at the placement the score was taken at (pbd_set_walk) instead of the reference's composed pointers
 //   --root-nms SZ: only the roots that are grid maxima of their score plane within SZ cells are walked and listed
@@ -40,6 +40,10 @@
 //   --part-scores: after the candidate lines, one line per listed candidate and part, "part_score CANDIDATE PART x y m appearance
 //           message bias total" (pbd_part_scores, DESIGN.md section 6s: the part's cell and mixture in its level's map and the
 //           four values, floats as %a so that every bit shows); not with --staged, --stream or --also
+//   --marginal-pose PART: after the candidate lines, the pose decoded from the best cell of part PART (of component 0) over all
+//           levels of its max-marginals (pbd_max_marginals / pbd_marginal_poses): one line "marginal_pose
+//           PART LEVEL X Y SCORE" (the part's level and cell, the score as %a) and the pose as a candidate line; not with --staged,
+//           --stream or --also
 //   --augment DEG[,mirror] OUT.ppm: no detection; the image's augmented copy rotate(mirror(image)) -- turned counter-clockwise by
 //           DEG degrees, nearest neighbour, zero outside (pbd_augment_frames) -- written as a binary PPM
 //           (PGM for grey) and one line "augment ROWS COLS"
@@ -61,6 +65,7 @@ static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
 static int g_top_k = 0;                   // --top-k
 static bool g_part_scores = false;        // --part-scores
+static int g_marginal_part = -1;          // --marginal-pose
 static bool g_prune = false;              // --depth-prune fx,width,tol
 static float g_prune_fx = 0.f, g_prune_width = 0.f, g_prune_tol = 0.f;
 
@@ -267,6 +272,43 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
                 std::printf("part_score %zu %zu %d %d %d %a %a %a %a\n", i, p, scores[j].x, scores[j].y, scores[j].m, scores[j].appearance,
                             scores[j].message, scores[j].bias, scores[j].total);
     }
+    if (g_marginal_part >= 0) {          // the pose with part PART at the best cell of its max-marginals
+        std::vector<MarginalLevel> levels;
+        pbd.maxMarginals(im, levels);
+        // the part's planes: component 0's parts come first, so its first plane is the types of the parts before it
+        int g0 = 0, K = 0;
+        const std::vector<std::vector<int> > &fid = model.filterid()[0];
+        if ((size_t)g_marginal_part >= fid.size()) {
+            std::fprintf(stderr, "--marginal-pose %d: component 0 has %zu parts\n", g_marginal_part, fid.size());
+            return -1;
+        }
+        for (int p = 0; p < g_marginal_part; ++p) g0 += (int)fid[p].size();
+        K = (int)fid[g_marginal_part].size();
+        double best = 0;
+        std::vector<int32_t> seed;
+        for (size_t l = 0; l < levels.size(); ++l) {
+            const MarginalLevel &L = levels[l];
+            const size_t hw = (size_t)L.rows * L.cols;
+            for (int m = 0; m < K; ++m)
+                for (size_t i = 0; i < hw; ++i) {
+                    const double v = L.values[(size_t)(g0 + m) * hw + i];
+                    if (seed.empty() || v > best) {
+                        best = v;
+                        const int32_t sd[6] = {(int32_t)l, 0, g_marginal_part, m, (int32_t)(i % L.cols), (int32_t)(i / L.cols)};
+                        seed.assign(sd, sd + 6);
+                    }
+                }
+        }
+        std::vector<int32_t> status;
+        std::vector<Candidate> pose;
+        if (!seed.empty()) pbd.marginalPoses(seed, status, pose);
+        if (pose.empty()) {
+            std::printf("marginal_pose %d none\n", g_marginal_part);
+        } else {
+            std::printf("marginal_pose %d %d %d %d %a\n", g_marginal_part, seed[0], seed[4], seed[5], (double)pose[0].score());
+            report(pose, im, false, -1.f, -1.f, 1);
+        }
+    }
     if (mask_path) {                     // Candidate::mask and the masked image of the listed candidates
         if (!pbd.handle()) pbd.distributeModel(model);
         const std::vector<Candidate> listed(candidates.begin(), candidates.begin() + std::min<size_t>(candidates.size(), (size_t)top));
@@ -338,7 +380,7 @@ static int run_augment(Model &model, const Image &im, double degrees, bool mirro
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--augment deg[,mirror] out.ppm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
     const char *augment_path = NULL;
@@ -359,6 +401,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--remove-planes")) remove_planes = true;
         else if (!std::strcmp(argv[i], "--poses")) poses = true;
         else if (!std::strcmp(argv[i], "--part-scores")) g_part_scores = true;
+        else if (!std::strcmp(argv[i], "--marginal-pose") && i + 1 < argc) g_marginal_part = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--mask") && i + 1 < argc) mask_path = argv[++i];
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked_path = argv[++i];
         else if (!std::strcmp(argv[i], "--nms") && i + 1 < argc) nms = (float)std::atof(argv[++i]);
@@ -434,6 +477,10 @@ int main(int argc, char **argv)
     }
     if (g_part_scores && (staged || stream_k > 0 || !also.empty())) {
         std::fprintf(stderr, "--part-scores reads the resident result of a single detect call: not with --staged, --stream or --also\n");
+        return -1;
+    }
+    if (g_marginal_part >= 0 && (staged || stream_k > 0 || !also.empty())) {
+        std::fprintf(stderr, "--marginal-pose reads the resident result of a single detect call: not with --staged, --stream or --also\n");
         return -1;
     }
     if (have_camera && !depth_path) {

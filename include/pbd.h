@@ -880,6 +880,58 @@ int pbd_score_placements(pbd_handle *h, const int32_t *cand, int ncand, int fram
                          void *scores);
 int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int capacity, int frame_offset, const int32_t *d_place,
                                 int32_t *d_status, void *d_scores);
+/* Max-marginals of every part and the poses they decode to (new surface; opt-in).  DESIGN.md section 6t; the rule in numpy:
+ * partsbaseddetector_amd/marginals.py.  The detector answers "the best configuration rooted at this cell"; the max-marginal
+ * mm_p[m][y][x] answers it for every part: the score of the best configuration with part p of type m at (x, y).
+ * Per (frame, level, component) on the level's H x W maps; T the handle's real type, q = parent(p), K_p the types of p, every +
+ * one addition rounded to T, a bias entering as (T)biasw[..]:
+ *   S_p[m]    the plane part p, type m, had accumulated when the upward pass consumed it (a leaf: its filter's response)
+ *   D_p[m]    = dt(S_p[m]; -w0, -w1, -w2, -w3; ox, oy), the upward transform (rows pass, then columns pass)
+ *   M_p[mq]   = reduceMax over m of (D_p[m] + bias(p, m)[mq]): strict >, the first of equals wins, K_p == 1 copies
+ *   root      down_0[m] = (T)bias of the root's type 0 for every root type m; mm_0[m] = S_0[m] + down_0[m]
+ *   context   C_p[mq] = resp(filter(q, mq)); for every child c of q in DESCENDING index order, c != p: C_p[mq] += M_c[mq]; last
+ *             C_p[mq] += down_q[mq]
+ *   mirrored  R_p[m][mq] = dt(C_p[mq]; -w0, +w1, -w2, +w3; -ox, -oy) with the weights and anchor of (p, m): the upward quadratic
+ *             seen from the child (the negated linear coefficients: an upward -0.0 becomes +0.0), the transform otherwise the
+ *             upward one, the NaN read-out rule of pbd_dp_min included
+ *   down      down_p[m] = reduceMax over mq of (R_p[m][mq] + bias(p, m)[mq]), the same first-wins rule and K_q == 1 copy;
+ *             Jk_p[m] the winning mq; (Jx_p[m], Jy_p[m]) the parent's cell, composed in arg-max order from the winner's pointer
+ *             planes: the columns pass's pointer first, then the rows pass's at that row
+ *   mm        mm_p[m] = S_p[m] + down_p[m]
+ * so reduceMax over m of mm_0[m] has the bits of the root scores (and its index is their type), and where every sum is exact in
+ * T, mm_p[m][y][x] is exactly the maximum over the configurations with p of type m at (x, y).
+ * pbd_max_marginals(h, frame): the planes of one frame of the resident dynamic-program result (after pbd_detect*, equal-size
+ *   frames, or pbd_dp_min: frame 0), kept on the device until the next detect call, pbd_dp_min, model update or
+ *   pbd_max_marginals.  Asynchronous on pbd_stream().  The resident detection result is not changed.  Device memory held:
+ *   (2 sizeof(T) + 5) NJ + sizeof(T) NS bytes per cell of the frame, plus scratch of sizeof(T) JGmax + 2 P max(JGmax, NJ) bytes per
+ *   cell (NJ: the (part, type) pairs of the model, NS its pointer slots, JGmax the transforms of its largest depth group, P the
+ *   bytes of a position: 1 while no map side exceeds 256, else 2).
+ *   PBD_ERR_STATE: no resident dynamic-program result (none yet, after a model update or pbd_conv_set_filters), a latent result
+ *   (pbd_detect_latent), a batch in flight.  PBD_ERR_INVALID: frame outside the result.  PBD_ERR_UNSUPPORTED: a model on the
+ *   sequential schedule (a filter id shared inside a component), fp16-resident responses (modes 3 and 6), a mixed-size result
+ *   (pbd_detect_frames), a level-sharded handle (world > 1).
+ * pbd_get_marginals(h, level, what, dst, dst_bytes): one level's block, synchronous.  PBD_MM_VALUES / PBD_MM_DOWN: T[NJ][H][W];
+ *   PBD_MM_PARENT_X / _Y / _K: int32[NJ][H][W], -1 in every plane of a root.  PBD_ERR_STATE without resident marginals.
+ * pbd_marginals_device(h, level, &d): the device pointer of the level's mm block T[NJ][H][W] (for pbd_grid_nms_device /
+ *   pbd_top_k_cells_device), valid as long as the marginals are.
+ * pbd_marginal_poses(h, n, seeds, scales, frame_offset, cand, place, status): seeds = int32[n][6] {level, component, part, type
+ *   or -1 (the first type with the largest mm at the cell), x, y}.  The pose of a seed: climb from the seed through Jk / Jx / Jy to
+ *   the root, which fixes every part on that path; every other part, in index order, takes the arg-max placement of the upward
+ *   pointers from its parent's (whatever pbd_set_walk says: the marginal was taken there).  cand = int32[n][stride] records:
+ *   frame (that of pbd_max_marginals) + frame_offset, component, level, the decoded root's x, y, (float)mm of the seed, parts, the
+ *   root's type in word 7, then the part boxes at the level's scale; scales = float[levels] as for pbd_dp_argmin, or NULL for the
+ *   plan's own (after pbd_detect*; NULL after pbd_dp_min is PBD_ERR_INVALID).  place = int32[n][max_parts][3] {x, y, type} or
+ *   NULL.  status = int32[n]: the parts of the pose, or -1 for a bad seed (a cell outside the map, a part, type, component or
+ *   level out of range), whose record and placement are not written.  Synchronous; pbd_marginal_poses_device takes device
+ *   arrays and is asynchronous on pbd_stream().  PBD_ERR_STATE without resident marginals. */
+enum { PBD_MM_VALUES = 0, PBD_MM_DOWN = 1, PBD_MM_PARENT_X = 2, PBD_MM_PARENT_Y = 3, PBD_MM_PARENT_K = 4 };
+int pbd_max_marginals(pbd_handle *h, int frame);
+int pbd_get_marginals(pbd_handle *h, int level, int what, void *dst, size_t dst_bytes);
+int pbd_marginals_device(pbd_handle *h, int level, void **d_values);
+int pbd_marginal_poses(pbd_handle *h, int n, const int32_t *seeds, const float *scales, int frame_offset, int32_t *cand,
+                       int32_t *place, int32_t *status);
+int pbd_marginal_poses_device(pbd_handle *h, int n, const int32_t *d_seeds, const float *scales, int frame_offset, int32_t *d_cand,
+                              int32_t *d_place, int32_t *d_status);
 /* Warped positives (new surface; opt-in): poswarp of the reference's Matlab training code (matlab/learning/train.m:131-162 with
  * matlab/learning/warppos.m, subarray.m and qp_poswrite), the examples every training run starts from (trainmodel.m:19-40 trains
  * each part mixture as a one-part model on them).  DESIGN.md section 6k.  Each annotated box is padded by one cell, cropped with
@@ -1294,6 +1346,10 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
        PBD_K_TOP_K,
        /* pbd_set_depth_prune / pbd_depth_prune*: the plausibility test of the root cells, or of a list's records */
        PBD_K_DEPTH_PRUNE,
+       /* pbd_max_marginals: the forward transforms re-run for the messages and the mirrored transforms (the detect path's
+          transform kernels, counted here and not under k_dt_rows / k_dt_cols), the messages, the contexts, the reduction over the
+          parent's types; pbd_marginal_poses*: the decode */
+       PBD_K_MM_DT_ROWS, PBD_K_MM_DT_COLS, PBD_K_MM_MESSAGES, PBD_K_MM_CONTEXT, PBD_K_MM_DOWN, PBD_K_MM_DECODE,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

@@ -505,6 +505,58 @@ inline void part_scores(pbd_handle *h, const std::vector<int32_t> &rec, int n, c
         }
 }
 
+// One level of the max-marginals (pbd_max_marginals / pbd_get_marginals, include/pbd.h): `planes` planes of rows x cols, plane
+// gm = the (part, type) pair's global index, values[gm * rows * cols + y * cols + x] held as double (exact for both real types)
+struct MarginalLevel {
+    int rows, cols, planes;
+    std::vector<double> values;
+    MarginalLevel() : rows(0), cols(0), planes(0) {}
+};
+
+// The max-marginals of frame `frame` of the last detect call on an im_rows x im_cols image (the levels are those of
+// pbd_pyramid_plan for that size); planes = the (part, type) pairs of the handle's model.  They stay on the device for
+// marginal_poses until the next detect call.
+template <class Tr>
+inline void max_marginals(pbd_handle *h, int frame, int im_rows, int im_cols, int planes, std::vector<MarginalLevel> &levels)
+{
+    typedef typename Tr::Real Real;
+    check<Tr>(h, pbd_max_marginals(h, frame));
+    int n = 0, ir[PBD_MAX_LEVELS], ic[PBD_MAX_LEVELS], fr[PBD_MAX_LEVELS], fc[PBD_MAX_LEVELS];
+    float sc[PBD_MAX_LEVELS];
+    check<Tr>(h, pbd_pyramid_plan(h, im_rows, im_cols, &n, ir, ic, fr, fc, sc));
+    levels.assign(n > 0 ? (size_t)n : 0, MarginalLevel());
+    std::vector<Real> buf;
+    for (int l = 0; l < n; ++l) {
+        MarginalLevel &L = levels[l];
+        L.rows = fr[l]; L.cols = fc[l]; L.planes = planes;
+        const size_t cnt = (size_t)planes * (size_t)fr[l] * (size_t)fc[l];
+        buf.assign(cnt + 1, Real(0));
+        check<Tr>(h, pbd_get_marginals(h, l, PBD_MM_VALUES, &buf[0], cnt * sizeof(Real)));
+        L.values.assign(buf.begin(), buf.begin() + cnt);
+    }
+}
+
+// The poses of n seeds {level, component, part, type or -1, x, y} (6 ints each) decoded from the max-marginals held
+// (pbd_marginal_poses), at the detect call's own scales: status[i] = the pose's parts or -1 for a bad seed; `candidates` receives
+// the poses of the good seeds in seed order, each with the seed's max-marginal as its score
+template <class Tr>
+inline void marginal_poses(pbd_handle *h, const std::vector<int32_t> &seeds, std::vector<int32_t> &status,
+                           std::vector<typename Tr::Candidate> &candidates)
+{
+    const size_t n = seeds.size() / 6, stride = (size_t)pbd_candidate_stride(h);
+    std::vector<int32_t> rec(n * stride + 1, 0);
+    status.assign(n + 1, 0);
+    check<Tr>(h, pbd_marginal_poses(h, (int)n, n ? &seeds[0] : NULL, NULL, 0, &rec[0], NULL, &status[0]));
+    status.resize(n);
+    std::vector<int32_t> one(stride + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (status[i] <= 0) continue;
+        std::copy(rec.begin() + i * stride, rec.begin() + (i + 1) * stride, one.begin());
+        one[7] = 0;
+        unpack_candidates<Tr>(h, one, 1, candidates);
+    }
+}
+
 // Frames of any sizes in one call (new surface: pbd_detect_frames; the reference has no batch API): candidates[i] receives
 // what detect(images[i]) gives.  The images share one depth and one channel count; any accepted depth.
 template <class Tr>

@@ -39,6 +39,7 @@ struct Error : std::runtime_error {
 };
 
 typedef pbdbind::PartScore PartScore;   // one part of a candidate's part scores (partScores, scorePlacements)
+typedef pbdbind::MarginalLevel MarginalLevel;   // one level of the max-marginals (maxMarginals)
 
 // ---------------------------------------------------------------------------------------------- basics
 struct Rect {
@@ -604,6 +605,7 @@ class PartsBasedDetector {
     float zfactor_;
     bool prune_on_;
     float prune_fx_, prune_width_, prune_tol_;
+    int planes_;                         // the (part, type) pairs of the distributed model: planes of a max-marginal level
     PartsBasedDetector(const PartsBasedDetector &);
     PartsBasedDetector &operator=(const PartsBasedDetector &);
 public:
@@ -613,7 +615,8 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), top_k_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f) {}
+          root_nms_(0), top_k_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
+          planes_(0) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
     pbd_handle *handle() const { return h_; }
@@ -628,6 +631,9 @@ public:
         if (top_k_) pbdbind::set_top_k<HostTraits<T> >(h_, top_k_);
         if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
         name_ = model.name();
+        planes_ = 0;
+        for (size_t c = 0; c < model.filterid().size(); ++c)
+            for (size_t p = 0; p < model.filterid()[c].size(); ++p) planes_ += (int)model.filterid()[c][p].size();
     }
     // new surface: detect() returns Candidate::sort + Candidate::nonMaximaSuppression(im, candidates, overlap) of what it
     // found, computed on the device (pbd_set_nms) -- the callers' post-step, cells/detect.cpp:237-238.  Kept across
@@ -981,6 +987,23 @@ public:
         std::vector<int> nparts(candidates.size());
         for (size_t i = 0; i < candidates.size(); ++i) nparts[i] = (int)candidates[i].parts_.size();
         pbdbind::part_scores<HostTraits<T> >(h_, rec, (int)candidates.size(), nparts, &place, status, scores);
+    }
+    // the max-marginals of every part on frame `frame` of the last detect() / detectBatch() of images of im's size
+    // (pbd_max_marginals, include/pbd.h): per level the planes of every (part, type) pair,
+    // values[gm][y][x] = the score of the best configuration with that part of that type at (x, y).  They stay on the device for
+    // marginalPoses() until the next detect call or model update
+    void maxMarginals(const Image &im, std::vector<MarginalLevel> &levels, int frame = 0)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "maxMarginals() before distributeModel()");
+        pbdbind::max_marginals<HostTraits<T> >(h_, frame, im.rows, im.cols, planes_, levels);
+    }
+    // the poses decoded from the max-marginals held (pbd_marginal_poses): seeds holds {level, component, part, type or -1 for the
+    // best at the cell, x, y} per seed; status[i] = the pose's parts or -1 for a bad seed, `candidates` the good seeds' poses in
+    // seed order, each scored with its seed's max-marginal
+    void marginalPoses(const std::vector<int32_t> &seeds, std::vector<int32_t> &status, std::vector<Candidate> &candidates)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "marginalPoses() before distributeModel()");
+        pbdbind::marginal_poses<HostTraits<T> >(h_, seeds, status, candidates);
     }
     // a training QP of `capacity` examples of this detector's model layout (pbd_qp_create; Cpos = C * wpos, Cneg = C)
     QP qp(int capacity, double C = 0.002, double wpos = 2.0)

@@ -309,6 +309,24 @@ inline void hipPartScores(pbd_handle *h, std::vector<typename CvTraits<T>::Candi
     pbdbind::part_scores<CvTraits<T> >(h, rec, (int)candidates.size(), std::vector<int>(), NULL, status, scores);
 }
 
+// The max-marginals of every part on frame `frame` of the last hipDetect of an im_rows x im_cols image (pbd_max_marginals;
+// include/pbd.h "Max-marginals"): per level the planes of every (part, type) pair of the model, `planes` of them.  They stay on
+// the device for hipMarginalPoses until the next detect call
+template <typename T>
+inline void hipMaxMarginals(pbd_handle *h, int frame, int im_rows, int im_cols, int planes, std::vector<pbdbind::MarginalLevel> &levels)
+{
+    pbdbind::max_marginals<CvTraits<T> >(h, frame, im_rows, im_cols, planes, levels);
+}
+
+// The poses of seeds {level, component, part, type or -1, x, y} decoded from the max-marginals held (pbd_marginal_poses):
+// status[i] = the pose's parts or -1 for a bad seed; `candidates` receives the good seeds' poses in seed order
+template <typename T>
+inline void hipMarginalPoses(pbd_handle *h, const std::vector<int32_t> &seeds, std::vector<int32_t> &status,
+                             std::vector<typename CvTraits<T>::Candidate> &candidates)
+{
+    pbdbind::marginal_poses<CvTraits<T> >(h, seeds, status, candidates);
+}
+
 // A training positive's augmented copy on the device (pbd_augment_frames; include/pbd.h "Augmented positives"): dst becomes
 // rotate(mirror(im)), turned counter-clockwise by `degrees` (nearest neighbour, zero outside the source), of im's depth and
 // channel count (CV_8U, CV_16U, CV_32F or CV_64F; 1 or 3 channels).  The keypoints follow with pbd_augment_points.

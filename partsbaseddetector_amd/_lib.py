@@ -36,6 +36,9 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_qp_slots", "k_qp_norm", "k_qp_wraw", "k_qp_gather", "k_warp", "k_warp_emit",
            "k_ev_nms_select", "k_ev_nms_pairs", "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
            "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick", "k_grid_nms", "k_top_k", "k_depth_prune"]
+# the profile ids of pbd_max_marginals / pbd_marginal_poses*, which follow KERNELS' (PBD_K_MM_*: id = len(KERNELS) + index)
+KERNELS_MM = ["k_mm_dt_rows", "k_mm_dt_cols", "k_mm_messages", "k_mm_context", "k_mm_down", "k_mm_decode"]
+MM_VALUES, MM_DOWN, MM_PARENT_X, MM_PARENT_Y, MM_PARENT_K = 0, 1, 2, 3, 4   # pbd_get_marginals' selector
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
 # every symbol include/pbd.h declares (checked by tests/test_capi_symbols.py)
@@ -61,6 +64,7 @@ SYMBOLS = [
     "pbd_set_depth_prune", "pbd_bind_depth", "pbd_bind_depth_device", "pbd_depth_prune", "pbd_depth_prune_device",
     "pbd_augment_plan", "pbd_augment_points", "pbd_augment_frames", "pbd_augment_frames_device", "pbd_detect_latent_device",
     "pbd_part_scores", "pbd_part_scores_device", "pbd_score_placements", "pbd_score_placements_device",
+    "pbd_max_marginals", "pbd_get_marginals", "pbd_marginals_device", "pbd_marginal_poses", "pbd_marginal_poses_device",
 ]
 
 
@@ -296,6 +300,11 @@ def load():
     lib.pbd_examples_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for fn in (lib.pbd_part_scores, lib.pbd_part_scores_device, lib.pbd_score_placements, lib.pbd_score_placements_device):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pbd_max_marginals.argtypes = [C.c_void_p, C.c_int]
+    lib.pbd_get_marginals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.pbd_marginals_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.pbd_marginal_poses.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pbd_marginal_poses_device.argtypes = lib.pbd_marginal_poses.argtypes
     lib.pbd_warp_positives.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pbd_warp_positives_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,

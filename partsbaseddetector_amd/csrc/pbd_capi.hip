@@ -2530,7 +2530,8 @@ const char *pbd_kernel_name(int k)
                                              "k_qp_gather", "k_warp", "k_warp_emit", "k_ev_nms_select", "k_ev_nms_pairs",
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
                                              "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick",
-                                             "k_grid_nms", "k_top_k", "k_depth_prune"};
+                                             "k_grid_nms", "k_top_k", "k_depth_prune", "k_mm_dt_rows", "k_mm_dt_cols",
+                                             "k_mm_messages", "k_mm_context", "k_mm_down", "k_mm_decode"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

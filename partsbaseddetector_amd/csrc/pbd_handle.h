@@ -302,7 +302,9 @@ struct Resident {
     bool features = false, resp = false, dp = false;   // the stages held, all for `plan`
     bool c31_zero = false;           // the features were written by the HOG kernels (channel 31 = 0), not uploaded by the caller
     bool latent = false;             // pbd_detect_latent: the result lives in the handle's latent twin (pbd_examples* read it there)
-    void drop_conv() { resp = dp = false; }   // the filter bank changed
+    bool marginals = false;          // pbd_max_marginals: the planes of frame mm_frame are held for this result (whoever replaces
+    int mm_frame = 0;                // the record drops them with it)
+    void drop_conv() { resp = dp = marginals = false; }   // the filter bank changed
     void clear() { *this = Resident{}; }
 };
 
@@ -460,6 +462,14 @@ struct Handle : ErrCtx {
     DevTable<int> sc_anchors, sc_nmix;
     StagedTable sc_defw;
     DevBuf sc_ws, sc_rec, sc_out;
+    // pbd_max_marginals / pbd_marginal_poses*: the planes of one frame (values, down, parent pointers, messages), the scratch
+    // of a slice of mirrored transforms (context planes and the transforms' pointer planes; their values and envelope stacks are
+    // the dynamic program's own scratch), the call's job tables (one staged block), the model's types per part (uploaded on first
+    // use), the decode's scales, the host form's seeds and outputs
+    DevBuf mm_val, mm_down, mm_jx, mm_jy, mm_jk, mm_msg, mm_ctx, mm_six, mm_siy;
+    StagedTable mm_tab;
+    DevTable<int> mm_nmix;
+    DevBuf mm_scales, mm_in, mm_out, mm_place;
     // pbd_set_model_vector* / pbd_qp_apply: the model vector on the device (T; written by the first update, from then on the
     // source of every weight table), whether the host copy `mvec` is behind it (brought up to date on demand: sync_mvec), the
     // update's index tables (built on first use), the host form's vector, and the status block {refused, -, -, -, biasw, defw}

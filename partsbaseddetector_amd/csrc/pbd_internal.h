@@ -769,6 +769,58 @@ struct PartScoreParams {
 };
 void launch_part_scores(const PartScoreParams &p, bool f64, int step, hipStream_t s);   // step 0: placements, 1: scores
 
+// max-marginals of every part (pbd_max_marginals, pbd_marginal_poses*; pbd_kernels_marginals.hip).  The
+// planes of ONE frame: mm / down T, Jx / Jy int16, Jk int8, each [cell_per_frame * NJ] with a level's block [gm][y][x] from its
+// cell offset on; msg T [cell_per_frame * NS], one plane per pointer slot (part, parent type).
+struct MmSlot {                   // k_mm_messages: one part p of an upward depth group, its message to every parent type
+    int job_begin, nmix;          // p's first transform of the group (the group's dt scratch), its types
+    int slot, npar;               // the message planes written: slot + mq, mq < npar (the parent's types)
+    int bias_off[kMaxMix];        // biasid of (p, m)
+};
+struct MmCtx {                    // k_mm_context: one context plane (part p, parent type mq) of a slice
+    int filter;                   // the response plane of (q, mq)
+    int sib_begin, sib_end;       // range in the sibling list: message planes slot(c) + mq, c descending, c != p
+    int down;                     // the down plane of (q, mq): global (part, type) index
+    int out;                      // the context plane written (index within the slice)
+};
+struct MmRun {                    // k_mm_down: parent types [mq0, mq1) of part p, whose transforms are one slice's jobs from job0 on,
+    int job0, nmix;               // ordered (mq, m); p's types
+    int mq0, mq1, npar;           // npar: the parent's types; mq0 > 0 resumes from the planes an earlier slice left
+    int gm0;                      // global index of (p, 0): the planes written
+    int s_from_acc;               // S_p[m] is the accumulated plane gm0 + m, else the response plane s_filter[m]
+    int s_filter[kMaxMix];
+    int bias_off[kMaxMix];
+};
+// (a root is a run with npar == 0: down_0[m] = (T)biasw[bias_off[0]] for every m, -1 in its pointer planes)
+struct MmParams {
+    const LevelDesc *lv;
+    int nlevels;
+    int F, NS, NC, NM, NJ;        // as DpParams (NJ: the (part, type) pairs = planes of the outputs)
+    long long cell_per_frame, quad_per_frame;
+    int frame;                    // the frame of the resident result
+    int ptr8;                     // the resident pointer planes hold uint8
+    const void *resp; const void *acc;               // the resident result (R)
+    const uint8_t *Ik; const void *IxRaw, *IyRaw;    // the resident upward pointers (k_mm_decode)
+    const float *biasw;
+    // the call's scratch, frame 0: dt = the transforms' values [cells * JG], sIx / sIy their pointer planes [cells * SJ] (plane =
+    // job index), ctx = the context planes [cells * JG]
+    const void *dt; const void *sIx, *sIy; void *ctx;
+    int JG, SJ, NCTX;             // planes per cell block of dt, of sIx / sIy, of ctx in this launch
+    int max_mix;
+    // the frame's planes
+    void *msg, *mm, *down; int16_t *Jx, *Jy; int8_t *Jk;
+    const MmSlot *slots; const MmCtx *ctxs; const int *sibs; const MmRun *runs;
+    // k_mm_decode
+    const PartWalk *walk; const int *walk_off; const int *part_nmix;
+    const float *scales;
+    const int32_t *seeds; int nseeds, stride, max_parts, frame_offset;
+    int32_t *cand, *place, *status;
+};
+void launch_mm_messages(const MmParams &p, int nslots, bool f64, hipStream_t s);
+void launch_mm_context(const MmParams &p, int nctx, bool f64, hipStream_t s);
+void launch_mm_down(const MmParams &p, int nruns, bool f64, hipStream_t s);
+void launch_mm_decode(const MmParams &p, bool f64, hipStream_t s);
+
 // latent positives (pbd_detect_latent; pbd_kernels_examples.hip).  The responses are those of the latent bank: one plane per
 // (component, part, mixture) = global mixture index gm, so a mask belongs to its (component, part, mixture).
 struct LatentParams {

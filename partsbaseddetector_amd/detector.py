@@ -36,6 +36,7 @@ class Candidate:
     root: tuple = (0, 0)
     offset: tuple = (0, 0)   # (x, y) of the region the candidate was found in (detect_regions); boxes are region-relative
     mixtures: np.ndarray = None   # the type (mixture) of every part, set by PartsBasedDetector.partScores
+    place: np.ndarray = None      # the cell (x, y) of every part in its level's map, set by PartsBasedDetector.marginalPoses
 
     def score(self) -> float:  # Candidate.hpp:82
         return float(self.confidence[0]) if len(self.confidence) else float("-inf")
@@ -268,6 +269,7 @@ class Handle:
         self.stride = self.lib.pbd_candidate_stride(self.h)
         self.max_parts = (self.stride - 8) // 4         # part boxes a record holds (pbd_candidate_stride)
         self.nms_overlap = None                          # the overlap of set_nms (None: off)
+        self.level_shapes = None                         # (rows, cols) of every level of the last detect / min call (max-marginals)
         self._model_stale = False                        # set_model_vector* / set_thresh: `flat` is behind the handle
         self._thresh = None
 
@@ -563,6 +565,47 @@ class Handle:
         """pbd_score_placements_device: score_placements on device arrays; asynchronous on the handle's stream"""
         self.check(self.lib.pbd_score_placements_device(self.h, d_payload_ptr, capacity, frame_offset, d_place_ptr, d_status_ptr,
                                                         d_scores_ptr))
+
+    def max_marginals(self, frame: int = 0) -> None:
+        """pbd_max_marginals: the max-marginal planes of one frame of the resident dynamic-program result, kept on the device until
+        the next detect call, min(), model update or max_marginals; asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_max_marginals(self.h, int(frame)))
+
+    def get_marginals(self, level: int, what: int, rows: int, cols: int) -> np.ndarray:
+        """pbd_get_marginals: one level's block (NJ, rows, cols): T for _lib.MM_VALUES / MM_DOWN, int32 for MM_PARENT_X / _Y / _K"""
+        nj = int(self.flat.mix_offset[-1])
+        dst = np.empty((nj, rows, cols), self.dtype if what in (_lib.MM_VALUES, _lib.MM_DOWN) else np.int32)
+        self.check(self.lib.pbd_get_marginals(self.h, int(level), int(what), dst.ctypes.data, dst.nbytes))
+        return dst
+
+    def marginals_device(self, level: int) -> int:
+        """pbd_marginals_device: the device address of the level's mm block T[NJ][rows][cols]"""
+        p = C.c_void_p()
+        self.check(self.lib.pbd_marginals_device(self.h, int(level), C.byref(p)))
+        return int(p.value or 0)
+
+    def marginal_poses(self, seeds, scales=None, frame_offset: int = 0, fill=0):
+        """pbd_marginal_poses: (status (n,) int32, records (n, stride) int32, place (n, max_parts, 3) int32 x, y, type) of the seeds
+        (n, 6) int32 {level, component, part, type or -1, x, y}; scales None: the resident plan's own (after a detect call).  A bad
+        seed has status -1 and keeps `fill`, as the entries past a pose's parts do."""
+        sd = np.ascontiguousarray(seeds, np.int32).reshape(-1, 6)
+        n = len(sd)
+        status = np.full(n, fill, np.int32)
+        rec = np.full((n, self.stride), fill, np.int32)
+        place = np.full((n, self.max_parts, 3), fill, np.int32)
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self.check(self.lib.pbd_marginal_poses(self.h, n, ptr(sd), None if sc is None else _lib.ptr(sc, C.c_float), frame_offset,
+                                               ptr(rec), ptr(place), ptr(status)))
+        return status, rec, place
+
+    def marginal_poses_device(self, n: int, d_seeds_ptr: int, scales, frame_offset: int, d_cand_ptr: int, d_place_ptr,
+                              d_status_ptr: int) -> None:
+        """pbd_marginal_poses_device: marginal_poses on device arrays (d_place_ptr may be None); asynchronous on the handle's
+        stream"""
+        sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
+        self.check(self.lib.pbd_marginal_poses_device(self.h, int(n), d_seeds_ptr or None, None if sc is None else _lib.ptr(sc, C.c_float),
+                                                      frame_offset, d_cand_ptr or None, d_place_ptr or None, d_status_ptr or None))
 
     def detect_latent(self, frames, part_boxes, overlap: float, mixtures=None):
         """pbd_detect_latent: (records (nframes, stride) int32, found (nframes,) int32) -- per frame the best root whose parts
@@ -1103,7 +1146,7 @@ class Handle:
 
     def profile_read(self):
         out = {}
-        for k, name in enumerate(_lib.KERNELS):
+        for k, name in enumerate(_lib.KERNELS + _lib.KERNELS_MM):
             ms, n = C.c_double(), C.c_int()
             self.check(self.lib.pbd_profile_read(self.h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)
@@ -1220,6 +1263,7 @@ class DynamicProgram:
         self.hd.check(self.hd.lib.pbd_dp_min(self.hd.h, len(sc), _lib.ptr(rows, C.c_int), _lib.ptr(cols, C.c_int),
                                              _lib.ptr_array(sc), _lib.ptr_array(Ix), _lib.ptr_array(Iy),
                                              _lib.ptr_array(Ik), _lib.ptr_array(rootv), _lib.ptr_array(rooti)))
+        self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(rows, cols)]
         return Ix, Iy, Ik, rootv, rooti
 
     def argmin(self, scales: np.ndarray, capacity: Optional[int] = None) -> List[Candidate]:
@@ -1603,7 +1647,9 @@ class PartsBasedDetector:
         else:
             self.hd.check(self.hd.lib.pbd_detect_typed(self.hd.h, im.ctypes.data, rows, cols, cn, im.strides[0],
                                                        _lib.DEPTH_CODE[im.dtype], buf.ctypes.data, cap, C.byref(n)))
-        self.features_._scales = self.hd.plan(rows, cols)["scales"]
+        plan = self.hd.plan(rows, cols)
+        self.features_._scales = plan["scales"]
+        self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
         return self.hd.unpack_candidates(buf, n.value)
 
     def modelVector(self) -> np.ndarray:
@@ -1646,6 +1692,90 @@ class PartsBasedDetector:
             c.confidence = conf
             c.mixtures = place[i, :n, 2].copy()
         return place, scores
+
+    # ---- max-marginals (the rule: marginals.py) -------------------------------------------------------
+    def _level_shapes(self, shapes=None):
+        shapes = self.hd.level_shapes if shapes is None else [(int(r), int(c)) for r, c in shapes]
+        if shapes is None:
+            raise PbdError(-5, "max-marginals before detect() / detect_batch() / dp_.min(): the level shapes are not known")
+        return shapes
+
+    def maxMarginals(self, frame: int = 0, device: bool = False, shapes=None):
+        """the max-marginals of every part on one frame of the last detect() / detect_batch() / dp_.min() call (pbd_max_marginals):
+        per level an (NJ, H, W) array of T, plane gm = the (part, type) pair's global index, mm[gm][y][x] the score of the best
+        configuration with that part of that type at (x, y).  device=True: torch views of the resident block instead of copies,
+        valid until the next detect call, min(), model update or maxMarginals().  shapes: the levels' (rows, cols) when the
+        result was not computed through this object's detect / min."""
+        self._need()
+        shapes = self._level_shapes(shapes)
+        self.hd.max_marginals(frame)
+        if not device:
+            return [self.hd.get_marginals(l, _lib.MM_VALUES, r, c) for l, (r, c) in enumerate(shapes)]
+        return [self._device_view(self.hd.marginals_device(l), (int(self.hd.flat.mix_offset[-1]), r, c)) for l, (r, c) in enumerate(shapes)]
+
+    def _device_view(self, ptr: int, shape):
+        """a torch tensor over device memory the handle owns (nothing is copied)"""
+        import torch
+        dt = np.dtype(self.hd.dtype)
+
+        class View:
+            __cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": dt.str, "data": (int(ptr), False), "version": 2,
+                                        "strides": None}
+        if 0 in shape or not ptr:
+            return torch.empty(tuple(shape), dtype=torch.float32 if dt == np.float32 else torch.float64, device=f"cuda:{self._kw['device']}")
+        return torch.as_tensor(View(), device=f"cuda:{self._kw['device']}")
+
+    def marginalPoses(self, seeds, frame_offset: int = 0, scales=None) -> List[Optional[Candidate]]:
+        """the poses of seeds (n, 6) int32 {level, component, part, type or -1 for the best at the cell, x, y} decoded from the
+        max-marginals held (pbd_marginal_poses): per seed a Candidate whose score is the seed's max-marginal, `mixtures` the
+        parts' types and `place` their cells (x, y), or None for a bad seed.  scales: as DynamicProgram.argmin takes them, needed
+        after dp_.min(); None: the detect call's own."""
+        self._need()
+        status, rec, place = self.hd.marginal_poses(seeds, scales, frame_offset)
+        out: List[Optional[Candidate]] = []
+        for i, st in enumerate(status):
+            if st <= 0:
+                out.append(None)
+                continue
+            c = self.hd.unpack_candidates(rec[i], 1)[0]
+            c.mixtures = place[i, :st, 2].copy()
+            c.place = place[i, :st, :2].copy()
+            out.append(c)
+        return out
+
+    def nBestPoses(self, part: int, k: int, sz: int = 2, frame: int = 0, component: int = 0, scales=None, shapes=None) -> List[Candidate]:
+        """up to k poses that differ at `part` (of `component`): per level the part's max-marginal planes are reduced over its types
+        on the device, the grid maxima of the reduced planes within sz cells are kept (pbd_grid_nms_device), the k best of them
+        over all levels selected (pbd_top_k_cells_device), and those cells decoded (type -1: the best at the cell).  Sorted by
+        score, ties in (level, y, x) order."""
+        self._need()
+        import torch
+        flat = self.hd.flat
+        if not 0 <= component < flat.ncomponents or not 0 <= part < int(flat.part_offset[component + 1]) - int(flat.part_offset[component]):
+            raise PbdError(-1, f"part {part} of component {component} is not in the model")
+        shapes = self._level_shapes(shapes)
+        mm = self.maxMarginals(frame, device=True, shapes=shapes)
+        gp = int(flat.part_offset[component]) + part
+        g0, g1 = int(flat.mix_offset[gp]), int(flat.mix_offset[gp + 1])
+        dev = f"cuda:{self._kw['device']}"
+        with torch.cuda.stream(torch.cuda.ExternalStream(self.hd.stream_ptr(), device=dev)):
+            red = torch.cat([m[g0:g1].amax(0).reshape(-1) for m in mm]) if mm else torch.zeros(0, device=dev)
+            red = red.contiguous()
+            grid = torch.zeros(red.numel(), dtype=torch.uint8, device=dev)
+            keep = torch.zeros(red.numel(), dtype=torch.uint8, device=dev)
+            real = _lib.REAL_F32 if self.hd.dtype == np.float32 else _lib.REAL_F64
+            self.hd.grid_nms_device([r for r, _ in shapes], [c for _, c in shapes], real, red.data_ptr(), None, sz, grid.data_ptr())
+            self.hd.top_k_cells_device([red.numel()], real, red.data_ptr(), grid.data_ptr(), k, keep.data_ptr())
+            idx = torch.nonzero(keep).reshape(-1).cpu().numpy()
+        off = np.concatenate([[0], np.cumsum([r * c for r, c in shapes])])
+        seeds = []
+        for i in idx:
+            l = int(np.searchsorted(off, i, side="right")) - 1
+            y, x = divmod(int(i - off[l]), shapes[l][1])
+            seeds.append((l, component, part, -1, x, y))
+        poses = [p for p in self.marginalPoses(np.asarray(seeds, np.int32).reshape(-1, 6), 0, scales) if p is not None]
+        poses.sort(key=lambda c: -c.score())
+        return poses
 
     def scorePlacements(self, candidates, place):
         """the same four values at placements the caller gives (pbd_score_placements): place (n, max_parts, 3) x, y, mixture,
@@ -1862,6 +1992,8 @@ class PartsBasedDetector:
         self._bind(depths)
         self.hd.check(self.hd.lib.pbd_detect_batch(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn,
                                                    buf.ctypes.data, cap, C.byref(n)))
+        plan = self.hd.plan(rows, cols)
+        self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
         return self.hd.unpack_candidates(buf, n.value)
 
     def detect_frames(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None, depths=None) -> List[Candidate]:
