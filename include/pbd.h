@@ -893,7 +893,10 @@ int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int cap
  *             C_p[mq] += down_q[mq]
  *   mirrored  R_p[m][mq] = dt(C_p[mq]; -w0, +w1, -w2, +w3; -ox, -oy) with the weights and anchor of (p, m): the upward quadratic
  *             seen from the child (the negated linear coefficients: an upward -0.0 becomes +0.0), the transform otherwise the
- *             upward one, the NaN read-out rule of pbd_dp_min included
+ *             upward one, the NaN read-out rule of pbd_dp_min included ("Non-finite scores", item 3: +-Inf and NaN responses are
+ *             accepted; a context plane may hold NaN the upward pass never saw, from -Inf + +Inf; NaN in mm and down stand at the
+ *             places of the rule run with that read-out, sign and payload unspecified; the pointer planes are the rule's.  With
+ *             K_q > 1 a NaN never wins the reduction, so down is -inf and Jk 0 where every R + bias is NaN or -inf)
  *   down      down_p[m] = reduceMax over mq of (R_p[m][mq] + bias(p, m)[mq]), the same first-wins rule and K_q == 1 copy;
  *             Jk_p[m] the winning mq; (Jx_p[m], Jy_p[m]) the parent's cell, composed in arg-max order from the winner's pointer
  *             planes: the columns pass's pointer first, then the rows pass's at that row
@@ -915,10 +918,12 @@ int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int cap
  * pbd_marginals_device(h, level, &d): the device pointer of the level's mm block T[NJ][H][W] (for pbd_grid_nms_device /
  *   pbd_top_k_cells_device), valid as long as the marginals are.
  * pbd_marginal_poses(h, n, seeds, scales, frame_offset, cand, place, status): seeds = int32[n][6] {level, component, part, type
- *   or -1 (the first type with the largest mm at the cell), x, y}.  The pose of a seed: climb from the seed through Jk / Jx / Jy to
+ *   or -1 (the first type with the largest mm at the cell; reduceMax's rule, so type 0 where no mm is above -inf: every one
+ *   NaN or -inf), x, y}.  The pose of a seed: climb from the seed through Jk / Jx / Jy to
  *   the root, which fixes every part on that path; every other part, in index order, takes the arg-max placement of the upward
  *   pointers from its parent's (whatever pbd_set_walk says: the marginal was taken there).  cand = int32[n][stride] records:
- *   frame (that of pbd_max_marginals) + frame_offset, component, level, the decoded root's x, y, (float)mm of the seed, parts, the
+ *   frame (that of pbd_max_marginals) + frame_offset, component, level, the decoded root's x, y, (float)mm of the seed (of the
+ *   type decoded for a type of -1: a NaN or -inf where no type won; a NaN's sign and payload are unspecified), parts, the
  *   root's type in word 7, then the part boxes at the level's scale; scales = float[levels] as for pbd_dp_argmin, or NULL for the
  *   plan's own (after pbd_detect*; NULL after pbd_dp_min is PBD_ERR_INVALID).  place = int32[n][max_parts][3] {x, y, type} or
  *   NULL.  status = int32[n]: the parts of the pose, or -1 for a bad seed (a cell outside the map, a part, type, component or

@@ -231,11 +231,10 @@ __global__ __launch_bounds__(kMmDecodeThreads) void k_mm_decode(MmParams p)
         const size_t blk = (size_t)d.cell_off * p.NJ;
         const R *mm = static_cast<const R *>(p.mm) + blk;
         const size_t cell0 = (size_t)y0 * d.cols + x0;
-        int bi = m;
-        R score;
-        if (m < 0) score = reduce_max<R>(p.part_nmix[p.walk_off[c] + part], [&](int t) { return mm[(size_t)(walk[part].mix0 + t) * HW + cell0]; }, bi);
-        else score = mm[(size_t)(walk[part].mix0 + m) * HW + cell0];
-        m = bi;
+        // type -1: the first type with the largest mm, type 0 where none wins (every mm NaN or -inf).  The score is the mm of the
+        // type decoded, not the running maximum: where no type wins that maximum is still the -inf the search started from
+        if (m < 0) reduce_max<R>(p.part_nmix[p.walk_off[c] + part], [&](int t) { return mm[(size_t)(walk[part].mix0 + t) * HW + cell0]; }, m);
+        const R score = mm[(size_t)(walk[part].mix0 + m) * HW + cell0];
         int32_t *place = p.place + (size_t)i * p.max_parts * 3;
         for (int q = 0; q < nparts; ++q) place[3 * q + 2] = -1;
         // the climb: every part between the seed and the root takes the cell and type the marginal was taken at

@@ -106,27 +106,50 @@ def walk(flat, c: int, x: int, y: int, Ix, Iy, Ik, rooti, argmax: bool = False) 
 _walk = walk   # for the functions below whose `walk` argument names the mode
 
 
-def dt_raw(oracle, score: np.ndarray, ax, bx, ay, by, osx: int, osy: int):
-    """(out, IxRaw, IyRaw) of one distance transform: the row pass as 1 x N calls of oracle.dt (osy = 0: the length-1 column
-    pass is the identity a 0 + b 0 + src), then the column pass as M x 1 calls on the row pass's output (osx = 0)"""
+def dt_raw(oracle, score: np.ndarray, ax, bx, ay, by, osx: int, osy: int, readout: str = "reference", nan_isect=None):
+    """(out, IxRaw, IyRaw) of one distance transform: the row pass as 1 x N transforms of the oracle (osy = 0: the length-1
+    column pass is the identity a 0 + b 0 + src), then the column pass as M x 1 transforms of the row pass's output (osx = 0).
+    They are what M + N calls of oracle.dt on those lines return, made on the lines in place through the oracle's library under
+    one setting of the rule, so that a plane costs two passes and not M + N trips through oracle.dt.  readout is the oracle's
+    read-out rule ("reference" or "max": include/pbd.h, pbd_dp_min, "Non-finite scores"); nan_isect, a one-element list, has
+    the NaN intersections the oracle counted in these transforms added to it."""
+    import ctypes as C
+    lib = oracle.lib()
+    dtype = score.dtype
+    score = np.ascontiguousarray(score)
     M, N = score.shape
-    tmp = np.empty_like(score)
+    fn = lib.pbdo_dt_f32 if dtype == np.float32 else lib.pbdo_dt_f64
+    size = score.itemsize
+    a = [C.c_double(v) for v in (ax, bx, ay, by)]
+    tmp = np.empty((M, N), dtype)
     IxRaw = np.empty((M, N), np.int32)
-    for m in range(M):
-        tmp[m:m + 1], IxRaw[m:m + 1], _ = oracle.dt(score[m:m + 1], ax, bx, ay, by, osx, 0)
-    out = np.empty_like(score)
-    IyRaw = np.empty((M, N), np.int32)
-    for n in range(N):
-        out[:, n:n + 1], _, IyRaw[:, n:n + 1] = oracle.dt(tmp[:, n:n + 1], ax, bx, ay, by, 0, osy)
-    return out, IxRaw, IyRaw
+    unused = np.empty(max(M, N), np.int32)
+    outT = np.empty((N, M), dtype)
+    IyRawT = np.empty((N, M), np.int32)
+    vp, up = C.c_void_p, unused.ctypes.data
+    lib.pbdo_set_dt_readout(oracle.READOUTS[readout])
+    lib.pbdo_nan_isect_reset()
+    try:
+        s0, t0, x0 = score.ctypes.data, tmp.ctypes.data, IxRaw.ctypes.data
+        for m in range(M):
+            fn(vp(s0 + m * N * size), 1, N, a[0], a[1], a[2], a[3], osx, 0, vp(t0 + m * N * size), vp(x0 + m * N * 4), vp(up))
+        tmpT = np.ascontiguousarray(tmp.T)
+        s0, t0, y0 = tmpT.ctypes.data, outT.ctypes.data, IyRawT.ctypes.data
+        for n in range(N):
+            fn(vp(s0 + n * M * size), M, 1, a[0], a[1], a[2], a[3], 0, osy, vp(t0 + n * M * size), vp(up), vp(y0 + n * M * 4))
+        if nan_isect is not None:
+            nan_isect[0] += oracle.nan_isect()
+    finally:
+        lib.pbdo_set_dt_readout(oracle.READOUTS["reference"])
+    return np.ascontiguousarray(outT.T), IxRaw, np.ascontiguousarray(IyRawT.T)
 
 
-def raw_maps(flat, c: int, resp: np.ndarray):
+def raw_maps(flat, c: int, resp: np.ndarray, readout: str = "reference"):
     """DynamicProgram::min of component c on one level's responses (nfilters, H, W) of T, restated in numpy
     (src/DynamicProgram.cpp:83-171): parts in descending order, a distance transform per child mixture (dt_raw), reduceMax
     over the child's mixtures with strict > from -inf (one mixture: a copy), and parent += max into the parent's plane, kept per
     filter id as the reference keeps it.  Returns IxRaw, IyRaw (totmix, H, W: one plane per global mixture, the two passes' own
-    pointers), Ik (nslots, H, W), rootv, rooti"""
+    pointers), Ik (nslots, H, W), rootv, rooti.  readout: the transform's read-out rule, as dt_raw takes it"""
     from oracle import oracle
     T = resp.dtype.type
     _, H, W = resp.shape
@@ -144,7 +167,7 @@ def raw_maps(flat, c: int, resp: np.ndarray):
             f, d = int(flat.filterid[gm]), int(flat.defid[gm])
             w = [float(v) for v in flat.defw[d]]
             o, IxRaw[gm], IyRaw[gm] = dt_raw(oracle, np.ascontiguousarray(nc.get(f, resp[f])), -w[0], -w[1], -w[2], -w[3],
-                                             int(flat.anchors[d][0]), int(flat.anchors[d][1]))
+                                             int(flat.anchors[d][0]), int(flat.anchors[d][1]), readout=readout)
             sc.append(o)
         for pm in range(int(flat.mix_offset[gpar + 1]) - int(flat.mix_offset[gpar])):
             fp = int(flat.filterid[int(flat.mix_offset[gpar]) + pm])

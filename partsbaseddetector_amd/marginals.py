@@ -35,10 +35,17 @@ def reduce_max(values: Sequence[np.ndarray], first_wins: bool = True):
 
 
 def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "descending", skip_self: bool = True,
-                  mirror_linear: bool = True, mirror_anchor: bool = True, first_wins: bool = True):
+                  mirror_linear: bool = True, mirror_anchor: bool = True, first_wins: bool = True, readout: str = "reference",
+                  nan_isect=None, contexts=None):
     """(mm, down, Jx, Jy, Jk) of component c on one level's responses resp (nfilters, H, W) of T.  mm and down are (NJ, H, W) of T,
     Jx / Jy / Jk (NJ, H, W) int32 with NJ the (part, type) pairs of the MODEL; planes of other components stay 0 (values) and the
     root's pointer planes are -1.
+
+    readout names the read-out rule of every transform, upward and mirrored ("reference" or "max", as oracle.dt takes it).  On
+    finite inputs the two agree; for inputs with +-Inf or NaN the yardstick of pbd_max_marginals is the rule run with "max", the
+    library's decision where a NaN intersection forms (include/pbd.h, pbd_dp_min, "Non-finite scores", item 3).  nan_isect, a
+    dict, receives the NaN intersections the oracle counted: "upward" over the transforms D_p[m], "mirrored" over R_p[m][mq];
+    contexts, a dict, receives the context planes C_p[mq] under the key (p, mq), the inputs of the mirrored transforms.
 
     The keyword arguments are NOT part of the rule: each names one choice the rule makes (the siblings' messages added in descending
     index order, a part's own message left out of its context, the linear coefficients negated, the anchor negated, the first of
@@ -54,7 +61,8 @@ def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "desce
     Jx = np.zeros((NJ, H, W), np.int32)
     Jy = np.zeros((NJ, H, W), np.int32)
     Jk = np.zeros((NJ, H, W), np.int32)
-    planes = PS.accumulated(flat, c, resp)[5]        # S_p[m]
+    planes = PS.accumulated(flat, c, resp, readout=readout)[5]        # S_p[m]
+    n_up, n_mir = [0], [0]
     gms = lambda p: range(int(flat.mix_offset[p0 + p]), int(flat.mix_offset[p0 + p + 1]))
     parent = [int(flat.parentid[p0 + p]) for p in range(n)]
     children = [[q for q in range(n - 1, 0, -1) if parent[q] == p] for p in range(n)]      # descending index
@@ -68,7 +76,7 @@ def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "desce
             d = int(flat.defid[gm])
             w = [float(v) for v in flat.defw[d]]
             D.append(E.dt_raw(oracle, np.ascontiguousarray(planes[p][m]), -w[0], -w[1], -w[2], -w[3], int(flat.anchors[d][0]),
-                              int(flat.anchors[d][1]))[0])
+                              int(flat.anchors[d][1]), readout=readout, nan_isect=n_up)[0])
         for mq in range(len(gms(parent[p]))):
             M[p, mq] = reduce_max([D[m] + bias(gm, mq) for m, gm in enumerate(gms(p))])[0]
 
@@ -92,6 +100,8 @@ def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "desce
                     continue
                 C = C + M[s, mq]
             ctx.append(C + down[gq])
+            if contexts is not None:
+                contexts[p, mq] = ctx[-1]
         for m, gm in enumerate(gms(p)):
             d = int(flat.defid[gm])
             w = [float(v) for v in flat.defw[d]]
@@ -100,7 +110,8 @@ def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "desce
             sa = -1 if mirror_anchor else 1
             R, px, py = [], [], []
             for mq in range(len(ctx)):
-                o, ix, iy = E.dt_raw(oracle, np.ascontiguousarray(ctx[mq]), -w[0], sl * -w[1], -w[2], sl * -w[3], sa * ox, sa * oy)
+                o, ix, iy = E.dt_raw(oracle, np.ascontiguousarray(ctx[mq]), -w[0], sl * -w[1], -w[2], sl * -w[3], sa * ox, sa * oy,
+                                     readout=readout, nan_isect=n_mir)
                 R.append(o + bias(gm, mq))
                 py.append(iy)                                  # the columns pass's pointer first,
                 px.append(ix[iy, cols])                        # then the rows pass's at that row
@@ -108,6 +119,9 @@ def max_marginals(flat, c: int, resp: np.ndarray, *, sibling_order: str = "desce
             Jx[gm] = np.take_along_axis(np.stack(px), Jk[gm][None], 0)[0]
             Jy[gm] = np.take_along_axis(np.stack(py), Jk[gm][None], 0)[0]
             mm[gm] = planes[p][m] + down[gm]
+    if nan_isect is not None:
+        nan_isect["upward"] = nan_isect.get("upward", 0) + n_up[0]
+        nan_isect["mirrored"] = nan_isect.get("mirrored", 0) + n_mir[0]
     return mm, down, Jx, Jy, Jk
 
 
@@ -115,7 +129,8 @@ def decode(flat, c: int, level: int, part: int, mtype: int, x: int, y: int, mm, 
            frame_offset: int = 0, dtype=np.float32) -> Tuple[List[Tuple[int, int, int]], np.ndarray]:
     """(placement [(x, y, type)] of every part, record int32[stride]) of the seed (level, c, part, mtype or -1, x, y): the climb
     through Jk / Jx / Jy to the root fixes the parts on that path; every other part, in index order, takes examples.walk's arg-max
-    step from its parent's placement on the upward maps IxRaw / IyRaw / Ik of examples.raw_maps."""
+    step from its parent's placement on the upward maps IxRaw / IyRaw / Ik of examples.raw_maps.  Type -1 is reduce_max's choice:
+    type 0 where no mm is above -inf (every one NaN or -inf); the score is the mm of the type decoded."""
     p0 = int(flat.part_offset[c])
     n = int(flat.part_offset[c + 1]) - p0
     g = lambda p: int(flat.mix_offset[p0 + p])

@@ -71,11 +71,12 @@ def part_scores(flat, resp: np.ndarray, c: int, placement, dtype=np.float32, *, 
     return np.array([[app[p], msg[p], bias[p], total[p]] for p in range(n)], dtype)
 
 
-def accumulated(flat, c: int, resp: np.ndarray):
+def accumulated(flat, c: int, resp: np.ndarray, readout: str = "reference"):
     """DynamicProgram::min of component c on one level's responses, as examples.raw_maps restates it, which also keeps what
     raw_maps drops: returns (IxRaw, IyRaw, Ik, rootv, rooti, planes) with planes[p][m] the (H, W) plane part p's mixture m had
     accumulated when it was consumed (a child: when its transform ran; the root: when the root scores were taken).  The planes
-    are kept per filter id as the reference keeps them, so parts that share an inner filter id see each other's messages."""
+    are kept per filter id as the reference keeps them, so parts that share an inner filter id see each other's messages.
+    readout: the transform's read-out rule, as examples.dt_raw takes it."""
     from oracle import oracle
     T = resp.dtype.type
     _, H, W = resp.shape
@@ -95,7 +96,7 @@ def accumulated(flat, c: int, resp: np.ndarray):
             src = np.ascontiguousarray(nc.get(f, resp[f]))
             planes[gp - p0].append(np.array(src, copy=True))
             o, IxRaw[gm], IyRaw[gm] = E.dt_raw(oracle, src, -w[0], -w[1], -w[2], -w[3], int(flat.anchors[d][0]),
-                                               int(flat.anchors[d][1]))
+                                               int(flat.anchors[d][1]), readout=readout)
             sc.append(o)
         for pm in range(int(flat.mix_offset[gpar + 1]) - int(flat.mix_offset[gpar])):
             fp = int(flat.filterid[int(flat.mix_offset[gpar]) + pm])

@@ -2,6 +2,15 @@
 of values each.  The inputs are response planes handed to pbd_dp_min / marginals.max_marginals, so a case needs no image and its
 levels can have any shape.
 
+Hard cases (test_marginals_hard_cpu.py, test_gpu_marginals_hard.py).  "wide8" and "wide16" have parts of up to 8 and 16 types:
+the two widest instantiations of k_mm_messages, reductions over more than 4 parent types, parent types of index 8 and above, and
+for "wide16" mirrored transforms cut into one slice per parent type (part 1: 16 x 9 transforms, a slice holds 20) and into slices
+of four parent types (part 2: 5 x 16).  The non-finite response sets give "tree" (dense values), "slices" and "wide16" (dyadic
+values) the planes of tests/dt_hard_planes.py with +-Inf and NaN cells (every kind of NONFINITE_F and NONFINITE_N but f16_sat:
+marginals are refused on fp16-resident responses) on the two level sets of tests/test_gpu_dt_nonfinite.py, base kinds unchanged:
+test_marginals_hard_cpu.py shows that mirrored context planes built from them do spill the deepest ring ("i16") and do pop a
+whole cooperative window ("u8").  Their yardstick is the rule with the "max" read-out.
+
 Dyadic values: responses on the integer grid, deformation weights in quarters (linear terms of both signs and exactly 0), integer
 biases, many of them equal so that ties occur; every sum the rule makes is then exact in float32 and float64.  Dense values:
 random floats."""
@@ -11,6 +20,8 @@ import functools
 
 import numpy as np
 
+import dt_hard_planes as H
+from test_gpu_dt_nonfinite import LEVELS as NF_LEVELS
 from partsbaseddetector_amd import examples as E
 from partsbaseddetector_amd import marginals as MG
 from partsbaseddetector_amd.model import Model
@@ -32,9 +43,21 @@ MODELS = {
     "two": [dict(pa=[0, 1], K=[2, 2], ks=[5, 5]), dict(pa=[0, 1, 1, 3], K=[1, 3, 2, 2], ks=[3, 5, 5, 3])],
     # part 1 alone at its depth: the scratch holds 3 transforms, its mirrored ones are 12, so every parent type is a slice of its own
     "slices": [dict(pa=[0, 1, 2], K=[4, 3, 2], ks=[5, 5, 5])],
+    # up to 8 types: k_mm_messages<R, 8>, reductions over 8 parent types
+    "wide8": [dict(pa=[0, 1, 1], K=[8, 5, 6], ks=[5, 5, 5])],
+    # 16 types under a parent of 9, 5 under a parent of 16: k_mm_messages<R, 16>, Jk up to 15.  The scratch holds 20 transforms:
+    # every parent type of part 1 is a slice of its own, parts 3 and 4 fill the slices' ends, part 2 resumes every 4 parent types.
+    # Parts 3 and 4 give part 1 two siblings, so that the order of their messages matters.
+    "wide16": [dict(pa=[0, 1, 2, 1, 1], K=[9, 16, 5, 2, 2], ks=[5, 5, 5, 5, 5])],
 }
 CASES = [(m, ls) for m in ("chain", "star", "tree", "two", "slices") for ls in ("A", "B")] + [("chain1", "A")]
 VALUES = ("dyadic", "dense")
+WIDE_CASES = [("wide8", "A"), ("wide16", "B")]          # not in CASES: the existing tests' parametrisation stays as it is
+
+# the non-finite cases: (model, its value set); every kind on both level sets
+NF_MODELS = [("tree", "dense"), ("slices", "dyadic"), ("wide16", "dyadic")]
+NF_KINDS = tuple(k for k in H.NONFINITE_F + H.NONFINITE_N if k != "f16_sat")
+NF_SETS = tuple(NF_LEVELS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,10 +187,12 @@ def seeds_of(name: str, levels: str, values: str, dtype: str):
 
 def decode_all(name: str, levels: str, values: str, dtype: str, seeds, frame_offset: int = 0, fill: int = 0):
     """(status, records, place) marginals.decode gives for the seeds, as Handle.marginal_poses returns them"""
-    flat = model(name, values).flatten()
-    ys = yardstick(name, levels, values, dtype)
-    shapes = LEVEL_SETS[levels]
-    sc = scales(levels)
+    return decode_seeds(model(name, values).flatten(), yardstick(name, levels, values, dtype), LEVEL_SETS[levels], scales(levels),
+                        dtype, seeds, frame_offset, fill)
+
+
+def decode_seeds(flat, ys, shapes, sc, dtype: str, seeds, frame_offset: int = 0, fill: int = 0):
+    """decode_all on a yardstick ys (per level, per component, the dict of yardstick()) of levels of the given shapes and scales"""
     n, mp = len(seeds), int(flat.max_parts)
     status = np.full(n, fill, np.int32)
     rec = np.full((n, 8 + 4 * mp), fill, np.int32)
@@ -185,3 +210,84 @@ def decode_all(name: str, levels: str, values: str, dtype: str, seeds, frame_off
         rec[i, :8 + 4 * k] = r[:8 + 4 * k]
         place[i, :k] = np.asarray(pl, np.int32)
     return status, rec, place
+
+
+# ---- the non-finite cases ----------------------------------------------------------------------------------------------------
+def nf_values(name: str) -> str:
+    return dict(NF_MODELS)[name]
+
+
+@functools.lru_cache(maxsize=None)
+def nf_responses(name: str, kind: str, set_name: str, dtype: str):
+    """per level (nfilters, H, W) of dtype: dt_hard_planes.nonfinite_scores on the level set, seeded as the DT suite seeds it"""
+    flat = model(name, nf_values(name)).flatten()
+    seed = 1000 * (H.NONFINITE_F + H.NONFINITE_N).index(kind) + {"u8": 11, "i16": 22}[set_name] + sum(map(ord, name))
+    return H.nonfinite_scores(flat, kind, NF_LEVELS[set_name], seed, np.dtype(dtype).type)
+
+
+def nf_shapes(set_name: str):
+    return [(h, w) for h, w, _ in NF_LEVELS[set_name]]
+
+
+def nf_scales(set_name: str) -> np.ndarray:
+    return np.array([1.0 + 0.37 * l for l in range(len(NF_LEVELS[set_name]))], np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def nf_yardstick(name: str, kind: str, set_name: str, dtype: str, readout: str = "max"):
+    """(per level, per component the dict of yardstick(); NaN intersections {"upward", "mirrored"} of all levels together) under
+    the given read-out; computed once, never written to"""
+    flat = model(name, nf_values(name)).flatten()
+    out, nans = [], {}
+    for resp in nf_responses(name, kind, set_name, dtype):
+        per_c = []
+        for c in range(flat.ncomponents):
+            mm, down, Jx, Jy, Jk = MG.max_marginals(flat, c, resp, readout=readout, nan_isect=nans)
+            IxRaw, IyRaw, Ik, rootv, rooti = E.raw_maps(flat, c, resp, readout=readout)
+            d = dict(mm=mm, down=down, Jx=Jx, Jy=Jy, Jk=Jk, IxRaw=IxRaw, IyRaw=IyRaw, Ik=Ik, rootv=rootv, rooti=rooti)
+            for v in d.values():
+                v.setflags(write=False)
+            per_c.append(d)
+        out.append(per_c)
+    return out, nans
+
+
+def nf_cells(name: str, kind: str, set_name: str, dtype: str):
+    """cells of the "max" yardstick a type -1 seed has to get right: ({"nan": seeds, "neginf": seeds, "finite": seeds}); "nan":
+    for each part the first cell (level, then raster order) where the mm of every type is NaN, "neginf": where every one is -Inf,
+    "finite": the cell of its largest finite mm of the first level that has one.  One-component models."""
+    flat = model(name, nf_values(name)).flatten()
+    ys = nf_yardstick(name, kind, set_name, dtype)[0]
+    out = {"nan": [], "neginf": [], "finite": []}
+    for p in range(int(flat.part_offset[1])):
+        pl = list(part_planes(flat, 0, p))
+        found = set()
+        for l, per_c in enumerate(ys):
+            blk = per_c[0]["mm"][pl[0]:pl[-1] + 1]
+            tests = {"nan": np.isnan(blk).all(0), "neginf": np.isneginf(blk).all(0), "finite": np.isfinite(blk).any(0)}
+            for key, t in tests.items():
+                if key in found or not t.any():
+                    continue
+                found.add(key)
+                if key == "finite":
+                    b = np.where(np.isfinite(blk), blk, -np.inf)
+                    _, y, x = np.unravel_index(int(np.argmax(b)), b.shape)
+                else:
+                    y, x = np.argwhere(t)[0]
+                out[key].append((l, 0, p, -1, int(x), int(y)))
+    return out
+
+
+def nf_seeds(name: str, kind: str, set_name: str, dtype: str):
+    """the decode's seeds of a non-finite case: the corners of the first level for the last part, nf_cells' (every part's best
+    finite cell, all-NaN and all -Inf cells), all with type -1, the best finite cells again with type 0, and bad seeds in between"""
+    flat = model(name, nf_values(name)).flatten()
+    cells = nf_cells(name, kind, set_name, dtype)
+    H0, W0 = nf_shapes(set_name)[0]
+    last = int(flat.part_offset[1]) - 1
+    seeds = [(0, 0, last, -1, x, y) for x, y in ((0, 0), (W0 - 1, 0), (0, H0 - 1), (W0 - 1, H0 - 1))]
+    seeds += cells["finite"] + cells["nan"] + cells["neginf"] + [(l, c, p, 0, x, y) for l, c, p, _, x, y in cells["finite"]]
+    nl = len(NF_LEVELS[set_name])
+    bad = [(0, 0, 0, 0, W0, 0), (0, 0, 0, 0, 0, H0), (0, 0, 0, 0, -1, 0), (nl, 0, 0, 0, 0, 0), (-1, 0, 0, 0, 0, 0), (0, flat.ncomponents, 0, 0, 0, 0),
+           (0, 0, 99, 0, 0, 0), (0, 0, 0, 16, 0, 0), (0, 0, 0, -2, 0, 0)]
+    return np.asarray(seeds[:3] + bad[:4] + seeds[3:] + bad[4:], np.int32)
