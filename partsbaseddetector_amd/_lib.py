@@ -111,6 +111,11 @@ class CDepthPruneCfg(C.Structure):
     _fields_ = [("fx", C.c_float), ("width", C.c_float), ("tol", C.c_float)]
 
 
+def prune_cfg(fx: float, width: float, tol: float):
+    """(const pbd_depth_prune_cfg *) of the three values"""
+    return C.byref(CDepthPruneCfg(float(fx), float(width), float(tol)))
+
+
 class CPinhole(C.Structure):
     """pbd_pinhole: one frame's pinhole intrinsics"""
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "tx", "ty")]
@@ -160,6 +165,81 @@ def frame_array(descs):
     for i, (p, r, c, st) in enumerate(descs):
         arr[i].data, arr[i].rows, arr[i].cols, arr[i].stride_bytes = p, r, c, st
     return arr
+
+
+# ---- marshalling rules of the Python binding, each stated once ------------------------------------------------------------
+def opt_ptr(a):
+    """the address of an array's data, or None for an empty array"""
+    return a.ctypes.data if a.size else None
+
+
+def real_code(dtype) -> int:
+    """REAL_F32 / REAL_F64 of a float dtype"""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise PbdError(-1, f"dtype {dt}: float32 or float64")
+    return REAL_F32 if dt == np.float32 else REAL_F64
+
+
+def shape_arrays(im_shapes):
+    """(rows, cols, their POINTER(c_int)s) of im_shapes[f] = (rows, cols), as int32 arrays; a pointer keeps its array alive"""
+    ir = np.array([int(s[0]) for s in im_shapes], np.int32)
+    ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+    return ir, ic, ptr(ir, C.c_int), ptr(ic, C.c_int)
+
+
+def depth_frames(depths):
+    """(arrays kept alive, pbd_frame[], depth code) of 2-D depth images of one dtype, rows of any pitch"""
+    dt = np.dtype(depths[0].dtype)
+    if dt not in DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
+        raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
+    ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
+    return ds, frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds]), DEPTH_CODE[dt]
+
+
+def hwc(f):
+    """rows x cols x channels of an image given as rows x cols or rows x cols x channels (a view)"""
+    return f if f.ndim == 3 else f[:, :, None]
+
+
+def image_frames(frames, bad_dtype: int = -1):
+    """(arrays kept alive, pbd_frame[], channels, depth code) of HW or HWC images of any sizes, of one dtype of DEPTH_CODE's four
+    (another one: PbdError(bad_dtype)) and one channel count.  A frame whose pixels are contiguous -- channels `itemsize` apart
+    (one channel: wherever), pixels `cn * itemsize` apart, a positive row pitch -- is described in place with that pitch, a
+    region of a larger image included; any other frame gets one contiguous copy.  No frames: 3 channels, code 0."""
+    fr = [hwc(f) for f in frames]
+    if not fr:
+        return fr, frame_array([]), 3, 0
+    dt, cn = fr[0].dtype, fr[0].shape[2]
+    if any(f.dtype != dt for f in fr):
+        raise PbdError(-1, "one call takes one image dtype: " + ", ".join(sorted({str(f.dtype) for f in fr})))
+    if dt not in DEPTH_CODE:
+        raise PbdError(bad_dtype, f"image dtype {dt}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
+    if any(f.shape[2] != cn for f in fr):
+        raise PbdError(-1, "one call takes one channel count: " + ", ".join(sorted({str(f.shape[2]) for f in fr})))
+    es = dt.itemsize
+    fr = [f if (cn == 1 or f.strides[2] == es) and f.strides[1] == cn * es and f.strides[0] > 0 else np.ascontiguousarray(f) for f in fr]
+    return fr, frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr]), cn, DEPTH_CODE[dt]
+
+
+def pack_arrays(arrays, masks, name: str):
+    """(arrays, real code, packed values, packed mask bytes or None) of float arrays of one dtype, any shapes, empty ones included,
+    and of None or one uint8 / bool mask of its array's shape per array: values and masks (non-zero -> 1) concatenated in order"""
+    arrs = [np.ascontiguousarray(a) for a in arrays]
+    dt = arrs[0].dtype if arrs else np.dtype(np.float32)
+    if dt not in (np.float32, np.float64) or any(a.dtype != dt for a in arrs):
+        raise PbdError(-1, f"{name}: arrays of one dtype, float32 or float64")
+    if masks is not None and (len(masks) != len(arrs) or any(np.shape(m) != a.shape for m, a in zip(masks, arrs))):
+        raise PbdError(-1, f"{name}: one mask of its array's shape per array")
+    src = np.concatenate([a.ravel() for a in arrs] or [np.zeros(0, dt)])
+    msk = None if masks is None else np.concatenate([(np.asarray(m) != 0).astype(np.uint8).ravel() for m in masks] or [np.zeros(0, np.uint8)])
+    return arrs, real_code(dt), src, msk
+
+
+def split_arrays(packed, arrays):
+    """pack_arrays' inverse on a packed per-element result: one array per input array, in its shape"""
+    off = np.concatenate([[0], np.cumsum([a.size for a in arrays], dtype=np.int64)])
+    return [packed[off[i]:off[i + 1]].reshape(a.shape) for i, a in enumerate(arrays)]
 
 
 class CQpConfig(C.Structure):

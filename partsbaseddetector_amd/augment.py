@@ -171,8 +171,7 @@ def points_c(xy, rows: int, cols: int, degrees: float, mirror: bool = False) -> 
     lib = _lib.load()
     p = np.ascontiguousarray(np.array(xy, np.float64).reshape(-1, 2))
     out = np.zeros_like(p)
-    rc = lib.pbd_augment_points(int(rows), int(cols), float(degrees), 1 if mirror else 0, len(p), p.ctypes.data if p.size else None,
-                                out.ctypes.data if out.size else None)
+    rc = lib.pbd_augment_points(int(rows), int(cols), float(degrees), 1 if mirror else 0, len(p), _lib.opt_ptr(p), _lib.opt_ptr(out))
     if rc != _lib.PBD_OK:
         raise _lib.PbdError(rc, lib.pbd_last_error(None).decode())
     return out

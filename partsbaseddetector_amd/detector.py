@@ -11,6 +11,7 @@ Every compute call runs HIP kernels through libpbd_hip.so; nothing here computes
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from dataclasses import dataclass, field
@@ -272,6 +273,7 @@ class Handle:
         self.level_shapes = None                         # (rows, cols) of every level of the last detect / min call (max-marginals)
         self._model_stale = False                        # set_model_vector* / set_thresh: `flat` is behind the handle
         self._thresh = None
+        self._buf = None                                 # the record buffer of the pipelined and device-batch calls, reused
 
     def close(self):
         if getattr(self, "h", None):
@@ -301,10 +303,7 @@ class Handle:
         """pbd_set_nms: every detect* call of this handle returns, per frame, Candidate.sort + Candidate.nonMaximaSuppression(
         (rows, cols), candidates, overlap) of what it found, computed on the device (cells/detect.cpp:237-238,
         ros/Node.cpp:192-196); None: off (the default).  `overlap` crosses the ABI as a float."""
-        if overlap is None:
-            self.check(self.lib.pbd_set_nms(self.h, 0, 0.0))
-        else:
-            self.check(self.lib.pbd_set_nms(self.h, 1, float(overlap)))
+        self.check(self.lib.pbd_set_nms(self.h, int(overlap is not None), float(overlap or 0.0)))
         self.nms_overlap = overlap
 
     def set_walk(self, mode: int) -> None:
@@ -322,31 +321,22 @@ class Handle:
         """pbd_grid_nms: nonMaximaSuppression(plane, sz, dst, mask) of every plane (2-D, all float32 or all float64, any sizes, empty
         ones included), one launch; masks: None, or one uint8 / bool plane per plane.  Returns the uint8 planes of 0 / 255.
         Equal to gridnms.grid_nms_ref."""
-        planes = [np.ascontiguousarray(a) for a in planes]
-        dt = planes[0].dtype if planes else np.dtype(np.float32)
-        if dt not in (np.float32, np.float64) or any(a.dtype != dt or a.ndim != 2 for a in planes):
-            raise PbdError(-1, "grid_nms: 2-D planes of one dtype, float32 or float64")
-        if masks is not None and (len(masks) != len(planes) or any(np.shape(m) != a.shape for m, a in zip(masks, planes))):
-            raise PbdError(-1, "grid_nms: one mask of its plane's shape per plane")
-        rows = np.array([a.shape[0] for a in planes], np.int32)
-        cols = np.array([a.shape[1] for a in planes], np.int32)
-        src = np.concatenate([a.ravel() for a in planes]) if planes else np.zeros(0, dt)
-        msk = None if masks is None else np.concatenate([(np.asarray(m) != 0).astype(np.uint8).ravel() for m in masks] or [np.zeros(0, np.uint8)])
+        planes, real, src, msk = _lib.pack_arrays(planes, masks, "grid_nms")
+        if any(a.ndim != 2 for a in planes):
+            raise PbdError(-1, "grid_nms: 2-D planes")
+        _, _, rows, cols = _lib.shape_arrays([a.shape for a in planes])
         dst = np.zeros(src.size, np.uint8)
-        self.check(self.lib.pbd_grid_nms(self.h, len(planes), _lib.ptr(rows, C.c_int), _lib.ptr(cols, C.c_int),
-                                         _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64, src.ctypes.data,
-                                         None if msk is None else msk.ctypes.data, int(sz), dst.ctypes.data))
-        off = np.concatenate([[0], np.cumsum(rows.astype(np.int64) * cols)])
-        return [dst[off[i]:off[i + 1]].reshape(a.shape) for i, a in enumerate(planes)]
+        self.check(self.lib.pbd_grid_nms(self.h, len(planes), rows, cols, real, src.ctypes.data, None if msk is None else msk.ctypes.data,
+                                         int(sz), dst.ctypes.data))
+        return _lib.split_arrays(dst, planes)
 
     def grid_nms_device(self, rows: Sequence[int], cols: Sequence[int], real_code: int, d_src_ptr: int, d_mask_ptr: Optional[int],
                         sz: int, d_dst_ptr: int) -> None:
         """pbd_grid_nms_device: the packed planes at d_src_ptr (rows[i] x cols[i] each, REAL_F32 or REAL_F64), the optional packed
         mask bytes, the packed result bytes; asynchronous on the handle's stream"""
-        r = np.asarray(rows, np.int32)
-        c = np.asarray(cols, np.int32)
-        self.check(self.lib.pbd_grid_nms_device(self.h, len(r), _lib.ptr(r, C.c_int), _lib.ptr(c, C.c_int), int(real_code),
-                                                d_src_ptr or None, d_mask_ptr or None, int(sz), d_dst_ptr or None))
+        ir, _, r, c = _lib.shape_arrays(list(zip(rows, cols)))
+        self.check(self.lib.pbd_grid_nms_device(self.h, len(ir), r, c, int(real_code), d_src_ptr or None, d_mask_ptr or None, int(sz),
+                                                d_dst_ptr or None))
 
     def set_top_k(self, k: int) -> None:
         """pbd_set_top_k: every detect* call of this handle keeps only the k best roots of each frame among the cells the threshold
@@ -357,20 +347,12 @@ class Handle:
         """pbd_top_k_cells: the k best eligible elements of every segment (1-D after ravel, all float32 or all float64, any lengths,
         empty ones included), one launch sequence; masks: None, or one uint8 / bool array per segment.  Returns the uint8 arrays of
         0 / 255 in the segments' shapes.  Equal to topk.top_k_cells_ref."""
-        segs = [np.ascontiguousarray(a) for a in segments]
-        dt = segs[0].dtype if segs else np.dtype(np.float32)
-        if dt not in (np.float32, np.float64) or any(a.dtype != dt for a in segs):
-            raise PbdError(-1, "top_k_cells: segments of one dtype, float32 or float64")
-        if masks is not None and (len(masks) != len(segs) or any(np.shape(m) != a.shape for m, a in zip(masks, segs))):
-            raise PbdError(-1, "top_k_cells: one mask of its segment's shape per segment")
+        segs, real, src, msk = _lib.pack_arrays(segments, masks, "top_k_cells")
         ln = np.array([a.size for a in segs], np.int64)
-        src = np.concatenate([a.ravel() for a in segs]) if segs else np.zeros(0, dt)
-        msk = None if masks is None else np.concatenate([(np.asarray(m) != 0).astype(np.uint8).ravel() for m in masks] or [np.zeros(0, np.uint8)])
         dst = np.zeros(src.size, np.uint8)
-        self.check(self.lib.pbd_top_k_cells(self.h, len(segs), _lib.ptr(ln, C.c_longlong), _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64,
-                                            src.ctypes.data, None if msk is None else msk.ctypes.data, int(k), dst.ctypes.data))
-        off = np.concatenate([[0], np.cumsum(ln)])
-        return [dst[off[i]:off[i + 1]].reshape(a.shape) for i, a in enumerate(segs)]
+        self.check(self.lib.pbd_top_k_cells(self.h, len(segs), _lib.ptr(ln, C.c_longlong), real, src.ctypes.data,
+                                            None if msk is None else msk.ctypes.data, int(k), dst.ctypes.data))
+        return _lib.split_arrays(dst, segs)
 
     def top_k_cells_device(self, lengths: Sequence[int], real_code: int, d_src_ptr: int, d_mask_ptr: Optional[int], k: int,
                            d_dst_ptr: int) -> None:
@@ -383,13 +365,7 @@ class Handle:
     def top_k(self, nframes: int, k: int, records: np.ndarray, frame_offset: int = 0, capacity: Optional[int] = None) -> np.ndarray:
         """pbd_top_k: per frame the k best records (n, stride) by score, ties to the earlier record, in input order; the records are
         grouped by ascending frame (equal to topk.top_k_records_ref)"""
-        rec = self._records(records)
-        cap = len(rec) if capacity is None else capacity
-        out = np.zeros((max(cap, 1), self.stride), np.int32)
-        n = C.c_int()
-        self.check(self.lib.pbd_top_k(self.h, int(nframes), int(k), rec.ctypes.data if rec.size else None, len(rec), frame_offset,
-                                      out.ctypes.data, cap, C.byref(n)))
-        return out[:min(n.value, cap)].copy()
+        return self._list_call(self.lib.pbd_top_k, (int(nframes), int(k)), records, frame_offset, capacity)
 
     def top_k_device(self, nframes: int, k: int, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
                      out_capacity: int) -> None:
@@ -441,35 +417,61 @@ class Handle:
         """pbd_boxes3d: Candidate::boundingBox3D of every record (n, stride) on the device, (n, 6) float64 in Rect3d member
         order.  depths[f]: 2-D depth image of frame f (one dtype for the call, rows of any pitch); im_shapes[f] = (rows, cols)
         of the colour frame; a record's frame index is its `frame` field - frame_offset."""
-        dt = np.dtype(depths[0].dtype)
-        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
-            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
-        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
-        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        rec = np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
+        ds, descs, code = _lib.depth_frames(depths)
+        _, _, ir, ic = _lib.shape_arrays(im_shapes)
+        rec = self._records(records)
         out = np.zeros((len(rec), 6), np.float64)
-        self.check(self.lib.pbd_boxes3d(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
-                                        rec.ctypes.data if rec.size else None, len(rec), frame_offset,
-                                        out.ctypes.data if out.size else None))
+        self.check(self.lib.pbd_boxes3d(self.h, len(ds), descs, code, ir, ic, _lib.opt_ptr(rec), len(rec), frame_offset, _lib.opt_ptr(out)))
         return out
 
     def boxes3d_device(self, descs, depth_code: int, im_shapes, d_payload_ptr: int, capacity: int, frame_offset: int,
                        d_out_ptr: int) -> None:
         """pbd_boxes3d_device: the records of a device payload (as detect_batch_device_out leaves it), depth frames
         (device pointer, rows, cols, pitch), boxes into double[6 * capacity] at d_out_ptr; asynchronous on the handle's stream"""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        self.check(self.lib.pbd_boxes3d_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
-                                               _lib.ptr(ic, C.c_int), d_payload_ptr, capacity, frame_offset, d_out_ptr))
+        _, _, ir, ic = _lib.shape_arrays(im_shapes)
+        self.check(self.lib.pbd_boxes3d_device(self.h, len(descs), _lib.frame_array(descs), depth_code, ir, ic, d_payload_ptr, capacity,
+                                               frame_offset, d_out_ptr))
 
     def _records(self, records) -> np.ndarray:
         return np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
 
+    def _list_call(self, fn, args, records, frame_offset: int, capacity: Optional[int]) -> np.ndarray:
+        """a host list-in / list-out entry point, fn(h, *args, records, n, frame_offset, out, capacity, &kept): the kept records.
+        capacity None: room for every record.  More kept than the capacity is the library's PBD_ERR_CAPACITY."""
+        rec = self._records(records)
+        cap = len(rec) if capacity is None else capacity
+        out = np.zeros((max(cap, 1), self.stride), np.int32)
+        n = C.c_int()
+        self.check(fn(self.h, *args, _lib.opt_ptr(rec), len(rec), frame_offset, out.ctypes.data, cap, C.byref(n)))
+        return out[:min(n.value, cap)].copy()
+
+    def _host_list(self, fn, args, capacity: Optional[int], raw: bool = False, cached: bool = False):
+        """a detect-family entry point that lists its records on the host, fn(h, *args, buf, capacity, &n): the list as Candidates,
+        or as (buf, n) for raw.  capacity None: max_candidates.  cached: into the handle's own buffer, grown on demand and reused
+        (nothing is allocated per call; a raw result is valid until the next cached call), else into a new one."""
+        cap = self.max_candidates if capacity is None else capacity
+        buf = getattr(self, "_buf", None) if cached else None
+        if buf is None or buf.size < cap * self.stride:
+            buf = np.zeros(max(cap, 1) * self.stride, np.int32)
+            if cached:
+                self._buf = buf
+        n = C.c_int()
+        self.check(fn(self.h, *args, buf.ctypes.data, cap, C.byref(n)))
+        return (buf, n.value) if raw else self.unpack_candidates(buf, n.value)
+
+    def synchronize(self) -> None:
+        """pbd_synchronize: wait for everything enqueued on the handle's stream"""
+        self.check(self.lib.pbd_synchronize(self.h))
+
+    def binsize(self) -> int:
+        return self.lib.pbd_binsize(self.h)
+
+    def model_vector_len(self) -> int:
+        return self.lib.pbd_model_vector_len(self.h)
+
     def model_vector(self) -> np.ndarray:
         """pbd_model_vector: w = [biasw | defw | filters] in T"""
-        w = np.zeros(self.lib.pbd_model_vector_len(self.h), self.dtype)
+        w = np.zeros(self.model_vector_len(), self.dtype)
         self.check(self.lib.pbd_model_vector(self.h, w.ctypes.data))
         return w
 
@@ -477,7 +479,7 @@ class Handle:
         """pbd_set_model_vector: the handle's parameters become w (model_vector()'s order, rounded to T), in place: afterwards
         the handle equals a new one created from Model.from_vector(w).  The resident detect result is dropped."""
         w = np.ascontiguousarray(w, self.dtype).ravel()
-        n = self.lib.pbd_model_vector_len(self.h)
+        n = self.model_vector_len()
         if len(w) != n:
             raise PbdError(-1, f"model vector of {len(w)} values, this handle's has {n}")
         self.check(self.lib.pbd_set_model_vector(self.h, w.ctypes.data))
@@ -486,10 +488,7 @@ class Handle:
     def set_model_vector_device(self, d_w_ptr: int, dtype) -> None:
         """pbd_set_model_vector_device: the same from model_vector_len float32 / float64 values on the handle's device (the
         caller orders their producer before stream_ptr()); nothing of the bank's size crosses to the host"""
-        dt = np.dtype(dtype)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise PbdError(-1, f"dtype {dt}: float32 or float64")
-        self.check(self.lib.pbd_set_model_vector_device(self.h, d_w_ptr, _lib.REAL_F32 if dt == np.float32 else _lib.REAL_F64))
+        self.check(self.lib.pbd_set_model_vector_device(self.h, d_w_ptr, _lib.real_code(dtype)))
         self._model_stale = True
 
     def set_thresh(self, thresh: float) -> None:
@@ -521,20 +520,17 @@ class Handle:
         hw, vw = self.example_stride()
         hdr = np.zeros((len(rec), hw), np.int32)
         vals = np.zeros((len(rec), vw), self.dtype)
-        self.check(self.lib.pbd_examples(self.h, rec.ctypes.data if rec.size else None, len(rec), frame_offset,
-                                         hdr.ctypes.data if hdr.size else None, vals.ctypes.data if vals.size else None))
+        self.check(self.lib.pbd_examples(self.h, _lib.opt_ptr(rec), len(rec), frame_offset, _lib.opt_ptr(hdr), _lib.opt_ptr(vals)))
         return hdr, vals
 
     def part_scores(self, records: np.ndarray, frame_offset: int = 0, fill=0):
         """pbd_part_scores: (status (n,) int32, place (n, max_parts, 3) int32 x, y, m, scores (n, max_parts, 4) T appearance,
         message, bias, total) of records (n, stride) of the last detect call, at the walk's placement.  Entries past a record's
         parts keep `fill`."""
-        rec = self._records(records)
-        mp = (self.stride - 8) // 4
+        rec, ptr = self._records(records), _lib.opt_ptr
         status = np.full(len(rec), fill, np.int32)
-        place = np.full((len(rec), mp, 3), fill, np.int32)
-        scores = np.full((len(rec), mp, 4), fill, self.dtype)
-        ptr = lambda a: a.ctypes.data if a.size else None
+        place = np.full((len(rec), self.max_parts, 3), fill, np.int32)
+        scores = np.full((len(rec), self.max_parts, 4), fill, self.dtype)
         self.check(self.lib.pbd_part_scores(self.h, ptr(rec), len(rec), frame_offset, ptr(status), ptr(place), ptr(scores)))
         return status, place, scores
 
@@ -542,14 +538,12 @@ class Handle:
         """pbd_score_placements: (status (n,) int32, scores (n, max_parts, 4) T) of the placements place (n, max_parts, 3) x, y, m
         (place[i][0] the root) in the frame, level and component of records (n, stride); a placement outside the map or the
         part's mixtures has status -1 and keeps `fill`"""
-        rec = self._records(records)
-        mp = (self.stride - 8) // 4
+        rec, ptr = self._records(records), _lib.opt_ptr
         place = np.ascontiguousarray(place, np.int32)
-        if place.shape != (len(rec), mp, 3):
-            raise PbdError(-1, f"placements of shape {place.shape}, expected {(len(rec), mp, 3)}")
+        if place.shape != (len(rec), self.max_parts, 3):
+            raise PbdError(-1, f"placements of shape {place.shape}, expected {(len(rec), self.max_parts, 3)}")
         status = np.full(len(rec), fill, np.int32)
-        scores = np.full((len(rec), mp, 4), fill, self.dtype)
-        ptr = lambda a: a.ctypes.data if a.size else None
+        scores = np.full((len(rec), self.max_parts, 4), fill, self.dtype)
         self.check(self.lib.pbd_score_placements(self.h, ptr(rec), len(rec), frame_offset, ptr(place), ptr(status), ptr(scores)))
         return status, scores
 
@@ -594,7 +588,7 @@ class Handle:
         rec = np.full((n, self.stride), fill, np.int32)
         place = np.full((n, self.max_parts, 3), fill, np.int32)
         sc = None if scales is None else np.ascontiguousarray(scales, np.float32)
-        ptr = lambda a: a.ctypes.data if a.size else None
+        ptr = _lib.opt_ptr
         self.check(self.lib.pbd_marginal_poses(self.h, n, ptr(sd), None if sc is None else _lib.ptr(sc, C.c_float), frame_offset,
                                                ptr(rec), ptr(place), ptr(status)))
         return status, rec, place
@@ -610,17 +604,15 @@ class Handle:
     def detect_latent(self, frames, part_boxes, overlap: float, mixtures=None):
         """pbd_detect_latent: (records (nframes, stride) int32, found (nframes,) int32) -- per frame the best root whose parts
         overlap part_boxes[f][p] = (x1, y1, x2, y2) inclusive by more than `overlap`; mixtures[f][p]: fixed mixture or -1"""
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
-        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        fr, descs, cn, code = _lib.image_frames(frames)
         boxes = np.ascontiguousarray(part_boxes, np.int32).reshape(len(fr), -1, 4)
         mix = None if mixtures is None else np.ascontiguousarray(mixtures, np.int32).reshape(len(fr), boxes.shape[1])
         if mix is not None and mix.shape != boxes.shape[:2]:
             raise PbdError(-1, "one mixture per part box")
         rec = np.zeros((len(fr), self.stride), np.int32)
         found = np.zeros(len(fr), np.int32)
-        self.check(self.lib.pbd_detect_latent(self.h, len(fr), descs, fr[0].shape[2], _lib.DEPTH_CODE[fr[0].dtype], boxes.ctypes.data,
-                                              None if mix is None else mix.ctypes.data, float(overlap), rec.ctypes.data,
-                                              found.ctypes.data))
+        self.check(self.lib.pbd_detect_latent(self.h, len(fr), descs, cn, code, boxes.ctypes.data, None if mix is None else mix.ctypes.data,
+                                              float(overlap), rec.ctypes.data, found.ctypes.data))
         return rec, found
 
     def detect_latent_device(self, descs, cn: int, depth_code: int, part_boxes, overlap: float, mixtures=None):
@@ -647,9 +639,7 @@ class Handle:
         """pbd_augment_frames: the copies rotate(mirror(frames[f])) of jobs (n, 3) = (frame, mirror, degrees) as host arrays;
         frames are arrays of one dtype and channel count, any sizes.  outs: destinations to write into (views with padded rows
         allowed), else new arrays."""
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
-        if fr and (any(f.dtype != fr[0].dtype or f.shape[2] != fr[0].shape[2] for f in fr) or fr[0].dtype not in _lib.DEPTH_CODE):
-            raise PbdError(-1, "one dtype (uint8, uint16, float32 or float64) and one channel count per call")
+        fr, descs, cn, code = _lib.image_frames(frames)
         jobs = [(int(f), bool(m), float(d)) for f, m, d in jobs]
         if outs is None:
             outs = []
@@ -658,10 +648,8 @@ class Handle:
                     raise PbdError(-1, f"frame {f} outside 0..{len(fr) - 1}")
                 r, c, _ = self.augment_plan(fr[f].shape[0], fr[f].shape[1], d)
                 outs.append(np.zeros((r, c, fr[f].shape[2]), fr[f].dtype))
-        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
         odesc = _lib.frame_array([(o.ctypes.data, o.shape[0], o.shape[1], o.strides[0]) for o in outs])
-        self.check(self.lib.pbd_augment_frames(self.h, len(fr), descs, fr[0].shape[2] if fr else 3,
-                                               _lib.DEPTH_CODE[fr[0].dtype] if fr else 0, len(jobs), _lib.augment_array(jobs), odesc))
+        self.check(self.lib.pbd_augment_frames(self.h, len(fr), descs, cn, code, len(jobs), _lib.augment_array(jobs), odesc))
         return outs
 
     def augment_frames_device(self, descs, cn: int, depth_code: int, jobs, out_descs) -> None:
@@ -681,19 +669,14 @@ class Handle:
         cropped with edge replication, resized to (k + 2) * sbin pixels, its HOG as the example [bias = 1 | filter block];
         a box skipped as too small has hdr[2] = -1.  Values past nvalues and the rows of skipped boxes stay 0.  The resident
         detect result is dropped."""
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
-        if fr and (any(f.dtype != fr[0].dtype or f.shape[2] != fr[0].shape[2] for f in fr) or fr[0].dtype not in _lib.DEPTH_CODE):
-            raise PbdError(-1, "one dtype (uint8, uint16, float32 or float64) and one channel count per call")
-        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
+        fr, descs, cn, code = _lib.image_frames(frames)
         bx = np.ascontiguousarray(boxes, np.int32).reshape(-1, 5)
         hw, vw = self.example_stride()
         hdr = np.zeros((len(bx), hw), np.int32)
         vals = np.zeros((len(bx), vw), self.dtype)
         kept = np.zeros(len(bx), np.int32)
-        self.check(self.lib.pbd_warp_positives(self.h, len(fr), descs, fr[0].shape[2] if fr else 3,
-                                               _lib.DEPTH_CODE[fr[0].dtype] if fr else 0, len(bx), bx.ctypes.data if bx.size else None,
-                                               filter, bias, 1 if skip_small else 0, hdr.ctypes.data if hdr.size else None,
-                                               vals.ctypes.data if vals.size else None, kept.ctypes.data if kept.size else None))
+        self.check(self.lib.pbd_warp_positives(self.h, len(fr), descs, cn, code, len(bx), _lib.opt_ptr(bx), filter, bias,
+                                               1 if skip_small else 0, _lib.opt_ptr(hdr), _lib.opt_ptr(vals), _lib.opt_ptr(kept)))
         return hdr, vals, kept
 
     def warp_positives_device(self, descs, cn: int, depth_code: int, boxes, filter: int, bias: int, skip_small: bool, id_offset: int,
@@ -703,26 +686,15 @@ class Handle:
         {id_offset + i, 0 ...}) on the device, ready for QP.add_device; asynchronous on the handle's stream"""
         bx = np.ascontiguousarray(boxes, np.int32).reshape(-1, 5)
         self.check(self.lib.pbd_warp_positives_device(self.h, len(descs), _lib.frame_array(descs), cn, depth_code, len(bx),
-                                                      bx.ctypes.data if bx.size else None, filter, bias, 1 if skip_small else 0,
-                                                      id_offset, d_payload_ptr, capacity, d_hdr_ptr, d_values_ptr))
+                                                      _lib.opt_ptr(bx), filter, bias, 1 if skip_small else 0, id_offset, d_payload_ptr,
+                                                      capacity, d_hdr_ptr, d_values_ptr))
 
     def depth_consistency(self, depths: Sequence[np.ndarray], records: np.ndarray, zfactor: float = 0.03, frame_offset: int = 0,
                           capacity: Optional[int] = None) -> np.ndarray:
         """pbd_depth_consistency: the records (n, stride) that SearchSpacePruning::filterCandidatesByDepth keeps, in input order,
         computed on the device.  depths[f]: the 2-D depth image of frame index f (one dtype per call, rows of any pitch)."""
-        dt = np.dtype(depths[0].dtype)
-        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
-            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
-        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
-        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
-        rec = self._records(records)
-        cap = len(rec) if capacity is None else capacity
-        out = np.zeros((max(cap, 1), self.stride), np.int32)
-        n = C.c_int()
-        self.check(self.lib.pbd_depth_consistency(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], float(zfactor),
-                                                  rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap,
-                                                  C.byref(n)))
-        return out[:n.value].copy()
+        ds, descs, code = _lib.depth_frames(depths)
+        return self._list_call(self.lib.pbd_depth_consistency, (len(ds), descs, code, float(zfactor)), records, frame_offset, capacity)
 
     def depth_consistency_device(self, descs, depth_code: int, zfactor: float, d_payload_ptr: int, capacity: int, frame_offset: int,
                                  d_out_ptr: int, out_capacity: int) -> None:
@@ -731,23 +703,13 @@ class Handle:
         self.check(self.lib.pbd_depth_consistency_device(self.h, len(descs), _lib.frame_array(descs), depth_code, float(zfactor),
                                                          d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
 
-    @staticmethod
-    def _depth_frames(depths: Sequence[np.ndarray]):
-        """(arrays kept alive, pbd_frame[], depth code) of 2-D depth images of one dtype, rows of any pitch"""
-        dt = np.dtype(depths[0].dtype)
-        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
-            raise PbdError(-1, "one depth dtype per call: uint8, uint16, float32 or float64")
-        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
-        return ds, _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds]), _lib.DEPTH_CODE[dt]
-
-    @staticmethod
-    def _prune_cfg(fx: float, width: float, tol: float):
-        return C.byref(_lib.CDepthPruneCfg(float(fx), float(width), float(tol)))
+    _depth_frames = staticmethod(_lib.depth_frames)     # the names the raw-call tests build their arguments with
+    _prune_cfg = staticmethod(_lib.prune_cfg)
 
     def set_depth_prune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """pbd_set_depth_prune: with depth images bound (bind_depth), every detect* call of this handle lists only the roots whose
         rectangle is depthprune.plausible(rect, depth, fx, width, tol); fx None: off (the default)"""
-        self.check(self.lib.pbd_set_depth_prune(self.h, None if fx is None else self._prune_cfg(fx, width, tol)))
+        self.check(self.lib.pbd_set_depth_prune(self.h, None if fx is None else _lib.prune_cfg(fx, width, tol)))
 
     def bind_depth(self, depths: Optional[Sequence[np.ndarray]]) -> None:
         """pbd_bind_depth: the depth images (one per frame, the frame's rows x cols) of the NEXT detect* call or argmin_device_out,
@@ -755,7 +717,7 @@ class Handle:
         if not depths:
             self.check(self.lib.pbd_bind_depth(self.h, 0, None, 0))
             return
-        ds, descs, code = self._depth_frames(depths)
+        ds, descs, code = _lib.depth_frames(depths)
         self.check(self.lib.pbd_bind_depth(self.h, len(ds), descs, code))
 
     def bind_depth_device(self, descs, depth_code: int) -> None:
@@ -766,44 +728,31 @@ class Handle:
                     frame_offset: int = 0, capacity: Optional[int] = None) -> np.ndarray:
         """pbd_depth_prune: the records (n, stride) whose root rectangle is plausible in their frame's depth image, in input order,
         decided on the device (equal to depthprune.filter_records)"""
-        ds, descs, code = self._depth_frames(depths)
-        rec = self._records(records)
-        cap = len(rec) if capacity is None else capacity
-        out = np.zeros((max(cap, 1), self.stride), np.int32)
-        n = C.c_int()
-        self.check(self.lib.pbd_depth_prune(self.h, self._prune_cfg(fx, width, tol), len(ds), descs, code,
-                                            rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap,
-                                            C.byref(n)))
-        return out[:n.value].copy()
+        ds, descs, code = _lib.depth_frames(depths)
+        return self._list_call(self.lib.pbd_depth_prune, (_lib.prune_cfg(fx, width, tol), len(ds), descs, code), records, frame_offset,
+                               capacity)
 
     def depth_prune_device(self, descs, depth_code: int, fx: float, width: float, tol: float, d_payload_ptr: int, capacity: int,
                            frame_offset: int, d_out_ptr: int, out_capacity: int) -> None:
         """pbd_depth_prune_device: the records of a device payload, depth frames (device pointer, rows, cols, pitch), the kept
         records into the payload at d_out_ptr (word 0 = kept count, -1 for an overflowed input); asynchronous"""
-        self.check(self.lib.pbd_depth_prune_device(self.h, self._prune_cfg(fx, width, tol), len(descs), _lib.frame_array(descs),
+        self.check(self.lib.pbd_depth_prune_device(self.h, _lib.prune_cfg(fx, width, tol), len(descs), _lib.frame_array(descs),
                                                    depth_code, d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
 
     def suppress(self, im_shapes, overlap: float, records: np.ndarray, frame_offset: int = 0,
                  capacity: Optional[int] = None) -> np.ndarray:
         """pbd_suppress: per frame Candidate.sort + Candidate.nonMaximaSuppression((rows, cols), ., overlap) of records grouped by
         ascending frame (the pbd_set_nms stage on a caller's list); im_shapes[f] = (rows, cols) of frame index f"""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        rec = self._records(records)
-        cap = len(rec) if capacity is None else capacity
-        out = np.zeros((max(cap, 1), self.stride), np.int32)
-        n = C.c_int()
-        self.check(self.lib.pbd_suppress(self.h, len(ir), _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), float(overlap),
-                                         rec.ctypes.data if rec.size else None, len(rec), frame_offset, out.ctypes.data, cap, C.byref(n)))
-        return out[:n.value].copy()
+        ir, _, pr, pc = _lib.shape_arrays(im_shapes)
+        return self._list_call(self.lib.pbd_suppress, (len(ir), pr, pc, float(overlap)), records, frame_offset, capacity)
 
     def suppress_device(self, im_shapes, overlap: float, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
                         out_capacity: int) -> None:
-        """pbd_suppress_device: suppress_device's payload in, the kept records into the payload at d_out_ptr; asynchronous"""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        self.check(self.lib.pbd_suppress_device(self.h, len(ir), _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), float(overlap),
-                                                d_payload_ptr, capacity, frame_offset, d_out_ptr, out_capacity))
+        """pbd_suppress_device: suppress on a device payload's records, the kept records into the payload at d_out_ptr (word 0 =
+        kept count, -1 for an overflowed input); asynchronous"""
+        ir, _, pr, pc = _lib.shape_arrays(im_shapes)
+        self.check(self.lib.pbd_suppress_device(self.h, len(ir), pr, pc, float(overlap), d_payload_ptr, capacity, frame_offset, d_out_ptr,
+                                                out_capacity))
 
     # ---- testing a model (include/pbd.h; the numpy yardstick is evaluation.py) ----------------------
     def eval_nparts(self) -> int:
@@ -815,13 +764,7 @@ class Handle:
                  capacity: Optional[int] = None) -> np.ndarray:
         """pbd_part_nms: matlab/detection/nms.m per frame of records grouped by ascending frame; the kept records, frame by
         frame, in pick order"""
-        rec = self._records(records)
-        cap = len(rec) if capacity is None else capacity
-        out = np.zeros((max(cap, 1), self.stride), np.int32)
-        n = C.c_int()
-        self.check(self.lib.pbd_part_nms(self.h, nframes, float(overlap), max_boxes, rec.ctypes.data if rec.size else None, len(rec),
-                                         frame_offset, out.ctypes.data, cap, C.byref(n)))
-        return out[:n.value].copy()
+        return self._list_call(self.lib.pbd_part_nms, (nframes, float(overlap), max_boxes), records, frame_offset, capacity)
 
     def part_nms_device(self, nframes: int, overlap: float, max_boxes: int, d_payload_ptr: int, capacity: int, frame_offset: int,
                         d_out_ptr: int, out_capacity: int) -> None:
@@ -837,8 +780,8 @@ class Handle:
         rec = self._records(records)
         out = np.zeros((len(gt), self.stride), np.int32)
         found = np.zeros(len(gt), np.int32)
-        self.check(self.lib.pbd_best_overlap(self.h, len(gt), gt.ctypes.data, float(overlap), rec.ctypes.data if rec.size else None,
-                                             len(rec), frame_offset, out.ctypes.data, found.ctypes.data))
+        self.check(self.lib.pbd_best_overlap(self.h, len(gt), gt.ctypes.data, float(overlap), _lib.opt_ptr(rec), len(rec), frame_offset,
+                                             out.ctypes.data, found.ctypes.data))
         return out, found
 
     def best_overlap_device(self, gtboxes, overlap: float, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
@@ -895,7 +838,7 @@ class Handle:
         prec = np.zeros((npart, len(rec))) if want_curves else None
         rcl = np.zeros((npart, len(rec))) if want_curves else None
         self.check(self.lib.pbd_eval_apk(self.h, len(off) - 1, off.ctypes.data, gt.ctypes.data, sc.ctypes.data, float(thresh),
-                                         rec.ctypes.data if rec.size else None, len(rec), frame_offset, apk.ctypes.data,
+                                         _lib.opt_ptr(rec), len(rec), frame_offset, apk.ctypes.data,
                                          prec.ctypes.data if want_curves else None, rcl.ctypes.data if want_curves else None))
         return apk, prec, rcl
 
@@ -951,42 +894,33 @@ class Handle:
                        frame_offset: int = 0):
         """pbd_boxes3d_camera: camera boxes (n, 6) float64, part centres (n, max_parts, 3) float32 (0 past ncentres), ncentres (n,)
         and dense (n,) int32 of the records (n, stride); depths[f] float32 2-D, cameras[f] with fx, fy, cx, cy, tx, ty."""
-        dt = np.dtype(depths[0].dtype)
-        if dt not in _lib.DEPTH_CODE or any(np.dtype(d.dtype) != dt for d in depths):
-            raise PbdError(-1, "one depth dtype per call")
-        ds = [d if d.ndim == 2 and d.strides[1] == d.itemsize and d.strides[0] > 0 else np.ascontiguousarray(d) for d in depths]
-        descs = _lib.frame_array([(d.ctypes.data, d.shape[0], d.shape[1], d.strides[0]) for d in ds])
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        rec = np.ascontiguousarray(records, np.int32).reshape(-1, self.stride)
+        ds, descs, code = _lib.depth_frames(depths)
+        _, _, ir, ic = _lib.shape_arrays(im_shapes)
+        rec, ptr = self._records(records), _lib.opt_ptr
         n = len(rec)
         box = np.zeros((n, 6))
         cen = np.zeros((n, self.max_parts, 3), np.float32)
         nc = np.zeros(n, np.int32)
         dn = np.zeros(n, np.int32)
-        ptr = (lambda a: a.ctypes.data if n else None)
-        self.check(self.lib.pbd_boxes3d_camera(self.h, len(ds), descs, _lib.DEPTH_CODE[dt], _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
-                                               _lib.pinhole_array(cameras), parts_mode, ptr(rec), n, frame_offset, ptr(box), ptr(cen),
-                                               ptr(nc), ptr(dn)))
+        self.check(self.lib.pbd_boxes3d_camera(self.h, len(ds), descs, code, ir, ic, _lib.pinhole_array(cameras), parts_mode, ptr(rec), n,
+                                               frame_offset, ptr(box), ptr(cen), ptr(nc), ptr(dn)))
         return box, cen, nc, dn
 
     def boxes3d_camera_device(self, descs, depth_code: int, im_shapes, cameras, parts_mode: int, d_payload_ptr: int, capacity: int,
                               frame_offset: int, d_box_ptr: int, d_centres_ptr: int, d_ncentres_ptr: int, d_dense_ptr: int) -> None:
         """pbd_boxes3d_camera_device: the records of a device payload, depth frames (device pointer, rows, cols, pitch), device
         outputs of `capacity` records; asynchronous on the handle's stream"""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
-        self.check(self.lib.pbd_boxes3d_camera_device(self.h, len(descs), _lib.frame_array(descs), depth_code, _lib.ptr(ir, C.c_int),
-                                                      _lib.ptr(ic, C.c_int), _lib.pinhole_array(cameras), parts_mode, d_payload_ptr,
-                                                      capacity, frame_offset, d_box_ptr, d_centres_ptr, d_ncentres_ptr, d_dense_ptr))
+        _, _, ir, ic = _lib.shape_arrays(im_shapes)
+        self.check(self.lib.pbd_boxes3d_camera_device(self.h, len(descs), _lib.frame_array(descs), depth_code, ir, ic,
+                                                      _lib.pinhole_array(cameras), parts_mode, d_payload_ptr, capacity, frame_offset,
+                                                      d_box_ptr, d_centres_ptr, d_ncentres_ptr, d_dense_ptr))
 
     def candidate_mask(self, im_shapes, records: np.ndarray, frames: Optional[Sequence[np.ndarray]] = None, frame_offset: int = 0,
                        labels: bool = True, in_place: bool = False):
         """pbd_candidate_mask: (labels, masked) of the records (n, stride) grouped by ascending frame; im_shapes[f] = (rows, cols) of
         frame index f.  labels: uint8 (rows, cols) per frame (None when labels=False); masked: with `frames` (uint8 (rows, cols) or
         (rows, cols, 1 | 3 | 4), any row pitch), each frame & (label != 0), written over the frames themselves when in_place."""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        ir, ic, pr, pc = _lib.shape_arrays(im_shapes)
         nf = len(ir)
         rec = self._records(records)
         labs = [np.zeros((int(ir[f]), int(ic[f])), np.uint8) for f in range(nf)] if labels else None
@@ -1002,8 +936,7 @@ class Handle:
             col_s = (C.c_size_t * nf)(*[f.strides[0] for f in frames])
             out_p = (C.c_void_p * nf)(*[f.ctypes.data for f in outs])
             out_s = (C.c_size_t * nf)(*[f.strides[0] for f in outs])
-        self.check(self.lib.pbd_candidate_mask(self.h, nf, _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int),
-                                               rec.ctypes.data if rec.size else None, len(rec), frame_offset, lab_p, lab_s, cn, col_p,
+        self.check(self.lib.pbd_candidate_mask(self.h, nf, pr, pc, _lib.opt_ptr(rec), len(rec), frame_offset, lab_p, lab_s, cn, col_p,
                                                col_s, out_p, out_s))
         return labs, outs
 
@@ -1011,13 +944,11 @@ class Handle:
                               colour_descs=None, masked_descs=None, d_status_ptr: int = 0) -> None:
         """pbd_candidate_mask_device: the records of a device payload; label_descs / colour_descs / masked_descs: (device pointer,
         pitch) per frame, or None to omit that output; the record count or -1 into the int32 at d_status_ptr; asynchronous"""
-        ir = np.array([int(s[0]) for s in im_shapes], np.int32)
-        ic = np.array([int(s[1]) for s in im_shapes], np.int32)
+        ir, _, pr, pc = _lib.shape_arrays(im_shapes)
         nf = len(ir)
         arr = (lambda d, k, t: None if d is None else (t * nf)(*[e[k] for e in d]))
-        self.check(self.lib.pbd_candidate_mask_device(self.h, nf, _lib.ptr(ir, C.c_int), _lib.ptr(ic, C.c_int), d_payload_ptr, capacity,
-                                                      frame_offset, arr(label_descs, 0, C.c_void_p), arr(label_descs, 1, C.c_size_t),
-                                                      channels, arr(colour_descs, 0, C.c_void_p), arr(colour_descs, 1, C.c_size_t),
+        self.check(self.lib.pbd_candidate_mask_device(self.h, nf, pr, pc, d_payload_ptr, capacity, frame_offset,
+                                                      arr(label_descs, 0, C.c_void_p), arr(label_descs, 1, C.c_size_t), channels, arr(colour_descs, 0, C.c_void_p), arr(colour_descs, 1, C.c_size_t),
                                                       arr(masked_descs, 0, C.c_void_p), arr(masked_descs, 1, C.c_size_t), d_status_ptr))
 
     def part_poses(self, centres: np.ndarray, ncentres: np.ndarray, dense: np.ndarray):
@@ -1031,7 +962,7 @@ class Handle:
         pos = np.zeros((n, 3), np.float32)
         ori = np.zeros((n, 4), np.float32)
         ev = np.zeros((n, 3), np.float32)
-        ptr = (lambda a: a.ctypes.data if n else None)
+        ptr = _lib.opt_ptr
         self.check(self.lib.pbd_part_poses(self.h, n, ptr(cen), ptr(nc), ptr(dn), ptr(cnt), ptr(pos), ptr(ori), ptr(ev)))
         return cnt, pos, ori, ev
 
@@ -1066,9 +997,8 @@ class Handle:
         cnt = np.zeros(n, np.int32)
         need = C.c_int()
         idx = np.zeros(max(min(cap, 1 << 22), 1) if index_capacity is None else max(cap, 1), np.int32)
-        rc = self.lib.pbd_cluster_objects(self.h, len(clouds), descs, bx.ctypes.data if n else None, fr.ctypes.data if n else None, n,
-                                          cen.ctypes.data if n else None, cnt.ctypes.data if n else None, idx.ctypes.data,
-                                          len(idx) if index_capacity is None else cap, C.byref(need))
+        rc = self.lib.pbd_cluster_objects(self.h, len(clouds), descs, _lib.opt_ptr(bx), _lib.opt_ptr(fr), n, _lib.opt_ptr(cen),
+                                          _lib.opt_ptr(cnt), idx.ctypes.data, len(idx) if index_capacity is None else cap, C.byref(need))
         if rc == -4 and index_capacity is None:          # our own guess was short: once more with the total
             idx = np.zeros(max(need.value, 1), np.int32)
             rc = self.lib.pbd_cluster_objects(self.h, len(clouds), descs, bx.ctypes.data, fr.ctypes.data, n, cen.ctypes.data,
@@ -1167,6 +1097,82 @@ class Handle:
                 self.check(rc)
                 return dst
 
+    # ---- the stages and the detect family, as the classes below call them: arguments prepared, one library call each ----------
+    def features_pyramid(self, im: np.ndarray, feats: Sequence[np.ndarray]) -> None:
+        """pbd_features_pyramid: one HWC image with contiguous pixels (any row pitch), the levels' maps into `feats`"""
+        rows, cols, cn = im.shape
+        self.check(self.lib.pbd_features_pyramid(self.h, im.ctypes.data, rows, cols, cn, im.strides[0], _lib.DEPTH_CODE[im.dtype],
+                                                 _lib.ptr_array(feats)))
+
+    def get_pyramid_image(self, frame: int, level: int, img: np.ndarray) -> None:
+        self.check(self.lib.pbd_get_pyramid_image(self.h, frame, level, img.ctypes.data))
+
+    def conv_set_filters(self, filters: Sequence[np.ndarray]) -> None:
+        ks = np.array([f.shape[0] for f in filters], np.int32)
+        self.check(self.lib.pbd_conv_set_filters(self.h, len(filters), _lib.ptr_array(filters), _lib.ptr(ks, C.c_int)))
+
+    def conv_pdf(self, feats, shapes, resp) -> None:
+        """pbd_conv_pdf: shapes[level] = (rows, cols) in cells"""
+        _, _, rows, cols = _lib.shape_arrays(shapes)
+        self.check(self.lib.pbd_conv_pdf(self.h, len(feats), _lib.ptr_array(feats), rows, cols, _lib.ptr_array(resp)))
+
+    def dp_min(self, scores, shapes, *outs) -> None:
+        """pbd_dp_min: outs = Ix, Iy, Ik, rootv, rooti, each a list of one array per level"""
+        _, _, rows, cols = _lib.shape_arrays(shapes)
+        self.check(self.lib.pbd_dp_min(self.h, len(scores), rows, cols, _lib.ptr_array(scores), *[_lib.ptr_array(o) for o in outs]))
+        self.level_shapes = [(int(r), int(c)) for r, c in shapes]
+
+    def dp_argmin(self, scales, capacity: Optional[int] = None) -> List[Candidate]:
+        """pbd_dp_argmin; capacity 0 is a capacity: nothing fits, PBD_ERR_CAPACITY"""
+        sc = np.ascontiguousarray(scales, np.float32)
+        return self._host_list(self.lib.pbd_dp_argmin, (_lib.ptr(sc, C.c_float),), capacity)
+
+    # the detect calls take capacity None or 0 as max_candidates
+    def detect(self, im: np.ndarray, capacity: Optional[int] = None) -> List[Candidate]:
+        """pbd_detect (uint8) / pbd_detect_typed: one HWC image with contiguous pixels (any row pitch)"""
+        args = (im.ctypes.data, im.shape[0], im.shape[1], im.shape[2], im.strides[0])
+        if im.dtype == np.uint8:
+            return self._host_list(self.lib.pbd_detect, args, capacity or None)
+        return self._host_list(self.lib.pbd_detect_typed, args + (_lib.DEPTH_CODE[im.dtype],), capacity or None)
+
+    def detect_batch(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None) -> List[Candidate]:
+        """pbd_detect_batch: dense uint8 HWC frames of one shape"""
+        rows, cols, cn = frames[0].shape
+        return self._host_list(self.lib.pbd_detect_batch, (len(frames), _lib.ptr_array(frames), rows, cols, cn, cols * cn), capacity or None)
+
+    def submit_batch(self, frames: Sequence[np.ndarray]) -> None:
+        """pbd_detect_batch_submit: dense uint8 HWC frames of one shape"""
+        rows, cols, cn = frames[0].shape
+        self.check(self.lib.pbd_detect_batch_submit(self.h, len(frames), _lib.ptr_array(frames), rows, cols, cn, cols * cn))
+
+    def wait_batch(self, capacity: Optional[int] = None, raw: bool = False):
+        return self._host_list(self.lib.pbd_detect_batch_wait, (), capacity or None, raw, cached=True)
+
+    def submit_batch_device(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int) -> None:
+        self.check(self.lib.pbd_detect_batch_device_submit(self.h, nframes, d_frames_ptr, rows, cols, cn))
+
+    def detect_batch_device(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int, capacity: Optional[int] = None,
+                            raw: bool = False):
+        return self._host_list(self.lib.pbd_detect_batch_device, (nframes, d_frames_ptr, rows, cols, cn), capacity or None, raw, cached=True)
+
+    def detect_batch_device_out(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int, frame_offset: int,
+                                d_payload_ptr: int, capacity: int) -> None:
+        self.check(self.lib.pbd_detect_batch_device_out(self.h, nframes, d_frames_ptr, rows, cols, cn, frame_offset, d_payload_ptr, capacity))
+
+    def argmin_device_out(self, frame_offset: int, d_payload_ptr: int, capacity: int) -> None:
+        self.check(self.lib.pbd_argmin_device_out(self.h, frame_offset, d_payload_ptr, capacity))
+
+    def detect_frames(self, descs, cn: int, depth_code: int, capacity: Optional[int] = None, device: bool = False) -> List[Candidate]:
+        """pbd_detect_frames (host frames) / pbd_detect_frames_device of a pbd_frame[]"""
+        fn = self.lib.pbd_detect_frames_device if device else self.lib.pbd_detect_frames
+        return self._host_list(fn, (len(descs), descs, cn, depth_code), capacity or None)
+
+    def detect_frames_device_out(self, descs, cn: int, depth_code: int, frame_offset: int, d_payload_ptr: int, capacity: int) -> None:
+        """pbd_detect_frames_device_out: frames (device pointer, rows, cols, pitch) of any sizes, the candidate list left on the
+        device as detect_batch_device_out leaves it; asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_detect_frames_device_out(self.h, len(descs), _lib.frame_array(descs), cn, depth_code, frame_offset,
+                                                         d_payload_ptr, capacity))
+
 
 class HOGFeatures:
     """IFeatures (include/IFeatures.hpp:49-73) as implemented by HOGFeatures<float>."""
@@ -1176,7 +1182,7 @@ class HOGFeatures:
         self._scales = np.zeros(0, np.float32)
 
     def binsize(self) -> int:
-        return self.hd.lib.pbd_binsize(self.hd.h)
+        return self.hd.binsize()
 
     def nscales(self) -> int:
         return len(self._scales)
@@ -1186,21 +1192,10 @@ class HOGFeatures:
 
     def pyramid(self, im: np.ndarray) -> List[np.ndarray]:
         """pyramid(im, pyrafeatures): list of (H, W*flen) maps of T, fine to coarse."""
-        if im.dtype not in _lib.DEPTH_CODE:
-            # src/HOGFeatures.cpp:136-146: 8U / 16U / 32F / 64F, anything else is CV_StsUnsupportedFormat
-            raise PbdError(-2, f"image dtype {im.dtype}: uint8, uint16, float32 or float64")
-        if im.ndim == 2:
-            im = im[:, :, None]
-        rows, cols, cn = im.shape
-        es = im.dtype.itemsize
-        if not im.flags.c_contiguous and not (im.strides[2] == es and im.strides[1] == cn * es):
-            im = np.ascontiguousarray(im)
-        plan = self.hd.plan(rows, cols)
-        feats = [np.empty((int(r), int(c) * self.hd.flat.flen), self.hd.dtype)
-                 for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
-        arr = _lib.ptr_array(feats)
-        self.hd.check(self.hd.lib.pbd_features_pyramid(self.hd.h, im.ctypes.data, rows, cols, cn, im.strides[0],
-                                                       _lib.DEPTH_CODE[im.dtype], arr))
+        (im,), _, _, _ = _lib.image_frames([im], bad_dtype=-2)     # 8U / 16U / 32F / 64F, anything else is CV_StsUnsupportedFormat
+        plan = self.hd.plan(im.shape[0], im.shape[1])
+        feats = [np.empty((int(r), int(c) * self.hd.flat.flen), self.hd.dtype) for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
+        self.hd.features_pyramid(im, feats)
         self._scales = plan["scales"]
         return feats
 
@@ -1210,7 +1205,7 @@ class HOGFeatures:
         out = []
         for l in range(plan["nlevels"]):
             img = np.empty((int(plan["img_rows"][l]), int(plan["img_cols"][l]), cn), dtype)
-            self.hd.check(self.hd.lib.pbd_get_pyramid_image(self.hd.h, 0, l, img.ctypes.data))
+            self.hd.get_pyramid_image(0, l, img)
             out.append(img)
         return out
 
@@ -1223,21 +1218,17 @@ class SpatialConvolutionEngine:
 
     def setFilters(self, filters: Sequence[np.ndarray]) -> None:
         fl = [np.ascontiguousarray(f, self.hd.dtype) for f in filters]
-        ks = np.array([f.shape[0] for f in fl], np.int32)
-        arr = _lib.ptr_array(fl)
-        self.hd.check(self.hd.lib.pbd_conv_set_filters(self.hd.h, len(fl), arr, _lib.ptr(ks, C.c_int)))
+        self.hd.conv_set_filters(fl)
         self._nfilters = len(fl)
 
     def pdf(self, features: Sequence[np.ndarray]) -> List[np.ndarray]:
         """pdf(features, responses): responses[level] is (nfilters, H, W); responses[level][filter] as in the reference."""
         flen = self.hd.flat.flen
         feats = [np.ascontiguousarray(f, self.hd.dtype) for f in features]
-        rows = np.array([f.shape[0] for f in feats], np.int32)
-        cols = np.array([f.shape[1] // flen for f in feats], np.int32)
+        shapes = [(f.shape[0], f.shape[1] // flen) for f in feats]
         nf = getattr(self, "_nfilters", self.hd.flat.nfilters)
-        resp = [np.empty((nf, int(r), int(c)), self.hd.dtype) for r, c in zip(rows, cols)]
-        self.hd.check(self.hd.lib.pbd_conv_pdf(self.hd.h, len(feats), _lib.ptr_array(feats), _lib.ptr(rows, C.c_int),
-                                               _lib.ptr(cols, C.c_int), _lib.ptr_array(resp)))
+        resp = [np.empty((nf, r, c), self.hd.dtype) for r, c in shapes]
+        self.hd.conv_pdf(feats, shapes, resp)
         return resp
 
 
@@ -1252,28 +1243,35 @@ class DynamicProgram:
         Returns per level: Ix, Iy, Ik as (nslots, H, W) int32 (slot = pbd_ptr_slot(c, part) + parent mixture),
         rootv (ncomponents, H, W) float32, rooti (ncomponents, H, W) int32."""
         sc = [np.ascontiguousarray(s, self.hd.dtype) for s in scores]
-        rows = np.array([s.shape[1] for s in sc], np.int32)
-        cols = np.array([s.shape[2] for s in sc], np.int32)
+        shapes = [s.shape[1:] for s in sc]
         ns, nc = max(self.hd.flat.nslots, 1), self.hd.flat.ncomponents
-        Ix = [np.zeros((ns, int(r), int(c)), np.int32) for r, c in zip(rows, cols)]
-        Iy = [np.zeros((ns, int(r), int(c)), np.int32) for r, c in zip(rows, cols)]
-        Ik = [np.zeros((ns, int(r), int(c)), np.int32) for r, c in zip(rows, cols)]
-        rootv = [np.empty((nc, int(r), int(c)), self.hd.dtype) for r, c in zip(rows, cols)]
-        rooti = [np.empty((nc, int(r), int(c)), np.int32) for r, c in zip(rows, cols)]
-        self.hd.check(self.hd.lib.pbd_dp_min(self.hd.h, len(sc), _lib.ptr(rows, C.c_int), _lib.ptr(cols, C.c_int),
-                                             _lib.ptr_array(sc), _lib.ptr_array(Ix), _lib.ptr_array(Iy),
-                                             _lib.ptr_array(Ik), _lib.ptr_array(rootv), _lib.ptr_array(rooti)))
-        self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(rows, cols)]
+        Ix, Iy, Ik = ([np.zeros((ns, r, c), np.int32) for r, c in shapes] for _ in range(3))
+        rootv = [np.empty((nc, r, c), self.hd.dtype) for r, c in shapes]
+        rooti = [np.empty((nc, r, c), np.int32) for r, c in shapes]
+        self.hd.dp_min(sc, shapes, Ix, Iy, Ik, rootv, rooti)
         return Ix, Iy, Ik, rootv, rooti
 
     def argmin(self, scales: np.ndarray, capacity: Optional[int] = None) -> List[Candidate]:
         """argmin(parts, rootv, rooti, scales, Ix, Iy, Ik, candidates) on the result of the last min()."""
-        cap = self.hd.max_candidates if capacity is None else capacity     # 0 is a capacity: nothing fits, PBD_ERR_CAPACITY
-        buf = np.zeros(max(cap, 1) * self.hd.stride, np.int32)
-        n = C.c_int()
-        sc = np.ascontiguousarray(scales, np.float32)
-        self.hd.check(self.hd.lib.pbd_dp_argmin(self.hd.h, _lib.ptr(sc, C.c_float), buf.ctypes.data, cap, C.byref(n)))
-        return self.hd.unpack_candidates(buf, n.value)
+        return self.hd.dp_argmin(scales, capacity)
+
+
+def _dense_batch(frames: Sequence[np.ndarray]) -> List[np.ndarray]:
+    """the frames of a pbd_detect_batch* call: dense uint8 HWC arrays of one shape (the call takes one pitch for all of them)"""
+    fr = [np.ascontiguousarray(_lib.hwc(f), np.uint8) for f in frames]
+    assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
+    return fr
+
+
+def kept_subsequence(items: Sequence, records: np.ndarray, kept: np.ndarray) -> list:
+    """the items whose records a filter kept: `kept` is a subsequence of `records` (items[i]'s is records[i]), matched in order,
+    each kept record to the earliest input record equal to it that is still free"""
+    keep, k = [], 0
+    for item, r in zip(items, records):
+        if k < len(kept) and np.array_equal(kept[k], r):
+            keep.append(item)
+            k += 1
+    return keep
 
 
 class PartsBasedDetector:
@@ -1383,13 +1381,7 @@ class PartsBasedDetector:
         if not cands:
             return []
         rec = self.hd.pack_candidates(cands)
-        kept = self.hd.top_k(int(rec[:, 0].max()) + 1, k, rec)
-        keep, j = [], 0
-        for i, c in enumerate(cands):          # the kept records are the input's, in order
-            if j < len(kept) and np.array_equal(kept[j], rec[i]):
-                keep.append(c)
-                j += 1
-        return keep
+        return kept_subsequence(cands, rec, self.hd.top_k(int(rec[:, 0].max()) + 1, k, rec))
 
     def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93) from now on
@@ -1420,13 +1412,7 @@ class PartsBasedDetector:
         if not cands:
             return []
         rec = self.hd.pack_candidates(cands)
-        kept = self.hd.depth_prune(list(depths), rec, fx, width, tol)
-        keep, k = [], 0
-        for i, c in enumerate(cands):          # the kept records are the input's, in order
-            if k < len(kept) and np.array_equal(kept[k], rec[i]):
-                keep.append(c)
-                k += 1
-        return keep
+        return kept_subsequence(cands, rec, self.hd.depth_prune(list(depths), rec, fx, width, tol))
 
     def setDepthConsistency(self, zfactor: Optional[float] = 0.03) -> None:
         """detect(im, depth) then runs filterCandidatesByDepth(., depth, zfactor) before the suppression, as the reference's
@@ -1446,13 +1432,7 @@ class PartsBasedDetector:
         if not cands:
             return []
         rec = self.hd.pack_candidates(cands)
-        kept = self.hd.depth_consistency(list(depths), rec, zfactor)
-        keep, k = [], 0
-        for i, c in enumerate(cands):          # the kept records are the input's, in order
-            if k < len(kept) and np.array_equal(kept[k], rec[i]):
-                keep.append(c)
-                k += 1
-        return keep
+        return kept_subsequence(cands, rec, self.hd.depth_consistency(list(depths), rec, zfactor))
 
     def suppress(self, candidates: Sequence[Candidate], im_shapes, overlap: float) -> List[Candidate]:
         """Candidate.sort + Candidate.nonMaximaSuppression per frame, on the device (pbd_suppress): candidates grouped by
@@ -1515,10 +1495,7 @@ class PartsBasedDetector:
         """the frames' unsuppressed list (the handle's own suppression off) in a device payload of the detector's; the list
         never reaches the host"""
         import torch
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None]) for f in frames]
-        dt = fr[0].dtype
-        if dt not in _lib.DEPTH_CODE or any(f.dtype != dt or f.shape[2] != fr[0].shape[2] for f in fr):
-            raise PbdError(-1, "one call takes one image dtype (uint8, uint16, float32, float64) and one channel count")
+        fr, _, cn, code = _lib.image_frames([np.ascontiguousarray(f) for f in frames])     # dense, as their uploads are
         dev = torch.device("cuda", self._kw["device"])
         d_fr = [torch.from_numpy(f).to(dev) for f in fr]
         torch.cuda.synchronize(dev)
@@ -1526,17 +1503,31 @@ class PartsBasedDetector:
         pays = getattr(self, "_ev_pays", None)
         if pays is None or pays[0].numel() != words or pays[0].device != dev:
             pays = self._ev_pays = [torch.empty(words, dtype=torch.int32, device=dev) for _ in range(2)]
+        with self._unsuppressed():
+            descs = [(t.data_ptr(), f.shape[0], f.shape[1], f.strides[0]) for t, f in zip(d_fr, fr)]
+            self.hd.detect_frames_device_out(descs, cn, code, 0, pays[0].data_ptr(), self.hd.max_candidates)
+        return pays, d_fr
+
+    @contextlib.contextmanager
+    def _unsuppressed(self):
+        """the handle's suppression off for the calls inside; gives the overlap it had and has again afterwards (None: off)"""
         overlap = self.hd.nms_overlap
         if overlap is not None:
             self.hd.set_nms(None)
         try:
-            descs = [(t.data_ptr(), f.shape[0], f.shape[1], f.strides[0]) for t, f in zip(d_fr, fr)]
-            self.hd.check(self.hd.lib.pbd_detect_frames_device_out(self.hd.h, len(fr), _lib.frame_array(descs), fr[0].shape[2],
-                                                                   _lib.DEPTH_CODE[dt], 0, pays[0].data_ptr(), self.hd.max_candidates))
+            yield overlap
         finally:
             if overlap is not None:
                 self.hd.set_nms(overlap)
-        return pays, d_fr
+
+    def _read_payload(self, pay, cap: int, overflow: str):
+        """(count, the first min(count, cap) records on the host) of a device payload, once the handle's stream has drained: word 0
+        is the count, negative when the list the payload was made from had overflowed (PBD_ERR_CAPACITY with `overflow`)"""
+        self.hd.synchronize()
+        found = int(pay[0].item())
+        if found < 0:
+            raise PbdError(-4, overflow)
+        return found, pay[1:1 + min(found, cap) * self.hd.stride].cpu().numpy()
 
     def testModel(self, frames: Sequence[np.ndarray], overlap: float = 0.3, max_boxes: int = 1000) -> List[Candidate]:
         """testmodel.m: detect_fast at the model's threshold, then nms(box, overlap), per frame (nframes <= max_batch).  The
@@ -1546,11 +1537,7 @@ class PartsBasedDetector:
         pays, keep = self._unsuppressed_payload(frames)
         cap = self.hd.max_candidates
         self.hd.part_nms_device(len(frames), overlap, max_boxes, pays[0].data_ptr(), cap, 0, pays[1].data_ptr(), cap)
-        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
-        kept = int(pays[1][0].item())
-        if kept < 0:
-            raise PbdError(-4, f"more than max_candidates ({cap}) candidates were found before the suppression")
-        buf = pays[1][1:1 + kept * self.hd.stride].cpu().numpy()
+        kept, buf = self._read_payload(pays[1], cap, f"more than max_candidates ({cap}) candidates were found before the suppression")
         return self.hd.unpack_candidates(buf, kept)
 
     def testModelGtbox(self, frames: Sequence[np.ndarray], gtboxes, overlap: float = 0.3) -> List[Optional[Candidate]]:
@@ -1565,9 +1552,10 @@ class PartsBasedDetector:
         torch.cuda.synchronize(out.device)
         self.hd.best_overlap_device(gtboxes, overlap, pays[0].data_ptr(), self.hd.max_candidates, 0, out.data_ptr(),
                                     out.data_ptr() + 4 * n * self.hd.stride)
-        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
-        if int(pays[0][0].item()) > self.hd.max_candidates:
-            raise PbdError(-4, f"more than max_candidates ({self.hd.max_candidates}) candidates were found")
+        overflow = f"more than max_candidates ({self.hd.max_candidates}) candidates were found"
+        found, _ = self._read_payload(pays[0], 0, overflow)       # the count alone: detect's own, of every root it found
+        if found > self.hd.max_candidates:
+            raise PbdError(-4, overflow)
         host = out.cpu().numpy()
         rec, found = host[:n * self.hd.stride], host[n * self.hd.stride:]
         return self._found(rec, found)
@@ -1589,18 +1577,11 @@ class PartsBasedDetector:
         pays = getattr(self, "_dc_pays", None)     # the three payloads live with the detector, allocated once per handle
         if pays is None or pays[0].numel() != words or pays[0].device != dev:
             pays = self._dc_pays = [torch.empty(words, dtype=torch.int32, device=dev) for _ in range(3)]
-        overlap = self.hd.nms_overlap
-        if overlap is not None:
-            self.hd.set_nms(None)
-        try:
+        with self._unsuppressed() as overlap:
             if self._dprune is not None:           # prune at the roots, then the consistency filter, then the suppression
                 self.hd.bind_depth_device([(d_depth.data_ptr(), dd.shape[0], dd.shape[1], dd.strides[0])], _lib.DEPTH_CODE[dd.dtype])
-            self.hd.check(self.hd.lib.pbd_detect_frames_device_out(
-                self.hd.h, 1, _lib.frame_array([(d_im.data_ptr(), rows, cols, cols * cn * im.dtype.itemsize)]), cn,
-                _lib.DEPTH_CODE[im.dtype], 0, pays[0].data_ptr(), self.hd.max_candidates))
-        finally:
-            if overlap is not None:
-                self.hd.set_nms(overlap)
+            self.hd.detect_frames_device_out([(d_im.data_ptr(), rows, cols, cols * cn * im.dtype.itemsize)], cn,
+                                             _lib.DEPTH_CODE[im.dtype], 0, pays[0].data_ptr(), self.hd.max_candidates)
         self.hd.depth_consistency_device([(d_depth.data_ptr(), dd.shape[0], dd.shape[1], dd.strides[0])], _lib.DEPTH_CODE[dd.dtype],
                                          self._zfactor, pays[0].data_ptr(), self.hd.max_candidates, 0, pays[1].data_ptr(),
                                          self.hd.max_candidates)
@@ -1609,16 +1590,11 @@ class PartsBasedDetector:
             self.hd.suppress_device([(rows, cols)], overlap, pays[1].data_ptr(), self.hd.max_candidates, 0, pays[2].data_ptr(),
                                     self.hd.max_candidates)
             out = pays[2]
-        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
-        found = int(out[0].item())
-        if found < 0:
-            raise PbdError(-4, f"more than max_candidates ({self.hd.max_candidates}) candidates were found before the filter")
-        n = min(found, cap)
-        buf = out[1:1 + n * self.hd.stride].cpu().numpy()
+        found, buf = self._read_payload(out, cap, f"more than max_candidates ({self.hd.max_candidates}) candidates were found before the filter")
         self.features_._scales = self.hd.plan(rows, cols)["scales"]
         if found > cap:
             raise PbdError(-4, f"{found} candidates kept, capacity {cap}")
-        return self.hd.unpack_candidates(buf, n)
+        return self.hd.unpack_candidates(buf, found)
 
     def detect(self, im: np.ndarray, depth: Optional[np.ndarray] = None, capacity: Optional[int] = None) -> List[Candidate]:
         """detect(im[, depth], candidates).  `depth` is ignored as in the reference (:91-93) unless setDepthConsistency(zfactor)
@@ -1627,30 +1603,19 @@ class PartsBasedDetector:
         (the reference's `if (!depth.empty())`).  With setDepthPrune on, `depth` (the frame's rows x cols) also prunes the roots
         before the walk: prune -> consistency filter -> suppression."""
         self._need()
-        if im.dtype not in _lib.DEPTH_CODE:
-            raise PbdError(-2, f"image dtype {im.dtype}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
-        if im.ndim == 2:
-            im = im[:, :, None]
-        es = im.dtype.itemsize
-        if not (im.strides[2] == es and im.strides[1] == im.shape[2] * es):
-            im = np.ascontiguousarray(im)
-        rows, cols, cn = im.shape
+        (im,), _, _, _ = _lib.image_frames([im], bad_dtype=-2)
         if self._zfactor is not None and depth is not None:
             return self._detect_depth(im, depth, capacity)
-        cap = capacity or self.hd.max_candidates
-        buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
         self._bind(None if depth is None else [depth])
-        if im.dtype == np.uint8:
-            self.hd.check(self.hd.lib.pbd_detect(self.hd.h, im.ctypes.data, rows, cols, cn, im.strides[0], buf.ctypes.data,
-                                                 cap, C.byref(n)))
-        else:
-            self.hd.check(self.hd.lib.pbd_detect_typed(self.hd.h, im.ctypes.data, rows, cols, cn, im.strides[0],
-                                                       _lib.DEPTH_CODE[im.dtype], buf.ctypes.data, cap, C.byref(n)))
+        out = self.hd.detect(im, capacity)
+        self.features_._scales = self._plan_levels(im.shape[0], im.shape[1])["scales"]
+        return out
+
+    def _plan_levels(self, rows: int, cols: int) -> dict:
+        """the pyramid plan of a rows x cols frame, its levels' shapes noted on the handle for the max-marginals"""
         plan = self.hd.plan(rows, cols)
-        self.features_._scales = plan["scales"]
         self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
-        return self.hd.unpack_candidates(buf, n.value)
+        return plan
 
     def modelVector(self) -> np.ndarray:
         """the model vector w = [biasw | defw | filters] in T (include/pbd.h pbd_model_vector; Model.to_vector)"""
@@ -1662,12 +1627,7 @@ class PartsBasedDetector:
         device (pbd_examples): (hdr (n, hdr_words) int32, values (n, values) T).  examples.dot(hdr, values, w) gives w . x,
         examples.densify(hdr, values, len(w)) the dense vectors."""
         self._need()
-        if isinstance(candidates, np.ndarray):
-            rec = candidates
-        else:
-            cands = list(candidates)
-            rec = self.hd.pack_candidates(cands) if cands else np.zeros((0, self.hd.stride), np.int32)
-        return self.hd.examples(rec)
+        return self.hd.examples(self._candidate_records(candidates)[0])
 
     def _candidate_records(self, candidates):
         if isinstance(candidates, np.ndarray):
@@ -1763,7 +1723,7 @@ class PartsBasedDetector:
             red = red.contiguous()
             grid = torch.zeros(red.numel(), dtype=torch.uint8, device=dev)
             keep = torch.zeros(red.numel(), dtype=torch.uint8, device=dev)
-            real = _lib.REAL_F32 if self.hd.dtype == np.float32 else _lib.REAL_F64
+            real = _lib.real_code(self.hd.dtype)
             self.hd.grid_nms_device([r for r, _ in shapes], [c for _, c in shapes], real, red.data_ptr(), None, sz, grid.data_ptr())
             self.hd.top_k_cells_device([red.numel()], real, red.data_ptr(), grid.data_ptr(), k, keep.data_ptr())
             idx = torch.nonzero(keep).reshape(-1).cpu().numpy()
@@ -1834,7 +1794,7 @@ class PartsBasedDetector:
         odesc = [(o.data_ptr(), o.shape[0], o.shape[1], o.stride(0) * o.element_size()) for o in outs]
         torch.cuda.synchronize(dev)
         self.hd.augment_frames_device(descs, cn, code, jobs, odesc)
-        self.hd.check(self.hd.lib.pbd_synchronize(self.hd.h))
+        self.hd.synchronize()
         return outs
 
     def warpPositives(self, frames, boxes, filter: int = 0, bias: int = 0, skip_small: bool = True):
@@ -1872,7 +1832,7 @@ class PartsBasedDetector:
         import torch
         if isinstance(w_or_qp, torch.Tensor):
             t = w_or_qp.contiguous()
-            if not t.is_cuda or t.dtype not in (torch.float32, torch.float64) or t.numel() != self.hd.lib.pbd_model_vector_len(self.hd.h):
+            if not t.is_cuda or t.dtype not in (torch.float32, torch.float64) or t.numel() != self.hd.model_vector_len():
                 raise PbdError(-1, "a float32 / float64 device tensor of model_vector_len values")
             torch.cuda.current_stream(t.device).synchronize()
             self.hd.set_model_vector_device(t.data_ptr(), np.float32 if t.dtype == torch.float32 else np.float64)
@@ -1983,40 +1943,19 @@ class PartsBasedDetector:
         self._need()
         if len({tuple(f.shape) for f in frames}) > 1:
             return self.detect_frames(frames, capacity, depths)
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None], np.uint8) for f in frames]
-        rows, cols, cn = fr[0].shape
-        assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
-        cap = capacity or self.hd.max_candidates
-        buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
+        fr = _dense_batch(frames)
         self._bind(depths)
-        self.hd.check(self.hd.lib.pbd_detect_batch(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn,
-                                                   buf.ctypes.data, cap, C.byref(n)))
-        plan = self.hd.plan(rows, cols)
-        self.hd.level_shapes = [(int(r), int(c)) for r, c in zip(plan["feat_rows"], plan["feat_cols"])]
-        return self.hd.unpack_candidates(buf, n.value)
+        out = self.hd.detect_batch(fr, capacity)
+        self._plan_levels(fr[0].shape[0], fr[0].shape[1])
+        return out
 
     def detect_frames(self, frames: Sequence[np.ndarray], capacity: Optional[int] = None, depths=None) -> List[Candidate]:
         """pbd_detect_frames: frames of any sizes in one call; the records of one detect() per frame, concatenated,
         `frame` = index in the list.  depths: one depth image per frame (its rows x cols), for setDepthPrune."""
         self._need()
-        fr = [f if f.ndim == 3 else f[:, :, None] for f in frames]
-        dt = fr[0].dtype
-        if any(f.dtype != dt for f in fr):
-            raise PbdError(-1, "one call takes one image dtype: " + ", ".join(sorted({str(f.dtype) for f in fr})))
-        if dt not in _lib.DEPTH_CODE:
-            raise PbdError(-2, f"image dtype {dt}: uint8, uint16, float32 or float64 (src/HOGFeatures.cpp:136-146)")
-        fr = [np.ascontiguousarray(f) for f in fr]
-        if len({f.shape[2] for f in fr}) != 1:
-            raise PbdError(-1, "one call takes one channel count")
-        descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in fr])
-        cap = capacity or self.hd.max_candidates
-        buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
+        fr, descs, cn, code = _lib.image_frames(frames, bad_dtype=-2)
         self._bind(depths)
-        self.hd.check(self.hd.lib.pbd_detect_frames(self.hd.h, len(fr), descs, fr[0].shape[2], _lib.DEPTH_CODE[dt],
-                                                    buf.ctypes.data, cap, C.byref(n)))
-        return self.hd.unpack_candidates(buf, n.value)
+        return self.hd.detect_frames(descs, cn, code, capacity)
 
     def detect_regions(self, image, rects, capacity: Optional[int] = None, depth=None) -> List[Candidate]:
         """Regions (x, y, w, h) of one device image -- a torch uint8 tensor, HWC (or HW), on this detector's device -- in
@@ -2044,9 +1983,6 @@ class PartsBasedDetector:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(image.device))
         torch.cuda.ExternalStream(self.hd.stream_ptr(), device=image.device).wait_event(ev)
-        cap = capacity or self.hd.max_candidates
-        buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
         if self._dprune is not None and depth is not None:
             codes = {torch.uint8: 0, torch.int16: 2, torch.float32: 5, torch.float64: 6}
             if depth.dtype not in codes or depth.device != image.device or depth.dim() != 2 or tuple(depth.shape) != (H, W) \
@@ -2054,9 +1990,7 @@ class PartsBasedDetector:
                 raise PbdError(-1, "detect_regions: depth is a 2-D tensor of the image's rows x cols on its device")
             es, dp = depth.element_size(), depth.stride(0) * depth.element_size()
             self.hd.bind_depth_device([(depth.data_ptr() + y * dp + x * es, h, w, dp) for (x, y, w, h) in rects], codes[depth.dtype])
-        self.hd.check(self.hd.lib.pbd_detect_frames_device(self.hd.h, len(descs), _lib.frame_array(descs), cn, 0,
-                                                           buf.ctypes.data, cap, C.byref(n)))
-        out = self.hd.unpack_candidates(buf, n.value)
+        out = self.hd.detect_frames(_lib.frame_array(descs), cn, 0, capacity, device=True)
         for c in out:
             c.offset = (int(rects[c.frame][0]), int(rects[c.frame][1]))
         return out
@@ -2066,62 +2000,50 @@ class PartsBasedDetector:
         """pbd_detect_frames_device_out: frames (device pointer, rows, cols, pitch) of any sizes, the candidate list left on
         the device as detect_batch_device_out leaves it; asynchronous on the handle's stream"""
         self._need()
-        self.hd.check(self.hd.lib.pbd_detect_frames_device_out(self.hd.h, len(descs), _lib.frame_array(descs), cn, depth_code,
-                                                               frame_offset, d_payload_ptr, capacity))
+        self.hd.detect_frames_device_out(descs, cn, depth_code, frame_offset, d_payload_ptr, capacity)
 
     def submit_batch(self, frames: Sequence[np.ndarray], depths=None) -> None:
         """pbd_detect_batch_submit: stage + transfer + enqueue the whole path for `frames` without waiting (at most
         two batches in flight); `wait_batch` returns the results in submission order.  depths: one depth image per frame, for
         setDepthPrune (copied before the call returns)."""
         self._need()
-        fr = [np.ascontiguousarray(f if f.ndim == 3 else f[:, :, None], np.uint8) for f in frames]
-        rows, cols, cn = fr[0].shape
-        assert all(f.shape == fr[0].shape for f in fr), "a batch holds equally sized frames"
+        fr = _dense_batch(frames)
         self._bind(depths)
-        self.hd.check(self.hd.lib.pbd_detect_batch_submit(self.hd.h, len(fr), _lib.ptr_array(fr), rows, cols, cn, cols * cn))
+        self.hd.submit_batch(fr)
 
     def wait_batch(self, capacity: Optional[int] = None, raw: bool = False):
+        """pbd_detect_batch_wait: the oldest submitted batch's candidates; raw: (the handle's record buffer, count), valid until
+        the next wait_batch / detect_batch_device"""
         self._need()
-        cap = capacity or self.hd.max_candidates
-        if not hasattr(self, "_buf") or self._buf.size < cap * self.hd.stride:
-            self._buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
-        self.hd.check(self.hd.lib.pbd_detect_batch_wait(self.hd.h, self._buf.ctypes.data, cap, C.byref(n)))
-        if raw:
-            return self._buf, n.value
-        return self.hd.unpack_candidates(self._buf, n.value)
+        return self.hd.wait_batch(capacity, raw)
+
+    @property
+    def _buf(self) -> Optional[np.ndarray]:
+        """the record buffer wait_batch / detect_batch_device fill and return with raw=True (the handle's, reused)"""
+        return self.hd._buf
 
     def submit_batch_device(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int) -> None:
         """pbd_detect_batch_device_submit: like submit_batch for frames already resident in device memory"""
         self._need()
-        self.hd.check(self.hd.lib.pbd_detect_batch_device_submit(self.hd.h, nframes, d_frames_ptr, rows, cols, cn))
+        self.hd.submit_batch_device(d_frames_ptr, nframes, rows, cols, cn)
 
     def detect_batch_device_out(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int, frame_offset: int,
                                 d_payload_ptr: int, capacity: int) -> None:
         """pbd_detect_batch_device_out: the whole path, candidate list left on the device in int32[1 + capacity*stride]
         ([found | sorted records], frame ids + frame_offset); asynchronous on the handle's stream"""
         self._need()
-        self.hd.check(self.hd.lib.pbd_detect_batch_device_out(self.hd.h, nframes, d_frames_ptr, rows, cols, cn, frame_offset,
-                                                              d_payload_ptr, capacity))
+        self.hd.detect_batch_device_out(d_frames_ptr, nframes, rows, cols, cn, frame_offset, d_payload_ptr, capacity)
 
     def argmin_device_out(self, frame_offset: int, d_payload_ptr: int, capacity: int) -> None:
         """pbd_argmin_device_out: re-emit the candidate list of the batch still resident on the device (after an overflow)"""
         self._need()
-        self.hd.check(self.hd.lib.pbd_argmin_device_out(self.hd.h, frame_offset, d_payload_ptr, capacity))
+        self.hd.argmin_device_out(frame_offset, d_payload_ptr, capacity)
 
     def detect_batch_device(self, d_frames_ptr: int, nframes: int, rows: int, cols: int, cn: int,
                             capacity: Optional[int] = None, raw: bool = False):
         """frames already resident in device memory (e.g. a torch uint8 tensor's data_ptr())."""
         self._need()
-        cap = capacity or self.hd.max_candidates
-        if not hasattr(self, "_buf") or self._buf.size < cap * self.hd.stride:
-            self._buf = np.zeros(cap * self.hd.stride, np.int32)
-        n = C.c_int()
-        self.hd.check(self.hd.lib.pbd_detect_batch_device(self.hd.h, nframes, d_frames_ptr, rows, cols, cn,
-                                                          self._buf.ctypes.data, cap, C.byref(n)))
-        if raw:
-            return self._buf, n.value
-        return self.hd.unpack_candidates(self._buf, n.value)
+        return self.hd.detect_batch_device(d_frames_ptr, nframes, rows, cols, cn, capacity, raw)
 
 
 class DetectorPool:

@@ -112,9 +112,7 @@ def threshold_of(scores) -> float:
     return float(np.float32(r[int(math.ceil(THRESH_QUANTILE * len(r))) - 1]))
 
 
-def _frame(im):
-    """rows x cols x channels of a host array or a device tensor (a view)"""
-    return im if im.ndim == 3 else im[:, :, None]
+_frame = _lib.hwc           # rows x cols x channels of a host array or a device tensor (a view)
 
 
 def _is_device(im) -> bool:
@@ -147,17 +145,7 @@ def _finish(info: dict, its: List[dict]) -> dict:
 # ---- the device loop ----------------------------------------------------------------------------------------------------
 def _detect_latent(hd, crops, boxes, overlap, mixtures):
     """pbd_detect_latent on crops that are views of their frames (rows `strides[0]` apart): nothing is copied on the host"""
-    for f in crops:
-        if f.strides[2] != f.itemsize or f.strides[1] != f.shape[2] * f.itemsize:
-            raise ValueError("a positive's image must have contiguous pixels")
-    descs = _lib.frame_array([(f.ctypes.data, f.shape[0], f.shape[1], f.strides[0]) for f in crops])
-    bx = np.ascontiguousarray(boxes, np.int32).reshape(len(crops), -1, 4)
-    mix = None if mixtures is None else np.ascontiguousarray(mixtures, np.int32).reshape(len(crops), bx.shape[1])
-    rec = np.zeros((len(crops), hd.stride), np.int32)
-    found = np.zeros(len(crops), np.int32)
-    hd.check(hd.lib.pbd_detect_latent(hd.h, len(crops), descs, crops[0].shape[2], _lib.DEPTH_CODE[crops[0].dtype], bx.ctypes.data,
-                                      None if mix is None else mix.ctypes.data, float(overlap), rec.ctypes.data, found.ctypes.data))
-    return rec, found
+    return hd.detect_latent(crops, boxes, overlap, mixtures)
 
 
 def _detect_latent_device(hd, crops, boxes, overlap, mixtures):
