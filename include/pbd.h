@@ -159,14 +159,19 @@ int pbd_pyramid_plan(pbd_handle *h, int rows, int cols, int *nlevels, int *img_r
  * refused with PBD_ERR_INVALID (here and in pbd_detect_typed): non-finite input is an error, not a silently different result. */
 int pbd_features_pyramid(pbd_handle *h, const void *img, int rows, int cols, int channels,
                          size_t stride_bytes, int depth_code, void *const *feat);
-/* the resampled level images of the last pbd_features_pyramid / pbd_detect call (for tests) */
+/* the resampled level images of the last pbd_features_pyramid / pbd_detect call (for tests), addressed as pbd_get_stage below;
+ * PBD_ERR_STATE when the last call that wrote the handle's pyramid was neither: none yet, pbd_conv_pdf and pbd_dp_min (which start
+ * from uploaded maps), pbd_detect_latent (whose level images are its twin's) and pbd_warp_positives (whose patches replaced them).
+ * pbd_conv_set_filters and a model update leave the level images readable. */
 int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst);
 
 /* Level sharding (new surface; the reference has no multi-device mode): pyramid levels are independent through HOG,
  * convolution and the dynamic program (src/DynamicProgram.cpp:115-119 reads only scores[n] of the same level), so ONE
  * frame can be split over `world` GPUs -- handle `rank` then computes only its share of the levels (longest-processing-
  * time assignment over the level sizes, the same on every rank) and returns only their candidates; the union over the
- * ranks is the full result.  pbd_pyramid_plan reports 0 x 0 feature maps for the levels of other ranks.  (1, 0..): off. */
+ * ranks is the full result.  pbd_pyramid_plan reports 0 x 0 feature maps for the levels of other ranks.  (1, 0..): off.
+ * A call that changes neither value leaves the resident result; one that changes the shard drops it (the image plans depend on
+ * the shard), and every read-back gives PBD_ERR_STATE until the next detect call. */
 int pbd_set_level_shard(pbd_handle *h, int rank, int world);
 
 /* Per-frame post-processing (opt-in; off on a new handle): what every caller of the reference runs after detect() --
@@ -785,6 +790,7 @@ int pbd_part_poses_device(pbd_handle *h, const int32_t *d_payload, int capacity,
  * apply, and the detect path of the handle is not touched.  Output per frame f: cand + f * pbd_candidate_stride() = the single
  * highest-scoring root over all levels, components and positions (ties: the first in (level, component, y, x) order), as a
  * normal record (`frame` = f, part boxes of the walk); found[f] = 1 iff its score > -5e9 (no masked term used).
+ * The level images stay in the twin: pbd_get_pyramid_image gives PBD_ERR_STATE after it.
  * The call leaves a resident result: pbd_examples* then give the positives' feature vectors (offsets in this handle's model
  * vector) and pbd_get_stage reads the stages of that run, addressed (frame, level) as after a mixed call: PBD_STAGE_RESPONSES is
  * the MASKED responses, one plane per (component, part, mixture) in global mixture order; PBD_STAGE_ROOTV / _ROOTI are the
@@ -905,7 +911,10 @@ int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int cap
  * T, mm_p[m][y][x] is exactly the maximum over the configurations with p of type m at (x, y).
  * pbd_max_marginals(h, frame): the planes of one frame of the resident dynamic-program result (after pbd_detect*, equal-size
  *   frames, or pbd_dp_min: frame 0), kept on the device until the next detect call, pbd_dp_min, model update or
- *   pbd_max_marginals.  Asynchronous on pbd_stream().  The resident detection result is not changed.  Device memory held:
+ *   pbd_max_marginals.  Asynchronous on pbd_stream().  The resident detection result is not changed.
+ *   The planes belong to the result they were computed from:
+ *   every call that replaces, cuts or drops the resident result drops the marginals with it
+ *   (pbd_features_pyramid, pbd_conv_pdf, pbd_conv_set_filters, pbd_detect_latent and pbd_warp_positives as well).  Device memory held:
  *   (2 sizeof(T) + 5) NJ + sizeof(T) NS bytes per cell of the frame, plus scratch of sizeof(T) JGmax + 2 P max(JGmax, NJ) bytes per
  *   cell (NJ: the (part, type) pairs of the model, NS its pointer slots, JGmax the transforms of its largest depth group, P the
  *   bytes of a position: 1 while no map side exceeds 256, else 2).
@@ -989,7 +998,8 @@ int pbd_marginal_poses_device(pbd_handle *h, int n, const int32_t *d_seeds, cons
  * The call works in the handle's pyramid and HOG workspaces, so the resident detect result is dropped as after
  * pbd_conv_set_filters: pbd_get_stage, pbd_examples*, pbd_argmin_device_out and pbd_dp_argmin give PBD_ERR_STATE until the next
  * detect call (a refused call and a call with nboxes == 0 leave it).  The detect path itself is untouched: a detect call gives
- * the same bytes before and after. */
+ * the same bytes before and after.  Nothing of the dropped result stays readable, its features and level images neither:
+ * pbd_get_pyramid_image, pbd_part_scores*, pbd_score_placements* and pbd_max_marginals likewise give PBD_ERR_STATE. */
 int pbd_warp_positives(pbd_handle *h, int nframes, const struct pbd_frame *frames, int channels, int depth_code, int nboxes,
                        const int32_t *boxes, int filter, int bias, int skip_small, int32_t *hdr, void *values, int32_t *kept);
 int pbd_warp_positives_device(pbd_handle *h, int nframes, const struct pbd_frame *d_frames, int channels, int depth_code, int nboxes,
@@ -1170,7 +1180,8 @@ int pbd_qp_entries(pbd_qp *q, int first, int count, int32_t *hdr, float *values,
  *   a 1 x 2 row collapses it to (x + y) / 2 in both coordinates), and max_iter exists.
  * info[p]: the picked trial, its iterations and its sumdist.  sumdist_all / iters_all ([nparts][trials], either may be NULL):
  *   every trial's.  pbd_cluster_parts is synchronous and takes host pointers; pbd_cluster_parts_device takes device pointers
- *   (def and every output; parent and K stay on the host), is asynchronous on pbd_stream() and reads def in place. */
+ *   (def and every output; parent and K stay on the host), is asynchronous on pbd_stream() and reads def in place.
+ * PBD_ERR_STATE while a batch is in flight.  pbd_cluster_parts* leave the resident detect result alone. */
 struct pbd_cluster_info {
     int32_t best_trial, iterations;
     double sumdist;
@@ -1222,7 +1233,8 @@ int pbd_dp_min(pbd_handle *h, int nlevels, const int *rows, const int *cols, con
  * (frame, level, component, root_y, root_x): the raster order of the reference's Math::find per (level, component)
  * (:208-216); its order ACROSS levels is nondeterministic (#pragma omp critical, :246-251).  The order is produced on the
  * device (ordered compaction, no sort); when more than `capacity` are found, the first `capacity` of that order are
- * returned with PBD_ERR_CAPACITY. */
+ * returned with PBD_ERR_CAPACITY.  PBD_ERR_STATE without one: none yet, after pbd_features_pyramid, pbd_conv_pdf, pbd_conv_set_filters,
+ * a model update, pbd_warp_positives, pbd_detect_latent or a mixed-size call. */
 int pbd_dp_argmin(pbd_handle *h, const float *scales, int32_t *cand, int capacity, int *ncand);
 
 /* ---- PartsBasedDetector<T>::detect (include/PartsBasedDetector.hpp:172-173, src/PartsBasedDetector.cpp:69-95).
@@ -1251,7 +1263,9 @@ int pbd_detect_batch(pbd_handle *h, int nframes, const void *const *imgs, int ro
  * records are delivered and counted in *ncand; or, with pbd_set_nms on, more than max_candidates before the suppression: *ncand = 0 -- has
  * consumed its batch: the next wait returns the NEXT batch, and a caller that wants the rest of the list has to submit the
  * frames again.  A caller that keeps a count of batches in flight (detector.DetectorPool, pbdhost::FrameStream) therefore
- * counts a failed wait as a collected batch.  A refused submit enqueues nothing and leaves the batches in flight as they were. */
+ * counts a failed wait as a collected batch.  A refused submit enqueues nothing and leaves the batches in flight as they were.
+ * A submit replaces the resident result where it enqueues.  After the last wait the resident result is that of the batch submitted last
+ * (the staged read-back, pbd_examples*, pbd_argmin_device_out and the rest read it as after pbd_detect_batch of those frames). */
 int pbd_detect_batch_submit(pbd_handle *h, int nframes, const void *const *imgs, int rows, int cols, int channels,
                             size_t stride_bytes);
 int pbd_detect_batch_wait(pbd_handle *h, int32_t *cand, int capacity, int *ncand);
@@ -1273,7 +1287,9 @@ int pbd_detect_batch_device(pbd_handle *h, int nframes, const void *d_frames, in
  * this buffer to all_gather_into_tensor as it is; nothing passes through the host).  ASYNCHRONOUS: the call returns once
  * the work is enqueued on pbd_stream(); order later work behind that stream (or call pbd_synchronize).
  * pbd_argmin_device_out re-emits the list of the batch still resident from the last pbd_detect* call -- used after a
- * capacity overflow (word 0 > capacity) with a larger buffer; the dynamic program is not run again. */
+ * capacity overflow (word 0 > capacity) with a larger buffer; the dynamic program is not run again.
+ * PBD_ERR_STATE without such a batch: none yet, or the last writer was one of the staged calls (pbd_features_pyramid, pbd_conv_pdf,
+ * pbd_dp_min), pbd_conv_set_filters, a model update, pbd_warp_positives or pbd_detect_latent. */
 int pbd_detect_batch_device_out(pbd_handle *h, int nframes, const void *d_frames, int rows, int cols, int channels,
                                 int frame_offset, int32_t *d_payload, int capacity);
 int pbd_argmin_device_out(pbd_handle *h, int frame_offset, int32_t *d_payload, int capacity);
@@ -1313,8 +1329,13 @@ int pbd_detect_frames_device_out(pbd_handle *h, int nframes, const pbd_frame *fr
 /* ---- staged read-back of the last pbd_detect* or pbd_detect_latent call (tests, profiling) ----
  * A stage is readable only if the last computation produced it: after pbd_conv_set_filters the responses and DP
  * results are gone, and after pbd_dp_min (which starts from uploaded responses) PBD_STAGE_FEATURES is PBD_ERR_STATE.
+ * After pbd_features_pyramid only PBD_STAGE_FEATURES and the level images are readable (the responses and DP results of an
+ * earlier call are gone); after pbd_conv_pdf PBD_STAGE_FEATURES (the uploaded maps) and PBD_STAGE_RESPONSES.
  * After pbd_detect_latent the stages are those of its masked run (see there), whose responses have one plane per
- * (component, part, mixture), not per filter; after a model update nothing of a latent result is readable.
+ * (component, part, mixture), not per filter; after a model update or pbd_conv_set_filters nothing of a latent result is readable
+ * (pbd_get_stage, pbd_examples* and pbd_part_scores* give PBD_ERR_STATE: its features live in the twin with everything else).
+ * Frames and levels are those of the last call alone: an address an earlier, larger result had is PBD_ERR_INVALID, and
+ * pbd_get_stage looks at the address before it looks at the stage (a bad address of a stage that is not held is PBD_ERR_INVALID).
  * A refused call leaves the previous result readable. */
 enum { PBD_STAGE_FEATURES = 0, PBD_STAGE_RESPONSES = 1, PBD_STAGE_ROOTV = 2, PBD_STAGE_ROOTI = 3 };
 int pbd_get_stage(pbd_handle *h, int stage, int frame, int level, void *dst, size_t dst_bytes);

@@ -2156,6 +2156,7 @@ int pbd_conv_set_filters(pbd_handle *h, int nfilters, const void *const *filters
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (int rc = upload_filters(h, nfilters, filters, ksize)) return rc;
         h->res.drop_conv();   // the resident responses were those of the old bank
+        if (h->lat) h->lat->res.drop_conv();   // a latent result lives in the twin: it goes as it does after a model update
         return revalidate_bank(h);
     });
 }

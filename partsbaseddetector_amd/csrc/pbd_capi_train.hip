@@ -725,9 +725,17 @@ int pbd_examples(pbd_handle *h, const int32_t *cand, int ncand, int frame_offset
         HIPCHK(h, hipMemcpyAsync(h->ex_rec.as<int32_t>() + 1, cand, (size_t)ncand * stride * sizeof(int32_t), hipMemcpyHostToDevice,
                                  h->stream));
         if (int rc = enqueue_examples(h, h->ex_rec.as<int32_t>(), ncand, frame_offset, d_hdr, d_val)) return rc;
+        // an example's values come back up to its nvalues: what lies past them in the workspace is an earlier call's, and the
+        // caller's bytes there stay ("values past nvalues are not written")
+        std::vector<char> hv(vb);
         HIPCHK(h, hipMemcpyAsync(hdr, d_hdr, hb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(values, d_val, vb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(hv.data(), d_val, vb, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        const size_t vrow = (size_t)h->ex_values * h->rs;
+        for (int i = 0; i < ncand; ++i) {
+            const int nv = std::min(std::max(hdr[(size_t)i * h->ex_hdr_words + 3], 0), h->ex_values);
+            memcpy(static_cast<char *>(values) + vrow * i, hv.data() + vrow * i, (size_t)nv * h->rs);
+        }
         return PBD_OK;
     });
 }

@@ -304,7 +304,7 @@ struct Resident {
     bool latent = false;             // pbd_detect_latent: the result lives in the handle's latent twin (pbd_examples* read it there)
     bool marginals = false;          // pbd_max_marginals: the planes of frame mm_frame are held for this result (whoever replaces
     int mm_frame = 0;                // the record drops them with it)
-    void drop_conv() { resp = dp = marginals = false; }   // the filter bank changed
+    void drop_conv() { resp = dp = marginals = false; }   // the filter bank changed (the caller cuts the latent twin's record too)
     void clear() { *this = Resident{}; }
 };
 
