@@ -3,7 +3,7 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--pad X[,Y]] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //            [--part-scores] [--marginal-pose PART]
@@ -13,6 +13,9 @@
 //           (pbd_set_root_nms: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales)); not with --staged
 //   --top-k K: at most K candidates per image: only the K best roots among those the threshold (and --root-nms, --depth-prune) leave
 //           are walked and listed (pbd_set_top_k); not with --staged
+//   --pad X[,Y]: the padded pyramid of the Matlab detector (pbd_set_padding): every feature level grows by X (Y; Y = X when not
+//           given) cells of the boundary occlusion feature on each side, so that roots and parts can lie outside the image; the
+//           root cell a candidate line prints is then a cell of the padded plane.  Not with --depth-prune or --marginal-pose
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT.  0 exact, 1 fma,
 //           2 / 3 matrix cores bf16 / fp16 (5x5 banks), 4 fp64 matrix cores (--double), 5 / 6 matrix cores bf16 / fp16 for
 //           every filter size and mixed banks (PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY; not with --double)
@@ -64,6 +67,7 @@ using namespace pbdhost;
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
 static int g_top_k = 0;                   // --top-k
+static int g_padx = 0, g_pady = 0;        // --pad
 static bool g_part_scores = false;        // --part-scores
 static int g_marginal_part = -1;          // --marginal-pose
 static bool g_prune = false;              // --depth-prune fx,width,tol
@@ -96,6 +100,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
+    pbd.setPadding(g_padx, g_pady);
     pbd.distributeModel(model);
     std::vector<std::vector<Candidate> > candidates;
     pbd.detectBatch(ims, candidates);
@@ -184,6 +189,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
+    pbd.setPadding(g_padx, g_pady);
     if (g_prune) pbd.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
@@ -192,6 +198,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         fs.setRootNMS(g_root_nms);
         fs.setTopK(g_top_k);
+        fs.setPadding(g_padx, g_pady);
         if (g_prune) fs.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
         std::vector<Candidate> first, cur;
         size_t got = 0;
@@ -237,6 +244,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     } else if (depth && dcz >= 0) {
         // filterCandidatesByDepth on the unsuppressed list (its counts), then the chain detect(im, depth) runs with the setting on
         PartsBasedDetector<T> raw(0, conv_mode);
+        raw.setPadding(g_padx, g_pady);
         raw.distributeModel(model);
         std::vector<Candidate> all, kept;
         raw.detect(im, all);
@@ -380,7 +388,7 @@ static int run_augment(Model &model, const Image &im, double degrees, bool mirro
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--pad x[,y]] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
     const char *augment_path = NULL;
@@ -417,6 +425,15 @@ int main(int argc, char **argv)
             char tail = 0;
             if (std::sscanf(argv[++i], "%d%c", &g_top_k, &tail) != 1 || g_top_k < 0 || g_top_k > (1 << 30)) {
                 std::fprintf(stderr, "--top-k takes a count, 0 (off) or 1..1073741824\n");
+                return -1;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--pad") && i + 1 < argc) {
+            char tail = 0;
+            const int got = std::sscanf(argv[++i], "%d,%d%c", &g_padx, &g_pady, &tail);
+            if (got == 1) g_pady = g_padx;
+            if (got < 1 || got > 2 || g_padx < 0 || g_padx > 31 || g_pady < 0 || g_pady > 31) {
+                std::fprintf(stderr, "--pad takes x[,y], each 0..31 cells\n");
                 return -1;
             }
         }
@@ -469,6 +486,10 @@ int main(int argc, char **argv)
     }
     if (g_prune && (!depth_path || staged)) {
         std::fprintf(stderr, "--depth-prune needs --depth, not with --staged\n");
+        return -1;
+    }
+    if ((g_padx || g_pady) && (g_prune || g_marginal_part >= 0)) {
+        std::fprintf(stderr, "--pad: depth pruning and max-marginals take no padded pyramid: not with --depth-prune or --marginal-pose\n");
         return -1;
     }
     if (g_top_k && staged) {

@@ -174,6 +174,36 @@ int pbd_get_pyramid_image(pbd_handle *h, int frame, int level, uint8_t *dst);
  * the shard), and every read-back gives PBD_ERR_STATE until the next detect call. */
 int pbd_set_level_shard(pbd_handle *h, int rank, int world);
 
+/* The padded pyramid (new surface; opt-in, off on a new handle).  The Matlab detector pads every feature
+ * level by a border of cells holding 0 on channels 0 .. 30 and 1 on channel 31, the boundary occlusion feature
+ * (featpyramid.m:36-45), places roots and parts on the larger map and takes the pad off in the box arithmetic
+ * (detect.m:266-270); the reference left the call commented out (src/HOGFeatures.cpp:147-148), so that no root or part can lie
+ * outside the map.  With padding (padx, pady) every non-empty level of every plan the handle builds AFTERWARDS -- single frame,
+ * equal-size batch, pbd_detect_frames*, regions, the _submit / _wait form and pbd_detect_latent* -- is
+ * (feat_rows + 2 pady) x (feat_cols + 2 padx) cells: the interior is bit for bit the unpadded plane, a pad cell holds +0 (sign
+ * bit clear) on channels 0 .. 30 and 1 on channel 31.  An empty level (too small, or another rank's under level sharding) stays
+ * empty.  Convolution in every mode, the distance transforms, the dynamic program, the find, root NMS and top-K run on the padded
+ * planes as on any others; everything a plan derives from level sizes (offsets, tile tables, the uint8 / int16 choice of the
+ * position planes at a longest side of 256, workspace sizes, the level-shard assignment) derives from the padded sizes.  A
+ * part's rectangle of plane cell (x, y) is that of cell (x - padx, y - pady): Point(x - padx - 1, y - pady - 1) * scale, cvRound.
+ * root_x / root_y of a record, the cells of pbd_part_scores* / pbd_score_placements*, the windows of pbd_examples* (beyond the
+ * padded plane the border rule holds as before) and every plane of pbd_get_stage are in PLANE coordinates; the image cell is
+ * root_x - padx.  pbd_pyramid_plan reports the padded feat_rows / feat_cols (image sizes, scales, the level count and the
+ * frame-size checks do not change); pbd_features_pyramid writes padded planes.  PBD_CONV_EXACT computes channel 31 like the
+ * others on a padded plan (its shortcut needs the channel to be 0 in every cell).  pbd_dp_argmin / pbd_argmin_device_out walk
+ * with the pad of the resident plan; after pbd_conv_pdf / pbd_dp_min on the caller's maps that is the handle's setting when
+ * they ran: the caller's planes are taken to be padded by it.  Patch plans of pbd_warp_positives* are never padded.
+ * pbd_set_nms / pbd_suppress (boxes are cut to the frame as before), pbd_set_walk, pbd_set_root_nms, pbd_set_top_k, level
+ * sharding, pbd_detect_latent* (a ground-truth box may lie partly outside the frame) and the post-detection calls that take
+ * records and images work on a padded handle.
+ * 0 <= padx, pady <= 31 (the largest filter side), else PBD_ERR_INVALID; (0, 0): off.  PBD_ERR_STATE while a batch is in
+ * flight.  A call that changes neither value leaves the resident result; one that changes a value drops it and the cached
+ * plans, and every read-back gives PBD_ERR_STATE until the next writing call.  A model update keeps the setting.
+ * PBD_ERR_UNSUPPORTED (a later change can lift these): a non-zero padding while pbd_set_depth_prune is enabled, and
+ * pbd_set_depth_prune(cfg != NULL) while the padding is non-zero; pbd_max_marginals, pbd_get_marginals and pbd_marginal_poses*
+ * on a padded resident result. */
+int pbd_set_padding(pbd_handle *h, int padx, int pady);
+
 /* Per-frame post-processing (opt-in; off on a new handle): what every caller of the reference runs after detect() --
  * Candidate::sort(candidates) then Candidate::nonMaximaSuppression(im, candidates, overlap) (cells/detect.cpp:237-238,
  * ros/Node.cpp:192-196; include/Candidate.hpp:91-99,277-304) -- on the device, on the handle's stream, after argmin.  Per frame:
@@ -518,7 +548,9 @@ int pbd_depth_consistency_device(pbd_handle *h, int nframes, const struct pbd_fr
  * (no model and no scales are read).  Conventions of pbd_depth_consistency* above, word for word: frame_offset, in place allowed
  * for the host form, *nout / word 0 = the kept count (which may exceed the capacity), an input word 0 that is negative or > capacity
  * gives -1, a record whose frame index is out of range or whose nparts is outside 1..max parts is dropped (host form: refused), no
- * host synchronisation in the device form, the resident result untouched, PBD_ERR_STATE while a batch is in flight. */
+ * host synchronisation in the device form, the resident result untouched, PBD_ERR_STATE while a batch is in flight.
+ * pbd_set_depth_prune(h, cfg != NULL) on a handle with a non-zero pbd_set_padding is PBD_ERR_UNSUPPORTED, as is a non-zero padding
+ * while the pruning is enabled: the rule has no padded form yet. */
 typedef struct pbd_depth_prune_cfg { float fx, width, tol; } pbd_depth_prune_cfg;
 int pbd_set_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg);
 int pbd_bind_depth(pbd_handle *h, int nframes, const struct pbd_frame *depth, int depth_code);
@@ -921,7 +953,8 @@ int pbd_score_placements_device(pbd_handle *h, const int32_t *d_payload, int cap
  *   PBD_ERR_STATE: no resident dynamic-program result (none yet, after a model update or pbd_conv_set_filters), a latent result
  *   (pbd_detect_latent), a batch in flight.  PBD_ERR_INVALID: frame outside the result.  PBD_ERR_UNSUPPORTED: a model on the
  *   sequential schedule (a filter id shared inside a component), fp16-resident responses (modes 3 and 6), a mixed-size result
- *   (pbd_detect_frames), a level-sharded handle (world > 1).
+ *   (pbd_detect_frames), a level-sharded handle (world > 1), a padded result (pbd_set_padding; pbd_get_marginals,
+ *   pbd_marginals_device and pbd_marginal_poses* refuse it likewise).
  * pbd_get_marginals(h, level, what, dst, dst_bytes): one level's block, synchronous.  PBD_MM_VALUES / PBD_MM_DOWN: T[NJ][H][W];
  *   PBD_MM_PARENT_X / _Y / _K: int32[NJ][H][W], -1 in every plane of a root.  PBD_ERR_STATE without resident marginals.
  * pbd_marginals_device(h, level, &d): the device pointer of the level's mm block T[NJ][H][W] (for pbd_grid_nms_device /

@@ -268,6 +268,14 @@ inline void grid_nms(pbd_handle *h, const typename Tr::Mat &src, int sz, const u
     check<Tr>(h, pbd_grid_nms(h, 1, &rows, &cols, RealCode<T>::value, Tr::cptr(s), mask, sz, dst));
 }
 
+// pbd_set_padding: every plan the handle builds afterwards pads its feature levels by (padx, pady) cells of the boundary occlusion
+// feature (0 on channels 0 .. 30, 1 on channel 31), so that roots and parts can lie outside the frame; (0, 0): off
+template <class Tr>
+inline void set_padding(pbd_handle *h, int padx, int pady)
+{
+    check<Tr>(h, pbd_set_padding(h, padx, pady));
+}
+
 // pbd_set_top_k: at most k candidates per frame from every later walk of this handle -- the k best roots of the frame among those
 // the threshold and the other root filters leave; k = 0: off
 template <class Tr>

@@ -601,6 +601,7 @@ class PartsBasedDetector {
     int walk_;
     int root_nms_;
     int top_k_;
+    int padx_, pady_;
     bool depth_on_;
     float zfactor_;
     bool prune_on_;
@@ -615,7 +616,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), top_k_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
+          root_nms_(0), top_k_(0), padx_(0), pady_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
           planes_(0) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
@@ -629,6 +630,7 @@ public:
         if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
         if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
         if (top_k_) pbdbind::set_top_k<HostTraits<T> >(h_, top_k_);
+        if (padx_ || pady_) pbdbind::set_padding<HostTraits<T> >(h_, padx_, pady_);
         if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
         name_ = model.name();
         planes_ = 0;
@@ -671,6 +673,17 @@ public:
         if (!mask.empty() && mask.size() != n) throw Error(PBD_ERR_INVALID, "gridNMS: the mask has the plane's size");
         dst.assign(n, 0);
         pbdbind::grid_nms<HostTraits<T> >(h_, src, sz, mask.empty() ? NULL : &mask[0], n ? &dst[0] : NULL);
+    }
+    // new surface: the padded pyramid of the Matlab detector from now on (pbd_set_padding): every feature level grows by padx / pady
+    // cells of the boundary occlusion feature on each side, so that roots and parts can lie outside the frame; (0, 0) turns it off
+    // (the default).  A Candidate's root is then a cell of the padded plane; its part boxes are frame coordinates as always.  Kept
+    // across distributeModel().  Not with setDepthPrune; maxMarginals / marginalPoses refuse a padded result.
+    void setPadding(int padx, int pady)
+    {
+        if (padx < 0 || padx > 31 || pady < 0 || pady > 31) throw Error(PBD_ERR_INVALID, "padding: 0..31 cells");
+        if (h_) pbdbind::set_padding<HostTraits<T> >(h_, padx, pady);
+        padx_ = padx;
+        pady_ = pady;
     }
     // new surface: at most k candidates per frame from now on (pbd_set_top_k): only the k best roots of each frame -- by score, ties
     // to the earlier cell -- among those the threshold, depth pruning and root NMS leave are walked and returned; k = 0 turns it
@@ -1375,6 +1388,11 @@ public:
     void setRootNMS(int sz)
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_root_nms<HostTraits<T> >(h_[i], sz);
+    }
+    // every handle detects on the padded pyramid (PartsBasedDetector::setPadding); nothing may be pending
+    void setPadding(int padx, int pady)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_padding<HostTraits<T> >(h_[i], padx, pady);
     }
     // every handle keeps at most k candidates per frame (PartsBasedDetector::setTopK); nothing may be pending
     void setTopK(int k)

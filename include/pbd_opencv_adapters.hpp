@@ -229,6 +229,15 @@ inline void hipSetRootNMS(pbd_handle *h, int sz)
     pbdbind::set_root_nms<CvTraits<T> >(h, sz);
 }
 
+// The padded pyramid of the Matlab detector (featpyramid.m:36-45) for every later hipDetect / hipDetectBatch of this handle
+// (pbd_set_padding): every feature level grows by padx / pady cells of the boundary occlusion feature on each side, and an object
+// cut off by the frame edge is found with the parts that are not visible placed in the pad.  (0, 0) turns it off
+template <typename T>
+inline void hipSetPadding(pbd_handle *h, int padx, int pady)
+{
+    pbdbind::set_padding<CvTraits<T> >(h, padx, pady);
+}
+
 // At most k candidates per frame from every later hipDetect / hipDetectBatch of this handle (pbd_set_top_k): the k best roots of
 // the frame among those the threshold and the other root filters leave; k = 0 turns it off
 template <typename T>

@@ -65,6 +65,7 @@ SYMBOLS = [
     "pbd_augment_plan", "pbd_augment_points", "pbd_augment_frames", "pbd_augment_frames_device", "pbd_detect_latent_device",
     "pbd_part_scores", "pbd_part_scores_device", "pbd_score_placements", "pbd_score_placements_device",
     "pbd_max_marginals", "pbd_get_marginals", "pbd_marginals_device", "pbd_marginal_poses", "pbd_marginal_poses_device",
+    "pbd_set_padding",
 ]
 
 
@@ -296,6 +297,7 @@ def load():
     lib.pbd_set_level_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
     lib.pbd_set_walk.argtypes = [C.c_void_p, C.c_int]
+    lib.pbd_set_padding.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pbd_set_root_nms.argtypes = [C.c_void_p, C.c_int]
     lib.pbd_grid_nms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p]

@@ -202,7 +202,9 @@ void cache_plan(pbd_handle *h, std::unique_ptr<Plan> P)
 
 // The host side of an image plan (no device work): level table, scales and resize tables of an unsharded rows x cols frame.
 // PBD_OK, or PBD_ERR_INVALID with the reason in `err`.
-int image_plan_host(int rows, int cols, int sbin, int interval, Plan &Pr, std::string &err)
+// padx / pady: the padded pyramid (pbd_set_padding) -- every non-empty feature map grows by the pad on each side, and all
+// that is derived from level sizes below and in finish_plan_tables follows.
+int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pady, Plan &Pr, std::string &err)
 {
     Plan *P = &Pr;
     char buf[160];
@@ -215,6 +217,7 @@ int image_plan_host(int rows, int cols, int sbin, int interval, Plan &Pr, std::s
         return PBD_ERR_INVALID;
     }
     P->kind = 0; P->rows = rows; P->cols = cols;
+    P->padded = padx != 0 || pady != 0;
     P->nlevels = n; P->scales = scales; P->interval = interval;
     P->lv.resize(n);
     std::vector<ResizeTabX> tabx;
@@ -234,6 +237,11 @@ int image_plan_host(int rows, int cols, int sbin, int interval, Plan &Pr, std::s
         d.blk_rows = (int)roundf((float)lr[l] / (float)sbin);
         d.cols = std::max(d.blk_cols - 2, 0);
         d.rows = std::max(d.blk_rows - 2, 0);
+        d.padx = d.pady = 0;
+        if (d.rows > 0 && d.cols > 0) {   // an empty level is never padded
+            d.padx = padx; d.pady = pady;
+            d.cols += 2 * padx; d.rows += 2 * pady;
+        }
         d.src_level = l >= interval ? l - interval : -1;
         d.img_off = pix; d.blk_off = blk; d.cell_off = cell;
         d.tab_x = d.tab_y = 0;
@@ -295,7 +303,7 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
     auto P = std::make_unique<Plan>();
     {
         std::string err;
-        if (int rc = image_plan_host(rows, cols, h->sbin, h->interval, *P, err)) return fail(h, rc, "%s", err.c_str());
+        if (int rc = image_plan_host(rows, cols, h->sbin, h->interval, h->padx, h->pady, *P, err)) return fail(h, rc, "%s", err.c_str());
     }
     const int n = P->nlevels;
     long long blk = P->blk_per_frame, cell = P->cell_per_frame;
@@ -320,7 +328,7 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
         blk = 0; cell = 0;
         for (int l = 0; l < n; ++l) {
             LevelDesc &d = P->lv[l];
-            if (owner[l] != h->shard_rank) d.blk_rows = d.blk_cols = d.rows = d.cols = 0;
+            if (owner[l] != h->shard_rank) d.blk_rows = d.blk_cols = d.rows = d.cols = d.padx = d.pady = 0;
             d.blk_off = blk; d.cell_off = cell;
             blk += (long long)d.blk_rows * d.blk_cols;
             cell += (long long)d.rows * d.cols;
@@ -351,6 +359,7 @@ int get_dims_plan(pbd_handle *h, int nlevels, const int *rows, const int *cols, 
         if (p->kind == 1 && p->key_dims == key) { *out = p.get(); return PBD_OK; }
     auto P = std::make_unique<Plan>();
     P->kind = 1; P->key_dims = key; P->nlevels = nlevels; P->interval = h->interval;
+    P->padded = h->padx != 0 || h->pady != 0;
     P->lv.resize(nlevels);
     P->scales.assign(nlevels, 1.f);
     long long cell = 0;
@@ -358,6 +367,7 @@ int get_dims_plan(pbd_handle *h, int nlevels, const int *rows, const int *cols, 
         LevelDesc &d = P->lv[l];
         memset(&d, 0, sizeof d);
         d.rows = rows[l]; d.cols = cols[l]; d.src_level = -1; d.cell_off = cell;
+        d.padx = h->padx; d.pady = h->pady;   // the caller's planes are taken to be padded by the handle's setting (the walk's rectangles)
         cell += (long long)rows[l] * cols[l];
     }
     P->cell_per_frame = cell;
@@ -395,6 +405,7 @@ void mixed_append(Plan &M, const Plan &Q)
     M.fdim.push_back(make_int2(Q.rows, Q.cols));
     M.key_dims.push_back(Q.rows); M.key_dims.push_back(Q.cols);
     M.mixed_frames += 1;
+    M.padded = M.padded || Q.padded;
 }
 
 
@@ -474,7 +485,7 @@ int get_mixed_plan(pbd_handle *h, int nframes, const int *rows, const int *cols,
             if (!B) {
                 B = std::make_unique<Plan>();
                 std::string err;
-                if (int rc = image_plan_host(rows[f], cols[f], h->sbin, h->interval, *B, err))
+                if (int rc = image_plan_host(rows[f], cols[f], h->sbin, h->interval, h->padx, h->pady, *B, err))
                     return fail(h, rc, "frame %d: %s", f, err.c_str());
             }
             Q = B.get();
@@ -1024,7 +1035,7 @@ void launch_hog_stage(pbd_handle *h, Plan &P, int cn, int depth, int f0, int nb,
     }
     {
         ProfScope ps(h, PBD_K_HOG_FEAT, st);
-        launch_hog_feat(hp, nb, h->f64, st);
+        launch_hog_feat(hp, nb, h->f64, P.padded, st);
     }
 }
 
@@ -1574,7 +1585,8 @@ int enqueue_features(pbd_handle *h, Plan &P, int nframes, const FrameSrc &src, i
     if (int rc = alloc_features(h, P, nframes, cn, depth)) return rc;
     launch_features(h, P, d_frames, cn, depth, 0, nframes, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->res.features = h->res.c31_zero = true;
+    h->res.features = true;
+    h->res.c31_zero = !P.padded;   // a pad cell holds 1 on channel 31
     return PBD_OK;
 }
 
@@ -1748,7 +1760,8 @@ int enqueue_detect_mixed(pbd_handle *h, Plan &P, int nframes, const pbd_frame *f
     if (int rc = alloc_features(h, P, 1, cn, depth)) return rc;
     launch_features_mixed(h, P, h->fd_tab.as<FrameDesc>(), cn, depth, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->res.features = h->res.c31_zero = true;
+    h->res.features = true;
+    h->res.c31_zero = !P.padded;   // a pad cell holds 1 on channel 31
     if (int rc = run_conv(h, P, 1)) return rc;
     if (mask) {   // pbd_detect_latent: the responses of the latent bank, masked before the dynamic program
         LatentParams lp = *mask;
@@ -1855,7 +1868,7 @@ int pbd_debug_mixed_plan(int sbin, int interval, int nframes, const int *rows, c
         for (int f = 0; f < nframes; ++f) {
             Plan Q;
             std::string err;
-            if (rows[f] < 1 || cols[f] < 1 || image_plan_host(rows[f], cols[f], sbin, interval, Q, err)) return PBD_ERR_INVALID;
+            if (rows[f] < 1 || cols[f] < 1 || image_plan_host(rows[f], cols[f], sbin, interval, 0, 0, Q, err)) return PBD_ERR_INVALID;
             mixed_append(M, Q);
         }
         mixed_finish(M, interval);
@@ -2044,6 +2057,28 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
     });
 }
 
+int pbd_set_padding(pbd_handle *h, int padx, int pady)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (padx < 0 || padx > kConvMaxK || pady < 0 || pady > kConvMaxK)
+            return fail(h, PBD_ERR_INVALID, "padding (%d, %d) outside 0..%d", padx, pady, kConvMaxK);
+        if ((padx || pady) && h->dprune)
+            return fail(h, PBD_ERR_UNSUPPORTED, "a padded pyramid with depth pruning on (pbd_set_depth_prune(h, NULL) first)");
+        if (padx == h->padx && pady == h->pady) return PBD_OK;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->padx = padx; h->pady = pady;
+        // every plan carries the pad it was built with (the explicit-size plans too: their walks take it off)
+        h->res.clear();
+        h->plans.clear();
+        if (h->lat) {
+            h->lat->padx = padx; h->lat->pady = pady;
+            h->lat->res.clear();
+            h->lat->plans.clear();
+        }
+        return PBD_OK;
+    });
+}
+
 int pbd_set_nms(pbd_handle *h, int enable, float overlap)
 {
     return entry(h, true, kIdle, [&]() -> int {
@@ -2079,6 +2114,8 @@ int pbd_set_depth_prune(pbd_handle *h, const pbd_depth_prune_cfg *cfg)
 {
     return entry(h, true, kIdle, [&]() -> int {
         if (!cfg) { h->dprune = false; return PBD_OK; }
+        if (h->padx || h->pady)
+            return fail(h, PBD_ERR_UNSUPPORTED, "depth pruning on a padded pyramid (pbd_set_padding(h, 0, 0) first)");
         if (int rc = depth_prune_rule(h, *cfg, &h->dprune_rule)) return rc;   // (a refused cfg leaves the setting as it was)
         h->dprune = true;                 // the resident result stays: it does not depend on the setting
         return PBD_OK;

@@ -102,6 +102,8 @@ void build_tables(const pbd_handle *h, MmTables &t)
 
 int check_marginals_held(pbd_handle *h)
 {
+    if (h->res.plan && h->res.plan->padded)
+        return fail(h, PBD_ERR_UNSUPPORTED, "max-marginals of a padded result (pbd_set_padding)");
     if (!h->res.plan || !h->res.marginals)
         return fail(h, PBD_ERR_STATE, "no max-marginals are held (pbd_max_marginals computes them; a detect call, pbd_dp_min or a model update drops them)");
     return PBD_OK;
@@ -161,6 +163,7 @@ int pbd_max_marginals(pbd_handle *h, int frame)
         if (!r.plan || !r.resp || !r.dp)
             return fail(h, PBD_ERR_STATE, "no resident dynamic-program result (pbd_detect* or pbd_dp_min computes one; a model update leaves none)");
         if (r.plan->kind == 2) return fail(h, PBD_ERR_UNSUPPORTED, "max-marginals of a mixed-size result (pbd_detect_frames)");
+        if (r.plan->padded) return fail(h, PBD_ERR_UNSUPPORTED, "max-marginals of a padded result (pbd_set_padding): the mirrored transforms take no pad");
         if (frame < 0 || frame >= r.frames) return fail(h, PBD_ERR_INVALID, "frame %d outside 0..%d", frame, r.frames - 1);
         Plan &P = *r.plan;
         r.marginals = false;          // the planes of an earlier call are overwritten from here on

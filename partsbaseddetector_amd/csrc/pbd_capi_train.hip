@@ -786,6 +786,7 @@ static int detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, in
             if (int rc = pbd_create(&m, &cfg, &t)) return fail(h, rc, "latent twin: %s", pbd_last_error(nullptr));
             h->lat.reset(t);
             t->walk_mode = h->walk_mode;
+            t->padx = h->padx; t->pady = h->pady;
             std::vector<int4> gm(T);
             for (int c = 0; c < h->NC; ++c)
                 for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)

@@ -143,10 +143,12 @@ template <> __device__ __forceinline__ int round_mul<double>(int a, double s) { 
 
 // a part's rectangle in the frame (src/DynamicProgram.cpp:238-241): Rect(Point(x - 1, y - 1) * scale, that + Point(ks, ks) *
 // scale - Point(1, 1)) -- cv::Rect from two points orders them; (x1, y1) .. (x2, y2) are its corners, w = x2 - x1, h = y2 - y1
+// (x, y) is a cell of the level's planes; a padded level (LevelDesc::padx / pady, pbd_set_padding) starts padx / pady cells left of
+// and above the image, which the rectangle takes off again (detect.m:266-270)
 struct PartRect { int x1, y1, x2, y2; };
-template <typename R> __device__ __forceinline__ PartRect part_rect(int x, int y, int ks, R scale)
+template <typename R> __device__ __forceinline__ PartRect part_rect(int x, int y, int ks, R scale, const LevelDesc &d)
 {
-    const int x1 = round_mul<R>(x - 1, scale), y1 = round_mul<R>(y - 1, scale);
+    const int x1 = round_mul<R>(x - d.padx - 1, scale), y1 = round_mul<R>(y - d.pady - 1, scale);
     const int x2 = x1 + round_mul<R>(ks, scale) - 1, y2 = y1 + round_mul<R>(ks, scale) - 1;
     return {min(x1, x2), min(y1, y2), max(x1, x2), max(y1, y2)};
 }

@@ -147,6 +147,7 @@ struct Plan {
     int nrows_flat = 0, ncols_flat = 0;
     bool ptr8 = false;              // no feature map side exceeds 256: positions fit uint8 (back-pointer planes at half the bytes)
     int longest = 0;                // longest side of any feature map of the plan (rows / columns of the distance transform)
+    bool padded = false;            // built under a non-zero pbd_set_padding: its levels carry the pad (LevelDesc::padx / pady)
     int ntiles = 0;
     // device tables
     DevTable<LevelDesc> d_lv;
@@ -372,6 +373,7 @@ struct Handle : ErrCtx {
     std::vector<std::unique_ptr<Plan>> plans;
     Resident res;
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
+    int padx = 0, pady = 0;          // the padded pyramid (pbd_set_padding): every plan built afterwards carries it; the latent twin follows
     int walk_mode = 0;               // PBD_WALK_* (pbd_set_walk), read when a walk is enqueued; the latent twin follows its handle
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
     float nms_overlap = 0.f;

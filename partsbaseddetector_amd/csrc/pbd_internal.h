@@ -20,7 +20,8 @@ namespace pbd {
 struct LevelDesc {
     int img_rows, img_cols;   // level image (pixels)
     int blk_rows, blk_cols;   // HOG blocks = round(dim / sbin)             (src/HOGFeatures.cpp:174)
-    int rows, cols;           // feature / response map = blocks - 2         (:175)
+    int rows, cols;           // feature / response map = blocks - 2         (:175), plus the pad on every side
+    int padx, pady;           // cells of padding left and right / above and below the map (pbd_set_padding); 0 on an empty level
     int src_level;            // pyrDown source level (level - interval), -1 for resized levels
     int tab_x, tab_y;         // offsets into the resize tables (levels < interval)
     long long img_off;        // pixel offset of the level image (multiply by channels for bytes)
@@ -527,7 +528,7 @@ void launch_resize_runs(const PyrParams &p, hipStream_t s);
 void launch_pyrdown_runs(const PyrParams &p, hipStream_t s);
 // `f64` selects the reference's T=double instantiation (every real-typed buffer then holds doubles)
 void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s);
-void launch_hog_feat(const HogParams &p, int nframes, bool f64, hipStream_t s);
+void launch_hog_feat(const HogParams &p, int nframes, bool f64, bool padded, hipStream_t s);
 void launch_conv(const ConvParams &p, int nframes, bool f64, hipStream_t s);
 int conv_occupancy(int nw);
 int conv_mfma_occupancy(bool f16);

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kDprThreads) void k_depth_prune_roots(ArgminParams 
         const int frame = (int)(o / per_frame);
         const RootCell rc = root_cell(p.lv, 0, p.nlevels, p.NC, o - (long long)frame * per_frame);
         const int ks = p.walk[p.walk_off[rc.comp]].ksize[p.rooti[o]];
-        const PartRect r = part_rect<R>(rc.x, rc.y, ks, (R)p.scales[rc.level]);
+        const PartRect r = part_rect<R>(rc.x, rc.y, ks, (R)p.scales[rc.level], p.lv[rc.level]);
         const int w = r.x2 - r.x1, h = r.y2 - r.y1;                  // the words k_argmin_walk writes
         ok = depth_plausible<D>(r.x1, r.y1, w, h, a.frames[p.lv_frame ? p.lv_frame[rc.level] : frame], a.rule);
     }

@@ -939,7 +939,7 @@ __global__ __launch_bounds__(64) void k_argmin_walk(ArgminParams p)
         }
         visited[pidx][threadIdx.x] = x | (y << 16);
         visited_m[pidx][threadIdx.x] = (uint8_t)m;
-        const PartRect r = part_rect<R>(x, y, walk[pidx].ksize[m], scale);
+        const PartRect r = part_rect<R>(x, y, walk[pidx].ksize[m], scale, d);
         rects[pidx * 4 + 0] = r.x1;
         rects[pidx * 4 + 1] = r.y1;
         rects[pidx * 4 + 2] = r.x2 - r.x1;

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void k_latent_mask(LatentParams p)
         const int f = p.lv_frame[lo];
         bool keep = !p.mix || p.mix[f * p.nparts + g.x] < 0 || p.mix[f * p.nparts + g.x] == g.y;
         if (keep) {
-            const PartRect r = part_rect<R>(x, y, g.z, (R)p.scales[lo]);
+            const PartRect r = part_rect<R>(x, y, g.z, (R)p.scales[lo], d);
             const long long rx1 = r.x1, ry1 = r.y1, rx2 = r.x2, ry2 = r.y2;
             const int4 b = p.boxes[f * p.nparts + g.x];
             const long long iw = max(0LL, min(rx2, (long long)b.z) - max(rx1, (long long)b.x) + 1);

@@ -841,6 +841,9 @@ void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s)
 // ------------------------------------------------------------------------------------------------
 // Normalisation and the 32 output channels per interior cell (src/HOGFeatures.cpp:286-340).
 // One thread per cell.  The four normalisers are evaluated in double as the reference does.
+// PAD: the levels carry a pad (LevelDesc::padx / pady, pbd_set_padding).  The thread of plane cell (y, x) computes interior cell
+// (y - pady, x - padx) as above, or writes a pad cell: +0 on channels 0 .. 30 and 1 on channel 31 (featpyramid.m:36-45).  The
+// cells leave as in the unpadded form, so a store instruction still covers 1 KB of consecutive addresses.
 // ------------------------------------------------------------------------------------------------
 template <typename R>
 __device__ __forceinline__ R hog_norm(const R *n, int stride)
@@ -849,7 +852,7 @@ __device__ __forceinline__ R hog_norm(const R *n, int stride)
     return (R)(1.0 / sqrt((double)s4 + 0.0001));
 }
 
-template <typename R>
+template <typename R, bool PAD>
 __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -866,7 +869,14 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
     if (valid) {
     const LevelCell c = level_cell<2>(p.lv, l, idx);
     const LevelDesc &d = c.d;
-    const int y = c.y, x = c.x;
+    int y = c.y, x = c.x;
+    bool interior = true;
+    if constexpr (PAD) {
+        y -= d.pady; x -= d.padx;
+        interior = y >= 0 && y < d.blk_rows - 2 && x >= 0 && x < d.blk_cols - 2;
+    }
+    R out[32];
+    if (interior) {
     const int bw = d.blk_cols;
     const R *norm = static_cast<const R *>(p.norm) + (size_t)frame * p.blk_per_frame + d.blk_off;
     const R n1 = hog_norm<R>(norm + (size_t)(y + 1) * bw + (x + 1), bw);
@@ -879,7 +889,6 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
     for (int o = 0; o < 18; ++o) hv[o] = hist[(size_t)o * p.blk_per_frame];
 
     const R lim = (R)0.2;
-    R out[32];
     R t1 = (R)0, t2 = (R)0, t3 = (R)0, t4 = (R)0;
 #pragma unroll
     for (int o = 0; o < 18; ++o) {
@@ -905,6 +914,11 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
     out[29] = (R)(0.2357 * (double)t3);
     out[30] = (R)(0.2357 * (double)t4);
     out[31] = (R)0;
+    } else {
+#pragma unroll
+        for (int o = 0; o < 31; ++o) out[o] = (R)0;
+        out[31] = (R)1;
+    }
     typedef R rv4 __attribute__((ext_vector_type(4)));
     if constexpr (VIA_LDS) {
 #pragma unroll
@@ -930,12 +944,17 @@ __global__ __launch_bounds__(256) void k_hog_feat(HogParams p)
     }
 }
 
-void launch_hog_feat(const HogParams &p, int nframes, bool f64, hipStream_t s)
+void launch_hog_feat(const HogParams &p, int nframes, bool f64, bool padded, hipStream_t s)
 {
     if (p.cell_per_frame == 0) return;
     dim3 grid((unsigned)((p.cell_per_frame + 255) / 256), nframes);
-    if (f64) PBD_LAUNCH(k_hog_feat<double>, grid, dim3(256), 0, s, p);
-    else PBD_LAUNCH(k_hog_feat<float>, grid, dim3(256), 0, s, p);
+    if (padded) {
+        if (f64) PBD_LAUNCH((k_hog_feat<double, true>), grid, dim3(256), 0, s, p);
+        else PBD_LAUNCH((k_hog_feat<float, true>), grid, dim3(256), 0, s, p);
+        return;
+    }
+    if (f64) PBD_LAUNCH((k_hog_feat<double, false>), grid, dim3(256), 0, s, p);
+    else PBD_LAUNCH((k_hog_feat<float, false>), grid, dim3(256), 0, s, p);
 }
 
 }  // namespace pbd

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kMmDecodeThreads) void k_mm_decode(MmParams p)
                 const WalkPos ch = walk_child<PT>(pl, w, par[0], par[1], par[2], true);
                 place[3 * q] = ch.x; place[3 * q + 1] = ch.y; place[3 * q + 2] = ch.m;
             }
-            const PartRect r = part_rect<R>(place[3 * q], place[3 * q + 1], w.ksize[place[3 * q + 2]], scale);
+            const PartRect r = part_rect<R>(place[3 * q], place[3 * q + 1], w.ksize[place[3 * q + 2]], scale, d);
             rec[8 + 4 * q] = r.x1; rec[8 + 4 * q + 1] = r.y1; rec[8 + 4 * q + 2] = r.x2 - r.x1; rec[8 + 4 * q + 3] = r.y2 - r.y1;
         }
         rec[0] = p.frame + p.frame_offset; rec[1] = c; rec[2] = l;

@@ -299,6 +299,12 @@ class Handle:
         """pbd_set_level_shard: this handle computes only its share of the pyramid levels of each frame"""
         self.check(self.lib.pbd_set_level_shard(self.h, rank, world))
 
+    def set_padding(self, padx: int, pady: int) -> None:
+        """pbd_set_padding: every plan the handle builds afterwards pads its feature levels by (padx, pady) cells holding 0 on
+        channels 0 .. 30 and 1 on channel 31 (the padded pyramid of featpyramid.m; padding.py states the rule); (0, 0): off.
+        Roots and cells are then plane coordinates: the image cell is root_x - padx"""
+        self.check(self.lib.pbd_set_padding(self.h, int(padx), int(pady)))
+
     def set_nms(self, overlap: Optional[float]) -> None:
         """pbd_set_nms: every detect* call of this handle returns, per frame, Candidate.sort + Candidate.nonMaximaSuppression(
         (rows, cols), candidates, overlap) of what it found, computed on the device (cells/detect.cpp:237-238,
@@ -1288,6 +1294,7 @@ class PartsBasedDetector:
                         stream=stream, real_type=_lib.REAL_F32 if np.dtype(dtype) == np.float32 else _lib.REAL_F64)
         self._nms = nms
         self._walk = "reference"
+        self._pad = (0, 0)                         # setPadding: off
         self._root_nms = 0                         # setRootNMS: off
         self._top_k = 0                            # setTopK: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
@@ -1315,6 +1322,8 @@ class PartsBasedDetector:
             self.hd.set_nms(self._nms)
         if self._walk != "reference":
             self.hd.set_walk(self.WALKS[self._walk])
+        if self._pad != (0, 0):
+            self.hd.set_padding(*self._pad)
         if self._root_nms:
             self.hd.set_root_nms(self._root_nms)
         if self._top_k:
@@ -1341,6 +1350,23 @@ class PartsBasedDetector:
         if self.hd is not None:
             self.hd.set_walk(self.WALKS[walk])
         self._walk = walk
+
+    def setPadding(self, padx: Optional[int], pady: Optional[int] = None) -> None:
+        """the padded pyramid of the Matlab detector from now on (pbd_set_padding; kept across distributeModel and updateModel):
+        every feature level grows by padx / pady cells of the boundary occlusion feature on each side, so that roots and parts
+        can lie outside the frame (a person cut off by the frame edge); pady None: pady = padx; padx None or 0: off (the
+        default).  Model.full_padding() gives the pad of featpyramid.m.  A Candidate's root is then a cell of the padded plane
+        (the image cell is root - (padx, pady)); its part boxes are frame coordinates as always.  Not with setDepthPrune, and
+        maxMarginals / marginalPoses refuse a padded result"""
+        px = int(padx or 0)
+        py = px if pady is None else int(pady or 0)
+        if not (0 <= px <= 31 and 0 <= py <= 31):
+            raise PbdError(-1, f"padding ({px}, {py}): 0..31 cells")
+        if (px or py) and self._dprune is not None:
+            raise PbdError(-2, "a padded pyramid with depth pruning on (setDepthPrune(None) first)")
+        if self.hd is not None:
+            self.hd.set_padding(px, py)
+        self._pad = (px, py)
 
     def setRootNMS(self, sz: int) -> None:
         """the reference's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) from now on
@@ -1392,6 +1418,8 @@ class PartsBasedDetector:
         cfg = None if fx is None else (float(fx), float(width), float(tol))
         if cfg is not None and not (all(math.isfinite(v) for v in cfg) and cfg[0] > 0 and cfg[1] > 0 and cfg[2] >= 0):
             raise PbdError(-1, f"depth prune: fx {fx}, width {width} (finite, > 0), tol {tol} (finite, >= 0)")
+        if cfg is not None and self._pad != (0, 0):
+            raise PbdError(-2, "depth pruning on a padded pyramid (setPadding(0) first)")
         if self.hd is not None:
             self.hd.set_depth_prune(*(cfg or (None,)))
         self._dprune = cfg
@@ -2117,6 +2145,11 @@ class DetectorPool:
         lane = self._lane(self._collected)
         self._collected += 1        # whatever the lane call does below: its slot is released, the cursor moves on
         return lane.wait_batch(capacity, raw)
+
+    def setPadding(self, padx: Optional[int], pady: Optional[int] = None) -> None:
+        """PartsBasedDetector.setPadding on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setPadding(padx, pady)
 
     def setRootNMS(self, sz: int) -> None:
         """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""

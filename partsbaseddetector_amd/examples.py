@@ -336,10 +336,13 @@ def placement_score(flat, resp: np.ndarray, c: int, placement) -> float:
 class FrameMaps:
     """the oracle's features, responses and per-component DP maps of one frame (computed on first use per level)"""
 
-    def __init__(self, flat, im: np.ndarray, dtype=np.float32, walk: str = "reference"):
+    def __init__(self, flat, im: np.ndarray, dtype=np.float32, walk: str = "reference", pad=(0, 0)):
         from oracle import oracle
         self.oracle, self.flat, self.dtype, self.walk = oracle, flat, dtype, walk
         self.feats, self.scales = oracle.features_pyramid(flat, im, dtype)
+        if tuple(pad) != (0, 0):   # the padded pyramid (padding.py): every map below follows the padded planes
+            from .padding import pad_features
+            self.feats = [pad_features(f, pad[0], pad[1], flat.flen) for f in self.feats]
         self._resp, self._dp = {}, {}
 
     def resp(self, level: int) -> np.ndarray:
@@ -405,9 +408,10 @@ def round_mul(a, s, dtype):
     return np.rint(t(a) * t(s)).astype(np.int64)
 
 
-def part_rects(x, y, k, scale, dtype):
-    """the record rectangle of a part of size k at (x, y) (src/DynamicProgram.cpp:238-241) as inclusive corners x1, y1, x2, y2"""
-    x1, y1 = round_mul(np.asarray(x) - 1, scale, dtype), round_mul(np.asarray(y) - 1, scale, dtype)
+def part_rects(x, y, k, scale, dtype, pad=(0, 0)):
+    """the record rectangle of a part of size k at (x, y) (src/DynamicProgram.cpp:238-241) as inclusive corners x1, y1, x2, y2;
+    pad: (padx, pady) of a padded pyramid, (x, y) being plane coordinates (padding.py)"""
+    x1, y1 = round_mul(np.asarray(x) - pad[0] - 1, scale, dtype), round_mul(np.asarray(y) - pad[1] - 1, scale, dtype)
     x2, y2 = x1 + round_mul(k, scale, dtype) - 1, y1 + round_mul(k, scale, dtype) - 1
     return np.minimum(x1, x2), np.minimum(y1, y2), np.maximum(x1, x2), np.maximum(y1, y2)
 
@@ -423,7 +427,7 @@ def overlap_passes(rect, box, overlap):
     return inter / (area + barea - inter) > overlap
 
 
-def mask_responses(uflat, resp, scale, boxes, overlap, mixtures=None, dtype=np.float32):
+def mask_responses(uflat, resp, scale, boxes, overlap, mixtures=None, dtype=np.float32, pad=(0, 0)):
     """the latent mask of one level's responses (F', H, W) of the unique model: a (part, mixture) plane keeps its value only where
     the mixture is allowed and the part's record rectangle passes the overlap test with the frame's box of that part"""
     out = np.array(resp, copy=True)
@@ -434,24 +438,29 @@ def mask_responses(uflat, resp, scale, boxes, overlap, mixtures=None, dtype=np.f
             p = gp - int(uflat.part_offset[c])
             for m, gm in enumerate(range(uflat.mix_offset[gp], uflat.mix_offset[gp + 1])):
                 k = int(uflat.filter_ksize[uflat.filterid[gm]])
-                keep = overlap_passes(part_rects(xs, ys, k, scale, dtype), boxes[p], overlap)
+                keep = overlap_passes(part_rects(xs, ys, k, scale, dtype, pad), boxes[p], overlap)
                 if mixtures is not None and mixtures[p] >= 0 and mixtures[p] != m:
                     keep[:] = False
                 out[int(uflat.filterid[gm])][~keep] = np.dtype(dtype).type(MASKED)
     return out
 
 
-def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, dtype=np.float32, walk: str = "reference"):
+def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, dtype=np.float32, walk: str = "reference",
+                  pad=(0, 0)):
     """the latent positive of one frame (pbd_detect_latent): dict(level, component, root_x, root_y, score (float), parts
     (nparts, 4) x, y, w, h, placement [(x, y, mixture)], found), walked through the oracle's maps of the masked responses of the
     unique model (walk "argmax": raw_maps' of the best level and component); ties go to the first in (level, component, y, x)
-    order"""
+    order.  pad: (padx, pady) of a padded pyramid (padding.py): root_x / root_y and the placement are plane coordinates"""
     from oracle import oracle
+    from .padding import pad_features
     uflat = unique_model(model).flatten()
     feats, scales = oracle.features_pyramid(uflat, im, dtype)
     best = None
     for lvl, feat in enumerate(feats):
-        resp = mask_responses(uflat, oracle.responses(uflat, feat), scales[lvl], boxes, overlap, mixtures, dtype)
+        feat = pad_features(feat, pad[0], pad[1], uflat.flen)
+        if feat.size == 0:
+            continue
+        resp = mask_responses(uflat, oracle.responses(uflat, feat), scales[lvl], boxes, overlap, mixtures, dtype, pad)
         for c in range(uflat.ncomponents):
             Ix, Iy, Ik, rootv, rooti = oracle.dp_min(uflat, c, resp)
             i = int(np.argmax(rootv))       # first maximum in raster order
@@ -466,7 +475,7 @@ def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, d
     parts = []
     for p, (px, py, m) in enumerate(pl):
         gm = int(uflat.mix_offset[uflat.part_offset[c] + p]) + m
-        x1, y1, x2, y2 = part_rects(px, py, int(uflat.filter_ksize[uflat.filterid[gm]]), scales[lvl], dtype)
+        x1, y1, x2, y2 = part_rects(px, py, int(uflat.filter_ksize[uflat.filterid[gm]]), scales[lvl], dtype, pad)
         parts.append((int(x1), int(y1), int(x2 - x1), int(y2 - y1)))
     score = float(np.float32(v))
     return {"level": lvl, "component": c, "root_x": x, "root_y": y, "score": score, "parts": np.asarray(parts, np.int32),

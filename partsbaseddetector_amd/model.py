@@ -48,6 +48,13 @@ class Model:
     def nfilters(self) -> int:
         return len(self.filtersw)
 
+    def full_padding(self) -> tuple:
+        """(k // 2, k // 2) for the largest filter side k: the pad at which every placement of featpyramid.m's padded pyramid
+        (padx = maxsize - 2 there, filters anchored at their corner) exists here, where a filter is anchored at its centre
+        (PartsBasedDetector.setPadding)"""
+        k = max(int(np.asarray(f).shape[0]) for f in self.filtersw)
+        return (k // 2, k // 2)
+
     def validate(self) -> None:
         """Structural checks before the tables reach pbd_create / the oracle; raises ValueError (never `assert`, which
         `python -O` strips)."""
