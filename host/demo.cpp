@@ -3,7 +3,7 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--pad X[,Y]] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--pad X[,Y]] [--fine-octave] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //            [--part-scores] [--marginal-pose PART]
@@ -16,6 +16,9 @@
 //   --pad X[,Y]: the padded pyramid of the Matlab detector (pbd_set_padding): every feature level grows by X (Y; Y = X when not
 //           given) cells of the boundary occlusion feature on each side, so that roots and parts can lie outside the image; the
 //           root cell a candidate line prints is then a cell of the padded plane.  Not with --depth-prune or --marginal-pose
+//   --fine-octave: search an octave above the frame (pbd_set_fine_octave): the first `interval` levels a second time at bin size
+//           sbin / 2, in front of the others (objects of half the template's size); the level a candidate line prints then
+//           indexes the longer list
 //   --conv-mode: the handles' convolution mode, a PBD_CONV_* value (include/pbd.h); default PBD_CONV_EXACT.  0 exact, 1 fma,
 //           2 / 3 matrix cores bf16 / fp16 (5x5 banks), 4 fp64 matrix cores (--double), 5 / 6 matrix cores bf16 / fp16 for
 //           every filter size and mixed banks (PBD_CONV_MFMA_ANY / PBD_CONV_MFMA_F16_ANY; not with --double)
@@ -68,6 +71,7 @@ static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
 static int g_top_k = 0;                   // --top-k
 static int g_padx = 0, g_pady = 0;        // --pad
+static bool g_fine = false;               // --fine-octave
 static bool g_part_scores = false;        // --part-scores
 static int g_marginal_part = -1;          // --marginal-pose
 static bool g_prune = false;              // --depth-prune fx,width,tol
@@ -101,6 +105,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
     pbd.setPadding(g_padx, g_pady);
+    pbd.setFineOctave(g_fine);
     pbd.distributeModel(model);
     std::vector<std::vector<Candidate> > candidates;
     pbd.detectBatch(ims, candidates);
@@ -190,6 +195,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
     pbd.setPadding(g_padx, g_pady);
+    pbd.setFineOctave(g_fine);
     if (g_prune) pbd.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
     std::vector<Candidate> candidates;
     if (stream_k > 0) {
@@ -199,6 +205,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         fs.setRootNMS(g_root_nms);
         fs.setTopK(g_top_k);
         fs.setPadding(g_padx, g_pady);
+        fs.setFineOctave(g_fine);
         if (g_prune) fs.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
         std::vector<Candidate> first, cur;
         size_t got = 0;
@@ -245,6 +252,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         // filterCandidatesByDepth on the unsuppressed list (its counts), then the chain detect(im, depth) runs with the setting on
         PartsBasedDetector<T> raw(0, conv_mode);
         raw.setPadding(g_padx, g_pady);
+        raw.setFineOctave(g_fine);
         raw.distributeModel(model);
         std::vector<Candidate> all, kept;
         raw.detect(im, all);
@@ -388,7 +396,7 @@ static int run_augment(Model &model, const Image &im, double degrees, bool mirro
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--pad x[,y]] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--pad x[,y]] [--fine-octave] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
     const char *augment_path = NULL;
@@ -437,6 +445,7 @@ int main(int argc, char **argv)
                 return -1;
             }
         }
+        else if (!std::strcmp(argv[i], "--fine-octave")) g_fine = true;
         else if (!std::strcmp(argv[i], "--top") && i + 1 < argc) top = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--conv-mode") && i + 1 < argc) conv_mode = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stream") && i + 2 < argc) { stream_k = std::atoi(argv[++i]); stream_n = std::atoi(argv[++i]); }

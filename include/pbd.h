@@ -204,6 +204,31 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world);
  * on a padded resident result. */
 int pbd_set_padding(pbd_handle *h, int padx, int pady);
 
+/* The fine octave (new surface; opt-in, off on a new handle; partsbaseddetector_amd/fineoctave.py states
+ * the rule in numpy).  The detector's smallest scale is the frame itself at the model's bin size (level 0, plan_pyramid), so an
+ * object smaller than the model's template cannot be found.  Felzenszwalb's featpyramid computes the first `interval` levels a
+ * second time at bin size sbin / 2 on the SAME resampled images -- an octave of levels at twice the feature resolution; the
+ * reference kept only the comment (matlab/detection/featpyramid.m:7).  With the octave on, every image plan the handle builds
+ * AFTERWARDS -- single frame, equal-size batch, pbd_detect_frames*, regions, the _submit / _wait form and pbd_detect_latent* --
+ * has nfine = min(interval, nlevels) more levels, IN FRONT: level i < nfine is the HOG of reference level i's image at bin size
+ * sbin / 2 (blocks = round(dim / (sbin / 2)), feature map = blocks - 2, plus the pad of pbd_set_padding) and its scale is
+ * scale[i] / 2 exactly; level nfine + l is the reference's level l, its features, scale and all that is computed from them bit
+ * for bit what they were.  No image is resampled anew: pbd_get_pyramid_image(level < nfine) returns the image of level
+ * nfine + level, and pbd_pyramid_plan reports nlevels + nfine levels, the fine ones with the image sizes of the levels they
+ * share and half their scales.  A record's `level`, the levels of pbd_get_stage, pbd_part_scores* / pbd_score_placements*,
+ * pbd_examples*, pbd_features_pyramid and the max-marginal calls index this longer list.  Convolution in every mode, the
+ * distance transforms, the dynamic program, the find, root NMS, top-K, depth pruning (its rule reads the level's scale), the
+ * walk, suppression, level sharding and padding see only more (and larger) levels; everything a plan derives from level sizes
+ * derives from the longer table (the uint8 / int16 choice of the position planes at a longest side of 256 included: a fine
+ * level is twice as long as its base level).  Parts at a finer octave than their parent remain out of scope.  Patch plans of
+ * pbd_warp_positives* and the explicit-size calls (pbd_conv_pdf, pbd_dp_min) never get the octave.
+ * PBD_ERR_STATE while a batch is in flight.  A call that does not change the setting leaves the resident result; one that
+ * changes it drops the result and the cached plans, and every read-back gives PBD_ERR_STATE until the next writing call.  A
+ * model update keeps the setting; the latent twin follows its handle.
+ * PBD_ERR_UNSUPPORTED: enabling it on a model whose sbin is odd or below 4 (the fine bin size must be an integer >= 2, the range
+ * the HOG kernels are pinned on); a frame whose plan would exceed PBD_MAX_LEVELS levels (reported by the call that plans it). */
+int pbd_set_fine_octave(pbd_handle *h, int enable);
+
 /* Per-frame post-processing (opt-in; off on a new handle): what every caller of the reference runs after detect() --
  * Candidate::sort(candidates) then Candidate::nonMaximaSuppression(im, candidates, overlap) (cells/detect.cpp:237-238,
  * ros/Node.cpp:192-196; include/Candidate.hpp:91-99,277-304) -- on the device, on the handle's stream, after argmin.  Per frame:

@@ -276,6 +276,14 @@ inline void set_padding(pbd_handle *h, int padx, int pady)
     check<Tr>(h, pbd_set_padding(h, padx, pady));
 }
 
+// pbd_set_fine_octave: every image plan the handle builds afterwards has the first `interval` levels a second time, in front, at
+// bin size sbin / 2 and half the scale (objects of half the template's size); levels then index the longer list
+template <class Tr>
+inline void set_fine_octave(pbd_handle *h, bool on)
+{
+    check<Tr>(h, pbd_set_fine_octave(h, on ? 1 : 0));
+}
+
 // pbd_set_top_k: at most k candidates per frame from every later walk of this handle -- the k best roots of the frame among those
 // the threshold and the other root filters leave; k = 0: off
 template <class Tr>

@@ -602,6 +602,7 @@ class PartsBasedDetector {
     int root_nms_;
     int top_k_;
     int padx_, pady_;
+    bool fine_;
     bool depth_on_;
     float zfactor_;
     bool prune_on_;
@@ -616,7 +617,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), top_k_(0), padx_(0), pady_(0), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
+          root_nms_(0), top_k_(0), padx_(0), pady_(0), fine_(false), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
           planes_(0) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
@@ -631,6 +632,7 @@ public:
         if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
         if (top_k_) pbdbind::set_top_k<HostTraits<T> >(h_, top_k_);
         if (padx_ || pady_) pbdbind::set_padding<HostTraits<T> >(h_, padx_, pady_);
+        if (fine_) pbdbind::set_fine_octave<HostTraits<T> >(h_, true);
         if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
         name_ = model.name();
         planes_ = 0;
@@ -684,6 +686,15 @@ public:
         if (h_) pbdbind::set_padding<HostTraits<T> >(h_, padx, pady);
         padx_ = padx;
         pady_ = pady;
+    }
+    // new surface: search an octave above the frame from now on (pbd_set_fine_octave): the first `interval` pyramid levels are
+    // computed a second time at bin size sbin / 2 on the same level images, so that an object of half the template's size is found.
+    // These levels come first: a Candidate's level then indexes the longer list.  Needs an even sbin >= 4.  Kept across
+    // distributeModel(); off by default.
+    void setFineOctave(bool on)
+    {
+        if (h_) pbdbind::set_fine_octave<HostTraits<T> >(h_, on);
+        fine_ = on;
     }
     // new surface: at most k candidates per frame from now on (pbd_set_top_k): only the k best roots of each frame -- by score, ties
     // to the earlier cell -- among those the threshold, depth pruning and root NMS leave are walked and returned; k = 0 turns it
@@ -1393,6 +1404,11 @@ public:
     void setPadding(int padx, int pady)
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_padding<HostTraits<T> >(h_[i], padx, pady);
+    }
+    // every handle searches the fine octave (PartsBasedDetector::setFineOctave); nothing may be pending
+    void setFineOctave(bool on)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_fine_octave<HostTraits<T> >(h_[i], on);
     }
     // every handle keeps at most k candidates per frame (PartsBasedDetector::setTopK); nothing may be pending
     void setTopK(int k)

@@ -238,6 +238,15 @@ inline void hipSetPadding(pbd_handle *h, int padx, int pady)
     pbdbind::set_padding<CvTraits<T> >(h, padx, pady);
 }
 
+// Search an octave above the frame in every later hipDetect / hipDetectBatch of this handle (pbd_set_fine_octave): the first
+// `interval` pyramid levels a second time at bin size sbin / 2, in front of the others, so that an object of half the template's
+// size is found; a candidate's level then indexes the longer list.  false turns it off
+template <typename T>
+inline void hipSetFineOctave(pbd_handle *h, bool on)
+{
+    pbdbind::set_fine_octave<CvTraits<T> >(h, on);
+}
+
 // At most k candidates per frame from every later hipDetect / hipDetectBatch of this handle (pbd_set_top_k): the k best roots of
 // the frame among those the threshold and the other root filters leave; k = 0 turns it off
 template <typename T>

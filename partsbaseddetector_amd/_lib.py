@@ -24,7 +24,7 @@ CONV_MFMA_ANY = 5          # CONV_MFMA's arithmetic for every filter size 1..31 
 CONV_MFMA_F16_ANY = 6      # CONV_MFMA_F16's arithmetic and fp16 resident responses, likewise
 STAGE_FEATURES, STAGE_RESPONSES, STAGE_ROOTV, STAGE_ROOTI = 0, 1, 2, 3
 # options of pbd_debug_set_option (forced launch choices of one handle; not declared in include/pbd.h)
-DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB, GRID_NMS_LANES = 0, 1, 2, 3, 4
+DT_LANE_SHIFT, DT_COOP, DT_COOP_G, DP_BUDGET_MB, GRID_NMS_LANES, HOG_TWO_PASS = 0, 1, 2, 3, 4, 5
 GRID_NMS_WAVE_SZ = 7       # kGnWaveSz: k_grid_nms runs one lane per block below this sz, one wave per block from it on
 # cv::Mat::depth() codes of the image depths HOGFeatures::pyramid accepts (src/HOGFeatures.cpp:136-146)
 DEPTH_CODE = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 2, np.dtype(np.float32): 5, np.dtype(np.float64): 6}
@@ -65,7 +65,7 @@ SYMBOLS = [
     "pbd_augment_plan", "pbd_augment_points", "pbd_augment_frames", "pbd_augment_frames_device", "pbd_detect_latent_device",
     "pbd_part_scores", "pbd_part_scores_device", "pbd_score_placements", "pbd_score_placements_device",
     "pbd_max_marginals", "pbd_get_marginals", "pbd_marginals_device", "pbd_marginal_poses", "pbd_marginal_poses_device",
-    "pbd_set_padding",
+    "pbd_set_padding", "pbd_set_fine_octave",
 ]
 
 
@@ -298,6 +298,7 @@ def load():
     lib.pbd_set_nms.argtypes = [C.c_void_p, C.c_int, C.c_float]
     lib.pbd_set_walk.argtypes = [C.c_void_p, C.c_int]
     lib.pbd_set_padding.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.pbd_set_fine_octave.argtypes = [C.c_void_p, C.c_int]
     lib.pbd_set_root_nms.argtypes = [C.c_void_p, C.c_int]
     lib.pbd_grid_nms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                  C.c_void_p]

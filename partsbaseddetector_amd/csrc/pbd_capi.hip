@@ -127,12 +127,22 @@ hipError_t finish_plan_tables(Plan &P, int sbin)
     std::vector<int> row2level, rowoff(P.nlevels + 1, 0), col2level, coloff(P.nlevels + 1, 0);
     std::vector<ConvTile> tiles, shaped[3], htiles;
     P.quad_per_frame = 0;
+    P.hgroups.clear();
+    P.fine = false;
+    std::vector<LevelDesc> lv_img;   // the levels of the model's bin size: every level image once
     for (int l = 0; l < P.nlevels; ++l) {
         P.lv[l].quad_off = P.quad_per_frame;
         P.quad_per_frame += ((long long)P.lv[l].rows * P.lv[l].cols + 3) / 4;
         const LevelDesc &d = P.lv[l];
-        for (int by0 = 0; by0 < d.blk_rows && d.blk_cols > 0; by0 += hog_tile_rows(sbin))
+        // the HOG stage's launches: one per run of levels of one bin size (blk1 / tile1 / lv1 grow with the run)
+        if (P.hgroups.empty() || P.hgroups.back().sbin != d.sbin)
+            P.hgroups.push_back(HogGroup{d.sbin, l, l, (int)htiles.size(), (int)htiles.size(), d.blk_off, d.blk_off});
+        if (d.sbin != sbin) P.fine = true;
+        else lv_img.push_back(d);
+        for (int by0 = 0; by0 < d.blk_rows && d.blk_cols > 0; by0 += hog_tile_rows(d.sbin))
             for (int bx0 = 0; bx0 < d.blk_cols; bx0 += kHogTBX) htiles.push_back({l, by0, bx0});
+        HogGroup &g = P.hgroups.back();
+        g.lv1 = l + 1; g.tile1 = (int)htiles.size(); g.blk1 = d.blk_off + (long long)d.blk_rows * d.blk_cols;
         rowoff[l] = (int)row2level.size();
         coloff[l] = (int)col2level.size();
         if (d.rows > 0 && d.cols > 0) {
@@ -178,6 +188,11 @@ hipError_t finish_plan_tables(Plan &P, int sbin)
     if ((e = P.d_stk_row_off.upload(srow)) != hipSuccess) return e;
     if ((e = P.d_stk_col_off.upload(scol)) != hipSuccess) return e;
     if ((e = P.d_lv.upload(P.lv)) != hipSuccess) return e;
+    P.nlv_img = 0;
+    if (P.fine) {
+        P.nlv_img = (int)lv_img.size();
+        if ((e = P.d_lv_img.upload(lv_img)) != hipSuccess) return e;
+    }
     if ((e = P.d_tiles.upload(tiles)) != hipSuccess) return e;
     if ((e = P.d_shaped.upload(all)) != hipSuccess) return e;
     if ((e = P.d_htiles.upload(htiles)) != hipSuccess) return e;
@@ -201,10 +216,13 @@ void cache_plan(pbd_handle *h, std::unique_ptr<Plan> P)
 }
 
 // The host side of an image plan (no device work): level table, scales and resize tables of an unsharded rows x cols frame.
-// PBD_OK, or PBD_ERR_INVALID with the reason in `err`.
+// PBD_OK, or PBD_ERR_INVALID / PBD_ERR_UNSUPPORTED with the reason in `err`.
 // padx / pady: the padded pyramid (pbd_set_padding) -- every non-empty feature map grows by the pad on each side, and all
 // that is derived from level sizes below and in finish_plan_tables follows.
-int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pady, Plan &Pr, std::string &err)
+// fine: the fine octave (pbd_set_fine_octave; fineoctave.py states the rule) -- the first nfine = min(interval, n) reference
+// levels come a second time, IN FRONT, at bin size sbin / 2 and half the scale.  A fine level owns no image: it shares the one
+// of its base level (img_off), so the pyramid does not grow.  Level nfine + l is the reference's level l, unchanged.
+int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pady, bool fine, Plan &Pr, std::string &err)
 {
     Plan *P = &Pr;
     char buf[160];
@@ -216,25 +234,38 @@ int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pa
         err = buf;
         return PBD_ERR_INVALID;
     }
+    const int nfine = fine ? std::min(interval, n) : 0;
+    if (fine && n + nfine > PBD_MAX_LEVELS) {
+        snprintf(buf, sizeof buf, "frame %dx%d: %d levels + %d of the fine octave exceed PBD_MAX_LEVELS (%d)", rows, cols, n, nfine, PBD_MAX_LEVELS);
+        err = buf;
+        return PBD_ERR_UNSUPPORTED;
+    }
     P->kind = 0; P->rows = rows; P->cols = cols;
     P->padded = padx != 0 || pady != 0;
-    P->nlevels = n; P->scales = scales; P->interval = interval;
-    P->lv.resize(n);
+    P->nlevels = n + nfine; P->nfine = nfine; P->interval = interval;
+    P->scales.resize(n + nfine);
+    P->lv.resize(n + nfine);
     std::vector<ResizeTabX> tabx;
     std::vector<ResizeTabY> taby;
     std::vector<ResizeTabXf> tabxf;
     std::vector<ResizeTabYf> tabyf;
-    long long pix = 0, blk = 0, cell = 0;
-    for (int l = 0; l < n; ++l) {
-        LevelDesc &d = P->lv[l];
+    std::vector<long long> img_off(n + 1, 0);
+    for (int l = 0; l < n; ++l) img_off[l + 1] = img_off[l] + (long long)lr[l] * lc[l];
+    long long blk = 0, cell = 0;
+    for (int L = 0; L < n + nfine; ++L) {
+        const int l = L < nfine ? L : L - nfine;        // the reference level whose image this level reads
+        const int sb = L < nfine ? sbin / 2 : sbin;
+        LevelDesc &d = P->lv[L];
+        P->scales[L] = L < nfine ? scales[l] / 2 : scales[l];
         d.img_rows = lr[l]; d.img_cols = lc[l];
         if (d.img_rows < 4 || d.img_cols < 4) {
             snprintf(buf, sizeof buf, "pyramid level %d is %dx%d", l, lr[l], lc[l]);
             err = buf;
             return PBD_ERR_INVALID;
         }
-        d.blk_cols = (int)roundf((float)lc[l] / (float)sbin);   // HOGFeatures.cpp:174
-        d.blk_rows = (int)roundf((float)lr[l] / (float)sbin);
+        d.sbin = sb;
+        d.blk_cols = (int)roundf((float)lc[l] / (float)sb);   // HOGFeatures.cpp:174
+        d.blk_rows = (int)roundf((float)lr[l] / (float)sb);
         d.cols = std::max(d.blk_cols - 2, 0);
         d.rows = std::max(d.blk_rows - 2, 0);
         d.padx = d.pady = 0;
@@ -242,14 +273,12 @@ int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pa
             d.padx = padx; d.pady = pady;
             d.cols += 2 * padx; d.rows += 2 * pady;
         }
-        d.src_level = l >= interval ? l - interval : -1;
-        d.img_off = pix; d.blk_off = blk; d.cell_off = cell;
+        d.src_level = L >= nfine && l >= interval ? l - interval : -1;
+        d.img_off = img_off[l]; d.blk_off = blk; d.cell_off = cell;
         d.tab_x = d.tab_y = 0;
-        pix += (long long)lr[l] * lc[l];
         blk += (long long)d.blk_rows * d.blk_cols;
         cell += (long long)d.rows * d.cols;
-        if (l == interval - 1) P->npix_resized = pix;
-        if (l < interval) {
+        if (L >= nfine && l < interval) {
             // cv::resize INTER_LINEAR coefficient tables (resize_taps_x / _y, pbd_handle.h)
             d.tab_x = (int)tabx.size();
             d.tab_y = (int)taby.size();
@@ -257,41 +286,52 @@ int image_plan_host(int rows, int cols, int sbin, int interval, int padx, int pa
             resize_taps_y(rows, lr[l], taby, tabyf);
         }
     }
-    P->pix_per_frame = pix; P->blk_per_frame = blk; P->cell_per_frame = cell;
-    if (P->npix_resized == 0) P->npix_resized = pix;
+    P->pix_per_frame = img_off[n]; P->blk_per_frame = blk; P->cell_per_frame = cell;
+    P->npix_resized = img_off[std::min(interval, n)];
     P->htabx = std::move(tabx); P->htaby = std::move(taby); P->htabxf = std::move(tabxf); P->htabyf = std::move(tabyf);
     return PBD_OK;
 }
 
-// the HOG coordinate table grows with the largest frame seen
+// the HOG coordinate table of bin size `sbin` with `need` entries, to `buf`
+int upload_coord(pbd_handle *h, int sbin, int need, DevBuf &buf)
+{
+    // HOGFeatures.cpp:252-259: yp = ((T)y+0.5)/(T)sbin - 0.5; iyp = floor(yp); vy0 = yp-iyp; vy1 = 1.0-vy0
+    if (h->f64) {
+        std::vector<HogCoordD> coord(need);
+        for (int t = 0; t < need; ++t) {
+            const double tp = ((double)t + 0.5) / (double)sbin - 0.5;
+            const int ip = (int)floor(tp);
+            const double v0 = tp - (double)ip;
+            coord[t] = {ip, v0, 1.0 - v0};
+        }
+        HIPCHK(h, buf.ensure(coord.size() * sizeof(HogCoordD)));
+        HIPCHK(h, hipMemcpy(buf.p, coord.data(), coord.size() * sizeof(HogCoordD), hipMemcpyHostToDevice));
+    } else {
+        std::vector<HogCoord> coord(need);
+        for (int t = 0; t < need; ++t) {
+            const float tp = (float)(((double)(float)t + 0.5) / (double)(float)sbin - 0.5);
+            const int ip = (int)floorf(tp);
+            const float v0 = tp - (float)ip;
+            const float v1 = (float)(1.0 - (double)v0);
+            coord[t] = {ip, v0, v1};
+        }
+        HIPCHK(h, buf.ensure(coord.size() * sizeof(HogCoord)));
+        HIPCHK(h, hipMemcpy(buf.p, coord.data(), coord.size() * sizeof(HogCoord), hipMemcpyHostToDevice));
+    }
+    return PBD_OK;
+}
+
+// the HOG coordinate tables grow with the largest frame seen: the model's bin size and, with the fine octave on, half of it
 int grow_coord(pbd_handle *h, int rows, int cols)
 {
     const int need = std::max(rows, cols) + 4 * h->sbin + 8;
     if (need > h->coord_n) {
-        // HOGFeatures.cpp:252-259: yp = ((T)y+0.5)/(T)sbin - 0.5; iyp = floor(yp); vy0 = yp-iyp; vy1 = 1.0-vy0
-        if (h->f64) {
-            std::vector<HogCoordD> coord(need);
-            for (int t = 0; t < need; ++t) {
-                const double tp = ((double)t + 0.5) / (double)h->sbin - 0.5;
-                const int ip = (int)floor(tp);
-                const double v0 = tp - (double)ip;
-                coord[t] = {ip, v0, 1.0 - v0};
-            }
-            HIPCHK(h, h->d_coord.ensure(coord.size() * sizeof(HogCoordD)));
-            HIPCHK(h, hipMemcpy(h->d_coord.p, coord.data(), coord.size() * sizeof(HogCoordD), hipMemcpyHostToDevice));
-        } else {
-            std::vector<HogCoord> coord(need);
-            for (int t = 0; t < need; ++t) {
-                const float tp = (float)(((double)(float)t + 0.5) / (double)(float)h->sbin - 0.5);
-                const int ip = (int)floorf(tp);
-                const float v0 = tp - (float)ip;
-                const float v1 = (float)(1.0 - (double)v0);
-                coord[t] = {ip, v0, v1};
-            }
-            HIPCHK(h, h->d_coord.ensure(coord.size() * sizeof(HogCoord)));
-            HIPCHK(h, hipMemcpy(h->d_coord.p, coord.data(), coord.size() * sizeof(HogCoord), hipMemcpyHostToDevice));
-        }
+        if (int rc = upload_coord(h, h->sbin, need, h->d_coord)) return rc;
         h->coord_n = need;
+    }
+    if (h->fine_octave && need > h->coord_fine_n) {
+        if (int rc = upload_coord(h, h->sbin / 2, need, h->d_coord_fine)) return rc;
+        h->coord_fine_n = need;
     }
     return PBD_OK;
 }
@@ -303,7 +343,7 @@ int get_image_plan(pbd_handle *h, int rows, int cols, Plan **out)
     auto P = std::make_unique<Plan>();
     {
         std::string err;
-        if (int rc = image_plan_host(rows, cols, h->sbin, h->interval, h->padx, h->pady, *P, err)) return fail(h, rc, "%s", err.c_str());
+        if (int rc = image_plan_host(rows, cols, h->sbin, h->interval, h->padx, h->pady, h->fine_octave, *P, err)) return fail(h, rc, "%s", err.c_str());
     }
     const int n = P->nlevels;
     long long blk = P->blk_per_frame, cell = P->cell_per_frame;
@@ -366,7 +406,7 @@ int get_dims_plan(pbd_handle *h, int nlevels, const int *rows, const int *cols, 
     for (int l = 0; l < nlevels; ++l) {
         LevelDesc &d = P->lv[l];
         memset(&d, 0, sizeof d);
-        d.rows = rows[l]; d.cols = cols[l]; d.src_level = -1; d.cell_off = cell;
+        d.rows = rows[l]; d.cols = cols[l]; d.src_level = -1; d.cell_off = cell; d.sbin = h->sbin;
         d.padx = h->padx; d.pady = h->pady;   // the caller's planes are taken to be padded by the handle's setting (the walk's rectangles)
         cell += (long long)rows[l] * cols[l];
     }
@@ -388,7 +428,7 @@ void mixed_append(Plan &M, const Plan &Q)
     for (int l = 0; l < Q.nlevels; ++l) {
         LevelDesc d = Q.lv[l];
         d.img_off += M.pix_per_frame; d.blk_off += M.blk_per_frame; d.cell_off += M.cell_per_frame;
-        if (d.src_level >= 0) d.src_level += lv0;
+        if (d.src_level >= 0) d.src_level += lv0 + Q.nfine;   // (Q's count from its first reference level; M's, from its level 0)
         else { d.tab_x += tx0; d.tab_y += ty0; }
         M.lv.push_back(d);
         M.scales.push_back(Q.scales[l]);
@@ -402,6 +442,7 @@ void mixed_append(Plan &M, const Plan &Q)
     M.nlevels += Q.nlevels;
     M.pix_per_frame += Q.pix_per_frame; M.blk_per_frame += Q.blk_per_frame; M.cell_per_frame += Q.cell_per_frame;
     M.frame_lv0.push_back(M.nlevels);
+    M.frame_nfine.push_back(Q.nfine);
     M.fdim.push_back(make_int2(Q.rows, Q.cols));
     M.key_dims.push_back(Q.rows); M.key_dims.push_back(Q.cols);
     M.mixed_frames += 1;
@@ -416,15 +457,16 @@ void mixed_finish(Plan &M, int interval)
     M.kind = 2; M.interval = interval;
     M.npix_resized = 0;
     int octaves = 0;
+    auto base0 = [&](int f) { return M.frame_lv0[f] + M.frame_nfine[f]; };   // the frame's first reference level: fine levels own no image
     for (int f = 0; f < M.mixed_frames; ++f)
-        octaves = std::max(octaves, (M.frame_lv0[f + 1] - M.frame_lv0[f] + interval - 1) / interval);
+        octaves = std::max(octaves, (M.frame_lv0[f + 1] - base0(f) + interval - 1) / interval);
     for (int k = 0; k < octaves; ++k) {
         M.run_lev0.push_back((int)M.run_lev.size());
         M.run_off0.push_back((long long)M.run_off.size());
         long long pix = 0;
         int n = 0;
         for (int f = 0; f < M.mixed_frames; ++f)
-            for (int l = M.frame_lv0[f] + k * interval; l < std::min(M.frame_lv0[f] + (k + 1) * interval, M.frame_lv0[f + 1]); ++l) {
+            for (int l = base0(f) + k * interval; l < std::min(base0(f) + (k + 1) * interval, M.frame_lv0[f + 1]); ++l) {
                 M.run_lev.push_back(l);
                 M.run_off.push_back(pix);
                 pix += (long long)M.lv[l].img_rows * M.lv[l].img_cols;
@@ -485,7 +527,7 @@ int get_mixed_plan(pbd_handle *h, int nframes, const int *rows, const int *cols,
             if (!B) {
                 B = std::make_unique<Plan>();
                 std::string err;
-                if (int rc = image_plan_host(rows[f], cols[f], h->sbin, h->interval, h->padx, h->pady, *B, err))
+                if (int rc = image_plan_host(rows[f], cols[f], h->sbin, h->interval, h->padx, h->pady, h->fine_octave, *B, err))
                     return fail(h, rc, "frame %d: %s", f, err.c_str());
             }
             Q = B.get();
@@ -1002,7 +1044,10 @@ void launch_hog_stage(pbd_handle *h, Plan &P, int cn, int depth, int f0, int nb,
 void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int depth, int f0, int nb, hipStream_t st)
 {
     PyrParams pp{};
-    pp.lv = P.d_lv.p; pp.nlevels = P.nlevels; pp.interval = std::min(P.interval, P.nlevels); pp.cn = cn; pp.frame0 = f0;
+    // the pyramid kernels see the reference levels alone (LevelDesc::src_level counts from there): fine levels own no image
+    const LevelDesc *lvb = P.lv.data() + P.nfine;
+    const int nbase = P.nlevels - P.nfine;
+    pp.lv = P.d_lv.p + P.nfine; pp.nlevels = nbase; pp.interval = std::min(P.interval, nbase); pp.cn = cn; pp.frame0 = f0;
     pp.pix_per_frame = P.pix_per_frame; pp.pyr = h->pyr.as<uint8_t>(); pp.frames = static_cast<const uint8_t *>(d_frames);
     pp.rows = P.rows; pp.cols = P.cols; pp.tabx = P.d_tabx.p; pp.taby = P.d_taby.p;
     pp.depth = depth; pp.tabxf = P.d_tabxf.p; pp.tabyf = P.d_tabyf.p;
@@ -1010,10 +1055,10 @@ void launch_features(pbd_handle *h, Plan &P, const void *d_frames, int cn, int d
         ProfScope ps(h, PBD_K_RESIZE, st);
         launch_resize(pp, nb, P.npix_resized, st);
     }
-    for (int first = P.interval; first < P.nlevels; first += P.interval) {
-        const int last = std::min(first + P.interval, P.nlevels);
-        const long long base = P.lv[first].img_off;
-        const long long end = (last < P.nlevels) ? P.lv[last].img_off : P.pix_per_frame;
+    for (int first = P.interval; first < nbase; first += P.interval) {
+        const int last = std::min(first + P.interval, nbase);
+        const long long base = lvb[first].img_off;
+        const long long end = (last < nbase) ? lvb[last].img_off : P.pix_per_frame;
         ProfScope ps(h, PBD_K_PYRDOWN, st);
         launch_pyrdown_range(pp, nb, first, last, base, end - base, st);
     }
@@ -1028,10 +1073,25 @@ void launch_hog_stage(pbd_handle *h, Plan &P, int cn, int depth, int f0, int nb,
     hp.pyr = h->pyr.as<uint8_t>(); hp.depth = depth; hp.coord = h->d_coord.p;
     hp.gmag = h->gmag.p; hp.gori = h->gori.as<uint8_t>();
     hp.hist = h->hist.p; hp.norm = h->norm.p; hp.feat = h->feat.p;
-    hp.htiles = P.d_htiles.p; hp.nhtiles = P.nhtiles;
     {
+        // one launch per bin size (Plan::hgroups; one group unless the plan has a fine octave); the groups that do not take the
+        // fused kernel share ONE pass 1 over the level images
         ProfScope ps(h, PBD_K_HOG_HIST, st);
-        launch_hog_hist(hp, nb, h->f64, st);
+        bool grad = false;
+        for (const HogGroup &g : P.hgroups) {
+            HogParams gp = hp;
+            gp.sbin = g.sbin; gp.coord = g.sbin == h->sbin ? h->d_coord.p : h->d_coord_fine.p;
+            gp.htiles = P.d_htiles.p + g.tile0; gp.nhtiles = g.tile1 - g.tile0;
+            gp.lv0 = g.lv0; gp.lv1 = g.lv1; gp.blk0 = g.blk0; gp.blk1 = g.blk1;
+            const bool fused = hog_fused(gp, h->f64) && !h->hog_two_pass;
+            if (!fused && !grad) {
+                HogParams ip = hp;
+                if (P.fine) { ip.lv = P.d_lv_img.p; ip.nlevels = P.nlv_img; }
+                launch_hog_grad(ip, nb, h->f64, st);
+                grad = true;
+            }
+            launch_hog_hist(gp, nb, h->f64, fused, P.hgroups.size() > 1, st);
+        }
     }
     {
         ProfScope ps(h, PBD_K_HOG_FEAT, st);
@@ -1791,6 +1851,7 @@ int warp_plan(pbd_handle *h, int n, int P, int cn, int depth, Plan **out)
             d.blk_rows = d.blk_cols = blk;
             d.rows = d.cols = std::max(blk - 2, 0);
             d.src_level = -1;
+            d.sbin = h->sbin;             // a patch plan never gets the fine octave
             d.img_off = (long long)l * P * P;
             d.blk_off = (long long)l * blk * blk;
             d.cell_off = (long long)l * d.rows * d.cols;
@@ -1868,7 +1929,7 @@ int pbd_debug_mixed_plan(int sbin, int interval, int nframes, const int *rows, c
         for (int f = 0; f < nframes; ++f) {
             Plan Q;
             std::string err;
-            if (rows[f] < 1 || cols[f] < 1 || image_plan_host(rows[f], cols[f], sbin, interval, 0, 0, Q, err)) return PBD_ERR_INVALID;
+            if (rows[f] < 1 || cols[f] < 1 || image_plan_host(rows[f], cols[f], sbin, interval, 0, 0, false, Q, err)) return PBD_ERR_INVALID;
             mixed_append(M, Q);
         }
         mixed_finish(M, interval);
@@ -1934,10 +1995,10 @@ int pbd_debug_postprocess(pbd_handle *h, int rows, int cols, const int32_t *reco
     });
 }
 
-// forces one of the handle's launch choices (tests: every distance-transform variant, DP chunking on small batches);
+// forces one of the handle's launch choices (tests: every distance-transform variant, DP chunking on small batches, the two-pass HOG);
 // each option's default value restores the automatic choice
 enum { PBD_DEBUG_DT_LANE_SHIFT = 0, PBD_DEBUG_DT_COOP = 1, PBD_DEBUG_DT_COOP_G = 2, PBD_DEBUG_DP_BUDGET_MB = 3,
-       PBD_DEBUG_GRID_NMS_LANES = 4 };
+       PBD_DEBUG_GRID_NMS_LANES = 4, PBD_DEBUG_HOG_TWO_PASS = 5 };
 int pbd_debug_set_option(pbd_handle *h, int option, int value)
 {
     return entry(h, true, kIdle, [&]() -> int {
@@ -1961,6 +2022,10 @@ int pbd_debug_set_option(pbd_handle *h, int option, int value)
         case PBD_DEBUG_GRID_NMS_LANES:  // 1 or 64 lanes per block of k_grid_nms; 0: by the window size
             if (value != 0 && value != 1 && value != 64) break;
             h->gn_lanes = value;
+            return PBD_OK;
+        case PBD_DEBUG_HOG_TWO_PASS:    // 1: the histogram stage never takes the fused gradient + histogram kernel; 0: where it applies
+            if (value != 0 && value != 1) break;
+            h->hog_two_pass = value != 0;
             return PBD_OK;
         default:
             return fail(h, PBD_ERR_INVALID, "debug option %d unknown", option);
@@ -2072,6 +2137,27 @@ int pbd_set_padding(pbd_handle *h, int padx, int pady)
         h->plans.clear();
         if (h->lat) {
             h->lat->padx = padx; h->lat->pady = pady;
+            h->lat->res.clear();
+            h->lat->plans.clear();
+        }
+        return PBD_OK;
+    });
+}
+
+int pbd_set_fine_octave(pbd_handle *h, int enable)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        const bool on = enable != 0;
+        if (on && (h->sbin < 4 || h->sbin % 2))
+            return fail(h, PBD_ERR_UNSUPPORTED, "a fine octave at bin size %d: sbin / 2 must be an integer >= 2", h->sbin);
+        if (on == h->fine_octave) return PBD_OK;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->fine_octave = on;
+        // every image plan carries the levels it was built with
+        h->res.clear();
+        h->plans.clear();
+        if (h->lat) {
+            h->lat->fine_octave = on;
             h->lat->res.clear();
             h->lat->plans.clear();
         }

@@ -787,6 +787,7 @@ static int detect_latent(pbd_handle *h, int nframes, const pbd_frame *frames, in
             h->lat.reset(t);
             t->walk_mode = h->walk_mode;
             t->padx = h->padx; t->pady = h->pady;
+            t->fine_octave = h->fine_octave;
             std::vector<int4> gm(T);
             for (int c = 0; c < h->NC; ++c)
                 for (int gp = h->part_offset[c]; gp < h->part_offset[c + 1]; ++gp)

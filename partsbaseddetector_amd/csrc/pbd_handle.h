@@ -148,9 +148,15 @@ struct Plan {
     bool ptr8 = false;              // no feature map side exceeds 256: positions fit uint8 (back-pointer planes at half the bytes)
     int longest = 0;                // longest side of any feature map of the plan (rows / columns of the distance transform)
     bool padded = false;            // built under a non-zero pbd_set_padding: its levels carry the pad (LevelDesc::padx / pady)
+    int nfine = 0;                  // image plans: the levels of the fine octave, which come first (pbd_set_fine_octave); lv[nfine] is
+                                    // the reference's level 0
+    bool fine = false;              // some level's bin size is not the model's (LevelDesc::sbin): the HOG stage runs per hgroups
+    std::vector<HogGroup> hgroups;  // the runs of consecutive levels of one bin size (finish_plan_tables)
     int ntiles = 0;
     // device tables
     DevTable<LevelDesc> d_lv;
+    DevTable<LevelDesc> d_lv_img;   // fine plans: the reference levels alone, every level image once (pass 1 of the two-pass HOG)
+    int nlv_img = 0;
     DevTable<ResizeTabX> d_tabx;
     DevTable<ResizeTabY> d_taby;
     DevTable<ResizeTabXf> d_tabxf;   // the same mapping with float coefficients (16U / 32F / 64F images)
@@ -174,6 +180,7 @@ struct Plan {
     int mixed_frames = 0;
     std::vector<int> lv_frame, lv_local;    // per virtual level: frame of the call, level of that frame's pyramid
     std::vector<int> frame_lv0;             // [mixed_frames + 1] first virtual level of each frame
+    std::vector<int> frame_nfine;           // [mixed_frames] fine levels at the head of each frame's levels
     DevTable<int> d_lv_frame, d_lv_local;
     // pyramid launches: launch 0 = every frame's resized levels, launch k >= 1 = octave k of every frame; launch k's levels are
     // run_lev[lev0[k] ..], its n[k] + 1 pixel offsets run_off[off0[k] ..]
@@ -364,6 +371,8 @@ struct Handle : ErrCtx {
     DevTable<PartWalk> d_walk;
     DevBuf d_coord;                  // HogCoordT<R>[]
     int coord_n = 0;
+    DevBuf d_coord_fine;             // the same table for the fine octave's bin size sbin / 2 (built while fine_octave is on)
+    int coord_fine_n = 0;
     bool f64 = false;                // reference template parameter T = double
     size_t rs = sizeof(float);       // sizeof(T)
     bool resp_half = false;          // conv_is_f16(mode): the responses live on the device as fp16 (BASELINE configs[4])
@@ -373,6 +382,7 @@ struct Handle : ErrCtx {
     std::vector<std::unique_ptr<Plan>> plans;
     Resident res;
     int shard_rank = 0, shard_world = 1;   // level sharding of single frames over several GPUs (pbd_set_level_shard)
+    bool fine_octave = false;        // pbd_set_fine_octave: every image plan built afterwards carries the octave; the latent twin follows
     int padx = 0, pady = 0;          // the padded pyramid (pbd_set_padding): every plan built afterwards carries it; the latent twin follows
     int walk_mode = 0;               // PBD_WALK_* (pbd_set_walk), read when a walk is enqueued; the latent twin follows its handle
     bool nms = false;                // per-frame sort + non-maxima suppression of the list (pbd_set_nms), latched at enqueue
@@ -394,6 +404,7 @@ struct Handle : ErrCtx {
     DevBuf dpl_ws;
     DtOptions dt_opt;               // forced distance-transform launch choices (pbd_debug_set_option)
     int dp_budget_mb = 0;            // DP scratch budget per chunk of frames; 0: 8 GB (pbd_debug_set_option)
+    bool hog_two_pass = false;       // the histogram stage never takes the fused kernel (pbd_debug_set_option)
 
     // workspace
     DevBuf frames, pyr, gmag, gori, hist, norm, feat, resp, acc, Ik, rootv, rooti;

@@ -19,12 +19,14 @@ namespace pbd {
 // starts at frame * (per-frame total).
 struct LevelDesc {
     int img_rows, img_cols;   // level image (pixels)
-    int blk_rows, blk_cols;   // HOG blocks = round(dim / sbin)             (src/HOGFeatures.cpp:174)
+    int blk_rows, blk_cols;   // HOG blocks = round(dim / sbin)             (src/HOGFeatures.cpp:174), sbin the LEVEL's (below)
     int rows, cols;           // feature / response map = blocks - 2         (:175), plus the pad on every side
     int padx, pady;           // cells of padding left and right / above and below the map (pbd_set_padding); 0 on an empty level
-    int src_level;            // pyrDown source level (level - interval), -1 for resized levels
+    int src_level;            // pyrDown source level (level - interval), -1 for resized levels; an index into the table the pyramid
+                              // kernels are given, which starts at the plan's first reference level (fine levels own no image)
     int tab_x, tab_y;         // offsets into the resize tables (levels < interval)
-    long long img_off;        // pixel offset of the level image (multiply by channels for bytes)
+    int sbin;                 // the level's bin size: the model's, or half of it on a level of the fine octave (pbd_set_fine_octave)
+    long long img_off;        // pixel offset of the level image (multiply by channels for bytes); a fine level shares its base level's
     long long blk_off;        // block offset
     long long cell_off;       // cell offset
     long long quad_off;       // offset in units of 4 consecutive cells of a level (combine step)
@@ -54,6 +56,9 @@ struct ConvSegTile { int nseg; int len[kConvMaxSeg]; ConvSeg seg[kConvMaxSeg]; }
 // tile of HOG blocks handled by one workgroup of the fused gradient + histogram kernel: kHogTBX x hog_tile_rows(sbin)
 constexpr int kHogTBX = 16;
 inline int hog_tile_rows(int sbin) { return sbin <= 4 ? 16 : 8; }
+// A run of consecutive levels of one bin size -- what one launch of the histogram kernels covers: levels [lv0, lv1), their blocks
+// [blk0, blk1) of the frame and their tiles [tile0, tile1) of the fused kernel's table.  A plan without a fine octave has one.
+struct HogGroup { int sbin, lv0, lv1, tile0, tile1; long long blk0, blk1; };
 
 // distance-transform job = (part, mixture) of one tree-depth group.  Its input is ONE plane: the raw
 // response of its filter for a leaf part, or the accumulated score (response + children's messages,
@@ -178,6 +183,8 @@ struct HogParams {
     void *feat;                   // R [frames][cell_per_frame*32]
     const ConvTile *htiles;       // block tiles of the fused gradient + histogram kernel ({level, by0, bx0})
     int nhtiles;
+    int lv0, lv1;                 // the ranged form of k_hog_hist (one HogGroup of several): its levels and ...
+    long long blk0, blk1;         // ... their blocks; sbin and coord are then the group's
 };
 
 struct ConvParams {
@@ -527,7 +534,11 @@ void launch_pyrdown_range(const PyrParams &p, int nframes, int first_level, int 
 void launch_resize_runs(const PyrParams &p, hipStream_t s);
 void launch_pyrdown_runs(const PyrParams &p, hipStream_t s);
 // `f64` selects the reference's T=double instantiation (every real-typed buffer then holds doubles)
-void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s);
+// pass 1 of the two-pass form over the level images `p.lv` (reference levels only: every image once); then, per HogGroup, the
+// histograms: the fused kernel (`fused`, only where hog_fused() holds), else pass 2 (`ranged`: the group is not the whole plan)
+bool hog_fused(const HogParams &p, bool f64);
+void launch_hog_grad(const HogParams &p, int nframes, bool f64, hipStream_t s);
+void launch_hog_hist(const HogParams &p, int nframes, bool f64, bool fused, bool ranged, hipStream_t s);
 void launch_hog_feat(const HogParams &p, int nframes, bool f64, bool padded, hipStream_t s);
 void launch_conv(const ConvParams &p, int nframes, bool f64, hipStream_t s);
 int conv_occupancy(int nw);

@@ -699,16 +699,20 @@ __device__ __forceinline__ void hog_hist_store(const R *h, R *hist, R *norm, lon
     *norm = e;
 }
 
-// Pass 2 of the two-pass form.  SB = compile-time sbin (4, 8) or 0 for any.
-template <typename R, int SB>
+// Pass 2 of the two-pass form.  SB = compile-time sbin (4, 8) or 0 for any.  RANGE: the launch covers the blocks [p.blk0, p.blk1)
+// of the levels [p.lv0, p.lv1) -- one bin size of a plan that has two (the fine octave, pbd_set_fine_octave) -- with p.sbin and
+// p.coord those of that bin size; without it, every block of the plan.
+template <typename R, int SB, bool RANGE = false>
 __global__ __launch_bounds__(256) void k_hog_hist(HogParams p)
 {
     __shared__ R bins[18 * 256];
-    const long long idx0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = idx0 < p.blk_per_frame;
-    const long long idx = active ? idx0 : p.blk_per_frame - 1;
+    long long idx0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, end = p.blk_per_frame;
+    int lv0 = 0, lv1 = p.nlevels;
+    if constexpr (RANGE) { idx0 += p.blk0; end = p.blk1; lv0 = p.lv0; lv1 = p.lv1; }
+    const bool active = idx0 < end;
+    const long long idx = active ? idx0 : end - 1;
     const int frame = p.frame0 + blockIdx.y;
-    const LevelCell c = level_cell<1>(p.lv, find_level_blk<1>(p.lv, 0, p.nlevels, idx), idx);
+    const LevelCell c = level_cell<1>(p.lv, find_level_blk<1>(p.lv, lv0, lv1, idx), idx);
     const LevelDesc &d = c.d;
     const int by = c.y, bx = c.x;
     const int sbin = p.sbin;
@@ -750,7 +754,8 @@ __global__ __launch_bounds__(256) void k_hog_hist(HogParams p)
                            static_cast<R *>(p.norm) + (size_t)frame * p.blk_per_frame + idx, p.blk_per_frame);
 }
 
-// Fused form of the two passes for the hot case (8-bit BGR frames, T = float, sbin 4 or 8): one workgroup = one tile of
+// Fused form of the two passes for the hot case (8-bit BGR frames, T = float, sbin 4 or 8, and 2: the fine octave of an
+// sbin-4 model): one workgroup = one tile of
 // TBX x TBY blocks.  The gradient magnitude / orientation of the pixels its blocks sample ((TB-1)*SB + 2*SB + 2 per side)
 // are computed straight from the level image into LDS, four pixels per lane as in k_hog_grad4, and the block threads
 // then walk their windows there: the 5 bytes per pixel of pass 1 never travel to HBM and back (they were 2/3 of the
@@ -811,31 +816,51 @@ __global__ __launch_bounds__(TBX * TBY) void k_hog_tile(HogParams p)
                               static_cast<float *>(p.norm) + (size_t)frame * p.blk_per_frame + idx, p.blk_per_frame);
 }
 
-void launch_hog_hist(const HogParams &p, int nframes, bool f64, hipStream_t s)
+// The launches below take one HogGroup each: p.htiles / p.nhtiles are the group's tiles, p.sbin and p.coord its bin size and
+// coordinate table, p.blk0 .. p.lv1 its blocks and levels (read by the ranged form only).
+bool hog_fused(const HogParams &p, bool f64)
 {
-    const bool bgr8 = !f64 && p.depth == kDepth8U && p.cn == 3;
-    if (bgr8 && (p.sbin == 4 || p.sbin == 8)) {
+    return !f64 && p.depth == kDepth8U && p.cn == 3 && (p.sbin == 2 || p.sbin == 4 || p.sbin == 8);
+}
+
+void launch_hog_grad(const HogParams &p, int nframes, bool f64, hipStream_t s)
+{
+    if (p.pix_per_frame == 0) return;
+    if (!f64 && p.depth == kDepth8U && p.cn == 3) {
+        dim3 grid4((unsigned)((p.pix_per_frame + 1023) / 1024), nframes);
+        PBD_LAUNCH(k_hog_grad4, grid4, dim3(256), 0, s, p);
+        return;
+    }
+    dim3 gridp((unsigned)((p.pix_per_frame + 255) / 256), nframes);
+    for_depth(p.depth, [&](auto t) {
+        if (f64) PBD_LAUNCH((k_hog_grad<double, decltype(t)>), gridp, dim3(256), 0, s, p);
+        else PBD_LAUNCH((k_hog_grad<float, decltype(t)>), gridp, dim3(256), 0, s, p);
+    });
+}
+
+template <bool RANGE>
+static void launch_hog_pass2(const HogParams &p, long long nblk, int nframes, bool f64, hipStream_t s)
+{
+    if (nblk == 0) return;
+    dim3 grid((unsigned)((nblk + 255) / 256), nframes);
+    if (f64) PBD_LAUNCH((k_hog_hist<double, 0, RANGE>), grid, dim3(256), 0, s, p);
+    else if (p.sbin == 4) PBD_LAUNCH((k_hog_hist<float, 4, RANGE>), grid, dim3(256), 0, s, p);
+    else if (p.sbin == 8) PBD_LAUNCH((k_hog_hist<float, 8, RANGE>), grid, dim3(256), 0, s, p);
+    else PBD_LAUNCH((k_hog_hist<float, 0, RANGE>), grid, dim3(256), 0, s, p);
+}
+
+void launch_hog_hist(const HogParams &p, int nframes, bool f64, bool fused, bool ranged, hipStream_t s)
+{
+    if (fused) {
         if (p.nhtiles == 0) return;
         dim3 grid((unsigned)p.nhtiles, nframes);
-        if (p.sbin == 4) PBD_LAUNCH((k_hog_tile<4, kHogTBX, 16>), grid, dim3(kHogTBX * 16), 0, s, p);
+        if (p.sbin == 2) PBD_LAUNCH((k_hog_tile<2, kHogTBX, 16>), grid, dim3(kHogTBX * 16), 0, s, p);
+        else if (p.sbin == 4) PBD_LAUNCH((k_hog_tile<4, kHogTBX, 16>), grid, dim3(kHogTBX * 16), 0, s, p);
         else PBD_LAUNCH((k_hog_tile<8, kHogTBX, 8>), grid, dim3(kHogTBX * 8), 0, s, p);
         return;
     }
-    if (bgr8) {
-        dim3 grid4((unsigned)((p.pix_per_frame + 1023) / 1024), nframes);
-        PBD_LAUNCH(k_hog_grad4, grid4, dim3(256), 0, s, p);
-    } else {
-        dim3 gridp((unsigned)((p.pix_per_frame + 255) / 256), nframes);
-        for_depth(p.depth, [&](auto t) {
-            if (f64) PBD_LAUNCH((k_hog_grad<double, decltype(t)>), gridp, dim3(256), 0, s, p);
-            else PBD_LAUNCH((k_hog_grad<float, decltype(t)>), gridp, dim3(256), 0, s, p);
-        });
-    }
-    dim3 grid((unsigned)((p.blk_per_frame + 255) / 256), nframes);
-    if (f64) PBD_LAUNCH((k_hog_hist<double, 0>), grid, dim3(256), 0, s, p);
-    else if (p.sbin == 4) PBD_LAUNCH((k_hog_hist<float, 4>), grid, dim3(256), 0, s, p);
-    else if (p.sbin == 8) PBD_LAUNCH((k_hog_hist<float, 8>), grid, dim3(256), 0, s, p);
-    else PBD_LAUNCH((k_hog_hist<float, 0>), grid, dim3(256), 0, s, p);
+    if (ranged) launch_hog_pass2<true>(p, p.blk1 - p.blk0, nframes, f64, s);
+    else launch_hog_pass2<false>(p, p.blk_per_frame, nframes, f64, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -305,6 +305,12 @@ class Handle:
         Roots and cells are then plane coordinates: the image cell is root_x - padx"""
         self.check(self.lib.pbd_set_padding(self.h, int(padx), int(pady)))
 
+    def set_fine_octave(self, on: bool) -> None:
+        """pbd_set_fine_octave: every image plan the handle builds afterwards has nfine = min(interval, nlevels) more levels in
+        front -- reference level i's image at bin size sbin / 2, scale halved (fineoctave.py states the rule); levels index the
+        longer list"""
+        self.check(self.lib.pbd_set_fine_octave(self.h, 1 if on else 0))
+
     def set_nms(self, overlap: Optional[float]) -> None:
         """pbd_set_nms: every detect* call of this handle returns, per frame, Candidate.sort + Candidate.nonMaximaSuppression(
         (rows, cols), candidates, overlap) of what it found, computed on the device (cells/detect.cpp:237-238,
@@ -384,7 +390,8 @@ class Handle:
         """pbd_debug_set_option: force one of this handle's launch choices (tests), the default value restoring the automatic
         one.  _lib.DT_LANE_SHIFT: 0..6, 64 >> value rows per wave of the distance transform (-1); _lib.DT_COOP: 0, never
         its cooperative kernel (1); _lib.DT_COOP_G: 4 or 8 rows per wave of that kernel (0); _lib.DP_BUDGET_MB: > 0, the
-        dynamic program's scratch per chunk of frames (0: 8 GB); _lib.GRID_NMS_LANES: 1 or 64 lanes per block of k_grid_nms (0: by sz)."""
+        dynamic program's scratch per chunk of frames (0: 8 GB); _lib.GRID_NMS_LANES: 1 or 64 lanes per block of k_grid_nms (0: by sz);
+        _lib.HOG_TWO_PASS: 1, the HOG histograms never take the fused gradient + histogram kernel (0)."""
         self.check(self.lib.pbd_debug_set_option(self.h, option, value))
 
     # ---- helpers -------------------------------------------------------------------------------
@@ -1295,6 +1302,7 @@ class PartsBasedDetector:
         self._nms = nms
         self._walk = "reference"
         self._pad = (0, 0)                         # setPadding: off
+        self._fine = False                         # setFineOctave: off
         self._root_nms = 0                         # setRootNMS: off
         self._top_k = 0                            # setTopK: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
@@ -1324,6 +1332,8 @@ class PartsBasedDetector:
             self.hd.set_walk(self.WALKS[self._walk])
         if self._pad != (0, 0):
             self.hd.set_padding(*self._pad)
+        if self._fine:
+            self.hd.set_fine_octave(True)
         if self._root_nms:
             self.hd.set_root_nms(self._root_nms)
         if self._top_k:
@@ -1367,6 +1377,16 @@ class PartsBasedDetector:
         if self.hd is not None:
             self.hd.set_padding(px, py)
         self._pad = (px, py)
+
+    def setFineOctave(self, on: bool) -> None:
+        """search an octave above the frame from now on (pbd_set_fine_octave; kept across distributeModel and updateModel): the
+        first `interval` pyramid levels are computed a second time at bin size sbin / 2 on the same level images, so that an
+        object of half the model's template size is found.  These levels come first: a Candidate's level then indexes the longer
+        list (features_.scales() gives its scales).  Needs an even sbin >= 4; off by default"""
+        on = bool(on)
+        if self.hd is not None:
+            self.hd.set_fine_octave(on)
+        self._fine = on
 
     def setRootNMS(self, sz: int) -> None:
         """the reference's commented-out ssp_.nonMaxSuppression(rootv, scales) (src/PartsBasedDetector.cpp:86) from now on
@@ -2150,6 +2170,11 @@ class DetectorPool:
         """PartsBasedDetector.setPadding on every lane (no batch may be pending)"""
         for d in self.dets:
             d.setPadding(padx, pady)
+
+    def setFineOctave(self, on: bool) -> None:
+        """PartsBasedDetector.setFineOctave on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setFineOctave(on)
 
     def setRootNMS(self, sz: int) -> None:
         """PartsBasedDetector.setRootNMS on every lane (no batch may be pending)"""

@@ -333,13 +333,22 @@ def placement_score(flat, resp: np.ndarray, c: int, placement) -> float:
     return s
 
 
+def _features_pyramid(flat, im, dtype, fine: bool):
+    """the oracle's level list, or with the fine octave in front of it (fineoctave.py): levels then index the longer list"""
+    from oracle import oracle
+    if not fine:
+        return oracle.features_pyramid(flat, im, dtype)
+    from .fineoctave import features_pyramid
+    return features_pyramid(flat, im, dtype, True)
+
+
 class FrameMaps:
     """the oracle's features, responses and per-component DP maps of one frame (computed on first use per level)"""
 
-    def __init__(self, flat, im: np.ndarray, dtype=np.float32, walk: str = "reference", pad=(0, 0)):
+    def __init__(self, flat, im: np.ndarray, dtype=np.float32, walk: str = "reference", pad=(0, 0), fine: bool = False):
         from oracle import oracle
         self.oracle, self.flat, self.dtype, self.walk = oracle, flat, dtype, walk
-        self.feats, self.scales = oracle.features_pyramid(flat, im, dtype)
+        self.feats, self.scales = _features_pyramid(flat, im, dtype, fine)
         if tuple(pad) != (0, 0):   # the padded pyramid (padding.py): every map below follows the padded planes
             from .padding import pad_features
             self.feats = [pad_features(f, pad[0], pad[1], flat.flen) for f in self.feats]
@@ -446,15 +455,16 @@ def mask_responses(uflat, resp, scale, boxes, overlap, mixtures=None, dtype=np.f
 
 
 def latent_search(model, im: np.ndarray, boxes, overlap: float, mixtures=None, dtype=np.float32, walk: str = "reference",
-                  pad=(0, 0)):
+                  pad=(0, 0), fine: bool = False):
     """the latent positive of one frame (pbd_detect_latent): dict(level, component, root_x, root_y, score (float), parts
     (nparts, 4) x, y, w, h, placement [(x, y, mixture)], found), walked through the oracle's maps of the masked responses of the
     unique model (walk "argmax": raw_maps' of the best level and component); ties go to the first in (level, component, y, x)
-    order.  pad: (padx, pady) of a padded pyramid (padding.py): root_x / root_y and the placement are plane coordinates"""
+    order.  pad: (padx, pady) of a padded pyramid (padding.py): root_x / root_y and the placement are plane coordinates.  fine: the
+    level list with the fine octave in front (fineoctave.py)"""
     from oracle import oracle
     from .padding import pad_features
     uflat = unique_model(model).flatten()
-    feats, scales = oracle.features_pyramid(uflat, im, dtype)
+    feats, scales = _features_pyramid(uflat, im, dtype, fine)
     best = None
     for lvl, feat in enumerate(feats):
         feat = pad_features(feat, pad[0], pad[1], uflat.flen)
