@@ -3,7 +3,7 @@
 //   detect -> "Number of candidates" -> Candidate::sort [-> nonMaximaSuppression] -> list the best ones.
 // The GUI part of the reference's demo (Visualize, highgui) is out of scope.
 //
-//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--pad X[,Y]] [--fine-octave] [--top N] [--staged]
+//   pbd_demo model.(yml|xml|mat) image.(ppm|pgm) [--double] [--nms OVERLAP] [--device-nms OVERLAP] [--walk reference|argmax] [--root-nms SZ] [--top-k K] [--scale-nms DL] [--pad X[,Y]] [--fine-octave] [--top N] [--staged]
 //            [--stream HANDLES FRAMES] [--conv-mode N] [--also IMAGE ...] [--depth DEPTH.pgm [--camera FX,FY,CX,CY]
 //            [--remove-planes] [--depth-consistency ZFACTOR] [--depth-prune FX,WIDTH,TOL] [--poses]] [--mask LABELS.pgm [--masked OUT.ppm]]
 //            [--part-scores] [--marginal-pose PART]
@@ -13,6 +13,8 @@
 //           (pbd_set_root_nms: the reference's commented-out ssp_.nonMaxSuppression(rootv, scales)); not with --staged
 //   --top-k K: at most K candidates per image: only the K best roots among those the threshold (and --root-nms, --depth-prune) leave
 //           are walked and listed (pbd_set_top_k); not with --staged
+//   --scale-nms DL: a root's duplicates within DL pyramid levels (0..255) and on other components are suppressed before the walk
+//           and before --top-k (pbd_set_scale_nms); not with --staged
 //   --pad X[,Y]: the padded pyramid of the Matlab detector (pbd_set_padding): every feature level grows by X (Y; Y = X when not
 //           given) cells of the boundary occlusion feature on each side, so that roots and parts can lie outside the image; the
 //           root cell a candidate line prints is then a cell of the padded plane.  Not with --depth-prune or --marginal-pose
@@ -70,6 +72,7 @@ using namespace pbdhost;
 static int g_walk = PBD_WALK_REFERENCE;   // --walk
 static int g_root_nms = 0;                // --root-nms
 static int g_top_k = 0;                   // --top-k
+static int g_scale_nms = -1;              // --scale-nms: the level distance, -1 off
 static int g_padx = 0, g_pady = 0;        // --pad
 static bool g_fine = false;               // --fine-octave
 static bool g_part_scores = false;        // --part-scores
@@ -104,6 +107,7 @@ static int run_batch(Model &model, const std::vector<Image> &ims, float nms, flo
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
+    pbd.setScaleNMS(g_scale_nms >= 0, g_scale_nms >= 0 ? g_scale_nms : 0);
     pbd.setPadding(g_padx, g_pady);
     pbd.setFineOctave(g_fine);
     pbd.distributeModel(model);
@@ -194,6 +198,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
     pbd.setWalk(g_walk);
     pbd.setRootNMS(g_root_nms);
     pbd.setTopK(g_top_k);
+    pbd.setScaleNMS(g_scale_nms >= 0, g_scale_nms >= 0 ? g_scale_nms : 0);
     pbd.setPadding(g_padx, g_pady);
     pbd.setFineOctave(g_fine);
     if (g_prune) pbd.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
@@ -204,6 +209,7 @@ static int run(Model &model, const Image &im, bool staged, float nms, float dnms
         if (dnms >= 0) fs.setNonMaximaSuppression(dnms);
         fs.setRootNMS(g_root_nms);
         fs.setTopK(g_top_k);
+        fs.setScaleNMS(g_scale_nms >= 0, g_scale_nms >= 0 ? g_scale_nms : 0);
         fs.setPadding(g_padx, g_pady);
         fs.setFineOctave(g_fine);
         if (g_prune) fs.setDepthPrune(true, g_prune_fx, g_prune_width, g_prune_tol);
@@ -396,7 +402,7 @@ static int run_augment(Model &model, const Image &im, double degrees, bool mirro
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--pad x[,y]] [--fine-octave] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
+        std::fprintf(stderr, "Usage: pbd_demo model_file image_file [--double] [--nms overlap] [--device-nms overlap] [--walk reference|argmax] [--root-nms sz] [--top-k k] [--scale-nms dl] [--pad x[,y]] [--fine-octave] [--top n] [--staged] [--stream handles frames] [--conv-mode 0..6 (5|6: matrix cores, any filter size, float only)] [--also image]... [--depth depth.pgm [--camera fx,fy,cx,cy] [--remove-planes] [--depth-consistency zfactor] [--depth-prune fx,width,tol] [--poses]] [--mask labels.pgm [--masked out.ppm]] [--part-scores] [--marginal-pose part] [--augment deg[,mirror] out.ppm]\n");
         return -1;
     }
     const char *augment_path = NULL;
@@ -433,6 +439,13 @@ int main(int argc, char **argv)
             char tail = 0;
             if (std::sscanf(argv[++i], "%d%c", &g_top_k, &tail) != 1 || g_top_k < 0 || g_top_k > (1 << 30)) {
                 std::fprintf(stderr, "--top-k takes a count, 0 (off) or 1..1073741824\n");
+                return -1;
+            }
+        }
+        else if (!std::strcmp(argv[i], "--scale-nms") && i + 1 < argc) {
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d%c", &g_scale_nms, &tail) != 1 || g_scale_nms < 0 || g_scale_nms > 255) {
+                std::fprintf(stderr, "--scale-nms takes a level distance, 0..255\n");
                 return -1;
             }
         }
@@ -503,6 +516,10 @@ int main(int argc, char **argv)
     }
     if (g_top_k && staged) {
         std::fprintf(stderr, "--top-k is not applied by the staged run: not with --staged\n");
+        return -1;
+    }
+    if (g_scale_nms >= 0 && staged) {
+        std::fprintf(stderr, "--scale-nms is not applied by the staged run: not with --staged\n");
         return -1;
     }
     if (g_part_scores && (staged || stream_k > 0 || !also.empty())) {

@@ -246,7 +246,8 @@ int pbd_set_fine_octave(pbd_handle *h, int enable);
  * enable = 0: off.  A NaN overlap is PBD_ERR_INVALID; PBD_ERR_STATE while a batch is in flight (the setting is latched at
  * submit); PBD_ERR_UNSUPPORTED together with level sharding (world > 1), in either order of the two calls: suppression of one
  * rank's levels is not suppression of the union.  With pbd_set_top_k on, K is taken before the suppression, so fewer than K may
- * survive it; root NMS plus top-K is the combination that keeps K distinct objects. */
+ * survive it; root NMS, scale NMS (pbd_set_scale_nms) and top-K together keep K distinct objects -- root NMS alone works
+ * inside one (level, component) plane, so that without scale NMS the K may be one object seen on K neighbouring levels. */
 int pbd_set_nms(pbd_handle *h, int enable, float overlap);
 /* The walk from a root to its parts (new surface, opt-in).  A child's mixture is m = Ik[slot + pm][py][px] in both modes; with k
  * the plane of that mixture:
@@ -628,6 +629,50 @@ int pbd_top_k(pbd_handle *h, int nframes, int k, const int32_t *cand, int ncand,
               int *nout);
 int pbd_top_k_device(pbd_handle *h, int nframes, int k, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out,
                      int out_capacity);
+
+/* Scale NMS: a root's duplicates on neighbouring pyramid levels and components (new surface; opt-in, off on a new handle).  An
+ * object fires at the same image position on several neighbouring levels and on several components; root NMS works inside one
+ * (level, component) plane only.  The reference's commented-out call took the scales: ssp_.nonMaxSuppression(rootv, scales)
+ * (src/PartsBasedDetector.cpp:86).  The rule, stated here once; all arithmetic is integer, on the rectangle the walk writes:
+ *   rect(r)          (x, y, w, h), the rectangle of part 0 of root r: words 8..11 of its record.  For a root cell: part_rect of the
+ *                    cell with the winning root type's filter side, the level's scale and the pad of pbd_set_padding
+ *   covers(a, b)     w_a > 0 and h_a > 0 and 2 x_a <= 2 x_b + w_b < 2 (x_a + w_a) and 2 y_a <= 2 y_b + h_b < 2 (y_a + h_a): b's
+ *                    centre, doubled to stay in integers, lies inside a's rectangle
+ *   neighbours(a, b) a != b, both in the same frame, |level_a - level_b| <= dl, and covers(a, b) or covers(b, a).  Symmetric.
+ *                    Every component takes part, and a's own plane does.  Levels are the indices of the frame's own level list
+ *                    (with the fine octave the longer list, whose scales still ascend; in a mixed-size or region call the frame's
+ *                    own levels); dl at or above the level count means every level
+ *   better(a, b)     score_a > score_b; at equal scores (+0.0 and -0.0 tie) a is better when it comes earlier in the find order
+ *                    (level, component, y, x).  The order is total.  In the detect path the scores are rootv in the handle's T; in
+ *                    the list form the records' float scores, and earlier means earlier in the list -- pbd_top_k*'s conventions,
+ *                    its remark on T = double included: only the detect-path form sees differences below float precision
+ *   eligible         rootv > (T)thresh, the find's own expression (NaN never is), and the bytes of depth pruning and of root NMS
+ *                    where those are on: the step runs after both and before top-K
+ *   result           an eligible root is kept iff no eligible neighbour is better.  A local-maximum rule, not a greedy pass: a
+ *                    root a better neighbour beats is dropped even if that neighbour is dropped itself.  The result does not
+ *                    depend on the order of evaluation; of two neighbouring roots at most one survives; a frame's best root does
+ * pbd_set_scale_nms(h, enable, dl): dl in 0..255 whatever `enable`, else PBD_ERR_INVALID; enable = 0 is off.  PBD_ERR_STATE while a
+ * batch is in flight (the setting is latched at submit); kept across model updates; the resident result stays.  With it on, every
+ * later call of the entry points pbd_set_top_k lists -- pbd_argmin_device_out included, which so re-emits the resident list
+ * under another dl without running the dynamic program again -- keeps only the scale-space maxima: the same records, fewer of
+ * them, in the same order, every word untouched.  max_candidates, the caller's capacity, PBD_ERR_CAPACITY, payload word 0,
+ * pbd_set_top_k (K is taken among the maxima) and pbd_set_nms see only the kept list.  NOT applied by pbd_dp_argmin,
+ * pbd_detect_latent* or the trainers' re-walks.  PBD_ERR_UNSUPPORTED together with level sharding (world > 1), in either order of
+ * the two calls, as for pbd_set_nms: one rank does not hold the neighbouring levels; pbd_scale_nms on the merged list is the form
+ * for sharded handles.
+ * pbd_scale_nms / pbd_scale_nms_device: the rule per frame of a caller's list (dl in 0..255, else PBD_ERR_INVALID).  A record with a
+ * NaN score is never kept and is nobody's neighbour; the kept records come out in their input order.  Records must be grouped by
+ * ascending frame, as for pbd_suppress* (host form: refused otherwise).  Conventions of pbd_depth_prune* above, word for word:
+ * frame_offset, in place allowed for the host form, *nout / word 0 = the kept count (which may exceed the capacity), an input word 0
+ * that is negative or > capacity gives -1, a record whose frame index is outside 0 .. nframes - 1 or whose nparts is outside
+ * 1..max parts is dropped and is nobody's rival (host form: refused), no host synchronisation in the device form, the resident
+ * result untouched, PBD_ERR_STATE while a batch is in flight.  Each record tests the records of its frame: the cost grows with
+ * the square of a frame's list. */
+int pbd_set_scale_nms(pbd_handle *h, int enable, int dl);
+int pbd_scale_nms(pbd_handle *h, int nframes, int dl, const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity,
+                  int *nout);
+int pbd_scale_nms_device(pbd_handle *h, int nframes, int dl, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out,
+                         int out_capacity);
 
 /* Suppression of a caller's list (new surface): exactly the pbd_set_nms stage above -- per frame the stable score sort, then the
  * greedy painted-canvas suppression -- applied to any records of this handle, e.g. after pbd_depth_consistency, or to the merged
@@ -1434,6 +1479,8 @@ enum { PBD_K_RESIZE = 0, PBD_K_PYRDOWN, PBD_K_HOG_HIST, PBD_K_HOG_FEAT, PBD_K_CO
           transform kernels, counted here and not under k_dt_rows / k_dt_cols), the messages, the contexts, the reduction over the
           parent's types; pbd_marginal_poses*: the decode */
        PBD_K_MM_DT_ROWS, PBD_K_MM_DT_COLS, PBD_K_MM_MESSAGES, PBD_K_MM_CONTEXT, PBD_K_MM_DOWN, PBD_K_MM_DECODE,
+       /* pbd_set_scale_nms / pbd_scale_nms*: the scale-space maxima of the root cells, or of a list's records */
+       PBD_K_SCALE_NMS,
        PBD_K_COUNT };
 /* on = 1: every kernel launch carries a start / stop event pair (the runtime isolates a timed dispatch: about 1 ms per
  * 64-frame step of ~45 launches); on = 2: only the convolution (one launch per step: free); 0: off */

@@ -313,6 +313,24 @@ inline void top_k(pbd_handle *h, int k, std::vector<int32_t> &buf, int &n)
     n = kept;
 }
 
+// pbd_set_scale_nms: only the roots no better root within dl pyramid levels beats whose rectangle's centre lies in its own, or the
+// other way round, from every later walk of this handle (after depth pruning and root NMS, before top-K); on = false: off
+template <class Tr>
+inline void set_scale_nms(pbd_handle *h, bool on, int dl)
+{
+    check<Tr>(h, pbd_set_scale_nms(h, on ? 1 : 0, dl));
+}
+
+// pbd_scale_nms over n records of this handle in `buf`, in place: n becomes the kept count, the kept records stay in order; every
+// record is taken as one of this frame (frame field 0)
+template <class Tr>
+inline void scale_nms(pbd_handle *h, int dl, std::vector<int32_t> &buf, int &n)
+{
+    int kept = 0;
+    check<Tr>(h, pbd_scale_nms(h, 1, dl, n ? &buf[0] : NULL, n, 0, n ? &buf[0] : NULL, n, &kept));
+    n = kept;
+}
+
 // pbd_candidate records -> the host's Candidates (include/Candidate.hpp:56-80)
 template <class Tr>
 inline void unpack_candidates(pbd_handle *h, const std::vector<int32_t> &buf, int n, std::vector<typename Tr::Candidate> &out)

@@ -601,6 +601,8 @@ class PartsBasedDetector {
     int walk_;
     int root_nms_;
     int top_k_;
+    bool scale_nms_on_;
+    int scale_nms_dl_;
     int padx_, pady_;
     bool fine_;
     bool depth_on_;
@@ -617,7 +619,7 @@ public:
     // max_batch: the most images one detectBatch() call takes
     explicit PartsBasedDetector(int device = 0, int conv_mode = PBD_CONV_EXACT, int max_batch = 64)
         : h_(NULL), device_(device), conv_mode_(conv_mode), max_batch_(max_batch), nms_(false), overlap_(0.f), walk_(PBD_WALK_REFERENCE),
-          root_nms_(0), top_k_(0), padx_(0), pady_(0), fine_(false), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
+          root_nms_(0), top_k_(0), scale_nms_on_(false), scale_nms_dl_(0), padx_(0), pady_(0), fine_(false), depth_on_(false), zfactor_(0.03f), prune_on_(false), prune_fx_(0.f), prune_width_(0.f), prune_tol_(0.3f),
           planes_(0) {}
     ~PartsBasedDetector() { pbd_destroy(h_); }
     const std::string &name() const { return name_; }
@@ -631,6 +633,7 @@ public:
         if (walk_ != PBD_WALK_REFERENCE) pbdbind::check<HostTraits<T> >(h_, pbd_set_walk(h_, walk_));
         if (root_nms_) pbdbind::set_root_nms<HostTraits<T> >(h_, root_nms_);
         if (top_k_) pbdbind::set_top_k<HostTraits<T> >(h_, top_k_);
+        if (scale_nms_on_) pbdbind::set_scale_nms<HostTraits<T> >(h_, true, scale_nms_dl_);
         if (padx_ || pady_) pbdbind::set_padding<HostTraits<T> >(h_, padx_, pady_);
         if (fine_) pbdbind::set_fine_octave<HostTraits<T> >(h_, true);
         if (prune_on_) pbdbind::set_depth_prune<HostTraits<T> >(h_, true, prune_fx_, prune_width_, prune_tol_);
@@ -724,6 +727,36 @@ public:
         const std::vector<int32_t> in = rec;
         int n = (int)candidates.size();
         pbdbind::top_k<HostTraits<T> >(h_, k, rec, n);
+        const size_t stride = (size_t)pbd_candidate_stride(h_);
+        std::vector<Candidate> kept;
+        for (size_t i = 0, j = 0; i < candidates.size() && j < (size_t)n; ++i)   // the kept records are the input's, in order
+            if (std::memcmp(&in[i * stride], &rec[j * stride], stride * sizeof(int32_t)) == 0) {
+                kept.push_back(candidates[i]);
+                ++j;
+            }
+        candidates.swap(kept);
+    }
+    // new surface: a root's duplicates on neighbouring pyramid levels and components suppressed from now on (pbd_set_scale_nms):
+    // of the roots the threshold, depth pruning and root NMS leave, only those are walked and returned that no better root within
+    // dl levels of the same frame beats -- two roots being neighbours when the centre of one's rectangle lies inside the other's;
+    // top-K is then taken among them.  dl in 0..255; on = false turns it off (the default).  Kept across distributeModel().
+    void setScaleNMS(bool on, int dl = 1)
+    {
+        if (dl < 0 || dl > 255) throw Error(PBD_ERR_INVALID, "scale NMS: a level distance of 0..255");
+        if (h_) pbdbind::set_scale_nms<HostTraits<T> >(h_, on, dl);
+        scale_nms_on_ = on;
+        scale_nms_dl_ = dl;
+    }
+    // the candidates no better neighbouring candidate within dl levels beats, in their input order, decided on the device
+    // (pbd_scale_nms): for a list built elsewhere, e.g. the merged lists of level-sharded detectors; every candidate is taken as one
+    // of this frame
+    void scaleNMS(std::vector<Candidate> &candidates, int dl)
+    {
+        if (!h_) throw Error(PBD_ERR_STATE, "scaleNMS() before distributeModel()");
+        std::vector<int32_t> rec = records(candidates);
+        const std::vector<int32_t> in = rec;
+        int n = (int)candidates.size();
+        pbdbind::scale_nms<HostTraits<T> >(h_, dl, rec, n);
         const size_t stride = (size_t)pbd_candidate_stride(h_);
         std::vector<Candidate> kept;
         for (size_t i = 0, j = 0; i < candidates.size() && j < (size_t)n; ++i)   // the kept records are the input's, in order
@@ -1414,6 +1447,11 @@ public:
     void setTopK(int k)
     {
         for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_top_k<HostTraits<T> >(h_[i], k);
+    }
+    // every handle suppresses a root's duplicates on neighbouring levels (PartsBasedDetector::setScaleNMS); nothing may be pending
+    void setScaleNMS(bool on, int dl = 1)
+    {
+        for (size_t i = 0; i < h_.size(); ++i) pbdbind::set_scale_nms<HostTraits<T> >(h_[i], on, dl);
     }
     // every handle prunes the roots of a frame submitted with its depth image (PartsBasedDetector::setDepthPrune); nothing may be
     // pending

@@ -292,6 +292,35 @@ inline void hipTopK(pbd_handle *h, std::vector<typename CvTraits<T>::Candidate> 
     candidates.swap(kept);
 }
 
+// A root's duplicates on neighbouring pyramid levels and components suppressed in every later hipDetect / hipDetectBatch of this
+// handle (pbd_set_scale_nms): only the roots no better root within dl levels beats whose rectangle's centre lies in its own, or the
+// other way round, are walked; dl in 0..255; on = false turns it off
+template <typename T>
+inline void hipSetScaleNMS(pbd_handle *h, bool on, int dl)
+{
+    pbdbind::set_scale_nms<CvTraits<T> >(h, on, dl);
+}
+
+// The candidates of one frame no better neighbouring candidate within dl levels beats, decided on the device (pbd_scale_nms), in
+// their input order: for a list built elsewhere, e.g. the merged lists of level-sharded handles
+template <typename T>
+inline void hipScaleNMS(pbd_handle *h, std::vector<typename CvTraits<T>::Candidate> &candidates, int dl)
+{
+    std::vector<int32_t> rec;
+    hipRecords(h, candidates, rec);
+    const std::vector<int32_t> in(rec);
+    int n = (int)candidates.size();
+    pbdbind::scale_nms<CvTraits<T> >(h, dl, rec, n);
+    const size_t stride = (size_t)pbd_candidate_stride(h);
+    std::vector<typename CvTraits<T>::Candidate> kept;
+    for (size_t i = 0, j = 0; i < candidates.size() && j < (size_t)n; ++i)   // the kept records are the input's, in order
+        if (std::memcmp(&in[i * stride], &rec[j * stride], stride * sizeof(int32_t)) == 0) {
+            kept.push_back(candidates[i]);
+            ++j;
+        }
+    candidates.swap(kept);
+}
+
 // Candidate::mask(im, candidates, mask) (include/Candidate.hpp:306-331) on the device (pbd_candidate_mask): mask becomes the
 // im.rows x im.cols CV_8U label image; every candidate is one of this frame
 template <typename T>

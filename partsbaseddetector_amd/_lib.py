@@ -38,6 +38,7 @@ KERNELS = ["k_resize", "k_pyrdown", "k_hog_hist", "k_hog_feat", "k_conv", "k_dt_
            "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick", "k_grid_nms", "k_top_k", "k_depth_prune"]
 # the profile ids of pbd_max_marginals / pbd_marginal_poses*, which follow KERNELS' (PBD_K_MM_*: id = len(KERNELS) + index)
 KERNELS_MM = ["k_mm_dt_rows", "k_mm_dt_cols", "k_mm_messages", "k_mm_context", "k_mm_down", "k_mm_decode"]
+KERNELS_SCALE_NMS = ["k_scale_nms"]   # PBD_K_SCALE_NMS, after PBD_K_MM_DECODE
 MM_VALUES, MM_DOWN, MM_PARENT_X, MM_PARENT_Y, MM_PARENT_K = 0, 1, 2, 3, 4   # pbd_get_marginals' selector
 PARTS_LITERAL, PARTS_XY = 0, 1   # pbd_boxes3d_camera's sample loop (include/pbd.h)
 
@@ -66,6 +67,7 @@ SYMBOLS = [
     "pbd_part_scores", "pbd_part_scores_device", "pbd_score_placements", "pbd_score_placements_device",
     "pbd_max_marginals", "pbd_get_marginals", "pbd_marginals_device", "pbd_marginal_poses", "pbd_marginal_poses_device",
     "pbd_set_padding", "pbd_set_fine_octave",
+    "pbd_set_scale_nms", "pbd_scale_nms", "pbd_scale_nms_device",
 ]
 
 
@@ -356,6 +358,9 @@ def load():
     lib.pbd_top_k_cells_device.argtypes = lib.pbd_top_k_cells.argtypes
     lib.pbd_top_k.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     lib.pbd_top_k_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.pbd_set_scale_nms.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.pbd_scale_nms.argtypes = lib.pbd_top_k.argtypes
+    lib.pbd_scale_nms_device.argtypes = lib.pbd_top_k_device.argtypes
     lib.pbd_set_depth_prune.argtypes = [C.c_void_p, C.POINTER(CDepthPruneCfg)]
     lib.pbd_bind_depth.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFrame), C.c_int]
     lib.pbd_bind_depth_device.argtypes = lib.pbd_bind_depth.argtypes

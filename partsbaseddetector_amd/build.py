@@ -17,7 +17,7 @@ SOURCES = ["pbd_capi.hip", "pbd_capi_post.hip", "pbd_capi_train.hip", "pbd_capi_
            "pbd_kernels_conv_mfma.hip", "pbd_kernels_conv_mfma_f64.hip", "pbd_kernels_conv_mfma_any.hip", "pbd_kernels_dp.hip", "pbd_kernels_post.hip",
            "pbd_kernels_depth.hip", "pbd_kernels_cloud.hip", "pbd_kernels_planes.hip", "pbd_kernels_consistency.hip",
            "pbd_kernels_publish.hip", "pbd_kernels_examples.hip", "pbd_kernels_qp.hip", "pbd_kernels_model.hip",
-           "pbd_kernels_warp.hip", "pbd_kernels_eval.hip", "pbd_kernels_kmeans.hip", "pbd_kernels_gridnms.hip", "pbd_kernels_topk.hip",
+           "pbd_kernels_warp.hip", "pbd_kernels_eval.hip", "pbd_kernels_kmeans.hip", "pbd_kernels_gridnms.hip", "pbd_kernels_topk.hip", "pbd_kernels_scalenms.hip",
            "pbd_kernels_depthprune.hip", "pbd_kernels_augment.hip", "pbd_kernels_partscores.hip", "pbd_kernels_marginals.hip"]
 HEADERS = ["pbd_internal.h", "pbd_handle.h", "pbd_device.h", "pbd_dp.h", "pbd_jacobi.h", "pbd_layout.h", "pbd_resample.h", "pbd_conv_mfma16.h", os.path.join("..", "..", "include", "pbd.h")]
 FLAGS = os.environ.get("PBD_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -1378,6 +1378,17 @@ static int enqueue_top_k(pbd_handle *h, Plan &P, int nframes, int k, const uint8
     return PBD_OK;
 }
 
+// pbd_set_scale_nms: of the root cells above the threshold whose bytes in ap.root_ok and ap.root_max (NULL: off) are set, those
+// no better neighbour within dl levels beats, a byte per root cell in h->sn_keep.  The byte implies the two it was built from.
+static int enqueue_scale_nms(pbd_handle *h, const ArgminParams &ap, int dl, hipStream_t st)
+{
+    HIPCHK(h, h->sn_keep.ensure(std::max<size_t>((size_t)ap.ntotal, 16)));
+    const ScaleNmsRoots a{dl, ap.root_ok, ap.root_max, h->sn_keep.as<uint8_t>()};
+    ProfScope ps(h, PBD_K_SCALE_NMS, st);
+    launch_scale_nms_roots(ap, a, h->f64, st);
+    return PBD_OK;
+}
+
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload,
                    int capacity, hipStream_t st, bool walk_only, RootSel sel)
 {
@@ -1409,6 +1420,10 @@ int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, i
     if (sel.nms > 0 && !walk_only) {
         if (int rc = enqueue_root_nms(h, P, nframes, sel.nms, ap.root_ok, st)) return rc;
         ap.root_max = h->gn_max.as<uint8_t>();
+    }
+    if (sel.scale >= 0 && !walk_only && ap.ntotal > 0) {   // handed on as root_max: k_top_k and the find need no new mask
+        if (int rc = enqueue_scale_nms(h, ap, sel.scale, st)) return rc;
+        ap.root_max = h->sn_keep.as<uint8_t>();
     }
     if (sel.top > 0 && !walk_only && ap.ntotal > 0) {
         if (int rc = enqueue_top_k(h, P, nframes, sel.top, ap.root_ok, ap.root_max, st)) return rc;
@@ -2111,6 +2126,9 @@ int pbd_set_level_shard(pbd_handle *h, int rank, int world)
         if (world > 1 && h->nms)
             return fail(h, PBD_ERR_UNSUPPORTED, "level sharding with non-maxima suppression on: suppression of one rank's levels "
                         "is not suppression of the union (pbd_set_nms(h, 0, ...) first)");
+        if (world > 1 && h->scale_nms >= 0)
+            return fail(h, PBD_ERR_UNSUPPORTED, "level sharding with scale NMS on: one rank does not hold the neighbouring levels "
+                        "(pbd_set_scale_nms(h, 0, 0) first; pbd_scale_nms on the merged list)");
         if (rank == h->shard_rank && world == h->shard_world) return PBD_OK;
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->shard_rank = rank; h->shard_world = world;
@@ -2192,6 +2210,18 @@ int pbd_set_top_k(pbd_handle *h, int k)
     return entry(h, true, kIdle, [&]() -> int {
         if (k < 0 || k > (1 << 30)) return fail(h, PBD_ERR_INVALID, "top-K %d (0: off, 1..2^30)", k);
         h->top_k = k;                     // the resident result stays: the planes do not depend on it
+        return PBD_OK;
+    });
+}
+
+int pbd_set_scale_nms(pbd_handle *h, int enable, int dl)
+{
+    return entry(h, true, kIdle, [&]() -> int {
+        if (dl < 0 || dl > 255) return fail(h, PBD_ERR_INVALID, "scale NMS level distance %d (0..255)", dl);
+        if (enable && h->shard_world > 1)
+            return fail(h, PBD_ERR_UNSUPPORTED, "scale NMS with level sharding (world %d): one rank does not hold the neighbouring "
+                        "levels (pbd_scale_nms on the merged list)", h->shard_world);
+        h->scale_nms = enable ? dl : -1;  // the resident result stays: the planes do not depend on it
         return PBD_OK;
     });
 }
@@ -2655,7 +2685,7 @@ const char *pbd_kernel_name(int k)
                                              "k_ev_nms_greedy", "k_ev_nms_emit", "k_ev_best", "k_ev_pck", "k_ev_apk_rank",
                                              "k_ev_apk_close", "k_ev_apk_ap", "k_qp_hinge", "k_km_trials", "k_km_pick",
                                              "k_grid_nms", "k_top_k", "k_depth_prune", "k_mm_dt_rows", "k_mm_dt_cols",
-                                             "k_mm_messages", "k_mm_context", "k_mm_down", "k_mm_decode"};
+                                             "k_mm_messages", "k_mm_context", "k_mm_down", "k_mm_decode", "k_scale_nms"};
     return (k >= 0 && k < PBD_K_COUNT) ? names[k] : "?";
 }
 int pbd_synchronize(pbd_handle *h)

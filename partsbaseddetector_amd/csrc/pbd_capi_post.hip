@@ -353,6 +353,36 @@ int enqueue_top_k_list(pbd_handle *h, int nframes, int k, const int32_t *d_in, i
     return PBD_OK;
 }
 
+// ---- scale NMS of a caller's list (pbd_scale_nms*; pbd_kernels_scalenms.hip)
+int check_scale_nms_list(pbd_handle *h, int nframes, int dl)
+{
+    if (nframes < 1) return fail(h, PBD_ERR_INVALID, "nframes %d", nframes);
+    if (dl < 0 || dl > 255) return fail(h, PBD_ERR_INVALID, "scale NMS level distance %d (0..255)", dl);
+    return PBD_OK;
+}
+
+// the kept flag of every record and the depth-consistency filter's compaction on the handle's stream: payload d_in (capacity
+// records) -> d_out (out_cap records)
+int enqueue_scale_nms_list(pbd_handle *h, int nframes, int dl, const int32_t *d_in, int capacity, int frame_offset, int32_t *d_out,
+                           int out_cap)
+{
+    const int cap = std::max(capacity, 0), blocks = dc_record_blocks(cap);
+    DcParams p{};
+    if (int rc = carve(h, h->snl_ws, [&](Carve &c) {
+            p.flag = c.take<int>((size_t)blocks * 256 * sizeof(int));
+            p.blk = c.take<int>((size_t)blocks * sizeof(int));
+        })) return rc;
+    p.in = d_in; p.in_cap = cap; p.stride = stride(h); p.max_parts = h->max_parts;
+    p.nframes = nframes; p.frame_offset = frame_offset;
+    p.out = d_out; p.out_cap = std::max(out_cap, 0);
+    {
+        ProfScope ps(h, PBD_K_SCALE_NMS, h->stream);
+        launch_scale_nms_records(p, dl, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return PBD_OK;
+}
+
 // ---- suppression of a caller's list (pbd_suppress*): the canvas tables of its frame sizes, kept for the next call of the
 // same sizes
 int get_suppress_plan(pbd_handle *h, int nframes, const int *rows, const int *cols, Plan **out)
@@ -1121,6 +1151,32 @@ int pbd_top_k_device(pbd_handle *h, int nframes, int k, const int32_t *d_payload
         if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
         if (int rc = check_top_k_list(h, nframes, k)) return rc;
         return enqueue_top_k_list(h, nframes, k, d_payload, capacity, frame_offset, d_out, out_capacity);
+    });
+}
+
+// The scale-space maxima of every frame of a caller's list.  See include/pbd.h.
+int pbd_scale_nms(pbd_handle *h, int nframes, int dl, const int32_t *cand, int ncand, int frame_offset, int32_t *out, int capacity,
+                  int *nout)
+{
+    return entry(h, nout && (ncand <= 0 || cand) && (capacity <= 0 || out), kIdle, [&]() -> int {
+        *nout = 0;
+        if (ncand < 0 || capacity < 0) return fail(h, PBD_ERR_INVALID, "ncand %d, capacity %d", ncand, capacity);
+        if (int rc = check_scale_nms_list(h, nframes, dl)) return rc;
+        if (int rc = check_records(h, nframes, cand, ncand, frame_offset, kRecAscending)) return rc;
+        if (ncand == 0) return PBD_OK;
+        return host_list_call(h, h->snl_in, h->snl_out, cand, ncand, out, capacity, nout, [&](const int32_t *din, int32_t *dout) {
+            return enqueue_scale_nms_list(h, nframes, dl, din, ncand, frame_offset, dout, ncand);
+        });
+    });
+}
+
+int pbd_scale_nms_device(pbd_handle *h, int nframes, int dl, const int32_t *d_payload, int capacity, int frame_offset, int32_t *d_out,
+                         int out_capacity)
+{
+    return entry(h, d_payload && d_out, kIdle, [&]() -> int {
+        if (capacity < 0 || out_capacity < 0) return fail(h, PBD_ERR_INVALID, "capacity %d, out_capacity %d", capacity, out_capacity);
+        if (int rc = check_scale_nms_list(h, nframes, dl)) return rc;
+        return enqueue_scale_nms_list(h, nframes, dl, d_payload, capacity, frame_offset, d_out, out_capacity);
     });
 }
 

@@ -389,6 +389,7 @@ struct Handle : ErrCtx {
     float nms_overlap = 0.f;
     int root_nms = 0;                // grid NMS of the root scores before the find (pbd_set_root_nms): window size, 0 = off; read at enqueue
     int top_k = 0;                   // the K best roots of each frame before the find (pbd_set_top_k): 0 = off; read at enqueue
+    int scale_nms = -1;              // scale NMS of the roots before top-K and the find (pbd_set_scale_nms): dl, -1 = off; read at enqueue
     int gn_lanes = 0;                // forced lanes per block of k_grid_nms, 1 or 64; 0: by sz (pbd_debug_set_option)
     // scale-depth pruning of the roots before the find (pbd_set_depth_prune; read at enqueue) and the depth images bound to the
     // next detect call (pbd_bind_depth*): their frame table, the host form's copies, the byte per root cell.  claim_depth moves
@@ -423,6 +424,10 @@ struct Handle : ErrCtx {
     StagedTable tk_tab;
     DevBuf tk_src, tk_mask, tk_dst;
     DevBuf tkl_ws, tkl_in, tkl_out;
+    // scale NMS: the detect path's byte per root cell (pbd_set_scale_nms); pbd_scale_nms*: the workspace (flags and block counts),
+    // the host form's records and output
+    DevBuf sn_keep;
+    DevBuf snl_ws, snl_in, snl_out;
     DevBuf dbg_in, dbg_out;          // pbd_debug_postprocess
     // pbd_boxes3d*: the frame table (staged in pinned memory, rewritten only once its previous copy has completed); the host
     // form's depth images, records and boxes.  Never the detect path's buffers: the resident result stays readable.
@@ -692,8 +697,8 @@ void post_canvas_plan(Plan &M);
 // what restricts the roots a find lists beyond the threshold: the window of pbd_set_root_nms (0: off) and whether the depth images
 // claimed for the call (h->dpr_call) prune them (pbd_set_depth_prune).  The detect entry points pass root_sel(h); DynamicProgram::
 // argmin, the latent search and the trainers' re-walks pass none
-struct RootSel { int nms = 0; bool prune = false; int top = 0; };   // top: the K of pbd_set_top_k (0: off)
-inline RootSel root_sel(const pbd_handle *h) { return {h->root_nms, !h->dpr_call.tab.empty(), h->top_k}; }
+struct RootSel { int nms = 0; bool prune = false; int top = 0; int scale = -1; };   // top: the K of pbd_set_top_k (0: off); scale: the dl of pbd_set_scale_nms (-1: off)
+inline RootSel root_sel(const pbd_handle *h) { return {h->root_nms, !h->dpr_call.tab.empty(), h->top_k, h->scale_nms}; }
 int enqueue_argmin(pbd_handle *h, Plan &P, int nframes, const float *d_scales, int frame_offset, int32_t *d_payload, int capacity,
                    hipStream_t st, bool walk_only = false, RootSel sel = {});
 int enqueue_post(pbd_handle *h, int nframes, int rows, int cols, float overlap, const int32_t *d_in, int in_cap, int frame_offset,

@@ -476,6 +476,14 @@ struct DepthPruneRoots {          // the plane form, next to the call's ArgminPa
     uint8_t *ok;                  // 1 / 0 per root cell, laid out as rootv; every byte written
 };
 
+// scale NMS of the root cells (pbd_set_scale_nms; pbd_kernels_scalenms.hip), next to the call's ArgminParams
+struct ScaleNmsRoots {
+    int dl;                       // neighbouring levels on either side, 0..255
+    const uint8_t *root_ok;       // pbd_set_depth_prune's byte per root cell (NULL: off)
+    const uint8_t *root_max;      // pbd_set_root_nms's byte per root cell (NULL: off)
+    uint8_t *dst;                 // 255 (eligible and kept) / 0 per root cell, laid out as rootv; every byte written
+};
+
 // the K best elements of every segment of a packed array (pbd_top_k_cells*, pbd_set_top_k; pbd_kernels_topk.hip)
 constexpr int kTkTile = 1024;     // elements per tile; every segment is cut into tiles of its own
 struct TopKTab {                  // [nseg + 1]: a segment's first element and first tile; entry nseg holds the totals
@@ -617,6 +625,10 @@ void launch_depth_prune_records(const DcParams &p, const DepthPruneRule &rule, h
 // the grid maxima of p's planes; lanes per block: grid_nms_lanes(sz, forced) = 1 or 64 (forced: 0 = by sz)
 int grid_nms_lanes(int sz, int forced);
 void launch_grid_nms(const GridNmsParams &p, bool f64, int lanes, hipStream_t s);
+// the scale-space maxima of the call's root cells into a.dst
+void launch_scale_nms_roots(const ArgminParams &p, const ScaleNmsRoots &a, bool f64, hipStream_t s);
+// the record form: p.flag / p.blk from the rule over each record's frame, then launch_dc_emit
+void launch_scale_nms_records(const DcParams &p, int dl, hipStream_t s);
 // the K best eligible elements of every segment of p (4 passes for float, 8 for double, then the ordered mark); the long longs of
 // p.part
 long long top_k_scan_parts(long long ntiles);

@@ -355,6 +355,24 @@ class Handle:
         and the other root filters leave (topk.top_k_cells_ref over the frame's rootv), before the walk; 0: off (the default)"""
         self.check(self.lib.pbd_set_top_k(self.h, int(k)))
 
+    def set_scale_nms(self, dl: Optional[int]) -> None:
+        """pbd_set_scale_nms: every detect* call of this handle keeps only the roots no better root beats whose rectangle's centre
+        lies in its own, or the other way round, within dl pyramid levels of the same frame (scalenms.keep_records over the
+        records), after depth pruning and root NMS and before top-K; None: off (the default)"""
+        self.check(self.lib.pbd_set_scale_nms(self.h, 0 if dl is None else 1, 0 if dl is None else int(dl)))
+
+    def scale_nms(self, nframes: int, dl: int, records: np.ndarray, frame_offset: int = 0, capacity: Optional[int] = None) -> np.ndarray:
+        """pbd_scale_nms: per frame the records (n, stride) no better neighbouring record beats, in input order; the records are
+        grouped by ascending frame (equal to scalenms.filter_records)"""
+        return self._list_call(self.lib.pbd_scale_nms, (int(nframes), int(dl)), records, frame_offset, capacity)
+
+    def scale_nms_device(self, nframes: int, dl: int, d_payload_ptr: int, capacity: int, frame_offset: int, d_out_ptr: int,
+                         out_capacity: int) -> None:
+        """pbd_scale_nms_device: the records of a device payload, the kept records into the payload at d_out_ptr (word 0 = kept
+        count, -1 when the input's word 0 is out of range); asynchronous on the handle's stream"""
+        self.check(self.lib.pbd_scale_nms_device(self.h, int(nframes), int(dl), d_payload_ptr, capacity, frame_offset, d_out_ptr,
+                                                 out_capacity))
+
     def top_k_cells(self, segments: Sequence[np.ndarray], k: int, masks: Optional[Sequence[Optional[np.ndarray]]] = None) -> List[np.ndarray]:
         """pbd_top_k_cells: the k best eligible elements of every segment (1-D after ravel, all float32 or all float64, any lengths,
         empty ones included), one launch sequence; masks: None, or one uint8 / bool array per segment.  Returns the uint8 arrays of
@@ -1089,7 +1107,7 @@ class Handle:
 
     def profile_read(self):
         out = {}
-        for k, name in enumerate(_lib.KERNELS + _lib.KERNELS_MM):
+        for k, name in enumerate(_lib.KERNELS + _lib.KERNELS_MM + _lib.KERNELS_SCALE_NMS):
             ms, n = C.c_double(), C.c_int()
             self.check(self.lib.pbd_profile_read(self.h, k, C.byref(ms), C.byref(n)))
             out[name] = (ms.value, n.value)
@@ -1305,6 +1323,7 @@ class PartsBasedDetector:
         self._fine = False                         # setFineOctave: off
         self._root_nms = 0                         # setRootNMS: off
         self._top_k = 0                            # setTopK: off
+        self._scale_nms: Optional[int] = None      # setScaleNMS: off
         self._zfactor: Optional[float] = None      # setDepthConsistency: off
         self._dprune: Optional[Tuple[float, float, float]] = None   # setDepthPrune: off
         self.remove_planes = bool(remove_planes)   # clusterObjects' default: the callers' remove_planes option
@@ -1338,6 +1357,8 @@ class PartsBasedDetector:
             self.hd.set_root_nms(self._root_nms)
         if self._top_k:
             self.hd.set_top_k(self._top_k)
+        if self._scale_nms is not None:
+            self.hd.set_scale_nms(self._scale_nms)
         if self._dprune is not None:
             self.hd.set_depth_prune(*self._dprune)
         self._name = getattr(model, "name", "")
@@ -1428,6 +1449,29 @@ class PartsBasedDetector:
             return []
         rec = self.hd.pack_candidates(cands)
         return kept_subsequence(cands, rec, self.hd.top_k(int(rec[:, 0].max()) + 1, k, rec))
+
+    def setScaleNMS(self, dl: Optional[int]) -> None:
+        """a root's duplicates on neighbouring pyramid levels and components suppressed from now on (pbd_set_scale_nms; kept across
+        distributeModel): of the roots the threshold, depth pruning and root NMS leave, only those are walked and returned that no
+        better root within dl levels of the same frame beats -- two roots being neighbours when the centre of one's rectangle lies
+        inside the other's.  Top-K is then taken among these scale-space maxima.  dl in 0..255; None: off (the default).
+        train() / trainmodel() never turn it on: mining needs every violator"""
+        if dl is not None and not 0 <= int(dl) <= 255:
+            raise PbdError(-1, f"scale NMS level distance {dl}: None (off) or 0..255")
+        if self.hd is not None:
+            self.hd.set_scale_nms(None if dl is None else int(dl))
+        self._scale_nms = None if dl is None else int(dl)
+
+    def scaleNMS(self, candidates: Sequence[Candidate], dl: int) -> List[Candidate]:
+        """per frame index the candidates no better neighbouring candidate within dl levels beats, in input order, decided on the
+        device (pbd_scale_nms); the candidates are grouped by ascending frame.  Equal to scalenms.filter_records.  The form for
+        the merged lists of level-sharded detectors"""
+        self._need()
+        cands = list(candidates)
+        if not cands:
+            return []
+        rec = self.hd.pack_candidates(cands)
+        return kept_subsequence(cands, rec, self.hd.scale_nms(int(rec[:, 0].max()) + 1, dl, rec))
 
     def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """the intent of the reference's commented-out ssp_.filterResponseByDepth (src/PartsBasedDetector.cpp:86-93) from now on
@@ -2185,6 +2229,11 @@ class DetectorPool:
         """PartsBasedDetector.setTopK on every lane (no batch may be pending)"""
         for d in self.dets:
             d.setTopK(k)
+
+    def setScaleNMS(self, dl: Optional[int]) -> None:
+        """PartsBasedDetector.setScaleNMS on every lane (no batch may be pending)"""
+        for d in self.dets:
+            d.setScaleNMS(dl)
 
     def setDepthPrune(self, fx: Optional[float], width: float = 0.0, tol: float = 0.3) -> None:
         """PartsBasedDetector.setDepthPrune on every lane (no batch may be pending)"""
